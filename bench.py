@@ -14,13 +14,15 @@ Workloads (BASELINE.json configs):
     default                --seeds-per-gpu 64   config 4 at N = 1 / weak scaling ("scaling": "weak")
     --total-seeds 64       config 4 as worded: 64 seeds in total over the N ranks ("scaling": "strong")
     --seeds-per-gpu 1      config 3: one instance x 8 line-search alphas
-The default run also times, after the timed region and under `extra`: config 3 (one instance), and the CONSTRAINED problem
-classes the headline's data never reach (its value function is identically zero: DESIGN.md 4d) -- `constrained_frame`
-(config 5's inputs: 3-row frame constraint at T-2, N(0,1)-seeded multiplier jacobians, mu = 1e3) and `constrained_config`
-(test/pinocchio_ddp.cpp's shape at the Talos size: e = 38 at every step) -- V != 0, K != 0, the line search halves.
+A plain run sets up, warms up, times --steps steps and prints the line; `--dump-outputs DIR` also writes what the last timed
+step computed (collect_outputs).  `--full` also times, after the timed region: the same steps without event brackets
+(`uninstrumented`), and under `extra` config 3 (one instance) and the CONSTRAINED problem classes the headline's data never
+reach (its value function is identically zero: DESIGN.md 4d) -- `constrained_frame` (config 5's inputs: 3-row frame constraint
+at T-2, N(0,1)-seeded multiplier jacobians, mu = 1e3) and `constrained_config` (test/pinocchio_ddp.cpp's shape at the Talos
+size: e = 38 at every step) -- V != 0, K != 0, the line search halves; and `cpu_baseline`.
 
 Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events on the library's own stream;
-`cpu_baseline` times the CPU oracle (oracle/, a port of the reference algorithm) on a bounded sample.
+`cpu_baseline` (--full) times the CPU oracle (oracle/, a port of the reference algorithm) on a bounded sample.
 """
 import argparse
 import json
@@ -67,8 +69,15 @@ def parse():
                     help="second-order tensors: 2 = second differences of f (problem.hpp:152-298, FD f_x, f_u: the north star); "
                          "1 = forward differences of the analytic jacobians (problem.hpp:67-150: what the reference's UR5 drivers use)")
     ap.add_argument("--n-alpha", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the config-3 (single instance) leg after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's own timed steps, also run the uninstrumented pass, the extra legs and the CPU "
+                         "baseline (off by default: a plain run only sets up, warms up and times --steps steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; a fixed, seeded sample of the "
+                         "larger arrays; under 50 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the uninstrumented pass and the extra legs after the timed region")
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="development: do not bracket the kernel launches with HIP events (no roofline / per-kernel times)")
     ap.add_argument("--cpu-sample-steps", type=int, default=0, help="horizon of the CPU sample (0 = auto: 50)")
@@ -118,6 +127,7 @@ class Iterator:
         t2 = time.perf_counter()
         rc, step, dcost = ctx.forward(self.mu, n_alpha=self.n_alpha)
         t3 = time.perf_counter()
+        self.last = {"reg": self.reg, "mu": self.mu, "restarts": restarts, "step": step, "dcost": dcost}
         self.reg = np.where(step >= 0.5, np.where(self.reg / 2 < 1e-5, 0.0, self.reg / 2), self.reg)   # ddp.hpp:819-824
         ctx.swap_traj()                                      # ddp.hpp:826
         if timed:
@@ -229,12 +239,14 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt[0])
     ctx.profile_enable(False)
+    # read back before anything after the timed region touches the context (the uninstrumented pass iterates on)
+    outputs = collect_outputs(ctx, it, picks) if a.dump_outputs else None
 
     # the same K iterations once more with no event brackets at all: the sweep then runs as one hipGraph launch (a profiled
     # sweep issues its 600 launches one by one), i.e. the product path as a host application drives it.  Reported beside the
     # instrumented numbers, never instead of them.
     plain_ms = None
-    if not a.no_kernel_events and not a.no_extra:
+    if a.full and not a.no_kernel_events and not a.no_extra:
         keep = dict(it.phase_ms)
         it.phase_ms = {k: 0.0 for k in keep}
         ctx.synchronize()
@@ -325,9 +337,11 @@ def main():
                                     "lin_first": ms_l1 / steps, "lin_second": ms_l2 / steps},
         }
     ctx.close()
+    if outputs is not None:
+        write_outputs(a.dump_outputs, outputs, f"_rank{rank}" if world > 1 else "")
     if rank == 0:
         extra = {}
-        if world == 1 and not a.no_extra and S != 1:
+        if world == 1 and a.full and not a.no_extra and S != 1:
             extra["config3_single_instance"] = single_instance_leg(capi, a, model, local_rank, T)
             if full and a.fd_mode == 2:
                 try:
@@ -342,7 +356,7 @@ def main():
                         extra[key] = {"error": repr(exc)}
         if extra:
             out["extra"] = extra
-        if not a.no_cpu_baseline and a.cpu_iterations > 0:
+        if a.full and not a.no_cpu_baseline and a.cpu_iterations > 0:
             out["cpu_baseline"] = cpu_baseline(a, model)
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -350,6 +364,35 @@ def main():
         if comm is not None:
             comm.close()
         dist.destroy_process_group()
+
+
+DUMP_CAP = 1 << 20      # elements kept of one dumped array (8 MB in float64): the six device arrays stay under 48 MB
+
+
+def collect_outputs(ctx, it, picks):
+    """What a caller of the timed path holds after its last step: the accepted trajectory (X, U after the swap) and its costs,
+    the feedback law of the backward sweep (FB_ORIGIN, FB_VAL = k, FB_JAC = K), the per-instance step, expected decrease,
+    reg, mu and LLT restarts, and the best-cost pick.  All float64; an array above DUMP_CAP elements is replaced by a fixed,
+    seeded sample of its flattened entries (the same positions for the same shape, so two builds compare entry for entry)."""
+    out = {}
+    for name in ("X", "U", "COSTS_OLD", "FB_ORIGIN", "FB_VAL", "FB_JAC"):
+        if ctx.seq_size(name):
+            out[name.lower()] = ctx.download(name)
+    for k, v in it.last.items():
+        out[k] = np.asarray(v, dtype=np.float64)
+    out["best_cost"] = np.array([picks[-1][0]], dtype=np.float64)
+    out["best_instance"] = np.array([picks[-1][1]], dtype=np.float64)
+    for k, v in out.items():
+        if v.size > DUMP_CAP:
+            idx = np.unique(np.random.default_rng(0xDD9000 + 8000).integers(0, v.size, size=DUMP_CAP))
+            out[k] = np.ascontiguousarray(v.reshape(-1)[idx])
+    return out
+
+
+def write_outputs(directory, outputs, suffix=""):
+    os.makedirs(directory, exist_ok=True)
+    for k, v in outputs.items():
+        np.save(os.path.join(directory, f"{k}{suffix}.npy"), v)
 
 
 def single_instance_leg(capi, a, model, device, T):

@@ -95,22 +95,73 @@ import json
 import sys
 
 GOLDEN_ACCESS = os.path.join(ROOT, "tests", "golden", "reference_member_access.json")
-REFERENCE = "/root/reference"
 
 
 def _access_table():
     return json.load(open(GOLDEN_ACCESS))
 
 
-def test_reference_member_access_table_is_current():
-    """tests/golden/reference_member_access.json (made by tools/reference_member_access.py) still matches the reference's
-    headers where they are readable (this container); on a box without /root/reference the committed table stands"""
-    if not os.path.isdir(os.path.join(REFERENCE, "include", "ddp")):
-        import pytest
-        pytest.skip("the reference's headers are not on this machine")
+def _rma():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import reference_member_access as rma
-    assert rma.table(REFERENCE) == _access_table()
+    return rma
+
+
+# headers of the shapes the tool meets in the reference (written for this test, not taken from it)
+_HEADERS = """\
+namespace ddp {
+/* struct hidden_t { private: int m_a; }; */
+struct plain_t {
+  int m_a;                          // public: a struct's default
+  struct inner_t {
+   private:
+    int m_b;                        // nested body: not plain_t's
+  };
+  char const* s = "private:";
+ private:
+  double m_b = 0;
+  void helper(int m_c) {}
+ public:
+  auto dynamics_aba() const -> int { return m_b; }
+ protected:
+  int m_c[3];
+};
+class model_t {
+  int m_model;                      // private: a class's default
+ public:
+  model_t();
+  int dt;
+};
+}
+"""
+
+
+def test_reference_member_access_tool_reads_access_specifiers():
+    """tools/reference_member_access.py, which makes tests/golden/reference_member_access.json from the reference's headers:
+    a struct's members default to public and a class's to private, `public:` / `private:` / `protected:` switch at the
+    body's own nesting depth only, and nested bodies, parameters, comments and strings hold no declarations of the struct"""
+    rma = _rma()
+    text = rma.strip(_HEADERS)
+    assert rma.access_of(text, "plain_t", "m_a") == ("public", 4)
+    assert rma.access_of(text, "plain_t", "m_b") == ("private", 11)
+    assert rma.access_of(text, "plain_t", "dynamics_aba") == ("public", 14)
+    assert rma.access_of(text, "plain_t", "m_c") == ("protected", 16)
+    assert rma.access_of(text, "inner_t", "m_b") == ("private", 7)
+    assert rma.access_of(text, "model_t", "m_model") == ("private", 19)
+    assert rma.access_of(text, "model_t", "dt") == ("public", 22)
+    assert rma.access_of(text, "hidden_t", "m_a") == (None, None)
+    assert rma.access_of(text, "plain_t", "m_missing") == (None, None)
+
+
+def test_reference_member_access_table_covers_every_used_member():
+    """the committed table holds one row per reference member the tool's USED list names (the check below reads nothing
+    else), in that order, each with an access specifier and a line.  After a change of the reference, regenerate it with
+    `tools/reference_member_access.py <reference checkout>`"""
+    rma = _rma()
+    table = _access_table()
+    assert [(r["header"], r["struct"], r["member"]) for r in table] == [("include/ddp/" + h, s, m) for h, s, m in rma.USED]
+    for r in table:
+        assert r["access"] in ("public", "private", "protected") and isinstance(r["line"], int) and r["line"] > 0, r
 
 
 def test_adapters_only_name_public_members_of_the_reference():

@@ -7,7 +7,7 @@ O=gpurun_out/final
 mkdir -p $O
 timeout -k 10 900 python -m pytest tests -q -m gpu > $O/gpu_tests.log 2>&1 || true
 tail -3 $O/gpu_tests.log
-timeout -k 10 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 timeout -k 10 300 python bench.py --fd-mode 1 --no-cpu-baseline --no-extra > $O/bench_fd1.json 2> $O/bench_fd1.err
 timeout -k 10 300 python bench.py --mode gn --no-cpu-baseline --no-extra > $O/bench_gn.json 2> $O/bench_gn.err
 ROOT=$(pwd)

@@ -6,8 +6,8 @@ in this image (Eigen / Boost / fmt are absent), so a member that is `private:` t
 goes unnoticed.  This script reads the reference's headers AS TEXT, walks every `struct` / `class` body, tracks
 `public:` / `private:` / `protected:` at the body's own nesting depth and records where each requested member is declared.
 Output: tests/golden/reference_member_access.json (data: header, struct, member, access, line -- no source text), which
-tests/test_adapters.py checks the adapters against; where /root/reference is present the test regenerates the table and
-compares.
+tests/test_adapters.py checks the adapters against; the same file tests this script on headers of its own and the table
+against USED.  Rerun it on a checkout of the reference when the reference changes.
 
 usage: tools/reference_member_access.py [reference_root] > tests/golden/reference_member_access.json
 """

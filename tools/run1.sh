@@ -6,7 +6,7 @@ timeout -k 10 900 python -m pytest tests -q -m gpu -x > $O/gpu_tests.log 2>&1
 rc=$?
 tail -15 $O/gpu_tests.log
 if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "tests timed out: stopping"; exit 1; fi
-timeout -k 10 600 python bench.py --no-cpu-baseline > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 600 python bench.py --full --no-cpu-baseline > $O/bench_default.json 2> $O/bench_default.err
 rc=$?
 echo "bench rc $rc"; tail -3 $O/bench_default.err
 python3 - <<'PY'
