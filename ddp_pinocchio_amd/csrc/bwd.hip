@@ -29,7 +29,7 @@ struct BwdParams {
   const double *eq_val, *eq_x, *eq_u, *eq_xx, *eq_ux, *eq_uu;
   const double *x, *mult_val, *mult_jac;
   double *fb_origin, *fb_val, *fb_jac, *vx_trace, *vxx_trace;
-  double *ws_V, *ws_Q, *ws_D, *reg, *mu;
+  double *ws_V, *ws_Q, *reg, *mu;
   int32_t* status;
   int64_t* restarts;
   const BwdJob* jobs;
@@ -38,8 +38,6 @@ struct BwdParams {
   int32_t half_mode;         // 1: symmetric tensors with two-entry upper halves (static mode-2 stencil); 2: this context's analytic mode-1
                              // tensors -- no symmetry, the upper half of every f_xx / f_ux column and all of f_uu exact zeros
   int32_t has_tensors;
-  int32_t b0;          // first instance of the group this launch sweeps
-  int32_t c_accumulate; // K3's epilogue adds its contraction to what is already in the Q workspace (bwd_v2.h) instead of storing it
   int32_t sym_tensors;  // f_xx is symmetric in its two input indices bit for bit (mode-2 / zero tensors of this context's own linearisation):
                         // K3 reads one of each pair of mirrored half-slabs (bwd_split.h, job kind 2)
 };
@@ -48,7 +46,7 @@ constexpr int BS = 256;
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 __global__ __launch_bounds__(BS) void bwd_init(BwdParams p) {
-  const int b = p.b0 + blockIdx.x;
+  const int b = blockIdx.x;
   const int s = p.status[b];
   if (s == 2) return;
   const int64_t n = p.d.n;
@@ -388,7 +386,7 @@ size_t gains_lds_bytes(const ddp_hip_ctx* ctx) {
   return (size_t)(ld * d.m + ld * (d.n + 1) + ld * d.n) * sizeof(double);
 }
 
-BwdParams make_params(ddp_hip_ctx* ctx) {
+BwdParams make_params(ddp_hip_ctx* ctx, const SweepPlan& plan) {
   BwdParams p{};
   p.d = ctx->d;
   p.ne = ctx->ne_d;
@@ -404,18 +402,13 @@ BwdParams make_params(ddp_hip_ctx* ctx) {
   p.mult_val = S(DDP_HIP_SEQ_MULT_VAL); p.mult_jac = S(DDP_HIP_SEQ_MULT_JAC);
   p.fb_origin = S(DDP_HIP_SEQ_FB_ORIGIN); p.fb_val = S(DDP_HIP_SEQ_FB_VAL); p.fb_jac = S(DDP_HIP_SEQ_FB_JAC);
   p.vx_trace = S(DDP_HIP_SEQ_VX_TRACE); p.vxx_trace = S(DDP_HIP_SEQ_VXX_TRACE);
-  p.ws_V = ctx->ws_V; p.ws_Q = ctx->ws_Q; p.ws_D = ctx->ws_D; p.reg = ctx->reg_d; p.mu = ctx->mu_d;
+  p.ws_V = ctx->ws_V; p.ws_Q = ctx->ws_Q; p.reg = ctx->reg_d; p.mu = ctx->mu_d;
   p.status = ctx->status_d; p.restarts = ctx->restarts_d;
-  p.sym_tensors = (ctx->tensors_sym && ctx->jobs_sym_d && getenv("DDP_HIP_K3_NO_SYM") == nullptr) ? 1 : 0;
-  p.jobs = p.sym_tensors ? ctx->jobs_sym_d : ctx->jobs_d;
-  // K3h needs both structural facts: symmetry and the zero configuration rows (the static stencil's own tensors)
-  const bool half = p.sym_tensors && ctx->tensor_tops_zero && ctx->tensor_tops_sparse && ctx->jobs_half_d && getenv("DDP_HIP_K3_NO_HALF") == nullptr;
-  // ... or the structure the analytic mode-1 pass leaves (lin_analytic.hip): q+ = q + dt v has constant jacobian rows and M^-1 does
-  // not depend on u, so the upper halves and f_uu are zeros it wrote itself
-  const bool half_m1 = !half && ctx->fuu_zero && ctx->model_h.fd_mode == 1 && ctx->jobs_half_d && getenv("DDP_HIP_K3_NO_HALF") == nullptr;
-  p.jobs_half = (half || half_m1) ? ctx->jobs_half_d : nullptr;
-  p.njobs_half = (half || half_m1) ? ctx->njobs_half : 0;
-  p.half_mode = half ? 1 : (half_m1 ? 2 : 0);
+  p.sym_tensors = plan.sym ? 1 : 0;
+  p.jobs = plan.sym ? ctx->jobs_sym_d : ctx->jobs_d;
+  p.jobs_half = plan.half_mode ? ctx->jobs_half_d : nullptr;
+  p.njobs_half = plan.half_mode ? ctx->njobs_half : 0;
+  p.half_mode = plan.half_mode;
   p.has_tensors = (ctx->flags & DDP_HIP_FLAG_NO_TENSORS) ? 0 : 1;
   return p;
 }
@@ -436,127 +429,38 @@ int launch_sweep(ddp_hip_ctx* ctx, const BwdParams& p, size_t lds_a, size_t lds_
   return DDP_HIP_OK;
 }
 
-// split path (compile-time shapes): K3 bwd_contract streams the tensors, K4 bwd_riccati does the rest.
-// The recursion chains K4(t+1) -> K3(t) -> K4(t) per instance, and K4 is a latency chain on one workgroup per instance
-// (a whole CU's LDS each): run back to back on one stream, K3 leaves HBM idle for as long as K4 takes.  The batch is
-// therefore swept in groups on their own streams, so that K3 of one group streams while K4 of the others factorises.
+// three-kernel step (bwd_v2.h): K5 dense terms on 8 workgroups per instance -> K3 tensor stream (+ P) -> K4' lean Riccati
 template <int NC, int MC>
-int launch_sweep_split(ddp_hip_ctx* ctx, const BwdParams& p0) {
+int enqueue_sweep_v2(ddp_hip_ctx* ctx, const BwdParams& p) {
   const Dims& d = ctx->d;
   const int cn_max = ctx->cbx > ctx->cbu ? ctx->cbx : ctx->cbu;
   const size_t lds_c = sizeof(double) * (size_t)(NC + (NC + MC) * cn_max + 2 * (NC / 2 + 1) * MC);
   const size_t lds_h = sizeof(double) * (size_t)(NC + 3 * NC + 2 * (MC / 2 + 1) * NC);
-  const size_t lds_r = sizeof(double) * (size_t)(2 * NC * (NC + MC));
-  const int G = ctx->bwd_groups;
-  const int64_t per = (d.batch + G - 1) / G;
-  if (G > 1) {
-    HIP_TRY(hipEventRecord(ctx->bwd_ev_start, ctx->stream));
-    for (int g = 0; g < G; ++g) HIP_TRY(hipStreamWaitEvent(ctx->bwd_stream[g], ctx->bwd_ev_start, 0));
-  }
-  BwdParams pg[8];
-  unsigned nb[8];
-  hipStream_t st[8];
-  for (int g = 0; g < G; ++g) {
-    pg[g] = p0;
-    pg[g].b0 = (int32_t)(g * per);
-    const int64_t n_ = d.batch - g * per < per ? d.batch - g * per : per;
-    nb[g] = n_ > 0 ? (unsigned)n_ : 0u;
-    st[g] = G > 1 ? ctx->bwd_stream[g] : ctx->stream;
-    if (!nb[g]) continue;
-    hipLaunchKernelGGL(bwd_init, dim3(nb[g]), dim3(BS), 0, st[g], pg[g]);
-    hipLaunchKernelGGL((bwd_dense0<NC, MC>), dim3(nb[g]), dim3(BSR), lds_r, st[g], pg[g]);
-  }
-  for (int64_t t = d.T - 1; t >= 0; --t) {
-    for (int g = 0; g < G; ++g) {
-      if (!nb[g]) continue;
-      if (p0.has_tensors) {
-        prof_begin(ctx, DDP_HIP_K_BWD_ASSEMBLE, st[g]);
-        if (pg[g].jobs_half) hipLaunchKernelGGL((bwd_contract_half<NC, MC>), dim3((unsigned)pg[g].njobs_half, nb[g]), dim3(BSF), lds_h, st[g], pg[g], t);
-        else hipLaunchKernelGGL((bwd_contract<NC, MC>), dim3((unsigned)ctx->njobs, nb[g]), dim3(BSF), lds_c, st[g], pg[g], t);
-        prof_end(ctx, DDP_HIP_K_BWD_ASSEMBLE, st[g]);
-      }
-      prof_begin(ctx, DDP_HIP_K_BWD_GAINS, st[g]);
-      hipLaunchKernelGGL((bwd_riccati<NC, MC>), dim3(nb[g]), dim3(BSR), lds_r, st[g], pg[g], t);
-      prof_end(ctx, DDP_HIP_K_BWD_GAINS, st[g]);
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  if (G > 1)
-    for (int g = 0; g < G; ++g) {
-      HIP_TRY(hipEventRecord(ctx->bwd_ev_done[g], ctx->bwd_stream[g]));
-      HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->bwd_ev_done[g], 0));
-    }
-  return DDP_HIP_OK;
-}
-
-// three-kernel step (bwd_v2.h): K5 dense terms on 8 workgroups per instance -> K3 tensor stream (+ P) -> K4' lean Riccati
-template <int NC, int MC>
-int enqueue_sweep_v2(ddp_hip_ctx* ctx, const BwdParams& p0) {
-  const Dims& d = ctx->d;
-  const int cn_max = ctx->cbx > ctx->cbu ? ctx->cbx : ctx->cbu;
-  size_t lds_c = sizeof(double) * (size_t)(NC + (NC + MC) * cn_max + 2 * (NC / 2 + 1) * MC);
-  if (ctx->bwd_k3_lds_pad > lds_c) lds_c = ctx->bwd_k3_lds_pad;
-  const size_t lds_h = sizeof(double) * (size_t)(NC + 3 * NC + 2 * (MC / 2 + 1) * NC);   // development: limits K3 to one workgroup per CU (room for K4' / K5 of another group)
   const size_t lds_5 = sizeof(double) * (size_t)(NC * NC + NC * (NC + MC) + NC + d.emax);
   const unsigned nblk5 = (unsigned)((NC + MC + CB5 - 1) / CB5);
-  const int G = ctx->bwd_groups;
-  // K5 (dense terms) and K3 (tensor stream) of a step both depend on K4' of the step before and on nothing else: with tensors,
-  // K5 goes to a side stream and K3 keeps its contracted blocks in a workspace of its own; K4' waits for both and forms P + C
-  const bool fork = ctx->bwd_fork && G == 1 && p0.has_tensors;
-  const int64_t per = (d.batch + G - 1) / G;
-  if (G > 1) {
-    HIP_TRY(hipEventRecord(ctx->bwd_ev_start, ctx->stream));
-    for (int g = 0; g < G; ++g) HIP_TRY(hipStreamWaitEvent(ctx->bwd_stream[g], ctx->bwd_ev_start, 0));
-  }
-  BwdParams pg[8];
-  unsigned nb[8];
-  hipStream_t st[8];
-  for (int g = 0; g < G; ++g) {
-    pg[g] = p0;
-    pg[g].b0 = (int32_t)(g * per);
-    pg[g].c_accumulate = fork ? 2 : 1;
-    const int64_t n_ = d.batch - g * per < per ? d.batch - g * per : per;
-    nb[g] = n_ > 0 ? (unsigned)n_ : 0u;
-    st[g] = G > 1 ? ctx->bwd_stream[g] : ctx->stream;
-    if (nb[g]) hipLaunchKernelGGL(bwd_init, dim3(nb[g]), dim3(BS), 0, st[g], pg[g]);
-  }
+  const unsigned B = (unsigned)d.batch;
+  hipLaunchKernelGGL(bwd_init, dim3(B), dim3(BS), 0, ctx->stream, p);
   for (int64_t t = d.T - 1; t >= 0; --t) {
-    for (int g = 0; g < G; ++g) {
-      if (!nb[g]) continue;
-      if (fork) {
-        HIP_TRY(hipEventRecord(ctx->bwd_ev_fork, st[g]));
-        HIP_TRY(hipStreamWaitEvent(ctx->bwd_side, ctx->bwd_ev_fork, 0));
-        hipLaunchKernelGGL((bwd_dense2<NC, MC>), dim3(nblk5, nb[g]), dim3(BS5), lds_5, ctx->bwd_side, pg[g], t);
-        HIP_TRY(hipEventRecord(ctx->bwd_ev_join, ctx->bwd_side));
-      } else {
-        prof_begin(ctx, DDP_HIP_K_BWD_GAINS, st[g]);
-        hipLaunchKernelGGL((bwd_dense2<NC, MC>), dim3(nblk5, nb[g]), dim3(BS5), lds_5, st[g], pg[g], t);
-        prof_end(ctx, DDP_HIP_K_BWD_GAINS, st[g]);
-      }
-      if (p0.has_tensors) {
-        prof_begin(ctx, DDP_HIP_K_BWD_ASSEMBLE, st[g]);
-        if (pg[g].jobs_half) hipLaunchKernelGGL((bwd_contract_half<NC, MC>), dim3((unsigned)pg[g].njobs_half, nb[g]), dim3(BSF), lds_h, st[g], pg[g], t);
-        else hipLaunchKernelGGL((bwd_contract<NC, MC>), dim3((unsigned)ctx->njobs, nb[g]), dim3(BSF), lds_c, st[g], pg[g], t);
-        prof_end(ctx, DDP_HIP_K_BWD_ASSEMBLE, st[g]);
-      }
-      if (fork) HIP_TRY(hipStreamWaitEvent(st[g], ctx->bwd_ev_join, 0));
-      prof_begin(ctx, DDP_HIP_K_BWD_GAINS, st[g]);
-      hipLaunchKernelGGL((bwd_gains2<NC, MC>), dim3(nb[g]), dim3(BS4), 0, st[g], pg[g], t);
-      prof_end(ctx, DDP_HIP_K_BWD_GAINS, st[g]);
+    prof_begin(ctx, DDP_HIP_K_BWD_GAINS);
+    hipLaunchKernelGGL((bwd_dense2<NC, MC>), dim3(nblk5, B), dim3(BS5), lds_5, ctx->stream, p, t);
+    prof_end(ctx, DDP_HIP_K_BWD_GAINS);
+    if (p.has_tensors) {
+      prof_begin(ctx, DDP_HIP_K_BWD_ASSEMBLE);
+      if (p.jobs_half) hipLaunchKernelGGL((bwd_contract_half<NC, MC>), dim3((unsigned)p.njobs_half, B), dim3(BSF), lds_h, ctx->stream, p, t);
+      else hipLaunchKernelGGL((bwd_contract<NC, MC>), dim3((unsigned)ctx->njobs, B), dim3(BSF), lds_c, ctx->stream, p, t);
+      prof_end(ctx, DDP_HIP_K_BWD_ASSEMBLE);
     }
+    prof_begin(ctx, DDP_HIP_K_BWD_GAINS);
+    hipLaunchKernelGGL((bwd_gains2<NC, MC>), dim3(B), dim3(BS4), 0, ctx->stream, p, t);
+    prof_end(ctx, DDP_HIP_K_BWD_GAINS);
   }
   HIP_TRY(hipGetLastError());
-  if (G > 1)
-    for (int g = 0; g < G; ++g) {
-      HIP_TRY(hipEventRecord(ctx->bwd_ev_done[g], ctx->bwd_stream[g]));
-      HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->bwd_ev_done[g], 0));
-    }
   return DDP_HIP_OK;
 }
 
-// The same enqueue, captured once into a hipGraph per state of the kernel arguments and replayed: the fork / join of
-// the group streams becomes graph edges, the 600 launches per group one submission.  Profiled sweeps (HIP events around
-// kernels) and DDP_HIP_BWD_NO_GRAPH=1 take the direct path.
+// The same enqueue, captured once into a hipGraph per state of the kernel arguments and replayed: the 600 launches of a
+// sweep become one submission of a straight chain.  Profiled sweeps (HIP events around kernels) and DDP_HIP_BWD_NO_GRAPH=1
+// take the direct path.
 template <int NC, int MC>
 int build_sweep_graph(ddp_hip_ctx* ctx, const BwdParams& p0, uint64_t key_misc, ddp_hip_ctx::BwdGraph** out) {
   ddp_hip_ctx::BwdGraph* slot = &ctx->bwd_graph[ctx->bwd_graph_next];
@@ -580,7 +484,7 @@ int launch_sweep_v2(ddp_hip_ctx* ctx, const BwdParams& p0) {
   const uint32_t bwd_mask = (2u << DDP_HIP_K_BWD_ASSEMBLE) | (2u << DDP_HIP_K_BWD_GAINS);
   // profiled sweeps take the direct path: events recorded by a graph's event-record nodes cannot be read back with
   // hipEventElapsedTime on this ROCm (hipErrorInvalidHandle -- tried)
-  if (!ctx->bwd_use_graph || (ctx->profile_mask & bwd_mask)) return enqueue_sweep_v2<NC, MC>(ctx, p0);
+  if (ctx->sw.bwd_no_graph || (ctx->profile_mask & bwd_mask)) return enqueue_sweep_v2<NC, MC>(ctx, p0);
   const uint64_t key_misc = (uint64_t)p0.has_tensors | ((uint64_t)(p0.vx_trace != nullptr) << 1) | ((uint64_t)p0.sym_tensors << 2) | ((uint64_t)(p0.jobs_half != nullptr) << 3) | ((uint64_t)p0.half_mode << 4);
   auto find = [&](const void* key_x) -> ddp_hip_ctx::BwdGraph* {
     for (auto& g : ctx->bwd_graph)
@@ -610,12 +514,28 @@ int launch_sweep_v2(ddp_hip_ctx* ctx, const BwdParams& p0) {
 
 }  // namespace
 
+SweepPlan sweep_plan(const ddp_hip_ctx* ctx) {
+  const Dims& d = ctx->d;
+  const DevSwitches& sw = ctx->sw;
+  SweepPlan s{};
+  // (K5 stages the multiplier jacobians over its V / F region: up to 52 constraint rows per step fit)
+  s.fast = d.n == 76 && d.m == 38 && d.emax <= 52 && !sw.generic_bwd;
+  s.sym_ok = s.fast && ctx->jobs_sym_d && !sw.k3_no_sym;
+  s.sym = s.sym_ok && ctx->tensors_sym;
+  const bool half_ok = s.fast && ctx->jobs_half_d && !sw.k3_no_half;
+  // K3h needs both structural facts: symmetry and the zero configuration rows (the static stencil's own tensors) ...
+  if (half_ok && s.sym && ctx->tensor_tops_zero && ctx->tensor_tops_sparse) s.half_mode = 1;
+  // ... or the structure the analytic mode-1 pass leaves (lin_analytic.hip): q+ = q + dt v has constant jacobian rows and M^-1 does
+  // not depend on u, so the upper halves and f_uu are zeros it wrote itself
+  else if (half_ok && ctx->fuu_zero && ctx->model_h.fd_mode == 1) s.half_mode = 2;
+  return s;
+}
+
 int bwd_setup(ddp_hip_ctx* ctx) {
   const Dims& d = ctx->d;
   const int64_t n = d.n, m = d.m, B = d.batch;
   HIP_TRY(hipMalloc(&ctx->ws_V, sizeof(double) * (size_t)(B * (n + n * n))));
   HIP_TRY(hipMalloc(&ctx->ws_Q, sizeof(double) * (size_t)(B * (n + m + n * n + m * n + m * m))));
-  HIP_TRY(hipMalloc(&ctx->ws_D, sizeof(double) * (size_t)(B * (n * n + m * n + m * m))));
   HIP_TRY(hipMalloc(&ctx->reg_d, sizeof(double) * (size_t)B));
   HIP_TRY(hipMalloc(&ctx->mu_d, sizeof(double) * (size_t)B));
   HIP_TRY(hipMalloc(&ctx->status_d, sizeof(int32_t) * (size_t)B));
@@ -634,49 +554,18 @@ int bwd_setup(ddp_hip_ctx* ctx) {
   // (3 units of f_uu): 89 equal jobs of 69 KB per instance.  Measured at 64 instances: 66 us per launch (6.1 TB/s) against 74 us
   // (5.5 TB/s) for the 31 jobs of 3 / 9 columns the rule above picks.
   if (n == 76 && m == 38) { cbx = 1; cbu = 3; }
-  if (const char* ev = getenv("DDP_HIP_BWD_CBX")) { int v = atoi(ev); if (v >= 1 && v <= 8) cbx = v; }    // tuning knobs
-  if (const char* ev = getenv("DDP_HIP_BWD_CBU")) { int v = atoi(ev); if (v >= 1 && v <= 16) cbu = v; }
+  if (ctx->sw.bwd_cbx) cbx = ctx->sw.bwd_cbx;    // tuning knobs
+  if (ctx->sw.bwd_cbu) cbu = ctx->sw.bwd_cbu;
   ctx->cbx = (int32_t)cbx; ctx->cbu = (int32_t)cbu;
   std::vector<BwdJob> jobs;
   for (int64_t c = 0; c < n; c += cbx) jobs.push_back(BwdJob{0, (int32_t)c, (int32_t)((n - c) < cbx ? (n - c) : cbx), 0});
   for (int64_t c = 0; c < m; c += cbu) jobs.push_back(BwdJob{1, (int32_t)c, (int32_t)((m - c) < cbu ? (m - c) : cbu), 0});
   ctx->njobs = (int32_t)jobs.size();
   if (n == 76 && m == 38) {
-    // K4 needs more than the default 64 KB of dynamic LDS.  The attribute is per device: it is set here, with the
+    // K5 needs more than the default 64 KB of dynamic LDS.  The attribute is per device: it is set here, with the
     // context's device current, by every context (not behind a process-wide flag)
-    const size_t lds_r = sizeof(double) * (size_t)(2 * 76 * (76 + 38));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_riccati<76, 38>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_dense0<76, 38>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r));
     const size_t lds_5 = sizeof(double) * (size_t)(76 * 76 + 76 * (76 + 38) + 76 + d.emax);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_dense2<76, 38>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_5));
-  }
-  if (n == 76 && m == 38) {
-    // groups of the sweep on their own streams (tuning knob DDP_HIP_BWD_GROUPS).  Default 1: measured at 64 instances, two
-    // and four groups do not overlap K3 with the other groups' K4' / K5 (K3's workgroups hold every VGPR of the CUs they
-    // run on; 28.7 / 29.7 ms against 30.7 ms)
-    int64_t G = 1;
-    if (const char* ev = getenv("DDP_HIP_BWD_GROUPS")) { const int v = atoi(ev); if (v >= 1 && v <= 8) G = v; }
-    ctx->bwd_use_graph = getenv("DDP_HIP_BWD_NO_GRAPH") ? 0 : 1;
-    if (const char* ev = getenv("DDP_HIP_K3_LDS")) {
-      ctx->bwd_k3_lds_pad = (size_t)atoi(ev) * 1024;
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_contract<76, 38>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    if (G > B) G = B;
-    ctx->bwd_groups = (int32_t)G;
-    // DDP_HIP_BWD_FORK=1 (development): K5 on a side stream beside K3.  Measured at 64 seeds: 29.2 ms against 26.6 ms for the
-    // serial chain -- with a K5 workgroup on every CU (116 KB of LDS, a quarter of the wave slots) K3 drops from 74 to 80 us
-    // per launch and the fork / join edges cost more than the 17 us of K5 they hide.  Off by default.
-    ctx->bwd_fork = getenv("DDP_HIP_BWD_FORK") ? 1 : 0;
-    HIP_TRY(hipStreamCreateWithFlags(&ctx->bwd_side, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&ctx->bwd_ev_fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&ctx->bwd_ev_join, hipEventDisableTiming));
-    if (G > 1) {
-      HIP_TRY(hipEventCreateWithFlags(&ctx->bwd_ev_start, hipEventDisableTiming));
-      for (int g = 0; g < G; ++g) {
-        HIP_TRY(hipStreamCreateWithFlags(&ctx->bwd_stream[g], hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&ctx->bwd_ev_done[g], hipEventDisableTiming));
-      }
-    }
   }
   HIP_TRY(hipMalloc(&ctx->jobs_d, sizeof(BwdJob) * jobs.size()));
   HIP_TRY(hipMemcpy(ctx->jobs_d, jobs.data(), sizeof(BwdJob) * jobs.size(), hipMemcpyHostToDevice));
@@ -702,17 +591,8 @@ void bwd_teardown(ddp_hip_ctx* ctx) {
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (g.graph) (void)hipGraphDestroy(g.graph);
   }
-  for (int g = 0; g < 8; ++g) {
-    if (ctx->bwd_stream[g]) { (void)hipStreamSynchronize(ctx->bwd_stream[g]); (void)hipStreamDestroy(ctx->bwd_stream[g]); }
-    if (ctx->bwd_ev_done[g]) (void)hipEventDestroy(ctx->bwd_ev_done[g]);
-  }
-  if (ctx->bwd_ev_start) (void)hipEventDestroy(ctx->bwd_ev_start);
-  if (ctx->bwd_side) { (void)hipStreamSynchronize(ctx->bwd_side); (void)hipStreamDestroy(ctx->bwd_side); }
-  if (ctx->bwd_ev_fork) (void)hipEventDestroy(ctx->bwd_ev_fork);
-  if (ctx->bwd_ev_join) (void)hipEventDestroy(ctx->bwd_ev_join);
   if (ctx->ws_V) (void)hipFree(ctx->ws_V);
   if (ctx->ws_Q) (void)hipFree(ctx->ws_Q);
-  if (ctx->ws_D) (void)hipFree(ctx->ws_D);
   if (ctx->reg_d) (void)hipFree(ctx->reg_d);
   if (ctx->mu_d) (void)hipFree(ctx->mu_d);
   if (ctx->status_d) (void)hipFree(ctx->status_d);
@@ -727,13 +607,12 @@ extern "C" int ddp_hip_backward(ddp_hip_ctx* ctx, double* reg_io, double* mu_io,
   const Dims& d = ctx->d;
   const int64_t B = d.batch;
   HIP_TRY(hipSetDevice(ctx->device));
-  BwdParams p = make_params(ctx);
+  const SweepPlan plan = sweep_plan(ctx);
+  BwdParams p = make_params(ctx, plan);
   if (p.has_tensors && (!p.fxx || !p.fux || !p.fuu)) return DDP_HIP_E_UNSUPPORTED;
-  {
-    // the static stencil leaves the f_xx block out that the symmetric sweep never reads: any other sweep needs it
-    const bool fast = d.n == 76 && d.m == 38 && d.emax <= 52 && getenv("DDP_HIP_GENERIC_BWD") == nullptr;
-    if (p.has_tensors && ctx->fxx_mirror_pending && !(fast && p.sym_tensors)) { const int rc_ = lin_materialize_fxx(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
-  }
+  // the static stencil leaves the f_xx block out that the symmetric sweep never reads: any other sweep needs it (the tensors
+  // may have changed since the linearisation: upload / device_ptr)
+  if (p.has_tensors && ctx->fxx_mirror_pending && !plan.sym) { const int rc_ = lin_materialize_fxx(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
 
   HIP_TRY(hipMemcpyAsync(ctx->reg_d, reg_io, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(ctx->mu_d, mu_io, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, ctx->stream));
@@ -750,11 +629,8 @@ extern "C" int ddp_hip_backward(ddp_hip_ctx* ctx, double* reg_io, double* mu_io,
   bool any_restart = false;
   int rc = DDP_HIP_OK;
   for (int64_t attempt = 0;; ++attempt) {
-    // the Talos-like shape runs the split K3 / K4 kernels; every other shape (and DDP_HIP_GENERIC_BWD=1, kept for
-    // cross-checking the two implementations against each other) the run-time-shaped pair
-    const bool generic = getenv("DDP_HIP_GENERIC_BWD") != nullptr;
-    // (K5 stages the multiplier jacobians over its V / F region: up to 52 constraint rows per step fit)
-    if (d.n == 76 && d.m == 38 && d.emax <= 52 && !generic) rc = getenv("DDP_HIP_BWD_V1") ? launch_sweep_split<76, 38>(ctx, p) : launch_sweep_v2<76, 38>(ctx, p);
+    // the Talos-like shape runs K5 / K3 / K4' (sweep_plan); every other shape the run-time-shaped pair
+    if (plan.fast) rc = launch_sweep_v2<76, 38>(ctx, p);
     else if (d.n == 12 && d.m == 6) rc = launch_sweep<12, 6>(ctx, p, lds_a, lds_g);
     else rc = launch_sweep<0, 0>(ctx, p, lds_a, lds_g);
     if (rc != DDP_HIP_OK) return rc;

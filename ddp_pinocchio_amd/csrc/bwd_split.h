@@ -1,16 +1,13 @@
-// bwd_split.h -- the backward step as the two kernels of SURVEY.md's kernel map (included by bwd.hip):
+// bwd_split.h -- the tensor stream of the Talos-shape backward step (included by bwd.hip before bwd_v2.h):
 //
 //   K3  bwd_contract<N, M>   grid (jobs, batch).  Pure HBM stream: C(j,k) = sum_i V_x,i T(i,j,k) for the three
 //       second-order tensors of one timestep (tensor.hpp:179-198 as called at ddp_bwd.ipp:75,81,87).
 //       Reads every tensor byte exactly once with 16-byte coalesced loads, three 69 KB units per workgroup
 //       always in flight; 0.25 flop/byte.
-//   K4  bwd_riccati<N, M>    grid (batch).  Everything else of the step, LDS / register resident:
-//       Q = l + f^T V_xx f + multiplier terms + C (ddp_bwd.ipp:61-87, in the reference's order of terms),
-//       LLT (:104-105), gains (:134-136), V update (:142-146), and -- while the new V_xx is still in LDS --
-//       the dense product D = [f_x f_u]^T V_xx [f_x f_u] of the NEXT step to be processed (t-1).
+//   K3h bwd_contract_half<N, M>  the same contraction for tensors with known structure: reads only what is not known
+//       in advance (below).
+//   Both add C to the Q workspace, which already holds every other term of Q (K5, bwd_v2.h).
 #pragma once
-
-constexpr int BSR = 512;   // workgroup size of K4
 
 template <int N, int M>
 __global__ __launch_bounds__(BSF, BWD_WAVES_PER_SIMD) void bwd_contract(BwdParams p, int64_t t) {
@@ -24,7 +21,6 @@ __global__ __launch_bounds__(BSF, BWD_WAVES_PER_SIMD) void bwd_contract(BwdParam
       b = xcd + 8 * (k / njobs);
       jb = k % njobs;
     } else { b = blockIdx.y; jb = blockIdx.x; }
-    b += p.b0;
   }
   if (p.status[b] != 0) return;
   const BwdJob job = p.jobs[jb];
@@ -43,10 +39,7 @@ __global__ __launch_bounds__(BSF, BWD_WAVES_PER_SIMD) void bwd_contract(BwdParam
   const int64_t bt = (int64_t)b * T + t;
 
   const double* Vx = p.ws_V + (int64_t)b * (n + n * n);
-  // c_accumulate 0: store into the Q workspace (round 1's K4 adds the rest); 1: add to what K5 left there; 2: store into a
-  // workspace of its own (K5 runs beside this kernel, K4' forms P + C)
-  double* C = p.c_accumulate == 2 ? p.ws_D + (int64_t)b * (n * n + m * n + m * m)
-                                  : p.ws_Q + (int64_t)b * (n + m + n * n + m * n + m * m) + n + m;
+  double* C = p.ws_Q + (int64_t)b * (n + m + n * n + m * n + m * m) + n + m;   // Q_xx | Q_ux | Q_uu, holding what K5 left
   double* Cxx = C;
   double* Cux = Cxx + n * n;
   double* Cuu = Cux + m * n;
@@ -123,16 +116,16 @@ __global__ __launch_bounds__(BSF, BWD_WAVES_PER_SIMD) void bwd_contract(BwdParam
   for (int idx = tid; idx < rows * cn; idx += BSF) {
     const int r = idx % rows, c = idx / rows;
     const int col = c0 + c;
-    // c_accumulate: the workspace already holds every other term of Q (K5, bwd_v2.h); the tensor term comes last in the
-    // reference as well (ddp_bwd.ipp:75,81,87)
+    // the workspace already holds every other term of Q (K5, bwd_v2.h); the tensor term comes last in the reference as well
+    // (ddp_bwd.ipp:75,81,87)
     if (kind == 2 && r < M) continue;                // (the half-slab this job kind leaves out)
     const bool square = kind == 1 || r < n;          // an entry of C_xx / C_uu (f_ux is not symmetric)
     if (sym && square && r < col) continue;          // the mirror image: written by the job of column r
     double* dst = kind != 1 ? (r < n ? Cxx + r + col * n : Cux + (r - n) + col * m) : Cuu + r + col * m;
-    *dst = p.c_accumulate == 1 ? *dst + s_out[idx] : s_out[idx];
+    *dst = *dst + s_out[idx];
     if (sym && square && r > col) {
       double* dm = kind != 1 ? Cxx + col + r * n : Cuu + col + r * m;   // C(col, r) = C(r, col)
-      *dm = p.c_accumulate == 1 ? *dm + s_out[idx] : s_out[idx];
+      *dm = *dm + s_out[idx];
     }
   }
 }
@@ -169,7 +162,6 @@ __global__ __launch_bounds__(BSF, BWD_WAVES_PER_SIMD) void bwd_contract_half(Bwd
       b = xcd + 8 * (k / njobs);
       jb = k % njobs;
     } else { b = blockIdx.y; jb = blockIdx.x; }
-    b += p.b0;
   }
   if (p.status[b] != 0) return;
   const BwdJob job = p.jobs_half[jb];
@@ -181,8 +173,7 @@ __global__ __launch_bounds__(BSF, BWD_WAVES_PER_SIMD) void bwd_contract_half(Bwd
   const bool m1 = p.half_mode == 2;            // analytic mode-1 tensors: every column read, no upper-half entries, f_uu all zeros
   const int64_t bt = (int64_t)b * T + t;
   const double* Vx = p.ws_V + (int64_t)b * (n + n * n);
-  double* C = p.c_accumulate == 2 ? p.ws_D + (int64_t)b * (n * n + m * n + m * m)
-                                  : p.ws_Q + (int64_t)b * (n + m + n * n + m * n + m * m) + n + m;
+  double* C = p.ws_Q + (int64_t)b * (n + m + n * n + m * n + m * m) + n + m;   // Q_xx | Q_ux | Q_uu, holding what K5 left
   double* Cxx = C;
   double* Cux = Cxx + n * n;
   double* Cuu = Cux + m * n;
@@ -234,8 +225,8 @@ __global__ __launch_bounds__(BSF, BWD_WAVES_PER_SIMD) void bwd_contract_half(Bwd
   if (U > 0) issue(0, buf0, top0);
   if (U > 1) issue(1, buf1, top1);
   if (U > 2) issue(2, buf2, top2);
-  // this lane's output entry (U * N <= BSF: one per lane) and what the workspace holds there (c_accumulate: the dense terms K5
-  // left), requested now so that the read-modify-write at the end does not wait for a round trip of its own
+  // this lane's output entry (U * N <= BSF: one per lane) and what the workspace holds there (the dense terms K5 left),
+  // requested now so that the read-modify-write at the end does not wait for a round trip of its own
   double* dst = nullptr;
   double* dm = nullptr;
   double old_d = 0.0, old_m = 0.0;
@@ -248,7 +239,8 @@ __global__ __launch_bounds__(BSF, BWD_WAVES_PER_SIMD) void bwd_contract_half(Bwd
         if (u < 2) { dst = Cxx + j + slab * n; if (j > slab && !m1) dm = Cxx + slab + j * n; }
         else dst = Cux + j + slab * m;
       } else { dst = Cuu + j + slab * m; if (j > slab && !m1) dm = Cuu + slab + j * m; }
-      if (p.c_accumulate == 1) { old_d = *dst; if (dm) old_m = *dm; }
+      old_d = *dst;
+      if (dm) old_m = *dm;
     }
   }
   for (int i = tid; i < n; i += BSF) s_v[i] = Vx[i];
@@ -303,372 +295,7 @@ __global__ __launch_bounds__(BSF, BWD_WAVES_PER_SIMD) void bwd_contract_half(Bwd
   __syncthreads();
   if (dst) {
     const double v = s_out[tid];
-    *dst = old_d + v;                                      // (old_d = 0 unless c_accumulate == 1: 0 + v == v)
+    *dst = old_d + v;
     if (dm) *dm = old_m + v;
   }
-}
-
-// D = [f_x f_u]^T V_xx [f_x f_u] (blocks xx, ux, uu) for timestep td, with V_xx already in s_VW[0 .. N*N).
-// LDS: s_VW (N*(N+M) doubles: V_xx, then W = V_xx F), s_F (N*(N+M) doubles).  All BSR lanes take part.
-// This is the one genuinely dense product of the step (3.3 MFLOP per instance and step); it runs on the FP64 matrix
-// cores: v_mfma_f64_16x16x4_f64, one 16 x 16 output tile per wave at a time, operands read from LDS.
-// Lane l feeds A[row = l & 15][k = l >> 4] and B[k = l >> 4][col = l & 15]; result register r of lane l is
-// D[row = (l >> 4) + 4 r][col = l & 15].  Rows / columns beyond the matrix are fed zeros.
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-// ... and, while F = [f_x | f_u] of step td is in LDS, the dense part of that step's Q_x | Q_u: g = F^T V_x
-// (ddp_bwd.ipp:62,67), left in the Q_x | Q_u slots of the instance's workspace for the K4 launch of step td
-template <int N, int M>
-__device__ __forceinline__ void dense_product(const BwdParams& p, int b, int64_t td, double* s_VW, double* s_F, const double* s_vxn) {
-  constexpr int n = N, m = M, NM = N + M;
-  const int tid = threadIdx.x;
-  const int64_t bt = (int64_t)b * p.d.T + td;
-  const double* fx = p.fx + bt * n * n;
-  const double* fu = p.fu + bt * n * m;
-  double* D = p.ws_D + (int64_t)b * (n * n + m * n + m * m);
-  double* Dxx = D;
-  double* Dux = Dxx + n * n;
-  double* Duu = Dux + m * n;
-  // F = [f_x | f_u], column-major, leading dimension N
-  {
-    const f64x2* a = reinterpret_cast<const f64x2*>(fx);
-    const f64x2* c = reinterpret_cast<const f64x2*>(fu);
-    f64x2* d = reinterpret_cast<f64x2*>(s_F);
-    for (int i = tid; i < n * n / 2; i += BSR) d[i] = a[i];
-    for (int i = tid; i < n * m / 2; i += BSR) d[n * n / 2 + i] = c[i];
-  }
-  __syncthreads();
-  const int wave = tid >> 6, lane = tid & 63;
-  const int l15 = lane & 15, l4 = lane >> 4;
-  constexpr int NW = BSR / 64;
-  constexpr int KS = N / 4;                                   // 19 k-steps of 4
-  static_assert(N % 4 == 0, "k-steps of 4");
-  constexpr int MT_V = (N + 15) / 16, NT = (NM + 15) / 16;    // 5 row tiles of V, 8 column tiles of F
-  // W = V_xx F  (76 x 114): tiles (mt, nt); results kept in registers until every wave is done reading V_xx
-  constexpr int W_TILES = MT_V * NT, W_PER_WAVE = (W_TILES + NW - 1) / NW;   // 40 tiles, 5 per wave
-  f64x4 wacc[W_PER_WAVE];
-#pragma unroll
-  for (int it = 0; it < W_PER_WAVE; ++it) {
-    const int tile = wave + it * NW;
-    const int mt = tile % MT_V, nt = (tile / MT_V) % NT;
-    const int row = 16 * mt + l15, col = 16 * nt + l15;
-    const bool rok = row < n, cok = col < NM;
-    const double* va = s_VW + (rok ? row : 0) + l4 * n;       // V(row, 4 s + l4)
-    const double* fb = s_F + (cok ? col : 0) * n + l4;        // F(4 s + l4, col)
-    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const double av = rok ? va[4 * s * n] : 0.0;
-      const double bv = cok ? fb[4 * s] : 0.0;
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-    }
-    wacc[it] = acc;
-  }
-  __syncthreads();   // every wave is done reading V_xx: W may overwrite it
-#pragma unroll
-  for (int it = 0; it < W_PER_WAVE; ++it) {
-    const int tile = wave + it * NW;
-    if (tile < W_TILES) {
-      const int mt = tile % MT_V, nt = tile / MT_V;
-      const int col = 16 * nt + l15;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * mt + l4 + 4 * r;
-        if (row < n && col < NM) s_VW[row + col * n] = wacc[it][r];
-      }
-    }
-  }
-  __syncthreads();
-  // D(j, c) = sum_k F(k, j) W(k, c): tiles (jt, ct) over 114 x 114, skipping those entirely inside the unused
-  // (j < N, c >= N) block
-  constexpr int JT = NT, CT = NT;
-  for (int tile = wave; tile < JT * CT; tile += NW) {
-    const int jt = tile % JT, ct = tile / JT;
-    if (16 * jt + 15 < n && 16 * ct >= n) continue;           // wave-uniform
-    const int j = 16 * jt + l15, c = 16 * ct + l15;
-    const bool jok = j < NM, cok = c < NM;
-    const double* fa = s_F + (jok ? j : 0) * n + l4;          // F(4 s + l4, j)  = A(j, k)
-    const double* wb = s_VW + (cok ? c : 0) * n + l4;         // W(4 s + l4, c)  = B(k, c)
-    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const double av = jok ? fa[4 * s] : 0.0;
-      const double bv = cok ? wb[4 * s] : 0.0;
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int jr = 16 * jt + l4 + 4 * r;                    // result row
-      if (jr >= NM || c >= NM) continue;
-      if (jr < n) { if (c < n) Dxx[jr + c * n] = acc[r]; }
-      else if (c < n) Dux[(jr - n) + c * m] = acc[r];
-      else Duu[(jr - n) + (c - n) * m] = acc[r];
-    }
-  }
-  // g = F^T V_x, one wave per column (two-term partials, then a shuffle tree)
-  double* g = p.ws_Q + (int64_t)b * (n + m + n * n + m * n + m * m);
-  for (int c = wave; c < NM; c += NW) {
-    const double* col = s_F + c * n;
-    double sacc = 0.0;
-    if (lane < n / 2) {
-      const f64x2 a = *reinterpret_cast<const f64x2*>(col + 2 * lane);
-      const f64x2 vv = *reinterpret_cast<const f64x2*>(s_vxn + 2 * lane);
-      sacc = a.x * vv.x + a.y * vv.y;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sacc += __shfl_down(sacc, off, 64);
-    if (lane == 0) g[c] = sacc;
-  }
-}
-
-// D for the first step to be processed (t = T-1), from V_xx = lfxx (ddp_bwd.ipp:27)
-template <int N, int M>
-__global__ __launch_bounds__(BSR) void bwd_dense0(BwdParams p) {
-  const int b = p.b0 + blockIdx.x;
-  if (p.status[b] != 0) return;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  double* s_VW = smem;
-  double* s_F = smem + N * (N + M);
-  const double* Vxx = p.ws_V + (int64_t)b * (N + N * N) + N;
-  __shared__ __attribute__((aligned(16))) double s_vxn[N];
-  for (int i = threadIdx.x; i < N * N; i += BSR) s_VW[i] = Vxx[i];
-  for (int i = threadIdx.x; i < N; i += BSR) s_vxn[i] = Vxx[i - N];          // V_x = lfx^T (ddp_bwd.ipp:28)
-  // (dense_product starts with a barrier after loading F)
-  dense_product<N, M>(p, b, p.d.T - 1, s_VW, s_F, s_vxn);
-}
-
-template <int N, int M>
-__global__ __launch_bounds__(BSR) void bwd_riccati(BwdParams p, int64_t t) {
-  const int b = p.b0 + blockIdx.x;
-  if (p.status[b] != 0) return;
-  constexpr int n = N, m = M;
-  const int nx = (int)p.d.nx;        // N + 1 with a free-flyer root
-  const int64_t T = p.d.T;
-  const int tid = threadIdx.x;
-  const int64_t bt = (int64_t)b * T + t;
-  const int e = (int)p.ne[t];
-  const int64_t Eo = p.Epre[t], Etot = p.d.Etot;
-  const double mu = p.mu[b];
-  const bool tens = p.has_tensors != 0;
-
-  double* Vx = p.ws_V + (int64_t)b * (n + n * n);
-  double* Vxx = Vx + n;
-  const double* C = p.ws_Q + (int64_t)b * (n + m + n * n + m * n + m * m) + n + m;   // K3's contraction
-  const double* Cxx = C;
-  const double* Cux = Cxx + n * n;
-  const double* Cuu = Cux + m * n;
-  const double* D = p.ws_D + (int64_t)b * (n * n + m * n + m * m);                  // dense f^T V_xx f
-  const double* Dxx = D;
-  const double* Dux = Dxx + n * n;
-  const double* Duu = Dux + m * n;
-  const double* eqv = p.eq_val + (int64_t)b * Etot + Eo;
-  const double* eqx = p.eq_x + ((int64_t)b * Etot + Eo) * n;
-  const double* equ = p.eq_u + ((int64_t)b * Etot + Eo) * m;
-  const double* pe = p.mult_val + (int64_t)b * Etot + Eo;
-  const double* pex = p.mult_jac + ((int64_t)b * Etot + Eo) * n;
-  const double* eq_xx = p.eq_xx + ((int64_t)b * Etot + Eo) * n * n;
-  const double* eq_ux = p.eq_ux + ((int64_t)b * Etot + Eo) * m * n;
-  const double* eq_uu = p.eq_uu + ((int64_t)b * Etot + Eo) * m * m;
-
-  constexpr int lda = M | 1, ldr = M | 1, NR = N + 1, NM = N + M;
-  constexpr int TJ = 6, AQ = (M + TJ - 1) / TJ;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  double* s_VW = smem;                         // N*NM: new V_xx, later W (dense tail)
-  double* s_F = smem + N * NM;                 // N*NM: F of step t-1 (dense tail); before that, the arrays below
-  double* A = s_F;                             // lda*M   Q_uu + reg I -> Cholesky factor (lower)
-  double* R = A + lda * M;                     // ldr*NR  [k | K]
-  double* S = R + ldr * NR;                    // ldr*N   Q_ux
-  double* s_q = S + ldr * N;                   // NM      Q_x | Q_u
-  double* s_tmp = s_q + NM;                    // emax    pe + mu eq   (ddp_bwd.ipp:46)
-  static_assert(lda * M + ldr * NR + ldr * N + NM + N + 64 <= N * NM, "phase-A arrays must fit the F region");
-
-  // entries of Q in the reference's order of terms (ddp_bwd.ipp:70-87): l, f^T V_xx f, multiplier terms, multiplier
-  // tensors, V_x-contracted tensors
-  auto q_uu = [&](int i, int j) -> double {
-    double acc = p.luu[bt * m * m + i + j * m];
-    acc += Duu[i + j * m];
-    if (e > 0) {
-      double s1 = 0.0;
-      for (int k = 0; k < e; ++k) s1 += equ[k + i * e] * equ[k + j * e];
-      acc += s1 * mu;                                                          // :79
-      if (tens) { double s3 = 0.0; for (int k = 0; k < e; ++k) s3 += s_tmp[k] * eq_uu[k + (i + j * m) * e]; acc += s3; }   // :80
-    }
-    if (tens) acc += Cuu[i + j * m];                                           // :81
-    return acc;
-  };
-  auto q_ux = [&](int i, int j) -> double {
-    double acc = p.lux[bt * m * n + i + j * m];
-    acc += Dux[i + j * m];
-    if (e > 0) {
-      double s1 = 0.0;
-      for (int k = 0; k < e; ++k) s1 += equ[k + i * e] * (pex[k + j * e] + mu * eqx[k + j * e]);   // :85
-      acc += s1;
-      if (tens) { double s3 = 0.0; for (int k = 0; k < e; ++k) s3 += s_tmp[k] * eq_ux[k + (i + j * m) * e]; acc += s3; }   // :86
-    }
-    if (tens) acc += Cux[i + j * m];                                           // :87
-    return acc;
-  };
-  auto q_xx = [&](int i, int j) -> double {
-    double acc = p.lxx[bt * n * n + i + j * n];
-    acc += Dxx[i + j * n];
-    if (e > 0) {
-      double s1 = 0.0, s2 = 0.0;
-      for (int k = 0; k < e; ++k) {
-        s1 += eqx[k + i * e] * (pex[k + j * e] + mu * eqx[k + j * e]);         // :72
-        s2 += pex[k + i * e] * eqx[k + j * e];                                 // :73
-      }
-      acc += s1;
-      acc += s2;
-      if (tens) { double s3 = 0.0; for (int k = 0; k < e; ++k) s3 += s_tmp[k] * eq_xx[k + (i + j * n) * e]; acc += s3; }   // :74
-    }
-    if (tens) acc += Cxx[i + j * n];                                           // :75
-    return acc;
-  };
-
-  __shared__ __attribute__((aligned(16))) double s_vxn[N];   // the new V_x, for the matvec of the next step (dense tail)
-  for (int i = tid; i < e; i += BSR) s_tmp[i] = pe[i] + mu * eqv[i];
-  __syncthreads();
-  // Q_x, Q_u (:61-68): the dense part f^T V_x was formed by the previous launch while f was in LDS
-  if (tid < NM) {
-    const int c = tid;
-    const double* g = p.ws_Q + (int64_t)b * (n + m + n * n + m * n + m * m);
-    double acc = c < n ? p.lx[bt * n + c] : p.lu[bt * m + (c - n)];
-    acc += g[c];
-    if (e > 0) {
-      double s1 = 0.0, s2 = 0.0;
-      if (c < n) { for (int k = 0; k < e; ++k) { s1 += eqx[k + c * e] * s_tmp[k]; s2 += pex[k + c * e] * eqv[k]; } acc += s1; acc += s2; }
-      else { for (int k = 0; k < e; ++k) s1 += equ[k + (c - n) * e] * s_tmp[k]; acc += s1; }
-    }
-    s_q[c] = acc;
-  }
-  for (int idx = tid; idx < m * n; idx += BSR) S[idx % m + (idx / m) * ldr] = q_ux(idx % m, idx / m);
-  __syncthreads();
-
-  const double reg = p.reg[b];
-  // right-hand sides [-Q_u | -Q_ux] (:135-136): lane 256 + c owns the whole column c in registers (waves 4-5), so the
-  // substitutions need no cross-lane traffic at all; waves 0-3 carry the factorisation
-  const int rc = tid - 256;
-  const bool rhs_lane = tid >= 256 && rc < NR;
-  double r[M];
-  if (rhs_lane) {
-#pragma unroll
-    for (int l = 0; l < m; ++l) r[l] = -(rc == 0 ? s_q[n + l] : S[l + (rc - 1) * ldr]);
-  }
-  // trailing matrix of the factorisation in registers: lane (ti, tj) owns row ti, columns tj, tj+6, ... <= ti
-  const int ti = tid % M, tj = tid / M;
-  const bool a_lane = tj < TJ;
-  double a[AQ];
-#pragma unroll
-  for (int q = 0; q < AQ; ++q) {
-    const int j = tj + TJ * q;
-    a[q] = (a_lane && j <= ti) ? q_uu(ti, j) + (ti == j ? reg : 0.0) : 0.0;           // :104
-  }
-  if (a_lane && tj == 0) A[ti] = a[0];       // raw column 0
-  __syncthreads();
-
-  // Cholesky (lower triangle only; fail <=> pivot <= 0, :105) with the forward substitution fused in: column k of L is
-  // final after step k, so y_k = r_k / L_kk and r_l -= L_lk y_k (l > k) ride along with the trailing update.  Per
-  // entry the updates arrive in ascending k: the order of Eigen's unblocked LLT and of its row-wise substitution.
-  bool failed = false;
-#pragma unroll
-  for (int k = 0; k < m; ++k) {
-    const double piv = A[k + k * lda];
-    if (piv <= 0.0) { failed = true; break; }
-    const double dk = sqrt(piv);
-    if (a_lane && tj == 0 && ti > k) A[ti + k * lda] = A[ti + k * lda] / dk;
-    if (rhs_lane) r[k] = r[k] / dk;
-    __syncthreads();
-    const double* Lk = A + k * lda;
-    if (a_lane) {
-      const double lik = Lk[ti];
-#pragma unroll
-      for (int q = 0; q < AQ; ++q) {
-        const int j = tj + TJ * q;
-        const double ljk = Lk[j < m ? j : m - 1];
-        a[q] = (j > k && j <= ti) ? a[q] - lik * ljk : a[q];
-      }
-      const int k1 = k + 1;
-      if (k1 < m && tj == k1 % TJ && ti >= k1) A[ti + k1 * lda] = a[k1 / TJ];   // raw column k+1, final after this update
-    }
-    if (rhs_lane) {
-#pragma unroll
-      for (int l = k + 1; l < m; ++l) r[l] -= Lk[l] * r[k];
-    }
-    if (tid == k) A[k + k * lda] = dk;
-    __syncthreads();
-  }
-  if (failed) {
-    if (tid == 0) {
-      double rg = p.reg[b], mu2 = p.mu[b];
-      if (rg < mu2) rg = mu2;      // :106-108
-      mu2 *= 2;                    // :109
-      rg *= 2;                     // :110
-      p.reg[b] = rg;
-      p.mu[b] = mu2;
-      p.status[b] = 1;
-      p.restarts[b] += 1;
-    }
-    return;
-  }
-  // back substitution L^T x = y, column oriented, entirely inside each right-hand-side lane
-  if (rhs_lane) {
-#pragma unroll
-    for (int k = m - 1; k >= 0; --k) {
-      r[k] = r[k] / A[k + k * lda];
-#pragma unroll
-      for (int i = 0; i < k; ++i) r[i] -= A[k + i * lda] * r[k];
-      __builtin_amdgcn_sched_barrier(0);   // keep the scheduler from hoisting all 703 LDS reads (register pressure)
-    }
-  }
-
-  double* fbo = p.fb_origin + bt * nx;
-  const double* xt = p.x + ((int64_t)b * (T + 1) + t) * nx;
-  for (int i = tid; i < nx; i += BSR) fbo[i] = xt[i];                        // :134
-  if (rhs_lane) {
-    double* dst = rc == 0 ? p.fb_val + bt * m : p.fb_jac + bt * m * n + (rc - 1) * m;
-#pragma unroll
-    for (int l = 0; l < m; ++l) { dst[l] = r[l]; R[l + rc * ldr] = r[l]; }
-  }
-  __syncthreads();
-
-  // V_x = Q_x + Q_ux^T k (:142-143);  V_xx = Q_xx + Q_ux^T K (:145-146), 1 x 4 register tiles; the new V_xx also
-  // goes to LDS for the dense product of the next step
-  for (int i = tid; i < n; i += BSR) {
-    double s = 0.0;
-#pragma unroll 2
-    for (int l = 0; l < m; ++l) s += S[l + i * ldr] * R[l];
-    const double v = s_q[i] + s;
-    Vx[i] = v;
-    s_vxn[i] = v;
-    if (p.vx_trace) p.vx_trace[bt * n + i] = v;
-  }
-  for (int idx = tid; idx < n * (n / 4); idx += BSR) {
-    const int i = idx % n, j0 = (idx / n) * 4;
-    const double* si = S + i * ldr;
-    const double* k0 = R + (j0 + 1) * ldr;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-#pragma unroll 2
-    for (int l = 0; l < m; ++l) {
-      const double sv = si[l];
-      s0 += sv * k0[l];
-      s1 += sv * k0[l + ldr];
-      s2 += sv * k0[l + 2 * ldr];
-      s3 += sv * k0[l + 3 * ldr];
-    }
-    const double sv4[4] = {s0, s1, s2, s3};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int o = i + (j0 + q) * n;
-      const double v = q_xx(i, j0 + q) + sv4[q];
-      Vxx[o] = v;
-      s_VW[o] = v;
-      if (p.vxx_trace) p.vxx_trace[bt * n * n + o] = v;
-    }
-  }
-  if (t == 0) {
-    if (tid == 0) p.status[b] = 2;                                           // :149-151
-    return;
-  }
-  __syncthreads();   // V_xx complete in LDS; A, R, S, Y are dead: their space becomes F
-  dense_product<N, M>(p, b, t - 1, s_VW, s_F, s_vxn);
 }

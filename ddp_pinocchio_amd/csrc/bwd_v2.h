@@ -11,8 +11,8 @@
 //       (the round-1 kernel took 76) -- then the 77 right-hand sides [-Q_u | -Q_ux] one per lane against L in LDS, V_x,
 //       and V_xx = Q_xx + Q_ux^T K on the matrix cores.
 //
-// Per instance the chain is K4'(t+1) -> K5(t) -> K3(t) -> K4'(t).  Same arithmetic conventions as bwd_split.h: no
-// symmetrisation, lower triangle only, fail <=> pivot <= 0, per-entry updates in ascending k.
+// Per instance the chain is K4'(t+1) -> K5(t) -> K3(t) -> K4'(t).  Same arithmetic conventions as bwd_gains (bwd.hip):
+// no symmetrisation, lower triangle only, fail <=> pivot <= 0, per-entry updates in ascending k.
 #pragma once
 
 // development: -DBWD_STAMPS builds in-kernel phase stamps (s_memrealtime, 100 MHz) of instance 0, read by tools/bwd_stamps.py
@@ -24,6 +24,8 @@ __device__ unsigned long long g_bwd_stamps[32];
 #define STAMP(i) do { } while (0)
 #define STAMP_T(i, T_) do { } while (0)
 #endif
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BS5 = 512;   // workgroup size of K5
 constexpr int BS4 = 512;   // workgroup size of K4' (wave 0: LLT, waves 1-2: right-hand sides, all eight: loads and the V update)
@@ -37,7 +39,7 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 template <int N, int M>
 __global__ __launch_bounds__(BS5) void bwd_dense2(BwdParams p, int64_t t) {
   constexpr int n = N, m = M, NM = N + M;
-  const int b = p.b0 + blockIdx.y;
+  const int b = blockIdx.y;
   if (p.status[b] != 0) return;
   const int c0 = blockIdx.x * CB5;                 // first column of this block (0 .. NM-1)
   const int tid = threadIdx.x;
@@ -418,7 +420,7 @@ __global__ __launch_bounds__(BS4) void bwd_gains2(BwdParams p, int64_t t) {
   const int nx = (int)p.d.nx;        // N + 1 with a free-flyer root
   constexpr int LD = M | 1;          // odd leading dimensions: conflict-free column walks
   constexpr int LP = M;              // a shifted column / reversed row holds at most M-1 entries; the rest stays zero (even: 16-byte aligned columns)
-  const int b = p.b0 + blockIdx.x;
+  const int b = blockIdx.x;
   if (p.status[b] != 0) return;
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63, l15 = lane & 15, l4 = lane >> 4;
@@ -440,12 +442,6 @@ __global__ __launch_bounds__(BS4) void bwd_gains2(BwdParams p, int64_t t) {
   const double* Qxx = Q + n + m;
   const double* Qux = Qxx + n * n;
   const double* Quu = Qux + m * n;
-  // c_accumulate == 2: K3 ran beside K5 and left its contracted blocks in a workspace of its own; Q = P + C is formed here
-  // (the same single addition K3's accumulating epilogue makes: the tensor term comes last, ddp_bwd.ipp:75,81,87)
-  const bool addc = p.c_accumulate == 2 && p.has_tensors != 0;
-  const double* Cxx = p.ws_D + (int64_t)b * (n * n + m * n + m * m);
-  const double* Cux = Cxx + n * n;
-  const double* Cuu = Cux + m * n;
 
   STAMP(8);
   // wave 0 only fetches what the factorisation needs -- its row of Q_uu -- and clears the two images of L itself, so that it can
@@ -459,7 +455,7 @@ __global__ __launch_bounds__(BS4) void bwd_gains2(BwdParams p, int64_t t) {
 #pragma unroll
     for (int j = 0; j < M; ++j) {
       double qv_ = 0.0;
-      if (lane < m && j <= lane) { qv_ = Quu[lane + j * m]; if (addc) qv_ = qv_ + Cuu[lane + j * m]; qv_ = qv_ + (lane == j ? reg : 0.0); }
+      if (lane < m && j <= lane) { qv_ = Quu[lane + j * m]; qv_ = qv_ + (lane == j ? reg : 0.0); }
       a[j] = qv_;
     }
     for (int i = lane; i < (M + 2) * LP; i += 64) { sL[i] = 0.0; sLt_[i] = 0.0; }
@@ -467,7 +463,7 @@ __global__ __launch_bounds__(BS4) void bwd_gains2(BwdParams p, int64_t t) {
     constexpr int BSO = BS4 - 64;
     const int to = tid - 64;
     for (int i = to; i < n + m; i += BSO) sQ[i] = Q[i];
-    for (int idx = to; idx < m * n; idx += BSO) sU[idx % m + (idx / m) * LD] = addc ? Qux[idx] + Cux[idx] : Qux[idx];
+    for (int idx = to; idx < m * n; idx += BSO) sU[idx % m + (idx / m) * LD] = Qux[idx];
   }
   STAMP(9);
   if (wave == 0) {
@@ -574,7 +570,7 @@ __global__ __launch_bounds__(BS4) void bwd_gains2(BwdParams p, int64_t t) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int j = 16 * jt + l4 + 4 * q;
-      qv[it_][q] = (tile < TT * TT && j < n && ib < n) ? (addc ? Qxx[ib + j * n] + Cxx[ib + j * n] : Qxx[ib + j * n]) : 0.0;
+      qv[it_][q] = (tile < TT * TT && j < n && ib < n) ? Qxx[ib + j * n] : 0.0;
     }
   }
 #pragma unroll

@@ -206,6 +206,29 @@ static int fill_device(ddp_hip_ctx* ctx, double* p, int64_t n, double v) {
   return DDP_HIP_OK;
 }
 
+// The development switches: the one place in the library that reads the environment
+static DevSwitches read_switches() {
+  auto on = [](const char* name) { return getenv(name) != nullptr; };
+  auto knob = [](const char* name, int lo, int hi) { const char* ev = getenv(name); const int v = ev ? atoi(ev) : 0; return v >= lo && v <= hi ? v : 0; };
+  DevSwitches sw;
+  sw.generic_bwd = on("DDP_HIP_GENERIC_BWD");
+  sw.k3_no_sym = on("DDP_HIP_K3_NO_SYM");
+  sw.k3_no_half = on("DDP_HIP_K3_NO_HALF");
+  sw.fxx_full = on("DDP_HIP_FXX_FULL");
+  sw.no_static = on("DDP_HIP_NO_STATIC");
+  sw.no_qcache = on("DDP_HIP_NO_QCACHE");
+  sw.ana_own_aba = on("DDP_HIP_ANA_OWN_ABA");
+  sw.ana_split = on("DDP_HIP_ANA_SPLIT");
+  sw.ana_eq_kernel = on("DDP_HIP_ANA_EQ_KERNEL");
+  sw.bwd_no_graph = on("DDP_HIP_BWD_NO_GRAPH");
+  sw.solve_sync = on("DDP_HIP_SOLVE_SYNC");
+  sw.bwd_cbx = knob("DDP_HIP_BWD_CBX", 1, 8);
+  sw.bwd_cbu = knob("DDP_HIP_BWD_CBU", 1, 16);
+  sw.qws_bt = knob("DDP_HIP_QWS_BT", 16, 65536);
+  sw.ana_bt = knob("DDP_HIP_ANA_BT", 1, 65536);
+  return sw;
+}
+
 extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t flags, ddp_hip_ctx** out) {
   if (!prob || !out) return DDP_HIP_E_ARG;
   *out = nullptr;
@@ -242,6 +265,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   if (!ctx) return DDP_HIP_E_HIP;
   ctx->device = device;
   ctx->flags = flags;
+  ctx->sw = read_switches();
   ctx->active_h.assign((size_t)prob->batch, 1);
   Dims& d = ctx->d;
   d.T = prob->T; d.nv = mo.nv; d.n = 2 * (int64_t)mo.nv; d.m = mo.nv; d.nx = 2 * (int64_t)mo.nv + (ff ? 1 : 0); d.batch = prob->batch;
@@ -430,7 +454,7 @@ extern "C" int ddp_hip_ctx_info(const ddp_hip_ctx* ctx, ddp_hip_info* out) {
   out->device = ctx->device;
   out->lin_path = ctx->model_h.kind == DDP_HIP_MODEL_PENDULUM ? 0 : (ctx->lin_static ? 1 + ctx->lin_static : 1);
   out->first_order = ctx->model_h.kind == DDP_HIP_MODEL_PENDULUM ? 0 : (ctx->model_h.first_order_fd ? 1 : 2);
-  out->bwd_path = (d.n == 76 && d.m == 38 && getenv("DDP_HIP_GENERIC_BWD") == nullptr) ? 1 : 0;
+  out->bwd_path = sweep_plan(ctx).fast ? 1 : 0;
   out->fwd_path = fwd_lat_supported(ctx) ? 1 : 0;
   out->has_tensors = (ctx->flags & DDP_HIP_FLAG_NO_TENSORS) ? 0 : 1;
   int64_t bytes = 0;
@@ -481,8 +505,6 @@ void prof_end(ddp_hip_ctx* ctx, int kid, hipStream_t stream) {
 }
 static void prof_collect(ddp_hip_ctx* ctx) {
   (void)hipStreamSynchronize(ctx->stream);
-  for (int g = 0; g < ctx->bwd_groups; ++g)
-    if (ctx->bwd_stream[g]) (void)hipStreamSynchronize(ctx->bwd_stream[g]);
   for (int k = 0; k < DDP_HIP_K_COUNT; ++k) {
     ProfSlot& p = ctx->prof[k];
     for (size_t i = 0; i < p.used; ++i) {
@@ -521,16 +543,14 @@ extern "C" int64_t ddp_hip_bwd_stream_bytes(const ddp_hip_ctx* ctx) {
   if (!ctx) return -1;
   if (ctx->flags & DDP_HIP_FLAG_NO_TENSORS) return 0;
   const int64_t n = ctx->d.n, m = ctx->d.m;
-  const bool fast = n == 76 && m == 38 && ctx->d.emax <= 52 && getenv("DDP_HIP_GENERIC_BWD") == nullptr;
-  const bool sym = fast && ctx->tensors_sym && ctx->jobs_sym_d && getenv("DDP_HIP_K3_NO_SYM") == nullptr;
-  const bool half = sym && ctx->tensor_tops_zero && ctx->tensor_tops_sparse && ctx->jobs_half_d && getenv("DDP_HIP_K3_NO_HALF") == nullptr;
-  if (half) {
+  const SweepPlan s = sweep_plan(ctx);
+  if (s.half_mode == 1) {
     const int64_t cxx = n * (n + 1) / 2, cux = n * m, cuu = m * (m + 1) / 2;
     return 8 * ((cxx + cux + cuu) * (n - m) + 2 * cxx - n + cux);       // lower halves + two entries per f_xx column (one on its diagonal), one per f_ux column
   }
-  if (fast && !half && ctx->fuu_zero && ctx->model_h.fd_mode == 1 && ctx->jobs_half_d && getenv("DDP_HIP_K3_NO_HALF") == nullptr)
+  if (s.half_mode == 2)
     return 8 * (n * n + n * m) * (n - m);                                // analytic mode 1: the lower halves of f_xx and f_ux, nothing of f_uu
-  if (sym) return 8 * (n * (n * (n + 1) / 2) + n * n * m + n * (m * (m + 1) / 2));
+  if (s.sym) return 8 * (n * (n * (n + 1) / 2) + n * n * m + n * (m * (m + 1) / 2));
   return 8 * (n * n * n + n * n * m + n * m * m);
 }
 

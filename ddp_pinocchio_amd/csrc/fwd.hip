@@ -182,98 +182,8 @@ __global__ void forward_kernel(FwdParams p) {
   p.fw_dcost[(int64_t)b * na + a] = dsum;
 }
 
-// Latency path of the same rollouts (tree models, no constraints): one 64-lane workgroup per instance, 8 lanes per
-// candidate.  The gain product K_t (x_new - x_old) is spread over the 8 lanes of a candidate (each takes every 8th
-// column of K_t, contiguous column loads, then three xor-shuffles); the forward dynamics keeps its per-joint state in
-// LDS and its 8 lanes walk the tree level by level (rbd::aba_tree_coop), so the legs, arms and head advance together.
-template <int NJ>
-__global__ __launch_bounds__(64) void forward_kernel_lat(FwdParams p) {
-  constexpr int NC = 8, NH = 8;                      // candidates per instance, helper lanes per candidate
-  constexpr int n = 2 * NJ, nx = 2 * NJ, nu = NJ;
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double* aba_state = lds;                           // ABA_LDS_SLOTS * NJ * NC
-  double* s_dx = lds + rbd::ABA_LDS_SLOTS * NJ * NC; // NC * n
-  double* s_x = s_dx + NC * n;                       // NC * nx
-  double* s_u = s_x + NC * nx;                       // NC * nu
-  double* s_qdd = s_u + NC * nu;                     // NC * nu
-  const int b = blockIdx.x;
-  if (p.state[b] != 0) return;
-  const int tid = threadIdx.x, a = tid / NH, h = tid % NH;
-  const int na = p.n_alpha;
-  const int cand = p.round * na + a;
-  const bool live = a < na && cand <= 33;            // 2^-34 < 1e-10: never tried (ddp_fwd.ipp:35-37)
-  if (a < na && cand > 33 && h == 0) p.fw_dcost[(int64_t)b * na + a] = INFINITY;
-  const double step = ldexp(1.0, -cand);
-  const DevModel& m = *p.model;
-  const int64_t T = p.d.T;
-  const double* xo = p.x_old + (int64_t)b * (T + 1) * nx;
-  const double* uo = p.u_old + (int64_t)b * T * nu;
-  double* xw = p.fw_x + ((int64_t)b * na + (a < na ? a : 0)) * (T + 1) * nx;
-  double* uw = p.fw_u + ((int64_t)b * na + (a < na ? a : 0)) * T * nu;
-  const double* cold = p.costs_old + (int64_t)b * (T + 1);
-  double* dx = s_dx + a * n;
-  double* x = s_x + a * nx;
-  double* u = s_u + a * nu;
-  double* qdd = s_qdd + a * nu;
-  const double* x0 = p.x_new + (int64_t)b * (T + 1) * nx;        // x_new,0 is preset by the caller (ddp.hpp:752)
-  if (live)
-    for (int i = h; i < nx; i += NH) { x[i] = x0[i]; xw[i] = x0[i]; }
-  double dsum = 0.0;
-  __syncthreads();
-  for (int64_t t = 0; t < T; ++t) {
-    const double* k = p.fb_val + ((int64_t)b * T + t) * nu;
-    const double* K = p.fb_jac + ((int64_t)b * T + t) * nu * n;
-    if (live)
-      for (int i = h; i < n; i += NH) dx[i] = x[i] - xo[t * nx + i];           // :45 difference(out, old, new)
-    __syncthreads();
-    double acc[NJ];
-#pragma unroll
-    for (int i = 0; i < nu; ++i) acc[i] = 0.0;
-    for (int l = h; l < n; l += NH) {
-      const double d = dx[l];
-      const double* Kc = K + (int64_t)l * nu;
-#pragma unroll
-      for (int i = 0; i < nu; ++i) acc[i] += Kc[i] * d;
-    }
-#pragma unroll
-    for (int i = 0; i < nu; ++i) {
-      acc[i] += __shfl_xor(acc[i], 1, 64);
-      acc[i] += __shfl_xor(acc[i], 2, 64);
-      acc[i] += __shfl_xor(acc[i], 4, 64);
-    }
-    if (h == 0 && live) {
-      double un = 0;
-#pragma unroll
-      for (int i = 0; i < nu; ++i) {
-        double ui = uo[t * nu + i] + step * k[i];                               // :47-48
-        ui += acc[i];                                                           // :49
-        u[i] = ui;
-        uw[t * nu + i] = ui;
-        un += ui * ui;
-      }
-      const double c_new = 0.5 * m.c * un;                                      // problem_t::l (no constraints on this path)
-      dsum += c_new - cold[t];
-    }
-    __syncthreads();
-    rbd::aba_tree_coop<NJ, NC, NH>(m, x, x + NJ, u, qdd, aba_state, a, h, live);   // :50 (ends with a barrier)
-    if (live)
-      for (int i = h; i < NJ; i += NH) {                                        // dynamics_t::eval_to, problem.hpp:441-461
-        const double vo = m.dt * x[NJ + i];
-        const double qn = x[i] + vo;
-        const double vn = x[NJ + i] + qdd[i] * m.dt;
-        x[i] = qn; x[NJ + i] = vn;
-        xw[(t + 1) * nx + i] = qn; xw[(t + 1) * nx + NJ + i] = vn;
-      }
-    __syncthreads();
-  }
-  if (h == 0 && live) {
-    dsum += 0.0 - cold[T];
-    p.fw_dcost[(int64_t)b * na + a] = dsum;
-  }
-}
-
-// Second latency path: one 64-lane workgroup (= one wave) per (instance, four candidates), 16 lanes per candidate.
-// What the first one waits for at every step is global memory: the 23 KB gain matrix K_t (written by the backward sweep a whole
+// Latency path of the same rollouts (trees of the Talos size): one 64-lane workgroup (= one wave) per (instance, four
+// candidates), 16 lanes per candidate.  What a rollout waits for at every step is global memory: the 23 KB gain matrix K_t (written by the backward sweep a whole
 // linearisation ago: an HBM read in the middle of the step), k_t, u_old, x_old, and the per-level reads of the model tables
 // inside the traversal (dependent L2 round trips, three per tree level).  Here
 //   * the model (inertias, axes, placements, level tables: rbd::CoopModel) is copied to LDS once per launch;
@@ -636,8 +546,7 @@ FwdParams make_params(ddp_hip_ctx* ctx) {
 bool fwd_lat_supported(const ddp_hip_ctx* ctx) {
   const DevModel& m = ctx->model_h;
   // (constrained problems: the rollout runs on the latency kernel, the candidates' cost terms on cand_cost_kernel)
-  if (m.kind != DDP_HIP_MODEL_TREE || ctx->d.nv != 38 || (m.ff && getenv("DDP_HIP_FWD_FF_SCRATCH") != nullptr) || getenv("DDP_HIP_FWD_SCRATCH") != nullptr) return false;
-  if (ctx->d.Etot != 0 && getenv("DDP_HIP_FWD_EQ_SCRATCH") != nullptr) return false;   // development: round 2's one-lane-per-rollout kernel for constrained problems
+  if (m.kind != DDP_HIP_MODEL_TREE || ctx->d.nv != 38) return false;
   // the cooperative traversal: at most 8 joints per tree level (one helper lane each), 16 levels and 3 children per joint
   // (rbd::coop_role packs a lane's joint of a level into one word)
   if (m.max_level_width > 8 || m.n_levels > 16) return false;
@@ -658,8 +567,6 @@ int fwd_setup(ddp_hip_ctx* ctx) {
   HIP_TRY(hipMalloc(&ctx->fw_state_d, sizeof(int32_t) * (size_t)B));
   if (d.nv == 38) {
     // per device, by every context (the attribute is not process-wide)
-    const size_t lds = sizeof(double) * (size_t)(rbd::ABA_LDS_SLOTS * 38 * 8 + 8 * (76 + 76 + 38 + 38));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat<38>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)sizeof(FwdLat2Lds<38>)));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -693,7 +600,7 @@ extern "C" int ddp_hip_rollout(ddp_hip_ctx* ctx) {
   if (!ctx) return DDP_HIP_E_ARG;
   HIP_TRY(hipSetDevice(ctx->device));
   FwdParams p = make_params(ctx);
-  if (fwd_lat_supported(ctx) && getenv("DDP_HIP_FWD_LAT1") == nullptr) {
+  if (fwd_lat_supported(ctx)) {
     // unconstrained trees of the Talos size: the open-loop form of the latency kernel (one workgroup per instance)
     if (ctx->model_h.ff) hipLaunchKernelGGL((forward_kernel_lat2<38, true, true>), dim3((unsigned)ctx->d.batch), dim3(128), sizeof(FwdLat2Lds<38>), ctx->stream, p);
     else hipLaunchKernelGGL((forward_kernel_lat2<38, true>), dim3((unsigned)ctx->d.batch), dim3(128), sizeof(FwdLat2Lds<38>), ctx->stream, p);
@@ -757,16 +664,13 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
     // tree models of the Talos size: the latency path (two workgroups per instance, 16 lanes per candidate); with constraints the
     // cost terms of the rolled-out candidates come from cand_cost_kernel (parallel over t) instead of the rollout itself
     const bool lat_path = fwd_lat_supported(ctx) && n_alpha <= 8;
-    if (lat_path && (getenv("DDP_HIP_FWD_LAT1") == nullptr || !p.cost_inline)) {
+    if (lat_path) {
       if (ctx->model_h.ff) hipLaunchKernelGGL((forward_kernel_lat2<38, false, true>), dim3((unsigned)(2 * B)), dim3(128), sizeof(FwdLat2Lds<38>), ctx->stream, p);
       else hipLaunchKernelGGL((forward_kernel_lat2<38>), dim3((unsigned)(2 * B)), dim3(128), sizeof(FwdLat2Lds<38>), ctx->stream, p);
       if (!p.cost_inline) {
         hipLaunchKernelGGL((cand_cost_kernel<38>), dim3((unsigned)((B * n_alpha * d.T + 63) / 64)), dim3(64), 0, ctx->stream, p);
         hipLaunchKernelGGL(cand_sum_kernel, dim3((unsigned)((B * n_alpha + 63) / 64)), dim3(64), 0, ctx->stream, p);
       }
-    } else if (lat_path) {
-      const size_t lds = sizeof(double) * (size_t)(rbd::ABA_LDS_SLOTS * 38 * 8 + 8 * (76 + 76 + 38 + 38));
-      hipLaunchKernelGGL((forward_kernel_lat<38>), dim3((unsigned)B), dim3(64), lds, ctx->stream, p);
     } else {
 #define CALL(NJ) hipLaunchKernelGGL((forward_kernel<NJ>), dim3(grid), dim3(bs), 0, ctx->stream, p)
       DISPATCH_NJ(d.nv, CALL);

@@ -60,6 +60,33 @@ struct BwdJob {
   int32_t pad_;
 };
 
+// Development switches (DDP_HIP_*), read once by ddp_hip_create (ctx.hip: read_switches): a context
+// keeps the paths it was created with.  A tuning knob of 0 is unset (or out of its range): the context's own choice holds.
+struct DevSwitches {
+  bool generic_bwd = false;    // GENERIC_BWD: the run-time-shaped sweep at the Talos shape as well
+  bool k3_no_sym = false;      // K3_NO_SYM: K3 reads every half-slab (and the static stencil writes the mirror images)
+  bool k3_no_half = false;     // K3_NO_HALF: no K3h
+  bool fxx_full = false;       // FXX_FULL: the static stencil writes the configuration rows and the mirror images
+  bool no_static = false;      // NO_STATIC: the generic level kernels instead of the static-topology ones
+  bool no_qcache = false;      // NO_QCACHE: no configuration caches
+  bool ana_own_aba = false;    // ANA_OWN_ABA: the analytic pass forms its own accelerations
+  bool ana_split = false;      // ANA_SPLIT: the three-kernel analytic path with its HBM workspaces
+  bool ana_eq_kernel = false;  // ANA_EQ_KERNEL: the constraint tensors in a kernel of their own
+  bool bwd_no_graph = false;   // BWD_NO_GRAPH: the sweep is enqueued launch by launch, not replayed as a hipGraph
+  bool solve_sync = false;     // SOLVE_SYNC: ddp_hip_solve waits for the stream at every call
+  int32_t bwd_cbx = 0, bwd_cbu = 0;   // BWD_CBX (1..8), BWD_CBU (1..16): columns per job of K3 / bwd_assemble
+  int64_t qws_bt = 0;          // QWS_BT (16..65536): (instance, t) pairs per configuration-level workspace slice
+  int64_t ana_bt = 0;          // ANA_BT (1..65536): (instance, t) pairs per analytic workspace slice
+};
+
+// The backward sweep a context runs on its tensors as they are (bwd.hip: sweep_plan)
+struct SweepPlan {
+  bool fast;       // the Talos-shape kernels K5 / K3 / K4' (bwd_v2.h); else the run-time-shaped pair
+  bool sym_ok;     // ... which would read symmetric tensors by halves: the static stencil may leave the mirror images out
+  bool sym;        // ... and they are symmetric now (tensors_sym): K3 reads one of each pair of mirrored half-slabs
+  int32_t half_mode;   // K3h (bwd_split.h: bwd_contract_half): 0 off, 1 the static stencil's tensors, 2 analytic mode 1
+};
+
 struct ProfSlot {
   std::vector<hipEvent_t> starts, stops;
   size_t used = 0;
@@ -79,11 +106,11 @@ struct ddp_hip_ctx {
   DevModel model_h{};
   DevModel* model_d = nullptr;
   SeqBuf seq[DDP_HIP_SEQ_COUNT];
+  DevSwitches sw;
 
   // backward workspace, per instance
   double* ws_V = nullptr;      // [batch][n + n*n]          V_x | V_xx
   double* ws_Q = nullptr;      // [batch][n + m + n*n + m*n + m*m]   Q_x | Q_u | Q_xx | Q_ux | Q_uu
-  double* ws_D = nullptr;      // [batch][n*n + m*n + m*m]   dense f^T V_xx f of the next step (split kernels)
   double* reg_d = nullptr;     // [batch]
   double* mu_d = nullptr;      // [batch]
   int32_t* status_d = nullptr; // [batch] 0 active, 1 failed this attempt, 2 done
@@ -98,20 +125,11 @@ struct ddp_hip_ctx {
   bool tensors_sym = false;       // FXX / FUU hold what this context's own mode-2 (or tensor-free: zero) linearisation wrote: symmetric bit for bit
   int32_t njobs = 0;
   int32_t cbx = 0, cbu = 0;
-  // the batch is swept in groups on their own streams: K3 of one group overlaps K4 of the others (bwd.hip)
-  int32_t bwd_groups = 1;
-  hipStream_t bwd_stream[8] = {};
-  hipEvent_t bwd_ev_start = nullptr, bwd_ev_done[8] = {};
-  hipStream_t bwd_side = nullptr;          // K5 of a step runs here, beside K3 on the main stream (bwd.hip: enqueue_sweep_v2)
-  hipEvent_t bwd_ev_fork = nullptr, bwd_ev_join = nullptr;
-  int bwd_fork = 0;
-  // the sweep as an instantiated hipGraph (600 launches per group and sweep otherwise pay the enqueue cost every time);
+  // the sweep as an instantiated hipGraph (600 launches per sweep otherwise pay the enqueue cost every time);
   // one per state of the kernel arguments (the X buffers trade places at every swap_traj)
   struct BwdGraph { const void* key_x = nullptr; uint64_t key_misc = 0; hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; };
   BwdGraph bwd_graph[4];
   int bwd_graph_next = 0;
-  int bwd_use_graph = 1;
-  size_t bwd_k3_lds_pad = 0;
 
   // forward workspace
   double* fw_x = nullptr;      // [batch][n_alpha_max][(T+1)*nx]
@@ -142,7 +160,6 @@ struct ddp_hip_ctx {
   bool ana_M0_fresh = false;   // ana_M0 was written by stage 0 of the linearisation call in progress
   bool fuu_zero = false;       // analytic mode 1: F_UU holds the exact zeros lin_analytic.hip left there (cleared by every other writer)
   double* ana_M0 = nullptr;    // [B T][nv][nv] M^-1 at the trajectory points (fused analytic path, mode 1)
-  bool ana_split = false;      // development: three-kernel analytic path (DDP_HIP_ANA_SPLIT)
   double* ana_A = nullptr;     // [B T][2nv][nv] accelerations of the mode-1 perturbed points (static first-order kernels, level 6)
   int64_t ana_nbt = 0;         // (instance, t) pairs per slice
   int lin_static = 0;          // id of the compiled-in topology the model's tree matches (lin_static.hip), 0 = none
@@ -172,6 +189,7 @@ void prof_end(ddp_hip_ctx* ctx, int kid, hipStream_t stream = nullptr);
 
 // per-op launchers implemented in their own translation units
 int bwd_setup(ddp_hip_ctx* ctx);
+SweepPlan sweep_plan(const ddp_hip_ctx* ctx);
 void bwd_teardown(ddp_hip_ctx* ctx);
 int fwd_setup(ddp_hip_ctx* ctx);
 bool fwd_lat_supported(const ddp_hip_ctx* ctx);   // the latency kernels of the forward sweep apply (tree, no constraints, Talos size)

@@ -772,9 +772,9 @@ LinParams make_params(ddp_hip_ctx* ctx) {
   p.eq_val = S(DDP_HIP_SEQ_EQ_VAL); p.eq_x = S(DDP_HIP_SEQ_EQ_X); p.eq_u = S(DDP_HIP_SEQ_EQ_U);
   p.eq_xx = S(DDP_HIP_SEQ_EQ_XX); p.eq_ux = S(DDP_HIP_SEQ_EQ_UX); p.eq_uu = S(DDP_HIP_SEQ_EQ_UU);
   p.has_tensors = (ctx->flags & DDP_HIP_FLAG_NO_TENSORS) ? 0 : 1;
-  p.skip_top = (ctx->lin_static && ctx->model_h.fd_mode == 2 && !ctx->model_h.ff && getenv("DDP_HIP_FXX_FULL") == nullptr) ? 1 : 0;
-  p.skip_qv_mirror = (ctx->jobs_sym_d && ctx->lin_static && ctx->model_h.fd_mode == 2 && getenv("DDP_HIP_K3_NO_SYM") == nullptr &&
-                      getenv("DDP_HIP_FXX_FULL") == nullptr) ? 1 : 0;
+  p.skip_top = (ctx->lin_static && ctx->model_h.fd_mode == 2 && !ctx->model_h.ff && !ctx->sw.fxx_full) ? 1 : 0;
+  // the mirror images are left out only for a sweep that never reads them (the mode-2 tensors written here are symmetric)
+  p.skip_qv_mirror = (ctx->lin_static && ctx->model_h.fd_mode == 2 && !ctx->sw.fxx_full && sweep_plan(ctx).sym_ok) ? 1 : 0;
   p.eq_xk = ctx->eq_ws;
   if (p.eq_xk) {
     const Dims& dd = ctx->d;
@@ -811,7 +811,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, uint32_t stages) {
   auto build_caches = [&]() {
     if (caches_built || !p.qcache) return;
     const int nv = (int)d.nv;
-    if (ctx->lin_static && getenv("DDP_HIP_NO_STATIC_CACHE") == nullptr) { const int rc_ = lin_static_launch(ctx, p, 5); if (rc_ != DDP_HIP_OK) static_rc = rc_; }
+    if (ctx->lin_static) { const int rc_ = lin_static_launch(ctx, p, 5); if (rc_ != DDP_HIP_OK) static_rc = rc_; }
     else {
       hipLaunchKernelGGL((lin_qcache_kernel<NJ>), dim3(blocks_for(BT * (nv + 1))), dim3(LBS), 0, ctx->stream, p);
       hipLaunchKernelGGL((lin_vcache_kernel<NJ>), dim3(blocks_for(BT * (2 * nv + 1))), dim3(LBS), 0, ctx->stream, p);
@@ -829,7 +829,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, uint32_t stages) {
         if (rc_ != DDP_HIP_OK) return rc_;
       }
     } else if (ctx->model_h.first_order_fd) {
-      if (ctx->lin_static && p.qcache && getenv("DDP_HIP_NO_STATIC_FIRST") == nullptr) { build_caches(); { const int rc_ = lin_static_launch(ctx, p, 0); if (rc_ != DDP_HIP_OK) return rc_; } }
+      if (ctx->lin_static && p.qcache) { build_caches(); { const int rc_ = lin_static_launch(ctx, p, 0); if (rc_ != DDP_HIP_OK) return rc_; } }
       else hipLaunchKernelGGL((lin_first_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p);
     }
     prof_end(ctx, DDP_HIP_K_LIN_FIRST);
@@ -841,14 +841,14 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, uint32_t stages) {
         const int nv = (int)d.nv;
         const int64_t TRI = (int64_t)nv * (nv - 1) / 2, Pv = (int64_t)nv * nv + TRI, Pu = 2 * (int64_t)nv * nv + TRI;
         build_caches();
-        if (ctx->lin_static && getenv("DDP_HIP_NO_STATIC_DIAG") == nullptr) { const int rc_ = lin_static_launch(ctx, p, 4); if (rc_ != DDP_HIP_OK) return rc_; }
+        if (ctx->lin_static) { const int rc_ = lin_static_launch(ctx, p, 4); if (rc_ != DDP_HIP_OK) return rc_; }
         else hipLaunchKernelGGL((lin_diag_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p);
         // torque level first: on the static path its row kernel also forms the diagonal entries of the q and v directions
         if (ctx->lin_static) { const int rc_ = lin_static_launch(ctx, p, 3); if (rc_ != DDP_HIP_OK) return rc_; }
         else hipLaunchKernelGGL((lin_offdiag_kernel<NJ, 3>), dim3(blocks_for(BT * Pu)), dim3(LBS), 0, ctx->stream, p);
         if (ctx->lin_static) { const int rc_ = lin_static_launch(ctx, p, 2); if (rc_ != DDP_HIP_OK) return rc_; }
         else hipLaunchKernelGGL((lin_offdiag_kernel<NJ, 2>), dim3(blocks_for(BT * Pv)), dim3(LBS), 0, ctx->stream, p);
-        if (ctx->lin_static && getenv("DDP_HIP_NO_STATIC_CFG") == nullptr) { const int rc_ = lin_static_launch(ctx, p, 1); if (rc_ != DDP_HIP_OK) return rc_; }
+        if (ctx->lin_static) { const int rc_ = lin_static_launch(ctx, p, 1); if (rc_ != DDP_HIP_OK) return rc_; }
         else hipLaunchKernelGGL((lin_offdiag_kernel<NJ, 1>), dim3(blocks_for(BT * TRI)), dim3(LBS), 0, ctx->stream, p);
       } else {
         hipLaunchKernelGGL((lin_diag_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p);
@@ -941,13 +941,13 @@ int lin_setup(ddp_hip_ctx* ctx) {
   // q-part cache of the mode-2 stencil (tree models with resident tensors only)
   const bool tree = ctx->model_h.kind == DDP_HIP_MODEL_TREE;
   const bool tensors = ctx->model_h.fd_mode == 2 && !(ctx->flags & DDP_HIP_FLAG_NO_TENSORS);
-  const bool want = tree && tensors && !ctx->model_h.ff && getenv("DDP_HIP_NO_QCACHE") == nullptr;   // the caches index q by joint: 1-DoF trees
-  const int topo = (tree && getenv("DDP_HIP_NO_STATIC") == nullptr) ? lin_static_supported(ctx->model_h) : 0;
+  const bool want = tree && tensors && !ctx->model_h.ff && !ctx->sw.no_qcache;   // the caches index q by joint: 1-DoF trees
+  const int topo = (tree && !ctx->sw.no_static) ? lin_static_supported(ctx->model_h) : 0;
   const Dims& d = ctx->d;
   if (want) { ctx->lin_ncfg = (int32_t)d.nv + 1; ctx->lin_nvcfg = 2 * (int32_t)d.nv + 1; }
   else if (topo && ctx->model_h.first_order_fd) { ctx->lin_ncfg = 1; ctx->lin_nvcfg = 1; }   // first order only: base q, base (q, v)
   else if (topo && tree && !ctx->model_h.ff && d.nv > 6 && ctx->model_h.fd_mode == 1 && !(ctx->flags & DDP_HIP_FLAG_NO_TENSORS) &&
-           getenv("DDP_HIP_ANA_OWN_ABA") == nullptr) {
+           !ctx->sw.ana_own_aba) {
     // analytic mode 1: the accelerations of its 2 nv perturbed points come from the static first-order kernels (lin_analytic.hip)
     ctx->lin_ncfg = 1; ctx->lin_nvcfg = 1;
   }
@@ -959,7 +959,7 @@ int lin_setup(ddp_hip_ctx* ctx) {
   if (ctx->lin_static) {
     const int64_t BT = ctx->d.batch * ctx->d.T;
     int64_t slice = 1024;
-    if (const char* ev = getenv("DDP_HIP_QWS_BT")) { const int v = atoi(ev); if (v >= 16 && v <= 65536) slice = v; }   // tuning knob
+    if (ctx->sw.qws_bt) slice = ctx->sw.qws_bt;   // tuning knob
     ctx->lin_qws_bt = BT < slice ? BT : slice;
     HIP_TRY(hipMalloc(&ctx->lin_qws, sizeof(double) * (size_t)(ctx->lin_qws_bt * lin_static_ws_per_bt(ctx->model_h))));
     if (ctx->lin_ncfg > 1) {     // the mode-2 stencil is resident: its configuration level runs slice-pipelined on two streams

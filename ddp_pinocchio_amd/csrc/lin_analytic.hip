@@ -1127,7 +1127,7 @@ int launch_t(ddp_hip_ctx* ctx, const LinParams& p, int stage, int flags) {
     HIP_TRY(hipGetLastError());
     return DDP_HIP_OK;
   }
-  if (!ctx->ana_split) {
+  if (!ctx->sw.ana_split) {
     // fused path: one wave takes an evaluation from the state to its output columns; no T / M workspace
     ap.M0 = ctx->ana_M0;
     if (stage == 0) {
@@ -1146,7 +1146,7 @@ int launch_t(ddp_hip_ctx* ctx, const LinParams& p, int stage, int flags) {
     }
     // config constraint: its x-direction tensors come out of the evaluation waves themselves and eq_uu is exactly zero (f_u does not
     // depend on u and C is constant: ana_eq_kernel forms the same sum twice and differences it) -- no workspace, no slices
-    const bool eq_inline = do_eq && ctx->model_h.eq_kind == DDP_HIP_EQ_CONFIG && getenv("DDP_HIP_ANA_EQ_KERNEL") == nullptr;
+    const bool eq_inline = do_eq && ctx->model_h.eq_kind == DDP_HIP_EQ_CONFIG && !ctx->sw.ana_eq_kernel;
     if (eq_inline) {
       ap.Fws = nullptr;
       ap.eq_inline = 1;
@@ -1186,15 +1186,14 @@ int lin_analytic_setup(ddp_hip_ctx* ctx) {
   if (ctx->model_h.max_level_width > AW) return DDP_HIP_E_UNSUPPORTED;
   const int64_t BT = d.batch * d.T;
   int64_t slice = 256;
-  if (const char* ev = getenv("DDP_HIP_ANA_BT")) { const int v = atoi(ev); if (v >= 1 && v <= 65536) slice = v; }   // tuning knob
+  if (ctx->sw.ana_bt) slice = ctx->sw.ana_bt;   // tuning knob
   ctx->ana_nbt = BT < slice ? BT : slice;
   const int64_t N = d.nv;
   // the stage-0 and stage-1 launches of one linearisation share the workspace: the base point keeps slot 0 of every pair
-  ctx->ana_split = getenv("DDP_HIP_ANA_SPLIT") != nullptr;    // development: the three-kernel form with its HBM workspaces
   const bool m1 = ctx->model_h.fd_mode == 1 && !(ctx->flags & DDP_HIP_FLAG_NO_TENSORS);
-  if (ctx->ana_split) HIP_TRY(hipMalloc(&ctx->ana_T, sizeof(double) * (size_t)(ctx->ana_nbt * (2 * N + 1) * N * 2 * N)));
-  if (ctx->ana_split || (m1 && d.Etot > 0)) HIP_TRY(hipMalloc(&ctx->ana_M, sizeof(double) * (size_t)(ctx->ana_nbt * (N + 1) * N * N)));
-  if (!ctx->ana_split && m1) HIP_TRY(hipMalloc(&ctx->ana_M0, sizeof(double) * (size_t)(BT * N * N)));
+  if (ctx->sw.ana_split) HIP_TRY(hipMalloc(&ctx->ana_T, sizeof(double) * (size_t)(ctx->ana_nbt * (2 * N + 1) * N * 2 * N)));
+  if (ctx->sw.ana_split || (m1 && d.Etot > 0)) HIP_TRY(hipMalloc(&ctx->ana_M, sizeof(double) * (size_t)(ctx->ana_nbt * (N + 1) * N * N)));
+  if (!ctx->sw.ana_split && m1) HIP_TRY(hipMalloc(&ctx->ana_M0, sizeof(double) * (size_t)(BT * N * N)));
   if (ctx->lin_static && ctx->lin_ws && ctx->model_h.fd_mode == 1 && !(ctx->flags & DDP_HIP_FLAG_NO_TENSORS))
     HIP_TRY(hipMalloc(&ctx->ana_A, sizeof(double) * (size_t)(BT * (3 * N + 1) * N)));
   if (d.Etot > 0) {

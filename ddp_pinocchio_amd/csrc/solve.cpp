@@ -12,8 +12,9 @@
 #include <vector>
 
 #include "ddp_hip/ddp_hip.h"
+#include "internal.h"
 
-// ddp_hip_ctx is opaque here: only the public C-ABI is used
+// only the public C-ABI is used on the context, and its development switches are read (DevSwitches)
 extern "C" int ddp_hip_solve(ddp_hip_ctx* ctx, const ddp_hip_solver_params* sp, ddp_hip_solve_log* log) {
   if (!ctx || !sp || !log || sp->max_iterations < 0 || sp->n_alpha < 1) return DDP_HIP_E_ARG;
   const int64_t B = ddp_hip_batch(ctx);
@@ -34,7 +35,7 @@ extern "C" int ddp_hip_solve(ddp_hip_ctx* ctx, const ddp_hip_solver_params* sp, 
 
   SOLVE_TRY(ddp_hip_set_active(ctx, nullptr));
   // the loop enqueues: only the calls that return values to the rules below wait for the device (ddp_hip_set_async)
-  SOLVE_TRY(ddp_hip_set_async(ctx, getenv("DDP_HIP_SOLVE_SYNC") ? 0 : 1));   // (DDP_HIP_SOLVE_SYNC: development A/B, every call waits as in round 2)
+  SOLVE_TRY(ddp_hip_set_async(ctx, ctx->sw.solve_sync ? 0 : 1));   // (DDP_HIP_SOLVE_SYNC: development A/B, every call waits as in round 2)
   SOLVE_TRY(ddp_hip_linearize(ctx));                                                        // :768
   tmp_reg = reg;
   SOLVE_TRY(ddp_hip_backward(ctx, tmp_reg.data(), mu.data(), nullptr, sp->max_restarts));   // :769-771 (mu is taken, reg is not)

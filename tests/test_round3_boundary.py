@@ -93,16 +93,38 @@ def test_shard_pick_and_broadcast_single_rank(gpu, with_comm):
             comm.close()
 
 
+def _context(capi, spec, monkeypatch, switch=None):
+    """a traced context, created with the development switch `switch` set: a context reads the switches once, when it is
+    created, so the switch is cleared again right away"""
+    if switch:
+        monkeypatch.setenv(switch, "1")
+    try:
+        return capi.Context(spec, flags=capi.FLAG_TRACE)
+    finally:
+        if switch:
+            monkeypatch.delenv(switch)
+
+
+def _dense_bytes(o):
+    return 8 * (o.n ** 3 + o.n * o.n * o.m + o.n * o.m * o.m)
+
+
 @pytest.mark.gpu
 def test_backward_reads_one_of_each_mirrored_half_slab_bit_for_bit(gpu, monkeypatch):
     """Mode-2 tensors are symmetric in their two input indices bit for bit (the stencil writes one value to both entries,
     problem.hpp:283-292).  K3 then skips the half-slab f_xx(:, 0:m, c) of the columns c >= m and takes its contraction from
     the mirror image (bwd_split.h, job kind 2): the sweep must give the very same gains and value function, bit for bit, as
-    with every half-slab read (DDP_HIP_K3_NO_SYM=1) -- and uploaded tensors (no symmetry known) take the full path."""
+    a context created with every half-slab read (DDP_HIP_K3_NO_SYM=1) -- whose stencil writes the mirror images that the
+    default context's download fills in, the same bits -- and uploaded tensors (no symmetry known) take the full path."""
     capi = gpu
     T = 5
     model, spec, o = make("tree38", T, batch=2, fd_mode=2)
-    with capi.Context(spec, flags=capi.FLAG_TRACE) as ctx:
+
+    def sweep(ctx):
+        rc, reg, mu, rs = ctx.backward(0.0, 1.0)
+        return ctx.download("FB_JAC"), ctx.download("FB_VAL"), ctx.download("VX_TRACE"), ctx.download("VXX_TRACE"), rs
+
+    def run(ctx):
         for b in range(2):
             x0, us, xs = initial_trajectory(o, model, seed=60 + b, u_sigma=0.4)
             ctx.upload("X", xs, b, 1); ctx.upload("U", us, b, 1)
@@ -110,22 +132,23 @@ def test_backward_reads_one_of_each_mirrored_half_slab_bit_for_bit(gpu, monkeypa
         # a V_x that is not zero: terminal cost gradient
         ctx.upload("LFX", np.random.default_rng(1).normal(size=(2, o.n)))
         ctx.upload("LFXX", np.tile(np.eye(o.n).reshape(-1), (2, 1)))
-        fxx = ctx.download("FXX")[0].reshape(T, o.n, o.n, o.n)                   # [t][k][j][i]
-        assert np.array_equal(fxx, fxx.transpose(0, 2, 1, 3)), "mode-2 f_xx is symmetric bit for bit"
+        out = sweep(ctx)
+        return out, [ctx.download(s) for s in ("FXX", "FUX", "FUU")]
 
-        def sweep():
-            rc, reg, mu, rs = ctx.backward(0.0, 1.0)
-            return ctx.download("FB_JAC"), ctx.download("FB_VAL"), ctx.download("VX_TRACE"), ctx.download("VXX_TRACE"), rs
-        sym = sweep()
-        monkeypatch.setenv("DDP_HIP_K3_NO_SYM", "1")
-        full = sweep()
-        monkeypatch.delenv("DDP_HIP_K3_NO_SYM")
+    with _context(capi, spec, monkeypatch) as ctx, _context(capi, spec, monkeypatch, "DDP_HIP_K3_NO_SYM") as ctx_full:
+        sym, tensors = run(ctx)
+        fxx = tensors[0][0].reshape(T, o.n, o.n, o.n)                           # [t][k][j][i]
+        assert np.array_equal(fxx, fxx.transpose(0, 2, 1, 3)), "mode-2 f_xx is symmetric bit for bit"
+        full, tensors_full = run(ctx_full)
+        assert ctx_full.bwd_stream_bytes() == _dense_bytes(o)
+        for a_, b_ in zip(tensors, tensors_full):
+            assert np.array_equal(a_, b_)
         for a_, b_ in zip(sym, full):
             assert np.array_equal(a_, b_)
         assert float(np.max(np.abs(sym[2]))) > 0
         # tensors from outside: the flag drops (the same values here, so the answer is still the same)
         ctx.upload("FXX", ctx.download("FXX"))
-        again = sweep()
+        again = sweep(ctx)
         for a_, b_ in zip(sym, again):
             assert np.array_equal(a_, b_)
 
@@ -163,29 +186,32 @@ def test_constrained_and_free_flyer_problems_take_the_latency_forward_kernel(gpu
 @pytest.mark.gpu
 def test_k3h_bit_for_bit_at_size(gpu, monkeypatch):
     """the same at BASELINE's size: T = 200, the benchmark's inputs (x0 neutral, u ~ N(0, 0.1^2)) plus a terminal gradient so
-    that V_x != 0 along the whole horizon; K3h against the dense kernel at every step of four instances"""
+    that V_x != 0 along the whole horizon; K3h against the dense kernel (a context created with DDP_HIP_K3_NO_SYM=1) at every
+    step of four instances.  The two contexts run one after the other: each holds about 5 GB of tensors."""
     capi = gpu
     T, B = 200, 4
     model, spec, o = make("tree38", T, batch=B, fd_mode=2)
-    with capi.Context(spec, flags=capi.FLAG_TRACE) as ctx:
+
+    def run(ctx):
         us = np.stack([0.1 * np.random.default_rng(0xDD9000 + 3000 + g).normal(size=T * o.m) for g in range(B)])
         ctx.upload("X", np.zeros((B, (T + 1) * o.nx))); ctx.upload("U", us)
         ctx.rollout()
         ctx.linearize()
         ctx.upload("LFX", 0.1 * np.random.default_rng(7).normal(size=(B, o.n)))
         ctx.upload("LFXX", np.tile(np.eye(o.n).reshape(-1), (B, 1)))
-        assert ctx.bwd_stream_bytes() < 0.4 * 8 * (o.n ** 3 + o.n * o.n * o.m + o.n * o.m * o.m)     # K3h is what runs
+        nbytes = ctx.bwd_stream_bytes()
+        rc, reg, mu, rs = ctx.backward(0.0, 1.0, 8)
+        return nbytes, (ctx.download("FB_JAC"), ctx.download("FB_VAL"), ctx.download("VX_TRACE"), rs, reg, mu)
 
-        def sweep():
-            rc, reg, mu, rs = ctx.backward(0.0, 1.0, 8)
-            return ctx.download("FB_JAC"), ctx.download("FB_VAL"), ctx.download("VX_TRACE"), rs, reg, mu
-        half = sweep()
-        monkeypatch.setenv("DDP_HIP_K3_NO_SYM", "1")
-        dense = sweep()
-        monkeypatch.delenv("DDP_HIP_K3_NO_SYM")
-        for a_, b_ in zip(half, dense):
-            assert np.array_equal(a_, b_)
-        assert np.all(np.isfinite(half[0])) and float(np.max(np.abs(half[2]))) > 0
+    with _context(capi, spec, monkeypatch) as ctx:
+        nbytes, half = run(ctx)
+    assert nbytes < 0.4 * _dense_bytes(o)                                        # K3h is what runs
+    with _context(capi, spec, monkeypatch, "DDP_HIP_K3_NO_SYM") as ctx:
+        nbytes_dense, dense = run(ctx)
+    assert nbytes_dense == _dense_bytes(o)
+    for a_, b_ in zip(half, dense):
+        assert np.array_equal(a_, b_)
+    assert np.all(np.isfinite(half[0])) and float(np.max(np.abs(half[2]))) > 0
 
 
 @pytest.mark.gpu
@@ -193,38 +219,50 @@ def test_k3h_on_analytic_mode1_tensors_bit_for_bit(gpu, monkeypatch):
     """Analytic mode 1 (lin_analytic.hip) leaves tensors with a structure of its own: the configuration rows of every f_xx / f_ux
     column are zeros it wrote itself (q+ = q + dt v has constant jacobian rows) and f_uu is zero (M^-1 does not depend on u), but
     f_xx is NOT symmetric (a forward difference of jacobians).  K3h then reads the lower half of every column and nothing of
-    f_uu (half_mode 2): the sweep must match the dense kernel (DDP_HIP_K3_NO_HALF=1) bit for bit, and uploaded tensors must
-    drop the assumption."""
+    f_uu (half_mode 2): the sweep must match the dense kernel (a context created with DDP_HIP_K3_NO_HALF=1) bit for bit, and
+    uploaded tensors must drop the assumption."""
     capi = gpu
     T, B = 12, 3
     model, spec, o = make("tree38", T, batch=B, fd_mode=1, first_order_fd=0)
-    full_bytes = 8 * (o.n ** 3 + o.n * o.n * o.m + o.n * o.m * o.m)
-    with capi.Context(spec, flags=capi.FLAG_TRACE) as ctx:
+    full_bytes = _dense_bytes(o)
+
+    def sweep(ctx):
+        rc, reg, mu, rs = ctx.backward(0.0, 1.0, 8)
+        return ctx.download("FB_JAC"), ctx.download("FB_VAL"), ctx.download("VX_TRACE"), rs, reg, mu
+
+    def inputs(ctx):
         us = np.stack([0.1 * np.random.default_rng(500 + g).normal(size=T * o.m) for g in range(B)])
         ctx.upload("X", np.zeros((B, (T + 1) * o.nx))); ctx.upload("U", us)
         ctx.rollout()
-        assert ctx.bwd_stream_bytes() == full_bytes                               # nothing known about the tensors yet
-        ctx.linearize()
-        assert ctx.bwd_stream_bytes() == 8 * (o.n * o.n + o.n * o.m) * (o.n - o.m)
-        fxx = ctx.download("FXX")[0].reshape(T, o.n, o.n, o.n)                    # [t][i][j][k]
-        fux = ctx.download("FUX")[0].reshape(T, o.n, o.m, o.n)
-        assert not np.any(fxx[..., :o.m]) and not np.any(fux[..., :o.m]) and not np.any(ctx.download("FUU"))
-        assert not np.array_equal(fxx, fxx.transpose(0, 2, 1, 3))
+
+    def gradient(ctx):
         ctx.upload("LFX", 0.1 * np.random.default_rng(7).normal(size=(B, o.n)))
         ctx.upload("LFXX", np.tile(np.eye(o.n).reshape(-1), (B, 1)))
 
-        def sweep():
-            rc, reg, mu, rs = ctx.backward(0.0, 1.0, 8)
-            return ctx.download("FB_JAC"), ctx.download("FB_VAL"), ctx.download("VX_TRACE"), rs, reg, mu
-        half = sweep()
-        monkeypatch.setenv("DDP_HIP_K3_NO_HALF", "1")
-        dense = sweep()
-        monkeypatch.delenv("DDP_HIP_K3_NO_HALF")
+    with _context(capi, spec, monkeypatch) as ctx, _context(capi, spec, monkeypatch, "DDP_HIP_K3_NO_HALF") as ctx_dense:
+        inputs(ctx)
+        assert ctx.bwd_stream_bytes() == full_bytes                               # nothing known about the tensors yet
+        ctx.linearize()
+        assert ctx.bwd_stream_bytes() == 8 * (o.n * o.n + o.n * o.m) * (o.n - o.m)
+        tensors = [ctx.download(s) for s in ("FXX", "FUX", "FUU")]
+        fxx = tensors[0][0].reshape(T, o.n, o.n, o.n)                             # [t][i][j][k]
+        fux = tensors[1][0].reshape(T, o.n, o.m, o.n)
+        assert not np.any(fxx[..., :o.m]) and not np.any(fux[..., :o.m]) and not np.any(tensors[2])
+        assert not np.array_equal(fxx, fxx.transpose(0, 2, 1, 3))
+        gradient(ctx)
+        half = sweep(ctx)
+        inputs(ctx_dense)
+        ctx_dense.linearize()
+        assert ctx_dense.bwd_stream_bytes() == full_bytes
+        for a_, b_ in zip(tensors, [ctx_dense.download(s) for s in ("FXX", "FUX", "FUU")]):
+            assert np.array_equal(a_, b_)
+        gradient(ctx_dense)
+        dense = sweep(ctx_dense)
         for a_, b_ in zip(half, dense):
             assert np.array_equal(a_, b_)
         assert np.all(np.isfinite(half[0])) and float(np.max(np.abs(half[2]))) > 0
         ctx.upload("FUX", ctx.download("FUX"))                                    # tensors from outside: the full read again
         assert ctx.bwd_stream_bytes() == full_bytes
-        again = sweep()
+        again = sweep(ctx)
         for a_, b_ in zip(half, again):
             assert np.array_equal(a_, b_)

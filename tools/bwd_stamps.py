@@ -8,7 +8,6 @@ sys.path.insert(0, ROOT)
 from ddp_pinocchio_amd import capi
 capi.LIB_PATH = os.path.join(ROOT, "build_ab", "libddp_hip_stamps.so")
 sys.argv = ["x", "--batch", "64", "--reps", "1"]
-os.environ.setdefault("DDP_HIP_BWD_GROUPS", "1")
 exec(open(os.path.join(ROOT, "tools", "dev_bwd_timing.py")).read())
 out = (C.c_ulonglong * 32)()
 assert capi.lib().ddp_hip_debug_stamps(out) == 0
