@@ -251,10 +251,11 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
       if (mo.parent[i] >= i || mo.parent[i] < -1) return DDP_HIP_E_ARG;
       if (i > 0 && mo.jtype[i] != DDP_HIP_JOINT_REVOLUTE && mo.jtype[i] != DDP_HIP_JOINT_PRISMATIC) return DDP_HIP_E_ARG;   // one free flyer, at the root
     }
-    // Lie-group configurations: forward-differenced jacobians (the north star) and mode 2 / tensor-free only -- the
-    // reference's mode 1 asserts nq == nv itself (problem.hpp:78-81); the config constraint subtracts configurations
-    // (problem.hpp:785-790), meaningless on a quaternion: frame constraints only
-    if (ff && (!prob->first_order_fd || prob->fd_mode == 1 || prob->eq_kind == DDP_HIP_EQ_CONFIG)) return DDP_HIP_E_UNSUPPORTED;
+    // Lie-group configurations: forward-differenced (the north star) or analytic jacobians (lin_analytic.hip:
+    // ana_ff_first_kernel, the reference's own first order), mode 0 / mode 2 / tensor-free only -- the reference's mode 1
+    // asserts nq == nv itself (problem.hpp:78-81); the config constraint subtracts configurations (problem.hpp:785-790),
+    // meaningless on a quaternion: frame constraints only
+    if (ff && (prob->fd_mode == 1 || prob->eq_kind == DDP_HIP_EQ_CONFIG)) return DDP_HIP_E_UNSUPPORTED;
   }
   int ndev = ddp_hip_device_count();
   if (ndev <= 0) return DDP_HIP_E_NODEVICE;

@@ -158,6 +158,59 @@ __device__ void se3_Jlog(const double* nu, double* J) {
     for (int j = 0; j < 3; ++j) { J[6 * i + j] = Ji[3 * i + j]; J[6 * (i + 3) + j + 3] = Ji[3 * i + j]; J[6 * i + j + 3] = -T2[3 * i + j]; }
 }
 
+// d(q (+) nu)/dq in the tangent at q (+) nu (pinocchio dIntegrate ARG0, oracle/ddp_oracle.c:orc_d_integrate_dq): Ad(exp6(nu)^-1)
+// on twists ordered [linear; angular] = [R^T, -R^T [p]x; 0, R^T], (R, p) = exp6(nu).  Row-major 6 x 6.
+__device__ void se3_d_integrate_dq(const double* nu, double* D) {
+  const double* v = nu; const double* w = nu + 3;
+  double b, c, d, pe[3], qe[4], R[9], P[9], RtP[9];
+  so3_coeffs(w[0] * w[0] + w[1] * w[1] + w[2] * w[2], b, c, d);
+  so3_apply(w, b, c, v, pe);
+  quat_exp(w, qe);
+  quat_to_R(qe, R);
+  skew(pe, P);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) RtP[3 * i + j] = R[i] * P[j] + R[3 + i] * P[3 + j] + R[6 + i] * P[6 + j];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      D[6 * i + j] = R[3 * j + i];
+      D[6 * (i + 3) + j + 3] = R[3 * j + i];
+      D[6 * i + j + 3] = -RtP[3 * i + j];
+      D[6 * (i + 3) + j] = 0.0;
+    }
+}
+// d(q (+) nu)/dnu in the tangent at q (+) nu (pinocchio dIntegrate ARG1 = Jexp6(nu) = Jlog6(exp6(nu))^-1; the oracle inverts
+// se3_Jlog numerically).  se3_Jlog is [A, -B; 0, A] with A = Jlog3(w), so its inverse is [Ar, Ar B Ar; 0, Ar] with
+// Ar = A^-1 = Jexp3(w) = I - b [w]x + c [w]x^2 (so3_coeffs).  Row-major 6 x 6.
+__device__ void se3_d_integrate_dv(const double* nu, double* D) {
+  const double* w = nu + 3;
+  double Jl[36], b, c, d, W[9], W2[9], Ar[9], B[9], T1[9], T2[9];
+  se3_Jlog(nu, Jl);
+  so3_coeffs(w[0] * w[0] + w[1] * w[1] + w[2] * w[2], b, c, d);
+  skew(w, W);
+  mm3(W, W, W2);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) Ar[k] = -b * W[k] + c * W2[k];
+  Ar[0] += 1; Ar[4] += 1; Ar[8] += 1;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) B[3 * i + j] = -Jl[6 * i + j + 3];
+  mm3(Ar, B, T1); mm3(T1, Ar, T2);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      D[6 * i + j] = Ar[3 * i + j];
+      D[6 * (i + 3) + j + 3] = Ar[3 * i + j];
+      D[6 * i + j + 3] = T2[3 * i + j];
+      D[6 * (i + 3) + j] = 0.0;
+    }
+}
+
 // ---- state level (x = [q(nq); v(nv)], tangent dimension 2 nv) -----------------------------------------------------------
 // x (+) eps e_idx in place: dynamics_t::integrate_x (problem.hpp:395-401) for a single tangent direction
 __device__ __forceinline__ void perturb_x(const DevModel& m, double* x, int idx, double eps) {

@@ -890,7 +890,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, uint32_t stages) {
       }
     }
     if (chained) {
-    } else if (ana_large) {
+    } else if (ana_large && !ctx->model_h.ff) {
       // analytic jacobians: base point from the resident f_x, f_u, then the tensors
       { const int rc_ = lin_analytic_launch(ctx, p, 0, LIN_ANA_EQ); if (rc_ != DDP_HIP_OK) return rc_; }
       if (p.has_tensors) {
@@ -910,12 +910,16 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, uint32_t stages) {
         }
       }
     } else {
-      // large models, forward-differenced jacobians: chain rule as three kernels; mode-2 second order reuses the per-point kernel
+      // large models with forward-differenced jacobians, and free-flyer models with analytic ones (their jacobians at the
+      // look-ahead states from lin_analytic.hip): chain rule as three kernels; mode-2 second order reuses the per-point kernel
       if (!p.eq_xk) return DDP_HIP_E_UNSUPPORTED;
       const int K = ctx->model_h.eq_advance;
       if (K < 1) return DDP_HIP_E_UNSUPPORTED;
       hipLaunchKernelGGL((eq_chain_kernel<NJ>), dim3(blocks_for(BT)), dim3(LBS), 0, ctx->stream, p);
-      if (K > 1) hipLaunchKernelGGL((eq_fdjac_kernel<NJ>), dim3(blocks_for(BT * (K - 1) * d.n)), dim3(LBS), 0, ctx->stream, p);
+      if (K > 1) {
+        if (ctx->model_h.first_order_fd) hipLaunchKernelGGL((eq_fdjac_kernel<NJ>), dim3(blocks_for(BT * (K - 1) * d.n)), dim3(LBS), 0, ctx->stream, p);
+        else { const int rc_ = lin_analytic_ff_lookahead(ctx, p); if (rc_ != DDP_HIP_OK) return rc_; }
+      }
       hipLaunchKernelGGL(eq_combine_kernel, dim3((unsigned)BT), dim3(256), sizeof(double) * (size_t)(2 * d.emax * d.n), ctx->stream, p);
       if (p.has_tensors) {
         if (fd_mode == 2) {
@@ -980,7 +984,7 @@ int lin_setup(ddp_hip_ctx* ctx) {
     if (rc_ != DDP_HIP_OK) return rc_;
   }
   // look-ahead states / jacobians of the constraint chain on large models
-  if (ctx->d.Etot > 0 && tree && ctx->model_h.first_order_fd) {
+  if (ctx->d.Etot > 0 && tree && (ctx->model_h.first_order_fd || ctx->model_h.ff)) {
     const Dims& d = ctx->d;
     const int64_t K = ctx->model_h.eq_advance;
     const size_t words = (size_t)(d.batch * d.T * (K * d.nx + (K > 1 ? K - 1 : 0) * d.n * d.n + d.emax * d.n));

@@ -16,6 +16,8 @@
 //                     constraint_advance_time_t::first_order_deriv (problem.hpp:569-605) on the analytic jacobians, at the
 //                     trajectory point (eq_val, eq_x, eq_u) and -- mode 1 -- at x (+) eps e_i, u + eps e_i, differenced into
 //                     eq_xx, eq_ux, eq_uu (problem.hpp:67-150 with Fn = the constraint chain, :611-620)
+// Models with a free-flyer root take ana_ff_first_kernel instead (first order only, one wave per point: rbd_deriv.h,
+// ff_derivatives_wave); their constraint chain is lin.hip's three-kernel form fed with its jacobians at the look-ahead states.
 #include <float.h>
 #include <math.h>
 #include <stdint.h>
@@ -1073,6 +1075,70 @@ __global__ __launch_bounds__(AW) void ana_eq_kernel(AnaParams ap) {
   }
 }
 
+// ---- free-flyer root (rbd_deriv.h: ff_derivatives_wave), first order only ----------------------------------------------------
+// One wave per point.  which == 0: the trajectory points (f_x, f_u); which == 1: the look-ahead states x_1 .. x_{K-1} of the
+// constraint chain (lin.hip: eq_chain_kernel), f_x into its workspace for eq_combine_kernel.  dynamics_t::first_order_deriv
+// (problem.hpp:463-503) on the group:
+//   f_x = [dInt_dq(q, dt v), dt dInt_dv(q, dt v); dt da/dq, I + dt da/dv],  f_u = [0; dt M^-1]
+// dInt_dq / dInt_dv are the identity off the root's 6 x 6 block (lie.h: se3_d_integrate_dq / dv).
+template <int NJ>
+__global__ __launch_bounds__(AW) void ana_ff_first_kernel(LinParams p, int which) {
+  const DevModel& m = *p.model;
+  const int N = m.nv, n = 2 * N, nq = m.nq, K = m.eq_advance;
+  const int64_t T = p.d.T;
+  const int64_t e = blockIdx.x;
+  const int lane = threadIdx.x;
+  int64_t bt;
+  const double* x;
+  double *fx, *fu = nullptr;
+  if (which == 0) {
+    bt = e;
+    const int b = (int)(bt / T);
+    x = p.x + ((int64_t)b * (T + 1) + bt % T) * p.d.nx;
+    fx = p.fx + bt * (int64_t)n * n;
+    fu = p.fu + bt * (int64_t)n * N;
+  } else {
+    const int k = (int)(e % (K - 1));
+    bt = e / (K - 1);
+    if (p.ne[bt % T] == 0) return;
+    x = p.eq_xk + (bt * K + k) * p.d.nx;                  // x_{k+1}
+    fx = p.eq_fxk + (bt * (K - 1) + k) * (int64_t)n * n;
+  }
+  const double* u = p.u + bt * N;
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  rbdd::ff_derivatives_wave<NJ>(m, x, x + nq, u, lds, lane);
+  const double dt = m.dt;
+  double* s_top = lds + rbdd::FfLds<NJ>::COL;             // the root blocks of dInt_dq, dInt_dv (the column records are spent)
+  if (lane < 2) {
+    double nu[6];
+    for (int k = 0; k < 6; ++k) nu[k] = dt * x[nq + k];
+    if (lane == 0) lie::se3_d_integrate_dq(nu, s_top); else lie::se3_d_integrate_dv(nu, s_top + 36);
+  }
+  __syncthreads();
+  // rows 0 .. nv-1 (configuration), column by column: lane = row
+  for (int j = 0; j < n; ++j) {
+    for (int r = lane; r < N; r += AW) {
+      const int jj = j < N ? j : j - N;
+      double val;
+      if (r < 6 && jj < 6) val = j < N ? s_top[6 * r + jj] : s_top[36 + 6 * r + jj] * dt;
+      else val = r == jj ? (j < N ? 1.0 : 1.0 * dt) : 0.0;
+      fx[r + (int64_t)j * n] = val;
+    }
+  }
+  // rows nv .. 2nv-1 (velocity)
+  for (int j = 0; j < n; ++j) {
+    for (int r = lane; r < N; r += AW) {
+      const double da = rbdd::ff_minv_T<NJ>(lds, N, r, j);
+      fx[N + r + (int64_t)j * n] = j < N ? da * dt : da * dt + (r == j - N ? 1.0 : 0.0);
+    }
+  }
+  if (fu) {
+    const double* s_X = lds + rbdd::FfLds<NJ>::X;
+    for (int j = 0; j < N; ++j)
+      for (int r = lane; r < n; r += AW) fu[r + (int64_t)j * n] = r < N ? 0.0 : s_X[(r - N) + j * N] * dt;
+  }
+}
+
 template <int NJ>
 size_t eq_lds_bytes(const Dims& d, bool no_aba = false) { return sizeof(double) * (size_t)((no_aba ? 0 : rbd::ABA_LDS_SLOTS * NJ) + 4 * NJ + d.emax * NJ); }
 
@@ -1182,7 +1248,17 @@ int launch_t(ddp_hip_ctx* ctx, const LinParams& p, int stage, int flags) {
 
 int lin_analytic_setup(ddp_hip_ctx* ctx) {
   const Dims& d = ctx->d;
-  if (ctx->model_h.kind != DDP_HIP_MODEL_TREE || ctx->model_h.first_order_fd || d.nv <= 6) return DDP_HIP_OK;
+  if (ctx->model_h.kind != DDP_HIP_MODEL_TREE || ctx->model_h.first_order_fd) return DDP_HIP_OK;
+  if (ctx->model_h.ff) {
+    // free-flyer root: first order only (mode 1 is refused at ddp_hip_create); the constraint chain runs on lin.hip's three
+    // kernels with these jacobians at the look-ahead states
+    if (d.nv > 38) return DDP_HIP_E_UNSUPPORTED;
+    ctx->ana_nbt = d.batch * d.T;
+    const size_t lds = sizeof(double) * (size_t)rbdd::FfLds<38>::TOTAL;
+    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ana_ff_first_kernel<38>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return DDP_HIP_OK;
+  }
+  if (d.nv <= 6) return DDP_HIP_OK;
   if (ctx->model_h.max_level_width > AW) return DDP_HIP_E_UNSUPPORTED;
   const int64_t BT = d.batch * d.T;
   int64_t slice = 256;
@@ -1213,6 +1289,16 @@ int lin_analytic_setup(ddp_hip_ctx* ctx) {
   return DDP_HIP_OK;
 }
 
+// f_x at the look-ahead states x_1 .. x_{K-1} of a free-flyer model's constraint chain (lin.hip: eq_chain_kernel wrote them)
+int lin_analytic_ff_lookahead(ddp_hip_ctx* ctx, const LinParams& p) {
+  const int K = ctx->model_h.eq_advance;
+  if (K < 2) return DDP_HIP_OK;
+  const size_t lds = sizeof(double) * (size_t)rbdd::FfLds<38>::TOTAL;
+  hipLaunchKernelGGL((ana_ff_first_kernel<38>), dim3((unsigned)(ctx->d.batch * ctx->d.T * (K - 1))), dim3(AW), lds, ctx->stream, p, 1);
+  HIP_TRY(hipGetLastError());
+  return DDP_HIP_OK;
+}
+
 void lin_analytic_teardown(ddp_hip_ctx* ctx) {
   if (ctx->ana_T) (void)hipFree(ctx->ana_T);
   if (ctx->ana_M) (void)hipFree(ctx->ana_M);
@@ -1224,6 +1310,13 @@ void lin_analytic_teardown(ddp_hip_ctx* ctx) {
 int lin_analytic_launch(ddp_hip_ctx* ctx, const LinParams& p, int stage, int flags) {
   if (ctx->ana_nbt <= 0) return DDP_HIP_E_UNSUPPORTED;   // lin_analytic_setup did not take this model
   if (stage == 1 && !p.has_tensors) return DDP_HIP_OK;
+  if (ctx->model_h.ff) {
+    if (stage != 0 || !(flags & LIN_ANA_F)) return DDP_HIP_E_UNSUPPORTED;
+    const size_t lds = sizeof(double) * (size_t)rbdd::FfLds<38>::TOTAL;
+    hipLaunchKernelGGL((ana_ff_first_kernel<38>), dim3((unsigned)(ctx->d.batch * ctx->d.T)), dim3(AW), lds, ctx->stream, p, 0);
+    HIP_TRY(hipGetLastError());
+    return DDP_HIP_OK;
+  }
   if (ctx->d.nv <= 38) return launch_t<38>(ctx, p, stage, flags);
   return launch_t<64>(ctx, p, stage, flags);
 }

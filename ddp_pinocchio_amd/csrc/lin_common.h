@@ -45,3 +45,5 @@ void lin_analytic_teardown(ddp_hip_ctx* ctx);
 constexpr int LIN_ANA_F = 1, LIN_ANA_EQ = 2;
 constexpr int LIN_ANA_ACCEL = 4;   // stage 0: the mode-1 pass follows in this linearisation call -- form its accelerations now and take the trajectory point's from them
 int lin_analytic_launch(ddp_hip_ctx* ctx, const LinParams& p, int stage, int flags);
+// free-flyer models: analytic f_x at the constraint chain's look-ahead states x_1 .. x_{K-1} (after lin.hip: eq_chain_kernel)
+int lin_analytic_ff_lookahead(ddp_hip_ctx* ctx, const LinParams& p);

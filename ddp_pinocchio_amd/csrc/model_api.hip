@@ -50,6 +50,21 @@ __global__ void model_aba_deriv_kernel(const DevModel* m, const double* in, doub
   rbdd::aba_derivatives_lane<NJ>(*m, q, v, tau, a, out, out + nv * nv, out + 2 * nv * nv);
 }
 
+// free-flyer root: the wave-cooperative recursion of the batched kernels (rbd_deriv.h: ff_derivatives_wave), one work-group
+template <int NJ>
+__global__ __launch_bounds__(64) void model_aba_deriv_ff_kernel(const DevModel* m, const double* in, double* out) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int nv = m->nv, nq = m->nq;
+  rbdd::ff_derivatives_wave<NJ>(*m, in, in + nq, in + nq + nv, lds, threadIdx.x);
+  const double* X = lds + rbdd::FfLds<NJ>::X;
+  for (int r = threadIdx.x; r < nv; r += blockDim.x)
+    for (int c = 0; c < nv; ++c) {
+      out[r + c * nv] = rbdd::ff_minv_T<NJ>(lds, nv, r, c);
+      out[nv * nv + r + c * nv] = rbdd::ff_minv_T<NJ>(lds, nv, r, nv + c);
+      out[2 * nv * nv + r + c * nv] = X[r + c * nv];
+    }
+}
+
 template <int NJ>
 __global__ void model_frame_kernel(const DevModel* m, const double* in, double* out, int want_jac) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -77,7 +92,13 @@ int run(ddp_hip_model_handle* h, const double* in, size_t n_in, double* out, siz
   } else if (what == 1) {
     // one lane holds the whole recursion in private memory: 38 joints is what its frame allows (the batched kernels of
     // lin_analytic.hip have no such limit)
-    if (nv <= 6) hipLaunchKernelGGL((model_aba_deriv_kernel<6>), dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o);
+    if (h->model_h.ff) {
+      if (nv > 38) return DDP_HIP_E_UNSUPPORTED;
+      const size_t lds = sizeof(double) * (size_t)rbdd::FfLds<38>::TOTAL;
+      if (lds > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&model_aba_deriv_ff_kernel<38>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL((model_aba_deriv_ff_kernel<38>), dim3(1), dim3(64), lds, h->stream, h->model_d, h->buf_d, o);
+    } else if (nv <= 6) hipLaunchKernelGGL((model_aba_deriv_kernel<6>), dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o);
     else if (nv <= 38) hipLaunchKernelGGL((model_aba_deriv_kernel<38>), dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o);
     else return DDP_HIP_E_UNSUPPORTED;
   } else {
@@ -146,14 +167,13 @@ extern "C" int ddp_hip_model_aba(ddp_hip_model_handle* h, const double* q, const
 extern "C" int ddp_hip_model_aba_derivatives(ddp_hip_model_handle* h, const double* q, const double* v, const double* tau,
                                              double* dq, double* dv, double* dtau) {
   if (!h || !q || !v || !tau || !dq || !dv || !dtau) return DDP_HIP_E_ARG;
-  if (h->model_h.ff) return DDP_HIP_E_UNSUPPORTED;        // analytic partials: vector-space configurations (as the reference's mode 1)
-  const int nv = h->model_h.nv;
-  double in[3 * DDP_MAXJ];
-  memcpy(in, q, sizeof(double) * nv); memcpy(in + nv, v, sizeof(double) * nv); memcpy(in + 2 * nv, tau, sizeof(double) * nv);
+  const int nv = h->model_h.nv, nq = h->model_h.nq;     // a free-flyer root: nq = nv + 1, partials in the tangent
+  double in[3 * DDP_MAXJ + 1];
+  memcpy(in, q, sizeof(double) * nq); memcpy(in + nq, v, sizeof(double) * nv); memcpy(in + nq + nv, tau, sizeof(double) * nv);
   const size_t nn = (size_t)nv * nv;
   double* out = new (std::nothrow) double[3 * nn];
   if (!out) return DDP_HIP_E_HIP;
-  const int rc = run(h, in, 3 * (size_t)nv, out, 3 * nn, 1, 0);
+  const int rc = run(h, in, (size_t)(nq + 2 * nv), out, 3 * nn, 1, 0);
   if (rc == DDP_HIP_OK) { memcpy(dq, out, sizeof(double) * nn); memcpy(dv, out + nn, sizeof(double) * nn); memcpy(dtau, out + 2 * nn, sizeof(double) * nn); }
   delete[] out;
   return rc;

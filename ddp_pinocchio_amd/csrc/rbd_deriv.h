@@ -278,4 +278,300 @@ __device__ void first_order_analytic_lane(const DevModel& m, const double* x, co
   }
 }
 
+// ---- free-flyer root (SE(3), lie.h), one wave per evaluation ---------------------------------------------------------------
+// The root contributes six columns J_0 .. J_5: the body-frame unit twists [linear; angular] of Pinocchio's JointModelFreeFlyer,
+// expressed in world coordinates (J_k = oX_0 e_k).  Derivatives are taken along q (+) delta = integrate(q, delta), a right
+// perturbation: perturbing column k of the root moves the whole tree rigidly by exp(J_k delta) in the world, exactly as a 1-DoF
+// joint moves its subtree.  What differs:
+//   - every root column lies in the "subtree" of every other one: d J_l / dq_k = J_k x J_l for all k, l of the root, so a
+//     root-root entry takes the proper-ancestor form (which carries the rotation of J_i) in both orders;
+//   - the root's parent is the world: u_k = J_k x 0 = 0 and g_k = -J_k x a_grav (a_grav = [0; -gravity], the world's
+//     acceleration), and the root's velocity term is J_dot v = ov_0 x ov_0 = 0;
+//   - d oa / dv_k = J_k x (ov - ov_0) below the root (the root's own acceleration carries no velocity term), so the velocity
+//     partials use w_k = J_k x ov_0 where a 1-DoF joint has 2 u_j.
+// With these, for columns i (row) and j (column) whose bodies lie on one path:
+//   body(i) a proper ancestor of body(j), or i == j (1-DoF):  d tau_i/dq_j = J_i . Fq_j,  d tau_i/dv_j = J_i . Fv_j
+//       Fq_j = J_j x* ofc_j - Bc_j u_j + Ic_j g_j,  Fv_j = Bc_j J_j - Ic_j w_j
+//   body(j) a proper ancestor of body(i), or both in the root:  d tau_i/dq_j = -z_i . u_j + y_i . g_j,  d tau_i/dv_j = z_i . J_j - y_i . w_j
+//       y_i = Ic_i J_i, z_i = Bc_i^T J_i;   M_ij = J_i . Ic J_j over the deeper body's composite inertia.
+// The trajectory point's acceleration is formed here as well, from the same recursion: qdd = M^-1 (tau - RNEA(q, v, 0)).
+// Column c belongs to body 0 (c < 6) or to joint c - 5; joint i >= 1 reads q[i + 6], v[i + 5] (rbd::place, rbd::aba_tree).
+__device__ __forceinline__ int ff_body(int c) { return c < 6 ? 0 : c - 5; }
+
+// LDS layout (doubles).  Body records (102): oR 9 | op 3 | ov 6 | oa 6 | Ic 36 | Bc 36 | f 6 (Ic | Bc | f: the subtree sums once
+// they are formed); column records (48): J 6 | u 6 | g 6 | w 6 | y 6 | z 6 | Fq 6 | Fv 6.  T = [d tau/dq | d tau/dv] (nv x 2 nv,
+// row-major) goes over the body records once they are spent; M is factorised in place (its lower triangle, column-major,
+// ld nv), M^-1 is formed in X (column-major, ld nv).
+template <int NJ> struct FfLds {
+  static constexpr int BR = 102, CR = 48;
+  static constexpr int LOC = 0, BOD = LOC + 12 * NJ, M = BOD + BR * NJ, COL = M + NJ * NJ, X = COL + CR * NJ, VEC = X + NJ * NJ,
+                       PAR = VEC + 5 * NJ + 1, TOTAL = PAR + NJ;
+  static constexpr int T = BOD;
+  static_assert(BR * NJ >= 2 * NJ * NJ, "T must fit over the body records");
+};
+
+// Partials of qdd = ABA(q, v, tau) for a free-flyer model in the tangent (nq = nv + 1): leaves T in lds + FfLds::T and M^-1 in
+// lds + FfLds::X, so that d qdd/dq = -M^-1 T(:, 0:nv), d qdd/dv = -M^-1 T(:, nv:2nv), d qdd/dtau = M^-1 (ff_minv_T_row).  Called by
+// every thread of a one-wave work-group; q, v, tau may be global.  nv <= NJ <= 64.
+template <int NJ>
+__device__ void ff_derivatives_wave(const DevModel& m, const double* q, const double* v, const double* tau, double* lds, int lane) {
+  typedef FfLds<NJ> L;
+  constexpr int BR = L::BR, CR = L::CR;
+  const int N = m.nv, NB = m.nj, W2 = 2 * N;
+  const int nth = blockDim.x;
+  double* s_loc = lds + L::LOC;
+  double* s_bod = lds + L::BOD;
+  double* s_M = lds + L::M;
+  double* s_col = lds + L::COL;
+  double* s_X = lds + L::X;
+  double* s_q = lds + L::VEC;
+  double* s_v = s_q + NJ + 1;
+  double* s_tau = s_v + NJ;
+  double* s_rhs = s_tau + NJ;
+  double* s_qdd = s_rhs + NJ;
+  int* s_par = reinterpret_cast<int*>(lds + L::PAR);
+  for (int k = lane; k <= N; k += nth) s_q[k] = q[k];
+  for (int k = lane; k < N; k += nth) { s_v[k] = v[k]; s_tau[k] = tau[k]; }
+  for (int k = lane; k < NB; k += nth) s_par[k] = m.parent[k];
+  for (int k = lane; k < N * N; k += nth) s_M[k] = 0.0;
+  __syncthreads();
+  // joint placements (parent coordinates = Rc child coordinates + r), then world placements along each body's path
+  if (lane < NB) {
+    double E[9], r[3];
+    rbd::place(m, lane, s_q, E, r);
+    double* o = s_loc + 12 * lane;
+    for (int k = 0; k < 3; ++k)
+      for (int l = 0; l < 3; ++l) o[3 * k + l] = E[3 * l + k];
+    for (int k = 0; k < 3; ++k) o[9 + k] = r[k];
+  }
+  __syncthreads();
+  if (lane < NB) {
+    double oR[9], op[3];
+    const double* o = s_loc + 12 * lane;
+    for (int k = 0; k < 9; ++k) oR[k] = o[k];
+    for (int k = 0; k < 3; ++k) op[k] = o[9 + k];
+    for (int a = s_par[lane]; a >= 0; a = s_par[a]) {
+      const double* wa = s_loc + 12 * a;
+      double t9[9], t3[3];
+      mm3(wa, oR, t9);
+      mv3(wa, op, t3);
+      for (int k = 0; k < 9; ++k) oR[k] = t9[k];
+      for (int k = 0; k < 3; ++k) op[k] = wa[9 + k] + t3[k];
+    }
+    double* br = s_bod + BR * lane;
+    for (int k = 0; k < 9; ++k) br[k] = oR[k];
+    for (int k = 0; k < 3; ++k) br[9 + k] = op[k];
+  }
+  __syncthreads();
+  // column axes J_c and J_c v_c (parked in the u slot)
+  if (lane < N) {
+    const int bc = ff_body(lane);
+    const double* br = s_bod + BR * bc;
+    double J[6];
+    if (lane < 6) {
+      const int k = lane % 3;
+      const double aw[3] = {br[k], br[3 + k], br[6 + k]};   // oR e_k
+      if (lane < 3) { J[0] = 0.0; J[1] = 0.0; J[2] = 0.0; J[3] = aw[0]; J[4] = aw[1]; J[5] = aw[2]; }
+      else { double t[3]; cross3(br + 9, aw, t); J[0] = aw[0]; J[1] = aw[1]; J[2] = aw[2]; J[3] = t[0]; J[4] = t[1]; J[5] = t[2]; }
+    } else {
+      world_axis(m, bc, br, br + 9, J);
+    }
+    double* cr = s_col + CR * lane;
+    for (int k = 0; k < 6; ++k) { cr[k] = J[k]; cr[6 + k] = J[k] * s_v[lane]; }
+  }
+  __syncthreads();
+  // body velocities: ov_b = sum over the columns of the path of J_c v_c
+  if (lane < NB) {
+    double ov[6] = {0, 0, 0, 0, 0, 0};
+    for (int a = lane; a >= 0; a = s_par[a]) {
+      const int c0 = a == 0 ? 0 : a + 5, c1 = a == 0 ? 6 : a + 6;
+      for (int c = c0; c < c1; ++c)
+        for (int k = 0; k < 6; ++k) ov[k] += s_col[CR * c + 6 + k];
+    }
+    for (int k = 0; k < 6; ++k) s_bod[BR * lane + 12 + k] = ov[k];
+  }
+  __syncthreads();
+  // velocity-product terms of the 1-DoF columns, ov_body x J_c v_c (parked in the g slot; the root's is zero)
+  if (lane < N) {
+    double* cr = s_col + CR * lane;
+    if (lane < 6) { for (int k = 0; k < 6; ++k) cr[12 + k] = 0.0; }
+    else crm(s_bod + BR * ff_body(lane) + 12, cr + 6, cr + 12);
+  }
+  __syncthreads();
+  // per body at qdd = 0: oa0 = a_grav + path sum of the velocity products; world inertia, bias matrix, force f0 = I oa0 + ov x* I ov
+  if (lane < NB) {
+    double* br = s_bod + BR * lane;
+    double oa[6] = {0, 0, 0, -m.gravity[0], -m.gravity[1], -m.gravity[2]};
+    for (int a = lane; a >= 1; a = s_par[a])
+      for (int k = 0; k < 6; ++k) oa[k] += s_col[CR * (a + 5) + 12 + k];
+    double I6[36], B[36], h[6], Ioa[6], vxh[6];
+    world_inertia(m.I6[lane], br, br + 9, I6);
+    m6v(I6, br + 12, h);
+    m6v(I6, oa, Ioa);
+    crf(br + 12, h, vxh);
+    bias_matrix(I6, br + 12, h, B);
+    for (int k = 0; k < 6; ++k) { br[18 + k] = oa[k]; br[96 + k] = Ioa[k] + vxh[k]; }
+    for (int k = 0; k < 36; ++k) { br[24 + k] = I6[k]; br[60 + k] = B[k]; }
+  }
+  __syncthreads();
+  // subtree sums leaves -> root (Ic | Bc | f0): a thread only ever touches its own entries, children precede parents
+  for (int i = NB - 1; i >= 1; --i) {
+    const int par = s_par[i];
+    for (int k = lane; k < 78; k += nth) s_bod[BR * par + 24 + k] += s_bod[BR * i + 24 + k];
+  }
+  __syncthreads();
+  // y_c = Ic J_c; the bias torques J_c . f0c; M's lower triangle: M(c, i) = J_i . y_c for the columns i <= c on c's path
+  if (lane < N) {
+    const int bc = ff_body(lane);
+    const double* br = s_bod + BR * bc;
+    double* cr = s_col + CR * lane;
+    double y[6], bias = 0.0;
+    m6v(br + 24, cr, y);
+    for (int k = 0; k < 6; ++k) { cr[24 + k] = y[k]; bias += cr[k] * br[96 + k]; }
+    s_rhs[lane] = s_tau[lane] - bias;
+    for (int a = bc; a >= 0; a = s_par[a]) {
+      const int c0 = a == 0 ? 0 : a + 5, c1 = a == 0 ? (bc == 0 ? lane + 1 : 6) : a + 6;   // (the root's columns: i <= c among themselves)
+      for (int i = c0; i < c1; ++i) {
+        double s = 0.0;
+        for (int k = 0; k < 6; ++k) s += s_col[CR * i + k] * y[k];
+        s_M[lane + i * N] = s;
+      }
+    }
+  }
+  __syncthreads();
+  // Cholesky M = L L^T in place (lower triangle): thread r owns row r
+  for (int k = 0; k < N; ++k) {
+    const double dk = sqrt(s_M[k + k * N]);
+    __syncthreads();
+    if (lane == k) s_M[k + k * N] = dk;
+    if (lane > k && lane < N) s_M[lane + k * N] = s_M[lane + k * N] / dk;
+    __syncthreads();
+    if (lane > k && lane < N) {
+      const double lrk = s_M[lane + k * N];
+      for (int c = k + 1; c <= lane; ++c) s_M[lane + c * N] -= lrk * s_M[c + k * N];
+    }
+    __syncthreads();
+  }
+  // M^-1: thread c solves L L^T x = e_c into column c of X
+  if (lane < N) {
+    double* x = s_X + lane * N;
+    for (int i = 0; i < N; ++i) {
+      double s = i == lane ? 1.0 : 0.0;
+      for (int l = 0; l < i; ++l) s -= s_M[i + l * N] * x[l];
+      x[i] = s / s_M[i + i * N];
+    }
+    for (int i = N - 1; i >= 0; --i) {
+      double s = x[i];
+      for (int l = i + 1; l < N; ++l) s -= s_M[l + i * N] * x[l];
+      x[i] = s / s_M[i + i * N];
+    }
+  }
+  __syncthreads();
+  if (lane < N) {
+    double s = 0.0;
+    for (int l = 0; l < N; ++l) s += s_X[lane + l * N] * s_rhs[l];
+    s_qdd[lane] = s;
+  }
+  __syncthreads();
+  // accelerations: oa = oa0 + alpha, alpha_b = path sum of J_c qdd_c; forces I_b alpha_b (over the spent placements) summed
+  // leaves -> root and added to f0c: ofc
+  if (lane < NB) {
+    double* br = s_bod + BR * lane;
+    double al[6] = {0, 0, 0, 0, 0, 0};
+    for (int a = lane; a >= 0; a = s_par[a]) {
+      const int c0 = a == 0 ? 0 : a + 5, c1 = a == 0 ? 6 : a + 6;
+      for (int c = c0; c < c1; ++c)
+        for (int k = 0; k < 6; ++k) al[k] += s_col[CR * c + k] * s_qdd[c];
+    }
+    double I6[36], f[6];
+    world_inertia(m.I6[lane], br, br + 9, I6);
+    m6v(I6, al, f);
+    for (int k = 0; k < 6; ++k) { br[18 + k] += al[k]; s_loc[12 * lane + k] = f[k]; }
+  }
+  __syncthreads();
+  for (int i = NB - 1; i >= 1; --i) {
+    const int par = s_par[i];
+    for (int k = lane; k < 6; k += nth) s_loc[12 * par + k] += s_loc[12 * i + k];
+  }
+  __syncthreads();
+  for (int k = lane; k < 6 * NB; k += nth) s_bod[BR * (k / 6) + 96 + k % 6] += s_loc[12 * (k / 6) + k % 6];
+  __syncthreads();
+  // column quantities u | g | w | z | Fq | Fv
+  if (lane < N) {
+    const int bc = ff_body(lane);
+    const double* br = s_bod + BR * bc;
+    double* cr = s_col + CR * lane;
+    const double* J = cr;
+    const double* ov = br + 12;
+    double u[6], g[6], w[6], t1[6], t2[6], t3[6];
+    m6tv(br + 60, J, cr + 30);                            // z
+    if (lane < 6) {
+      const double ag[6] = {0, 0, 0, -m.gravity[0], -m.gravity[1], -m.gravity[2]};
+      crm(J, ag, t1);
+      for (int k = 0; k < 6; ++k) { u[k] = 0.0; g[k] = -t1[k]; }
+      crm(J, ov, w);
+    } else {
+      crm(J, ov, u);
+      crm(u, ov, t1);
+      crm(J, br + 18, t2);
+      for (int k = 0; k < 6; ++k) { g[k] = t1[k] - t2[k]; w[k] = 2.0 * u[k]; }
+    }
+    for (int k = 0; k < 6; ++k) { cr[6 + k] = u[k]; cr[12 + k] = g[k]; cr[18 + k] = w[k]; }
+    crf(J, br + 96, t1);
+    m6v(br + 60, u, t2);
+    m6v(br + 24, g, t3);
+    for (int k = 0; k < 6; ++k) cr[36 + k] = t1[k] - t2[k] + t3[k];
+    m6v(br + 60, J, t1);
+    m6v(br + 24, w, t2);
+    for (int k = 0; k < 6; ++k) cr[42 + k] = t1[k] - t2[k];
+  }
+  __syncthreads();
+  double* s_T = lds + L::T;
+  for (int k = lane; k < N * W2; k += nth) s_T[k] = 0.0;
+  __syncthreads();
+  // T: thread c walks the bodies of its path; it writes row c (columns i of the path) and column c of the rows of its proper
+  // ancestors' columns -- no entry has two writers
+  if (lane < N) {
+    const int c = lane, bc = ff_body(c);
+    const double* cc = s_col + CR * c;
+    for (int a = bc; a >= 0; a = s_par[a]) {
+      const int c0 = a == 0 ? 0 : a + 5, c1 = a == 0 ? 6 : a + 6;
+      for (int i = c0; i < c1; ++i) {
+        const double* ci = s_col + CR * i;
+        if (a == bc && i == c && c >= 6) {                // a 1-DoF column with itself
+          double sq = 0, sv = 0;
+          for (int k = 0; k < 6; ++k) { sq += cc[k] * cc[36 + k]; sv += cc[k] * cc[42 + k]; }
+          s_T[c * W2 + c] = sq;
+          s_T[c * W2 + N + c] = sv;
+          continue;
+        }
+        if (a != bc) {                                    // i on a proper ancestor: d tau_i / d(q, v)_c
+          double sq = 0, sv = 0;
+          for (int k = 0; k < 6; ++k) { sq += ci[k] * cc[36 + k]; sv += ci[k] * cc[42 + k]; }
+          s_T[i * W2 + c] = sq;
+          s_T[i * W2 + N + c] = sv;
+        }
+        double sq = 0, sv = 0;                            // d tau_c / d(q, v)_i: a proper ancestor, or both in the root
+        for (int k = 0; k < 6; ++k) {
+          sq += -cc[30 + k] * ci[6 + k] + cc[24 + k] * ci[12 + k];
+          sv += cc[30 + k] * ci[k] - cc[24 + k] * ci[18 + k];
+        }
+        s_T[c * W2 + i] = sq;
+        s_T[c * W2 + N + i] = sv;
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// row r of -M^-1 T, column j (after ff_derivatives_wave)
+template <int NJ>
+__device__ __forceinline__ double ff_minv_T(const double* lds, int N, int r, int j) {
+  const double* s_X = lds + FfLds<NJ>::X;
+  const double* s_T = lds + FfLds<NJ>::T;
+  double s = 0.0;
+  for (int l = 0; l < N; ++l) s += s_X[r + l * N] * s_T[l * 2 * N + j];
+  return -s;
+}
+
 }  // namespace rbdd

@@ -61,7 +61,8 @@ enum {
 enum { DDP_HIP_MODEL_PENDULUM = 0, DDP_HIP_MODEL_TREE = 1 };
 enum { DDP_HIP_EQ_NONE = 0, DDP_HIP_EQ_CONFIG = 1, DDP_HIP_EQ_FRAME = 2 };
 /* FREEFLYER: joint 0 only (parent -1): an SE(3) joint, q = [p(3), quaternion x y z w], v = [linear(3), angular(3)] in the
- * body frame (Pinocchio's JointModelFreeFlyer); the model then has nq = nv + 1 and nv - 5 joints */
+ * body frame (Pinocchio's JointModelFreeFlyer); the model then has nq = nv + 1 and nv - 5 joints.  Derivatives are taken in
+ * the tangent along q (+) delta = integrate(q, delta); with either first order, fd_mode 0 or 2 and no config constraint */
 enum { DDP_HIP_JOINT_REVOLUTE = 0, DDP_HIP_JOINT_PRISMATIC = 1, DDP_HIP_JOINT_FREEFLYER = 2 };
 
 #define DDP_HIP_MAX_JOINTS 64
@@ -97,7 +98,8 @@ typedef struct ddp_hip_problem {
   const double* eq_target;       /* concatenated over t, ne[t] doubles each (shared by the batch) */
   int32_t frame_joint;
   double frame_off[3];
-  int32_t first_order_fd;        /* 0 analytic (pendulum only), 1 forward FD with eps = sqrt(DBL_EPSILON) */
+  int32_t first_order_fd;        /* 0 analytic (the pendulum's closed form; trees: ABA derivatives, free-flyer root included,
+                                    nv <= 38 with a free flyer), 1 forward FD with eps = sqrt(DBL_EPSILON) */
   int32_t fd_mode;               /* second order: 0 none (tensors zero), 1 problem.hpp:67-150, 2 problem.hpp:152-298 */
 } ddp_hip_problem;
 
@@ -282,7 +284,8 @@ int ddp_hip_model_create(const ddp_hip_model* model, int device, ddp_hip_model_h
 int ddp_hip_model_destroy(ddp_hip_model_handle* h);
 /* model_t::dynamics_aba, pinocchio_model.ipp:337-356 */
 int ddp_hip_model_aba(ddp_hip_model_handle* h, const double* q, const double* v, const double* tau, double* qdd);
-/* model_t::d_dynamics_aba, pinocchio_model.ipp:359-400 */
+/* model_t::d_dynamics_aba, pinocchio_model.ipp:359-400: d qdd/dq, d qdd/dv, d qdd/dtau = M^-1, each nv x nv; with a free-flyer
+ * root the q partials are taken in the tangent (q (+) delta), nq = nv + 1 inputs in q */
 int ddp_hip_model_aba_derivatives(ddp_hip_model_handle* h, const double* q, const double* v, const double* tau,
                                   double* dq, double* dv, double* dtau);
 /* model_t::frame_coordinates / d_frame_coordinates, pinocchio_model.ipp:418-462 (J: 3 x nv, may be NULL; the reference's
