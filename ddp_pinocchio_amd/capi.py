@@ -23,7 +23,7 @@ MODEL_PENDULUM, MODEL_TREE = 0, 1
 EQ_NONE, EQ_CONFIG, EQ_FRAME = 0, 1, 2
 BUILTIN_PENDULUM, BUILTIN_CHAIN6, BUILTIN_TREE38, BUILTIN_CHAIN6_FF, BUILTIN_TREE38_FF = 0, 1, 2, 3, 4
 JOINT_REVOLUTE, JOINT_PRISMATIC, JOINT_FREEFLYER = 0, 1, 2
-FLAG_NO_TENSORS, FLAG_TRACE = 1, 2
+FLAG_NO_TENSORS, FLAG_TRACE, FLAG_TRACKING_COST = 1, 2, 4
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
 
 SEQ_NAMES = [
@@ -32,6 +32,7 @@ SEQ_NAMES = [
     "EQ_VAL", "EQ_X", "EQ_U", "EQ_XX", "EQ_UX", "EQ_UU",
     "MULT_ORIGIN", "MULT_VAL", "MULT_JAC", "FB_ORIGIN", "FB_VAL", "FB_JAC",
     "VX_TRACE", "VXX_TRACE", "COSTS_OLD", "COSTS_NEW",
+    "COST_XREF", "COST_WX", "COST_UREF", "COST_WU",
 ]
 SEQ = {name: i for i, name in enumerate(SEQ_NAMES)}
 
@@ -365,6 +366,24 @@ class Context:
         out = np.empty((count, self.seq_size(name)), dtype=np.float64)
         _check(lib().ddp_hip_download(self._h, SEQ[name], _ptr(out), first, count), f"download {name}")
         return out
+
+    def set_tracking_cost(self, xref=None, wx=None, uref=None, wu=None, first=0, count=None):
+        """The tracking cost of instances first .. first + count - 1 (a context created with FLAG_TRACKING_COST; ddp_hip.h):
+        xref (T+1, nx), wx (T+1, n), uref (T, m), wu (T, m), each either one array for every instance of the range or
+        (count, ...) with one per instance.  None leaves that sequence as it is."""
+        count = self.batch - first if count is None else count
+        sp = self.spec
+        shapes = {"COST_XREF": (sp.T + 1, sp.nx), "COST_WX": (sp.T + 1, sp.n), "COST_UREF": (sp.T, sp.m), "COST_WU": (sp.T, sp.m)}
+        for name, arr in (("COST_XREF", xref), ("COST_WX", wx), ("COST_UREF", uref), ("COST_WU", wu)):
+            if arr is None:
+                continue
+            arr = _f64(arr)
+            shape = shapes[name]
+            if arr.shape == shape:
+                arr = np.broadcast_to(arr, (count,) + shape)
+            elif arr.shape != (count,) + shape:
+                raise ValueError(f"{name}: shape {arr.shape}, expected {shape} or {(count,) + shape}")
+            self.upload(name, arr, first, count)
 
     def fill(self, name, value):
         _check(lib().ddp_hip_fill(self._h, SEQ[name], float(value)), f"fill {name}")

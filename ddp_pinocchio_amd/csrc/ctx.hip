@@ -170,6 +170,9 @@ static int64_t seq_size_of(const Dims& d, int s) {
     case DDP_HIP_SEQ_VX_TRACE: return T * n;
     case DDP_HIP_SEQ_VXX_TRACE: return T * n * n;
     case DDP_HIP_SEQ_COSTS_OLD: case DDP_HIP_SEQ_COSTS_NEW: return T + 1;
+    case DDP_HIP_SEQ_COST_XREF: return (T + 1) * nx;
+    case DDP_HIP_SEQ_COST_WX: return (T + 1) * n;
+    case DDP_HIP_SEQ_COST_UREF: case DDP_HIP_SEQ_COST_WU: return T * m;
     default: return -1;
   }
 }
@@ -179,6 +182,7 @@ static bool is_tensor_seq(int s) {
          s == DDP_HIP_SEQ_EQ_UX || s == DDP_HIP_SEQ_EQ_UU;
 }
 static bool is_trace_seq(int s) { return s == DDP_HIP_SEQ_VX_TRACE || s == DDP_HIP_SEQ_VXX_TRACE; }
+static bool is_cost_seq(int s) { return s >= DDP_HIP_SEQ_COST_XREF && s <= DDP_HIP_SEQ_COST_WU; }
 static bool nan_init_seq(int s) {
   // mat_seq_t storage is NaN-poisoned at construction (detail/mat_seq.hpp:34-37); uninit_derivative_storage
   // then zeroes every derivative sequence except f_val, and leaves lfx / lfxx NaN (ddp.hpp:441-442,476-511)
@@ -317,12 +321,22 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     ctx->seq[s].size = sz;
     if ((flags & DDP_HIP_FLAG_NO_TENSORS) && is_tensor_seq(s)) continue;
     if (!(flags & DDP_HIP_FLAG_TRACE) && is_trace_seq(s)) continue;
+    if (!(flags & DDP_HIP_FLAG_TRACKING_COST) && is_cost_seq(s)) continue;
     if (sz <= 0) continue;
     CTX_TRY(hipMalloc(&ctx->seq[s].ptr, sizeof(double) * (size_t)(sz * d.batch)));
     if (fill_device(ctx, ctx->seq[s].ptr, sz * d.batch, nan_init_seq(s) ? qnan : 0.0) != DDP_HIP_OK) {
       ddp_hip_destroy(ctx);
       return DDP_HIP_E_HIP;
     }
+  }
+  if (flags & DDP_HIP_FLAG_TRACKING_COST) {
+    // the reference state starts at the neutral state at every t (weights and reference controls start at 0): a zero-filled
+    // root quaternion would make the cost NaN even under zero weights
+    std::vector<double> xr((size_t)(ctx->seq[DDP_HIP_SEQ_COST_XREF].size * d.batch), 0.0);
+    if (ff)
+      for (size_t k = 0; k < xr.size(); k += (size_t)d.nx) xr[k + 6] = 1.0;
+    CTX_TRY(hipMemcpyAsync(ctx->seq[DDP_HIP_SEQ_COST_XREF].ptr, xr.data(), sizeof(double) * xr.size(), hipMemcpyHostToDevice, ctx->stream));
+    CTX_TRY(hipStreamSynchronize(ctx->stream));
   }
   int rc = bwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = fwd_setup(ctx);
@@ -389,12 +403,30 @@ static int check_range(ddp_hip_ctx* ctx, int seq, int64_t first, int64_t count) 
   return DDP_HIP_OK;
 }
 
+// what the tracking cost accepts (DDP_HIP_FLAG_TRACKING_COST): finite, non-negative weights; unit root quaternions
+static bool cost_weight_ok(double w) { return isfinite(w) && w >= 0.0; }
+static bool cost_quat_ok(double norm2) { return isfinite(norm2) && fabs(sqrt(norm2) - 1.0) <= 1e-10; }
+
+static bool cost_values_ok(const ddp_hip_ctx* ctx, int seq, const double* host, int64_t words) {
+  if (seq == DDP_HIP_SEQ_COST_WX || seq == DDP_HIP_SEQ_COST_WU) {
+    for (int64_t i = 0; i < words; ++i)
+      if (!cost_weight_ok(host[i])) return false;
+  } else if (seq == DDP_HIP_SEQ_COST_XREF && ctx->model_h.ff) {
+    for (int64_t k = 0; k < words; k += ctx->d.nx) {
+      const double* qt = host + k + 3;
+      if (!cost_quat_ok(qt[0] * qt[0] + qt[1] * qt[1] + qt[2] * qt[2] + qt[3] * qt[3])) return false;
+    }
+  }
+  return true;
+}
+
 extern "C" int ddp_hip_upload(ddp_hip_ctx* ctx, int seq, const double* host, int64_t first, int64_t count) {
   int rc = check_range(ctx, seq, first, count);
   if (rc != DDP_HIP_OK) return rc;
   int64_t sz = ctx->seq[seq].size;
   if (sz == 0 || count == 0) return DDP_HIP_OK;
   if (!host) return DDP_HIP_E_ARG;
+  if (!cost_values_ok(ctx, seq, host, sz * count)) return DDP_HIP_E_ARG;
   HIP_TRY(hipSetDevice(ctx->device));
   if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUX || seq == DDP_HIP_SEQ_FUU) { ctx->tensor_tops_zero = false; ctx->tensor_tops_sparse = false; ctx->fuu_zero = false; }
   if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUU) {   // tensors from outside: no symmetry assumed (bwd_split.h)
@@ -422,6 +454,8 @@ extern "C" int ddp_hip_download(ddp_hip_ctx* ctx, int seq, double* host, int64_t
 extern "C" int ddp_hip_fill(ddp_hip_ctx* ctx, int seq, double value) {
   int rc = check_range(ctx, seq, 0, 0);
   if (rc != DDP_HIP_OK) return rc;
+  if ((seq == DDP_HIP_SEQ_COST_WX || seq == DDP_HIP_SEQ_COST_WU) && !cost_weight_ok(value)) return DDP_HIP_E_ARG;
+  if (seq == DDP_HIP_SEQ_COST_XREF && ctx->model_h.ff && !cost_quat_ok(4 * value * value)) return DDP_HIP_E_ARG;
   HIP_TRY(hipSetDevice(ctx->device));
   if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUX || seq == DDP_HIP_SEQ_FUU) { ctx->tensor_tops_zero = false; ctx->tensor_tops_sparse = false; ctx->fuu_zero = false; }
   if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUU) {

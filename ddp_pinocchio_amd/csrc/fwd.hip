@@ -35,6 +35,8 @@ struct FwdParams {
   int32_t no_linesearch;         // ddp_fwd.ipp:61-63: the full step is taken whatever the cost does
   int32_t cost_inline;           // latency kernel: 1 = forms sum_t (cost_new - cost_old) itself (no constraints), 0 = cand_cost_kernel does
   double* fw_cost;               // [batch][n_alpha][T+1] cost terms of the candidates (constrained problems on the latency path)
+  const double *xref, *wx, *uref, *wu;   // tracking cost (DDP_HIP_FLAG_TRACKING_COST), else null
+  int32_t track;
 };
 
 // constraint value at solver time t: constraint_advance_time_t::eval_to (problem.hpp:563-567) applied
@@ -58,6 +60,38 @@ __device__ void eval_eq(const DevModel& m, const double* target, int e, const do
   }
 }
 
+// 1/2 sum_i w_i d_i^2, d = x (-) xr (lie::difference_x, formed entry by entry): the state terms of the tracking cost
+// (ddp_hip.h: DDP_HIP_FLAG_TRACKING_COST).  A term of weight 0 is left out, not multiplied by 0: a diverging rollout (inf)
+// costs what it costs without the flag instead of NaN
+__device__ __forceinline__ double track_state_sum(bool ff, int nv, const double* xr, const double* x, const double* w) {
+  const int nq = ff ? nv + 1 : nv;
+  double s = 0;
+  int i = 0;
+  if (ff) {
+    double d6[6];
+    lie::se3_difference(xr, x, d6);
+    for (; i < 6; ++i) if (w[i] != 0.0) s += w[i] * d6[i] * d6[i];
+  }
+  for (; i < nv; ++i) { const double di = x[i + nq - nv] - xr[i + nq - nv]; if (w[i] != 0.0) s += w[i] * di * di; }
+  for (; i < 2 * nv; ++i) { const double di = x[nq + i - nv] - xr[nq + i - nv]; if (w[i] != 0.0) s += w[i] * di * di; }
+  return 0.5 * s;
+}
+// ... at time t of instance b; t = T: the terminal cost lf
+__device__ __forceinline__ double track_state_cost(const FwdParams& p, int b, int64_t t, const double* x) {
+  const int nv = (int)p.d.nv, nx = (int)p.d.nx;
+  const int64_t bt = (int64_t)b * (p.d.T + 1) + t;
+  return track_state_sum(nx > 2 * nv, nv, p.xref + bt * nx, x, p.wx + bt * 2 * nv);
+}
+// 1/2 sum_j wu_j (u_j - uref_j)^2 at time t < T of instance b
+__device__ __forceinline__ double track_control_sum(const FwdParams& p, int b, int64_t t, const double* u) {
+  const int nv = (int)p.d.nv;
+  const double* ur = p.uref + ((int64_t)b * p.d.T + t) * nv;
+  const double* wu = p.wu + ((int64_t)b * p.d.T + t) * nv;
+  double su = 0;
+  for (int i = 0; i < nv; ++i) { const double du = u[i] - ur[i]; if (wu[i] != 0.0) su += wu[i] * du * du; }
+  return 0.5 * su;
+}
+
 // one term of cost_seq_aug (ddp.hpp:730): l + pe.ce + mu/2 |ce|^2
 template <int NJ>
 __device__ double stage_cost(const FwdParams& p, const DevModel& m, int b, int64_t t, const double* x, const double* u, double mu) {
@@ -65,6 +99,7 @@ __device__ double stage_cost(const FwdParams& p, const DevModel& m, int b, int64
   double un = 0;
   for (int i = 0; i < nv; ++i) un += u[i] * u[i];
   double cost = 0.5 * m.c * un;                                   // problem_t::l, problem.hpp:937-942
+  if (p.track) cost += track_state_cost(p, b, t, x) + track_control_sum(p, b, t, u);   // + the tracking terms
   const int e = (int)p.ne[t];
   if (e > 0) {
     double ce[NJ > 3 ? NJ : 3];
@@ -107,6 +142,11 @@ __global__ void rollout_kernel(FwdParams p) {
   }
 }
 
+// problem_t::lf (problem.hpp:932-936: 0), or the tracking cost's terminal term
+__device__ __forceinline__ double terminal_cost(const FwdParams& p, int b, const double* x) {
+  return p.track ? track_state_cost(p, b, p.d.T, x) : 0.0;
+}
+
 // cost_seq_aug of one trajectory: one lane per (instance, t)
 template <int NJ>
 __global__ void cost_kernel(FwdParams p, int which) {
@@ -118,8 +158,8 @@ __global__ void cost_kernel(FwdParams p, int which) {
   const DevModel& m = *p.model;
   const int nx = m.nq + m.nv, nu = m.nv;
   double* out = (which == 0 ? p.costs_old : p.costs_new) + (int64_t)b * (T + 1);
-  if (t == T) { out[T] = 0.0; return; }                           // problem_t::lf, problem.hpp:932-936
   const double* xs = (which == 0 ? p.x_old : p.x_new) + ((int64_t)b * (T + 1) + t) * nx;
+  if (t == T) { out[T] = terminal_cost(p, b, xs); return; }
   const double* us = (which == 0 ? p.u_old : p.u_new) + ((int64_t)b * T + t) * nu;
   double x[2 * NJ + 1], u[NJ];
   for (int i = 0; i < nx; ++i) x[i] = xs[i];
@@ -178,8 +218,43 @@ __global__ void forward_kernel(FwdParams p) {
     rbd::eval_f<NJ>(m, x, u, xn);                                             // :50
     for (int i = 0; i < nx; ++i) { x[i] = xn[i]; xw[(t + 1) * nx + i] = xn[i]; }
   }
-  dsum += 0.0 - cold[T];
+  dsum += terminal_cost(p, b, x) - cold[T];
   p.fw_dcost[(int64_t)b * na + a] = dsum;
+}
+
+// The tracking terms of one candidate of forward_kernel_lat2 at time t (t = T: lf, no control terms), by its 16 lanes h: lane h
+// takes the state rows r0 + h, r0 + h + 16, ... and the controls h, h + 16, ...; lane 0 the six rows of a free-flyer root
+// (lie::se3_difference); the 16 partial sums meet in a fixed butterfly.  Every lane of the wave calls it (the shuffles span
+// the candidate's 16 lanes); not live: 0
+template <bool FF>
+__device__ __forceinline__ double track_lanes_sum(const FwdParams& p, int b, int64_t t, const double* x, const double* u, int h, bool live) {
+  const int nv = (int)p.d.nv, n = 2 * nv, nx = (int)p.d.nx, nq = nx - nv, r0 = FF ? 6 : 0;
+  constexpr int NH = 16;
+  const int64_t T = p.d.T, bt1 = (int64_t)b * (T + 1) + t;
+  const double* xr = p.xref + bt1 * nx;
+  const double* w = p.wx + bt1 * n;
+  double s = 0, su = 0;
+  if (live) {
+    if (FF && h == 0) {
+      double d6[6];
+      lie::se3_difference(xr, x, d6);
+      for (int i = 0; i < 6; ++i) if (w[i] != 0.0) s += w[i] * d6[i] * d6[i];
+    }
+    for (int i = r0 + h; i < n; i += NH) {
+      const int k = i < nv ? i + nq - nv : nq + i - nv;
+      const double di = x[k] - xr[k];
+      if (w[i] != 0.0) s += w[i] * di * di;
+    }
+    if (t < T) {
+      const double* ur = p.uref + ((int64_t)b * T + t) * nv;
+      const double* wu = p.wu + ((int64_t)b * T + t) * nv;
+      for (int j = h; j < nv; j += NH) { const double du = u[j] - ur[j]; if (wu[j] != 0.0) su += wu[j] * du * du; }
+    }
+  }
+  double v = 0.5 * s + 0.5 * su;
+#pragma unroll
+  for (int k = NH / 2; k >= 1; k /= 2) v += __shfl_xor(v, k, NH);
+  return v;
 }
 
 // Latency path of the same rollouts (trees of the Talos size): one 64-lane workgroup (= one wave) per (instance, four
@@ -211,7 +286,9 @@ __device__ unsigned long long g_fwd_stamps[12];
 // OPEN: the open-loop rollout of make_trajectory (ddp.hpp:392-415) on the same machinery: one candidate, u = U as given, x to X
 // FF: free-flyer root (nq = nv + 1): x_new (-) x_old and q (+) dt v go through SE(3) for the root (lie.h), the dynamics through
 // rbd::aba_tree_coop2w's free-flyer form
-template <int NJ, bool OPEN = false, bool FF = false>
+// TRACK: the tracking cost (DDP_HIP_FLAG_TRACKING_COST) of an unconstrained problem, formed inline by the 16 lanes of a candidate
+// (track_lanes_sum); an instantiation of its own, so that the kernel without it is the one it was
+template <int NJ, bool OPEN = false, bool FF = false, bool TRACK = false>
 __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
   using L = FwdLat2Lds<NJ>;
   constexpr int NC = L::NC, NH = L::NH;
@@ -368,10 +445,13 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
     }
     rbd::coop_sync<true>();
     FSTAMP(fs, 0);
+    double c_track = 0.0;
+    if constexpr (TRACK) c_track = track_lanes_sum<FF>(p, b, t, x, u, h, live);
     if (h == 0 && live && p.cost_inline) {
       double un = 0;
       for (int i = 0; i < nu; ++i) un += u[i] * u[i];
-      const double c_new = 0.5 * mc * un;                                       // problem_t::l (constrained problems: cand_cost_kernel)
+      double c_new = 0.5 * mc * un;                                             // problem_t::l (constrained problems: cand_cost_kernel)
+      if constexpr (TRACK) c_new += c_track;
       dsum += c_new - cold_t;
     }
     }
@@ -420,33 +500,37 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
   if (threadIdx.x == 0 && blockIdx.x == 0)
     for (int i = 0; i < 12; ++i) g_fwd_stamps[i] = fsv.acc[i];
 #endif
+  double c_term = 0.0;
+  if constexpr (TRACK) { if (lead) c_term = track_lanes_sum<FF>(p, b, T, x, u, h, live); }
   if (!OPEN && h == 0 && live && lead && p.cost_inline) {
-    dsum += 0.0 - cold[T];
+    dsum += c_term - cold[T];
     p.fw_dcost[(int64_t)b * na + a] = dsum;
   }
 }
 
-// Constrained problems on the latency path.  Only the rollout is sequential in t; the cost terms of a rolled-out candidate
-// (cost_seq_aug, ddp.hpp:699-735: l + pe . ce + mu/2 |ce|^2, with ce_t = eq(t, x_t, u_t) two look-ahead dynamics steps away,
-// problem.hpp:563-567) are independent across t: one lane per (instance, candidate, t) ...
+// Constrained problems on the latency path.  Only the rollout is sequential in t; the cost terms of a rolled-out
+// candidate (cost_seq_aug, ddp.hpp:699-735: l + pe . ce + mu/2 |ce|^2, with ce_t = eq(t, x_t, u_t) two look-ahead dynamics steps
+// away, problem.hpp:563-567; lf at t = T) are independent across t: one lane per (instance, candidate, t), t = 0 .. T ...
 template <int NJ>
 __global__ void cand_cost_kernel(FwdParams p) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t T = p.d.T;
   const int na = p.n_alpha;
-  if (gid >= p.d.batch * na * T) return;
-  const int64_t t = gid % T;
-  const int a = (int)((gid / T) % na);
-  const int b = (int)(gid / (T * na));
+  if (gid >= p.d.batch * na * (T + 1)) return;
+  const int64_t t = gid % (T + 1);
+  const int a = (int)((gid / (T + 1)) % na);
+  const int b = (int)(gid / ((T + 1) * na));
   if (p.state[b] != 0 || p.round * na + a > 33) return;
   const DevModel& m = *p.model;
   const int nx = m.nq + m.nv, nu = m.nv;
   const double* xs = p.fw_x + (((int64_t)b * na + a) * (T + 1) + t) * nx;
-  const double* us = p.fw_u + (((int64_t)b * na + a) * T + t) * nu;
   double x[2 * NJ + 1], u[NJ];
   for (int i = 0; i < nx; ++i) x[i] = xs[i];
+  double* out = p.fw_cost + ((int64_t)b * na + a) * (T + 1) + t;
+  if (t == T) { *out = terminal_cost(p, b, x); return; }
+  const double* us = p.fw_u + (((int64_t)b * na + a) * T + t) * nu;
   for (int i = 0; i < nu; ++i) u[i] = us[i];
-  p.fw_cost[((int64_t)b * na + a) * (T + 1) + t] = stage_cost<NJ>(p, m, b, t, x, u, p.mu[b]);
+  *out = stage_cost<NJ>(p, m, b, t, x, u, p.mu[b]);
 }
 // ... and one lane per (instance, candidate) adds the differences up in the order of forward_kernel (ddp_fwd.ipp:54-56)
 __global__ void cand_sum_kernel(FwdParams p) {
@@ -460,7 +544,7 @@ __global__ void cand_sum_kernel(FwdParams p) {
   const double* cnew = p.fw_cost + ((int64_t)b * na + a) * (T + 1);
   double dsum = 0.0;
   for (int64_t t = 0; t < T; ++t) dsum += cnew[t] - cold[t];
-  dsum += 0.0 - cold[T];
+  dsum += cnew[T] - cold[T];
   p.fw_dcost[(int64_t)b * na + a] = dsum;
 }
 
@@ -527,6 +611,8 @@ FwdParams make_params(ddp_hip_ctx* ctx) {
   p.fw_x = ctx->fw_x; p.fw_u = ctx->fw_u; p.fw_dcost = ctx->fw_dcost;
   p.step = ctx->step_d; p.dcost_acc = ctx->fw_dcost_acc_d; p.state = ctx->fw_state_d;
   p.n_alpha = ctx->n_alpha_max;
+  p.track = (ctx->flags & DDP_HIP_FLAG_TRACKING_COST) ? 1 : 0;
+  p.xref = S(DDP_HIP_SEQ_COST_XREF); p.wx = S(DDP_HIP_SEQ_COST_WX); p.uref = S(DDP_HIP_SEQ_COST_UREF); p.wu = S(DDP_HIP_SEQ_COST_WU);
   p.cost_inline = ctx->d.Etot == 0 ? 1 : 0;
   p.fw_cost = ctx->fw_cost;
   p.round = 0;
@@ -574,6 +660,10 @@ int fwd_setup(ddp_hip_ctx* ctx) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)sizeof(FwdLat2Lds<38>)));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)sizeof(FwdLat2Lds<38>)));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)sizeof(FwdLat2Lds<38>)));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)sizeof(FwdLat2Lds<38>)));
   }
   return DDP_HIP_OK;
@@ -665,10 +755,15 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
     // cost terms of the rolled-out candidates come from cand_cost_kernel (parallel over t) instead of the rollout itself
     const bool lat_path = fwd_lat_supported(ctx) && n_alpha <= 8;
     if (lat_path) {
-      if (ctx->model_h.ff) hipLaunchKernelGGL((forward_kernel_lat2<38, false, true>), dim3((unsigned)(2 * B)), dim3(128), sizeof(FwdLat2Lds<38>), ctx->stream, p);
-      else hipLaunchKernelGGL((forward_kernel_lat2<38>), dim3((unsigned)(2 * B)), dim3(128), sizeof(FwdLat2Lds<38>), ctx->stream, p);
+      const dim3 g((unsigned)(2 * B)), blk(128);
+      const size_t lds = sizeof(FwdLat2Lds<38>);
+      if (p.track && p.cost_inline) {
+        if (ctx->model_h.ff) hipLaunchKernelGGL((forward_kernel_lat2<38, false, true, true>), g, blk, lds, ctx->stream, p);
+        else hipLaunchKernelGGL((forward_kernel_lat2<38, false, false, true>), g, blk, lds, ctx->stream, p);
+      } else if (ctx->model_h.ff) hipLaunchKernelGGL((forward_kernel_lat2<38, false, true>), g, blk, lds, ctx->stream, p);
+      else hipLaunchKernelGGL((forward_kernel_lat2<38>), g, blk, lds, ctx->stream, p);
       if (!p.cost_inline) {
-        hipLaunchKernelGGL((cand_cost_kernel<38>), dim3((unsigned)((B * n_alpha * d.T + 63) / 64)), dim3(64), 0, ctx->stream, p);
+        hipLaunchKernelGGL((cand_cost_kernel<38>), dim3((unsigned)((B * n_alpha * (d.T + 1) + 63) / 64)), dim3(64), 0, ctx->stream, p);
         hipLaunchKernelGGL(cand_sum_kernel, dim3((unsigned)((B * n_alpha + 63) / 64)), dim3(64), 0, ctx->stream, p);
       }
     } else {

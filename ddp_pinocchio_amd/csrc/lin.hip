@@ -42,6 +42,61 @@ __global__ void lin_cost_kernel(LinParams p) {
   for (int i = tid; i < m * m; i += blockDim.x) p.luu[bt * m * m + i] = (i % m == i / m) ? 1.0 * c : 0.0;
 }
 
+// Tracking cost (DDP_HIP_FLAG_TRACKING_COST, ddp_hip.h): one workgroup per (instance, t), t = 0 .. T; t = T writes lfx / lfxx.
+// d = x (-) xref, J = dd/ddx: the identity but on a free-flyer root block, where it is Jlog6(d_root) (lie::se3_Jlog).
+//   lx = J^T (wx o d), lxx = J^T diag(wx) J (Gauss-Newton on the root block: the term sum_k wx_k d_k d^2(d_k) is left out,
+//   exact where d_root = 0), lu = c u + wu o (u - uref), luu = c I + diag(wu), lux = 0.
+// Every entry of the dense blocks is stored, as lin_cost_kernel stores them.  A term of weight 0 is left out (fwd.hip:
+// track_state_sum): with every weight 0 the bytes are lin_cost_kernel's, whatever the state.
+__global__ void lin_track_cost_kernel(LinParams p) {
+  const int64_t T = p.d.T;
+  const int64_t bt1 = blockIdx.x;
+  const int b = (int)(bt1 / (T + 1));
+  const int64_t t = bt1 % (T + 1);
+  const int n = (int)p.d.n, m = (int)p.d.m, nx = (int)p.d.nx, nv = (int)p.d.nv;
+  const DevModel& md = *p.model;
+  const int nq = nx - nv, r0 = md.ff ? 6 : 0;   // rows r0 .. n-1 of d are plain differences
+  const double c = md.c;
+  const int tid = threadIdx.x;
+  __shared__ double s_d[2 * DDP_MAXJ], s_w[2 * DDP_MAXJ], s_J[36];
+  const double* x = p.x + ((int64_t)b * (T + 1) + t) * nx;
+  const double* xr = p.xref + ((int64_t)b * (T + 1) + t) * nx;
+  const double* w = p.wx + ((int64_t)b * (T + 1) + t) * n;
+  if (md.ff && tid == 0) { lie::se3_difference(xr, x, s_d); lie::se3_Jlog(s_d, s_J); }   // lie::difference_x, root rows
+  for (int i = r0 + tid; i < n; i += blockDim.x) {
+    const int k = i < nv ? i + (nq - nv) : nq + i - nv;
+    s_d[i] = x[k] - xr[k];
+  }
+  for (int i = tid; i < n; i += blockDim.x) s_w[i] = w[i];
+  __syncthreads();
+  double* gx = t < T ? p.lx + (b * T + t) * n : p.lfx + (int64_t)b * n;
+  double* gxx = t < T ? p.lxx + (b * T + t) * n * n : p.lfxx + (int64_t)b * n * n;
+  for (int i = tid; i < n; i += blockDim.x) {
+    double g;
+    if (i < r0) { g = 0; for (int k = 0; k < 6; ++k) if (s_w[k] != 0.0) g += s_J[6 * k + i] * (s_w[k] * s_d[k]); }
+    else g = s_w[i] != 0.0 ? s_w[i] * s_d[i] : 0.0;
+    gx[i] = g;
+  }
+  for (int e = tid; e < n * n; e += blockDim.x) {
+    const int i = e % n, j = e / n;
+    double h = 0.0;
+    if (i < r0 && j < r0) {   // (min, max) order: the block is symmetric bit for bit
+      const int a = i < j ? i : j, a2 = i < j ? j : i;
+      for (int k = 0; k < 6; ++k) if (s_w[k] != 0.0) h += s_J[6 * k + a] * s_w[k] * s_J[6 * k + a2];
+    } else if (i == j) h = s_w[i];
+    gxx[e] = h;
+  }
+  if (t == T) return;
+  const int64_t bt = (int64_t)b * T + t;
+  for (int i = tid; i < m * n; i += blockDim.x) p.lux[bt * m * n + i] = 0.0;
+  for (int i = tid; i < m; i += blockDim.x) {
+    const double u = p.u[bt * m + i];
+    const double wu = p.wu[bt * m + i];
+    p.lu[bt * m + i] = wu != 0.0 ? c * u + wu * (u - p.uref[bt * m + i]) : c * u;
+  }
+  for (int i = tid; i < m * m; i += blockDim.x) p.luu[bt * m * m + i] = (i % m == i / m) ? 1.0 * c + p.wu[bt * m + i % m] : 0.0;
+}
+
 template <int NJ>
 __device__ __forceinline__ void load_xu(const LinParams& p, int b, int64_t t, double* x, double* u) {
   const int nx = (int)p.d.nx, m = (int)p.d.m;
@@ -785,6 +840,7 @@ LinParams make_params(ddp_hip_ctx* ctx) {
   p.qcache = reinterpret_cast<double*>(ctx->lin_ws);
   p.ncfg = ctx->lin_ncfg; p.nvcfg = ctx->lin_nvcfg;
   p.vcache = p.qcache ? p.qcache + ctx->d.batch * ctx->d.T * (int64_t)ctx->lin_ncfg * ctx->d.nv * rbd::QC_STRIDE : nullptr;
+  p.xref = S(DDP_HIP_SEQ_COST_XREF); p.wx = S(DDP_HIP_SEQ_COST_WX); p.uref = S(DDP_HIP_SEQ_COST_UREF); p.wu = S(DDP_HIP_SEQ_COST_WU);
   return p;
 }
 
@@ -803,7 +859,11 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, uint32_t stages) {
   const bool ana_large = !small && !ctx->model_h.first_order_fd && ctx->model_h.kind == DDP_HIP_MODEL_TREE;
   const bool eq_stage = (stages & DDP_HIP_LIN_EQ) && d.Etot > 0;
   const bool m1_fused = ana_large && fd_mode == 1 && p.has_tensors && eq_stage;   // LIN_SECOND's mode-1 pass is issued by the LIN_EQ stage
-  if (stages & DDP_HIP_LIN_COST) hipLaunchKernelGGL(lin_cost_kernel, dim3((unsigned)BT), dim3(64), 0, ctx->stream, p);
+  if (stages & DDP_HIP_LIN_COST) {
+    if (ctx->flags & DDP_HIP_FLAG_TRACKING_COST)
+      hipLaunchKernelGGL(lin_track_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p);
+    else hipLaunchKernelGGL(lin_cost_kernel, dim3((unsigned)BT), dim3(64), 0, ctx->stream, p);
+  }
   // static-topology path: the q- / v-caches of the mode-2 stencil also serve the first order (base configuration and
   // base (q, v)), so they are built ahead of whichever stage comes first
   bool caches_built = false;

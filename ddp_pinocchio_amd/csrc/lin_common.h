@@ -27,6 +27,7 @@ struct LinParams {
                          // points, [pair][3 nv directions: q, v, u | the unperturbed point][nv], instead of the jacobian columns (lin_analytic.hip: mode 1 reads them)
   int32_t ncfg, nvcfg;   // entries per (instance, t) of the q- / v-cache: nv+1 / 2nv+1 with the mode-2 stencil resident,
                          // 1 / 1 when only the first order is formed (tensor-free contexts: base configuration and base (q, v))
+  const double *xref, *wx, *uref, *wu;   // tracking cost (DDP_HIP_FLAG_TRACKING_COST), else null
 };
 
 constexpr int LBS = 64;

@@ -115,6 +115,11 @@ enum ddp_hip_seq {
   DDP_HIP_SEQ_FB_ORIGIN, DDP_HIP_SEQ_FB_VAL, DDP_HIP_SEQ_FB_JAC,
   DDP_HIP_SEQ_VX_TRACE, DDP_HIP_SEQ_VXX_TRACE,   /* V_x / V_xx after every step (parity only) */
   DDP_HIP_SEQ_COSTS_OLD, DDP_HIP_SEQ_COSTS_NEW,  /* T+1 doubles each (cost_seq_aug) */
+  /* per-instance quadratic tracking cost (DDP_HIP_FLAG_TRACKING_COST; not allocated without it) */
+  DDP_HIP_SEQ_COST_XREF,   /* [T+1][nx] reference states (create: the neutral state: q neutral, unit root quaternion, v = 0) */
+  DDP_HIP_SEQ_COST_WX,     /* [T+1][n]  state weights, tangent rows (create: 0) */
+  DDP_HIP_SEQ_COST_UREF,   /* [T][m]    reference controls (create: 0) */
+  DDP_HIP_SEQ_COST_WU,     /* [T][m]    control weights (create: 0) */
   DDP_HIP_SEQ_COUNT
 };
 
@@ -123,6 +128,19 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
 /* create flags */
 #define DDP_HIP_FLAG_NO_TENSORS 1u   /* do not allocate fxx/fux/fuu/eq_xx/eq_ux/eq_uu (Gauss-Newton sweeps only) */
 #define DDP_HIP_FLAG_TRACE 2u        /* allocate the V_x / V_xx trace sequences */
+/* Allocate the COST_* sequences and optimise, per instance b, with d_t = x_t (-) xref[b][t] (lie::difference_x: a plain
+ * subtraction on vector-space models, log6(Mref^-1 M) on a free-flyer root's six rows):
+ *   l(t, x, u) = c/2 |u|^2 + 1/2 sum_i wx[t][i] d_i^2 + 1/2 sum_j wu[t][j] (u_j - uref[t][j])^2      t < T
+ *   lf(x_T)    = 1/2 sum_i wx[T][i] d_T,i^2
+ * instead of the reference's fixed c/2 |u|^2, lf = 0 (problem.hpp:932-942); the constraint terms of cost_seq_aug are unchanged.
+ * Derivatives in the tangent at x, J = dd/ddx (the identity but on a free-flyer root block: Jlog6(d_root)):
+ *   lx = J^T (wx o d), lxx = J^T diag(wx) J, lu = c u + wu o (u - uref), luu = c I + diag(wu), lux = 0, lfx / lfxx alike at T.
+ * lxx is exact on vector-space models and Gauss-Newton on the root block (the term sum_i wx_i d_i d^2(d_i) is dropped: exact
+ * where d_root = 0).  ddp_hip_upload refuses (DDP_HIP_E_ARG) negative or non-finite weights and, on a free-flyer model, a
+ * reference root quaternion with | |quat| - 1 | > 1e-10; writes through ddp_hip_device_ptr are the caller's responsibility.
+ * A term of weight 0 is left out (not multiplied by 0): with all weights 0 a context computes bit for bit what it computes
+ * without the flag. */
+#define DDP_HIP_FLAG_TRACKING_COST 4u
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
