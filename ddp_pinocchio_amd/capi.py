@@ -23,7 +23,7 @@ MODEL_PENDULUM, MODEL_TREE = 0, 1
 EQ_NONE, EQ_CONFIG, EQ_FRAME = 0, 1, 2
 BUILTIN_PENDULUM, BUILTIN_CHAIN6, BUILTIN_TREE38, BUILTIN_CHAIN6_FF, BUILTIN_TREE38_FF = 0, 1, 2, 3, 4
 JOINT_REVOLUTE, JOINT_PRISMATIC, JOINT_FREEFLYER = 0, 1, 2
-FLAG_NO_TENSORS, FLAG_TRACE, FLAG_TRACKING_COST = 1, 2, 4
+FLAG_NO_TENSORS, FLAG_TRACE, FLAG_TRACKING_COST, FLAG_CONTROL_BOUNDS = 1, 2, 4, 8
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
 
 SEQ_NAMES = [
@@ -33,6 +33,7 @@ SEQ_NAMES = [
     "MULT_ORIGIN", "MULT_VAL", "MULT_JAC", "FB_ORIGIN", "FB_VAL", "FB_JAC",
     "VX_TRACE", "VXX_TRACE", "COSTS_OLD", "COSTS_NEW",
     "COST_XREF", "COST_WX", "COST_UREF", "COST_WU",
+    "CTRL_LO", "CTRL_HI", "BOX_STAT",
 ]
 SEQ = {name: i for i, name in enumerate(SEQ_NAMES)}
 
@@ -383,6 +384,28 @@ class Context:
                 arr = np.broadcast_to(arr, (count,) + shape)
             elif arr.shape != (count,) + shape:
                 raise ValueError(f"{name}: shape {arr.shape}, expected {shape} or {(count,) + shape}")
+            self.upload(name, arr, first, count)
+
+    def set_control_bounds(self, lo=None, hi=None, first=0, count=None):
+        """The control bounds lo <= u_t <= hi of instances first .. first + count - 1 (a context created with
+        FLAG_CONTROL_BOUNDS; ddp_hip.h): a scalar or an (m,) vector for every step, a (T, m) array for every instance of the
+        range, or (count, T, m) with one per instance.  -inf / +inf: no bound on that side.  None leaves that side as it is
+        (the library then checks lo <= hi at the next sweep)."""
+        count = self.batch - first if count is None else count
+        sp = self.spec
+        full = (count, sp.T, sp.m)
+        arrs = {}
+        for name, arr in (("CTRL_LO", lo), ("CTRL_HI", hi)):
+            if arr is None:
+                continue
+            arr = np.asarray(arr, dtype=np.float64)
+            if arr.ndim > 3 or (arr.ndim == 3 and arr.shape != full) or (arr.ndim == 2 and arr.shape != full[1:]) or \
+                    (arr.ndim == 1 and arr.shape != full[2:]):
+                raise ValueError(f"{name}: shape {arr.shape}, expected a scalar, {full[2:]}, {full[1:]} or {full}")
+            arrs[name] = np.ascontiguousarray(np.broadcast_to(arr, full))
+        if len(arrs) == 2 and bool(np.any(arrs["CTRL_LO"] > arrs["CTRL_HI"])):
+            raise ValueError("set_control_bounds: some lo > hi")
+        for name, arr in arrs.items():
             self.upload(name, arr, first, count)
 
     def fill(self, name, value):

@@ -37,6 +37,8 @@ struct BwdParams {
   int32_t njobs_half;
   int32_t half_mode;         // 1: symmetric tensors with two-entry upper halves (static mode-2 stencil); 2: this context's analytic mode-1
                              // tensors -- no symmetry, the upper half of every f_xx / f_ux column and all of f_uu exact zeros
+  const double *u, *ctrl_lo, *ctrl_hi;   // control bounds (DDP_HIP_FLAG_CONTROL_BOUNDS), else ctrl_lo / ctrl_hi null
+  double* box_stat;
   int32_t has_tensors;
   int32_t sym_tensors;  // f_xx is symmetric in its two input indices bit for bit (mode-2 / zero tensors of this context's own linearisation):
                         // K3 reads one of each pair of mirrored half-slabs (bwd_split.h, job kind 2)
@@ -253,7 +255,65 @@ __global__ __launch_bounds__(BS) void bwd_assemble(BwdParams p, int64_t t) {
   }
 }
 
-template <int NC, int MC>
+// ---- control bounds (ddp_hip.h: DDP_HIP_FLAG_CONTROL_BOUNDS): the box QP of one step by projected Newton iterations ----
+constexpr int BOX_MAX_ITER = 32;      // projected-Newton iterations per step
+constexpr int BOX_MAX_HALVINGS = 33;  // step sizes 2^0 .. 2^-33 of one Armijo search
+constexpr double BOX_ARMIJO = 0.1;
+constexpr double BOX_GRAD_TOL = 1e-10;
+
+__device__ __forceinline__ double box_clip(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// workgroup-level pieces of the box QP for bwd_gains (any shape, m <= 64 <= BS): every lane runs them, the results are uniform.
+// LLT of the lower triangle of A in place, the arithmetic of bwd_gains' own loop; true <=> a pivot <= 0
+__device__ bool box_llt(double* A, int lda, int m, int tid) {
+  for (int k = 0; k < m; ++k) {
+    const double piv = A[k + k * lda];
+    if (piv <= 0.0) return true;
+    const double dk = sqrt(piv);
+    for (int i = k + 1 + tid; i < m; i += BS) A[i + k * lda] = A[i + k * lda] / dk;
+    __syncthreads();
+    const int w = m - k - 1;
+    for (int idx = tid; idx < w * w; idx += BS) {
+      const int i = k + 1 + idx % w, j = k + 1 + idx / w;
+      if (j <= i) A[i + j * lda] -= A[i + k * lda] * A[j + k * lda];
+    }
+    if (tid == 0) A[k + k * lda] = dk;
+    __syncthreads();
+  }
+  return false;
+}
+// r <- (L L^T)^-1 r, one right-hand side, lane = row
+__device__ void box_solve(const double* A, int lda, int m, double* r, int tid) {
+  for (int k = 0; k < m; ++k) {
+    const double yk = r[k] / A[k + k * lda];
+    __syncthreads();
+    if (tid == k) r[k] = yk;
+    else if (tid > k && tid < m) r[tid] -= A[tid + k * lda] * yk;
+    __syncthreads();
+  }
+  for (int k = m - 1; k >= 0; --k) {
+    const double xk = r[k] / A[k + k * lda];
+    __syncthreads();
+    if (tid == k) r[k] = xk;
+    else if (tid < k) r[tid] -= A[k + tid * lda] * xk;
+    __syncthreads();
+  }
+}
+// obj(v) = 1/2 v^T H v + g^T v, summed in index order
+__device__ double box_obj(const double* H, int lda, int m, const double* g, const double* v, double* tmp, int tid) {
+  if (tid < m) {
+    double s = 0.0;
+    for (int j = 0; j < m; ++j) s += H[tid + j * lda] * v[j];
+    tmp[tid] = v[tid] * (0.5 * s + g[tid]);
+  }
+  __syncthreads();
+  double o = 0.0;
+  for (int j = 0; j < m; ++j) o += tmp[j];
+  __syncthreads();
+  return o;
+}
+
+template <int NC, int MC, bool BOX = false>
 __global__ __launch_bounds__(BS) void bwd_gains(BwdParams p, int64_t t) {
   const int b = blockIdx.x;
   if (p.status[b] != 0) return;
@@ -281,6 +341,94 @@ __global__ __launch_bounds__(BS) void bwd_gains(BwdParams p, int64_t t) {
   double* S = R + ldr * (n + 1);       // ldr * n      Q_ux
 
   const double reg = p.reg[b];
+  bool failed = false;
+  if constexpr (BOX) {
+    // The box QP (ddp_hip.h).  H = the symmetric matrix of the lower triangle of Q_uu + reg I; x starts at clip(0); every
+    // iteration factorises the masked matrix (rows and columns of clamped indices replaced by the identity's: LLT(H') is
+    // LLT(H_ff) with ones on the clamped diagonal) and searches along the projected Newton direction
+    double* H = S + ldr * n;             // lda * m
+    double* g = H + lda * m;             // m each: Q_u, x, lo - u, hi - u, gradient, direction, candidate, scratch
+    double *bx = g + m, *bl = bx + m, *bh = bl + m, *gr = bh + m, *dxv = gr + m, *xc = dxv + m, *tmp = xc + m;
+    int* cl = reinterpret_cast<int*>(tmp + m);
+    for (int idx = tid; idx < m * m; idx += BS) {
+      const int i = idx % m, j = idx / m;
+      H[i + j * lda] = (i >= j ? Quu[i + j * m] : Quu[j + i * m]) + (i == j ? reg : 0.0);
+    }
+    if (tid < m) {
+      const double ut = p.u[bt * m + tid];
+      const double lo = p.ctrl_lo[bt * m + tid] - ut, hi = p.ctrl_hi[bt * m + tid] - ut;
+      g[tid] = Qu[tid]; bl[tid] = lo; bh[tid] = hi;
+      bx[tid] = box_clip(0.0, lo, hi);
+    }
+    __syncthreads();
+    double gabs = 0.0;
+    for (int j = 0; j < m; ++j) gabs = fmax(gabs, fabs(g[j]));
+    const double tol = BOX_GRAD_TOL * fmax(1.0, gabs);
+    int iters = 0, nclamped = 0;
+    for (;; ++iters) {
+      if (tid < m) {
+        double s = 0.0;
+        for (int j = 0; j < m; ++j) s += H[tid + j * lda] * bx[j];
+        const double gv = g[tid] + s;
+        gr[tid] = gv;
+        cl[tid] = ((bx[tid] <= bl[tid] && gv > 0.0) || (bx[tid] >= bh[tid] && gv < 0.0)) ? 1 : 0;
+      }
+      __syncthreads();
+      double gmax = 0.0;
+      nclamped = 0;
+      for (int j = 0; j < m; ++j) { if (cl[j]) ++nclamped; else gmax = fmax(gmax, fabs(gr[j])); }
+      if (nclamped == m || gmax <= tol || iters == BOX_MAX_ITER) break;
+      for (int idx = tid; idx < m * m; idx += BS) {
+        const int i = idx % m, j = idx / m;
+        if (i >= j) A[i + j * lda] = (cl[i] || cl[j]) ? (i == j ? 1.0 : 0.0) : H[i + j * lda];
+      }
+      if (tid < m) dxv[tid] = cl[tid] ? 0.0 : -gr[tid];
+      __syncthreads();
+      failed = box_llt(A, lda, m, tid);
+      if (failed) break;
+      box_solve(A, lda, m, dxv, tid);
+      const double o0 = box_obj(H, lda, m, g, bx, tmp, tid);
+      bool taken = false;
+      double a = 1.0;
+      for (int hv = 0; hv <= BOX_MAX_HALVINGS && !taken; ++hv, a *= 0.5) {
+        if (tid < m) xc[tid] = box_clip(bx[tid] + a * dxv[tid], bl[tid], bh[tid]);
+        __syncthreads();
+        double gd = 0.0;
+        for (int j = 0; j < m; ++j) gd += gr[j] * (xc[j] - bx[j]);
+        const double o1 = box_obj(H, lda, m, g, xc, tmp, tid);   // (ends on a barrier: the next candidate may overwrite xc)
+        taken = o1 - o0 <= BOX_ARMIJO * gd;
+      }
+      if (!taken) break;                 // no step size accepted: x stays
+      __syncthreads();
+      if (tid < m) bx[tid] = xc[tid];
+      __syncthreads();
+    }
+    if (!failed) {
+      // polish on the final clamped set: with an empty set, operation for operation, the step without bounds
+      for (int idx = tid; idx < m * m; idx += BS) {
+        const int i = idx % m, j = idx / m;
+        if (i >= j) A[i + j * lda] = (cl[i] || cl[j]) ? (i == j ? 1.0 : 0.0) : H[i + j * lda];
+      }
+      if (tid < m) {
+        double r0;
+        if (cl[tid]) r0 = bx[tid];                                           // k_c: its bound
+        else if (nclamped == 0) r0 = -Qu[tid];
+        else {
+          double s = 0.0;
+          for (int j = 0; j < m; ++j) if (cl[j]) s += H[tid + j * lda] * bx[j];
+          r0 = -(g[tid] + s);                                                // -(g_f + H_fc k_c)
+        }
+        R[tid] = r0;
+      }
+      for (int idx = tid; idx < m * n; idx += BS) {
+        const int i = idx % m, j = idx / m;
+        const double q = Qux[idx];
+        R[i + (j + 1) * ldr] = cl[i] ? 0.0 : -q;                             // K_c = 0
+        S[i + j * ldr] = q;
+      }
+      if (tid == 0) { p.box_stat[bt * 2] = (double)nclamped; p.box_stat[bt * 2 + 1] = (double)iters; }
+    }
+  } else {
   for (int idx = tid; idx < m * m; idx += BS) {
     const int i = idx % m, j = idx / m;
     A[i + j * lda] = Quu[idx] + (i == j ? reg : 0.0);                        // ddp_bwd.ipp:104
@@ -292,12 +440,12 @@ __global__ __launch_bounds__(BS) void bwd_gains(BwdParams p, int64_t t) {
     R[i + (j + 1) * ldr] = -q;                                               // :136
     S[i + j * ldr] = q;
   }
+  }
   __syncthreads();
 
   // Cholesky, lower triangle only; the update order per entry (k ascending) equals the left-looking
   // order of Eigen's unblocked LLT.  Failure <=> a pivot is <= 0.
-  bool failed = false;
-  for (int k = 0; k < m; ++k) {
+  for (int k = 0; k < m && !failed; ++k) {
     const double piv = A[k + k * lda];
     if (piv <= 0.0) { failed = true; break; }
     const double dk = sqrt(piv);
@@ -383,7 +531,9 @@ size_t assemble_lds_bytes(const ddp_hip_ctx* ctx, int cn_max) {
 size_t gains_lds_bytes(const ddp_hip_ctx* ctx) {
   const Dims& d = ctx->d;
   int64_t ld = d.m | 1;
-  return (size_t)(ld * d.m + ld * (d.n + 1) + ld * d.n) * sizeof(double);
+  int64_t words = ld * d.m + ld * (d.n + 1) + ld * d.n;
+  if (ctx->flags & DDP_HIP_FLAG_CONTROL_BOUNDS) words += ld * d.m + 9 * d.m;   // H, eight vectors and the clamp flags of the box QP
+  return (size_t)words * sizeof(double);
 }
 
 BwdParams make_params(ddp_hip_ctx* ctx, const SweepPlan& plan) {
@@ -399,6 +549,7 @@ BwdParams make_params(ddp_hip_ctx* ctx, const SweepPlan& plan) {
   p.eq_val = S(DDP_HIP_SEQ_EQ_VAL); p.eq_x = S(DDP_HIP_SEQ_EQ_X); p.eq_u = S(DDP_HIP_SEQ_EQ_U);
   p.eq_xx = S(DDP_HIP_SEQ_EQ_XX); p.eq_ux = S(DDP_HIP_SEQ_EQ_UX); p.eq_uu = S(DDP_HIP_SEQ_EQ_UU);
   p.x = S(DDP_HIP_SEQ_X);
+  p.u = S(DDP_HIP_SEQ_U); p.ctrl_lo = S(DDP_HIP_SEQ_CTRL_LO); p.ctrl_hi = S(DDP_HIP_SEQ_CTRL_HI); p.box_stat = S(DDP_HIP_SEQ_BOX_STAT);
   p.mult_val = S(DDP_HIP_SEQ_MULT_VAL); p.mult_jac = S(DDP_HIP_SEQ_MULT_JAC);
   p.fb_origin = S(DDP_HIP_SEQ_FB_ORIGIN); p.fb_val = S(DDP_HIP_SEQ_FB_VAL); p.fb_jac = S(DDP_HIP_SEQ_FB_JAC);
   p.vx_trace = S(DDP_HIP_SEQ_VX_TRACE); p.vxx_trace = S(DDP_HIP_SEQ_VXX_TRACE);
@@ -413,7 +564,7 @@ BwdParams make_params(ddp_hip_ctx* ctx, const SweepPlan& plan) {
   return p;
 }
 
-template <int NC, int MC>
+template <int NC, int MC, bool BOX = false>
 int launch_sweep(ddp_hip_ctx* ctx, const BwdParams& p, size_t lds_a, size_t lds_g) {
   const Dims& d = ctx->d;
   hipLaunchKernelGGL(bwd_init, dim3((unsigned)d.batch), dim3(BS), 0, ctx->stream, p);
@@ -422,7 +573,7 @@ int launch_sweep(ddp_hip_ctx* ctx, const BwdParams& p, size_t lds_a, size_t lds_
     hipLaunchKernelGGL((bwd_assemble<NC, MC>), dim3((unsigned)ctx->njobs, (unsigned)d.batch), dim3(BS), lds_a, ctx->stream, p, t);
     prof_end(ctx, DDP_HIP_K_BWD_ASSEMBLE);
     prof_begin(ctx, DDP_HIP_K_BWD_GAINS);
-    hipLaunchKernelGGL((bwd_gains<NC, MC>), dim3((unsigned)d.batch), dim3(BS), lds_g, ctx->stream, p, t);
+    hipLaunchKernelGGL((bwd_gains<NC, MC, BOX>), dim3((unsigned)d.batch), dim3(BS), lds_g, ctx->stream, p, t);
     prof_end(ctx, DDP_HIP_K_BWD_GAINS);
   }
   HIP_TRY(hipGetLastError());
@@ -430,7 +581,7 @@ int launch_sweep(ddp_hip_ctx* ctx, const BwdParams& p, size_t lds_a, size_t lds_
 }
 
 // three-kernel step (bwd_v2.h): K5 dense terms on 8 workgroups per instance -> K3 tensor stream (+ P) -> K4' lean Riccati
-template <int NC, int MC>
+template <int NC, int MC, bool BOX>
 int enqueue_sweep_v2(ddp_hip_ctx* ctx, const BwdParams& p) {
   const Dims& d = ctx->d;
   const int cn_max = ctx->cbx > ctx->cbu ? ctx->cbx : ctx->cbu;
@@ -451,7 +602,7 @@ int enqueue_sweep_v2(ddp_hip_ctx* ctx, const BwdParams& p) {
       prof_end(ctx, DDP_HIP_K_BWD_ASSEMBLE);
     }
     prof_begin(ctx, DDP_HIP_K_BWD_GAINS);
-    hipLaunchKernelGGL((bwd_gains2<NC, MC>), dim3(B), dim3(BS4), 0, ctx->stream, p, t);
+    hipLaunchKernelGGL((bwd_gains2<NC, MC, BOX>), dim3(B), dim3(BS4), 0, ctx->stream, p, t);
     prof_end(ctx, DDP_HIP_K_BWD_GAINS);
   }
   HIP_TRY(hipGetLastError());
@@ -461,14 +612,14 @@ int enqueue_sweep_v2(ddp_hip_ctx* ctx, const BwdParams& p) {
 // The same enqueue, captured once into a hipGraph per state of the kernel arguments and replayed: the 600 launches of a
 // sweep become one submission of a straight chain.  Profiled sweeps (HIP events around kernels) and DDP_HIP_BWD_NO_GRAPH=1
 // take the direct path.
-template <int NC, int MC>
+template <int NC, int MC, bool BOX>
 int build_sweep_graph(ddp_hip_ctx* ctx, const BwdParams& p0, uint64_t key_misc, ddp_hip_ctx::BwdGraph** out) {
   ddp_hip_ctx::BwdGraph* slot = &ctx->bwd_graph[ctx->bwd_graph_next];
   ctx->bwd_graph_next = (ctx->bwd_graph_next + 1) % 4;
   if (slot->exec) { (void)hipGraphExecDestroy(slot->exec); slot->exec = nullptr; }
   if (slot->graph) { (void)hipGraphDestroy(slot->graph); slot->graph = nullptr; }
   HIP_TRY(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-  const int rc = enqueue_sweep_v2<NC, MC>(ctx, p0);
+  const int rc = enqueue_sweep_v2<NC, MC, BOX>(ctx, p0);
   hipGraph_t graph = nullptr;
   const hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
   if (rc != DDP_HIP_OK || e != hipSuccess || !graph) { (void)hipGetLastError(); if (graph) (void)hipGraphDestroy(graph); return rc != DDP_HIP_OK ? rc : DDP_HIP_E_HIP; }
@@ -479,12 +630,12 @@ int build_sweep_graph(ddp_hip_ctx* ctx, const BwdParams& p0, uint64_t key_misc, 
   return DDP_HIP_OK;
 }
 
-template <int NC, int MC>
+template <int NC, int MC, bool BOX = false>
 int launch_sweep_v2(ddp_hip_ctx* ctx, const BwdParams& p0) {
   const uint32_t bwd_mask = (2u << DDP_HIP_K_BWD_ASSEMBLE) | (2u << DDP_HIP_K_BWD_GAINS);
   // profiled sweeps take the direct path: events recorded by a graph's event-record nodes cannot be read back with
   // hipEventElapsedTime on this ROCm (hipErrorInvalidHandle -- tried)
-  if (ctx->sw.bwd_no_graph || (ctx->profile_mask & bwd_mask)) return enqueue_sweep_v2<NC, MC>(ctx, p0);
+  if (ctx->sw.bwd_no_graph || (ctx->profile_mask & bwd_mask)) return enqueue_sweep_v2<NC, MC, BOX>(ctx, p0);
   const uint64_t key_misc = (uint64_t)p0.has_tensors | ((uint64_t)(p0.vx_trace != nullptr) << 1) | ((uint64_t)p0.sym_tensors << 2) | ((uint64_t)(p0.jobs_half != nullptr) << 3) | ((uint64_t)p0.half_mode << 4);
   auto find = [&](const void* key_x) -> ddp_hip_ctx::BwdGraph* {
     for (auto& g : ctx->bwd_graph)
@@ -493,7 +644,7 @@ int launch_sweep_v2(ddp_hip_ctx* ctx, const BwdParams& p0) {
   };
   ddp_hip_ctx::BwdGraph* slot = find(p0.x);
   if (!slot) {
-    int rc = build_sweep_graph<NC, MC>(ctx, p0, key_misc, &slot);
+    int rc = build_sweep_graph<NC, MC, BOX>(ctx, p0, key_misc, &slot);
     if (rc != DDP_HIP_OK) return rc;
     // the trajectory buffers trade places after every iteration (ddp_hip_swap_traj) and x is the one kernel argument that
     // follows them: the twin graph is built now as well, so that no later sweep pays for a capture
@@ -501,8 +652,9 @@ int launch_sweep_v2(ddp_hip_ctx* ctx, const BwdParams& p0) {
     if (other && other != p0.x && !find(other)) {
       BwdParams p1 = p0;
       p1.x = other;
+      p1.u = ctx->seq[DDP_HIP_SEQ_U_NEW].ptr;      // (read by the box QP only: U trades places together with X)
       ddp_hip_ctx::BwdGraph* twin = nullptr;
-      rc = build_sweep_graph<NC, MC>(ctx, p1, key_misc, &twin);
+      rc = build_sweep_graph<NC, MC, BOX>(ctx, p1, key_misc, &twin);
       if (rc != DDP_HIP_OK) return rc;
       slot = find(p0.x);
       if (!slot) return DDP_HIP_E_HIP;
@@ -567,6 +719,10 @@ int bwd_setup(ddp_hip_ctx* ctx) {
     const size_t lds_5 = sizeof(double) * (size_t)(76 * 76 + 76 * (76 + 38) + 76 + d.emax);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_dense2<76, 38>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_5));
   }
+  if ((ctx->flags & DDP_HIP_FLAG_CONTROL_BOUNDS) && gains_lds_bytes(ctx) <= 160 * 1024) {
+    // the box QP keeps a second copy of Q_uu in LDS: past the default 64 KB of dynamic LDS from m = 35 on
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_gains<0, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gains_lds_bytes(ctx)));
+  }
   HIP_TRY(hipMalloc(&ctx->jobs_d, sizeof(BwdJob) * jobs.size()));
   HIP_TRY(hipMemcpy(ctx->jobs_d, jobs.data(), sizeof(BwdJob) * jobs.size(), hipMemcpyHostToDevice));
   if (n == 76 && m == 38 && cbx == 1) {
@@ -610,6 +766,8 @@ extern "C" int ddp_hip_backward(ddp_hip_ctx* ctx, double* reg_io, double* mu_io,
   const SweepPlan plan = sweep_plan(ctx);
   BwdParams p = make_params(ctx, plan);
   if (p.has_tensors && (!p.fxx || !p.fux || !p.fuu)) return DDP_HIP_E_UNSUPPORTED;
+  const bool box = (ctx->flags & DDP_HIP_FLAG_CONTROL_BOUNDS) != 0;
+  if (box) { const int rc_ = box_check(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
   // the static stencil leaves the f_xx block out that the symmetric sweep never reads: any other sweep needs it (the tensors
   // may have changed since the linearisation: upload / device_ptr)
   if (p.has_tensors && ctx->fxx_mirror_pending && !plan.sym) { const int rc_ = lin_materialize_fxx(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
@@ -630,9 +788,10 @@ extern "C" int ddp_hip_backward(ddp_hip_ctx* ctx, double* reg_io, double* mu_io,
   int rc = DDP_HIP_OK;
   for (int64_t attempt = 0;; ++attempt) {
     // the Talos-like shape runs K5 / K3 / K4' (sweep_plan); every other shape the run-time-shaped pair
-    if (plan.fast) rc = launch_sweep_v2<76, 38>(ctx, p);
-    else if (d.n == 12 && d.m == 6) rc = launch_sweep<12, 6>(ctx, p, lds_a, lds_g);
-    else rc = launch_sweep<0, 0>(ctx, p, lds_a, lds_g);
+    // (with control bounds: the box instantiations of the gains kernels)
+    if (plan.fast) rc = box ? launch_sweep_v2<76, 38, true>(ctx, p) : launch_sweep_v2<76, 38>(ctx, p);
+    else if (d.n == 12 && d.m == 6) rc = box ? launch_sweep<12, 6, true>(ctx, p, lds_a, lds_g) : launch_sweep<12, 6>(ctx, p, lds_a, lds_g);
+    else rc = box ? launch_sweep<0, 0, true>(ctx, p, lds_a, lds_g) : launch_sweep<0, 0>(ctx, p, lds_a, lds_g);
     if (rc != DDP_HIP_OK) return rc;
     HIP_TRY(hipMemcpyAsync(status.data(), ctx->status_d, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

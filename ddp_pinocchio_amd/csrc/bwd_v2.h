@@ -414,7 +414,53 @@ __device__ __forceinline__ void subst_phases(double (&r)[M], double (&La)[M - 1]
   if constexpr (K0 + STEPS < M) subst_phases<K0 + STEPS, M, LP, DIR>(r, La, Lb, lp, outp, dinvp);
 }
 
-template <int N, int M>
+// ---- control bounds: the in-wave pieces of the box QP of K4' (lane = row, wave 0) ----
+// sums / maxima over the wave in a fixed butterfly: every lane ends with the same bits
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int k = 32; k >= 1; k /= 2) v += __shfl_xor(v, k, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int k = 32; k >= 1; k /= 2) v = fmax(v, __shfl_xor(v, k, 64));
+  return v;
+}
+// the LLT of bwd_gains2 on the row a (consumed), into sL / sLt; diag = L(lane, lane); true <=> a pivot <= 0
+template <int M, int LP>
+__device__ __forceinline__ bool llt_wave(double (&a)[M], int lane, int m, double* sL, double* sLt, double& diag) {
+  const double piv = readlane_f64(a[0], 0);
+  bool failed = !(piv > 0.0);
+  const double dk = sqrt(piv);
+  double lik = lane == 0 ? dk : a[0] / dk;
+  if (lane > 0 && lane < m) { sL[lane - 1] = lik; sLt[lane * LP + (lane - 1)] = lik; }
+  diag = dk;
+  __builtin_amdgcn_wave_barrier();
+  const double* cj = static_cast<const double*>(__builtin_assume_aligned(sL, 16));
+  int k = 0;
+  chol_phases<0, M, LP>(a, lik, failed, k, cj, lane, m, sL, sLt, diag);
+  return failed;
+}
+// r <- (L L^T)^-1 r in the wave: one right-hand side, lane = row, the pivot broadcast with v_readlane, L from LDS
+template <int M, int LP>
+__device__ __forceinline__ double solve_wave(double r, double dinv, int lane, const double* sL, const double* sLt) {
+#pragma unroll 1
+  for (int k = 0; k < M; ++k) {
+    const double yk = readlane_f64(r, k) * readlane_f64(dinv, k);
+    const double lik = (lane > k && lane < M) ? sL[k * LP + (lane - 1 - k)] : 0.0;
+    r = lane == k ? yk : r - lik * yk;
+  }
+#pragma unroll 1
+  for (int k = M - 1; k >= 0; --k) {
+    const double xk = readlane_f64(r, k) * readlane_f64(dinv, k);
+    const double lki = lane < k ? sLt[k * LP + (k - 1 - lane)] : 0.0;
+    r = lane == k ? xk : r - lki * xk;
+  }
+  return r;
+}
+
+// BOX: the control-bounds instantiation (DDP_HIP_FLAG_CONTROL_BOUNDS), a kernel of its own: the kernel without it is the code it was
+template <int N, int M, bool BOX = false>
 __global__ __launch_bounds__(BS4) void bwd_gains2(BwdParams p, int64_t t) {
   constexpr int n = N, m = M, NR = N + 1;
   const int nx = (int)p.d.nx;        // N + 1 with a free-flyer root
@@ -435,6 +481,8 @@ __global__ __launch_bounds__(BS4) void bwd_gains2(BwdParams p, int64_t t) {
   __shared__ double sDinv[M], sQ[N + M];
   double* const sLt = sLt_ + 2 * LP;   // rows -2, -1 exist (zero): the backward loop prefetches two rows ahead without a clamp
   __shared__ int s_failed;
+  __shared__ double sB[BOX ? M : 1];             // box QP: the first right-hand side, [-(g_f + H_fc k_c) ; k_c]
+  __shared__ unsigned long long s_cmask;         // ... and the clamped set
 
   double* Vx = p.ws_V + (int64_t)b * (n + n * n);
   double* Vxx = Vx + n;
@@ -451,6 +499,83 @@ __global__ __launch_bounds__(BS4) void bwd_gains2(BwdParams p, int64_t t) {
   if (wave == 0) {
     if (tid == 0) s_failed = 0;
     const double reg = p.reg[b];
+    if constexpr (BOX) {
+      // The box QP (ddp_hip.h) in this wave, no workgroup barrier.  The lane's full row of H = sym(lower(Q_uu + reg I)) is parked
+      // in the LDS of [k | K] (idle until the substitutions; beside the running row and the pivot column of the LLT it would not
+      // fit the register file).  Every pass forms the gradient (x broadcast lane by lane with v_readlane), takes the clamped set
+      // as one ballot and runs the LLT on the masked row (rows / columns of clamped indices from the identity); unless the
+      // iteration stops there it solves the one right-hand side in the wave and searches along the projected Newton direction.
+      // The pass that stops has factorised the final set: that factor is the polish's.
+      for (int i = lane; i < (M + 2) * LP; i += 64) { sL[i] = 0.0; sLt_[i] = 0.0; }
+      const bool act = lane < m;
+      const int li = act ? lane : m - 1;
+      double* sH = sK + li;                          // H(lane, j) at sH[j * M]: written and read by this lane alone
+#pragma unroll
+      for (int j = 0; j < M; ++j) {
+        double qv_ = j <= li ? Quu[li + j * m] : Quu[j + li * m];
+        qv_ = qv_ + (li == j ? reg : 0.0);
+        if (act) sH[j * M] = qv_;
+      }
+      const double ut = p.u[bt * m + li];
+      const double g = act ? Q[n + li] : 0.0;
+      const double bl = act ? p.ctrl_lo[bt * m + li] - ut : -INFINITY, bh = act ? p.ctrl_hi[bt * m + li] - ut : INFINITY;
+      double x = box_clip(0.0, bl, bh);
+      const double tol = BOX_GRAD_TOL * fmax(1.0, wave_max(fabs(g)));
+      auto row_times = [&](double v) {               // (H v)_lane
+        double s_ = 0.0;
+#pragma unroll
+        for (int j = 0; j < M; ++j) s_ += sH[j * M] * readlane_f64(v, j);
+        return act ? s_ : 0.0;
+      };
+      unsigned long long cm = 0;
+      bool c = false, failed = false;
+      double diag = 1.0;
+      int iters = 0;
+#pragma unroll 1
+      for (;; ++iters) {
+        asm volatile("" ::: "memory");               // (H is read from LDS where it is used: hoisted out of the loop it would take the registers it was parked for)
+        const double hx = row_times(x);
+        const double grad = g + hx;
+        c = act && ((x <= bl && grad > 0.0) || (x >= bh && grad < 0.0));
+        cm = __ballot(c);
+        const double gmax = wave_max((act && !c) ? fabs(grad) : 0.0);
+        // (the butterflies leave the same bits in every lane: the branches on them are made scalar)
+        const bool stop = __builtin_amdgcn_readfirstlane((int)(__popcll(cm) == m || gmax <= tol || iters == BOX_MAX_ITER)) != 0;
+        int ln = lane;
+        asm volatile("" : "+v"(ln));                 // (the loop's invariants in `lane` -- 38 constants lane == j ? 1 : 0, the LDS addresses of every
+                                                     // phase of the LLT -- are formed where they are used, not hoisted out of the loop and held)
+#pragma unroll
+        for (int j = 0; j < M; ++j) a[j] = (act && j <= ln) ? ((c || ((cm >> j) & 1)) ? (ln == j ? 1.0 : 0.0) : sH[j * M]) : 0.0;
+        failed = llt_wave<M, LP>(a, ln, m, sL, sLt, diag);
+        asm volatile("" ::: "memory");
+        if (failed || stop) break;
+        double dx = solve_wave<M, LP>(c ? 0.0 : -grad, 1.0 / diag, ln, sL, sLt);
+        dx = act ? dx : 0.0;
+        const double o0 = wave_sum(x * (0.5 * hx + g));
+        bool taken = false;
+        double al = 1.0, xc = x;
+#pragma unroll 1
+        for (int hv = 0; hv <= BOX_MAX_HALVINGS && !taken; ++hv, al *= 0.5) {
+          asm volatile("" ::: "memory");
+          xc = box_clip(x + al * dx, bl, bh);
+          const double o1 = wave_sum(xc * (0.5 * row_times(xc) + g));
+          const double gd = wave_sum(grad * (xc - x));
+          taken = __builtin_amdgcn_readfirstlane((int)(o1 - o0 <= BOX_ARMIJO * gd)) != 0;
+        }
+        if (!taken) break;                           // no step size accepted: x stays, and so does the set just factorised
+        x = xc;
+      }
+      if (!failed) {
+        // the polish's first right-hand side [-(g_f + H_fc k_c) ; k_c] (terms of other indices left out); with an empty set: -Q_u
+        double sc = 0.0;
+#pragma unroll
+        for (int j = 0; j < M; ++j) if ((cm >> j) & 1) sc += sH[j * M] * readlane_f64(x, j);
+        const double r0 = c ? x : (cm == 0 ? -g : -(g + sc));
+        if (act) { sB[lane] = r0; sDinv[lane] = 1.0 / diag; }
+        if (lane == 0) { s_cmask = cm; p.box_stat[bt * 2] = (double)__popcll(cm); p.box_stat[bt * 2 + 1] = (double)iters; }
+      }
+      if (failed && lane == 0) s_failed = 1;
+    } else {
     // row `lane` of the lower triangle of Q_uu + reg I (ddp_bwd.ipp:104), entry j at a[j]
 #pragma unroll
     for (int j = 0; j < M; ++j) {
@@ -459,6 +584,7 @@ __global__ __launch_bounds__(BS4) void bwd_gains2(BwdParams p, int64_t t) {
       a[j] = qv_;
     }
     for (int i = lane; i < (M + 2) * LP; i += 64) { sL[i] = 0.0; sLt_[i] = 0.0; }
+    }
   } else {
     constexpr int BSO = BS4 - 64;
     const int to = tid - 64;
@@ -467,6 +593,7 @@ __global__ __launch_bounds__(BS4) void bwd_gains2(BwdParams p, int64_t t) {
   }
   STAMP(9);
   if (wave == 0) {
+    if constexpr (!BOX) {
     // Cholesky, lower triangle only; fail <=> pivot <= 0 (:105).  Per entry the updates arrive in ascending k: the order
     // of Eigen's unblocked LLT.  After step k the row is shifted: a[p] holds entry (lane, k+1+p).
     // Software-pipelined over the columns: the next pivot only needs entry (lane, k+1) updated with column k -- one
@@ -489,6 +616,7 @@ __global__ __launch_bounds__(BS4) void bwd_gains2(BwdParams p, int64_t t) {
     chol_phases<0, M, LP>(a, lik, failed, k, cj, lane, m, sL, sLt, diag);
     if (lane < m) sDinv[lane] = 1.0 / diag;        // (garbage on a failed factorisation: nobody reads it then)
     if (failed && lane == 0) s_failed = 1;
+    }
   } else if (wave == 3) {
     double* fbo = p.fb_origin + bt * nx;
     const double* xt = p.x + ((int64_t)b * (T + 1) + t) * nx;
@@ -513,8 +641,14 @@ __global__ __launch_bounds__(BS4) void bwd_gains2(BwdParams p, int64_t t) {
   const int rc = tid - 64;
   if (rc >= 0 && rc < NR) {
     double r[M];
+    if constexpr (BOX) {
+      const unsigned long long cm = s_cmask;
+#pragma unroll
+      for (int l = 0; l < m; ++l) r[l] = rc == 0 ? sB[l] : (((cm >> l) & 1) ? 0.0 : -sU[l + (rc - 1) * LD]);
+    } else {
 #pragma unroll
     for (int l = 0; l < m; ++l) r[l] = -(rc == 0 ? sQ[n + l] : sU[l + (rc - 1) * LD]);
+    }
     double* out = sK + rc * LD;
     // forward: y_k = r_k / L_kk, r_l -= L_lk y_k (l > k); the running column is shifted so that the pivot is r[0].
     // Column k+1 of L is fetched (LDS broadcasts) while column k is applied: two register buffers, the loop unrolled by 2.

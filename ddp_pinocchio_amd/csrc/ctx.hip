@@ -173,6 +173,8 @@ static int64_t seq_size_of(const Dims& d, int s) {
     case DDP_HIP_SEQ_COST_XREF: return (T + 1) * nx;
     case DDP_HIP_SEQ_COST_WX: return (T + 1) * n;
     case DDP_HIP_SEQ_COST_UREF: case DDP_HIP_SEQ_COST_WU: return T * m;
+    case DDP_HIP_SEQ_CTRL_LO: case DDP_HIP_SEQ_CTRL_HI: return T * m;
+    case DDP_HIP_SEQ_BOX_STAT: return T * 2;
     default: return -1;
   }
 }
@@ -183,6 +185,7 @@ static bool is_tensor_seq(int s) {
 }
 static bool is_trace_seq(int s) { return s == DDP_HIP_SEQ_VX_TRACE || s == DDP_HIP_SEQ_VXX_TRACE; }
 static bool is_cost_seq(int s) { return s >= DDP_HIP_SEQ_COST_XREF && s <= DDP_HIP_SEQ_COST_WU; }
+static bool is_box_seq(int s) { return s >= DDP_HIP_SEQ_CTRL_LO && s <= DDP_HIP_SEQ_BOX_STAT; }
 static bool nan_init_seq(int s) {
   // mat_seq_t storage is NaN-poisoned at construction (detail/mat_seq.hpp:34-37); uninit_derivative_storage
   // then zeroes every derivative sequence except f_val, and leaves lfx / lfxx NaN (ddp.hpp:441-442,476-511)
@@ -318,13 +321,15 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   const double qnan = std::numeric_limits<double>::quiet_NaN();
   for (int s = 0; s < DDP_HIP_SEQ_COUNT; ++s) {
     int64_t sz = seq_size_of(d, s);
+    if (!(flags & DDP_HIP_FLAG_CONTROL_BOUNDS) && is_box_seq(s)) sz = 0;   // (ddp_hip_seq_size: 0, uploads refused)
     ctx->seq[s].size = sz;
     if ((flags & DDP_HIP_FLAG_NO_TENSORS) && is_tensor_seq(s)) continue;
     if (!(flags & DDP_HIP_FLAG_TRACE) && is_trace_seq(s)) continue;
     if (!(flags & DDP_HIP_FLAG_TRACKING_COST) && is_cost_seq(s)) continue;
     if (sz <= 0) continue;
     CTX_TRY(hipMalloc(&ctx->seq[s].ptr, sizeof(double) * (size_t)(sz * d.batch)));
-    if (fill_device(ctx, ctx->seq[s].ptr, sz * d.batch, nan_init_seq(s) ? qnan : 0.0) != DDP_HIP_OK) {
+    const double v0 = s == DDP_HIP_SEQ_CTRL_LO ? -INFINITY : s == DDP_HIP_SEQ_CTRL_HI ? INFINITY : nan_init_seq(s) ? qnan : 0.0;
+    if (fill_device(ctx, ctx->seq[s].ptr, sz * d.batch, v0) != DDP_HIP_OK) {
       ddp_hip_destroy(ctx);
       return DDP_HIP_E_HIP;
     }
@@ -407,7 +412,15 @@ static int check_range(ddp_hip_ctx* ctx, int seq, int64_t first, int64_t count) 
 static bool cost_weight_ok(double w) { return isfinite(w) && w >= 0.0; }
 static bool cost_quat_ok(double norm2) { return isfinite(norm2) && fabs(sqrt(norm2) - 1.0) <= 1e-10; }
 
+// what a control bound accepts (DDP_HIP_FLAG_CONTROL_BOUNDS): no NaN, no lower bound of +inf, no upper bound of -inf
+static bool bound_ok(int seq, double v) { return !isnan(v) && !(seq == DDP_HIP_SEQ_CTRL_LO ? v == INFINITY : v == -INFINITY); }
+
 static bool cost_values_ok(const ddp_hip_ctx* ctx, int seq, const double* host, int64_t words) {
+  if (seq == DDP_HIP_SEQ_CTRL_LO || seq == DDP_HIP_SEQ_CTRL_HI) {
+    for (int64_t i = 0; i < words; ++i)
+      if (!bound_ok(seq, host[i])) return false;
+    return true;
+  }
   if (seq == DDP_HIP_SEQ_COST_WX || seq == DDP_HIP_SEQ_COST_WU) {
     for (int64_t i = 0; i < words; ++i)
       if (!cost_weight_ok(host[i])) return false;
@@ -424,6 +437,7 @@ extern "C" int ddp_hip_upload(ddp_hip_ctx* ctx, int seq, const double* host, int
   int rc = check_range(ctx, seq, first, count);
   if (rc != DDP_HIP_OK) return rc;
   int64_t sz = ctx->seq[seq].size;
+  if (is_box_seq(seq) && !(ctx->flags & DDP_HIP_FLAG_CONTROL_BOUNDS)) return DDP_HIP_E_UNSUPPORTED;
   if (sz == 0 || count == 0) return DDP_HIP_OK;
   if (!host) return DDP_HIP_E_ARG;
   if (!cost_values_ok(ctx, seq, host, sz * count)) return DDP_HIP_E_ARG;
@@ -435,6 +449,22 @@ extern "C" int ddp_hip_upload(ddp_hip_ctx* ctx, int seq, const double* host, int
   }
   HIP_TRY(hipMemcpyAsync(ctx->seq[seq].ptr + first * sz, host, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (seq == DDP_HIP_SEQ_CTRL_LO || seq == DDP_HIP_SEQ_CTRL_HI) ctx->box_dirty = true;
+  return DDP_HIP_OK;
+}
+
+// lo <= hi can only be checked once both sequences are there: the sweeps ask before they launch, and the bounds are read
+// back only after an upload of either
+int box_check(ddp_hip_ctx* ctx) {
+  if (!ctx->box_dirty) return DDP_HIP_OK;
+  const size_t words = (size_t)(ctx->seq[DDP_HIP_SEQ_CTRL_LO].size * ctx->d.batch);
+  std::vector<double> lo(words), hi(words);
+  HIP_TRY(hipMemcpyAsync(lo.data(), ctx->seq[DDP_HIP_SEQ_CTRL_LO].ptr, sizeof(double) * words, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(hi.data(), ctx->seq[DDP_HIP_SEQ_CTRL_HI].ptr, sizeof(double) * words, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < words; ++i)
+    if (lo[i] > hi[i]) return DDP_HIP_E_ARG;
+  ctx->box_dirty = false;
   return DDP_HIP_OK;
 }
 
@@ -456,6 +486,8 @@ extern "C" int ddp_hip_fill(ddp_hip_ctx* ctx, int seq, double value) {
   if (rc != DDP_HIP_OK) return rc;
   if ((seq == DDP_HIP_SEQ_COST_WX || seq == DDP_HIP_SEQ_COST_WU) && !cost_weight_ok(value)) return DDP_HIP_E_ARG;
   if (seq == DDP_HIP_SEQ_COST_XREF && ctx->model_h.ff && !cost_quat_ok(4 * value * value)) return DDP_HIP_E_ARG;
+  if ((seq == DDP_HIP_SEQ_CTRL_LO || seq == DDP_HIP_SEQ_CTRL_HI) && !bound_ok(seq, value)) return DDP_HIP_E_ARG;
+  if (seq == DDP_HIP_SEQ_CTRL_LO || seq == DDP_HIP_SEQ_CTRL_HI) ctx->box_dirty = true;
   HIP_TRY(hipSetDevice(ctx->device));
   if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUX || seq == DDP_HIP_SEQ_FUU) { ctx->tensor_tops_zero = false; ctx->tensor_tops_sparse = false; ctx->fuu_zero = false; }
   if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUU) {

@@ -8,6 +8,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "internal.h"
@@ -37,6 +38,7 @@ struct FwdParams {
   double* fw_cost;               // [batch][n_alpha][T+1] cost terms of the candidates (constrained problems on the latency path)
   const double *xref, *wx, *uref, *wu;   // tracking cost (DDP_HIP_FLAG_TRACKING_COST), else null
   int32_t track;
+  const double *ctrl_lo, *ctrl_hi;       // control bounds (DDP_HIP_FLAG_CONTROL_BOUNDS), else null
 };
 
 // constraint value at solver time t: constraint_advance_time_t::eval_to (problem.hpp:563-567) applied
@@ -212,6 +214,12 @@ __global__ void forward_kernel(FwdParams p) {
       for (int l = 0; l < n; ++l) s += K[i + l * nu] * dx[l];
       u[i] += s;                                                              // :49
     }
+    if (p.ctrl_lo) {
+      // control bounds: this form, not fmin / fmax -- the NaN of a diverged candidate stays a NaN
+      const double* lo = p.ctrl_lo + ((int64_t)b * T + t) * nu;
+      const double* hi = p.ctrl_hi + ((int64_t)b * T + t) * nu;
+      for (int i = 0; i < nu; ++i) u[i] = u[i] < lo[i] ? lo[i] : (u[i] > hi[i] ? hi[i] : u[i]);
+    }
     for (int i = 0; i < nu; ++i) uw[t * nu + i] = u[i];
     const double c_new = stage_cost<NJ>(p, m, b, t, x, u, mu);
     dsum += c_new - cold[t];
@@ -279,6 +287,12 @@ struct FwdLat2Lds {
   rbd::CoopModel<NJ> model;
 };
 
+// ... of the control-bounds instantiations: lo_t, hi_t beside k_t
+template <int NJ>
+struct FwdLat2LdsBox : FwdLat2Lds<NJ> {
+  double lo[NJ], hi[NJ];
+};
+
 #ifdef FWD_STAMPS
 __device__ unsigned long long g_fwd_stamps[12];
 #endif
@@ -288,9 +302,12 @@ __device__ unsigned long long g_fwd_stamps[12];
 // rbd::aba_tree_coop2w's free-flyer form
 // TRACK: the tracking cost (DDP_HIP_FLAG_TRACKING_COST) of an unconstrained problem, formed inline by the 16 lanes of a candidate
 // (track_lanes_sum); an instantiation of its own, so that the kernel without it is the one it was
-template <int NJ, bool OPEN = false, bool FF = false, bool TRACK = false>
+// BOX: control bounds (DDP_HIP_FLAG_CONTROL_BOUNDS): u is clamped to [lo_t, hi_t] after the control update; lo_t, hi_t ride in the
+// prefetch beside k_t.  Closed loop only, an instantiation of its own as well
+template <int NJ, bool OPEN = false, bool FF = false, bool TRACK = false, bool BOX = false>
 __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
-  using L = FwdLat2Lds<NJ>;
+  static_assert(!(OPEN && BOX), "the open-loop rollout applies U as given");
+  using L = typename std::conditional<BOX, FwdLat2LdsBox<NJ>, FwdLat2Lds<NJ>>::type;
   constexpr int NC = L::NC, NH = L::NH;
   constexpr int n = 2 * NJ, nq = FF ? NJ + 1 : NJ, nx = nq + NJ, nu = NJ, XS = L::n;   // XS: stride of a candidate's state in LDS
   constexpr int K2 = nu * n / 2, KR = (K2 + 63) / 64;        // K_t as 16-byte words; words per lane
@@ -354,6 +371,7 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
   typedef double d2 __attribute__((ext_vector_type(2)));
   d2 Kreg[KR];
   double kreg = 0.0, uoreg = 0.0, xoreg0 = 0.0, xoreg1 = 0.0, coldreg = 0.0;
+  [[maybe_unused]] double loreg = 0.0, hireg = 0.0;
   auto request = [&](int64_t t) {                    // step t's operands: K_t, k_t, u_old,t, x_old,t, the old cost term
     const int iu = tid < nu ? tid : nu - 1;
     uoreg = uo[t * nu + iu];
@@ -362,6 +380,7 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
 #pragma unroll
       for (int j = 0; j < KR; ++j) { const int e = j * 64 + tid; Kreg[j] = Kt[e < K2 ? e : K2 - 1]; }
       kreg = kg[t * nu + iu];
+      if constexpr (BOX) { loreg = p.ctrl_lo[((int64_t)b * T + t) * nu + iu]; hireg = p.ctrl_hi[((int64_t)b * T + t) * nu + iu]; }
       xoreg0 = xo[t * nx + (tid < nx ? tid : nx - 1)];
       xoreg1 = xo[t * nx + (64 + tid < nx ? 64 + tid : nx - 1)];
       coldreg = cold[t];
@@ -374,6 +393,7 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
 #pragma unroll
       for (int j = 0; j < KR; ++j) { const int e = j * 64 + tid; if (e < K2) Ks[e] = Kreg[j]; }
       if (tid < nu) S.k[tid] = kreg;
+      if constexpr (BOX) { if (tid < nu) { S.lo[tid] = loreg; S.hi[tid] = hireg; } }
       if (tid < nx) S.xo[tid] = xoreg0;
       if (64 + tid < nx) S.xo[64 + tid] = xoreg1;
     }
@@ -438,6 +458,7 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
         if (i < nu && live) {
           double ui = S.uo[i] + step * S.k[i];                                  // :47-48
           ui += acc[r];                                                         // :49
+          if constexpr (BOX) { const double lo = S.lo[i], hi = S.hi[i]; ui = ui < lo ? lo : (ui > hi ? hi : ui); }   // (a NaN stays a NaN)
           u[i] = ui;
           uw[t * nu + i] = ui;
         }
@@ -615,6 +636,7 @@ FwdParams make_params(ddp_hip_ctx* ctx) {
   p.xref = S(DDP_HIP_SEQ_COST_XREF); p.wx = S(DDP_HIP_SEQ_COST_WX); p.uref = S(DDP_HIP_SEQ_COST_UREF); p.wu = S(DDP_HIP_SEQ_COST_WU);
   p.cost_inline = ctx->d.Etot == 0 ? 1 : 0;
   p.fw_cost = ctx->fw_cost;
+  p.ctrl_lo = S(DDP_HIP_SEQ_CTRL_LO); p.ctrl_hi = S(DDP_HIP_SEQ_CTRL_HI);
   p.round = 0;
   return p;
 }
@@ -665,6 +687,13 @@ int fwd_setup(ddp_hip_ctx* ctx) {
                                 (int)sizeof(FwdLat2Lds<38>)));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)sizeof(FwdLat2Lds<38>)));
+    if (ctx->flags & DDP_HIP_FLAG_CONTROL_BOUNDS) {
+      const int lds_box = (int)sizeof(FwdLat2LdsBox<38>);
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_box));
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_box));
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, false, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_box));
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, false, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_box));
+    }
   }
   return DDP_HIP_OK;
 }
@@ -736,6 +765,7 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
   const Dims& d = ctx->d;
   const int64_t B = d.batch;
   HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->flags & DDP_HIP_FLAG_CONTROL_BOUNDS) { const int rc_ = box_check(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
   HIP_TRY(hipMemcpyAsync(ctx->mu_d, mu, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, ctx->stream));
   std::vector<int32_t> state((size_t)B);
   for (int64_t b = 0; b < B; ++b) state[(size_t)b] = ctx->active_h[(size_t)b] ? 0 : 1;   // a frozen instance is not searched
@@ -757,7 +787,14 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
     if (lat_path) {
       const dim3 g((unsigned)(2 * B)), blk(128);
       const size_t lds = sizeof(FwdLat2Lds<38>);
-      if (p.track && p.cost_inline) {
+      if (p.ctrl_lo) {
+        const size_t ldb = sizeof(FwdLat2LdsBox<38>);
+        const bool tr = p.track && p.cost_inline;
+        if (tr && ctx->model_h.ff) hipLaunchKernelGGL((forward_kernel_lat2<38, false, true, true, true>), g, blk, ldb, ctx->stream, p);
+        else if (tr) hipLaunchKernelGGL((forward_kernel_lat2<38, false, false, true, true>), g, blk, ldb, ctx->stream, p);
+        else if (ctx->model_h.ff) hipLaunchKernelGGL((forward_kernel_lat2<38, false, true, false, true>), g, blk, ldb, ctx->stream, p);
+        else hipLaunchKernelGGL((forward_kernel_lat2<38, false, false, false, true>), g, blk, ldb, ctx->stream, p);
+      } else if (p.track && p.cost_inline) {
         if (ctx->model_h.ff) hipLaunchKernelGGL((forward_kernel_lat2<38, false, true, true>), g, blk, lds, ctx->stream, p);
         else hipLaunchKernelGGL((forward_kernel_lat2<38, false, false, true>), g, blk, lds, ctx->stream, p);
       } else if (ctx->model_h.ff) hipLaunchKernelGGL((forward_kernel_lat2<38, false, true>), g, blk, lds, ctx->stream, p);

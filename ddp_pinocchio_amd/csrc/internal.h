@@ -169,6 +169,8 @@ struct ddp_hip_ctx {
   std::vector<int32_t> active_h;   // [batch], 1 = active
   bool all_active = true;
 
+  bool box_dirty = false;       // CTRL_LO / CTRL_HI were uploaded since lo <= hi was last checked (ctx.hip: box_check)
+
   bool async_mode = false;     // ddp_hip_set_async: entry points that hand nothing back to the host do not wait for the stream
   uint32_t profile_mask = 0;   // bit (1 + kernel_id): that kernel class is bracketed by HIP events
   ProfSlot prof[DDP_HIP_K_COUNT];
@@ -191,6 +193,7 @@ void prof_end(ddp_hip_ctx* ctx, int kid, hipStream_t stream = nullptr);
 int bwd_setup(ddp_hip_ctx* ctx);
 SweepPlan sweep_plan(const ddp_hip_ctx* ctx);
 void bwd_teardown(ddp_hip_ctx* ctx);
+int box_check(ddp_hip_ctx* ctx);                  // control bounds: DDP_HIP_E_ARG if an upload left some lo > hi (ctx.hip)
 int fwd_setup(ddp_hip_ctx* ctx);
 bool fwd_lat_supported(const ddp_hip_ctx* ctx);   // the latency kernels of the forward sweep apply (tree, no constraints, Talos size)
 void fwd_teardown(ddp_hip_ctx* ctx);

@@ -25,6 +25,7 @@ struct OuterParams {
   double *f_origin, *f_val, *f_jac;   // control feedback (rows m)
   const double* mu;                   // [batch], device
   double* out;                        // [batch][2]: optimality_obj, optimality_constr
+  const double *u, *ctrl_lo, *ctrl_hi;  // control bounds (DDP_HIP_FLAG_CONTROL_BOUNDS), else ctrl_lo / ctrl_hi null
 };
 
 constexpr int OBS = 128;
@@ -127,7 +128,14 @@ __global__ __launch_bounds__(OBS) void optimality_kernel(OuterParams p) {
     __syncthreads();
     if (tid == 0) {                               // norms in index order, like the reference's .norm() on a short vector
       double nr = 0.0;
-      for (int j = 0; j < m; ++j) nr += lu[j] * lu[j];
+      for (int j = 0; j < m; ++j) {
+        if (p.ctrl_lo) {
+          // a control on a bound whose gradient points out of the box is at its optimum: left out of the norm
+          const double uj = p.u[bt * m + j];
+          if ((uj <= p.ctrl_lo[bt * m + j] && lu[j] >= 0.0) || (uj >= p.ctrl_hi[bt * m + j] && lu[j] <= 0.0)) continue;
+        }
+        nr += lu[j] * lu[j];
+      }
       nr = sqrt(nr);
       if (nr > obj) obj = nr;
       double s = 0.0;
@@ -200,6 +208,7 @@ OuterParams make_params(ddp_hip_ctx* ctx) {
   p.m_origin = S(DDP_HIP_SEQ_MULT_ORIGIN); p.m_val = S(DDP_HIP_SEQ_MULT_VAL); p.m_jac = S(DDP_HIP_SEQ_MULT_JAC);
   p.f_origin = S(DDP_HIP_SEQ_FB_ORIGIN); p.f_val = S(DDP_HIP_SEQ_FB_VAL); p.f_jac = S(DDP_HIP_SEQ_FB_JAC);
   p.mu = ctx->mu_d;
+  p.u = S(DDP_HIP_SEQ_U); p.ctrl_lo = S(DDP_HIP_SEQ_CTRL_LO); p.ctrl_hi = S(DDP_HIP_SEQ_CTRL_HI);
   p.out = ctx->ws_Q;      // two doubles per instance of the backward workspace, idle between sweeps
   return p;
 }

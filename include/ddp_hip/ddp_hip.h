@@ -120,6 +120,10 @@ enum ddp_hip_seq {
   DDP_HIP_SEQ_COST_WX,     /* [T+1][n]  state weights, tangent rows (create: 0) */
   DDP_HIP_SEQ_COST_UREF,   /* [T][m]    reference controls (create: 0) */
   DDP_HIP_SEQ_COST_WU,     /* [T][m]    control weights (create: 0) */
+  /* per-instance control bounds (DDP_HIP_FLAG_CONTROL_BOUNDS; not allocated without it) */
+  DDP_HIP_SEQ_CTRL_LO,     /* [T][m]    lower bounds on u_t (create: -inf = none) */
+  DDP_HIP_SEQ_CTRL_HI,     /* [T][m]    upper bounds on u_t (create: +inf = none) */
+  DDP_HIP_SEQ_BOX_STAT,    /* [T][2]    written by ddp_hip_backward: clamped controls, projected-Newton iterations of step t */
   DDP_HIP_SEQ_COUNT
 };
 
@@ -141,6 +145,18 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * A term of weight 0 is left out (not multiplied by 0): with all weights 0 a context computes bit for bit what it computes
  * without the flag. */
 #define DDP_HIP_FLAG_TRACKING_COST 4u
+/* Allocate CTRL_LO / CTRL_HI / BOX_STAT and keep lo[t] <= u_t <= hi[t], per instance (control-limited DDP: Tassa, Mansard,
+ * Todorov, ICRA 2014).  The backward step solves, instead of Q_uu k = -Q_u over R^m, the box QP
+ *   min_k 1/2 k^T H k + Q_u^T k,  lo_t - u_t <= k <= hi_t - u_t,   H = Q_uu + reg I (lower triangle)
+ * by projected Newton steps (at most 32; Armijo 0.1, halving) from k = clip(0), then takes k and K from the final clamped set
+ * alone: k_c on its bound, k_f = -H_ff^-1 (Q_u,f + H_fc k_c), K_c = 0, K_f = -H_ff^-1 Q_ux,f.  A pivot <= 0 of any H_ff fails the
+ * step as ddp_bwd.ipp:105-110 does.  V_x / V_xx keep the reference's lines.  The forward rollouts clamp u = u < lo ? lo : (u > hi ?
+ * hi : u) after the control update (ddp_fwd.ipp:47-49; ddp_hip_rollout applies U as given), and optimality_obj leaves out the
+ * components of a control on a bound whose gradient points out of the box.  -inf / +inf: no bound on that side.  ddp_hip_upload
+ * refuses (DDP_HIP_E_ARG) a NaN, a lo of +inf, a hi of -inf; ddp_hip_backward / ddp_hip_forward return DDP_HIP_E_ARG if some
+ * lo > hi (checked after an upload of either); writes through ddp_hip_device_ptr are the caller's responsibility.  With bounds
+ * that never bind a context computes bit for bit what it computes without the flag. */
+#define DDP_HIP_FLAG_CONTROL_BOUNDS 8u
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
