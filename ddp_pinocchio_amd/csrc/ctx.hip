@@ -224,6 +224,7 @@ static DevSwitches read_switches() {
   sw.fxx_full = on("DDP_HIP_FXX_FULL");
   sw.no_static = on("DDP_HIP_NO_STATIC");
   sw.no_qcache = on("DDP_HIP_NO_QCACHE");
+  sw.cfg_full_aba = on("DDP_HIP_CFG_FULL_ABA");
   sw.ana_own_aba = on("DDP_HIP_ANA_OWN_ABA");
   sw.ana_split = on("DDP_HIP_ANA_SPLIT");
   sw.ana_eq_kernel = on("DDP_HIP_ANA_EQ_KERNEL");

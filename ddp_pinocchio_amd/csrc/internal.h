@@ -69,6 +69,7 @@ struct DevSwitches {
   bool fxx_full = false;       // FXX_FULL: the static stencil writes the configuration rows and the mirror images
   bool no_static = false;      // NO_STATIC: the generic level kernels instead of the static-topology ones
   bool no_qcache = false;      // NO_QCACHE: no configuration caches
+  bool cfg_full_aba = false;   // CFG_FULL_ABA: the (q_i, q_j) points of the static stencil run the whole ABA (two kernels, two streams)
   bool ana_own_aba = false;    // ANA_OWN_ABA: the analytic pass forms its own accelerations
   bool ana_split = false;      // ANA_SPLIT: the three-kernel analytic path with its HBM workspaces
   bool ana_eq_kernel = false;  // ANA_EQ_KERNEL: the constraint tensors in a kernel of their own
@@ -150,7 +151,7 @@ struct ddp_hip_ctx {
   int32_t lin_ncfg = 0, lin_nvcfg = 0;   // q- / v-cache entries per (instance, t)
   double* lin_qws = nullptr;   // configuration-level workspace of the static path, lin_qws_bt (instance, t) pairs at a time
   int64_t lin_qws_bt = 0;
-  double* lin_qws2 = nullptr;  // second workspace + stream + events: the two configuration-level kernels of consecutive slices overlap
+  double* lin_qws2 = nullptr;  // second workspace + stream + events (DDP_HIP_CFG_FULL_ABA only): the two full-ABA kernels of consecutive slices overlap
   hipStream_t lin_stream2 = nullptr;
   hipEvent_t lin_ev_up[2] = {nullptr, nullptr}, lin_ev_dn[2] = {nullptr, nullptr};
   double* ana_T = nullptr;     // analytic-derivative workspace (lin_analytic.hip): T = [dtau/dq | dtau/dv] per evaluation of a slice

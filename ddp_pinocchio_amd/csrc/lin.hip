@@ -1026,7 +1026,7 @@ int lin_setup(ddp_hip_ctx* ctx) {
     if (ctx->sw.qws_bt) slice = ctx->sw.qws_bt;   // tuning knob
     ctx->lin_qws_bt = BT < slice ? BT : slice;
     HIP_TRY(hipMalloc(&ctx->lin_qws, sizeof(double) * (size_t)(ctx->lin_qws_bt * lin_static_ws_per_bt(ctx->model_h))));
-    if (ctx->lin_ncfg > 1) {     // the mode-2 stencil is resident: its configuration level runs slice-pipelined on two streams
+    if (ctx->lin_ncfg > 1 && ctx->sw.cfg_full_aba) {     // the full-ABA configuration level runs slice-pipelined on two streams
       HIP_TRY(hipMalloc(&ctx->lin_qws2, sizeof(double) * (size_t)(ctx->lin_qws_bt * lin_static_ws_per_bt(ctx->model_h))));
       HIP_TRY(hipStreamCreateWithFlags(&ctx->lin_stream2, hipStreamNonBlocking));
       for (int k = 0; k < 2; ++k) {

@@ -651,6 +651,14 @@ struct VelCtx {
   double* uq;            // LDS: u_i, then the joint acceleration, of this lane (joint K at uq[K * UQS])
   int i, j;              // perturbed directions (x indices; q directions do not change v)
   double eps;
+  // operands of joint K: E | r (12 doubles; buf: room for a context that has to form them), U | 1/D (7 doubles), and the
+  // product Ia cb, which is all the evaluator takes from Ia
+  template <int K> __device__ __forceinline__ const double* er(double*) const { return qp + K * QS; }
+  template <int K> __device__ __forceinline__ const double* er_down(double* b) const { return er<K>(b); }   // E | r again, in the acceleration pass
+  template <int K> __device__ __forceinline__ const double* ud() const { return qp + K * QS + 12; }
+  // Ia cb (ud: what ud<K>() returned)
+  template <int K> __device__ __forceinline__ void ia_cb(const double*, const double* cb, double* Iac) const { rbd::sym6_mv(qc + K * rbd::QC_STRIDE + 19, cb, Iac); }
+  template <int K> __device__ __forceinline__ const double* ud_down() const { return ud<K>(); }   // U | 1/D again, in the acceleration pass
 };
 
 template <int NV, class C>
@@ -664,7 +672,8 @@ __device__ __forceinline__ double lane_v(const C& c, int K) {
 template <class T, int K, class C>
 __device__ __forceinline__ void joint_vel(const C& c, const double* vel_par, double* vel) {
   constexpr int o = T::prismatic[K] ? 3 : 0;
-  const double* E = c.qp + K * C::QS;
+  double Pb[12];
+  const double* E = c.template er<K>(Pb);
   const double* r = E + 9;
   const double* a = c.m->axis[K];
   const double vK = lane_v<T::N>(c, K);
@@ -707,11 +716,11 @@ __device__ __forceinline__ void chain_down(const C& c, VelState<T>& s) {
 template <class T, int K, int F, class C>
 __device__ __forceinline__ void chain_up(const C& c, VelState<T>& s) {
   constexpr int o = T::prismatic[K] ? 3 : 0;
-  const double* E = c.qp + K * C::QS;
+  double Pb[12];
+  const double* E = c.template er<K>(Pb);
   const double* r = E + 9;
-  const double* U = E + 12;
-  const double dinv = E[18];
-  const double* Ia = c.qc + K * rbd::QC_STRIDE + 19;
+  const double* U = c.template ud<K>();
+  const double dinv = U[6];
   const double* a = c.m->axis[K];
   double pAi[6];
   if constexpr (has_child<T>(K)) {
@@ -731,7 +740,7 @@ __device__ __forceinline__ void chain_up(const C& c, VelState<T>& s) {
     double vJ[6] = {0, 0, 0, 0, 0, 0}, cb[6], pa[6], Iac[6], fp[6];
     vJ[o] = a[0] * vK; vJ[o + 1] = a[1] * vK; vJ[o + 2] = a[2] * vK;
     rbd::crm(s.vel[K], vJ, cb);
-    rbd::sym6_mv(Ia, cb, Iac);
+    c.template ia_cb<K>(U, cb, Iac);
 #pragma unroll
     for (int k = 0; k < 6; ++k) pa[k] = pAi[k] + Iac[k] + U[k] * (ui * dinv);
     rbd::xform_force_T(E, r, pa, fp);
@@ -772,10 +781,11 @@ template <class T, int K, class C>
 __device__ __forceinline__ void vel_down(const C& c, VelState<T>& s) {
   constexpr int o = T::prismatic[K] ? 3 : 0;
   constexpr int par = T::parent[K];
-  const double* E = c.qp + K * C::QS;
+  double Pb[12];
+  const double* E = c.template er_down<K>(Pb);
   const double* r = E + 9;
-  const double* U = E + 12;
-  const double dinv = E[18];
+  const double* U = c.template ud_down<K>();
+  const double dinv = U[6];
   const double* a = c.m->axis[K];
   const double vK = lane_v<T::N>(c, K);
   double vJ[6] = {0, 0, 0, 0, 0, 0}, vel[6], cb[6], ap[6];
@@ -894,7 +904,8 @@ __global__ __launch_bounds__(LBS, ROWS ? 3 : 1) void lin_static_vel_kernel(LinPa
   }
 }
 
-// ---- configuration level: the (q_i, q_j) points ---------------------------------------------------------------------
+// ---- configuration level, full ABA: the first-order q columns, and the (q_i, q_j) points under DDP_HIP_CFG_FULL_ABA ----
+// (the (q_i, q_j) points otherwise: "configuration level by splice" below)
 // Every point has its own configuration, so the whole articulated-body algorithm runs per lane (rbd::aba_tree): the
 // chain-wise sweep of the velocity level, with the articulated inertias accumulated alongside the bias forces.  Only
 // the placements of joints i and j differ from the base configuration: each lane fetches those two from the q-cache of
@@ -1184,6 +1195,267 @@ __global__ __launch_bounds__(LBS) void lin_static_cfg_down_kernel(LinParams p, c
   LinParams po;
   po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top;
   offdiag_emit<nv, LBS>(po, S, valid, c.i, c.j, bt, c.xg, model->dt);
+}
+
+// ---- configuration level by splice: the (q_i, q_j) points from cached q-parts --------------------------------------
+// In the local-frame ABA the record of joint K is E | r (a function of q_K alone) and U | 1/D | Ia (functions of the q of
+// the strict descendants of K alone).  At q + eps e_i + eps e_j, with S_x the strict ancestors of x:
+//   E | r of K        : configuration 1+K of the q-cache if K is i or j, else the base configuration;
+//   U | 1/D | Ia of K : base if K is in neither S_i nor S_j; configuration 1+i if in S_i only; configuration 1+j if in
+//                       S_j only; recomputed only on the spine S_i & S_j (a path that ends at the root), from I6[K] and its
+//                       children's X^T Ia X in the order of the q-cache kernel, each child's Ia by the same rule.
+// The spine records are formed by a pre-pass (a lane per pair); with them a point is a velocity-level evaluation whose
+// per-joint operands are selected per lane: no per-lane inertia state, nothing handed from pass to pass but u_i.
+// What the evaluator takes from Ia is Ia cb alone, and on the spine cb is the base one (the link velocity of K moves with the q of
+// K and of its ancestors only): the pre-pass forms Ia cb with the cb of v-cache entry 0 and a spine record is U | 1/D | Ia cb.
+constexpr int SREC = 13;            // doubles per spine record: U[6] | 1/D | Ia cb[6]
+
+// The pairs of one (instance, t) are dealt to the lanes in the order of their spine's deepest joint (`top`), ties in tri_index order:
+// the lanes of a wave then mostly walk the same joints (little divergence, the same model constants, in the pre-pass), and the records
+// of one top are laid out [depth][pair of that top], so that what a wave writes or gathers for one joint is one contiguous run.
+template <class T>
+struct SpineTab {
+  static constexpr int N = T::N, TRI = N * (N - 1) / 2;
+  static_assert(N >= 2 && N <= 64, "ancestor masks are 64 bits wide");
+  unsigned long long mask[N];       // desc_mask: bit i set <=> the joint is a strict ancestor of i
+  unsigned long long anc[N];        // the transpose: bit K set <=> K is a strict ancestor of the joint
+  int depth[N];                     // number of strict ancestors
+  int nrec;                         // records per (instance, t): the sum of the spine lengths
+  // per lane slot (pairs ordered by top):
+  short pi[TRI], pj[TRI];           // the pair, i < j
+  short top[TRI];                   // deepest joint of its spine S_i & S_j (-1: empty); the spine is top and its ancestors
+  int rbase[TRI], rstride[TRI];     // the record of its spine joint of depth d: rbase + d * rstride
+};
+template <class T>
+constexpr SpineTab<T> make_spine_tab() {
+  SpineTab<T> t{};
+  for (int k = 0; k < T::N; ++k)
+    for (int a = T::parent[k]; a >= 0; a = T::parent[a]) { ++t.depth[k]; t.mask[a] |= 1ull << k; t.anc[k] |= 1ull << a; }
+  // counting sort by top + 1
+  int cnt[T::N + 2] = {}, start[T::N + 2] = {}, goff[T::N + 2] = {};
+  for (int i = 0; i < T::N; ++i)
+    for (int j = i + 1; j < T::N; ++j) {
+      int a = T::parent[i];
+      while (a >= 0 && !((t.mask[a] >> j) & 1)) a = T::parent[a];
+      ++cnt[a + 1];
+    }
+  for (int g = 0; g <= T::N; ++g) {
+    start[g + 1] = start[g] + cnt[g];
+    goff[g + 1] = goff[g] + cnt[g] * (g == 0 ? 0 : t.depth[g - 1] + 1);
+  }
+  t.nrec = goff[T::N + 1];
+  int fill[T::N + 2] = {};
+  for (int i = 0; i < T::N; ++i)
+    for (int j = i + 1; j < T::N; ++j) {
+      int a = T::parent[i];
+      while (a >= 0 && !((t.mask[a] >> j) & 1)) a = T::parent[a];
+      const int g = a + 1, rank = fill[g]++, slot = start[g] + rank;
+      t.pi[slot] = (short)i; t.pj[slot] = (short)j; t.top[slot] = (short)a;
+      t.rbase[slot] = goff[g] + rank;
+      t.rstride[slot] = cnt[g];
+    }
+  return t;
+}
+template <class T> __device__ const SpineTab<T> g_spine_tab = make_spine_tab<T>();
+template <class T> constexpr unsigned long long desc_mask(int k) { return make_spine_tab<T>().mask[k]; }
+template <class T> constexpr int depth_of(int k) { return make_spine_tab<T>().depth[k]; }
+template <class T> constexpr int spine_records() { return make_spine_tab<T>().nrec; }
+// on some pair's spine: at least two strict descendants
+template <class T> constexpr bool spine_joint(int k) { const unsigned long long mk = desc_mask<T>(k); return (mk & (mk - 1)) != 0; }
+
+// Workgroups x and x + 8 run on the same XCD: the GU waves of one (instance, t) are dealt to one XCD, whose L2 then serves
+// their re-reads of that (instance, t)'s q-cache block and spine records.  Grid: GU workgroups for each of nb rounded up
+// to a multiple of 8; false: a padding workgroup.
+template <int GU>
+__device__ __forceinline__ bool xcd_slot(int nb, int& btl, int& g) {
+  const int x = (int)blockIdx.x, s = x >> 3;
+  btl = (s / GU) * 8 + (x & 7);
+  g = s % GU;
+  return btl < nb;
+}
+
+// One lane per pair: its spine from the deepest joint to the root (the expressions of qv_chain_up).  Joint indices are
+// run-time values here, so the per-joint constants come from the model in memory; register arrays are indexed by constants only.
+template <class T>
+__global__ __launch_bounds__(LBS) void lin_static_spine_kernel(const DevModel* __restrict__ model, const double* __restrict__ qcache,
+                                                               const double* __restrict__ vcache, double* __restrict__ spine, int64_t bt0, int nb) {
+  constexpr int nv = T::N, TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS, NREC = spine_records<T>();
+  int btl, g;
+  if (!xcd_slot<GU>(nb, btl, g)) return;
+  const int slot = g * LBS + (int)threadIdx.x;
+  if (slot >= TRI) return;                                  // (no barrier below)
+  const SpineTab<T>& tab = g_spine_tab<T>;
+  const DevModel& m = *model;
+  const int i = tab.pi[slot], j = tab.pj[slot];
+  const int rstride = tab.rstride[slot];
+  const double* __restrict__ qc0 = qcache + ((bt0 + btl) * (nv + 1)) * (int64_t)nv * rbd::QC_STRIDE;
+  const double* __restrict__ vc0 = vcache + ((bt0 + btl) * (2 * nv + 1)) * (int64_t)nv * rbd::VC_STRIDE;   // entry 0: the base (q, v)
+  double* __restrict__ out = spine + ((int64_t)btl * NREC + tab.rbase[slot]) * SREC;
+  double Ia[21];
+#pragma unroll
+  for (int k = 0; k < 21; ++k) Ia[k] = 0.0;
+  int prev = -1;
+  for (int K = tab.top[slot]; K >= 0; K = m.parent[K]) {
+    double IA[21];
+#pragma unroll
+    for (int k = 0; k < 21; ++k) IA[k] = m.I6[K][k];
+    for (int sl = m.child_start[K]; sl < m.child_start[K + 1]; ++sl) {     // descending index: the order of the leaf -> root pass
+      const int c = m.child_list[sl];
+      const unsigned long long mc = tab.mask[c];
+      const int cfg_p = (c == i || c == j) ? 1 + c : 0;
+      const int cfg_i = ((mc >> i) & 1) ? 1 + i : (((mc >> j) & 1) ? 1 + j : 0);   // (c == prev: on the spine, the value just formed)
+      const double* Pg = qc0 + ((int64_t)cfg_p * nv + c) * rbd::QC_STRIDE;
+      const double* Ig = qc0 + ((int64_t)cfg_i * nv + c) * rbd::QC_STRIDE + 19;
+      double P[12], Ic[21];
+#pragma unroll
+      for (int k = 0; k < 12; ++k) P[k] = Pg[k];
+#pragma unroll
+      for (int k = 0; k < 21; ++k) { const double v = Ig[k]; Ic[k] = c == prev ? Ia[k] : v; }
+      rbd::add_xtix(P, P + 9, Ic, IA);
+    }
+    const bool pris = m.jtype[K] == DDP_HIP_JOINT_PRISMATIC;
+    const double* a = m.axis[K];
+    double U[6], d = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      const double u0 = IA[rbd::sidx(r, 0)] * a[0] + IA[rbd::sidx(r, 1)] * a[1] + IA[rbd::sidx(r, 2)] * a[2];
+      const double u3 = IA[rbd::sidx(r, 3)] * a[0] + IA[rbd::sidx(r, 4)] * a[1] + IA[rbd::sidx(r, 5)] * a[2];
+      U[r] = pris ? u3 : u0;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) d += a[k] * (pris ? U[3 + k] : U[k]);
+    const double dinv = 1.0 / d;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int cc = 0; cc <= r; ++cc) Ia[rbd::sidx(r, cc)] = IA[rbd::sidx(r, cc)] - U[r] * U[cc] * dinv;
+    double cb[6], Iac[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) cb[k] = vc0[K * rbd::VC_STRIDE + k];
+    rbd::sym6_mv(Ia, cb, Iac);
+    double* o = out + (int64_t)tab.depth[K] * rstride * SREC;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o[k] = U[k];
+    o[6] = dinv;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o[7 + k] = Iac[k];
+    prev = K;
+  }
+}
+
+// The velocity-level evaluator's context for a (q_i, q_j) point.  Every operand is read through a per-lane pointer: E | r of K
+// from the base configuration or from configuration 1+K; U | 1/D | Ia of a joint with children from one of the sources above
+// (re-reads of the (instance, t)'s q-cache block and spine records, mostly the same address in every lane).  Branch-free:
+// selections by integer arithmetic and one select between two finished pointers -- a conditional address computation becomes a
+// branch, and control flow in the middle of the evaluation tears it away from its operand loads.
+template <class T>
+struct SpliceCtx {
+  static constexpr int UQS = 1;
+  const DevModel* m;
+  const double* __restrict__ qc0;   // q-cache of the (instance, t): configuration c at qc0 + c * nv * QC_STRIDE
+  const double* __restrict__ xg;
+  const double* __restrict__ ug;
+  const double* __restrict__ spb;   // spine records of the (instance, t)
+  int rbase, rstride;               // ... this lane's: the joint of depth d at spb + (rbase + d * rstride) * SREC
+  double* uq;
+  int i, j;                         // perturbed joints, i < j
+  unsigned long long ai, aj;        // their strict ancestors (SpineTab::anc): K is in S_i <=> bit K of ai
+  template <int K> __device__ __forceinline__ const double* er(double*) const {
+    const int own = (int)(K == i) | (int)(K == j);
+    return qc0 + (K * rbd::QC_STRIDE + own * ((1 + K) * T::N * rbd::QC_STRIDE));
+  }
+  template <int K> __device__ __forceinline__ const double* ud() const {
+    constexpr int DK = depth_of<T>(K);
+    if constexpr (desc_mask<T>(K) == 0) return qc0 + (K * rbd::QC_STRIDE + 12);     // a leaf: nothing below it moves
+    else {
+      const int si = (int)((ai >> K) & 1), sj = (int)((aj >> K) & 1);
+      const int cfg = (si & (sj ^ 1)) * (1 + i) + (sj & (si ^ 1)) * (1 + j);
+      const double* p = qc0 + ((cfg * T::N + K) * rbd::QC_STRIDE + 12);
+      if constexpr (!spine_joint<T>(K)) return p;
+      else {
+        const double* q = spb + (rbase + DK * rstride) * SREC;
+        return (si & sj) ? q : p;
+      }
+    }
+  }
+  // The same addresses, written differently on purpose: recognised as the same values, the per-lane pointers of the leaf -> root
+  // pass would stay alive until the acceleration pass comes by, and the kernel would not fit two waves per SIMD
+  template <int K> __device__ __forceinline__ const double* er_down(double*) const {
+    const int64_t own = (K - i) * (K - j) == 0 ? (int64_t)(1 + K) * T::N * rbd::QC_STRIDE : 0;
+    return qc0 + K * rbd::QC_STRIDE + own;
+  }
+  template <int K> __device__ __forceinline__ const double* ud_down() const {
+    constexpr int DK = depth_of<T>(K);
+    if constexpr (desc_mask<T>(K) == 0) return qc0 + (K * rbd::QC_STRIDE + 12);
+    else {
+      const bool si = (ai >> K) & 1, sj = (aj >> K) & 1;
+      const int cfg = sj ? 1 + j : (si ? 1 + i : 0);
+      const double* p = qc0 + (int64_t)cfg * (T::N * rbd::QC_STRIDE) + (K * rbd::QC_STRIDE + 12);
+      if constexpr (!spine_joint<T>(K)) return p;
+      else {
+        const double* q = spb + ((int64_t)rbase + (int64_t)DK * rstride) * SREC;
+        return ((ai & aj) >> K) & 1 ? q : p;
+      }
+    }
+  }
+  // Ia cb: off the spine from the 21 entries behind U | 1/D; on it the pre-pass has formed it (behind U | 1/D as well: for the
+  // other lanes those six doubles are the head of Ia, loaded anyway), and Ia is read from the base record and not used
+  template <int K> __device__ __forceinline__ void ia_cb(const double* ud, const double* cb, double* Iac) const {
+    if constexpr (!spine_joint<T>(K)) rbd::sym6_mv(ud + 7, cb, Iac);
+    else {
+      const int on = (int)(((ai & aj) >> K) & 1);
+      const double* pIa = on ? qc0 + (K * rbd::QC_STRIDE + 19) : ud + 7;
+      const double w1 = (double)on, w0 = (double)(on ^ 1);
+      double t[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) t[k] = ud[7 + k];
+      rbd::sym6_mv(pIa, cb, Iac);
+      // (an exact blend by weights 0 and 1, all values finite: as a select the product would be sunk into a branch)
+#pragma unroll
+      for (int k = 0; k < 6; ++k) Iac[k] = w1 * t[k] + w0 * Iac[k];
+    }
+  }
+};
+template <int NV, class T>
+__device__ __forceinline__ double lane_v(const SpliceCtx<T>& c, int K) { return c.xg[NV + K]; }   // q directions do not change v
+
+// One wave = 64 (q_i, q_j) pairs, i < j: the velocity-level pair kernel on spliced operands
+template <class T>
+__global__ __launch_bounds__(LBS, 2) void lin_static_cfg_pair_kernel(LinParams p, const double* __restrict__ spine, int64_t bt0, int nb) {
+  constexpr int nv = T::N, n = 2 * nv;
+  constexpr int TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS, NREC = spine_records<T>();
+  int btl, g;
+  if (!xcd_slot<GU>(nb, btl, g)) return;                    // the whole workgroup (one wave), ahead of every barrier
+  const int64_t bt = bt0 + btl;
+  const int lane = threadIdx.x;
+  const int64_t Tn = p.d.T;
+  const int b = (int)(bt / Tn);
+  const int64_t t = bt % Tn;
+  const int slot = g * LBS + lane;
+  const bool valid = slot < TRI;
+  const int sc = valid ? slot : 0;
+  const SpineTab<T>& tab = g_spine_tab<T>;
+  __shared__ OutStage<nv> S;
+  SpliceCtx<T> c;
+  c.i = tab.pi[sc]; c.j = tab.pj[sc];
+  c.ai = tab.anc[c.i];
+  c.aj = tab.anc[c.j];
+  c.rbase = tab.rbase[sc]; c.rstride = tab.rstride[sc];
+  c.m = p.model;
+  c.qc0 = p.qcache + (bt * (nv + 1)) * (int64_t)nv * rbd::QC_STRIDE;
+  c.xg = p.x + ((int64_t)b * (Tn + 1) + t) * n;
+  c.ug = p.u + ((int64_t)b * Tn + t) * nv;
+  c.spb = spine + (int64_t)btl * NREC * SREC;
+  c.uq = &S.qdd[lane * (nv + 1)];
+  VelState<T> s;
+  vel_up_all<T>(c, s, std::make_integer_sequence<int, nv>{});
+  vel_down_all<T>(c, s, std::make_integer_sequence<int, nv>{});
+  __builtin_amdgcn_sched_barrier(0);
+  typedef __attribute__((address_space(4))) const LinParams* kernarg_t;
+  const kernarg_t kp = (kernarg_t)__builtin_amdgcn_kernarg_segment_ptr();
+  LinParams po;
+  po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top;
+  offdiag_emit<nv, LBS>(po, S, valid, c.i, c.j, bt, c.xg, c.m->dt);
 }
 
 // ---- first order: forward differences of f (problem.hpp:105-126 stepping, eps = sqrt(DBL_EPSILON)) -------------------
@@ -1570,9 +1842,20 @@ int lin_static_supported(const DevModel& m) {
 }
 
 // doubles of workspace one (instance, t) needs at the configuration level
+// (the larger of: the sweep's 8 doubles per joint and lane, which the first-order q columns and the full-ABA level need, and
+// the pairs' spine records)
 int64_t lin_static_ws_per_bt(const DevModel& m) {
   const int64_t nv = m.nv, TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS;
-  return GU * nv * WS_PER_JOINT * LBS;
+  int64_t rec = 0;
+  for (int i = 0; i < nv; ++i)
+    for (int j = i + 1; j < nv; ++j) {
+      const auto anc = [&](int a, int x) { for (int k = m.parent[x]; k >= 0; k = m.parent[k]) if (k == a) return true; return false; };
+      int a = m.parent[i];
+      while (a >= 0 && !anc(a, j)) a = m.parent[a];
+      for (; a >= 0; a = m.parent[a]) ++rec;
+    }
+  const int64_t sweep = GU * nv * WS_PER_JOINT * LBS, splice = rec * SREC;
+  return sweep > splice ? sweep : splice;
 }
 
 // level 3: torque-level points (replaces lin_offdiag_kernel<NJ, 3>)
@@ -1608,7 +1891,21 @@ static int lin_static_launch_t(ddp_hip_ctx* ctx, const LinParams& p, int level) 
     // diagonal second-order entries of the u directions; those of the q and v directions are formed by the torque-level
     // row kernel (level 3) on an otherwise idle lane, which therefore runs ahead of levels 2 and 1
     hipLaunchKernelGGL((lin_static_first_kernel<T, 3, true>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
+  } else if (level == 1 && !ctx->sw.cfg_full_aba) {
+    // Spine pre-pass, then the pair kernel on spliced operands, in slices of (instance, t) whose spine records share the workspace.
+    // The workspace is sized for lin_qws_bt sweeps (lin_static_ws_per_bt: the first-order q columns run one); a spine set is
+    // smaller, so a slice holds more of them (Talos: 4.2 x; few long launches instead of many short ones: measured below)
+    constexpr int64_t NREC = spine_records<T>(), SWEEP = (int64_t)GU * nv * WS_PER_JOINT * LBS;
+    constexpr int64_t WS_BT = SWEEP > NREC * SREC ? SWEEP : NREC * SREC;
+    const int64_t per = NREC > 0 ? ctx->lin_qws_bt * WS_BT / (NREC * SREC) : BT;
+    for (int64_t bt0 = 0; bt0 < BT; bt0 += per) {
+      const int nb = (int)(BT - bt0 < per ? BT - bt0 : per);
+      const dim3 grid((unsigned)((nb + 7) / 8 * 8 * GU));
+      hipLaunchKernelGGL((lin_static_spine_kernel<T>), grid, dim3(LBS), 0, ctx->stream, p.model, p.qcache, p.vcache, ctx->lin_qws, bt0, nb);
+      hipLaunchKernelGGL((lin_static_cfg_pair_kernel<T>), grid, dim3(LBS), 0, ctx->stream, p, ctx->lin_qws, bt0, nb);
+    }
   } else if (level == 1) {
+    // DDP_HIP_CFG_FULL_ABA (development A/B): every point runs the whole articulated-body algorithm.
     // In slices of (instance, t), so that the per-wave workspace stays small.  The sweep kernel of slice k+1 (one wave per
     // SIMD, long waves) and the acceleration / output kernel of slice k run on two streams with two workspaces: each
     // fills the other's tail instead of leaving the chip to drain between launches.

@@ -228,6 +228,33 @@ def main():
     assert err < 1e-10, err                      # the counted sequence IS the forward dynamics
     print(f"joints {N}: full evaluation {total} ops  (q-dependent part {cnt_q}, (q,v)-dependent part {cnt_v}, tau-dependent rest {total - cnt_q - cnt_v})")
     print(f"FLOPS_FULL = {total}   FLOPS_VEL = {total - cnt_q}   FLOPS_TAU = {total - cnt_q - cnt_v}   (check vs oracle ABA: rel err {err:.1e})")
+    # a (q_i, q_j) point by splice (lin_static.hip: spine pre-pass + velocity-level evaluation on spliced records): per joint of the
+    # pair's spine S_i & S_j one X^T Ia X per child, U, 1/D, Ia and Ia cb; then one velocity-level evaluation
+    one = [C(1.0)] * 21
+    N_OPS[0] = 0
+    add_xtix([C(1.0)] * 9, [C(1.0)] * 3, one, list(one))
+    c_child = N_OPS[0]
+    N_OPS[0] = 0
+    a = [C(1.0)] * 3
+    Uo = [one[sidx(r, 0)] * a[0] + one[sidx(r, 1)] * a[1] + one[sidx(r, 2)] * a[2] for r in range(6)]
+    dinv = 1.0 / (a[0] * Uo[0] + a[1] * Uo[1] + a[2] * Uo[2])
+    Ia = [one[sidx(r, c)] - Uo[r] * Uo[c] * dinv for r in range(6) for c in range(r + 1)]
+    sym6_mv(Ia, [C(1.0)] * 6)
+    c_joint = N_OPS[0]
+    par = model["parent"]
+    anc = []
+    for i in range(N):
+        s_, k = set(), par[i]
+        while k >= 0:
+            s_.add(k); k = par[k]
+        anc.append(s_)
+    nch = [sum(1 for c in range(N) if par[c] == k) for k in range(N)]
+    spine_ops = [sum(nch[K] * c_child + c_joint for K in anc[i] & anc[j]) for i in range(N) for j in range(i + 1, N)]
+    lens = [len(anc[i] & anc[j]) for i in range(N) for j in range(i + 1, N)]
+    mean_spine = sum(spine_ops) / len(spine_ops)
+    print(f"(q_i, q_j) by splice: {len(lens)} pairs, {sum(lens)} spine joints (mean {sum(lens) / len(lens):.2f}, max {max(lens)}); per spine joint "
+          f"{c_joint} ops + {c_child} per child; mean spine pre-pass {mean_spine:.0f} ops per pair")
+    print(f"FLOPS_SPLICE = {total - cnt_q + mean_spine:.0f} per pair on average (FLOPS_VEL + spine), against FLOPS_FULL = {total}")
 
 
 if __name__ == "__main__":
