@@ -24,6 +24,8 @@ EQ_NONE, EQ_CONFIG, EQ_FRAME = 0, 1, 2
 BUILTIN_PENDULUM, BUILTIN_CHAIN6, BUILTIN_TREE38, BUILTIN_CHAIN6_FF, BUILTIN_TREE38_FF = 0, 1, 2, 3, 4
 JOINT_REVOLUTE, JOINT_PRISMATIC, JOINT_FREEFLYER = 0, 1, 2
 FLAG_NO_TENSORS, FLAG_TRACE, FLAG_TRACKING_COST, FLAG_CONTROL_BOUNDS = 1, 2, 4, 8
+FLAG_FRAME_COST = 16
+MAX_COST_FRAMES = 4
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
 
 SEQ_NAMES = [
@@ -52,6 +54,7 @@ EXPORTS = [
     "ddp_hip_builtin_model",
     "ddp_hip_batch", "ddp_hip_set_active", "ddp_hip_solve", "ddp_hip_ctx_info",
     "ddp_hip_model_create", "ddp_hip_model_destroy", "ddp_hip_model_aba", "ddp_hip_model_aba_derivatives", "ddp_hip_model_frame",
+    "ddp_hip_frame_cost_set_frames", "ddp_hip_frame_cost_upload", "ddp_hip_frame_cost_download",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -131,6 +134,10 @@ def lib():
     L.ddp_hip_upload.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64, C.c_int64]
     L.ddp_hip_download.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64, C.c_int64]
     L.ddp_hip_fill.argtypes = [C.c_void_p, C.c_int, C.c_double]
+    if hasattr(L, "ddp_hip_frame_cost_upload"):      # (DDP_HIP_LIB may name an older build for an A/B run: set_frame_cost then fails there)
+        L.ddp_hip_frame_cost_set_frames.argtypes = [C.c_void_p, C.c_int32, _ip, _dp]
+        L.ddp_hip_frame_cost_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_frame_cost_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
     L.ddp_hip_rollout.argtypes = [C.c_void_p]
     L.ddp_hip_linearize.argtypes = [C.c_void_p]
     L.ddp_hip_linearize_stages.argtypes = [C.c_void_p, C.c_uint32]
@@ -332,6 +339,7 @@ class Context:
         self._c_problem = spec.c_struct()
         _check(lib().ddp_hip_create(C.byref(self._c_problem), device, flags, C.byref(self._h)), "ddp_hip_create")
         self.batch = spec.batch
+        self.n_cost_frames = 0
 
     def close(self):
         if self._h:
@@ -407,6 +415,48 @@ class Context:
             raise ValueError("set_control_bounds: some lo > hi")
         for name, arr in arrs.items():
             self.upload(name, arr, first, count)
+
+    def set_frame_cost(self, frames=None, target=None, weight=None, first=0, count=None):
+        """The frame-position cost (a context created with FLAG_FRAME_COST; ddp_hip.h).  frames: a list of up to
+        MAX_COST_FRAMES (joint, off) pairs, shared by the batch (another count than before resets targets and weights to 0).
+        target / weight of instances first .. first + count - 1: (T+1, F, 3) for every instance of the range or
+        (count, T+1, F, 3) with one per instance; weight also takes (F, 3), (3,) and scalars by broadcast.  None leaves that
+        side as it is."""
+        count = self.batch - first if count is None else count
+        n_frames = self.n_cost_frames
+        if frames is not None:
+            frames = list(frames)
+            n_frames = len(frames)
+            joint = np.ascontiguousarray([int(j) for j, _ in frames], dtype=np.int32)
+            off = [np.asarray(o, dtype=np.float64) for _, o in frames]
+            if any(o.shape != (3,) for o in off):
+                raise ValueError("set_frame_cost frames: every off is a 3-vector")
+            off = _f64(off).reshape(-1)
+        per = (self.spec.T + 1, n_frames, 3)
+        full = (count,) + per
+        arrs = {}
+        for name, arr in (("target", target), ("weight", weight)):
+            if arr is None:
+                continue
+            arr = np.asarray(arr, dtype=np.float64)
+            if not (arr.shape in (full, per) or (name == "weight" and arr.shape in (per[1:], per[2:], ()))):
+                raise ValueError(f"set_frame_cost {name}: shape {arr.shape}, expected {per} or {full}")
+            arrs[name] = np.ascontiguousarray(np.broadcast_to(arr, full))
+        if frames is not None:
+            _check(lib().ddp_hip_frame_cost_set_frames(self._h, n_frames, joint.ctypes.data_as(_ip), _ptr(off)), "frame_cost_set_frames")
+            self.n_cost_frames = n_frames
+        if arrs:
+            t, w = arrs.get("target"), arrs.get("weight")
+            _check(lib().ddp_hip_frame_cost_upload(self._h, _ptr(t) if t is not None else None, _ptr(w) if w is not None else None,
+                                                   first, count), "frame_cost_upload")
+
+    def frame_cost(self, first=0, count=None):
+        """(target, weight) of instances first .. first + count - 1, each (count, T+1, F, 3)"""
+        count = self.batch - first if count is None else count
+        shape = (count, self.spec.T + 1, self.n_cost_frames, 3)
+        t, w = np.zeros(shape), np.zeros(shape)
+        _check(lib().ddp_hip_frame_cost_download(self._h, _ptr(t), _ptr(w), first, count), "frame_cost_download")
+        return t, w
 
     def fill(self, name, value):
         _check(lib().ddp_hip_fill(self._h, SEQ[name], float(value)), f"fill {name}")

@@ -245,6 +245,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   if (mo.kind != DDP_HIP_MODEL_PENDULUM && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_ARG;
   if (mo.kind == DDP_HIP_MODEL_PENDULUM && mo.nv != 1) return DDP_HIP_E_ARG;
   if (prob->fd_mode < 0 || prob->fd_mode > 2) return DDP_HIP_E_ARG;
+  if ((flags & DDP_HIP_FLAG_FRAME_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // frames are points of a tree's joints
   if (prob->eq_kind != DDP_HIP_EQ_NONE && (!prob->ne || prob->eq_advance < 0 || prob->eq_advance > 4)) return DDP_HIP_E_ARG;
   if (prob->eq_kind == DDP_HIP_EQ_FRAME && (mo.kind != DDP_HIP_MODEL_TREE || prob->frame_joint < 0 ||
                                             prob->frame_joint >= (mo.jtype && mo.jtype[0] == DDP_HIP_JOINT_FREEFLYER ? mo.nv - 5 : mo.nv)))
@@ -344,6 +345,14 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipMemcpyAsync(ctx->seq[DDP_HIP_SEQ_COST_XREF].ptr, xr.data(), sizeof(double) * xr.size(), hipMemcpyHostToDevice, ctx->stream));
     CTX_TRY(hipStreamSynchronize(ctx->stream));
   }
+  if (flags & DDP_HIP_FLAG_FRAME_COST) {
+    // no frames yet; targets and weights start at 0
+    const size_t words = (size_t)(d.batch * (d.T + 1) * DDP_HIP_MAX_COST_FRAMES * 3);
+    CTX_TRY(hipMalloc(&ctx->fc_target_d, sizeof(double) * words));
+    CTX_TRY(hipMalloc(&ctx->fc_weight_d, sizeof(double) * words));
+    CTX_TRY(hipMemsetAsync(ctx->fc_target_d, 0, sizeof(double) * words, ctx->stream));
+    CTX_TRY(hipMemsetAsync(ctx->fc_weight_d, 0, sizeof(double) * words, ctx->stream));
+  }
   int rc = bwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = fwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = lin_setup(ctx);
@@ -363,6 +372,8 @@ extern "C" int ddp_hip_destroy(ddp_hip_ctx* ctx) {
   bwd_teardown(ctx);
   for (int s = 0; s < DDP_HIP_SEQ_COUNT; ++s)
     if (ctx->seq[s].ptr) (void)hipFree(ctx->seq[s].ptr);
+  if (ctx->fc_target_d) (void)hipFree(ctx->fc_target_d);
+  if (ctx->fc_weight_d) (void)hipFree(ctx->fc_weight_d);
   if (ctx->ne_d) (void)hipFree(ctx->ne_d);
   if (ctx->Epre_d) (void)hipFree(ctx->Epre_d);
   if (ctx->target_d) (void)hipFree(ctx->target_d);
@@ -497,6 +508,76 @@ extern "C" int ddp_hip_fill(ddp_hip_ctx* ctx, int seq, double value) {
     ctx->tensors_sym = false;
   }
   return fill_device(ctx, ctx->seq[seq].ptr, ctx->seq[seq].size * ctx->d.batch, value);
+}
+
+// ---- frame-position cost (DDP_HIP_FLAG_FRAME_COST): frames shared by the batch, targets and weights per instance ----------
+extern "C" int ddp_hip_frame_cost_set_frames(ddp_hip_ctx* ctx, int32_t n_frames, const int32_t* joint, const double* off) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_FRAME_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (n_frames < 1 || n_frames > DDP_HIP_MAX_COST_FRAMES || !joint || !off) return DDP_HIP_E_ARG;
+  for (int f = 0; f < n_frames; ++f) {
+    if (joint[f] < 0 || joint[f] >= ctx->model_h.nj) return DDP_HIP_E_ARG;
+    for (int a = 0; a < 3; ++a)
+      if (!isfinite(off[3 * f + a])) return DDP_HIP_E_ARG;
+  }
+  if (n_frames != ctx->fc_nf) {
+    // another count is another layout: targets and weights start again at 0
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t words = (size_t)(ctx->d.batch * (ctx->d.T + 1) * DDP_HIP_MAX_COST_FRAMES * 3);
+    HIP_TRY(hipMemsetAsync(ctx->fc_target_d, 0, sizeof(double) * words, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->fc_weight_d, 0, sizeof(double) * words, ctx->stream));
+    ctx->fc_live = false;
+  }
+  ctx->fc_nf = n_frames;
+  for (int f = 0; f < n_frames; ++f) {
+    ctx->fc_joint[f] = joint[f];
+    for (int a = 0; a < 3; ++a) ctx->fc_off[f][a] = off[3 * f + a];
+  }
+  return DDP_HIP_OK;
+}
+
+static int frame_cost_range(ddp_hip_ctx* ctx, int64_t first, int64_t count) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_FRAME_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (first < 0 || count < 0 || first + count > ctx->d.batch) return DDP_HIP_E_ARG;
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_frame_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first, int64_t count) {
+  int rc = frame_cost_range(ctx, first, count);
+  if (rc != DDP_HIP_OK) return rc;
+  if (ctx->fc_nf == 0) return DDP_HIP_E_ARG;                // no frames set: the arrays have no shape yet
+  const int64_t sz = (ctx->d.T + 1) * ctx->fc_nf * 3;
+  bool nonzero = false;
+  if (target)
+    for (int64_t i = 0; i < sz * count; ++i)
+      if (!isfinite(target[i])) return DDP_HIP_E_ARG;
+  if (weight)
+    for (int64_t i = 0; i < sz * count; ++i) {
+      if (!cost_weight_ok(weight[i])) return DDP_HIP_E_ARG;
+      nonzero |= weight[i] != 0.0;
+    }
+  if (count == 0 || (!target && !weight)) return DDP_HIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (target) HIP_TRY(hipMemcpyAsync(ctx->fc_target_d + first * sz, target, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
+  if (weight) HIP_TRY(hipMemcpyAsync(ctx->fc_weight_d + first * sz, weight, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  // any non-zero weight switches the terms on; only ONE upload of zeros for the whole batch (first 0, count batch) switches
+  // them off again -- zeros arriving range by range leave the frame kernels running (same bits: they skip zero weights themselves)
+  if (weight) ctx->fc_live = nonzero || (ctx->fc_live && !(first == 0 && count == ctx->d.batch));
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_frame_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first, int64_t count) {
+  int rc = frame_cost_range(ctx, first, count);
+  if (rc != DDP_HIP_OK) return rc;
+  const int64_t sz = (ctx->d.T + 1) * ctx->fc_nf * 3;
+  if (sz == 0 || count == 0 || (!target && !weight)) return DDP_HIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (target) HIP_TRY(hipMemcpyAsync(target, ctx->fc_target_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
+  if (weight) HIP_TRY(hipMemcpyAsync(weight, ctx->fc_weight_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return DDP_HIP_OK;
 }
 
 extern "C" int ddp_hip_set_async(ddp_hip_ctx* ctx, int on) {

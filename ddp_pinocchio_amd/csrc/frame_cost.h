@@ -1,0 +1,121 @@
+// frame_cost.h -- per-instance frame-position costs (DDP_HIP_FLAG_FRAME_COST, ddp_hip.h): the kernel-side description and
+// the two traversals they need.  The terms themselves are formed in fwd.hip (cost values) and lin.hip (derivatives).
+#pragma once
+#include "internal.h"
+#include "lie.h"
+#include "rbd.h"
+
+// What a kernel reads of the context's frame cost.  target == nullptr: no terms (the flag is off, no frames are set, or no
+// non-zero weight has been uploaded since the frames were set)
+struct FrameCostDev {
+  const double *target, *weight;   // [batch][T+1][nf][3]
+  int32_t nf, pad_;
+  int32_t joint[DDP_HIP_MAX_COST_FRAMES];
+  double off[DDP_HIP_MAX_COST_FRAMES][3];
+};
+
+inline FrameCostDev frame_cost_dev(const ddp_hip_ctx* ctx) {
+  FrameCostDev f{};
+  if (!ctx->fc_live) return f;
+  f.target = ctx->fc_target_d; f.weight = ctx->fc_weight_d;
+  f.nf = ctx->fc_nf;
+  for (int k = 0; k < ctx->fc_nf; ++k) {
+    f.joint[k] = ctx->fc_joint[k];
+    for (int a = 0; a < 3; ++a) f.off[k][a] = ctx->fc_off[k][a];
+  }
+  return f;
+}
+
+namespace rbd {
+
+// World position of the point `off` of joint `joint`, walking joint -> root with the point alone (no placements are kept):
+// p <- Rp (R_axis(q_i) p) + pp for a revolute joint, Rp (p + q_i axis) + pp for a prismatic one, R(quat) p + trans for a
+// free-flyer root.  M: DevModel or CoopModel (the tables in LDS)
+template <class M>
+__device__ __forceinline__ void frame_point(const M& m, bool ff, int joint, const double* off, const double* q, double* p) {
+  double v[3] = {off[0], off[1], off[2]};
+  for (int j = joint; j >= 0; j = m.parent[j]) {
+    double w[3];
+    if (j == 0 && ff) {
+      double R[9];
+      lie::quat_to_R(q + 3, R);
+      mv3(R, v, w);
+      v[0] = w[0] + q[0]; v[1] = w[1] + q[1]; v[2] = w[2] + q[2];
+      break;
+    }
+    const double* a = m.axis[j];
+    const double qj = q[ff ? j + 6 : j];
+    if (m.jtype[j] == DDP_HIP_JOINT_REVOLUTE) {
+      double s, c, av[3], aav[3];
+      sincos(qj, &s, &c);
+      cross3(a, v, av);
+      cross3(a, av, aav);
+      const double omc = 1.0 - c;
+      w[0] = v[0] + (s * av[0] + omc * aav[0]); w[1] = v[1] + (s * av[1] + omc * aav[1]); w[2] = v[2] + (s * av[2] + omc * aav[2]);
+    } else {
+      w[0] = v[0] + a[0] * qj; w[1] = v[1] + a[1] * qj; w[2] = v[2] + a[2] * qj;
+    }
+    mv3(m.Rp[j], w, v);
+    v[0] += m.pp[j][0]; v[1] += m.pp[j][1]; v[2] += m.pp[j][2];
+  }
+  p[0] = v[0]; p[1] = v[1]; p[2] = v[2];
+}
+
+// a term of weight 0 is left out, and with all three of a frame the walk itself
+__device__ __forceinline__ bool frame_weights_any(const double* w) { return w[0] != 0.0 || w[1] != 0.0 || w[2] != 0.0; }
+
+// The frame's world position p and its true point jacobian P = dp / d(delta q) (3 x nv, stored at P[3 * column + row]; only
+// the columns of the joints on the path root .. joint are written, their tangent indices are returned as a bit mask):
+//   revolute joint i: a_i x (p - o_i), prismatic: a_i (world axis a_i, world origin o_i of joint i);
+//   free-flyer root (body twists, linear part first): R_0 e_c and (R_0 e_c) x (p - o_0).
+// Not rbd::frame_position's rows: those are the reference's WORLD-frame rows, whose lever arm goes to the world origin.
+// chain, aw, ow: room for the path, its world axes (9 + 3 * joints doubles: a free-flyer root's rotation comes first) and its
+// world origins (3 * joints doubles)
+__device__ inline unsigned long long frame_point_jacobian(const DevModel& m, int joint, const double* off, const double* q, double* p,
+                                                          double* P, int* chain, double* aw, double* ow) {
+  int len = 0;
+  for (int j = joint; j >= 0; j = m.parent[j]) chain[len++] = j;
+  double oR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, op[3] = {0, 0, 0};
+  for (int c = len - 1; c >= 0; --c) {
+    const int i = chain[c];
+    double E[9], r[3], Rc[9], t[3], nR[9];
+    place(m, i, q, E, r);
+    for (int k = 0; k < 3; ++k)
+      for (int l = 0; l < 3; ++l) Rc[3 * k + l] = E[3 * l + k];
+    mv3(oR, r, t);
+    op[0] += t[0]; op[1] += t[1]; op[2] += t[2];
+    mm3(oR, Rc, nR);
+    for (int k = 0; k < 9; ++k) oR[k] = nR[k];
+    if (i == 0 && m.ff) {
+      for (int k = 0; k < 9; ++k) aw[k] = oR[k];             // the root's rotation: its columns are R_0 e_c
+    } else {
+      mv3(oR, m.axis[i], aw + 9 + 3 * c);
+    }
+    ow[3 * c] = op[0]; ow[3 * c + 1] = op[1]; ow[3 * c + 2] = op[2];
+  }
+  double t[3];
+  mv3(oR, off, t);
+  p[0] = op[0] + t[0]; p[1] = op[1] + t[1]; p[2] = op[2] + t[2];
+  unsigned long long mask = 0;
+  for (int c = len - 1; c >= 0; --c) {
+    const int i = chain[c];
+    const double lever[3] = {p[0] - ow[3 * c], p[1] - ow[3 * c + 1], p[2] - ow[3 * c + 2]};
+    if (i == 0 && m.ff) {
+      for (int cc = 0; cc < 3; ++cc) {
+        const double e[3] = {aw[cc], aw[3 + cc], aw[6 + cc]};
+        P[3 * cc] = e[0]; P[3 * cc + 1] = e[1]; P[3 * cc + 2] = e[2];
+        cross3(e, lever, P + 3 * (3 + cc));
+      }
+      mask |= 63ull;
+    } else {
+      const int vi = m.ff ? i + 5 : i;
+      const double* a = aw + 9 + 3 * c;
+      if (m.jtype[i] == DDP_HIP_JOINT_REVOLUTE) cross3(a, lever, P + 3 * vi);
+      else { P[3 * vi] = a[0]; P[3 * vi + 1] = a[1]; P[3 * vi + 2] = a[2]; }
+      mask |= 1ull << vi;
+    }
+  }
+  return mask;
+}
+
+}  // namespace rbd

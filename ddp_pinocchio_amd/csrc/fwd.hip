@@ -11,6 +11,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "frame_cost.h"
 #include "internal.h"
 #include "rbd.h"
 
@@ -39,6 +40,7 @@ struct FwdParams {
   const double *xref, *wx, *uref, *wu;   // tracking cost (DDP_HIP_FLAG_TRACKING_COST), else null
   int32_t track;
   const double *ctrl_lo, *ctrl_hi;       // control bounds (DDP_HIP_FLAG_CONTROL_BOUNDS), else null
+  FrameCostDev fc;                       // frame-position cost (DDP_HIP_FLAG_FRAME_COST); fc.target null: no terms
 };
 
 // constraint value at solver time t: constraint_advance_time_t::eval_to (problem.hpp:563-567) applied
@@ -94,14 +96,37 @@ __device__ __forceinline__ double track_control_sum(const FwdParams& p, int b, i
   return 0.5 * su;
 }
 
+// sum_a w_a (p_f(q)_a - g_a)^2 of frame f at (instance, t) pair bt1 = b (T + 1) + t (ddp_hip.h: DDP_HIP_FLAG_FRAME_COST).  A term
+// of weight 0 is left out, and with all three of them the walk along the frame's path.  M: DevModel, or the CoopModel in LDS
+template <class M>
+__device__ __forceinline__ double frame_term(const FrameCostDev& fc, const M& m, bool ff, int f, int64_t bt1, const double* q) {
+  const double* w = fc.weight + (bt1 * fc.nf + f) * 3;
+  if (!rbd::frame_weights_any(w)) return 0.0;
+  const double* g = fc.target + (bt1 * fc.nf + f) * 3;
+  const double off[3] = {fc.off[f][0], fc.off[f][1], fc.off[f][2]};
+  double pf[3], s = 0;
+  rbd::frame_point(m, ff, fc.joint[f], off, q, pf);
+  for (int a = 0; a < 3; ++a) { const double r = pf[a] - g[a]; if (w[a] != 0.0) s += w[a] * r * r; }
+  return s;
+}
+// the frame terms of l at time t of instance b (t = T: of lf), one lane for all frames
+__device__ double frame_cost_sum(const FrameCostDev& fc, const DevModel& m, int64_t bt1, const double* x) {
+  double s = 0;
+  for (int f = 0; f < fc.nf; ++f) s += frame_term(fc, m, m.ff != 0, f, bt1, x);
+  return 0.5 * s;
+}
+
 // one term of cost_seq_aug (ddp.hpp:730): l + pe.ce + mu/2 |ce|^2
-template <int NJ>
+// FRAME: + the frame terms (DDP_HIP_FLAG_FRAME_COST), in instantiations of their own of cost_kernel, forward_kernel and
+// cand_cost_kernel: a run-time branch here moved the spills of the kernels that exist without the flag
+template <int NJ, bool FRAME = false>
 __device__ double stage_cost(const FwdParams& p, const DevModel& m, int b, int64_t t, const double* x, const double* u, double mu) {
   const int nv = m.nv, n = 2 * nv, nx = m.nq + nv;
   double un = 0;
   for (int i = 0; i < nv; ++i) un += u[i] * u[i];
   double cost = 0.5 * m.c * un;                                   // problem_t::l, problem.hpp:937-942
   if (p.track) cost += track_state_cost(p, b, t, x) + track_control_sum(p, b, t, u);   // + the tracking terms
+  if constexpr (FRAME) cost += frame_cost_sum(p.fc, m, (int64_t)b * (p.d.T + 1) + t, x);   // + the frame terms
   const int e = (int)p.ne[t];
   if (e > 0) {
     double ce[NJ > 3 ? NJ : 3];
@@ -145,12 +170,15 @@ __global__ void rollout_kernel(FwdParams p) {
 }
 
 // problem_t::lf (problem.hpp:932-936: 0), or the tracking cost's terminal term
-__device__ __forceinline__ double terminal_cost(const FwdParams& p, int b, const double* x) {
-  return p.track ? track_state_cost(p, b, p.d.T, x) : 0.0;
+template <bool FRAME = false>
+__device__ __forceinline__ double terminal_cost(const FwdParams& p, const DevModel& m, int b, const double* x) {
+  double cost = p.track ? track_state_cost(p, b, p.d.T, x) : 0.0;
+  if constexpr (FRAME) cost += frame_cost_sum(p.fc, m, (int64_t)b * (p.d.T + 1) + p.d.T, x);
+  return cost;
 }
 
 // cost_seq_aug of one trajectory: one lane per (instance, t)
-template <int NJ>
+template <int NJ, bool FRAME = false>
 __global__ void cost_kernel(FwdParams p, int which) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t T = p.d.T;
@@ -161,17 +189,17 @@ __global__ void cost_kernel(FwdParams p, int which) {
   const int nx = m.nq + m.nv, nu = m.nv;
   double* out = (which == 0 ? p.costs_old : p.costs_new) + (int64_t)b * (T + 1);
   const double* xs = (which == 0 ? p.x_old : p.x_new) + ((int64_t)b * (T + 1) + t) * nx;
-  if (t == T) { out[T] = terminal_cost(p, b, xs); return; }
+  if (t == T) { out[T] = terminal_cost<FRAME>(p, m, b, xs); return; }
   const double* us = (which == 0 ? p.u_old : p.u_new) + ((int64_t)b * T + t) * nu;
   double x[2 * NJ + 1], u[NJ];
   for (int i = 0; i < nx; ++i) x[i] = xs[i];
   for (int i = 0; i < nu; ++i) u[i] = us[i];
-  out[t] = stage_cost<NJ>(p, m, b, t, x, u, p.mu[b]);
+  out[t] = stage_cost<NJ, FRAME>(p, m, b, t, x, u, p.mu[b]);
 }
 
 // closed-loop rollouts (ddp_fwd.ipp:39-51) of n_alpha candidate steps per instance + their summed cost
 // difference (ddp_fwd.ipp:54-56)
-template <int NJ>
+template <int NJ, bool FRAME = false>
 __global__ void forward_kernel(FwdParams p) {
   // the model table in LDS: the dynamics of every step read it joint by joint (axis, placement, inertia: some 40 words per joint
   // and evaluation), and from global memory each of those reads is a dependent L2 round trip of the one lane that rolls out
@@ -221,12 +249,12 @@ __global__ void forward_kernel(FwdParams p) {
       for (int i = 0; i < nu; ++i) u[i] = u[i] < lo[i] ? lo[i] : (u[i] > hi[i] ? hi[i] : u[i]);
     }
     for (int i = 0; i < nu; ++i) uw[t * nu + i] = u[i];
-    const double c_new = stage_cost<NJ>(p, m, b, t, x, u, mu);
+    const double c_new = stage_cost<NJ, FRAME>(p, m, b, t, x, u, mu);
     dsum += c_new - cold[t];
     rbd::eval_f<NJ>(m, x, u, xn);                                             // :50
     for (int i = 0; i < nx; ++i) { x[i] = xn[i]; xw[(t + 1) * nx + i] = xn[i]; }
   }
-  dsum += terminal_cost(p, b, x) - cold[T];
+  dsum += terminal_cost<FRAME>(p, m, b, x) - cold[T];
   p.fw_dcost[(int64_t)b * na + a] = dsum;
 }
 
@@ -260,6 +288,20 @@ __device__ __forceinline__ double track_lanes_sum(const FwdParams& p, int b, int
     }
   }
   double v = 0.5 * s + 0.5 * su;
+#pragma unroll
+  for (int k = NH / 2; k >= 1; k /= 2) v += __shfl_xor(v, k, NH);
+  return v;
+}
+
+// The frame terms of one candidate of forward_kernel_lat2 at time t (t = T: lf): lane h < nf walks frame h's path from the
+// candidate's state and the model tables in LDS (the placements of q_t do not exist yet where this is called, and x_T never
+// gets a dynamics step); the partial sums meet in the same fixed butterfly as track_lanes_sum's.  Every lane of the wave calls it
+template <bool FF, class M>
+__device__ __forceinline__ double frame_lanes_sum(const FwdParams& p, const M& cm, int b, int64_t t, const double* x, int h, bool live) {
+  constexpr int NH = 16;
+  double s = 0;
+  if (live && h < p.fc.nf) s = frame_term(p.fc, cm, FF, h, (int64_t)b * (p.d.T + 1) + t, x);
+  double v = 0.5 * s;
 #pragma unroll
   for (int k = NH / 2; k >= 1; k /= 2) v += __shfl_xor(v, k, NH);
   return v;
@@ -302,11 +344,14 @@ __device__ unsigned long long g_fwd_stamps[12];
 // rbd::aba_tree_coop2w's free-flyer form
 // TRACK: the tracking cost (DDP_HIP_FLAG_TRACKING_COST) of an unconstrained problem, formed inline by the 16 lanes of a candidate
 // (track_lanes_sum); an instantiation of its own, so that the kernel without it is the one it was
+// COST: bit 0 the tracking terms (TRACK above), bit 1 the frame terms (DDP_HIP_FLAG_FRAME_COST: frame_lanes_sum), each
+// combination an instantiation of its own as well
 // BOX: control bounds (DDP_HIP_FLAG_CONTROL_BOUNDS): u is clamped to [lo_t, hi_t] after the control update; lo_t, hi_t ride in the
 // prefetch beside k_t.  Closed loop only, an instantiation of its own as well
-template <int NJ, bool OPEN = false, bool FF = false, bool TRACK = false, bool BOX = false>
+template <int NJ, bool OPEN = false, bool FF = false, int COST = 0, bool BOX = false>
 __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
   static_assert(!(OPEN && BOX), "the open-loop rollout applies U as given");
+  constexpr bool TRACK = (COST & 1) != 0, FRAME = (COST & 2) != 0;
   using L = typename std::conditional<BOX, FwdLat2LdsBox<NJ>, FwdLat2Lds<NJ>>::type;
   constexpr int NC = L::NC, NH = L::NH;
   constexpr int n = 2 * NJ, nq = FF ? NJ + 1 : NJ, nx = nq + NJ, nu = NJ, XS = L::n;   // XS: stride of a candidate's state in LDS
@@ -468,11 +513,12 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
     FSTAMP(fs, 0);
     double c_track = 0.0;
     if constexpr (TRACK) c_track = track_lanes_sum<FF>(p, b, t, x, u, h, live);
+    if constexpr (FRAME) c_track += frame_lanes_sum<FF>(p, S.model, b, t, x, h, live);
     if (h == 0 && live && p.cost_inline) {
       double un = 0;
       for (int i = 0; i < nu; ++i) un += u[i] * u[i];
       double c_new = 0.5 * mc * un;                                             // problem_t::l (constrained problems: cand_cost_kernel)
-      if constexpr (TRACK) c_new += c_track;
+      if constexpr (TRACK || FRAME) c_new += c_track;
       dsum += c_new - cold_t;
     }
     }
@@ -523,6 +569,7 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
 #endif
   double c_term = 0.0;
   if constexpr (TRACK) { if (lead) c_term = track_lanes_sum<FF>(p, b, T, x, u, h, live); }
+  if constexpr (FRAME) { if (lead) c_term += frame_lanes_sum<FF>(p, S.model, b, T, x, h, live); }
   if (!OPEN && h == 0 && live && lead && p.cost_inline) {
     dsum += c_term - cold[T];
     p.fw_dcost[(int64_t)b * na + a] = dsum;
@@ -532,7 +579,7 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
 // Constrained problems on the latency path.  Only the rollout is sequential in t; the cost terms of a rolled-out
 // candidate (cost_seq_aug, ddp.hpp:699-735: l + pe . ce + mu/2 |ce|^2, with ce_t = eq(t, x_t, u_t) two look-ahead dynamics steps
 // away, problem.hpp:563-567; lf at t = T) are independent across t: one lane per (instance, candidate, t), t = 0 .. T ...
-template <int NJ>
+template <int NJ, bool FRAME = false>
 __global__ void cand_cost_kernel(FwdParams p) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t T = p.d.T;
@@ -548,10 +595,10 @@ __global__ void cand_cost_kernel(FwdParams p) {
   double x[2 * NJ + 1], u[NJ];
   for (int i = 0; i < nx; ++i) x[i] = xs[i];
   double* out = p.fw_cost + ((int64_t)b * na + a) * (T + 1) + t;
-  if (t == T) { *out = terminal_cost(p, b, x); return; }
+  if (t == T) { *out = terminal_cost<FRAME>(p, m, b, x); return; }
   const double* us = p.fw_u + (((int64_t)b * na + a) * T + t) * nu;
   for (int i = 0; i < nu; ++i) u[i] = us[i];
-  *out = stage_cost<NJ>(p, m, b, t, x, u, p.mu[b]);
+  *out = stage_cost<NJ, FRAME>(p, m, b, t, x, u, p.mu[b]);
 }
 // ... and one lane per (instance, candidate) adds the differences up in the order of forward_kernel (ddp_fwd.ipp:54-56)
 __global__ void cand_sum_kernel(FwdParams p) {
@@ -637,8 +684,19 @@ FwdParams make_params(ddp_hip_ctx* ctx) {
   p.cost_inline = ctx->d.Etot == 0 ? 1 : 0;
   p.fw_cost = ctx->fw_cost;
   p.ctrl_lo = S(DDP_HIP_SEQ_CTRL_LO); p.ctrl_hi = S(DDP_HIP_SEQ_CTRL_HI);
+  p.fc = frame_cost_dev(ctx);
   p.round = 0;
   return p;
+}
+
+// the closed-loop instantiation of the latency kernel for (free-flyer root, inline cost terms, control bounds)
+using Lat2Fn = void (*)(FwdParams);
+Lat2Fn lat2_kernel(bool ff, int cost, bool box) {
+#define LAT2_ROW(FF, COST) {&forward_kernel_lat2<38, false, FF, COST, false>, &forward_kernel_lat2<38, false, FF, COST, true>}
+  static const Lat2Fn table[2][4][2] = {{LAT2_ROW(false, 0), LAT2_ROW(false, 1), LAT2_ROW(false, 2), LAT2_ROW(false, 3)},
+                                        {LAT2_ROW(true, 0), LAT2_ROW(true, 1), LAT2_ROW(true, 2), LAT2_ROW(true, 3)}};
+#undef LAT2_ROW
+  return table[ff ? 1 : 0][cost & 3][box ? 1 : 0];
 }
 
 #define DISPATCH_NJ(nv, CALL)                 \
@@ -675,25 +733,16 @@ int fwd_setup(ddp_hip_ctx* ctx) {
   HIP_TRY(hipMalloc(&ctx->fw_state_d, sizeof(int32_t) * (size_t)B));
   if (d.nv == 38) {
     // per device, by every context (the attribute is not process-wide)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)sizeof(FwdLat2Lds<38>)));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)sizeof(FwdLat2Lds<38>)));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)sizeof(FwdLat2Lds<38>)));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)sizeof(FwdLat2Lds<38>)));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)sizeof(FwdLat2Lds<38>)));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)sizeof(FwdLat2Lds<38>)));
-    if (ctx->flags & DDP_HIP_FLAG_CONTROL_BOUNDS) {
-      const int lds_box = (int)sizeof(FwdLat2LdsBox<38>);
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_box));
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_box));
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, false, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_box));
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, false, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_box));
-    }
+    const int lds = (int)sizeof(FwdLat2Lds<38>), lds_box = (int)sizeof(FwdLat2LdsBox<38>);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    // the closed-loop instantiations this context's flags can reach (lat2_kernel)
+    const bool frame = (ctx->flags & DDP_HIP_FLAG_FRAME_COST) != 0, bounds = (ctx->flags & DDP_HIP_FLAG_CONTROL_BOUNDS) != 0;
+    for (int ff = 0; ff < 2; ++ff)
+      for (int cost = 0; cost < (frame ? 4 : 2); ++cost)
+        for (int box = 0; box < (bounds ? 2 : 1); ++box)
+          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lat2_kernel(ff != 0, cost, box != 0)), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      box ? lds_box : lds));
   }
   return DDP_HIP_OK;
 }
@@ -740,7 +789,10 @@ static int launch_cost(ddp_hip_ctx* ctx, FwdParams& p, int which) {
   const int64_t total = ctx->d.batch * (ctx->d.T + 1);
   const unsigned grid = (unsigned)((total + bs - 1) / bs);
 #define CALL(NJ) hipLaunchKernelGGL((cost_kernel<NJ>), dim3(grid), dim3(bs), 0, ctx->stream, p, which)
-  DISPATCH_NJ(ctx->d.nv, CALL);
+#define CALL_FRAME(NJ) hipLaunchKernelGGL((cost_kernel<NJ, true>), dim3(grid), dim3(bs), 0, ctx->stream, p, which)
+  if (p.fc.target) DISPATCH_NJ(ctx->d.nv, CALL_FRAME);
+  else DISPATCH_NJ(ctx->d.nv, CALL);
+#undef CALL_FRAME
 #undef CALL
   HIP_TRY(hipGetLastError());
   return DDP_HIP_OK;
@@ -786,26 +838,22 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
     const bool lat_path = fwd_lat_supported(ctx) && n_alpha <= 8;
     if (lat_path) {
       const dim3 g((unsigned)(2 * B)), blk(128);
-      const size_t lds = sizeof(FwdLat2Lds<38>);
-      if (p.ctrl_lo) {
-        const size_t ldb = sizeof(FwdLat2LdsBox<38>);
-        const bool tr = p.track && p.cost_inline;
-        if (tr && ctx->model_h.ff) hipLaunchKernelGGL((forward_kernel_lat2<38, false, true, true, true>), g, blk, ldb, ctx->stream, p);
-        else if (tr) hipLaunchKernelGGL((forward_kernel_lat2<38, false, false, true, true>), g, blk, ldb, ctx->stream, p);
-        else if (ctx->model_h.ff) hipLaunchKernelGGL((forward_kernel_lat2<38, false, true, false, true>), g, blk, ldb, ctx->stream, p);
-        else hipLaunchKernelGGL((forward_kernel_lat2<38, false, false, false, true>), g, blk, ldb, ctx->stream, p);
-      } else if (p.track && p.cost_inline) {
-        if (ctx->model_h.ff) hipLaunchKernelGGL((forward_kernel_lat2<38, false, true, true>), g, blk, lds, ctx->stream, p);
-        else hipLaunchKernelGGL((forward_kernel_lat2<38, false, false, true>), g, blk, lds, ctx->stream, p);
-      } else if (ctx->model_h.ff) hipLaunchKernelGGL((forward_kernel_lat2<38, false, true>), g, blk, lds, ctx->stream, p);
-      else hipLaunchKernelGGL((forward_kernel_lat2<38>), g, blk, lds, ctx->stream, p);
+      // the cost terms an unconstrained problem forms inline: bit 0 tracking, bit 1 frames (forward_kernel_lat2: COST)
+      const int cost = p.cost_inline ? (p.track ? 1 : 0) | (p.fc.target ? 2 : 0) : 0;
+      const bool box = p.ctrl_lo != nullptr;
+      hipLaunchKernelGGL(lat2_kernel(ctx->model_h.ff != 0, cost, box), g, blk, box ? sizeof(FwdLat2LdsBox<38>) : sizeof(FwdLat2Lds<38>), ctx->stream, p);
       if (!p.cost_inline) {
-        hipLaunchKernelGGL((cand_cost_kernel<38>), dim3((unsigned)((B * n_alpha * (d.T + 1) + 63) / 64)), dim3(64), 0, ctx->stream, p);
+        const dim3 gc((unsigned)((B * n_alpha * (d.T + 1) + 63) / 64));
+        if (p.fc.target) hipLaunchKernelGGL((cand_cost_kernel<38, true>), gc, dim3(64), 0, ctx->stream, p);
+        else hipLaunchKernelGGL((cand_cost_kernel<38>), gc, dim3(64), 0, ctx->stream, p);
         hipLaunchKernelGGL(cand_sum_kernel, dim3((unsigned)((B * n_alpha + 63) / 64)), dim3(64), 0, ctx->stream, p);
       }
     } else {
 #define CALL(NJ) hipLaunchKernelGGL((forward_kernel<NJ>), dim3(grid), dim3(bs), 0, ctx->stream, p)
-      DISPATCH_NJ(d.nv, CALL);
+#define CALL_FRAME(NJ) hipLaunchKernelGGL((forward_kernel<NJ, true>), dim3(grid), dim3(bs), 0, ctx->stream, p)
+      if (p.fc.target) DISPATCH_NJ(d.nv, CALL_FRAME);
+      else DISPATCH_NJ(d.nv, CALL);
+#undef CALL_FRAME
 #undef CALL
     }
     prof_end(ctx, DDP_HIP_K_FWD_ROLLOUT);

@@ -170,6 +170,14 @@ struct ddp_hip_ctx {
   std::vector<int32_t> active_h;   // [batch], 1 = active
   bool all_active = true;
 
+  // frame-position cost (DDP_HIP_FLAG_FRAME_COST; ctx.hip: ddp_hip_frame_cost_*, frame_cost.h)
+  int32_t fc_nf = 0;                          // cost frames set (0: none yet)
+  int32_t fc_joint[DDP_HIP_MAX_COST_FRAMES] = {};
+  double fc_off[DDP_HIP_MAX_COST_FRAMES][3] = {};
+  double* fc_target_d = nullptr;              // [batch][T+1][fc_nf][3] (room for DDP_HIP_MAX_COST_FRAMES)
+  double* fc_weight_d = nullptr;
+  bool fc_live = false;                       // some non-zero weight was uploaded since the frames were set: the kernels form the terms
+
   bool box_dirty = false;       // CTRL_LO / CTRL_HI were uploaded since lo <= hi was last checked (ctx.hip: box_check)
 
   bool async_mode = false;     // ddp_hip_set_async: entry points that hand nothing back to the host do not wait for the stream

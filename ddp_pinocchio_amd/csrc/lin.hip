@@ -13,6 +13,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include "frame_cost.h"
 #include "internal.h"
 #include "lin_common.h"
 #include "rbd.h"
@@ -95,6 +96,72 @@ __global__ void lin_track_cost_kernel(LinParams p) {
     p.lu[bt * m + i] = wu != 0.0 ? c * u + wu * (u - p.uref[bt * m + i]) : c * u;
   }
   for (int i = tid; i < m * m; i += blockDim.x) p.luu[bt * m * m + i] = (i % m == i / m) ? 1.0 * c + p.wu[bt * m + i % m] : 0.0;
+}
+
+// Frame-position cost (DDP_HIP_FLAG_FRAME_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after lin_cost_kernel /
+// lin_track_cost_kernel on the same stream: their output is the starting point, and only the entries of the joints on the
+// frames' paths are read and rewritten.  Lane f walks frame f's path once for p_f and the path columns of its point jacobian
+// P_f (rbd::frame_point_jacobian), kept in LDS; then the wave adds
+//   lx[i] += sum_f sum_a P_f[a][i] (w_a r_a),   lxx[i][j] += sum_f sum_a P_f[a][min] w_a P_f[a][max]     (Gauss-Newton)
+// over the tangent rows i, j < nv, frames and axes in their fixed order and entry (i, j) in (min, max) order: the block stays
+// symmetric bit for bit.  A term of weight 0 is left out, a block whose weights are all 0 returns at once.  t = T: lfx / lfxx
+__global__ __launch_bounds__(64) void lin_frame_cost_kernel(LinParams p, FrameCostDev fc) {
+  constexpr int F = DDP_HIP_MAX_COST_FRAMES;
+  const int64_t T = p.d.T;
+  const int64_t bt1 = blockIdx.x;
+  const int b = (int)(bt1 / (T + 1));
+  const int64_t t = bt1 % (T + 1);
+  const int n = (int)p.d.n, nv = (int)p.d.nv, nx = (int)p.d.nx;
+  const int tid = threadIdx.x, nf = fc.nf;
+  const double* g = fc.target + bt1 * nf * 3;
+  const double* w = fc.weight + bt1 * nf * 3;
+  bool any = false;
+  for (int k = 0; k < 3 * nf; ++k) any |= w[k] != 0.0;
+  if (!any) return;
+  __shared__ double s_P[F][3 * DDP_MAXJ], s_aw[F][9 + 3 * DDP_MAXJ], s_ow[F][3 * DDP_MAXJ], s_w[F][3], s_wr[F][3];
+  __shared__ int s_chain[F][DDP_MAXJ];
+  __shared__ unsigned long long s_mask[F];
+  if (tid < nf) {
+    unsigned long long mask = 0;
+    if (rbd::frame_weights_any(w + 3 * tid)) {
+      double pf[3];
+      const double off[3] = {fc.off[tid][0], fc.off[tid][1], fc.off[tid][2]};
+      mask = rbd::frame_point_jacobian(*p.model, fc.joint[tid], off, p.x + bt1 * nx, pf, s_P[tid], s_chain[tid], s_aw[tid], s_ow[tid]);
+      for (int a = 0; a < 3; ++a) {
+        const double wa = w[3 * tid + a];
+        s_w[tid][a] = wa;
+        s_wr[tid][a] = wa != 0.0 ? wa * (pf[a] - g[3 * tid + a]) : 0.0;
+      }
+    }
+    s_mask[tid] = mask;
+  }
+  __syncthreads();
+  unsigned long long all = 0;
+  for (int f = 0; f < nf; ++f) all |= s_mask[f];
+  double* gx = t < T ? p.lx + ((int64_t)b * T + t) * n : p.lfx + (int64_t)b * n;
+  double* gxx = t < T ? p.lxx + ((int64_t)b * T + t) * n * n : p.lfxx + (int64_t)b * n * n;
+  for (int i = tid; i < nv; i += blockDim.x) {
+    if (!((all >> i) & 1)) continue;
+    double s = 0.0;
+    for (int f = 0; f < nf; ++f)
+      if ((s_mask[f] >> i) & 1)
+        for (int a = 0; a < 3; ++a)
+          if (s_w[f][a] != 0.0) s += s_P[f][3 * i + a] * s_wr[f][a];
+    gx[i] += s;
+  }
+  for (int e = tid; e < nv * nv; e += blockDim.x) {
+    const int i = e % nv, j = e / nv;
+    const int lo = i < j ? i : j, hi = i < j ? j : i;
+    double h = 0.0;
+    bool hit = false;
+    for (int f = 0; f < nf; ++f)
+      if (((s_mask[f] >> i) & 1) && ((s_mask[f] >> j) & 1)) {
+        hit = true;
+        for (int a = 0; a < 3; ++a)
+          if (s_w[f][a] != 0.0) h += s_P[f][3 * lo + a] * s_w[f][a] * s_P[f][3 * hi + a];
+      }
+    if (hit) gxx[i + (int64_t)j * n] += h;
+  }
 }
 
 template <int NJ>
@@ -863,6 +930,8 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, uint32_t stages) {
     if (ctx->flags & DDP_HIP_FLAG_TRACKING_COST)
       hipLaunchKernelGGL(lin_track_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p);
     else hipLaunchKernelGGL(lin_cost_kernel, dim3((unsigned)BT), dim3(64), 0, ctx->stream, p);
+    const FrameCostDev fc = frame_cost_dev(ctx);
+    if (fc.target) hipLaunchKernelGGL(lin_frame_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, fc);
   }
   // static-topology path: the q- / v-caches of the mode-2 stencil also serve the first order (base configuration and
   // base (q, v)), so they are built ahead of whichever stage comes first

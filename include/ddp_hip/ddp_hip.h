@@ -157,6 +157,23 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * lo > hi (checked after an upload of either); writes through ddp_hip_device_ptr are the caller's responsibility.  With bounds
  * that never bind a context computes bit for bit what it computes without the flag. */
 #define DDP_HIP_FLAG_CONTROL_BOUNDS 8u
+/* Carry up to DDP_HIP_MAX_COST_FRAMES cost frames -- frame f is the point off_f fixed in joint joint_f (the convention of
+ * ddp_hip_problem.frame_joint / frame_off), shared by the batch -- and add, per instance b, with p_f(q) the frame's world
+ * position, targets g[b][t][f] in R^3 and weights w[b][t][f] in R^3 (per world axis, >= 0), r_f = p_f(q_t) - g[b][t][f]:
+ *   l(t, x, u) += 1/2 sum_f sum_a w[b][t][f][a] r_f,a^2      t < T
+ *   lf(x_T)    += 1/2 sum_f sum_a w[b][T][f][a] r_f,a^2
+ * to whatever the context optimises otherwise (c/2 |u|^2, the tracking terms, the constraint terms of cost_seq_aug).
+ * Derivatives in the tangent at x, P_f = dp_f / d(delta q) (3 x nv, the true point jacobian: a_i x (p_f - o_i) for a revolute
+ * joint i on the path root .. joint_f with world axis a_i and world origin o_i, a_i for a prismatic one, R_0 e_c and
+ * (R_0 e_c) x (p_f - o_0) on a free-flyer root; NOT the WORLD-frame rows of ddp_hip_model_frame):
+ *   lx[q rows] += sum_f P_f^T (w o r_f),  lxx[q, q] += sum_f P_f^T diag(w) P_f,  lfx / lfxx alike at T;
+ * velocity rows and columns, lu, luu and lux are untouched.  lxx is Gauss-Newton (the term sum_a w_a r_a d^2 p_a is dropped:
+ * exact where r = 0) and symmetric bit for bit.  The frame data travels through ddp_hip_frame_cost_* below, not through
+ * ddp_hip_upload.  At create there are no frames; tree models only (a pendulum: DDP_HIP_E_UNSUPPORTED).  A term of weight 0 is
+ * left out (not multiplied by 0): with no frames or all weights 0 a context computes bit for bit what it computes without the
+ * flag. */
+#define DDP_HIP_FLAG_FRAME_COST 16u
+#define DDP_HIP_MAX_COST_FRAMES 4
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -181,6 +198,14 @@ double* ddp_hip_device_ptr(ddp_hip_ctx* ctx, int seq);               /* [batch][
 int ddp_hip_upload(ddp_hip_ctx* ctx, int seq, const double* host, int64_t first_instance, int64_t n_instances);
 int ddp_hip_download(ddp_hip_ctx* ctx, int seq, double* host, int64_t first_instance, int64_t n_instances);
 int ddp_hip_fill(ddp_hip_ctx* ctx, int seq, double value);
+/* The frame cost of a context created with DDP_HIP_FLAG_FRAME_COST (else DDP_HIP_E_UNSUPPORTED), stream-ordered like
+ * ddp_hip_upload.  set_frames: n_frames in 1 .. DDP_HIP_MAX_COST_FRAMES, joint[n_frames] inside the model, off[n_frames][3]
+ * finite (else DDP_HIP_E_ARG); it may be called again: with the same count the targets and weights stay, with another they
+ * are reset to 0.  upload / download: host arrays [n_instances][T+1][n_frames][3]; a NULL pointer leaves that side as it is;
+ * an upload before frames are set, a negative or non-finite weight and a non-finite target are refused (DDP_HIP_E_ARG). */
+int ddp_hip_frame_cost_set_frames(ddp_hip_ctx* ctx, int32_t n_frames, const int32_t* joint, const double* off);
+int ddp_hip_frame_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first_instance, int64_t n_instances);
+int ddp_hip_frame_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first_instance, int64_t n_instances);
 
 /* make_trajectory (ddp.hpp:392-415): X[0] and U given -> X[1..T] */
 int ddp_hip_rollout(ddp_hip_ctx* ctx);
