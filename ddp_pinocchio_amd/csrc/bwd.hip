@@ -673,13 +673,14 @@ SweepPlan sweep_plan(const ddp_hip_ctx* ctx) {
   // (K5 stages the multiplier jacobians over its V / F region: up to 52 constraint rows per step fit)
   s.fast = d.n == 76 && d.m == 38 && d.emax <= 52 && !sw.generic_bwd;
   s.sym_ok = s.fast && ctx->jobs_sym_d && !sw.k3_no_sym;
-  s.sym = s.sym_ok && ctx->tensors_sym;
+  const TensorOrigin o = ctx->tensors.origin;
+  s.sym = s.sym_ok && (o == TensorOrigin::Symmetric || o == TensorOrigin::Stencil);
   const bool half_ok = s.fast && ctx->jobs_half_d && !sw.k3_no_half;
   // K3h needs both structural facts: symmetry and the zero configuration rows (the static stencil's own tensors) ...
-  if (half_ok && s.sym && ctx->tensor_tops_zero && ctx->tensor_tops_sparse) s.half_mode = 1;
+  if (half_ok && s.sym && o == TensorOrigin::Stencil) s.half_mode = 1;
   // ... or the structure the analytic mode-1 pass leaves (lin_analytic.hip): q+ = q + dt v has constant jacobian rows and M^-1 does
   // not depend on u, so the upper halves and f_uu are zeros it wrote itself
-  else if (half_ok && ctx->fuu_zero && ctx->model_h.fd_mode == 1) s.half_mode = 2;
+  else if (half_ok && o == TensorOrigin::Analytic1) s.half_mode = 2;
   return s;
 }
 
@@ -770,7 +771,7 @@ extern "C" int ddp_hip_backward(ddp_hip_ctx* ctx, double* reg_io, double* mu_io,
   if (box) { const int rc_ = box_check(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
   // the static stencil leaves the f_xx block out that the symmetric sweep never reads: any other sweep needs it (the tensors
   // may have changed since the linearisation: upload / device_ptr)
-  if (p.has_tensors && ctx->fxx_mirror_pending && !plan.sym) { const int rc_ = lin_materialize_fxx(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
+  if (p.has_tensors && ctx->tensors.mirror_pending && !plan.sym) { const int rc_ = lin_materialize_fxx(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
 
   HIP_TRY(hipMemcpyAsync(ctx->reg_d, reg_io, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(ctx->mu_d, mu_io, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, ctx->stream));

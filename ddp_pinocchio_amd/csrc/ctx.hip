@@ -404,12 +404,8 @@ extern "C" int64_t ddp_hip_seq_size(const ddp_hip_ctx* ctx, int seq) {
 
 extern "C" double* ddp_hip_device_ptr(ddp_hip_ctx* ctx, int seq) {
   if (!ctx || seq < 0 || seq >= DDP_HIP_SEQ_COUNT) return nullptr;
-  if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUX || seq == DDP_HIP_SEQ_FUU) { ctx->tensor_tops_zero = false; ctx->tensor_tops_sparse = false; ctx->fuu_zero = false; }
-  if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUU) {
-    (void)hipSetDevice(ctx->device);
-    if (lin_materialize_fxx(ctx) != DDP_HIP_OK) return nullptr;
-    ctx->tensors_sym = false;                              // the caller may write through the pointer: K3 reads every half-slab again
-  }
+  if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUU) (void)hipSetDevice(ctx->device);   // (the mirror images may have to be formed)
+  if (tensors_written_outside(ctx, seq) != DDP_HIP_OK) return nullptr;   // the caller may write through the pointer
   return ctx->seq[seq].ptr;
 }
 
@@ -454,11 +450,7 @@ extern "C" int ddp_hip_upload(ddp_hip_ctx* ctx, int seq, const double* host, int
   if (!host) return DDP_HIP_E_ARG;
   if (!cost_values_ok(ctx, seq, host, sz * count)) return DDP_HIP_E_ARG;
   HIP_TRY(hipSetDevice(ctx->device));
-  if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUX || seq == DDP_HIP_SEQ_FUU) { ctx->tensor_tops_zero = false; ctx->tensor_tops_sparse = false; ctx->fuu_zero = false; }
-  if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUU) {   // tensors from outside: no symmetry assumed (bwd_split.h)
-    { const int rc_ = lin_materialize_fxx(ctx); if (rc_ != DDP_HIP_OK) return rc_; }   // what is not overwritten (other instances, the other tensor) stays whole
-    ctx->tensors_sym = false;
-  }
+  { const int rc_ = tensors_written_outside(ctx, seq); if (rc_ != DDP_HIP_OK) return rc_; }
   HIP_TRY(hipMemcpyAsync(ctx->seq[seq].ptr + first * sz, host, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (seq == DDP_HIP_SEQ_CTRL_LO || seq == DDP_HIP_SEQ_CTRL_HI) ctx->box_dirty = true;
@@ -501,12 +493,7 @@ extern "C" int ddp_hip_fill(ddp_hip_ctx* ctx, int seq, double value) {
   if ((seq == DDP_HIP_SEQ_CTRL_LO || seq == DDP_HIP_SEQ_CTRL_HI) && !bound_ok(seq, value)) return DDP_HIP_E_ARG;
   if (seq == DDP_HIP_SEQ_CTRL_LO || seq == DDP_HIP_SEQ_CTRL_HI) ctx->box_dirty = true;
   HIP_TRY(hipSetDevice(ctx->device));
-  if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUX || seq == DDP_HIP_SEQ_FUU) { ctx->tensor_tops_zero = false; ctx->tensor_tops_sparse = false; ctx->fuu_zero = false; }
-  if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUU) {
-    const int rc_ = lin_materialize_fxx(ctx);
-    if (rc_ != DDP_HIP_OK) return rc_;
-    ctx->tensors_sym = false;
-  }
+  { const int rc_ = tensors_written_outside(ctx, seq); if (rc_ != DDP_HIP_OK) return rc_; }
   return fill_device(ctx, ctx->seq[seq].ptr, ctx->seq[seq].size * ctx->d.batch, value);
 }
 
@@ -601,11 +588,11 @@ extern "C" int ddp_hip_ctx_info(const ddp_hip_ctx* ctx, ddp_hip_info* out) {
   if (!ctx || !out) return DDP_HIP_E_ARG;
   const Dims& d = ctx->d;
   out->device = ctx->device;
-  out->lin_path = ctx->model_h.kind == DDP_HIP_MODEL_PENDULUM ? 0 : (ctx->lin_static ? 1 + ctx->lin_static : 1);
-  out->first_order = ctx->model_h.kind == DDP_HIP_MODEL_PENDULUM ? 0 : (ctx->model_h.first_order_fd ? 1 : 2);
+  out->lin_path = ctx->plan.lin_path;
+  out->first_order = ctx->plan.first_order;
   out->bwd_path = sweep_plan(ctx).fast ? 1 : 0;
   out->fwd_path = fwd_lat_supported(ctx) ? 1 : 0;
-  out->has_tensors = (ctx->flags & DDP_HIP_FLAG_NO_TENSORS) ? 0 : 1;
+  out->has_tensors = ctx->plan.has_tensors ? 1 : 0;
   int64_t bytes = 0;
   for (int s = 0; s < DDP_HIP_SEQ_COUNT; ++s)
     if (ctx->seq[s].ptr) bytes += 8 * ctx->seq[s].size * d.batch;

@@ -84,8 +84,84 @@ struct DevSwitches {
 struct SweepPlan {
   bool fast;       // the Talos-shape kernels K5 / K3 / K4' (bwd_v2.h); else the run-time-shaped pair
   bool sym_ok;     // ... which would read symmetric tensors by halves: the static stencil may leave the mirror images out
-  bool sym;        // ... and they are symmetric now (tensors_sym): K3 reads one of each pair of mirrored half-slabs
+  bool sym;        // ... and they are symmetric now (TensorState): K3 reads one of each pair of mirrored half-slabs
   int32_t half_mode;   // K3h (bwd_split.h: bwd_contract_half): 0 off, 1 the static stencil's tensors, 2 analytic mode 1
+};
+
+// Which kernels a context's linearisation runs and which workspaces they need: decided once, by lin_plan_decide (lin_plan.cpp, a
+// pure function of what ddp_hip_create was given), stored by lin_setup and read by everything else.
+enum class LinFirst : int32_t {
+  Base,            // f alone (lin_base_kernel): the pendulum's closed-form jacobians come with it
+  AnalyticSmall,   // one lane per (instance, t) (lin_first_analytic_small_kernel)
+  AnalyticWave,    // one wave per evaluation (lin_analytic.hip: stage 0)
+  AnalyticFF,      // free-flyer root (lin_analytic.hip: ana_ff_first_kernel)
+  FdStatic,        // forward differences on the static-topology kernels, from the base point's caches
+  FdGeneric,       // forward differences on the run-time tree (lin_first_kernel)
+};
+enum class LinSecond : int32_t {
+  None,            // tensor-free context
+  Zeros,           // mode 0
+  Mode2Static,     // the stencil on the static-topology kernels
+  Mode2Caches,     // the stencil on the run-time tree, from the q- / v-caches
+  Mode2Plain,      // the stencil on the run-time tree, every point a full evaluation
+  Mode1Small,      // forward differences of the analytic jacobians, one lane per direction (second_m1_kernel)
+  Mode1Wave,       // ... one wave per evaluation (lin_analytic.hip: stage 1)
+};
+enum class LinEq : int32_t {
+  None,            // no constraint rows
+  PerLane,         // small vector-space models with analytic jacobians: the whole chain in one lane (eq_first_kernel)
+  Analytic,        // large trees with analytic jacobians (lin_analytic.hip: ana_eq_kernel)
+  Chain,           // forward-differenced jacobians, and free-flyer models: eq_chain / look-ahead jacobians / eq_combine
+};
+enum class LinEqJac : int32_t { None, Fd, FfLookahead };   // Chain with K > 1: where f_x at the look-ahead states comes from
+enum class LinEqSecond : int32_t { None, Zeros, Mode2, Mode1Small, Mode1Wave };   // the constraint tensors: as LinSecond
+struct LinPlan {
+  int32_t refuse = 0;          // DDP_HIP_E_UNSUPPORTED: ddp_hip_create refuses the context (lin_setup returns it)
+  int32_t nj = 0;              // the NJ instantiation of lin.hip's kernels: 1 / 6 / 38 / 64
+  int32_t topo = 0;            // id of the compiled-in topology whose kernels run (lin_static.hip), 0: none
+  LinFirst first = LinFirst::Base;
+  LinSecond second = LinSecond::None;
+  LinEq eq = LinEq::None;
+  LinEqJac eq_jac = LinEqJac::None;
+  LinEqSecond eq_second = LinEqSecond::None;
+  bool eq_inline = false;      // Mode1Wave, config constraint: its tensors come out of the evaluation waves (no ana_eq_kernel, no slices)
+  bool accel_static = false;   // Mode1Wave: the perturbed points' accelerations come from the static first-order kernels (ana_A)
+  bool accel_with_u = false;   // ... along the u directions as well (the constraint chain differences along them)
+  bool m1_fused = false;       // Mode1Wave: the pass is issued by the LIN_EQ stage, together with the constraint tensors
+  int32_t ncfg = 0, nvcfg = 0; // q- / v-cache entries per (instance, t)
+  bool has_tensors = false;    // FXX / FUX / FUU are resident
+  bool skip_top = false;       // LinParams::skip_top
+  bool skip_qv_mirror = false; // LinParams::skip_qv_mirror
+  // the workspaces that exist (lin_setup, lin_analytic_setup allocate exactly these)
+  bool ws_lin = false, ws_qws = false, ws_qws2 = false;   // the caches; the static path's configuration-level workspace; its twin + stream
+  bool ws_ana_T = false, ws_ana_M = false, ws_ana_M0 = false, ws_ana_A = false, ws_ana_F = false;
+  bool ws_eq = false;
+  bool ana_sliced = false;     // lin_analytic.hip takes the model: ctx->ana_nbt is set
+  int64_t eq_fxk_off = 0, eq_c_off = 0, eq_words = 0;   // eq_ws: x_1..x_K | f_x(x_1..x_{K-1}) at eq_fxk_off | base jacobian at eq_c_off
+  int32_t lin_path = 0, first_order = 0;   // what ddp_hip_ctx_info reports
+};
+LinPlan lin_plan_decide(const DevModel& m, const Dims& d, uint32_t flags, const DevSwitches& sw, int topo_id, bool sweep_sym_ok);
+
+// What FXX / FUX / FUU hold, as far as a reader inside the library may rely on it.  The record changes
+// only through the four transitions declared below (lin.hip); sweep_plan reads it and nothing else about the tensors.
+enum class TensorOrigin : int32_t {
+  Unknown,     // never written, written from outside (upload / fill / device_ptr), or left by a linearisation that failed: no structure
+  Symmetric,   // this context's mode 2 on the run-time-tree kernels, or mode 0: f_xx and f_uu symmetric bit for bit
+  Stencil,     // the static mode-2 stencil's own: symmetric, and the configuration rows k < nv zeros but two entries per column
+  Analytic1,   // analytic mode 1's own (lin_analytic.hip): zero configuration rows, zero f_uu, not symmetric
+};
+struct TensorState {
+  TensorOrigin origin = TensorOrigin::Unknown;
+  // the static stencil left the mirror images f_xx(:, i, j), f_uu(:, i, j), i < j, out (LinParams::skip_qv_mirror).  Its own bit
+  // because it outlives the origin: an upload of FUX alone takes Stencil to Symmetric and leaves the images unwritten
+  bool mirror_pending = false;
+};
+
+// State of one linearisation call (lin.hip: ddp_hip_linearize_stages creates it, lin_analytic.hip reads and marks it)
+struct LinCall {
+  bool ana_A_fresh = false;    // ana_A was formed by stage 0 of this call
+  bool ana_M0_fresh = false;   // ana_M0 was written by stage 0 of this call
+  bool fuu_zero = false;       // F_UU holds exact zeros: analytic mode 1 left them (TensorOrigin::Analytic1 at entry) or has just written them
 };
 
 struct ProfSlot {
@@ -119,11 +195,8 @@ struct ddp_hip_ctx {
   BwdJob* jobs_d = nullptr;
   BwdJob* jobs_half_d = nullptr;  // K3h's job list (bwd_split.h: bwd_contract_half)
   int32_t njobs_half = 0;
-  bool tensor_tops_sparse = false; // the tensors' configuration rows are as the static mode-2 stencil leaves them: zeros but the two entries per column
+  TensorState tensors;            // what FXX / FUX / FUU hold
   BwdJob* jobs_sym_d = nullptr;   // K3's job list for symmetric tensors (bwd_split.h, job kind 2)
-  bool fxx_mirror_pending = false; // the static stencil left f_xx(:, q_i, v_c) out (lin.hip: lin_materialize_fxx forms it on demand)
-  bool tensor_tops_zero = false;   // rows k < nv of every column of FXX / FUX / FUU hold zeros (what LinParams::skip_top relies on)
-  bool tensors_sym = false;       // FXX / FUU hold what this context's own mode-2 (or tensor-free: zero) linearisation wrote: symmetric bit for bit
   int32_t njobs = 0;
   int32_t cbx = 0, cbu = 0;
   // the sweep as an instantiated hipGraph (600 launches per sweep otherwise pay the enqueue cost every time);
@@ -147,8 +220,7 @@ struct ddp_hip_ctx {
   // linearize workspace
   double* eq_ws = nullptr;     // constraint-chain workspace (large models)
   double* lin_ws = nullptr;
-  size_t lin_ws_bytes = 0;
-  int32_t lin_ncfg = 0, lin_nvcfg = 0;   // q- / v-cache entries per (instance, t)
+  LinPlan plan;                // what the linearisation runs (set by lin_setup)
   double* lin_qws = nullptr;   // configuration-level workspace of the static path, lin_qws_bt (instance, t) pairs at a time
   int64_t lin_qws_bt = 0;
   double* lin_qws2 = nullptr;  // second workspace + stream + events (DDP_HIP_CFG_FULL_ABA only): the two full-ABA kernels of consecutive slices overlap
@@ -157,13 +229,9 @@ struct ddp_hip_ctx {
   double* ana_T = nullptr;     // analytic-derivative workspace (lin_analytic.hip): T = [dtau/dq | dtau/dv] per evaluation of a slice
   double* ana_M = nullptr;     // ... and M / M^-1 per configuration of a slice
   double* ana_F = nullptr;     // ... and the v rows of f_x at the perturbed points (mode-1 constraint tensors)
-  bool ana_A_fresh = false;    // ana_A was formed by stage 0 of the linearisation call in progress
-  bool ana_M0_fresh = false;   // ana_M0 was written by stage 0 of the linearisation call in progress
-  bool fuu_zero = false;       // analytic mode 1: F_UU holds the exact zeros lin_analytic.hip left there (cleared by every other writer)
   double* ana_M0 = nullptr;    // [B T][nv][nv] M^-1 at the trajectory points (fused analytic path, mode 1)
-  double* ana_A = nullptr;     // [B T][2nv][nv] accelerations of the mode-1 perturbed points (static first-order kernels, level 6)
+  double* ana_A = nullptr;     // [B T][2nv][nv] accelerations of the mode-1 perturbed points (static first-order kernels, StaticLevel::AccelX)
   int64_t ana_nbt = 0;         // (instance, t) pairs per slice
-  int lin_static = 0;          // id of the compiled-in topology the model's tree matches (lin_static.hip), 0 = none
 
   // per-instance activity (ddp_hip_set_active): an inactive instance is frozen -- the sweeps skip it and swap_traj
   // keeps its trajectory (solve<M> returns an instance at its first optimum, ddp.hpp:799-800)
@@ -207,7 +275,9 @@ int fwd_setup(ddp_hip_ctx* ctx);
 bool fwd_lat_supported(const ddp_hip_ctx* ctx);   // the latency kernels of the forward sweep apply (tree, no constraints, Talos size)
 void fwd_teardown(ddp_hip_ctx* ctx);
 int lin_setup(ddp_hip_ctx* ctx);
-int lin_materialize_fxx(ddp_hip_ctx* ctx);   // FXX complete for readers outside the symmetric sweep (lin.hip)
+// the transitions of ctx->tensors (lin.hip); linearise's own two (about to write / has written the second order) are local to it
+int tensors_written_outside(ddp_hip_ctx* ctx, int seq);   // ddp_hip_device_ptr / upload / fill of `seq`: a no-op unless it is FXX / FUX / FUU
+int lin_materialize_fxx(ddp_hip_ctx* ctx);   // the mirror images formed: FXX / FUU complete for readers outside the symmetric sweep
 void lin_teardown(ddp_hip_ctx* ctx);
 
 // best-cost pick, device side (pick.hip): {cost, global index} of the local best / of G gathered pairs

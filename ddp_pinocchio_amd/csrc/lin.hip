@@ -893,39 +893,68 @@ LinParams make_params(ddp_hip_ctx* ctx) {
   p.fxx = S(DDP_HIP_SEQ_FXX); p.fux = S(DDP_HIP_SEQ_FUX); p.fuu = S(DDP_HIP_SEQ_FUU);
   p.eq_val = S(DDP_HIP_SEQ_EQ_VAL); p.eq_x = S(DDP_HIP_SEQ_EQ_X); p.eq_u = S(DDP_HIP_SEQ_EQ_U);
   p.eq_xx = S(DDP_HIP_SEQ_EQ_XX); p.eq_ux = S(DDP_HIP_SEQ_EQ_UX); p.eq_uu = S(DDP_HIP_SEQ_EQ_UU);
-  p.has_tensors = (ctx->flags & DDP_HIP_FLAG_NO_TENSORS) ? 0 : 1;
-  p.skip_top = (ctx->lin_static && ctx->model_h.fd_mode == 2 && !ctx->model_h.ff && !ctx->sw.fxx_full) ? 1 : 0;
-  // the mirror images are left out only for a sweep that never reads them (the mode-2 tensors written here are symmetric)
-  p.skip_qv_mirror = (ctx->lin_static && ctx->model_h.fd_mode == 2 && !ctx->sw.fxx_full && sweep_plan(ctx).sym_ok) ? 1 : 0;
+  const LinPlan& pl = ctx->plan;
+  p.has_tensors = pl.has_tensors ? 1 : 0;
+  p.skip_top = pl.skip_top ? 1 : 0;
+  p.skip_qv_mirror = pl.skip_qv_mirror ? 1 : 0;
   p.eq_xk = ctx->eq_ws;
-  if (p.eq_xk) {
-    const Dims& dd = ctx->d;
-    const int64_t K = ctx->model_h.eq_advance;
-    p.eq_fxk = p.eq_xk + dd.batch * dd.T * K * dd.nx;
-    p.eq_c = p.eq_fxk + dd.batch * dd.T * (K > 1 ? K - 1 : 0) * dd.n * dd.n;
-  }
-  p.qcache = reinterpret_cast<double*>(ctx->lin_ws);
-  p.ncfg = ctx->lin_ncfg; p.nvcfg = ctx->lin_nvcfg;
-  p.vcache = p.qcache ? p.qcache + ctx->d.batch * ctx->d.T * (int64_t)ctx->lin_ncfg * ctx->d.nv * rbd::QC_STRIDE : nullptr;
+  if (p.eq_xk) { p.eq_fxk = p.eq_xk + pl.eq_fxk_off; p.eq_c = p.eq_xk + pl.eq_c_off; }
+  p.qcache = ctx->lin_ws;
+  p.ncfg = pl.ncfg; p.nvcfg = pl.nvcfg;
+  p.vcache = p.qcache ? p.qcache + ctx->d.batch * ctx->d.T * (int64_t)pl.ncfg * ctx->d.nv * rbd::QC_STRIDE : nullptr;
   p.xref = S(DDP_HIP_SEQ_COST_XREF); p.wx = S(DDP_HIP_SEQ_COST_WX); p.uref = S(DDP_HIP_SEQ_COST_UREF); p.wu = S(DDP_HIP_SEQ_COST_WU);
   return p;
 }
 
 inline unsigned blocks_for(int64_t total) { return (unsigned)((total + LBS - 1) / LBS); }
 
+// the constraint tensors eq_xx, eq_ux, eq_uu, in the form the plan names
 template <int NJ>
-int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, uint32_t stages) {
+int eq_second_order(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t stages) {
   const Dims& d = ctx->d;
   const int64_t BT = d.batch * d.T;
   const int W = (int)(d.n + d.m);
   const int64_t P = (int64_t)W * (W - 1) / 2;
-  const int fd_mode = ctx->model_h.fd_mode;
-  const bool small = NJ <= 6;
-  // large trees with analytic first order: the constraint chain runs on the analytic jacobians (lin_analytic.hip:
-  // ana_eq_kernel), and in mode 1 its tensors come out of the same pass over the perturbed points as the dynamics' own
-  const bool ana_large = !small && !ctx->model_h.first_order_fd && ctx->model_h.kind == DDP_HIP_MODEL_TREE;
-  const bool eq_stage = (stages & DDP_HIP_LIN_EQ) && d.Etot > 0;
-  const bool m1_fused = ana_large && fd_mode == 1 && p.has_tensors && eq_stage;   // LIN_SECOND's mode-1 pass is issued by the LIN_EQ stage
+  switch (ctx->plan.eq_second) {
+    case LinEqSecond::None: break;
+    case LinEqSecond::Mode2:
+      hipLaunchKernelGGL((eq_second_m2_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p, 0);
+      hipLaunchKernelGGL((eq_second_m2_kernel<NJ>), dim3(blocks_for(BT * P)), dim3(LBS), 0, ctx->stream, p, 1);
+      break;
+    case LinEqSecond::Mode1Small:
+      if constexpr (NJ <= 6) hipLaunchKernelGGL((second_m1_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p, 1);
+      break;
+    case LinEqSecond::Mode1Wave: {
+      // (with LIN_SECOND among the stages this is the dynamics' own mode-1 pass as well: LinPlan::m1_fused)
+      const int fl = LIN_ANA_EQ | ((stages & DDP_HIP_LIN_SECOND) ? LIN_ANA_F : 0);
+      if (fl & LIN_ANA_F) prof_begin(ctx, DDP_HIP_K_LIN_SECOND);
+      const int rc_ = lin_analytic_launch(ctx, p, call, 1, fl);
+      if (fl & LIN_ANA_F) prof_end(ctx, DDP_HIP_K_LIN_SECOND);
+      if (rc_ != DDP_HIP_OK) return rc_;
+      break;
+    }
+    case LinEqSecond::Zeros:
+      HIP_TRY(hipMemsetAsync(p.eq_xx, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_EQ_XX].size * d.batch), ctx->stream));
+      HIP_TRY(hipMemsetAsync(p.eq_ux, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_EQ_UX].size * d.batch), ctx->stream));
+      HIP_TRY(hipMemsetAsync(p.eq_uu, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_EQ_UU].size * d.batch), ctx->stream));
+      break;
+  }
+  return DDP_HIP_OK;
+}
+
+// One linearisation: the stages asked for, each on the leg ctx->plan names (the legs that need the one-lane kernels of small
+// models are instantiated for NJ <= 6 only; the plan selects them for no other NJ)
+template <int NJ>
+int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t stages) {
+  const LinPlan& pl = ctx->plan;
+  const Dims& d = ctx->d;
+  const int64_t BT = d.batch * d.T;
+  const int W = (int)(d.n + d.m);
+  const int nv = (int)d.nv;
+  [[maybe_unused]] constexpr bool small = NJ <= 6;
+  const bool second_stage = (stages & DDP_HIP_LIN_SECOND) && pl.second != LinSecond::None;
+  const bool eq_stage = (stages & DDP_HIP_LIN_EQ) && pl.eq != LinEq::None;
+  const bool m1_fused = pl.m1_fused && eq_stage;   // LIN_SECOND's mode-1 pass is issued by the LIN_EQ stage
   if (stages & DDP_HIP_LIN_COST) {
     if (ctx->flags & DDP_HIP_FLAG_TRACKING_COST)
       hipLaunchKernelGGL(lin_track_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p);
@@ -933,14 +962,13 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, uint32_t stages) {
     const FrameCostDev fc = frame_cost_dev(ctx);
     if (fc.target) hipLaunchKernelGGL(lin_frame_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, fc);
   }
-  // static-topology path: the q- / v-caches of the mode-2 stencil also serve the first order (base configuration and
-  // base (q, v)), so they are built ahead of whichever stage comes first
+  // the q- / v-caches of the mode-2 stencil also serve the first order (base configuration and base (q, v)), so they are built
+  // ahead of whichever stage comes first
   bool caches_built = false;
   int static_rc = DDP_HIP_OK;
   auto build_caches = [&]() {
-    if (caches_built || !p.qcache) return;
-    const int nv = (int)d.nv;
-    if (ctx->lin_static) { const int rc_ = lin_static_launch(ctx, p, 5); if (rc_ != DDP_HIP_OK) static_rc = rc_; }
+    if (caches_built) return;
+    if (pl.topo) { const int rc_ = lin_static_launch(ctx, p, StaticLevel::Caches); if (rc_ != DDP_HIP_OK) static_rc = rc_; }
     else {
       hipLaunchKernelGGL((lin_qcache_kernel<NJ>), dim3(blocks_for(BT * (nv + 1))), dim3(LBS), 0, ctx->stream, p);
       hipLaunchKernelGGL((lin_vcache_kernel<NJ>), dim3(blocks_for(BT * (2 * nv + 1))), dim3(LBS), 0, ctx->stream, p);
@@ -950,152 +978,146 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, uint32_t stages) {
   if (stages & DDP_HIP_LIN_FIRST) {
     prof_begin(ctx, DDP_HIP_K_LIN_FIRST);
     hipLaunchKernelGGL((lin_base_kernel<NJ>), dim3(blocks_for(BT)), dim3(LBS), 0, ctx->stream, p);
-    if (!ctx->model_h.first_order_fd && ctx->model_h.kind == DDP_HIP_MODEL_TREE) {
-      if constexpr (small) hipLaunchKernelGGL((lin_first_analytic_small_kernel<NJ>), dim3(blocks_for(BT)), dim3(LBS), 0, ctx->stream, p);
-      else {
-        const bool m1_next = fd_mode == 1 && p.has_tensors && (stages & DDP_HIP_LIN_SECOND);
-        const int rc_ = lin_analytic_launch(ctx, p, 0, LIN_ANA_F | (m1_next ? LIN_ANA_ACCEL : 0) | (m1_next && eq_stage ? LIN_ANA_EQ << 4 : 0));
+    switch (pl.first) {
+      case LinFirst::Base: break;
+      case LinFirst::AnalyticSmall:
+        if constexpr (small) hipLaunchKernelGGL((lin_first_analytic_small_kernel<NJ>), dim3(blocks_for(BT)), dim3(LBS), 0, ctx->stream, p);
+        break;
+      case LinFirst::AnalyticWave:
+      case LinFirst::AnalyticFF: {
+        const bool m1_next = pl.second == LinSecond::Mode1Wave && second_stage;   // its accelerations are formed now
+        const int rc_ = lin_analytic_launch(ctx, p, call, 0, LIN_ANA_F | (m1_next ? LIN_ANA_ACCEL : 0) | (m1_next && eq_stage ? LIN_ANA_EQ << 4 : 0));
         if (rc_ != DDP_HIP_OK) return rc_;
+        break;
       }
-    } else if (ctx->model_h.first_order_fd) {
-      if (ctx->lin_static && p.qcache) { build_caches(); { const int rc_ = lin_static_launch(ctx, p, 0); if (rc_ != DDP_HIP_OK) return rc_; } }
-      else hipLaunchKernelGGL((lin_first_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p);
+      case LinFirst::FdStatic: {
+        build_caches();
+        const int rc_ = lin_static_launch(ctx, p, StaticLevel::FirstOrder);
+        if (rc_ != DDP_HIP_OK) return rc_;
+        break;
+      }
+      case LinFirst::FdGeneric:
+        hipLaunchKernelGGL((lin_first_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p);
+        break;
     }
     prof_end(ctx, DDP_HIP_K_LIN_FIRST);
   }
-  if ((stages & DDP_HIP_LIN_SECOND) && p.has_tensors) {
+  if (second_stage) {
+    const int64_t P = (int64_t)W * (W - 1) / 2, TRI = (int64_t)nv * (nv - 1) / 2, Pv = (int64_t)nv * nv + TRI, Pu = 2 * (int64_t)nv * nv + TRI;
     prof_begin(ctx, DDP_HIP_K_LIN_SECOND);
-    if (fd_mode == 2) {
-      if (p.qcache && p.ncfg > 1) {
-        const int nv = (int)d.nv;
-        const int64_t TRI = (int64_t)nv * (nv - 1) / 2, Pv = (int64_t)nv * nv + TRI, Pu = 2 * (int64_t)nv * nv + TRI;
+    switch (pl.second) {
+      case LinSecond::None: break;
+      case LinSecond::Mode2Static:
         build_caches();
-        if (ctx->lin_static) { const int rc_ = lin_static_launch(ctx, p, 4); if (rc_ != DDP_HIP_OK) return rc_; }
-        else hipLaunchKernelGGL((lin_diag_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p);
-        // torque level first: on the static path its row kernel also forms the diagonal entries of the q and v directions
-        if (ctx->lin_static) { const int rc_ = lin_static_launch(ctx, p, 3); if (rc_ != DDP_HIP_OK) return rc_; }
-        else hipLaunchKernelGGL((lin_offdiag_kernel<NJ, 3>), dim3(blocks_for(BT * Pu)), dim3(LBS), 0, ctx->stream, p);
-        if (ctx->lin_static) { const int rc_ = lin_static_launch(ctx, p, 2); if (rc_ != DDP_HIP_OK) return rc_; }
-        else hipLaunchKernelGGL((lin_offdiag_kernel<NJ, 2>), dim3(blocks_for(BT * Pv)), dim3(LBS), 0, ctx->stream, p);
-        if (ctx->lin_static) { const int rc_ = lin_static_launch(ctx, p, 1); if (rc_ != DDP_HIP_OK) return rc_; }
-        else hipLaunchKernelGGL((lin_offdiag_kernel<NJ, 1>), dim3(blocks_for(BT * TRI)), dim3(LBS), 0, ctx->stream, p);
-      } else {
+        // torque level ahead of the other two: its row kernel also forms the diagonal entries of the q and v directions
+        for (StaticLevel level : {StaticLevel::UDiagonal, StaticLevel::Torque, StaticLevel::Velocity, StaticLevel::Configuration}) {
+          const int rc_ = lin_static_launch(ctx, p, level);
+          if (rc_ != DDP_HIP_OK) return rc_;
+        }
+        break;
+      case LinSecond::Mode2Caches:
+        build_caches();
+        hipLaunchKernelGGL((lin_diag_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p);
+        hipLaunchKernelGGL((lin_offdiag_kernel<NJ, 3>), dim3(blocks_for(BT * Pu)), dim3(LBS), 0, ctx->stream, p);
+        hipLaunchKernelGGL((lin_offdiag_kernel<NJ, 2>), dim3(blocks_for(BT * Pv)), dim3(LBS), 0, ctx->stream, p);
+        hipLaunchKernelGGL((lin_offdiag_kernel<NJ, 1>), dim3(blocks_for(BT * TRI)), dim3(LBS), 0, ctx->stream, p);
+        break;
+      case LinSecond::Mode2Plain:
         hipLaunchKernelGGL((lin_diag_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p);
         hipLaunchKernelGGL((lin_offdiag_kernel<NJ, 0>), dim3(blocks_for(BT * P)), dim3(LBS), 0, ctx->stream, p);
-      }
-    } else if (fd_mode == 1) {
-      if (ctx->model_h.first_order_fd) return DDP_HIP_E_UNSUPPORTED;  // forward differences of FD jacobians are numerically void (refused at ddp_hip_create already)
-      if constexpr (small) hipLaunchKernelGGL((second_m1_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p, 0);
-      else if (!m1_fused) { const int rc_ = lin_analytic_launch(ctx, p, 1, LIN_ANA_F); if (rc_ != DDP_HIP_OK) return rc_; }
-    } else {
-      // fd_mode 0: Gauss-Newton variant, tensors are zero
-      HIP_TRY(hipMemsetAsync(p.fxx, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_FXX].size * d.batch), ctx->stream));
-      HIP_TRY(hipMemsetAsync(p.fux, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_FUX].size * d.batch), ctx->stream));
-      HIP_TRY(hipMemsetAsync(p.fuu, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_FUU].size * d.batch), ctx->stream));
+        break;
+      case LinSecond::Mode1Small:
+        if constexpr (small) hipLaunchKernelGGL((second_m1_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p, 0);
+        break;
+      case LinSecond::Mode1Wave:
+        if (!m1_fused) { const int rc_ = lin_analytic_launch(ctx, p, call, 1, LIN_ANA_F); if (rc_ != DDP_HIP_OK) return rc_; }
+        break;
+      case LinSecond::Zeros:   // the Gauss-Newton variant
+        HIP_TRY(hipMemsetAsync(p.fxx, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_FXX].size * d.batch), ctx->stream));
+        HIP_TRY(hipMemsetAsync(p.fux, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_FUX].size * d.batch), ctx->stream));
+        HIP_TRY(hipMemsetAsync(p.fuu, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_FUU].size * d.batch), ctx->stream));
+        break;
     }
     prof_end(ctx, DDP_HIP_K_LIN_SECOND);
   }
   if (eq_stage) {
-    // small vector-space models with analytic jacobians (the pendulum, UR5-like arms in the drivers' mode) chain per lane; every
-    // model with forward-differenced jacobians takes the three-kernel chain (round 3: the per-lane form differenced 2 x 18 full
-    // dynamics evaluations and multiplied 12 x 12 matrices in ONE lane per (instance, t): 3.2 ms of latency at any size)
-    bool chained = false;
-    if constexpr (small) {
-      if (!p.eq_xk) {
-        chained = true;
-        hipLaunchKernelGGL((eq_first_kernel<NJ>), dim3(blocks_for(BT)), dim3(LBS), 0, ctx->stream, p);
-        if (p.has_tensors) {
-          if (fd_mode == 2) {
-            hipLaunchKernelGGL((eq_second_m2_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p, 0);
-            hipLaunchKernelGGL((eq_second_m2_kernel<NJ>), dim3(blocks_for(BT * P)), dim3(LBS), 0, ctx->stream, p, 1);
-          } else if (fd_mode == 1) {
-            hipLaunchKernelGGL((second_m1_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p, 1);
-          } else {
-            HIP_TRY(hipMemsetAsync(p.eq_xx, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_EQ_XX].size * d.batch), ctx->stream));
-            HIP_TRY(hipMemsetAsync(p.eq_ux, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_EQ_UX].size * d.batch), ctx->stream));
-            HIP_TRY(hipMemsetAsync(p.eq_uu, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_EQ_UU].size * d.batch), ctx->stream));
-          }
-        }
+    switch (pl.eq) {
+      case LinEq::None: break;
+      case LinEq::PerLane:
+        if constexpr (small) hipLaunchKernelGGL((eq_first_kernel<NJ>), dim3(blocks_for(BT)), dim3(LBS), 0, ctx->stream, p);
+        break;
+      case LinEq::Analytic: {   // base point from the resident f_x, f_u
+        const int rc_ = lin_analytic_launch(ctx, p, call, 0, LIN_ANA_EQ);
+        if (rc_ != DDP_HIP_OK) return rc_;
+        break;
+      }
+      case LinEq::Chain: {
+        // chain rule as three kernels (round 3: the per-lane form differenced 2 x 18 full dynamics evaluations and multiplied
+        // 12 x 12 matrices in ONE lane per (instance, t): 3.2 ms of latency at any size)
+        const int K = ctx->model_h.eq_advance;
+        if (K < 1) return DDP_HIP_E_UNSUPPORTED;
+        hipLaunchKernelGGL((eq_chain_kernel<NJ>), dim3(blocks_for(BT)), dim3(LBS), 0, ctx->stream, p);
+        if (pl.eq_jac == LinEqJac::Fd) hipLaunchKernelGGL((eq_fdjac_kernel<NJ>), dim3(blocks_for(BT * (K - 1) * d.n)), dim3(LBS), 0, ctx->stream, p);
+        else if (pl.eq_jac == LinEqJac::FfLookahead) { const int rc_ = lin_analytic_ff_lookahead(ctx, p); if (rc_ != DDP_HIP_OK) return rc_; }
+        hipLaunchKernelGGL(eq_combine_kernel, dim3((unsigned)BT), dim3(256), sizeof(double) * (size_t)(2 * d.emax * d.n), ctx->stream, p);
+        break;
       }
     }
-    if (chained) {
-    } else if (ana_large && !ctx->model_h.ff) {
-      // analytic jacobians: base point from the resident f_x, f_u, then the tensors
-      { const int rc_ = lin_analytic_launch(ctx, p, 0, LIN_ANA_EQ); if (rc_ != DDP_HIP_OK) return rc_; }
-      if (p.has_tensors) {
-        if (fd_mode == 2) {
-          hipLaunchKernelGGL((eq_second_m2_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p, 0);
-          hipLaunchKernelGGL((eq_second_m2_kernel<NJ>), dim3(blocks_for(BT * P)), dim3(LBS), 0, ctx->stream, p, 1);
-        } else if (fd_mode == 1) {
-          const int fl = LIN_ANA_EQ | ((stages & DDP_HIP_LIN_SECOND) ? LIN_ANA_F : 0);
-          if (fl & LIN_ANA_F) prof_begin(ctx, DDP_HIP_K_LIN_SECOND);
-          const int rc_ = lin_analytic_launch(ctx, p, 1, fl);
-          if (fl & LIN_ANA_F) prof_end(ctx, DDP_HIP_K_LIN_SECOND);
-          if (rc_ != DDP_HIP_OK) return rc_;
-        } else {
-          HIP_TRY(hipMemsetAsync(p.eq_xx, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_EQ_XX].size * d.batch), ctx->stream));
-          HIP_TRY(hipMemsetAsync(p.eq_ux, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_EQ_UX].size * d.batch), ctx->stream));
-          HIP_TRY(hipMemsetAsync(p.eq_uu, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_EQ_UU].size * d.batch), ctx->stream));
-        }
-      }
-    } else {
-      // large models with forward-differenced jacobians, and free-flyer models with analytic ones (their jacobians at the
-      // look-ahead states from lin_analytic.hip): chain rule as three kernels; mode-2 second order reuses the per-point kernel
-      if (!p.eq_xk) return DDP_HIP_E_UNSUPPORTED;
-      const int K = ctx->model_h.eq_advance;
-      if (K < 1) return DDP_HIP_E_UNSUPPORTED;
-      hipLaunchKernelGGL((eq_chain_kernel<NJ>), dim3(blocks_for(BT)), dim3(LBS), 0, ctx->stream, p);
-      if (K > 1) {
-        if (ctx->model_h.first_order_fd) hipLaunchKernelGGL((eq_fdjac_kernel<NJ>), dim3(blocks_for(BT * (K - 1) * d.n)), dim3(LBS), 0, ctx->stream, p);
-        else { const int rc_ = lin_analytic_ff_lookahead(ctx, p); if (rc_ != DDP_HIP_OK) return rc_; }
-      }
-      hipLaunchKernelGGL(eq_combine_kernel, dim3((unsigned)BT), dim3(256), sizeof(double) * (size_t)(2 * d.emax * d.n), ctx->stream, p);
-      if (p.has_tensors) {
-        if (fd_mode == 2) {
-          hipLaunchKernelGGL((eq_second_m2_kernel<NJ>), dim3(blocks_for(BT * W)), dim3(LBS), 0, ctx->stream, p, 0);
-          hipLaunchKernelGGL((eq_second_m2_kernel<NJ>), dim3(blocks_for(BT * P)), dim3(LBS), 0, ctx->stream, p, 1);
-        } else if (fd_mode == 1) {
-          return DDP_HIP_E_UNSUPPORTED;   // forward differences of FD jacobians: refused at ddp_hip_create
-        } else {
-          HIP_TRY(hipMemsetAsync(p.eq_xx, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_EQ_XX].size * d.batch), ctx->stream));
-          HIP_TRY(hipMemsetAsync(p.eq_ux, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_EQ_UX].size * d.batch), ctx->stream));
-          HIP_TRY(hipMemsetAsync(p.eq_uu, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_EQ_UU].size * d.batch), ctx->stream));
-        }
-      }
-    }
+    const int rc_ = eq_second_order<NJ>(ctx, p, call, stages);
+    if (rc_ != DDP_HIP_OK) return rc_;
   }
   HIP_TRY(hipGetLastError());
   return static_rc;
 }
 
+// ---- ctx->tensors: linearise's own two transitions (the other two follow ddp_hip_linearize_stages) ---------------------------
+// Linearise is about to write the second order.  The record drops to Unknown until tensors_end_second: a call that returns an
+// error in between leaves it there.  What the previous origin spares this call is decided first: the configuration rows the
+// static stencil leaves alone must hold zeros (once per context, and again after somebody else has written to the tensors), and
+// analytic mode 1 zeroes f_uu unless its own zeros are still there (lin_analytic.hip: launch_t, where that memset keeps its place)
+int tensors_begin_second(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call) {
+  const TensorOrigin was = ctx->tensors.origin;
+  ctx->tensors.origin = TensorOrigin::Unknown;
+  call.fuu_zero = was == TensorOrigin::Analytic1;
+  if (p.skip_top && was != TensorOrigin::Stencil) {
+    const int64_t BT = ctx->d.batch * ctx->d.T, n = ctx->d.n, m = ctx->d.m;
+    const int nv = (int)ctx->d.nv;
+    hipLaunchKernelGGL(tensor_zero_top_kernel, dim3(8192), dim3(256), 0, ctx->stream, p.fxx, BT * n * n, (int)n, nv);
+    hipLaunchKernelGGL(tensor_zero_top_kernel, dim3(8192), dim3(256), 0, ctx->stream, p.fux, BT * m * n, (int)n, nv);
+    hipLaunchKernelGGL(tensor_zero_top_kernel, dim3(8192), dim3(256), 0, ctx->stream, p.fuu, BT * m * m, (int)n, nv);
+    HIP_TRY(hipGetLastError());
+  }
+  return DDP_HIP_OK;
+}
+
+// Linearise has written the second order.  Mode 2 writes one value to both (i, j, k) and (i, k, j) (problem.hpp:283-292), mode 0
+// leaves zeros: f_xx is symmetric bit for bit; mode 1's forward differences of jacobians are not.  (The run-time-tree kernels and
+// mode 0 leave the stencil's zero rows as well -- a property of the values, not of who writes them -- but only the static mode-2
+// path has been held to it bit for bit: tests/test_round3_boundary.py.)
+void tensors_end_second(ddp_hip_ctx* ctx, const LinParams& p, const LinCall& call) {
+  TensorState& t = ctx->tensors;
+  if (ctx->model_h.fd_mode == 1) t.origin = call.fuu_zero ? TensorOrigin::Analytic1 : TensorOrigin::Unknown;   // (small models' mode 1: no structure kept)
+  else t.origin = p.skip_top ? TensorOrigin::Stencil : TensorOrigin::Symmetric;
+  t.mirror_pending = p.skip_qv_mirror != 0;
+}
+
 }  // namespace
 
 int lin_setup(ddp_hip_ctx* ctx) {
-  // q-part cache of the mode-2 stencil (tree models with resident tensors only)
-  const bool tree = ctx->model_h.kind == DDP_HIP_MODEL_TREE;
-  const bool tensors = ctx->model_h.fd_mode == 2 && !(ctx->flags & DDP_HIP_FLAG_NO_TENSORS);
-  const bool want = tree && tensors && !ctx->model_h.ff && !ctx->sw.no_qcache;   // the caches index q by joint: 1-DoF trees
-  const int topo = (tree && !ctx->sw.no_static) ? lin_static_supported(ctx->model_h) : 0;
   const Dims& d = ctx->d;
-  if (want) { ctx->lin_ncfg = (int32_t)d.nv + 1; ctx->lin_nvcfg = 2 * (int32_t)d.nv + 1; }
-  else if (topo && ctx->model_h.first_order_fd) { ctx->lin_ncfg = 1; ctx->lin_nvcfg = 1; }   // first order only: base q, base (q, v)
-  else if (topo && tree && !ctx->model_h.ff && d.nv > 6 && ctx->model_h.fd_mode == 1 && !(ctx->flags & DDP_HIP_FLAG_NO_TENSORS) &&
-           !ctx->sw.ana_own_aba) {
-    // analytic mode 1: the accelerations of its 2 nv perturbed points come from the static first-order kernels (lin_analytic.hip)
-    ctx->lin_ncfg = 1; ctx->lin_nvcfg = 1;
-  }
-  if (ctx->lin_ncfg) {
-    ctx->lin_ws_bytes = sizeof(double) * (size_t)(d.batch * d.T * ((int64_t)ctx->lin_ncfg * d.nv * rbd::QC_STRIDE + (int64_t)ctx->lin_nvcfg * d.nv * rbd::VC_STRIDE));
-    HIP_TRY(hipMalloc(&ctx->lin_ws, ctx->lin_ws_bytes));
-    ctx->lin_static = topo;
-  }
-  if (ctx->lin_static) {
-    const int64_t BT = ctx->d.batch * ctx->d.T;
+  const int topo_id = ctx->model_h.kind == DDP_HIP_MODEL_TREE ? lin_static_supported(ctx->model_h) : 0;
+  ctx->plan = lin_plan_decide(ctx->model_h, d, ctx->flags, ctx->sw, topo_id, sweep_plan(ctx).sym_ok);
+  const LinPlan& pl = ctx->plan;
+  if (pl.refuse) return pl.refuse;
+  if (pl.ws_lin)
+    HIP_TRY(hipMalloc(&ctx->lin_ws, sizeof(double) * (size_t)(d.batch * d.T * ((int64_t)pl.ncfg * d.nv * rbd::QC_STRIDE + (int64_t)pl.nvcfg * d.nv * rbd::VC_STRIDE))));
+  if (pl.ws_qws) {
+    const int64_t BT = d.batch * d.T;
     int64_t slice = 1024;
     if (ctx->sw.qws_bt) slice = ctx->sw.qws_bt;   // tuning knob
     ctx->lin_qws_bt = BT < slice ? BT : slice;
     HIP_TRY(hipMalloc(&ctx->lin_qws, sizeof(double) * (size_t)(ctx->lin_qws_bt * lin_static_ws_per_bt(ctx->model_h))));
-    if (ctx->lin_ncfg > 1 && ctx->sw.cfg_full_aba) {     // the full-ABA configuration level runs slice-pipelined on two streams
+    if (pl.ws_qws2) {     // the full-ABA configuration level runs slice-pipelined on two streams
       HIP_TRY(hipMalloc(&ctx->lin_qws2, sizeof(double) * (size_t)(ctx->lin_qws_bt * lin_static_ws_per_bt(ctx->model_h))));
       HIP_TRY(hipStreamCreateWithFlags(&ctx->lin_stream2, hipStreamNonBlocking));
       for (int k = 0; k < 2; ++k) {
@@ -1104,21 +1126,8 @@ int lin_setup(ddp_hip_ctx* ctx) {
       }
     }
   }
-  {
-    // analytic first order on large trees: its own kernels and workspace (incl. the constraint chain on the analytic
-    // jacobians, lin_analytic.hip: ana_eq_kernel).  Mode 1 on forward-differenced jacobians is numerically void -- eps_mach /
-    // sqrt(eps_mach)^2 = O(1) noise -- and the reference cannot express it (its first order is always analytic): refused here
-    if (ctx->model_h.fd_mode == 1 && ctx->model_h.first_order_fd && !(ctx->flags & DDP_HIP_FLAG_NO_TENSORS)) return DDP_HIP_E_UNSUPPORTED;
-    const int rc_ = lin_analytic_setup(ctx);
-    if (rc_ != DDP_HIP_OK) return rc_;
-  }
-  // look-ahead states / jacobians of the constraint chain on large models
-  if (ctx->d.Etot > 0 && tree && (ctx->model_h.first_order_fd || ctx->model_h.ff)) {
-    const Dims& d = ctx->d;
-    const int64_t K = ctx->model_h.eq_advance;
-    const size_t words = (size_t)(d.batch * d.T * (K * d.nx + (K > 1 ? K - 1 : 0) * d.n * d.n + d.emax * d.n));
-    HIP_TRY(hipMalloc(&ctx->eq_ws, sizeof(double) * words));
-  }
+  { const int rc_ = lin_analytic_setup(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
+  if (pl.ws_eq) HIP_TRY(hipMalloc(&ctx->eq_ws, sizeof(double) * (size_t)pl.eq_words));   // look-ahead states / jacobians of the constraint chain
   return DDP_HIP_OK;
 }
 void lin_teardown(ddp_hip_ctx* ctx) {
@@ -1138,42 +1147,43 @@ extern "C" int ddp_hip_linearize_stages(ddp_hip_ctx* ctx, uint32_t stages) {
   if (!ctx) return DDP_HIP_E_ARG;
   HIP_TRY(hipSetDevice(ctx->device));
   LinParams p = make_params(ctx);
+  LinCall call;
+  const bool second = (stages & DDP_HIP_LIN_SECOND) && p.has_tensors;
+  if (second) { const int rc_ = tensors_begin_second(ctx, p, call); if (rc_ != DDP_HIP_OK) return rc_; }
   int rc;
-  const int nv = (int)ctx->d.nv;
-  if ((stages & DDP_HIP_LIN_SECOND) && p.has_tensors && p.skip_top && !ctx->tensor_tops_zero) {
-    // the configuration rows the static stencil leaves alone must hold zeros: once per context, and again after somebody
-    // else has written to the tensors (upload / fill / device_ptr)
-    const int64_t BT = ctx->d.batch * ctx->d.T, n = ctx->d.n, m = ctx->d.m;
-    hipLaunchKernelGGL(tensor_zero_top_kernel, dim3(8192), dim3(256), 0, ctx->stream, p.fxx, BT * n * n, (int)n, nv);
-    hipLaunchKernelGGL(tensor_zero_top_kernel, dim3(8192), dim3(256), 0, ctx->stream, p.fux, BT * m * n, (int)n, nv);
-    hipLaunchKernelGGL(tensor_zero_top_kernel, dim3(8192), dim3(256), 0, ctx->stream, p.fuu, BT * m * m, (int)n, nv);
-    HIP_TRY(hipGetLastError());
-    ctx->tensor_tops_zero = true;
+  switch (ctx->plan.nj) {
+    case 1: rc = run_linearize<1>(ctx, p, call, stages); break;
+    case 6: rc = run_linearize<6>(ctx, p, call, stages); break;
+    case 38: rc = run_linearize<38>(ctx, p, call, stages); break;
+    default: rc = run_linearize<64>(ctx, p, call, stages); break;
   }
-  if (nv <= 1) rc = run_linearize<1>(ctx, p, stages);
-  else if (nv <= 6 && !ctx->model_h.ff) rc = run_linearize<6>(ctx, p, stages);   // (the one-lane constraint chain of small models is vector-space only)
-  else if (nv <= 38) rc = run_linearize<38>(ctx, p, stages);
-  else rc = run_linearize<64>(ctx, p, stages);
-  ctx->ana_M0_fresh = false;
-  ctx->ana_A_fresh = false;
   if (rc != DDP_HIP_OK) return rc;
   END_SYNC(ctx);
-  // mode 2 writes one value to both (i, j, k) and (i, k, j) (problem.hpp:283-292), mode 0 leaves zeros: f_xx is symmetric bit
-  // for bit and the backward sweep reads one of each pair of mirrored half-slabs (bwd_split.h); mode 1's forward differences
-  // of jacobians are not
-  if ((stages & DDP_HIP_LIN_SECOND) && p.has_tensors) {
-    ctx->tensors_sym = ctx->model_h.fd_mode == 2 || ctx->model_h.fd_mode == 0;
-    ctx->fxx_mirror_pending = p.skip_qv_mirror != 0;
-    // (the run-time-tree kernels and mode 0 leave the same structure -- it is a property of the stencil's values, not of who
-    // writes them -- but only the static mode-2 path has been held to it bit for bit: tests/test_round3_boundary.py)
-    ctx->tensor_tops_sparse = p.skip_top != 0;
-  }
+  if (second) tensors_end_second(ctx, p, call);
   return DDP_HIP_OK;
 }
 
-// FXX complete for a reader that does not know about the skipped block (download, device_ptr, the run-time-shaped sweep)
+// ---- the other two transitions of ctx->tensors ------------------------------------------------------------------------------
+int tensors_written_outside(ddp_hip_ctx* ctx, int seq) {
+  if (seq != DDP_HIP_SEQ_FXX && seq != DDP_HIP_SEQ_FUX && seq != DDP_HIP_SEQ_FUU) return DDP_HIP_OK;
+  TensorState& t = ctx->tensors;
+  if (seq == DDP_HIP_SEQ_FUX) {
+    // f_ux carries no symmetry: f_xx / f_uu stay as symmetric as they were (and as incomplete), the zero rows are gone
+    t.origin = (t.origin == TensorOrigin::Symmetric || t.origin == TensorOrigin::Stencil) ? TensorOrigin::Symmetric : TensorOrigin::Unknown;
+    return DDP_HIP_OK;
+  }
+  // what the caller does not overwrite (other instances, the other tensor) stays whole; no symmetry assumed from here on:
+  // K3 reads every half-slab again (bwd_split.h)
+  const int rc_ = lin_materialize_fxx(ctx);
+  if (rc_ != DDP_HIP_OK) return rc_;
+  t.origin = TensorOrigin::Unknown;
+  return DDP_HIP_OK;
+}
+
+// the mirror images materialised: FXX / FUU complete for a reader that does not know about the skipped block (download,
+// device_ptr, the run-time-shaped sweep)
 int lin_materialize_fxx(ddp_hip_ctx* ctx) {
-  if (!ctx->fxx_mirror_pending) return DDP_HIP_OK;
+  if (!ctx->tensors.mirror_pending) return DDP_HIP_OK;
   double* fxx = ctx->seq[DDP_HIP_SEQ_FXX].ptr;
   double* fuu = ctx->seq[DDP_HIP_SEQ_FUU].ptr;
   if (fxx && fuu) {
@@ -1183,7 +1193,7 @@ int lin_materialize_fxx(ddp_hip_ctx* ctx) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
   }
-  ctx->fxx_mirror_pending = false;
+  ctx->tensors.mirror_pending = false;
   return DDP_HIP_OK;
 }
 

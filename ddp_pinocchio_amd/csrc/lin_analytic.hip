@@ -52,7 +52,7 @@ struct AnaParams {
   int32_t pad3_;
   int32_t eq_no_aba;   // ana_eq_kernel: no evaluation of this launch runs forward dynamics (stage 1 with `accel`): no ABA state in LDS
   const double* accel;   // stage 1: [pair][3 nv: q, v, u directions][nv] accelerations of the perturbed points, formed by the static first-order kernels
-                         // (lin_static.hip, level 6) -- or null: every evaluation runs its own forward dynamics
+                         // (lin_static.hip, StaticLevel::AccelX) -- or null: every evaluation runs its own forward dynamics
 };
 
 // ---- LDS layout of ana_eval_kernel (doubles) -----------------------------------------------------------------------------
@@ -1145,8 +1145,9 @@ size_t eq_lds_bytes(const Dims& d, bool no_aba = false) { return sizeof(double) 
 // flags: ANA_F the dynamics' own outputs (stage 0: f_x, f_u; stage 1: f_xx, f_ux, f_uu), ANA_EQ the constraint chain's
 // (stage 0: eq_val, eq_x, eq_u from the resident f_x, f_u; stage 1: eq_xx, eq_ux, eq_uu)
 template <int NJ>
-int launch_t(ddp_hip_ctx* ctx, const LinParams& p, int stage, int flags) {
+int launch_t(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, int stage, int flags) {
   const Dims& d = ctx->d;
+  const LinPlan& pl = ctx->plan;
   const int64_t BT = d.batch * d.T;
   const int N = (int)d.nv;
   const size_t lds = sizeof(double) * (size_t)AnaLds<NJ>::TOTAL;
@@ -1159,25 +1160,24 @@ int launch_t(ddp_hip_ctx* ctx, const LinParams& p, int stage, int flags) {
   ap.stage = stage;
   ap.write_f = do_f ? 1 : 0;
   ap.Fws = (stage == 1 && do_eq) ? ctx->ana_F : nullptr;
-  if (stage == 1 && do_eq && !ctx->ana_F) return DDP_HIP_E_UNSUPPORTED;
-  if (stage == 1 && do_f && !ctx->fuu_zero) {
-    // f_uu is exactly zero (see the header of this file); it stays so until someone else writes the sequence (ctx.hip clears the flag)
+  if (stage == 1 && do_f && !call.fuu_zero) {
+    // f_uu is exactly zero (see the header of this file); it stays so until someone else writes the sequence (TensorOrigin::Analytic1)
     HIP_TRY(hipMemsetAsync(p.fuu, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_FUU].size * d.batch), ctx->stream));
-    ctx->fuu_zero = true;
+    call.fuu_zero = true;
   }
   const bool accel_now = stage == 0 && (flags & ANA_ACCEL) != 0 && do_f;
-  if ((stage == 1 || accel_now) && ctx->ana_A && ctx->lin_static && p.qcache) {
+  if ((stage == 1 || accel_now) && pl.accel_static) {
     // the forward dynamics of the 2 nv perturbed points: the static first-order kernels evaluate exactly these points
     // (x + sqrt(eps_mach) e_k) chain-wise from the base point's cache, ~25x cheaper than one cooperative ABA per point.  When the
     // mode-1 pass follows in the same linearisation call they are formed ahead of stage 0, which then takes the trajectory point's
     // own acceleration from the same kernels (the idle lanes of the v-level wave evaluate it) instead of running an ABA per point
-    if (!ctx->ana_A_fresh) {
+    if (!call.ana_A_fresh) {
       LinParams pa = p;
       pa.accel_out = ctx->ana_A;
-      const bool with_u = stage == 1 ? do_eq : ((flags & ANA_EQ_NEXT) != 0 && d.Etot > 0);   // the constraint chain also differences along the u directions
-      const int rc_ = lin_static_launch(ctx, pa, with_u ? 7 : 6);
+      const bool with_u = pl.accel_with_u && (flags & (stage == 1 ? ANA_EQ : ANA_EQ_NEXT)) != 0;   // the constraint chain also differences along the u directions
+      const int rc_ = lin_static_launch(ctx, pa, with_u ? StaticLevel::AccelXU : StaticLevel::AccelX);
       if (rc_ != DDP_HIP_OK) return rc_;
-      ctx->ana_A_fresh = accel_now;                       // (lin.hip drops the mark when the linearisation call returns)
+      call.ana_A_fresh = accel_now;
     }
     ap.accel = ctx->ana_A;
     ap.accel_base = accel_now ? 1 : 0;
@@ -1199,20 +1199,19 @@ int launch_t(ddp_hip_ctx* ctx, const LinParams& p, int stage, int flags) {
     if (stage == 0) {
       ap.bt0 = 0; ap.nbt = (int32_t)BT;
       hipLaunchKernelGGL((ana_eval_kernel<NJ, true>), dim3((unsigned)BT), dim3(AW), lds, ctx->stream, ap);
-      ctx->ana_M0_fresh = ctx->ana_M0 != nullptr;         // (lin.hip drops the mark when the linearisation call returns)
+      call.ana_M0_fresh = ctx->ana_M0 != nullptr;
       if (do_eq) hipLaunchKernelGGL((ana_eq_kernel<NJ>), dim3((unsigned)BT), dim3(AW), eq_lds_bytes<NJ>(d), ctx->stream, ap);
       HIP_TRY(hipGetLastError());
       return DDP_HIP_OK;
     }
-    if (!ctx->ana_M0) return DDP_HIP_E_UNSUPPORTED;
-    if (!ctx->ana_M0_fresh) {                             // M^-1 at the trajectory points, for the v directions (else: stage 0 of this very linearisation left it)
+    if (!call.ana_M0_fresh) {                             // M^-1 at the trajectory points, for the v directions (else: stage 0 of this very linearisation left it)
       AnaParams a0 = ap;
       a0.stage = 0; a0.m0_only = 1; a0.bt0 = 0; a0.nbt = (int32_t)BT; a0.Fws = nullptr; a0.accel = nullptr;
       hipLaunchKernelGGL((ana_eval_kernel<NJ, true>), dim3((unsigned)BT), dim3(AW), lds, ctx->stream, a0);
     }
     // config constraint: its x-direction tensors come out of the evaluation waves themselves and eq_uu is exactly zero (f_u does not
     // depend on u and C is constant: ana_eq_kernel forms the same sum twice and differences it) -- no workspace, no slices
-    const bool eq_inline = do_eq && ctx->model_h.eq_kind == DDP_HIP_EQ_CONFIG && !ctx->sw.ana_eq_kernel;
+    const bool eq_inline = do_eq && pl.eq_inline;
     if (eq_inline) {
       ap.Fws = nullptr;
       ap.eq_inline = 1;
@@ -1246,37 +1245,31 @@ int launch_t(ddp_hip_ctx* ctx, const LinParams& p, int stage, int flags) {
 
 }  // namespace
 
+// the slice size, the workspaces ctx->plan lists and the kernels' LDS attributes (what the plan refuses never gets here)
 int lin_analytic_setup(ddp_hip_ctx* ctx) {
   const Dims& d = ctx->d;
-  if (ctx->model_h.kind != DDP_HIP_MODEL_TREE || ctx->model_h.first_order_fd) return DDP_HIP_OK;
-  if (ctx->model_h.ff) {
-    // free-flyer root: first order only (mode 1 is refused at ddp_hip_create); the constraint chain runs on lin.hip's three
-    // kernels with these jacobians at the look-ahead states
-    if (d.nv > 38) return DDP_HIP_E_UNSUPPORTED;
-    ctx->ana_nbt = d.batch * d.T;
+  const LinPlan& pl = ctx->plan;
+  if (!pl.ana_sliced) return DDP_HIP_OK;
+  const int64_t BT = d.batch * d.T;
+  if (pl.first == LinFirst::AnalyticFF) {
+    // free-flyer root: first order only; the constraint chain runs on lin.hip's three kernels with these jacobians at the
+    // look-ahead states
+    ctx->ana_nbt = BT;
     const size_t lds = sizeof(double) * (size_t)rbdd::FfLds<38>::TOTAL;
     if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ana_ff_first_kernel<38>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     return DDP_HIP_OK;
   }
-  if (d.nv <= 6) return DDP_HIP_OK;
-  if (ctx->model_h.max_level_width > AW) return DDP_HIP_E_UNSUPPORTED;
-  const int64_t BT = d.batch * d.T;
   int64_t slice = 256;
   if (ctx->sw.ana_bt) slice = ctx->sw.ana_bt;   // tuning knob
   ctx->ana_nbt = BT < slice ? BT : slice;
   const int64_t N = d.nv;
   // the stage-0 and stage-1 launches of one linearisation share the workspace: the base point keeps slot 0 of every pair
-  const bool m1 = ctx->model_h.fd_mode == 1 && !(ctx->flags & DDP_HIP_FLAG_NO_TENSORS);
-  if (ctx->sw.ana_split) HIP_TRY(hipMalloc(&ctx->ana_T, sizeof(double) * (size_t)(ctx->ana_nbt * (2 * N + 1) * N * 2 * N)));
-  if (ctx->sw.ana_split || (m1 && d.Etot > 0)) HIP_TRY(hipMalloc(&ctx->ana_M, sizeof(double) * (size_t)(ctx->ana_nbt * (N + 1) * N * N)));
-  if (!ctx->sw.ana_split && m1) HIP_TRY(hipMalloc(&ctx->ana_M0, sizeof(double) * (size_t)(BT * N * N)));
-  if (ctx->lin_static && ctx->lin_ws && ctx->model_h.fd_mode == 1 && !(ctx->flags & DDP_HIP_FLAG_NO_TENSORS))
-    HIP_TRY(hipMalloc(&ctx->ana_A, sizeof(double) * (size_t)(BT * (3 * N + 1) * N)));
+  if (pl.ws_ana_T) HIP_TRY(hipMalloc(&ctx->ana_T, sizeof(double) * (size_t)(ctx->ana_nbt * (2 * N + 1) * N * 2 * N)));
+  if (pl.ws_ana_M) HIP_TRY(hipMalloc(&ctx->ana_M, sizeof(double) * (size_t)(ctx->ana_nbt * (N + 1) * N * N)));
+  if (pl.ws_ana_M0) HIP_TRY(hipMalloc(&ctx->ana_M0, sizeof(double) * (size_t)(BT * N * N)));
+  if (pl.ws_ana_A) HIP_TRY(hipMalloc(&ctx->ana_A, sizeof(double) * (size_t)(BT * (3 * N + 1) * N)));
+  if (pl.ws_ana_F) HIP_TRY(hipMalloc(&ctx->ana_F, sizeof(double) * (size_t)(ctx->ana_nbt * 2 * N * N * 2 * N)));
   if (d.Etot > 0) {
-    // the constraint chain on analytic jacobians (ana_eq_kernel): K <= 2 look-ahead steps, see the kernel's header
-    if (ctx->model_h.eq_advance < 1 || ctx->model_h.eq_advance > 2) return DDP_HIP_E_UNSUPPORTED;
-    if (ctx->model_h.fd_mode == 1 && !(ctx->flags & DDP_HIP_FLAG_NO_TENSORS))
-      HIP_TRY(hipMalloc(&ctx->ana_F, sizeof(double) * (size_t)(ctx->ana_nbt * 2 * N * N * 2 * N)));
     const size_t l38 = eq_lds_bytes<38>(d), l64 = eq_lds_bytes<64>(d);
     if (l38 > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ana_eq_kernel<38>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l38));
     if (d.nv > 38 && l64 > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ana_eq_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l64));
@@ -1307,16 +1300,14 @@ void lin_analytic_teardown(ddp_hip_ctx* ctx) {
   if (ctx->ana_M0) (void)hipFree(ctx->ana_M0);
 }
 
-int lin_analytic_launch(ddp_hip_ctx* ctx, const LinParams& p, int stage, int flags) {
-  if (ctx->ana_nbt <= 0) return DDP_HIP_E_UNSUPPORTED;   // lin_analytic_setup did not take this model
-  if (stage == 1 && !p.has_tensors) return DDP_HIP_OK;
-  if (ctx->model_h.ff) {
-    if (stage != 0 || !(flags & LIN_ANA_F)) return DDP_HIP_E_UNSUPPORTED;
+// (the plan calls it on the legs lin_analytic_setup prepared: stage 0 of AnalyticFF / AnalyticWave, every stage of the wave legs)
+int lin_analytic_launch(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, int stage, int flags) {
+  if (ctx->plan.first == LinFirst::AnalyticFF) {
     const size_t lds = sizeof(double) * (size_t)rbdd::FfLds<38>::TOTAL;
     hipLaunchKernelGGL((ana_ff_first_kernel<38>), dim3((unsigned)(ctx->d.batch * ctx->d.T)), dim3(AW), lds, ctx->stream, p, 0);
     HIP_TRY(hipGetLastError());
     return DDP_HIP_OK;
   }
-  if (ctx->d.nv <= 38) return launch_t<38>(ctx, p, stage, flags);
-  return launch_t<64>(ctx, p, stage, flags);
+  if (ctx->d.nv <= 38) return launch_t<38>(ctx, p, call, stage, flags);
+  return launch_t<64>(ctx, p, call, stage, flags);
 }

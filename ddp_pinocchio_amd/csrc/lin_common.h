@@ -35,7 +35,17 @@ constexpr int LBS = 64;
 // static-topology second-order path (lin_static.hip): returns non-zero when the model's tree matches a compiled-in
 // topology; the launcher covers the velocity- and torque-level stencil points of finite_diff_hessian_compute mode 2
 int lin_static_supported(const DevModel& m);   // 0: none, else the id of the compiled-in topology
-int lin_static_launch(ddp_hip_ctx* ctx, const LinParams& p, int level);   // DDP_HIP_OK or an error code
+enum class StaticLevel {
+  Caches,          // the q- and v-caches every other level reads
+  FirstOrder,      // f_x, f_u: the first-order kernels along q, v, u
+  UDiagonal,       // mode 2: diagonal second-order entries of the u directions
+  Torque,          // mode 2: torque-level stencil points (and the diagonal entries of the q and v directions)
+  Velocity,        // mode 2: velocity-level stencil points
+  Configuration,   // mode 2: (q_i, q_j) stencil points
+  AccelX,          // mode 1: accelerations at x + sqrt(eps_mach) e_k into p.accel_out (builds the base caches itself)
+  AccelXU,         // ... and at u + sqrt(eps_mach) e_k
+};
+int lin_static_launch(ddp_hip_ctx* ctx, const LinParams& p, StaticLevel level);   // DDP_HIP_OK or an error code
 int64_t lin_static_ws_per_bt(const DevModel& m);
 
 // analytic first order / mode-1 second order of large tree models (lin_analytic.hip): stage 0 = f_x, f_u at the
@@ -45,6 +55,6 @@ void lin_analytic_teardown(ddp_hip_ctx* ctx);
 // flags: LIN_ANA_F the dynamics' outputs, LIN_ANA_EQ the constraint chain's (problem.hpp:569-620 on the analytic jacobians)
 constexpr int LIN_ANA_F = 1, LIN_ANA_EQ = 2;
 constexpr int LIN_ANA_ACCEL = 4;   // stage 0: the mode-1 pass follows in this linearisation call -- form its accelerations now and take the trajectory point's from them
-int lin_analytic_launch(ddp_hip_ctx* ctx, const LinParams& p, int stage, int flags);
+int lin_analytic_launch(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, int stage, int flags);
 // free-flyer models: analytic f_x at the constraint chain's look-ahead states x_1 .. x_{K-1} (after lin.hip: eq_chain_kernel)
 int lin_analytic_ff_lookahead(ddp_hip_ctx* ctx, const LinParams& p);

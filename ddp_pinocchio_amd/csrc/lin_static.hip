@@ -1858,40 +1858,41 @@ int64_t lin_static_ws_per_bt(const DevModel& m) {
   return sweep > splice ? sweep : splice;
 }
 
-// level 3: torque-level points (replaces lin_offdiag_kernel<NJ, 3>)
+// the first-order kernels along the q, v and (with_u) u directions: jacobian columns, or accelerations with p.accel_out set
 template <class T>
-static int lin_static_launch_t(ddp_hip_ctx* ctx, const LinParams& p, int level) {
+static void launch_first_columns(ddp_hip_ctx* ctx, const LinParams& p, bool with_u) {
   const int64_t BT = ctx->d.batch * ctx->d.T;
   constexpr int nv = T::N, TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS;
-  if (level == 3) {
+  const int64_t per = ctx->lin_qws_bt * GU;     // one wave per (instance, t) uses one of the GU workspace slots of a slice entry
+  for (int64_t bt0 = 0; bt0 < BT; bt0 += per) {
+    const int64_t nb = BT - bt0 < per ? BT - bt0 : per;
+    hipLaunchKernelGGL((lin_static_first_kernel<T, 1, false>), dim3((unsigned)nb), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, bt0);
+  }
+  hipLaunchKernelGGL((lin_static_first_kernel<T, 2, false>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
+  if (with_u) hipLaunchKernelGGL((lin_static_first_kernel<T, 3, false>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
+}
+
+template <class T>
+static int lin_static_launch_t(ddp_hip_ctx* ctx, const LinParams& p, StaticLevel level) {
+  const int64_t BT = ctx->d.batch * ctx->d.T;
+  constexpr int nv = T::N, TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS;
+  if (level == StaticLevel::Torque) {             // torque-level points (replaces lin_offdiag_kernel<NJ, 3>)
     hipLaunchKernelGGL((lin_static_tau_kernel<T, true>), dim3((unsigned)(BT * 2 * nv)), dim3(LBS), 0, ctx->stream, p);
     hipLaunchKernelGGL((lin_static_tau_kernel<T, false>), dim3((unsigned)(BT * GU)), dim3(LBS), 0, ctx->stream, p);
-  } else if (level == 5) {                        // q- and v-caches
+  } else if (level == StaticLevel::Caches) {
     hipLaunchKernelGGL((lin_static_qvcache_kernel<T>), dim3((unsigned)((BT * p.ncfg + LBS - 1) / LBS)), dim3(LBS), 0, ctx->stream, p, p.model, p.x, p.qcache, p.vcache);
     if (p.nvcfg > 1) hipLaunchKernelGGL((lin_static_vcache_kernel<T>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.x, p.qcache, p.vcache);
-  } else if (level == 6 || level == 7) {          // accelerations at x + sqrt(eps_mach) e_k (level 7: and u + sqrt(eps_mach) e_k) -> p.accel_out, after the base caches
+  } else if (level == StaticLevel::AccelXU || level == StaticLevel::AccelX) {   // -> p.accel_out, after the base caches
     if (!p.accel_out) return DDP_HIP_E_ARG;
     hipLaunchKernelGGL((lin_static_qvcache_kernel<T>), dim3((unsigned)((BT * p.ncfg + LBS - 1) / LBS)), dim3(LBS), 0, ctx->stream, p, p.model, p.x, p.qcache, p.vcache);
-    const int64_t per = ctx->lin_qws_bt * GU;
-    for (int64_t bt0 = 0; bt0 < BT; bt0 += per) {
-      const int64_t nb = BT - bt0 < per ? BT - bt0 : per;
-      hipLaunchKernelGGL((lin_static_first_kernel<T, 1, false>), dim3((unsigned)nb), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, bt0);
-    }
-    hipLaunchKernelGGL((lin_static_first_kernel<T, 2, false>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
-    if (level == 7) hipLaunchKernelGGL((lin_static_first_kernel<T, 3, false>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
-  } else if (level == 0) {                        // first order
-    const int64_t per = ctx->lin_qws_bt * GU;     // one wave per (instance, t) uses one of the GU workspace slots of a slice entry
-    for (int64_t bt0 = 0; bt0 < BT; bt0 += per) {
-      const int64_t nb = BT - bt0 < per ? BT - bt0 : per;
-      hipLaunchKernelGGL((lin_static_first_kernel<T, 1, false>), dim3((unsigned)nb), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, bt0);
-    }
-    hipLaunchKernelGGL((lin_static_first_kernel<T, 2, false>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
-    hipLaunchKernelGGL((lin_static_first_kernel<T, 3, false>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
-  } else if (level == 4) {
+    launch_first_columns<T>(ctx, p, level == StaticLevel::AccelXU);
+  } else if (level == StaticLevel::FirstOrder) {
+    launch_first_columns<T>(ctx, p, true);
+  } else if (level == StaticLevel::UDiagonal) {
     // diagonal second-order entries of the u directions; those of the q and v directions are formed by the torque-level
-    // row kernel (level 3) on an otherwise idle lane, which therefore runs ahead of levels 2 and 1
+    // row kernel (Torque) on an otherwise idle lane, which therefore runs ahead of Velocity and Configuration
     hipLaunchKernelGGL((lin_static_first_kernel<T, 3, true>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
-  } else if (level == 1 && !ctx->sw.cfg_full_aba) {
+  } else if (level == StaticLevel::Configuration && !ctx->sw.cfg_full_aba) {
     // Spine pre-pass, then the pair kernel on spliced operands, in slices of (instance, t) whose spine records share the workspace.
     // The workspace is sized for lin_qws_bt sweeps (lin_static_ws_per_bt: the first-order q columns run one); a spine set is
     // smaller, so a slice holds more of them (Talos: 4.2 x; few long launches instead of many short ones: measured below)
@@ -1904,7 +1905,7 @@ static int lin_static_launch_t(ddp_hip_ctx* ctx, const LinParams& p, int level) 
       hipLaunchKernelGGL((lin_static_spine_kernel<T>), grid, dim3(LBS), 0, ctx->stream, p.model, p.qcache, p.vcache, ctx->lin_qws, bt0, nb);
       hipLaunchKernelGGL((lin_static_cfg_pair_kernel<T>), grid, dim3(LBS), 0, ctx->stream, p, ctx->lin_qws, bt0, nb);
     }
-  } else if (level == 1) {
+  } else if (level == StaticLevel::Configuration) {
     // DDP_HIP_CFG_FULL_ABA (development A/B): every point runs the whole articulated-body algorithm.
     // In slices of (instance, t), so that the per-wave workspace stays small.  The sweep kernel of slice k+1 (one wave per
     // SIMD, long waves) and the acceleration / output kernel of slice k run on two streams with two workspaces: each
@@ -1926,7 +1927,7 @@ static int lin_static_launch_t(ddp_hip_ctx* ctx, const LinParams& p, int level) 
     }
     if (k >= 1) HIP_TRY(hipStreamWaitEvent(s0, ctx->lin_ev_dn[0], 0));
     if (k >= 2) HIP_TRY(hipStreamWaitEvent(s0, ctx->lin_ev_dn[1], 0));
-  } else if (level == 2) {
+  } else if (level == StaticLevel::Velocity) {
     hipLaunchKernelGGL((lin_static_vel_kernel<T, true>), dim3((unsigned)(BT * nv)), dim3(LBS), 0, ctx->stream, p);
     hipLaunchKernelGGL((lin_static_vel_kernel<T, false>), dim3((unsigned)(BT * GU)), dim3(LBS), 0, ctx->stream, p);
   }
@@ -1934,10 +1935,10 @@ static int lin_static_launch_t(ddp_hip_ctx* ctx, const LinParams& p, int level) 
   return DDP_HIP_OK;
 }
 
-int lin_static_launch(ddp_hip_ctx* ctx, const LinParams& p, int level) {
-  if (ctx->lin_static == 1) return lin_static_launch_t<TopoTalos38>(ctx, p, level);
-  if (ctx->lin_static == 2) return lin_static_launch_t<TopoChain6>(ctx, p, level);
-#define DDP_TOPO_LAUNCH(ID, TOPO) if (ctx->lin_static == (ID) - 1) return lin_static_launch_t<TOPO>(ctx, p, level);
+int lin_static_launch(ddp_hip_ctx* ctx, const LinParams& p, StaticLevel level) {
+  if (ctx->plan.topo == 1) return lin_static_launch_t<TopoTalos38>(ctx, p, level);
+  if (ctx->plan.topo == 2) return lin_static_launch_t<TopoChain6>(ctx, p, level);
+#define DDP_TOPO_LAUNCH(ID, TOPO) if (ctx->plan.topo == (ID) - 1) return lin_static_launch_t<TOPO>(ctx, p, level);
   DDP_TOPO_EXTRA(DDP_TOPO_LAUNCH)
 #undef DDP_TOPO_LAUNCH
   return DDP_HIP_E_UNSUPPORTED;

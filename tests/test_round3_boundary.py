@@ -94,15 +94,16 @@ def test_shard_pick_and_broadcast_single_rank(gpu, with_comm):
 
 
 def _context(capi, spec, monkeypatch, switch=None):
-    """a traced context, created with the development switch `switch` set: a context reads the switches once, when it is
-    created, so the switch is cleared again right away"""
-    if switch:
-        monkeypatch.setenv(switch, "1")
+    """a traced context, created with the development switch `switch` (or each of a tuple of them) set: a context reads the
+    switches once, when it is created, so they are cleared again right away"""
+    switches = (switch,) if isinstance(switch, str) else tuple(switch or ())
+    for s in switches:
+        monkeypatch.setenv(s, "1")
     try:
         return capi.Context(spec, flags=capi.FLAG_TRACE)
     finally:
-        if switch:
-            monkeypatch.delenv(switch)
+        for s in switches:
+            monkeypatch.delenv(s)
 
 
 def _dense_bytes(o):
@@ -266,3 +267,129 @@ def test_k3h_on_analytic_mode1_tensors_bit_for_bit(gpu, monkeypatch):
         again = sweep(ctx)
         for a_, b_ in zip(half, again):
             assert np.array_equal(a_, b_)
+
+
+# what the backward sweep may assume about FXX / FUX / FUU is one record with four transitions; K3's bytes per
+# (instance, step) name the state from outside: the closed forms of ddp_hip_bwd_stream_bytes
+def _sym_bytes(o):
+    n, m = o.n, o.m
+    return 8 * (n * (n * (n + 1) // 2) + n * n * m + n * (m * (m + 1) // 2))
+
+
+def _k3h_stencil_bytes(o):
+    n, m = o.n, o.m
+    cxx, cux, cuu = n * (n + 1) // 2, n * m, m * (m + 1) // 2
+    return 8 * ((cxx + cux + cuu) * (n - m) + 2 * cxx - n + cux)
+
+
+def _k3h_analytic1_bytes(o):
+    return 8 * (o.n * o.n + o.n * o.m) * (o.n - o.m)
+
+
+_FIRST_ONLY = 2   # capi.LIN_FIRST
+
+
+def _walk_mode2(ctx, o, T):
+    """the whole walk on the static stencil's tensors; ends dense with F_UU filled with zeros"""
+    dense, k3h = _dense_bytes(o), _k3h_stencil_bytes(o)
+    assert ctx.bwd_stream_bytes() == dense                     # nothing known about the tensors yet
+    ctx.linearize()
+    assert ctx.bwd_stream_bytes() == k3h
+    fxx = ctx.download("FXX")                                  # a reader from outside: the mirror images are formed for it ...
+    assert ctx.bwd_stream_bytes() == k3h                       # ... and the sweep goes on reading what it read
+    f = fxx[0].reshape(T, o.n, o.n, o.n)
+    assert np.array_equal(f, f.transpose(0, 2, 1, 3))
+    ctx.upload("FUX", ctx.download("FUX"))
+    # f_ux from outside: the zero configuration rows are no longer known, f_xx / f_uu are as symmetric as before (no symmetry
+    # is a statement about f_ux)
+    assert ctx.bwd_stream_bytes() == _sym_bytes(o)
+    ctx.linearize()
+    assert ctx.bwd_stream_bytes() == k3h
+    assert ctx.device_ptr("FXX")
+    assert ctx.bwd_stream_bytes() == dense                     # the caller may write through the pointer
+    ctx.linearize()
+    assert ctx.bwd_stream_bytes() == k3h
+    assert np.array_equal(ctx.download("FXX"), fxx)
+    ctx.fill("FUU", 0.0)
+    assert ctx.bwd_stream_bytes() == dense
+    ctx.linearize(_FIRST_ONLY)
+    assert ctx.bwd_stream_bytes() == dense                     # the first order alone says nothing about the tensors
+
+
+def _walk_mode2_ref(ctx, o, T):
+    ctx.linearize()
+    ctx.fill("FUU", 0.0)
+
+
+def _walk_sym(ctx, o, T):
+    ctx.linearize()
+    assert ctx.bwd_stream_bytes() == _sym_bytes(o)
+
+
+def _walk_mode1(ctx, o, T):
+    dense, k3h = _dense_bytes(o), _k3h_analytic1_bytes(o)
+    assert ctx.bwd_stream_bytes() == dense
+    ctx.linearize()
+    assert ctx.bwd_stream_bytes() == k3h
+    ctx.upload("FXX", ctx.download("FXX"))
+    assert ctx.bwd_stream_bytes() == dense
+    ctx.linearize()
+    assert ctx.bwd_stream_bytes() == k3h
+
+
+def _walk_dense(ctx, o, T):
+    dense = _dense_bytes(o)
+    assert ctx.bwd_stream_bytes() == dense
+    ctx.linearize()
+    assert ctx.bwd_stream_bytes() == dense
+    ctx.upload("FUX", ctx.download("FUX"))
+    assert ctx.bwd_stream_bytes() == dense
+    ctx.linearize()
+    assert ctx.bwd_stream_bytes() == dense
+
+
+def _plain(ctx, o, T):
+    ctx.linearize()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,fd_mode,fo,switch,ref_switch,walk,ref_walk", [
+    ("tree38", 2, None, None, "DDP_HIP_K3_NO_SYM", _walk_mode2, _walk_mode2_ref),
+    ("tree38", 0, None, None, "DDP_HIP_K3_NO_SYM", _walk_sym, _plain),
+    ("tree38", 2, None, "DDP_HIP_NO_STATIC", ("DDP_HIP_NO_STATIC", "DDP_HIP_K3_NO_SYM"), _walk_sym, _plain),
+    ("tree38", 1, 0, None, "DDP_HIP_K3_NO_HALF", _walk_mode1, _plain),
+    ("chain6", 2, None, None, None, _walk_dense, _plain),
+], ids=["mode2", "mode0", "mode2-no-static", "mode1-analytic", "chain6"])
+def test_tensor_state_transitions(gpu, monkeypatch, name, fd_mode, fo, switch, ref_switch, walk, ref_walk):
+    """Every state of the tensor record and every transition between them, at the smallest shape that reaches them (the fast
+    sweep needs n = 76, m = 38; chain6 never takes it), named from outside by K3's bytes per (instance, step).  After the walk
+    one backward sweep gives, bit for bit, the gains and the value function of a context that reached the same tensors by one
+    plain linearisation and reads them without the assumption the walk ended on (created with `ref_switch`)."""
+    capi = gpu
+    T = 2
+    model, spec, o = make(name, T, batch=1, fd_mode=fd_mode, first_order_fd=fo)
+    x0, us, xs = initial_trajectory(o, model, seed=91, u_sigma=0.3)
+    mults = o.alloc_affine(o.Etot)
+    mults["origin"][:] = xs[:T * o.nx]
+    if o.Etot:
+        mults["jac"][:o.Etot * o.n] = 0.01 * np.random.default_rng(4).normal(size=o.Etot * o.n)
+
+    def run(ctx, steps):
+        ctx.upload("X", xs); ctx.upload("U", us)
+        for k, sname in (("origin", "MULT_ORIGIN"), ("val", "MULT_VAL"), ("jac", "MULT_JAC")):
+            if ctx.seq_size(sname):
+                ctx.upload(sname, mults[k][:ctx.seq_size(sname)])
+        steps(ctx, o, T)
+        ctx.upload("LFX", np.random.default_rng(1).normal(size=(1, o.n)))           # a V_x that is not zero
+        ctx.upload("LFXX", np.eye(o.n).reshape(1, -1))
+        nbytes = ctx.bwd_stream_bytes()
+        rc, reg, mu, rs = ctx.backward(0.0, 100.0)
+        return nbytes, [ctx.download(s) for s in ("FB_JAC", "FB_VAL", "VX_TRACE", "FXX", "FUX", "FUU")] + [rc, reg, mu, rs]
+
+    with _context(capi, spec, monkeypatch, switch) as ctx, _context(capi, spec, monkeypatch, ref_switch) as ctx_ref:
+        nbytes, got = run(ctx, walk)
+        nbytes_ref, ref = run(ctx_ref, ref_walk)
+    assert nbytes_ref == _dense_bytes(o)
+    for a_, b_ in zip(got, ref):
+        assert np.array_equal(a_, b_)
+    assert np.all(np.isfinite(got[0])) and float(np.max(np.abs(got[2]))) > 0
