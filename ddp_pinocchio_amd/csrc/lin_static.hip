@@ -7,8 +7,10 @@
 // loop over the joints is expanded at compile time, every index is a constant and the running state of an
 // evaluation lives in registers.  One wave = 64 stencil points that share their configuration q (and, at the
 // torque level, their velocity): what the articulated-body algorithm derives from q (and v) alone is read from the
-// q- / v-caches through the scalar path (wave-uniform addresses), each lane only carries what its own perturbation
-// changes.  The arithmetic is the operation sequence of rbd::aba_u_cached / rbd::aba_vu_cached.
+// q- / v-caches -- wave-uniform blocks, copied into LDS with every load in flight and read as broadcasts by the row and
+// pair kernels of the velocity and torque levels, walked through the scalar path by the first-order kernels -- and each
+// lane only carries what its own perturbation changes.  The arithmetic is the operation sequence of
+// rbd::aba_u_cached / rbd::aba_vu_cached.
 #include <float.h>
 #include <math.h>
 #include <stdlib.h>
@@ -180,26 +182,6 @@ __device__ __forceinline__ void stage_placements(double* sp, const double* __res
     const int K = idx / 19, e = idx - K * 19;
     sp[K * PS + e] = qc[K * rbd::QC_STRIDE + e];
   }
-}
-
-// Pull a wave-uniform block into the L2 ahead of the scalar loads that walk it: 64 lanes x 16 bytes per KiB, all in
-// flight at once (the scalar path alone would pay the HBM latency once per 64-byte line, one line after the other).
-// Returns a word that depends on every byte loaded; the caller folds it into the start of its dependency chain so that
-// the evaluation begins once the block has arrived.  Plain loads on purpose: inline asm or a memory-writing intrinsic
-// anywhere ahead of the operand loads makes the compiler fall back from scalar to per-lane vector loads.
-template <int BYTES>
-__device__ __forceinline__ unsigned int warm_block(const double* base, int lane) {
-  typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-  const char* b = reinterpret_cast<const char*>(base);
-  unsigned int sink = 0;
-#pragma unroll
-  for (int off = 0; off < BYTES; off += LBS * 16) {
-    int o = off + lane * 16;
-    o = o < BYTES - 16 ? o : BYTES - 16;
-    const u4 v = *reinterpret_cast<const u4*>(b + o);
-    sink ^= v.x ^ v.y ^ v.z ^ v.w;
-  }
-  return sink;
 }
 
 template <class T> constexpr bool parents_at_least(int from, int lo) {
@@ -530,47 +512,37 @@ __global__ __launch_bounds__(LBS, ROWS ? 1 : 3) void lin_static_tau_kernel(LinPa
     tri_index(valid ? pid : 0, nv, i, j);
     i += n; j += n; cfg = 0; vcfg = 0;
   }
-  double eps = sqrt(sqrt(DBL_EPSILON));
+  const double eps = sqrt(sqrt(DBL_EPSILON));
   const double* __restrict__ qc = p.qcache + (bt * (nv + 1) + cfg) * (int64_t)nv * rbd::QC_STRIDE;
   const double* __restrict__ vc = p.vcache + (bt * (2 * nv + 1) + vcfg) * (int64_t)nv * rbd::VC_STRIDE;
   const double* __restrict__ xg = p.x + ((int64_t)b * (Tn + 1) + t) * n;
   const double* __restrict__ ug = p.u + ((int64_t)b * Tn + t) * nv;
   const int iu = i - n, ju = j - n;
-  // rows: the staged operands are dead once the acceleration pass is over, the output stage's buffers are not alive
-  // before: one LDS region for both (the evaluation and the output stage are a barrier apart)
-  __shared__ union TauLds { double P[ROWS ? nv * PS + nv * rbd::VC_STRIDE : 1]; RowStage<nv> S; } s_lds;
+  // the staged operands are dead once the acceleration pass is over, the output stage's buffers (rows: RowStage, pairs: OutStage)
+  // are not alive before: one LDS region for all of them (the evaluation and the output stage are a barrier apart)
+  __shared__ union TauLds { double P[nv * PS + nv * rbd::VC_STRIDE]; RowStage<nv> S; OutStage<nv, LBS / 2> O; } s_lds;
   double* s_P = s_lds.P;
-  // rows: the v-cache block of the row goes to LDS as well, in one coalesced pass (all of it in flight at once).  Through the
-  // scalar path its 76 per-joint reads are 76 serialised L2 round trips per wave (measured: 19.5 -> 17.6 ms at 64 seeds)
-  unsigned int w = 0;
+  // the v-cache block goes to LDS as well, in one coalesced pass (all of it in flight at once).  Through the scalar path its
+  // 76 per-joint reads are 76 serialised L2 round trips per wave (measured on the rows: 19.5 -> 17.6 ms at 64 seeds)
   double* s_V = s_P + nv * PS;
-  constexpr int KH = ROWS ? stage_split<T>() : 0;
-  StageRegs<nv, 0, (ROWS && KH > 0) ? KH : 1> lower;   // (KH == 0: joint 0 once more, harmless)            // joints 0 .. KH-1: in flight through the first half of the leaf -> root pass
-  if constexpr (ROWS) {
+  constexpr int KH = stage_split<T>();
+  StageRegs<nv, 0, (KH > 0) ? KH : 1> lower;   // (KH == 0: joint 0 once more, harmless)            // joints 0 .. KH-1: in flight through the first half of the leaf -> root pass
+  {
     StageRegs<nv, KH, nv> upper;
     upper.load(qc, vc, lane);
     lower.load(qc, vc, lane);
     upper.park(s_P, s_V, lane);
     rbd::coop_sync<true>();                         // one wave per workgroup: LDS is in order, no vmcnt(0) behind this fence
-  } else {
-    w = warm_block<nv * rbd::VC_STRIDE * 8>(vc, lane);
-    w ^= warm_block<nv * rbd::QC_STRIDE * 8>(qc, lane);
   }
-  if (w == 0x7fc01234u) eps = 0.0;     // never true for cache contents that are finite doubles in practice; orders the chain
   TauState<T> s;
   auto tau = [&](int k) { double v = ug[k]; if (k == iu) v = v + eps; if (k == ju) v = v + eps; return v; };
-  if constexpr (ROWS) {
-    // joints nv-1 .. KH+1 only touch records KH .. nv-1 (their own and their parents': checked below), joint KH needs its parent's
-    static_assert(!ROWS || parents_at_least<T>(KH + 1, KH), "the first half of the pass must not reach below record KH");
-    tau_up_range<T, PS, nv - 1>(m, s_P, s_V, tau, s, std::make_integer_sequence<int, nv - 1 - KH>{});
-    lower.park(s_P, s_V, lane);
-    rbd::coop_sync<true>();
-    tau_up_range<T, PS, KH>(m, s_P, s_V, tau, s, std::make_integer_sequence<int, KH + 1>{});
-    tau_down_all<T, PS>(m, s_P, s_V, s, std::make_integer_sequence<int, nv>{});
-  } else {
-    tau_up_all<T, rbd::QC_STRIDE>(m, qc, vc, tau, s, std::make_integer_sequence<int, nv>{});
-    tau_down_all<T, rbd::QC_STRIDE>(m, qc, vc, s, std::make_integer_sequence<int, nv>{});
-  }
+  // joints nv-1 .. KH+1 only touch records KH .. nv-1 (their own and their parents': checked below), joint KH needs its parent's
+  static_assert(parents_at_least<T>(KH + 1, KH), "the first half of the pass must not reach below record KH");
+  tau_up_range<T, PS, nv - 1>(m, s_P, s_V, tau, s, std::make_integer_sequence<int, nv - 1 - KH>{});
+  lower.park(s_P, s_V, lane);
+  rbd::coop_sync<true>();
+  tau_up_range<T, PS, KH>(m, s_P, s_V, tau, s, std::make_integer_sequence<int, KH + 1>{});
+  tau_down_all<T, PS>(m, s_P, s_V, s, std::make_integer_sequence<int, nv>{});
   // The output stage reads its pointers from the kernel-argument segment only now: taken from `p` they would be
   // loaded at kernel entry and stay live through the whole evaluation, and the scalar registers would spill.
   __builtin_amdgcn_sched_barrier(0);
@@ -592,10 +564,11 @@ __global__ __launch_bounds__(LBS, ROWS ? 1 : 3) void lin_static_tau_kernel(LinPa
                             kp->fuu + bt * n * mm * mm, (int64_t)n + (int64_t)n * mm, m.dt, kp->f_val + bt * n,
                             kp->fx + bt * n * n + (int64_t)i * n, kp->fxx + bt * n * n * n + (int64_t)i * n + (int64_t)i * n * n, xg, kp->skip_top != 0);
   } else {
-    __shared__ OutStage<nv, LBS / 2> S;
+    OutStage<nv, LBS / 2>& S = s_lds.O;
     LinParams po;
     po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top;
     const double dt = m.dt;
+    __syncthreads();                       // every lane is done with the staged operands
 #pragma unroll 1
     for (int pass = 0; pass < 2; ++pass) {
       if (pass) __syncthreads();                  // the first half's slots have been read
@@ -613,8 +586,8 @@ __global__ __launch_bounds__(LBS, ROWS ? 1 : 3) void lin_static_tau_kernel(LinPa
 // its first two passes are walked chain by chain (a chain = a run of single-child joints): down a chain computing the
 // link velocities, back up it forming the bias forces, so that only one chain's velocities are alive at a time; the
 // velocity of a branching joint is formed when its first child chain needs it.  The third pass recomputes the link
-// velocities on its way down instead of keeping 12 doubles per joint from the first.  u_i lives in LDS (the buffer the
-// output stage reads the accelerations from).
+// velocities on its way down instead of keeping 12 doubles per joint from the first.  u_i lives in registers in the row
+// and pair kernels below (VelCtx<0>), in the LDS buffer the output stage reads the accelerations from elsewhere.
 template <class T> constexpr int n_children(int k) {
   int c = 0;
   for (int j = k + 1; j < T::N; ++j) if (T::parent[j] == k) ++c;
@@ -823,9 +796,9 @@ __device__ __forceinline__ void vel_down_all(const C& c, VelState<T>& s, std::in
 
 // One wave per group; the groups of one (instance, t):
 //   ROWS:  g < nv : (q_g, v_lane)      cfg 1+g   38 of 64 lanes, row-block output (+ mirror image)
-//   !ROWS: (v_i, v_j) pairs, cfg 0, 64 pairs per wave, generic output
+//   !ROWS: (v_i, v_j) pairs, cfg 0, 64 pairs per wave, generic output in two half-wave passes
 template <class T, bool ROWS>
-__global__ __launch_bounds__(LBS, ROWS ? 3 : 1) void lin_static_vel_kernel(LinParams p) {
+__global__ __launch_bounds__(LBS, ROWS ? 3 : 2) void lin_static_vel_kernel(LinParams p) {
   constexpr int nv = T::N, n = 2 * nv;
   constexpr int TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS, G = ROWS ? nv : GU;
   const int64_t bt = blockIdx.x / G;
@@ -843,26 +816,25 @@ __global__ __launch_bounds__(LBS, ROWS ? 3 : 1) void lin_static_vel_kernel(LinPa
     tri_index(valid ? pid : 0, nv, i, j);
     i += nv; j += nv; cfg = 0;
   }
-  // rows: u_i / the accelerations stay in registers, and the staged operands (dead after the acceleration pass) share
-  // their LDS with the output stage's buffers (alive after it)
-  using Stage = typename std::conditional<ROWS, RowStage<nv>, OutStage<nv>>::type;
-  // rows: the whole q-cache block of the row (placements, U, 1/D and the articulated inertias: 12 KB) is staged in LDS, all of
-  // its loads in flight at once; nothing of the evaluation goes through the scalar path's serialised round trips
-  __shared__ union VelLds { Stage S; double P[ROWS ? nv * rbd::QC_STRIDE : 1]; } s_lds;
+  // u_i / the accelerations stay in registers, and the staged operands (dead after the acceleration pass) share their LDS with
+  // the output stage's buffers (alive after it).  Pairs: the output stage takes the wave's points in two halves (PairStage)
+  struct PairStage { OutStage<nv, LBS / 2> O; double spare[nv + 1]; };   // spare: where the half that is not emitted leaves its values
+  using Stage = typename std::conditional<ROWS, RowStage<nv>, PairStage>::type;
+  // the whole q-cache block of the wave's configuration (placements, U, 1/D and the articulated inertias: 12 KB) is staged in
+  // LDS, all of its loads in flight at once; nothing of the evaluation goes through the scalar path's serialised round trips
+  __shared__ union VelLds { Stage S; double P[nv * rbd::QC_STRIDE]; } s_lds;
   Stage& S = s_lds.S;
   double* s_P = s_lds.P;
-  VelCtx<ROWS ? 0 : 1, rbd::QC_STRIDE> c;
+  VelCtx<0, rbd::QC_STRIDE> c;
   c.m = p.model;
   c.qc = p.qcache + (bt * (nv + 1) + cfg) * (int64_t)nv * rbd::QC_STRIDE;
-  c.qp = ROWS ? s_P : c.qc;
+  c.qp = s_P;
   c.xg = p.x + ((int64_t)b * (Tn + 1) + t) * n;
   c.ug = p.u + ((int64_t)b * Tn + t) * nv;
   c.i = i; c.j = j;
   c.eps = sqrt(sqrt(DBL_EPSILON));
-  // pairs: this lane's row of the output stage's acceleration buffer (lane-major, odd stride)
-  if constexpr (ROWS) c.uq = nullptr;
-  else c.uq = &S.qdd[lane * (nv + 1)];
-  if constexpr (ROWS) {
+  c.uq = nullptr;
+  {
     constexpr int NW = nv * rbd::QC_STRIDE, CW = (NW + LBS - 1) / LBS;
     double rq[CW];
 #pragma unroll
@@ -871,9 +843,6 @@ __global__ __launch_bounds__(LBS, ROWS ? 3 : 1) void lin_static_vel_kernel(LinPa
     for (int r = 0; r < CW; ++r) { const int idx = r * LBS + lane; s_P[idx < NW ? idx : NW - 1] = rq[r]; }
     c.qc = s_P;
     rbd::coop_sync<true>();
-  } else {
-    const unsigned int w = warm_block<nv * rbd::QC_STRIDE * 8>(c.qc, lane);
-    if (w == 0x7fc01234u) c.eps = 0.0;     // never true in practice; orders the evaluation behind the warm-up
   }
   VelState<T> s;
   vel_up_all<T>(c, s, std::make_integer_sequence<int, nv>{});
@@ -898,9 +867,27 @@ __global__ __launch_bounds__(LBS, ROWS ? 3 : 1) void lin_static_vel_kernel(LinPa
                              fxb + (int64_t)nv * n, fxx + (int64_t)nv * n + (int64_t)nv * n * n, (int64_t)n + (int64_t)n * n, dt,
                              kp->f_val + bt * n, fxb + (int64_t)i * n, fxx + (int64_t)i * n + (int64_t)i * n * n, c.xg, kp->skip_top != 0);
   } else {
+    constexpr int NP = LBS / 2;
     LinParams po;
     po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top;
-    offdiag_emit<nv, LBS>(po, S, valid, i, j, bt, c.xg, dt);
+    __syncthreads();                       // every lane is done with the staged operands
+    // point-major with an odd stride (OutStage); the second half of the wave parks its values in the spare row for now.
+    // Unconditional stores right behind the evaluation (see the torque-level kernel)
+    double* const own = &S.O.qdd[(lane % NP) * (nv + 1)];
+    double* const row = lane < NP ? own : S.spare;
+#pragma unroll
+    for (int k = 0; k < nv; ++k) row[k] = s.uu[k];
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+      if (pass) {
+        __syncthreads();                  // the first half's slots have been read
+        if (lane >= NP) {
+#pragma unroll
+          for (int k = 0; k < nv; ++k) own[k] = s.uu[k];
+        }
+      }
+      offdiag_emit<nv, NP>(po, S.O, valid, i, j, bt, c.xg, dt, pass);
+    }
   }
 }
 
