@@ -25,6 +25,7 @@ BUILTIN_PENDULUM, BUILTIN_CHAIN6, BUILTIN_TREE38, BUILTIN_CHAIN6_FF, BUILTIN_TRE
 JOINT_REVOLUTE, JOINT_PRISMATIC, JOINT_FREEFLYER = 0, 1, 2
 FLAG_NO_TENSORS, FLAG_TRACE, FLAG_TRACKING_COST, FLAG_CONTROL_BOUNDS = 1, 2, 4, 8
 FLAG_FRAME_COST = 16
+FLAG_STATE_LIMITS = 32
 MAX_COST_FRAMES = 4
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
 
@@ -55,6 +56,7 @@ EXPORTS = [
     "ddp_hip_batch", "ddp_hip_set_active", "ddp_hip_solve", "ddp_hip_ctx_info",
     "ddp_hip_model_create", "ddp_hip_model_destroy", "ddp_hip_model_aba", "ddp_hip_model_aba_derivatives", "ddp_hip_model_frame",
     "ddp_hip_frame_cost_set_frames", "ddp_hip_frame_cost_upload", "ddp_hip_frame_cost_download",
+    "ddp_hip_state_limits_upload", "ddp_hip_state_limits_download",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -138,6 +140,9 @@ def lib():
         L.ddp_hip_frame_cost_set_frames.argtypes = [C.c_void_p, C.c_int32, _ip, _dp]
         L.ddp_hip_frame_cost_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_frame_cost_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+    if hasattr(L, "ddp_hip_state_limits_upload"):    # (likewise: set_state_limits fails on an older build)
+        L.ddp_hip_state_limits_upload.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_state_limits_download.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int64]
     L.ddp_hip_rollout.argtypes = [C.c_void_p]
     L.ddp_hip_linearize.argtypes = [C.c_void_p]
     L.ddp_hip_linearize_stages.argtypes = [C.c_void_p, C.c_uint32]
@@ -457,6 +462,38 @@ class Context:
         t, w = np.zeros(shape), np.zeros(shape)
         _check(lib().ddp_hip_frame_cost_download(self._h, _ptr(t), _ptr(w), first, count), "frame_cost_download")
         return t, w
+
+    def set_state_limits(self, lo=None, hi=None, weight=None, first=0, count=None):
+        """The soft state limits of instances first .. first + count - 1 (a context created with FLAG_STATE_LIMITS; ddp_hip.h),
+        over the tangent rows (n = 2 nv: configuration rows, then velocity rows): each of lo, hi, weight a scalar or an (n,)
+        vector for every step, a (T+1, n) array for every instance of the range, or (count, T+1, n) with one per instance.
+        -inf / +inf: no bound on that side.  None leaves that side as it is (the library then holds the side that arrives
+        against the resident other one)."""
+        count = self.batch - first if count is None else count
+        sp = self.spec
+        full = (count, sp.T + 1, sp.n)
+        arrs = {}
+        for name, arr in (("lo", lo), ("hi", hi), ("weight", weight)):
+            if arr is None:
+                continue
+            arr = np.asarray(arr, dtype=np.float64)
+            if arr.ndim > 3 or (arr.ndim == 3 and arr.shape != full) or (arr.ndim == 2 and arr.shape != full[1:]) or \
+                    (arr.ndim == 1 and arr.shape != full[2:]):
+                raise ValueError(f"set_state_limits {name}: shape {arr.shape}, expected a scalar, {full[2:]}, {full[1:]} or {full}")
+            arrs[name] = np.ascontiguousarray(np.broadcast_to(arr, full))
+        if "lo" in arrs and "hi" in arrs and bool(np.any(arrs["lo"] > arrs["hi"])):
+            raise ValueError("set_state_limits: some lo > hi")
+        if arrs:
+            a = [_ptr(arrs[k]) if k in arrs else None for k in ("lo", "hi", "weight")]
+            _check(lib().ddp_hip_state_limits_upload(self._h, a[0], a[1], a[2], first, count), "state_limits_upload")
+
+    def state_limits(self, first=0, count=None):
+        """(lo, hi, weight) of instances first .. first + count - 1, each (count, T+1, n)"""
+        count = self.batch - first if count is None else count
+        shape = (max(count, 0), self.spec.T + 1, self.spec.n)
+        lo, hi, w = np.zeros(shape), np.zeros(shape), np.zeros(shape)
+        _check(lib().ddp_hip_state_limits_download(self._h, _ptr(lo), _ptr(hi), _ptr(w), first, count), "state_limits_download")
+        return lo, hi, w
 
     def fill(self, name, value):
         _check(lib().ddp_hip_fill(self._h, SEQ[name], float(value)), f"fill {name}")

@@ -353,6 +353,16 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipMemsetAsync(ctx->fc_target_d, 0, sizeof(double) * words, ctx->stream));
     CTX_TRY(hipMemsetAsync(ctx->fc_weight_d, 0, sizeof(double) * words, ctx->stream));
   }
+  if (flags & DDP_HIP_FLAG_STATE_LIMITS) {
+    // lo = -inf, hi = +inf, w = 0: no limit anywhere
+    const int64_t words = d.batch * (d.T + 1) * d.n;
+    CTX_TRY(hipMalloc(&ctx->sl_d, sizeof(double) * (size_t)(3 * words)));
+    if (fill_device(ctx, ctx->sl_d, words, -INFINITY) != DDP_HIP_OK || fill_device(ctx, ctx->sl_d + words, words, INFINITY) != DDP_HIP_OK ||
+        fill_device(ctx, ctx->sl_d + 2 * words, words, 0.0) != DDP_HIP_OK) {
+      ddp_hip_destroy(ctx);
+      return DDP_HIP_E_HIP;
+    }
+  }
   int rc = bwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = fwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = lin_setup(ctx);
@@ -374,6 +384,7 @@ extern "C" int ddp_hip_destroy(ddp_hip_ctx* ctx) {
     if (ctx->seq[s].ptr) (void)hipFree(ctx->seq[s].ptr);
   if (ctx->fc_target_d) (void)hipFree(ctx->fc_target_d);
   if (ctx->fc_weight_d) (void)hipFree(ctx->fc_weight_d);
+  if (ctx->sl_d) (void)hipFree(ctx->sl_d);
   if (ctx->ne_d) (void)hipFree(ctx->ne_d);
   if (ctx->Epre_d) (void)hipFree(ctx->Epre_d);
   if (ctx->target_d) (void)hipFree(ctx->target_d);
@@ -563,6 +574,72 @@ extern "C" int ddp_hip_frame_cost_download(ddp_hip_ctx* ctx, double* target, dou
   HIP_TRY(hipSetDevice(ctx->device));
   if (target) HIP_TRY(hipMemcpyAsync(target, ctx->fc_target_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
   if (weight) HIP_TRY(hipMemcpyAsync(weight, ctx->fc_weight_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return DDP_HIP_OK;
+}
+
+// ---- soft state limits (DDP_HIP_FLAG_STATE_LIMITS): lo, hi, weight per (instance, t, tangent row) --------------------------
+static int state_limits_range(ddp_hip_ctx* ctx, int64_t first, int64_t count) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_STATE_LIMITS)) return DDP_HIP_E_UNSUPPORTED;
+  if (first < 0 || count < 0 || first + count > ctx->d.batch) return DDP_HIP_E_ARG;
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_state_limits_upload(ddp_hip_ctx* ctx, const double* lo, const double* hi, const double* weight, int64_t first,
+                                           int64_t count) {
+  int rc = state_limits_range(ctx, first, count);
+  if (rc != DDP_HIP_OK) return rc;
+  const int64_t n = ctx->d.n, sz = (ctx->d.T + 1) * n, words = sz * count, all = sz * ctx->d.batch;
+  bool nonzero = false;
+  if (lo)
+    for (int64_t i = 0; i < words; ++i)
+      if (isnan(lo[i]) || lo[i] == INFINITY) return DDP_HIP_E_ARG;
+  if (hi)
+    for (int64_t i = 0; i < words; ++i)
+      if (isnan(hi[i]) || hi[i] == -INFINITY) return DDP_HIP_E_ARG;
+  if (weight)
+    for (int64_t i = 0; i < words; ++i) {
+      if (!cost_weight_ok(weight[i])) return DDP_HIP_E_ARG;
+      if (ctx->model_h.ff && i % n < 6 && weight[i] != 0.0) return DDP_HIP_E_ARG;   // a free-flyer root's pose rows carry no limit
+      nonzero |= weight[i] != 0.0;
+    }
+  if (count == 0 || (!lo && !hi && !weight)) return DDP_HIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  double* lo_d = ctx->sl_d + first * sz;
+  double* hi_d = ctx->sl_d + all + first * sz;
+  // lo <= hi, before anything is written: a side that arrives alone is held against the resident other side (read back: uploads
+  // are not a hot path)
+  if (lo || hi) {
+    std::vector<double> other;
+    const double *l = lo, *h = hi;
+    if (!lo || !hi) {
+      other.resize((size_t)words);
+      HIP_TRY(hipMemcpyAsync(other.data(), lo ? hi_d : lo_d, sizeof(double) * (size_t)words, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(hipStreamSynchronize(ctx->stream));
+      (lo ? h : l) = other.data();
+    }
+    for (int64_t i = 0; i < words; ++i)
+      if (l[i] > h[i]) return DDP_HIP_E_ARG;
+  }
+  if (lo) HIP_TRY(hipMemcpyAsync(lo_d, lo, sizeof(double) * (size_t)words, hipMemcpyHostToDevice, ctx->stream));
+  if (hi) HIP_TRY(hipMemcpyAsync(hi_d, hi, sizeof(double) * (size_t)words, hipMemcpyHostToDevice, ctx->stream));
+  if (weight) HIP_TRY(hipMemcpyAsync(ctx->sl_d + 2 * all + first * sz, weight, sizeof(double) * (size_t)words, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  // as fc_live: any non-zero weight switches the terms on, only ONE upload of zeros for the whole batch switches them off again
+  if (weight) ctx->sl_live = nonzero || (ctx->sl_live && !(first == 0 && count == ctx->d.batch));
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_state_limits_download(ddp_hip_ctx* ctx, double* lo, double* hi, double* weight, int64_t first, int64_t count) {
+  int rc = state_limits_range(ctx, first, count);
+  if (rc != DDP_HIP_OK) return rc;
+  const int64_t sz = (ctx->d.T + 1) * ctx->d.n, words = sz * count, all = sz * ctx->d.batch;
+  if (count == 0 || (!lo && !hi && !weight)) return DDP_HIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  double* side[3] = {lo, hi, weight};
+  for (int k = 0; k < 3; ++k)
+    if (side[k]) HIP_TRY(hipMemcpyAsync(side[k], ctx->sl_d + k * all + first * sz, sizeof(double) * (size_t)words, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return DDP_HIP_OK;
 }

@@ -14,6 +14,7 @@
 #include "frame_cost.h"
 #include "internal.h"
 #include "rbd.h"
+#include "state_limits.h"
 
 namespace {
 
@@ -41,6 +42,7 @@ struct FwdParams {
   int32_t track;
   const double *ctrl_lo, *ctrl_hi;       // control bounds (DDP_HIP_FLAG_CONTROL_BOUNDS), else null
   FrameCostDev fc;                       // frame-position cost (DDP_HIP_FLAG_FRAME_COST); fc.target null: no terms
+  StateLimitsDev sl;                     // soft state limits (DDP_HIP_FLAG_STATE_LIMITS); sl.weight null: no terms
 };
 
 // constraint value at solver time t: constraint_advance_time_t::eval_to (problem.hpp:563-567) applied
@@ -116,10 +118,29 @@ __device__ double frame_cost_sum(const FrameCostDev& fc, const DevModel& m, int6
   return 0.5 * s;
 }
 
+// 1/2 sum_i w_i e_i^2 over the tangent rows of the state at (instance, t) pair bt1, e_i the amount by which the row's state
+// coordinate leaves [lo_i, hi_i] (ddp_hip.h: DDP_HIP_FLAG_STATE_LIMITS): a sibling of track_state_sum, one lane, rows in order.
+// A row of weight 0 reads neither bound and a row inside its interval adds nothing: with limits that do not bind the sum is +0
+__device__ __forceinline__ double limit_state_sum(const StateLimitsDev& sl, bool ff, int nv, int64_t bt1, const double* x) {
+  const int nq = ff ? nv + 1 : nv, n = 2 * nv;
+  const double* w = sl.weight + bt1 * n;
+  const double* lo = sl.lo + bt1 * n;
+  const double* hi = sl.hi + bt1 * n;
+  double s = 0;
+  for (int i = ff ? 6 : 0; i < n; ++i) {
+    const double wi = w[i];
+    if (wi == 0.0) continue;
+    const double e = limit_excess(x[limit_coord(i, nv, nq)], lo[i], hi[i]);
+    if (e != 0.0) s += wi * e * e;
+  }
+  return 0.5 * s;
+}
+
 // one term of cost_seq_aug (ddp.hpp:730): l + pe.ce + mu/2 |ce|^2
 // FRAME: + the frame terms (DDP_HIP_FLAG_FRAME_COST), in instantiations of their own of cost_kernel, forward_kernel and
 // cand_cost_kernel: a run-time branch here moved the spills of the kernels that exist without the flag
-template <int NJ, bool FRAME = false>
+// LIMIT: + the state-limit terms (DDP_HIP_FLAG_STATE_LIMITS), after the frame terms, in instantiations of their own alike
+template <int NJ, bool FRAME = false, bool LIMIT = false>
 __device__ double stage_cost(const FwdParams& p, const DevModel& m, int b, int64_t t, const double* x, const double* u, double mu) {
   const int nv = m.nv, n = 2 * nv, nx = m.nq + nv;
   double un = 0;
@@ -127,6 +148,7 @@ __device__ double stage_cost(const FwdParams& p, const DevModel& m, int b, int64
   double cost = 0.5 * m.c * un;                                   // problem_t::l, problem.hpp:937-942
   if (p.track) cost += track_state_cost(p, b, t, x) + track_control_sum(p, b, t, u);   // + the tracking terms
   if constexpr (FRAME) cost += frame_cost_sum(p.fc, m, (int64_t)b * (p.d.T + 1) + t, x);   // + the frame terms
+  if constexpr (LIMIT) cost += limit_state_sum(p.sl, m.ff != 0, nv, (int64_t)b * (p.d.T + 1) + t, x);   // + the state-limit terms
   const int e = (int)p.ne[t];
   if (e > 0) {
     double ce[NJ > 3 ? NJ : 3];
@@ -170,15 +192,16 @@ __global__ void rollout_kernel(FwdParams p) {
 }
 
 // problem_t::lf (problem.hpp:932-936: 0), or the tracking cost's terminal term
-template <bool FRAME = false>
+template <bool FRAME = false, bool LIMIT = false>
 __device__ __forceinline__ double terminal_cost(const FwdParams& p, const DevModel& m, int b, const double* x) {
   double cost = p.track ? track_state_cost(p, b, p.d.T, x) : 0.0;
   if constexpr (FRAME) cost += frame_cost_sum(p.fc, m, (int64_t)b * (p.d.T + 1) + p.d.T, x);
+  if constexpr (LIMIT) cost += limit_state_sum(p.sl, m.ff != 0, m.nv, (int64_t)b * (p.d.T + 1) + p.d.T, x);
   return cost;
 }
 
 // cost_seq_aug of one trajectory: one lane per (instance, t)
-template <int NJ, bool FRAME = false>
+template <int NJ, bool FRAME = false, bool LIMIT = false>
 __global__ void cost_kernel(FwdParams p, int which) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t T = p.d.T;
@@ -189,17 +212,17 @@ __global__ void cost_kernel(FwdParams p, int which) {
   const int nx = m.nq + m.nv, nu = m.nv;
   double* out = (which == 0 ? p.costs_old : p.costs_new) + (int64_t)b * (T + 1);
   const double* xs = (which == 0 ? p.x_old : p.x_new) + ((int64_t)b * (T + 1) + t) * nx;
-  if (t == T) { out[T] = terminal_cost<FRAME>(p, m, b, xs); return; }
+  if (t == T) { out[T] = terminal_cost<FRAME, LIMIT>(p, m, b, xs); return; }
   const double* us = (which == 0 ? p.u_old : p.u_new) + ((int64_t)b * T + t) * nu;
   double x[2 * NJ + 1], u[NJ];
   for (int i = 0; i < nx; ++i) x[i] = xs[i];
   for (int i = 0; i < nu; ++i) u[i] = us[i];
-  out[t] = stage_cost<NJ, FRAME>(p, m, b, t, x, u, p.mu[b]);
+  out[t] = stage_cost<NJ, FRAME, LIMIT>(p, m, b, t, x, u, p.mu[b]);
 }
 
 // closed-loop rollouts (ddp_fwd.ipp:39-51) of n_alpha candidate steps per instance + their summed cost
 // difference (ddp_fwd.ipp:54-56)
-template <int NJ, bool FRAME = false>
+template <int NJ, bool FRAME = false, bool LIMIT = false>
 __global__ void forward_kernel(FwdParams p) {
   // the model table in LDS: the dynamics of every step read it joint by joint (axis, placement, inertia: some 40 words per joint
   // and evaluation), and from global memory each of those reads is a dependent L2 round trip of the one lane that rolls out
@@ -249,12 +272,12 @@ __global__ void forward_kernel(FwdParams p) {
       for (int i = 0; i < nu; ++i) u[i] = u[i] < lo[i] ? lo[i] : (u[i] > hi[i] ? hi[i] : u[i]);
     }
     for (int i = 0; i < nu; ++i) uw[t * nu + i] = u[i];
-    const double c_new = stage_cost<NJ, FRAME>(p, m, b, t, x, u, mu);
+    const double c_new = stage_cost<NJ, FRAME, LIMIT>(p, m, b, t, x, u, mu);
     dsum += c_new - cold[t];
     rbd::eval_f<NJ>(m, x, u, xn);                                             // :50
     for (int i = 0; i < nx; ++i) { x[i] = xn[i]; xw[(t + 1) * nx + i] = xn[i]; }
   }
-  dsum += terminal_cost<FRAME>(p, m, b, x) - cold[T];
+  dsum += terminal_cost<FRAME, LIMIT>(p, m, b, x) - cold[T];
   p.fw_dcost[(int64_t)b * na + a] = dsum;
 }
 
@@ -307,6 +330,31 @@ __device__ __forceinline__ double frame_lanes_sum(const FwdParams& p, const M& c
   return v;
 }
 
+// The state-limit terms of one candidate of forward_kernel_lat2 at time t (t = T: lf): lane h takes the tangent rows r0 + h,
+// r0 + h + 16, ... (r0 = 6 on a free flyer, whose pose rows carry no limit), track_lanes_sum's split; a row of weight 0 reads
+// neither bound; the partial sums meet in the same fixed butterfly.  Every lane of the wave calls it
+template <bool FF>
+__device__ __forceinline__ double limit_lanes_sum(const FwdParams& p, int b, int64_t t, const double* x, int h, bool live) {
+  const int nv = (int)p.d.nv, n = 2 * nv, nq = (int)p.d.nx - nv, r0 = FF ? 6 : 0;
+  constexpr int NH = 16;
+  const int64_t bt1 = (int64_t)b * (p.d.T + 1) + t;
+  const double* w = p.sl.weight + bt1 * n;
+  const double* lo = p.sl.lo + bt1 * n;
+  const double* hi = p.sl.hi + bt1 * n;
+  double s = 0;
+  if (live)
+    for (int i = r0 + h; i < n; i += NH) {
+      const double wi = w[i];
+      if (wi == 0.0) continue;
+      const double e = limit_excess(x[limit_coord(i, nv, nq)], lo[i], hi[i]);
+      if (e != 0.0) s += wi * e * e;
+    }
+  double v = 0.5 * s;
+#pragma unroll
+  for (int k = NH / 2; k >= 1; k /= 2) v += __shfl_xor(v, k, NH);
+  return v;
+}
+
 // Latency path of the same rollouts (trees of the Talos size): one 64-lane workgroup (= one wave) per (instance, four
 // candidates), 16 lanes per candidate.  What a rollout waits for at every step is global memory: the 23 KB gain matrix K_t (written by the backward sweep a whole
 // linearisation ago: an HBM read in the middle of the step), k_t, u_old, x_old, and the per-level reads of the model tables
@@ -344,14 +392,15 @@ __device__ unsigned long long g_fwd_stamps[12];
 // rbd::aba_tree_coop2w's free-flyer form
 // TRACK: the tracking cost (DDP_HIP_FLAG_TRACKING_COST) of an unconstrained problem, formed inline by the 16 lanes of a candidate
 // (track_lanes_sum); an instantiation of its own, so that the kernel without it is the one it was
-// COST: bit 0 the tracking terms (TRACK above), bit 1 the frame terms (DDP_HIP_FLAG_FRAME_COST: frame_lanes_sum), each
-// combination an instantiation of its own as well
+// COST: bit 0 the tracking terms (TRACK above), bit 1 the frame terms (DDP_HIP_FLAG_FRAME_COST: frame_lanes_sum), bit 2 the
+// state-limit terms (DDP_HIP_FLAG_STATE_LIMITS: limit_lanes_sum, added after the other two), each combination an instantiation
+// of its own as well
 // BOX: control bounds (DDP_HIP_FLAG_CONTROL_BOUNDS): u is clamped to [lo_t, hi_t] after the control update; lo_t, hi_t ride in the
 // prefetch beside k_t.  Closed loop only, an instantiation of its own as well
 template <int NJ, bool OPEN = false, bool FF = false, int COST = 0, bool BOX = false>
 __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
   static_assert(!(OPEN && BOX), "the open-loop rollout applies U as given");
-  constexpr bool TRACK = (COST & 1) != 0, FRAME = (COST & 2) != 0;
+  constexpr bool TRACK = (COST & 1) != 0, FRAME = (COST & 2) != 0, LIMIT = (COST & 4) != 0;
   using L = typename std::conditional<BOX, FwdLat2LdsBox<NJ>, FwdLat2Lds<NJ>>::type;
   constexpr int NC = L::NC, NH = L::NH;
   constexpr int n = 2 * NJ, nq = FF ? NJ + 1 : NJ, nx = nq + NJ, nu = NJ, XS = L::n;   // XS: stride of a candidate's state in LDS
@@ -514,11 +563,12 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
     double c_track = 0.0;
     if constexpr (TRACK) c_track = track_lanes_sum<FF>(p, b, t, x, u, h, live);
     if constexpr (FRAME) c_track += frame_lanes_sum<FF>(p, S.model, b, t, x, h, live);
+    if constexpr (LIMIT) c_track += limit_lanes_sum<FF>(p, b, t, x, h, live);
     if (h == 0 && live && p.cost_inline) {
       double un = 0;
       for (int i = 0; i < nu; ++i) un += u[i] * u[i];
       double c_new = 0.5 * mc * un;                                             // problem_t::l (constrained problems: cand_cost_kernel)
-      if constexpr (TRACK || FRAME) c_new += c_track;
+      if constexpr (TRACK || FRAME || LIMIT) c_new += c_track;
       dsum += c_new - cold_t;
     }
     }
@@ -570,6 +620,7 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
   double c_term = 0.0;
   if constexpr (TRACK) { if (lead) c_term = track_lanes_sum<FF>(p, b, T, x, u, h, live); }
   if constexpr (FRAME) { if (lead) c_term += frame_lanes_sum<FF>(p, S.model, b, T, x, h, live); }
+  if constexpr (LIMIT) { if (lead) c_term += limit_lanes_sum<FF>(p, b, T, x, h, live); }
   if (!OPEN && h == 0 && live && lead && p.cost_inline) {
     dsum += c_term - cold[T];
     p.fw_dcost[(int64_t)b * na + a] = dsum;
@@ -579,7 +630,7 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
 // Constrained problems on the latency path.  Only the rollout is sequential in t; the cost terms of a rolled-out
 // candidate (cost_seq_aug, ddp.hpp:699-735: l + pe . ce + mu/2 |ce|^2, with ce_t = eq(t, x_t, u_t) two look-ahead dynamics steps
 // away, problem.hpp:563-567; lf at t = T) are independent across t: one lane per (instance, candidate, t), t = 0 .. T ...
-template <int NJ, bool FRAME = false>
+template <int NJ, bool FRAME = false, bool LIMIT = false>
 __global__ void cand_cost_kernel(FwdParams p) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t T = p.d.T;
@@ -595,10 +646,10 @@ __global__ void cand_cost_kernel(FwdParams p) {
   double x[2 * NJ + 1], u[NJ];
   for (int i = 0; i < nx; ++i) x[i] = xs[i];
   double* out = p.fw_cost + ((int64_t)b * na + a) * (T + 1) + t;
-  if (t == T) { *out = terminal_cost<FRAME>(p, m, b, x); return; }
+  if (t == T) { *out = terminal_cost<FRAME, LIMIT>(p, m, b, x); return; }
   const double* us = p.fw_u + (((int64_t)b * na + a) * T + t) * nu;
   for (int i = 0; i < nu; ++i) u[i] = us[i];
-  *out = stage_cost<NJ, FRAME>(p, m, b, t, x, u, p.mu[b]);
+  *out = stage_cost<NJ, FRAME, LIMIT>(p, m, b, t, x, u, p.mu[b]);
 }
 // ... and one lane per (instance, candidate) adds the differences up in the order of forward_kernel (ddp_fwd.ipp:54-56)
 __global__ void cand_sum_kernel(FwdParams p) {
@@ -685,6 +736,7 @@ FwdParams make_params(ddp_hip_ctx* ctx) {
   p.fw_cost = ctx->fw_cost;
   p.ctrl_lo = S(DDP_HIP_SEQ_CTRL_LO); p.ctrl_hi = S(DDP_HIP_SEQ_CTRL_HI);
   p.fc = frame_cost_dev(ctx);
+  p.sl = state_limits_dev(ctx);
   p.round = 0;
   return p;
 }
@@ -693,10 +745,12 @@ FwdParams make_params(ddp_hip_ctx* ctx) {
 using Lat2Fn = void (*)(FwdParams);
 Lat2Fn lat2_kernel(bool ff, int cost, bool box) {
 #define LAT2_ROW(FF, COST) {&forward_kernel_lat2<38, false, FF, COST, false>, &forward_kernel_lat2<38, false, FF, COST, true>}
-  static const Lat2Fn table[2][4][2] = {{LAT2_ROW(false, 0), LAT2_ROW(false, 1), LAT2_ROW(false, 2), LAT2_ROW(false, 3)},
-                                        {LAT2_ROW(true, 0), LAT2_ROW(true, 1), LAT2_ROW(true, 2), LAT2_ROW(true, 3)}};
+  static const Lat2Fn table[2][8][2] = {{LAT2_ROW(false, 0), LAT2_ROW(false, 1), LAT2_ROW(false, 2), LAT2_ROW(false, 3),
+                                         LAT2_ROW(false, 4), LAT2_ROW(false, 5), LAT2_ROW(false, 6), LAT2_ROW(false, 7)},
+                                        {LAT2_ROW(true, 0), LAT2_ROW(true, 1), LAT2_ROW(true, 2), LAT2_ROW(true, 3),
+                                         LAT2_ROW(true, 4), LAT2_ROW(true, 5), LAT2_ROW(true, 6), LAT2_ROW(true, 7)}};
 #undef LAT2_ROW
-  return table[ff ? 1 : 0][cost & 3][box ? 1 : 0];
+  return table[ff ? 1 : 0][cost & 7][box ? 1 : 0];
 }
 
 #define DISPATCH_NJ(nv, CALL)                 \
@@ -738,9 +792,11 @@ int fwd_setup(ddp_hip_ctx* ctx) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     // the closed-loop instantiations this context's flags can reach (lat2_kernel)
     const bool frame = (ctx->flags & DDP_HIP_FLAG_FRAME_COST) != 0, bounds = (ctx->flags & DDP_HIP_FLAG_CONTROL_BOUNDS) != 0;
+    const int costs = 1 | (frame ? 2 : 0) | ((ctx->flags & DDP_HIP_FLAG_STATE_LIMITS) ? 4 : 0);   // the COST bits this context can set
     for (int ff = 0; ff < 2; ++ff)
-      for (int cost = 0; cost < (frame ? 4 : 2); ++cost)
+      for (int cost = 0; cost < 8; ++cost)
         for (int box = 0; box < (bounds ? 2 : 1); ++box)
+          if (!(cost & ~costs))
           HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lat2_kernel(ff != 0, cost, box != 0)), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       box ? lds_box : lds));
   }
@@ -784,15 +840,24 @@ extern "C" int ddp_hip_rollout(ddp_hip_ctx* ctx) {
   return DDP_HIP_OK;
 }
 
+// the (FRAME, LIMIT) instantiation that the resident cost data asks for: frames with a non-zero weight, limits with one
+#define DISPATCH_COST(p, LAUNCH)                               \
+  do {                                                         \
+    const bool fr_ = (p).fc.target != nullptr, li_ = (p).sl.weight != nullptr; \
+    if (fr_ && li_) LAUNCH(true, true);                        \
+    else if (li_) LAUNCH(false, true);                         \
+    else if (fr_) LAUNCH(true, false);                         \
+    else LAUNCH(false, false);                                 \
+  } while (0)
+
 static int launch_cost(ddp_hip_ctx* ctx, FwdParams& p, int which) {
   const int bs = 64;
   const int64_t total = ctx->d.batch * (ctx->d.T + 1);
   const unsigned grid = (unsigned)((total + bs - 1) / bs);
-#define CALL(NJ) hipLaunchKernelGGL((cost_kernel<NJ>), dim3(grid), dim3(bs), 0, ctx->stream, p, which)
-#define CALL_FRAME(NJ) hipLaunchKernelGGL((cost_kernel<NJ, true>), dim3(grid), dim3(bs), 0, ctx->stream, p, which)
-  if (p.fc.target) DISPATCH_NJ(ctx->d.nv, CALL_FRAME);
-  else DISPATCH_NJ(ctx->d.nv, CALL);
-#undef CALL_FRAME
+#define CALL(NJ) hipLaunchKernelGGL((cost_kernel<NJ, FR, LI>), dim3(grid), dim3(bs), 0, ctx->stream, p, which)
+#define LAUNCH(F, L) do { constexpr bool FR = F, LI = L; DISPATCH_NJ(ctx->d.nv, CALL); } while (0)
+  DISPATCH_COST(p, LAUNCH);
+#undef LAUNCH
 #undef CALL
   HIP_TRY(hipGetLastError());
   return DDP_HIP_OK;
@@ -838,22 +903,22 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
     const bool lat_path = fwd_lat_supported(ctx) && n_alpha <= 8;
     if (lat_path) {
       const dim3 g((unsigned)(2 * B)), blk(128);
-      // the cost terms an unconstrained problem forms inline: bit 0 tracking, bit 1 frames (forward_kernel_lat2: COST)
-      const int cost = p.cost_inline ? (p.track ? 1 : 0) | (p.fc.target ? 2 : 0) : 0;
+      // the cost terms an unconstrained problem forms inline: bit 0 tracking, bit 1 frames, bit 2 state limits (forward_kernel_lat2: COST)
+      const int cost = p.cost_inline ? (p.track ? 1 : 0) | (p.fc.target ? 2 : 0) | (p.sl.weight ? 4 : 0) : 0;
       const bool box = p.ctrl_lo != nullptr;
       hipLaunchKernelGGL(lat2_kernel(ctx->model_h.ff != 0, cost, box), g, blk, box ? sizeof(FwdLat2LdsBox<38>) : sizeof(FwdLat2Lds<38>), ctx->stream, p);
       if (!p.cost_inline) {
         const dim3 gc((unsigned)((B * n_alpha * (d.T + 1) + 63) / 64));
-        if (p.fc.target) hipLaunchKernelGGL((cand_cost_kernel<38, true>), gc, dim3(64), 0, ctx->stream, p);
-        else hipLaunchKernelGGL((cand_cost_kernel<38>), gc, dim3(64), 0, ctx->stream, p);
+#define LAUNCH(F, L) hipLaunchKernelGGL((cand_cost_kernel<38, F, L>), gc, dim3(64), 0, ctx->stream, p)
+        DISPATCH_COST(p, LAUNCH);
+#undef LAUNCH
         hipLaunchKernelGGL(cand_sum_kernel, dim3((unsigned)((B * n_alpha + 63) / 64)), dim3(64), 0, ctx->stream, p);
       }
     } else {
-#define CALL(NJ) hipLaunchKernelGGL((forward_kernel<NJ>), dim3(grid), dim3(bs), 0, ctx->stream, p)
-#define CALL_FRAME(NJ) hipLaunchKernelGGL((forward_kernel<NJ, true>), dim3(grid), dim3(bs), 0, ctx->stream, p)
-      if (p.fc.target) DISPATCH_NJ(d.nv, CALL_FRAME);
-      else DISPATCH_NJ(d.nv, CALL);
-#undef CALL_FRAME
+#define CALL(NJ) hipLaunchKernelGGL((forward_kernel<NJ, FR, LI>), dim3(grid), dim3(bs), 0, ctx->stream, p)
+#define LAUNCH(F, L) do { constexpr bool FR = F, LI = L; DISPATCH_NJ(d.nv, CALL); } while (0)
+      DISPATCH_COST(p, LAUNCH);
+#undef LAUNCH
 #undef CALL
     }
     prof_end(ctx, DDP_HIP_K_FWD_ROLLOUT);

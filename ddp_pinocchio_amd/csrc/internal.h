@@ -246,6 +246,10 @@ struct ddp_hip_ctx {
   double* fc_weight_d = nullptr;
   bool fc_live = false;                       // some non-zero weight was uploaded since the frames were set: the kernels form the terms
 
+  // soft state limits (DDP_HIP_FLAG_STATE_LIMITS; ctx.hip: ddp_hip_state_limits_*, state_limits.h)
+  double* sl_d = nullptr;                     // lo | hi | weight, each [batch][T+1][n]
+  bool sl_live = false;                       // some non-zero weight was uploaded: the kernels form the terms
+
   bool box_dirty = false;       // CTRL_LO / CTRL_HI were uploaded since lo <= hi was last checked (ctx.hip: box_check)
 
   bool async_mode = false;     // ddp_hip_set_async: entry points that hand nothing back to the host do not wait for the stream

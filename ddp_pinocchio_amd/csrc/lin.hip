@@ -18,6 +18,7 @@
 #include "lin_common.h"
 #include "rbd.h"
 #include "rbd_deriv.h"
+#include "state_limits.h"
 
 namespace {
 
@@ -161,6 +162,34 @@ __global__ __launch_bounds__(64) void lin_frame_cost_kernel(LinParams p, FrameCo
           if (s_w[f][a] != 0.0) h += s_P[f][3 * lo + a] * s_w[f][a] * s_P[f][3 * hi + a];
       }
     if (hit) gxx[i + (int64_t)j * n] += h;
+  }
+}
+
+// Soft state limits (DDP_HIP_FLAG_STATE_LIMITS, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after lin_cost_kernel /
+// lin_track_cost_kernel and lin_frame_cost_kernel on the same stream: their output is the starting point.  Lane i takes the
+// tangent rows i, i + 64, ...; a row of weight 0 reads neither bound, and only a violated row (e != 0) is touched:
+//   lx[i] += w_i e_i,   lxx[i][i] += w_i
+// Nothing else is read or written (a diagonal entry: the block stays symmetric).  Rows 0 .. 5 of a free-flyer root carry no
+// limit.  t = T: lfx / lfxx
+__global__ __launch_bounds__(64) void lin_limit_cost_kernel(LinParams p, StateLimitsDev sl) {
+  const int64_t T = p.d.T;
+  const int64_t bt1 = blockIdx.x;
+  const int b = (int)(bt1 / (T + 1));
+  const int64_t t = bt1 % (T + 1);
+  const int n = (int)p.d.n, nv = (int)p.d.nv, nx = (int)p.d.nx, nq = nx - nv;
+  const double* x = p.x + bt1 * nx;
+  const double* w = sl.weight + bt1 * n;
+  const double* lo = sl.lo + bt1 * n;
+  const double* hi = sl.hi + bt1 * n;
+  double* gx = t < T ? p.lx + ((int64_t)b * T + t) * n : p.lfx + (int64_t)b * n;
+  double* gxx = t < T ? p.lxx + ((int64_t)b * T + t) * n * n : p.lfxx + (int64_t)b * n * n;
+  for (int i = (nx > n ? 6 : 0) + threadIdx.x; i < n; i += blockDim.x) {
+    const double wi = w[i];
+    if (wi == 0.0) continue;
+    const double e = limit_excess(x[limit_coord(i, nv, nq)], lo[i], hi[i]);
+    if (e == 0.0) continue;
+    gx[i] += wi * e;
+    gxx[i + (int64_t)i * n] += wi;
   }
 }
 
@@ -961,6 +990,8 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     else hipLaunchKernelGGL(lin_cost_kernel, dim3((unsigned)BT), dim3(64), 0, ctx->stream, p);
     const FrameCostDev fc = frame_cost_dev(ctx);
     if (fc.target) hipLaunchKernelGGL(lin_frame_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, fc);
+    const StateLimitsDev sl = state_limits_dev(ctx);
+    if (sl.weight) hipLaunchKernelGGL(lin_limit_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, sl);
   }
   // the q- / v-caches of the mode-2 stencil also serve the first order (base configuration and base (q, v)), so they are built
   // ahead of whichever stage comes first

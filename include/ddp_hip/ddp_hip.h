@@ -174,6 +174,25 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * flag. */
 #define DDP_HIP_FLAG_FRAME_COST 16u
 #define DDP_HIP_MAX_COST_FRAMES 4
+/* Carry, per instance b, t = 0 .. T and tangent row i = 0 .. n-1 (n = 2 nv: configuration rows 0 .. nv-1, velocity rows
+ * nv .. 2nv-1), a lower bound lo, an upper bound hi and a weight w >= 0, and add the soft limit (a one-sided quadratic penalty
+ * on the amount by which a state coordinate leaves [lo, hi]) to whatever the context optimises otherwise.  With s_i(x) the
+ * state coordinate of row i (x[i + nq - nv] for i < nv, else x[nq + i - nv]):
+ *   e_i = s_i < lo_i ? s_i - lo_i : (s_i > hi_i ? s_i - hi_i : 0)
+ *   l(t, x, u) += 1/2 sum_i w[b][t][i] e_i^2      t < T
+ *   lf(x_T)    += 1/2 sum_i w[b][T][i] e_i^2
+ * Derivatives in the tangent at x, for the rows with w_i != 0 and e_i != 0 only:
+ *   lx[i] += w_i e_i,  lxx[i][i] += w_i,  lfx / lfxx alike at T;
+ * lu, luu, lux and the off-diagonal entries are untouched.  The Hessian is exact wherever the cost is twice differentiable
+ * and positive semidefinite.  -inf / +inf: no bound on that side.  At create lo = -inf, hi = +inf, w = 0.  A term with w = 0
+ * or e = 0 is left out (not multiplied by 0), and a row of weight 0 reads neither bound.  Tangent rows 0 .. 5 of a free-flyer
+ * root are a pose on SE(3) and carry no limit; its six velocity rows and every 1-DoF joint's rows are ordinary rows.  The
+ * pendulum is supported.  The data travels through ddp_hip_state_limits_* below, not through ddp_hip_upload; an upload is refused
+ * (DDP_HIP_E_ARG, nothing written) for a NaN, a lo of +inf, a hi of -inf, a negative or non-finite weight, a non-zero weight on rows
+ * 0 .. 5 of a free-flyer model and lo > hi.  Two exactness properties: with nothing uploaded or every weight 0, and with
+ * non-zero weights and bounds that neither the trajectory nor any line-search candidate violates, a context computes bit for
+ * bit what it computes without the flag. */
+#define DDP_HIP_FLAG_STATE_LIMITS 32u
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -206,6 +225,13 @@ int ddp_hip_fill(ddp_hip_ctx* ctx, int seq, double value);
 int ddp_hip_frame_cost_set_frames(ddp_hip_ctx* ctx, int32_t n_frames, const int32_t* joint, const double* off);
 int ddp_hip_frame_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first_instance, int64_t n_instances);
 int ddp_hip_frame_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first_instance, int64_t n_instances);
+/* The state limits of a context created with DDP_HIP_FLAG_STATE_LIMITS (else DDP_HIP_E_UNSUPPORTED), stream-ordered like
+ * ddp_hip_frame_cost_upload.  Host arrays [n_instances][T+1][n]; a NULL pointer leaves that side as it is; a bad instance range
+ * is DDP_HIP_E_ARG.  An upload is refused as a whole (DDP_HIP_E_ARG, nothing written) for the values listed at the flag;
+ * lo <= hi is checked inside the upload, a side that arrives alone against the resident other side. */
+int ddp_hip_state_limits_upload(ddp_hip_ctx* ctx, const double* lo, const double* hi, const double* weight, int64_t first_instance,
+                                int64_t n_instances);
+int ddp_hip_state_limits_download(ddp_hip_ctx* ctx, double* lo, double* hi, double* weight, int64_t first_instance, int64_t n_instances);
 
 /* make_trajectory (ddp.hpp:392-415): X[0] and U given -> X[1..T] */
 int ddp_hip_rollout(ddp_hip_ctx* ctx);
