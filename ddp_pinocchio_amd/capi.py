@@ -26,6 +26,7 @@ JOINT_REVOLUTE, JOINT_PRISMATIC, JOINT_FREEFLYER = 0, 1, 2
 FLAG_NO_TENSORS, FLAG_TRACE, FLAG_TRACKING_COST, FLAG_CONTROL_BOUNDS = 1, 2, 4, 8
 FLAG_FRAME_COST = 16
 FLAG_STATE_LIMITS = 32
+FLAG_FRAME_ORIENT_COST = 64
 MAX_COST_FRAMES = 4
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
 
@@ -56,6 +57,7 @@ EXPORTS = [
     "ddp_hip_batch", "ddp_hip_set_active", "ddp_hip_solve", "ddp_hip_ctx_info",
     "ddp_hip_model_create", "ddp_hip_model_destroy", "ddp_hip_model_aba", "ddp_hip_model_aba_derivatives", "ddp_hip_model_frame",
     "ddp_hip_frame_cost_set_frames", "ddp_hip_frame_cost_upload", "ddp_hip_frame_cost_download",
+    "ddp_hip_frame_orient_upload", "ddp_hip_frame_orient_download",
     "ddp_hip_state_limits_upload", "ddp_hip_state_limits_download",
 ]
 
@@ -140,6 +142,9 @@ def lib():
         L.ddp_hip_frame_cost_set_frames.argtypes = [C.c_void_p, C.c_int32, _ip, _dp]
         L.ddp_hip_frame_cost_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_frame_cost_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+    if hasattr(L, "ddp_hip_frame_orient_upload"):    # (likewise: set_frame_orient_cost fails on an older build)
+        L.ddp_hip_frame_orient_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_frame_orient_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
     if hasattr(L, "ddp_hip_state_limits_upload"):    # (likewise: set_state_limits fails on an older build)
         L.ddp_hip_state_limits_upload.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_state_limits_download.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int64]
@@ -462,6 +467,38 @@ class Context:
         t, w = np.zeros(shape), np.zeros(shape)
         _check(lib().ddp_hip_frame_cost_download(self._h, _ptr(t), _ptr(w), first, count), "frame_cost_download")
         return t, w
+
+    def set_frame_orient_cost(self, quat=None, weight=None, first=0, count=None):
+        """The orientation terms of the cost frames (a context created with FLAG_FRAME_COST | FLAG_FRAME_ORIENT_COST, frames
+        set through set_frame_cost; ddp_hip.h).  quat: reference rotations as unit quaternions (x y z w), weight: per axis of
+        the frame, >= 0; of instances first .. first + count - 1: (T+1, F, 4) / (T+1, F, 3) for every instance of the range or
+        (count, T+1, F, .) with one per instance; weight also takes (F, 3), (3,) and scalars by broadcast.  None leaves that
+        side as it is."""
+        count = self.batch - first if count is None else count
+        arrs = {}
+        for name, arr, k in (("quat", quat, 4), ("weight", weight, 3)):
+            if arr is None:
+                continue
+            per = (self.spec.T + 1, self.n_cost_frames, k)
+            full = (count,) + per
+            arr = np.asarray(arr, dtype=np.float64)
+            if not (arr.shape in (full, per) or (name == "weight" and arr.shape in (per[1:], per[2:], ()))):
+                raise ValueError(f"set_frame_orient_cost {name}: shape {arr.shape}, expected {per} or {full}")
+            arrs[name] = np.ascontiguousarray(np.broadcast_to(arr, full))
+        if "quat" in arrs and not bool(np.all(np.abs(np.sqrt(np.sum(arrs["quat"] ** 2, axis=-1)) - 1.0) <= 1e-10)):
+            raise ValueError("set_frame_orient_cost quat: every quaternion has unit norm (to 1e-10)")
+        if arrs:
+            q, w = arrs.get("quat"), arrs.get("weight")
+            _check(lib().ddp_hip_frame_orient_upload(self._h, _ptr(q) if q is not None else None, _ptr(w) if w is not None else None,
+                                                     first, count), "frame_orient_upload")
+
+    def frame_orient_cost(self, first=0, count=None):
+        """(quat, weight) of instances first .. first + count - 1: (count, T+1, F, 4) and (count, T+1, F, 3)"""
+        count = self.batch - first if count is None else count
+        q = np.zeros((count, self.spec.T + 1, self.n_cost_frames, 4))
+        w = np.zeros((count, self.spec.T + 1, self.n_cost_frames, 3))
+        _check(lib().ddp_hip_frame_orient_download(self._h, _ptr(q), _ptr(w), first, count), "frame_orient_download")
+        return q, w
 
     def set_state_limits(self, lo=None, hi=None, weight=None, first=0, count=None):
         """The soft state limits of instances first .. first + count - 1 (a context created with FLAG_STATE_LIMITS; ddp_hip.h),

@@ -237,6 +237,18 @@ static DevSwitches read_switches() {
   return sw;
 }
 
+// the orientation data as it is at create: every quaternion (0, 0, 0, 1), every weight 0, the terms off
+static int frame_orient_reset(ddp_hip_ctx* ctx) {
+  const int64_t slots = ctx->d.batch * (ctx->d.T + 1) * DDP_HIP_MAX_COST_FRAMES;
+  std::vector<double> qt((size_t)(slots * 4), 0.0);
+  for (size_t k = 3; k < qt.size(); k += 4) qt[k] = 1.0;
+  HIP_TRY(hipMemcpyAsync(ctx->fo_quat_d, qt.data(), sizeof(double) * qt.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemsetAsync(ctx->fo_weight_d, 0, sizeof(double) * (size_t)(slots * 3), ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ctx->fo_live = false;
+  return DDP_HIP_OK;
+}
+
 extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t flags, ddp_hip_ctx** out) {
   if (!prob || !out) return DDP_HIP_E_ARG;
   *out = nullptr;
@@ -246,6 +258,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   if (mo.kind == DDP_HIP_MODEL_PENDULUM && mo.nv != 1) return DDP_HIP_E_ARG;
   if (prob->fd_mode < 0 || prob->fd_mode > 2) return DDP_HIP_E_ARG;
   if ((flags & DDP_HIP_FLAG_FRAME_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // frames are points of a tree's joints
+  if ((flags & DDP_HIP_FLAG_FRAME_ORIENT_COST) && !(flags & DDP_HIP_FLAG_FRAME_COST)) return DDP_HIP_E_ARG;   // the orientation terms are of the cost frames
   if (prob->eq_kind != DDP_HIP_EQ_NONE && (!prob->ne || prob->eq_advance < 0 || prob->eq_advance > 4)) return DDP_HIP_E_ARG;
   if (prob->eq_kind == DDP_HIP_EQ_FRAME && (mo.kind != DDP_HIP_MODEL_TREE || prob->frame_joint < 0 ||
                                             prob->frame_joint >= (mo.jtype && mo.jtype[0] == DDP_HIP_JOINT_FREEFLYER ? mo.nv - 5 : mo.nv)))
@@ -353,6 +366,13 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipMemsetAsync(ctx->fc_target_d, 0, sizeof(double) * words, ctx->stream));
     CTX_TRY(hipMemsetAsync(ctx->fc_weight_d, 0, sizeof(double) * words, ctx->stream));
   }
+  if (flags & DDP_HIP_FLAG_FRAME_ORIENT_COST) {
+    // identity quaternions (a zero-filled one has no rotation) and weights 0
+    const int64_t slots = d.batch * (d.T + 1) * DDP_HIP_MAX_COST_FRAMES;
+    CTX_TRY(hipMalloc(&ctx->fo_quat_d, sizeof(double) * (size_t)(slots * 4)));
+    CTX_TRY(hipMalloc(&ctx->fo_weight_d, sizeof(double) * (size_t)(slots * 3)));
+    if (frame_orient_reset(ctx) != DDP_HIP_OK) { ddp_hip_destroy(ctx); return DDP_HIP_E_HIP; }
+  }
   if (flags & DDP_HIP_FLAG_STATE_LIMITS) {
     // lo = -inf, hi = +inf, w = 0: no limit anywhere
     const int64_t words = d.batch * (d.T + 1) * d.n;
@@ -384,6 +404,8 @@ extern "C" int ddp_hip_destroy(ddp_hip_ctx* ctx) {
     if (ctx->seq[s].ptr) (void)hipFree(ctx->seq[s].ptr);
   if (ctx->fc_target_d) (void)hipFree(ctx->fc_target_d);
   if (ctx->fc_weight_d) (void)hipFree(ctx->fc_weight_d);
+  if (ctx->fo_quat_d) (void)hipFree(ctx->fo_quat_d);
+  if (ctx->fo_weight_d) (void)hipFree(ctx->fo_weight_d);
   if (ctx->sl_d) (void)hipFree(ctx->sl_d);
   if (ctx->ne_d) (void)hipFree(ctx->ne_d);
   if (ctx->Epre_d) (void)hipFree(ctx->Epre_d);
@@ -525,6 +547,7 @@ extern "C" int ddp_hip_frame_cost_set_frames(ddp_hip_ctx* ctx, int32_t n_frames,
     HIP_TRY(hipMemsetAsync(ctx->fc_target_d, 0, sizeof(double) * words, ctx->stream));
     HIP_TRY(hipMemsetAsync(ctx->fc_weight_d, 0, sizeof(double) * words, ctx->stream));
     ctx->fc_live = false;
+    if (ctx->flags & DDP_HIP_FLAG_FRAME_ORIENT_COST) { const int rc_ = frame_orient_reset(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
   }
   ctx->fc_nf = n_frames;
   for (int f = 0; f < n_frames; ++f) {
@@ -574,6 +597,52 @@ extern "C" int ddp_hip_frame_cost_download(ddp_hip_ctx* ctx, double* target, dou
   HIP_TRY(hipSetDevice(ctx->device));
   if (target) HIP_TRY(hipMemcpyAsync(target, ctx->fc_target_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
   if (weight) HIP_TRY(hipMemcpyAsync(weight, ctx->fc_weight_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return DDP_HIP_OK;
+}
+
+// ---- frame-orientation cost (DDP_HIP_FLAG_FRAME_ORIENT_COST): reference rotations and weights of the cost frames ----------
+static int frame_orient_range(ddp_hip_ctx* ctx, int64_t first, int64_t count) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_FRAME_ORIENT_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (first < 0 || count < 0 || first + count > ctx->d.batch) return DDP_HIP_E_ARG;
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_frame_orient_upload(ddp_hip_ctx* ctx, const double* quat, const double* weight, int64_t first, int64_t count) {
+  int rc = frame_orient_range(ctx, first, count);
+  if (rc != DDP_HIP_OK) return rc;
+  if (ctx->fc_nf == 0) return DDP_HIP_E_ARG;                // no frames set: the arrays have no shape yet
+  const int64_t slots = (ctx->d.T + 1) * ctx->fc_nf;
+  bool nonzero = false;
+  if (quat)
+    for (int64_t k = 0; k < slots * count; ++k) {
+      const double* qt = quat + 4 * k;
+      if (!cost_quat_ok(qt[0] * qt[0] + qt[1] * qt[1] + qt[2] * qt[2] + qt[3] * qt[3])) return DDP_HIP_E_ARG;   // (a non-finite entry fails it too)
+    }
+  if (weight)
+    for (int64_t i = 0; i < slots * 3 * count; ++i) {
+      if (!cost_weight_ok(weight[i])) return DDP_HIP_E_ARG;
+      nonzero |= weight[i] != 0.0;
+    }
+  if (count == 0 || (!quat && !weight)) return DDP_HIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (quat) HIP_TRY(hipMemcpyAsync(ctx->fo_quat_d + first * slots * 4, quat, sizeof(double) * (size_t)(slots * 4 * count), hipMemcpyHostToDevice, ctx->stream));
+  if (weight) HIP_TRY(hipMemcpyAsync(ctx->fo_weight_d + first * slots * 3, weight, sizeof(double) * (size_t)(slots * 3 * count), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  // as fc_live: any non-zero weight switches the terms on, only ONE upload of zeros for the whole batch switches them off again
+  if (weight) ctx->fo_live = nonzero || (ctx->fo_live && !(first == 0 && count == ctx->d.batch));
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_frame_orient_download(ddp_hip_ctx* ctx, double* quat, double* weight, int64_t first, int64_t count) {
+  int rc = frame_orient_range(ctx, first, count);
+  if (rc != DDP_HIP_OK) return rc;
+  const int64_t slots = (ctx->d.T + 1) * ctx->fc_nf;
+  if (slots == 0 || count == 0 || (!quat && !weight)) return DDP_HIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (quat) HIP_TRY(hipMemcpyAsync(quat, ctx->fo_quat_d + first * slots * 4, sizeof(double) * (size_t)(slots * 4 * count), hipMemcpyDeviceToHost, ctx->stream));
+  if (weight) HIP_TRY(hipMemcpyAsync(weight, ctx->fo_weight_d + first * slots * 3, sizeof(double) * (size_t)(slots * 3 * count), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return DDP_HIP_OK;
 }

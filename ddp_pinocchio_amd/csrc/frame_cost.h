@@ -1,14 +1,17 @@
-// frame_cost.h -- per-instance frame-position costs (DDP_HIP_FLAG_FRAME_COST, ddp_hip.h): the kernel-side description and
-// the two traversals they need.  The terms themselves are formed in fwd.hip (cost values) and lin.hip (derivatives).
+// frame_cost.h -- per-instance frame-position costs (DDP_HIP_FLAG_FRAME_COST, ddp_hip.h) and frame-orientation costs
+// (DDP_HIP_FLAG_FRAME_ORIENT_COST): the kernel-side description and the traversals they need.  The terms themselves are formed
+// in fwd.hip (cost values) and lin.hip (derivatives).
 #pragma once
 #include "internal.h"
 #include "lie.h"
 #include "rbd.h"
 
 // What a kernel reads of the context's frame cost.  target == nullptr: no terms (the flag is off, no frames are set, or no
-// non-zero weight has been uploaded since the frames were set)
+// non-zero weight has been uploaded since the frames were set).  oquat == nullptr: no orientation terms, alike (fo_live); the
+// two sides are independent, and nf / joint are filled when either is live
 struct FrameCostDev {
   const double *target, *weight;   // [batch][T+1][nf][3]
+  const double *oquat, *oweight;   // [batch][T+1][nf][4] (unit quaternions x y z w), [batch][T+1][nf][3]
   int32_t nf, pad_;
   int32_t joint[DDP_HIP_MAX_COST_FRAMES];
   double off[DDP_HIP_MAX_COST_FRAMES][3];
@@ -16,8 +19,9 @@ struct FrameCostDev {
 
 inline FrameCostDev frame_cost_dev(const ddp_hip_ctx* ctx) {
   FrameCostDev f{};
-  if (!ctx->fc_live) return f;
-  f.target = ctx->fc_target_d; f.weight = ctx->fc_weight_d;
+  if (!ctx->fc_live && !ctx->fo_live) return f;
+  if (ctx->fc_live) { f.target = ctx->fc_target_d; f.weight = ctx->fc_weight_d; }
+  if (ctx->fo_live) { f.oquat = ctx->fo_quat_d; f.oweight = ctx->fo_weight_d; }
   f.nf = ctx->fc_nf;
   for (int k = 0; k < ctx->fc_nf; ++k) {
     f.joint[k] = ctx->fc_joint[k];
@@ -63,6 +67,45 @@ __device__ __forceinline__ void frame_point(const M& m, bool ff, int joint, cons
 
 // a term of weight 0 is left out, and with all three of a frame the walk itself
 __device__ __forceinline__ bool frame_weights_any(const double* w) { return w[0] != 0.0 || w[1] != 0.0 || w[2] != 0.0; }
+
+// World rotation R (row-major, world = R body) of joint `joint`'s frame, walking joint -> root like frame_point with the three
+// columns R e_a alone: c <- Rp (R_axis(q_i) c) for a revolute joint, Rp c for a prismatic one, R(quat) c for a free-flyer root.
+// M: DevModel or CoopModel (the tables in LDS)
+template <class M>
+__device__ __forceinline__ void frame_rotation(const M& m, bool ff, int joint, const double* q, double* R) {
+  double c[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+  for (int j = joint; j >= 0; j = m.parent[j]) {
+    double w[3];
+    if (j == 0 && ff) {
+      double Rq[9];
+      lie::quat_to_R(q + 3, Rq);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { mv3(Rq, c[k], w); c[k][0] = w[0]; c[k][1] = w[1]; c[k][2] = w[2]; }
+      break;
+    }
+    if (m.jtype[j] == DDP_HIP_JOINT_REVOLUTE) {
+      const double* a = m.axis[j];
+      double s, cs;
+      sincos(q[ff ? j + 6 : j], &s, &cs);
+      const double omc = 1.0 - cs;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        double av[3], aav[3];
+        cross3(a, c[k], av);
+        cross3(a, av, aav);
+        w[0] = c[k][0] + (s * av[0] + omc * aav[0]); w[1] = c[k][1] + (s * av[1] + omc * aav[1]); w[2] = c[k][2] + (s * av[2] + omc * aav[2]);
+        mv3(m.Rp[j], w, c[k]);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { mv3(m.Rp[j], c[k], w); c[k][0] = w[0]; c[k][1] = w[1]; c[k][2] = w[2]; }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) R[3 * r + k] = c[k][r];
+}
 
 // The frame's world position p and its true point jacobian P = dp / d(delta q) (3 x nv, stored at P[3 * column + row]; only
 // the columns of the joints on the path root .. joint are written, their tangent indices are returned as a bit mask):
@@ -115,6 +158,36 @@ __device__ inline unsigned long long frame_point_jacobian(const DevModel& m, int
       mask |= 1ull << vi;
     }
   }
+  return mask;
+}
+
+// The frame's world rotation R (row-major) and its world angular jacobian W = d(world rotation vector) / d(delta q) (3 x nv,
+// stored at W[3 * column + row]; only the columns that carry rotation are written, their tangent indices are returned as a bit
+// mask): the world axis a_i of a revolute joint i on the path root .. joint, R_0 e_c for the angular columns 3 .. 5 of a
+// free-flyer root; a prismatic joint and the root's linear columns 0 .. 2 have no column.  chain: room for the path
+__device__ inline unsigned long long frame_rotation_jacobian(const DevModel& m, int joint, const double* q, double* R, double* W, int* chain) {
+  int len = 0;
+  for (int j = joint; j >= 0; j = m.parent[j]) chain[len++] = j;
+  double oR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  unsigned long long mask = 0;
+  for (int c = len - 1; c >= 0; --c) {
+    const int i = chain[c];
+    double E[9], r[3], Rc[9], nR[9];
+    place(m, i, q, E, r);
+    for (int k = 0; k < 3; ++k)
+      for (int l = 0; l < 3; ++l) Rc[3 * k + l] = E[3 * l + k];
+    mm3(oR, Rc, nR);
+    for (int k = 0; k < 9; ++k) oR[k] = nR[k];
+    if (i == 0 && m.ff) {
+      for (int cc = 0; cc < 3; ++cc) { W[3 * (3 + cc)] = oR[cc]; W[3 * (3 + cc) + 1] = oR[3 + cc]; W[3 * (3 + cc) + 2] = oR[6 + cc]; }
+      mask |= 56ull;
+    } else if (m.jtype[i] == DDP_HIP_JOINT_REVOLUTE) {
+      const int vi = m.ff ? i + 5 : i;
+      mv3(oR, m.axis[i], W + 3 * vi);
+      mask |= 1ull << vi;
+    }
+  }
+  for (int k = 0; k < 9; ++k) R[k] = oR[k];
   return mask;
 }
 

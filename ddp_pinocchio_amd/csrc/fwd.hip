@@ -41,7 +41,8 @@ struct FwdParams {
   const double *xref, *wx, *uref, *wu;   // tracking cost (DDP_HIP_FLAG_TRACKING_COST), else null
   int32_t track;
   const double *ctrl_lo, *ctrl_hi;       // control bounds (DDP_HIP_FLAG_CONTROL_BOUNDS), else null
-  FrameCostDev fc;                       // frame-position cost (DDP_HIP_FLAG_FRAME_COST); fc.target null: no terms
+  FrameCostDev fc;                       // frame-position cost (DDP_HIP_FLAG_FRAME_COST); fc.target null: no terms; fc.oquat null: no
+                                         // orientation terms (DDP_HIP_FLAG_FRAME_ORIENT_COST)
   StateLimitsDev sl;                     // soft state limits (DDP_HIP_FLAG_STATE_LIMITS); sl.weight null: no terms
 };
 
@@ -118,6 +119,25 @@ __device__ double frame_cost_sum(const FrameCostDev& fc, const DevModel& m, int6
   return 0.5 * s;
 }
 
+// sum_a w_a e_a^2 of frame f at (instance, t) pair bt1, e = log3(R_ref^T R_f(q)) (ddp_hip.h: DDP_HIP_FLAG_FRAME_ORIENT_COST): a
+// sibling of frame_term.  A term of weight 0 is left out, and with all three of them the walk along the frame's path
+template <class M>
+__device__ __forceinline__ double frame_orient_term(const FrameCostDev& fc, const M& m, bool ff, int f, int64_t bt1, const double* q) {
+  const double* w = fc.oweight + (bt1 * fc.nf + f) * 3;
+  if (!rbd::frame_weights_any(w)) return 0.0;
+  double R[9], e[3], s = 0;
+  rbd::frame_rotation(m, ff, fc.joint[f], q, R);
+  lie::so3_log_rel(fc.oquat + (bt1 * fc.nf + f) * 4, R, e);
+  for (int a = 0; a < 3; ++a) if (w[a] != 0.0) s += w[a] * e[a] * e[a];
+  return s;
+}
+// the orientation terms of l at time t of instance b (t = T: of lf), one lane for all frames
+__device__ double frame_orient_sum(const FrameCostDev& fc, const DevModel& m, int64_t bt1, const double* x) {
+  double s = 0;
+  for (int f = 0; f < fc.nf; ++f) s += frame_orient_term(fc, m, m.ff != 0, f, bt1, x);
+  return 0.5 * s;
+}
+
 // 1/2 sum_i w_i e_i^2 over the tangent rows of the state at (instance, t) pair bt1, e_i the amount by which the row's state
 // coordinate leaves [lo_i, hi_i] (ddp_hip.h: DDP_HIP_FLAG_STATE_LIMITS): a sibling of track_state_sum, one lane, rows in order.
 // A row of weight 0 reads neither bound and a row inside its interval adds nothing: with limits that do not bind the sum is +0
@@ -137,17 +157,23 @@ __device__ __forceinline__ double limit_state_sum(const StateLimitsDev& sl, bool
 }
 
 // one term of cost_seq_aug (ddp.hpp:730): l + pe.ce + mu/2 |ce|^2
-// FRAME: + the frame terms (DDP_HIP_FLAG_FRAME_COST), in instantiations of their own of cost_kernel, forward_kernel and
-// cand_cost_kernel: a run-time branch here moved the spills of the kernels that exist without the flag
+// FRAME: a level -- 0 none, 1 + the frame-position terms (DDP_HIP_FLAG_FRAME_COST), 2 + the frame-orientation terms after them
+// (DDP_HIP_FLAG_FRAME_ORIENT_COST; the position side may be off there: fc.target null) -- in instantiations of their own of
+// cost_kernel, forward_kernel and cand_cost_kernel: a run-time branch here moved the spills of the kernels that exist without
+// the flag
 // LIMIT: + the state-limit terms (DDP_HIP_FLAG_STATE_LIMITS), after the frame terms, in instantiations of their own alike
-template <int NJ, bool FRAME = false, bool LIMIT = false>
+template <int NJ, int FRAME = 0, bool LIMIT = false>
 __device__ double stage_cost(const FwdParams& p, const DevModel& m, int b, int64_t t, const double* x, const double* u, double mu) {
   const int nv = m.nv, n = 2 * nv, nx = m.nq + nv;
   double un = 0;
   for (int i = 0; i < nv; ++i) un += u[i] * u[i];
   double cost = 0.5 * m.c * un;                                   // problem_t::l, problem.hpp:937-942
   if (p.track) cost += track_state_cost(p, b, t, x) + track_control_sum(p, b, t, u);   // + the tracking terms
-  if constexpr (FRAME) cost += frame_cost_sum(p.fc, m, (int64_t)b * (p.d.T + 1) + t, x);   // + the frame terms
+  if constexpr (FRAME == 1) cost += frame_cost_sum(p.fc, m, (int64_t)b * (p.d.T + 1) + t, x);   // + the frame terms
+  if constexpr (FRAME == 2) {
+    if (p.fc.target) cost += frame_cost_sum(p.fc, m, (int64_t)b * (p.d.T + 1) + t, x);
+    cost += frame_orient_sum(p.fc, m, (int64_t)b * (p.d.T + 1) + t, x);                   // + the frame-orientation terms
+  }
   if constexpr (LIMIT) cost += limit_state_sum(p.sl, m.ff != 0, nv, (int64_t)b * (p.d.T + 1) + t, x);   // + the state-limit terms
   const int e = (int)p.ne[t];
   if (e > 0) {
@@ -192,16 +218,20 @@ __global__ void rollout_kernel(FwdParams p) {
 }
 
 // problem_t::lf (problem.hpp:932-936: 0), or the tracking cost's terminal term
-template <bool FRAME = false, bool LIMIT = false>
+template <int FRAME = 0, bool LIMIT = false>
 __device__ __forceinline__ double terminal_cost(const FwdParams& p, const DevModel& m, int b, const double* x) {
   double cost = p.track ? track_state_cost(p, b, p.d.T, x) : 0.0;
-  if constexpr (FRAME) cost += frame_cost_sum(p.fc, m, (int64_t)b * (p.d.T + 1) + p.d.T, x);
+  if constexpr (FRAME == 1) cost += frame_cost_sum(p.fc, m, (int64_t)b * (p.d.T + 1) + p.d.T, x);
+  if constexpr (FRAME == 2) {
+    if (p.fc.target) cost += frame_cost_sum(p.fc, m, (int64_t)b * (p.d.T + 1) + p.d.T, x);
+    cost += frame_orient_sum(p.fc, m, (int64_t)b * (p.d.T + 1) + p.d.T, x);
+  }
   if constexpr (LIMIT) cost += limit_state_sum(p.sl, m.ff != 0, m.nv, (int64_t)b * (p.d.T + 1) + p.d.T, x);
   return cost;
 }
 
 // cost_seq_aug of one trajectory: one lane per (instance, t)
-template <int NJ, bool FRAME = false, bool LIMIT = false>
+template <int NJ, int FRAME = 0, bool LIMIT = false>
 __global__ void cost_kernel(FwdParams p, int which) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t T = p.d.T;
@@ -222,7 +252,7 @@ __global__ void cost_kernel(FwdParams p, int which) {
 
 // closed-loop rollouts (ddp_fwd.ipp:39-51) of n_alpha candidate steps per instance + their summed cost
 // difference (ddp_fwd.ipp:54-56)
-template <int NJ, bool FRAME = false, bool LIMIT = false>
+template <int NJ, int FRAME = 0, bool LIMIT = false>
 __global__ void forward_kernel(FwdParams p) {
   // the model table in LDS: the dynamics of every step read it joint by joint (axis, placement, inertia: some 40 words per joint
   // and evaluation), and from global memory each of those reads is a dependent L2 round trip of the one lane that rolls out
@@ -330,6 +360,24 @@ __device__ __forceinline__ double frame_lanes_sum(const FwdParams& p, const M& c
   return v;
 }
 
+// The frame terms of one candidate of a COST bit 3 instantiation: lane h < nf keeps frame h's position term as in
+// frame_lanes_sum (none while the position side is off: fc.target null), lane 4 + h forms frame h's orientation term
+// (frame_orient_term) from the same state and tables; the same fixed butterfly.  Every lane of the wave calls it
+template <bool FF, class M>
+__device__ __forceinline__ double frame_orient_lanes_sum(const FwdParams& p, const M& cm, int b, int64_t t, const double* x, int h, bool live) {
+  constexpr int NH = 16;
+  static_assert(2 * DDP_HIP_MAX_COST_FRAMES <= NH, "a lane per frame and kind of term");
+  double s = 0;
+  if (live) {
+    if (h < DDP_HIP_MAX_COST_FRAMES) { if (h < p.fc.nf && p.fc.target) s = frame_term(p.fc, cm, FF, h, (int64_t)b * (p.d.T + 1) + t, x); }
+    else if (h - DDP_HIP_MAX_COST_FRAMES < p.fc.nf) s = frame_orient_term(p.fc, cm, FF, h - DDP_HIP_MAX_COST_FRAMES, (int64_t)b * (p.d.T + 1) + t, x);
+  }
+  double v = 0.5 * s;
+#pragma unroll
+  for (int k = NH / 2; k >= 1; k /= 2) v += __shfl_xor(v, k, NH);
+  return v;
+}
+
 // The state-limit terms of one candidate of forward_kernel_lat2 at time t (t = T: lf): lane h takes the tangent rows r0 + h,
 // r0 + h + 16, ... (r0 = 6 on a free flyer, whose pose rows carry no limit), track_lanes_sum's split; a row of weight 0 reads
 // neither bound; the partial sums meet in the same fixed butterfly.  Every lane of the wave calls it
@@ -393,14 +441,16 @@ __device__ unsigned long long g_fwd_stamps[12];
 // TRACK: the tracking cost (DDP_HIP_FLAG_TRACKING_COST) of an unconstrained problem, formed inline by the 16 lanes of a candidate
 // (track_lanes_sum); an instantiation of its own, so that the kernel without it is the one it was
 // COST: bit 0 the tracking terms (TRACK above), bit 1 the frame terms (DDP_HIP_FLAG_FRAME_COST: frame_lanes_sum), bit 2 the
-// state-limit terms (DDP_HIP_FLAG_STATE_LIMITS: limit_lanes_sum, added after the other two), each combination an instantiation
-// of its own as well
+// state-limit terms (DDP_HIP_FLAG_STATE_LIMITS: limit_lanes_sum, added after the other two), bit 3 the frame-orientation terms
+// (DDP_HIP_FLAG_FRAME_ORIENT_COST: frame_orient_lanes_sum in the place of frame_lanes_sum; it implies bit 1), each combination an
+// instantiation of its own as well
 // BOX: control bounds (DDP_HIP_FLAG_CONTROL_BOUNDS): u is clamped to [lo_t, hi_t] after the control update; lo_t, hi_t ride in the
 // prefetch beside k_t.  Closed loop only, an instantiation of its own as well
 template <int NJ, bool OPEN = false, bool FF = false, int COST = 0, bool BOX = false>
 __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
   static_assert(!(OPEN && BOX), "the open-loop rollout applies U as given");
-  constexpr bool TRACK = (COST & 1) != 0, FRAME = (COST & 2) != 0, LIMIT = (COST & 4) != 0;
+  constexpr bool TRACK = (COST & 1) != 0, FRAME = (COST & 2) != 0, LIMIT = (COST & 4) != 0, ORIENT = (COST & 8) != 0;
+  static_assert(!ORIENT || FRAME, "the orientation terms are of the cost frames: bit 3 implies bit 1");
   using L = typename std::conditional<BOX, FwdLat2LdsBox<NJ>, FwdLat2Lds<NJ>>::type;
   constexpr int NC = L::NC, NH = L::NH;
   constexpr int n = 2 * NJ, nq = FF ? NJ + 1 : NJ, nx = nq + NJ, nu = NJ, XS = L::n;   // XS: stride of a candidate's state in LDS
@@ -562,7 +612,8 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
     FSTAMP(fs, 0);
     double c_track = 0.0;
     if constexpr (TRACK) c_track = track_lanes_sum<FF>(p, b, t, x, u, h, live);
-    if constexpr (FRAME) c_track += frame_lanes_sum<FF>(p, S.model, b, t, x, h, live);
+    if constexpr (FRAME && !ORIENT) c_track += frame_lanes_sum<FF>(p, S.model, b, t, x, h, live);
+    if constexpr (ORIENT) c_track += frame_orient_lanes_sum<FF>(p, S.model, b, t, x, h, live);
     if constexpr (LIMIT) c_track += limit_lanes_sum<FF>(p, b, t, x, h, live);
     if (h == 0 && live && p.cost_inline) {
       double un = 0;
@@ -619,7 +670,8 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
 #endif
   double c_term = 0.0;
   if constexpr (TRACK) { if (lead) c_term = track_lanes_sum<FF>(p, b, T, x, u, h, live); }
-  if constexpr (FRAME) { if (lead) c_term += frame_lanes_sum<FF>(p, S.model, b, T, x, h, live); }
+  if constexpr (FRAME && !ORIENT) { if (lead) c_term += frame_lanes_sum<FF>(p, S.model, b, T, x, h, live); }
+  if constexpr (ORIENT) { if (lead) c_term += frame_orient_lanes_sum<FF>(p, S.model, b, T, x, h, live); }
   if constexpr (LIMIT) { if (lead) c_term += limit_lanes_sum<FF>(p, b, T, x, h, live); }
   if (!OPEN && h == 0 && live && lead && p.cost_inline) {
     dsum += c_term - cold[T];
@@ -630,7 +682,7 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
 // Constrained problems on the latency path.  Only the rollout is sequential in t; the cost terms of a rolled-out
 // candidate (cost_seq_aug, ddp.hpp:699-735: l + pe . ce + mu/2 |ce|^2, with ce_t = eq(t, x_t, u_t) two look-ahead dynamics steps
 // away, problem.hpp:563-567; lf at t = T) are independent across t: one lane per (instance, candidate, t), t = 0 .. T ...
-template <int NJ, bool FRAME = false, bool LIMIT = false>
+template <int NJ, int FRAME = 0, bool LIMIT = false>
 __global__ void cand_cost_kernel(FwdParams p) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t T = p.d.T;
@@ -745,12 +797,17 @@ FwdParams make_params(ddp_hip_ctx* ctx) {
 using Lat2Fn = void (*)(FwdParams);
 Lat2Fn lat2_kernel(bool ff, int cost, bool box) {
 #define LAT2_ROW(FF, COST) {&forward_kernel_lat2<38, false, FF, COST, false>, &forward_kernel_lat2<38, false, FF, COST, true>}
-  static const Lat2Fn table[2][8][2] = {{LAT2_ROW(false, 0), LAT2_ROW(false, 1), LAT2_ROW(false, 2), LAT2_ROW(false, 3),
-                                         LAT2_ROW(false, 4), LAT2_ROW(false, 5), LAT2_ROW(false, 6), LAT2_ROW(false, 7)},
-                                        {LAT2_ROW(true, 0), LAT2_ROW(true, 1), LAT2_ROW(true, 2), LAT2_ROW(true, 3),
-                                         LAT2_ROW(true, 4), LAT2_ROW(true, 5), LAT2_ROW(true, 6), LAT2_ROW(true, 7)}};
+  // COST 8 .. 15: the orientation terms; bit 3 implies bit 1, so only 10, 11, 14 and 15 exist (slots 8 .. 11)
+  static const Lat2Fn table[2][12][2] = {{LAT2_ROW(false, 0), LAT2_ROW(false, 1), LAT2_ROW(false, 2), LAT2_ROW(false, 3),
+                                          LAT2_ROW(false, 4), LAT2_ROW(false, 5), LAT2_ROW(false, 6), LAT2_ROW(false, 7),
+                                          LAT2_ROW(false, 10), LAT2_ROW(false, 11), LAT2_ROW(false, 14), LAT2_ROW(false, 15)},
+                                         {LAT2_ROW(true, 0), LAT2_ROW(true, 1), LAT2_ROW(true, 2), LAT2_ROW(true, 3),
+                                          LAT2_ROW(true, 4), LAT2_ROW(true, 5), LAT2_ROW(true, 6), LAT2_ROW(true, 7),
+                                          LAT2_ROW(true, 10), LAT2_ROW(true, 11), LAT2_ROW(true, 14), LAT2_ROW(true, 15)}};
 #undef LAT2_ROW
-  return table[ff ? 1 : 0][cost & 7][box ? 1 : 0];
+  if ((cost & 8) && !(cost & 2)) return nullptr;
+  const int slot = (cost & 8) ? 8 + (cost & 1) + ((cost & 4) ? 2 : 0) : cost & 7;
+  return table[ff ? 1 : 0][slot][box ? 1 : 0];
 }
 
 #define DISPATCH_NJ(nv, CALL)                 \
@@ -792,11 +849,12 @@ int fwd_setup(ddp_hip_ctx* ctx) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     // the closed-loop instantiations this context's flags can reach (lat2_kernel)
     const bool frame = (ctx->flags & DDP_HIP_FLAG_FRAME_COST) != 0, bounds = (ctx->flags & DDP_HIP_FLAG_CONTROL_BOUNDS) != 0;
-    const int costs = 1 | (frame ? 2 : 0) | ((ctx->flags & DDP_HIP_FLAG_STATE_LIMITS) ? 4 : 0);   // the COST bits this context can set
+    const int costs = 1 | (frame ? 2 : 0) | ((ctx->flags & DDP_HIP_FLAG_STATE_LIMITS) ? 4 : 0) |
+                      ((ctx->flags & DDP_HIP_FLAG_FRAME_ORIENT_COST) ? 8 : 0);   // the COST bits this context can set
     for (int ff = 0; ff < 2; ++ff)
-      for (int cost = 0; cost < 8; ++cost)
+      for (int cost = 0; cost < 16; ++cost)
         for (int box = 0; box < (bounds ? 2 : 1); ++box)
-          if (!(cost & ~costs))
+          if (!(cost & ~costs) && (!(cost & 8) || (cost & 2)))
           HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lat2_kernel(ff != 0, cost, box != 0)), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       box ? lds_box : lds));
   }
@@ -840,14 +898,17 @@ extern "C" int ddp_hip_rollout(ddp_hip_ctx* ctx) {
   return DDP_HIP_OK;
 }
 
-// the (FRAME, LIMIT) instantiation that the resident cost data asks for: frames with a non-zero weight, limits with one
+// the (FRAME, LIMIT) instantiation that the resident cost data asks for: frames with a non-zero weight (level 2 only with a
+// non-zero orientation weight), limits with one
 #define DISPATCH_COST(p, LAUNCH)                               \
   do {                                                         \
-    const bool fr_ = (p).fc.target != nullptr, li_ = (p).sl.weight != nullptr; \
-    if (fr_ && li_) LAUNCH(true, true);                        \
-    else if (li_) LAUNCH(false, true);                         \
-    else if (fr_) LAUNCH(true, false);                         \
-    else LAUNCH(false, false);                                 \
+    const bool fr_ = (p).fc.target != nullptr, or_ = (p).fc.oquat != nullptr, li_ = (p).sl.weight != nullptr; \
+    if (or_ && li_) LAUNCH(2, true);                           \
+    else if (or_) LAUNCH(2, false);                            \
+    else if (fr_ && li_) LAUNCH(1, true);                      \
+    else if (li_) LAUNCH(0, true);                             \
+    else if (fr_) LAUNCH(1, false);                            \
+    else LAUNCH(0, false);                                     \
   } while (0)
 
 static int launch_cost(ddp_hip_ctx* ctx, FwdParams& p, int which) {
@@ -855,7 +916,7 @@ static int launch_cost(ddp_hip_ctx* ctx, FwdParams& p, int which) {
   const int64_t total = ctx->d.batch * (ctx->d.T + 1);
   const unsigned grid = (unsigned)((total + bs - 1) / bs);
 #define CALL(NJ) hipLaunchKernelGGL((cost_kernel<NJ, FR, LI>), dim3(grid), dim3(bs), 0, ctx->stream, p, which)
-#define LAUNCH(F, L) do { constexpr bool FR = F, LI = L; DISPATCH_NJ(ctx->d.nv, CALL); } while (0)
+#define LAUNCH(F, L) do { constexpr int FR = F; constexpr bool LI = L; DISPATCH_NJ(ctx->d.nv, CALL); } while (0)
   DISPATCH_COST(p, LAUNCH);
 #undef LAUNCH
 #undef CALL
@@ -904,7 +965,8 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
     if (lat_path) {
       const dim3 g((unsigned)(2 * B)), blk(128);
       // the cost terms an unconstrained problem forms inline: bit 0 tracking, bit 1 frames, bit 2 state limits (forward_kernel_lat2: COST)
-      const int cost = p.cost_inline ? (p.track ? 1 : 0) | (p.fc.target ? 2 : 0) | (p.sl.weight ? 4 : 0) : 0;
+      // bit 3 the frame orientations, which imply bit 1
+      const int cost = p.cost_inline ? (p.track ? 1 : 0) | (p.fc.target ? 2 : 0) | (p.sl.weight ? 4 : 0) | (p.fc.oquat ? 10 : 0) : 0;
       const bool box = p.ctrl_lo != nullptr;
       hipLaunchKernelGGL(lat2_kernel(ctx->model_h.ff != 0, cost, box), g, blk, box ? sizeof(FwdLat2LdsBox<38>) : sizeof(FwdLat2Lds<38>), ctx->stream, p);
       if (!p.cost_inline) {
@@ -916,7 +978,7 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
       }
     } else {
 #define CALL(NJ) hipLaunchKernelGGL((forward_kernel<NJ, FR, LI>), dim3(grid), dim3(bs), 0, ctx->stream, p)
-#define LAUNCH(F, L) do { constexpr bool FR = F, LI = L; DISPATCH_NJ(d.nv, CALL); } while (0)
+#define LAUNCH(F, L) do { constexpr int FR = F; constexpr bool LI = L; DISPATCH_NJ(d.nv, CALL); } while (0)
       DISPATCH_COST(p, LAUNCH);
 #undef LAUNCH
 #undef CALL

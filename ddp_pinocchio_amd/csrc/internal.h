@@ -245,6 +245,10 @@ struct ddp_hip_ctx {
   double* fc_target_d = nullptr;              // [batch][T+1][fc_nf][3] (room for DDP_HIP_MAX_COST_FRAMES)
   double* fc_weight_d = nullptr;
   bool fc_live = false;                       // some non-zero weight was uploaded since the frames were set: the kernels form the terms
+  // frame-orientation cost (DDP_HIP_FLAG_FRAME_ORIENT_COST; ctx.hip: ddp_hip_frame_orient_*): of the same frames
+  double* fo_quat_d = nullptr;                // [batch][T+1][fc_nf][4] unit quaternions x y z w (room for DDP_HIP_MAX_COST_FRAMES)
+  double* fo_weight_d = nullptr;              // [batch][T+1][fc_nf][3]
+  bool fo_live = false;                       // as fc_live, for the orientation weights: the two are independent
 
   // soft state limits (DDP_HIP_FLAG_STATE_LIMITS; ctx.hip: ddp_hip_state_limits_*, state_limits.h)
   double* sl_d = nullptr;                     // lo | hi | weight, each [batch][T+1][n]

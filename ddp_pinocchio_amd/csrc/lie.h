@@ -76,6 +76,47 @@ __device__ __forceinline__ void quat_log(const double* qin, double* w) {
   else { const double nn = sqrt(n2); k = 2 * atan2(nn, qt[3]) / nn; }
   w[0] = k * qt[0]; w[1] = k * qt[1]; w[2] = k * qt[2];
 }
+// the quaternion (x y z w, either sign) of a rotation matrix, by its largest of trace and diagonal entries (Shepperd): no
+// cancellation at any angle.  A matrix that is a rotation to rounding gives a quaternion that is unit to rounding
+__device__ __forceinline__ void R_to_quat(const double* M, double* qt) {
+  const double tr = M[0] + M[4] + M[8];
+  if (tr > 0) {
+    const double s = 2 * sqrt(tr + 1);
+    qt[3] = 0.25 * s; qt[0] = (M[7] - M[5]) / s; qt[1] = (M[2] - M[6]) / s; qt[2] = (M[3] - M[1]) / s;
+  } else if (M[0] > M[4] && M[0] > M[8]) {
+    const double s = 2 * sqrt(1 + M[0] - M[4] - M[8]);
+    qt[3] = (M[7] - M[5]) / s; qt[0] = 0.25 * s; qt[1] = (M[1] + M[3]) / s; qt[2] = (M[2] + M[6]) / s;
+  } else if (M[4] > M[8]) {
+    const double s = 2 * sqrt(1 + M[4] - M[0] - M[8]);
+    qt[3] = (M[2] - M[6]) / s; qt[0] = (M[1] + M[3]) / s; qt[1] = 0.25 * s; qt[2] = (M[5] + M[7]) / s;
+  } else {
+    const double s = 2 * sqrt(1 + M[8] - M[0] - M[4]);
+    qt[3] = (M[3] - M[1]) / s; qt[0] = (M[2] + M[6]) / s; qt[1] = (M[5] + M[7]) / s; qt[2] = 0.25 * s;
+  }
+}
+// e = log3(R_ref^T R), |e| <= pi, R_ref the rotation of the unit quaternion qref, R row-major: the rotation from the reference
+// frame to R's, in the axes of either (exp(e) e = e).  Through the quaternion of R_ref^T R and quat_log, whose k = 2 atan2(|v|, w)
+// / |v| does not depend on the quaternion's norm.  At |e| = pi the log is not differentiable, and which of the two axes +-e comes
+// out there is decided by rounding
+__device__ __forceinline__ void so3_log_rel(const double* qref, const double* R, double* e) {
+  double Rr[9], M[9], qt[4];
+  quat_to_R(qref, Rr);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) M[3 * i + j] = Rr[i] * R[j] + Rr[3 + i] * R[3 + j] + Rr[6 + i] * R[6 + j];
+  R_to_quat(M, qt);
+  quat_log(qt, e);
+}
+// Jlog3(e) = I + 1/2 [e]x + d(|e|^2) [e]x^2 (d: so3_coeffs): d log3(R exp(dw)) / d dw at e = log3(R); row-major 3 x 3
+__device__ __forceinline__ void so3_Jlog(const double* e, double* J) {
+  double b, c, d;
+  so3_coeffs(e[0] * e[0] + e[1] * e[1] + e[2] * e[2], b, c, d);
+  const double xx = e[0] * e[0], yy = e[1] * e[1], zz = e[2] * e[2], xy = e[0] * e[1], xz = e[0] * e[2], yz = e[1] * e[2];
+  J[0] = 1 - d * (yy + zz);         J[1] = -0.5 * e[2] + d * xy;      J[2] = 0.5 * e[1] + d * xz;
+  J[3] = 0.5 * e[2] + d * xy;       J[4] = 1 - d * (xx + zz);         J[5] = -0.5 * e[0] + d * yz;
+  J[6] = -0.5 * e[1] + d * xz;      J[7] = 0.5 * e[0] + d * yz;       J[8] = 1 - d * (xx + yy);
+}
 // y = (I + alpha [w]x + beta [w]x^2) x
 __device__ __forceinline__ void so3_apply(const double* w, double alpha, double beta, const double* x, double* y) {
   double wx[3], wwx[3];

@@ -165,6 +165,83 @@ __global__ __launch_bounds__(64) void lin_frame_cost_kernel(LinParams p, FrameCo
   }
 }
 
+// Frame-orientation cost (DDP_HIP_FLAG_FRAME_ORIENT_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after
+// lin_frame_cost_kernel and before lin_limit_cost_kernel on the same stream (the fixed order of additions: cost, tracking, frame
+// positions, frame orientations, limits).  Lane f walks frame f's path once for R_f and the path columns of its world angular
+// jacobian W_f (rbd::frame_rotation_jacobian), forms e_f = log3(R_ref^T R_f) and turns the columns in place into those of
+// A_f = Jlog3(e_f) R_f^T W_f, kept in LDS with w o e_f; then the wave adds
+//   lx[i] += sum_f sum_a A_f[a][i] (w_a e_a),   lxx[i][j] += sum_f sum_a A_f[a][min] w_a A_f[a][max]     (Gauss-Newton)
+// over the columns that carry rotation (revolute joints of the path, the angular columns of a free-flyer root), frames and axes
+// in their fixed order and entry (i, j) in (min, max) order: the block stays symmetric bit for bit.  Nothing else is read or
+// written.  A term of weight 0 is left out, a frame whose weights are 0 is not walked, a block whose weights are all 0 returns
+// at once.  t = T: lfx / lfxx
+__global__ __launch_bounds__(64) void lin_frame_orient_cost_kernel(LinParams p, FrameCostDev fc) {
+  constexpr int F = DDP_HIP_MAX_COST_FRAMES;
+  const int64_t T = p.d.T;
+  const int64_t bt1 = blockIdx.x;
+  const int b = (int)(bt1 / (T + 1));
+  const int64_t t = bt1 % (T + 1);
+  const int n = (int)p.d.n, nv = (int)p.d.nv, nx = (int)p.d.nx;
+  const int tid = threadIdx.x, nf = fc.nf;
+  const double* r = fc.oquat + bt1 * nf * 4;
+  const double* w = fc.oweight + bt1 * nf * 3;
+  bool any = false;
+  for (int k = 0; k < 3 * nf; ++k) any |= w[k] != 0.0;
+  if (!any) return;
+  __shared__ double s_A[F][3 * DDP_MAXJ], s_w[F][3], s_we[F][3];
+  __shared__ int s_chain[F][DDP_MAXJ];
+  __shared__ unsigned long long s_mask[F];
+  if (tid < nf) {
+    unsigned long long mask = 0;
+    if (rbd::frame_weights_any(w + 3 * tid)) {
+      double R[9], e[3], J[9], M[9];
+      mask = rbd::frame_rotation_jacobian(*p.model, fc.joint[tid], p.x + bt1 * nx, R, s_A[tid], s_chain[tid]);
+      lie::so3_log_rel(r + 4 * tid, R, e);
+      lie::so3_Jlog(e, J);
+      for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) M[3 * i + j] = J[3 * i] * R[3 * j] + J[3 * i + 1] * R[3 * j + 1] + J[3 * i + 2] * R[3 * j + 2];   // Jlog3 R_f^T
+      for (int i = 0; i < nv; ++i) {
+        if (!((mask >> i) & 1)) continue;
+        const double wc[3] = {s_A[tid][3 * i], s_A[tid][3 * i + 1], s_A[tid][3 * i + 2]};
+        rbd::mv3(M, wc, s_A[tid] + 3 * i);
+      }
+      for (int a = 0; a < 3; ++a) {
+        const double wa = w[3 * tid + a];
+        s_w[tid][a] = wa;
+        s_we[tid][a] = wa != 0.0 ? wa * e[a] : 0.0;
+      }
+    }
+    s_mask[tid] = mask;
+  }
+  __syncthreads();
+  unsigned long long all = 0;
+  for (int f = 0; f < nf; ++f) all |= s_mask[f];
+  double* gx = t < T ? p.lx + ((int64_t)b * T + t) * n : p.lfx + (int64_t)b * n;
+  double* gxx = t < T ? p.lxx + ((int64_t)b * T + t) * n * n : p.lfxx + (int64_t)b * n * n;
+  for (int i = tid; i < nv; i += blockDim.x) {
+    if (!((all >> i) & 1)) continue;
+    double s = 0.0;
+    for (int f = 0; f < nf; ++f)
+      if ((s_mask[f] >> i) & 1)
+        for (int a = 0; a < 3; ++a)
+          if (s_w[f][a] != 0.0) s += s_A[f][3 * i + a] * s_we[f][a];
+    gx[i] += s;
+  }
+  for (int e = tid; e < nv * nv; e += blockDim.x) {
+    const int i = e % nv, j = e / nv;
+    const int lo = i < j ? i : j, hi = i < j ? j : i;
+    double h = 0.0;
+    bool hit = false;
+    for (int f = 0; f < nf; ++f)
+      if (((s_mask[f] >> i) & 1) && ((s_mask[f] >> j) & 1)) {
+        hit = true;
+        for (int a = 0; a < 3; ++a)
+          if (s_w[f][a] != 0.0) h += s_A[f][3 * lo + a] * s_w[f][a] * s_A[f][3 * hi + a];
+      }
+    if (hit) gxx[i + (int64_t)j * n] += h;
+  }
+}
+
 // Soft state limits (DDP_HIP_FLAG_STATE_LIMITS, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after lin_cost_kernel /
 // lin_track_cost_kernel and lin_frame_cost_kernel on the same stream: their output is the starting point.  Lane i takes the
 // tangent rows i, i + 64, ...; a row of weight 0 reads neither bound, and only a violated row (e != 0) is touched:
@@ -990,6 +1067,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     else hipLaunchKernelGGL(lin_cost_kernel, dim3((unsigned)BT), dim3(64), 0, ctx->stream, p);
     const FrameCostDev fc = frame_cost_dev(ctx);
     if (fc.target) hipLaunchKernelGGL(lin_frame_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, fc);
+    if (fc.oquat) hipLaunchKernelGGL(lin_frame_orient_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, fc);
     const StateLimitsDev sl = state_limits_dev(ctx);
     if (sl.weight) hipLaunchKernelGGL(lin_limit_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, sl);
   }

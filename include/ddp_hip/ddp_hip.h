@@ -193,6 +193,28 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * non-zero weights and bounds that neither the trajectory nor any line-search candidate violates, a context computes bit for
  * bit what it computes without the flag. */
 #define DDP_HIP_FLAG_STATE_LIMITS 32u
+/* Give the cost frames of DDP_HIP_FLAG_FRAME_COST (valid only together with it: alone, ddp_hip_create returns DDP_HIP_E_ARG) an
+ * orientation term, which makes a cost frame a full placement cost.  With R_f(q) the world rotation of joint joint_f's frame
+ * (world = R body; off_f plays no part), per instance b a reference rotation given as a unit quaternion r[b][t][f] = (x y z w)
+ * (the convention of the free-flyer root) with rotation R_ref, and weights w[b][t][f] in R^3 (>= 0):
+ *   e_f = log3(R_ref^T R_f(q_t)) in R^3, |e_f| <= pi
+ *   l(t, x, u) += 1/2 sum_f sum_a w[b][t][f][a] e_f,a^2      t < T
+ *   lf(x_T)    += 1/2 sum_f sum_a w[b][T][f][a] e_f,a^2
+ * to whatever the context optimises otherwise.  The components of e are along the frame's own axes, which are the reference
+ * frame's too (exp(e) e = e): w = (w, w, 0) on a foot whose z axis is vertical at the target means "flat, yaw free".
+ * Derivatives in the tangent at x, W_f (3 x nv) the world angular jacobian (the world axis a_i of a revolute joint i on the path
+ * root .. joint_f, R_0 e_c for the angular columns 3 .. 5 of a free-flyer root; a prismatic joint and the root's linear columns
+ * have no column), A_f = Jlog3(e_f) R_f^T W_f, Jlog3(e) = I + 1/2 [e]x + d(|e|^2) [e]x^2:
+ *   lx[q rows] += sum_f A_f^T (w o e_f),  lxx[q, q] += sum_f A_f^T diag(w) A_f,  lfx / lfxx alike at T;
+ * velocity rows and columns, lu, luu and lux are untouched, and columns that carry no rotation are left out, not added as
+ * zeros.  lxx is Gauss-Newton (the term sum_a w_a e_a d^2 e_a is dropped: exact where e = 0), positive semidefinite and symmetric
+ * bit for bit.  At |e| = pi the log is not differentiable: the value there is what the quaternion logarithm gives (one of the
+ * two axes +-e, decided by rounding), and r and -r are the same reference.  At create every quaternion is (0, 0, 0, 1) and every
+ * weight 0.  The data travels through ddp_hip_frame_orient_* below, not through ddp_hip_upload or ddp_hip_device_ptr.  A term of
+ * weight 0 is left out (not multiplied by 0), a frame whose three orientation weights are 0 is not walked, and position and
+ * orientation weights are independent: with nothing uploaded or all orientation weights 0 a context computes bit for bit what
+ * it computes with DDP_HIP_FLAG_FRAME_COST alone. */
+#define DDP_HIP_FLAG_FRAME_ORIENT_COST 64u
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -225,6 +247,15 @@ int ddp_hip_fill(ddp_hip_ctx* ctx, int seq, double value);
 int ddp_hip_frame_cost_set_frames(ddp_hip_ctx* ctx, int32_t n_frames, const int32_t* joint, const double* off);
 int ddp_hip_frame_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first_instance, int64_t n_instances);
 int ddp_hip_frame_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first_instance, int64_t n_instances);
+/* The orientation terms of the cost frames, of a context created with DDP_HIP_FLAG_FRAME_ORIENT_COST (else
+ * DDP_HIP_E_UNSUPPORTED), stream-ordered like ddp_hip_frame_cost_upload.  Host arrays quat [n_instances][T+1][n_frames][4] and
+ * weight [n_instances][T+1][n_frames][3] over the frames of ddp_hip_frame_cost_set_frames; a NULL pointer leaves that side as it
+ * is.  An upload is refused as a whole (DDP_HIP_E_ARG, nothing written) before frames are set, for a bad instance range, a
+ * non-finite value, a quaternion whose norm differs from 1 by more than 1e-10 and a negative weight.
+ * ddp_hip_frame_cost_set_frames with another frame count resets the orientation data to identity quaternions and weights 0;
+ * with the same count it stays. */
+int ddp_hip_frame_orient_upload(ddp_hip_ctx* ctx, const double* quat, const double* weight, int64_t first_instance, int64_t n_instances);
+int ddp_hip_frame_orient_download(ddp_hip_ctx* ctx, double* quat, double* weight, int64_t first_instance, int64_t n_instances);
 /* The state limits of a context created with DDP_HIP_FLAG_STATE_LIMITS (else DDP_HIP_E_UNSUPPORTED), stream-ordered like
  * ddp_hip_frame_cost_upload.  Host arrays [n_instances][T+1][n]; a NULL pointer leaves that side as it is; a bad instance range
  * is DDP_HIP_E_ARG.  An upload is refused as a whole (DDP_HIP_E_ARG, nothing written) for the values listed at the flag;
