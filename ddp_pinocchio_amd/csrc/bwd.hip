@@ -37,6 +37,7 @@ struct BwdParams {
   int32_t njobs_half;
   int32_t half_mode;         // 1: symmetric tensors with two-entry upper halves (static mode-2 stencil); 2: this context's analytic mode-1
                              // tensors -- no symmetry, the upper half of every f_xx / f_ux column and all of f_uu exact zeros
+  int32_t packed;            // half_mode 1: the tensors are the stencil's packed records (lin_common.h: LinParams::pack)
   const double *u, *ctrl_lo, *ctrl_hi;   // control bounds (DDP_HIP_FLAG_CONTROL_BOUNDS), else ctrl_lo / ctrl_hi null
   double* box_stat;
   int32_t has_tensors;
@@ -560,6 +561,7 @@ BwdParams make_params(ddp_hip_ctx* ctx, const SweepPlan& plan) {
   p.jobs_half = plan.half_mode ? ctx->jobs_half_d : nullptr;
   p.njobs_half = plan.half_mode ? ctx->njobs_half : 0;
   p.half_mode = plan.half_mode;
+  p.packed = plan.packed ? 1 : 0;
   p.has_tensors = (ctx->flags & DDP_HIP_FLAG_NO_TENSORS) ? 0 : 1;
   return p;
 }
@@ -597,7 +599,8 @@ int enqueue_sweep_v2(ddp_hip_ctx* ctx, const BwdParams& p) {
     prof_end(ctx, DDP_HIP_K_BWD_GAINS);
     if (p.has_tensors) {
       prof_begin(ctx, DDP_HIP_K_BWD_ASSEMBLE);
-      if (p.jobs_half) hipLaunchKernelGGL((bwd_contract_half<NC, MC>), dim3((unsigned)p.njobs_half, B), dim3(BSF), lds_h, ctx->stream, p, t);
+      if (p.jobs_half && p.packed) hipLaunchKernelGGL((bwd_contract_half<NC, MC, true>), dim3((unsigned)p.njobs_half, B), dim3(BSF), lds_h, ctx->stream, p, t);
+      else if (p.jobs_half) hipLaunchKernelGGL((bwd_contract_half<NC, MC, false>), dim3((unsigned)p.njobs_half, B), dim3(BSF), lds_h, ctx->stream, p, t);
       else hipLaunchKernelGGL((bwd_contract<NC, MC>), dim3((unsigned)ctx->njobs, B), dim3(BSF), lds_c, ctx->stream, p, t);
       prof_end(ctx, DDP_HIP_K_BWD_ASSEMBLE);
     }
@@ -636,7 +639,7 @@ int launch_sweep_v2(ddp_hip_ctx* ctx, const BwdParams& p0) {
   // profiled sweeps take the direct path: events recorded by a graph's event-record nodes cannot be read back with
   // hipEventElapsedTime on this ROCm (hipErrorInvalidHandle -- tried)
   if (ctx->sw.bwd_no_graph || (ctx->profile_mask & bwd_mask)) return enqueue_sweep_v2<NC, MC, BOX>(ctx, p0);
-  const uint64_t key_misc = (uint64_t)p0.has_tensors | ((uint64_t)(p0.vx_trace != nullptr) << 1) | ((uint64_t)p0.sym_tensors << 2) | ((uint64_t)(p0.jobs_half != nullptr) << 3) | ((uint64_t)p0.half_mode << 4);
+  const uint64_t key_misc = (uint64_t)p0.has_tensors | ((uint64_t)(p0.vx_trace != nullptr) << 1) | ((uint64_t)p0.sym_tensors << 2) | ((uint64_t)(p0.jobs_half != nullptr) << 3) | ((uint64_t)p0.half_mode << 4) | ((uint64_t)p0.packed << 8);
   auto find = [&](const void* key_x) -> ddp_hip_ctx::BwdGraph* {
     for (auto& g : ctx->bwd_graph)
       if (g.exec && g.key_x == key_x && g.key_misc == key_misc) return &g;
@@ -677,7 +680,7 @@ SweepPlan sweep_plan(const ddp_hip_ctx* ctx) {
   s.sym = s.sym_ok && (o == TensorOrigin::Symmetric || o == TensorOrigin::Stencil);
   const bool half_ok = s.fast && ctx->jobs_half_d && !sw.k3_no_half;
   // K3h needs both structural facts: symmetry and the zero configuration rows (the static stencil's own tensors) ...
-  if (half_ok && s.sym && o == TensorOrigin::Stencil) s.half_mode = 1;
+  if (half_ok && s.sym && o == TensorOrigin::Stencil) { s.half_mode = 1; s.packed = ctx->tensors.packed; }   // (on the stencil's records where it left them packed)
   // ... or the structure the analytic mode-1 pass leaves (lin_analytic.hip): q+ = q + dt v has constant jacobian rows and M^-1 does
   // not depend on u, so the upper halves and f_uu are zeros it wrote itself
   else if (half_ok && o == TensorOrigin::Analytic1) s.half_mode = 2;
@@ -764,7 +767,13 @@ extern "C" int ddp_hip_backward(ddp_hip_ctx* ctx, double* reg_io, double* mu_io,
   const Dims& d = ctx->d;
   const int64_t B = d.batch;
   HIP_TRY(hipSetDevice(ctx->device));
-  const SweepPlan plan = sweep_plan(ctx);
+  SweepPlan plan = sweep_plan(ctx);
+  // packed records are for the packed K3h alone: any other sweep reads the contract layout
+  if (ctx->tensors.packed && !plan.packed) {
+    const int rc_ = lin_materialize_fxx(ctx);
+    if (rc_ != DDP_HIP_OK) return rc_;
+    plan = sweep_plan(ctx);
+  }
   BwdParams p = make_params(ctx, plan);
   if (p.has_tensors && (!p.fxx || !p.fux || !p.fuu)) return DDP_HIP_E_UNSUPPORTED;
   const bool box = (ctx->flags & DDP_HIP_FLAG_CONTROL_BOUNDS) != 0;

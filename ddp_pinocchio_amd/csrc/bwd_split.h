@@ -151,7 +151,10 @@ static_assert(38 % 2 == 0, "row pairs");
 
 // kinds: 10 = x-columns c0, c0 + 1 (units: f_xx slab c0 | f_xx slab c0 + 1 | f_ux slabs c0, c0 + 1); 11 = cn u-columns from c0,
 // cn even (units: f_uu slabs in pairs)
-template <int N, int M>
+// PK: the tensors are the stencil's packed records (lin_common.h: LinParams::pack) -- column j of a slab is the M + 2 doubles
+// [top0, top1, rows M .. N-1] at slab + j (M + 2), so a unit's bytes are one contiguous run per slab (two for f_ux / f_uu units,
+// whose slabs keep their bases) and the two upper-half entries are word 0 of the record.  Same jobs, same lanes, same sums.
+template <int N, int M, bool PK>
 __global__ __launch_bounds__(BSF, BWD_WAVES_PER_SIMD) void bwd_contract_half(BwdParams p, int64_t t) {
   int b, jb;
   {
@@ -202,6 +205,9 @@ __global__ __launch_bounds__(BSF, BWD_WAVES_PER_SIMD) void bwd_contract_half(Bwd
   double top0[2], top1[2], top2[2], top3[2];   // lane jj < N: the (at most) two entries of its column's upper half
   auto issue = [&](int u, f64x2 (&buf)[HS::R], double (&top)[2]) {
     const f64x2* base = reinterpret_cast<const f64x2*>(unit_base(u));
+    // packed: first word of column jj's record (a unit of two M-column slabs: the second slab's records start at its own base)
+    const bool two = !(kind == 10 && u < 2);
+    auto rec_word = [&](int jj) -> int { return (two && jj >= m) ? (N * M) / 2 + (jj - m) * (HS::HP + 1) : jj * (HS::HP + 1); };
 #pragma unroll
     for (int r = 0; r < HS::R; ++r) {
       const int f = tid + r * BSF;
@@ -209,16 +215,23 @@ __global__ __launch_bounds__(BSF, BWD_WAVES_PER_SIMD) void bwd_contract_half(Bwd
       const int jj = f / HS::HP, ip = f - jj * HS::HP;
       int slab, j; bool xcol;
       if (need) need = col_info(u, jj < n ? jj : n - 1, slab, j, xcol) && !(m1 && kind == 11);
-      if (need) buf[r] = BWD_NT ? __builtin_nontemporal_load(&base[jj * (N / 2) + HS::HP + ip]) : base[jj * (N / 2) + HS::HP + ip];
+      const int w = PK ? rec_word(jj) + 1 + ip : jj * (N / 2) + HS::HP + ip;
+      if (need) buf[r] = BWD_NT ? __builtin_nontemporal_load(&base[w]) : base[w];
       else buf[r] = f64x2{0.0, 0.0};
     }
     top[0] = 0.0; top[1] = 0.0;
     if (tid < n) {
       int slab, j; bool xcol;
       if (col_info(u, tid, slab, j, xcol) && kind == 10 && !m1) {   // f_uu: its directions are controls, the upper half is all zeros
-        const double* colp = unit_base(u) + (int64_t)tid * n;
-        top[0] = colp[slab % M];                                     // the slab's direction is an x direction (f_xx and f_ux)
-        if (xcol && (j % M) != (slab % M)) top[1] = colp[j % M];
+        if constexpr (PK) {
+          const f64x2 tw = base[rec_word(tid)];
+          top[0] = tw.x;
+          if (xcol && (j % M) != (slab % M)) top[1] = tw.y;          // (else: never written)
+        } else {
+          const double* colp = unit_base(u) + (int64_t)tid * n;
+          top[0] = colp[slab % M];                                     // the slab's direction is an x direction (f_xx and f_ux)
+          if (xcol && (j % M) != (slab % M)) top[1] = colp[j % M];
+        }
       }
     }
   };

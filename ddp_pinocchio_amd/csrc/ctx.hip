@@ -221,6 +221,7 @@ static DevSwitches read_switches() {
   sw.generic_bwd = on("DDP_HIP_GENERIC_BWD");
   sw.k3_no_sym = on("DDP_HIP_K3_NO_SYM");
   sw.k3_no_half = on("DDP_HIP_K3_NO_HALF");
+  sw.k3_no_pack = on("DDP_HIP_K3_NO_PACK");
   sw.fxx_full = on("DDP_HIP_FXX_FULL");
   sw.no_static = on("DDP_HIP_NO_STATIC");
   sw.no_qcache = on("DDP_HIP_NO_QCACHE");
@@ -437,7 +438,7 @@ extern "C" int64_t ddp_hip_seq_size(const ddp_hip_ctx* ctx, int seq) {
 
 extern "C" double* ddp_hip_device_ptr(ddp_hip_ctx* ctx, int seq) {
   if (!ctx || seq < 0 || seq >= DDP_HIP_SEQ_COUNT) return nullptr;
-  if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUU) (void)hipSetDevice(ctx->device);   // (the mirror images may have to be formed)
+  if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUX || seq == DDP_HIP_SEQ_FUU) (void)hipSetDevice(ctx->device);   // (the tensors may have to be unpacked, the mirror images formed)
   if (tensors_written_outside(ctx, seq) != DDP_HIP_OK) return nullptr;   // the caller may write through the pointer
   return ctx->seq[seq].ptr;
 }
@@ -512,7 +513,7 @@ extern "C" int ddp_hip_download(ddp_hip_ctx* ctx, int seq, double* host, int64_t
   if (sz == 0 || count == 0) return DDP_HIP_OK;
   if (!host) return DDP_HIP_E_ARG;
   HIP_TRY(hipSetDevice(ctx->device));
-  if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUU) { const int rc_ = lin_materialize_fxx(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
+  if (seq == DDP_HIP_SEQ_FXX || seq == DDP_HIP_SEQ_FUU || (seq == DDP_HIP_SEQ_FUX && ctx->tensors.packed)) { const int rc_ = lin_materialize_fxx(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
   HIP_TRY(hipMemcpyAsync(host, ctx->seq[seq].ptr + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return DDP_HIP_OK;
@@ -820,7 +821,9 @@ extern "C" int ddp_hip_profile_get(ddp_hip_ctx* ctx, int kernel_id, double* tota
 
 // Bytes of f_xx / f_ux / f_uu the contraction kernel (K3) reads per (instance, step) with the tensors in their current state:
 // everything (tensors from outside), the columns j >= c of slab c (symmetric: this context's own mode-2 / zero tensors), or the
-// lower halves of those columns plus the (at most) two non-zero entries of each upper half (the static stencil's own tensors)
+// lower halves of those columns plus the (at most) two non-zero entries of each upper half (the static stencil's own tensors).
+// (From packed records K3h takes the two upper-half entries of a column as one 16-byte word whether or not the second is used:
+// about 1 % more than the closed form below, which counts what the contraction needs.)
 extern "C" int64_t ddp_hip_bwd_stream_bytes(const ddp_hip_ctx* ctx) {
   if (!ctx) return -1;
   if (ctx->flags & DDP_HIP_FLAG_NO_TENSORS) return 0;

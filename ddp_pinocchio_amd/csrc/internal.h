@@ -66,6 +66,7 @@ struct DevSwitches {
   bool generic_bwd = false;    // GENERIC_BWD: the run-time-shaped sweep at the Talos shape as well
   bool k3_no_sym = false;      // K3_NO_SYM: K3 reads every half-slab (and the static stencil writes the mirror images)
   bool k3_no_half = false;     // K3_NO_HALF: no K3h
+  bool k3_no_pack = false;     // K3_NO_PACK: the static stencil writes the contract layout, K3h reads it strided (no packed records)
   bool fxx_full = false;       // FXX_FULL: the static stencil writes the configuration rows and the mirror images
   bool no_static = false;      // NO_STATIC: the generic level kernels instead of the static-topology ones
   bool no_qcache = false;      // NO_QCACHE: no configuration caches
@@ -86,6 +87,7 @@ struct SweepPlan {
   bool sym_ok;     // ... which would read symmetric tensors by halves: the static stencil may leave the mirror images out
   bool sym;        // ... and they are symmetric now (TensorState): K3 reads one of each pair of mirrored half-slabs
   int32_t half_mode;   // K3h (bwd_split.h: bwd_contract_half): 0 off, 1 the static stencil's tensors, 2 analytic mode 1
+  bool packed;         // half_mode 1 on the stencil's packed records (TensorState::packed)
 };
 
 // Which kernels a context's linearisation runs and which workspaces they need: decided once, by lin_plan_decide (lin_plan.cpp, a
@@ -132,6 +134,7 @@ struct LinPlan {
   bool has_tensors = false;    // FXX / FUX / FUU are resident
   bool skip_top = false;       // LinParams::skip_top
   bool skip_qv_mirror = false; // LinParams::skip_qv_mirror
+  bool pack = false;           // LinParams::pack: the static stencil leaves packed records, which K3h streams
   // the workspaces that exist (lin_setup, lin_analytic_setup allocate exactly these)
   bool ws_lin = false, ws_qws = false, ws_qws2 = false;   // the caches; the static path's configuration-level workspace; its twin + stream
   bool ws_ana_T = false, ws_ana_M = false, ws_ana_M0 = false, ws_ana_A = false, ws_ana_F = false;
@@ -155,6 +158,9 @@ struct TensorState {
   // the static stencil left the mirror images f_xx(:, i, j), f_uu(:, i, j), i < j, out (LinParams::skip_qv_mirror).  Its own bit
   // because it outlives the origin: an upload of FUX alone takes Stencil to Symmetric and leaves the images unwritten
   bool mirror_pending = false;
+  // the three tensors hold the static stencil's packed records (LinParams::pack), not the contract layout: only the packed K3h
+  // reads them as they are, every other reader goes through lin_materialize_fxx first.  Implies origin == Stencil
+  bool packed = false;
 };
 
 // State of one linearisation call (lin.hip: ddp_hip_linearize_stages creates it, lin_analytic.hip reads and marks it)
@@ -285,7 +291,7 @@ void fwd_teardown(ddp_hip_ctx* ctx);
 int lin_setup(ddp_hip_ctx* ctx);
 // the transitions of ctx->tensors (lin.hip); linearise's own two (about to write / has written the second order) are local to it
 int tensors_written_outside(ddp_hip_ctx* ctx, int seq);   // ddp_hip_device_ptr / upload / fill of `seq`: a no-op unless it is FXX / FUX / FUU
-int lin_materialize_fxx(ddp_hip_ctx* ctx);   // the mirror images formed: FXX / FUU complete for readers outside the symmetric sweep
+int lin_materialize_fxx(ddp_hip_ctx* ctx);   // packed records back in the contract layout, the mirror images formed: FXX / FUX / FUU complete for readers other than the sweep they were left for
 void lin_teardown(ddp_hip_ctx* ctx);
 
 // best-cost pick, device side (pick.hip): {cost, global index} of the local best / of G gathered pairs

@@ -984,6 +984,38 @@ __global__ void tensor_zero_top_kernel(double* Tn, int64_t total_cols, int n, in
   }
 }
 
+// Packed records (LinParams::pack) back into the contract layout, in place: one workgroup per slab (grid: the n slabs of f_xx, the
+// n of f_ux, the m of f_uu of every (instance, t)).  The packed image (L (nv + 2) doubles at the front of the slab) overlaps the
+// contract image it becomes, so the whole of it goes through LDS before the first store.  Upper halves: +0.0 but the tops; f_uu
+// has none.  Columns the symmetric stencil never wrote (j < slab) carry over whatever their records held: tensor_mirror_kernel
+// overwrites all of them next.
+constexpr int UNPACK_BS = 256;
+__global__ __launch_bounds__(UNPACK_BS) void tensor_unpack_kernel(double* fxx, double* fux, double* fuu, int n, int m, int nv) {
+  extern __shared__ __attribute__((aligned(16))) double s_rec[];   // n (nv + 2)
+  const int per = 2 * n + m;
+  const int64_t bt = blockIdx.x / per;
+  const int s = (int)(blockIdx.x % per);
+  double* slab;
+  int L, c;
+  bool tops;
+  if (s < n) { c = s; L = n; tops = true; slab = fxx + (bt * n + c) * (int64_t)n * n; }
+  else if (s < 2 * n) { c = s - n; L = m; tops = true; slab = fux + (bt * n + c) * (int64_t)n * m; }
+  else { c = s - 2 * n; L = m; tops = false; slab = fuu + (bt * m + c) * (int64_t)n * m; }
+  const int R = nv + 2, words = L * R;
+  for (int e = threadIdx.x; e < words; e += UNPACK_BS) s_rec[e] = slab[e];
+  __syncthreads();
+  const int r0 = c % nv;
+  for (int e = threadIdx.x; e < L * n; e += UNPACK_BS) {
+    const int j = e / n, k = e - j * n;
+    const double* rec = s_rec + j * R;
+    double v = 0.0;
+    if (k >= nv) v = rec[2 + (k - nv)];
+    else if (tops && k == r0) v = rec[0];
+    else if (tops && L == n && k == j % nv) v = rec[1];
+    slab[e] = v;
+  }
+}
+
 LinParams make_params(ddp_hip_ctx* ctx) {
   LinParams p{};
   p.d = ctx->d;
@@ -1003,6 +1035,7 @@ LinParams make_params(ddp_hip_ctx* ctx) {
   p.has_tensors = pl.has_tensors ? 1 : 0;
   p.skip_top = pl.skip_top ? 1 : 0;
   p.skip_qv_mirror = pl.skip_qv_mirror ? 1 : 0;
+  p.pack = pl.pack ? 1 : 0;
   p.eq_xk = ctx->eq_ws;
   if (p.eq_xk) { p.eq_fxk = p.eq_xk + pl.eq_fxk_off; p.eq_c = p.eq_xk + pl.eq_c_off; }
   p.qcache = ctx->lin_ws;
@@ -1187,8 +1220,10 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
 int tensors_begin_second(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call) {
   const TensorOrigin was = ctx->tensors.origin;
   ctx->tensors.origin = TensorOrigin::Unknown;
+  ctx->tensors.packed = false;   // (records that are about to be overwritten, or contents nobody may rely on)
   call.fuu_zero = was == TensorOrigin::Analytic1;
-  if (p.skip_top && was != TensorOrigin::Stencil) {
+  // (packed records have no zero rows: unpacking writes them)
+  if (p.skip_top && !p.pack && was != TensorOrigin::Stencil) {
     const int64_t BT = ctx->d.batch * ctx->d.T, n = ctx->d.n, m = ctx->d.m;
     const int nv = (int)ctx->d.nv;
     hipLaunchKernelGGL(tensor_zero_top_kernel, dim3(8192), dim3(256), 0, ctx->stream, p.fxx, BT * n * n, (int)n, nv);
@@ -1208,6 +1243,7 @@ void tensors_end_second(ddp_hip_ctx* ctx, const LinParams& p, const LinCall& cal
   if (ctx->model_h.fd_mode == 1) t.origin = call.fuu_zero ? TensorOrigin::Analytic1 : TensorOrigin::Unknown;   // (small models' mode 1: no structure kept)
   else t.origin = p.skip_top ? TensorOrigin::Stencil : TensorOrigin::Symmetric;
   t.mirror_pending = p.skip_qv_mirror != 0;
+  t.packed = p.pack != 0;
 }
 
 }  // namespace
@@ -1276,6 +1312,8 @@ extern "C" int ddp_hip_linearize_stages(ddp_hip_ctx* ctx, uint32_t stages) {
 int tensors_written_outside(ddp_hip_ctx* ctx, int seq) {
   if (seq != DDP_HIP_SEQ_FXX && seq != DDP_HIP_SEQ_FUX && seq != DDP_HIP_SEQ_FUU) return DDP_HIP_OK;
   TensorState& t = ctx->tensors;
+  // packed records are unpacked first, all three tensors together: the caller overwrites part of one of them at most
+  if (t.packed) { const int rc_ = lin_materialize_fxx(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
   if (seq == DDP_HIP_SEQ_FUX) {
     // f_ux carries no symmetry: f_xx / f_uu stay as symmetric as they were (and as incomplete), the zero rows are gone
     t.origin = (t.origin == TensorOrigin::Symmetric || t.origin == TensorOrigin::Stencil) ? TensorOrigin::Symmetric : TensorOrigin::Unknown;
@@ -1289,12 +1327,23 @@ int tensors_written_outside(ddp_hip_ctx* ctx, int seq) {
   return DDP_HIP_OK;
 }
 
-// the mirror images materialised: FXX / FUU complete for a reader that does not know about the skipped block (download,
-// device_ptr, the run-time-shaped sweep)
+// the tensors materialised: packed records back in the contract layout, then the mirror images formed -- FXX / FUX / FUU complete
+// for a reader that knows neither the records nor the skipped block (download, device_ptr, upload / fill, any sweep but the
+// packed K3h).  Afterwards the state is what a linearisation without packing leaves: Stencil, read by the strided K3h
 int lin_materialize_fxx(ddp_hip_ctx* ctx) {
-  if (!ctx->tensors.mirror_pending) return DDP_HIP_OK;
   double* fxx = ctx->seq[DDP_HIP_SEQ_FXX].ptr;
   double* fuu = ctx->seq[DDP_HIP_SEQ_FUU].ptr;
+  if (ctx->tensors.packed) {
+    double* fux = ctx->seq[DDP_HIP_SEQ_FUX].ptr;
+    const int64_t BT = ctx->d.batch * ctx->d.T, n = ctx->d.n, m = ctx->d.m, nv = ctx->d.nv;
+    if (!fxx || !fux || !fuu || m > n) return DDP_HIP_E_UNSUPPORTED;
+    hipLaunchKernelGGL(tensor_unpack_kernel, dim3((unsigned)(BT * (2 * n + m))), dim3(UNPACK_BS), sizeof(double) * (size_t)(n * (nv + 2)), ctx->stream,
+                       fxx, fux, fuu, (int)n, (int)m, (int)nv);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->tensors.packed = false;
+  }
+  if (!ctx->tensors.mirror_pending) return DDP_HIP_OK;
   if (fxx && fuu) {
     const int64_t BT = ctx->d.batch * ctx->d.T;
     hipLaunchKernelGGL(tensor_mirror_kernel, dim3(8192), dim3(256), 0, ctx->stream, fxx, BT, (int)ctx->d.n, (int)ctx->d.n);

@@ -23,6 +23,11 @@ struct LinParams {
                             // direction) mod nv and k = (second direction) mod nv -- q+ = q + dt v is affine, and row k of every stencil
                             // point but those two is bit for bit the base point's -- so only those two and the rows k >= nv are formed
                             // and stored; the other rows hold the zeros lin.hip: tensor_zero_top_kernel left there
+  int32_t pack;             // static stencil (with skip_top and skip_qv_mirror): the tensors are left as packed records, not in the contract
+                            // layout.  A slab keeps its base address; inside it column j is the record [top0, top1, rows nv .. n-1] of
+                            // nv + 2 doubles at slab + j (nv + 2): top0 the entry of row (slab direction) mod nv, top1 that of row j mod nv
+                            // where it is another row (x columns only); f_uu's tops are never written.  K3h streams the records
+                            // (bwd_split.h); any other reader has them unpacked first (lin.hip: lin_materialize_fxx)
   double* accel_out;     // static first-order kernels, levels 1 and 2: when set, the wave stores the accelerations of its nv perturbed
                          // points, [pair][3 nv directions: q, v, u | the unperturbed point][nv], instead of the jacobian columns (lin_analytic.hip: mode 1 reads them)
   int32_t ncfg, nvcfg;   // entries per (instance, t) of the q- / v-cache: nv+1 / 2nv+1 with the mode-2 stencil resident,

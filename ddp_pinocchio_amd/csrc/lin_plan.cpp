@@ -47,6 +47,8 @@ LinPlan lin_plan_decide(const DevModel& m, const Dims& d, uint32_t flags, const 
   // (with DDP_HIP_NO_QCACHE on forward-differenced jacobians the two marks below are set although Mode2Plain runs: DESIGN.md 4j)
   pl.skip_top = pl.topo && mode == 2 && tensors && !sw.fxx_full;
   pl.skip_qv_mirror = pl.skip_top && sweep_sym_ok;   // only for a sweep that never reads the mirror images
+  // packed records: the static stencil writing for the fast symmetric sweep's K3h (sweep_sym_ok: the Talos shape, where K3h's job list exists)
+  pl.pack = pl.skip_qv_mirror && pl.second == LinSecond::Mode2Static && !sw.k3_no_half && !sw.k3_no_pack;
 
   const bool m1_wave = wave && pl.second == LinSecond::Mode1Wave;
   pl.ana_sliced = analytic && !small;
@@ -86,7 +88,7 @@ int main() {
   static const char* const sw_names[] = {"none", "generic_bwd", "k3_no_sym", "k3_no_half", "fxx_full", "no_static", "no_qcache",
                                          "cfg_full_aba", "ana_own_aba", "ana_split", "ana_eq_kernel", "bwd_no_graph", "solve_sync"};
   printf("kind nv ff fo_fd mode tensors etot eq_kind K matched sw sym_ok created refuse nj topo first second eq eq_jac eq_second "
-         "eq_inline accel_static accel_with_u m1_fused ncfg nvcfg has_tensors skip_top skip_qv_mirror ws_lin ws_qws ws_qws2 ws_ana_T "
+         "eq_inline accel_static accel_with_u m1_fused ncfg nvcfg has_tensors skip_top skip_qv_mirror pack ws_lin ws_qws ws_qws2 ws_ana_T "
          "ws_ana_M ws_ana_M0 ws_ana_A ws_ana_F ws_eq ana_sliced eq_fxk_off eq_c_off eq_words lin_path first_order\n");
   printf("#");
   for (const char* s : sw_names) printf(" %s", s);
@@ -111,11 +113,11 @@ int main() {
     const bool created = (kind == DDP_HIP_MODEL_TREE || (nv == 1 && !ff)) && (!ff || (nv >= 6 && mode != 1 && eqk != DDP_HIP_EQ_CONFIG)) &&
                          (eqk != DDP_HIP_EQ_NONE || !etot);
     const LinPlan p = lin_plan_decide(m, d, tensors ? 0u : (uint32_t)DDP_HIP_FLAG_NO_TENSORS, sw, matched && !ff ? 1 : 0, sym_ok != 0);
-    printf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %lld %lld %lld %d %d\n",
+    printf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %lld %lld %lld %d %d\n",
            kind == DDP_HIP_MODEL_TREE, nv, ff, fo, mode, tensors, etot, eqk == DDP_HIP_EQ_NONE ? 0 : eqk == DDP_HIP_EQ_CONFIG ? 1 : 2, K, matched, s, sym_ok,
            (int)created, p.refuse != 0, p.nj, p.topo, (int)p.first, (int)p.second, (int)p.eq, (int)p.eq_jac, (int)p.eq_second,
            (int)p.eq_inline, (int)p.accel_static, (int)p.accel_with_u, (int)p.m1_fused, p.ncfg, p.nvcfg, (int)p.has_tensors, (int)p.skip_top,
-           (int)p.skip_qv_mirror, (int)p.ws_lin, (int)p.ws_qws, (int)p.ws_qws2, (int)p.ws_ana_T, (int)p.ws_ana_M, (int)p.ws_ana_M0, (int)p.ws_ana_A,
+           (int)p.skip_qv_mirror, (int)p.pack, (int)p.ws_lin, (int)p.ws_qws, (int)p.ws_qws2, (int)p.ws_ana_T, (int)p.ws_ana_M, (int)p.ws_ana_M0, (int)p.ws_ana_A,
            (int)p.ws_ana_F, (int)p.ws_eq, (int)p.ana_sliced, (long long)p.eq_fxk_off, (long long)p.eq_c_off, (long long)p.eq_words, p.lin_path, p.first_order);
   }
   return 0;

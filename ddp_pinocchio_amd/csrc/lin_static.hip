@@ -248,6 +248,15 @@ __device__ __forceinline__ void tri_index(int64_t q, int Wd, int& ii, int& jj) {
   jj = (int)(q - (int64_t)a * (2 * Wd - a - 1) / 2) + a + 1;
 }
 
+// Where row k of a tensor column lives, counted from the column's base: k in the contract layout; in a packed record
+// (LinParams::pack: [top0, top1, rows NV .. n-1]) the rows k >= NV behind the two tops, row r0 -- the slab direction's
+// configuration row -- at top0, and the one other configuration row a column can hold at top1.  rec_zero: the rows a packed
+// column does not hold (exact zeros in the contract layout); with r0 = -1 all of its configuration rows (u directions).
+// A reader asks rec_row for every row and lets rec_zero discard: for those rows rec_row names top1, which a diagonal or u
+// column never writes, so that load of unwritten memory is intended -- it stays inside the record and its value is dropped
+template <int NV> __device__ __forceinline__ int rec_row(bool pack, int k, int r0) { return !pack ? k : (k >= NV ? k - NV + 2 : (k == r0 ? 0 : 1)); }
+template <int NV> __device__ __forceinline__ bool rec_zero(bool pack, int k, int r0) { return pack && k < NV && k != r0; }
+
 // ---- output stage of the pair kernels (problem.hpp:226-296) -----------------------------------------------------------
 // NP: points per pass of the output stage (LBS: all of the wave's at once; LBS / 2: the torque-level pair kernel, whose
 // accelerations are in registers until then, emits its two half-waves one after the other and needs half the LDS)
@@ -267,9 +276,12 @@ struct OutStage {
 // (Round 1's form walked four points per 16-row chunk and re-read the addresses for every chunk: 8 LDS reads per element, the
 // acceleration among them 16-way bank-conflicted; the stage was 12.5 ms of the 86 ms linearisation.)
 // pass: which NP-block of the wave's lanes owns the slots this time (the caller has put their accelerations into S.qdd)
-template <int NV, int NP>
-__device__ __forceinline__ void offdiag_emit(const LinParams& p, OutStage<NV, NP>& S, bool valid, int i, int j, int64_t bt,
-                                             const double* __restrict__ xg, double dt, int pass = 0) {
+// PACK: the tensors are packed records (the diagonal columns read here as well as the columns written); a compile-time matter
+// inside the stage.  UU: every point of the caller is a (u_i, u_j) pair -- with records no configuration row is read or written
+// then (used under PACK only: the contract-layout code of every caller is what it was)
+template <int NV, int NP, bool PACK, bool UU>
+__device__ __forceinline__ void offdiag_emit_as(const LinParams& p, OutStage<NV, NP>& S, bool valid, int i, int j, int64_t bt,
+                                                const double* __restrict__ xg, double dt, int pass) {
   constexpr int n = 2 * NV, mm = NV;
   // points in flight per group: two; one where the caller still holds the accelerations of the second half in registers
   constexpr int RW = 16, NJ = (n + RW - 1) / RW, GRP = LBS / RW, PPG = NP / GRP, NB = NP == LBS ? 2 : 1;
@@ -286,6 +298,9 @@ __device__ __forceinline__ void offdiag_emit(const LinParams& p, OutStage<NV, NP
   __syncthreads();
   const int kk = lane % RW, grp = lane / RW;
   const double* f0 = p.f_val + bt * n;
+  constexpr bool pack = PACK, uu = UU && PACK;
+  const bool skip_top = PACK || p.skip_top != 0;   // (packed records come with the skipped rows)
+  constexpr int cs = pack ? NV + 2 : n;    // doubles from one tensor column to the next
   double f0k[NJ], xk[NJ], xvk[NJ];
 #pragma unroll
   for (int jx = 0; jx < NJ; ++jx) {
@@ -300,7 +315,7 @@ __device__ __forceinline__ void offdiag_emit(const LinParams& p, OutStage<NV, NP
     double a1[NB][NJ], a2[NB][NJ], d1[NB][NJ], d2[NB][NJ];
     double* o0[NB];
     double* o1[NB];
-    int ie[NB], je[NB], ee[NB];
+    int ie[NB], je[NB], ee[NB], r2[NB];
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
       const int e = (pt + u) * GRP + grp;
@@ -309,24 +324,29 @@ __device__ __forceinline__ void offdiag_emit(const LinParams& p, OutStage<NV, NP
       const int i1 = pk & 255, j1 = (pk >> 8) & 255;
       ie[u] = i1;
       je[u] = j1;
-      const bool at_x_1 = i1 < n, at_x_2 = j1 < n;
+      const bool at_x_1 = !uu && i1 < n, at_x_2 = !uu && j1 < n;
       const int idx_1 = at_x_1 ? i1 : i1 - n, idx_2 = at_x_2 ? j1 : j1 - n;
       double* tensor;
       int L;
       if (at_x_1) { if (at_x_2) { tensor = fxx; L = n; } else { tensor = fux; L = mm; } }
       else { tensor = fuu; L = mm; }
-      o0[u] = (pk >> 16) ? tensor + (int64_t)idx_2 * n + (int64_t)idx_1 * n * L : nullptr;
-      o1[u] = ((pk >> 16) && at_x_1 == at_x_2 && !p.skip_qv_mirror) ? tensor + (int64_t)idx_1 * n + (int64_t)idx_2 * n * L : nullptr;
+      r2[u] = at_x_1 ? idx_1 % NV : -1;
+      o0[u] = (pk >> 16) ? tensor + (int64_t)idx_2 * cs + (int64_t)idx_1 * n * L : nullptr;
+      o1[u] = ((pk >> 16) && at_x_1 == at_x_2 && !p.skip_qv_mirror) ? tensor + (int64_t)idx_1 * n + (int64_t)idx_2 * n * L : nullptr;   // (never with pack)
       if (o0[u]) {
         const double* q0 = at_x_1 ? fxb + (int64_t)idx_1 * n : fub + (int64_t)idx_1 * n;
         const double* q1 = at_x_2 ? fxb + (int64_t)idx_2 * n : fub + (int64_t)idx_2 * n;
-        const double* q2 = at_x_1 ? fxx + (int64_t)idx_1 * n + (int64_t)idx_1 * n * n : fuu + (int64_t)idx_1 * n + (int64_t)idx_1 * n * mm;
-        const double* q3 = at_x_2 ? fxx + (int64_t)idx_2 * n + (int64_t)idx_2 * n * n : fuu + (int64_t)idx_2 * n + (int64_t)idx_2 * n * mm;
+        const double* q2 = at_x_1 ? fxx + (int64_t)idx_1 * cs + (int64_t)idx_1 * n * n : fuu + (int64_t)idx_1 * cs + (int64_t)idx_1 * n * mm;
+        const double* q3 = at_x_2 ? fxx + (int64_t)idx_2 * cs + (int64_t)idx_2 * n * n : fuu + (int64_t)idx_2 * cs + (int64_t)idx_2 * n * mm;
+        const int r3 = at_x_2 ? idx_2 % NV : -1;   // the one configuration row a diagonal column holds (r2: that of the first direction's)
 #pragma unroll
         for (int jx = 0; jx < NJ; ++jx) {
           const int k = kk + RW * jx;
           const int kc = k < n ? k : n - 1;
-          a1[u][jx] = q0[kc]; a2[u][jx] = q1[kc]; d1[u][jx] = q2[kc]; d2[u][jx] = q3[kc];
+          a1[u][jx] = q0[kc]; a2[u][jx] = q1[kc];
+          const double v2 = q2[rec_row<NV>(pack, kc, r2[u])], v3 = q3[rec_row<NV>(pack, kc, r3)];
+          d1[u][jx] = rec_zero<NV>(pack, kc, r2[u]) ? 0.0 : v2;
+          d2[u][jx] = rec_zero<NV>(pack, kc, r3) ? 0.0 : v3;
         }
       }
     }
@@ -339,7 +359,7 @@ __device__ __forceinline__ void offdiag_emit(const LinParams& p, OutStage<NV, NP
         if (k >= n) continue;
         // configuration rows: q+ = q + dt v does not see the dynamics; row k < nv of a stencil point differs from the base point's
         // only when one of the two directions is q_k or v_k -- every other entry is an exact zero, already in memory (skip_top)
-        if (p.skip_top && k < NV && !((ie[u] < n && ie[u] % NV == k) || (je[u] < n && je[u] % NV == k))) continue;
+        if (skip_top && k < NV && (uu || !((ie[u] < n && ie[u] % NV == k) || (je[u] < n && je[u] % NV == k)))) continue;
         // row k of f(x + dx, u + du) (dynamics_t::eval_to, problem.hpp:441-461)
         double xs = k == ie[u] ? xk[jx] + eps : xk[jx];
         if (k == je[u]) xs = xs + eps;
@@ -357,11 +377,19 @@ __device__ __forceinline__ void offdiag_emit(const LinParams& p, OutStage<NV, NP
         df -= eps * a2[u][jx];
         df *= 2;
         const double val = 0.5 * (df / eps2 - d1[u][jx] - d2[u][jx]);
-        o0[u][k] = val;
+        o0[u][rec_row<NV>(pack, k, r2[u])] = val;
         if (o1[u]) o1[u][k] = val;
       }
     }
   }
+}
+
+// the layout picked at run time, for the callers with registers to spare (velocity and configuration pairs)
+template <int NV, int NP>
+__device__ __forceinline__ void offdiag_emit(const LinParams& p, OutStage<NV, NP>& S, bool valid, int i, int j, int64_t bt,
+                                             const double* __restrict__ xg, double dt, int pass = 0) {
+  if (p.pack) offdiag_emit_as<NV, NP, true, false>(p, S, valid, i, j, bt, xg, dt, pass);
+  else offdiag_emit_as<NV, NP, false, false>(p, S, valid, i, j, bt, xg, dt, pass);
 }
 
 // ---- output stage for a row of the stencil: first direction i shared by the wave, second direction jb + lane -----
@@ -389,9 +417,10 @@ template <int NV, bool DIAG_ROW, class ST>
 __device__ __forceinline__ void rowblock_emit(const ST& S, int lane, int i, int jb, double* __restrict__ out, double* __restrict__ mirror,
                                               int64_t mstride, const double* __restrict__ a2, const double* __restrict__ d2, int64_t dstride,
                                               double dt, const double* __restrict__ f0g, const double* __restrict__ a1g,
-                                              double* __restrict__ d1g, const double* __restrict__ xg, bool skip_top = false) {
+                                              double* __restrict__ d1g, const double* __restrict__ xg, bool skip_top = false, bool pack = false) {
   constexpr int n = 2 * NV, RW = 16, NJ = (n + RW - 1) / RW, CG = LBS / RW, NIT = (NV + CG - 1) / CG;
   const int r1 = i % NV;                             // the configuration row the first direction (an x direction) touches
+  const int cs = pack ? NV + 2 : n;                  // doubles from one column of `out` to the next (pack: records; the caller's out, d2, dstride, d1g are the records')
   const double eps = sqrt(sqrt(DBL_EPSILON));
   const double eps2 = eps * eps;
   const int kk = lane % RW, cg = lane / RW;
@@ -423,9 +452,10 @@ __device__ __forceinline__ void rowblock_emit(const ST& S, int lane, int i, int 
       df *= 2;
       const double dd = df / eps2;
       d1k[j] = dd;
-      if (cg == 0 && k < n && !(skip_top && k < NV && k != r1)) d1g[k] = dd;   // (a configuration row other than r1: an exact zero, in memory)
+      if (cg == 0 && k < n && !(skip_top && k < NV && k != r1)) d1g[rec_row<NV>(pack, k, r1)] = dd;   // (a configuration row other than r1: an exact zero, in memory)
     } else {
-      d1k[j] = d1g[kc];
+      const double v = d1g[rec_row<NV>(pack, kc, r1)];
+      d1k[j] = rec_zero<NV>(pack, kc, r1) ? 0.0 : v;
     }
   }
   // software-pipelined over the column groups: the operands of group it + 1 are requested before group it is formed and stored
@@ -434,12 +464,14 @@ __device__ __forceinline__ void rowblock_emit(const ST& S, int lane, int i, int 
   auto fetch = [&](int it, double (&A)[NJ], double (&D)[NJ]) {
     const int c = it * CG + cg;
     const int cc = c < NV ? c : NV - 1;
+    const int rd = jb + cc < n ? (jb + cc) % NV : -1;   // the one configuration row the column's diagonal column holds
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int k = kk + RW * j;
       const int kc = k < n ? k : n - 1;
       A[j] = a2[kc + cc * n];
-      D[j] = d2[kc + cc * dstride];
+      const double v = d2[rec_row<NV>(pack, kc, rd) + cc * dstride];
+      D[j] = rec_zero<NV>(pack, kc, rd) ? 0.0 : v;
     }
   };
   auto form = [&](int it, const double (&A)[NJ], const double (&D)[NJ]) {
@@ -470,7 +502,7 @@ __device__ __forceinline__ void rowblock_emit(const ST& S, int lane, int i, int 
       df -= eps * A[j];
       df *= 2;
       const double val = 0.5 * (df / eps2 - d1k[j] - D[j]);
-      out[k + c * n] = val;
+      out[rec_row<NV>(pack, k, r1) + c * cs] = val;
       if (mirror) mirror[k + c * mstride] = val;
     }
   };
@@ -491,7 +523,10 @@ __device__ __forceinline__ void rowblock_emit(const ST& S, int lane, int i, int 
 //   g <  nv        : (q_g, u_lane)       cfg 1+g, vcfg nv+1+g   38 of 64 lanes
 //   g <  2 nv      : (v_{g-nv}, u_lane)  cfg 0,   vcfg 1+(g-nv) 38 of 64 lanes
 //   g >= 2 nv      : (u_i, u_j) pairs    cfg 0,   vcfg 0        64 pairs per wave
-template <class T, bool ROWS>
+// PACK (pairs only): the output stage writes packed records.  An instantiation of its own because this kernel sits at its
+// register bound: with the layout picked at run time inside the stage it gains scratch (132 -> 148-164 B per lane in three forms
+// tried), as a template parameter the contract-layout kernel is untouched and the record one needs no scratch
+template <class T, bool ROWS, bool PACK = false>
 __global__ __launch_bounds__(LBS, ROWS ? 1 : 3) void lin_static_tau_kernel(LinParams p) {
   constexpr int nv = T::N, n = 2 * nv;
   constexpr int TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS, G = ROWS ? 2 * nv : GU;
@@ -560,13 +595,15 @@ __global__ __launch_bounds__(LBS, ROWS ? 1 : 3) void lin_static_tau_kernel(LinPa
     // (the staging loop comes after these stores: the evaluation must meet its first use in its own basic block)
     __syncthreads();     // row nv of q is another lane's
     // column (k, u_c) of the (x_i, u) slab of f_ux: k + c n + i n m
+    const bool pack = kp->pack != 0;
+    const int64_t cs = pack ? nv + 2 : n;     // column stride of the tensors: records or contract columns
     rowblock_emit<nv, true>(S, lane, i, n, kp->fux + bt * n * mm * n + (int64_t)i * n * mm, nullptr, 0, kp->fu + bt * n * mm,
-                            kp->fuu + bt * n * mm * mm, (int64_t)n + (int64_t)n * mm, m.dt, kp->f_val + bt * n,
-                            kp->fx + bt * n * n + (int64_t)i * n, kp->fxx + bt * n * n * n + (int64_t)i * n + (int64_t)i * n * n, xg, kp->skip_top != 0);
+                            kp->fuu + bt * n * mm * mm, cs + (int64_t)n * mm, m.dt, kp->f_val + bt * n,
+                            kp->fx + bt * n * n + (int64_t)i * n, kp->fxx + bt * n * n * n + (int64_t)i * cs + (int64_t)i * n * n, xg, kp->skip_top != 0, pack);
   } else {
     OutStage<nv, LBS / 2>& S = s_lds.O;
     LinParams po;
-    po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top;
+    po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top; po.pack = kp->pack;
     const double dt = m.dt;
     __syncthreads();                       // every lane is done with the staged operands
 #pragma unroll 1
@@ -576,7 +613,7 @@ __global__ __launch_bounds__(LBS, ROWS ? 1 : 3) void lin_static_tau_kernel(LinPa
 #pragma unroll
         for (int k = 0; k < nv; ++k) S.qdd[(lane % (LBS / 2)) * (nv + 1) + k] = s.uu[k];
       }
-      offdiag_emit<nv, LBS / 2>(po, S, valid, i, j, bt, xg, dt, pass);
+      offdiag_emit_as<nv, LBS / 2, PACK, true>(po, S, valid, i, j, bt, xg, dt, pass);
     }
   }
 }
@@ -862,14 +899,16 @@ __global__ __launch_bounds__(LBS, ROWS ? 3 : 2) void lin_static_vel_kernel(LinPa
     for (int k = 0; k < nv; ++k) S.q[row * (nv + 1) + k] = s.uu[k];
     __syncthreads();
     // column (k, v_c) of slab q_i of f_xx: k + (nv + c) n + i n n; its mirror image: column q_i of slab v_c
-    rowblock_emit<nv, false>(S, lane, i, nv, fxx + (int64_t)nv * n + (int64_t)i * n * n,
+    const bool pack = kp->pack != 0;
+    const int64_t cs = pack ? nv + 2 : n;     // column stride of f_xx: records or contract columns
+    rowblock_emit<nv, false>(S, lane, i, nv, fxx + (int64_t)nv * cs + (int64_t)i * n * n,
                              kp->skip_qv_mirror ? nullptr : fxx + (int64_t)i * n + (int64_t)nv * n * n, (int64_t)n * n,
-                             fxb + (int64_t)nv * n, fxx + (int64_t)nv * n + (int64_t)nv * n * n, (int64_t)n + (int64_t)n * n, dt,
-                             kp->f_val + bt * n, fxb + (int64_t)i * n, fxx + (int64_t)i * n + (int64_t)i * n * n, c.xg, kp->skip_top != 0);
+                             fxb + (int64_t)nv * n, fxx + (int64_t)nv * cs + (int64_t)nv * n * n, cs + (int64_t)n * n, dt,
+                             kp->f_val + bt * n, fxb + (int64_t)i * n, fxx + (int64_t)i * cs + (int64_t)i * n * n, c.xg, kp->skip_top != 0, pack);
   } else {
     constexpr int NP = LBS / 2;
     LinParams po;
-    po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top;
+    po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top; po.pack = kp->pack;
     __syncthreads();                       // every lane is done with the staged operands
     // point-major with an odd stride (OutStage); the second half of the wave parks its values in the spare row for now.
     // Unconditional stores right behind the evaluation (see the torque-level kernel)
@@ -1180,7 +1219,7 @@ __global__ __launch_bounds__(LBS) void lin_static_cfg_down_kernel(LinParams p, c
   typedef __attribute__((address_space(4))) const LinParams* kernarg_t;
   const kernarg_t kp = (kernarg_t)__builtin_amdgcn_kernarg_segment_ptr();
   LinParams po;
-  po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top;
+  po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top; po.pack = kp->pack;
   offdiag_emit<nv, LBS>(po, S, valid, c.i, c.j, bt, c.xg, model->dt);
 }
 
@@ -1441,7 +1480,7 @@ __global__ __launch_bounds__(LBS, 2) void lin_static_cfg_pair_kernel(LinParams p
   typedef __attribute__((address_space(4))) const LinParams* kernarg_t;
   const kernarg_t kp = (kernarg_t)__builtin_amdgcn_kernarg_segment_ptr();
   LinParams po;
-  po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top;
+  po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top; po.pack = kp->pack;
   offdiag_emit<nv, LBS>(po, S, valid, c.i, c.j, bt, c.xg, c.m->dt);
 }
 
@@ -1455,7 +1494,7 @@ __global__ __launch_bounds__(LBS, 2) void lin_static_cfg_pair_kernel(LinParams p
 template <int NV, bool DIAG>
 __device__ __forceinline__ void first_output(const double* q /* LDS, lane-major, stride NV + 1 */, int lane, int d0, double* __restrict__ out,
                                              int64_t ostride, const double* __restrict__ fcol, const double* __restrict__ f0,
-                                             const double* __restrict__ xg, double dt, double eps, bool skip_top = false) {
+                                             const double* __restrict__ xg, double dt, double eps, bool skip_top = false, bool pack = false) {
   constexpr int n = 2 * NV, TOT = NV * n;
   const double eps2 = eps * eps;
   for (int e = lane; e < TOT; e += LBS) {
@@ -1477,7 +1516,7 @@ __device__ __forceinline__ void first_output(const double* q /* LDS, lane-major,
       double df = fv - f0[k];
       df -= eps * fcol[e];
       df *= 2;
-      out[k + c * ostride] = df / eps2;
+      out[rec_row<NV>(pack, k, d < n ? d % NV : -1) + c * ostride] = df / eps2;
     } else {
       out[e] = (fv - f0[k]) / eps;
     }
@@ -1561,10 +1600,12 @@ __global__ __launch_bounds__(LBS) void lin_static_first_kernel(LinParams p, cons
   int64_t ostride = n;
   if constexpr (DIAG) {
     // column (d, d): f_xx at d (n + n n), f_uu at d (n + n m)
-    if (LEVEL == 3) { out = kp->fuu + bt * n * nv * nv; ostride = n + (int64_t)n * nv; }
-    else { ostride = n + (int64_t)n * n; out = kp->fxx + bt * n * n * n + (LEVEL == 2 ? nv * ostride : 0); }
+    const int64_t cs = kp->pack ? nv + 2 : n;     // column stride of the tensors: records (LinParams::pack) or contract columns
+    if (LEVEL == 3) { out = kp->fuu + bt * n * nv * nv; ostride = cs + (int64_t)n * nv; }
+    else { ostride = cs + (int64_t)n * n; out = kp->fxx + bt * n * n * n + (LEVEL == 2 ? nv * ostride : 0); }
   }
-  first_output<nv, DIAG>(s_q, lane, LEVEL == 1 ? 0 : (LEVEL == 2 ? nv : n), out, ostride, fcol, kp->f_val + bt * n, xg, model->dt, eps, kp->skip_top != 0);
+  first_output<nv, DIAG>(s_q, lane, LEVEL == 1 ? 0 : (LEVEL == 2 ? nv : n), out, ostride, fcol, kp->f_val + bt * n, xg, model->dt, eps, kp->skip_top != 0,
+                         DIAG && kp->pack != 0);
 }
 
 // ---- q- and v-caches ------------------------------------------------------------------------------------------------
@@ -1865,7 +1906,8 @@ static int lin_static_launch_t(ddp_hip_ctx* ctx, const LinParams& p, StaticLevel
   constexpr int nv = T::N, TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS;
   if (level == StaticLevel::Torque) {             // torque-level points (replaces lin_offdiag_kernel<NJ, 3>)
     hipLaunchKernelGGL((lin_static_tau_kernel<T, true>), dim3((unsigned)(BT * 2 * nv)), dim3(LBS), 0, ctx->stream, p);
-    hipLaunchKernelGGL((lin_static_tau_kernel<T, false>), dim3((unsigned)(BT * GU)), dim3(LBS), 0, ctx->stream, p);
+    if (p.pack) hipLaunchKernelGGL((lin_static_tau_kernel<T, false, true>), dim3((unsigned)(BT * GU)), dim3(LBS), 0, ctx->stream, p);
+    else hipLaunchKernelGGL((lin_static_tau_kernel<T, false, false>), dim3((unsigned)(BT * GU)), dim3(LBS), 0, ctx->stream, p);
   } else if (level == StaticLevel::Caches) {
     hipLaunchKernelGGL((lin_static_qvcache_kernel<T>), dim3((unsigned)((BT * p.ncfg + LBS - 1) / LBS)), dim3(LBS), 0, ctx->stream, p, p.model, p.x, p.qcache, p.vcache);
     if (p.nvcfg > 1) hipLaunchKernelGGL((lin_static_vcache_kernel<T>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.x, p.qcache, p.vcache);
