@@ -27,6 +27,7 @@ FLAG_NO_TENSORS, FLAG_TRACE, FLAG_TRACKING_COST, FLAG_CONTROL_BOUNDS = 1, 2, 4, 
 FLAG_FRAME_COST = 16
 FLAG_STATE_LIMITS = 32
 FLAG_FRAME_ORIENT_COST = 64
+FLAG_COM_COST = 128
 MAX_COST_FRAMES = 4
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
 
@@ -59,6 +60,7 @@ EXPORTS = [
     "ddp_hip_frame_cost_set_frames", "ddp_hip_frame_cost_upload", "ddp_hip_frame_cost_download",
     "ddp_hip_frame_orient_upload", "ddp_hip_frame_orient_download",
     "ddp_hip_state_limits_upload", "ddp_hip_state_limits_download",
+    "ddp_hip_com_cost_upload", "ddp_hip_com_cost_download", "ddp_hip_model_com",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -148,6 +150,10 @@ def lib():
     if hasattr(L, "ddp_hip_state_limits_upload"):    # (likewise: set_state_limits fails on an older build)
         L.ddp_hip_state_limits_upload.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_state_limits_download.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int64]
+    if hasattr(L, "ddp_hip_com_cost_upload"):        # (likewise: set_com_cost and ModelHandle.com fail on an older build)
+        L.ddp_hip_com_cost_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_com_cost_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_model_com.argtypes = [C.c_void_p, _dp, _dp, _dp]
     L.ddp_hip_rollout.argtypes = [C.c_void_p]
     L.ddp_hip_linearize.argtypes = [C.c_void_p]
     L.ddp_hip_linearize_stages.argtypes = [C.c_void_p, C.c_uint32]
@@ -307,6 +313,15 @@ class ModelHandle:
         p3, J = np.zeros(3), np.zeros(3 * self.nv)
         _check(lib().ddp_hip_model_frame(self._h, joint, _ptr(off), _ptr(q), _ptr(p3), _ptr(J) if jac else None), "model_frame")
         return p3, J.reshape(self.nv, 3).T.copy()
+
+
+    def com(self, q, jacobian=False):
+        """The centre of mass c(q) of a tree model; with jacobian=True (c, Jc), Jc = dc / d(delta q) as (3, nv): the true
+        jacobian of FLAG_COM_COST (ddp_hip.h)"""
+        q = _f64(q)
+        c3, J = np.zeros(3), np.zeros(3 * self.nv)
+        _check(lib().ddp_hip_model_com(self._h, _ptr(q), _ptr(c3), _ptr(J) if jacobian else None), "model_com")
+        return (c3, J.reshape(self.nv, 3).T.copy()) if jacobian else c3
 
 
 class ProblemSpec:
@@ -499,6 +514,35 @@ class Context:
         w = np.zeros((count, self.spec.T + 1, self.n_cost_frames, 3))
         _check(lib().ddp_hip_frame_orient_download(self._h, _ptr(q), _ptr(w), first, count), "frame_orient_download")
         return q, w
+
+    def set_com_cost(self, target=None, weight=None, first=0, count=None):
+        """The centre-of-mass terms of instances first .. first + count - 1 (a context created with FLAG_COM_COST; ddp_hip.h).
+        target: world positions, weight: per world axis, >= 0; each (T+1, 3) for every instance of the range or
+        (count, T+1, 3) with one per instance; weight also takes (3,) and scalars for every step.  None leaves that side as
+        it is."""
+        count = self.batch - first if count is None else count
+        per = (self.spec.T + 1, 3)
+        full = (count,) + per
+        arrs = {}
+        for name, arr in (("target", target), ("weight", weight)):
+            if arr is None:
+                continue
+            arr = np.asarray(arr, dtype=np.float64)
+            if not (arr.shape in (full, per) or (name == "weight" and arr.shape in ((3,), ()))):
+                raise ValueError(f"set_com_cost {name}: shape {arr.shape}, expected {per} or {full}")
+            arrs[name] = np.ascontiguousarray(np.broadcast_to(arr, full))
+        if arrs:
+            t, w = arrs.get("target"), arrs.get("weight")
+            _check(lib().ddp_hip_com_cost_upload(self._h, _ptr(t) if t is not None else None, _ptr(w) if w is not None else None,
+                                                 first, count), "com_cost_upload")
+
+    def com_cost(self, first=0, count=None):
+        """(target, weight) of instances first .. first + count - 1, each (count, T+1, 3)"""
+        count = self.batch - first if count is None else count
+        t = np.zeros((count, self.spec.T + 1, 3))
+        w = np.zeros((count, self.spec.T + 1, 3))
+        _check(lib().ddp_hip_com_cost_download(self._h, _ptr(t), _ptr(w), first, count), "com_cost_download")
+        return t, w
 
     def set_state_limits(self, lo=None, hi=None, weight=None, first=0, count=None):
         """The soft state limits of instances first .. first + count - 1 (a context created with FLAG_STATE_LIMITS; ddp_hip.h),

@@ -260,6 +260,13 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   if (prob->fd_mode < 0 || prob->fd_mode > 2) return DDP_HIP_E_ARG;
   if ((flags & DDP_HIP_FLAG_FRAME_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // frames are points of a tree's joints
   if ((flags & DDP_HIP_FLAG_FRAME_ORIENT_COST) && !(flags & DDP_HIP_FLAG_FRAME_COST)) return DDP_HIP_E_ARG;   // the orientation terms are of the cost frames
+  if (flags & DDP_HIP_FLAG_COM_COST) {
+    if (mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the CoM is of a tree's bodies
+    if (!mo.mass_j || !mo.jtype) return DDP_HIP_E_ARG;
+    double total = 0.0;
+    for (int i = 0; i < (mo.jtype[0] == DDP_HIP_JOINT_FREEFLYER ? mo.nv - 5 : mo.nv); ++i) total += mo.mass_j[i];
+    if (!(total > 0.0) || !isfinite(total)) return DDP_HIP_E_ARG;      // c(q) divides by the total mass
+  }
   if (prob->eq_kind != DDP_HIP_EQ_NONE && (!prob->ne || prob->eq_advance < 0 || prob->eq_advance > 4)) return DDP_HIP_E_ARG;
   if (prob->eq_kind == DDP_HIP_EQ_FRAME && (mo.kind != DDP_HIP_MODEL_TREE || prob->frame_joint < 0 ||
                                             prob->frame_joint >= (mo.jtype && mo.jtype[0] == DDP_HIP_JOINT_FREEFLYER ? mo.nv - 5 : mo.nv)))
@@ -374,6 +381,13 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipMalloc(&ctx->fo_weight_d, sizeof(double) * (size_t)(slots * 3)));
     if (frame_orient_reset(ctx) != DDP_HIP_OK) { ddp_hip_destroy(ctx); return DDP_HIP_E_HIP; }
   }
+  if (flags & DDP_HIP_FLAG_COM_COST) {
+    const size_t words = (size_t)(d.batch * (d.T + 1) * 3);
+    CTX_TRY(hipMalloc(&ctx->cm_target_d, sizeof(double) * words));
+    CTX_TRY(hipMalloc(&ctx->cm_weight_d, sizeof(double) * words));
+    CTX_TRY(hipMemsetAsync(ctx->cm_target_d, 0, sizeof(double) * words, ctx->stream));
+    CTX_TRY(hipMemsetAsync(ctx->cm_weight_d, 0, sizeof(double) * words, ctx->stream));
+  }
   if (flags & DDP_HIP_FLAG_STATE_LIMITS) {
     // lo = -inf, hi = +inf, w = 0: no limit anywhere
     const int64_t words = d.batch * (d.T + 1) * d.n;
@@ -407,6 +421,8 @@ extern "C" int ddp_hip_destroy(ddp_hip_ctx* ctx) {
   if (ctx->fc_weight_d) (void)hipFree(ctx->fc_weight_d);
   if (ctx->fo_quat_d) (void)hipFree(ctx->fo_quat_d);
   if (ctx->fo_weight_d) (void)hipFree(ctx->fo_weight_d);
+  if (ctx->cm_target_d) (void)hipFree(ctx->cm_target_d);
+  if (ctx->cm_weight_d) (void)hipFree(ctx->cm_weight_d);
   if (ctx->sl_d) (void)hipFree(ctx->sl_d);
   if (ctx->ne_d) (void)hipFree(ctx->ne_d);
   if (ctx->Epre_d) (void)hipFree(ctx->Epre_d);
@@ -644,6 +660,52 @@ extern "C" int ddp_hip_frame_orient_download(ddp_hip_ctx* ctx, double* quat, dou
   HIP_TRY(hipSetDevice(ctx->device));
   if (quat) HIP_TRY(hipMemcpyAsync(quat, ctx->fo_quat_d + first * slots * 4, sizeof(double) * (size_t)(slots * 4 * count), hipMemcpyDeviceToHost, ctx->stream));
   if (weight) HIP_TRY(hipMemcpyAsync(weight, ctx->fo_weight_d + first * slots * 3, sizeof(double) * (size_t)(slots * 3 * count), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return DDP_HIP_OK;
+}
+
+// ---- centre-of-mass cost (DDP_HIP_FLAG_COM_COST): target and weights per (instance, t) -----------------------------------
+static int com_cost_range(ddp_hip_ctx* ctx, int64_t first, int64_t count) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_COM_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (first < 0 || count < 0 || first + count > ctx->d.batch) return DDP_HIP_E_ARG;
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_com_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first, int64_t count) {
+  int rc = com_cost_range(ctx, first, count);
+  if (rc != DDP_HIP_OK) return rc;
+  const int64_t sz = (ctx->d.T + 1) * 3;
+  bool nonzero = false;
+  if (target)
+    for (int64_t i = 0; i < sz * count; ++i)
+      if (!isfinite(target[i])) return DDP_HIP_E_ARG;
+  if (weight)
+    for (int64_t i = 0; i < sz * count; ++i) {
+      if (!cost_weight_ok(weight[i])) return DDP_HIP_E_ARG;
+      nonzero |= weight[i] != 0.0;
+    }
+  if (count == 0 || (!target && !weight)) return DDP_HIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  // the candidates' term array of the line search exists from the first non-zero weight on (fwd.hip: com_cost_kernel)
+  if (nonzero && !ctx->cm_new) HIP_TRY(hipMalloc(&ctx->cm_new, sizeof(double) * (size_t)(ctx->d.batch * ctx->n_alpha_max * (ctx->d.T + 1))));
+  if (target) HIP_TRY(hipMemcpyAsync(ctx->cm_target_d + first * sz, target, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
+  if (weight) HIP_TRY(hipMemcpyAsync(ctx->cm_weight_d + first * sz, weight, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  // exactly fc_live's rule: any non-zero weight switches the kernels on, only ONE upload of zeros for the whole batch switches
+  // them off again
+  if (weight) ctx->cm_live = nonzero || (ctx->cm_live && !(first == 0 && count == ctx->d.batch));
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_com_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first, int64_t count) {
+  int rc = com_cost_range(ctx, first, count);
+  if (rc != DDP_HIP_OK) return rc;
+  const int64_t sz = (ctx->d.T + 1) * 3;
+  if (count == 0 || (!target && !weight)) return DDP_HIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (target) HIP_TRY(hipMemcpyAsync(target, ctx->cm_target_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
+  if (weight) HIP_TRY(hipMemcpyAsync(weight, ctx->cm_weight_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return DDP_HIP_OK;
 }

@@ -11,6 +11,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "com_cost.h"
 #include "frame_cost.h"
 #include "internal.h"
 #include "rbd.h"
@@ -719,6 +720,64 @@ __global__ void cand_sum_kernel(FwdParams p) {
   p.fw_dcost[(int64_t)b * na + a] = dsum;
 }
 
+// The centre-of-mass terms (DDP_HIP_FLAG_COM_COST, ddp_hip.h) of a list of states, in kernels of their own that add onto what the
+// kernels above leave (none of them knows the term).  The list: `count` (trajectory, t) pairs, t = 0 .. T, trajectory k's states
+// at xs + k traj_stride, `na` trajectories per instance (1: a resident trajectory, n_alpha: the candidates of fw_x).  `lpe` lanes
+// (a power of two >= the joint count) cooperate on one evaluation, 64 / lpe evaluations per wave: lane j walks joint j's path
+// with its body's CoM alone (rbd::com_body_point: no per-joint arrays, no scratch) and leaves m_j p_j in LDS, the group's first
+// lane adds them up in ascending order (rbd::com_fold) and forms 1/2 sum_a w_a (c_a - g_a)^2.  A term of weight 0 is left out,
+// and with all three of them the walk: such a pair adds nothing (add != 0) or stores +0 (add == 0).  add != 0: out[pair] +=
+// term (COSTS_OLD / COSTS_NEW behind cost_kernel); add == 0: out[pair] = term (cm_new of a line-search round), and the
+// candidates the rollout kernels skip (state != 0, beyond 2^-33) are skipped here.  A non-finite state gives a NaN term, as
+// frame_cost_sum does: the candidate's sum is NaN and select_kernel's `<= 0` does not accept it
+__global__ __launch_bounds__(64) void com_cost_kernel(CoMCostDev cm, const DevModel* model, const double* xs, int64_t traj_stride,
+                                                      int64_t count, int32_t T1, int32_t nx, int32_t na, int32_t lpe, const int32_t* state,
+                                                      int32_t round, double* out, int32_t add) {
+  __shared__ double s_m[64], s_mp[64 * 3];
+  const DevModel& m = *model;
+  const int tid = threadIdx.x, g = tid / lpe, j = tid % lpe;
+  const int64_t e = (int64_t)blockIdx.x * (64 / lpe) + g;
+  bool live = e < count;
+  int64_t traj = 0, bt1 = 0;
+  int t = 0;
+  if (live) {
+    traj = e / T1;
+    t = (int)(e % T1);
+    const int64_t b = traj / na;
+    if (state && (state[b] != 0 || round * na + (int)(traj % na) > 33)) live = false;
+    bt1 = b * T1 + t;
+  }
+  const bool skip = !live;                                           // nothing is written for this pair
+  if (live && !rbd::frame_weights_any(cm.weight + bt1 * 3)) live = false;
+  if (live && j < m.nj) s_m[tid] = rbd::com_body_point(m, m.ff != 0, j, xs + traj * traj_stride + (int64_t)t * nx, s_mp + 3 * tid);
+  __syncthreads();
+  if (j != 0 || skip) return;
+  double term = 0.0;
+  if (live) {
+    const double* w = cm.weight + bt1 * 3;
+    const double* gt = cm.target + bt1 * 3;
+    double c[3], s = 0.0;
+    rbd::com_fold(s_m + tid, s_mp + 3 * tid, m.nj, c);
+    for (int a = 0; a < 3; ++a) { const double r = c[a] - gt[a]; if (w[a] != 0.0) s += w[a] * r * r; }
+    term = 0.5 * s;
+  } else if (add) return;
+  if (add) out[e] += term;
+  else out[e] = term;
+}
+// ... and one lane per (instance, candidate) adds a candidate's terms up in ascending t and adds the sum once onto what the
+// rollout path left in fw_dcost (sum_t (new term without the CoM's - COSTS_OLD[t]): COSTS_OLD holds the old trajectory's CoM
+// terms already), before select_kernel reads it.  A sum of +0 (an instance without CoM weights) is not added: its -0 stays -0
+__global__ void com_sum_kernel(const double* cm_new, double* fw_dcost, const int32_t* state, int32_t batch, int32_t na, int32_t round, int64_t T) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= batch * na) return;
+  const int b = gid / na, a = gid % na;
+  if (state[b] != 0 || round * na + a > 33) return;                  // (beyond 2^-33 the INFINITY stays)
+  const double* c = cm_new + (int64_t)gid * (T + 1);
+  double s = 0.0;
+  for (int64_t t = 0; t <= T; ++t) s += c[t];
+  if (s != 0.0) fw_dcost[gid] += s;
+}
+
 // accept rule (ddp_fwd.ipp:56-60): the first (= largest) candidate with sum(new - old) <= 0; the winner's
 // trajectory becomes (X_NEW, U_NEW).  grid = batch.
 __global__ void select_kernel(FwdParams p) {
@@ -866,6 +925,7 @@ void fwd_teardown(ddp_hip_ctx* ctx) {
   if (ctx->fw_u) (void)hipFree(ctx->fw_u);
   if (ctx->fw_dcost) (void)hipFree(ctx->fw_dcost);
   if (ctx->fw_cost) (void)hipFree(ctx->fw_cost);
+  if (ctx->cm_new) (void)hipFree(ctx->cm_new);
   if (ctx->step_d) (void)hipFree(ctx->step_d);
   if (ctx->fw_dcost_acc_d) (void)hipFree(ctx->fw_dcost_acc_d);
   if (ctx->pick_pair_d) (void)hipFree(ctx->pick_pair_d);
@@ -911,6 +971,17 @@ extern "C" int ddp_hip_rollout(ddp_hip_ctx* ctx) {
     else LAUNCH(0, false);                                     \
   } while (0)
 
+// com_cost_kernel over `count` (trajectory, t) pairs of trajectories laid out like X (na per instance)
+static void launch_com_cost(ddp_hip_ctx* ctx, const CoMCostDev& cm, const double* xs, int na, int64_t count, const int32_t* state, int round,
+                            double* out, int add) {
+  const Dims& d = ctx->d;
+  int lpe = 8;
+  while (lpe < ctx->model_h.nj) lpe *= 2;                            // (nj <= DDP_MAXJ = 64: one wave)
+  const int64_t per = 64 / lpe;
+  hipLaunchKernelGGL(com_cost_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(64), 0, ctx->stream, cm, ctx->model_d, xs,
+                     (d.T + 1) * d.nx, count, (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, (int32_t)lpe, state, (int32_t)round, out, (int32_t)add);
+}
+
 static int launch_cost(ddp_hip_ctx* ctx, FwdParams& p, int which) {
   const int bs = 64;
   const int64_t total = ctx->d.batch * (ctx->d.T + 1);
@@ -920,6 +991,9 @@ static int launch_cost(ddp_hip_ctx* ctx, FwdParams& p, int which) {
   DISPATCH_COST(p, LAUNCH);
 #undef LAUNCH
 #undef CALL
+  const CoMCostDev cm = com_cost_dev(ctx);
+  if (cm.target)                                                     // + the CoM terms, onto what cost_kernel has left
+    launch_com_cost(ctx, cm, which == 0 ? p.x_old : p.x_new, 1, total, nullptr, 0, which == 0 ? p.costs_old : p.costs_new, 1);
   HIP_TRY(hipGetLastError());
   return DDP_HIP_OK;
 }
@@ -952,6 +1026,7 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
   p.n_alpha = n_alpha;
   p.no_linesearch = no_linesearch ? 1 : 0;
   int rc = launch_cost(ctx, p, 0);                                   // ddp_fwd.ipp:24-26
+  const CoMCostDev cm = com_cost_dev(ctx);
   if (rc != DDP_HIP_OK) return rc;
   const int bs = 64;
   const unsigned grid = (unsigned)((B * n_alpha + bs - 1) / bs);
@@ -984,6 +1059,12 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
 #undef CALL
     }
     prof_end(ctx, DDP_HIP_K_FWD_ROLLOUT);
+    if (cm.target) {
+      // the candidates' CoM terms, whichever rollout path ran: over fw_x into cm_new, then once onto fw_dcost
+      launch_com_cost(ctx, cm, p.fw_x, n_alpha, B * n_alpha * (d.T + 1), p.state, round, ctx->cm_new, 0);
+      hipLaunchKernelGGL(com_sum_kernel, dim3((unsigned)((B * n_alpha + 63) / 64)), dim3(64), 0, ctx->stream, ctx->cm_new, p.fw_dcost, p.state,
+                         (int32_t)B, (int32_t)n_alpha, (int32_t)round, d.T);
+    }
     hipLaunchKernelGGL(select_kernel, dim3((unsigned)B), dim3(256), 0, ctx->stream, p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(state.data(), ctx->fw_state_d, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));

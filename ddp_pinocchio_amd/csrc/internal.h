@@ -260,6 +260,12 @@ struct ddp_hip_ctx {
   double* sl_d = nullptr;                     // lo | hi | weight, each [batch][T+1][n]
   bool sl_live = false;                       // some non-zero weight was uploaded: the kernels form the terms
 
+  // centre-of-mass cost (DDP_HIP_FLAG_COM_COST; ctx.hip: ddp_hip_com_cost_*, com_cost.h)
+  double* cm_target_d = nullptr;              // [batch][T+1][3]
+  double* cm_weight_d = nullptr;
+  double* cm_new = nullptr;                   // [batch][n_alpha_max][T+1] the candidates' CoM terms of a line-search round (since the first non-zero weight)
+  bool cm_live = false;                       // as fc_live: the CoM kernels are launched
+
   bool box_dirty = false;       // CTRL_LO / CTRL_HI were uploaded since lo <= hi was last checked (ctx.hip: box_check)
 
   bool async_mode = false;     // ddp_hip_set_async: entry points that hand nothing back to the host do not wait for the stream

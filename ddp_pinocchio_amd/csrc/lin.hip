@@ -13,6 +13,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include "com_cost.h"
 #include "frame_cost.h"
 #include "internal.h"
 #include "lin_common.h"
@@ -267,6 +268,56 @@ __global__ __launch_bounds__(64) void lin_limit_cost_kernel(LinParams p, StateLi
     if (e == 0.0) continue;
     gx[i] += wi * e;
     gxx[i + (int64_t)i * n] += wi;
+  }
+}
+
+// Centre-of-mass cost (DDP_HIP_FLAG_COM_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost kernel
+// on the same stream (the fixed order of additions: cost, tracking, frame positions, frame orientations, limits, CoM): their
+// output is the starting point.  Every joint has a column, so the work is lane-parallel over joints: lane j walks its own path
+// once and leaves a_j, o_j, m_j p_j and the path as a bit mask in LDS (rbd::com_stage_lane); lane j then forms the mass and
+// first moment of its subtree over the records in ascending order and its column of Jc (rbd::com_column_lane); then the wave adds
+//   lx[i] += sum_a Jc[a][i] (w_a r_a),   lxx[i][j] += sum_a Jc[a][min] w_a Jc[a][max]     (Gauss-Newton),   r = c(q) - g
+// over the tangent rows i, j < nv, the axes in their fixed order and entry (i, j) in (min, max) order: the block stays symmetric
+// bit for bit.  It reads p.x and touches nothing but those entries.  A term of weight 0 is left out, a block whose three weights
+// are 0 returns at once.  t = T: lfx / lfxx
+__global__ __launch_bounds__(64) void lin_com_cost_kernel(LinParams p, CoMCostDev cm) {
+  const int64_t T = p.d.T;
+  const int64_t bt1 = blockIdx.x;
+  const int b = (int)(bt1 / (T + 1));
+  const int64_t t = bt1 % (T + 1);
+  const int n = (int)p.d.n, nv = (int)p.d.nv, nx = (int)p.d.nx;
+  const int tid = threadIdx.x;
+  const double* w = cm.weight + bt1 * 3;
+  if (!rbd::frame_weights_any(w)) return;
+  const DevModel& m = *p.model;
+  const double* q = p.x + bt1 * nx;
+  __shared__ rbd::CoMWaveLds S;
+  __shared__ double s_w[3], s_wr[3];
+  if (tid < m.nj) rbd::com_stage_lane(m, q, tid, S);
+  __syncthreads();
+  if (tid < m.nj) rbd::com_column_lane(m, q, tid, S);
+  __syncthreads();
+  if (tid < 3) {
+    const double wa = w[tid];
+    s_w[tid] = wa;
+    s_wr[tid] = wa != 0.0 ? wa * (S.c[tid] - cm.target[bt1 * 3 + tid]) : 0.0;
+  }
+  __syncthreads();
+  double* gx = t < T ? p.lx + ((int64_t)b * T + t) * n : p.lfx + (int64_t)b * n;
+  double* gxx = t < T ? p.lxx + ((int64_t)b * T + t) * n * n : p.lfxx + (int64_t)b * n * n;
+  for (int i = tid; i < nv; i += blockDim.x) {
+    double s = 0.0;
+    for (int a = 0; a < 3; ++a)
+      if (s_w[a] != 0.0) s += S.J[3 * i + a] * s_wr[a];
+    gx[i] += s;
+  }
+  for (int e = tid; e < nv * nv; e += blockDim.x) {
+    const int i = e % nv, j = e / nv;
+    const int lo = i < j ? i : j, hi = i < j ? j : i;
+    double h = 0.0;
+    for (int a = 0; a < 3; ++a)
+      if (s_w[a] != 0.0) h += S.J[3 * lo + a] * s_w[a] * S.J[3 * hi + a];
+    gxx[i + (int64_t)j * n] += h;
   }
 }
 
@@ -1103,6 +1154,8 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     if (fc.oquat) hipLaunchKernelGGL(lin_frame_orient_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, fc);
     const StateLimitsDev sl = state_limits_dev(ctx);
     if (sl.weight) hipLaunchKernelGGL(lin_limit_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, sl);
+    const CoMCostDev cm = com_cost_dev(ctx);
+    if (cm.target) hipLaunchKernelGGL(lin_com_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, cm);
   }
   // the q- / v-caches of the mode-2 stencil also serve the first order (base configuration and base (q, v)), so they are built
   // ahead of whichever stage comes first

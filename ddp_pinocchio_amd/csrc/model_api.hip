@@ -7,6 +7,7 @@
 
 #include <new>
 
+#include "com_cost.h"
 #include "internal.h"
 #include "rbd.h"
 #include "rbd_deriv.h"
@@ -73,6 +74,18 @@ __global__ void model_frame_kernel(const DevModel* m, const double* in, double* 
   rbd::frame_position<NJ>(*m, q, out, want_jac ? out + 3 : nullptr);
 }
 
+// c(q) and Jc by one wave, with the traversal of the CoM cost kernels (com_cost.h): out = c[3] | Jc[3 nv]
+__global__ __launch_bounds__(64) void model_com_kernel(const DevModel* m, const double* in, double* out) {
+  __shared__ rbd::CoMWaveLds S;
+  const int tid = threadIdx.x;
+  if (tid < m->nj) rbd::com_stage_lane(*m, in, tid, S);
+  __syncthreads();
+  if (tid < m->nj) rbd::com_column_lane(*m, in, tid, S);
+  __syncthreads();
+  if (tid < 3) out[tid] = S.c[tid];
+  for (int i = tid; i < 3 * m->nv; i += blockDim.x) out[3 + i] = S.J[i];
+}
+
 #define MODEL_DISPATCH(nv, CALL)       \
   do {                                 \
     if ((nv) <= 6) { CALL(6); }        \
@@ -101,6 +114,8 @@ int run(ddp_hip_model_handle* h, const double* in, size_t n_in, double* out, siz
     } else if (nv <= 6) hipLaunchKernelGGL((model_aba_deriv_kernel<6>), dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o);
     else if (nv <= 38) hipLaunchKernelGGL((model_aba_deriv_kernel<38>), dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o);
     else return DDP_HIP_E_UNSUPPORTED;
+  } else if (what == 3) {
+    hipLaunchKernelGGL(model_com_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o);
   } else {
 #define CALL(NJ) hipLaunchKernelGGL((model_frame_kernel<NJ>), dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac)
     MODEL_DISPATCH(nv, CALL);
@@ -191,6 +206,20 @@ extern "C" int ddp_hip_model_frame(ddp_hip_model_handle* h, int32_t joint, const
   const int rc = run(h, q, (size_t)h->model_h.nq, out, (size_t)(3 + (J ? 3 * nv : 0)), 2, J ? 1 : 0);
   if (rc != DDP_HIP_OK) return rc;
   memcpy(p3, out, sizeof(double) * 3);
+  if (J) memcpy(J, out + 3, sizeof(double) * 3 * nv);
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_model_com(ddp_hip_model_handle* h, const double* q, double* c3, double* J) {
+  if (!h || !q || !c3 || h->model_h.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_ARG;
+  const int nv = h->model_h.nv;
+  double total = 0.0;
+  for (int i = 0; i < h->model_h.nj; ++i) total += h->model_h.I6[i][9];   // the body masses (ctx.hip: pack_body_inertia)
+  if (!(total > 0.0)) return DDP_HIP_E_ARG;
+  double out[3 + 3 * DDP_MAXJ];
+  const int rc = run(h, q, (size_t)h->model_h.nq, out, (size_t)(3 + (J ? 3 * nv : 0)), 3, 0);
+  if (rc != DDP_HIP_OK) return rc;
+  memcpy(c3, out, sizeof(double) * 3);
   if (J) memcpy(J, out + 3, sizeof(double) * 3 * nv);
   return DDP_HIP_OK;
 }

@@ -215,6 +215,26 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * orientation weights are independent: with nothing uploaded or all orientation weights 0 a context computes bit for bit what
  * it computes with DDP_HIP_FLAG_FRAME_COST alone. */
 #define DDP_HIP_FLAG_FRAME_ORIENT_COST 64u
+/* Give every instance a centre-of-mass (CoM) tracking term: balance tasks.  The model is a tree with body masses m_i (mass_j),
+ * body CoMs c_i in the joint frame (com) and total mass M = sum_i m_i > 0 (else ddp_hip_create returns DDP_HIP_E_ARG):
+ *   c(q) = (1/M) sum_i m_i p_i(q),      p_i(q) = world position of the point c_i of joint i
+ * Per instance b and t = 0 .. T a target g[b][t] in R^3 and weights w[b][t] in R^3 (per world axis, >= 0), r = c(q_t) - g[b][t]:
+ *   l(t, x, u) += 1/2 sum_a w[b][t][a] r_a^2      t < T
+ *   lf(x_T)    += 1/2 sum_a w[b][T][a] r_a^2
+ * to whatever the context optimises otherwise; "CoM over the foot, height free" is w = (w, w, 0).
+ * Derivatives in the tangent at x, Jc = dc / d(delta q) (3 x nv), by column, with m_sub_j and c_sub_j the mass and the CoM of
+ * the subtree rooted at joint j (itself included), a_j the world axis and o_j the world origin of joint j:
+ *   revolute joint j:   (m_sub_j / M) a_j x (c_sub_j - o_j)          prismatic joint j:   (m_sub_j / M) a_j
+ *   free-flyer root (body twists, linear part first): R_0 e_c for the linear columns, (R_0 e_c) x (c - o_0) for the angular ones;
+ * equivalently Jc = (1/M) sum_i m_i P_i with P_i the true point jacobian of DDP_HIP_FLAG_FRAME_COST.
+ *   lx[q rows] += Jc^T (w o r),  lxx[q, q] += Jc^T diag(w) Jc,  lfx / lfxx alike at T;
+ * velocity rows and columns, lu, luu and lux are untouched.  lxx is Gauss-Newton (the term sum_a w_a r_a d^2 c_a is dropped:
+ * exact where r = 0); entry (i, j) is formed in (min, max) order with the axes in fixed order: symmetric bit for bit.  The data
+ * travels through ddp_hip_com_cost_* below, not through ddp_hip_upload or ddp_hip_device_ptr.  At create targets and weights
+ * are 0.  A term of weight 0 is left out (not multiplied by 0); with nothing uploaded or every weight 0 a context computes bit
+ * for bit what it computes without the flag.  Tree models only (the pendulum: DDP_HIP_E_UNSUPPORTED).  The flag combines with
+ * every other flag: the terms are formed by kernels of their own, which add onto what the other terms' kernels leave. */
+#define DDP_HIP_FLAG_COM_COST 128u
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -263,6 +283,12 @@ int ddp_hip_frame_orient_download(ddp_hip_ctx* ctx, double* quat, double* weight
 int ddp_hip_state_limits_upload(ddp_hip_ctx* ctx, const double* lo, const double* hi, const double* weight, int64_t first_instance,
                                 int64_t n_instances);
 int ddp_hip_state_limits_download(ddp_hip_ctx* ctx, double* lo, double* hi, double* weight, int64_t first_instance, int64_t n_instances);
+/* The CoM targets and weights of a context created with DDP_HIP_FLAG_COM_COST (else DDP_HIP_E_UNSUPPORTED), stream-ordered like
+ * ddp_hip_frame_cost_upload.  Host arrays [n_instances][T+1][3]; a NULL pointer leaves that side as it is.  An upload is refused
+ * as a whole (DDP_HIP_E_ARG, nothing written) for a bad instance range, a non-finite target and a negative or non-finite
+ * weight. */
+int ddp_hip_com_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first_instance, int64_t n_instances);
+int ddp_hip_com_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first_instance, int64_t n_instances);
 
 /* make_trajectory (ddp.hpp:392-415): X[0] and U given -> X[1..T] */
 int ddp_hip_rollout(ddp_hip_ctx* ctx);
@@ -407,6 +433,9 @@ int ddp_hip_model_aba_derivatives(ddp_hip_model_handle* h, const double* q, cons
 /* model_t::frame_coordinates / d_frame_coordinates, pinocchio_model.ipp:418-462 (J: 3 x nv, may be NULL; the reference's
  * WORLD-frame rows) */
 int ddp_hip_model_frame(ddp_hip_model_handle* h, int32_t joint, const double off[3], const double* q, double* p3, double* J);
+/* The centre of mass c(q) of a tree model and, if J is not NULL, Jc = dc / d(delta q) as 3 x nv column-major: the true jacobian
+ * of DDP_HIP_FLAG_COM_COST, formed by the traversal the cost kernels use.  For targets such as "where the CoM is now, plus 5 cm" */
+int ddp_hip_model_com(ddp_hip_model_handle* h, const double* q, double* c3, double* J);
 
 /* ---- built-in seeded model tables (no URDF exists offline: SURVEY.md D4, 8d) -------------- */
 /* ..._FF: the same robots on a free-flyer root instead of a fixed base / 3 prismatic + 3 revolute base joints */
