@@ -28,6 +28,7 @@ FLAG_FRAME_COST = 16
 FLAG_STATE_LIMITS = 32
 FLAG_FRAME_ORIENT_COST = 64
 FLAG_COM_COST = 128
+FLAG_FRAME_VEL_COST = 256
 MAX_COST_FRAMES = 4
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
 
@@ -61,6 +62,7 @@ EXPORTS = [
     "ddp_hip_frame_orient_upload", "ddp_hip_frame_orient_download",
     "ddp_hip_state_limits_upload", "ddp_hip_state_limits_download",
     "ddp_hip_com_cost_upload", "ddp_hip_com_cost_download", "ddp_hip_model_com",
+    "ddp_hip_frame_vel_upload", "ddp_hip_frame_vel_download", "ddp_hip_model_frame_velocity",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -154,6 +156,10 @@ def lib():
         L.ddp_hip_com_cost_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_com_cost_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_model_com.argtypes = [C.c_void_p, _dp, _dp, _dp]
+    if hasattr(L, "ddp_hip_frame_vel_upload"):       # (likewise: set_frame_vel_cost and ModelHandle.frame_velocity)
+        L.ddp_hip_frame_vel_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_frame_vel_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_model_frame_velocity.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]
     L.ddp_hip_rollout.argtypes = [C.c_void_p]
     L.ddp_hip_linearize.argtypes = [C.c_void_p]
     L.ddp_hip_linearize_stages.argtypes = [C.c_void_p, C.c_uint32]
@@ -322,6 +328,16 @@ class ModelHandle:
         c3, J = np.zeros(3), np.zeros(3 * self.nv)
         _check(lib().ddp_hip_model_com(self._h, _ptr(q), _ptr(c3), _ptr(J) if jacobian else None), "model_com")
         return (c3, J.reshape(self.nv, 3).T.copy()) if jacobian else c3
+    def frame_velocity(self, joint, off, q, v, jacobian=False):
+        """The velocity (pdot, omega) of the point `off` of joint `joint` at the state (q, v), world-aligned axes, as (6,); with
+        jacobian=True (vel6, Jq, Jv), Jq = d vel6 / d(delta q) and Jv = d vel6 / dv as (6, nv): the jacobians of
+        FLAG_FRAME_VEL_COST (ddp_hip.h)"""
+        q, v, off = _f64(q), _f64(v), _f64(off)
+        vel, Jq, Jv = np.zeros(6), np.zeros(6 * self.nv), np.zeros(6 * self.nv)
+        _check(lib().ddp_hip_model_frame_velocity(self._h, int(joint), _ptr(off), _ptr(q), _ptr(v), _ptr(vel), _ptr(Jq) if jacobian else None,
+                                                  _ptr(Jv) if jacobian else None), "model_frame_velocity")
+        return (vel, Jq.reshape(self.nv, 6).T.copy(), Jv.reshape(self.nv, 6).T.copy()) if jacobian else vel
+
 
 
 class ProblemSpec:
@@ -542,6 +558,37 @@ class Context:
         t = np.zeros((count, self.spec.T + 1, 3))
         w = np.zeros((count, self.spec.T + 1, 3))
         _check(lib().ddp_hip_com_cost_download(self._h, _ptr(t), _ptr(w), first, count), "com_cost_download")
+        return t, w
+
+    def set_frame_vel_cost(self, target=None, weight=None, first=0, count=None):
+        """The frame-velocity terms of instances first .. first + count - 1 (a context created with FLAG_FRAME_VEL_COST; ddp_hip.h),
+        of the F frames of set_frame_cost.  target: desired linear, then angular velocity in world axes, weight: per axis, >= 0;
+        each (T+1, F, 6) for every instance of the range or (count, T+1, F, 6) with one per instance; weight also takes (6,) and
+        scalars for every step and frame.  None leaves that side as it is."""
+        count = self.batch - first if count is None else count
+        F = getattr(self, "n_cost_frames", 0)
+        per = (self.spec.T + 1, F, 6)
+        full = (count,) + per
+        arrs = {}
+        for name, arr in (("target", target), ("weight", weight)):
+            if arr is None:
+                continue
+            arr = np.asarray(arr, dtype=np.float64)
+            if not (arr.shape in (full, per) or (name == "weight" and arr.shape in ((6,), ()))):
+                raise ValueError(f"set_frame_vel_cost {name}: shape {arr.shape}, expected {per} or {full}")
+            arrs[name] = np.ascontiguousarray(np.broadcast_to(arr, full))
+        if arrs:
+            t, w = arrs.get("target"), arrs.get("weight")
+            _check(lib().ddp_hip_frame_vel_upload(self._h, _ptr(t) if t is not None else None, _ptr(w) if w is not None else None,
+                                                  first, count), "frame_vel_upload")
+
+    def frame_vel_cost(self, first=0, count=None):
+        """(target, weight) of instances first .. first + count - 1, each (count, T+1, F, 6)"""
+        count = self.batch - first if count is None else count
+        F = getattr(self, "n_cost_frames", 0)
+        t = np.zeros((count, self.spec.T + 1, F, 6))
+        w = np.zeros((count, self.spec.T + 1, F, 6))
+        _check(lib().ddp_hip_frame_vel_download(self._h, _ptr(t), _ptr(w), first, count), "frame_vel_download")
         return t, w
 
     def set_state_limits(self, lo=None, hi=None, weight=None, first=0, count=None):

@@ -250,6 +250,15 @@ static int frame_orient_reset(ddp_hip_ctx* ctx) {
   return DDP_HIP_OK;
 }
 
+// the frame-velocity data as it is at create: every target and every weight 0, the terms off
+static int frame_vel_reset(ddp_hip_ctx* ctx) {
+  const size_t words = (size_t)(ctx->d.batch * (ctx->d.T + 1) * DDP_HIP_MAX_COST_FRAMES * 6);
+  HIP_TRY(hipMemsetAsync(ctx->fv_target_d, 0, sizeof(double) * words, ctx->stream));
+  HIP_TRY(hipMemsetAsync(ctx->fv_weight_d, 0, sizeof(double) * words, ctx->stream));
+  ctx->fv_live = false;
+  return DDP_HIP_OK;
+}
+
 extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t flags, ddp_hip_ctx** out) {
   if (!prob || !out) return DDP_HIP_E_ARG;
   *out = nullptr;
@@ -260,6 +269,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   if (prob->fd_mode < 0 || prob->fd_mode > 2) return DDP_HIP_E_ARG;
   if ((flags & DDP_HIP_FLAG_FRAME_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // frames are points of a tree's joints
   if ((flags & DDP_HIP_FLAG_FRAME_ORIENT_COST) && !(flags & DDP_HIP_FLAG_FRAME_COST)) return DDP_HIP_E_ARG;   // the orientation terms are of the cost frames
+  if ((flags & DDP_HIP_FLAG_FRAME_VEL_COST) && !(flags & DDP_HIP_FLAG_FRAME_COST)) return DDP_HIP_E_ARG;   // the velocity terms alike
   if (flags & DDP_HIP_FLAG_COM_COST) {
     if (mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the CoM is of a tree's bodies
     if (!mo.mass_j || !mo.jtype) return DDP_HIP_E_ARG;
@@ -381,6 +391,12 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipMalloc(&ctx->fo_weight_d, sizeof(double) * (size_t)(slots * 3)));
     if (frame_orient_reset(ctx) != DDP_HIP_OK) { ddp_hip_destroy(ctx); return DDP_HIP_E_HIP; }
   }
+  if (flags & DDP_HIP_FLAG_FRAME_VEL_COST) {
+    const size_t words = (size_t)(d.batch * (d.T + 1) * DDP_HIP_MAX_COST_FRAMES * 6);
+    CTX_TRY(hipMalloc(&ctx->fv_target_d, sizeof(double) * words));
+    CTX_TRY(hipMalloc(&ctx->fv_weight_d, sizeof(double) * words));
+    if (frame_vel_reset(ctx) != DDP_HIP_OK) { ddp_hip_destroy(ctx); return DDP_HIP_E_HIP; }
+  }
   if (flags & DDP_HIP_FLAG_COM_COST) {
     const size_t words = (size_t)(d.batch * (d.T + 1) * 3);
     CTX_TRY(hipMalloc(&ctx->cm_target_d, sizeof(double) * words));
@@ -421,6 +437,8 @@ extern "C" int ddp_hip_destroy(ddp_hip_ctx* ctx) {
   if (ctx->fc_weight_d) (void)hipFree(ctx->fc_weight_d);
   if (ctx->fo_quat_d) (void)hipFree(ctx->fo_quat_d);
   if (ctx->fo_weight_d) (void)hipFree(ctx->fo_weight_d);
+  if (ctx->fv_target_d) (void)hipFree(ctx->fv_target_d);
+  if (ctx->fv_weight_d) (void)hipFree(ctx->fv_weight_d);
   if (ctx->cm_target_d) (void)hipFree(ctx->cm_target_d);
   if (ctx->cm_weight_d) (void)hipFree(ctx->cm_weight_d);
   if (ctx->sl_d) (void)hipFree(ctx->sl_d);
@@ -565,6 +583,7 @@ extern "C" int ddp_hip_frame_cost_set_frames(ddp_hip_ctx* ctx, int32_t n_frames,
     HIP_TRY(hipMemsetAsync(ctx->fc_weight_d, 0, sizeof(double) * words, ctx->stream));
     ctx->fc_live = false;
     if (ctx->flags & DDP_HIP_FLAG_FRAME_ORIENT_COST) { const int rc_ = frame_orient_reset(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
+    if (ctx->flags & DDP_HIP_FLAG_FRAME_VEL_COST) { const int rc_ = frame_vel_reset(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
   }
   ctx->fc_nf = n_frames;
   for (int f = 0; f < n_frames; ++f) {
@@ -660,6 +679,53 @@ extern "C" int ddp_hip_frame_orient_download(ddp_hip_ctx* ctx, double* quat, dou
   HIP_TRY(hipSetDevice(ctx->device));
   if (quat) HIP_TRY(hipMemcpyAsync(quat, ctx->fo_quat_d + first * slots * 4, sizeof(double) * (size_t)(slots * 4 * count), hipMemcpyDeviceToHost, ctx->stream));
   if (weight) HIP_TRY(hipMemcpyAsync(weight, ctx->fo_weight_d + first * slots * 3, sizeof(double) * (size_t)(slots * 3 * count), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return DDP_HIP_OK;
+}
+
+// ---- frame-velocity cost (DDP_HIP_FLAG_FRAME_VEL_COST): velocity targets and weights of the cost frames -------------------------
+static int frame_vel_range(ddp_hip_ctx* ctx, int64_t first, int64_t count) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_FRAME_VEL_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (first < 0 || count < 0 || first + count > ctx->d.batch) return DDP_HIP_E_ARG;
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_frame_vel_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first, int64_t count) {
+  int rc = frame_vel_range(ctx, first, count);
+  if (rc != DDP_HIP_OK) return rc;
+  if (ctx->fc_nf == 0) return DDP_HIP_E_ARG;                // no frames set: the arrays have no shape yet
+  const int64_t sz = (ctx->d.T + 1) * ctx->fc_nf * 6;
+  bool nonzero = false;
+  if (target)
+    for (int64_t i = 0; i < sz * count; ++i)
+      if (!isfinite(target[i])) return DDP_HIP_E_ARG;
+  if (weight)
+    for (int64_t i = 0; i < sz * count; ++i) {
+      if (!cost_weight_ok(weight[i])) return DDP_HIP_E_ARG;
+      nonzero |= weight[i] != 0.0;
+    }
+  if (count == 0 || (!target && !weight)) return DDP_HIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  // the candidates' term array of the line search exists from the first non-zero weight on (fwd.hip: frame_vel_cost_kernel)
+  if (nonzero && !ctx->fv_new) HIP_TRY(hipMalloc(&ctx->fv_new, sizeof(double) * (size_t)(ctx->d.batch * ctx->n_alpha_max * (ctx->d.T + 1))));
+  if (target) HIP_TRY(hipMemcpyAsync(ctx->fv_target_d + first * sz, target, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
+  if (weight) HIP_TRY(hipMemcpyAsync(ctx->fv_weight_d + first * sz, weight, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  // exactly cm_live's rule: any non-zero weight switches the kernels on, only ONE upload of zeros for the whole batch switches
+  // them off again
+  if (weight) ctx->fv_live = nonzero || (ctx->fv_live && !(first == 0 && count == ctx->d.batch));
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_frame_vel_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first, int64_t count) {
+  int rc = frame_vel_range(ctx, first, count);
+  if (rc != DDP_HIP_OK) return rc;
+  const int64_t sz = (ctx->d.T + 1) * ctx->fc_nf * 6;
+  if (sz == 0 || count == 0 || (!target && !weight)) return DDP_HIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (target) HIP_TRY(hipMemcpyAsync(target, ctx->fv_target_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
+  if (weight) HIP_TRY(hipMemcpyAsync(weight, ctx->fv_weight_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return DDP_HIP_OK;
 }

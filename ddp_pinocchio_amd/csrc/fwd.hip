@@ -13,6 +13,7 @@
 
 #include "com_cost.h"
 #include "frame_cost.h"
+#include "frame_vel_cost.h"
 #include "internal.h"
 #include "rbd.h"
 #include "state_limits.h"
@@ -778,6 +779,59 @@ __global__ void com_sum_kernel(const double* cm_new, double* fw_dcost, const int
   if (s != 0.0) fw_dcost[gid] += s;
 }
 
+// The frame-velocity terms (DDP_HIP_FLAG_FRAME_VEL_COST, ddp_hip.h) of a list of states, added on top like the CoM terms above:
+// the same list (`count` (trajectory, t) pairs, trajectory k's states at xs + k traj_stride, `na` trajectories per instance), the
+// same two uses (add != 0: out[pair] += term behind cost_kernel; add == 0: out[pair] = term, fv_new of a line-search round, with
+// the candidates the rollout kernels skip skipped here).  DDP_HIP_MAX_COST_FRAMES lanes per pair, 16 pairs per wave: lane f walks
+// frame f's path once, joint -> root, carrying the point, its velocity and the angular velocity (rbd::frame_velocity: no
+// jacobian, no per-joint arrays), and leaves 1/2 sum_a w_a r_a^2 in LDS; the group's first lane adds the frames' terms in
+// ascending order.  A term of weight 0 is left out, a frame whose six weights are 0 is not walked, and a pair without a live
+// weight adds nothing (add != 0) or stores +0 (add == 0).  A non-finite state gives a NaN term, as com_cost_kernel's does
+__global__ __launch_bounds__(64) void frame_vel_cost_kernel(FrameVelCostDev fv, const DevModel* model, const double* xs, int64_t traj_stride,
+                                                            int64_t count, int32_t T1, int32_t nx, int32_t na, const int32_t* state,
+                                                            int32_t round, double* out, int32_t add) {
+  constexpr int L = DDP_HIP_MAX_COST_FRAMES;
+  __shared__ double s_term[64];
+  __shared__ int32_t s_live[64];
+  const DevModel& m = *model;
+  const int tid = threadIdx.x, g = tid / L, f = tid % L;
+  const int64_t e = (int64_t)blockIdx.x * (64 / L) + g;
+  bool live = e < count;
+  int64_t traj = 0, bt1 = 0;
+  int t = 0;
+  if (live) {
+    traj = e / T1;
+    t = (int)(e % T1);
+    const int64_t b = traj / na;
+    if (state && (state[b] != 0 || round * na + (int)(traj % na) > 33)) live = false;
+    bt1 = b * T1 + t;
+  }
+  const bool skip = !live;                                           // nothing is written for this pair
+  double term = 0.0;
+  int32_t walked = 0;
+  if (live && f < fv.nf) {
+    const double* w = fv.weight + (bt1 * fv.nf + f) * 6;
+    const bool lin = rbd::frame_weights_any(w), ang = rbd::frame_weights_any(w + 3);
+    if (lin || ang) {
+      const double* x = xs + traj * traj_stride + (int64_t)t * nx;
+      double pd[3] = {0.0, 0.0, 0.0}, om[3] = {0.0, 0.0, 0.0};
+      rbd::frame_velocity(m, fv.joint[f], fv.off[f], x, x + m.nq, lin, ang, pd, om);
+      term = rbd::frame_vel_term(w, fv.target + (bt1 * fv.nf + f) * 6, pd, om);
+      walked = 1;
+    }
+  }
+  s_term[tid] = term;
+  s_live[tid] = walked;
+  __syncthreads();
+  if (f != 0 || skip) return;
+  double sum = 0.0;
+  bool any = false;
+  for (int k = 0; k < fv.nf; ++k)
+    if (s_live[tid + k]) { sum += s_term[tid + k]; any = true; }
+  if (add) { if (any) out[e] += sum; }
+  else out[e] = sum;
+}
+
 // accept rule (ddp_fwd.ipp:56-60): the first (= largest) candidate with sum(new - old) <= 0; the winner's
 // trajectory becomes (X_NEW, U_NEW).  grid = batch.
 __global__ void select_kernel(FwdParams p) {
@@ -926,6 +980,7 @@ void fwd_teardown(ddp_hip_ctx* ctx) {
   if (ctx->fw_dcost) (void)hipFree(ctx->fw_dcost);
   if (ctx->fw_cost) (void)hipFree(ctx->fw_cost);
   if (ctx->cm_new) (void)hipFree(ctx->cm_new);
+  if (ctx->fv_new) (void)hipFree(ctx->fv_new);
   if (ctx->step_d) (void)hipFree(ctx->step_d);
   if (ctx->fw_dcost_acc_d) (void)hipFree(ctx->fw_dcost_acc_d);
   if (ctx->pick_pair_d) (void)hipFree(ctx->pick_pair_d);
@@ -982,6 +1037,15 @@ static void launch_com_cost(ddp_hip_ctx* ctx, const CoMCostDev& cm, const double
                      (d.T + 1) * d.nx, count, (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, (int32_t)lpe, state, (int32_t)round, out, (int32_t)add);
 }
 
+// frame_vel_cost_kernel over the same kind of list
+static void launch_frame_vel_cost(ddp_hip_ctx* ctx, const FrameVelCostDev& fv, const double* xs, int na, int64_t count, const int32_t* state,
+                                  int round, double* out, int add) {
+  const Dims& d = ctx->d;
+  const int64_t per = 64 / DDP_HIP_MAX_COST_FRAMES;
+  hipLaunchKernelGGL(frame_vel_cost_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(64), 0, ctx->stream, fv, ctx->model_d, xs,
+                     (d.T + 1) * d.nx, count, (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, state, (int32_t)round, out, (int32_t)add);
+}
+
 static int launch_cost(ddp_hip_ctx* ctx, FwdParams& p, int which) {
   const int bs = 64;
   const int64_t total = ctx->d.batch * (ctx->d.T + 1);
@@ -994,6 +1058,9 @@ static int launch_cost(ddp_hip_ctx* ctx, FwdParams& p, int which) {
   const CoMCostDev cm = com_cost_dev(ctx);
   if (cm.target)                                                     // + the CoM terms, onto what cost_kernel has left
     launch_com_cost(ctx, cm, which == 0 ? p.x_old : p.x_new, 1, total, nullptr, 0, which == 0 ? p.costs_old : p.costs_new, 1);
+  const FrameVelCostDev fv = frame_vel_cost_dev(ctx);
+  if (fv.target)                                                     // + the frame-velocity terms, after the CoM's
+    launch_frame_vel_cost(ctx, fv, which == 0 ? p.x_old : p.x_new, 1, total, nullptr, 0, which == 0 ? p.costs_old : p.costs_new, 1);
   HIP_TRY(hipGetLastError());
   return DDP_HIP_OK;
 }
@@ -1027,6 +1094,7 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
   p.no_linesearch = no_linesearch ? 1 : 0;
   int rc = launch_cost(ctx, p, 0);                                   // ddp_fwd.ipp:24-26
   const CoMCostDev cm = com_cost_dev(ctx);
+  const FrameVelCostDev fv = frame_vel_cost_dev(ctx);
   if (rc != DDP_HIP_OK) return rc;
   const int bs = 64;
   const unsigned grid = (unsigned)((B * n_alpha + bs - 1) / bs);
@@ -1063,6 +1131,12 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
       // the candidates' CoM terms, whichever rollout path ran: over fw_x into cm_new, then once onto fw_dcost
       launch_com_cost(ctx, cm, p.fw_x, n_alpha, B * n_alpha * (d.T + 1), p.state, round, ctx->cm_new, 0);
       hipLaunchKernelGGL(com_sum_kernel, dim3((unsigned)((B * n_alpha + 63) / 64)), dim3(64), 0, ctx->stream, ctx->cm_new, p.fw_dcost, p.state,
+                         (int32_t)B, (int32_t)n_alpha, (int32_t)round, d.T);
+    }
+    if (fv.target) {
+      // the candidates' frame-velocity terms alike, into fv_new, and once onto fw_dcost after the CoM's sum
+      launch_frame_vel_cost(ctx, fv, p.fw_x, n_alpha, B * n_alpha * (d.T + 1), p.state, round, ctx->fv_new, 0);
+      hipLaunchKernelGGL(com_sum_kernel, dim3((unsigned)((B * n_alpha + 63) / 64)), dim3(64), 0, ctx->stream, ctx->fv_new, p.fw_dcost, p.state,
                          (int32_t)B, (int32_t)n_alpha, (int32_t)round, d.T);
     }
     hipLaunchKernelGGL(select_kernel, dim3((unsigned)B), dim3(256), 0, ctx->stream, p);

@@ -266,6 +266,12 @@ struct ddp_hip_ctx {
   double* cm_new = nullptr;                   // [batch][n_alpha_max][T+1] the candidates' CoM terms of a line-search round (since the first non-zero weight)
   bool cm_live = false;                       // as fc_live: the CoM kernels are launched
 
+  // frame-velocity cost (DDP_HIP_FLAG_FRAME_VEL_COST; ctx.hip: ddp_hip_frame_vel_*, frame_vel_cost.h), of the frames above
+  double* fv_target_d = nullptr;              // [batch][T+1][fc_nf][6] (room for DDP_HIP_MAX_COST_FRAMES): linear, then angular
+  double* fv_weight_d = nullptr;
+  double* fv_new = nullptr;                   // [batch][n_alpha_max][T+1] the candidates' terms of a line-search round (since the first non-zero weight)
+  bool fv_live = false;                       // as cm_live: the frame-velocity kernels are launched
+
   bool box_dirty = false;       // CTRL_LO / CTRL_HI were uploaded since lo <= hi was last checked (ctx.hip: box_check)
 
   bool async_mode = false;     // ddp_hip_set_async: entry points that hand nothing back to the host do not wait for the stream

@@ -15,6 +15,7 @@
 
 #include "com_cost.h"
 #include "frame_cost.h"
+#include "frame_vel_cost.h"
 #include "internal.h"
 #include "lin_common.h"
 #include "rbd.h"
@@ -319,6 +320,60 @@ __global__ __launch_bounds__(64) void lin_com_cost_kernel(LinParams p, CoMCostDe
       if (s_w[a] != 0.0) h += S.J[3 * lo + a] * s_w[a] * S.J[3 * hi + a];
     gxx[i + (int64_t)j * n] += h;
   }
+}
+
+// Frame-velocity cost (DDP_HIP_FLAG_FRAME_VEL_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost
+// kernel on the same stream (the fixed order of additions: cost, tracking, frame positions, frame orientations, limits, CoM, frame
+// velocities).  r_f = (P_f v - g_lin, W_f v - g_ang) depends on q and on v, so A_f = [dr/d(delta q) | dr/dv] fills the q-q, q-v,
+// v-q and v-v blocks on the frame's path.  Lane-parallel over joints like lin_com_cost_kernel: lane j walks its own path once and
+// leaves a_j, o_j, its rate's contributions and its path as a bit mask in LDS (rbd::vel_stage_lane), then forms omega_<=j over its
+// path in ascending order (rbd::vel_prefix_lane); per live frame the lanes on the frame's path form pdot_<=j alike and their
+// columns of P, W, D and E (rbd::vel_frame_lane); then the wave adds the gradient rows and the path x path entries
+// (rbd::vel_add_wave: entry (i, j) in (min, max) order, symmetric bit for bit).  It reads p.x and touches nothing but those
+// entries.  A term of weight 0 is left out, a frame whose six weights are 0 is not walked, a block without a live weight returns
+// at once.  t = T: lfx / lfxx
+__global__ __launch_bounds__(64) void lin_frame_vel_cost_kernel(LinParams p, FrameVelCostDev fv) {
+  const int64_t T = p.d.T;
+  const int64_t bt1 = blockIdx.x;
+  const int b = (int)(bt1 / (T + 1));
+  const int64_t t = bt1 % (T + 1);
+  const int n = (int)p.d.n, nv = (int)p.d.nv, nx = (int)p.d.nx;
+  const int tid = threadIdx.x, nf = fv.nf;
+  const double* w = fv.weight + bt1 * nf * 6;
+  bool any = false;
+  for (int k = 0; k < 6 * nf; ++k) any |= w[k] != 0.0;
+  if (!any) return;
+  const DevModel& m = *p.model;
+  const bool ff = m.ff != 0;
+  const double* q = p.x + bt1 * nx;
+  const double* v = q + m.nq;
+  __shared__ rbd::VelWaveLds S;
+  __shared__ double s_w[6 * DDP_HIP_MAX_COST_FRAMES], s_wr[6 * DDP_HIP_MAX_COST_FRAMES];
+  if (tid < m.nj) rbd::vel_stage_lane(m, q, v, tid, S);
+  for (int f = 0; f < nf; ++f)
+    if (tid == 63 - f && (rbd::frame_weights_any(w + 6 * f) || rbd::frame_weights_any(w + 6 * f + 3)))
+      rbd::frame_point(m, ff, fv.joint[f], fv.off[f], q, S.p[f]);
+  __syncthreads();
+  if (tid < m.nj) rbd::vel_prefix_lane(tid, S);
+  __syncthreads();
+  unsigned long long U = 0;
+  for (int f = 0; f < nf; ++f) {
+    const bool lin = rbd::frame_weights_any(w + 6 * f), ang = rbd::frame_weights_any(w + 6 * f + 3);
+    if (!lin && !ang) continue;
+    U |= rbd::vel_tangent_mask(ff, S.mask[fv.joint[f]]);
+    if (tid < m.nj) rbd::vel_frame_lane(m, tid, f, fv.joint[f], lin, ang, S);
+  }
+  rbd::vel_index_lane(U, tid, S);
+  __syncthreads();
+  if (tid < 6 * nf) {
+    const double wa = w[tid];
+    s_w[tid] = wa;
+    s_wr[tid] = wa != 0.0 ? wa * (S.vel[tid / 6][tid % 6] - fv.target[bt1 * nf * 6 + tid]) : 0.0;
+  }
+  __syncthreads();
+  double* gx = t < T ? p.lx + ((int64_t)b * T + t) * n : p.lfx + (int64_t)b * n;
+  double* gxx = t < T ? p.lxx + ((int64_t)b * T + t) * n * n : p.lfxx + (int64_t)b * n * n;
+  rbd::vel_add_wave(S, nf, s_w, s_wr, __builtin_popcountll(U), tid, (int)blockDim.x, nv, n, gx, gxx);
 }
 
 template <int NJ>
@@ -1156,6 +1211,8 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     if (sl.weight) hipLaunchKernelGGL(lin_limit_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, sl);
     const CoMCostDev cm = com_cost_dev(ctx);
     if (cm.target) hipLaunchKernelGGL(lin_com_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, cm);
+    const FrameVelCostDev fv = frame_vel_cost_dev(ctx);
+    if (fv.target) hipLaunchKernelGGL(lin_frame_vel_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, fv);
   }
   // the q- / v-caches of the mode-2 stencil also serve the first order (base configuration and base (q, v)), so they are built
   // ahead of whichever stage comes first

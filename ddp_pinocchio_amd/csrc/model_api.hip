@@ -8,6 +8,7 @@
 #include <new>
 
 #include "com_cost.h"
+#include "frame_vel_cost.h"
 #include "internal.h"
 #include "rbd.h"
 #include "rbd_deriv.h"
@@ -86,6 +87,28 @@ __global__ __launch_bounds__(64) void model_com_kernel(const DevModel* m, const 
   for (int i = tid; i < 3 * m->nv; i += blockDim.x) out[3 + i] = S.J[i];
 }
 
+// (pdot, omega) of the point `off` of joint `joint`, and A = [dr/d(delta q) | dr/dv], by one wave with the traversal of
+// lin_frame_vel_cost_kernel (frame_vel_cost.h): in = q | v | off[3], out = vel6 | Jq[6 nv] | Jv[6 nv] (columns off the path 0)
+__global__ __launch_bounds__(64) void model_frame_vel_kernel(const DevModel* m, const double* in, double* out, int joint) {
+  __shared__ rbd::VelWaveLds S;
+  const int tid = threadIdx.x, nv = m->nv;
+  const bool ff = m->ff != 0;
+  const double* q = in;
+  const double* v = in + m->nq;
+  if (tid < m->nj) rbd::vel_stage_lane(*m, q, v, tid, S);
+  if (tid == 63) rbd::frame_point(*m, ff, joint, in + m->nq + nv, q, S.p[0]);
+  __syncthreads();
+  if (tid < m->nj) rbd::vel_prefix_lane(tid, S);
+  __syncthreads();
+  if (tid < m->nj) rbd::vel_frame_lane(*m, tid, 0, joint, true, true, S);
+  __syncthreads();
+  if (tid < 6) out[tid] = S.vel[0][tid];
+  for (int i = tid; i < 12 * nv; i += blockDim.x) {
+    const int h = i / (6 * nv), c = (i % (6 * nv)) / 6, a = i % 6;
+    out[6 + i] = ((S.cm[0][2 * h + a / 3] >> c) & 1) ? S.A[0][h][c][a] : 0.0;
+  }
+}
+
 #define MODEL_DISPATCH(nv, CALL)       \
   do {                                 \
     if ((nv) <= 6) { CALL(6); }        \
@@ -116,6 +139,8 @@ int run(ddp_hip_model_handle* h, const double* in, size_t n_in, double* out, siz
     else return DDP_HIP_E_UNSUPPORTED;
   } else if (what == 3) {
     hipLaunchKernelGGL(model_com_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o);
+  } else if (what == 4) {
+    hipLaunchKernelGGL(model_frame_vel_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac);   // (want_jac: the joint)
   } else {
 #define CALL(NJ) hipLaunchKernelGGL((model_frame_kernel<NJ>), dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac)
     MODEL_DISPATCH(nv, CALL);
@@ -221,5 +246,20 @@ extern "C" int ddp_hip_model_com(ddp_hip_model_handle* h, const double* q, doubl
   if (rc != DDP_HIP_OK) return rc;
   memcpy(c3, out, sizeof(double) * 3);
   if (J) memcpy(J, out + 3, sizeof(double) * 3 * nv);
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_model_frame_velocity(ddp_hip_model_handle* h, int32_t joint, const double off[3], const double* q, const double* v,
+                                            double* vel6, double* Jq, double* Jv) {
+  if (!h || !off || !q || !v || !vel6 || h->model_h.kind != DDP_HIP_MODEL_TREE || joint < 0 || joint >= h->model_h.nj) return DDP_HIP_E_ARG;
+  const int nv = h->model_h.nv, nq = h->model_h.nq;
+  double in[2 * DDP_MAXJ + 4];
+  memcpy(in, q, sizeof(double) * nq); memcpy(in + nq, v, sizeof(double) * nv); memcpy(in + nq + nv, off, sizeof(double) * 3);
+  double out[6 + 12 * DDP_MAXJ];
+  const int rc = run(h, in, (size_t)(nq + nv + 3), out, (size_t)(6 + ((Jq || Jv) ? 12 * nv : 0)), 4, joint);
+  if (rc != DDP_HIP_OK) return rc;
+  memcpy(vel6, out, sizeof(double) * 6);
+  if (Jq) memcpy(Jq, out + 6, sizeof(double) * 6 * nv);
+  if (Jv) memcpy(Jv, out + 6 + 6 * nv, sizeof(double) * 6 * nv);
   return DDP_HIP_OK;
 }

@@ -235,6 +235,35 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * for bit what it computes without the flag.  Tree models only (the pendulum: DDP_HIP_E_UNSUPPORTED).  The flag combines with
  * every other flag: the terms are formed by kernels of their own, which add onto what the other terms' kernels leave. */
 #define DDP_HIP_FLAG_COM_COST 128u
+/* Give every cost frame of DDP_HIP_FLAG_FRAME_COST a velocity term as well: "arrive at rest", "touch down with zero foot
+ * velocity", "move the hand along x at 0.2 m/s".  Valid only together with DDP_HIP_FLAG_FRAME_COST (alone: ddp_hip_create returns
+ * DDP_HIP_E_ARG); the frames are those of ddp_hip_frame_cost_set_frames.  For frame f (point off_f of joint joint_f, world position
+ * p_f), with P_f the true point jacobian and W_f the world angular jacobian of the two flags above, the frame's velocity in
+ * world-aligned axes is
+ *   pdot_f = P_f(q) v   (the point's linear velocity),      omega_f = W_f(q) v   (the angular velocity of joint_f's frame)
+ * with v the tangent velocity of the state (on a free-flyer root its first six entries are the body twist, linear part first).
+ * Per instance b, t = 0 .. T and frame f a target g[b][t][f] in R^6 (desired linear, then angular velocity, world axes) and weights
+ * w[b][t][f] in R^6 (>= 0), r_f = (pdot_f - g_lin, omega_f - g_ang):
+ *   l(t, x, u) += 1/2 sum_f sum_a w[b][t][f][a] r_f,a^2      t < T
+ *   lf(x_T)    += 1/2 sum_f sum_a w[b][T][f][a] r_f,a^2
+ * to whatever the context optimises otherwise.  Derivatives in the tangent at x: A_f = [ dr/d(delta q) | dr/dv ] (6 x 2 nv), the
+ * right half [P_f; W_f], the left half [D; E] by column of the joints j on the path root .. joint_f, with a_j the world axis and
+ * o_j the world origin of joint j and the prefix sums over the path joints up to and including j (the root's six columns
+ * included)  omega_<=j = sum_{i<=j} W_i v_i,  pdot_<=j = sum_{i<=j} P_i v_i:
+ *   revolute j:    D_j = omega_<=j x (a_j x (p_f - o_j)) + a_j x (pdot_f - pdot_<=j),      E_j = a_j x (omega_f - omega_<=j)
+ *   prismatic j:   D_j = omega_<=j x a_j,                                                  E_j = 0
+ *   free-flyer root: linear columns 0 .. 2: D = E = 0;  angular column 3 + c: D = (R_0 e_c) x pdot_f,  E = (R_0 e_c) x omega_f
+ *   lx[rows] += sum_f A_f^T (w o r_f),   lxx[rows, rows] += sum_f A_f^T diag(w) A_f,   lfx / lfxx alike at T,
+ * the rows being the path's q rows and v rows: the term fills the q-q, q-v, v-q and v-v blocks on the path.  Rows and columns off
+ * the path, lu, luu and lux are untouched; columns that carry nothing (a prismatic joint's angular part, the root's linear D
+ * columns) are left out, not added as zeros.  lxx is Gauss-Newton (the term sum_a w_a r_a d^2 r_a is dropped: exact where r = 0,
+ * positive semidefinite); entry (i, j) is formed in (min, max) order with the frames and axes in fixed order: symmetric bit for
+ * bit.  The data travels through ddp_hip_frame_vel_* below.  At create targets and weights are 0.  A term of weight 0 is left out
+ * (not multiplied by 0): a frame whose six weights are 0 is not walked, one whose three angular (linear) weights are 0 forms no
+ * angular (linear) quantities, and with nothing uploaded or every weight 0 a context computes bit for bit what it computes with
+ * DDP_HIP_FLAG_FRAME_COST alone.  The flag combines with every other flag: the terms are formed by kernels of their own, which
+ * add onto what the other terms' kernels leave (after the CoM's). */
+#define DDP_HIP_FLAG_FRAME_VEL_COST 256u
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -289,6 +318,13 @@ int ddp_hip_state_limits_download(ddp_hip_ctx* ctx, double* lo, double* hi, doub
  * weight. */
 int ddp_hip_com_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first_instance, int64_t n_instances);
 int ddp_hip_com_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first_instance, int64_t n_instances);
+/* The velocity targets and weights of the cost frames in a context created with DDP_HIP_FLAG_FRAME_VEL_COST (else
+ * DDP_HIP_E_UNSUPPORTED), stream-ordered like ddp_hip_frame_orient_upload.  Host arrays [n_instances][T+1][n_frames][6] (linear
+ * part, then angular part); a NULL pointer leaves that side as it is.  An upload is refused as a whole (DDP_HIP_E_ARG, nothing
+ * written) before frames are set, for a bad instance range, a non-finite target and a negative or non-finite weight.
+ * ddp_hip_frame_cost_set_frames with another frame count resets this data to 0 as well; with the same count it stays. */
+int ddp_hip_frame_vel_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first_instance, int64_t n_instances);
+int ddp_hip_frame_vel_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first_instance, int64_t n_instances);
 
 /* make_trajectory (ddp.hpp:392-415): X[0] and U given -> X[1..T] */
 int ddp_hip_rollout(ddp_hip_ctx* ctx);
@@ -436,6 +472,12 @@ int ddp_hip_model_frame(ddp_hip_model_handle* h, int32_t joint, const double off
 /* The centre of mass c(q) of a tree model and, if J is not NULL, Jc = dc / d(delta q) as 3 x nv column-major: the true jacobian
  * of DDP_HIP_FLAG_COM_COST, formed by the traversal the cost kernels use.  For targets such as "where the CoM is now, plus 5 cm" */
 int ddp_hip_model_com(ddp_hip_model_handle* h, const double* q, double* c3, double* J);
+/* The velocity vel6 = (pdot, omega) of the point `off` of joint `joint` at the state (q, v), world-aligned axes, as
+ * DDP_HIP_FLAG_FRAME_VEL_COST defines it, and, where not NULL, its jacobians Jq = d vel6 / d(delta q) = [D; E] and
+ * Jv = d vel6 / dv = [P; W], each 6 x nv column-major, formed by the traversal the cost kernels use.  For targets such as "half
+ * the hand's present speed" */
+int ddp_hip_model_frame_velocity(ddp_hip_model_handle* h, int32_t joint, const double off[3], const double* q, const double* v,
+                                 double* vel6, double* Jq, double* Jv);
 
 /* ---- built-in seeded model tables (no URDF exists offline: SURVEY.md D4, 8d) -------------- */
 /* ..._FF: the same robots on a free-flyer root instead of a fixed base / 3 prismatic + 3 revolute base joints */
