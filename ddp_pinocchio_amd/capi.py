@@ -29,7 +29,10 @@ FLAG_STATE_LIMITS = 32
 FLAG_FRAME_ORIENT_COST = 64
 FLAG_COM_COST = 128
 FLAG_FRAME_VEL_COST = 256
+FLAG_OBSTACLE_COST = 512
 MAX_COST_FRAMES = 4
+MAX_COLLISION_POINTS, MAX_OBSTACLES = 16, 8
+OBSTACLE_SPHERE, OBSTACLE_HALFSPACE = 0, 1
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
 
 SEQ_NAMES = [
@@ -63,6 +66,7 @@ EXPORTS = [
     "ddp_hip_state_limits_upload", "ddp_hip_state_limits_download",
     "ddp_hip_com_cost_upload", "ddp_hip_com_cost_download", "ddp_hip_model_com",
     "ddp_hip_frame_vel_upload", "ddp_hip_frame_vel_download", "ddp_hip_model_frame_velocity",
+    "ddp_hip_obstacle_set_points", "ddp_hip_obstacle_upload", "ddp_hip_obstacle_download", "ddp_hip_obstacle_clearance",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -160,6 +164,11 @@ def lib():
         L.ddp_hip_frame_vel_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_frame_vel_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_model_frame_velocity.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]
+    if hasattr(L, "ddp_hip_obstacle_upload"):        # (likewise: set_obstacle_points, set_obstacle_cost, obstacle_clearance)
+        L.ddp_hip_obstacle_set_points.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), _dp, _dp, C.c_int32, C.POINTER(C.c_int32)]
+        L.ddp_hip_obstacle_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_obstacle_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_obstacle_clearance.argtypes = [C.c_void_p, C.c_int, _dp]
     L.ddp_hip_rollout.argtypes = [C.c_void_p]
     L.ddp_hip_linearize.argtypes = [C.c_void_p]
     L.ddp_hip_linearize_stages.argtypes = [C.c_void_p, C.c_uint32]
@@ -381,6 +390,7 @@ class Context:
         _check(lib().ddp_hip_create(C.byref(self._c_problem), device, flags, C.byref(self._h)), "ddp_hip_create")
         self.batch = spec.batch
         self.n_cost_frames = 0
+        self.n_obstacles = 0
 
     def close(self):
         if self._h:
@@ -590,6 +600,62 @@ class Context:
         w = np.zeros((count, self.spec.T + 1, F, 6))
         _check(lib().ddp_hip_frame_vel_download(self._h, _ptr(t), _ptr(w), first, count), "frame_vel_download")
         return t, w
+
+    def set_obstacle_points(self, points, kinds):
+        """The collision points [(joint, off, radius), ...] (up to MAX_COLLISION_POINTS spheres on the robot) and the kinds of the
+        obstacle slots (OBSTACLE_SPHERE / OBSTACLE_HALFSPACE, up to MAX_OBSTACLES) of a context created with FLAG_OBSTACLE_COST
+        (ddp_hip.h), shared by the batch.  With the same counts and kinds as before the per-instance data stays, else it is reset"""
+        joint = np.ascontiguousarray([int(p[0]) for p in points], dtype=np.int32)
+        off = np.ascontiguousarray([p[1] for p in points], dtype=np.float64).reshape(-1)
+        radius = np.ascontiguousarray([p[2] for p in points], dtype=np.float64)
+        kind = np.ascontiguousarray([int(k) for k in kinds], dtype=np.int32)
+        if off.size != 3 * len(joint):
+            raise ValueError("set_obstacle_points: every point is (joint, (x, y, z), radius)")
+        ip = C.POINTER(C.c_int32)
+        _check(lib().ddp_hip_obstacle_set_points(self._h, len(joint), joint.ctypes.data_as(ip), _ptr(off), _ptr(radius), len(kind),
+                                                 kind.ctypes.data_as(ip)), "obstacle_set_points")
+        self.n_obstacles = len(kind)
+
+    def set_obstacle_cost(self, geom=None, weight=None, first=0, count=None):
+        """The obstacles of instances first .. first + count - 1 (a context created with FLAG_OBSTACLE_COST; ddp_hip.h), of the
+        n_obs slots of set_obstacle_points.  geom: (c, rho) of a sphere, (n, h) of a half-space, as (n_obs, 4) for every instance
+        and t, (T+1, n_obs, 4) for every instance or (count, T+1, n_obs, 4); weight: >= 0, as (n_obs,), (T+1, n_obs) or
+        (count, T+1, n_obs).  None leaves that side as it is.  The slot count is the one this object last passed to
+        set_obstacle_points; before that call there is no shape to check against and the call raises ValueError."""
+        count = self.batch - first if count is None else count
+        no = getattr(self, "n_obstacles", 0)
+        if not no:
+            raise ValueError("set_obstacle_cost: no obstacle slots yet, call set_obstacle_points first")
+        arrs = {}
+        for name, arr, tail in (("geom", geom, (no, 4)), ("weight", weight, (no,))):
+            if arr is None:
+                continue
+            arr = np.asarray(arr, dtype=np.float64)
+            per = (self.spec.T + 1,) + tail
+            full = (count,) + per
+            if arr.shape not in (full, per, tail):
+                raise ValueError(f"set_obstacle_cost {name}: shape {arr.shape}, expected {tail}, {per} or {full}")
+            arrs[name] = np.ascontiguousarray(np.broadcast_to(arr, full))
+        if arrs:
+            g, w = arrs.get("geom"), arrs.get("weight")
+            _check(lib().ddp_hip_obstacle_upload(self._h, _ptr(g) if g is not None else None, _ptr(w) if w is not None else None,
+                                                 first, count), "obstacle_upload")
+
+    def obstacle_cost(self, first=0, count=None):
+        """(geom, weight) of instances first .. first + count - 1: (count, T+1, n_obs, 4) and (count, T+1, n_obs)"""
+        count = self.batch - first if count is None else count
+        no = getattr(self, "n_obstacles", 0)               # (0 before set_obstacle_points: empty arrays)
+        g = np.zeros((count, self.spec.T + 1, no, 4))
+        w = np.zeros((count, self.spec.T + 1, no))
+        _check(lib().ddp_hip_obstacle_download(self._h, _ptr(g), _ptr(w), first, count), "obstacle_download")
+        return g, w
+
+    def obstacle_clearance(self, which=0):
+        """(batch, T+1): the least signed distance of a collision point to an obstacle of non-zero weight along X (which = 0) or
+        X_NEW (which = 1); +inf where no slot is live, negative where the robot penetrates"""
+        out = np.zeros((self.batch, self.spec.T + 1))
+        _check(lib().ddp_hip_obstacle_clearance(self._h, int(which), _ptr(out)), "obstacle_clearance")
+        return out
 
     def set_state_limits(self, lo=None, hi=None, weight=None, first=0, count=None):
         """The soft state limits of instances first .. first + count - 1 (a context created with FLAG_STATE_LIMITS; ddp_hip.h),

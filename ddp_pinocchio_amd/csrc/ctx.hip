@@ -259,6 +259,15 @@ static int frame_vel_reset(ddp_hip_ctx* ctx) {
   return DDP_HIP_OK;
 }
 
+// the obstacle data as it is at create: every geom and every weight 0, the terms off
+static int obstacle_reset(ddp_hip_ctx* ctx) {
+  const size_t slots = (size_t)(ctx->d.batch * (ctx->d.T + 1) * DDP_HIP_MAX_OBSTACLES);
+  HIP_TRY(hipMemsetAsync(ctx->ob_geom_d, 0, sizeof(double) * slots * 4, ctx->stream));
+  HIP_TRY(hipMemsetAsync(ctx->ob_weight_d, 0, sizeof(double) * slots, ctx->stream));
+  ctx->ob_live = false;
+  return DDP_HIP_OK;
+}
+
 extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t flags, ddp_hip_ctx** out) {
   if (!prob || !out) return DDP_HIP_E_ARG;
   *out = nullptr;
@@ -270,6 +279,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   if ((flags & DDP_HIP_FLAG_FRAME_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // frames are points of a tree's joints
   if ((flags & DDP_HIP_FLAG_FRAME_ORIENT_COST) && !(flags & DDP_HIP_FLAG_FRAME_COST)) return DDP_HIP_E_ARG;   // the orientation terms are of the cost frames
   if ((flags & DDP_HIP_FLAG_FRAME_VEL_COST) && !(flags & DDP_HIP_FLAG_FRAME_COST)) return DDP_HIP_E_ARG;   // the velocity terms alike
+  if ((flags & DDP_HIP_FLAG_OBSTACLE_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // collision points are points of a tree's joints
   if (flags & DDP_HIP_FLAG_COM_COST) {
     if (mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the CoM is of a tree's bodies
     if (!mo.mass_j || !mo.jtype) return DDP_HIP_E_ARG;
@@ -397,6 +407,13 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipMalloc(&ctx->fv_weight_d, sizeof(double) * words));
     if (frame_vel_reset(ctx) != DDP_HIP_OK) { ddp_hip_destroy(ctx); return DDP_HIP_E_HIP; }
   }
+  if (flags & DDP_HIP_FLAG_OBSTACLE_COST) {
+    const size_t slots = (size_t)(d.batch * (d.T + 1) * DDP_HIP_MAX_OBSTACLES);
+    CTX_TRY(hipMalloc(&ctx->ob_geom_d, sizeof(double) * slots * 4));
+    CTX_TRY(hipMalloc(&ctx->ob_weight_d, sizeof(double) * slots));
+    CTX_TRY(hipMalloc(&ctx->ob_clear_d, sizeof(double) * (size_t)(d.batch * (d.T + 1))));
+    if (obstacle_reset(ctx) != DDP_HIP_OK) { ddp_hip_destroy(ctx); return DDP_HIP_E_HIP; }
+  }
   if (flags & DDP_HIP_FLAG_COM_COST) {
     const size_t words = (size_t)(d.batch * (d.T + 1) * 3);
     CTX_TRY(hipMalloc(&ctx->cm_target_d, sizeof(double) * words));
@@ -439,6 +456,9 @@ extern "C" int ddp_hip_destroy(ddp_hip_ctx* ctx) {
   if (ctx->fo_weight_d) (void)hipFree(ctx->fo_weight_d);
   if (ctx->fv_target_d) (void)hipFree(ctx->fv_target_d);
   if (ctx->fv_weight_d) (void)hipFree(ctx->fv_weight_d);
+  if (ctx->ob_geom_d) (void)hipFree(ctx->ob_geom_d);
+  if (ctx->ob_weight_d) (void)hipFree(ctx->ob_weight_d);
+  if (ctx->ob_clear_d) (void)hipFree(ctx->ob_clear_d);
   if (ctx->cm_target_d) (void)hipFree(ctx->cm_target_d);
   if (ctx->cm_weight_d) (void)hipFree(ctx->cm_weight_d);
   if (ctx->sl_d) (void)hipFree(ctx->sl_d);
@@ -726,6 +746,94 @@ extern "C" int ddp_hip_frame_vel_download(ddp_hip_ctx* ctx, double* target, doub
   HIP_TRY(hipSetDevice(ctx->device));
   if (target) HIP_TRY(hipMemcpyAsync(target, ctx->fv_target_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
   if (weight) HIP_TRY(hipMemcpyAsync(weight, ctx->fv_weight_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return DDP_HIP_OK;
+}
+
+// ---- obstacle cost (DDP_HIP_FLAG_OBSTACLE_COST): collision points and slot kinds shared by the batch, geometry and weights per
+// (instance, t, slot) ------------------------------------------------------------------------------------------------------------
+extern "C" int ddp_hip_obstacle_set_points(ddp_hip_ctx* ctx, int32_t n_points, const int32_t* joint, const double* off, const double* radius,
+                                           int32_t n_obstacles, const int32_t* kind) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_OBSTACLE_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (n_points < 1 || n_points > DDP_HIP_MAX_COLLISION_POINTS || n_obstacles < 1 || n_obstacles > DDP_HIP_MAX_OBSTACLES) return DDP_HIP_E_ARG;
+  if (!joint || !off || !radius || !kind) return DDP_HIP_E_ARG;
+  for (int k = 0; k < n_points; ++k) {
+    if (joint[k] < 0 || joint[k] >= ctx->model_h.nj) return DDP_HIP_E_ARG;
+    for (int a = 0; a < 3; ++a)
+      if (!isfinite(off[3 * k + a])) return DDP_HIP_E_ARG;
+    if (!isfinite(radius[k]) || radius[k] < 0.0) return DDP_HIP_E_ARG;
+  }
+  for (int o = 0; o < n_obstacles; ++o)
+    if (kind[o] != DDP_HIP_OBSTACLE_SPHERE && kind[o] != DDP_HIP_OBSTACLE_HALFSPACE) return DDP_HIP_E_ARG;
+  bool same = n_points == ctx->ob_np && n_obstacles == ctx->ob_no;
+  for (int o = 0; same && o < n_obstacles; ++o) same = kind[o] == ctx->ob_kind[o];
+  if (!same) {
+    // other counts are another layout, other kinds another meaning of the four doubles: geometry and weights start again at 0
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int rc_ = obstacle_reset(ctx);
+    if (rc_ != DDP_HIP_OK) return rc_;
+  }
+  ctx->ob_np = n_points;
+  ctx->ob_no = n_obstacles;
+  for (int k = 0; k < n_points; ++k) {
+    ctx->ob_joint[k] = joint[k];
+    ctx->ob_radius[k] = radius[k];
+    for (int a = 0; a < 3; ++a) ctx->ob_off[k][a] = off[3 * k + a];
+  }
+  for (int o = 0; o < n_obstacles; ++o) ctx->ob_kind[o] = kind[o];
+  return DDP_HIP_OK;
+}
+
+static int obstacle_range(ddp_hip_ctx* ctx, int64_t first, int64_t count) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_OBSTACLE_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (first < 0 || count < 0 || first + count > ctx->d.batch) return DDP_HIP_E_ARG;
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_obstacle_upload(ddp_hip_ctx* ctx, const double* geom, const double* weight, int64_t first, int64_t count) {
+  int rc = obstacle_range(ctx, first, count);
+  if (rc != DDP_HIP_OK) return rc;
+  if (ctx->ob_np == 0) return DDP_HIP_E_ARG;                // no points set: the arrays have no shape yet
+  const int64_t no = ctx->ob_no, sz = (ctx->d.T + 1) * no;
+  bool nonzero = false;
+  if (geom)
+    for (int64_t i = 0; i < sz * count; ++i) {
+      const double* g = geom + 4 * i;
+      if (!isfinite(g[0]) || !isfinite(g[1]) || !isfinite(g[2]) || !isfinite(g[3])) return DDP_HIP_E_ARG;
+      if (ctx->ob_kind[i % no] == DDP_HIP_OBSTACLE_SPHERE) {
+        if (g[3] < 0.0) return DDP_HIP_E_ARG;               // a sphere's radius
+      } else if (fabs(sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) - 1.0) > 1e-10) {
+        return DDP_HIP_E_ARG;                               // a half-space's unit normal
+      }
+    }
+  if (weight)
+    for (int64_t i = 0; i < sz * count; ++i) {
+      if (!cost_weight_ok(weight[i])) return DDP_HIP_E_ARG;
+      nonzero |= weight[i] != 0.0;
+    }
+  if (count == 0 || (!geom && !weight)) return DDP_HIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  // the candidates' term array of the line search exists from the first non-zero weight on (fwd.hip: obstacle_cost_kernel)
+  if (nonzero && !ctx->ob_new) HIP_TRY(hipMalloc(&ctx->ob_new, sizeof(double) * (size_t)(ctx->d.batch * ctx->n_alpha_max * (ctx->d.T + 1))));
+  if (geom) HIP_TRY(hipMemcpyAsync(ctx->ob_geom_d + first * sz * 4, geom, sizeof(double) * (size_t)(sz * count * 4), hipMemcpyHostToDevice, ctx->stream));
+  if (weight) HIP_TRY(hipMemcpyAsync(ctx->ob_weight_d + first * sz, weight, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  // exactly cm_live's rule: any non-zero weight switches the kernels on, only ONE upload of zeros for the whole batch switches
+  // them off again
+  if (weight) ctx->ob_live = nonzero || (ctx->ob_live && !(first == 0 && count == ctx->d.batch));
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_obstacle_download(ddp_hip_ctx* ctx, double* geom, double* weight, int64_t first, int64_t count) {
+  int rc = obstacle_range(ctx, first, count);
+  if (rc != DDP_HIP_OK) return rc;
+  const int64_t sz = (ctx->d.T + 1) * ctx->ob_no;
+  if (sz == 0 || count == 0 || (!geom && !weight)) return DDP_HIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (geom) HIP_TRY(hipMemcpyAsync(geom, ctx->ob_geom_d + first * sz * 4, sizeof(double) * (size_t)(sz * count * 4), hipMemcpyDeviceToHost, ctx->stream));
+  if (weight) HIP_TRY(hipMemcpyAsync(weight, ctx->ob_weight_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return DDP_HIP_OK;
 }

@@ -15,6 +15,7 @@
 #include "frame_cost.h"
 #include "frame_vel_cost.h"
 #include "internal.h"
+#include "obstacle_cost.h"
 #include "rbd.h"
 #include "state_limits.h"
 
@@ -832,6 +833,89 @@ __global__ __launch_bounds__(64) void frame_vel_cost_kernel(FrameVelCostDev fv, 
   else out[e] = sum;
 }
 
+// The obstacle terms (DDP_HIP_FLAG_OBSTACLE_COST, ddp_hip.h) of a list of states, added on top like the frame-velocity terms above:
+// the same list, the same two uses (add != 0: out[pair] += term behind cost_kernel; add == 0: out[pair] = term, ob_new of a
+// line-search round, with the candidates the rollout kernels skip skipped here).  DDP_HIP_MAX_COLLISION_POINTS lanes per pair, 4
+// pairs per wave: lane k walks point k once (rbd::frame_point: no jacobian, no per-joint arrays) and leaves 1/2 sum_o w e^2 over
+// its live slots in LDS; the group's first lane adds the points' terms in ascending order.  A pair (point, slot) with w == 0 or
+// e == 0 is left out, a block whose weights are all 0 walks nothing, and a pair without an active term adds nothing (add != 0) or
+// stores +0 (add == 0).  A non-finite state gives a NaN term, as com_cost_kernel's does
+__global__ __launch_bounds__(64) void obstacle_cost_kernel(ObstacleCostDev ob, const DevModel* model, const double* xs, int64_t traj_stride,
+                                                           int64_t count, int32_t T1, int32_t nx, int32_t na, const int32_t* state,
+                                                           int32_t round, double* out, int32_t add) {
+  constexpr int L = DDP_HIP_MAX_COLLISION_POINTS;
+  __shared__ double s_term[64];
+  __shared__ int32_t s_act[64];
+  const DevModel& m = *model;
+  const int tid = threadIdx.x, g = tid / L, k = tid % L;
+  const int64_t e = (int64_t)blockIdx.x * (64 / L) + g;
+  bool live = e < count;
+  int64_t traj = 0, bt1 = 0;
+  int t = 0;
+  if (live) {
+    traj = e / T1;
+    t = (int)(e % T1);
+    const int64_t b = traj / na;
+    if (state && (state[b] != 0 || round * na + (int)(traj % na) > 33)) live = false;
+    bt1 = b * T1 + t;
+  }
+  const bool skip = !live;                                           // nothing is written for this pair
+  double term = 0.0;
+  int32_t act = 0;
+  if (live && k < ob.np) {
+    const double* w = ob.weight + bt1 * ob.no;
+    bool any = false;
+    for (int o = 0; o < ob.no; ++o) any |= w[o] != 0.0;
+    if (any) {
+      const double off[3] = {ob.off[k][0], ob.off[k][1], ob.off[k][2]};
+      double pk[3];
+      bool a = false;
+      rbd::frame_point(m, m.ff != 0, ob.joint[k], off, xs + traj * traj_stride + (int64_t)t * nx, pk);
+      term = rbd::obstacle_point_term(ob, k, pk, ob.geom + bt1 * ob.no * 4, w, &a);
+      act = a ? 1 : 0;
+    }
+  }
+  s_term[tid] = term;
+  s_act[tid] = act;
+  __syncthreads();
+  if (k != 0 || skip) return;
+  double sum = 0.0;
+  bool any = false;
+  for (int i = 0; i < ob.np; ++i)
+    if (s_act[tid + i]) { sum += s_term[tid + i]; any = true; }
+  if (add) { if (any) out[e] += sum; }
+  else out[e] = sum;
+}
+
+// ddp_hip_obstacle_clearance: the same lane layout over the `count` (instance, t) pairs of one resident trajectory, min instead of
+// sum: out[pair] = min over points and over slots with w != 0 of d_ko, +inf where no slot is live, NaN where a distance is NaN
+__global__ __launch_bounds__(64) void obstacle_clearance_kernel(ObstacleCostDev ob, const DevModel* model, const double* xs, int64_t count,
+                                                                int32_t nx, double* out) {
+  constexpr int L = DDP_HIP_MAX_COLLISION_POINTS;
+  __shared__ double s_min[64];
+  const DevModel& m = *model;
+  const int tid = threadIdx.x, g = tid / L, k = tid % L;
+  const int64_t e = (int64_t)blockIdx.x * (64 / L) + g;
+  const bool live = e < count;
+  double best = INFINITY;
+  if (live && k < ob.np) {
+    const double* w = ob.weight + e * ob.no;
+    bool any = false;
+    for (int o = 0; o < ob.no; ++o) any |= w[o] != 0.0;
+    if (any) {
+      const double off[3] = {ob.off[k][0], ob.off[k][1], ob.off[k][2]};
+      double pk[3];
+      rbd::frame_point(m, m.ff != 0, ob.joint[k], off, xs + e * nx, pk);
+      best = rbd::obstacle_point_clearance(ob, k, pk, ob.geom + e * ob.no * 4, w);
+    }
+  }
+  s_min[tid] = best;
+  __syncthreads();
+  if (k != 0 || !live) return;
+  for (int i = 1; i < ob.np; ++i) best = rbd::obstacle_min(best, s_min[tid + i]);
+  out[e] = best;
+}
+
 // accept rule (ddp_fwd.ipp:56-60): the first (= largest) candidate with sum(new - old) <= 0; the winner's
 // trajectory becomes (X_NEW, U_NEW).  grid = batch.
 __global__ void select_kernel(FwdParams p) {
@@ -981,6 +1065,7 @@ void fwd_teardown(ddp_hip_ctx* ctx) {
   if (ctx->fw_cost) (void)hipFree(ctx->fw_cost);
   if (ctx->cm_new) (void)hipFree(ctx->cm_new);
   if (ctx->fv_new) (void)hipFree(ctx->fv_new);
+  if (ctx->ob_new) (void)hipFree(ctx->ob_new);
   if (ctx->step_d) (void)hipFree(ctx->step_d);
   if (ctx->fw_dcost_acc_d) (void)hipFree(ctx->fw_dcost_acc_d);
   if (ctx->pick_pair_d) (void)hipFree(ctx->pick_pair_d);
@@ -1046,6 +1131,15 @@ static void launch_frame_vel_cost(ddp_hip_ctx* ctx, const FrameVelCostDev& fv, c
                      (d.T + 1) * d.nx, count, (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, state, (int32_t)round, out, (int32_t)add);
 }
 
+// obstacle_cost_kernel over the same kind of list
+static void launch_obstacle_cost(ddp_hip_ctx* ctx, const ObstacleCostDev& ob, const double* xs, int na, int64_t count, const int32_t* state,
+                                 int round, double* out, int add) {
+  const Dims& d = ctx->d;
+  const int64_t per = 64 / DDP_HIP_MAX_COLLISION_POINTS;
+  hipLaunchKernelGGL(obstacle_cost_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(64), 0, ctx->stream, ob, ctx->model_d, xs,
+                     (d.T + 1) * d.nx, count, (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, state, (int32_t)round, out, (int32_t)add);
+}
+
 static int launch_cost(ddp_hip_ctx* ctx, FwdParams& p, int which) {
   const int bs = 64;
   const int64_t total = ctx->d.batch * (ctx->d.T + 1);
@@ -1061,6 +1155,9 @@ static int launch_cost(ddp_hip_ctx* ctx, FwdParams& p, int which) {
   const FrameVelCostDev fv = frame_vel_cost_dev(ctx);
   if (fv.target)                                                     // + the frame-velocity terms, after the CoM's
     launch_frame_vel_cost(ctx, fv, which == 0 ? p.x_old : p.x_new, 1, total, nullptr, 0, which == 0 ? p.costs_old : p.costs_new, 1);
+  const ObstacleCostDev ob = obstacle_cost_dev(ctx);
+  if (ob.geom)                                                       // + the obstacle terms, last
+    launch_obstacle_cost(ctx, ob, which == 0 ? p.x_old : p.x_new, 1, total, nullptr, 0, which == 0 ? p.costs_old : p.costs_new, 1);
   HIP_TRY(hipGetLastError());
   return DDP_HIP_OK;
 }
@@ -1072,6 +1169,23 @@ extern "C" int ddp_hip_cost_seq_aug(ddp_hip_ctx* ctx, int which, const double* m
   FwdParams p = make_params(ctx);
   int rc = launch_cost(ctx, p, which);
   if (rc != DDP_HIP_OK) return rc;
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_obstacle_clearance(ddp_hip_ctx* ctx, int which, double* out) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_OBSTACLE_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (!out || (which != 0 && which != 1) || ctx->ob_np == 0) return DDP_HIP_E_ARG;   // (no points set: nothing to measure)
+  HIP_TRY(hipSetDevice(ctx->device));
+  const FwdParams p = make_params(ctx);
+  const ObstacleCostDev ob = obstacle_cost_dev(ctx, true);
+  const int64_t total = ctx->d.batch * (ctx->d.T + 1);
+  const int64_t per = 64 / DDP_HIP_MAX_COLLISION_POINTS;
+  hipLaunchKernelGGL(obstacle_clearance_kernel, dim3((unsigned)((total + per - 1) / per)), dim3(64), 0, ctx->stream, ob, ctx->model_d,
+                     which == 0 ? p.x_old : p.x_new, total, (int32_t)ctx->d.nx, ctx->ob_clear_d);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, ctx->ob_clear_d, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return DDP_HIP_OK;
 }
@@ -1095,6 +1209,7 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
   int rc = launch_cost(ctx, p, 0);                                   // ddp_fwd.ipp:24-26
   const CoMCostDev cm = com_cost_dev(ctx);
   const FrameVelCostDev fv = frame_vel_cost_dev(ctx);
+  const ObstacleCostDev ob = obstacle_cost_dev(ctx);
   if (rc != DDP_HIP_OK) return rc;
   const int bs = 64;
   const unsigned grid = (unsigned)((B * n_alpha + bs - 1) / bs);
@@ -1137,6 +1252,13 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
       // the candidates' frame-velocity terms alike, into fv_new, and once onto fw_dcost after the CoM's sum
       launch_frame_vel_cost(ctx, fv, p.fw_x, n_alpha, B * n_alpha * (d.T + 1), p.state, round, ctx->fv_new, 0);
       hipLaunchKernelGGL(com_sum_kernel, dim3((unsigned)((B * n_alpha + 63) / 64)), dim3(64), 0, ctx->stream, ctx->fv_new, p.fw_dcost, p.state,
+                         (int32_t)B, (int32_t)n_alpha, (int32_t)round, d.T);
+    }
+    if (ob.geom) {
+      // the candidates' obstacle terms alike, into ob_new, and once onto fw_dcost after the frame velocities' sum: a candidate
+      // that touches no obstacle has the sum +0, which com_sum_kernel does not add
+      launch_obstacle_cost(ctx, ob, p.fw_x, n_alpha, B * n_alpha * (d.T + 1), p.state, round, ctx->ob_new, 0);
+      hipLaunchKernelGGL(com_sum_kernel, dim3((unsigned)((B * n_alpha + 63) / 64)), dim3(64), 0, ctx->stream, ctx->ob_new, p.fw_dcost, p.state,
                          (int32_t)B, (int32_t)n_alpha, (int32_t)round, d.T);
     }
     hipLaunchKernelGGL(select_kernel, dim3((unsigned)B), dim3(256), 0, ctx->stream, p);

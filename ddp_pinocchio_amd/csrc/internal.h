@@ -272,6 +272,18 @@ struct ddp_hip_ctx {
   double* fv_new = nullptr;                   // [batch][n_alpha_max][T+1] the candidates' terms of a line-search round (since the first non-zero weight)
   bool fv_live = false;                       // as cm_live: the frame-velocity kernels are launched
 
+  // obstacle cost (DDP_HIP_FLAG_OBSTACLE_COST; ctx.hip: ddp_hip_obstacle_*, obstacle_cost.h)
+  int32_t ob_np = 0, ob_no = 0;               // collision points and obstacle slots set (0: none yet)
+  int32_t ob_joint[DDP_HIP_MAX_COLLISION_POINTS] = {};
+  double ob_off[DDP_HIP_MAX_COLLISION_POINTS][3] = {};
+  double ob_radius[DDP_HIP_MAX_COLLISION_POINTS] = {};
+  int32_t ob_kind[DDP_HIP_MAX_OBSTACLES] = {};
+  double* ob_geom_d = nullptr;                // [batch][T+1][ob_no][4] (room for DDP_HIP_MAX_OBSTACLES)
+  double* ob_weight_d = nullptr;              // [batch][T+1][ob_no]
+  double* ob_clear_d = nullptr;               // [batch][T+1] what ddp_hip_obstacle_clearance hands back
+  double* ob_new = nullptr;                   // [batch][n_alpha_max][T+1] the candidates' terms of a line-search round (since the first non-zero weight)
+  bool ob_live = false;                       // as cm_live: the obstacle kernels are launched
+
   bool box_dirty = false;       // CTRL_LO / CTRL_HI were uploaded since lo <= hi was last checked (ctx.hip: box_check)
 
   bool async_mode = false;     // ddp_hip_set_async: entry points that hand nothing back to the host do not wait for the stream

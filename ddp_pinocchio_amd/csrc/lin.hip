@@ -18,6 +18,7 @@
 #include "frame_vel_cost.h"
 #include "internal.h"
 #include "lin_common.h"
+#include "obstacle_cost.h"
 #include "rbd.h"
 #include "rbd_deriv.h"
 #include "state_limits.h"
@@ -374,6 +375,60 @@ __global__ __launch_bounds__(64) void lin_frame_vel_cost_kernel(LinParams p, Fra
   double* gx = t < T ? p.lx + ((int64_t)b * T + t) * n : p.lfx + (int64_t)b * n;
   double* gxx = t < T ? p.lxx + ((int64_t)b * T + t) * n * n : p.lfxx + (int64_t)b * n * n;
   rbd::vel_add_wave(S, nf, s_w, s_wr, __builtin_popcountll(U), tid, (int)blockDim.x, nv, n, gx, gxx);
+}
+
+// Obstacle cost (DDP_HIP_FLAG_OBSTACLE_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost kernel
+// on the same stream (the fixed order of additions: ..., CoM, frame velocities, obstacles).  The penalty is one-sided, so most
+// waves have nothing to add and must cost next to nothing.  A block whose weights are all 0 returns at once.  Phase 1: lane
+// k < n_points walks point k (rbd::frame_point) and runs over its live slots in ascending order; a lane with an active pair
+// (w != 0, e != 0, a direction u) forms g_k = sum_o w e u and the symmetric M_k = sum_o w u u^T on the way, in registers.  One
+// wave-level vote (no LDS, no barrier) decides: a wave without an active pair returns here.  Phase 2: lanes j < nj stage world
+// axis, world origin and path of their joint in LDS (rbd::obstacle_stage_lane), the active lanes their p_k, g_k, M_k; the wave
+// then adds, over the union of the active points' paths alone,
+//   lx[i] += sum_k P_k[:, i] . g_k,     lxx[i][j] += sum_k P_k[:, min]^T M_k P_k[:, max]     (Gauss-Newton)
+// with the columns of P_k formed from the staged axes and origins (rbd::obstacle_add_wave: points in ascending order, entry
+// (i, j) in (min, max) order, symmetric bit for bit).  It reads p.x and touches nothing but those entries.  No atomics.
+// t = T: lfx / lfxx
+__global__ __launch_bounds__(64) void lin_obstacle_cost_kernel(LinParams p, ObstacleCostDev ob) {
+  const int64_t T = p.d.T;
+  const int64_t bt1 = blockIdx.x;
+  const int b = (int)(bt1 / (T + 1));
+  const int64_t t = bt1 % (T + 1);
+  const int n = (int)p.d.n, nx = (int)p.d.nx;
+  const int tid = threadIdx.x;
+  const double* w = ob.weight + bt1 * ob.no;
+  bool any = false;
+  for (int o = 0; o < ob.no; ++o) any |= w[o] != 0.0;
+  if (!any) return;
+  const DevModel& m = *p.model;
+  const bool ff = m.ff != 0;
+  const double* q = p.x + bt1 * nx;
+  double pk[3] = {0.0, 0.0, 0.0}, g[3], M[6];
+  bool act = false;
+  if (tid < ob.np) {
+    const double off[3] = {ob.off[tid][0], ob.off[tid][1], ob.off[tid][2]};
+    rbd::frame_point(m, ff, ob.joint[tid], off, q, pk);
+    act = rbd::obstacle_point_reduce(ob, tid, pk, ob.geom + bt1 * ob.no * 4, w, g, M);
+  }
+  const unsigned active = (unsigned)__ballot(act);                  // bit k: point k has an active pair
+  if (active == 0) return;
+  __shared__ rbd::ObstacleWaveLds S;
+  if (tid < m.nj) rbd::obstacle_stage_lane(m, q, tid, S);
+  if (act) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { S.p[tid][a] = pk[a]; S.g[tid][a] = g[a]; }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) S.M[tid][a] = M[a];
+  }
+  __syncthreads();
+  unsigned long long U = 0;
+  for (int k = 0; k < ob.np; ++k)
+    if ((active >> k) & 1) U |= rbd::vel_tangent_mask(ff, S.mask[ob.joint[k]]);
+  if ((U >> tid) & 1) S.idx[__builtin_popcountll(U & ((1ull << tid) - 1))] = tid;
+  __syncthreads();
+  double* gx = t < T ? p.lx + ((int64_t)b * T + t) * n : p.lfx + (int64_t)b * n;
+  double* gxx = t < T ? p.lxx + ((int64_t)b * T + t) * n * n : p.lfxx + (int64_t)b * n * n;
+  rbd::obstacle_add_wave(m, S, ob, active, __builtin_popcountll(U), tid, (int)blockDim.x, n, gx, gxx);
 }
 
 template <int NJ>
@@ -1213,6 +1268,8 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     if (cm.target) hipLaunchKernelGGL(lin_com_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, cm);
     const FrameVelCostDev fv = frame_vel_cost_dev(ctx);
     if (fv.target) hipLaunchKernelGGL(lin_frame_vel_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, fv);
+    const ObstacleCostDev ob = obstacle_cost_dev(ctx);
+    if (ob.geom) hipLaunchKernelGGL(lin_obstacle_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, ob);
   }
   // the q- / v-caches of the mode-2 stencil also serve the first order (base configuration and base (q, v)), so they are built
   // ahead of whichever stage comes first

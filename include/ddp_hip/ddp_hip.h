@@ -264,6 +264,35 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * DDP_HIP_FLAG_FRAME_COST alone.  The flag combines with every other flag: the terms are formed by kernels of their own, which
  * add onto what the other terms' kernels leave (after the CoM's). */
 #define DDP_HIP_FLAG_FRAME_VEL_COST 256u
+/* Say where the robot must not go: collision spheres on the robot against obstacles that every instance carries for itself, as
+ * a one-sided soft cost -- "reach past the table edge", "the swing foot clears the step", "stay 10 cm away from that person".
+ * Collision points, shared by the batch, up to DDP_HIP_MAX_COLLISION_POINTS: point k is the point off_k fixed in joint joint_k
+ * (the convention of the cost frames) with a radius r_k >= 0, a sphere on the robot; p_k(q) is its world position.  Obstacle
+ * slots, shared by the batch, up to DDP_HIP_MAX_OBSTACLES: slot o has a kind, DDP_HIP_OBSTACLE_SPHERE or
+ * DDP_HIP_OBSTACLE_HALFSPACE.  Per instance b, t = 0 .. T and slot o four doubles geom[b][t][o] and a weight w[b][t][o] >= 0
+ * (per-instance scenes; obstacles that move with t):
+ *   sphere:      geom = (centre c, radius rho >= 0),             d_ko = |p_k - c| - (r_k + rho),   u_ko = (p_k - c) / |p_k - c|
+ *   half-space:  geom = (unit normal n, offset h), free side n . p >= h,   d_ko = n . p_k - h - r_k,   u_ko = n
+ * A safety margin is part of the radii or of the offset.  With e_ko = d_ko < 0 ? d_ko : 0:
+ *   l(t, x, u) += 1/2 sum_k sum_o w[b][t][o] e_ko^2      t < T
+ *   lf(x_T)    += 1/2 sum_k sum_o w[b][T][o] e_ko^2
+ * to whatever the context optimises otherwise.  Derivatives in the tangent at x, with P_k the true point jacobian of
+ * DDP_HIP_FLAG_FRAME_COST and z_ko = P_k^T u_ko, over the pairs with w != 0 and e != 0 only:
+ *   lx[q rows] += sum w e_ko z_ko,   lxx[q rows, q rows] += sum w z_ko z_ko^T,   lfx / lfxx alike at T.
+ * Velocity rows and columns, lu, luu, lux and the q rows off every active point's path are untouched.  lxx is Gauss-Newton (the
+ * curvature of the sphere distance and d^2 p_k are dropped: positive semidefinite); entry (i, j) is formed in (min, max) order
+ * with the points, then the slots in ascending order: symmetric bit for bit.  A sphere pair with |p_k - c| == 0 contributes its
+ * value 1/2 w (r_k + rho)^2 and no derivative.  A pair with w == 0 or e == 0 is left out (not multiplied by 0, not added as
+ * +0): with nothing uploaded, with every weight 0, and with non-zero weights on obstacles that neither the trajectory nor any
+ * line-search candidate touches, a context computes bit for bit what it computes without the flag.  The data travels through
+ * ddp_hip_obstacle_* below; at create no points are set and geometry and weights are 0.  Tree models only (the pendulum:
+ * DDP_HIP_E_UNSUPPORTED).  The flag combines with every other flag: the terms are formed by kernels of their own, which add onto
+ * what the other terms' kernels leave (last, after the frame velocities'). */
+#define DDP_HIP_FLAG_OBSTACLE_COST 512u
+#define DDP_HIP_MAX_COLLISION_POINTS 16
+#define DDP_HIP_MAX_OBSTACLES 8
+#define DDP_HIP_OBSTACLE_SPHERE 0
+#define DDP_HIP_OBSTACLE_HALFSPACE 1
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -325,6 +354,24 @@ int ddp_hip_com_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, 
  * ddp_hip_frame_cost_set_frames with another frame count resets this data to 0 as well; with the same count it stays. */
 int ddp_hip_frame_vel_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first_instance, int64_t n_instances);
 int ddp_hip_frame_vel_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first_instance, int64_t n_instances);
+/* The collision points and the obstacle slots of a context created with DDP_HIP_FLAG_OBSTACLE_COST (else DDP_HIP_E_UNSUPPORTED),
+ * shared by the batch: joint[n_points], off[n_points][3], radius[n_points], kind[n_obstacles].  DDP_HIP_E_ARG for counts outside
+ * 1 .. DDP_HIP_MAX_COLLISION_POINTS or 1 .. DDP_HIP_MAX_OBSTACLES, a joint outside the model, a non-finite offset, a negative or
+ * non-finite radius, an unknown kind.  It may be called again: with the same two counts and the same kinds the per-instance data
+ * stays (points may move, radii may change), otherwise geometry and weights are reset to 0. */
+int ddp_hip_obstacle_set_points(ddp_hip_ctx* ctx, int32_t n_points, const int32_t* joint, const double* off, const double* radius,
+                                int32_t n_obstacles, const int32_t* kind);
+/* The obstacles' geometry and weights, stream-ordered like ddp_hip_com_cost_upload.  Host arrays [n_instances][T+1][n_obstacles][4]
+ * and [n_instances][T+1][n_obstacles]; a NULL pointer leaves that side as it is.  An upload is refused as a whole (DDP_HIP_E_ARG,
+ * nothing written) before ddp_hip_obstacle_set_points, for a bad instance range, a non-finite value, a negative weight, a negative
+ * sphere radius and a half-space normal n with | |n| - 1 | > 1e-10.  A geom that arrives alone is checked against the slot kinds;
+ * weights that arrive alone need no geometry check. */
+int ddp_hip_obstacle_upload(ddp_hip_ctx* ctx, const double* geom, const double* weight, int64_t first_instance, int64_t n_instances);
+int ddp_hip_obstacle_download(ddp_hip_ctx* ctx, double* geom, double* weight, int64_t first_instance, int64_t n_instances);
+/* "Did the result collide, where, by how much": out[batch][T+1] (host) = min over the collision points and over the slots with
+ * w != 0 of d_ko along X (which = 0) or X_NEW (which = 1), +inf where no slot is live.  From the first
+ * ddp_hip_obstacle_set_points on (before: DDP_HIP_E_ARG), live weights or not. */
+int ddp_hip_obstacle_clearance(ddp_hip_ctx* ctx, int which, double* out);
 
 /* make_trajectory (ddp.hpp:392-415): X[0] and U given -> X[1..T] */
 int ddp_hip_rollout(ddp_hip_ctx* ctx);
