@@ -231,6 +231,7 @@ static DevSwitches read_switches() {
   sw.ana_eq_kernel = on("DDP_HIP_ANA_EQ_KERNEL");
   sw.bwd_no_graph = on("DDP_HIP_BWD_NO_GRAPH");
   sw.solve_sync = on("DDP_HIP_SOLVE_SYNC");
+  sw.fwd_no_pipe = on("DDP_HIP_FWD_NO_PIPE");
   sw.bwd_cbx = knob("DDP_HIP_BWD_CBX", 1, 8);
   sw.bwd_cbu = knob("DDP_HIP_BWD_CBU", 1, 16);
   sw.qws_bt = knob("DDP_HIP_QWS_BT", 16, 65536);
@@ -317,6 +318,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   ctx->device = device;
   ctx->flags = flags;
   ctx->sw = read_switches();
+  if (hipDeviceGetAttribute(&ctx->cu_count, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) { delete ctx; return DDP_HIP_E_HIP; }
   ctx->active_h.assign((size_t)prob->batch, 1);
   Dims& d = ctx->d;
   d.T = prob->T; d.nv = mo.nv; d.n = 2 * (int64_t)mo.nv; d.m = mo.nv; d.nx = 2 * (int64_t)mo.nv + (ff ? 1 : 0); d.batch = prob->batch;

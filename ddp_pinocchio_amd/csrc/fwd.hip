@@ -434,8 +434,34 @@ struct FwdLat2LdsBox : FwdLat2Lds<NJ> {
   double lo[NJ], hi[NJ];
 };
 
+// ... of the pipelined form (PIPE below): two candidates per workgroup.  Per joint and candidate the q-part's record twice (step t's
+// is read while step t + 1's is written), its contribution slots and the x-part's own slots, 2 x 41 + 21 + 19 = 122 words against
+// 59: at four candidates 148 KB of state alone, at two 74 KB (118 KB with K_t and the model).  The state x twice as well: the helper
+// wave writes q_{t+1} into the other copy while the leading wave still reads x_t
+template <int NJ>
+struct FwdPipeLds {
+  static constexpr int NC = 2, NH = 16, n = 2 * NJ + 1, nu = NJ;
+  double rec[2][rbd::ABA_PIPE_QSLOTS * NJ * NC];
+  double z[rbd::ABA_PIPE_ZSLOTS * NJ * NC];
+  double state[rbd::ABA_PIPE_XSLOTS * NJ * NC];
+  double K[nu * n];
+  double k[nu], uo[nu], xo[n];
+  double dx[NC * n], x[2 * NC * n], u[NC * nu], qdd[NC * nu];
+  rbd::CoopModel<NJ> model;
+};
+template <int NJ>
+struct FwdPipeLdsBox : FwdPipeLds<NJ> {
+  double lo[NJ], hi[NJ];
+};
+
+// The form a launch takes: the pipelined one while its grid, one workgroup per (instance, two candidates), fits the compute units
+// (each workgroup fills a CU's LDS: more of them than CUs would run in two rounds where the four-candidate form runs in one)
+static bool fwd_use_pipe(const ddp_hip_ctx* ctx, int64_t batch, int n_alpha) {
+  return !ctx->sw.fwd_no_pipe && batch * ((n_alpha + 1) / 2) <= ctx->cu_count;
+}
+
 #ifdef FWD_STAMPS
-__device__ unsigned long long g_fwd_stamps[12];
+__device__ unsigned long long g_fwd_stamps[24];   // the leading wave's phases | the pipelined form's helper wave's
 #endif
 
 // OPEN: the open-loop rollout of make_trajectory (ddp.hpp:392-415) on the same machinery: one candidate, u = U as given, x to X
@@ -449,28 +475,39 @@ __device__ unsigned long long g_fwd_stamps[12];
 // instantiation of its own as well
 // BOX: control bounds (DDP_HIP_FLAG_CONTROL_BOUNDS): u is clamped to [lo_t, hi_t] after the control update; lo_t, hi_t ride in the
 // prefetch beside k_t.  Closed loop only, an instantiation of its own as well
-template <int NJ, bool OPEN = false, bool FF = false, int COST = 0, bool BOX = false>
+// PIPE: the pipelined form ("Forward"): q_{t+1} = q_t (+) dt v_t needs no dynamics, so the second wave forms
+// it at the start of step t and runs the q-part of step t + 1's traversal (rbd::aba_pipe_q: placements, inertia sums, U, 1/D, Ia,
+// X^T Ia X) into the record buffer (t + 1) & 1 while the leading wave runs step t's x-part (rbd::aba_pipe_x) on buffer t & 1; the
+// two meet at ONE workgroup barrier per step.  Two candidates per workgroup (FwdPipeLds), grid = instances x ceil(n_alpha / 2).
+// Iteration t = -1 is the prologue: the helper forms the q-part of step 0, the leading wave waits.  Every early return above the
+// loop is workgroup-uniform and both waves run T + 1 iterations with one barrier each, whatever `live` is
+template <int NJ, bool OPEN = false, bool FF = false, int COST = 0, bool BOX = false, bool PIPE = false>
 __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
   static_assert(!(OPEN && BOX), "the open-loop rollout applies U as given");
   constexpr bool TRACK = (COST & 1) != 0, FRAME = (COST & 2) != 0, LIMIT = (COST & 4) != 0, ORIENT = (COST & 8) != 0;
   static_assert(!ORIENT || FRAME, "the orientation terms are of the cost frames: bit 3 implies bit 1");
-  using L = typename std::conditional<BOX, FwdLat2LdsBox<NJ>, FwdLat2Lds<NJ>>::type;
+  using L = typename std::conditional<PIPE, typename std::conditional<BOX, FwdPipeLdsBox<NJ>, FwdPipeLds<NJ>>::type,
+                                      typename std::conditional<BOX, FwdLat2LdsBox<NJ>, FwdLat2Lds<NJ>>::type>::type;
   constexpr int NC = L::NC, NH = L::NH;
   constexpr int n = 2 * NJ, nq = FF ? NJ + 1 : NJ, nx = nq + NJ, nu = NJ, XS = L::n;   // XS: stride of a candidate's state in LDS
   constexpr int K2 = nu * n / 2, KR = (K2 + 63) / 64;        // K_t as 16-byte words; words per lane
   static_assert((nu * n) % 2 == 0, "K_t is moved in 16-byte words");
   extern __shared__ __attribute__((aligned(16))) double lds[];
   L& S = *reinterpret_cast<L*>(lds);
-  const int b = OPEN ? blockIdx.x : blockIdx.x / 2, half = OPEN ? 0 : blockIdx.x % 2;
-  if (!OPEN && p.state[b] != 0) return;
   const int na = OPEN ? 1 : p.n_alpha;
+  const int groups = PIPE ? (na + NC - 1) / NC : 2;   // workgroups per instance
+  const int b = OPEN ? blockIdx.x : blockIdx.x / groups, half = OPEN ? 0 : blockIdx.x % groups;
+  if (!OPEN && p.state[b] != 0) return;
   if (half * NC >= na) return;
-  // two waves: wave 0 runs the rollout, wave 1 joins it for the inertia half of the leaf -> root pass (rbd::aba_tree_coop2w)
-  const int wave = threadIdx.x / 64, tid = threadIdx.x % 64, al = tid / NH, h = tid % NH;
+  // two waves: wave 0 runs the rollout, wave 1 joins it for the inertia half of the leaf -> root pass (rbd::aba_tree_coop2w), or
+  // runs one step ahead of it (PIPE)
+  const int wave = threadIdx.x / 64, tid = threadIdx.x % 64, al0 = tid / NH, h = tid % NH;
+  const int al = al0 < NC ? al0 : NC - 1;            // (PIPE: the upper lanes of a wave have no candidate; they stay inside the arrays)
   const int a = half * NC + al;
   const int cand = p.round * na + a;
-  const bool live = a < na && cand <= 33;            // 2^-34 < 1e-10: never tried (ddp_fwd.ipp:35-37)
-  if (!OPEN && a < na && cand > 33 && h == 0 && wave == 0) p.fw_dcost[(int64_t)b * na + a] = INFINITY;
+  const bool mine = al0 < NC && a < na;
+  const bool live = mine && cand <= 33;              // 2^-34 < 1e-10: never tried (ddp_fwd.ipp:35-37)
+  if (!OPEN && mine && cand > 33 && h == 0 && wave == 0) p.fw_dcost[(int64_t)b * na + a] = INFINITY;
   const double step = ldexp(1.0, -cand);
   const int64_t T = p.d.T;
   const double* xo = p.x_old + (int64_t)b * (T + 1) * nx;
@@ -563,11 +600,12 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
   rbd::FwdStamp* fs = nullptr;
 #ifdef FWD_STAMPS
   rbd::FwdStamp fsv{};
-  if (lead) fs = &fsv;
+  if (lead || PIPE) fs = &fsv;
   fsv.last = wall_clock64();
 #endif
-  for (int64_t t = 0; t < T; ++t) {
-    if (lead) {
+  for (int64_t t = PIPE ? -1 : 0; t < T; ++t) {
+    if constexpr (PIPE) x = S.x + ((int)(t & 1) * NC + al) * XS;   // x_t; t = -1: the prologue
+    if (lead && (!PIPE || t >= 0)) {
     if constexpr (OPEN) {
       if (live)
         for (int i = h; i < nu; i += NH) u[i] = S.uo[i];
@@ -631,6 +669,50 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
     if (t + 1 < T) request(t + 1);
     FSTAMP(fs, 2);
     }
+    if constexpr (PIPE) {
+      double* xn = S.x + ((int)((t + 1) & 1) * NC + al) * XS;                    // x_{t+1}: q by the helper, v by the leading wave
+      if (lead) {
+        if (t >= 0) {
+          rbd::aba_pipe_x<NJ, NC, NH, rbd::CoopModel<NJ>, FF>(S.model, S.rec[t & 1], x + nq, u, qdd, S.state, al, h, live, fs);   // :50
+          if (live)
+            for (int i = h; i < NJ; i += NH) {                                  // dynamics_t::eval_to, problem.hpp:441-461: the velocities
+              const double vn = x[nq + i] + qdd[i] * mdt;
+              xn[nq + i] = vn;
+              xw[(t + 1) * nx + nq + i] = vn;
+            }
+          FSTAMP(fs, 7);
+          if (t + 1 < T) { park(); cold_t = coldreg; }
+          FSTAMP(fs, 8);
+        }
+      } else {
+        if (t >= 0) {
+          // ... the configuration: the one expression q_{t+1} comes from
+          if constexpr (FF) {
+            if (live && h == 0) {
+              double dq[6], q7[7];
+#pragma unroll
+              for (int k = 0; k < 6; ++k) dq[k] = mdt * x[nq + k];
+              lie::se3_integrate(x, dq, q7);
+#pragma unroll
+              for (int k = 0; k < 7; ++k) xn[k] = q7[k];
+            }
+            if (live)
+              for (int i = 6 + h; i < NJ; i += NH) { const double vo = mdt * x[nq + i]; xn[i + 1] = x[i + 1] + vo; }
+          } else {
+            if (live)
+              for (int i = h; i < NJ; i += NH) { const double vo = mdt * x[NJ + i]; xn[i] = x[i] + vo; }
+          }
+          rbd::coop_sync<true>();
+          FSTAMP(fs, 0);
+        }
+        if (t + 1 < T) rbd::aba_pipe_q<NJ, NC, NH, rbd::CoopModel<NJ>, FF>(S.model, xn, S.rec[(t + 1) & 1], S.z, al, h, live, fs);
+      }
+      rbd::wg_sync_lds();                            // the step's one barrier: x_{t+1} and its record are whole
+      FSTAMP(fs, lead ? 3 : 5);
+      if (lead && t >= 0 && live)
+        for (int i = h; i < nq; i += NH) xw[(t + 1) * nx + i] = xn[i];
+      continue;
+    }
     rbd::aba_tree_coop2w<NJ, NC, NH, rbd::CoopModel<NJ>, FF>(S.model, x, x + nq, u, qdd, S.state, al, h, live, wave, fs);   // :50
     if (!lead) continue;
     if constexpr (FF) {
@@ -668,9 +750,10 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
     FSTAMP(fs, 8);
   }
 #ifdef FWD_STAMPS
-  if (threadIdx.x == 0 && blockIdx.x == 0)
-    for (int i = 0; i < 12; ++i) g_fwd_stamps[i] = fsv.acc[i];
+  if (tid == 0 && blockIdx.x == 0)
+    for (int i = 0; i < 12; ++i) g_fwd_stamps[12 * wave + i] = PIPE || lead ? fsv.acc[i] : 0;
 #endif
+  if constexpr (PIPE) x = S.x + ((int)(T & 1) * NC + al) * XS;                   // x_T
   double c_term = 0.0;
   if constexpr (TRACK) { if (lead) c_term = track_lanes_sum<FF>(p, b, T, x, u, h, live); }
   if constexpr (FRAME && !ORIENT) { if (lead) c_term += frame_lanes_sum<FF>(p, S.model, b, T, x, h, live); }
@@ -992,19 +1075,31 @@ FwdParams make_params(ddp_hip_ctx* ctx) {
 
 // the closed-loop instantiation of the latency kernel for (free-flyer root, inline cost terms, control bounds)
 using Lat2Fn = void (*)(FwdParams);
-Lat2Fn lat2_kernel(bool ff, int cost, bool box) {
-#define LAT2_ROW(FF, COST) {&forward_kernel_lat2<38, false, FF, COST, false>, &forward_kernel_lat2<38, false, FF, COST, true>}
+Lat2Fn lat2_kernel(bool ff, int cost, bool box, bool pipe) {
+#define LAT2_ROW(FF, COST) {{&forward_kernel_lat2<38, false, FF, COST, false, false>, &forward_kernel_lat2<38, false, FF, COST, false, true>}, \
+                            {&forward_kernel_lat2<38, false, FF, COST, true, false>, &forward_kernel_lat2<38, false, FF, COST, true, true>}}
   // COST 8 .. 15: the orientation terms; bit 3 implies bit 1, so only 10, 11, 14 and 15 exist (slots 8 .. 11)
-  static const Lat2Fn table[2][12][2] = {{LAT2_ROW(false, 0), LAT2_ROW(false, 1), LAT2_ROW(false, 2), LAT2_ROW(false, 3),
-                                          LAT2_ROW(false, 4), LAT2_ROW(false, 5), LAT2_ROW(false, 6), LAT2_ROW(false, 7),
-                                          LAT2_ROW(false, 10), LAT2_ROW(false, 11), LAT2_ROW(false, 14), LAT2_ROW(false, 15)},
-                                         {LAT2_ROW(true, 0), LAT2_ROW(true, 1), LAT2_ROW(true, 2), LAT2_ROW(true, 3),
-                                          LAT2_ROW(true, 4), LAT2_ROW(true, 5), LAT2_ROW(true, 6), LAT2_ROW(true, 7),
-                                          LAT2_ROW(true, 10), LAT2_ROW(true, 11), LAT2_ROW(true, 14), LAT2_ROW(true, 15)}};
+  static const Lat2Fn table[2][12][2][2] = {{LAT2_ROW(false, 0), LAT2_ROW(false, 1), LAT2_ROW(false, 2), LAT2_ROW(false, 3),
+                                             LAT2_ROW(false, 4), LAT2_ROW(false, 5), LAT2_ROW(false, 6), LAT2_ROW(false, 7),
+                                             LAT2_ROW(false, 10), LAT2_ROW(false, 11), LAT2_ROW(false, 14), LAT2_ROW(false, 15)},
+                                            {LAT2_ROW(true, 0), LAT2_ROW(true, 1), LAT2_ROW(true, 2), LAT2_ROW(true, 3),
+                                             LAT2_ROW(true, 4), LAT2_ROW(true, 5), LAT2_ROW(true, 6), LAT2_ROW(true, 7),
+                                             LAT2_ROW(true, 10), LAT2_ROW(true, 11), LAT2_ROW(true, 14), LAT2_ROW(true, 15)}};
 #undef LAT2_ROW
   if ((cost & 8) && !(cost & 2)) return nullptr;
   const int slot = (cost & 8) ? 8 + (cost & 1) + ((cost & 4) ? 2 : 0) : cost & 7;
-  return table[ff ? 1 : 0][slot][box ? 1 : 0];
+  return table[ff ? 1 : 0][slot][box ? 1 : 0][pipe ? 1 : 0];
+}
+// the open-loop instantiation (ddp_hip_rollout)
+Lat2Fn lat2_open_kernel(bool ff, bool pipe) {
+  static const Lat2Fn table[2][2] = {{&forward_kernel_lat2<38, true, false, 0, false, false>, &forward_kernel_lat2<38, true, false, 0, false, true>},
+                                     {&forward_kernel_lat2<38, true, true, 0, false, false>, &forward_kernel_lat2<38, true, true, 0, false, true>}};
+  return table[ff ? 1 : 0][pipe ? 1 : 0];
+}
+// ... and the dynamic LDS of a launch
+size_t lat2_lds(bool box, bool pipe) {
+  if (pipe) return box ? sizeof(FwdPipeLdsBox<38>) : sizeof(FwdPipeLds<38>);
+  return box ? sizeof(FwdLat2LdsBox<38>) : sizeof(FwdLat2Lds<38>);
 }
 
 #define DISPATCH_NJ(nv, CALL)                 \
@@ -1041,9 +1136,10 @@ int fwd_setup(ddp_hip_ctx* ctx) {
   HIP_TRY(hipMalloc(&ctx->fw_state_d, sizeof(int32_t) * (size_t)B));
   if (d.nv == 38) {
     // per device, by every context (the attribute is not process-wide)
-    const int lds = (int)sizeof(FwdLat2Lds<38>), lds_box = (int)sizeof(FwdLat2LdsBox<38>);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&forward_kernel_lat2<38, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    for (int ff = 0; ff < 2; ++ff)
+      for (int pipe = 0; pipe < 2; ++pipe)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lat2_open_kernel(ff != 0, pipe != 0)), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lat2_lds(false, pipe != 0)));
     // the closed-loop instantiations this context's flags can reach (lat2_kernel)
     const bool frame = (ctx->flags & DDP_HIP_FLAG_FRAME_COST) != 0, bounds = (ctx->flags & DDP_HIP_FLAG_CONTROL_BOUNDS) != 0;
     const int costs = 1 | (frame ? 2 : 0) | ((ctx->flags & DDP_HIP_FLAG_STATE_LIMITS) ? 4 : 0) |
@@ -1051,9 +1147,10 @@ int fwd_setup(ddp_hip_ctx* ctx) {
     for (int ff = 0; ff < 2; ++ff)
       for (int cost = 0; cost < 16; ++cost)
         for (int box = 0; box < (bounds ? 2 : 1); ++box)
-          if (!(cost & ~costs) && (!(cost & 8) || (cost & 2)))
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lat2_kernel(ff != 0, cost, box != 0)), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      box ? lds_box : lds));
+          for (int pipe = 0; pipe < 2; ++pipe)
+            if (!(cost & ~costs) && (!(cost & 8) || (cost & 2)))
+              HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lat2_kernel(ff != 0, cost, box != 0, pipe != 0)),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lat2_lds(box != 0, pipe != 0)));
   }
   return DDP_HIP_OK;
 }
@@ -1073,8 +1170,8 @@ void fwd_teardown(ddp_hip_ctx* ctx) {
 }
 
 #ifdef FWD_STAMPS
-extern "C" int ddp_hip_debug_fwd_stamps(unsigned long long* out12) {
-  return hipMemcpyFromSymbol(out12, HIP_SYMBOL(g_fwd_stamps), sizeof(unsigned long long) * 12) == hipSuccess ? 0 : -2;
+extern "C" int ddp_hip_debug_fwd_stamps(unsigned long long* out24) {
+  return hipMemcpyFromSymbol(out24, HIP_SYMBOL(g_fwd_stamps), sizeof(unsigned long long) * 24) == hipSuccess ? 0 : -2;
 }
 #endif
 
@@ -1084,8 +1181,8 @@ extern "C" int ddp_hip_rollout(ddp_hip_ctx* ctx) {
   FwdParams p = make_params(ctx);
   if (fwd_lat_supported(ctx)) {
     // unconstrained trees of the Talos size: the open-loop form of the latency kernel (one workgroup per instance)
-    if (ctx->model_h.ff) hipLaunchKernelGGL((forward_kernel_lat2<38, true, true>), dim3((unsigned)ctx->d.batch), dim3(128), sizeof(FwdLat2Lds<38>), ctx->stream, p);
-    else hipLaunchKernelGGL((forward_kernel_lat2<38, true>), dim3((unsigned)ctx->d.batch), dim3(128), sizeof(FwdLat2Lds<38>), ctx->stream, p);
+    const bool pipe = fwd_use_pipe(ctx, ctx->d.batch, 1);
+    hipLaunchKernelGGL(lat2_open_kernel(ctx->model_h.ff != 0, pipe), dim3((unsigned)ctx->d.batch), dim3(128), lat2_lds(false, pipe), ctx->stream, p);
   } else {
     const int bs = 64;
     const unsigned grid = (unsigned)((ctx->d.batch + bs - 1) / bs);
@@ -1221,12 +1318,14 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
     // cost terms of the rolled-out candidates come from cand_cost_kernel (parallel over t) instead of the rollout itself
     const bool lat_path = fwd_lat_supported(ctx) && n_alpha <= 8;
     if (lat_path) {
-      const dim3 g((unsigned)(2 * B)), blk(128);
+      // the pipelined form while its grid fits the device (fwd_use_pipe), else four candidates per workgroup
+      const bool pipe = fwd_use_pipe(ctx, B, n_alpha);
+      const dim3 g((unsigned)(pipe ? B * ((n_alpha + 1) / 2) : 2 * B)), blk(128);
       // the cost terms an unconstrained problem forms inline: bit 0 tracking, bit 1 frames, bit 2 state limits (forward_kernel_lat2: COST)
       // bit 3 the frame orientations, which imply bit 1
       const int cost = p.cost_inline ? (p.track ? 1 : 0) | (p.fc.target ? 2 : 0) | (p.sl.weight ? 4 : 0) | (p.fc.oquat ? 10 : 0) : 0;
       const bool box = p.ctrl_lo != nullptr;
-      hipLaunchKernelGGL(lat2_kernel(ctx->model_h.ff != 0, cost, box), g, blk, box ? sizeof(FwdLat2LdsBox<38>) : sizeof(FwdLat2Lds<38>), ctx->stream, p);
+      hipLaunchKernelGGL(lat2_kernel(ctx->model_h.ff != 0, cost, box, pipe), g, blk, lat2_lds(box, pipe), ctx->stream, p);
       if (!p.cost_inline) {
         const dim3 gc((unsigned)((B * n_alpha * (d.T + 1) + 63) / 64));
 #define LAUNCH(F, L) hipLaunchKernelGGL((cand_cost_kernel<38, F, L>), gc, dim3(64), 0, ctx->stream, p)

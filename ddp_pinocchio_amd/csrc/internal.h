@@ -76,6 +76,7 @@ struct DevSwitches {
   bool ana_eq_kernel = false;  // ANA_EQ_KERNEL: the constraint tensors in a kernel of their own
   bool bwd_no_graph = false;   // BWD_NO_GRAPH: the sweep is enqueued launch by launch, not replayed as a hipGraph
   bool solve_sync = false;     // SOLVE_SYNC: ddp_hip_solve waits for the stream at every call
+  bool fwd_no_pipe = false;    // FWD_NO_PIPE: the forward latency kernel in its four-candidate form, never the pipelined one
   int32_t bwd_cbx = 0, bwd_cbu = 0;   // BWD_CBX (1..8), BWD_CBU (1..16): columns per job of K3 / bwd_assemble
   int64_t qws_bt = 0;          // QWS_BT (16..65536): (instance, t) pairs per configuration-level workspace slice
   int64_t ana_bt = 0;          // ANA_BT (1..65536): (instance, t) pairs per analytic workspace slice
@@ -179,6 +180,7 @@ struct ProfSlot {
 
 struct ddp_hip_ctx {
   int device = 0;
+  int cu_count = 0;                    // the device's compute units, read once at create (fwd.hip: which form a forward launch takes)
   uint32_t flags = 0;
   hipStream_t stream = nullptr;
   Dims d{};

@@ -1263,4 +1263,270 @@ __device__ __forceinline__ void aba_tree_coop2w(const M& m, const double* q, con
   FSTAMP(fs, 6);
 }
 
+// ---- pipelined variant (fwd.hip: forward_kernel_lat2<…, PIPE>) --------------------------------------------------------
+// q_{t+1} = q_t (+) dt v_t is known before the dynamics of step t start, and the placements E | r, the children's inertia sums,
+// U, 1/D, Ia = IA - U U^T / D and X^T Ia X depend on q alone.  aba_tree_coop2w split in two along that line: the q-part, run by a
+// helper wave one step ahead into a record of its own per joint (E | r | U | 1/D | Ia), and the x-part (pass 1, the force half of
+// pass 2, pass 3), which only reads such a record.  The q-part's contributions X^T Ia X live in slots private to it; the x-part's
+// cb | pA | uu | vel in slots private to it: inside either part the exchange points are wave-level fences.  Every entry is formed
+// by the same operations in the same order as in aba_tree_coop2w (descending child order, the free-flyer root's sym6_solve
+// branch: its articulated inertia rides in the Ia slots of its record, which a root has no other use for).
+constexpr int ABA_PIPE_QSLOTS = 41;   // per joint: E 9 | r 3 | U 6 | Dinv 1 | Ia 21 | one unused (an odd stride spreads the joints of a level over the LDS banks)
+constexpr int ABA_PIPE_ZSLOTS = 21;   // per joint: X^T Ia X
+constexpr int ABA_PIPE_XSLOTS = 19;   // per joint: cb 6 | pA 6 | uu 1 | vel/acc 6
+
+// the q-part at configuration q into `rec`; `zst`: its contribution slots.  One wave; every lane of it calls
+template <int NJ, int TPB, int NH, class M, bool FF = false>
+__device__ __forceinline__ void aba_pipe_q(const M& m, const double* q, double* rec, double* zst, int cand, int h, bool live,
+                                           FwdStamp* fs = nullptr) {
+  const int nj = FF ? m.nv - 5 : m.nv;
+  auto QI = [](int i) { return FF ? i + 6 : i; };
+  auto Q = [&](int joint, int slot) -> double& { return rec[(joint * ABA_PIPE_QSLOTS + slot) * TPB + cand]; };
+  auto Z = [&](int joint, int slot) -> double& { return zst[(joint * ABA_PIPE_ZSLOTS + slot) * TPB + cand]; };
+  constexpr int oE = 0, oR = 9, oU = 12, oD = 18, oA = 19;
+  const int NL = m.n_levels;
+  if (live)
+    for (int i = h; i < nj; i += NH) {
+      double E[9], R[3];
+      if (FF && i == 0) {                            // rbd::place: E = R(quaternion)^T, r = p
+        double Rq[9];
+        lie::quat_to_R(q + 3, Rq);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+          for (int l = 0; l < 3; ++l) E[3 * k + l] = Rq[3 * l + k];
+        R[0] = q[0]; R[1] = q[1]; R[2] = q[2];
+      } else {
+        joint_placement(m, i, q[QI(i)], E, R);
+      }
+#pragma unroll
+      for (int k = 0; k < 9; ++k) Q(i, oE + k) = E[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) Q(i, oR + k) = R[k];
+    }
+  coop_sync<true>();
+  FSTAMP(fs, 3);
+  for (int L = NL - 1; L >= 0; --L) {                // leaves -> root: the inertia half of pass 2
+    const unsigned long long rr = m.role[L * NH + h];
+    if (live && role_joint(rr) != 255) {
+      const int i = role_joint(rr);
+      const double* a = m.axis[i];
+      const bool rev = role_rev(rr);
+      const int nch = role_nchildren(rr);
+      double IA[21], U[6];
+#pragma unroll
+      for (int k = 0; k < 21; ++k) IA[k] = m.I6[i][k];
+#pragma unroll
+      for (int ci = 0; ci < ROLE_MAX_CHILDREN; ++ci) {   // contributions, descending child index
+        if (ci < nch) {
+          const int c = role_child(rr, ci);
+#pragma unroll
+          for (int k = 0; k < 21; ++k) IA[k] += Z(c, k);
+        }
+      }
+      FSTAMP(fs, 9);
+      if (FF && i == 0) {
+#pragma unroll
+        for (int k = 0; k < 21; ++k) Q(i, oA + k) = IA[k];   // resolved in the x-part's last pass (sym6_solve)
+      } else {
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+          const double i0 = rev ? IA[sidx(r, 0)] : IA[sidx(r, 3)];
+          const double i1 = rev ? IA[sidx(r, 1)] : IA[sidx(r, 4)];
+          const double i2 = rev ? IA[sidx(r, 2)] : IA[sidx(r, 5)];
+          U[r] = i0 * a[0] + i1 * a[1] + i2 * a[2];
+        }
+        double d = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) d += a[k] * (rev ? U[k] : U[3 + k]);
+        const double dinv = 1.0 / d;
+        FSTAMP(fs, 10);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) Q(i, oU + k) = U[k];
+        Q(i, oD) = dinv;
+        if (role_parent(rr) >= 0) {
+          double E[9], R[3], Ia[21], Zc[21];
+#pragma unroll
+          for (int k = 0; k < 9; ++k) E[k] = Q(i, oE + k);
+#pragma unroll
+          for (int k = 0; k < 3; ++k) R[k] = Q(i, oR + k);
+#pragma unroll
+          for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = 0; c <= r; ++c) Ia[sidx(r, c)] = IA[sidx(r, c)] - U[r] * U[c] * dinv;
+#pragma unroll
+          for (int k = 0; k < 21; ++k) Q(i, oA + k) = Ia[k];
+#pragma unroll
+          for (int k = 0; k < 21; ++k) Zc[k] = 0.0;
+          add_xtix(E, R, Ia, Zc);
+#pragma unroll
+          for (int k = 0; k < 21; ++k) Z(i, k) = Zc[k];
+        }
+      }   // (not the free-flyer root)
+    }
+    FSTAMP(fs, 11);
+    coop_sync<true>();
+  }
+}
+
+// the x-part from a finished record `rec` of q; `xst`: its own per-joint slots.  One wave; every lane of it calls
+template <int NJ, int TPB, int NH, class M, bool FF = false>
+__device__ __forceinline__ void aba_pipe_x(const M& m, const double* rec, const double* v, const double* tau, double* qdd,
+                                           double* xst, int cand, int h, bool live, FwdStamp* fs = nullptr) {
+  auto VI = [](int i) { return FF ? i + 5 : i; };
+  auto Q = [&](int joint, int slot) -> const double& { return rec[(joint * ABA_PIPE_QSLOTS + slot) * TPB + cand]; };
+  auto S = [&](int joint, int slot) -> double& { return xst[(joint * ABA_PIPE_XSLOTS + slot) * TPB + cand]; };
+  constexpr int oE = 0, oR = 9, oU = 12, oD = 18, oA = 19;   // the record
+  constexpr int oC = 0, oP = 6, oT = 12, oV = 13;            // the x-part's own slots
+  const int NL = m.n_levels;
+  for (int L = 0; L < NL; ++L) {                   // pass 1, root -> leaves
+    const unsigned long long rr = m.role[L * NH + h];
+    if (live && role_joint(rr) != 255) {
+      const int i = role_joint(rr);
+      double E[9], R[3], vel[6], vp[6], cb[6], pA[6], Iv[6], I6[21];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) E[k] = Q(i, oE + k);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) R[k] = Q(i, oR + k);
+      const double* a = m.axis[i];
+      double vJ[6] = {0, 0, 0, 0, 0, 0};
+      const int o = role_rev(rr) ? 0 : 3;
+      if (FF && i == 0) { vJ[0] = v[3]; vJ[1] = v[4]; vJ[2] = v[5]; vJ[3] = v[0]; vJ[4] = v[1]; vJ[5] = v[2]; }   // S = identity on the body twist
+      else { const double vi = v[VI(i)]; vJ[o] = a[0] * vi; vJ[o + 1] = a[1] * vi; vJ[o + 2] = a[2] * vi; }
+      const int par = role_parent(rr);
+      if (par >= 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) vp[k] = S(par, oV + k);
+        xform_motion(E, R, vp, vel);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) vel[k] = 0.0;
+      }
+#pragma unroll
+      for (int k = 0; k < 6; ++k) vel[k] += vJ[k];
+      crm(vel, vJ, cb);
+#pragma unroll
+      for (int k = 0; k < 21; ++k) I6[k] = m.I6[i][k];
+      sym6_mv(I6, vel, Iv);
+      crf(vel, Iv, pA);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) { S(i, oV + k) = vel[k]; S(i, oC + k) = cb[k]; S(i, oP + k) = pA[k]; }
+    }
+    coop_sync<true>();
+  }
+  FSTAMP(fs, 4);
+  for (int L = NL - 1; L >= 0; --L) {              // pass 2, leaves -> root: the forces
+    const unsigned long long rr = m.role[L * NH + h];
+    if (live && role_joint(rr) != 255) {
+      const int i = role_joint(rr);
+      const double* a = m.axis[i];
+      const bool rev = role_rev(rr);
+      const int nch = role_nchildren(rr);
+      double pAi[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) pAi[k] = S(i, oP + k);
+      if (FF && i == 0) {
+        // the free-flyer root is resolved in the last pass: its bias force stays in its slots; it has no parent to contribute to
+#pragma unroll
+        for (int ci = 0; ci < ROLE_MAX_CHILDREN; ++ci) {
+          if (ci < nch) {
+            const int c = role_child(rr, ci);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) pAi[k] += S(c, oP + k);
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) S(i, oP + k) = pAi[k];
+      } else {
+        double cb[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) cb[k] = S(i, oC + k);
+#pragma unroll
+        for (int ci = 0; ci < ROLE_MAX_CHILDREN; ++ci) {
+          if (ci < nch) {
+            const int c = role_child(rr, ci);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) pAi[k] += S(c, oP + k);
+          }
+        }
+        double sp = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) sp += a[k] * (rev ? pAi[k] : pAi[3 + k]);
+        const double ui = tau[VI(i)] - sp;
+        S(i, oT) = ui;
+        if (role_parent(rr) >= 0) {
+          double E[9], R[3], U[6], Ia[21], pa[6], Iac[6], fp[6];
+#pragma unroll
+          for (int k = 0; k < 9; ++k) E[k] = Q(i, oE + k);
+#pragma unroll
+          for (int k = 0; k < 3; ++k) R[k] = Q(i, oR + k);
+#pragma unroll
+          for (int k = 0; k < 6; ++k) U[k] = Q(i, oU + k);
+          const double dinv = Q(i, oD);
+#pragma unroll
+          for (int k = 0; k < 21; ++k) Ia[k] = Q(i, oA + k);
+          sym6_mv(Ia, cb, Iac);
+#pragma unroll
+          for (int k = 0; k < 6; ++k) pa[k] = pAi[k] + Iac[k] + U[k] * (ui * dinv);
+          xform_force_T(E, R, pa, fp);
+#pragma unroll
+          for (int k = 0; k < 6; ++k) S(i, oP + k) = fp[k];
+        }
+      }   // (not the free-flyer root)
+    }
+    coop_sync<true>();
+  }
+  FSTAMP(fs, 5);
+  for (int L = 0; L < NL; ++L) {                   // pass 3, root -> leaves
+    const unsigned long long rr = m.role[L * NH + h];
+    if (live && role_joint(rr) != 255) {
+      const int i = role_joint(rr);
+      double E[9], R[3], ap[6], accp[6], U[6], cb[6];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) E[k] = Q(i, oE + k);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) R[k] = Q(i, oR + k);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) { U[k] = Q(i, oU + k); cb[k] = S(i, oC + k); }
+      const int par = role_parent(rr);
+      if (par >= 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) accp[k] = S(par, oV + k);
+        xform_motion(E, R, accp, ap);
+      } else {
+        const double a0[6] = {0, 0, 0, -m.gravity[0], -m.gravity[1], -m.gravity[2]};
+        xform_motion(E, R, a0, ap);
+      }
+      if (FF && i == 0) {
+        // S = I: qdd_s = IA^-1 (tau_s - pA) - a' in the spatial ordering [angular; linear]; tau / qdd are ordered [linear; angular]
+        double IAr[21], rhs[6], qs[6];
+#pragma unroll
+        for (int k = 0; k < 21; ++k) IAr[k] = Q(i, oA + k);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { rhs[k] = tau[3 + k] - S(i, oP + k); rhs[3 + k] = tau[k] - S(i, oP + 3 + k); }
+        sym6_solve(IAr, rhs, qs);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) { ap[k] += cb[k]; qs[k] -= ap[k]; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { qdd[k] = qs[3 + k]; qdd[3 + k] = qs[k]; }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) S(i, oV + k) = ap[k] + qs[k];
+      } else {
+      double s = 0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) { ap[k] += cb[k]; s += U[k] * ap[k]; }
+      const double qd = (S(i, oT) - s) * Q(i, oD);
+      qdd[VI(i)] = qd;
+      const double* a = m.axis[i];
+      const int o = role_rev(rr) ? 0 : 3;
+      ap[o] += a[0] * qd; ap[o + 1] += a[1] * qd; ap[o + 2] += a[2] * qd;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) S(i, oV + k) = ap[k];
+      }   // (not the free-flyer root)
+    }
+    coop_sync<true>();
+  }
+  FSTAMP(fs, 6);
+}
+
 }  // namespace rbd
