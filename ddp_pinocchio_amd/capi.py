@@ -467,13 +467,41 @@ class Context:
         for name, arr in arrs.items():
             self.upload(name, arr, first, count)
 
+    def _cost_sides(self, where, sides, first, count):
+        """The sides of one add-on cost term's upload, checked before the library is touched: each side is (label, array or
+        None, per-instance shape, further accepted shapes).  An array is (count,) + per, per, or one of the further shapes,
+        and is broadcast to (count,) + per.  Returns (count, the contiguous arrays or None per side)"""
+        count = self.batch - first if count is None else count
+        out = []
+        for label, arr, per, extra in sides:
+            if arr is not None:
+                arr = np.asarray(arr, dtype=np.float64)
+                full = (count,) + tuple(per)
+                accepted = (full, tuple(per)) + tuple(extra)
+                if arr.shape not in accepted:
+                    raise ValueError(f"{where} {label}: shape {arr.shape}, expected one of {accepted[::-1]}")
+                arr = np.ascontiguousarray(np.broadcast_to(arr, full))
+            out.append(arr)
+        return count, out
+
+    def _cost_upload(self, fn, where, arrs, first, count):
+        """... and their single library call (no side given: no call)"""
+        if any(a is not None for a in arrs):
+            _check(fn(self._h, *[_ptr(a) if a is not None else None for a in arrs], first, count), where)
+
+    def _cost_download(self, fn, where, pers, first, count):
+        """One add-on cost term's sides of instances first .. first + count - 1, each (count,) + per"""
+        count = self.batch - first if count is None else count
+        out = tuple(np.zeros((max(count, 0),) + tuple(per)) for per in pers)
+        _check(fn(self._h, *[_ptr(a) for a in out], first, count), where)
+        return out
+
     def set_frame_cost(self, frames=None, target=None, weight=None, first=0, count=None):
         """The frame-position cost (a context created with FLAG_FRAME_COST; ddp_hip.h).  frames: a list of up to
         MAX_COST_FRAMES (joint, off) pairs, shared by the batch (another count than before resets targets and weights to 0).
         target / weight of instances first .. first + count - 1: (T+1, F, 3) for every instance of the range or
         (count, T+1, F, 3) with one per instance; weight also takes (F, 3), (3,) and scalars by broadcast.  None leaves that
         side as it is."""
-        count = self.batch - first if count is None else count
         n_frames = self.n_cost_frames
         if frames is not None:
             frames = list(frames)
@@ -484,30 +512,17 @@ class Context:
                 raise ValueError("set_frame_cost frames: every off is a 3-vector")
             off = _f64(off).reshape(-1)
         per = (self.spec.T + 1, n_frames, 3)
-        full = (count,) + per
-        arrs = {}
-        for name, arr in (("target", target), ("weight", weight)):
-            if arr is None:
-                continue
-            arr = np.asarray(arr, dtype=np.float64)
-            if not (arr.shape in (full, per) or (name == "weight" and arr.shape in (per[1:], per[2:], ()))):
-                raise ValueError(f"set_frame_cost {name}: shape {arr.shape}, expected {per} or {full}")
-            arrs[name] = np.ascontiguousarray(np.broadcast_to(arr, full))
+        count, arrs = self._cost_sides("set_frame_cost", (("target", target, per, ()), ("weight", weight, per, (per[1:], per[2:], ()))),
+                                       first, count)
         if frames is not None:
             _check(lib().ddp_hip_frame_cost_set_frames(self._h, n_frames, joint.ctypes.data_as(_ip), _ptr(off)), "frame_cost_set_frames")
             self.n_cost_frames = n_frames
-        if arrs:
-            t, w = arrs.get("target"), arrs.get("weight")
-            _check(lib().ddp_hip_frame_cost_upload(self._h, _ptr(t) if t is not None else None, _ptr(w) if w is not None else None,
-                                                   first, count), "frame_cost_upload")
+        self._cost_upload(lib().ddp_hip_frame_cost_upload, "frame_cost_upload", arrs, first, count)
 
     def frame_cost(self, first=0, count=None):
         """(target, weight) of instances first .. first + count - 1, each (count, T+1, F, 3)"""
-        count = self.batch - first if count is None else count
-        shape = (count, self.spec.T + 1, self.n_cost_frames, 3)
-        t, w = np.zeros(shape), np.zeros(shape)
-        _check(lib().ddp_hip_frame_cost_download(self._h, _ptr(t), _ptr(w), first, count), "frame_cost_download")
-        return t, w
+        per = (self.spec.T + 1, self.n_cost_frames, 3)
+        return self._cost_download(lib().ddp_hip_frame_cost_download, "frame_cost_download", (per, per), first, count)
 
     def set_frame_orient_cost(self, quat=None, weight=None, first=0, count=None):
         """The orientation terms of the cost frames (a context created with FLAG_FRAME_COST | FLAG_FRAME_ORIENT_COST, frames
@@ -515,91 +530,45 @@ class Context:
         the frame, >= 0; of instances first .. first + count - 1: (T+1, F, 4) / (T+1, F, 3) for every instance of the range or
         (count, T+1, F, .) with one per instance; weight also takes (F, 3), (3,) and scalars by broadcast.  None leaves that
         side as it is."""
-        count = self.batch - first if count is None else count
-        arrs = {}
-        for name, arr, k in (("quat", quat, 4), ("weight", weight, 3)):
-            if arr is None:
-                continue
-            per = (self.spec.T + 1, self.n_cost_frames, k)
-            full = (count,) + per
-            arr = np.asarray(arr, dtype=np.float64)
-            if not (arr.shape in (full, per) or (name == "weight" and arr.shape in (per[1:], per[2:], ()))):
-                raise ValueError(f"set_frame_orient_cost {name}: shape {arr.shape}, expected {per} or {full}")
-            arrs[name] = np.ascontiguousarray(np.broadcast_to(arr, full))
-        if "quat" in arrs and not bool(np.all(np.abs(np.sqrt(np.sum(arrs["quat"] ** 2, axis=-1)) - 1.0) <= 1e-10)):
+        T1, F = self.spec.T + 1, self.n_cost_frames
+        count, arrs = self._cost_sides("set_frame_orient_cost", (("quat", quat, (T1, F, 4), ()), ("weight", weight, (T1, F, 3), ((F, 3), (3,), ()))),
+                                       first, count)
+        if arrs[0] is not None and not bool(np.all(np.abs(np.sqrt(np.sum(arrs[0] ** 2, axis=-1)) - 1.0) <= 1e-10)):
             raise ValueError("set_frame_orient_cost quat: every quaternion has unit norm (to 1e-10)")
-        if arrs:
-            q, w = arrs.get("quat"), arrs.get("weight")
-            _check(lib().ddp_hip_frame_orient_upload(self._h, _ptr(q) if q is not None else None, _ptr(w) if w is not None else None,
-                                                     first, count), "frame_orient_upload")
+        self._cost_upload(lib().ddp_hip_frame_orient_upload, "frame_orient_upload", arrs, first, count)
 
     def frame_orient_cost(self, first=0, count=None):
         """(quat, weight) of instances first .. first + count - 1: (count, T+1, F, 4) and (count, T+1, F, 3)"""
-        count = self.batch - first if count is None else count
-        q = np.zeros((count, self.spec.T + 1, self.n_cost_frames, 4))
-        w = np.zeros((count, self.spec.T + 1, self.n_cost_frames, 3))
-        _check(lib().ddp_hip_frame_orient_download(self._h, _ptr(q), _ptr(w), first, count), "frame_orient_download")
-        return q, w
+        T1, F = self.spec.T + 1, self.n_cost_frames
+        return self._cost_download(lib().ddp_hip_frame_orient_download, "frame_orient_download", ((T1, F, 4), (T1, F, 3)), first, count)
 
     def set_com_cost(self, target=None, weight=None, first=0, count=None):
         """The centre-of-mass terms of instances first .. first + count - 1 (a context created with FLAG_COM_COST; ddp_hip.h).
         target: world positions, weight: per world axis, >= 0; each (T+1, 3) for every instance of the range or
         (count, T+1, 3) with one per instance; weight also takes (3,) and scalars for every step.  None leaves that side as
         it is."""
-        count = self.batch - first if count is None else count
         per = (self.spec.T + 1, 3)
-        full = (count,) + per
-        arrs = {}
-        for name, arr in (("target", target), ("weight", weight)):
-            if arr is None:
-                continue
-            arr = np.asarray(arr, dtype=np.float64)
-            if not (arr.shape in (full, per) or (name == "weight" and arr.shape in ((3,), ()))):
-                raise ValueError(f"set_com_cost {name}: shape {arr.shape}, expected {per} or {full}")
-            arrs[name] = np.ascontiguousarray(np.broadcast_to(arr, full))
-        if arrs:
-            t, w = arrs.get("target"), arrs.get("weight")
-            _check(lib().ddp_hip_com_cost_upload(self._h, _ptr(t) if t is not None else None, _ptr(w) if w is not None else None,
-                                                 first, count), "com_cost_upload")
+        count, arrs = self._cost_sides("set_com_cost", (("target", target, per, ()), ("weight", weight, per, ((3,), ()))), first, count)
+        self._cost_upload(lib().ddp_hip_com_cost_upload, "com_cost_upload", arrs, first, count)
 
     def com_cost(self, first=0, count=None):
         """(target, weight) of instances first .. first + count - 1, each (count, T+1, 3)"""
-        count = self.batch - first if count is None else count
-        t = np.zeros((count, self.spec.T + 1, 3))
-        w = np.zeros((count, self.spec.T + 1, 3))
-        _check(lib().ddp_hip_com_cost_download(self._h, _ptr(t), _ptr(w), first, count), "com_cost_download")
-        return t, w
+        per = (self.spec.T + 1, 3)
+        return self._cost_download(lib().ddp_hip_com_cost_download, "com_cost_download", (per, per), first, count)
 
     def set_frame_vel_cost(self, target=None, weight=None, first=0, count=None):
         """The frame-velocity terms of instances first .. first + count - 1 (a context created with FLAG_FRAME_VEL_COST; ddp_hip.h),
         of the F frames of set_frame_cost.  target: desired linear, then angular velocity in world axes, weight: per axis, >= 0;
         each (T+1, F, 6) for every instance of the range or (count, T+1, F, 6) with one per instance; weight also takes (6,) and
         scalars for every step and frame.  None leaves that side as it is."""
-        count = self.batch - first if count is None else count
-        F = getattr(self, "n_cost_frames", 0)
-        per = (self.spec.T + 1, F, 6)
-        full = (count,) + per
-        arrs = {}
-        for name, arr in (("target", target), ("weight", weight)):
-            if arr is None:
-                continue
-            arr = np.asarray(arr, dtype=np.float64)
-            if not (arr.shape in (full, per) or (name == "weight" and arr.shape in ((6,), ()))):
-                raise ValueError(f"set_frame_vel_cost {name}: shape {arr.shape}, expected {per} or {full}")
-            arrs[name] = np.ascontiguousarray(np.broadcast_to(arr, full))
-        if arrs:
-            t, w = arrs.get("target"), arrs.get("weight")
-            _check(lib().ddp_hip_frame_vel_upload(self._h, _ptr(t) if t is not None else None, _ptr(w) if w is not None else None,
-                                                  first, count), "frame_vel_upload")
+        per = (self.spec.T + 1, getattr(self, "n_cost_frames", 0), 6)
+        count, arrs = self._cost_sides("set_frame_vel_cost", (("target", target, per, ()), ("weight", weight, per, ((6,), ()))), first, count)
+        self._cost_upload(lib().ddp_hip_frame_vel_upload, "frame_vel_upload", arrs, first, count)
 
     def frame_vel_cost(self, first=0, count=None):
         """(target, weight) of instances first .. first + count - 1, each (count, T+1, F, 6)"""
-        count = self.batch - first if count is None else count
-        F = getattr(self, "n_cost_frames", 0)
-        t = np.zeros((count, self.spec.T + 1, F, 6))
-        w = np.zeros((count, self.spec.T + 1, F, 6))
-        _check(lib().ddp_hip_frame_vel_download(self._h, _ptr(t), _ptr(w), first, count), "frame_vel_download")
-        return t, w
+        per = (self.spec.T + 1, getattr(self, "n_cost_frames", 0), 6)
+        return self._cost_download(lib().ddp_hip_frame_vel_download, "frame_vel_download", (per, per), first, count)
 
     def set_obstacle_points(self, points, kinds):
         """The collision points [(joint, off, radius), ...] (up to MAX_COLLISION_POINTS spheres on the robot) and the kinds of the
@@ -622,33 +591,17 @@ class Context:
         and t, (T+1, n_obs, 4) for every instance or (count, T+1, n_obs, 4); weight: >= 0, as (n_obs,), (T+1, n_obs) or
         (count, T+1, n_obs).  None leaves that side as it is.  The slot count is the one this object last passed to
         set_obstacle_points; before that call there is no shape to check against and the call raises ValueError."""
-        count = self.batch - first if count is None else count
-        no = getattr(self, "n_obstacles", 0)
+        T1, no = self.spec.T + 1, getattr(self, "n_obstacles", 0)
         if not no:
             raise ValueError("set_obstacle_cost: no obstacle slots yet, call set_obstacle_points first")
-        arrs = {}
-        for name, arr, tail in (("geom", geom, (no, 4)), ("weight", weight, (no,))):
-            if arr is None:
-                continue
-            arr = np.asarray(arr, dtype=np.float64)
-            per = (self.spec.T + 1,) + tail
-            full = (count,) + per
-            if arr.shape not in (full, per, tail):
-                raise ValueError(f"set_obstacle_cost {name}: shape {arr.shape}, expected {tail}, {per} or {full}")
-            arrs[name] = np.ascontiguousarray(np.broadcast_to(arr, full))
-        if arrs:
-            g, w = arrs.get("geom"), arrs.get("weight")
-            _check(lib().ddp_hip_obstacle_upload(self._h, _ptr(g) if g is not None else None, _ptr(w) if w is not None else None,
-                                                 first, count), "obstacle_upload")
+        count, arrs = self._cost_sides("set_obstacle_cost", (("geom", geom, (T1, no, 4), ((no, 4),)), ("weight", weight, (T1, no), ((no,),))),
+                                       first, count)
+        self._cost_upload(lib().ddp_hip_obstacle_upload, "obstacle_upload", arrs, first, count)
 
     def obstacle_cost(self, first=0, count=None):
         """(geom, weight) of instances first .. first + count - 1: (count, T+1, n_obs, 4) and (count, T+1, n_obs)"""
-        count = self.batch - first if count is None else count
-        no = getattr(self, "n_obstacles", 0)               # (0 before set_obstacle_points: empty arrays)
-        g = np.zeros((count, self.spec.T + 1, no, 4))
-        w = np.zeros((count, self.spec.T + 1, no))
-        _check(lib().ddp_hip_obstacle_download(self._h, _ptr(g), _ptr(w), first, count), "obstacle_download")
-        return g, w
+        T1, no = self.spec.T + 1, getattr(self, "n_obstacles", 0)               # (0 before set_obstacle_points: empty arrays)
+        return self._cost_download(lib().ddp_hip_obstacle_download, "obstacle_download", ((T1, no, 4), (T1, no)), first, count)
 
     def obstacle_clearance(self, which=0):
         """(batch, T+1): the least signed distance of a collision point to an obstacle of non-zero weight along X (which = 0) or
@@ -663,31 +616,17 @@ class Context:
         vector for every step, a (T+1, n) array for every instance of the range, or (count, T+1, n) with one per instance.
         -inf / +inf: no bound on that side.  None leaves that side as it is (the library then holds the side that arrives
         against the resident other one)."""
-        count = self.batch - first if count is None else count
-        sp = self.spec
-        full = (count, sp.T + 1, sp.n)
-        arrs = {}
-        for name, arr in (("lo", lo), ("hi", hi), ("weight", weight)):
-            if arr is None:
-                continue
-            arr = np.asarray(arr, dtype=np.float64)
-            if arr.ndim > 3 or (arr.ndim == 3 and arr.shape != full) or (arr.ndim == 2 and arr.shape != full[1:]) or \
-                    (arr.ndim == 1 and arr.shape != full[2:]):
-                raise ValueError(f"set_state_limits {name}: shape {arr.shape}, expected a scalar, {full[2:]}, {full[1:]} or {full}")
-            arrs[name] = np.ascontiguousarray(np.broadcast_to(arr, full))
-        if "lo" in arrs and "hi" in arrs and bool(np.any(arrs["lo"] > arrs["hi"])):
+        per, extra = (self.spec.T + 1, self.spec.n), ((self.spec.n,), ())
+        count, arrs = self._cost_sides("set_state_limits", (("lo", lo, per, extra), ("hi", hi, per, extra), ("weight", weight, per, extra)),
+                                       first, count)
+        if arrs[0] is not None and arrs[1] is not None and bool(np.any(arrs[0] > arrs[1])):
             raise ValueError("set_state_limits: some lo > hi")
-        if arrs:
-            a = [_ptr(arrs[k]) if k in arrs else None for k in ("lo", "hi", "weight")]
-            _check(lib().ddp_hip_state_limits_upload(self._h, a[0], a[1], a[2], first, count), "state_limits_upload")
+        self._cost_upload(lib().ddp_hip_state_limits_upload, "state_limits_upload", arrs, first, count)
 
     def state_limits(self, first=0, count=None):
         """(lo, hi, weight) of instances first .. first + count - 1, each (count, T+1, n)"""
-        count = self.batch - first if count is None else count
-        shape = (max(count, 0), self.spec.T + 1, self.spec.n)
-        lo, hi, w = np.zeros(shape), np.zeros(shape), np.zeros(shape)
-        _check(lib().ddp_hip_state_limits_download(self._h, _ptr(lo), _ptr(hi), _ptr(w), first, count), "state_limits_download")
-        return lo, hi, w
+        per = (self.spec.T + 1, self.spec.n)
+        return self._cost_download(lib().ddp_hip_state_limits_download, "state_limits_download", (per, per, per), first, count)
 
     def fill(self, name, value):
         _check(lib().ddp_hip_fill(self._h, SEQ[name], float(value)), f"fill {name}")

@@ -7,14 +7,15 @@
 #include "rbd.h"
 
 // What a kernel reads of the context's CoM cost.  target == nullptr: no terms (the flag is off, or no non-zero weight has been
-// uploaded: cm_live)
+// uploaded: the block's CostBlock::live)
 struct CoMCostDev {
   const double *target, *weight;   // [batch][T+1][3]
 };
 
 inline CoMCostDev com_cost_dev(const ddp_hip_ctx* ctx) {
   CoMCostDev c{};
-  if (ctx->cm_live) { c.target = ctx->cm_target_d; c.weight = ctx->cm_weight_d; }
+  const CostBlock& k = ctx->cost[COST_COM];
+  if (k.live) { c.target = k.side[0]; c.weight = k.side[1]; }
   return c;
 }
 

@@ -1,0 +1,152 @@
+// cost_block.h -- the per-instance add-on cost terms as records: what a term's arrays look like, and the
+// parts of its upload that call no HIP function -- flag and range checks, the per-side validators, the non-zero scan, the live
+// rule.  Host code without a device dependency: ctx.hip builds the upload path on it, host/test_cost_block.cpp runs it alone.
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+
+#include "ddp_hip/ddp_hip.h"
+
+// The terms, in the order the kernels add them (after the stage cost and the tracking cost): lin.hip launches one kernel per
+// live term in this order, fwd.hip forms the first three inline and the last three in kernels of their own, in this order
+enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_LIMITS, COST_COM, COST_FRAME_VEL, COST_OBSTACLE, COST_COUNT };
+
+enum CostFill : int32_t { FILL_ZERO, FILL_NEG_INF, FILL_POS_INF, FILL_QUAT };   // FILL_QUAT: identity quaternions (0, 0, 0, 1)
+
+#define COST_MAX_SIDES 3
+
+// What a term is made of.  A side is one array [batch][T+1][items][unit]; the last side is the weights
+struct CostDesc {
+  uint32_t flag;                    // the creation flag that enables the term
+  int32_t nside;
+  int32_t unit[COST_MAX_SIDES];     // doubles per item
+  int32_t fill[COST_MAX_SIDES];     // CostFill: what a side holds at create and after a change of layout
+  int32_t max_items;                // items the arrays have room for; 0: the tangent dimension n (CostBlock::max_items, set at create)
+  bool fixed;                       // laid out at create for max_items; else by the frames / slots set, up to max_items
+  bool cand;                        // the term has a candidates' array for the line search
+};
+
+static const CostDesc kCostDesc[COST_COUNT] = {
+    // flag, sides, doubles per item, fill, room, fixed, cand
+    {DDP_HIP_FLAG_FRAME_COST, 2, {3, 3, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, false},          // target | weight, per frame
+    {DDP_HIP_FLAG_FRAME_ORIENT_COST, 2, {4, 3, 0}, {FILL_QUAT, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, false},   // quat | weight, per frame
+    {DDP_HIP_FLAG_STATE_LIMITS, 3, {1, 1, 1}, {FILL_NEG_INF, FILL_POS_INF, FILL_ZERO}, 0, true, false},                 // lo | hi | weight, per tangent row
+    {DDP_HIP_FLAG_COM_COST, 2, {3, 3, 0}, {FILL_ZERO, FILL_ZERO, 0}, 1, true, true},                                    // target | weight
+    {DDP_HIP_FLAG_FRAME_VEL_COST, 2, {6, 6, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, true},       // target | weight, per frame
+    {DDP_HIP_FLAG_OBSTACLE_COST, 2, {4, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_OBSTACLES, false, true},          // geom | weight, per slot
+};
+
+// One term of one context
+struct CostBlock {
+  const CostDesc* desc = nullptr;
+  int32_t max_items = 0;            // the arrays are allocated for this many items per (instance, t) ...
+  int32_t items = 0;                // ... and laid out by this many (frames / slots set); 0: no layout yet
+  double* side[COST_MAX_SIDES] = {nullptr, nullptr, nullptr};   // device arrays (null: the flag is off)
+  double* cand = nullptr;           // [batch][n_alpha_max][T+1] the candidates' terms of a line-search round, from the first non-zero weight on
+  bool live = false;                // some non-zero weight is resident: the kernels form the term (cost_live_rule)
+};
+
+// doubles of side s per instance, as laid out now
+static inline int64_t cost_side_words(const CostBlock& k, int s, int64_t T) { return (T + 1) * (int64_t)k.items * k.desc->unit[s]; }
+
+// What the validators of one upload know beside the values
+struct CostCheck {
+  int64_t items = 0;                // per (instance, t)
+  bool ff = false;                  // free-flyer root: the first six tangent rows carry no limit
+  const int32_t* kind = nullptr;    // [items] obstacle slot kinds
+};
+typedef bool (*CostSideOk)(const CostCheck& c, const double* v, int64_t words);
+
+static inline bool cost_weight_ok(double w) { return isfinite(w) && w >= 0.0; }
+static inline bool cost_quat_ok(double norm2) { return isfinite(norm2) && fabs(sqrt(norm2) - 1.0) <= 1e-10; }
+
+static inline bool cost_finite_side(const CostCheck&, const double* v, int64_t words) {
+  for (int64_t i = 0; i < words; ++i)
+    if (!isfinite(v[i])) return false;
+  return true;
+}
+static inline bool cost_weight_side(const CostCheck&, const double* v, int64_t words) {
+  for (int64_t i = 0; i < words; ++i)
+    if (!cost_weight_ok(v[i])) return false;
+  return true;
+}
+// unit quaternions x y z w (a non-finite entry fails too)
+static inline bool cost_quat_side(const CostCheck&, const double* v, int64_t words) {
+  for (int64_t k = 0; k < words; k += 4)
+    if (!cost_quat_ok(v[k] * v[k] + v[k + 1] * v[k + 1] + v[k + 2] * v[k + 2] + v[k + 3] * v[k + 3])) return false;
+  return true;
+}
+// obstacle geometry by slot kind: a sphere's radius >= 0, a half-space's unit normal
+static inline bool cost_obstacle_geom_side(const CostCheck& c, const double* v, int64_t words) {
+  for (int64_t i = 0; i < words / 4; ++i) {
+    const double* g = v + 4 * i;
+    if (!isfinite(g[0]) || !isfinite(g[1]) || !isfinite(g[2]) || !isfinite(g[3])) return false;
+    if (c.kind[i % c.items] == DDP_HIP_OBSTACLE_SPHERE) {
+      if (g[3] < 0.0) return false;
+    } else if (fabs(sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) - 1.0) > 1e-10) {
+      return false;
+    }
+  }
+  return true;
+}
+// a limit's sides: no NaN, no lower bound of +inf, no upper bound of -inf
+static inline bool cost_limit_lo_side(const CostCheck&, const double* v, int64_t words) {
+  for (int64_t i = 0; i < words; ++i)
+    if (isnan(v[i]) || v[i] == INFINITY) return false;
+  return true;
+}
+static inline bool cost_limit_hi_side(const CostCheck&, const double* v, int64_t words) {
+  for (int64_t i = 0; i < words; ++i)
+    if (isnan(v[i]) || v[i] == -INFINITY) return false;
+  return true;
+}
+// ... and its weights: a free-flyer root's pose rows carry no limit
+static inline bool cost_limit_weight_side(const CostCheck& c, const double* v, int64_t words) {
+  for (int64_t i = 0; i < words; ++i) {
+    if (!cost_weight_ok(v[i])) return false;
+    if (c.ff && i % c.items < 6 && v[i] != 0.0) return false;
+  }
+  return true;
+}
+
+static inline bool cost_any_nonzero(const double* v, int64_t words) {
+  for (int64_t i = 0; i < words; ++i)
+    if (v[i] != 0.0) return true;
+  return false;
+}
+
+// flag off -> E_UNSUPPORTED, bad range -> E_ARG (uploads and downloads alike)
+static inline int cost_range_check(uint32_t ctx_flags, const CostBlock& k, int64_t batch, int64_t first, int64_t count) {
+  if (!(ctx_flags & k.desc->flag)) return DDP_HIP_E_UNSUPPORTED;
+  if (first < 0 || count < 0 || first + count > batch) return DDP_HIP_E_ARG;
+  return DDP_HIP_OK;
+}
+
+// Everything an upload decides before it touches the device, in this order: flag, range, layout, every side of the whole range
+// (nothing is written unless all of it is valid).  *copy: there is something to write; *nonzero: the weights carry a non-zero
+static inline int cost_upload_check(uint32_t ctx_flags, const CostBlock& k, const CostCheck& c, int64_t batch, int64_t T,
+                                    const double* const* host, const CostSideOk* ok, int64_t first, int64_t count, bool* copy,
+                                    bool* nonzero) {
+  *copy = *nonzero = false;
+  const int rc = cost_range_check(ctx_flags, k, batch, first, count);
+  if (rc != DDP_HIP_OK) return rc;
+  if (k.items == 0) return DDP_HIP_E_ARG;                             // no frames / points set: the arrays have no shape yet
+  bool any = false;
+  for (int s = 0; s < k.desc->nside; ++s) {
+    if (!host[s]) continue;
+    any = true;
+    if (!ok[s](c, host[s], cost_side_words(k, s, T) * count)) return DDP_HIP_E_ARG;
+  }
+  *copy = count != 0 && any;
+  const int w = k.desc->nside - 1;
+  *nonzero = host[w] && cost_any_nonzero(host[w], cost_side_words(k, w, T) * count);
+  return DDP_HIP_OK;
+}
+
+// The live rule: an upload of weights with a non-zero entry switches the term's kernels on; only ONE upload of zeros for the
+// whole batch (first 0, count batch) switches them off again.  Zeros arriving range by range leave the kernels launched, with
+// the same bits: they skip zero weights themselves
+static inline bool cost_live_rule(bool live, bool nonzero, int64_t first, int64_t count, int64_t batch) {
+  return nonzero || (live && !(first == 0 && count == batch));
+}

@@ -239,33 +239,27 @@ static DevSwitches read_switches() {
   return sw;
 }
 
-// the orientation data as it is at create: every quaternion (0, 0, 0, 1), every weight 0, the terms off
-static int frame_orient_reset(ddp_hip_ctx* ctx) {
-  const int64_t slots = ctx->d.batch * (ctx->d.T + 1) * DDP_HIP_MAX_COST_FRAMES;
-  std::vector<double> qt((size_t)(slots * 4), 0.0);
-  for (size_t k = 3; k < qt.size(); k += 4) qt[k] = 1.0;
-  HIP_TRY(hipMemcpyAsync(ctx->fo_quat_d, qt.data(), sizeof(double) * qt.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(hipMemsetAsync(ctx->fo_weight_d, 0, sizeof(double) * (size_t)(slots * 3), ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  ctx->fo_live = false;
-  return DDP_HIP_OK;
-}
-
-// the frame-velocity data as it is at create: every target and every weight 0, the terms off
-static int frame_vel_reset(ddp_hip_ctx* ctx) {
-  const size_t words = (size_t)(ctx->d.batch * (ctx->d.T + 1) * DDP_HIP_MAX_COST_FRAMES * 6);
-  HIP_TRY(hipMemsetAsync(ctx->fv_target_d, 0, sizeof(double) * words, ctx->stream));
-  HIP_TRY(hipMemsetAsync(ctx->fv_weight_d, 0, sizeof(double) * words, ctx->stream));
-  ctx->fv_live = false;
-  return DDP_HIP_OK;
-}
-
-// the obstacle data as it is at create: every geom and every weight 0, the terms off
-static int obstacle_reset(ddp_hip_ctx* ctx) {
-  const size_t slots = (size_t)(ctx->d.batch * (ctx->d.T + 1) * DDP_HIP_MAX_OBSTACLES);
-  HIP_TRY(hipMemsetAsync(ctx->ob_geom_d, 0, sizeof(double) * slots * 4, ctx->stream));
-  HIP_TRY(hipMemsetAsync(ctx->ob_weight_d, 0, sizeof(double) * slots, ctx->stream));
-  ctx->ob_live = false;
+// A term's arrays as they are at create: allocated (once) for max_items, every side at its fill value over that whole capacity,
+// the term off, laid out by `items`.  ddp_hip_create, and the set_frames / set_points entry points when the layout changes
+static int cost_block_setup(ddp_hip_ctx* ctx, int term, int32_t items) {
+  CostBlock& k = ctx->cost[term];
+  const int64_t slots = ctx->d.batch * (ctx->d.T + 1) * k.max_items;
+  for (int s = 0; s < k.desc->nside; ++s) {
+    const int64_t words = slots * k.desc->unit[s];
+    const int fill = k.desc->fill[s];
+    if (!k.side[s]) HIP_TRY(hipMalloc(&k.side[s], sizeof(double) * (size_t)words));
+    if (fill == FILL_QUAT) {   // (a zero-filled quaternion has no rotation)
+      std::vector<double> qt((size_t)words, 0.0);
+      for (size_t i = 3; i < qt.size(); i += 4) qt[i] = 1.0;
+      HIP_TRY(hipMemcpyAsync(k.side[s], qt.data(), sizeof(double) * qt.size(), hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(hipStreamSynchronize(ctx->stream));
+    } else {
+      const int rc = fill_device(ctx, k.side[s], words, fill == FILL_NEG_INF ? -INFINITY : fill == FILL_POS_INF ? INFINITY : 0.0);
+      if (rc != DDP_HIP_OK) return rc;
+    }
+  }
+  k.items = items;
+  k.live = false;
   return DDP_HIP_OK;
 }
 
@@ -388,51 +382,16 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipMemcpyAsync(ctx->seq[DDP_HIP_SEQ_COST_XREF].ptr, xr.data(), sizeof(double) * xr.size(), hipMemcpyHostToDevice, ctx->stream));
     CTX_TRY(hipStreamSynchronize(ctx->stream));
   }
-  if (flags & DDP_HIP_FLAG_FRAME_COST) {
-    // no frames yet; targets and weights start at 0
-    const size_t words = (size_t)(d.batch * (d.T + 1) * DDP_HIP_MAX_COST_FRAMES * 3);
-    CTX_TRY(hipMalloc(&ctx->fc_target_d, sizeof(double) * words));
-    CTX_TRY(hipMalloc(&ctx->fc_weight_d, sizeof(double) * words));
-    CTX_TRY(hipMemsetAsync(ctx->fc_target_d, 0, sizeof(double) * words, ctx->stream));
-    CTX_TRY(hipMemsetAsync(ctx->fc_weight_d, 0, sizeof(double) * words, ctx->stream));
+  for (int term = 0; term < COST_COUNT; ++term) {
+    // frames and obstacle slots: no layout until they are set; limits (lo = -inf, hi = +inf, w = 0: no limit anywhere) and CoM: fixed
+    CostBlock& k = ctx->cost[term];
+    k.desc = &kCostDesc[term];
+    k.max_items = k.desc->max_items ? k.desc->max_items : (int32_t)d.n;
+    if (!(flags & k.desc->flag)) continue;
+    const int rc_ = cost_block_setup(ctx, term, k.desc->fixed ? k.max_items : 0);
+    if (rc_ != DDP_HIP_OK) { ddp_hip_destroy(ctx); return rc_; }
   }
-  if (flags & DDP_HIP_FLAG_FRAME_ORIENT_COST) {
-    // identity quaternions (a zero-filled one has no rotation) and weights 0
-    const int64_t slots = d.batch * (d.T + 1) * DDP_HIP_MAX_COST_FRAMES;
-    CTX_TRY(hipMalloc(&ctx->fo_quat_d, sizeof(double) * (size_t)(slots * 4)));
-    CTX_TRY(hipMalloc(&ctx->fo_weight_d, sizeof(double) * (size_t)(slots * 3)));
-    if (frame_orient_reset(ctx) != DDP_HIP_OK) { ddp_hip_destroy(ctx); return DDP_HIP_E_HIP; }
-  }
-  if (flags & DDP_HIP_FLAG_FRAME_VEL_COST) {
-    const size_t words = (size_t)(d.batch * (d.T + 1) * DDP_HIP_MAX_COST_FRAMES * 6);
-    CTX_TRY(hipMalloc(&ctx->fv_target_d, sizeof(double) * words));
-    CTX_TRY(hipMalloc(&ctx->fv_weight_d, sizeof(double) * words));
-    if (frame_vel_reset(ctx) != DDP_HIP_OK) { ddp_hip_destroy(ctx); return DDP_HIP_E_HIP; }
-  }
-  if (flags & DDP_HIP_FLAG_OBSTACLE_COST) {
-    const size_t slots = (size_t)(d.batch * (d.T + 1) * DDP_HIP_MAX_OBSTACLES);
-    CTX_TRY(hipMalloc(&ctx->ob_geom_d, sizeof(double) * slots * 4));
-    CTX_TRY(hipMalloc(&ctx->ob_weight_d, sizeof(double) * slots));
-    CTX_TRY(hipMalloc(&ctx->ob_clear_d, sizeof(double) * (size_t)(d.batch * (d.T + 1))));
-    if (obstacle_reset(ctx) != DDP_HIP_OK) { ddp_hip_destroy(ctx); return DDP_HIP_E_HIP; }
-  }
-  if (flags & DDP_HIP_FLAG_COM_COST) {
-    const size_t words = (size_t)(d.batch * (d.T + 1) * 3);
-    CTX_TRY(hipMalloc(&ctx->cm_target_d, sizeof(double) * words));
-    CTX_TRY(hipMalloc(&ctx->cm_weight_d, sizeof(double) * words));
-    CTX_TRY(hipMemsetAsync(ctx->cm_target_d, 0, sizeof(double) * words, ctx->stream));
-    CTX_TRY(hipMemsetAsync(ctx->cm_weight_d, 0, sizeof(double) * words, ctx->stream));
-  }
-  if (flags & DDP_HIP_FLAG_STATE_LIMITS) {
-    // lo = -inf, hi = +inf, w = 0: no limit anywhere
-    const int64_t words = d.batch * (d.T + 1) * d.n;
-    CTX_TRY(hipMalloc(&ctx->sl_d, sizeof(double) * (size_t)(3 * words)));
-    if (fill_device(ctx, ctx->sl_d, words, -INFINITY) != DDP_HIP_OK || fill_device(ctx, ctx->sl_d + words, words, INFINITY) != DDP_HIP_OK ||
-        fill_device(ctx, ctx->sl_d + 2 * words, words, 0.0) != DDP_HIP_OK) {
-      ddp_hip_destroy(ctx);
-      return DDP_HIP_E_HIP;
-    }
-  }
+  if (flags & DDP_HIP_FLAG_OBSTACLE_COST) CTX_TRY(hipMalloc(&ctx->ob_clear_d, sizeof(double) * (size_t)(d.batch * (d.T + 1))));
   int rc = bwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = fwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = lin_setup(ctx);
@@ -452,18 +411,12 @@ extern "C" int ddp_hip_destroy(ddp_hip_ctx* ctx) {
   bwd_teardown(ctx);
   for (int s = 0; s < DDP_HIP_SEQ_COUNT; ++s)
     if (ctx->seq[s].ptr) (void)hipFree(ctx->seq[s].ptr);
-  if (ctx->fc_target_d) (void)hipFree(ctx->fc_target_d);
-  if (ctx->fc_weight_d) (void)hipFree(ctx->fc_weight_d);
-  if (ctx->fo_quat_d) (void)hipFree(ctx->fo_quat_d);
-  if (ctx->fo_weight_d) (void)hipFree(ctx->fo_weight_d);
-  if (ctx->fv_target_d) (void)hipFree(ctx->fv_target_d);
-  if (ctx->fv_weight_d) (void)hipFree(ctx->fv_weight_d);
-  if (ctx->ob_geom_d) (void)hipFree(ctx->ob_geom_d);
-  if (ctx->ob_weight_d) (void)hipFree(ctx->ob_weight_d);
+  for (CostBlock& k : ctx->cost) {
+    for (double* p : k.side)
+      if (p) (void)hipFree(p);
+    if (k.cand) (void)hipFree(k.cand);
+  }
   if (ctx->ob_clear_d) (void)hipFree(ctx->ob_clear_d);
-  if (ctx->cm_target_d) (void)hipFree(ctx->cm_target_d);
-  if (ctx->cm_weight_d) (void)hipFree(ctx->cm_weight_d);
-  if (ctx->sl_d) (void)hipFree(ctx->sl_d);
   if (ctx->ne_d) (void)hipFree(ctx->ne_d);
   if (ctx->Epre_d) (void)hipFree(ctx->Epre_d);
   if (ctx->target_d) (void)hipFree(ctx->target_d);
@@ -507,8 +460,7 @@ static int check_range(ddp_hip_ctx* ctx, int seq, int64_t first, int64_t count) 
 }
 
 // what the tracking cost accepts (DDP_HIP_FLAG_TRACKING_COST): finite, non-negative weights; unit root quaternions
-static bool cost_weight_ok(double w) { return isfinite(w) && w >= 0.0; }
-static bool cost_quat_ok(double norm2) { return isfinite(norm2) && fabs(sqrt(norm2) - 1.0) <= 1e-10; }
+// (cost_weight_ok, cost_quat_ok: cost_block.h)
 
 // what a control bound accepts (DDP_HIP_FLAG_CONTROL_BOUNDS): no NaN, no lower bound of +inf, no upper bound of -inf
 static bool bound_ok(int seq, double v) { return !isnan(v) && !(seq == DDP_HIP_SEQ_CTRL_LO ? v == INFINITY : v == -INFINITY); }
@@ -587,7 +539,51 @@ extern "C" int ddp_hip_fill(ddp_hip_ctx* ctx, int seq, double value) {
   return fill_device(ctx, ctx->seq[seq].ptr, ctx->seq[seq].size * ctx->d.batch, value);
 }
 
-// ---- frame-position cost (DDP_HIP_FLAG_FRAME_COST): frames shared by the batch, targets and weights per instance ----------
+// ---- the add-on cost terms (cost_block.h): one upload path, one download path ------------------------------
+// host[s] == nullptr leaves side s as it is.  The order of the checks is part of the interface: null context, flag, range, layout,
+// every side of the whole range (cost_upload_check), and only then the device: `before_copy` (state limits), the candidates'
+// array at the first non-zero weight, the copies, one synchronise, the live rule
+static int cost_block_upload(ddp_hip_ctx* ctx, int term, const double* const* host, const CostSideOk* ok, int64_t first, int64_t count,
+                             int (*before_copy)(ddp_hip_ctx*, const double* const*, int64_t, int64_t) = nullptr) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  CostBlock& k = ctx->cost[term];
+  const Dims& d = ctx->d;
+  CostCheck c;
+  c.items = k.items; c.ff = ctx->model_h.ff != 0; c.kind = ctx->ob_kind;
+  bool copy, nonzero;
+  const int rc = cost_upload_check(ctx->flags, k, c, d.batch, d.T, host, ok, first, count, &copy, &nonzero);
+  if (rc != DDP_HIP_OK || !copy) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (before_copy) { const int rc_ = before_copy(ctx, host, first, count); if (rc_ != DDP_HIP_OK) return rc_; }
+  // the candidates' term array of the line search exists from the first non-zero weight on (fwd.hip: addon_terms)
+  if (nonzero && k.desc->cand && !k.cand) HIP_TRY(hipMalloc(&k.cand, sizeof(double) * (size_t)(d.batch * ctx->n_alpha_max * (d.T + 1))));
+  for (int s = 0; s < k.desc->nside; ++s) {
+    const int64_t sz = cost_side_words(k, s, d.T);
+    if (host[s]) HIP_TRY(hipMemcpyAsync(k.side[s] + first * sz, host[s], sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (host[k.desc->nside - 1]) k.live = cost_live_rule(k.live, nonzero, first, count, d.batch);
+  return DDP_HIP_OK;
+}
+
+static int cost_block_download(ddp_hip_ctx* ctx, int term, double* const* host, int64_t first, int64_t count) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  const CostBlock& k = ctx->cost[term];
+  const int rc = cost_range_check(ctx->flags, k, ctx->d.batch, first, count);
+  if (rc != DDP_HIP_OK) return rc;
+  bool any = false;
+  for (int s = 0; s < k.desc->nside; ++s) any |= host[s] != nullptr;
+  if (k.items == 0 || count == 0 || !any) return DDP_HIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  for (int s = 0; s < k.desc->nside; ++s) {
+    const int64_t sz = cost_side_words(k, s, ctx->d.T);
+    if (host[s]) HIP_TRY(hipMemcpyAsync(host[s], k.side[s] + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return DDP_HIP_OK;
+}
+
+// frames shared by the batch: of the position, orientation and velocity terms
 extern "C" int ddp_hip_frame_cost_set_frames(ddp_hip_ctx* ctx, int32_t n_frames, const int32_t* joint, const double* off) {
   if (!ctx) return DDP_HIP_E_ARG;
   if (!(ctx->flags & DDP_HIP_FLAG_FRAME_COST)) return DDP_HIP_E_UNSUPPORTED;
@@ -598,14 +594,10 @@ extern "C" int ddp_hip_frame_cost_set_frames(ddp_hip_ctx* ctx, int32_t n_frames,
       if (!isfinite(off[3 * f + a])) return DDP_HIP_E_ARG;
   }
   if (n_frames != ctx->fc_nf) {
-    // another count is another layout: targets and weights start again at 0
+    // another count is another layout: the three terms' data start again as at create
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t words = (size_t)(ctx->d.batch * (ctx->d.T + 1) * DDP_HIP_MAX_COST_FRAMES * 3);
-    HIP_TRY(hipMemsetAsync(ctx->fc_target_d, 0, sizeof(double) * words, ctx->stream));
-    HIP_TRY(hipMemsetAsync(ctx->fc_weight_d, 0, sizeof(double) * words, ctx->stream));
-    ctx->fc_live = false;
-    if (ctx->flags & DDP_HIP_FLAG_FRAME_ORIENT_COST) { const int rc_ = frame_orient_reset(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
-    if (ctx->flags & DDP_HIP_FLAG_FRAME_VEL_COST) { const int rc_ = frame_vel_reset(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
+    for (int term : {COST_FRAME, COST_ORIENT, COST_FRAME_VEL})
+      if (ctx->flags & kCostDesc[term].flag) { const int rc_ = cost_block_setup(ctx, term, n_frames); if (rc_ != DDP_HIP_OK) return rc_; }
   }
   ctx->fc_nf = n_frames;
   for (int f = 0; f < n_frames; ++f) {
@@ -615,145 +607,37 @@ extern "C" int ddp_hip_frame_cost_set_frames(ddp_hip_ctx* ctx, int32_t n_frames,
   return DDP_HIP_OK;
 }
 
-static int frame_cost_range(ddp_hip_ctx* ctx, int64_t first, int64_t count) {
-  if (!ctx) return DDP_HIP_E_ARG;
-  if (!(ctx->flags & DDP_HIP_FLAG_FRAME_COST)) return DDP_HIP_E_UNSUPPORTED;
-  if (first < 0 || count < 0 || first + count > ctx->d.batch) return DDP_HIP_E_ARG;
-  return DDP_HIP_OK;
-}
-
 extern "C" int ddp_hip_frame_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first, int64_t count) {
-  int rc = frame_cost_range(ctx, first, count);
-  if (rc != DDP_HIP_OK) return rc;
-  if (ctx->fc_nf == 0) return DDP_HIP_E_ARG;                // no frames set: the arrays have no shape yet
-  const int64_t sz = (ctx->d.T + 1) * ctx->fc_nf * 3;
-  bool nonzero = false;
-  if (target)
-    for (int64_t i = 0; i < sz * count; ++i)
-      if (!isfinite(target[i])) return DDP_HIP_E_ARG;
-  if (weight)
-    for (int64_t i = 0; i < sz * count; ++i) {
-      if (!cost_weight_ok(weight[i])) return DDP_HIP_E_ARG;
-      nonzero |= weight[i] != 0.0;
-    }
-  if (count == 0 || (!target && !weight)) return DDP_HIP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  if (target) HIP_TRY(hipMemcpyAsync(ctx->fc_target_d + first * sz, target, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
-  if (weight) HIP_TRY(hipMemcpyAsync(ctx->fc_weight_d + first * sz, weight, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  // any non-zero weight switches the terms on; only ONE upload of zeros for the whole batch (first 0, count batch) switches
-  // them off again -- zeros arriving range by range leave the frame kernels running (same bits: they skip zero weights themselves)
-  if (weight) ctx->fc_live = nonzero || (ctx->fc_live && !(first == 0 && count == ctx->d.batch));
-  return DDP_HIP_OK;
+  const double* host[] = {target, weight};
+  const CostSideOk ok[] = {cost_finite_side, cost_weight_side};
+  return cost_block_upload(ctx, COST_FRAME, host, ok, first, count);
 }
-
 extern "C" int ddp_hip_frame_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first, int64_t count) {
-  int rc = frame_cost_range(ctx, first, count);
-  if (rc != DDP_HIP_OK) return rc;
-  const int64_t sz = (ctx->d.T + 1) * ctx->fc_nf * 3;
-  if (sz == 0 || count == 0 || (!target && !weight)) return DDP_HIP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  if (target) HIP_TRY(hipMemcpyAsync(target, ctx->fc_target_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
-  if (weight) HIP_TRY(hipMemcpyAsync(weight, ctx->fc_weight_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  return DDP_HIP_OK;
-}
-
-// ---- frame-orientation cost (DDP_HIP_FLAG_FRAME_ORIENT_COST): reference rotations and weights of the cost frames ----------
-static int frame_orient_range(ddp_hip_ctx* ctx, int64_t first, int64_t count) {
-  if (!ctx) return DDP_HIP_E_ARG;
-  if (!(ctx->flags & DDP_HIP_FLAG_FRAME_ORIENT_COST)) return DDP_HIP_E_UNSUPPORTED;
-  if (first < 0 || count < 0 || first + count > ctx->d.batch) return DDP_HIP_E_ARG;
-  return DDP_HIP_OK;
+  double* host[] = {target, weight};
+  return cost_block_download(ctx, COST_FRAME, host, first, count);
 }
 
 extern "C" int ddp_hip_frame_orient_upload(ddp_hip_ctx* ctx, const double* quat, const double* weight, int64_t first, int64_t count) {
-  int rc = frame_orient_range(ctx, first, count);
-  if (rc != DDP_HIP_OK) return rc;
-  if (ctx->fc_nf == 0) return DDP_HIP_E_ARG;                // no frames set: the arrays have no shape yet
-  const int64_t slots = (ctx->d.T + 1) * ctx->fc_nf;
-  bool nonzero = false;
-  if (quat)
-    for (int64_t k = 0; k < slots * count; ++k) {
-      const double* qt = quat + 4 * k;
-      if (!cost_quat_ok(qt[0] * qt[0] + qt[1] * qt[1] + qt[2] * qt[2] + qt[3] * qt[3])) return DDP_HIP_E_ARG;   // (a non-finite entry fails it too)
-    }
-  if (weight)
-    for (int64_t i = 0; i < slots * 3 * count; ++i) {
-      if (!cost_weight_ok(weight[i])) return DDP_HIP_E_ARG;
-      nonzero |= weight[i] != 0.0;
-    }
-  if (count == 0 || (!quat && !weight)) return DDP_HIP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  if (quat) HIP_TRY(hipMemcpyAsync(ctx->fo_quat_d + first * slots * 4, quat, sizeof(double) * (size_t)(slots * 4 * count), hipMemcpyHostToDevice, ctx->stream));
-  if (weight) HIP_TRY(hipMemcpyAsync(ctx->fo_weight_d + first * slots * 3, weight, sizeof(double) * (size_t)(slots * 3 * count), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  // as fc_live: any non-zero weight switches the terms on, only ONE upload of zeros for the whole batch switches them off again
-  if (weight) ctx->fo_live = nonzero || (ctx->fo_live && !(first == 0 && count == ctx->d.batch));
-  return DDP_HIP_OK;
+  const double* host[] = {quat, weight};
+  const CostSideOk ok[] = {cost_quat_side, cost_weight_side};
+  return cost_block_upload(ctx, COST_ORIENT, host, ok, first, count);
 }
-
 extern "C" int ddp_hip_frame_orient_download(ddp_hip_ctx* ctx, double* quat, double* weight, int64_t first, int64_t count) {
-  int rc = frame_orient_range(ctx, first, count);
-  if (rc != DDP_HIP_OK) return rc;
-  const int64_t slots = (ctx->d.T + 1) * ctx->fc_nf;
-  if (slots == 0 || count == 0 || (!quat && !weight)) return DDP_HIP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  if (quat) HIP_TRY(hipMemcpyAsync(quat, ctx->fo_quat_d + first * slots * 4, sizeof(double) * (size_t)(slots * 4 * count), hipMemcpyDeviceToHost, ctx->stream));
-  if (weight) HIP_TRY(hipMemcpyAsync(weight, ctx->fo_weight_d + first * slots * 3, sizeof(double) * (size_t)(slots * 3 * count), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  return DDP_HIP_OK;
-}
-
-// ---- frame-velocity cost (DDP_HIP_FLAG_FRAME_VEL_COST): velocity targets and weights of the cost frames -------------------------
-static int frame_vel_range(ddp_hip_ctx* ctx, int64_t first, int64_t count) {
-  if (!ctx) return DDP_HIP_E_ARG;
-  if (!(ctx->flags & DDP_HIP_FLAG_FRAME_VEL_COST)) return DDP_HIP_E_UNSUPPORTED;
-  if (first < 0 || count < 0 || first + count > ctx->d.batch) return DDP_HIP_E_ARG;
-  return DDP_HIP_OK;
+  double* host[] = {quat, weight};
+  return cost_block_download(ctx, COST_ORIENT, host, first, count);
 }
 
 extern "C" int ddp_hip_frame_vel_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first, int64_t count) {
-  int rc = frame_vel_range(ctx, first, count);
-  if (rc != DDP_HIP_OK) return rc;
-  if (ctx->fc_nf == 0) return DDP_HIP_E_ARG;                // no frames set: the arrays have no shape yet
-  const int64_t sz = (ctx->d.T + 1) * ctx->fc_nf * 6;
-  bool nonzero = false;
-  if (target)
-    for (int64_t i = 0; i < sz * count; ++i)
-      if (!isfinite(target[i])) return DDP_HIP_E_ARG;
-  if (weight)
-    for (int64_t i = 0; i < sz * count; ++i) {
-      if (!cost_weight_ok(weight[i])) return DDP_HIP_E_ARG;
-      nonzero |= weight[i] != 0.0;
-    }
-  if (count == 0 || (!target && !weight)) return DDP_HIP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  // the candidates' term array of the line search exists from the first non-zero weight on (fwd.hip: frame_vel_cost_kernel)
-  if (nonzero && !ctx->fv_new) HIP_TRY(hipMalloc(&ctx->fv_new, sizeof(double) * (size_t)(ctx->d.batch * ctx->n_alpha_max * (ctx->d.T + 1))));
-  if (target) HIP_TRY(hipMemcpyAsync(ctx->fv_target_d + first * sz, target, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
-  if (weight) HIP_TRY(hipMemcpyAsync(ctx->fv_weight_d + first * sz, weight, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  // exactly cm_live's rule: any non-zero weight switches the kernels on, only ONE upload of zeros for the whole batch switches
-  // them off again
-  if (weight) ctx->fv_live = nonzero || (ctx->fv_live && !(first == 0 && count == ctx->d.batch));
-  return DDP_HIP_OK;
+  const double* host[] = {target, weight};
+  const CostSideOk ok[] = {cost_finite_side, cost_weight_side};
+  return cost_block_upload(ctx, COST_FRAME_VEL, host, ok, first, count);
 }
-
 extern "C" int ddp_hip_frame_vel_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first, int64_t count) {
-  int rc = frame_vel_range(ctx, first, count);
-  if (rc != DDP_HIP_OK) return rc;
-  const int64_t sz = (ctx->d.T + 1) * ctx->fc_nf * 6;
-  if (sz == 0 || count == 0 || (!target && !weight)) return DDP_HIP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  if (target) HIP_TRY(hipMemcpyAsync(target, ctx->fv_target_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
-  if (weight) HIP_TRY(hipMemcpyAsync(weight, ctx->fv_weight_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  return DDP_HIP_OK;
+  double* host[] = {target, weight};
+  return cost_block_download(ctx, COST_FRAME_VEL, host, first, count);
 }
 
-// ---- obstacle cost (DDP_HIP_FLAG_OBSTACLE_COST): collision points and slot kinds shared by the batch, geometry and weights per
-// (instance, t, slot) ------------------------------------------------------------------------------------------------------------
+// collision points and slot kinds shared by the batch; geometry and weights per (instance, t, slot)
 extern "C" int ddp_hip_obstacle_set_points(ddp_hip_ctx* ctx, int32_t n_points, const int32_t* joint, const double* off, const double* radius,
                                            int32_t n_obstacles, const int32_t* kind) {
   if (!ctx) return DDP_HIP_E_ARG;
@@ -773,7 +657,7 @@ extern "C" int ddp_hip_obstacle_set_points(ddp_hip_ctx* ctx, int32_t n_points, c
   if (!same) {
     // other counts are another layout, other kinds another meaning of the four doubles: geometry and weights start again at 0
     HIP_TRY(hipSetDevice(ctx->device));
-    const int rc_ = obstacle_reset(ctx);
+    const int rc_ = cost_block_setup(ctx, COST_OBSTACLE, n_obstacles);
     if (rc_ != DDP_HIP_OK) return rc_;
   }
   ctx->ob_np = n_points;
@@ -787,169 +671,54 @@ extern "C" int ddp_hip_obstacle_set_points(ddp_hip_ctx* ctx, int32_t n_points, c
   return DDP_HIP_OK;
 }
 
-static int obstacle_range(ddp_hip_ctx* ctx, int64_t first, int64_t count) {
-  if (!ctx) return DDP_HIP_E_ARG;
-  if (!(ctx->flags & DDP_HIP_FLAG_OBSTACLE_COST)) return DDP_HIP_E_UNSUPPORTED;
-  if (first < 0 || count < 0 || first + count > ctx->d.batch) return DDP_HIP_E_ARG;
-  return DDP_HIP_OK;
-}
-
 extern "C" int ddp_hip_obstacle_upload(ddp_hip_ctx* ctx, const double* geom, const double* weight, int64_t first, int64_t count) {
-  int rc = obstacle_range(ctx, first, count);
-  if (rc != DDP_HIP_OK) return rc;
-  if (ctx->ob_np == 0) return DDP_HIP_E_ARG;                // no points set: the arrays have no shape yet
-  const int64_t no = ctx->ob_no, sz = (ctx->d.T + 1) * no;
-  bool nonzero = false;
-  if (geom)
-    for (int64_t i = 0; i < sz * count; ++i) {
-      const double* g = geom + 4 * i;
-      if (!isfinite(g[0]) || !isfinite(g[1]) || !isfinite(g[2]) || !isfinite(g[3])) return DDP_HIP_E_ARG;
-      if (ctx->ob_kind[i % no] == DDP_HIP_OBSTACLE_SPHERE) {
-        if (g[3] < 0.0) return DDP_HIP_E_ARG;               // a sphere's radius
-      } else if (fabs(sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) - 1.0) > 1e-10) {
-        return DDP_HIP_E_ARG;                               // a half-space's unit normal
-      }
-    }
-  if (weight)
-    for (int64_t i = 0; i < sz * count; ++i) {
-      if (!cost_weight_ok(weight[i])) return DDP_HIP_E_ARG;
-      nonzero |= weight[i] != 0.0;
-    }
-  if (count == 0 || (!geom && !weight)) return DDP_HIP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  // the candidates' term array of the line search exists from the first non-zero weight on (fwd.hip: obstacle_cost_kernel)
-  if (nonzero && !ctx->ob_new) HIP_TRY(hipMalloc(&ctx->ob_new, sizeof(double) * (size_t)(ctx->d.batch * ctx->n_alpha_max * (ctx->d.T + 1))));
-  if (geom) HIP_TRY(hipMemcpyAsync(ctx->ob_geom_d + first * sz * 4, geom, sizeof(double) * (size_t)(sz * count * 4), hipMemcpyHostToDevice, ctx->stream));
-  if (weight) HIP_TRY(hipMemcpyAsync(ctx->ob_weight_d + first * sz, weight, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  // exactly cm_live's rule: any non-zero weight switches the kernels on, only ONE upload of zeros for the whole batch switches
-  // them off again
-  if (weight) ctx->ob_live = nonzero || (ctx->ob_live && !(first == 0 && count == ctx->d.batch));
-  return DDP_HIP_OK;
+  const double* host[] = {geom, weight};
+  const CostSideOk ok[] = {cost_obstacle_geom_side, cost_weight_side};
+  return cost_block_upload(ctx, COST_OBSTACLE, host, ok, first, count);
 }
-
 extern "C" int ddp_hip_obstacle_download(ddp_hip_ctx* ctx, double* geom, double* weight, int64_t first, int64_t count) {
-  int rc = obstacle_range(ctx, first, count);
-  if (rc != DDP_HIP_OK) return rc;
-  const int64_t sz = (ctx->d.T + 1) * ctx->ob_no;
-  if (sz == 0 || count == 0 || (!geom && !weight)) return DDP_HIP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  if (geom) HIP_TRY(hipMemcpyAsync(geom, ctx->ob_geom_d + first * sz * 4, sizeof(double) * (size_t)(sz * count * 4), hipMemcpyDeviceToHost, ctx->stream));
-  if (weight) HIP_TRY(hipMemcpyAsync(weight, ctx->ob_weight_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  return DDP_HIP_OK;
-}
-
-// ---- centre-of-mass cost (DDP_HIP_FLAG_COM_COST): target and weights per (instance, t) -----------------------------------
-static int com_cost_range(ddp_hip_ctx* ctx, int64_t first, int64_t count) {
-  if (!ctx) return DDP_HIP_E_ARG;
-  if (!(ctx->flags & DDP_HIP_FLAG_COM_COST)) return DDP_HIP_E_UNSUPPORTED;
-  if (first < 0 || count < 0 || first + count > ctx->d.batch) return DDP_HIP_E_ARG;
-  return DDP_HIP_OK;
+  double* host[] = {geom, weight};
+  return cost_block_download(ctx, COST_OBSTACLE, host, first, count);
 }
 
 extern "C" int ddp_hip_com_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first, int64_t count) {
-  int rc = com_cost_range(ctx, first, count);
-  if (rc != DDP_HIP_OK) return rc;
-  const int64_t sz = (ctx->d.T + 1) * 3;
-  bool nonzero = false;
-  if (target)
-    for (int64_t i = 0; i < sz * count; ++i)
-      if (!isfinite(target[i])) return DDP_HIP_E_ARG;
-  if (weight)
-    for (int64_t i = 0; i < sz * count; ++i) {
-      if (!cost_weight_ok(weight[i])) return DDP_HIP_E_ARG;
-      nonzero |= weight[i] != 0.0;
-    }
-  if (count == 0 || (!target && !weight)) return DDP_HIP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  // the candidates' term array of the line search exists from the first non-zero weight on (fwd.hip: com_cost_kernel)
-  if (nonzero && !ctx->cm_new) HIP_TRY(hipMalloc(&ctx->cm_new, sizeof(double) * (size_t)(ctx->d.batch * ctx->n_alpha_max * (ctx->d.T + 1))));
-  if (target) HIP_TRY(hipMemcpyAsync(ctx->cm_target_d + first * sz, target, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
-  if (weight) HIP_TRY(hipMemcpyAsync(ctx->cm_weight_d + first * sz, weight, sizeof(double) * (size_t)(sz * count), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  // exactly fc_live's rule: any non-zero weight switches the kernels on, only ONE upload of zeros for the whole batch switches
-  // them off again
-  if (weight) ctx->cm_live = nonzero || (ctx->cm_live && !(first == 0 && count == ctx->d.batch));
-  return DDP_HIP_OK;
+  const double* host[] = {target, weight};
+  const CostSideOk ok[] = {cost_finite_side, cost_weight_side};
+  return cost_block_upload(ctx, COST_COM, host, ok, first, count);
 }
-
 extern "C" int ddp_hip_com_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first, int64_t count) {
-  int rc = com_cost_range(ctx, first, count);
-  if (rc != DDP_HIP_OK) return rc;
-  const int64_t sz = (ctx->d.T + 1) * 3;
-  if (count == 0 || (!target && !weight)) return DDP_HIP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  if (target) HIP_TRY(hipMemcpyAsync(target, ctx->cm_target_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
-  if (weight) HIP_TRY(hipMemcpyAsync(weight, ctx->cm_weight_d + first * sz, sizeof(double) * (size_t)(sz * count), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  return DDP_HIP_OK;
+  double* host[] = {target, weight};
+  return cost_block_download(ctx, COST_COM, host, first, count);
 }
 
-// ---- soft state limits (DDP_HIP_FLAG_STATE_LIMITS): lo, hi, weight per (instance, t, tangent row) --------------------------
-static int state_limits_range(ddp_hip_ctx* ctx, int64_t first, int64_t count) {
-  if (!ctx) return DDP_HIP_E_ARG;
-  if (!(ctx->flags & DDP_HIP_FLAG_STATE_LIMITS)) return DDP_HIP_E_UNSUPPORTED;
-  if (first < 0 || count < 0 || first + count > ctx->d.batch) return DDP_HIP_E_ARG;
+// state limits: lo <= hi, before anything is written: a side that arrives alone is held against the resident other side (read
+// back: uploads are not a hot path)
+static int limits_lo_le_hi(ddp_hip_ctx* ctx, const double* const* host, int64_t first, int64_t count) {
+  const double *l = host[0], *h = host[1];
+  if (!l && !h) return DDP_HIP_OK;
+  const CostBlock& k = ctx->cost[COST_LIMITS];
+  const int64_t sz = cost_side_words(k, 0, ctx->d.T), words = sz * count;
+  std::vector<double> other;
+  if (!l || !h) {
+    other.resize((size_t)words);
+    HIP_TRY(hipMemcpyAsync(other.data(), k.side[l ? 1 : 0] + first * sz, sizeof(double) * (size_t)words, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    (l ? h : l) = other.data();
+  }
+  for (int64_t i = 0; i < words; ++i)
+    if (l[i] > h[i]) return DDP_HIP_E_ARG;
   return DDP_HIP_OK;
 }
 
 extern "C" int ddp_hip_state_limits_upload(ddp_hip_ctx* ctx, const double* lo, const double* hi, const double* weight, int64_t first,
                                            int64_t count) {
-  int rc = state_limits_range(ctx, first, count);
-  if (rc != DDP_HIP_OK) return rc;
-  const int64_t n = ctx->d.n, sz = (ctx->d.T + 1) * n, words = sz * count, all = sz * ctx->d.batch;
-  bool nonzero = false;
-  if (lo)
-    for (int64_t i = 0; i < words; ++i)
-      if (isnan(lo[i]) || lo[i] == INFINITY) return DDP_HIP_E_ARG;
-  if (hi)
-    for (int64_t i = 0; i < words; ++i)
-      if (isnan(hi[i]) || hi[i] == -INFINITY) return DDP_HIP_E_ARG;
-  if (weight)
-    for (int64_t i = 0; i < words; ++i) {
-      if (!cost_weight_ok(weight[i])) return DDP_HIP_E_ARG;
-      if (ctx->model_h.ff && i % n < 6 && weight[i] != 0.0) return DDP_HIP_E_ARG;   // a free-flyer root's pose rows carry no limit
-      nonzero |= weight[i] != 0.0;
-    }
-  if (count == 0 || (!lo && !hi && !weight)) return DDP_HIP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  double* lo_d = ctx->sl_d + first * sz;
-  double* hi_d = ctx->sl_d + all + first * sz;
-  // lo <= hi, before anything is written: a side that arrives alone is held against the resident other side (read back: uploads
-  // are not a hot path)
-  if (lo || hi) {
-    std::vector<double> other;
-    const double *l = lo, *h = hi;
-    if (!lo || !hi) {
-      other.resize((size_t)words);
-      HIP_TRY(hipMemcpyAsync(other.data(), lo ? hi_d : lo_d, sizeof(double) * (size_t)words, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      (lo ? h : l) = other.data();
-    }
-    for (int64_t i = 0; i < words; ++i)
-      if (l[i] > h[i]) return DDP_HIP_E_ARG;
-  }
-  if (lo) HIP_TRY(hipMemcpyAsync(lo_d, lo, sizeof(double) * (size_t)words, hipMemcpyHostToDevice, ctx->stream));
-  if (hi) HIP_TRY(hipMemcpyAsync(hi_d, hi, sizeof(double) * (size_t)words, hipMemcpyHostToDevice, ctx->stream));
-  if (weight) HIP_TRY(hipMemcpyAsync(ctx->sl_d + 2 * all + first * sz, weight, sizeof(double) * (size_t)words, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  // as fc_live: any non-zero weight switches the terms on, only ONE upload of zeros for the whole batch switches them off again
-  if (weight) ctx->sl_live = nonzero || (ctx->sl_live && !(first == 0 && count == ctx->d.batch));
-  return DDP_HIP_OK;
+  const double* host[] = {lo, hi, weight};
+  const CostSideOk ok[] = {cost_limit_lo_side, cost_limit_hi_side, cost_limit_weight_side};
+  return cost_block_upload(ctx, COST_LIMITS, host, ok, first, count, limits_lo_le_hi);
 }
-
 extern "C" int ddp_hip_state_limits_download(ddp_hip_ctx* ctx, double* lo, double* hi, double* weight, int64_t first, int64_t count) {
-  int rc = state_limits_range(ctx, first, count);
-  if (rc != DDP_HIP_OK) return rc;
-  const int64_t sz = (ctx->d.T + 1) * ctx->d.n, words = sz * count, all = sz * ctx->d.batch;
-  if (count == 0 || (!lo && !hi && !weight)) return DDP_HIP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  double* side[3] = {lo, hi, weight};
-  for (int k = 0; k < 3; ++k)
-    if (side[k]) HIP_TRY(hipMemcpyAsync(side[k], ctx->sl_d + k * all + first * sz, sizeof(double) * (size_t)words, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  return DDP_HIP_OK;
+  double* host[] = {lo, hi, weight};
+  return cost_block_download(ctx, COST_LIMITS, host, first, count);
 }
 
 extern "C" int ddp_hip_set_async(ddp_hip_ctx* ctx, int on) {

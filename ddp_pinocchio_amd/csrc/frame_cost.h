@@ -7,7 +7,7 @@
 #include "rbd.h"
 
 // What a kernel reads of the context's frame cost.  target == nullptr: no terms (the flag is off, no frames are set, or no
-// non-zero weight has been uploaded since the frames were set).  oquat == nullptr: no orientation terms, alike (fo_live); the
+// non-zero weight is resident: the block's CostBlock::live).  oquat == nullptr: no orientation terms, alike (their own block); the
 // two sides are independent, and nf / joint are filled when either is live
 struct FrameCostDev {
   const double *target, *weight;   // [batch][T+1][nf][3]
@@ -19,9 +19,10 @@ struct FrameCostDev {
 
 inline FrameCostDev frame_cost_dev(const ddp_hip_ctx* ctx) {
   FrameCostDev f{};
-  if (!ctx->fc_live && !ctx->fo_live) return f;
-  if (ctx->fc_live) { f.target = ctx->fc_target_d; f.weight = ctx->fc_weight_d; }
-  if (ctx->fo_live) { f.oquat = ctx->fo_quat_d; f.oweight = ctx->fo_weight_d; }
+  const CostBlock &fc = ctx->cost[COST_FRAME], &fo = ctx->cost[COST_ORIENT];
+  if (!fc.live && !fo.live) return f;
+  if (fc.live) { f.target = fc.side[0]; f.weight = fc.side[1]; }
+  if (fo.live) { f.oquat = fo.side[0]; f.oweight = fo.side[1]; }
   f.nf = ctx->fc_nf;
   for (int k = 0; k < ctx->fc_nf; ++k) {
     f.joint[k] = ctx->fc_joint[k];
@@ -67,6 +68,12 @@ __device__ __forceinline__ void frame_point(const M& m, bool ff, int joint, cons
 
 // a term of weight 0 is left out, and with all three of a frame the walk itself
 __device__ __forceinline__ bool frame_weights_any(const double* w) { return w[0] != 0.0 || w[1] != 0.0 || w[2] != 0.0; }
+// ... and with all n of a block the block's work
+__device__ __forceinline__ bool weights_any(const double* w, int n) {
+  bool any = false;
+  for (int k = 0; k < n; ++k) any |= w[k] != 0.0;
+  return any;
+}
 
 // World rotation R (row-major, world = R body) of joint `joint`'s frame, walking joint -> root like frame_point with the three
 // columns R e_a alone: c <- Rp (R_axis(q_i) c) for a revolute joint, Rp c for a prismatic one, R(quat) c for a free-flyer root.

@@ -10,7 +10,7 @@
 #include "rbd.h"
 
 // What a kernel reads of the context's frame-velocity cost.  target == nullptr: no terms (the flag is off, no frames are set, or
-// no non-zero weight has been uploaded: fv_live)
+// no non-zero weight has been uploaded: the block's CostBlock::live)
 struct FrameVelCostDev {
   const double *target, *weight;   // [batch][T+1][nf][6]: linear part, then angular part, world axes
   int32_t nf, pad_;
@@ -20,9 +20,10 @@ struct FrameVelCostDev {
 
 inline FrameVelCostDev frame_vel_cost_dev(const ddp_hip_ctx* ctx) {
   FrameVelCostDev f{};
-  if (!ctx->fv_live) return f;
-  f.target = ctx->fv_target_d;
-  f.weight = ctx->fv_weight_d;
+  const CostBlock& k = ctx->cost[COST_FRAME_VEL];
+  if (!k.live) return f;
+  f.target = k.side[0];
+  f.weight = k.side[1];
   f.nf = ctx->fc_nf;
   for (int k = 0; k < ctx->fc_nf; ++k) {
     f.joint[k] = ctx->fc_joint[k];

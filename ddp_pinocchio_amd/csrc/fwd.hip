@@ -805,6 +805,34 @@ __global__ void cand_sum_kernel(FwdParams p) {
   p.fw_dcost[(int64_t)b * na + a] = dsum;
 }
 
+// The add-on cost kernels below (CoM, frame velocities, obstacles) run over a list of `count` (trajectory, t) pairs, t = 0 .. T,
+// `na` trajectories per instance.  Pair e: which trajectory, which t, whose instance, which block bt1 = b (T+1) + t of the term's
+// data.  skip: nothing is written for this pair (past the list, or a candidate the rollout kernels skip: state != 0, beyond
+// 2^-33; state == nullptr: a resident trajectory, none is skipped).  live: the pair is evaluated (the kernels narrow it further)
+struct CostPair {
+  int64_t traj, b, bt1;
+  int t;
+  bool skip, live;
+};
+__device__ __forceinline__ CostPair cost_pair_decode(int64_t e, int64_t count, int32_t T1, int32_t na, const int32_t* state, int32_t round) {
+  CostPair p{0, 0, 0, 0, true, e < count};
+  if (p.live) {
+    p.traj = e / T1;
+    p.t = (int)(e % T1);
+    p.b = p.traj / na;
+    if (state && (state[p.b] != 0 || round * na + (int)(p.traj % na) > 33)) p.live = false;
+    p.bt1 = p.b * T1 + p.t;
+  }
+  p.skip = !p.live;
+  return p;
+}
+// ... and what a pair's first lane leaves: add != 0: out[e] += sum, if some term was formed (COSTS_OLD / COSTS_NEW behind
+// cost_kernel: x + 0 is x but for x = -0); add == 0: out[e] = sum (the candidates' array of a line-search round)
+__device__ __forceinline__ void cost_pair_store(double* out, int64_t e, double sum, bool any, int32_t add) {
+  if (add) { if (any) out[e] += sum; }
+  else out[e] = sum;
+}
+
 // The centre-of-mass terms (DDP_HIP_FLAG_COM_COST, ddp_hip.h) of a list of states, in kernels of their own that add onto what the
 // kernels above leave (none of them knows the term).  The list: `count` (trajectory, t) pairs, t = 0 .. T, trajectory k's states
 // at xs + k traj_stride, `na` trajectories per instance (1: a resident trajectory, n_alpha: the candidates of fw_x).  `lpe` lanes
@@ -812,9 +840,9 @@ __global__ void cand_sum_kernel(FwdParams p) {
 // with its body's CoM alone (rbd::com_body_point: no per-joint arrays, no scratch) and leaves m_j p_j in LDS, the group's first
 // lane adds them up in ascending order (rbd::com_fold) and forms 1/2 sum_a w_a (c_a - g_a)^2.  A term of weight 0 is left out,
 // and with all three of them the walk: such a pair adds nothing (add != 0) or stores +0 (add == 0).  add != 0: out[pair] +=
-// term (COSTS_OLD / COSTS_NEW behind cost_kernel); add == 0: out[pair] = term (cm_new of a line-search round), and the
-// candidates the rollout kernels skip (state != 0, beyond 2^-33) are skipped here.  A non-finite state gives a NaN term, as
-// frame_cost_sum does: the candidate's sum is NaN and select_kernel's `<= 0` does not accept it
+// term (COSTS_OLD / COSTS_NEW behind cost_kernel); add == 0: out[pair] = term (the term's candidates' array in a line-search
+// round), and the candidates the rollout kernels skip (state != 0, beyond 2^-33) are skipped here.  A non-finite state gives a
+// NaN term, as frame_cost_sum does: the candidate's sum is NaN and select_kernel's `<= 0` does not accept it
 __global__ __launch_bounds__(64) void com_cost_kernel(CoMCostDev cm, const DevModel* model, const double* xs, int64_t traj_stride,
                                                       int64_t count, int32_t T1, int32_t nx, int32_t na, int32_t lpe, const int32_t* state,
                                                       int32_t round, double* out, int32_t add) {
@@ -822,17 +850,11 @@ __global__ __launch_bounds__(64) void com_cost_kernel(CoMCostDev cm, const DevMo
   const DevModel& m = *model;
   const int tid = threadIdx.x, g = tid / lpe, j = tid % lpe;
   const int64_t e = (int64_t)blockIdx.x * (64 / lpe) + g;
-  bool live = e < count;
-  int64_t traj = 0, bt1 = 0;
-  int t = 0;
-  if (live) {
-    traj = e / T1;
-    t = (int)(e % T1);
-    const int64_t b = traj / na;
-    if (state && (state[b] != 0 || round * na + (int)(traj % na) > 33)) live = false;
-    bt1 = b * T1 + t;
-  }
-  const bool skip = !live;                                           // nothing is written for this pair
+  const CostPair pr = cost_pair_decode(e, count, T1, na, state, round);
+  const int64_t traj = pr.traj, bt1 = pr.bt1;
+  const int t = pr.t;
+  const bool skip = pr.skip;
+  bool live = pr.live;
   if (live && !rbd::frame_weights_any(cm.weight + bt1 * 3)) live = false;
   if (live && j < m.nj) s_m[tid] = rbd::com_body_point(m, m.ff != 0, j, xs + traj * traj_stride + (int64_t)t * nx, s_mp + 3 * tid);
   __syncthreads();
@@ -845,19 +867,19 @@ __global__ __launch_bounds__(64) void com_cost_kernel(CoMCostDev cm, const DevMo
     rbd::com_fold(s_m + tid, s_mp + 3 * tid, m.nj, c);
     for (int a = 0; a < 3; ++a) { const double r = c[a] - gt[a]; if (w[a] != 0.0) s += w[a] * r * r; }
     term = 0.5 * s;
-  } else if (add) return;
-  if (add) out[e] += term;
-  else out[e] = term;
+  }
+  cost_pair_store(out, e, term, live, add);
 }
 // ... and one lane per (instance, candidate) adds a candidate's terms up in ascending t and adds the sum once onto what the
-// rollout path left in fw_dcost (sum_t (new term without the CoM's - COSTS_OLD[t]): COSTS_OLD holds the old trajectory's CoM
-// terms already), before select_kernel reads it.  A sum of +0 (an instance without CoM weights) is not added: its -0 stays -0
-__global__ void com_sum_kernel(const double* cm_new, double* fw_dcost, const int32_t* state, int32_t batch, int32_t na, int32_t round, int64_t T) {
+// rollout path left in fw_dcost (sum_t (new term without this one - COSTS_OLD[t]): COSTS_OLD holds the old trajectory's terms
+// already), before select_kernel reads it.  A sum of +0 (an instance without weights) is not added: its -0 stays -0.  Named for
+// its first user: it sums any add-on term's candidates (CostBlock::cand), once per live term and round
+__global__ void com_sum_kernel(const double* cand, double* fw_dcost, const int32_t* state, int32_t batch, int32_t na, int32_t round, int64_t T) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= batch * na) return;
   const int b = gid / na, a = gid % na;
   if (state[b] != 0 || round * na + a > 33) return;                  // (beyond 2^-33 the INFINITY stays)
-  const double* c = cm_new + (int64_t)gid * (T + 1);
+  const double* c = cand + (int64_t)gid * (T + 1);
   double s = 0.0;
   for (int64_t t = 0; t <= T; ++t) s += c[t];
   if (s != 0.0) fw_dcost[gid] += s;
@@ -865,8 +887,8 @@ __global__ void com_sum_kernel(const double* cm_new, double* fw_dcost, const int
 
 // The frame-velocity terms (DDP_HIP_FLAG_FRAME_VEL_COST, ddp_hip.h) of a list of states, added on top like the CoM terms above:
 // the same list (`count` (trajectory, t) pairs, trajectory k's states at xs + k traj_stride, `na` trajectories per instance), the
-// same two uses (add != 0: out[pair] += term behind cost_kernel; add == 0: out[pair] = term, fv_new of a line-search round, with
-// the candidates the rollout kernels skip skipped here).  DDP_HIP_MAX_COST_FRAMES lanes per pair, 16 pairs per wave: lane f walks
+// same two uses (add != 0: out[pair] += term behind cost_kernel; add == 0: out[pair] = term, its candidates' array in a line-search
+// round, with the candidates the rollout kernels skip skipped here).  DDP_HIP_MAX_COST_FRAMES lanes per pair, 16 pairs per wave: lane f walks
 // frame f's path once, joint -> root, carrying the point, its velocity and the angular velocity (rbd::frame_velocity: no
 // jacobian, no per-joint arrays), and leaves 1/2 sum_a w_a r_a^2 in LDS; the group's first lane adds the frames' terms in
 // ascending order.  A term of weight 0 is left out, a frame whose six weights are 0 is not walked, and a pair without a live
@@ -880,17 +902,11 @@ __global__ __launch_bounds__(64) void frame_vel_cost_kernel(FrameVelCostDev fv, 
   const DevModel& m = *model;
   const int tid = threadIdx.x, g = tid / L, f = tid % L;
   const int64_t e = (int64_t)blockIdx.x * (64 / L) + g;
-  bool live = e < count;
-  int64_t traj = 0, bt1 = 0;
-  int t = 0;
-  if (live) {
-    traj = e / T1;
-    t = (int)(e % T1);
-    const int64_t b = traj / na;
-    if (state && (state[b] != 0 || round * na + (int)(traj % na) > 33)) live = false;
-    bt1 = b * T1 + t;
-  }
-  const bool skip = !live;                                           // nothing is written for this pair
+  const CostPair pr = cost_pair_decode(e, count, T1, na, state, round);
+  const int64_t traj = pr.traj, bt1 = pr.bt1;
+  const int t = pr.t;
+  const bool skip = pr.skip;
+  bool live = pr.live;
   double term = 0.0;
   int32_t walked = 0;
   if (live && f < fv.nf) {
@@ -912,12 +928,11 @@ __global__ __launch_bounds__(64) void frame_vel_cost_kernel(FrameVelCostDev fv, 
   bool any = false;
   for (int k = 0; k < fv.nf; ++k)
     if (s_live[tid + k]) { sum += s_term[tid + k]; any = true; }
-  if (add) { if (any) out[e] += sum; }
-  else out[e] = sum;
+  cost_pair_store(out, e, sum, any, add);
 }
 
 // The obstacle terms (DDP_HIP_FLAG_OBSTACLE_COST, ddp_hip.h) of a list of states, added on top like the frame-velocity terms above:
-// the same list, the same two uses (add != 0: out[pair] += term behind cost_kernel; add == 0: out[pair] = term, ob_new of a
+// the same list, the same two uses (add != 0: out[pair] += term behind cost_kernel; add == 0: out[pair] = term, the candidates' array in a
 // line-search round, with the candidates the rollout kernels skip skipped here).  DDP_HIP_MAX_COLLISION_POINTS lanes per pair, 4
 // pairs per wave: lane k walks point k once (rbd::frame_point: no jacobian, no per-joint arrays) and leaves 1/2 sum_o w e^2 over
 // its live slots in LDS; the group's first lane adds the points' terms in ascending order.  A pair (point, slot) with w == 0 or
@@ -932,24 +947,16 @@ __global__ __launch_bounds__(64) void obstacle_cost_kernel(ObstacleCostDev ob, c
   const DevModel& m = *model;
   const int tid = threadIdx.x, g = tid / L, k = tid % L;
   const int64_t e = (int64_t)blockIdx.x * (64 / L) + g;
-  bool live = e < count;
-  int64_t traj = 0, bt1 = 0;
-  int t = 0;
-  if (live) {
-    traj = e / T1;
-    t = (int)(e % T1);
-    const int64_t b = traj / na;
-    if (state && (state[b] != 0 || round * na + (int)(traj % na) > 33)) live = false;
-    bt1 = b * T1 + t;
-  }
-  const bool skip = !live;                                           // nothing is written for this pair
+  const CostPair pr = cost_pair_decode(e, count, T1, na, state, round);
+  const int64_t traj = pr.traj, bt1 = pr.bt1;
+  const int t = pr.t;
+  const bool skip = pr.skip;
+  bool live = pr.live;
   double term = 0.0;
   int32_t act = 0;
   if (live && k < ob.np) {
     const double* w = ob.weight + bt1 * ob.no;
-    bool any = false;
-    for (int o = 0; o < ob.no; ++o) any |= w[o] != 0.0;
-    if (any) {
+    if (rbd::weights_any(w, ob.no)) {
       const double off[3] = {ob.off[k][0], ob.off[k][1], ob.off[k][2]};
       double pk[3];
       bool a = false;
@@ -966,8 +973,7 @@ __global__ __launch_bounds__(64) void obstacle_cost_kernel(ObstacleCostDev ob, c
   bool any = false;
   for (int i = 0; i < ob.np; ++i)
     if (s_act[tid + i]) { sum += s_term[tid + i]; any = true; }
-  if (add) { if (any) out[e] += sum; }
-  else out[e] = sum;
+  cost_pair_store(out, e, sum, any, add);
 }
 
 // ddp_hip_obstacle_clearance: the same lane layout over the `count` (instance, t) pairs of one resident trajectory, min instead of
@@ -983,9 +989,7 @@ __global__ __launch_bounds__(64) void obstacle_clearance_kernel(ObstacleCostDev 
   double best = INFINITY;
   if (live && k < ob.np) {
     const double* w = ob.weight + e * ob.no;
-    bool any = false;
-    for (int o = 0; o < ob.no; ++o) any |= w[o] != 0.0;
-    if (any) {
+    if (rbd::weights_any(w, ob.no)) {
       const double off[3] = {ob.off[k][0], ob.off[k][1], ob.off[k][2]};
       double pk[3];
       rbd::frame_point(m, m.ff != 0, ob.joint[k], off, xs + e * nx, pk);
@@ -1160,9 +1164,6 @@ void fwd_teardown(ddp_hip_ctx* ctx) {
   if (ctx->fw_u) (void)hipFree(ctx->fw_u);
   if (ctx->fw_dcost) (void)hipFree(ctx->fw_dcost);
   if (ctx->fw_cost) (void)hipFree(ctx->fw_cost);
-  if (ctx->cm_new) (void)hipFree(ctx->cm_new);
-  if (ctx->fv_new) (void)hipFree(ctx->fv_new);
-  if (ctx->ob_new) (void)hipFree(ctx->ob_new);
   if (ctx->step_d) (void)hipFree(ctx->step_d);
   if (ctx->fw_dcost_acc_d) (void)hipFree(ctx->fw_dcost_acc_d);
   if (ctx->pick_pair_d) (void)hipFree(ctx->pick_pair_d);
@@ -1208,34 +1209,39 @@ extern "C" int ddp_hip_rollout(ddp_hip_ctx* ctx) {
     else LAUNCH(0, false);                                     \
   } while (0)
 
-// com_cost_kernel over `count` (trajectory, t) pairs of trajectories laid out like X (na per instance)
-static void launch_com_cost(ddp_hip_ctx* ctx, const CoMCostDev& cm, const double* xs, int na, int64_t count, const int32_t* state, int round,
-                            double* out, int add) {
+// The add-on kernels over `count` (trajectory, t) pairs of trajectories laid out like X (na per instance): one signature
+typedef void (*AddOnLaunch)(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add);
+
+static void launch_com_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   const Dims& d = ctx->d;
   int lpe = 8;
   while (lpe < ctx->model_h.nj) lpe *= 2;                            // (nj <= DDP_MAXJ = 64: one wave)
   const int64_t per = 64 / lpe;
-  hipLaunchKernelGGL(com_cost_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(64), 0, ctx->stream, cm, ctx->model_d, xs,
+  hipLaunchKernelGGL(com_cost_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(64), 0, ctx->stream, com_cost_dev(ctx), ctx->model_d, xs,
                      (d.T + 1) * d.nx, count, (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, (int32_t)lpe, state, (int32_t)round, out, (int32_t)add);
 }
 
-// frame_vel_cost_kernel over the same kind of list
-static void launch_frame_vel_cost(ddp_hip_ctx* ctx, const FrameVelCostDev& fv, const double* xs, int na, int64_t count, const int32_t* state,
-                                  int round, double* out, int add) {
+static void launch_frame_vel_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   const Dims& d = ctx->d;
   const int64_t per = 64 / DDP_HIP_MAX_COST_FRAMES;
-  hipLaunchKernelGGL(frame_vel_cost_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(64), 0, ctx->stream, fv, ctx->model_d, xs,
+  hipLaunchKernelGGL(frame_vel_cost_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(64), 0, ctx->stream, frame_vel_cost_dev(ctx), ctx->model_d, xs,
                      (d.T + 1) * d.nx, count, (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, state, (int32_t)round, out, (int32_t)add);
 }
 
-// obstacle_cost_kernel over the same kind of list
-static void launch_obstacle_cost(ddp_hip_ctx* ctx, const ObstacleCostDev& ob, const double* xs, int na, int64_t count, const int32_t* state,
-                                 int round, double* out, int add) {
+static void launch_obstacle_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   const Dims& d = ctx->d;
   const int64_t per = 64 / DDP_HIP_MAX_COLLISION_POINTS;
-  hipLaunchKernelGGL(obstacle_cost_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(64), 0, ctx->stream, ob, ctx->model_d, xs,
+  hipLaunchKernelGGL(obstacle_cost_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(64), 0, ctx->stream, obstacle_cost_dev(ctx), ctx->model_d, xs,
                      (d.T + 1) * d.nx, count, (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, state, (int32_t)round, out, (int32_t)add);
 }
+
+// The terms formed out of line, in the fixed order of their additions (after everything cost_kernel / the rollout kernels form
+// inline): CoM, frame velocities, obstacles.  launch_cost and ddp_hip_forward both walk this table and nothing else
+struct AddOnTerm {
+  int term;
+  AddOnLaunch launch;
+};
+static const AddOnTerm kAddOn[] = {{COST_COM, launch_com_cost}, {COST_FRAME_VEL, launch_frame_vel_cost}, {COST_OBSTACLE, launch_obstacle_cost}};
 
 static int launch_cost(ddp_hip_ctx* ctx, FwdParams& p, int which) {
   const int bs = 64;
@@ -1246,15 +1252,8 @@ static int launch_cost(ddp_hip_ctx* ctx, FwdParams& p, int which) {
   DISPATCH_COST(p, LAUNCH);
 #undef LAUNCH
 #undef CALL
-  const CoMCostDev cm = com_cost_dev(ctx);
-  if (cm.target)                                                     // + the CoM terms, onto what cost_kernel has left
-    launch_com_cost(ctx, cm, which == 0 ? p.x_old : p.x_new, 1, total, nullptr, 0, which == 0 ? p.costs_old : p.costs_new, 1);
-  const FrameVelCostDev fv = frame_vel_cost_dev(ctx);
-  if (fv.target)                                                     // + the frame-velocity terms, after the CoM's
-    launch_frame_vel_cost(ctx, fv, which == 0 ? p.x_old : p.x_new, 1, total, nullptr, 0, which == 0 ? p.costs_old : p.costs_new, 1);
-  const ObstacleCostDev ob = obstacle_cost_dev(ctx);
-  if (ob.geom)                                                       // + the obstacle terms, last
-    launch_obstacle_cost(ctx, ob, which == 0 ? p.x_old : p.x_new, 1, total, nullptr, 0, which == 0 ? p.costs_old : p.costs_new, 1);
+  for (const AddOnTerm& a : kAddOn)                                   // + each live add-on term, onto what cost_kernel has left
+    if (ctx->cost[a.term].live) a.launch(ctx, which == 0 ? p.x_old : p.x_new, 1, total, nullptr, 0, which == 0 ? p.costs_old : p.costs_new, 1);
   HIP_TRY(hipGetLastError());
   return DDP_HIP_OK;
 }
@@ -1304,9 +1303,6 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
   p.n_alpha = n_alpha;
   p.no_linesearch = no_linesearch ? 1 : 0;
   int rc = launch_cost(ctx, p, 0);                                   // ddp_fwd.ipp:24-26
-  const CoMCostDev cm = com_cost_dev(ctx);
-  const FrameVelCostDev fv = frame_vel_cost_dev(ctx);
-  const ObstacleCostDev ob = obstacle_cost_dev(ctx);
   if (rc != DDP_HIP_OK) return rc;
   const int bs = 64;
   const unsigned grid = (unsigned)((B * n_alpha + bs - 1) / bs);
@@ -1341,23 +1337,13 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
 #undef CALL
     }
     prof_end(ctx, DDP_HIP_K_FWD_ROLLOUT);
-    if (cm.target) {
-      // the candidates' CoM terms, whichever rollout path ran: over fw_x into cm_new, then once onto fw_dcost
-      launch_com_cost(ctx, cm, p.fw_x, n_alpha, B * n_alpha * (d.T + 1), p.state, round, ctx->cm_new, 0);
-      hipLaunchKernelGGL(com_sum_kernel, dim3((unsigned)((B * n_alpha + 63) / 64)), dim3(64), 0, ctx->stream, ctx->cm_new, p.fw_dcost, p.state,
-                         (int32_t)B, (int32_t)n_alpha, (int32_t)round, d.T);
-    }
-    if (fv.target) {
-      // the candidates' frame-velocity terms alike, into fv_new, and once onto fw_dcost after the CoM's sum
-      launch_frame_vel_cost(ctx, fv, p.fw_x, n_alpha, B * n_alpha * (d.T + 1), p.state, round, ctx->fv_new, 0);
-      hipLaunchKernelGGL(com_sum_kernel, dim3((unsigned)((B * n_alpha + 63) / 64)), dim3(64), 0, ctx->stream, ctx->fv_new, p.fw_dcost, p.state,
-                         (int32_t)B, (int32_t)n_alpha, (int32_t)round, d.T);
-    }
-    if (ob.geom) {
-      // the candidates' obstacle terms alike, into ob_new, and once onto fw_dcost after the frame velocities' sum: a candidate
-      // that touches no obstacle has the sum +0, which com_sum_kernel does not add
-      launch_obstacle_cost(ctx, ob, p.fw_x, n_alpha, B * n_alpha * (d.T + 1), p.state, round, ctx->ob_new, 0);
-      hipLaunchKernelGGL(com_sum_kernel, dim3((unsigned)((B * n_alpha + 63) / 64)), dim3(64), 0, ctx->stream, ctx->ob_new, p.fw_dcost, p.state,
+    for (const AddOnTerm& a : kAddOn) {
+      // a live term's candidates, whichever rollout path ran: over fw_x into the term's candidates' array, then summed once onto
+      // fw_dcost (a candidate whose sum is +0 -- no weight, no obstacle touched -- has nothing added)
+      const CostBlock& k = ctx->cost[a.term];
+      if (!k.live) continue;
+      a.launch(ctx, p.fw_x, n_alpha, B * n_alpha * (d.T + 1), p.state, round, k.cand, 0);
+      hipLaunchKernelGGL(com_sum_kernel, dim3((unsigned)((B * n_alpha + 63) / 64)), dim3(64), 0, ctx->stream, k.cand, p.fw_dcost, p.state,
                          (int32_t)B, (int32_t)n_alpha, (int32_t)round, d.T);
     }
     hipLaunchKernelGGL(select_kernel, dim3((unsigned)B), dim3(256), 0, ctx->stream, p);

@@ -6,6 +6,7 @@
 
 #include <vector>
 
+#include "cost_block.h"
 #include "ddp_hip/ddp_hip.h"
 
 #define DDP_MAXJ DDP_HIP_MAX_JOINTS
@@ -246,45 +247,20 @@ struct ddp_hip_ctx {
   std::vector<int32_t> active_h;   // [batch], 1 = active
   bool all_active = true;
 
-  // frame-position cost (DDP_HIP_FLAG_FRAME_COST; ctx.hip: ddp_hip_frame_cost_*, frame_cost.h)
+  // the per-instance add-on cost terms (cost_block.h; ctx.hip: ddp_hip_*_upload / _download): one record
+  // each.  What the batch shares -- the geometry -- stays beside them
+  CostBlock cost[COST_COUNT];
+  // the cost frames (ddp_hip_frame_cost_set_frames): of the position, orientation and velocity terms alike
   int32_t fc_nf = 0;                          // cost frames set (0: none yet)
   int32_t fc_joint[DDP_HIP_MAX_COST_FRAMES] = {};
   double fc_off[DDP_HIP_MAX_COST_FRAMES][3] = {};
-  double* fc_target_d = nullptr;              // [batch][T+1][fc_nf][3] (room for DDP_HIP_MAX_COST_FRAMES)
-  double* fc_weight_d = nullptr;
-  bool fc_live = false;                       // some non-zero weight was uploaded since the frames were set: the kernels form the terms
-  // frame-orientation cost (DDP_HIP_FLAG_FRAME_ORIENT_COST; ctx.hip: ddp_hip_frame_orient_*): of the same frames
-  double* fo_quat_d = nullptr;                // [batch][T+1][fc_nf][4] unit quaternions x y z w (room for DDP_HIP_MAX_COST_FRAMES)
-  double* fo_weight_d = nullptr;              // [batch][T+1][fc_nf][3]
-  bool fo_live = false;                       // as fc_live, for the orientation weights: the two are independent
-
-  // soft state limits (DDP_HIP_FLAG_STATE_LIMITS; ctx.hip: ddp_hip_state_limits_*, state_limits.h)
-  double* sl_d = nullptr;                     // lo | hi | weight, each [batch][T+1][n]
-  bool sl_live = false;                       // some non-zero weight was uploaded: the kernels form the terms
-
-  // centre-of-mass cost (DDP_HIP_FLAG_COM_COST; ctx.hip: ddp_hip_com_cost_*, com_cost.h)
-  double* cm_target_d = nullptr;              // [batch][T+1][3]
-  double* cm_weight_d = nullptr;
-  double* cm_new = nullptr;                   // [batch][n_alpha_max][T+1] the candidates' CoM terms of a line-search round (since the first non-zero weight)
-  bool cm_live = false;                       // as fc_live: the CoM kernels are launched
-
-  // frame-velocity cost (DDP_HIP_FLAG_FRAME_VEL_COST; ctx.hip: ddp_hip_frame_vel_*, frame_vel_cost.h), of the frames above
-  double* fv_target_d = nullptr;              // [batch][T+1][fc_nf][6] (room for DDP_HIP_MAX_COST_FRAMES): linear, then angular
-  double* fv_weight_d = nullptr;
-  double* fv_new = nullptr;                   // [batch][n_alpha_max][T+1] the candidates' terms of a line-search round (since the first non-zero weight)
-  bool fv_live = false;                       // as cm_live: the frame-velocity kernels are launched
-
-  // obstacle cost (DDP_HIP_FLAG_OBSTACLE_COST; ctx.hip: ddp_hip_obstacle_*, obstacle_cost.h)
+  // the collision points and the obstacle slots' kinds (ddp_hip_obstacle_set_points)
   int32_t ob_np = 0, ob_no = 0;               // collision points and obstacle slots set (0: none yet)
   int32_t ob_joint[DDP_HIP_MAX_COLLISION_POINTS] = {};
   double ob_off[DDP_HIP_MAX_COLLISION_POINTS][3] = {};
   double ob_radius[DDP_HIP_MAX_COLLISION_POINTS] = {};
   int32_t ob_kind[DDP_HIP_MAX_OBSTACLES] = {};
-  double* ob_geom_d = nullptr;                // [batch][T+1][ob_no][4] (room for DDP_HIP_MAX_OBSTACLES)
-  double* ob_weight_d = nullptr;              // [batch][T+1][ob_no]
   double* ob_clear_d = nullptr;               // [batch][T+1] what ddp_hip_obstacle_clearance hands back
-  double* ob_new = nullptr;                   // [batch][n_alpha_max][T+1] the candidates' terms of a line-search round (since the first non-zero weight)
-  bool ob_live = false;                       // as cm_live: the obstacle kernels are launched
 
   bool box_dirty = false;       // CTRL_LO / CTRL_HI were uploaded since lo <= hi was last checked (ctx.hip: box_check)
 

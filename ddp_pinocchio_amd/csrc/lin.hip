@@ -102,6 +102,25 @@ __global__ void lin_track_cost_kernel(LinParams p) {
   for (int i = tid; i < m * m; i += blockDim.x) p.luu[bt * m * m + i] = (i % m == i / m) ? 1.0 * c + p.wu[bt * m + i % m] : 0.0;
 }
 
+// What the add-on cost kernels below know of their block bt1 = b (T+1) + t, t = 0 .. T (one workgroup each): the state, and the
+// gradient and Hessian they add onto -- lx / lxx of (b, t), or lfx / lfxx at t = T
+struct LinCostBlock {
+  int b;
+  int64_t t;
+  const double* q;
+  double *gx, *gxx;
+};
+__device__ __forceinline__ LinCostBlock lin_cost_block(const LinParams& p, int64_t bt1) {
+  const int64_t T = p.d.T, n = p.d.n;
+  LinCostBlock k;
+  k.b = (int)(bt1 / (T + 1));
+  k.t = bt1 % (T + 1);
+  k.q = p.x + bt1 * p.d.nx;
+  k.gx = k.t < T ? p.lx + ((int64_t)k.b * T + k.t) * n : p.lfx + (int64_t)k.b * n;
+  k.gxx = k.t < T ? p.lxx + ((int64_t)k.b * T + k.t) * n * n : p.lfxx + (int64_t)k.b * n * n;
+  return k;
+}
+
 // Frame-position cost (DDP_HIP_FLAG_FRAME_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after lin_cost_kernel /
 // lin_track_cost_kernel on the same stream: their output is the starting point, and only the entries of the joints on the
 // frames' paths are read and rewritten.  Lane f walks frame f's path once for p_f and the path columns of its point jacobian
@@ -111,17 +130,13 @@ __global__ void lin_track_cost_kernel(LinParams p) {
 // symmetric bit for bit.  A term of weight 0 is left out, a block whose weights are all 0 returns at once.  t = T: lfx / lfxx
 __global__ __launch_bounds__(64) void lin_frame_cost_kernel(LinParams p, FrameCostDev fc) {
   constexpr int F = DDP_HIP_MAX_COST_FRAMES;
-  const int64_t T = p.d.T;
   const int64_t bt1 = blockIdx.x;
-  const int b = (int)(bt1 / (T + 1));
-  const int64_t t = bt1 % (T + 1);
-  const int n = (int)p.d.n, nv = (int)p.d.nv, nx = (int)p.d.nx;
+  const int n = (int)p.d.n, nv = (int)p.d.nv;
   const int tid = threadIdx.x, nf = fc.nf;
   const double* g = fc.target + bt1 * nf * 3;
   const double* w = fc.weight + bt1 * nf * 3;
-  bool any = false;
-  for (int k = 0; k < 3 * nf; ++k) any |= w[k] != 0.0;
-  if (!any) return;
+  if (!rbd::weights_any(w, 3 * nf)) return;
+  const LinCostBlock blk = lin_cost_block(p, bt1);
   __shared__ double s_P[F][3 * DDP_MAXJ], s_aw[F][9 + 3 * DDP_MAXJ], s_ow[F][3 * DDP_MAXJ], s_w[F][3], s_wr[F][3];
   __shared__ int s_chain[F][DDP_MAXJ];
   __shared__ unsigned long long s_mask[F];
@@ -130,7 +145,7 @@ __global__ __launch_bounds__(64) void lin_frame_cost_kernel(LinParams p, FrameCo
     if (rbd::frame_weights_any(w + 3 * tid)) {
       double pf[3];
       const double off[3] = {fc.off[tid][0], fc.off[tid][1], fc.off[tid][2]};
-      mask = rbd::frame_point_jacobian(*p.model, fc.joint[tid], off, p.x + bt1 * nx, pf, s_P[tid], s_chain[tid], s_aw[tid], s_ow[tid]);
+      mask = rbd::frame_point_jacobian(*p.model, fc.joint[tid], off, blk.q, pf, s_P[tid], s_chain[tid], s_aw[tid], s_ow[tid]);
       for (int a = 0; a < 3; ++a) {
         const double wa = w[3 * tid + a];
         s_w[tid][a] = wa;
@@ -142,8 +157,7 @@ __global__ __launch_bounds__(64) void lin_frame_cost_kernel(LinParams p, FrameCo
   __syncthreads();
   unsigned long long all = 0;
   for (int f = 0; f < nf; ++f) all |= s_mask[f];
-  double* gx = t < T ? p.lx + ((int64_t)b * T + t) * n : p.lfx + (int64_t)b * n;
-  double* gxx = t < T ? p.lxx + ((int64_t)b * T + t) * n * n : p.lfxx + (int64_t)b * n * n;
+  double *gx = blk.gx, *gxx = blk.gxx;
   for (int i = tid; i < nv; i += blockDim.x) {
     if (!((all >> i) & 1)) continue;
     double s = 0.0;
@@ -180,17 +194,13 @@ __global__ __launch_bounds__(64) void lin_frame_cost_kernel(LinParams p, FrameCo
 // at once.  t = T: lfx / lfxx
 __global__ __launch_bounds__(64) void lin_frame_orient_cost_kernel(LinParams p, FrameCostDev fc) {
   constexpr int F = DDP_HIP_MAX_COST_FRAMES;
-  const int64_t T = p.d.T;
   const int64_t bt1 = blockIdx.x;
-  const int b = (int)(bt1 / (T + 1));
-  const int64_t t = bt1 % (T + 1);
-  const int n = (int)p.d.n, nv = (int)p.d.nv, nx = (int)p.d.nx;
+  const int n = (int)p.d.n, nv = (int)p.d.nv;
   const int tid = threadIdx.x, nf = fc.nf;
   const double* r = fc.oquat + bt1 * nf * 4;
   const double* w = fc.oweight + bt1 * nf * 3;
-  bool any = false;
-  for (int k = 0; k < 3 * nf; ++k) any |= w[k] != 0.0;
-  if (!any) return;
+  if (!rbd::weights_any(w, 3 * nf)) return;
+  const LinCostBlock blk = lin_cost_block(p, bt1);
   __shared__ double s_A[F][3 * DDP_MAXJ], s_w[F][3], s_we[F][3];
   __shared__ int s_chain[F][DDP_MAXJ];
   __shared__ unsigned long long s_mask[F];
@@ -198,7 +208,7 @@ __global__ __launch_bounds__(64) void lin_frame_orient_cost_kernel(LinParams p, 
     unsigned long long mask = 0;
     if (rbd::frame_weights_any(w + 3 * tid)) {
       double R[9], e[3], J[9], M[9];
-      mask = rbd::frame_rotation_jacobian(*p.model, fc.joint[tid], p.x + bt1 * nx, R, s_A[tid], s_chain[tid]);
+      mask = rbd::frame_rotation_jacobian(*p.model, fc.joint[tid], blk.q, R, s_A[tid], s_chain[tid]);
       lie::so3_log_rel(r + 4 * tid, R, e);
       lie::so3_Jlog(e, J);
       for (int i = 0; i < 3; ++i)
@@ -219,8 +229,7 @@ __global__ __launch_bounds__(64) void lin_frame_orient_cost_kernel(LinParams p, 
   __syncthreads();
   unsigned long long all = 0;
   for (int f = 0; f < nf; ++f) all |= s_mask[f];
-  double* gx = t < T ? p.lx + ((int64_t)b * T + t) * n : p.lfx + (int64_t)b * n;
-  double* gxx = t < T ? p.lxx + ((int64_t)b * T + t) * n * n : p.lfxx + (int64_t)b * n * n;
+  double *gx = blk.gx, *gxx = blk.gxx;
   for (int i = tid; i < nv; i += blockDim.x) {
     if (!((all >> i) & 1)) continue;
     double s = 0.0;
@@ -252,17 +261,14 @@ __global__ __launch_bounds__(64) void lin_frame_orient_cost_kernel(LinParams p, 
 // Nothing else is read or written (a diagonal entry: the block stays symmetric).  Rows 0 .. 5 of a free-flyer root carry no
 // limit.  t = T: lfx / lfxx
 __global__ __launch_bounds__(64) void lin_limit_cost_kernel(LinParams p, StateLimitsDev sl) {
-  const int64_t T = p.d.T;
   const int64_t bt1 = blockIdx.x;
-  const int b = (int)(bt1 / (T + 1));
-  const int64_t t = bt1 % (T + 1);
   const int n = (int)p.d.n, nv = (int)p.d.nv, nx = (int)p.d.nx, nq = nx - nv;
-  const double* x = p.x + bt1 * nx;
+  const LinCostBlock blk = lin_cost_block(p, bt1);
+  const double* x = blk.q;
   const double* w = sl.weight + bt1 * n;
   const double* lo = sl.lo + bt1 * n;
   const double* hi = sl.hi + bt1 * n;
-  double* gx = t < T ? p.lx + ((int64_t)b * T + t) * n : p.lfx + (int64_t)b * n;
-  double* gxx = t < T ? p.lxx + ((int64_t)b * T + t) * n * n : p.lfxx + (int64_t)b * n * n;
+  double *gx = blk.gx, *gxx = blk.gxx;
   for (int i = (nx > n ? 6 : 0) + threadIdx.x; i < n; i += blockDim.x) {
     const double wi = w[i];
     if (wi == 0.0) continue;
@@ -283,16 +289,14 @@ __global__ __launch_bounds__(64) void lin_limit_cost_kernel(LinParams p, StateLi
 // bit for bit.  It reads p.x and touches nothing but those entries.  A term of weight 0 is left out, a block whose three weights
 // are 0 returns at once.  t = T: lfx / lfxx
 __global__ __launch_bounds__(64) void lin_com_cost_kernel(LinParams p, CoMCostDev cm) {
-  const int64_t T = p.d.T;
   const int64_t bt1 = blockIdx.x;
-  const int b = (int)(bt1 / (T + 1));
-  const int64_t t = bt1 % (T + 1);
-  const int n = (int)p.d.n, nv = (int)p.d.nv, nx = (int)p.d.nx;
+  const int n = (int)p.d.n, nv = (int)p.d.nv;
   const int tid = threadIdx.x;
   const double* w = cm.weight + bt1 * 3;
   if (!rbd::frame_weights_any(w)) return;
   const DevModel& m = *p.model;
-  const double* q = p.x + bt1 * nx;
+  const LinCostBlock blk = lin_cost_block(p, bt1);
+  const double* q = blk.q;
   __shared__ rbd::CoMWaveLds S;
   __shared__ double s_w[3], s_wr[3];
   if (tid < m.nj) rbd::com_stage_lane(m, q, tid, S);
@@ -305,8 +309,7 @@ __global__ __launch_bounds__(64) void lin_com_cost_kernel(LinParams p, CoMCostDe
     s_wr[tid] = wa != 0.0 ? wa * (S.c[tid] - cm.target[bt1 * 3 + tid]) : 0.0;
   }
   __syncthreads();
-  double* gx = t < T ? p.lx + ((int64_t)b * T + t) * n : p.lfx + (int64_t)b * n;
-  double* gxx = t < T ? p.lxx + ((int64_t)b * T + t) * n * n : p.lfxx + (int64_t)b * n * n;
+  double *gx = blk.gx, *gxx = blk.gxx;
   for (int i = tid; i < nv; i += blockDim.x) {
     double s = 0.0;
     for (int a = 0; a < 3; ++a)
@@ -334,19 +337,15 @@ __global__ __launch_bounds__(64) void lin_com_cost_kernel(LinParams p, CoMCostDe
 // entries.  A term of weight 0 is left out, a frame whose six weights are 0 is not walked, a block without a live weight returns
 // at once.  t = T: lfx / lfxx
 __global__ __launch_bounds__(64) void lin_frame_vel_cost_kernel(LinParams p, FrameVelCostDev fv) {
-  const int64_t T = p.d.T;
   const int64_t bt1 = blockIdx.x;
-  const int b = (int)(bt1 / (T + 1));
-  const int64_t t = bt1 % (T + 1);
-  const int n = (int)p.d.n, nv = (int)p.d.nv, nx = (int)p.d.nx;
+  const int n = (int)p.d.n, nv = (int)p.d.nv;
   const int tid = threadIdx.x, nf = fv.nf;
   const double* w = fv.weight + bt1 * nf * 6;
-  bool any = false;
-  for (int k = 0; k < 6 * nf; ++k) any |= w[k] != 0.0;
-  if (!any) return;
+  if (!rbd::weights_any(w, 6 * nf)) return;
   const DevModel& m = *p.model;
   const bool ff = m.ff != 0;
-  const double* q = p.x + bt1 * nx;
+  const LinCostBlock blk = lin_cost_block(p, bt1);
+  const double* q = blk.q;
   const double* v = q + m.nq;
   __shared__ rbd::VelWaveLds S;
   __shared__ double s_w[6 * DDP_HIP_MAX_COST_FRAMES], s_wr[6 * DDP_HIP_MAX_COST_FRAMES];
@@ -372,8 +371,7 @@ __global__ __launch_bounds__(64) void lin_frame_vel_cost_kernel(LinParams p, Fra
     s_wr[tid] = wa != 0.0 ? wa * (S.vel[tid / 6][tid % 6] - fv.target[bt1 * nf * 6 + tid]) : 0.0;
   }
   __syncthreads();
-  double* gx = t < T ? p.lx + ((int64_t)b * T + t) * n : p.lfx + (int64_t)b * n;
-  double* gxx = t < T ? p.lxx + ((int64_t)b * T + t) * n * n : p.lfxx + (int64_t)b * n * n;
+  double *gx = blk.gx, *gxx = blk.gxx;
   rbd::vel_add_wave(S, nf, s_w, s_wr, __builtin_popcountll(U), tid, (int)blockDim.x, nv, n, gx, gxx);
 }
 
@@ -390,19 +388,15 @@ __global__ __launch_bounds__(64) void lin_frame_vel_cost_kernel(LinParams p, Fra
 // (i, j) in (min, max) order, symmetric bit for bit).  It reads p.x and touches nothing but those entries.  No atomics.
 // t = T: lfx / lfxx
 __global__ __launch_bounds__(64) void lin_obstacle_cost_kernel(LinParams p, ObstacleCostDev ob) {
-  const int64_t T = p.d.T;
   const int64_t bt1 = blockIdx.x;
-  const int b = (int)(bt1 / (T + 1));
-  const int64_t t = bt1 % (T + 1);
-  const int n = (int)p.d.n, nx = (int)p.d.nx;
+  const int n = (int)p.d.n;
   const int tid = threadIdx.x;
   const double* w = ob.weight + bt1 * ob.no;
-  bool any = false;
-  for (int o = 0; o < ob.no; ++o) any |= w[o] != 0.0;
-  if (!any) return;
+  if (!rbd::weights_any(w, ob.no)) return;
   const DevModel& m = *p.model;
   const bool ff = m.ff != 0;
-  const double* q = p.x + bt1 * nx;
+  const LinCostBlock blk = lin_cost_block(p, bt1);
+  const double* q = blk.q;
   double pk[3] = {0.0, 0.0, 0.0}, g[3], M[6];
   bool act = false;
   if (tid < ob.np) {
@@ -426,8 +420,7 @@ __global__ __launch_bounds__(64) void lin_obstacle_cost_kernel(LinParams p, Obst
     if ((active >> k) & 1) U |= rbd::vel_tangent_mask(ff, S.mask[ob.joint[k]]);
   if ((U >> tid) & 1) S.idx[__builtin_popcountll(U & ((1ull << tid) - 1))] = tid;
   __syncthreads();
-  double* gx = t < T ? p.lx + ((int64_t)b * T + t) * n : p.lfx + (int64_t)b * n;
-  double* gxx = t < T ? p.lxx + ((int64_t)b * T + t) * n * n : p.lfxx + (int64_t)b * n * n;
+  double *gx = blk.gx, *gxx = blk.gxx;
   rbd::obstacle_add_wave(m, S, ob, active, __builtin_popcountll(U), tid, (int)blockDim.x, n, gx, gxx);
 }
 
@@ -1259,17 +1252,21 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     if (ctx->flags & DDP_HIP_FLAG_TRACKING_COST)
       hipLaunchKernelGGL(lin_track_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p);
     else hipLaunchKernelGGL(lin_cost_kernel, dim3((unsigned)BT), dim3(64), 0, ctx->stream, p);
+    // the add-on terms, one kernel per live term, each adding onto what the ones before it left.  The fixed order of additions:
+    // cost, tracking, frame positions, frame orientations, limits, CoM, frame velocities, obstacles
+    const dim3 blocks((unsigned)(BT + d.batch));
     const FrameCostDev fc = frame_cost_dev(ctx);
-    if (fc.target) hipLaunchKernelGGL(lin_frame_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, fc);
-    if (fc.oquat) hipLaunchKernelGGL(lin_frame_orient_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, fc);
     const StateLimitsDev sl = state_limits_dev(ctx);
-    if (sl.weight) hipLaunchKernelGGL(lin_limit_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, sl);
     const CoMCostDev cm = com_cost_dev(ctx);
-    if (cm.target) hipLaunchKernelGGL(lin_com_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, cm);
     const FrameVelCostDev fv = frame_vel_cost_dev(ctx);
-    if (fv.target) hipLaunchKernelGGL(lin_frame_vel_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, fv);
     const ObstacleCostDev ob = obstacle_cost_dev(ctx);
-    if (ob.geom) hipLaunchKernelGGL(lin_obstacle_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p, ob);
+    auto add = [&](bool live, auto kernel, const auto& dev) { if (live) hipLaunchKernelGGL(kernel, blocks, dim3(64), 0, ctx->stream, p, dev); };
+    add(fc.target, lin_frame_cost_kernel, fc);
+    add(fc.oquat, lin_frame_orient_cost_kernel, fc);
+    add(sl.weight, lin_limit_cost_kernel, sl);
+    add(cm.target, lin_com_cost_kernel, cm);
+    add(fv.target, lin_frame_vel_cost_kernel, fv);
+    add(ob.geom, lin_obstacle_cost_kernel, ob);
   }
   // the q- / v-caches of the mode-2 stencil also serve the first order (base configuration and base (q, v)), so they are built
   // ahead of whichever stage comes first

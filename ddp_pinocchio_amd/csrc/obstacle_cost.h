@@ -10,7 +10,7 @@
 #include "rbd.h"
 
 // What a kernel reads of the context's obstacle cost.  geom == nullptr: no terms (the flag is off, no points are set, or no
-// non-zero weight has been uploaded: ob_live)
+// non-zero weight has been uploaded: the block's CostBlock::live)
 struct ObstacleCostDev {
   const double *geom, *weight;     // [batch][T+1][no][4], [batch][T+1][no]
   int32_t np, no;                  // collision points, obstacle slots
@@ -23,9 +23,10 @@ struct ObstacleCostDev {
 // always: the description whether or not a weight is live (ddp_hip_obstacle_clearance works from the first set_points on)
 inline ObstacleCostDev obstacle_cost_dev(const ddp_hip_ctx* ctx, bool always = false) {
   ObstacleCostDev c{};
-  if (!(always ? ctx->ob_np > 0 : ctx->ob_live)) return c;
-  c.geom = ctx->ob_geom_d;
-  c.weight = ctx->ob_weight_d;
+  const CostBlock& k = ctx->cost[COST_OBSTACLE];
+  if (!(always ? ctx->ob_np > 0 : k.live)) return c;
+  c.geom = k.side[0];
+  c.weight = k.side[1];
   c.np = ctx->ob_np;
   c.no = ctx->ob_no;
   for (int k = 0; k < ctx->ob_np; ++k) {

@@ -4,16 +4,15 @@
 #include "internal.h"
 
 // What a kernel reads of the context's state limits: three arrays [batch][T+1][n] over the tangent rows (n = 2 nv).
-// weight == nullptr: no terms (the flag is off, or no non-zero weight has been uploaded)
+// weight == nullptr: no terms (the flag is off, or no non-zero weight is resident: CostBlock::live)
 struct StateLimitsDev {
   const double *lo, *hi, *weight;
 };
 
 inline StateLimitsDev state_limits_dev(const ddp_hip_ctx* ctx) {
   StateLimitsDev s{};
-  if (!ctx->sl_live) return s;
-  const int64_t words = ctx->d.batch * (ctx->d.T + 1) * ctx->d.n;
-  s.lo = ctx->sl_d; s.hi = ctx->sl_d + words; s.weight = ctx->sl_d + 2 * words;
+  const CostBlock& k = ctx->cost[COST_LIMITS];
+  if (k.live) { s.lo = k.side[0]; s.hi = k.side[1]; s.weight = k.side[2]; }
   return s;
 }
 

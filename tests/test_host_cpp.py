@@ -19,6 +19,14 @@ def test_indexer_and_mat_seq_known_answers():
     assert out.returncode == 0, out.stdout + out.stderr
 
 
+def test_cost_block_host_logic():
+    """host/test_cost_block.cpp: the validators, range arithmetic, non-zero scan and live rule of the add-on cost terms' upload
+    path (csrc/cost_block.h), which need no device"""
+    _build()
+    out = subprocess.run([os.path.join(HOST, "test_cost_block")], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+
+
 def test_driver_refuses_without_a_device():
     from ddp_pinocchio_amd import capi
     if capi.lib().ddp_hip_device_count() > 0:

@@ -11,7 +11,7 @@ Every call is synchronous and timed by the wall clock: median [min - max] of 20 
 Linearise is timed with weights of order 1.  The backward sweep is timed on the flag-off derivatives: at T = 200 the full-DDP
 sweep of this tree does not stay positive definite once the dense CoM block enters V_xx, not even with the weights scaled by
 1e-12 (the CPU oracle exhausts its restarts on the same derivatives), and a sweep that restarts is not one
-sweep.  So before it the weights are zeroed in two half-batch uploads, which leaves the CoM kernels launched (cm_live's rule)
+sweep.  So before it the weights are zeroed in two half-batch uploads, which leaves the CoM kernels launched (the live rule)
 with nothing to add; the sweep's kernels and bytes do not depend on the values.  The forward is then timed with the weights
 of order 1 back in place, on those gains: com_cost_kernel does its full work on every candidate.  The forward's wall time
 counts line-search rounds, so it is also given per round (forward_ms_per_round: rollout + com_cost_kernel over the

@@ -14,7 +14,7 @@ Every call is synchronous and timed by the wall clock: median [min - max] of 20 
 backward sweep is timed on the flag-off derivatives, as tools/com_cost_timing.py does and for its reason (at
 T = 200 the full-DDP sweep of these held trajectories does not stay positive definite once a dense cost block enters V_xx, and
 a sweep that restarts is not one sweep): before it the weights are zeroed in two half-batch uploads, which leaves the kernels
-launched (fv_live's rule) with nothing to add.  The forward is then timed with the weights back in place, on those gains:
+launched (the live rule) with nothing to add.  The forward is then timed with the weights back in place, on those gains:
 frame_vel_cost_kernel does its full work on every candidate.  The forward's wall time counts line-search rounds, so it is also
 given per round (forward_ms_per_round), beside the rollout kernel alone from the ddp_hip_profile_* events
 (rollout_ms_per_round).  The new kernels on their own are the differences on against off of

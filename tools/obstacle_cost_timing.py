@@ -17,7 +17,7 @@ ddp_hip_linearize_stages(LIN_COST) (lin_obstacle_cost_kernel: batch x (T+1) wave
 over batch x (T+1) states); the forward counts line-search rounds, so it is also given per round (rollout + obstacle_cost_kernel
 over the batch x 8 x (T+1) candidate states + com_sum_kernel + select), beside the rollout kernel alone from the
 ddp_hip_profile_* events.  The backward sweep that provides the forward's gains runs on the flag-off derivatives (the weights are
-zeroed in two half-batch uploads, which leaves the kernels launched with nothing to add: ob_live's rule), as in
+zeroed in two half-batch uploads, which leaves the kernels launched with nothing to add: the live rule), as in
 tools/com_cost_timing.py; the weights are back in place for the forward.  The expectation: the "clear" line sits near the
 flag-off line."""
 import argparse
