@@ -727,6 +727,15 @@ int bwd_setup(ddp_hip_ctx* ctx) {
     // the box QP keeps a second copy of Q_uu in LDS: past the default 64 KB of dynamic LDS from m = 35 on
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_gains<0, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gains_lds_bytes(ctx)));
   }
+  // ... and so do the run-time-shaped kernels of every other robot: bwd_gains from nv = 40, bwd_assemble from nv = 60 (at this
+  // context's job width).  A size past 160 KB gets no attribute: ddp_hip_backward refuses it (bwd_lds_check)
+  {
+    const size_t lds_a = assemble_lds_bytes(ctx, (int)(cbx > cbu ? cbx : cbu)), lds_g = gains_lds_bytes(ctx);
+    if (lds_a > 64 * 1024 && lds_a <= 160 * 1024)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_assemble<0, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
+    if (!(ctx->flags & DDP_HIP_FLAG_CONTROL_BOUNDS) && lds_g > 64 * 1024 && lds_g <= 160 * 1024)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd_gains<0, 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g));
+  }
   HIP_TRY(hipMalloc(&ctx->jobs_d, sizeof(BwdJob) * jobs.size()));
   HIP_TRY(hipMemcpy(ctx->jobs_d, jobs.data(), sizeof(BwdJob) * jobs.size(), hipMemcpyHostToDevice));
   if (n == 76 && m == 38 && cbx == 1) {
@@ -762,8 +771,18 @@ void bwd_teardown(ddp_hip_ctx* ctx) {
   if (ctx->jobs_half_d) (void)hipFree(ctx->jobs_half_d);
 }
 
+// The sweep's LDS against the 160 KB of a gfx950 workgroup, on the host: bwd_gains holds Q_uu, [k | K] and Q_ux, which fits up to
+// nv = 63 (57 with control bounds: the box QP's second copy of Q_uu).  The Talos shape's own kernels are sized at compile time
+int bwd_lds_check(const ddp_hip_ctx* ctx) {
+  if (sweep_plan(ctx).fast) return DDP_HIP_OK;
+  const int cn_max = ctx->cbx > ctx->cbu ? ctx->cbx : ctx->cbu;
+  if (assemble_lds_bytes(ctx, cn_max) > 160 * 1024 || gains_lds_bytes(ctx) > 160 * 1024) return DDP_HIP_E_UNSUPPORTED;
+  return DDP_HIP_OK;
+}
+
 extern "C" int ddp_hip_backward(ddp_hip_ctx* ctx, double* reg_io, double* mu_io, int64_t* restarts_out, int64_t max_restarts) {
   if (!ctx || !reg_io || !mu_io) return DDP_HIP_E_ARG;
+  { const int rc_ = bwd_lds_check(ctx); if (rc_ != DDP_HIP_OK) return rc_; }   // (ahead of the first launch, copy or conversion of the tensors)
   const Dims& d = ctx->d;
   const int64_t B = d.batch;
   HIP_TRY(hipSetDevice(ctx->device));
@@ -792,7 +811,6 @@ extern "C" int ddp_hip_backward(ddp_hip_ctx* ctx, double* reg_io, double* mu_io,
   const int cn_max = ctx->cbx > ctx->cbu ? ctx->cbx : ctx->cbu;
   const size_t lds_a = assemble_lds_bytes(ctx, cn_max);
   const size_t lds_g = gains_lds_bytes(ctx);
-  if (lds_a > 160 * 1024 || lds_g > 160 * 1024) return DDP_HIP_E_UNSUPPORTED;
 
   bool any_restart = false;
   int rc = DDP_HIP_OK;

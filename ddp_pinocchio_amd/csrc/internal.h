@@ -286,6 +286,7 @@ void prof_end(ddp_hip_ctx* ctx, int kid, hipStream_t stream = nullptr);
 int bwd_setup(ddp_hip_ctx* ctx);
 SweepPlan sweep_plan(const ddp_hip_ctx* ctx);
 void bwd_teardown(ddp_hip_ctx* ctx);
+int bwd_lds_check(const ddp_hip_ctx* ctx);       // DDP_HIP_E_UNSUPPORTED if the sweep's kernels need more LDS than a workgroup has (nv = 64; with control bounds nv >= 58)
 int box_check(ddp_hip_ctx* ctx);                  // control bounds: DDP_HIP_E_ARG if an upload left some lo > hi (ctx.hip)
 int fwd_setup(ddp_hip_ctx* ctx);
 bool fwd_lat_supported(const ddp_hip_ctx* ctx);   // the latency kernels of the forward sweep apply (tree, no constraints, Talos size)

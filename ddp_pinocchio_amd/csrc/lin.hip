@@ -1437,6 +1437,12 @@ int lin_setup(ddp_hip_ctx* ctx) {
   }
   { const int rc_ = lin_analytic_setup(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
   if (pl.ws_eq) HIP_TRY(hipMalloc(&ctx->eq_ws, sizeof(double) * (size_t)pl.eq_words));   // look-ahead states / jacobians of the constraint chain
+  if (pl.eq == LinEq::Chain) {
+    // eq_combine_kernel keeps two e x n matrices in LDS: past the default 64 KB of dynamic LDS with a config constraint from nv = 46 on
+    // (128 KB at nv = 64: it always fits the workgroup's 160 KB)
+    const size_t lds = sizeof(double) * (size_t)(2 * d.emax * d.n);
+    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&eq_combine_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
   return DDP_HIP_OK;
 }
 void lin_teardown(ddp_hip_ctx* ctx) {

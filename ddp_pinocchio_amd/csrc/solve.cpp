@@ -33,6 +33,7 @@ extern "C" int ddp_hip_solve(ddp_hip_ctx* ctx, const ddp_hip_solver_params* sp, 
     if (rc > 0) ev |= rc;                                        \
   } while (0)
 
+  SOLVE_TRY(bwd_lds_check(ctx));   // a size the sweep refuses: refused here, ahead of the first linearisation
   SOLVE_TRY(ddp_hip_set_active(ctx, nullptr));
   // the loop enqueues: only the calls that return values to the rules below wait for the device (ddp_hip_set_async)
   SOLVE_TRY(ddp_hip_set_async(ctx, ctx->sw.solve_sync ? 0 : 1));   // (DDP_HIP_SOLVE_SYNC: development A/B, every call waits as in round 2)

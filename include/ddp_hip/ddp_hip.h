@@ -387,7 +387,9 @@ int ddp_hip_linearize_stages(ddp_hip_ctx* ctx, uint32_t stages);
 
 /* backward_pass<primal_dual_affine_multipliers> (ddp_bwd.ipp:9-155).
  * reg_io / mu_io: host arrays [batch], in-out (ddp_bwd.ipp:106-110,154); restarts_out: host [batch] or NULL.
- * max_restarts bounds the reference's unbounded while(!success). */
+ * max_restarts bounds the reference's unbounded while(!success).
+ * DDP_HIP_E_UNSUPPORTED, ahead of any launch, where the sweep's kernels need more LDS than a workgroup has: 64 joints, or 58
+ * and more with DDP_HIP_FLAG_CONTROL_BOUNDS (ddp_hip_solve answers the same way). */
 int ddp_hip_backward(ddp_hip_ctx* ctx, double* reg_io, double* mu_io, int64_t* restarts_out, int64_t max_restarts);
 
 /* forward_pass (ddp_fwd.ipp:9-67) with the step halving evaluated n_alpha candidates at a time:

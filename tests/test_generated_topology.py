@@ -9,11 +9,10 @@ import sys
 import numpy as np
 import pytest
 
+from robots import ARM7, BIPED12, TREE44, seeded_tree   # (the trees and the seeded robot on them live in the catalogue now)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GEN = os.path.join(ROOT, "tools", "gen_topology.py")
-
-ARM7 = [-1, 0, 1, 2, 3, 4, 5]
-BIPED12 = [-1, 0, 1, 2, 3, 4, 5, 0, 7, 8, 9, 10]
 
 
 def test_generated_header_is_in_sync_and_lists_the_shipped_topologies():
@@ -41,28 +40,6 @@ def test_generator_reads_a_urdf(tmp_path):
     assert parents == [-1, 0, 1] and prismatic == [0, 1, 0]
     text = gen_topology.render([{"name": "X3", "parents": parents, "prismatic": prismatic, "source": "arm.urdf"}])
     assert "struct TopoX3" in text and "parent[N] = {-1, 0, 1}" in text and "X(4, TopoX3)" in text
-
-
-def seeded_tree(parents, seed):
-    """a random robot on a given tree: revolute joints, random axes / placements / inertias"""
-    from ddp_pinocchio_amd import capi
-    rng = np.random.default_rng(seed)
-    nv = len(parents)
-    axis = rng.normal(size=(nv, 3)); axis /= np.linalg.norm(axis, axis=1, keepdims=True)
-    Rp = np.stack([np.linalg.qr(rng.normal(size=(3, 3)))[0] for _ in range(nv)])
-    for k in range(nv):
-        if np.linalg.det(Rp[k]) < 0:
-            Rp[k][:, 0] = -Rp[k][:, 0]
-    pp = rng.uniform(0.05, 0.3, size=(nv, 3)) * rng.choice([-1.0, 1.0], size=(nv, 3))
-    mass = rng.uniform(0.5, 5.0, size=nv)
-    com = rng.uniform(-0.05, 0.05, size=(nv, 3))
-    Ic = np.zeros((nv, 3, 3))
-    for k in range(nv):
-        a = rng.uniform(0.05, 0.3, size=3)                  # a box with these half sizes
-        Ic[k] = np.diag(mass[k] / 3.0 * np.array([a[1] ** 2 + a[2] ** 2, a[0] ** 2 + a[2] ** 2, a[0] ** 2 + a[1] ** 2]))
-        Q = np.linalg.qr(rng.normal(size=(3, 3)))[0]
-        Ic[k] = Q @ Ic[k] @ Q.T
-    return capi.TableModel(parents, [capi.JOINT_REVOLUTE] * nv, axis, Rp, pp, mass, com, Ic)
 
 
 @pytest.mark.gpu
@@ -108,10 +85,6 @@ def test_generated_topology_takes_the_static_kernels_and_matches_the_oracle(gpu,
             assert float(np.max(np.abs(got[key][b] - ref))) <= tol, (key, b)
             # ... and so do the run-time-tree kernels (the A/B partner of the static path), i.e. the two agree within FD noise
             assert float(np.max(np.abs(got_g[key][b] - ref))) <= tol, (key, b, "generic")
-
-
-TREE44 = [-1, 0, 1, 2, 3, 4] + [5, 6, 7, 8, 9, 10] + [5, 12, 13, 14, 15, 16] + [5, 18] + [19, 20, 21, 22, 23, 24, 25] + \
-         [19, 27, 28, 29, 30, 31, 32] + [19, 34] + [26, 36, 37] + [33, 39, 40] + [35, 42]
 
 
 @pytest.mark.gpu
