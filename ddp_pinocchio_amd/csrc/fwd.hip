@@ -421,7 +421,7 @@ __device__ __forceinline__ double limit_lanes_sum(const FwdParams& p, int b, int
 template <int NJ>
 struct FwdLat2Lds {
   static constexpr int NC = 4, NH = 16, n = 2 * NJ + 1, nu = NJ;   // n: room for the state of a free-flyer model (nq = nv + 1)
-  double state[rbd::ABA_LDS_SLOTS2 * (NJ + NJ / 8) * NC];      // (+ NJ / 8: the bank skew of rbd::aba_tree_coop2w)
+  double state[rbd::ABA_LDS_SLOTS * (NJ + NJ / 8) * NC];       // (+ NJ / 8: the bank skew of rbd::aba_tree_coop2w)
   double K[nu * n];
   double k[nu], uo[nu], xo[n];
   double dx[NC * n], x[NC * n], u[NC * nu], qdd[NC * nu];

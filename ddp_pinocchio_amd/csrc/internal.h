@@ -32,7 +32,8 @@ struct DevModel {
   int32_t slot_up[DDP_MAXJ];        // slot of the joint's accumulator in the leaf->root pass (-1: leaf)
   int32_t slot_down[DDP_MAXJ];      // slot of the joint's value in the root->leaf pass (-1: leaf)
   int32_t n_slots;
-  // level schedule for the wave-cooperative traversals (rbd.h: aba_tree_coop): joints sorted by tree depth
+  // level schedule for the wave-cooperative traversals: joints sorted by tree depth (rbd.h: aba_tree_coop walks these tables; the
+  // forward kernel's traversals read them packed into one role word per lane and level, CoopModel::role)
   int32_t n_levels, max_level_width;
   int32_t lvl_start[DDP_MAXJ + 1];  // joints of level L are lvl_joint[lvl_start[L] .. lvl_start[L+1])
   int32_t lvl_joint[DDP_MAXJ];

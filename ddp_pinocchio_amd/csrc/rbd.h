@@ -544,139 +544,6 @@ __device__ void eval_f_cached(const DevModel& m, const double* __restrict__ qc, 
 
 }  // namespace rbd
 
-// ---- latency-oriented variant: per-evaluation state in LDS instead of scratch ------------------------------------
-// The closed-loop rollouts of the forward sweep are a few hundred sequential chains: too few lanes to hide the
-// latency of scratch (private HBM-backed) arrays.  Here the per-joint state of one evaluation lives in LDS,
-// interleaved over the TPB lanes of the workgroup ([slot][lane], conflict free); same arithmetic as aba_tree.
-namespace rbd {
-
-constexpr int ABA_LDS_SLOTS = 59;   // per joint: E 9 | r 3 | cb 6 | pA 6 | IA 21 | U 6 | Dinv 1 | uu 1 | vel/acc 6
-
-template <int NJ, int TPB>
-__device__ void aba_tree_lds(const DevModel& m, const double* q, const double* v, const double* tau, double* qdd,
-                             double* st, int lane) {
-  const int N = m.nv;
-  auto S = [&](int joint, int slot) -> double& { return st[(joint * ABA_LDS_SLOTS + slot) * TPB + lane]; };
-  constexpr int oE = 0, oR = 9, oC = 12, oP = 18, oI = 24, oU = 45, oD = 51, oT = 52, oV = 53;
-  for (int i = 0; i < N; ++i) {
-    double E[9], R[3], vel[6], vp[6], cb[6], pA[6], Iv[6], I6[21];
-    joint_placement(m, i, q[i], E, R);
-    const double* a = m.axis[i];
-    double vJ[6] = {0, 0, 0, 0, 0, 0};
-    const int o = m.jtype[i] == DDP_HIP_JOINT_REVOLUTE ? 0 : 3;
-    vJ[o] = a[0] * v[i]; vJ[o + 1] = a[1] * v[i]; vJ[o + 2] = a[2] * v[i];
-    const int par = m.parent[i];
-    if (par >= 0) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) vp[k] = S(par, oV + k);
-      xform_motion(E, R, vp, vel);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) vel[k] = 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) vel[k] += vJ[k];
-    crm(vel, vJ, cb);
-#pragma unroll
-    for (int k = 0; k < 21; ++k) I6[k] = m.I6[i][k];
-    sym6_mv(I6, vel, Iv);
-    crf(vel, Iv, pA);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) S(i, oE + k) = E[k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) S(i, oR + k) = R[k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) { S(i, oV + k) = vel[k]; S(i, oC + k) = cb[k]; S(i, oP + k) = pA[k]; }
-#pragma unroll
-    for (int k = 0; k < 21; ++k) S(i, oI + k) = I6[k];
-  }
-  for (int i = N - 1; i >= 0; --i) {
-    const double* a = m.axis[i];
-    const int o = m.jtype[i] == DDP_HIP_JOINT_REVOLUTE ? 0 : 3;
-    double IA[21], U[6], pAi[6], cb[6];
-#pragma unroll
-    for (int k = 0; k < 21; ++k) IA[k] = S(i, oI + k);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) { pAi[k] = S(i, oP + k); cb[k] = S(i, oC + k); }
-    double d = 0, sp = 0;
-#pragma unroll
-    for (int r = 0; r < 6; ++r) U[r] = IA[sidx(r, o)] * a[0] + IA[sidx(r, o + 1)] * a[1] + IA[sidx(r, o + 2)] * a[2];
-    for (int k = 0; k < 3; ++k) { d += a[k] * U[o + k]; sp += a[k] * pAi[o + k]; }
-    const double dinv = 1.0 / d;
-    const double ui = tau[i] - sp;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) S(i, oU + k) = U[k];
-    S(i, oD) = dinv;
-    S(i, oT) = ui;
-    const int par = m.parent[i];
-    if (par >= 0) {
-      double E[9], R[3], Ia[21], pa[6], Iac[6], fp[6], IAp[21];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) E[k] = S(i, oE + k);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) R[k] = S(i, oR + k);
-#pragma unroll
-      for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c <= r; ++c) Ia[sidx(r, c)] = IA[sidx(r, c)] - U[r] * U[c] * dinv;
-      sym6_mv(Ia, cb, Iac);
-#pragma unroll
-      for (int k = 0; k < 6; ++k) pa[k] = pAi[k] + Iac[k] + U[k] * (ui * dinv);
-#pragma unroll
-      for (int k = 0; k < 21; ++k) IAp[k] = S(par, oI + k);
-      add_xtix(E, R, Ia, IAp);
-#pragma unroll
-      for (int k = 0; k < 21; ++k) S(par, oI + k) = IAp[k];
-      xform_force_T(E, R, pa, fp);
-#pragma unroll
-      for (int k = 0; k < 6; ++k) S(par, oP + k) += fp[k];
-    }
-  }
-  for (int i = 0; i < N; ++i) {
-    double E[9], R[3], ap[6], accp[6], U[6], cb[6];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) E[k] = S(i, oE + k);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) R[k] = S(i, oR + k);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) { U[k] = S(i, oU + k); cb[k] = S(i, oC + k); }
-    const int par = m.parent[i];
-    if (par >= 0) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) accp[k] = S(par, oV + k);
-      xform_motion(E, R, accp, ap);
-    } else {
-      const double a0[6] = {0, 0, 0, -m.gravity[0], -m.gravity[1], -m.gravity[2]};
-      xform_motion(E, R, a0, ap);
-    }
-    double s = 0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) { ap[k] += cb[k]; s += U[k] * ap[k]; }
-    const double qd = (S(i, oT) - s) * S(i, oD);
-    qdd[i] = qd;
-    const double* a = m.axis[i];
-    const int o = m.jtype[i] == DDP_HIP_JOINT_REVOLUTE ? 0 : 3;
-    ap[o] += a[0] * qd; ap[o + 1] += a[1] * qd; ap[o + 2] += a[2] * qd;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) S(i, oV + k) = ap[k];
-  }
-}
-
-template <int NJ, int TPB>
-__device__ void eval_f_lds(const DevModel& m, const double* x, const double* u, double* x_out, double* st, int lane) {
-  const int nv = m.nv;
-  if (m.kind == DDP_HIP_MODEL_PENDULUM) { eval_f<NJ>(m, x, u, x_out); return; }
-  double acc[NJ];
-  aba_tree_lds<NJ, TPB>(m, x, x + nv, u, acc, st, lane);
-  for (int i = 0; i < nv; ++i) {
-    const double vo = m.dt * x[nv + i];
-    x_out[i] = x[i] + vo;
-    x_out[nv + i] = x[nv + i] + acc[i] * m.dt;
-  }
-}
-
-}  // namespace rbd
-
 // ---- second level of the split: what depends on (q, v) but not on tau ---------------------------------------------
 namespace rbd {
 
@@ -789,9 +656,10 @@ __device__ void eval_f_ucached(const DevModel& m, const double* __restrict__ qc,
 
 // ---- wave-cooperative variant: the lanes of one evaluation walk the tree level by level -----------------------------
 // NH lanes share one evaluation; in every round lane h takes the h-th joint of the current tree level (the branches of a
-// humanoid advance side by side: 16 rounds per pass instead of 38 joints).  State as in aba_tree_lds ([slot][candidate]
-// in LDS).  A child leaves its contribution to the parent (X^T Ia X, X^T pa) in its own slots; the parent adds its
-// children's contributions in descending index order, i.e. in exactly the order of the sequential loop.
+// humanoid advance side by side: 16 rounds per pass instead of 38 joints).  The per-joint state of one evaluation lives in LDS,
+// interleaved over the candidates of the workgroup ([slot][candidate], conflict free): too few chains run side by side to hide
+// the latency of scratch arrays.  A child leaves its contribution to the parent (X^T Ia X, X^T pa) in its own slots; the parent
+// adds its children's contributions in descending index order, i.e. in exactly the order of the sequential loop.
 // Must be called by all lanes of the workgroup (it contains workgroup barriers); q, v, tau, qdd live in LDS.
 namespace rbd {
 
@@ -852,6 +720,158 @@ struct FwdStamp {
 #define FSTAMP(fs, i) do { } while (0)
 #endif
 
+// ---- the joint steps of the cooperative traversals ------------------------------------------------------------------------
+// The arithmetic of one joint in one pass, written once for aba_tree_coop, aba_tree_coop2w, aba_pipe_q and aba_pipe_x: the
+// operations of aba_tree in their order.  A step works on register arrays; it knows nothing of where a traversal keeps a joint's
+// numbers, of lanes, waves or exchange points.  A traversal is then its storage, its schedule and its fences, and the body of a
+// level is: load the operands, call the step, store the results.  A change to the joint arithmetic is made here, once, and
+// reaches every traversal; that they agree bit for bit (tests/test_fwd_pipeline.py) follows from the text.
+// FF / ff_root: joint 0 is a free-flyer root (SE(3); q = [p, quaternion x y z w | joint angles], v = [linear, angular | joint
+// rates] in the body frame): S = identity on the body twist; joint i >= 1 reads q[i + 6], v[i + 5].
+
+// placement E | r of joint i from the configuration vector; the free-flyer root as in rbd::place: E = R(quaternion)^T, r = p
+template <bool FF, class M>
+__device__ __forceinline__ void step_place(const M& m, int i, const double* q, double* E, double* r) {
+  if (FF && i == 0) {
+    double Rq[9];
+    lie::quat_to_R(q + 3, Rq);
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int l = 0; l < 3; ++l) E[3 * k + l] = Rq[3 * l + k];
+    r[0] = q[0]; r[1] = q[1]; r[2] = q[2];
+  } else {
+    joint_placement(m, i, q[FF ? i + 6 : i], E, r);
+  }
+}
+
+// pass 1: the joint's velocity vel from its parent's (vp; a root has none), the velocity product cb = vel x vJ and the bias
+// force pA = vel x* (I6 vel).  vi: the joint's own rate; the six of a free-flyer root, [linear; angular]
+__device__ __forceinline__ void step_velocity(const double* E, const double* r, const double* a, bool rev, bool ff_root,
+                                              const double* vi, bool has_parent, const double* vp, const double* I6,
+                                              double* vel, double* cb, double* pA) {
+  double vJ[6] = {0, 0, 0, 0, 0, 0}, Iv[6];
+  const int o = rev ? 0 : 3;
+  if (ff_root) { vJ[0] = vi[3]; vJ[1] = vi[4]; vJ[2] = vi[5]; vJ[3] = vi[0]; vJ[4] = vi[1]; vJ[5] = vi[2]; }
+  else { const double w = vi[0]; vJ[o] = a[0] * w; vJ[o + 1] = a[1] * w; vJ[o + 2] = a[2] * w; }
+  if (has_parent) {
+    xform_motion(E, r, vp, vel);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) vel[k] = 0.0;
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) vel[k] += vJ[k];
+  crm(vel, vJ, cb);
+  sym6_mv(I6, vel, Iv);
+  crf(vel, Iv, pA);
+}
+
+// acc[0 .. W) += the contributions of the children named in role word rr, descending child index; contrib(c, k): word k of child c's
+template <int W, class F>
+__device__ __forceinline__ void step_add_children(unsigned long long rr, double* acc, F contrib) {
+  const int nch = role_nchildren(rr);
+#pragma unroll
+  for (int ci = 0; ci < ROLE_MAX_CHILDREN; ++ci) {
+    if (ci < nch) {
+      const int c = role_child(rr, ci);
+#pragma unroll
+      for (int k = 0; k < W; ++k) acc[k] += contrib(c, k);
+    }
+  }
+}
+
+// U = IA S for the 1-DoF joint along a (S = [a; 0] revolute, [0; a] prismatic); returns 1 / D, D = S^T U.
+// rev is per lane: static indices under a select (dynamic ones would put IA in scratch: a store / load round trip per level)
+__device__ __forceinline__ double step_U(const double* IA, const double* a, bool rev, double* U) {
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    const double i0 = rev ? IA[sidx(r, 0)] : IA[sidx(r, 3)];
+    const double i1 = rev ? IA[sidx(r, 1)] : IA[sidx(r, 4)];
+    const double i2 = rev ? IA[sidx(r, 2)] : IA[sidx(r, 5)];
+    U[r] = i0 * a[0] + i1 * a[1] + i2 * a[2];
+  }
+  double d = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) d += a[k] * (rev ? U[k] : U[3 + k]);
+  return 1.0 / d;
+}
+
+// Ia = IA - U U^T / D
+__device__ __forceinline__ void step_Ia(const double* IA, const double* U, double dinv, double* Ia) {
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = 0; c <= r; ++c) Ia[sidx(r, c)] = IA[sidx(r, c)] - U[r] * U[c] * dinv;
+}
+
+// the joint's contribution to its parent's articulated inertia: Z = X^T Ia X
+__device__ __forceinline__ void step_inertia_up(const double* E, const double* r, const double* Ia, double* Z) {
+#pragma unroll
+  for (int k = 0; k < 21; ++k) Z[k] = 0.0;
+  add_xtix(E, r, Ia, Z);
+}
+
+// u = tau - S^T pA  (pA: the joint's bias force with its children's contributions)
+__device__ __forceinline__ double step_u(const double* pAi, const double* a, bool rev, double tau) {
+  double sp = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) sp += a[k] * (rev ? pAi[k] : pAi[3 + k]);
+  return tau - sp;
+}
+
+// the joint's contribution to its parent's bias force: fp = X^T (pA + Ia cb + U u / D)
+__device__ __forceinline__ void step_force_up(const double* E, const double* r, const double* pAi, const double* cb, const double* U,
+                                              double dinv, double ui, const double* Ia, double* fp) {
+  double pa[6], Iac[6];
+  sym6_mv(Ia, cb, Iac);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) pa[k] = pAi[k] + Iac[k] + U[k] * (ui * dinv);
+  xform_force_T(E, r, pa, fp);
+}
+
+// pass 3 in three steps.  First: ap = the parent's acceleration accp (at a root: that of gravity) in the joint's frame
+__device__ __forceinline__ void step_accel_in(const double* E, const double* r, bool has_parent, const double* accp, const double* g,
+                                              double* ap) {
+  if (has_parent) {
+    xform_motion(E, r, accp, ap);
+  } else {
+    const double a0[6] = {0, 0, 0, -g[0], -g[1], -g[2]};
+    xform_motion(E, r, a0, ap);
+  }
+}
+// then a 1-DoF joint: returns qdd = (u - U^T (ap + cb)) / D and leaves the joint's own acceleration in ap
+__device__ __forceinline__ double step_accel(const double* U, const double* cb, double ui, double dinv, const double* a, bool rev, double* ap) {
+  double s = 0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { ap[k] += cb[k]; s += U[k] * ap[k]; }
+  const double qd = (ui - s) * dinv;
+  const int o = rev ? 0 : 3;
+  ap[o] += a[0] * qd; ap[o + 1] += a[1] * qd; ap[o + 2] += a[2] * qd;
+  return qd;
+}
+// or the free-flyer root, S = I: qdd_s = IA^-1 (tau_s - pA) - a' in the spatial ordering [angular; linear]; tau / qdd (six each)
+// are ordered [linear; angular].  IAr, pAr: its articulated inertia and bias force with the children's contributions
+__device__ __forceinline__ void step_accel_ff_root(const double* IAr, const double* pAr, const double* tau, const double* cb, double* ap,
+                                                   double* qdd) {
+  double rhs[6], qs[6];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { rhs[k] = tau[3 + k] - pAr[k]; rhs[3 + k] = tau[k] - pAr[3 + k]; }
+  sym6_solve(IAr, rhs, qs);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { ap[k] += cb[k]; qs[k] -= ap[k]; }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { qdd[k] = qs[3 + k]; qdd[3 + k] = qs[k]; }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) ap[k] = ap[k] + qs[k];
+}
+
+// ---- one wave or one workgroup, level tables (lin_analytic.hip) -------------------------------------------------------------
+constexpr int ABA_LDS_SLOTS = 59;   // per joint: E 9 | r 3 | cb 6 | pA 6 | IA 21 (aba_tree_coop2w: the contribution X^T Ia X) | U 6 | Dinv 1 | uu 1 | vel/acc 6
+
+// Built from step_place, step_velocity, step_U, step_u, step_Ia, step_inertia_up, step_force_up, step_accel_in and step_accel.
+// A lane finds its joint and its children in the level tables (lvl_start / lvl_joint / child_list), not in a role word, so the
+// children's sum is this traversal's own loop: IA and pA together, the same descending order.
 template <int NJ, int TPB, int NH, bool WAVE_SYNC = false, class M = DevModel>
 __device__ void aba_tree_coop(const M& m, const double* q, const double* v, const double* tau, double* qdd,
                               double* st, int cand, int h, bool live, FwdStamp* fs = nullptr) {
@@ -862,7 +882,7 @@ __device__ void aba_tree_coop(const M& m, const double* q, const double* v, cons
   if (live)
     for (int i = h; i < m.nv; i += NH) {
       double E[9], R[3];
-      joint_placement(m, i, q[i], E, R);
+      step_place<false>(m, i, q, E, R);
 #pragma unroll
       for (int k = 0; k < 9; ++k) S(i, oE + k) = E[k];
 #pragma unroll
@@ -874,31 +894,19 @@ __device__ void aba_tree_coop(const M& m, const double* q, const double* v, cons
     const int idx = m.lvl_start[L] + h;
     if (live && idx < m.lvl_start[L + 1]) {
       const int i = m.lvl_joint[idx];
-      double E[9], R[3], vel[6], vp[6], cb[6], pA[6], Iv[6], I6[21];
+      double E[9], R[3], vel[6], vp[6], cb[6], pA[6], I6[21];
 #pragma unroll
       for (int k = 0; k < 9; ++k) E[k] = S(i, oE + k);
 #pragma unroll
       for (int k = 0; k < 3; ++k) R[k] = S(i, oR + k);
-      const double* a = m.axis[i];
-      double vJ[6] = {0, 0, 0, 0, 0, 0};
-      const int o = m.jtype[i] == DDP_HIP_JOINT_REVOLUTE ? 0 : 3;
-      vJ[o] = a[0] * v[i]; vJ[o + 1] = a[1] * v[i]; vJ[o + 2] = a[2] * v[i];
       const int par = m.parent[i];
       if (par >= 0) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) vp[k] = S(par, oV + k);
-        xform_motion(E, R, vp, vel);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) vel[k] = 0.0;
       }
 #pragma unroll
-      for (int k = 0; k < 6; ++k) vel[k] += vJ[k];
-      crm(vel, vJ, cb);
-#pragma unroll
       for (int k = 0; k < 21; ++k) I6[k] = m.I6[i][k];
-      sym6_mv(I6, vel, Iv);
-      crf(vel, Iv, pA);
+      step_velocity(E, R, m.axis[i], m.jtype[i] == DDP_HIP_JOINT_REVOLUTE, false, v + i, par >= 0, vp, I6, vel, cb, pA);
 #pragma unroll
       for (int k = 0; k < 6; ++k) { S(i, oV + k) = vel[k]; S(i, oC + k) = cb[k]; S(i, oP + k) = pA[k]; }
 #pragma unroll
@@ -912,7 +920,7 @@ __device__ void aba_tree_coop(const M& m, const double* q, const double* v, cons
     if (live && idx < m.lvl_start[L + 1]) {
       const int i = m.lvl_joint[idx];
       const double* a = m.axis[i];
-      const int o = m.jtype[i] == DDP_HIP_JOINT_REVOLUTE ? 0 : 3;
+      const bool rev = m.jtype[i] == DDP_HIP_JOINT_REVOLUTE;
       double IA[21], U[6], pAi[6], cb[6];
 #pragma unroll
       for (int k = 0; k < 21; ++k) IA[k] = S(i, oI + k);
@@ -925,48 +933,23 @@ __device__ void aba_tree_coop(const M& m, const double* q, const double* v, cons
 #pragma unroll
         for (int k = 0; k < 6; ++k) pAi[k] += S(c, oP + k);
       }
-      double d = 0, sp = 0;
-      // o is per lane: static indices under a select (dynamic ones would put IA in scratch: a store / load round trip per level)
-      const bool rev = o == 0;
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        const double i0 = rev ? IA[sidx(r, 0)] : IA[sidx(r, 3)];
-        const double i1 = rev ? IA[sidx(r, 1)] : IA[sidx(r, 4)];
-        const double i2 = rev ? IA[sidx(r, 2)] : IA[sidx(r, 5)];
-        U[r] = i0 * a[0] + i1 * a[1] + i2 * a[2];
-      }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const double Uk = rev ? U[k] : U[3 + k];
-        const double pk = rev ? pAi[k] : pAi[3 + k];
-        d += a[k] * Uk;
-        sp += a[k] * pk;
-      }
-      const double dinv = 1.0 / d;
-      const double ui = tau[i] - sp;
+      const double dinv = step_U(IA, a, rev, U);
+      const double ui = step_u(pAi, a, rev, tau[i]);
 #pragma unroll
       for (int k = 0; k < 6; ++k) S(i, oU + k) = U[k];
       S(i, oD) = dinv;
       S(i, oT) = ui;
       if (m.parent[i] >= 0) {
-        double E[9], R[3], Ia[21], pa[6], Iac[6], fp[6], Z[21];
+        double E[9], R[3], Ia[21], fp[6], Z[21];
 #pragma unroll
         for (int k = 0; k < 9; ++k) E[k] = S(i, oE + k);
 #pragma unroll
         for (int k = 0; k < 3; ++k) R[k] = S(i, oR + k);
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-          for (int c = 0; c <= r; ++c) Ia[sidx(r, c)] = IA[sidx(r, c)] - U[r] * U[c] * dinv;
-        sym6_mv(Ia, cb, Iac);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) pa[k] = pAi[k] + Iac[k] + U[k] * (ui * dinv);
-#pragma unroll
-        for (int k = 0; k < 21; ++k) Z[k] = 0.0;
-        add_xtix(E, R, Ia, Z);                    // this joint's contribution to its parent, left in its own slots
+        step_Ia(IA, U, dinv, Ia);
+        step_force_up(E, R, pAi, cb, U, dinv, ui, Ia, fp);
+        step_inertia_up(E, R, Ia, Z);               // this joint's contributions to its parent, left in its own slots
 #pragma unroll
         for (int k = 0; k < 21; ++k) S(i, oI + k) = Z[k];
-        xform_force_T(E, R, pa, fp);
 #pragma unroll
         for (int k = 0; k < 6; ++k) S(i, oP + k) = fp[k];
       }
@@ -989,19 +972,9 @@ __device__ void aba_tree_coop(const M& m, const double* q, const double* v, cons
       if (par >= 0) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) accp[k] = S(par, oV + k);
-        xform_motion(E, R, accp, ap);
-      } else {
-        const double a0[6] = {0, 0, 0, -m.gravity[0], -m.gravity[1], -m.gravity[2]};
-        xform_motion(E, R, a0, ap);
       }
-      double s = 0;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) { ap[k] += cb[k]; s += U[k] * ap[k]; }
-      const double qd = (S(i, oT) - s) * S(i, oD);
-      qdd[i] = qd;
-      const double* a = m.axis[i];
-      const int o = m.jtype[i] == DDP_HIP_JOINT_REVOLUTE ? 0 : 3;
-      ap[o] += a[0] * qd; ap[o + 1] += a[1] * qd; ap[o + 2] += a[2] * qd;
+      step_accel_in(E, R, par >= 0, accp, m.gravity, ap);
+      qdd[i] = step_accel(U, cb, S(i, oT), S(i, oD), m.axis[i], m.jtype[i] == DDP_HIP_JOINT_REVOLUTE, ap);
 #pragma unroll
       for (int k = 0; k < 6; ++k) S(i, oV + k) = ap[k];
     }
@@ -1017,22 +990,20 @@ __device__ void aba_tree_coop(const M& m, const double* q, const double* v, cons
 // wave of the workgroup forms X^T Ia X while the first does the force half; both recompute the short common prefix (children's
 // sums, U, 1/D) so that neither waits for the other inside a level; one workgroup barrier per level.  The joint's own inertia
 // is read from the model table (not from a per-candidate copy), so the slots the second wave writes its contribution to (oZ) are
-// read by nobody before the level's barrier.  Every entry is formed by the same operations in the same order as in aba_tree_coop.
-constexpr int ABA_LDS_SLOTS2 = ABA_LDS_SLOTS;   // same record: the joint's own inertia now comes from the model table, its 21 slots hold the contribution
+// read by nobody before the level's barrier.  Built from the same steps as aba_tree_coop, plus step_add_children and, for the
+// free-flyer root (FF), step_accel_ff_root: wave 0 calls step_u / step_force_up, wave 1 step_inertia_up, both step_U and step_Ia.
 __device__ __forceinline__ void wg_sync_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// FF: joint 0 is a free-flyer root (SE(3); q = [p, quaternion x y z w | joint angles], v = [linear, angular | joint rates] in the
-// body frame): S = identity on the body twist, its 6 x 6 articulated inertia is solved in registers (sym6_solve) -- the
-// operations of aba_tree's free-flyer branches, in their order; joint i >= 1 reads q[i + 6], v[i + 5]
 template <int NJ, int TPB, int NH, class M, bool FF = false>
 __device__ __forceinline__ void aba_tree_coop2w(const M& m, const double* q, const double* v, const double* tau, double* qdd,
                                 double* st, int cand, int h, bool live, int wave, FwdStamp* fs = nullptr) {
   const int nj = FF ? m.nv - 5 : m.nv;
-  auto QI = [](int i) { return FF ? i + 6 : i; };
   auto VI = [](int i) { return FF ? i + 5 : i; };
   // joints eight apart (the two arms and the head of a humanoid advance side by side) would share LDS banks: skew the records
-  auto S = [&](int joint, int slot) -> double& { return st[((joint + (joint >> 3)) * ABA_LDS_SLOTS2 + slot) * TPB + cand]; };
+  auto S = [&](int joint, int slot) -> double& { return st[((joint + (joint >> 3)) * ABA_LDS_SLOTS + slot) * TPB + cand]; };
   constexpr int oE = 0, oR = 9, oC = 12, oP = 18, oZ = 24, oU = 45, oD = 51, oT = 52, oV = 53;
+  auto childZ = [&](int c, int k) { return S(c, oZ + k); };
+  auto childP = [&](int c, int k) { return S(c, oP + k); };
   const int NL = m.n_levels;
   // m.role[L * NH + h]: everything lane h needs to know about its joint of level L in one LDS word (coop_role): the level loops
   // otherwise walk lvl_start -> lvl_joint -> parent / child_start -> child_list, four dependent LDS round trips per level and pass
@@ -1040,17 +1011,7 @@ __device__ __forceinline__ void aba_tree_coop2w(const M& m, const double* q, con
     if (live)
       for (int i = h; i < nj; i += NH) {
         double E[9], R[3];
-        if (FF && i == 0) {                          // rbd::place: E = R(quaternion)^T, r = p
-          double Rq[9];
-          lie::quat_to_R(q + 3, Rq);
-#pragma unroll
-          for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int l = 0; l < 3; ++l) E[3 * k + l] = Rq[3 * l + k];
-          R[0] = q[0]; R[1] = q[1]; R[2] = q[2];
-        } else {
-          joint_placement(m, i, q[QI(i)], E, R);
-        }
+        step_place<FF>(m, i, q, E, R);
 #pragma unroll
         for (int k = 0; k < 9; ++k) S(i, oE + k) = E[k];
 #pragma unroll
@@ -1062,32 +1023,17 @@ __device__ __forceinline__ void aba_tree_coop2w(const M& m, const double* q, con
       const unsigned long long rr = m.role[L * NH + h];
       if (live && role_joint(rr) != 255) {
         const int i = role_joint(rr);
-        double E[9], R[3], vel[6], vp[6], cb[6], pA[6], Iv[6], I6[21];
+        double E[9], R[3], vel[6], vp[6], cb[6], pA[6];
 #pragma unroll
         for (int k = 0; k < 9; ++k) E[k] = S(i, oE + k);
 #pragma unroll
         for (int k = 0; k < 3; ++k) R[k] = S(i, oR + k);
-        const double* a = m.axis[i];
-        double vJ[6] = {0, 0, 0, 0, 0, 0};
-        const int o = role_rev(rr) ? 0 : 3;
-        if (FF && i == 0) { vJ[0] = v[3]; vJ[1] = v[4]; vJ[2] = v[5]; vJ[3] = v[0]; vJ[4] = v[1]; vJ[5] = v[2]; }   // S = identity on the body twist
-        else { const double vi = v[VI(i)]; vJ[o] = a[0] * vi; vJ[o + 1] = a[1] * vi; vJ[o + 2] = a[2] * vi; }
         const int par = role_parent(rr);
         if (par >= 0) {
 #pragma unroll
           for (int k = 0; k < 6; ++k) vp[k] = S(par, oV + k);
-          xform_motion(E, R, vp, vel);
-        } else {
-#pragma unroll
-          for (int k = 0; k < 6; ++k) vel[k] = 0.0;
         }
-#pragma unroll
-        for (int k = 0; k < 6; ++k) vel[k] += vJ[k];
-        crm(vel, vJ, cb);
-#pragma unroll
-        for (int k = 0; k < 21; ++k) I6[k] = m.I6[i][k];
-        sym6_mv(I6, vel, Iv);
-        crf(vel, Iv, pA);
+        step_velocity(E, R, m.axis[i], role_rev(rr), FF && i == 0, v + (FF && i == 0 ? 0 : VI(i)), par >= 0, vp, m.I6[i], vel, cb, pA);
 #pragma unroll
         for (int k = 0; k < 6; ++k) { S(i, oV + k) = vel[k]; S(i, oC + k) = cb[k]; S(i, oP + k) = pA[k]; }
       }
@@ -1102,18 +1048,10 @@ __device__ __forceinline__ void aba_tree_coop2w(const M& m, const double* q, con
       const int i = role_joint(rr);
       const double* a = m.axis[i];
       const bool rev = role_rev(rr);
-      const int nch = role_nchildren(rr);
       double IA[21], U[6];
 #pragma unroll
       for (int k = 0; k < 21; ++k) IA[k] = m.I6[i][k];
-#pragma unroll
-      for (int ci = 0; ci < ROLE_MAX_CHILDREN; ++ci) {   // contributions, descending child index
-        if (ci < nch) {
-          const int c = role_child(rr, ci);
-#pragma unroll
-          for (int k = 0; k < 21; ++k) IA[k] += S(c, oZ + k);
-        }
-      }
+      step_add_children<21>(rr, IA, childZ);
       FSTAMP(fs, 9);
       if (FF && i == 0) {
         // the free-flyer root is resolved in the last pass: its articulated inertia (wave 1) and bias force (wave 0) stay in
@@ -1122,14 +1060,7 @@ __device__ __forceinline__ void aba_tree_coop2w(const M& m, const double* q, con
           double pAi[6];
 #pragma unroll
           for (int k = 0; k < 6; ++k) pAi[k] = S(i, oP + k);
-#pragma unroll
-          for (int ci = 0; ci < ROLE_MAX_CHILDREN; ++ci) {
-            if (ci < nch) {
-              const int c = role_child(rr, ci);
-#pragma unroll
-              for (int k = 0; k < 6; ++k) pAi[k] += S(c, oP + k);
-            }
-          }
+          step_add_children<6>(rr, pAi, childP);
 #pragma unroll
           for (int k = 0; k < 6; ++k) S(i, oP + k) = pAi[k];
         } else {
@@ -1137,72 +1068,41 @@ __device__ __forceinline__ void aba_tree_coop2w(const M& m, const double* q, con
           for (int k = 0; k < 21; ++k) S(i, oZ + k) = IA[k];
         }
       } else {
+        const double dinv = step_U(IA, a, rev, U);
+        FSTAMP(fs, 10);
+        const bool has_parent = role_parent(rr) >= 0;
+        if (wave == 0) {
+          double pAi[6], cb[6];
 #pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        const double i0 = rev ? IA[sidx(r, 0)] : IA[sidx(r, 3)];
-        const double i1 = rev ? IA[sidx(r, 1)] : IA[sidx(r, 4)];
-        const double i2 = rev ? IA[sidx(r, 2)] : IA[sidx(r, 5)];
-        U[r] = i0 * a[0] + i1 * a[1] + i2 * a[2];
-      }
-      double d = 0;
+          for (int k = 0; k < 6; ++k) { pAi[k] = S(i, oP + k); cb[k] = S(i, oC + k); }
+          step_add_children<6>(rr, pAi, childP);
+          const double ui = step_u(pAi, a, rev, tau[VI(i)]);
 #pragma unroll
-      for (int k = 0; k < 3; ++k) d += a[k] * (rev ? U[k] : U[3 + k]);
-      const double dinv = 1.0 / d;
-      FSTAMP(fs, 10);
-      const bool has_parent = role_parent(rr) >= 0;
-      if (wave == 0) {
-        double pAi[6], cb[6];
+          for (int k = 0; k < 6; ++k) S(i, oU + k) = U[k];
+          S(i, oD) = dinv;
+          S(i, oT) = ui;
+          if (has_parent) {
+            double E[9], R[3], Ia[21], fp[6];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) { pAi[k] = S(i, oP + k); cb[k] = S(i, oC + k); }
+            for (int k = 0; k < 9; ++k) E[k] = S(i, oE + k);
 #pragma unroll
-        for (int ci = 0; ci < ROLE_MAX_CHILDREN; ++ci) {
-          if (ci < nch) {
-            const int c = role_child(rr, ci);
+            for (int k = 0; k < 3; ++k) R[k] = S(i, oR + k);
+            step_Ia(IA, U, dinv, Ia);
+            step_force_up(E, R, pAi, cb, U, dinv, ui, Ia, fp);
 #pragma unroll
-            for (int k = 0; k < 6; ++k) pAi[k] += S(c, oP + k);
+            for (int k = 0; k < 6; ++k) S(i, oP + k) = fp[k];
           }
-        }
-        double sp = 0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) sp += a[k] * (rev ? pAi[k] : pAi[3 + k]);
-        const double ui = tau[VI(i)] - sp;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) S(i, oU + k) = U[k];
-        S(i, oD) = dinv;
-        S(i, oT) = ui;
-        if (has_parent) {
-          double E[9], R[3], Ia[21], pa[6], Iac[6], fp[6];
+        } else if (has_parent) {
+          double E[9], R[3], Ia[21], Z[21];
 #pragma unroll
           for (int k = 0; k < 9; ++k) E[k] = S(i, oE + k);
 #pragma unroll
           for (int k = 0; k < 3; ++k) R[k] = S(i, oR + k);
+          step_Ia(IA, U, dinv, Ia);
+          step_inertia_up(E, R, Ia, Z);
 #pragma unroll
-          for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int c = 0; c <= r; ++c) Ia[sidx(r, c)] = IA[sidx(r, c)] - U[r] * U[c] * dinv;
-          sym6_mv(Ia, cb, Iac);
-#pragma unroll
-          for (int k = 0; k < 6; ++k) pa[k] = pAi[k] + Iac[k] + U[k] * (ui * dinv);
-          xform_force_T(E, R, pa, fp);
-#pragma unroll
-          for (int k = 0; k < 6; ++k) S(i, oP + k) = fp[k];
+          for (int k = 0; k < 21; ++k) S(i, oZ + k) = Z[k];
         }
-      } else if (has_parent) {
-        double E[9], R[3], Ia[21], Z[21];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) E[k] = S(i, oE + k);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) R[k] = S(i, oR + k);
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-          for (int c = 0; c <= r; ++c) Ia[sidx(r, c)] = IA[sidx(r, c)] - U[r] * U[c] * dinv;
-#pragma unroll
-        for (int k = 0; k < 21; ++k) Z[k] = 0.0;
-        add_xtix(E, R, Ia, Z);
-#pragma unroll
-        for (int k = 0; k < 21; ++k) S(i, oZ + k) = Z[k];
-      }
       }   // (not the free-flyer root)
     }
     FSTAMP(fs, 11);
@@ -1226,37 +1126,20 @@ __device__ __forceinline__ void aba_tree_coop2w(const M& m, const double* q, con
       if (par >= 0) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) accp[k] = S(par, oV + k);
-        xform_motion(E, R, accp, ap);
-      } else {
-        const double a0[6] = {0, 0, 0, -m.gravity[0], -m.gravity[1], -m.gravity[2]};
-        xform_motion(E, R, a0, ap);
       }
+      step_accel_in(E, R, par >= 0, accp, m.gravity, ap);
       if (FF && i == 0) {
-        // S = I: qdd_s = IA^-1 (tau_s - pA) - a' in the spatial ordering [angular; linear]; tau / qdd are ordered [linear; angular]
-        double IAr[21], rhs[6], qs[6];
+        double IAr[21], pAr[6];
 #pragma unroll
         for (int k = 0; k < 21; ++k) IAr[k] = S(i, oZ + k);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { rhs[k] = tau[3 + k] - S(i, oP + k); rhs[3 + k] = tau[k] - S(i, oP + 3 + k); }
-        sym6_solve(IAr, rhs, qs);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) { ap[k] += cb[k]; qs[k] -= ap[k]; }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { qdd[k] = qs[3 + k]; qdd[3 + k] = qs[k]; }
-#pragma unroll
-        for (int k = 0; k < 6; ++k) S(i, oV + k) = ap[k] + qs[k];
+        for (int k = 0; k < 6; ++k) pAr[k] = S(i, oP + k);
+        step_accel_ff_root(IAr, pAr, tau, cb, ap, qdd);
       } else {
-      double s = 0;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) { ap[k] += cb[k]; s += U[k] * ap[k]; }
-      const double qd = (S(i, oT) - s) * S(i, oD);
-      qdd[VI(i)] = qd;
-      const double* a = m.axis[i];
-      const int o = role_rev(rr) ? 0 : 3;
-      ap[o] += a[0] * qd; ap[o + 1] += a[1] * qd; ap[o + 2] += a[2] * qd;
+        qdd[VI(i)] = step_accel(U, cb, S(i, oT), S(i, oD), m.axis[i], role_rev(rr), ap);
+      }
 #pragma unroll
       for (int k = 0; k < 6; ++k) S(i, oV + k) = ap[k];
-      }   // (not the free-flyer root)
     }
     coop_sync<true>();
   }
@@ -1268,9 +1151,10 @@ __device__ __forceinline__ void aba_tree_coop2w(const M& m, const double* q, con
 // U, 1/D, Ia = IA - U U^T / D and X^T Ia X depend on q alone.  aba_tree_coop2w split in two along that line: the q-part, run by a
 // helper wave one step ahead into a record of its own per joint (E | r | U | 1/D | Ia), and the x-part (pass 1, the force half of
 // pass 2, pass 3), which only reads such a record.  The q-part's contributions X^T Ia X live in slots private to it; the x-part's
-// cb | pA | uu | vel in slots private to it: inside either part the exchange points are wave-level fences.  Every entry is formed
-// by the same operations in the same order as in aba_tree_coop2w (descending child order, the free-flyer root's sym6_solve
-// branch: its articulated inertia rides in the Ia slots of its record, which a root has no other use for).
+// cb | pA | uu | vel in slots private to it: inside either part the exchange points are wave-level fences.  The q-part is built
+// from step_place, step_add_children, step_U, step_Ia and step_inertia_up; the x-part from step_velocity, step_add_children,
+// step_u, step_force_up, step_accel_in, step_accel and step_accel_ff_root (the free-flyer root's articulated inertia rides in the
+// Ia slots of its record, which a root has no other use for).
 constexpr int ABA_PIPE_QSLOTS = 41;   // per joint: E 9 | r 3 | U 6 | Dinv 1 | Ia 21 | one unused (an odd stride spreads the joints of a level over the LDS banks)
 constexpr int ABA_PIPE_ZSLOTS = 21;   // per joint: X^T Ia X
 constexpr int ABA_PIPE_XSLOTS = 19;   // per joint: cb 6 | pA 6 | uu 1 | vel/acc 6
@@ -1280,7 +1164,6 @@ template <int NJ, int TPB, int NH, class M, bool FF = false>
 __device__ __forceinline__ void aba_pipe_q(const M& m, const double* q, double* rec, double* zst, int cand, int h, bool live,
                                            FwdStamp* fs = nullptr) {
   const int nj = FF ? m.nv - 5 : m.nv;
-  auto QI = [](int i) { return FF ? i + 6 : i; };
   auto Q = [&](int joint, int slot) -> double& { return rec[(joint * ABA_PIPE_QSLOTS + slot) * TPB + cand]; };
   auto Z = [&](int joint, int slot) -> double& { return zst[(joint * ABA_PIPE_ZSLOTS + slot) * TPB + cand]; };
   constexpr int oE = 0, oR = 9, oU = 12, oD = 18, oA = 19;
@@ -1288,17 +1171,7 @@ __device__ __forceinline__ void aba_pipe_q(const M& m, const double* q, double* 
   if (live)
     for (int i = h; i < nj; i += NH) {
       double E[9], R[3];
-      if (FF && i == 0) {                            // rbd::place: E = R(quaternion)^T, r = p
-        double Rq[9];
-        lie::quat_to_R(q + 3, Rq);
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-          for (int l = 0; l < 3; ++l) E[3 * k + l] = Rq[3 * l + k];
-        R[0] = q[0]; R[1] = q[1]; R[2] = q[2];
-      } else {
-        joint_placement(m, i, q[QI(i)], E, R);
-      }
+      step_place<FF>(m, i, q, E, R);
 #pragma unroll
       for (int k = 0; k < 9; ++k) Q(i, oE + k) = E[k];
 #pragma unroll
@@ -1310,36 +1183,16 @@ __device__ __forceinline__ void aba_pipe_q(const M& m, const double* q, double* 
     const unsigned long long rr = m.role[L * NH + h];
     if (live && role_joint(rr) != 255) {
       const int i = role_joint(rr);
-      const double* a = m.axis[i];
-      const bool rev = role_rev(rr);
-      const int nch = role_nchildren(rr);
       double IA[21], U[6];
 #pragma unroll
       for (int k = 0; k < 21; ++k) IA[k] = m.I6[i][k];
-#pragma unroll
-      for (int ci = 0; ci < ROLE_MAX_CHILDREN; ++ci) {   // contributions, descending child index
-        if (ci < nch) {
-          const int c = role_child(rr, ci);
-#pragma unroll
-          for (int k = 0; k < 21; ++k) IA[k] += Z(c, k);
-        }
-      }
+      step_add_children<21>(rr, IA, [&](int c, int k) { return Z(c, k); });
       FSTAMP(fs, 9);
       if (FF && i == 0) {
 #pragma unroll
-        for (int k = 0; k < 21; ++k) Q(i, oA + k) = IA[k];   // resolved in the x-part's last pass (sym6_solve)
+        for (int k = 0; k < 21; ++k) Q(i, oA + k) = IA[k];   // resolved in the x-part's last pass (step_accel_ff_root)
       } else {
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-          const double i0 = rev ? IA[sidx(r, 0)] : IA[sidx(r, 3)];
-          const double i1 = rev ? IA[sidx(r, 1)] : IA[sidx(r, 4)];
-          const double i2 = rev ? IA[sidx(r, 2)] : IA[sidx(r, 5)];
-          U[r] = i0 * a[0] + i1 * a[1] + i2 * a[2];
-        }
-        double d = 0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) d += a[k] * (rev ? U[k] : U[3 + k]);
-        const double dinv = 1.0 / d;
+        const double dinv = step_U(IA, m.axis[i], role_rev(rr), U);
         FSTAMP(fs, 10);
 #pragma unroll
         for (int k = 0; k < 6; ++k) Q(i, oU + k) = U[k];
@@ -1350,15 +1203,10 @@ __device__ __forceinline__ void aba_pipe_q(const M& m, const double* q, double* 
           for (int k = 0; k < 9; ++k) E[k] = Q(i, oE + k);
 #pragma unroll
           for (int k = 0; k < 3; ++k) R[k] = Q(i, oR + k);
-#pragma unroll
-          for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int c = 0; c <= r; ++c) Ia[sidx(r, c)] = IA[sidx(r, c)] - U[r] * U[c] * dinv;
+          step_Ia(IA, U, dinv, Ia);
 #pragma unroll
           for (int k = 0; k < 21; ++k) Q(i, oA + k) = Ia[k];
-#pragma unroll
-          for (int k = 0; k < 21; ++k) Zc[k] = 0.0;
-          add_xtix(E, R, Ia, Zc);
+          step_inertia_up(E, R, Ia, Zc);
 #pragma unroll
           for (int k = 0; k < 21; ++k) Z(i, k) = Zc[k];
         }
@@ -1383,32 +1231,17 @@ __device__ __forceinline__ void aba_pipe_x(const M& m, const double* rec, const 
     const unsigned long long rr = m.role[L * NH + h];
     if (live && role_joint(rr) != 255) {
       const int i = role_joint(rr);
-      double E[9], R[3], vel[6], vp[6], cb[6], pA[6], Iv[6], I6[21];
+      double E[9], R[3], vel[6], vp[6], cb[6], pA[6];
 #pragma unroll
       for (int k = 0; k < 9; ++k) E[k] = Q(i, oE + k);
 #pragma unroll
       for (int k = 0; k < 3; ++k) R[k] = Q(i, oR + k);
-      const double* a = m.axis[i];
-      double vJ[6] = {0, 0, 0, 0, 0, 0};
-      const int o = role_rev(rr) ? 0 : 3;
-      if (FF && i == 0) { vJ[0] = v[3]; vJ[1] = v[4]; vJ[2] = v[5]; vJ[3] = v[0]; vJ[4] = v[1]; vJ[5] = v[2]; }   // S = identity on the body twist
-      else { const double vi = v[VI(i)]; vJ[o] = a[0] * vi; vJ[o + 1] = a[1] * vi; vJ[o + 2] = a[2] * vi; }
       const int par = role_parent(rr);
       if (par >= 0) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) vp[k] = S(par, oV + k);
-        xform_motion(E, R, vp, vel);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) vel[k] = 0.0;
       }
-#pragma unroll
-      for (int k = 0; k < 6; ++k) vel[k] += vJ[k];
-      crm(vel, vJ, cb);
-#pragma unroll
-      for (int k = 0; k < 21; ++k) I6[k] = m.I6[i][k];
-      sym6_mv(I6, vel, Iv);
-      crf(vel, Iv, pA);
+      step_velocity(E, R, m.axis[i], role_rev(rr), FF && i == 0, v + (FF && i == 0 ? 0 : VI(i)), par >= 0, vp, m.I6[i], vel, cb, pA);
 #pragma unroll
       for (int k = 0; k < 6; ++k) { S(i, oV + k) = vel[k]; S(i, oC + k) = cb[k]; S(i, oP + k) = pA[k]; }
     }
@@ -1419,56 +1252,28 @@ __device__ __forceinline__ void aba_pipe_x(const M& m, const double* rec, const 
     const unsigned long long rr = m.role[L * NH + h];
     if (live && role_joint(rr) != 255) {
       const int i = role_joint(rr);
-      const double* a = m.axis[i];
-      const bool rev = role_rev(rr);
-      const int nch = role_nchildren(rr);
       double pAi[6];
 #pragma unroll
       for (int k = 0; k < 6; ++k) pAi[k] = S(i, oP + k);
+      step_add_children<6>(rr, pAi, [&](int c, int k) { return S(c, oP + k); });
       if (FF && i == 0) {
         // the free-flyer root is resolved in the last pass: its bias force stays in its slots; it has no parent to contribute to
 #pragma unroll
-        for (int ci = 0; ci < ROLE_MAX_CHILDREN; ++ci) {
-          if (ci < nch) {
-            const int c = role_child(rr, ci);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) pAi[k] += S(c, oP + k);
-          }
-        }
-#pragma unroll
         for (int k = 0; k < 6; ++k) S(i, oP + k) = pAi[k];
       } else {
-        double cb[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) cb[k] = S(i, oC + k);
-#pragma unroll
-        for (int ci = 0; ci < ROLE_MAX_CHILDREN; ++ci) {
-          if (ci < nch) {
-            const int c = role_child(rr, ci);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) pAi[k] += S(c, oP + k);
-          }
-        }
-        double sp = 0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) sp += a[k] * (rev ? pAi[k] : pAi[3 + k]);
-        const double ui = tau[VI(i)] - sp;
+        const double ui = step_u(pAi, m.axis[i], role_rev(rr), tau[VI(i)]);
         S(i, oT) = ui;
         if (role_parent(rr) >= 0) {
-          double E[9], R[3], U[6], Ia[21], pa[6], Iac[6], fp[6];
+          double E[9], R[3], U[6], cb[6], Ia[21], fp[6];
 #pragma unroll
           for (int k = 0; k < 9; ++k) E[k] = Q(i, oE + k);
 #pragma unroll
           for (int k = 0; k < 3; ++k) R[k] = Q(i, oR + k);
 #pragma unroll
-          for (int k = 0; k < 6; ++k) U[k] = Q(i, oU + k);
-          const double dinv = Q(i, oD);
+          for (int k = 0; k < 6; ++k) { U[k] = Q(i, oU + k); cb[k] = S(i, oC + k); }
 #pragma unroll
           for (int k = 0; k < 21; ++k) Ia[k] = Q(i, oA + k);
-          sym6_mv(Ia, cb, Iac);
-#pragma unroll
-          for (int k = 0; k < 6; ++k) pa[k] = pAi[k] + Iac[k] + U[k] * (ui * dinv);
-          xform_force_T(E, R, pa, fp);
+          step_force_up(E, R, pAi, cb, U, Q(i, oD), ui, Ia, fp);
 #pragma unroll
           for (int k = 0; k < 6; ++k) S(i, oP + k) = fp[k];
         }
@@ -1492,37 +1297,20 @@ __device__ __forceinline__ void aba_pipe_x(const M& m, const double* rec, const 
       if (par >= 0) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) accp[k] = S(par, oV + k);
-        xform_motion(E, R, accp, ap);
-      } else {
-        const double a0[6] = {0, 0, 0, -m.gravity[0], -m.gravity[1], -m.gravity[2]};
-        xform_motion(E, R, a0, ap);
       }
+      step_accel_in(E, R, par >= 0, accp, m.gravity, ap);
       if (FF && i == 0) {
-        // S = I: qdd_s = IA^-1 (tau_s - pA) - a' in the spatial ordering [angular; linear]; tau / qdd are ordered [linear; angular]
-        double IAr[21], rhs[6], qs[6];
+        double IAr[21], pAr[6];
 #pragma unroll
         for (int k = 0; k < 21; ++k) IAr[k] = Q(i, oA + k);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { rhs[k] = tau[3 + k] - S(i, oP + k); rhs[3 + k] = tau[k] - S(i, oP + 3 + k); }
-        sym6_solve(IAr, rhs, qs);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) { ap[k] += cb[k]; qs[k] -= ap[k]; }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { qdd[k] = qs[3 + k]; qdd[3 + k] = qs[k]; }
-#pragma unroll
-        for (int k = 0; k < 6; ++k) S(i, oV + k) = ap[k] + qs[k];
+        for (int k = 0; k < 6; ++k) pAr[k] = S(i, oP + k);
+        step_accel_ff_root(IAr, pAr, tau, cb, ap, qdd);
       } else {
-      double s = 0;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) { ap[k] += cb[k]; s += U[k] * ap[k]; }
-      const double qd = (S(i, oT) - s) * Q(i, oD);
-      qdd[VI(i)] = qd;
-      const double* a = m.axis[i];
-      const int o = role_rev(rr) ? 0 : 3;
-      ap[o] += a[0] * qd; ap[o + 1] += a[1] * qd; ap[o + 2] += a[2] * qd;
+        qdd[VI(i)] = step_accel(U, cb, S(i, oT), Q(i, oD), m.axis[i], role_rev(rr), ap);
+      }
 #pragma unroll
       for (int k = 0; k < 6; ++k) S(i, oV + k) = ap[k];
-      }   // (not the free-flyer root)
     }
     coop_sync<true>();
   }
