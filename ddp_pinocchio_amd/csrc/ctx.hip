@@ -213,32 +213,6 @@ static int fill_device(ddp_hip_ctx* ctx, double* p, int64_t n, double v) {
   return DDP_HIP_OK;
 }
 
-// The development switches: the one place in the library that reads the environment
-static DevSwitches read_switches() {
-  auto on = [](const char* name) { return getenv(name) != nullptr; };
-  auto knob = [](const char* name, int lo, int hi) { const char* ev = getenv(name); const int v = ev ? atoi(ev) : 0; return v >= lo && v <= hi ? v : 0; };
-  DevSwitches sw;
-  sw.generic_bwd = on("DDP_HIP_GENERIC_BWD");
-  sw.k3_no_sym = on("DDP_HIP_K3_NO_SYM");
-  sw.k3_no_half = on("DDP_HIP_K3_NO_HALF");
-  sw.k3_no_pack = on("DDP_HIP_K3_NO_PACK");
-  sw.fxx_full = on("DDP_HIP_FXX_FULL");
-  sw.no_static = on("DDP_HIP_NO_STATIC");
-  sw.no_qcache = on("DDP_HIP_NO_QCACHE");
-  sw.cfg_full_aba = on("DDP_HIP_CFG_FULL_ABA");
-  sw.ana_own_aba = on("DDP_HIP_ANA_OWN_ABA");
-  sw.ana_split = on("DDP_HIP_ANA_SPLIT");
-  sw.ana_eq_kernel = on("DDP_HIP_ANA_EQ_KERNEL");
-  sw.bwd_no_graph = on("DDP_HIP_BWD_NO_GRAPH");
-  sw.solve_sync = on("DDP_HIP_SOLVE_SYNC");
-  sw.fwd_no_pipe = on("DDP_HIP_FWD_NO_PIPE");
-  sw.bwd_cbx = knob("DDP_HIP_BWD_CBX", 1, 8);
-  sw.bwd_cbu = knob("DDP_HIP_BWD_CBU", 1, 16);
-  sw.qws_bt = knob("DDP_HIP_QWS_BT", 16, 65536);
-  sw.ana_bt = knob("DDP_HIP_ANA_BT", 1, 65536);
-  return sw;
-}
-
 // A term's arrays as they are at create: allocated (once) for max_items, every side at its fill value over that whole capacity,
 // the term off, laid out by `items`.  ddp_hip_create, and the set_frames / set_points entry points when the layout changes
 static int cost_block_setup(ddp_hip_ctx* ctx, int term, int32_t items) {

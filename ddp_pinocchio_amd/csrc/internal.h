@@ -62,7 +62,7 @@ struct BwdJob {
   int32_t pad_;
 };
 
-// Development switches (DDP_HIP_*), read once by ddp_hip_create (ctx.hip: read_switches): a context
+// Development switches (DDP_HIP_*), read once by ddp_hip_create (lin_plan.cpp: read_switches): a context
 // keeps the paths it was created with.  A tuning knob of 0 is unset (or out of its range): the context's own choice holds.
 struct DevSwitches {
   bool generic_bwd = false;    // GENERIC_BWD: the run-time-shaped sweep at the Talos shape as well
@@ -79,6 +79,8 @@ struct DevSwitches {
   bool bwd_no_graph = false;   // BWD_NO_GRAPH: the sweep is enqueued launch by launch, not replayed as a hipGraph
   bool solve_sync = false;     // SOLVE_SYNC: ddp_hip_solve waits for the stream at every call
   bool fwd_no_pipe = false;    // FWD_NO_PIPE: the forward latency kernel in its four-candidate form, never the pipelined one
+  bool lin_serial = false;     // LIN_SERIAL: every kernel of a linearisation on the context's stream, in the single-stream order (no side streams)
+  int32_t lin_forks = 0;       // LIN_FORKS (1..3): the LinFork bits a concurrent linearisation keeps (A/B of one fork at a time)
   int32_t bwd_cbx = 0, bwd_cbu = 0;   // BWD_CBX (1..8), BWD_CBU (1..16): columns per job of K3 / bwd_assemble
   int64_t qws_bt = 0;          // QWS_BT (16..65536): (instance, t) pairs per configuration-level workspace slice
   int64_t ana_bt = 0;          // ANA_BT (1..65536): (instance, t) pairs per analytic workspace slice
@@ -118,6 +120,13 @@ enum class LinEq : int32_t {
   Analytic,        // large trees with analytic jacobians (lin_analytic.hip: ana_eq_kernel)
   Chain,           // forward-differenced jacobians, and free-flyer models: eq_chain / look-ahead jacobians / eq_combine
 };
+// The forks of a static-topology linearisation's schedule (LinPlan::forks): each moves kernels that depend
+// on nothing the context's stream is running onto the side stream, and is joined back before the profiling bracket it was forked in ends
+enum LinFork : uint32_t {
+  LIN_FORK_CFG = 1,        // the configuration level (spine + pairs, slice by slice) beside the velocity level
+  LIN_FORK_SPINE = 2,      // ... its first spine pre-pass already beside the u diagonal and the torque rows (with LIN_FORK_CFG)
+  LIN_FORK_DEFAULT = LIN_FORK_CFG | LIN_FORK_SPINE,
+};
 enum class LinEqJac : int32_t { None, Fd, FfLookahead };   // Chain with K > 1: where f_x at the look-ahead states comes from
 enum class LinEqSecond : int32_t { None, Zeros, Mode2, Mode1Small, Mode1Wave };   // the constraint tensors: as LinSecond
 struct LinPlan {
@@ -144,8 +153,10 @@ struct LinPlan {
   bool ws_eq = false;
   bool ana_sliced = false;     // lin_analytic.hip takes the model: ctx->ana_nbt is set
   int64_t eq_fxk_off = 0, eq_c_off = 0, eq_words = 0;   // eq_ws: x_1..x_K | f_x(x_1..x_{K-1}) at eq_fxk_off | base jacobian at eq_c_off
+  uint32_t forks = 0;          // LinFork bits: the schedule's forks onto the side streams (0: the single-stream order)
   int32_t lin_path = 0, first_order = 0;   // what ddp_hip_ctx_info reports
 };
+DevSwitches read_switches();   // lin_plan.cpp: the one place in the library that reads the environment
 LinPlan lin_plan_decide(const DevModel& m, const Dims& d, uint32_t flags, const DevSwitches& sw, int topo_id, bool sweep_sym_ok);
 
 // What FXX / FUX / FUU hold, as far as a reader inside the library may rely on it.  The record changes
@@ -236,6 +247,10 @@ struct ddp_hip_ctx {
   double* lin_qws2 = nullptr;  // second workspace + stream + events (DDP_HIP_CFG_FULL_ABA only): the two full-ABA kernels of consecutive slices overlap
   hipStream_t lin_stream2 = nullptr;
   hipEvent_t lin_ev_up[2] = {nullptr, nullptr}, lin_ev_dn[2] = {nullptr, nullptr};
+  // the concurrent schedule (LinPlan::forks) runs its side branch on lin_stream2: fork / done events, and the torque rows'
+  // completion.  lin_side_busy: work has been forked onto the side stream and not joined back yet (LinJoin)
+  hipEvent_t lin_ev_fork = nullptr, lin_ev_done = nullptr, lin_ev_rows = nullptr;
+  bool lin_side_busy = false;
   double* ana_T = nullptr;     // analytic-derivative workspace (lin_analytic.hip): T = [dtau/dq | dtau/dv] per evaluation of a slice
   double* ana_M = nullptr;     // ... and M / M^-1 per configuration of a slice
   double* ana_F = nullptr;     // ... and the v rows of f_x at the perturbed points (mode-1 constraint tensors)
@@ -278,6 +293,32 @@ struct ddp_hip_ctx {
 
 // end of an entry point that returns nothing to the host: wait for the stream unless the context is in asynchronous mode
 #define END_SYNC(ctx) do { if (!(ctx)->async_mode) HIP_TRY(hipStreamSynchronize((ctx)->stream)); } while (0)
+
+// The side stream of the concurrent linearisation schedule.  lin_fork: it continues from where ctx->stream stands now; lin_join:
+// ctx->stream continues only after what it holds.  Nothing else in the library looks at the side stream: the entry point that
+// may fork holds a LinJoin, whose destructor joins whatever is still out, on every return path.
+inline hipError_t lin_fork(ddp_hip_ctx* ctx) {
+  hipError_t e = hipEventRecord(ctx->lin_ev_fork, ctx->stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->lin_stream2, ctx->lin_ev_fork, 0);
+  if (e == hipSuccess) ctx->lin_side_busy = true;
+  return e;
+}
+inline hipError_t lin_join(ddp_hip_ctx* ctx) {
+  if (!ctx->lin_side_busy) return hipSuccess;
+  hipError_t e = hipEventRecord(ctx->lin_ev_done, ctx->lin_stream2);
+  if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->lin_ev_done, 0);
+  // a join that cannot be enqueued leaves no order between the streams: the host waits instead
+  if (e != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(ctx->lin_stream2); }
+  ctx->lin_side_busy = false;
+  return e;
+}
+struct LinJoin {
+  ddp_hip_ctx* ctx;
+  explicit LinJoin(ddp_hip_ctx* c) : ctx(c) {}
+  LinJoin(const LinJoin&) = delete;
+  LinJoin& operator=(const LinJoin&) = delete;
+  ~LinJoin() { (void)lin_join(ctx); }
+};
 
 // profile helpers (ctx.hip)
 void prof_begin(ddp_hip_ctx* ctx, int kid, hipStream_t stream = nullptr);   // stream: the one the kernel is launched on (default: the context's)

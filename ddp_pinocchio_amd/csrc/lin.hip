@@ -1315,6 +1315,11 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
       case LinSecond::None: break;
       case LinSecond::Mode2Static:
         build_caches();
+        if (pl.forks) {   // the whole second order as one launch graph on the context's stream and the side stream
+          const int rc_ = lin_static_launch(ctx, p, StaticLevel::SecondOrder);
+          if (rc_ != DDP_HIP_OK) return rc_;
+          break;
+        }
         // torque level ahead of the other two: its row kernel also forms the diagonal entries of the q and v directions
         for (StaticLevel level : {StaticLevel::UDiagonal, StaticLevel::Torque, StaticLevel::Velocity, StaticLevel::Configuration}) {
           const int rc_ = lin_static_launch(ctx, p, level);
@@ -1344,6 +1349,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
         HIP_TRY(hipMemsetAsync(p.fuu, 0, sizeof(double) * (size_t)(ctx->seq[DDP_HIP_SEQ_FUU].size * d.batch), ctx->stream));
         break;
     }
+    HIP_TRY(lin_join(ctx));   // (what was forked inside the bracket ends inside it)
     prof_end(ctx, DDP_HIP_K_LIN_SECOND);
   }
   if (eq_stage) {
@@ -1422,7 +1428,10 @@ int lin_setup(ddp_hip_ctx* ctx) {
     HIP_TRY(hipMalloc(&ctx->lin_ws, sizeof(double) * (size_t)(d.batch * d.T * ((int64_t)pl.ncfg * d.nv * rbd::QC_STRIDE + (int64_t)pl.nvcfg * d.nv * rbd::VC_STRIDE))));
   if (pl.ws_qws) {
     const int64_t BT = d.batch * d.T;
-    int64_t slice = 1024;
+    // With the spine pre-pass forked ahead of the torque rows (LIN_FORK_SPINE) only the first slice's pre-pass runs beside them.
+    // 3200 entries hold 13 330 spine sets of the Talos-like tree, its 64 seeds x 200 steps in one slice (measured: DESIGN.md
+    // section 6b; the single-stream order is indifferent to the slice size)
+    int64_t slice = (pl.forks & LIN_FORK_SPINE) ? 3200 : 1024;
     if (ctx->sw.qws_bt) slice = ctx->sw.qws_bt;   // tuning knob
     ctx->lin_qws_bt = BT < slice ? BT : slice;
     HIP_TRY(hipMalloc(&ctx->lin_qws, sizeof(double) * (size_t)(ctx->lin_qws_bt * lin_static_ws_per_bt(ctx->model_h))));
@@ -1434,6 +1443,12 @@ int lin_setup(ddp_hip_ctx* ctx) {
         HIP_TRY(hipEventCreateWithFlags(&ctx->lin_ev_dn[k], hipEventDisableTiming));
       }
     }
+  }
+  if (pl.forks) {   // the concurrent schedule: one side stream and its events, for the context's life
+    HIP_TRY(hipStreamCreateWithFlags(&ctx->lin_stream2, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&ctx->lin_ev_fork, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&ctx->lin_ev_done, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&ctx->lin_ev_rows, hipEventDisableTiming));
   }
   { const int rc_ = lin_analytic_setup(ctx); if (rc_ != DDP_HIP_OK) return rc_; }
   if (pl.ws_eq) HIP_TRY(hipMalloc(&ctx->eq_ws, sizeof(double) * (size_t)pl.eq_words));   // look-ahead states / jacobians of the constraint chain
@@ -1451,6 +1466,7 @@ void lin_teardown(ddp_hip_ctx* ctx) {
     if (ctx->lin_ev_up[k]) (void)hipEventDestroy(ctx->lin_ev_up[k]);
     if (ctx->lin_ev_dn[k]) (void)hipEventDestroy(ctx->lin_ev_dn[k]);
   }
+  for (hipEvent_t ev : {ctx->lin_ev_fork, ctx->lin_ev_done, ctx->lin_ev_rows}) if (ev) (void)hipEventDestroy(ev);
   if (ctx->lin_stream2) (void)hipStreamDestroy(ctx->lin_stream2);
   if (ctx->lin_qws2) (void)hipFree(ctx->lin_qws2);
   if (ctx->lin_qws) (void)hipFree(ctx->lin_qws);
@@ -1463,6 +1479,7 @@ extern "C" int ddp_hip_linearize_stages(ddp_hip_ctx* ctx, uint32_t stages) {
   HIP_TRY(hipSetDevice(ctx->device));
   LinParams p = make_params(ctx);
   LinCall call;
+  LinJoin joined(ctx);   // whatever this call leaves on the side stream is joined into ctx->stream on every way out
   const bool second = (stages & DDP_HIP_LIN_SECOND) && p.has_tensors;
   if (second) { const int rc_ = tensors_begin_second(ctx, p, call); if (rc_ != DDP_HIP_OK) return rc_; }
   int rc;

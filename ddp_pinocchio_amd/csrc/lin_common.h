@@ -47,6 +47,7 @@ enum class StaticLevel {
   Torque,          // mode 2: torque-level stencil points (and the diagonal entries of the q and v directions)
   Velocity,        // mode 2: velocity-level stencil points
   Configuration,   // mode 2: (q_i, q_j) stencil points
+  SecondOrder,     // mode 2, concurrent schedule (LinPlan::forks): UDiagonal, Torque, Velocity and Configuration as one launch graph
   AccelX,          // mode 1: accelerations at x + sqrt(eps_mach) e_k into p.accel_out (builds the base caches itself)
   AccelXU,         // ... and at u + sqrt(eps_mach) e_k
 };

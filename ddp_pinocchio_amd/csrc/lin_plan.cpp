@@ -1,6 +1,38 @@
-// lin_plan.cpp -- which kernels a context's linearisation runs: one pure function, no HIP calls.
-// With -DLIN_PLAN_TABLE the file is a program that prints the plan of every combination of its inputs (tests/test_lin_plan.py).
+// lin_plan.cpp -- which kernels a context's linearisation runs: one pure function, no HIP calls, and the
+// development switches it is a function of, read from the environment.
+// With -DLIN_PLAN_TABLE the file is a program that prints the plan of every combination of its inputs (tests/test_lin_plan.py),
+// or, as `lin_plan_table schedule`, the schedule of the flagship plan under the environment's switches (tests/test_lin_overlap.py).
+#include <stdlib.h>
+
 #include "internal.h"
+
+// The development switches: the one place in the library that reads the environment
+DevSwitches read_switches() {
+  auto on = [](const char* name) { return getenv(name) != nullptr; };
+  auto knob = [](const char* name, int lo, int hi) { const char* ev = getenv(name); const int v = ev ? atoi(ev) : 0; return v >= lo && v <= hi ? v : 0; };
+  DevSwitches sw;
+  sw.generic_bwd = on("DDP_HIP_GENERIC_BWD");
+  sw.k3_no_sym = on("DDP_HIP_K3_NO_SYM");
+  sw.k3_no_half = on("DDP_HIP_K3_NO_HALF");
+  sw.k3_no_pack = on("DDP_HIP_K3_NO_PACK");
+  sw.fxx_full = on("DDP_HIP_FXX_FULL");
+  sw.no_static = on("DDP_HIP_NO_STATIC");
+  sw.no_qcache = on("DDP_HIP_NO_QCACHE");
+  sw.cfg_full_aba = on("DDP_HIP_CFG_FULL_ABA");
+  sw.ana_own_aba = on("DDP_HIP_ANA_OWN_ABA");
+  sw.ana_split = on("DDP_HIP_ANA_SPLIT");
+  sw.ana_eq_kernel = on("DDP_HIP_ANA_EQ_KERNEL");
+  sw.bwd_no_graph = on("DDP_HIP_BWD_NO_GRAPH");
+  sw.solve_sync = on("DDP_HIP_SOLVE_SYNC");
+  sw.fwd_no_pipe = on("DDP_HIP_FWD_NO_PIPE");
+  sw.lin_serial = on("DDP_HIP_LIN_SERIAL");
+  sw.lin_forks = knob("DDP_HIP_LIN_FORKS", 1, 3);
+  sw.bwd_cbx = knob("DDP_HIP_BWD_CBX", 1, 8);
+  sw.bwd_cbu = knob("DDP_HIP_BWD_CBU", 1, 16);
+  sw.qws_bt = knob("DDP_HIP_QWS_BT", 16, 65536);
+  sw.ana_bt = knob("DDP_HIP_ANA_BT", 1, 65536);
+  return sw;
+}
 
 // topo_id: what lin_static_supported returned for the model's tree (0: no compiled-in topology, always 0 with a free flyer);
 // sweep_sym_ok: sweep_plan(ctx).sym_ok, a property of the shape and the switches alone (bwd_setup runs ahead of lin_setup)
@@ -73,6 +105,9 @@ LinPlan lin_plan_decide(const DevModel& m, const Dims& d, uint32_t flags, const 
     pl.eq_c_off = pl.eq_fxk_off + d.batch * d.T * (K > 1 ? K - 1 : 0) * d.n * d.n;
     pl.eq_words = pl.eq_c_off + d.batch * d.T * d.emax * d.n;
   }
+  // the concurrent schedule: the static stencil's own.  The full-ABA configuration level keeps its two-stream
+  // slice pipeline to itself
+  if (pl.second == LinSecond::Mode2Static && !sw.lin_serial && !sw.cfg_full_aba) pl.forks = sw.lin_forks ? (uint32_t)sw.lin_forks : (uint32_t)LIN_FORK_DEFAULT;
   pl.lin_path = tree ? 1 + pl.topo : 0;
   pl.first_order = tree ? (fo_fd ? 1 : 2) : 0;
   return pl;
@@ -84,7 +119,18 @@ LinPlan lin_plan_decide(const DevModel& m, const Dims& d, uint32_t flags, const 
 // One line of integers per combination of the inputs (the first line names the columns).  `created`: ddp_hip_create's own
 // argument checks let the combination through to lin_setup (ctx.hip: a pendulum has nv = 1 and no free flyer; a free flyer
 // leaves nj = nv - 5 >= 1 joints and is refused in mode 1 and under the config constraint; no constraint kind, no rows).
-int main() {
+int main(int argc, char** argv) {
+  if (argc > 1 && argv[1][0] == 's') {
+    // `schedule`: the forks of the flagship plan (Talos-size tree on its compiled-in topology, mode 2, forward-differenced first
+    // order) under the switches of this process's environment (tests/test_lin_overlap.py)
+    DevModel m{};
+    m.kind = DDP_HIP_MODEL_TREE; m.nv = 38; m.nj = 38; m.nq = 38; m.first_order_fd = 1; m.fd_mode = 2; m.max_level_width = 4;
+    Dims d{};
+    d.T = 3; d.batch = 2; d.nv = 38; d.n = 76; d.m = 38; d.nx = 76;
+    const LinPlan p = lin_plan_decide(m, d, 0u, read_switches(), 1, true);
+    printf("forks %u topo %d\n", p.forks, p.topo);
+    return 0;
+  }
   static const char* const sw_names[] = {"none", "generic_bwd", "k3_no_sym", "k3_no_half", "fxx_full", "no_static", "no_qcache",
                                          "cfg_full_aba", "ana_own_aba", "ana_split", "ana_eq_kernel", "bwd_no_graph", "solve_sync"};
   printf("kind nv ff fo_fd mode tensors etot eq_kind K matched sw sym_ok created refuse nj topo first second eq eq_jac eq_second "

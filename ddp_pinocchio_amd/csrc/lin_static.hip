@@ -834,8 +834,12 @@ __device__ __forceinline__ void vel_down_all(const C& c, VelState<T>& s, std::in
 // One wave per group; the groups of one (instance, t):
 //   ROWS:  g < nv : (q_g, v_lane)      cfg 1+g   38 of 64 lanes, row-block output (+ mirror image)
 //   !ROWS: (v_i, v_j) pairs, cfg 0, 64 pairs per wave, generic output in two half-wave passes
+// (the pairs: 2 waves per SIMD and no scratch, or -DDDP_VEL_PAIR_WAVES=3 with 208 B of it: the A/B build of DESIGN.md section 4)
+#ifndef DDP_VEL_PAIR_WAVES
+#define DDP_VEL_PAIR_WAVES 2
+#endif
 template <class T, bool ROWS>
-__global__ __launch_bounds__(LBS, ROWS ? 3 : 2) void lin_static_vel_kernel(LinParams p) {
+__global__ __launch_bounds__(LBS, ROWS ? 3 : DDP_VEL_PAIR_WAVES) void lin_static_vel_kernel(LinParams p) {
   constexpr int nv = T::N, n = 2 * nv;
   constexpr int TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS, G = ROWS ? nv : GU;
   const int64_t bt = blockIdx.x / G;
@@ -1900,6 +1904,58 @@ static void launch_first_columns(ddp_hip_ctx* ctx, const LinParams& p, bool with
   if (with_u) hipLaunchKernelGGL((lin_static_first_kernel<T, 3, false>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
 }
 
+// the configuration level's slices on `s`: spine pre-pass, then the pair kernel on spliced operands, in slices of (instance, t)
+// whose spine records share the workspace.  The workspace is sized for lin_qws_bt sweeps (lin_static_ws_per_bt: the first-order q
+// columns run one); a spine set is smaller, so a slice holds more of them (Talos: 4.2 x; few long launches instead of many short
+// ones).  rows_done (or null): an event the first pair kernel waits for, behind its spine pre-pass (LIN_FORK_SPINE)
+template <class T>
+static int launch_cfg_slices(ddp_hip_ctx* ctx, const LinParams& p, hipStream_t s, hipEvent_t rows_done) {
+  const int64_t BT = ctx->d.batch * ctx->d.T;
+  constexpr int nv = T::N, TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS;
+  constexpr int64_t NREC = spine_records<T>(), SWEEP = (int64_t)GU * nv * WS_PER_JOINT * LBS;
+  constexpr int64_t WS_BT = SWEEP > NREC * SREC ? SWEEP : NREC * SREC;
+  const int64_t per = NREC > 0 ? ctx->lin_qws_bt * WS_BT / (NREC * SREC) : BT;
+  for (int64_t bt0 = 0; bt0 < BT; bt0 += per) {
+    const int nb = (int)(BT - bt0 < per ? BT - bt0 : per);
+    const dim3 grid((unsigned)((nb + 7) / 8 * 8 * GU));
+    hipLaunchKernelGGL((lin_static_spine_kernel<T>), grid, dim3(LBS), 0, s, p.model, p.qcache, p.vcache, ctx->lin_qws, bt0, nb);
+    if (rows_done) { HIP_TRY(hipStreamWaitEvent(s, rows_done, 0)); rows_done = nullptr; }
+    hipLaunchKernelGGL((lin_static_cfg_pair_kernel<T>), grid, dim3(LBS), 0, s, p, ctx->lin_qws, bt0, nb);
+  }
+  return DDP_HIP_OK;
+}
+
+// Mode 2's second order under the concurrent schedule (LinPlan::forks; the reads and writes of every kernel: DESIGN.md section
+// 4r).  The u diagonal and the torque rows come first: the rows read every first-order column and the u diagonal, and leave the
+// q / v diagonal columns every other point reads.  Behind them the configuration slices run on the side stream beside the (u, u)
+// pairs and the velocity level: every off-diagonal point, its mirror image included, belongs to one kernel, so the two branches
+// write disjoint columns in every layout.  The first spine pre-pass reads the caches alone and writes the workspace, which the
+// first order's q columns are done with at this point of the stream: it starts beside the u diagonal.  Each fork is taken only
+// with its LinFork bit; without it the kernels keep their place in the single-stream order.  The caller joins the side stream
+// (lin.hip: ahead of the bracket's end).
+template <class T>
+static int launch_second_order(ddp_hip_ctx* ctx, const LinParams& p) {
+  const int64_t BT = ctx->d.batch * ctx->d.T;
+  constexpr int nv = T::N, TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS;
+  const bool fork_cfg = (ctx->plan.forks & LIN_FORK_CFG) != 0, spine_ahead = fork_cfg && (ctx->plan.forks & LIN_FORK_SPINE);
+  hipStream_t s0 = ctx->stream;
+  if (spine_ahead) HIP_TRY(lin_fork(ctx));
+  hipLaunchKernelGGL((lin_static_first_kernel<T, 3, true>), dim3((unsigned)BT), dim3(LBS), 0, s0, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
+  hipLaunchKernelGGL((lin_static_tau_kernel<T, true>), dim3((unsigned)(BT * 2 * nv)), dim3(LBS), 0, s0, p);
+  if (fork_cfg) {
+    if (spine_ahead) HIP_TRY(hipEventRecord(ctx->lin_ev_rows, s0));
+    else HIP_TRY(lin_fork(ctx));                    // (taken behind the rows: nothing more to wait for)
+    const int rc_ = launch_cfg_slices<T>(ctx, p, ctx->lin_stream2, spine_ahead ? ctx->lin_ev_rows : nullptr);
+    if (rc_ != DDP_HIP_OK) return rc_;
+  }
+  if (p.pack) hipLaunchKernelGGL((lin_static_tau_kernel<T, false, true>), dim3((unsigned)(BT * GU)), dim3(LBS), 0, s0, p);
+  else hipLaunchKernelGGL((lin_static_tau_kernel<T, false, false>), dim3((unsigned)(BT * GU)), dim3(LBS), 0, s0, p);
+  hipLaunchKernelGGL((lin_static_vel_kernel<T, true>), dim3((unsigned)(BT * nv)), dim3(LBS), 0, s0, p);
+  hipLaunchKernelGGL((lin_static_vel_kernel<T, false>), dim3((unsigned)(BT * GU)), dim3(LBS), 0, s0, p);
+  if (!fork_cfg) { const int rc_ = launch_cfg_slices<T>(ctx, p, s0, nullptr); if (rc_ != DDP_HIP_OK) return rc_; }
+  return DDP_HIP_OK;
+}
+
 template <class T>
 static int lin_static_launch_t(ddp_hip_ctx* ctx, const LinParams& p, StaticLevel level) {
   const int64_t BT = ctx->d.batch * ctx->d.T;
@@ -1917,23 +1973,14 @@ static int lin_static_launch_t(ddp_hip_ctx* ctx, const LinParams& p, StaticLevel
     launch_first_columns<T>(ctx, p, level == StaticLevel::AccelXU);
   } else if (level == StaticLevel::FirstOrder) {
     launch_first_columns<T>(ctx, p, true);
+  } else if (level == StaticLevel::SecondOrder) {
+    { const int rc_ = launch_second_order<T>(ctx, p); if (rc_ != DDP_HIP_OK) return rc_; }
   } else if (level == StaticLevel::UDiagonal) {
     // diagonal second-order entries of the u directions; those of the q and v directions are formed by the torque-level
     // row kernel (Torque) on an otherwise idle lane, which therefore runs ahead of Velocity and Configuration
     hipLaunchKernelGGL((lin_static_first_kernel<T, 3, true>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
   } else if (level == StaticLevel::Configuration && !ctx->sw.cfg_full_aba) {
-    // Spine pre-pass, then the pair kernel on spliced operands, in slices of (instance, t) whose spine records share the workspace.
-    // The workspace is sized for lin_qws_bt sweeps (lin_static_ws_per_bt: the first-order q columns run one); a spine set is
-    // smaller, so a slice holds more of them (Talos: 4.2 x; few long launches instead of many short ones: measured below)
-    constexpr int64_t NREC = spine_records<T>(), SWEEP = (int64_t)GU * nv * WS_PER_JOINT * LBS;
-    constexpr int64_t WS_BT = SWEEP > NREC * SREC ? SWEEP : NREC * SREC;
-    const int64_t per = NREC > 0 ? ctx->lin_qws_bt * WS_BT / (NREC * SREC) : BT;
-    for (int64_t bt0 = 0; bt0 < BT; bt0 += per) {
-      const int nb = (int)(BT - bt0 < per ? BT - bt0 : per);
-      const dim3 grid((unsigned)((nb + 7) / 8 * 8 * GU));
-      hipLaunchKernelGGL((lin_static_spine_kernel<T>), grid, dim3(LBS), 0, ctx->stream, p.model, p.qcache, p.vcache, ctx->lin_qws, bt0, nb);
-      hipLaunchKernelGGL((lin_static_cfg_pair_kernel<T>), grid, dim3(LBS), 0, ctx->stream, p, ctx->lin_qws, bt0, nb);
-    }
+    { const int rc_ = launch_cfg_slices<T>(ctx, p, ctx->stream, nullptr); if (rc_ != DDP_HIP_OK) return rc_; }
   } else if (level == StaticLevel::Configuration) {
     // DDP_HIP_CFG_FULL_ABA (development A/B): every point runs the whole articulated-body algorithm.
     // In slices of (instance, t), so that the per-wave workspace stays small.  The sweep kernel of slice k+1 (one wave per

@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 class switch:
-    """a development switch of the library in the environment while a context is created (ctx.hip: read_switches)"""
+    """a development switch of the library in the environment while a context is created (lin_plan.cpp: read_switches)"""
 
     def __init__(self, name=None):
         self.name = name
