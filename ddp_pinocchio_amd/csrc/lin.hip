@@ -1170,6 +1170,12 @@ __global__ __launch_bounds__(UNPACK_BS) void tensor_unpack_kernel(double* fxx, d
   }
 }
 
+// doubles per (instance, t) of the q-cache: ncfg whole blocks, or the static stencil's base block + deltas
+int64_t lin_qc_per_bt(const ddp_hip_ctx* ctx) {
+  const LinPlan& pl = ctx->plan;
+  return pl.qc_sparse ? lin_static_qc_per_bt(pl.topo) : (int64_t)pl.ncfg * ctx->d.nv * rbd::QC_STRIDE;
+}
+
 LinParams make_params(ddp_hip_ctx* ctx) {
   LinParams p{};
   p.d = ctx->d;
@@ -1194,7 +1200,9 @@ LinParams make_params(ddp_hip_ctx* ctx) {
   if (p.eq_xk) { p.eq_fxk = p.eq_xk + pl.eq_fxk_off; p.eq_c = p.eq_xk + pl.eq_c_off; }
   p.qcache = ctx->lin_ws;
   p.ncfg = pl.ncfg; p.nvcfg = pl.nvcfg;
-  p.vcache = p.qcache ? p.qcache + ctx->d.batch * ctx->d.T * (int64_t)pl.ncfg * ctx->d.nv * rbd::QC_STRIDE : nullptr;
+  p.qc_sparse = pl.qc_sparse ? 1 : 0;
+  p.qc_bt = lin_qc_per_bt(ctx);
+  p.vcache = p.qcache ? p.qcache + ctx->d.batch * ctx->d.T * p.qc_bt : nullptr;
   p.xref = S(DDP_HIP_SEQ_COST_XREF); p.wx = S(DDP_HIP_SEQ_COST_WX); p.uref = S(DDP_HIP_SEQ_COST_UREF); p.wu = S(DDP_HIP_SEQ_COST_WU);
   return p;
 }
@@ -1425,7 +1433,7 @@ int lin_setup(ddp_hip_ctx* ctx) {
   const LinPlan& pl = ctx->plan;
   if (pl.refuse) return pl.refuse;
   if (pl.ws_lin)
-    HIP_TRY(hipMalloc(&ctx->lin_ws, sizeof(double) * (size_t)(d.batch * d.T * ((int64_t)pl.ncfg * d.nv * rbd::QC_STRIDE + (int64_t)pl.nvcfg * d.nv * rbd::VC_STRIDE))));
+    HIP_TRY(hipMalloc(&ctx->lin_ws, sizeof(double) * (size_t)(d.batch * d.T * (lin_qc_per_bt(ctx) + (int64_t)pl.nvcfg * d.nv * rbd::VC_STRIDE))));
   if (pl.ws_qws) {
     const int64_t BT = d.batch * d.T;
     // With the spine pre-pass forked ahead of the torque rows (LIN_FORK_SPINE) only the first slice's pre-pass runs beside them.

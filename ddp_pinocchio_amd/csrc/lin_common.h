@@ -15,7 +15,10 @@ struct LinParams {
   int32_t has_tensors;
   double *eq_xk, *eq_fxk, *eq_c;   // large-model constraint chain workspace: x_1..x_K | f_x(x_1..x_{K-1}) | base jacobian
   double* vcache;   // [batch*T][2nv+1][nv*VC_STRIDE]: (q, v)-dependent part at (q,v), (q, v+eps e_i), (q+eps e_i, v)
-  double* qcache;   // [batch*T][nv+1][nv*QC_STRIDE]: q-dependent part of the ABA at the base q and at q + eps e_i (mode 2)
+  double* qcache;   // [batch*T][nv+1][nv*QC_STRIDE]: q-dependent part of the ABA at the base q and at q + eps e_i (mode 2);
+                    // with qc_sparse, per (instance, t): the base block and the records a step changes (lin_static.hip: QcLayout)
+  int64_t qc_bt;    // doubles per (instance, t) of the q-cache: ncfg * nv * QC_STRIDE, or QcLayout::WORDS
+  int32_t qc_sparse;   // LinPlan::qc_sparse
   int32_t skip_qv_mirror;   // static stencil: do not write the mirror images f_xx(:, i, j), f_uu(:, i, j), i < j, of the symmetric pairs --
                             // the backward sweep never reads them when it knows the tensors symmetric (bwd_split.h: only the columns
                             // j >= c of slab c); formed on demand for any other reader (lin.hip: lin_materialize_fxx)
@@ -53,6 +56,7 @@ enum class StaticLevel {
 };
 int lin_static_launch(ddp_hip_ctx* ctx, const LinParams& p, StaticLevel level);   // DDP_HIP_OK or an error code
 int64_t lin_static_ws_per_bt(const DevModel& m);
+int64_t lin_static_qc_per_bt(int topo);   // doubles per (instance, t) of the base + deltas q-cache of a compiled-in topology (LinPlan::qc_sparse)
 
 // analytic first order / mode-1 second order of large tree models (lin_analytic.hip): stage 0 = f_x, f_u at the
 // trajectory points (problem.hpp:463-503), stage 1 = forward differences of those jacobians (problem.hpp:67-150)

@@ -1,7 +1,8 @@
 // lin_plan.cpp -- which kernels a context's linearisation runs: one pure function, no HIP calls, and the
 // development switches it is a function of, read from the environment.
 // With -DLIN_PLAN_TABLE the file is a program that prints the plan of every combination of its inputs (tests/test_lin_plan.py),
-// or, as `lin_plan_table schedule`, the schedule of the flagship plan under the environment's switches (tests/test_lin_overlap.py).
+// or, as `lin_plan_table schedule` / `lin_plan_table caches`, the schedule / the cache layout of the flagship plan under the
+// environment's switches (tests/test_lin_overlap.py, tests/test_sparse_caches.py).
 #include <stdlib.h>
 
 #include "internal.h"
@@ -18,6 +19,7 @@ DevSwitches read_switches() {
   sw.fxx_full = on("DDP_HIP_FXX_FULL");
   sw.no_static = on("DDP_HIP_NO_STATIC");
   sw.no_qcache = on("DDP_HIP_NO_QCACHE");
+  sw.qcache_dense = on("DDP_HIP_QCACHE_DENSE");
   sw.cfg_full_aba = on("DDP_HIP_CFG_FULL_ABA");
   sw.ana_own_aba = on("DDP_HIP_ANA_OWN_ABA");
   sw.ana_split = on("DDP_HIP_ANA_SPLIT");
@@ -76,6 +78,8 @@ LinPlan lin_plan_decide(const DevModel& m, const Dims& d, uint32_t flags, const 
   else if (pl.ncfg > 1) pl.second = pl.topo ? LinSecond::Mode2Static : LinSecond::Mode2Caches;
   else pl.second = LinSecond::Mode2Plain;
   pl.ws_qws2 = pl.second == LinSecond::Mode2Static && sw.cfg_full_aba;
+  // base + deltas q-cache: the static stencil's readers alone know it (the full-ABA configuration level reads whole blocks)
+  pl.qc_sparse = pl.second == LinSecond::Mode2Static && !sw.qcache_dense && !sw.cfg_full_aba;
   // (with DDP_HIP_NO_QCACHE on forward-differenced jacobians the two marks below are set although Mode2Plain runs: DESIGN.md 4j)
   pl.skip_top = pl.topo && mode == 2 && tensors && !sw.fxx_full;
   pl.skip_qv_mirror = pl.skip_top && sweep_sym_ok;   // only for a sweep that never reads the mirror images
@@ -120,7 +124,7 @@ LinPlan lin_plan_decide(const DevModel& m, const Dims& d, uint32_t flags, const 
 // argument checks let the combination through to lin_setup (ctx.hip: a pendulum has nv = 1 and no free flyer; a free flyer
 // leaves nj = nv - 5 >= 1 joints and is refused in mode 1 and under the config constraint; no constraint kind, no rows).
 int main(int argc, char** argv) {
-  if (argc > 1 && argv[1][0] == 's') {
+  if (argc > 1 && (argv[1][0] == 's' || argv[1][0] == 'c')) {
     // `schedule`: the forks of the flagship plan (Talos-size tree on its compiled-in topology, mode 2, forward-differenced first
     // order) under the switches of this process's environment (tests/test_lin_overlap.py)
     DevModel m{};
@@ -128,6 +132,8 @@ int main(int argc, char** argv) {
     Dims d{};
     d.T = 3; d.batch = 2; d.nv = 38; d.n = 76; d.m = 38; d.nx = 76;
     const LinPlan p = lin_plan_decide(m, d, 0u, read_switches(), 1, true);
+    // `caches`: the q-cache layout of the same plan (tests/test_sparse_caches.py)
+    if (argv[1][0] == 'c') { printf("qc_sparse %d ncfg %d nvcfg %d\n", (int)p.qc_sparse, p.ncfg, p.nvcfg); return 0; }
     printf("forks %u topo %d\n", p.forks, p.topo);
     return 0;
   }

@@ -74,6 +74,48 @@ bool topo_matches(const DevModel& m) {
   return true;
 }
 
+// ---- the q-cache as a base block and deltas (LinPlan::qc_sparse) ---------------------------------------------------------
+// In the local-frame ABA, record K of configuration 1+g (q_g stepped) differs from the base record in E | r (12 words) if
+// K == g, and in U | 1/D | Ia (28 words) if K is a strict ancestor of g; everything else is the base record bit for bit
+// ("configuration level by splice" below).  Per (instance, t) the cache therefore holds
+//   the base block        [N][QC_STRIDE]        at 0       configuration 0, the layout every base reader knows
+//   the delta blocks      [N][12 + MAXD * 28]   at DELTA   of stepped joint g: E | r of g at q_g + eps, then U | 1/D | Ia of g's
+//                                                          strict ancestors at configuration 1+g, root first (by depth)
+// (padded to the deepest joint's depth: 143 KB per (instance, t) for the Talos-like tree, base block included, against 474 KB
+// for its 39 whole blocks)
+template <class T>
+struct QcLayout {
+  static constexpr int N = T::N, ER = 12, UD = rbd::QC_STRIDE - ER;
+  static constexpr int max_depth() {
+    int best = 1;
+    for (int k = 0; k < N; ++k) { int d = 0; for (int a = T::parent[k]; a >= 0; a = T::parent[a]) ++d; if (d > best) best = d; }
+    return best;
+  }
+  static constexpr int MAXD = max_depth();
+  static constexpr int DW = ER + MAXD * UD;                          // doubles per delta block
+  static constexpr int DELTA = N * rbd::QC_STRIDE, WORDS = DELTA + N * DW;
+  static constexpr int PATH0 = DELTA + ER;                           // path record (g, d) at PATH0 + g * DW + d * UD
+};
+// strict ancestors of every joint as bit masks (bit K of anc[g] <=> K is a strict ancestor of g): what a row wave selects by.
+// The ancestors of a joint have smaller indices than it, so among the ancestors of g the one of depth d is the d-th set bit
+template <class T> struct AncTab { unsigned long long anc[T::N]; };
+template <class T> constexpr AncTab<T> make_anc_tab() {
+  static_assert(T::N <= 64, "ancestor masks are 64 bits wide");
+  AncTab<T> t{};
+  for (int k = 0; k < T::N; ++k) for (int a = T::parent[k]; a >= 0; a = T::parent[a]) t.anc[k] |= 1ull << a;
+  return t;
+}
+template <class T> __device__ const AncTab<T> g_anc_tab = make_anc_tab<T>();
+// Where word e of joint K's record at configuration 1+g lives, counted from the (instance, t)'s q-cache (g = -1, anc = 0: the
+// base configuration).  A blend of finished offsets by 0 / 1 weights: no control flow
+template <class T>
+__device__ __forceinline__ int qc_word(int g, unsigned long long anc, int K, int e) {
+  using L = QcLayout<T>;
+  const int d = __popcll(anc & ((1ull << K) - 1ull));                // depth of K, where K is an ancestor of g
+  const int base = K * rbd::QC_STRIDE + e, own = L::DELTA + g * L::DW + e, path = L::PATH0 + g * L::DW + d * L::UD + (e - L::ER);
+  const int w_own = (int)(e < L::ER) & (int)(K == g), w_path = (int)(e >= L::ER) & (int)((anc >> K) & 1ull);
+  return base + w_own * (own - base) + w_path * (path - base);
+}
 // ---- per-lane state ----------------------------------------------------------------------------------------------
 template <class T>
 struct TauState {
@@ -212,6 +254,23 @@ struct StageRegs {
       idx = idx < NPW ? idx : NPW - 1;
       const int K = K0 + idx / 19, e = idx % 19;
       rp[c] = qc[K * rbd::QC_STRIDE + e];
+    }
+#pragma unroll
+    for (int c = 0; c < CV; ++c) {
+      int idx = c * LBS + lane;
+      idx = idx < NVW ? idx : NVW - 1;
+      rv[c] = vc[K0 * rbd::VC_STRIDE + idx];
+    }
+  }
+  // the same words from the base + deltas layout: qc0 the (instance, t)'s q-cache, the row's configuration 1+g (qc_word)
+  template <class T>
+  __device__ __forceinline__ void load_sparse(const double* __restrict__ qc0, int g, unsigned long long anc, const double* __restrict__ vc, int lane) {
+#pragma unroll
+    for (int c = 0; c < CP; ++c) {
+      int idx = c * LBS + lane;
+      idx = idx < NPW ? idx : NPW - 1;
+      const int K = K0 + idx / 19, e = idx % 19;
+      rp[c] = qc0[qc_word<T>(g, anc, K, e)];
     }
 #pragma unroll
     for (int c = 0; c < CV; ++c) {
@@ -526,7 +585,8 @@ __device__ __forceinline__ void rowblock_emit(const ST& S, int lane, int i, int 
 // PACK (pairs only): the output stage writes packed records.  An instantiation of its own because this kernel sits at its
 // register bound: with the layout picked at run time inside the stage it gains scratch (132 -> 148-164 B per lane in three forms
 // tried), as a template parameter the contract-layout kernel is untouched and the record one needs no scratch
-template <class T, bool ROWS, bool PACK = false>
+// SP (rows only): the q-cache is a base block and deltas; the staged LDS image is the same, word by word
+template <class T, bool ROWS, bool PACK = false, bool SP = false>
 __global__ __launch_bounds__(LBS, ROWS ? 1 : 3) void lin_static_tau_kernel(LinParams p) {
   constexpr int nv = T::N, n = 2 * nv;
   constexpr int TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS, G = ROWS ? 2 * nv : GU;
@@ -548,11 +608,14 @@ __global__ __launch_bounds__(LBS, ROWS ? 1 : 3) void lin_static_tau_kernel(LinPa
     i += n; j += n; cfg = 0; vcfg = 0;
   }
   const double eps = sqrt(sqrt(DBL_EPSILON));
-  const double* __restrict__ qc = p.qcache + (bt * (nv + 1) + cfg) * (int64_t)nv * rbd::QC_STRIDE;
+  static_assert(ROWS || !SP, "the pairs read the base block alone");
+  const double* __restrict__ qc = p.qcache + bt * p.qc_bt + (SP ? 0 : cfg * (nv * rbd::QC_STRIDE));
   const double* __restrict__ vc = p.vcache + (bt * (2 * nv + 1) + vcfg) * (int64_t)nv * rbd::VC_STRIDE;
   const double* __restrict__ xg = p.x + ((int64_t)b * (Tn + 1) + t) * n;
   const double* __restrict__ ug = p.u + ((int64_t)b * Tn + t) * nv;
   const int iu = i - n, ju = j - n;
+  const int gq = cfg - 1;                                                         // the stepped joint, -1: none (SP)
+  [[maybe_unused]] const unsigned long long ganc = SP && cfg > 0 ? g_anc_tab<T>.anc[gq] : 0ull;
   // the staged operands are dead once the acceleration pass is over, the output stage's buffers (rows: RowStage, pairs: OutStage)
   // are not alive before: one LDS region for all of them (the evaluation and the output stage are a barrier apart)
   __shared__ union TauLds { double P[nv * PS + nv * rbd::VC_STRIDE]; RowStage<nv> S; OutStage<nv, LBS / 2> O; } s_lds;
@@ -564,8 +627,8 @@ __global__ __launch_bounds__(LBS, ROWS ? 1 : 3) void lin_static_tau_kernel(LinPa
   StageRegs<nv, 0, (KH > 0) ? KH : 1> lower;   // (KH == 0: joint 0 once more, harmless)            // joints 0 .. KH-1: in flight through the first half of the leaf -> root pass
   {
     StageRegs<nv, KH, nv> upper;
-    upper.load(qc, vc, lane);
-    lower.load(qc, vc, lane);
+    if constexpr (SP) { upper.template load_sparse<T>(qc, gq, ganc, vc, lane); lower.template load_sparse<T>(qc, gq, ganc, vc, lane); }
+    else { upper.load(qc, vc, lane); lower.load(qc, vc, lane); }
     upper.park(s_P, s_V, lane);
     rbd::coop_sync<true>();                         // one wave per workgroup: LDS is in order, no vmcnt(0) behind this fence
   }
@@ -838,8 +901,9 @@ __device__ __forceinline__ void vel_down_all(const C& c, VelState<T>& s, std::in
 #ifndef DDP_VEL_PAIR_WAVES
 #define DDP_VEL_PAIR_WAVES 2
 #endif
-template <class T, bool ROWS>
+template <class T, bool ROWS, bool SP = false>
 __global__ __launch_bounds__(LBS, ROWS ? 3 : DDP_VEL_PAIR_WAVES) void lin_static_vel_kernel(LinParams p) {
+  static_assert(ROWS || !SP, "the pairs read the base block alone");
   constexpr int nv = T::N, n = 2 * nv;
   constexpr int TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS, G = ROWS ? nv : GU;
   const int64_t bt = blockIdx.x / G;
@@ -868,7 +932,7 @@ __global__ __launch_bounds__(LBS, ROWS ? 3 : DDP_VEL_PAIR_WAVES) void lin_static
   double* s_P = s_lds.P;
   VelCtx<0, rbd::QC_STRIDE> c;
   c.m = p.model;
-  c.qc = p.qcache + (bt * (nv + 1) + cfg) * (int64_t)nv * rbd::QC_STRIDE;
+  c.qc = p.qcache + bt * p.qc_bt + (SP ? 0 : cfg * (nv * rbd::QC_STRIDE));
   c.qp = s_P;
   c.xg = p.x + ((int64_t)b * (Tn + 1) + t) * n;
   c.ug = p.u + ((int64_t)b * Tn + t) * nv;
@@ -878,8 +942,15 @@ __global__ __launch_bounds__(LBS, ROWS ? 3 : DDP_VEL_PAIR_WAVES) void lin_static
   {
     constexpr int NW = nv * rbd::QC_STRIDE, CW = (NW + LBS - 1) / LBS;
     double rq[CW];
+    // (SP: word by word from the base block or the row's delta block -- the same image as the dense block of configuration 1+g)
+    [[maybe_unused]] const unsigned long long ganc = SP ? g_anc_tab<T>.anc[g] : 0ull;
 #pragma unroll
-    for (int r = 0; r < CW; ++r) { const int idx = r * LBS + lane; rq[r] = c.qc[idx < NW ? idx : NW - 1]; }
+    for (int r = 0; r < CW; ++r) {
+      int idx = r * LBS + lane;
+      idx = idx < NW ? idx : NW - 1;
+      if constexpr (SP) idx = qc_word<T>(g, ganc, idx / rbd::QC_STRIDE, idx % rbd::QC_STRIDE);
+      rq[r] = c.qc[idx];
+    }
 #pragma unroll
     for (int r = 0; r < CW; ++r) { const int idx = r * LBS + lane; s_P[idx < NW ? idx : NW - 1] = rq[r]; }
     c.qc = s_P;
@@ -1180,7 +1251,7 @@ __device__ __forceinline__ void cfg_setup(CfgCtx& c, const LinParams& p, const D
   valid = pid < TRI;
   tri_index(valid ? pid : 0, nv, c.i, c.j);
   c.m = model;
-  c.qc0 = qcache + (bt * (nv + 1)) * (int64_t)nv * rbd::QC_STRIDE;
+  c.qc0 = qcache + bt * p.qc_bt;          // (whole blocks: LinPlan::qc_sparse is off with the full-ABA level)
   c.xg = xs + ((int64_t)b * (Tn + 1) + t) * n;
   c.ug = us + ((int64_t)b * Tn + t) * nv;
   c.W = ws + (int64_t)blockIdx.x * (nv * WS_PER_JOINT * LBS) + lane;
@@ -1306,8 +1377,9 @@ __device__ __forceinline__ bool xcd_slot(int nb, int& btl, int& g) {
 
 // One lane per pair: its spine from the deepest joint to the root (the expressions of qv_chain_up).  Joint indices are
 // run-time values here, so the per-joint constants come from the model in memory; register arrays are indexed by constants only.
-template <class T>
-__global__ __launch_bounds__(LBS) void lin_static_spine_kernel(const DevModel* __restrict__ model, const double* __restrict__ qcache,
+// SP: the stepped configurations' records come from the delta blocks (they are exactly the records a step changes)
+template <class T, bool SP>
+__global__ __launch_bounds__(LBS) void lin_static_spine_kernel(const DevModel* __restrict__ model, const double* __restrict__ qcache, int64_t qc_bt,
                                                                const double* __restrict__ vcache, double* __restrict__ spine, int64_t bt0, int nb) {
   constexpr int nv = T::N, TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS, NREC = spine_records<T>();
   int btl, g;
@@ -1318,7 +1390,8 @@ __global__ __launch_bounds__(LBS) void lin_static_spine_kernel(const DevModel* _
   const DevModel& m = *model;
   const int i = tab.pi[slot], j = tab.pj[slot];
   const int rstride = tab.rstride[slot];
-  const double* __restrict__ qc0 = qcache + ((bt0 + btl) * (nv + 1)) * (int64_t)nv * rbd::QC_STRIDE;
+  [[maybe_unused]] const unsigned long long anc_i = tab.anc[i], anc_j = tab.anc[j];
+  const double* __restrict__ qc0 = qcache + (bt0 + btl) * qc_bt;
   const double* __restrict__ vc0 = vcache + ((bt0 + btl) * (2 * nv + 1)) * (int64_t)nv * rbd::VC_STRIDE;   // entry 0: the base (q, v)
   double* __restrict__ out = spine + ((int64_t)btl * NREC + tab.rbase[slot]) * SREC;
   double Ia[21];
@@ -1334,8 +1407,17 @@ __global__ __launch_bounds__(LBS) void lin_static_spine_kernel(const DevModel* _
       const unsigned long long mc = tab.mask[c];
       const int cfg_p = (c == i || c == j) ? 1 + c : 0;
       const int cfg_i = ((mc >> i) & 1) ? 1 + i : (((mc >> j) & 1) ? 1 + j : 0);   // (c == prev: on the spine, the value just formed)
-      const double* Pg = qc0 + ((int64_t)cfg_p * nv + c) * rbd::QC_STRIDE;
-      const double* Ig = qc0 + ((int64_t)cfg_i * nv + c) * rbd::QC_STRIDE + 19;
+      const double *Pg, *Ig;
+      if constexpr (SP) {
+        using L = QcLayout<T>;
+        Pg = qc0 + (cfg_p ? L::DELTA + c * L::DW : c * rbd::QC_STRIDE);
+        // (the depth of c among the stepped joint's ancestors by counting, not from the table: no load ahead of the Ia loads)
+        const int dc = __popcll((((mc >> i) & 1) ? anc_i : anc_j) & ((1ull << c) - 1ull));
+        Ig = qc0 + (cfg_i ? L::PATH0 + (cfg_i - 1) * L::DW + dc * L::UD + 7 : c * rbd::QC_STRIDE + 19);
+      } else {
+        Pg = qc0 + ((int64_t)cfg_p * nv + c) * rbd::QC_STRIDE;
+        Ig = qc0 + ((int64_t)cfg_i * nv + c) * rbd::QC_STRIDE + 19;
+      }
       double P[12], Ic[21];
 #pragma unroll
       for (int k = 0; k < 12; ++k) P[k] = Pg[k];
@@ -1378,8 +1460,11 @@ __global__ __launch_bounds__(LBS) void lin_static_spine_kernel(const DevModel* _
 // (re-reads of the (instance, t)'s q-cache block and spine records, mostly the same address in every lane).  Branch-free:
 // selections by integer arithmetic and one select between two finished pointers -- a conditional address computation becomes a
 // branch, and control flow in the middle of the evaluation tears it away from its operand loads.
-template <class T>
+// SP: records of configuration 1+g come from the delta block of g (E | r of g, U | 1/D | Ia of g's ancestors by depth); the
+// selections keep their form, only the offsets differ
+template <class T, bool SP>
 struct SpliceCtx {
+  using L = QcLayout<T>;
   static constexpr int UQS = 1;
   const DevModel* m;
   const double* __restrict__ qc0;   // q-cache of the (instance, t): configuration c at qc0 + c * nv * QC_STRIDE
@@ -1392,7 +1477,8 @@ struct SpliceCtx {
   unsigned long long ai, aj;        // their strict ancestors (SpineTab::anc): K is in S_i <=> bit K of ai
   template <int K> __device__ __forceinline__ const double* er(double*) const {
     const int own = (int)(K == i) | (int)(K == j);
-    return qc0 + (K * rbd::QC_STRIDE + own * ((1 + K) * T::N * rbd::QC_STRIDE));
+    if constexpr (SP) return qc0 + (K * rbd::QC_STRIDE + own * (L::DELTA + K * L::DW - K * rbd::QC_STRIDE));
+    else return qc0 + (K * rbd::QC_STRIDE + own * ((1 + K) * T::N * rbd::QC_STRIDE));
   }
   template <int K> __device__ __forceinline__ const double* ud() const {
     constexpr int DK = depth_of<T>(K);
@@ -1400,7 +1486,9 @@ struct SpliceCtx {
     else {
       const int si = (int)((ai >> K) & 1), sj = (int)((aj >> K) & 1);
       const int cfg = (si & (sj ^ 1)) * (1 + i) + (sj & (si ^ 1)) * (1 + j);
-      const double* p = qc0 + ((cfg * T::N + K) * rbd::QC_STRIDE + 12);
+      // (SP: cfg - 1 is the stepped joint whose delta block holds the record, at this joint's depth)
+      const double* p = SP ? qc0 + ((K * rbd::QC_STRIDE + 12) + (si ^ sj) * (L::PATH0 - L::DW + DK * L::UD - (K * rbd::QC_STRIDE + 12)) + cfg * L::DW)
+                           : qc0 + ((cfg * T::N + K) * rbd::QC_STRIDE + 12);
       if constexpr (!spine_joint<T>(K)) return p;
       else {
         const double* q = spb + (rbase + DK * rstride) * SREC;
@@ -1411,7 +1499,7 @@ struct SpliceCtx {
   // The same addresses, written differently on purpose: recognised as the same values, the per-lane pointers of the leaf -> root
   // pass would stay alive until the acceleration pass comes by, and the kernel would not fit two waves per SIMD
   template <int K> __device__ __forceinline__ const double* er_down(double*) const {
-    const int64_t own = (K - i) * (K - j) == 0 ? (int64_t)(1 + K) * T::N * rbd::QC_STRIDE : 0;
+    const int64_t own = (K - i) * (K - j) == 0 ? (SP ? (int64_t)(L::DELTA + K * L::DW - K * rbd::QC_STRIDE) : (int64_t)(1 + K) * T::N * rbd::QC_STRIDE) : 0;
     return qc0 + K * rbd::QC_STRIDE + own;
   }
   template <int K> __device__ __forceinline__ const double* ud_down() const {
@@ -1420,7 +1508,8 @@ struct SpliceCtx {
     else {
       const bool si = (ai >> K) & 1, sj = (aj >> K) & 1;
       const int cfg = sj ? 1 + j : (si ? 1 + i : 0);
-      const double* p = qc0 + (int64_t)cfg * (T::N * rbd::QC_STRIDE) + (K * rbd::QC_STRIDE + 12);
+      const double* p = SP ? qc0 + (cfg ? (int64_t)(cfg - 1) * L::DW + (L::PATH0 + DK * L::UD) : (int64_t)(K * rbd::QC_STRIDE + 12))
+                           : qc0 + (int64_t)cfg * (T::N * rbd::QC_STRIDE) + (K * rbd::QC_STRIDE + 12);
       if constexpr (!spine_joint<T>(K)) return p;
       else {
         const double* q = spb + ((int64_t)rbase + (int64_t)DK * rstride) * SREC;
@@ -1446,11 +1535,11 @@ struct SpliceCtx {
     }
   }
 };
-template <int NV, class T>
-__device__ __forceinline__ double lane_v(const SpliceCtx<T>& c, int K) { return c.xg[NV + K]; }   // q directions do not change v
+template <int NV, class T, bool SP>
+__device__ __forceinline__ double lane_v(const SpliceCtx<T, SP>& c, int K) { return c.xg[NV + K]; }   // q directions do not change v
 
 // One wave = 64 (q_i, q_j) pairs, i < j: the velocity-level pair kernel on spliced operands
-template <class T>
+template <class T, bool SP>
 __global__ __launch_bounds__(LBS, 2) void lin_static_cfg_pair_kernel(LinParams p, const double* __restrict__ spine, int64_t bt0, int nb) {
   constexpr int nv = T::N, n = 2 * nv;
   constexpr int TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS, NREC = spine_records<T>();
@@ -1466,13 +1555,13 @@ __global__ __launch_bounds__(LBS, 2) void lin_static_cfg_pair_kernel(LinParams p
   const int sc = valid ? slot : 0;
   const SpineTab<T>& tab = g_spine_tab<T>;
   __shared__ OutStage<nv> S;
-  SpliceCtx<T> c;
+  SpliceCtx<T, SP> c;
   c.i = tab.pi[sc]; c.j = tab.pj[sc];
   c.ai = tab.anc[c.i];
   c.aj = tab.anc[c.j];
   c.rbase = tab.rbase[sc]; c.rstride = tab.rstride[sc];
   c.m = p.model;
-  c.qc0 = p.qcache + (bt * (nv + 1)) * (int64_t)nv * rbd::QC_STRIDE;
+  c.qc0 = p.qcache + bt * p.qc_bt;
   c.xg = p.x + ((int64_t)b * (Tn + 1) + t) * n;
   c.ug = p.u + ((int64_t)b * Tn + t) * nv;
   c.spb = spine + (int64_t)btl * NREC * SREC;
@@ -1539,7 +1628,7 @@ __global__ __launch_bounds__(LBS) void lin_static_first_kernel(LinParams p, cons
   const int64_t t = bt % Tn;
   const bool valid = lane < nv;
   const double eps = DIAG ? sqrt(sqrt(DBL_EPSILON)) : sqrt(DBL_EPSILON);
-  const double* __restrict__ qc0 = qcache + (bt * p.ncfg) * (int64_t)nv * rbd::QC_STRIDE;
+  const double* __restrict__ qc0 = qcache + bt * p.qc_bt;      // the base block: first in either layout
   const double* __restrict__ xg = xs + ((int64_t)b * (Tn + 1) + t) * n;
   const double* __restrict__ ug = us + ((int64_t)b * Tn + t) * nv;
   __shared__ double s_q[(nv + 1) * (nv + 1)];
@@ -1617,6 +1706,9 @@ __global__ __launch_bounds__(LBS) void lin_static_first_kernel(LinParams p, cons
 // q + eps e_i).  The chain-wise sweep of the configuration level, reduced to what the caches hold: rbd::aba_qpart
 // (E | r | U | 1/D | Ia per joint) and, at the base velocity, rbd::aba_vpart_cached (cb | pA0 | Ia cb) -- v-cache entry 0
 // for the base configuration, nv+1+i for configuration 1+i.
+// SP (LinPlan::qc_sparse): the lane of configuration 1+g stores the records its step changes -- E | r of g and U | 1/D | Ia of
+// g's strict ancestors -- into the delta block of g (QcLayout), and everything else, like the base configuration's lane, onto the
+// base block.  The chain itself is the same in every lane (the v-part needs all of it).
 template <class T, int K>
 __device__ __forceinline__ void placement_static(const DevModel& m, double q, double* P) {
   const double* Rp = m.Rp[K];
@@ -1651,10 +1743,15 @@ __device__ __forceinline__ void placement_static(const DevModel& m, double q, do
   }
 }
 
+template <bool SP_>
 struct QvCtx {
+  static constexpr bool SP = SP_;
   const DevModel* __restrict__ m;
   const double* __restrict__ xg;
-  double* __restrict__ qc;     // this lane's q-cache block
+  double* qc;                  // this lane's q-cache block (SP: the base block of its (instance, t), which all of its lanes store onto)
+  double* qown;                // SP, a stepped configuration: E | r of the stepped joint, the head of its delta block
+  double* qpath;               // SP, a stepped configuration: the path records behind it ([depth][28])
+  unsigned long long anc;      // SP: strict ancestors of the stepped joint
   double* __restrict__ vc;     // this lane's v-cache block
   double* lvel;                // LDS: link velocities of the chain being swept
   int jn;                      // joint whose position this lane steps (-1: none)
@@ -1665,14 +1762,14 @@ struct QvState {
   double vel[T::N][6];
   double accI[T::N][21];
 };
-template <class T, int K>
-__device__ __forceinline__ void qv_placement(const QvCtx& c, double* P) {
+template <class T, int K, class C>
+__device__ __forceinline__ void qv_placement(const C& c, double* P) {
   double q = c.xg[K];
   if (K == c.jn) q = q + c.eps;
   placement_static<T, K>(*c.m, q, P);
 }
-template <class T, int K>
-__device__ __forceinline__ void qv_joint_vel(const QvCtx& c, const double* P, const double* vel_par, double* vel) {
+template <class T, int K, class C>
+__device__ __forceinline__ void qv_joint_vel(const C& c, const double* P, const double* vel_par, double* vel) {
   constexpr int o = T::prismatic[K] ? 3 : 0;
   const double* a = c.m->axis[K];
   const double vK = c.xg[T::N + K];
@@ -1686,8 +1783,8 @@ __device__ __forceinline__ void qv_joint_vel(const QvCtx& c, const double* P, co
 #pragma unroll
   for (int k = 0; k < 6; ++k) vel[k] += vJ[k];
 }
-template <class T, int K>
-__device__ __forceinline__ void qv_vel_from_root(const QvCtx& c, double* vel) {
+template <class T, int K, class C>
+__device__ __forceinline__ void qv_vel_from_root(const C& c, double* vel) {
   double P[12];
   qv_placement<T, K>(c, P);
   if constexpr (T::parent[K] >= 0) {
@@ -1698,8 +1795,8 @@ __device__ __forceinline__ void qv_vel_from_root(const QvCtx& c, double* vel) {
     qv_joint_vel<T, K>(c, P, nullptr, vel);
   }
 }
-template <class T, int K, int F, int E>
-__device__ __forceinline__ void qv_chain_down(const QvCtx& c, double* cur) {
+template <class T, int K, int F, int E, class C>
+__device__ __forceinline__ void qv_chain_down(const C& c, double* cur) {
   double P[12], vel[6];
   qv_placement<T, K>(c, P);
   if constexpr (T::parent[K] >= 0) qv_joint_vel<T, K>(c, P, cur, vel);
@@ -1709,8 +1806,8 @@ __device__ __forceinline__ void qv_chain_down(const QvCtx& c, double* cur) {
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (K < E) qv_chain_down<T, K + 1, F, E>(c, cur);
 }
-template <class T, int K, int F>
-__device__ __forceinline__ void qv_chain_up(const QvCtx& c, QvState<T>& s) {
+template <class T, int K, int F, class C>
+__device__ __forceinline__ void qv_chain_up(const C& c, QvState<T>& s) {
   constexpr int o = T::prismatic[K] ? 3 : 0;
   const double* a = c.m->axis[K];
   double P[12], IA[21], U[6], Ia[21], vel[6];
@@ -1750,22 +1847,32 @@ __device__ __forceinline__ void qv_chain_up(const QvCtx& c, QvState<T>& s) {
   rbd::sym6_mv(c.m->I6[K], vel, Iv);
   rbd::crf(vel, Iv, pA);
   rbd::sym6_mv(Ia, cb, Iac);
-  double* qo = c.qc + K * rbd::QC_STRIDE;
+  // where the two halves of the record go.  SP: a half the lane's step changes goes to its delta block; any other half IS the
+  // base record, bit for bit (the same instructions on the same operands in every lane), and is stored onto it: the lanes of an
+  // (instance, t) then write one line with one value instead of a line each.  Selected addresses, not predicated stores: with
+  // control flow in the chain the compiler contracts its products and sums differently from the dense kernel
+  double* qo_er = c.qc + K * rbd::QC_STRIDE;
+  double* qo_ud = qo_er + 12;
+  if constexpr (C::SP) {
+    constexpr int DK = depth_of<T>(K);       // (a constant expression: the table is not to be built at run time)
+    qo_er = K == c.jn ? c.qown : qo_er;
+    if constexpr (has_child<T>(K)) qo_ud = ((c.anc >> K) & 1ull) ? c.qpath + DK * QcLayout<T>::UD : qo_ud;
+  }
 #pragma unroll
-  for (int k = 0; k < 12; ++k) qo[k] = P[k];
+  for (int k = 0; k < 12; ++k) qo_er[k] = P[k];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) qo[12 + k] = U[k];
-  qo[18] = dinv;
+  for (int k = 0; k < 6; ++k) qo_ud[k] = U[k];
+  qo_ud[6] = dinv;
 #pragma unroll
-  for (int k = 0; k < 21; ++k) qo[19 + k] = Ia[k];
+  for (int k = 0; k < 21; ++k) qo_ud[7 + k] = Ia[k];
   double* vo = c.vc + K * rbd::VC_STRIDE;
 #pragma unroll
   for (int k = 0; k < 6; ++k) { vo[k] = cb[k]; vo[6 + k] = pA[k]; vo[12 + k] = Iac[k]; }
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (K > F) qv_chain_up<T, K - 1, F>(c, s);
 }
-template <class T, int K>
-__device__ __forceinline__ void qv_chain_at(const QvCtx& c, QvState<T>& s) {
+template <class T, int K, class C>
+__device__ __forceinline__ void qv_chain_at(const C& c, QvState<T>& s) {
   if constexpr (chain_end<T>(K)) {
     constexpr int F = chain_first<T>(K), P = T::parent[F];
     double cur[6] = {0, 0, 0, 0, 0, 0};
@@ -1778,12 +1885,12 @@ __device__ __forceinline__ void qv_chain_at(const QvCtx& c, QvState<T>& s) {
     qv_chain_up<T, K, F>(c, s);
   }
 }
-template <class T, int... Ks>
-__device__ __forceinline__ void qv_all(const QvCtx& c, QvState<T>& s, std::integer_sequence<int, Ks...>) {
+template <class T, class C, int... Ks>
+__device__ __forceinline__ void qv_all(const C& c, QvState<T>& s, std::integer_sequence<int, Ks...>) {
   (qv_chain_at<T, T::N - 1 - Ks>(c, s), ...);
 }
 
-template <class T>
+template <class T, bool SP>
 __global__ __launch_bounds__(LBS, 2) void lin_static_qvcache_kernel(LinParams p, const DevModel* __restrict__ model, const double* __restrict__ xs,
                                                                  double* __restrict__ qcache, double* __restrict__ vcache) {
   constexpr int nv = T::N, n = 2 * nv, MAXCH = max_chain<T>();
@@ -1798,10 +1905,16 @@ __global__ __launch_bounds__(LBS, 2) void lin_static_qvcache_kernel(LinParams p,
   const int64_t t = bt % Tn;
   __shared__ double s_vel[MAXCH * 6 * LBS];
   if (bt >= p.d.batch * Tn) return;                       // (no workgroup barrier below)
-  QvCtx c;
+  QvCtx<SP> c;
   c.m = model;
   c.xg = xs + ((int64_t)b * (Tn + 1) + t) * n;
-  c.qc = qcache + (bt * p.ncfg + cfgi) * (int64_t)nv * rbd::QC_STRIDE;
+  c.qc = qcache + bt * p.qc_bt + (SP ? 0 : cfgi * (nv * rbd::QC_STRIDE));
+  {
+    const int g = cfgi > 0 ? cfgi - 1 : 0;
+    c.qown = c.qc + (QcLayout<T>::DELTA + g * QcLayout<T>::DW);
+    c.qpath = c.qown + QcLayout<T>::ER;
+    c.anc = g_anc_tab<T>.anc[g];
+  }
   c.vc = vcache + (bt * p.nvcfg + (cfgi == 0 ? 0 : nv + cfgi)) * (int64_t)nv * rbd::VC_STRIDE;
   c.lvel = s_vel + lane;
   c.jn = cfgi - 1;
@@ -1854,7 +1967,7 @@ __global__ __launch_bounds__(LBS) void lin_static_vcache_kernel(LinParams p, con
   const int b = (int)(bt / Tn);
   const int64_t t = bt % Tn;
   if (lane >= nv) return;
-  const double* __restrict__ qc = qcache + (bt * (nv + 1)) * (int64_t)nv * rbd::QC_STRIDE;
+  const double* __restrict__ qc = qcache + bt * p.qc_bt;       // the base block
   const double* __restrict__ xg = xs + ((int64_t)b * (Tn + 1) + t) * n;
   double* __restrict__ vc = vcache + (bt * (2 * nv + 1) + 1 + lane) * (int64_t)nv * rbd::VC_STRIDE;
   double vel[nv][6];
@@ -1876,6 +1989,15 @@ int lin_static_supported(const DevModel& m) {
 // doubles of workspace one (instance, t) needs at the configuration level
 // (the larger of: the sweep's 8 doubles per joint and lane, which the first-order q columns and the full-ABA level need, and
 // the pairs' spine records)
+int64_t lin_static_qc_per_bt(int topo) {
+  if (topo == 1) return QcLayout<TopoTalos38>::WORDS;
+  if (topo == 2) return QcLayout<TopoChain6>::WORDS;
+#define DDP_TOPO_QC(ID, TOPO) if (topo == (ID) - 1) return QcLayout<TOPO>::WORDS;
+  DDP_TOPO_EXTRA(DDP_TOPO_QC)
+#undef DDP_TOPO_QC
+  return 0;
+}
+
 int64_t lin_static_ws_per_bt(const DevModel& m) {
   const int64_t nv = m.nv, TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS;
   int64_t rec = 0;
@@ -1888,6 +2010,26 @@ int64_t lin_static_ws_per_bt(const DevModel& m) {
     }
   const int64_t sweep = GU * nv * WS_PER_JOINT * LBS, splice = rec * SREC;
   return sweep > splice ? sweep : splice;
+}
+
+// the kernels that exist for both q-cache layouts, each launched in the form LinParams::qc_sparse names
+template <class T>
+static void launch_qvcache(const LinParams& p, int64_t BT, hipStream_t s) {
+  const dim3 grid((unsigned)((BT * p.ncfg + LBS - 1) / LBS));
+  if (p.qc_sparse) hipLaunchKernelGGL((lin_static_qvcache_kernel<T, true>), grid, dim3(LBS), 0, s, p, p.model, p.x, p.qcache, p.vcache);
+  else hipLaunchKernelGGL((lin_static_qvcache_kernel<T, false>), grid, dim3(LBS), 0, s, p, p.model, p.x, p.qcache, p.vcache);
+}
+template <class T>
+static void launch_tau_rows(const LinParams& p, int64_t BT, hipStream_t s) {
+  const dim3 grid((unsigned)(BT * 2 * T::N));
+  if (p.qc_sparse) hipLaunchKernelGGL((lin_static_tau_kernel<T, true, false, true>), grid, dim3(LBS), 0, s, p);
+  else hipLaunchKernelGGL((lin_static_tau_kernel<T, true>), grid, dim3(LBS), 0, s, p);
+}
+template <class T>
+static void launch_vel_rows(const LinParams& p, int64_t BT, hipStream_t s) {
+  const dim3 grid((unsigned)(BT * T::N));
+  if (p.qc_sparse) hipLaunchKernelGGL((lin_static_vel_kernel<T, true, true>), grid, dim3(LBS), 0, s, p);
+  else hipLaunchKernelGGL((lin_static_vel_kernel<T, true>), grid, dim3(LBS), 0, s, p);
 }
 
 // the first-order kernels along the q, v and (with_u) u directions: jacobian columns, or accelerations with p.accel_out set
@@ -1918,9 +2060,11 @@ static int launch_cfg_slices(ddp_hip_ctx* ctx, const LinParams& p, hipStream_t s
   for (int64_t bt0 = 0; bt0 < BT; bt0 += per) {
     const int nb = (int)(BT - bt0 < per ? BT - bt0 : per);
     const dim3 grid((unsigned)((nb + 7) / 8 * 8 * GU));
-    hipLaunchKernelGGL((lin_static_spine_kernel<T>), grid, dim3(LBS), 0, s, p.model, p.qcache, p.vcache, ctx->lin_qws, bt0, nb);
+    if (p.qc_sparse) hipLaunchKernelGGL((lin_static_spine_kernel<T, true>), grid, dim3(LBS), 0, s, p.model, p.qcache, p.qc_bt, p.vcache, ctx->lin_qws, bt0, nb);
+    else hipLaunchKernelGGL((lin_static_spine_kernel<T, false>), grid, dim3(LBS), 0, s, p.model, p.qcache, p.qc_bt, p.vcache, ctx->lin_qws, bt0, nb);
     if (rows_done) { HIP_TRY(hipStreamWaitEvent(s, rows_done, 0)); rows_done = nullptr; }
-    hipLaunchKernelGGL((lin_static_cfg_pair_kernel<T>), grid, dim3(LBS), 0, s, p, ctx->lin_qws, bt0, nb);
+    if (p.qc_sparse) hipLaunchKernelGGL((lin_static_cfg_pair_kernel<T, true>), grid, dim3(LBS), 0, s, p, ctx->lin_qws, bt0, nb);
+    else hipLaunchKernelGGL((lin_static_cfg_pair_kernel<T, false>), grid, dim3(LBS), 0, s, p, ctx->lin_qws, bt0, nb);
   }
   return DDP_HIP_OK;
 }
@@ -1941,7 +2085,7 @@ static int launch_second_order(ddp_hip_ctx* ctx, const LinParams& p) {
   hipStream_t s0 = ctx->stream;
   if (spine_ahead) HIP_TRY(lin_fork(ctx));
   hipLaunchKernelGGL((lin_static_first_kernel<T, 3, true>), dim3((unsigned)BT), dim3(LBS), 0, s0, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
-  hipLaunchKernelGGL((lin_static_tau_kernel<T, true>), dim3((unsigned)(BT * 2 * nv)), dim3(LBS), 0, s0, p);
+  launch_tau_rows<T>(p, BT, s0);
   if (fork_cfg) {
     if (spine_ahead) HIP_TRY(hipEventRecord(ctx->lin_ev_rows, s0));
     else HIP_TRY(lin_fork(ctx));                    // (taken behind the rows: nothing more to wait for)
@@ -1950,7 +2094,7 @@ static int launch_second_order(ddp_hip_ctx* ctx, const LinParams& p) {
   }
   if (p.pack) hipLaunchKernelGGL((lin_static_tau_kernel<T, false, true>), dim3((unsigned)(BT * GU)), dim3(LBS), 0, s0, p);
   else hipLaunchKernelGGL((lin_static_tau_kernel<T, false, false>), dim3((unsigned)(BT * GU)), dim3(LBS), 0, s0, p);
-  hipLaunchKernelGGL((lin_static_vel_kernel<T, true>), dim3((unsigned)(BT * nv)), dim3(LBS), 0, s0, p);
+  launch_vel_rows<T>(p, BT, s0);
   hipLaunchKernelGGL((lin_static_vel_kernel<T, false>), dim3((unsigned)(BT * GU)), dim3(LBS), 0, s0, p);
   if (!fork_cfg) { const int rc_ = launch_cfg_slices<T>(ctx, p, s0, nullptr); if (rc_ != DDP_HIP_OK) return rc_; }
   return DDP_HIP_OK;
@@ -1961,15 +2105,15 @@ static int lin_static_launch_t(ddp_hip_ctx* ctx, const LinParams& p, StaticLevel
   const int64_t BT = ctx->d.batch * ctx->d.T;
   constexpr int nv = T::N, TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS;
   if (level == StaticLevel::Torque) {             // torque-level points (replaces lin_offdiag_kernel<NJ, 3>)
-    hipLaunchKernelGGL((lin_static_tau_kernel<T, true>), dim3((unsigned)(BT * 2 * nv)), dim3(LBS), 0, ctx->stream, p);
+    launch_tau_rows<T>(p, BT, ctx->stream);
     if (p.pack) hipLaunchKernelGGL((lin_static_tau_kernel<T, false, true>), dim3((unsigned)(BT * GU)), dim3(LBS), 0, ctx->stream, p);
     else hipLaunchKernelGGL((lin_static_tau_kernel<T, false, false>), dim3((unsigned)(BT * GU)), dim3(LBS), 0, ctx->stream, p);
   } else if (level == StaticLevel::Caches) {
-    hipLaunchKernelGGL((lin_static_qvcache_kernel<T>), dim3((unsigned)((BT * p.ncfg + LBS - 1) / LBS)), dim3(LBS), 0, ctx->stream, p, p.model, p.x, p.qcache, p.vcache);
+    launch_qvcache<T>(p, BT, ctx->stream);
     if (p.nvcfg > 1) hipLaunchKernelGGL((lin_static_vcache_kernel<T>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.x, p.qcache, p.vcache);
   } else if (level == StaticLevel::AccelXU || level == StaticLevel::AccelX) {   // -> p.accel_out, after the base caches
     if (!p.accel_out) return DDP_HIP_E_ARG;
-    hipLaunchKernelGGL((lin_static_qvcache_kernel<T>), dim3((unsigned)((BT * p.ncfg + LBS - 1) / LBS)), dim3(LBS), 0, ctx->stream, p, p.model, p.x, p.qcache, p.vcache);
+    launch_qvcache<T>(p, BT, ctx->stream);
     launch_first_columns<T>(ctx, p, level == StaticLevel::AccelXU);
   } else if (level == StaticLevel::FirstOrder) {
     launch_first_columns<T>(ctx, p, true);
@@ -2004,7 +2148,7 @@ static int lin_static_launch_t(ddp_hip_ctx* ctx, const LinParams& p, StaticLevel
     if (k >= 1) HIP_TRY(hipStreamWaitEvent(s0, ctx->lin_ev_dn[0], 0));
     if (k >= 2) HIP_TRY(hipStreamWaitEvent(s0, ctx->lin_ev_dn[1], 0));
   } else if (level == StaticLevel::Velocity) {
-    hipLaunchKernelGGL((lin_static_vel_kernel<T, true>), dim3((unsigned)(BT * nv)), dim3(LBS), 0, ctx->stream, p);
+    launch_vel_rows<T>(p, BT, ctx->stream);
     hipLaunchKernelGGL((lin_static_vel_kernel<T, false>), dim3((unsigned)(BT * GU)), dim3(LBS), 0, ctx->stream, p);
   }
   HIP_TRY(hipGetLastError());
