@@ -577,6 +577,19 @@ __device__ __forceinline__ void rowblock_emit(const ST& S, int lane, int i, int 
   }
 }
 
+// The output stages read their parameters from the kernel-argument segment (LinParams is every emitting kernel's first argument),
+// and only behind the evaluation and a sched_barrier: taken from `p` they would be loaded at kernel entry and stay live through the
+// whole evaluation, and the scalar registers would spill.  Through the address-space-4 pointer the reads stay scalar loads.
+typedef __attribute__((address_space(4))) const LinParams* kernarg_t;
+__device__ __forceinline__ kernarg_t kernarg_params() { return (kernarg_t)__builtin_amdgcn_kernarg_segment_ptr(); }
+// ... and the part of them the off-diagonal output stage (offdiag_emit) takes, as a LinParams of its own
+__device__ __forceinline__ LinParams emit_params() {
+  const kernarg_t kp = kernarg_params();
+  LinParams po;
+  po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top; po.pack = kp->pack;
+  return po;
+}
+
 // ---- torque level: the (x_i, u_j) and (u_i, u_j) points -------------------------------------------------------------
 // One wave per group; the groups of one (instance, t):
 //   g <  nv        : (q_g, u_lane)       cfg 1+g, vcfg nv+1+g   38 of 64 lanes
@@ -641,12 +654,10 @@ __global__ __launch_bounds__(LBS, ROWS ? 1 : 3) void lin_static_tau_kernel(LinPa
   rbd::coop_sync<true>();
   tau_up_range<T, PS, KH>(m, s_P, s_V, tau, s, std::make_integer_sequence<int, KH + 1>{});
   tau_down_all<T, PS>(m, s_P, s_V, s, std::make_integer_sequence<int, nv>{});
-  // The output stage reads its pointers from the kernel-argument segment only now: taken from `p` they would be
-  // loaded at kernel entry and stay live through the whole evaluation, and the scalar registers would spill.
+  // the output stage reads its pointers from the kernel-argument segment only now (kernarg_params)
   __builtin_amdgcn_sched_barrier(0);
-  typedef __attribute__((address_space(4))) const LinParams* kernarg_t;
-  const kernarg_t kp = (kernarg_t)__builtin_amdgcn_kernarg_segment_ptr();
   if constexpr (ROWS) {
+    const kernarg_t kp = kernarg_params();
     RowStage<nv>& S = s_lds.S;
     const int mm = nv;
     __syncthreads();                       // every lane is done with the staged operands
@@ -665,8 +676,7 @@ __global__ __launch_bounds__(LBS, ROWS ? 1 : 3) void lin_static_tau_kernel(LinPa
                             kp->fx + bt * n * n + (int64_t)i * n, kp->fxx + bt * n * n * n + (int64_t)i * cs + (int64_t)i * n * n, xg, kp->skip_top != 0, pack);
   } else {
     OutStage<nv, LBS / 2>& S = s_lds.O;
-    LinParams po;
-    po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top; po.pack = kp->pack;
+    const LinParams po = emit_params();
     const double dt = m.dt;
     __syncthreads();                       // every lane is done with the staged operands
 #pragma unroll 1
@@ -704,6 +714,111 @@ template <class T> constexpr int max_chain() {
   return best;
 }
 
+// ---- the joint steps the static sweeps share ------------------------------------------------------------------------------
+// The per-joint arithmetic of the local-frame ABA with the joint type a compile-time constant (o: where the joint's axis sits in a
+// motion vector, 0 revolute / 3 prismatic), on pointers and register arrays, written once.  A sweep family (velocity level,
+// configuration level, cache fill, v-cache rows) fetches its operands its own way, calls the steps and stores the results its own way.
+// The order of the floating-point operations in a step is part of it: the families are held bit-equal to each other by tests.
+
+// joint motion vector vJ = S_K v_K (the first loop of rbd::aba_tree / aba_vu_cached)
+template <int o>
+__device__ __forceinline__ void step_joint_motion(const double* a, double vK, double* vJ) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) vJ[k] = 0.0;
+  vJ[o] = a[0] * vK; vJ[o + 1] = a[1] * vK; vJ[o + 2] = a[2] * vK;
+}
+// link velocity v_K = X_K v_parent + vJ (the same loop); ROOT: no parent, vel_par is not read
+template <bool ROOT>
+__device__ __forceinline__ void step_link_vel(const double* E, const double* r, const double* vel_par, const double* vJ, double* vel) {
+  if constexpr (!ROOT) rbd::xform_motion(E, r, vel_par, vel);
+  else {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) vel[k] = 0.0;
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) vel[k] += vJ[k];
+}
+// bias force of a link that no child has contributed to yet: pA = v x* (I v) (rbd::aba_tree, first loop)
+__device__ __forceinline__ void step_bias_force0(const double* I6, const double* vel, double* pA) {
+  double Iv[6];
+  rbd::sym6_mv(I6, vel, Iv);
+  rbd::crf(vel, Iv, pA);
+}
+// U = IA S and 1/D = 1 / (S^T U) (rbd::aba_tree / aba_qpart, leaf -> root loop)
+template <int o>
+__device__ __forceinline__ void step_U_dinv(const double* IA, const double* a, double* U, double& dinv) {
+  double d = 0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) U[r] = IA[rbd::sidx(r, o)] * a[0] + IA[rbd::sidx(r, o + 1)] * a[1] + IA[rbd::sidx(r, o + 2)] * a[2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) d += a[k] * U[o + k];
+  dinv = 1.0 / d;
+}
+// Ia = IA - U U^T / D (the same loop)
+__device__ __forceinline__ void step_Ia(const double* IA, const double* U, double dinv, double* Ia) {
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int cc = 0; cc <= r; ++cc) Ia[rbd::sidx(r, cc)] = IA[rbd::sidx(r, cc)] - U[r] * U[cc] * dinv;
+}
+// u_K = tau_K - S^T pA (the same loop).  tau_K is read where it is used, behind the sum: passed by value, its load moves ahead of the
+// sum and the dense velocity rows of the Talos-like tree gain 8 B of scratch (profiles/summary_static_shared_steps.txt)
+template <int o>
+__device__ __forceinline__ double step_u(const double* a, const double* pA, const double* tauK) {
+  double sp = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) sp += a[k] * pA[o + k];
+  return *tauK - sp;
+}
+// force handed up to the parent: fp = X^T (pA + Ia cb + U u / D) (the same loop; the inertia handed up is rbd::add_xtix)
+__device__ __forceinline__ void step_force_up(const double* E, const double* r, const double* pA, const double* Iac, const double* U,
+                                              double ui, double dinv, double* fp) {
+  double pa[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) pa[k] = pA[k] + Iac[k] + U[k] * (ui * dinv);
+  rbd::xform_force_T(E, r, pa, fp);
+}
+// acceleration step of joint K (the root -> leaf loop of rbd::aba_tree / aba_vu_cached), the link velocity recomputed on the way:
+// uK holds u_K on entry and the joint acceleration on return; vel / acc of the parent are read (a root starts from gravity), those
+// of K are left for its children.  acc holds the bias-force accumulators of the pass before until this step overwrites them
+template <class T, int K>
+__device__ __forceinline__ void step_accel(const DevModel* m, const double* E, const double* r, const double* U, double dinv, double vK,
+                                           double& uK, double (&vel_all)[T::N][6], double (&acc_all)[T::N][6]) {
+  constexpr int o = T::prismatic[K] ? 3 : 0;
+  constexpr int par = T::parent[K];
+  const double* a = m->axis[K];
+  double vJ[6], vel[6], cb[6], ap[6];
+  step_joint_motion<o>(a, vK, vJ);
+  if constexpr (par >= 0) {
+    rbd::xform_motion(E, r, vel_all[par], vel);
+    rbd::xform_motion(E, r, acc_all[par], ap);
+  } else {
+    const double a0[6] = {0, 0, 0, -m->gravity[0], -m->gravity[1], -m->gravity[2]};
+#pragma unroll
+    for (int k = 0; k < 6; ++k) vel[k] = 0.0;
+    rbd::xform_motion(E, r, a0, ap);
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) vel[k] += vJ[k];
+  rbd::crm(vel, vJ, cb);
+  double sum = 0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { ap[k] += cb[k]; sum += U[k] * ap[k]; }
+  const double qd = (uK - sum) * dinv;
+  uK = qd;
+  if constexpr (has_child<T>(K)) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) { vel_all[K][k] = vel[k]; acc_all[K][k] = ap[k]; }
+    acc_all[K][o] += a[0] * qd; acc_all[K][o + 1] += a[1] * qd; acc_all[K][o + 2] += a[2] * qd;
+  }
+}
+// the v-part record of a joint, cb | pA0 | Ia cb (rbd::aba_vpart_cached), into rec[18]
+__device__ __forceinline__ void step_vpart(const double* I6, const double* Ia, const double* vel, const double* vJ, double* rec) {
+  rbd::crm(vel, vJ, rec);
+  step_bias_force0(I6, vel, rec + 6);
+  rbd::sym6_mv(Ia, rec, rec + 12);
+}
+
 template <class T>
 struct VelState {
   double vel[T::N][6];   // link velocities (a chain at a time, plus the branching joints)
@@ -716,6 +831,8 @@ struct VelCtx {
   static constexpr int UQS = UQS_;   // stride between consecutive joints of this lane's u_i / acceleration buffer in LDS;
                                      // 0: no buffer, the values stay in registers (VelState::uu)
   static constexpr int QS = QS_;     // doubles per joint of the (E | r | U | 1/D) block behind qp
+  static constexpr bool V_STEPPED = true;   // the lane steps velocities (lane_v)
+  static constexpr bool LDS_VEL = false;    // a chain's link velocities stay in registers (VelState::vel)
   const DevModel* m;
   const double* qp;                  // (E | r | U | 1/D): the q-cache block itself, or its copy in LDS
   const double* __restrict__ qc;
@@ -734,58 +851,68 @@ struct VelCtx {
   template <int K> __device__ __forceinline__ const double* ud_down() const { return ud<K>(); }   // U | 1/D again, in the acceleration pass
 };
 
+// v_K of this lane's point: stepped at the velocity level, the base one in the contexts whose points differ in q alone
 template <int NV, class C>
 __device__ __forceinline__ double lane_v(const C& c, int K) {
   double v = c.xg[NV + K];
-  if (NV + K == c.i) v = v + c.eps;
-  if (NV + K == c.j) v = v + c.eps;
+  if constexpr (C::V_STEPPED) {
+    if (NV + K == c.i) v = v + c.eps;
+    if (NV + K == c.j) v = v + c.eps;
+  }
   return v;
 }
 
+// ---- the chain drivers: generic over the context (what a context has to offer: VelCtx) -------------------------------------
+// A chain's link velocities live in registers (VelState::vel, the velocity level) or in LDS (C::LDS_VEL: the sweeps that also carry
+// articulated inertias -- full ABA, cache fill -- slot K - F of c.lvel); the branching joints' stay in registers in both forms.
 template <class T, int K, class C>
-__device__ __forceinline__ void joint_vel(const C& c, const double* vel_par, double* vel) {
-  constexpr int o = T::prismatic[K] ? 3 : 0;
-  double Pb[12];
-  const double* E = c.template er<K>(Pb);
-  const double* r = E + 9;
-  const double* a = c.m->axis[K];
-  const double vK = lane_v<T::N>(c, K);
-  double vJ[6] = {0, 0, 0, 0, 0, 0};
-  vJ[o] = a[0] * vK; vJ[o + 1] = a[1] * vK; vJ[o + 2] = a[2] * vK;
-  if constexpr (T::parent[K] >= 0) rbd::xform_motion(E, r, vel_par, vel);
-  else {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) vel[k] = 0.0;
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) vel[k] += vJ[k];
+__device__ __forceinline__ void joint_vel(const C& c, const double* E, const double* vel_par, double* vel) {
+  double vJ[6];
+  step_joint_motion<T::prismatic[K] ? 3 : 0>(c.m->axis[K], lane_v<T::N>(c, K), vJ);
+  step_link_vel<(T::parent[K] < 0)>(E, E + 9, vel_par, vJ, vel);
 }
-// velocity of joint K from the root (used for the branching joints)
+// velocity of joint K from the root (used for the branching joints).  A joint's E | r is fetched behind its ancestors' steps: fetched
+// ahead of them, every placement of the path is alive at once where a context forms it (the cache fill and the full-ABA sweep of
+// the Talos-like tree spilled 48 to 64 B more that way)
 template <class T, int K, class C>
 __device__ __forceinline__ void vel_from_root(const C& c, double* vel) {
-  if constexpr (T::parent[K] >= 0) {
-    double vp[6];
-    vel_from_root<T, T::parent[K]>(c, vp);
-    joint_vel<T, K>(c, vp, vel);
-  } else {
-    joint_vel<T, K>(c, nullptr, vel);
-  }
-}
-template <class T, int K, class C>
-__device__ __forceinline__ void bias_force0(const C& c, const double* vel, double* pA) {
-  double Iv[6];
-  rbd::sym6_mv(c.m->I6[K], vel, Iv);
-  rbd::crf(vel, Iv, pA);
+  double Pb[12], vp[6];
+  if constexpr (T::parent[K] >= 0) vel_from_root<T, T::parent[K]>(c, vp);
+  const double* E = c.template er<K>(Pb);
+  joint_vel<T, K>(c, E, vp, vel);
 }
 
+// register form: joints K .. E of a chain
 template <class T, int K, int E, class C>
 __device__ __forceinline__ void chain_down(const C& c, VelState<T>& s) {
-  if constexpr (T::parent[K] >= 0) joint_vel<T, K>(c, s.vel[T::parent[K]], s.vel[K]);
-  else joint_vel<T, K>(c, nullptr, s.vel[K]);
+  double Pb[12];
+  joint_vel<T, K>(c, c.template er<K>(Pb), s.vel[T::parent[K] >= 0 ? T::parent[K] : 0], s.vel[K]);   // (a root: no parent is read)
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (K < E) chain_down<T, K + 1, E>(c, s);
 }
+// LDS form: joints K .. E of the chain that starts at F go to slots K - F; `cur` carries the velocity of the previous joint
+template <class T, int K, int F, int E, class C>
+__device__ __forceinline__ void chain_down_lds(const C& c, double* cur) {
+  double Pb[12], vel[6];
+  joint_vel<T, K>(c, c.template er<K>(Pb), cur, vel);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { cur[k] = vel[k]; c.lvel[((K - F) * 6 + k) * LBS] = vel[k]; }
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (K < E) chain_down_lds<T, K + 1, F, E>(c, cur);
+}
+// LDS form: the velocity of joint K of the chain that starts at F, or of the joint the chain hangs from (K < F: a branching joint)
+template <class T, int K, int F, class C>
+__device__ __forceinline__ void chain_vel_load(const C& c, const double (&vel_all)[T::N][6], double* vel) {
+  if constexpr (K >= F) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) vel[k] = c.lvel[((K - F) * 6 + k) * LBS];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) vel[k] = vel_all[K][k];
+  }
+}
 
+// leaf -> root step of the velocity level (rbd::aba_vu_cached, second loop) for the joints K .. F of a chain
 template <class T, int K, int F, class C>
 __device__ __forceinline__ void chain_up(const C& c, VelState<T>& s) {
   constexpr int o = T::prismatic[K] ? 3 : 0;
@@ -800,26 +927,20 @@ __device__ __forceinline__ void chain_up(const C& c, VelState<T>& s) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) pAi[k] = s.acc[K][k];
   } else {
-    bias_force0<T, K>(c, s.vel[K], pAi);
+    step_bias_force0(c.m->I6[K], s.vel[K], pAi);
   }
-  double sp = 0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) sp += a[k] * pAi[o + k];
-  const double ui = c.ug[K] - sp;
+  const double ui = step_u<o>(a, pAi, c.ug + K);
   if constexpr (C::UQS == 0) s.uu[K] = ui; else c.uq[K * C::UQS] = ui;
   constexpr int par = T::parent[K];
   if constexpr (par >= 0) {
-    const double vK = lane_v<T::N>(c, K);
-    double vJ[6] = {0, 0, 0, 0, 0, 0}, cb[6], pa[6], Iac[6], fp[6];
-    vJ[o] = a[0] * vK; vJ[o + 1] = a[1] * vK; vJ[o + 2] = a[2] * vK;
+    double vJ[6], cb[6], Iac[6], fp[6];
+    step_joint_motion<o>(a, lane_v<T::N>(c, K), vJ);
     rbd::crm(s.vel[K], vJ, cb);
     c.template ia_cb<K>(U, cb, Iac);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) pa[k] = pAi[k] + Iac[k] + U[k] * (ui * dinv);
-    rbd::xform_force_T(E, r, pa, fp);
+    step_force_up(E, r, pAi, Iac, U, ui, dinv, fp);
     if constexpr (first_contrib<T>(K)) {
       double p0[6];
-      bias_force0<T, par>(c, s.vel[par], p0);
+      step_bias_force0(c.m->I6[par], s.vel[par], p0);
 #pragma unroll
       for (int k = 0; k < 6; ++k) s.acc[par][k] = p0[k] + fp[k];
     } else {
@@ -831,62 +952,43 @@ __device__ __forceinline__ void chain_up(const C& c, VelState<T>& s) {
   if constexpr (K > F) chain_up<T, K - 1, F>(c, s);
 }
 
-// chains in descending order of their joints: a chain is processed when the fold reaches its last joint
-template <class T, int K, class C>
-__device__ __forceinline__ void chain_at(const C& c, VelState<T>& s) {
+// Chains in descending order of their joints: a chain is processed when the fold reaches its last joint -- down it for the link
+// velocities, back up it with the family's leaf -> root step (the chain_up overload of the family's context and state)
+template <class T, int K, class C, class S>
+__device__ __forceinline__ void chain_at(const C& c, S& s) {
   if constexpr (chain_end<T>(K)) {
     constexpr int F = chain_first<T>(K), P = T::parent[F];
     if constexpr (P >= 0) {
       // the largest-index child chain of a branching joint is the first to need (and to form) that joint's velocity
       if constexpr (first_contrib<T>(F) && n_children<T>(P) > 1) vel_from_root<T, P>(c, s.vel[P]);
     }
-    chain_down<T, F, K>(c, s);
+    if constexpr (C::LDS_VEL) {
+      double cur[6] = {0, 0, 0, 0, 0, 0};
+      if constexpr (P >= 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) cur[k] = s.vel[P][k];
+      }
+      chain_down_lds<T, F, F, K>(c, cur);
+    } else {
+      chain_down<T, F, K>(c, s);
+    }
     chain_up<T, K, F>(c, s);
   }
 }
-template <class T, class C, int... Ks>
-__device__ __forceinline__ void vel_up_all(const C& c, VelState<T>& s, std::integer_sequence<int, Ks...>) {
+template <class T, class C, class S, int... Ks>
+__device__ __forceinline__ void chains_up_all(const C& c, S& s, std::integer_sequence<int, Ks...>) {
   (chain_at<T, T::N - 1 - Ks>(c, s), ...);
 }
 
 // acceleration pass (rbd::aba_vu_cached, third loop), link velocities recomputed on the way
 template <class T, int K, class C>
 __device__ __forceinline__ void vel_down(const C& c, VelState<T>& s) {
-  constexpr int o = T::prismatic[K] ? 3 : 0;
-  constexpr int par = T::parent[K];
   double Pb[12];
   const double* E = c.template er_down<K>(Pb);
-  const double* r = E + 9;
   const double* U = c.template ud_down<K>();
-  const double dinv = U[6];
-  const double* a = c.m->axis[K];
-  const double vK = lane_v<T::N>(c, K);
-  double vJ[6] = {0, 0, 0, 0, 0, 0}, vel[6], cb[6], ap[6];
-  vJ[o] = a[0] * vK; vJ[o + 1] = a[1] * vK; vJ[o + 2] = a[2] * vK;
-  if constexpr (par >= 0) {
-    rbd::xform_motion(E, r, s.vel[par], vel);
-    rbd::xform_motion(E, r, s.acc[par], ap);
-  } else {
-    const double a0[6] = {0, 0, 0, -c.m->gravity[0], -c.m->gravity[1], -c.m->gravity[2]};
-#pragma unroll
-    for (int k = 0; k < 6; ++k) vel[k] = 0.0;
-    rbd::xform_motion(E, r, a0, ap);
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) vel[k] += vJ[k];
-  rbd::crm(vel, vJ, cb);
-  double sum = 0;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) { ap[k] += cb[k]; sum += U[k] * ap[k]; }
-  double ui;
-  if constexpr (C::UQS == 0) ui = s.uu[K]; else ui = c.uq[K * C::UQS];
-  const double qd = (ui - sum) * dinv;
-  if constexpr (C::UQS == 0) s.uu[K] = qd; else c.uq[K * C::UQS] = qd;
-  if constexpr (has_child<T>(K)) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) { s.vel[K][k] = vel[k]; s.acc[K][k] = ap[k]; }
-    s.acc[K][o] += a[0] * qd; s.acc[K][o + 1] += a[1] * qd; s.acc[K][o + 2] += a[2] * qd;
-  }
+  double* uK;
+  if constexpr (C::UQS == 0) uK = &s.uu[K]; else uK = c.uq + K * C::UQS;
+  step_accel<T, K>(c.m, E, E + 9, U, U[6], lane_v<T::N>(c, K), *uK, s.vel, s.acc);
   __builtin_amdgcn_sched_barrier(0);
 }
 template <class T, class C, int... Ks>
@@ -957,13 +1059,12 @@ __global__ __launch_bounds__(LBS, ROWS ? 3 : DDP_VEL_PAIR_WAVES) void lin_static
     rbd::coop_sync<true>();
   }
   VelState<T> s;
-  vel_up_all<T>(c, s, std::make_integer_sequence<int, nv>{});
+  chains_up_all<T>(c, s, std::make_integer_sequence<int, nv>{});
   vel_down_all<T>(c, s, std::make_integer_sequence<int, nv>{});
   __builtin_amdgcn_sched_barrier(0);
-  typedef __attribute__((address_space(4))) const LinParams* kernarg_t;
-  const kernarg_t kp = (kernarg_t)__builtin_amdgcn_kernarg_segment_ptr();
   const double dt = c.m->dt;
   if constexpr (ROWS) {
+    const kernarg_t kp = kernarg_params();
     double* fxx = kp->fxx + bt * n * n * n;
     const double* fxb = kp->fx + bt * n * n;
     __syncthreads();                       // every lane is done with the staged operands
@@ -982,8 +1083,7 @@ __global__ __launch_bounds__(LBS, ROWS ? 3 : DDP_VEL_PAIR_WAVES) void lin_static
                              kp->f_val + bt * n, fxb + (int64_t)i * n, fxx + (int64_t)i * cs + (int64_t)i * n * n, c.xg, kp->skip_top != 0, pack);
   } else {
     constexpr int NP = LBS / 2;
-    LinParams po;
-    po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top; po.pack = kp->pack;
+    const LinParams po = emit_params();
     __syncthreads();                       // every lane is done with the staged operands
     // point-major with an odd stride (OutStage); the second half of the wave parks its values in the spare row for now.
     // Unconditional stores right behind the evaluation (see the torque-level kernel)
@@ -1023,7 +1123,10 @@ struct CfgState {
   double w[2][WS_PER_JOINT];   // third pass: workspace values of the current / next joint
 };
 
+template <class T>
 struct CfgCtx {
+  static constexpr bool V_STEPPED = false;
+  static constexpr bool LDS_VEL = true;
   const DevModel* __restrict__ m;
   const double* __restrict__ qc0;   // q-cache of the base configuration
   const double* __restrict__ xg;
@@ -1033,82 +1136,24 @@ struct CfgCtx {
   int i, j;
   const double* own;                // null: joints i, j take E | r from configurations 1+i, 1+j of the q-cache;
                                     // else this lane's own E | r of joint i (first order: a step the cache does not hold)
+  // E | r of joint K at q_K and at q_K + eps (configuration 1+K of the q-cache): both wave-uniform, selected per lane into P
+  template <int K> __device__ __forceinline__ const double* er(double* P) const {
+    const double* base = qc0 + K * rbd::QC_STRIDE;
+    const double* pert = own ? own : qc0 + ((int64_t)(1 + K) * T::N + K) * rbd::QC_STRIDE;
+    const bool mine = K == i || K == j;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) P[e] = mine ? pert[e] : base[e];
+    return P;
+  }
 };
 
-template <int K, int NV>
-__device__ __forceinline__ void lane_placement(const CfgCtx& c, double* P) {
-  // E | r of joint K at q_K and at q_K + eps (configuration 1+K of the q-cache): both wave-uniform, selected per lane
-  const double* base = c.qc0 + K * rbd::QC_STRIDE;
-  const double* pert = c.own ? c.own : c.qc0 + ((int64_t)(1 + K) * NV + K) * rbd::QC_STRIDE;
-  const bool own = K == c.i || K == c.j;
-#pragma unroll
-  for (int e = 0; e < 12; ++e) P[e] = own ? pert[e] : base[e];
-}
-
-template <class T, int K>
-__device__ __forceinline__ void cfg_joint_vel(const CfgCtx& c, const double* P, const double* vel_par, double* vel) {
+// leaf -> root step of the full ABA (rbd::aba_tree, second loop) for the joints K .. F of a chain
+template <class T, int K, int F>
+__device__ __forceinline__ void chain_up(const CfgCtx<T>& c, CfgState<T>& s) {
   constexpr int o = T::prismatic[K] ? 3 : 0;
   const double* a = c.m->axis[K];
-  const double vK = c.xg[T::N + K];
-  double vJ[6] = {0, 0, 0, 0, 0, 0};
-  vJ[o] = a[0] * vK; vJ[o + 1] = a[1] * vK; vJ[o + 2] = a[2] * vK;
-  if constexpr (T::parent[K] >= 0) rbd::xform_motion(P, P + 9, vel_par, vel);
-  else {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) vel[k] = 0.0;
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) vel[k] += vJ[k];
-}
-template <class T, int K>
-__device__ __forceinline__ void cfg_vel_from_root(const CfgCtx& c, double* vel) {
-  double P[12];
-  lane_placement<K, T::N>(c, P);
-  if constexpr (T::parent[K] >= 0) {
-    double vp[6];
-    cfg_vel_from_root<T, T::parent[K]>(c, vp);
-    cfg_joint_vel<T, K>(c, P, vp, vel);
-  } else {
-    cfg_joint_vel<T, K>(c, P, nullptr, vel);
-  }
-}
-template <int K>
-__device__ __forceinline__ void cfg_bias_force0(const CfgCtx& c, const double* vel, double* pA) {
-  double Iv[6];
-  rbd::sym6_mv(c.m->I6[K], vel, Iv);
-  rbd::crf(vel, Iv, pA);
-}
-
-// the link velocities of a chain go to LDS slot (K - F); `cur` carries the velocity of the previous joint
-template <class T, int K, int F, int E>
-__device__ __forceinline__ void cfg_chain_down(const CfgCtx& c, CfgState<T>& s, double* cur) {
-  double P[12], vel[6];
-  lane_placement<K, T::N>(c, P);
-  if constexpr (T::parent[K] >= 0) cfg_joint_vel<T, K>(c, P, cur, vel);
-  else cfg_joint_vel<T, K>(c, P, nullptr, vel);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) { cur[k] = vel[k]; c.lvel[((K - F) * 6 + k) * LBS] = vel[k]; }
-  __builtin_amdgcn_sched_barrier(0);
-  if constexpr (K < E) cfg_chain_down<T, K + 1, F, E>(c, s, cur);
-}
-template <class T, int K, int F>
-__device__ __forceinline__ void chain_vel_load(const CfgCtx& c, const CfgState<T>& s, double* vel) {
-  if constexpr (K >= F) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) vel[k] = c.lvel[((K - F) * 6 + k) * LBS];
-  } else {   // the joint the chain hangs from: a branching joint, kept in registers
-#pragma unroll
-    for (int k = 0; k < 6; ++k) vel[k] = s.vel[K][k];
-  }
-}
-
-// leaf -> root step of joint K (rbd::aba_tree, second loop)
-template <class T, int K, int F>
-__device__ __forceinline__ void cfg_chain_up(const CfgCtx& c, CfgState<T>& s) {
-  constexpr int o = T::prismatic[K] ? 3 : 0;
-  const double* a = c.m->axis[K];
-  double IA[21], pAi[6], U[6], velK[6];
-  chain_vel_load<T, K, F>(c, s, velK);
+  double IA[21], pAi[6], U[6], velK[6], dinv;
+  chain_vel_load<T, K, F>(c, s.vel, velK);
   if constexpr (has_child<T>(K)) {
 #pragma unroll
     for (int k = 0; k < 21; ++k) IA[k] = s.accI[K][k];
@@ -1117,68 +1162,36 @@ __device__ __forceinline__ void cfg_chain_up(const CfgCtx& c, CfgState<T>& s) {
   } else {
 #pragma unroll
     for (int k = 0; k < 21; ++k) IA[k] = c.m->I6[K][k];
-    cfg_bias_force0<K>(c, velK, pAi);
+    step_bias_force0(c.m->I6[K], velK, pAi);
   }
-  double d = 0, sp = 0;
-#pragma unroll
-  for (int r = 0; r < 6; ++r) U[r] = IA[rbd::sidx(r, o)] * a[0] + IA[rbd::sidx(r, o + 1)] * a[1] + IA[rbd::sidx(r, o + 2)] * a[2];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { d += a[k] * U[o + k]; sp += a[k] * pAi[o + k]; }
-  const double dinv = 1.0 / d;
-  const double ui = c.ug[K] - sp;
+  step_U_dinv<o>(IA, a, U, dinv);
+  const double ui = step_u<o>(a, pAi, c.ug + K);
 #pragma unroll
   for (int k = 0; k < 6; ++k) c.W[(K * WS_PER_JOINT + k) * LBS] = U[k];
   c.W[(K * WS_PER_JOINT + 6) * LBS] = dinv;
   c.W[(K * WS_PER_JOINT + 7) * LBS] = ui;
   constexpr int par = T::parent[K];
   if constexpr (par >= 0) {
-    double P[12], Ia[21], vJ[6] = {0, 0, 0, 0, 0, 0}, cb[6], pa[6], Iac[6], fp[6];
-    lane_placement<K, T::N>(c, P);
-    const double vK = c.xg[T::N + K];
-    vJ[o] = a[0] * vK; vJ[o + 1] = a[1] * vK; vJ[o + 2] = a[2] * vK;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int cc = 0; cc <= r; ++cc) Ia[rbd::sidx(r, cc)] = IA[rbd::sidx(r, cc)] - U[r] * U[cc] * dinv;
+    double Pb[12], Ia[21], vJ[6], cb[6], Iac[6], fp[6];
+    const double* P = c.template er<K>(Pb);
+    step_joint_motion<o>(a, lane_v<T::N>(c, K), vJ);
+    step_Ia(IA, U, dinv, Ia);
     rbd::crm(velK, vJ, cb);
     rbd::sym6_mv(Ia, cb, Iac);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) pa[k] = pAi[k] + Iac[k] + U[k] * (ui * dinv);
+    step_force_up(P, P + 9, pAi, Iac, U, ui, dinv, fp);
     if constexpr (first_contrib<T>(K)) {
       double velP[6];
-      chain_vel_load<T, par, F>(c, s, velP);
+      chain_vel_load<T, par, F>(c, s.vel, velP);
 #pragma unroll
       for (int k = 0; k < 21; ++k) s.accI[par][k] = c.m->I6[par][k];
-      cfg_bias_force0<par>(c, velP, s.accP[par]);
+      step_bias_force0(c.m->I6[par], velP, s.accP[par]);
     }
     rbd::add_xtix(P, P + 9, Ia, s.accI[par]);
-    rbd::xform_force_T(P, P + 9, pa, fp);
 #pragma unroll
     for (int k = 0; k < 6; ++k) s.accP[par][k] += fp[k];
   }
   __builtin_amdgcn_sched_barrier(0);
-  if constexpr (K > F) cfg_chain_up<T, K - 1, F>(c, s);
-}
-
-template <class T, int K>
-__device__ __forceinline__ void cfg_chain_at(const CfgCtx& c, CfgState<T>& s) {
-  if constexpr (chain_end<T>(K)) {
-    constexpr int F = chain_first<T>(K), P = T::parent[F];
-    if constexpr (P >= 0) {
-      if constexpr (first_contrib<T>(F) && n_children<T>(P) > 1) cfg_vel_from_root<T, P>(c, s.vel[P]);
-    }
-    double cur[6] = {0, 0, 0, 0, 0, 0};
-    if constexpr (P >= 0) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) cur[k] = s.vel[P][k];
-    }
-    cfg_chain_down<T, F, F, K>(c, s, cur);
-    cfg_chain_up<T, K, F>(c, s);
-  }
-}
-template <class T, int... Ks>
-__device__ __forceinline__ void cfg_up_all(const CfgCtx& c, CfgState<T>& s, std::integer_sequence<int, Ks...>) {
-  (cfg_chain_at<T, T::N - 1 - Ks>(c, s), ...);
+  if constexpr (K > F) chain_up<T, K - 1, F>(c, s);
 }
 
 // acceleration pass (rbd::aba_tree, third loop); link velocities recomputed, (U, 1/D, u) read back one joint ahead
@@ -1188,46 +1201,21 @@ template <int STRIDE_>
 struct CfgDownOut { double* uq; static constexpr int STRIDE = STRIDE_; };
 
 template <class T, int K, class O>
-__device__ __forceinline__ void cfg_down(const CfgCtx& c, CfgState<T>& s, const O& out) {
-  constexpr int o = T::prismatic[K] ? 3 : 0;
-  constexpr int par = T::parent[K];
+__device__ __forceinline__ void cfg_down(const CfgCtx<T>& c, CfgState<T>& s, const O& out) {
   if constexpr (K + 1 < T::N) {
 #pragma unroll
     for (int e = 0; e < WS_PER_JOINT; ++e) s.w[(K + 1) & 1][e] = c.W[((K + 1) * WS_PER_JOINT + e) * LBS];
   }
   const double* U = s.w[K & 1];
-  const double dinv = s.w[K & 1][6], ui = s.w[K & 1][7];
-  const double* a = c.m->axis[K];
-  const double vK = c.xg[T::N + K];
-  double P[12], vJ[6] = {0, 0, 0, 0, 0, 0}, vel[6], cb[6], ap[6];
-  lane_placement<K, T::N>(c, P);
-  vJ[o] = a[0] * vK; vJ[o + 1] = a[1] * vK; vJ[o + 2] = a[2] * vK;
-  if constexpr (par >= 0) {
-    rbd::xform_motion(P, P + 9, s.vel[par], vel);
-    rbd::xform_motion(P, P + 9, s.accP[par], ap);
-  } else {
-    const double a0[6] = {0, 0, 0, -c.m->gravity[0], -c.m->gravity[1], -c.m->gravity[2]};
-#pragma unroll
-    for (int k = 0; k < 6; ++k) vel[k] = 0.0;
-    rbd::xform_motion(P, P + 9, a0, ap);
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) vel[k] += vJ[k];
-  rbd::crm(vel, vJ, cb);
-  double sum = 0;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) { ap[k] += cb[k]; sum += U[k] * ap[k]; }
-  const double qd = (ui - sum) * dinv;
-  out.uq[K * (O::STRIDE == LBS ? LBS : 1)] = qd;
-  if constexpr (has_child<T>(K)) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) { s.vel[K][k] = vel[k]; s.accP[K][k] = ap[k]; }
-    s.accP[K][o] += a[0] * qd; s.accP[K][o + 1] += a[1] * qd; s.accP[K][o + 2] += a[2] * qd;
-  }
+  const double vK = lane_v<T::N>(c, K);
+  double Pb[12], uK = U[7];
+  const double* P = c.template er<K>(Pb);
+  step_accel<T, K>(c.m, P, P + 9, U, U[6], vK, uK, s.vel, s.accP);
+  out.uq[K * (O::STRIDE == LBS ? LBS : 1)] = uK;
   __builtin_amdgcn_sched_barrier(0);
 }
 template <class T, class O, int... Ks>
-__device__ __forceinline__ void cfg_down_all(const CfgCtx& c, CfgState<T>& s, const O& out, std::integer_sequence<int, Ks...>) {
+__device__ __forceinline__ void cfg_down_all(const CfgCtx<T>& c, CfgState<T>& s, const O& out, std::integer_sequence<int, Ks...>) {
   (cfg_down<T, Ks>(c, s, out), ...);
 }
 
@@ -1236,7 +1224,7 @@ __device__ __forceinline__ void cfg_down_all(const CfgCtx& c, CfgState<T>& s, co
 // SIMD hide the workspace reads).  The pointers the evaluation reads through are separate restrict-qualified arguments:
 // the workspace stores must not turn the scalar operand loads that follow them into per-lane loads.
 template <class T>
-__device__ __forceinline__ void cfg_setup(CfgCtx& c, const LinParams& p, const DevModel* __restrict__ model, const double* __restrict__ qcache,
+__device__ __forceinline__ void cfg_setup(CfgCtx<T>& c, const LinParams& p, const DevModel* __restrict__ model, const double* __restrict__ qcache,
                                           const double* __restrict__ xs, const double* __restrict__ us, double* __restrict__ ws,
                                           int64_t bt0, int64_t& bt, bool& valid) {
   constexpr int nv = T::N, n = 2 * nv;
@@ -1265,13 +1253,13 @@ __global__ __launch_bounds__(LBS) void lin_static_cfg_up_kernel(LinParams p, con
   constexpr int nv = T::N;
   constexpr int MAXCH = max_chain<T>();  // longest chain of the topology
   __shared__ double s_vel[MAXCH * 6 * LBS];
-  CfgCtx c;
+  CfgCtx<T> c;
   int64_t bt;
   bool valid;
   cfg_setup<T>(c, p, model, qcache, xs, us, ws, bt0, bt, valid);
   c.lvel = s_vel + threadIdx.x;
   CfgState<T> s;
-  cfg_up_all<T>(c, s, std::make_integer_sequence<int, nv>{});
+  chains_up_all<T>(c, s, std::make_integer_sequence<int, nv>{});
 }
 
 template <class T>
@@ -1280,7 +1268,7 @@ __global__ __launch_bounds__(LBS) void lin_static_cfg_down_kernel(LinParams p, c
                                                                   double* __restrict__ ws, int64_t bt0) {
   constexpr int nv = T::N;
   __shared__ OutStage<nv> S;
-  CfgCtx c;
+  CfgCtx<T> c;
   int64_t bt;
   bool valid;
   cfg_setup<T>(c, p, model, qcache, xs, us, ws, bt0, bt, valid);
@@ -1291,11 +1279,7 @@ __global__ __launch_bounds__(LBS) void lin_static_cfg_down_kernel(LinParams p, c
   CfgDownOut<nv + 1> o{&S.qdd[threadIdx.x * (nv + 1)]};
   cfg_down_all<T>(c, s, o, std::make_integer_sequence<int, nv>{});
   __builtin_amdgcn_sched_barrier(0);
-  typedef __attribute__((address_space(4))) const LinParams* kernarg_t;
-  const kernarg_t kp = (kernarg_t)__builtin_amdgcn_kernarg_segment_ptr();
-  LinParams po;
-  po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top; po.pack = kp->pack;
-  offdiag_emit<nv, LBS>(po, S, valid, c.i, c.j, bt, c.xg, model->dt);
+  offdiag_emit<nv, LBS>(emit_params(), S, valid, c.i, c.j, bt, c.xg, model->dt);
 }
 
 // ---- configuration level by splice: the (q_i, q_j) points from cached q-parts --------------------------------------
@@ -1375,8 +1359,9 @@ __device__ __forceinline__ bool xcd_slot(int nb, int& btl, int& g) {
   return btl < nb;
 }
 
-// One lane per pair: its spine from the deepest joint to the root (the expressions of qv_chain_up).  Joint indices are
-// run-time values here, so the per-joint constants come from the model in memory; register arrays are indexed by constants only.
+// One lane per pair: its spine from the deepest joint to the root (the expressions of the cache fill's chain_up).  Joint indices are
+// run-time values here, so the per-joint constants come from the model in memory, register arrays are indexed by constants only and
+// the joint type is a select: the U | 1/D | Ia block below is step_U_dinv / step_Ia in that run-time form, kept as it was.
 // SP: the stepped configurations' records come from the delta blocks (they are exactly the records a step changes)
 template <class T, bool SP>
 __global__ __launch_bounds__(LBS) void lin_static_spine_kernel(const DevModel* __restrict__ model, const double* __restrict__ qcache, int64_t qc_bt,
@@ -1466,6 +1451,8 @@ template <class T, bool SP>
 struct SpliceCtx {
   using L = QcLayout<T>;
   static constexpr int UQS = 1;
+  static constexpr bool V_STEPPED = false;   // q directions do not change v
+  static constexpr bool LDS_VEL = false;
   const DevModel* m;
   const double* __restrict__ qc0;   // q-cache of the (instance, t): configuration c at qc0 + c * nv * QC_STRIDE
   const double* __restrict__ xg;
@@ -1535,9 +1522,6 @@ struct SpliceCtx {
     }
   }
 };
-template <int NV, class T, bool SP>
-__device__ __forceinline__ double lane_v(const SpliceCtx<T, SP>& c, int K) { return c.xg[NV + K]; }   // q directions do not change v
-
 // One wave = 64 (q_i, q_j) pairs, i < j: the velocity-level pair kernel on spliced operands
 template <class T, bool SP>
 __global__ __launch_bounds__(LBS, 2) void lin_static_cfg_pair_kernel(LinParams p, const double* __restrict__ spine, int64_t bt0, int nb) {
@@ -1567,14 +1551,10 @@ __global__ __launch_bounds__(LBS, 2) void lin_static_cfg_pair_kernel(LinParams p
   c.spb = spine + (int64_t)btl * NREC * SREC;
   c.uq = &S.qdd[lane * (nv + 1)];
   VelState<T> s;
-  vel_up_all<T>(c, s, std::make_integer_sequence<int, nv>{});
+  chains_up_all<T>(c, s, std::make_integer_sequence<int, nv>{});
   vel_down_all<T>(c, s, std::make_integer_sequence<int, nv>{});
   __builtin_amdgcn_sched_barrier(0);
-  typedef __attribute__((address_space(4))) const LinParams* kernarg_t;
-  const kernarg_t kp = (kernarg_t)__builtin_amdgcn_kernarg_segment_ptr();
-  LinParams po;
-  po.f_val = kp->f_val; po.fx = kp->fx; po.fu = kp->fu; po.fxx = kp->fxx; po.fux = kp->fux; po.fuu = kp->fuu; po.skip_qv_mirror = kp->skip_qv_mirror; po.skip_top = kp->skip_top; po.pack = kp->pack;
-  offdiag_emit<nv, LBS>(po, S, valid, c.i, c.j, bt, c.xg, c.m->dt);
+  offdiag_emit<nv, LBS>(emit_params(), S, valid, c.i, c.j, bt, c.xg, c.m->dt);
 }
 
 // ---- first order: forward differences of f (problem.hpp:105-126 stepping, eps = sqrt(DBL_EPSILON)) -------------------
@@ -1646,7 +1626,7 @@ __global__ __launch_bounds__(LBS) void lin_static_first_kernel(LinParams p, cons
     c.m = model; c.qc = qc0; c.qp = qc0; c.xg = xg; c.ug = ug; c.uq = uq;
     c.i = nv + lane; c.j = -1; c.eps = eps;
     VelState<T> s;
-    vel_up_all<T>(c, s, std::make_integer_sequence<int, nv>{});
+    chains_up_all<T>(c, s, std::make_integer_sequence<int, nv>{});
     vel_down_all<T>(c, s, std::make_integer_sequence<int, nv>{});
   } else {
     constexpr int MAXCH = max_chain<T>();
@@ -1661,22 +1641,21 @@ __global__ __launch_bounds__(LBS) void lin_static_first_kernel(LinParams p, cons
 #pragma unroll
       for (int e = 0; e < 3; ++e) s_own[lane * 12 + 9 + e] = r[e];
     }
-    CfgCtx c;
+    CfgCtx<T> c;
     c.m = model; c.qc0 = qc0; c.xg = xg; c.ug = ug;
     c.W = ws + (int64_t)blockIdx.x * (nv * WS_PER_JOINT * LBS) + lane;
     c.lvel = s_vel + lane;
     c.i = valid ? lane : 0; c.j = -1;
     c.own = DIAG ? nullptr : s_own + lane * 12;     // eps_mach^(1/4) steps are the ones the q-cache holds
     CfgState<T> s;
-    cfg_up_all<T>(c, s, std::make_integer_sequence<int, nv>{});
+    chains_up_all<T>(c, s, std::make_integer_sequence<int, nv>{});
 #pragma unroll
     for (int e = 0; e < WS_PER_JOINT; ++e) s.w[0][e] = c.W[e * LBS];
     CfgDownOut<nv + 1> o{uq};
     cfg_down_all<T>(c, s, o, std::make_integer_sequence<int, nv>{});
   }
   __builtin_amdgcn_sched_barrier(0);
-  typedef __attribute__((address_space(4))) const LinParams* kernarg_t;
-  const kernarg_t kp = (kernarg_t)__builtin_amdgcn_kernarg_segment_ptr();
+  const kernarg_t kp = kernarg_params();
   __syncthreads();
   if constexpr (!DIAG) {
     if (double* ao = kp->accel_out) {           // accelerations of the nv perturbed points of this level ([pair][3 nv directions: q, v, u | the point itself][nv]), for the analytic mode-1 pass
@@ -1743,9 +1722,11 @@ __device__ __forceinline__ void placement_static(const DevModel& m, double q, do
   }
 }
 
-template <bool SP_>
+template <class T, bool SP_>
 struct QvCtx {
   static constexpr bool SP = SP_;
+  static constexpr bool V_STEPPED = false;
+  static constexpr bool LDS_VEL = true;
   const DevModel* __restrict__ m;
   const double* __restrict__ xg;
   double* qc;                  // this lane's q-cache block (SP: the base block of its (instance, t), which all of its lanes store onto)
@@ -1756,64 +1737,27 @@ struct QvCtx {
   double* lvel;                // LDS: link velocities of the chain being swept
   int jn;                      // joint whose position this lane steps (-1: none)
   double eps;
+  // E | r of joint K at this lane's configuration, formed into P
+  template <int K> __device__ __forceinline__ const double* er(double* P) const {
+    double q = xg[K];
+    if (K == jn) q = q + eps;
+    placement_static<T, K>(*m, q, P);
+    return P;
+  }
 };
 template <class T>
 struct QvState {
   double vel[T::N][6];
   double accI[T::N][21];
 };
-template <class T, int K, class C>
-__device__ __forceinline__ void qv_placement(const C& c, double* P) {
-  double q = c.xg[K];
-  if (K == c.jn) q = q + c.eps;
-  placement_static<T, K>(*c.m, q, P);
-}
-template <class T, int K, class C>
-__device__ __forceinline__ void qv_joint_vel(const C& c, const double* P, const double* vel_par, double* vel) {
+// leaf -> root step of the cache fill (rbd::aba_qpart, and rbd::aba_vpart_cached at the base velocity) for the joints K .. F of a chain
+template <class T, int K, int F, bool SP>
+__device__ __forceinline__ void chain_up(const QvCtx<T, SP>& c, QvState<T>& s) {
   constexpr int o = T::prismatic[K] ? 3 : 0;
   const double* a = c.m->axis[K];
-  const double vK = c.xg[T::N + K];
-  double vJ[6] = {0, 0, 0, 0, 0, 0};
-  vJ[o] = a[0] * vK; vJ[o + 1] = a[1] * vK; vJ[o + 2] = a[2] * vK;
-  if constexpr (T::parent[K] >= 0) rbd::xform_motion(P, P + 9, vel_par, vel);
-  else {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) vel[k] = 0.0;
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) vel[k] += vJ[k];
-}
-template <class T, int K, class C>
-__device__ __forceinline__ void qv_vel_from_root(const C& c, double* vel) {
-  double P[12];
-  qv_placement<T, K>(c, P);
-  if constexpr (T::parent[K] >= 0) {
-    double vp[6];
-    qv_vel_from_root<T, T::parent[K]>(c, vp);
-    qv_joint_vel<T, K>(c, P, vp, vel);
-  } else {
-    qv_joint_vel<T, K>(c, P, nullptr, vel);
-  }
-}
-template <class T, int K, int F, int E, class C>
-__device__ __forceinline__ void qv_chain_down(const C& c, double* cur) {
-  double P[12], vel[6];
-  qv_placement<T, K>(c, P);
-  if constexpr (T::parent[K] >= 0) qv_joint_vel<T, K>(c, P, cur, vel);
-  else qv_joint_vel<T, K>(c, P, nullptr, vel);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) { cur[k] = vel[k]; c.lvel[((K - F) * 6 + k) * LBS] = vel[k]; }
-  __builtin_amdgcn_sched_barrier(0);
-  if constexpr (K < E) qv_chain_down<T, K + 1, F, E>(c, cur);
-}
-template <class T, int K, int F, class C>
-__device__ __forceinline__ void qv_chain_up(const C& c, QvState<T>& s) {
-  constexpr int o = T::prismatic[K] ? 3 : 0;
-  const double* a = c.m->axis[K];
-  double P[12], IA[21], U[6], Ia[21], vel[6];
-  qv_placement<T, K>(c, P);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) vel[k] = c.lvel[((K - F) * 6 + k) * LBS];
+  double Pb[12], IA[21], U[6], Ia[21], vel[6], dinv;
+  const double* P = c.template er<K>(Pb);
+  chain_vel_load<T, K, F>(c, s.vel, vel);
   if constexpr (has_child<T>(K)) {
 #pragma unroll
     for (int k = 0; k < 21; ++k) IA[k] = s.accI[K][k];
@@ -1821,16 +1765,8 @@ __device__ __forceinline__ void qv_chain_up(const C& c, QvState<T>& s) {
 #pragma unroll
     for (int k = 0; k < 21; ++k) IA[k] = c.m->I6[K][k];
   }
-  double d = 0;
-#pragma unroll
-  for (int r = 0; r < 6; ++r) U[r] = IA[rbd::sidx(r, o)] * a[0] + IA[rbd::sidx(r, o + 1)] * a[1] + IA[rbd::sidx(r, o + 2)] * a[2];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) d += a[k] * U[o + k];
-  const double dinv = 1.0 / d;
-#pragma unroll
-  for (int r = 0; r < 6; ++r)
-#pragma unroll
-    for (int cc = 0; cc <= r; ++cc) Ia[rbd::sidx(r, cc)] = IA[rbd::sidx(r, cc)] - U[r] * U[cc] * dinv;
+  step_U_dinv<o>(IA, a, U, dinv);
+  step_Ia(IA, U, dinv, Ia);
   constexpr int par = T::parent[K];
   if constexpr (par >= 0) {
     if constexpr (first_contrib<T>(K)) {
@@ -1839,21 +1775,16 @@ __device__ __forceinline__ void qv_chain_up(const C& c, QvState<T>& s) {
     }
     rbd::add_xtix(P, P + 9, Ia, s.accI[par]);
   }
-  // rbd::aba_vpart_cached at the base velocity
-  const double vK = c.xg[T::N + K];
-  double vJ[6] = {0, 0, 0, 0, 0, 0}, cb[6], pA[6], Iv[6], Iac[6];
-  vJ[o] = a[0] * vK; vJ[o + 1] = a[1] * vK; vJ[o + 2] = a[2] * vK;
-  rbd::crm(vel, vJ, cb);
-  rbd::sym6_mv(c.m->I6[K], vel, Iv);
-  rbd::crf(vel, Iv, pA);
-  rbd::sym6_mv(Ia, cb, Iac);
+  double vJ[6], vrec[18];
+  step_joint_motion<o>(a, lane_v<T::N>(c, K), vJ);
+  step_vpart(c.m->I6[K], Ia, vel, vJ, vrec);
   // where the two halves of the record go.  SP: a half the lane's step changes goes to its delta block; any other half IS the
   // base record, bit for bit (the same instructions on the same operands in every lane), and is stored onto it: the lanes of an
   // (instance, t) then write one line with one value instead of a line each.  Selected addresses, not predicated stores: with
   // control flow in the chain the compiler contracts its products and sums differently from the dense kernel
   double* qo_er = c.qc + K * rbd::QC_STRIDE;
   double* qo_ud = qo_er + 12;
-  if constexpr (C::SP) {
+  if constexpr (SP) {
     constexpr int DK = depth_of<T>(K);       // (a constant expression: the table is not to be built at run time)
     qo_er = K == c.jn ? c.qown : qo_er;
     if constexpr (has_child<T>(K)) qo_ud = ((c.anc >> K) & 1ull) ? c.qpath + DK * QcLayout<T>::UD : qo_ud;
@@ -1867,27 +1798,9 @@ __device__ __forceinline__ void qv_chain_up(const C& c, QvState<T>& s) {
   for (int k = 0; k < 21; ++k) qo_ud[7 + k] = Ia[k];
   double* vo = c.vc + K * rbd::VC_STRIDE;
 #pragma unroll
-  for (int k = 0; k < 6; ++k) { vo[k] = cb[k]; vo[6 + k] = pA[k]; vo[12 + k] = Iac[k]; }
+  for (int k = 0; k < 18; ++k) vo[k] = vrec[k];
   __builtin_amdgcn_sched_barrier(0);
-  if constexpr (K > F) qv_chain_up<T, K - 1, F>(c, s);
-}
-template <class T, int K, class C>
-__device__ __forceinline__ void qv_chain_at(const C& c, QvState<T>& s) {
-  if constexpr (chain_end<T>(K)) {
-    constexpr int F = chain_first<T>(K), P = T::parent[F];
-    double cur[6] = {0, 0, 0, 0, 0, 0};
-    if constexpr (P >= 0) {
-      if constexpr (first_contrib<T>(F) && n_children<T>(P) > 1) qv_vel_from_root<T, P>(c, s.vel[P]);
-#pragma unroll
-      for (int k = 0; k < 6; ++k) cur[k] = s.vel[P][k];
-    }
-    qv_chain_down<T, F, F, K>(c, cur);
-    qv_chain_up<T, K, F>(c, s);
-  }
-}
-template <class T, class C, int... Ks>
-__device__ __forceinline__ void qv_all(const C& c, QvState<T>& s, std::integer_sequence<int, Ks...>) {
-  (qv_chain_at<T, T::N - 1 - Ks>(c, s), ...);
+  if constexpr (K > F) chain_up<T, K - 1, F>(c, s);
 }
 
 template <class T, bool SP>
@@ -1905,7 +1818,7 @@ __global__ __launch_bounds__(LBS, 2) void lin_static_qvcache_kernel(LinParams p,
   const int64_t t = bt % Tn;
   __shared__ double s_vel[MAXCH * 6 * LBS];
   if (bt >= p.d.batch * Tn) return;                       // (no workgroup barrier below)
-  QvCtx<SP> c;
+  QvCtx<T, SP> c;
   c.m = model;
   c.xg = xs + ((int64_t)b * (Tn + 1) + t) * n;
   c.qc = qcache + bt * p.qc_bt + (SP ? 0 : cfgi * (nv * rbd::QC_STRIDE));
@@ -1920,7 +1833,7 @@ __global__ __launch_bounds__(LBS, 2) void lin_static_qvcache_kernel(LinParams p,
   c.jn = cfgi - 1;
   c.eps = sqrt(sqrt(DBL_EPSILON));
   QvState<T> s;
-  qv_all<T>(c, s, std::make_integer_sequence<int, nv>{});
+  chains_up_all<T>(c, s, std::make_integer_sequence<int, nv>{});
 }
 
 // lin_static_vcache_kernel: v-cache entries 1 + i = (q, v + eps e_i): first pass of the ABA on the cached base q-part
@@ -1934,22 +1847,13 @@ __device__ __forceinline__ void vc_joint(const DevModel& m, const double* __rest
   const double* a = m.axis[K];
   double vK = xg[T::N + K];
   if (K == iv) vK = vK + eps;
-  double vJ[6] = {0, 0, 0, 0, 0, 0}, v[6], cb[6], pA[6], Iv[6], Iac[6];
-  vJ[o] = a[0] * vK; vJ[o + 1] = a[1] * vK; vJ[o + 2] = a[2] * vK;
-  if constexpr (T::parent[K] >= 0) rbd::xform_motion(E, r, vel[T::parent[K]], v);
-  else {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) v[k] = 0.0;
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) { v[k] += vJ[k]; vel[K][k] = v[k]; }
-  rbd::crm(v, vJ, cb);
-  rbd::sym6_mv(m.I6[K], v, Iv);
-  rbd::crf(v, Iv, pA);
-  rbd::sym6_mv(Ia, cb, Iac);
+  double vJ[6], vrec[18];
+  step_joint_motion<o>(a, vK, vJ);
+  step_link_vel<(T::parent[K] < 0)>(E, r, vel[T::parent[K] >= 0 ? T::parent[K] : 0], vJ, vel[K]);
+  step_vpart(m.I6[K], Ia, vel[K], vJ, vrec);
   double* vo = vc + K * rbd::VC_STRIDE;
 #pragma unroll
-  for (int k = 0; k < 6; ++k) { vo[k] = cb[k]; vo[6 + k] = pA[k]; vo[12 + k] = Iac[k]; }
+  for (int k = 0; k < 18; ++k) vo[k] = vrec[k];
   __builtin_amdgcn_sched_barrier(0);
 }
 template <class T, int... Ks>
