@@ -1,7 +1,9 @@
 // frame_cost.h -- per-instance frame-position costs (DDP_HIP_FLAG_FRAME_COST, ddp_hip.h) and frame-orientation costs
-// (DDP_HIP_FLAG_FRAME_ORIENT_COST): the kernel-side description and the traversals they need.  The terms themselves are formed
-// in fwd.hip (cost values) and lin.hip (derivatives).
+// (DDP_HIP_FLAG_FRAME_ORIENT_COST): the kernel-side description and the jacobians they need (the walks for the values,
+// rbd::frame_point and rbd::frame_rotation, are frame_walk.h's).  The terms themselves are formed in fwd.hip (cost values) and
+// lin.hip (derivatives).
 #pragma once
+#include "frame_walk.h"
 #include "internal.h"
 #include "lie.h"
 #include "rbd.h"
@@ -32,87 +34,6 @@ inline FrameCostDev frame_cost_dev(const ddp_hip_ctx* ctx) {
 }
 
 namespace rbd {
-
-// World position of the point `off` of joint `joint`, walking joint -> root with the point alone (no placements are kept):
-// p <- Rp (R_axis(q_i) p) + pp for a revolute joint, Rp (p + q_i axis) + pp for a prismatic one, R(quat) p + trans for a
-// free-flyer root.  M: DevModel or CoopModel (the tables in LDS)
-template <class M>
-__device__ __forceinline__ void frame_point(const M& m, bool ff, int joint, const double* off, const double* q, double* p) {
-  double v[3] = {off[0], off[1], off[2]};
-  for (int j = joint; j >= 0; j = m.parent[j]) {
-    double w[3];
-    if (j == 0 && ff) {
-      double R[9];
-      lie::quat_to_R(q + 3, R);
-      mv3(R, v, w);
-      v[0] = w[0] + q[0]; v[1] = w[1] + q[1]; v[2] = w[2] + q[2];
-      break;
-    }
-    const double* a = m.axis[j];
-    const double qj = q[ff ? j + 6 : j];
-    if (m.jtype[j] == DDP_HIP_JOINT_REVOLUTE) {
-      double s, c, av[3], aav[3];
-      sincos(qj, &s, &c);
-      cross3(a, v, av);
-      cross3(a, av, aav);
-      const double omc = 1.0 - c;
-      w[0] = v[0] + (s * av[0] + omc * aav[0]); w[1] = v[1] + (s * av[1] + omc * aav[1]); w[2] = v[2] + (s * av[2] + omc * aav[2]);
-    } else {
-      w[0] = v[0] + a[0] * qj; w[1] = v[1] + a[1] * qj; w[2] = v[2] + a[2] * qj;
-    }
-    mv3(m.Rp[j], w, v);
-    v[0] += m.pp[j][0]; v[1] += m.pp[j][1]; v[2] += m.pp[j][2];
-  }
-  p[0] = v[0]; p[1] = v[1]; p[2] = v[2];
-}
-
-// a term of weight 0 is left out, and with all three of a frame the walk itself
-__device__ __forceinline__ bool frame_weights_any(const double* w) { return w[0] != 0.0 || w[1] != 0.0 || w[2] != 0.0; }
-// ... and with all n of a block the block's work
-__device__ __forceinline__ bool weights_any(const double* w, int n) {
-  bool any = false;
-  for (int k = 0; k < n; ++k) any |= w[k] != 0.0;
-  return any;
-}
-
-// World rotation R (row-major, world = R body) of joint `joint`'s frame, walking joint -> root like frame_point with the three
-// columns R e_a alone: c <- Rp (R_axis(q_i) c) for a revolute joint, Rp c for a prismatic one, R(quat) c for a free-flyer root.
-// M: DevModel or CoopModel (the tables in LDS)
-template <class M>
-__device__ __forceinline__ void frame_rotation(const M& m, bool ff, int joint, const double* q, double* R) {
-  double c[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  for (int j = joint; j >= 0; j = m.parent[j]) {
-    double w[3];
-    if (j == 0 && ff) {
-      double Rq[9];
-      lie::quat_to_R(q + 3, Rq);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { mv3(Rq, c[k], w); c[k][0] = w[0]; c[k][1] = w[1]; c[k][2] = w[2]; }
-      break;
-    }
-    if (m.jtype[j] == DDP_HIP_JOINT_REVOLUTE) {
-      const double* a = m.axis[j];
-      double s, cs;
-      sincos(q[ff ? j + 6 : j], &s, &cs);
-      const double omc = 1.0 - cs;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        double av[3], aav[3];
-        cross3(a, c[k], av);
-        cross3(a, av, aav);
-        w[0] = c[k][0] + (s * av[0] + omc * aav[0]); w[1] = c[k][1] + (s * av[1] + omc * aav[1]); w[2] = c[k][2] + (s * av[2] + omc * aav[2]);
-        mv3(m.Rp[j], w, c[k]);
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { mv3(m.Rp[j], c[k], w); c[k][0] = w[0]; c[k][1] = w[1]; c[k][2] = w[2]; }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) R[3 * r + k] = c[k][r];
-}
 
 // The frame's world position p and its true point jacobian P = dp / d(delta q) (3 x nv, stored at P[3 * column + row]; only
 // the columns of the joints on the path root .. joint are written, their tangent indices are returned as a bit mask):

@@ -3,8 +3,7 @@
 // of their own in fwd.hip (cost values: frame_vel_cost_kernel, summed by com_sum_kernel) and lin.hip (derivatives:
 // lin_frame_vel_cost_kernel); model_api.hip evaluates one state with the same code.
 #pragma once
-#include "com_cost.h"
-#include "frame_cost.h"
+#include "frame_walk.h"
 #include "internal.h"
 #include "lie.h"
 #include "rbd.h"
@@ -38,7 +37,8 @@ namespace rbd {
 // the point p, its linear velocity l and the frame's angular velocity w are carried in the current joint's axes, every joint
 // adds its own rate (revolute: w += v_j a, l += v_j a x p; prismatic: l += v_j a; free-flyer root, body twist with the linear part
 // first: l += v_lin + v_ang x p, w += v_ang) and rotates the three into its parent's axes.  No per-joint arrays.  lin / ang: form
-// the linear / the angular quantities (pd / om are left alone otherwise)
+// the linear / the angular quantities (pd / om are left alone otherwise).  Its own loop, not walk_to_root: the rates enter
+// between a joint's rotation and the step to its parent; the step's pieces are the walk's (frame_walk.h)
 __device__ __forceinline__ void frame_velocity(const DevModel& m, int joint, const double* off, const double* q, const double* v, bool lin,
                                                bool ang, double* pd, double* om) {
   const bool ff = m.ff != 0;
@@ -50,11 +50,11 @@ __device__ __forceinline__ void frame_velocity(const DevModel& m, int joint, con
       if (lin) {
         cross3(v + 3, p, t);
         l[0] += v[0] + t[0]; l[1] += v[1] + t[1]; l[2] += v[2] + t[2];
-        mv3(R, l, t); l[0] = t[0]; l[1] = t[1]; l[2] = t[2];
+        dir_to_world(R, l);
       }
       if (ang) {
         w[0] += v[3]; w[1] += v[4]; w[2] += v[5];
-        mv3(R, w, t); w[0] = t[0]; w[1] = t[1]; w[2] = t[2];
+        dir_to_world(R, w);
       }
       break;
     }
@@ -64,23 +64,23 @@ __device__ __forceinline__ void frame_velocity(const DevModel& m, int joint, con
       double s, c;
       sincos(qj, &s, &c);
       const double omc = 1.0 - c;
-      com_rotate(a, s, omc, p);
+      axis_rotate(a, s, omc, p);
       if (lin) {
-        com_rotate(a, s, omc, l);
+        axis_rotate(a, s, omc, l);
         cross3(a, p, t);
         l[0] += vj * t[0]; l[1] += vj * t[1]; l[2] += vj * t[2];
       }
       if (ang) {
-        com_rotate(a, s, omc, w);
+        axis_rotate(a, s, omc, w);
         w[0] += vj * a[0]; w[1] += vj * a[1]; w[2] += vj * a[2];
       }
     } else {
       p[0] += a[0] * qj; p[1] += a[1] * qj; p[2] += a[2] * qj;
       if (lin) { l[0] += vj * a[0]; l[1] += vj * a[1]; l[2] += vj * a[2]; }
     }
-    mv3(m.Rp[j], p, t); p[0] = t[0] + m.pp[j][0]; p[1] = t[1] + m.pp[j][1]; p[2] = t[2] + m.pp[j][2];
-    if (lin) { mv3(m.Rp[j], l, t); l[0] = t[0]; l[1] = t[1]; l[2] = t[2]; }
-    if (ang) { mv3(m.Rp[j], w, t); w[0] = t[0]; w[1] = t[1]; w[2] = t[2]; }
+    point_to_parent(m, j, p);
+    if (lin) dir_to_parent(m, j, l);
+    if (ang) dir_to_parent(m, j, w);
   }
   if (lin) { pd[0] = l[0]; pd[1] = l[1]; pd[2] = l[2]; }
   if (ang) { om[0] = w[0]; om[1] = w[1]; om[2] = w[2]; }
@@ -100,12 +100,10 @@ __device__ __forceinline__ double frame_vel_term(const double* w, const double* 
 
 // What the lanes of one wave leave each other for one state: lane j's joint in slot j, then the frames' jacobians
 struct VelWaveLds {
-  double a[DDP_MAXJ][3], o[DDP_MAXJ][3];   // world axis a_j (0 on a free-flyer root), world origin o_j of joint j
+  JointWorldLds jw;                        // a_j, o_j, the paths, R_0
   double wv[DDP_MAXJ][3];                  // W_j v_j: v_j a_j (revolute), 0 (prismatic), R_0 v_ang (free-flyer root)
   double lv[DDP_MAXJ][3];                  // the part of P_j v_j that no lever arm enters: v_j a_j (prismatic), R_0 v_lin (root)
   double om[DDP_MAXJ][3];                  // omega_<=j = sum_{i <= j on j's path} W_i v_i
-  unsigned long long mask[DDP_MAXJ];       // bit i: joint i is on the path root .. j (j itself included)
-  double R0[9];                            // a free-flyer root's rotation (row-major)
   double p[DDP_HIP_MAX_COST_FRAMES][3];    // p_f
   double vel[DDP_HIP_MAX_COST_FRAMES][6];  // (pdot_f, omega_f)
   // A_f = [ dr/d(delta q) | dr/dv ] by tangent column: A[f][0][c] = (D_c, E_c), A[f][1][c] = (P_c, W_c)
@@ -115,73 +113,27 @@ struct VelWaveLds {
   int idx[DDP_MAXJ];                       // the tangent columns of the live frames' paths, ascending
 };
 
-// a path as a mask over tangent columns: joint j is column j, behind a free-flyer root column j + 5 and the root columns 0 .. 5
-__device__ __forceinline__ unsigned long long vel_tangent_mask(bool ff, unsigned long long joints) {
-  return ff ? (((joints >> 1) << 6) | 63ull) : joints;
-}
-
-// Joint `joint` seen from the world, walking joint -> root like com_walk with two vectors: o, the origin of the joint's frame (a
-// point) and a, the joint's axis (a direction; 0 on a free-flyer root).  Returns the path as a bit mask over joints
-__device__ __forceinline__ unsigned long long vel_walk(const DevModel& m, bool ff, int joint, const double* q, double* o, double* a) {
-  o[0] = o[1] = o[2] = 0.0;
-  if (joint == 0 && ff) { a[0] = a[1] = a[2] = 0.0; }
-  else { a[0] = m.axis[joint][0]; a[1] = m.axis[joint][1]; a[2] = m.axis[joint][2]; }
-  unsigned long long mask = 0;
-  for (int j = joint; j >= 0; j = m.parent[j]) {
-    mask |= 1ull << j;
-    double w[3];
-    if (j == 0 && ff) {
-      double R[9];
-      lie::quat_to_R(q + 3, R);
-      mv3(R, o, w); o[0] = w[0] + q[0]; o[1] = w[1] + q[1]; o[2] = w[2] + q[2];
-      mv3(R, a, w); a[0] = w[0]; a[1] = w[1]; a[2] = w[2];
-      break;
-    }
-    const double* ax = m.axis[j];
-    const double qj = q[ff ? j + 6 : j];
-    if (m.jtype[j] == DDP_HIP_JOINT_REVOLUTE) {
-      double s, c;
-      sincos(qj, &s, &c);
-      const double omc = 1.0 - c;
-      com_rotate(ax, s, omc, o);
-      if (j != joint) com_rotate(ax, s, omc, a);           // (a joint's own rotation leaves its axis where it is)
-    } else {
-      o[0] += ax[0] * qj; o[1] += ax[1] * qj; o[2] += ax[2] * qj;
-    }
-    mv3(m.Rp[j], o, w); o[0] = w[0] + m.pp[j][0]; o[1] = w[1] + m.pp[j][1]; o[2] = w[2] + m.pp[j][2];
-    mv3(m.Rp[j], a, w); a[0] = w[0]; a[1] = w[1]; a[2] = w[2];
-  }
-  return mask;
-}
-
-// The jacobians by a wave, step 1 of 4: lane j < nj walks its joint's path once and leaves a_j, o_j, its path and what its own
-// rate contributes (W_j v_j, and the lever-free part of P_j v_j) in S.  (A workgroup barrier follows.)
+// The jacobians by a wave, step 1 of 4: lane j < nj walks its joint's path once and leaves a_j, o_j, its path (stage_joint_lane)
+// and what its own rate contributes (W_j v_j, and the lever-free part of P_j v_j) in S.  (A workgroup barrier follows.)
 __device__ __forceinline__ void vel_stage_lane(const DevModel& m, const double* q, const double* v, int j, VelWaveLds& S) {
   const bool ff = m.ff != 0;
-  double o[3], a[3];
-  S.mask[j] = vel_walk(m, ff, j, q, o, a);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { S.a[j][k] = a[k]; S.o[j][k] = o[k]; }
+  stage_joint_lane<0>(m, q, j, S.jw, nullptr);
   if (j == 0 && ff) {
-    double R[9], t[3];
-    lie::quat_to_R(q + 3, R);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) S.R0[k] = R[k];
-    mv3(R, v, t); S.lv[0][0] = t[0]; S.lv[0][1] = t[1]; S.lv[0][2] = t[2];
-    mv3(R, v + 3, t); S.wv[0][0] = t[0]; S.wv[0][1] = t[1]; S.wv[0][2] = t[2];
+    mv3(S.jw.R0, v, S.lv[0]);
+    mv3(S.jw.R0, v + 3, S.wv[0]);
     return;
   }
   const double vj = v[ff ? j + 5 : j];
   const bool rev = m.jtype[j] == DDP_HIP_JOINT_REVOLUTE;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) { S.wv[j][k] = rev ? vj * a[k] : 0.0; S.lv[j][k] = rev ? 0.0 : vj * a[k]; }
+  for (int k = 0; k < 3; ++k) { S.wv[j][k] = rev ? vj * S.jw.a[j][k] : 0.0; S.lv[j][k] = rev ? 0.0 : vj * S.jw.a[j][k]; }
 }
 
 // ... step 2 of 4: lane j < nj adds W_i v_i over its path in ascending order (a fixed order, no atomics): omega_<=j.  (A
 // workgroup barrier follows.)
 __device__ __forceinline__ void vel_prefix_lane(int j, VelWaveLds& S) {
   double s[3] = {0.0, 0.0, 0.0};
-  for (unsigned long long rest = S.mask[j]; rest; rest &= rest - 1) {
+  for (unsigned long long rest = S.jw.mask[j]; rest; rest &= rest - 1) {
     const int i = __builtin_ctzll(rest);
     s[0] += S.wv[i][0]; s[1] += S.wv[i][1]; s[2] += S.wv[i][2];
   }
@@ -195,7 +147,8 @@ __device__ __forceinline__ void vel_prefix_lane(int j, VelWaveLds& S) {
 // velocity and the masks of the columns that carry something.  (A workgroup barrier follows the last frame.)
 __device__ __forceinline__ void vel_frame_lane(const DevModel& m, int j, int f, int jf, bool lin, bool ang, VelWaveLds& S) {
   const bool ff = m.ff != 0;
-  const unsigned long long Mf = S.mask[jf];
+  const JointWorldLds& W = S.jw;
+  const unsigned long long Mf = W.mask[jf];
   if (!((Mf >> j) & 1)) return;
   const double pf[3] = {S.p[f][0], S.p[f][1], S.p[f][2]};
   const double wf[3] = {S.om[jf][0], S.om[jf][1], S.om[jf][2]};
@@ -204,7 +157,7 @@ __device__ __forceinline__ void vel_frame_lane(const DevModel& m, int j, int f, 
   if (lin)
     for (unsigned long long rest = Mf; rest; rest &= rest - 1) {
       const int i = __builtin_ctzll(rest);
-      const double lever[3] = {pf[0] - S.o[i][0], pf[1] - S.o[i][1], pf[2] - S.o[i][2]};
+      const double lever[3] = {pf[0] - W.o[i][0], pf[1] - W.o[i][1], pf[2] - W.o[i][2]};
       double c[3];
       cross3(S.wv[i], lever, c);
       const double term[3] = {S.lv[i][0] + c[0], S.lv[i][1] + c[1], S.lv[i][2] + c[2]};
@@ -216,31 +169,28 @@ __device__ __forceinline__ void vel_frame_lane(const DevModel& m, int j, int f, 
     for (int k = 0; k < 3; ++k) { S.vel[f][k] = pd[k]; S.vel[f][3 + k] = wf[k]; }
     // the columns that carry something: P all of the path; W and E the revolute joints and the root's angular columns; D those
     // and the prismatic joints (the root's linear columns have neither D nor E)
-    unsigned long long rot = 0, all = 0;
+    const unsigned long long all = tangent_mask(ff, Mf);
+    unsigned long long rot = 0;
     for (unsigned long long rest = Mf; rest; rest &= rest - 1) {
       const int i = __builtin_ctzll(rest);
-      if (i == 0 && ff) { all |= 63ull; rot |= 56ull; continue; }
-      const unsigned long long bit = 1ull << (ff ? i + 5 : i);
-      all |= bit;
-      if (m.jtype[i] == DDP_HIP_JOINT_REVOLUTE) rot |= bit;
+      if (i == 0 && ff) { rot |= 56ull; continue; }
+      if (m.jtype[i] == DDP_HIP_JOINT_REVOLUTE) rot |= 1ull << (ff ? i + 5 : i);
     }
     S.cm[f][0] = lin ? (ff ? all & ~7ull : all) : 0ull;
     S.cm[f][1] = ang ? rot : 0ull;
     S.cm[f][2] = lin ? all : 0ull;
     S.cm[f][3] = ang ? rot : 0ull;
   }
-  const double lever[3] = {pf[0] - S.o[j][0], pf[1] - S.o[j][1], pf[2] - S.o[j][2]};
   double t[3];
   if (j == 0 && ff) {
 #pragma unroll
     for (int cc = 0; cc < 3; ++cc) {
-      const double e[3] = {S.R0[cc], S.R0[3 + cc], S.R0[6 + cc]};
+      const double e[3] = {W.R0[cc], W.R0[3 + cc], W.R0[6 + cc]};
       double* Aq = S.A[f][0][3 + cc];
       double* Av = S.A[f][1][3 + cc];
-      double* Al = S.A[f][1][cc];
       if (lin) {
-        Al[0] = e[0]; Al[1] = e[1]; Al[2] = e[2];
-        cross3(e, lever, t); Av[0] = t[0]; Av[1] = t[1]; Av[2] = t[2];
+        point_column(m, ff, W, cc, pf, S.A[f][1][cc]);
+        point_column(m, ff, W, 3 + cc, pf, Av);
         cross3(e, pd, t); Aq[0] = t[0]; Aq[1] = t[1]; Aq[2] = t[2];
       }
       if (ang) {
@@ -251,14 +201,17 @@ __device__ __forceinline__ void vel_frame_lane(const DevModel& m, int j, int f, 
     return;
   }
   const int vi = ff ? j + 5 : j;
-  const double a[3] = {S.a[j][0], S.a[j][1], S.a[j][2]};
+  const double a[3] = {W.a[j][0], W.a[j][1], W.a[j][2]};
   double* Aq = S.A[f][0][vi];
   double* Av = S.A[f][1][vi];
+  double P[3];
+  if (lin) {
+    point_column(m, ff, W, vi, pf, P);
+    Av[0] = P[0]; Av[1] = P[1]; Av[2] = P[2];
+  }
   if (m.jtype[j] == DDP_HIP_JOINT_REVOLUTE) {
     if (lin) {
-      double P[3], d1[3], d2[3];
-      cross3(a, lever, P);
-      Av[0] = P[0]; Av[1] = P[1]; Av[2] = P[2];
+      double d1[3], d2[3];
       cross3(wj, P, d1);
       const double rest[3] = {pd[0] - pj[0], pd[1] - pj[1], pd[2] - pj[2]};
       cross3(a, rest, d2);
@@ -270,15 +223,8 @@ __device__ __forceinline__ void vel_frame_lane(const DevModel& m, int j, int f, 
       cross3(a, dw, t); Aq[3] = t[0]; Aq[4] = t[1]; Aq[5] = t[2];
     }
   } else if (lin) {
-    Av[0] = a[0]; Av[1] = a[1]; Av[2] = a[2];
     cross3(wj, a, t); Aq[0] = t[0]; Aq[1] = t[1]; Aq[2] = t[2];
   }
-}
-
-// the tangent columns of the live frames' paths (U, the same in every lane), ascending, into S.idx by lane `tid`.  (A workgroup
-// barrier follows.)
-__device__ __forceinline__ void vel_index_lane(unsigned long long U, int tid, VelWaveLds& S) {
-  if (tid < 64 && ((U >> tid) & 1)) S.idx[__builtin_popcountll(U & ((1ull << tid) - 1))] = tid;
 }
 
 // ... step 4 of 4: the wave (lane tid of nt) adds, over the rows and columns of the live frames' paths alone (nu tangent columns

@@ -832,6 +832,32 @@ __device__ __forceinline__ void cost_pair_store(double* out, int64_t e, double s
   if (add) { if (any) out[e] += sum; }
   else out[e] = sum;
 }
+// The value kernels with L lanes per pair (64 / L pairs per wave) share this body: decode the pair; lane k < n of the group forms
+// one term, form(k, bt1, x, &term) -> formed (x: the pair's state), and leaves term and flag in LDS (s_term, s_formed: 64 entries
+// each, the kernel's own); the group's first lane folds the n terms in ascending order -- the sum of the formed ones, or with MIN
+// the rbd::obstacle_min of them all from +inf (no flags: s_formed may be null) -- and cost_pair_store writes the result
+template <int L, bool MIN, class Form>
+__device__ __forceinline__ void pair_lanes_fold(double* s_term, int32_t* s_formed, int n, const double* xs, int64_t traj_stride, int64_t count,
+                                                int32_t T1, int32_t nx, int32_t na, const int32_t* state, int32_t round, double* out, int32_t add,
+                                                Form form) {
+  const int tid = threadIdx.x, g = tid / L, k = tid % L;
+  const int64_t e = (int64_t)blockIdx.x * (64 / L) + g;
+  const CostPair pr = cost_pair_decode(e, count, T1, na, state, round);
+  double term = MIN ? INFINITY : 0.0;
+  bool formed = false;
+  if (pr.live && k < n) formed = form(k, pr.bt1, xs + pr.traj * traj_stride + (int64_t)pr.t * nx, &term);
+  s_term[tid] = term;
+  if (!MIN) s_formed[tid] = formed ? 1 : 0;
+  __syncthreads();
+  if (k != 0 || pr.skip) return;
+  double acc = MIN ? INFINITY : 0.0;
+  bool any = false;
+  for (int i = 0; i < n; ++i) {
+    if (MIN) acc = rbd::obstacle_min(acc, s_term[tid + i]);
+    else if (s_formed[tid + i]) { acc += s_term[tid + i]; any = true; }
+  }
+  cost_pair_store(out, e, acc, any, add);
+}
 
 // The centre-of-mass terms (DDP_HIP_FLAG_COM_COST, ddp_hip.h) of a list of states, in kernels of their own that add onto what the
 // kernels above leave (none of them knows the term).  The list: `count` (trajectory, t) pairs, t = 0 .. T, trajectory k's states
@@ -896,39 +922,19 @@ __global__ void com_sum_kernel(const double* cand, double* fw_dcost, const int32
 __global__ __launch_bounds__(64) void frame_vel_cost_kernel(FrameVelCostDev fv, const DevModel* model, const double* xs, int64_t traj_stride,
                                                             int64_t count, int32_t T1, int32_t nx, int32_t na, const int32_t* state,
                                                             int32_t round, double* out, int32_t add) {
-  constexpr int L = DDP_HIP_MAX_COST_FRAMES;
   __shared__ double s_term[64];
-  __shared__ int32_t s_live[64];
+  __shared__ int32_t s_walked[64];
   const DevModel& m = *model;
-  const int tid = threadIdx.x, g = tid / L, f = tid % L;
-  const int64_t e = (int64_t)blockIdx.x * (64 / L) + g;
-  const CostPair pr = cost_pair_decode(e, count, T1, na, state, round);
-  const int64_t traj = pr.traj, bt1 = pr.bt1;
-  const int t = pr.t;
-  const bool skip = pr.skip;
-  bool live = pr.live;
-  double term = 0.0;
-  int32_t walked = 0;
-  if (live && f < fv.nf) {
+  pair_lanes_fold<DDP_HIP_MAX_COST_FRAMES, false>(s_term, s_walked, fv.nf, xs, traj_stride, count, T1, nx, na, state, round, out, add,
+                                                  [&](int f, int64_t bt1, const double* x, double* term) {
     const double* w = fv.weight + (bt1 * fv.nf + f) * 6;
     const bool lin = rbd::frame_weights_any(w), ang = rbd::frame_weights_any(w + 3);
-    if (lin || ang) {
-      const double* x = xs + traj * traj_stride + (int64_t)t * nx;
-      double pd[3] = {0.0, 0.0, 0.0}, om[3] = {0.0, 0.0, 0.0};
-      rbd::frame_velocity(m, fv.joint[f], fv.off[f], x, x + m.nq, lin, ang, pd, om);
-      term = rbd::frame_vel_term(w, fv.target + (bt1 * fv.nf + f) * 6, pd, om);
-      walked = 1;
-    }
-  }
-  s_term[tid] = term;
-  s_live[tid] = walked;
-  __syncthreads();
-  if (f != 0 || skip) return;
-  double sum = 0.0;
-  bool any = false;
-  for (int k = 0; k < fv.nf; ++k)
-    if (s_live[tid + k]) { sum += s_term[tid + k]; any = true; }
-  cost_pair_store(out, e, sum, any, add);
+    if (!lin && !ang) return false;
+    double pd[3] = {0.0, 0.0, 0.0}, om[3] = {0.0, 0.0, 0.0};
+    rbd::frame_velocity(m, fv.joint[f], fv.off[f], x, x + m.nq, lin, ang, pd, om);
+    *term = rbd::frame_vel_term(w, fv.target + (bt1 * fv.nf + f) * 6, pd, om);
+    return true;
+  });
 }
 
 // The obstacle terms (DDP_HIP_FLAG_OBSTACLE_COST, ddp_hip.h) of a list of states, added on top like the frame-velocity terms above:
@@ -941,66 +947,39 @@ __global__ __launch_bounds__(64) void frame_vel_cost_kernel(FrameVelCostDev fv, 
 __global__ __launch_bounds__(64) void obstacle_cost_kernel(ObstacleCostDev ob, const DevModel* model, const double* xs, int64_t traj_stride,
                                                            int64_t count, int32_t T1, int32_t nx, int32_t na, const int32_t* state,
                                                            int32_t round, double* out, int32_t add) {
-  constexpr int L = DDP_HIP_MAX_COLLISION_POINTS;
   __shared__ double s_term[64];
   __shared__ int32_t s_act[64];
   const DevModel& m = *model;
-  const int tid = threadIdx.x, g = tid / L, k = tid % L;
-  const int64_t e = (int64_t)blockIdx.x * (64 / L) + g;
-  const CostPair pr = cost_pair_decode(e, count, T1, na, state, round);
-  const int64_t traj = pr.traj, bt1 = pr.bt1;
-  const int t = pr.t;
-  const bool skip = pr.skip;
-  bool live = pr.live;
-  double term = 0.0;
-  int32_t act = 0;
-  if (live && k < ob.np) {
+  pair_lanes_fold<DDP_HIP_MAX_COLLISION_POINTS, false>(s_term, s_act, ob.np, xs, traj_stride, count, T1, nx, na, state, round, out, add,
+                                                       [&](int k, int64_t bt1, const double* x, double* term) {
     const double* w = ob.weight + bt1 * ob.no;
-    if (rbd::weights_any(w, ob.no)) {
-      const double off[3] = {ob.off[k][0], ob.off[k][1], ob.off[k][2]};
-      double pk[3];
-      bool a = false;
-      rbd::frame_point(m, m.ff != 0, ob.joint[k], off, xs + traj * traj_stride + (int64_t)t * nx, pk);
-      term = rbd::obstacle_point_term(ob, k, pk, ob.geom + bt1 * ob.no * 4, w, &a);
-      act = a ? 1 : 0;
-    }
-  }
-  s_term[tid] = term;
-  s_act[tid] = act;
-  __syncthreads();
-  if (k != 0 || skip) return;
-  double sum = 0.0;
-  bool any = false;
-  for (int i = 0; i < ob.np; ++i)
-    if (s_act[tid + i]) { sum += s_term[tid + i]; any = true; }
-  cost_pair_store(out, e, sum, any, add);
+    if (!rbd::weights_any(w, ob.no)) return false;
+    const double off[3] = {ob.off[k][0], ob.off[k][1], ob.off[k][2]};
+    double pk[3];
+    bool act = false;
+    rbd::frame_point(m, m.ff != 0, ob.joint[k], off, x, pk);
+    *term = rbd::obstacle_point_term(ob, k, pk, ob.geom + bt1 * ob.no * 4, w, &act);
+    return act;
+  });
 }
 
-// ddp_hip_obstacle_clearance: the same lane layout over the `count` (instance, t) pairs of one resident trajectory, min instead of
-// sum: out[pair] = min over points and over slots with w != 0 of d_ko, +inf where no slot is live, NaN where a distance is NaN
+// ddp_hip_obstacle_clearance: the same lane layout over the `count` (instance, t) pairs of one resident trajectory (a list of
+// one-state trajectories, no candidates to skip), min instead of sum: out[pair] = min over points and over slots with w != 0 of
+// d_ko, +inf where no slot is live, NaN where a distance is NaN
 __global__ __launch_bounds__(64) void obstacle_clearance_kernel(ObstacleCostDev ob, const DevModel* model, const double* xs, int64_t count,
                                                                 int32_t nx, double* out) {
-  constexpr int L = DDP_HIP_MAX_COLLISION_POINTS;
   __shared__ double s_min[64];
   const DevModel& m = *model;
-  const int tid = threadIdx.x, g = tid / L, k = tid % L;
-  const int64_t e = (int64_t)blockIdx.x * (64 / L) + g;
-  const bool live = e < count;
-  double best = INFINITY;
-  if (live && k < ob.np) {
+  pair_lanes_fold<DDP_HIP_MAX_COLLISION_POINTS, true>(s_min, nullptr, ob.np, xs, nx, count, 1, nx, 1, nullptr, 0, out, 0,
+                                                      [&](int k, int64_t e, const double* x, double* best) {
     const double* w = ob.weight + e * ob.no;
-    if (rbd::weights_any(w, ob.no)) {
-      const double off[3] = {ob.off[k][0], ob.off[k][1], ob.off[k][2]};
-      double pk[3];
-      rbd::frame_point(m, m.ff != 0, ob.joint[k], off, xs + e * nx, pk);
-      best = rbd::obstacle_point_clearance(ob, k, pk, ob.geom + e * ob.no * 4, w);
-    }
-  }
-  s_min[tid] = best;
-  __syncthreads();
-  if (k != 0 || !live) return;
-  for (int i = 1; i < ob.np; ++i) best = rbd::obstacle_min(best, s_min[tid + i]);
-  out[e] = best;
+    if (!rbd::weights_any(w, ob.no)) return false;
+    const double off[3] = {ob.off[k][0], ob.off[k][1], ob.off[k][2]};
+    double pk[3];
+    rbd::frame_point(m, m.ff != 0, ob.joint[k], off, x, pk);
+    *best = rbd::obstacle_point_clearance(ob, k, pk, ob.geom + e * ob.no * 4, w);
+    return true;
+  });
 }
 
 // accept rule (ddp_fwd.ipp:56-60): the first (= largest) candidate with sum(new - old) <= 0; the winner's
@@ -1212,27 +1191,27 @@ extern "C" int ddp_hip_rollout(ddp_hip_ctx* ctx) {
 // The add-on kernels over `count` (trajectory, t) pairs of trajectories laid out like X (na per instance): one signature
 typedef void (*AddOnLaunch)(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add);
 
+// ... and one launch: one wave per `lanes`-lane group of pairs, the kernel's view `dev` of its term first; mid: what a kernel takes
+// between na and state (com_cost_kernel's lanes per evaluation)
+template <class Kernel, class Dev, class... Mid>
+static void launch_add_on(Kernel kernel, const Dev& dev, int lanes, ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state,
+                          int round, double* out, int add, Mid... mid) {
+  const Dims& d = ctx->d;
+  const int64_t per = 64 / lanes;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((count + per - 1) / per)), dim3(64), 0, ctx->stream, dev, ctx->model_d, xs, (d.T + 1) * d.nx, count,
+                     (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, mid..., state, (int32_t)round, out, (int32_t)add);
+}
+
 static void launch_com_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
-  const Dims& d = ctx->d;
-  int lpe = 8;
+  int32_t lpe = 8;
   while (lpe < ctx->model_h.nj) lpe *= 2;                            // (nj <= DDP_MAXJ = 64: one wave)
-  const int64_t per = 64 / lpe;
-  hipLaunchKernelGGL(com_cost_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(64), 0, ctx->stream, com_cost_dev(ctx), ctx->model_d, xs,
-                     (d.T + 1) * d.nx, count, (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, (int32_t)lpe, state, (int32_t)round, out, (int32_t)add);
+  launch_add_on(com_cost_kernel, com_cost_dev(ctx), lpe, ctx, xs, na, count, state, round, out, add, lpe);
 }
-
 static void launch_frame_vel_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
-  const Dims& d = ctx->d;
-  const int64_t per = 64 / DDP_HIP_MAX_COST_FRAMES;
-  hipLaunchKernelGGL(frame_vel_cost_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(64), 0, ctx->stream, frame_vel_cost_dev(ctx), ctx->model_d, xs,
-                     (d.T + 1) * d.nx, count, (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, state, (int32_t)round, out, (int32_t)add);
+  launch_add_on(frame_vel_cost_kernel, frame_vel_cost_dev(ctx), DDP_HIP_MAX_COST_FRAMES, ctx, xs, na, count, state, round, out, add);
 }
-
 static void launch_obstacle_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
-  const Dims& d = ctx->d;
-  const int64_t per = 64 / DDP_HIP_MAX_COLLISION_POINTS;
-  hipLaunchKernelGGL(obstacle_cost_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(64), 0, ctx->stream, obstacle_cost_dev(ctx), ctx->model_d, xs,
-                     (d.T + 1) * d.nx, count, (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, state, (int32_t)round, out, (int32_t)add);
+  launch_add_on(obstacle_cost_kernel, obstacle_cost_dev(ctx), DDP_HIP_MAX_COLLISION_POINTS, ctx, xs, na, count, state, round, out, add);
 }
 
 // The terms formed out of line, in the fixed order of their additions (after everything cost_kernel / the rollout kernels form

@@ -121,6 +121,42 @@ __device__ __forceinline__ LinCostBlock lin_cost_block(const LinParams& p, int64
   return k;
 }
 
+// The Gauss-Newton add of the terms with three axes per frame (frame positions, frame orientations, CoM), by the wave:
+//   gx[i] += sum_f sum_a A_f[a][i] (w_a r_a),   gxx[i][j] += sum_f sum_a A_f[a][min] w_a A_f[a][max]
+// over the tangent columns i, j < nv that some frame's mask holds (mask_of(f): the columns of A_f that are written; 0: the frame
+// is left out), frames and axes in their fixed order and entry (i, j) in (min, max) order: the block stays symmetric bit for
+// bit.  A: A_f[a][i] at A[f lda + 3 i + a]; w / wr: weights and weighted residuals [nf][3].  A term of weight 0 is left out, an
+// entry that no frame reaches is not touched
+template <class MaskOf>
+__device__ __forceinline__ void gn_add_wave(int nf, MaskOf mask_of, const double* A, int lda, const double* w, const double* wr, int nv, int n,
+                                            double* gx, double* gxx) {
+  const int tid = threadIdx.x;
+  unsigned long long all = 0;
+  for (int f = 0; f < nf; ++f) all |= mask_of(f);
+  for (int i = tid; i < nv; i += blockDim.x) {
+    if (!((all >> i) & 1)) continue;
+    double s = 0.0;
+    for (int f = 0; f < nf; ++f)
+      if ((mask_of(f) >> i) & 1)
+        for (int a = 0; a < 3; ++a)
+          if (w[3 * f + a] != 0.0) s += A[f * lda + 3 * i + a] * wr[3 * f + a];
+    gx[i] += s;
+  }
+  for (int e = tid; e < nv * nv; e += blockDim.x) {
+    const int i = e % nv, j = e / nv;
+    const int lo = i < j ? i : j, hi = i < j ? j : i;
+    double h = 0.0;
+    bool hit = false;
+    for (int f = 0; f < nf; ++f)
+      if (((mask_of(f) >> i) & 1) && ((mask_of(f) >> j) & 1)) {
+        hit = true;
+        for (int a = 0; a < 3; ++a)
+          if (w[3 * f + a] != 0.0) h += A[f * lda + 3 * lo + a] * w[3 * f + a] * A[f * lda + 3 * hi + a];
+      }
+    if (hit) gxx[i + (int64_t)j * n] += h;
+  }
+}
+
 // Frame-position cost (DDP_HIP_FLAG_FRAME_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after lin_cost_kernel /
 // lin_track_cost_kernel on the same stream: their output is the starting point, and only the entries of the joints on the
 // frames' paths are read and rewritten.  Lane f walks frame f's path once for p_f and the path columns of its point jacobian
@@ -155,31 +191,7 @@ __global__ __launch_bounds__(64) void lin_frame_cost_kernel(LinParams p, FrameCo
     s_mask[tid] = mask;
   }
   __syncthreads();
-  unsigned long long all = 0;
-  for (int f = 0; f < nf; ++f) all |= s_mask[f];
-  double *gx = blk.gx, *gxx = blk.gxx;
-  for (int i = tid; i < nv; i += blockDim.x) {
-    if (!((all >> i) & 1)) continue;
-    double s = 0.0;
-    for (int f = 0; f < nf; ++f)
-      if ((s_mask[f] >> i) & 1)
-        for (int a = 0; a < 3; ++a)
-          if (s_w[f][a] != 0.0) s += s_P[f][3 * i + a] * s_wr[f][a];
-    gx[i] += s;
-  }
-  for (int e = tid; e < nv * nv; e += blockDim.x) {
-    const int i = e % nv, j = e / nv;
-    const int lo = i < j ? i : j, hi = i < j ? j : i;
-    double h = 0.0;
-    bool hit = false;
-    for (int f = 0; f < nf; ++f)
-      if (((s_mask[f] >> i) & 1) && ((s_mask[f] >> j) & 1)) {
-        hit = true;
-        for (int a = 0; a < 3; ++a)
-          if (s_w[f][a] != 0.0) h += s_P[f][3 * lo + a] * s_w[f][a] * s_P[f][3 * hi + a];
-      }
-    if (hit) gxx[i + (int64_t)j * n] += h;
-  }
+  gn_add_wave(nf, [&](int f) { return s_mask[f]; }, &s_P[0][0], 3 * DDP_MAXJ, &s_w[0][0], &s_wr[0][0], nv, n, blk.gx, blk.gxx);
 }
 
 // Frame-orientation cost (DDP_HIP_FLAG_FRAME_ORIENT_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after
@@ -227,31 +239,7 @@ __global__ __launch_bounds__(64) void lin_frame_orient_cost_kernel(LinParams p, 
     s_mask[tid] = mask;
   }
   __syncthreads();
-  unsigned long long all = 0;
-  for (int f = 0; f < nf; ++f) all |= s_mask[f];
-  double *gx = blk.gx, *gxx = blk.gxx;
-  for (int i = tid; i < nv; i += blockDim.x) {
-    if (!((all >> i) & 1)) continue;
-    double s = 0.0;
-    for (int f = 0; f < nf; ++f)
-      if ((s_mask[f] >> i) & 1)
-        for (int a = 0; a < 3; ++a)
-          if (s_w[f][a] != 0.0) s += s_A[f][3 * i + a] * s_we[f][a];
-    gx[i] += s;
-  }
-  for (int e = tid; e < nv * nv; e += blockDim.x) {
-    const int i = e % nv, j = e / nv;
-    const int lo = i < j ? i : j, hi = i < j ? j : i;
-    double h = 0.0;
-    bool hit = false;
-    for (int f = 0; f < nf; ++f)
-      if (((s_mask[f] >> i) & 1) && ((s_mask[f] >> j) & 1)) {
-        hit = true;
-        for (int a = 0; a < 3; ++a)
-          if (s_w[f][a] != 0.0) h += s_A[f][3 * lo + a] * s_w[f][a] * s_A[f][3 * hi + a];
-      }
-    if (hit) gxx[i + (int64_t)j * n] += h;
-  }
+  gn_add_wave(nf, [&](int f) { return s_mask[f]; }, &s_A[0][0], 3 * DDP_MAXJ, &s_w[0][0], &s_we[0][0], nv, n, blk.gx, blk.gxx);
 }
 
 // Soft state limits (DDP_HIP_FLAG_STATE_LIMITS, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after lin_cost_kernel /
@@ -301,7 +289,7 @@ __global__ __launch_bounds__(64) void lin_com_cost_kernel(LinParams p, CoMCostDe
   __shared__ double s_w[3], s_wr[3];
   if (tid < m.nj) rbd::com_stage_lane(m, q, tid, S);
   __syncthreads();
-  if (tid < m.nj) rbd::com_column_lane(m, q, tid, S);
+  if (tid < m.nj) rbd::com_column_lane(m, tid, S);
   __syncthreads();
   if (tid < 3) {
     const double wa = w[tid];
@@ -309,21 +297,7 @@ __global__ __launch_bounds__(64) void lin_com_cost_kernel(LinParams p, CoMCostDe
     s_wr[tid] = wa != 0.0 ? wa * (S.c[tid] - cm.target[bt1 * 3 + tid]) : 0.0;
   }
   __syncthreads();
-  double *gx = blk.gx, *gxx = blk.gxx;
-  for (int i = tid; i < nv; i += blockDim.x) {
-    double s = 0.0;
-    for (int a = 0; a < 3; ++a)
-      if (s_w[a] != 0.0) s += S.J[3 * i + a] * s_wr[a];
-    gx[i] += s;
-  }
-  for (int e = tid; e < nv * nv; e += blockDim.x) {
-    const int i = e % nv, j = e / nv;
-    const int lo = i < j ? i : j, hi = i < j ? j : i;
-    double h = 0.0;
-    for (int a = 0; a < 3; ++a)
-      if (s_w[a] != 0.0) h += S.J[3 * lo + a] * s_w[a] * S.J[3 * hi + a];
-    gxx[i + (int64_t)j * n] += h;
-  }
+  gn_add_wave(1, [](int) { return ~0ull; }, S.J, 0, s_w, s_wr, nv, n, blk.gx, blk.gxx);   // one "frame" whose mask is every column
 }
 
 // Frame-velocity cost (DDP_HIP_FLAG_FRAME_VEL_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost
@@ -360,10 +334,10 @@ __global__ __launch_bounds__(64) void lin_frame_vel_cost_kernel(LinParams p, Fra
   for (int f = 0; f < nf; ++f) {
     const bool lin = rbd::frame_weights_any(w + 6 * f), ang = rbd::frame_weights_any(w + 6 * f + 3);
     if (!lin && !ang) continue;
-    U |= rbd::vel_tangent_mask(ff, S.mask[fv.joint[f]]);
+    U |= rbd::tangent_mask(ff, S.jw.mask[fv.joint[f]]);
     if (tid < m.nj) rbd::vel_frame_lane(m, tid, f, fv.joint[f], lin, ang, S);
   }
-  rbd::vel_index_lane(U, tid, S);
+  rbd::column_index_lane(U, tid, S.idx);
   __syncthreads();
   if (tid < 6 * nf) {
     const double wa = w[tid];
@@ -381,7 +355,7 @@ __global__ __launch_bounds__(64) void lin_frame_vel_cost_kernel(LinParams p, Fra
 // k < n_points walks point k (rbd::frame_point) and runs over its live slots in ascending order; a lane with an active pair
 // (w != 0, e != 0, a direction u) forms g_k = sum_o w e u and the symmetric M_k = sum_o w u u^T on the way, in registers.  One
 // wave-level vote (no LDS, no barrier) decides: a wave without an active pair returns here.  Phase 2: lanes j < nj stage world
-// axis, world origin and path of their joint in LDS (rbd::obstacle_stage_lane), the active lanes their p_k, g_k, M_k; the wave
+// axis, world origin and path of their joint in LDS (rbd::stage_joint_lane), the active lanes their p_k, g_k, M_k; the wave
 // then adds, over the union of the active points' paths alone,
 //   lx[i] += sum_k P_k[:, i] . g_k,     lxx[i][j] += sum_k P_k[:, min]^T M_k P_k[:, max]     (Gauss-Newton)
 // with the columns of P_k formed from the staged axes and origins (rbd::obstacle_add_wave: points in ascending order, entry
@@ -407,7 +381,7 @@ __global__ __launch_bounds__(64) void lin_obstacle_cost_kernel(LinParams p, Obst
   const unsigned active = (unsigned)__ballot(act);                  // bit k: point k has an active pair
   if (active == 0) return;
   __shared__ rbd::ObstacleWaveLds S;
-  if (tid < m.nj) rbd::obstacle_stage_lane(m, q, tid, S);
+  if (tid < m.nj) rbd::stage_joint_lane<0>(m, q, tid, S.jw, nullptr);
   if (act) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) { S.p[tid][a] = pk[a]; S.g[tid][a] = g[a]; }
@@ -417,8 +391,8 @@ __global__ __launch_bounds__(64) void lin_obstacle_cost_kernel(LinParams p, Obst
   __syncthreads();
   unsigned long long U = 0;
   for (int k = 0; k < ob.np; ++k)
-    if ((active >> k) & 1) U |= rbd::vel_tangent_mask(ff, S.mask[ob.joint[k]]);
-  if ((U >> tid) & 1) S.idx[__builtin_popcountll(U & ((1ull << tid) - 1))] = tid;
+    if ((active >> k) & 1) U |= rbd::tangent_mask(ff, S.jw.mask[ob.joint[k]]);
+  rbd::column_index_lane(U, tid, S.idx);
   __syncthreads();
   double *gx = blk.gx, *gxx = blk.gxx;
   rbd::obstacle_add_wave(m, S, ob, active, __builtin_popcountll(U), tid, (int)blockDim.x, n, gx, gxx);

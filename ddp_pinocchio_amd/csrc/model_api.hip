@@ -81,7 +81,7 @@ __global__ __launch_bounds__(64) void model_com_kernel(const DevModel* m, const 
   const int tid = threadIdx.x;
   if (tid < m->nj) rbd::com_stage_lane(*m, in, tid, S);
   __syncthreads();
-  if (tid < m->nj) rbd::com_column_lane(*m, in, tid, S);
+  if (tid < m->nj) rbd::com_column_lane(*m, tid, S);
   __syncthreads();
   if (tid < 3) out[tid] = S.c[tid];
   for (int i = tid; i < 3 * m->nv; i += blockDim.x) out[3 + i] = S.J[i];

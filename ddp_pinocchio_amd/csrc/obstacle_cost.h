@@ -3,8 +3,7 @@
 // the terms themselves are formed by kernels of their own in fwd.hip (cost values: obstacle_cost_kernel, summed by
 // com_sum_kernel; clearances: obstacle_clearance_kernel) and lin.hip (derivatives: lin_obstacle_cost_kernel).
 #pragma once
-#include "frame_cost.h"
-#include "frame_vel_cost.h"
+#include "frame_walk.h"
 #include "internal.h"
 #include "lie.h"
 #include "rbd.h"
@@ -95,27 +94,15 @@ __device__ __forceinline__ double obstacle_point_clearance(const ObstacleCostDev
   return best;
 }
 
-// What the lanes of one wave leave each other for the derivatives at one configuration (lin_obstacle_cost_kernel, phase 2)
+// What the lanes of one wave leave each other for the derivatives at one configuration (lin_obstacle_cost_kernel, phase 2):
+// lanes j < nj their joint (rbd::stage_joint_lane), the active lanes their point
 struct ObstacleWaveLds {
-  double a[DDP_MAXJ][3], o[DDP_MAXJ][3];       // world axis a_j (0 on a free-flyer root), world origin o_j of joint j
-  unsigned long long mask[DDP_MAXJ];           // bit i: joint i is on the path root .. j (j itself included)
-  double R0[9];                                // a free-flyer root's rotation (row-major)
+  JointWorldLds jw;                            // a_j, o_j, the paths, R_0
   double p[DDP_HIP_MAX_COLLISION_POINTS][3];   // p_k of the active points
   double g[DDP_HIP_MAX_COLLISION_POINTS][3];   // g_k = sum_o w e u
   double M[DDP_HIP_MAX_COLLISION_POINTS][6];   // M_k = sum_o w u u^T: xx xy xz yy yz zz
   int idx[DDP_MAXJ];                           // the tangent columns of the active points' paths, ascending
 };
-
-// Phase 2, step 1: lane j < nj walks its joint's path once and leaves a_j, o_j and the path (as rbd::com_stage_lane does, without
-// the masses); lane 0 of a free-flyer model leaves the root's rotation.  (A workgroup barrier follows.)
-__device__ __forceinline__ void obstacle_stage_lane(const DevModel& m, const double* q, int j, ObstacleWaveLds& S) {
-  const bool ff = m.ff != 0;
-  double o[3], a[3];
-  S.mask[j] = vel_walk(m, ff, j, q, o, a);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { S.a[j][k] = a[k]; S.o[j][k] = o[k]; }
-  if (j == 0 && ff) lie::quat_to_R(q + 3, S.R0);
-}
 
 // g_k and M_k of one point over its slots in ascending order, the pairs with w == 0 or e == 0 left out (and a sphere's centre at
 // p: no direction).  Returns whether any pair took part
@@ -139,32 +126,11 @@ __device__ __forceinline__ bool obstacle_point_reduce(const ObstacleCostDev& ob,
   return act;
 }
 
-// Column i (a tangent index on the point's path) of the true point jacobian P of the point p, from the staged axes and origins,
-// as frame_point_jacobian forms it: a_j x (p - o_j) for a revolute joint, a_j for a prismatic one; a free-flyer root (body
-// twists, linear part first): R_0 e_c and (R_0 e_c) x (p - o_0)
-__device__ __forceinline__ void obstacle_column(const DevModel& m, bool ff, const ObstacleWaveLds& S, int i, const double* p, double* col) {
-  if (ff && i < 6) {
-    const int c = i < 3 ? i : i - 3;
-    const double e[3] = {S.R0[c], S.R0[3 + c], S.R0[6 + c]};
-    if (i < 3) { col[0] = e[0]; col[1] = e[1]; col[2] = e[2]; return; }
-    const double lever[3] = {p[0] - S.o[0][0], p[1] - S.o[0][1], p[2] - S.o[0][2]};
-    cross3(e, lever, col);
-    return;
-  }
-  const int j = ff ? i - 5 : i;
-  if (m.jtype[j] == DDP_HIP_JOINT_REVOLUTE) {
-    const double lever[3] = {p[0] - S.o[j][0], p[1] - S.o[j][1], p[2] - S.o[j][2]};
-    cross3(S.a[j], lever, col);
-  } else {
-    col[0] = S.a[j][0]; col[1] = S.a[j][1]; col[2] = S.a[j][2];
-  }
-}
-
 // Phase 2, last step: the wave (lane tid of nt) adds, over the nu tangent columns of S.idx (the union of the active points'
 // paths) alone,
 //   gx[i] += sum_k P_k[:, i] . g_k,      gxx[i][j] += sum_k P_k[:, min]^T M_k P_k[:, max]      (Gauss-Newton)
 // the active points (bit k of `active`) in ascending order, a point off whose path i or j lies left out, entry (i, j) in
-// (min, max) order: the block stays symmetric bit for bit.  tmask[k]: point k's path as a mask over tangent columns
+// (min, max) order: the block stays symmetric bit for bit.  The columns of P_k are formed on the fly (rbd::point_column)
 __device__ __forceinline__ void obstacle_add_wave(const DevModel& m, const ObstacleWaveLds& S, const ObstacleCostDev& ob, unsigned active, int nu,
                                                   int tid, int nt, int n, double* gx, double* gxx) {
   const bool ff = m.ff != 0;
@@ -172,9 +138,9 @@ __device__ __forceinline__ void obstacle_add_wave(const DevModel& m, const Obsta
     const int i = S.idx[r];
     double s = 0.0;
     for (int k = 0; k < ob.np; ++k) {
-      if (!((active >> k) & 1) || !((vel_tangent_mask(ff, S.mask[ob.joint[k]]) >> i) & 1)) continue;
+      if (!((active >> k) & 1) || !((tangent_mask(ff, S.jw.mask[ob.joint[k]]) >> i) & 1)) continue;
       double c[3];
-      obstacle_column(m, ff, S, i, S.p[k], c);
+      point_column(m, ff, S.jw, i, S.p[k], c);
       s += c[0] * S.g[k][0] + c[1] * S.g[k][1] + c[2] * S.g[k][2];
     }
     gx[i] += s;
@@ -186,11 +152,11 @@ __device__ __forceinline__ void obstacle_add_wave(const DevModel& m, const Obsta
     bool hit = false;
     for (int k = 0; k < ob.np; ++k) {
       if (!((active >> k) & 1)) continue;
-      const unsigned long long tm = vel_tangent_mask(ff, S.mask[ob.joint[k]]);
+      const unsigned long long tm = tangent_mask(ff, S.jw.mask[ob.joint[k]]);
       if (!((tm >> i) & 1) || !((tm >> j) & 1)) continue;
       double cl[3], ch[3];
-      obstacle_column(m, ff, S, lo, S.p[k], cl);
-      obstacle_column(m, ff, S, hi, S.p[k], ch);
+      point_column(m, ff, S.jw, lo, S.p[k], cl);
+      point_column(m, ff, S.jw, hi, S.p[k], ch);
       const double* M = S.M[k];
       const double t0 = M[0] * ch[0] + M[1] * ch[1] + M[2] * ch[2];
       const double t1 = M[1] * ch[0] + M[3] * ch[1] + M[4] * ch[2];

@@ -4,7 +4,8 @@
     python tools/cost_terms_ab.py --compare A.npz B.npz               every entry np.array_equal(..., equal_nan=True), else exit 1
 
 The cases are those of tests/test_cost_terms_together.py (three models, batch 3, T = 4, n_alpha 1 / 3 / 8, all seven cost flags
-live; the zero-weight uploads of its upload rules), each term alone, and a list of refused calls with their return codes.  What
+live; the zero-weight uploads of its upload rules), each term alone, a list of refused calls with their return codes, the model
+entry points com and frame_velocity with their jacobians, and each term alone on the prismatic tree table7.  What
 is written: every derivative sequence linearise leaves, COSTS_OLD / COSTS_NEW, step, dcost, X_NEW, U_NEW, the clearances, what
 the getters hand back, and the return codes."""
 import argparse
@@ -16,6 +17,58 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def model_entry_points(capi, model, o, frames):
+    """com and frame_velocity with their jacobians at two states: the staging and column lanes of the CoM and frame-velocity
+    kernels on their own (ddp_hip_model_com, ddp_hip_model_frame_velocity)"""
+    out = {}
+    rng = np.random.default_rng(5)
+    with capi.ModelHandle(model) as h:
+        for k in range(2):
+            q, v = rng.normal(size=o.nq), rng.normal(size=o.nv)
+            if o.nq != o.nv:
+                q[3:7] /= np.linalg.norm(q[3:7])
+            out[f"com_c{k}"], out[f"com_J{k}"] = h.com(q, jacobian=True)
+            for f, (j, off) in enumerate(frames):
+                for key, val in zip(("vel", "Jq", "Jv"), h.frame_velocity(j, off, q, v, jacobian=True)):
+                    out[f"fv{k}_{f}_{key}"] = val
+    return out
+
+
+def table7(capi, tt, put):
+    """each term alone on the tree of tests/test_com_cost.py: joint 1 is prismatic and no leaf, joint 4 a prismatic leaf, so
+    the prismatic step sits in the middle of a walk (of the models above only tree38's root is prismatic).  Batch 3, T = 4:
+    linearise, both cost sequences, the clearances"""
+    B, T = 3, 4
+    cm, fc, fo, fv, ob, tc = tt.cm, tt.fc, tt.fo, tt.fv, tt.ob, tt.tc
+    model, spec, o = cm.make_any("table7", T, batch=B, fd_mode=2)
+    xs, us = tc._trajs(o, model, B, 61)
+    xs2, us2 = tc._trajs(o, model, B, 62)
+    mults, mu = tc._mults(o, xs[0], 63), np.ones(B)
+    frames, pts, kinds = fc.pick_frames(model, 3), ob.pick_points(model), ob.KINDS
+    t_fc, t_fo = fc.random_task(o, xs, frames, B, 64), fo.random_orient(o, xs, frames, B, 65)
+    t_cm, t_fv = cm.random_task(o, model, xs, B, 66), fv.random_task(o, xs, frames, B, 67)
+    t_ob = ob.random_task(o, pts, kinds, xs, B, 68)
+    alone = {"frame": (capi.FLAG_FRAME_COST, lambda x: x.set_frame_cost(frames=frames, target=t_fc[0], weight=t_fc[1])),
+             "orient": (capi.FLAG_FRAME_COST | capi.FLAG_FRAME_ORIENT_COST,
+                        lambda x: (x.set_frame_cost(frames=frames), x.set_frame_orient_cost(quat=t_fo[0], weight=t_fo[1]))),
+             "com": (capi.FLAG_COM_COST, lambda x: x.set_com_cost(target=t_cm[0], weight=t_cm[1])),
+             "vel": (capi.FLAG_FRAME_COST | capi.FLAG_FRAME_VEL_COST,
+                     lambda x: (x.set_frame_cost(frames=frames), x.set_frame_vel_cost(target=t_fv[0], weight=t_fv[1]))),
+             "obstacle": (capi.FLAG_OBSTACLE_COST, lambda x: ob.set_task(x, pts, kinds, t_ob[0], t_ob[1]))}
+    for term, (flags, upload) in alone.items():
+        with capi.Context(spec, flags=flags | capi.FLAG_NO_TENSORS) as ctx:
+            tc._setup(ctx, xs, us, mults, o.Etot)
+            upload(ctx)
+            ctx.linearize()
+            put(f"table7/alone/{term}", {s: ctx.download(s) for s in tt.DERIVS})
+            ctx.upload("X_NEW", xs2); ctx.upload("U_NEW", us2)
+            ctx.cost_seq_aug(0, mu); ctx.cost_seq_aug(1, mu)
+            put(f"table7/alone/{term}", {s: ctx.download(s) for s in ("COSTS_OLD", "COSTS_NEW")})
+            if term == "obstacle":
+                put(f"table7/alone/{term}", {"clear0": ctx.obstacle_clearance(0), "clear1": ctx.obstacle_clearance(1)})
+    put("table7/model", model_entry_points(capi, model, o, frames))
 
 
 def dump(path):
@@ -147,6 +200,8 @@ def dump(path):
             rc.append(fn(None, None, None, 0, 0))                                    # a null context
         rc.append(L.ddp_hip_state_limits_upload(None, None, None, None, 0, 0))
         out[f"{name}/return_codes"] = np.array(rc, dtype=np.int64)
+        put(f"{name}/model", model_entry_points(capi, c["model"], c["o"], c["frames"]))
+    table7(capi, tt, put)
     os.makedirs(path, exist_ok=True)
     np.savez(os.path.join(path, "cost_terms.npz"), **out)
     print(f"cost_terms_ab: {len(out)} entries under {os.path.basename(capi.LIB_PATH)} -> {os.path.join(path, 'cost_terms.npz')}")
