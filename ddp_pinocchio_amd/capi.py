@@ -30,8 +30,10 @@ FLAG_FRAME_ORIENT_COST = 64
 FLAG_COM_COST = 128
 FLAG_FRAME_VEL_COST = 256
 FLAG_OBSTACLE_COST = 512
+FLAG_SELF_COLLISION_COST = 1024
 MAX_COST_FRAMES = 4
 MAX_COLLISION_POINTS, MAX_OBSTACLES = 16, 8
+MAX_COLLISION_PAIRS = 32
 OBSTACLE_SPHERE, OBSTACLE_HALFSPACE = 0, 1
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
 
@@ -67,6 +69,8 @@ EXPORTS = [
     "ddp_hip_com_cost_upload", "ddp_hip_com_cost_download", "ddp_hip_model_com",
     "ddp_hip_frame_vel_upload", "ddp_hip_frame_vel_download", "ddp_hip_model_frame_velocity",
     "ddp_hip_obstacle_set_points", "ddp_hip_obstacle_upload", "ddp_hip_obstacle_download", "ddp_hip_obstacle_clearance",
+    "ddp_hip_self_collision_set_pairs", "ddp_hip_self_collision_upload", "ddp_hip_self_collision_download",
+    "ddp_hip_self_collision_clearance",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -169,6 +173,11 @@ def lib():
         L.ddp_hip_obstacle_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_obstacle_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_obstacle_clearance.argtypes = [C.c_void_p, C.c_int, _dp]
+    if hasattr(L, "ddp_hip_self_collision_upload"):  # (likewise: set_self_collision_pairs, set_self_collision_cost, self_collision_clearance)
+        L.ddp_hip_self_collision_set_pairs.argtypes = [C.c_void_p, C.c_int32, _ip, _dp, _dp, C.c_int32, _ip, _ip]
+        L.ddp_hip_self_collision_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_self_collision_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_self_collision_clearance.argtypes = [C.c_void_p, C.c_int, _dp]
     L.ddp_hip_rollout.argtypes = [C.c_void_p]
     L.ddp_hip_linearize.argtypes = [C.c_void_p]
     L.ddp_hip_linearize_stages.argtypes = [C.c_void_p, C.c_uint32]
@@ -391,6 +400,7 @@ class Context:
         self.batch = spec.batch
         self.n_cost_frames = 0
         self.n_obstacles = 0
+        self.n_collision_pairs = 0
 
     def close(self):
         if self._h:
@@ -608,6 +618,50 @@ class Context:
         X_NEW (which = 1); +inf where no slot is live, negative where the robot penetrates"""
         out = np.zeros((self.batch, self.spec.T + 1))
         _check(lib().ddp_hip_obstacle_clearance(self._h, int(which), _ptr(out)), "obstacle_clearance")
+        return out
+
+    def set_self_collision_pairs(self, points, pairs):
+        """The spheres [(joint, off, radius), ...] (2 .. MAX_COLLISION_POINTS of them) and the pairs [(a, b), ...] of sphere indices
+        (up to MAX_COLLISION_PAIRS, the two spheres of a pair on different joints) of a context created with
+        FLAG_SELF_COLLISION_COST (ddp_hip.h), shared by the batch.  With the same pair list as before the per-instance data stays
+        (points may move, radii may change), else margins and weights are reset to 0"""
+        points, pairs = list(points), list(pairs)
+        if any(len(p) != 3 for p in points) or any(len(p) != 2 for p in pairs):
+            raise ValueError("set_self_collision_pairs: every point is (joint, (x, y, z), radius), every pair (a, b)")
+        joint = np.ascontiguousarray([int(p[0]) for p in points], dtype=np.int32)
+        off = np.ascontiguousarray([p[1] for p in points], dtype=np.float64).reshape(-1)
+        radius = np.ascontiguousarray([p[2] for p in points], dtype=np.float64)
+        if off.size != 3 * len(joint) or radius.shape != (len(joint),):
+            raise ValueError("set_self_collision_pairs: every point is (joint, (x, y, z), radius)")
+        pa = np.ascontiguousarray([int(p[0]) for p in pairs], dtype=np.int32)
+        pb = np.ascontiguousarray([int(p[1]) for p in pairs], dtype=np.int32)
+        _check(lib().ddp_hip_self_collision_set_pairs(self._h, len(joint), joint.ctypes.data_as(_ip), _ptr(off), _ptr(radius), len(pa),
+                                                      pa.ctypes.data_as(_ip), pb.ctypes.data_as(_ip)), "self_collision_set_pairs")
+        self.n_collision_pairs = len(pa)
+
+    def set_self_collision_cost(self, margin=None, weight=None, first=0, count=None):
+        """The self-collision terms of instances first .. first + count - 1 (a context created with FLAG_SELF_COLLISION_COST;
+        ddp_hip.h), of the n_pairs pairs of set_self_collision_pairs.  margin: finite, may be negative; weight: >= 0; each as
+        (n_pairs,) for every instance and t, (T+1, n_pairs) for every instance or (count, T+1, n_pairs).  None leaves that side
+        as it is.  The pair count is the one this object last passed to set_self_collision_pairs; before that call there is no
+        shape to check against and the call raises ValueError."""
+        T1, npair = self.spec.T + 1, getattr(self, "n_collision_pairs", 0)
+        if not npair:
+            raise ValueError("set_self_collision_cost: no pairs yet, call set_self_collision_pairs first")
+        count, arrs = self._cost_sides("set_self_collision_cost", (("margin", margin, (T1, npair), ((npair,),)),
+                                                                   ("weight", weight, (T1, npair), ((npair,),))), first, count)
+        self._cost_upload(lib().ddp_hip_self_collision_upload, "self_collision_upload", arrs, first, count)
+
+    def self_collision_cost(self, first=0, count=None):
+        """(margin, weight) of instances first .. first + count - 1, each (count, T+1, n_pairs)"""
+        T1, npair = self.spec.T + 1, getattr(self, "n_collision_pairs", 0)      # (0 before set_self_collision_pairs: empty arrays)
+        return self._cost_download(lib().ddp_hip_self_collision_download, "self_collision_download", ((T1, npair), (T1, npair)), first, count)
+
+    def self_collision_clearance(self, which=0):
+        """(batch, T+1): the least signed distance d_i of a pair of non-zero weight along X (which = 0) or X_NEW (which = 1);
+        +inf where no pair is live, negative where two spheres are closer than their radii and margin allow"""
+        out = np.zeros((self.batch, self.spec.T + 1))
+        _check(lib().ddp_hip_self_collision_clearance(self._h, int(which), _ptr(out)), "self_collision_clearance")
         return out
 
     def set_state_limits(self, lo=None, hi=None, weight=None, first=0, count=None):

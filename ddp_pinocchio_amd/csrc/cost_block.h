@@ -9,8 +9,8 @@
 #include "ddp_hip/ddp_hip.h"
 
 // The terms, in the order the kernels add them (after the stage cost and the tracking cost): lin.hip launches one kernel per
-// live term in this order, fwd.hip forms the first three inline and the last three in kernels of their own, in this order
-enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_LIMITS, COST_COM, COST_FRAME_VEL, COST_OBSTACLE, COST_COUNT };
+// live term in this order, fwd.hip forms the first three inline and the others in kernels of their own, in this order
+enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_LIMITS, COST_COM, COST_FRAME_VEL, COST_OBSTACLE, COST_SELF_COLLISION, COST_COUNT };
 
 enum CostFill : int32_t { FILL_ZERO, FILL_NEG_INF, FILL_POS_INF, FILL_QUAT };   // FILL_QUAT: identity quaternions (0, 0, 0, 1)
 
@@ -35,6 +35,7 @@ static const CostDesc kCostDesc[COST_COUNT] = {
     {DDP_HIP_FLAG_COM_COST, 2, {3, 3, 0}, {FILL_ZERO, FILL_ZERO, 0}, 1, true, true},                                    // target | weight
     {DDP_HIP_FLAG_FRAME_VEL_COST, 2, {6, 6, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, true},       // target | weight, per frame
     {DDP_HIP_FLAG_OBSTACLE_COST, 2, {4, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_OBSTACLES, false, true},          // geom | weight, per slot
+    {DDP_HIP_FLAG_SELF_COLLISION_COST, 2, {1, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COLLISION_PAIRS, false, true},   // margin | weight, per pair
 };
 
 // One term of one context
@@ -106,6 +107,16 @@ static inline bool cost_limit_weight_side(const CostCheck& c, const double* v, i
   for (int64_t i = 0; i < words; ++i) {
     if (!cost_weight_ok(v[i])) return false;
     if (c.ff && i % c.items < 6 && v[i] != 0.0) return false;
+  }
+  return true;
+}
+
+// a self-collision pair list over n_points spheres (sphere k on joint[k]): indices in range, a != b, and not both spheres on one
+// joint (their distance is constant).  Duplicate pairs are allowed
+static inline bool cost_pair_list_ok(int32_t n_points, const int32_t* joint, int32_t n_pairs, const int32_t* a, const int32_t* b) {
+  for (int32_t i = 0; i < n_pairs; ++i) {
+    if (a[i] < 0 || a[i] >= n_points || b[i] < 0 || b[i] >= n_points) return false;
+    if (a[i] == b[i] || joint[a[i]] == joint[b[i]]) return false;
   }
   return true;
 }

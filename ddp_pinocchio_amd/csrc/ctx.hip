@@ -249,6 +249,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   if ((flags & DDP_HIP_FLAG_FRAME_ORIENT_COST) && !(flags & DDP_HIP_FLAG_FRAME_COST)) return DDP_HIP_E_ARG;   // the orientation terms are of the cost frames
   if ((flags & DDP_HIP_FLAG_FRAME_VEL_COST) && !(flags & DDP_HIP_FLAG_FRAME_COST)) return DDP_HIP_E_ARG;   // the velocity terms alike
   if ((flags & DDP_HIP_FLAG_OBSTACLE_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // collision points are points of a tree's joints
+  if ((flags & DDP_HIP_FLAG_SELF_COLLISION_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the spheres alike
   if (flags & DDP_HIP_FLAG_COM_COST) {
     if (mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the CoM is of a tree's bodies
     if (!mo.mass_j || !mo.jtype) return DDP_HIP_E_ARG;
@@ -357,7 +358,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipStreamSynchronize(ctx->stream));
   }
   for (int term = 0; term < COST_COUNT; ++term) {
-    // frames and obstacle slots: no layout until they are set; limits (lo = -inf, hi = +inf, w = 0: no limit anywhere) and CoM: fixed
+    // frames, obstacle slots and self-collision pairs: no layout until they are set; limits (lo = -inf, hi = +inf, w = 0: no limit anywhere) and CoM: fixed
     CostBlock& k = ctx->cost[term];
     k.desc = &kCostDesc[term];
     k.max_items = k.desc->max_items ? k.desc->max_items : (int32_t)d.n;
@@ -366,6 +367,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     if (rc_ != DDP_HIP_OK) { ddp_hip_destroy(ctx); return rc_; }
   }
   if (flags & DDP_HIP_FLAG_OBSTACLE_COST) CTX_TRY(hipMalloc(&ctx->ob_clear_d, sizeof(double) * (size_t)(d.batch * (d.T + 1))));
+  if (flags & DDP_HIP_FLAG_SELF_COLLISION_COST) CTX_TRY(hipMalloc(&ctx->sc_clear_d, sizeof(double) * (size_t)(d.batch * (d.T + 1))));
   int rc = bwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = fwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = lin_setup(ctx);
@@ -391,6 +393,7 @@ extern "C" int ddp_hip_destroy(ddp_hip_ctx* ctx) {
     if (k.cand) (void)hipFree(k.cand);
   }
   if (ctx->ob_clear_d) (void)hipFree(ctx->ob_clear_d);
+  if (ctx->sc_clear_d) (void)hipFree(ctx->sc_clear_d);
   if (ctx->ne_d) (void)hipFree(ctx->ne_d);
   if (ctx->Epre_d) (void)hipFree(ctx->Epre_d);
   if (ctx->target_d) (void)hipFree(ctx->target_d);
@@ -653,6 +656,49 @@ extern "C" int ddp_hip_obstacle_upload(ddp_hip_ctx* ctx, const double* geom, con
 extern "C" int ddp_hip_obstacle_download(ddp_hip_ctx* ctx, double* geom, double* weight, int64_t first, int64_t count) {
   double* host[] = {geom, weight};
   return cost_block_download(ctx, COST_OBSTACLE, host, first, count);
+}
+
+// spheres and pairs shared by the batch; a margin and a weight per (instance, t, pair)
+extern "C" int ddp_hip_self_collision_set_pairs(ddp_hip_ctx* ctx, int32_t n_points, const int32_t* joint, const double* off, const double* radius,
+                                                int32_t n_pairs, const int32_t* pair_a, const int32_t* pair_b) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_SELF_COLLISION_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (n_points < 2 || n_points > DDP_HIP_MAX_COLLISION_POINTS || n_pairs < 1 || n_pairs > DDP_HIP_MAX_COLLISION_PAIRS) return DDP_HIP_E_ARG;
+  if (!joint || !off || !radius || !pair_a || !pair_b) return DDP_HIP_E_ARG;
+  for (int k = 0; k < n_points; ++k) {
+    if (joint[k] < 0 || joint[k] >= ctx->model_h.nj) return DDP_HIP_E_ARG;
+    for (int a = 0; a < 3; ++a)
+      if (!isfinite(off[3 * k + a])) return DDP_HIP_E_ARG;
+    if (!isfinite(radius[k]) || radius[k] < 0.0) return DDP_HIP_E_ARG;
+  }
+  if (!cost_pair_list_ok(n_points, joint, n_pairs, pair_a, pair_b)) return DDP_HIP_E_ARG;
+  bool same = n_pairs == ctx->sc_npair;
+  for (int i = 0; same && i < n_pairs; ++i) same = pair_a[i] == ctx->sc_pa[i] && pair_b[i] == ctx->sc_pb[i];
+  if (!same) {
+    // another list is another meaning of the per-pair data: margins and weights start again at 0
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int rc_ = cost_block_setup(ctx, COST_SELF_COLLISION, n_pairs);
+    if (rc_ != DDP_HIP_OK) return rc_;
+  }
+  ctx->sc_np = n_points;
+  ctx->sc_npair = n_pairs;
+  for (int k = 0; k < n_points; ++k) {
+    ctx->sc_joint[k] = joint[k];
+    ctx->sc_radius[k] = radius[k];
+    for (int a = 0; a < 3; ++a) ctx->sc_off[k][a] = off[3 * k + a];
+  }
+  for (int i = 0; i < n_pairs; ++i) { ctx->sc_pa[i] = pair_a[i]; ctx->sc_pb[i] = pair_b[i]; }
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_self_collision_upload(ddp_hip_ctx* ctx, const double* margin, const double* weight, int64_t first, int64_t count) {
+  const double* host[] = {margin, weight};
+  const CostSideOk ok[] = {cost_finite_side, cost_weight_side};
+  return cost_block_upload(ctx, COST_SELF_COLLISION, host, ok, first, count);
+}
+extern "C" int ddp_hip_self_collision_download(ddp_hip_ctx* ctx, double* margin, double* weight, int64_t first, int64_t count) {
+  double* host[] = {margin, weight};
+  return cost_block_download(ctx, COST_SELF_COLLISION, host, first, count);
 }
 
 extern "C" int ddp_hip_com_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first, int64_t count) {

@@ -17,6 +17,7 @@
 #include "internal.h"
 #include "obstacle_cost.h"
 #include "rbd.h"
+#include "self_collision_cost.h"
 #include "state_limits.h"
 
 namespace {
@@ -982,6 +983,75 @@ __global__ __launch_bounds__(64) void obstacle_clearance_kernel(ObstacleCostDev 
   });
 }
 
+// The self-collision kernels below need two steps per state, so they do not fit pair_lanes_fold: DDP_HIP_MAX_COLLISION_POINTS lanes
+// per pair of the list (a state), 4 states per wave.  Step 1: lane k < n_points of the group walks sphere k (rbd::frame_point) and
+// leaves p_k in LDS (s_p: 64 x 3, the kernel's own).  After a barrier, step 2: the lanes take the collision pairs, lane k pair k,
+// k + 16, ... (more than one per lane once n_pairs exceeds the group width), and leave w d^2 of an active pair -- with MIN: d of a
+// pair with w != 0 -- and a flag in LDS (s_term, s_formed: 4 x DDP_HIP_MAX_COLLISION_PAIRS each).  After a second barrier the
+// group's first lane folds in ascending pair order: 1/2 the sum of the formed ones, or with MIN the rbd::obstacle_min of them all
+// from +inf, and cost_pair_store writes the result.  A state whose weights are all 0 is not walked
+template <bool MIN>
+__device__ __forceinline__ void self_collision_fold(const SelfCollisionDev& sc, const DevModel& m, double (*s_p)[3], double* s_term,
+                                                    int32_t* s_formed, const double* xs, int64_t traj_stride, int64_t count, int32_t T1,
+                                                    int32_t nx, int32_t na, const int32_t* state, int32_t round, double* out, int32_t add) {
+  constexpr int L = DDP_HIP_MAX_COLLISION_POINTS, NP = DDP_HIP_MAX_COLLISION_PAIRS;
+  const int tid = threadIdx.x, g = tid / L, k = tid % L;
+  const int64_t e = (int64_t)blockIdx.x * (64 / L) + g;
+  const CostPair pr = cost_pair_decode(e, count, T1, na, state, round);
+  const double* w = sc.weight + pr.bt1 * sc.npair;
+  const bool live = pr.live && rbd::weights_any(w, sc.npair);
+  if (live && k < sc.np) {
+    const double off[3] = {sc.off[k][0], sc.off[k][1], sc.off[k][2]};
+    rbd::frame_point(m, m.ff != 0, sc.joint[k], off, xs + pr.traj * traj_stride + (int64_t)pr.t * nx, s_p[tid]);
+  }
+  __syncthreads();
+  for (int i = k; i < NP; i += L) {
+    double term = MIN ? INFINITY : 0.0;
+    bool formed = false;
+    if (live && i < sc.npair && w[i] != 0.0) {
+      double d;
+      (void)rbd::self_collision_distance(sc, i, s_p[g * L + sc.pa[i]], s_p[g * L + sc.pb[i]], sc.margin[pr.bt1 * sc.npair + i], &d, nullptr);
+      if (MIN) { term = d; formed = true; }
+      else if (rbd::obstacle_active(d)) { term = w[i] * d * d; formed = true; }
+    }
+    s_term[g * NP + i] = term;
+    s_formed[g * NP + i] = formed ? 1 : 0;
+  }
+  __syncthreads();
+  if (k != 0 || pr.skip) return;
+  double acc = MIN ? INFINITY : 0.0;
+  bool any = false;
+  for (int i = 0; i < sc.npair; ++i) {
+    if (!s_formed[g * NP + i]) continue;
+    acc = MIN ? rbd::obstacle_min(acc, s_term[g * NP + i]) : acc + s_term[g * NP + i];
+    any = true;
+  }
+  cost_pair_store(out, e, MIN ? acc : 0.5 * acc, any, add);
+}
+
+// The self-collision terms (DDP_HIP_FLAG_SELF_COLLISION_COST, ddp_hip.h) of a list of states, added on top like the obstacle terms
+// above: the same list, the same two uses (add != 0: out[pair] += term behind cost_kernel; add == 0: out[pair] = term, the
+// candidates' array in a line-search round, with the candidates the rollout kernels skip skipped here).  A pair of spheres with
+// w == 0 or e == 0 is left out, and a state without an active pair adds nothing (add != 0) or stores +0 (add == 0).  A non-finite
+// state gives a NaN term, as com_cost_kernel's does
+__global__ __launch_bounds__(64) void self_collision_cost_kernel(SelfCollisionDev sc, const DevModel* model, const double* xs, int64_t traj_stride,
+                                                                 int64_t count, int32_t T1, int32_t nx, int32_t na, const int32_t* state,
+                                                                 int32_t round, double* out, int32_t add) {
+  __shared__ double s_p[64][3], s_term[4 * DDP_HIP_MAX_COLLISION_PAIRS];
+  __shared__ int32_t s_act[4 * DDP_HIP_MAX_COLLISION_PAIRS];
+  self_collision_fold<false>(sc, *model, s_p, s_term, s_act, xs, traj_stride, count, T1, nx, na, state, round, out, add);
+}
+
+// ddp_hip_self_collision_clearance: the same layout over the `count` (instance, t) pairs of one resident trajectory (a list of
+// one-state trajectories, no candidates to skip), min instead of sum: out[pair] = min over the pairs of spheres with w != 0 of d_i,
+// +inf where none is live, NaN where a distance is NaN
+__global__ __launch_bounds__(64) void self_collision_clearance_kernel(SelfCollisionDev sc, const DevModel* model, const double* xs, int64_t count,
+                                                                      int32_t nx, double* out) {
+  __shared__ double s_p[64][3], s_min[4 * DDP_HIP_MAX_COLLISION_PAIRS];
+  __shared__ int32_t s_live[4 * DDP_HIP_MAX_COLLISION_PAIRS];
+  self_collision_fold<true>(sc, *model, s_p, s_min, s_live, xs, nx, count, 1, nx, 1, nullptr, 0, out, 0);
+}
+
 // accept rule (ddp_fwd.ipp:56-60): the first (= largest) candidate with sum(new - old) <= 0; the winner's
 // trajectory becomes (X_NEW, U_NEW).  grid = batch.
 __global__ void select_kernel(FwdParams p) {
@@ -1213,14 +1283,20 @@ static void launch_frame_vel_cost(ddp_hip_ctx* ctx, const double* xs, int na, in
 static void launch_obstacle_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   launch_add_on(obstacle_cost_kernel, obstacle_cost_dev(ctx), DDP_HIP_MAX_COLLISION_POINTS, ctx, xs, na, count, state, round, out, add);
 }
+static void launch_self_collision_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
+  launch_add_on(self_collision_cost_kernel, self_collision_dev(ctx), DDP_HIP_MAX_COLLISION_POINTS, ctx, xs, na, count, state, round, out, add);
+}
 
 // The terms formed out of line, in the fixed order of their additions (after everything cost_kernel / the rollout kernels form
-// inline): CoM, frame velocities, obstacles.  launch_cost and ddp_hip_forward both walk this table and nothing else
+// inline): CoM, frame velocities, obstacles, self-collision.  launch_cost and ddp_hip_forward both walk this table and nothing else
 struct AddOnTerm {
   int term;
   AddOnLaunch launch;
 };
-static const AddOnTerm kAddOn[] = {{COST_COM, launch_com_cost}, {COST_FRAME_VEL, launch_frame_vel_cost}, {COST_OBSTACLE, launch_obstacle_cost}};
+static const AddOnTerm kAddOn[] = {{COST_COM, launch_com_cost},
+                                   {COST_FRAME_VEL, launch_frame_vel_cost},
+                                   {COST_OBSTACLE, launch_obstacle_cost},
+                                   {COST_SELF_COLLISION, launch_self_collision_cost}};
 
 static int launch_cost(ddp_hip_ctx* ctx, FwdParams& p, int which) {
   const int bs = 64;
@@ -1261,6 +1337,23 @@ extern "C" int ddp_hip_obstacle_clearance(ddp_hip_ctx* ctx, int which, double* o
                      which == 0 ? p.x_old : p.x_new, total, (int32_t)ctx->d.nx, ctx->ob_clear_d);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, ctx->ob_clear_d, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_self_collision_clearance(ddp_hip_ctx* ctx, int which, double* out) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_SELF_COLLISION_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (!out || (which != 0 && which != 1) || ctx->sc_npair == 0) return DDP_HIP_E_ARG;   // (no pairs set: nothing to measure)
+  HIP_TRY(hipSetDevice(ctx->device));
+  const FwdParams p = make_params(ctx);
+  const SelfCollisionDev sc = self_collision_dev(ctx, true);
+  const int64_t total = ctx->d.batch * (ctx->d.T + 1);
+  const int64_t per = 64 / DDP_HIP_MAX_COLLISION_POINTS;
+  hipLaunchKernelGGL(self_collision_clearance_kernel, dim3((unsigned)((total + per - 1) / per)), dim3(64), 0, ctx->stream, sc, ctx->model_d,
+                     which == 0 ? p.x_old : p.x_new, total, (int32_t)ctx->d.nx, ctx->sc_clear_d);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, ctx->sc_clear_d, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return DDP_HIP_OK;
 }

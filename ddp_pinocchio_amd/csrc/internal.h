@@ -280,6 +280,13 @@ struct ddp_hip_ctx {
   double ob_radius[DDP_HIP_MAX_COLLISION_POINTS] = {};
   int32_t ob_kind[DDP_HIP_MAX_OBSTACLES] = {};
   double* ob_clear_d = nullptr;               // [batch][T+1] what ddp_hip_obstacle_clearance hands back
+  // the self-collision spheres and the pairs of them (ddp_hip_self_collision_set_pairs)
+  int32_t sc_np = 0, sc_npair = 0;            // spheres and pairs set (0: none yet)
+  int32_t sc_joint[DDP_HIP_MAX_COLLISION_POINTS] = {};
+  double sc_off[DDP_HIP_MAX_COLLISION_POINTS][3] = {};
+  double sc_radius[DDP_HIP_MAX_COLLISION_POINTS] = {};
+  int32_t sc_pa[DDP_HIP_MAX_COLLISION_PAIRS] = {}, sc_pb[DDP_HIP_MAX_COLLISION_PAIRS] = {};
+  double* sc_clear_d = nullptr;               // [batch][T+1] what ddp_hip_self_collision_clearance hands back
 
   bool box_dirty = false;       // CTRL_LO / CTRL_HI were uploaded since lo <= hi was last checked (ctx.hip: box_check)
 

@@ -21,6 +21,7 @@
 #include "obstacle_cost.h"
 #include "rbd.h"
 #include "rbd_deriv.h"
+#include "self_collision_cost.h"
 #include "state_limits.h"
 
 namespace {
@@ -396,6 +397,70 @@ __global__ __launch_bounds__(64) void lin_obstacle_cost_kernel(LinParams p, Obst
   __syncthreads();
   double *gx = blk.gx, *gxx = blk.gxx;
   rbd::obstacle_add_wave(m, S, ob, active, __builtin_popcountll(U), tid, (int)blockDim.x, n, gx, gxx);
+}
+
+// Self-collision cost (DDP_HIP_FLAG_SELF_COLLISION_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost
+// kernel on the same stream (the fixed order of additions: ..., frame velocities, obstacles, self-collision).  One-sided like the
+// obstacle cost: most waves have nothing to add.  A block whose weights are all 0 returns at once.  Phase 1: lane k < n_points
+// walks sphere k (rbd::frame_point); lane i < n_pairs fetches p_a and p_b from the lanes that hold them (cross-lane reads: no
+// LDS) and forms d_i.  One wave-level vote decides: a wave without an active pair (w != 0, e != 0, a direction u) returns here,
+// before any LDS access or barrier.  Phase 2: lanes j < nj stage world axis, world origin and path of their joint in LDS
+// (rbd::stage_joint_lane), lanes k < n_points their p_k, the active pairs' lanes u_i, w_i, w_i e_i; after the barrier the same
+// lanes leave the two halves of their pair's symmetric difference, path(a) \ path(b) and path(b) \ path(a), as column masks.  A
+// joint on both paths moves both spheres alike and is in neither: the wave adds over the union of the symmetric differences alone
+//   lx[c] += sum_i (w e)_i z_i[c],     lxx[r][c] += sum_i w_i z_i[min] z_i[max]     (Gauss-Newton)
+// (rbd::self_collision_add_wave: pairs in ascending order, z formed on the fly, symmetric bit for bit).  It reads p.x and touches
+// nothing but those entries.  No atomics.  t = T: lfx / lfxx
+__global__ __launch_bounds__(64) void lin_self_collision_cost_kernel(LinParams p, SelfCollisionDev sc) {
+  const int64_t bt1 = blockIdx.x;
+  const int n = (int)p.d.n;
+  const int tid = threadIdx.x;
+  const double* w = sc.weight + bt1 * sc.npair;
+  if (!rbd::weights_any(w, sc.npair)) return;
+  const DevModel& m = *p.model;
+  const bool ff = m.ff != 0;
+  const LinCostBlock blk = lin_cost_block(p, bt1);
+  const double* q = blk.q;
+  double pk[3] = {0.0, 0.0, 0.0};
+  if (tid < sc.np) {
+    const double off[3] = {sc.off[tid][0], sc.off[tid][1], sc.off[tid][2]};
+    rbd::frame_point(m, ff, sc.joint[tid], off, q, pk);
+  }
+  const bool pair_lane = tid < sc.npair;
+  const int ia = pair_lane ? sc.pa[tid] : 0, ib = pair_lane ? sc.pb[tid] : 0;
+  const double pa[3] = {__shfl(pk[0], ia), __shfl(pk[1], ia), __shfl(pk[2], ia)};
+  const double pb[3] = {__shfl(pk[0], ib), __shfl(pk[1], ib), __shfl(pk[2], ib)};
+  double d = 0.0, u[3] = {0.0, 0.0, 0.0}, wi = 0.0;
+  bool act = false;
+  if (pair_lane) {
+    wi = w[tid];
+    if (wi != 0.0) {
+      const bool has_u = rbd::self_collision_distance(sc, tid, pa, pb, sc.margin[bt1 * sc.npair + tid], &d, u);
+      act = rbd::obstacle_active(d) && has_u;
+    }
+  }
+  const unsigned active = (unsigned)__ballot(act);                  // bit i: pair i is active
+  if (active == 0) return;
+  __shared__ rbd::SelfCollisionWaveLds S;
+  if (tid < m.nj) rbd::stage_joint_lane<0>(m, q, tid, S.jw, nullptr);
+  if (tid < sc.np) { S.p[tid][0] = pk[0]; S.p[tid][1] = pk[1]; S.p[tid][2] = pk[2]; }
+  if (act) {
+    S.u[tid][0] = u[0]; S.u[tid][1] = u[1]; S.u[tid][2] = u[2];
+    S.w[tid] = wi;
+    S.we[tid] = wi * d;
+  }
+  __syncthreads();
+  unsigned long long U = 0;
+  for (int i = 0; i < sc.npair; ++i) {
+    if (!((active >> i) & 1)) continue;
+    const unsigned long long ma = rbd::tangent_mask(ff, S.jw.mask[sc.joint[sc.pa[i]]]), mb = rbd::tangent_mask(ff, S.jw.mask[sc.joint[sc.pb[i]]]);
+    U |= ma ^ mb;
+    if (i == tid) { S.ca[i] = ma & ~mb; S.cb[i] = mb & ~ma; }
+  }
+  rbd::column_index_lane(U, tid, S.idx);
+  __syncthreads();
+  double *gx = blk.gx, *gxx = blk.gxx;
+  rbd::self_collision_add_wave(m, S, sc, active, __builtin_popcountll(U), tid, (int)blockDim.x, n, gx, gxx);
 }
 
 template <int NJ>
@@ -1235,13 +1300,14 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
       hipLaunchKernelGGL(lin_track_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p);
     else hipLaunchKernelGGL(lin_cost_kernel, dim3((unsigned)BT), dim3(64), 0, ctx->stream, p);
     // the add-on terms, one kernel per live term, each adding onto what the ones before it left.  The fixed order of additions:
-    // cost, tracking, frame positions, frame orientations, limits, CoM, frame velocities, obstacles
+    // cost, tracking, frame positions, frame orientations, limits, CoM, frame velocities, obstacles, self-collision
     const dim3 blocks((unsigned)(BT + d.batch));
     const FrameCostDev fc = frame_cost_dev(ctx);
     const StateLimitsDev sl = state_limits_dev(ctx);
     const CoMCostDev cm = com_cost_dev(ctx);
     const FrameVelCostDev fv = frame_vel_cost_dev(ctx);
     const ObstacleCostDev ob = obstacle_cost_dev(ctx);
+    const SelfCollisionDev sc = self_collision_dev(ctx);
     auto add = [&](bool live, auto kernel, const auto& dev) { if (live) hipLaunchKernelGGL(kernel, blocks, dim3(64), 0, ctx->stream, p, dev); };
     add(fc.target, lin_frame_cost_kernel, fc);
     add(fc.oquat, lin_frame_orient_cost_kernel, fc);
@@ -1249,6 +1315,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     add(cm.target, lin_com_cost_kernel, cm);
     add(fv.target, lin_frame_vel_cost_kernel, fv);
     add(ob.geom, lin_obstacle_cost_kernel, ob);
+    add(sc.margin, lin_self_collision_cost_kernel, sc);
   }
   // the q- / v-caches of the mode-2 stencil also serve the first order (base configuration and base (q, v)), so they are built
   // ahead of whichever stage comes first

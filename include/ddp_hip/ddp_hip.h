@@ -293,6 +293,38 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
 #define DDP_HIP_MAX_OBSTACLES 8
 #define DDP_HIP_OBSTACLE_SPHERE 0
 #define DDP_HIP_OBSTACLE_HALFSPACE 1
+/* Say "do not run one part of the robot through another": pairs of spheres on the robot, a one-sided soft cost on their distance
+ * -- "the hand stays out of the torso", "the knees do not cross".  Both ends of a pair move with q, which the obstacle flag cannot
+ * express.  The flag stands alone: it needs no DDP_HIP_FLAG_OBSTACLE_COST and has its own spheres.  Spheres, shared by the batch,
+ * up to DDP_HIP_MAX_COLLISION_POINTS: sphere k is the point off_k fixed in joint joint_k (the convention of the cost frames and
+ * of the obstacle flag's collision points) with a radius r_k >= 0; p_k(q) is its world position.  Pairs, shared by the batch, up
+ * to DDP_HIP_MAX_COLLISION_PAIRS: pair i = (a_i, b_i) of sphere indices, the two on different joints.  Per instance b, t = 0 .. T
+ * and pair i a margin m[b][t][i] (finite, may be negative) and a weight w[b][t][i] >= 0:
+ *   D_i = |p_a - p_b|,   d_i = D_i - (r_a + r_b + m_i),   u_i = (p_a - p_b) / D_i
+ *   e_i = d_i < 0 ? d_i : 0          (a NaN distance is active and its term NaN)
+ *   l(t, x, u) += 1/2 sum_i w[b][t][i] e_i^2      t < T
+ *   lf(x_T)    += 1/2 sum_i w[b][T][i] e_i^2
+ * to whatever the context optimises otherwise.  Derivatives in the tangent at x, over the pairs with w != 0, e != 0 and D_i != 0
+ * only, with P_k the true point jacobian of DDP_HIP_FLAG_FRAME_COST:
+ *   z_i[c] = + P_a[:, c] . u_i     c a tangent column of path(a_i) that is not on path(b_i)
+ *   z_i[c] = - P_b[:, c] . u_i     c a tangent column of path(b_i) that is not on path(a_i)
+ *            nothing                c on both paths or on neither
+ *   lx[q rows] += sum_i w e_i z_i,   lxx[q rows, q rows] += sum_i w z_i z_i^T,   lfx / lfxx alike at T.
+ * The distance of two points does not change when a common ancestor joint moves: for a column on both paths the two
+ * contributions cancel (a revolute joint: a x (p_a - p_b) is perpendicular to u; a prismatic one: a - a = 0; a free-flyer root:
+ * the same in its six columns), and such a column is left out, not added as rounding residue.  The term therefore touches the
+ * symmetric difference of the two paths only; velocity rows and columns, lu, luu, lux, every q row outside the symmetric
+ * differences of the active pairs and a free-flyer root's six rows are untouched.  lxx is Gauss-Newton (the term w e grad^2 d is
+ * dropped: positive semidefinite); entry (r, c) is formed in (min, max) order with the pairs in ascending order: symmetric bit
+ * for bit, no atomics.  A pair with D_i == 0 contributes its value 1/2 w (r_a + r_b + m)^2 and no derivative.  A pair with
+ * w == 0 or e == 0 is left out (not multiplied by 0, not added as +0): with nothing uploaded, with every weight 0, and with
+ * non-zero weights on pairs that neither the trajectory nor any line-search candidate brings within their margin, a context
+ * computes bit for bit what it computes without the flag.  The data travels through ddp_hip_self_collision_* below; at create no
+ * pairs are set and margins and weights are 0.  Tree models only (the pendulum: DDP_HIP_E_UNSUPPORTED).  The flag combines with
+ * every other flag: the terms are formed by kernels of their own, which add onto what the other terms' kernels leave (last,
+ * after the obstacles'). */
+#define DDP_HIP_FLAG_SELF_COLLISION_COST 1024u
+#define DDP_HIP_MAX_COLLISION_PAIRS 32
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -372,6 +404,24 @@ int ddp_hip_obstacle_download(ddp_hip_ctx* ctx, double* geom, double* weight, in
  * w != 0 of d_ko along X (which = 0) or X_NEW (which = 1), +inf where no slot is live.  From the first
  * ddp_hip_obstacle_set_points on (before: DDP_HIP_E_ARG), live weights or not. */
 int ddp_hip_obstacle_clearance(ddp_hip_ctx* ctx, int which, double* out);
+/* The spheres and the pairs of a context created with DDP_HIP_FLAG_SELF_COLLISION_COST (else DDP_HIP_E_UNSUPPORTED), shared by the
+ * batch: joint[n_points], off[n_points][3], radius[n_points], pair_a[n_pairs], pair_b[n_pairs].  DDP_HIP_E_ARG for n_points
+ * outside 2 .. DDP_HIP_MAX_COLLISION_POINTS, n_pairs outside 1 .. DDP_HIP_MAX_COLLISION_PAIRS, a joint outside the model, a
+ * non-finite offset, a negative or non-finite radius, a sphere index outside the points, a == b, and both spheres of a pair on
+ * the same joint (their distance is constant).  Duplicate pairs are allowed.  It may be called again: with the same pair count
+ * and the same (a, b) list the per-instance data stays (points may move, radii may change), otherwise margins and weights are
+ * reset to 0. */
+int ddp_hip_self_collision_set_pairs(ddp_hip_ctx* ctx, int32_t n_points, const int32_t* joint, const double* off, const double* radius,
+                                     int32_t n_pairs, const int32_t* pair_a, const int32_t* pair_b);
+/* The pairs' margins and weights, stream-ordered like ddp_hip_obstacle_upload.  Host arrays [n_instances][T+1][n_pairs] each; a
+ * NULL pointer leaves that side as it is.  An upload is refused as a whole (DDP_HIP_E_ARG, nothing written) before
+ * ddp_hip_self_collision_set_pairs, for a bad instance range, a non-finite margin and a negative or non-finite weight. */
+int ddp_hip_self_collision_upload(ddp_hip_ctx* ctx, const double* margin, const double* weight, int64_t first_instance, int64_t n_instances);
+int ddp_hip_self_collision_download(ddp_hip_ctx* ctx, double* margin, double* weight, int64_t first_instance, int64_t n_instances);
+/* "Did the result fold into itself, where, by how much": out[batch][T+1] (host) = min over the pairs with w != 0 of d_i along X
+ * (which = 0) or X_NEW (which = 1), +inf where no pair is live, NaN where a distance is.  From the first
+ * ddp_hip_self_collision_set_pairs on (before: DDP_HIP_E_ARG), live weights or not. */
+int ddp_hip_self_collision_clearance(ddp_hip_ctx* ctx, int which, double* out);
 
 /* make_trajectory (ddp.hpp:392-415): X[0] and U given -> X[1..T] */
 int ddp_hip_rollout(ddp_hip_ctx* ctx);
