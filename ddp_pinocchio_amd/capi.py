@@ -31,6 +31,7 @@ FLAG_COM_COST = 128
 FLAG_FRAME_VEL_COST = 256
 FLAG_OBSTACLE_COST = 512
 FLAG_SELF_COLLISION_COST = 1024
+FLAG_MOMENTUM_COST = 2048
 MAX_COST_FRAMES = 4
 MAX_COLLISION_POINTS, MAX_OBSTACLES = 16, 8
 MAX_COLLISION_PAIRS = 32
@@ -71,6 +72,7 @@ EXPORTS = [
     "ddp_hip_obstacle_set_points", "ddp_hip_obstacle_upload", "ddp_hip_obstacle_download", "ddp_hip_obstacle_clearance",
     "ddp_hip_self_collision_set_pairs", "ddp_hip_self_collision_upload", "ddp_hip_self_collision_download",
     "ddp_hip_self_collision_clearance",
+    "ddp_hip_momentum_cost_upload", "ddp_hip_momentum_cost_download", "ddp_hip_model_centroidal_momentum",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -178,6 +180,10 @@ def lib():
         L.ddp_hip_self_collision_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_self_collision_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_self_collision_clearance.argtypes = [C.c_void_p, C.c_int, _dp]
+    if hasattr(L, "ddp_hip_momentum_cost_upload"):   # (likewise: set_momentum_cost and ModelHandle.centroidal_momentum)
+        L.ddp_hip_momentum_cost_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_momentum_cost_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_model_centroidal_momentum.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp]
     L.ddp_hip_rollout.argtypes = [C.c_void_p]
     L.ddp_hip_linearize.argtypes = [C.c_void_p]
     L.ddp_hip_linearize_stages.argtypes = [C.c_void_p, C.c_uint32]
@@ -355,6 +361,16 @@ class ModelHandle:
         _check(lib().ddp_hip_model_frame_velocity(self._h, int(joint), _ptr(off), _ptr(q), _ptr(v), _ptr(vel), _ptr(Jq) if jacobian else None,
                                                   _ptr(Jv) if jacobian else None), "model_frame_velocity")
         return (vel, Jq.reshape(self.nv, 6).T.copy(), Jv.reshape(self.nv, 6).T.copy()) if jacobian else vel
+
+    def centroidal_momentum(self, q, v, jacobian=False):
+        """The centroidal momentum h = (l, k) of a tree model at the state (q, v), world-aligned axes, k about the centre of
+        mass, as (6,); with jacobian=True (h6, Jq, Jv), Jq = dh / d(delta q) and Jv = dh / dv = A_G as (6, nv): the jacobians of
+        FLAG_MOMENTUM_COST (ddp_hip.h)"""
+        q, v = _f64(q), _f64(v)
+        h6, Jq, Jv = np.zeros(6), np.zeros(6 * self.nv), np.zeros(6 * self.nv)
+        _check(lib().ddp_hip_model_centroidal_momentum(self._h, _ptr(q), _ptr(v), _ptr(h6), _ptr(Jq) if jacobian else None,
+                                                       _ptr(Jv) if jacobian else None), "model_centroidal_momentum")
+        return (h6, Jq.reshape(self.nv, 6).T.copy(), Jv.reshape(self.nv, 6).T.copy()) if jacobian else h6
 
 
 
@@ -579,6 +595,20 @@ class Context:
         """(target, weight) of instances first .. first + count - 1, each (count, T+1, F, 6)"""
         per = (self.spec.T + 1, getattr(self, "n_cost_frames", 0), 6)
         return self._cost_download(lib().ddp_hip_frame_vel_download, "frame_vel_download", (per, per), first, count)
+
+    def set_momentum_cost(self, target=None, weight=None, first=0, count=None):
+        """The centroidal-momentum terms of instances first .. first + count - 1 (a context created with FLAG_MOMENTUM_COST;
+        ddp_hip.h).  target: desired linear, then angular momentum (about the centre of mass) in world axes, weight: per axis,
+        >= 0; each (T+1, 6) for every instance of the range or (count, T+1, 6) with one per instance; weight also takes (6,) and
+        scalars for every step.  None leaves that side as it is."""
+        per = (self.spec.T + 1, 6)
+        count, arrs = self._cost_sides("set_momentum_cost", (("target", target, per, ()), ("weight", weight, per, ((6,), ()))), first, count)
+        self._cost_upload(lib().ddp_hip_momentum_cost_upload, "momentum_cost_upload", arrs, first, count)
+
+    def momentum_cost(self, first=0, count=None):
+        """(target, weight) of instances first .. first + count - 1, each (count, T+1, 6)"""
+        per = (self.spec.T + 1, 6)
+        return self._cost_download(lib().ddp_hip_momentum_cost_download, "momentum_cost_download", (per, per), first, count)
 
     def set_obstacle_points(self, points, kinds):
         """The collision points [(joint, off, radius), ...] (up to MAX_COLLISION_POINTS spheres on the robot) and the kinds of the

@@ -10,7 +10,7 @@
 
 // The terms, in the order the kernels add them (after the stage cost and the tracking cost): lin.hip launches one kernel per
 // live term in this order, fwd.hip forms the first three inline and the others in kernels of their own, in this order
-enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_LIMITS, COST_COM, COST_FRAME_VEL, COST_OBSTACLE, COST_SELF_COLLISION, COST_COUNT };
+enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_LIMITS, COST_COM, COST_FRAME_VEL, COST_MOMENTUM, COST_OBSTACLE, COST_SELF_COLLISION, COST_COUNT };
 
 enum CostFill : int32_t { FILL_ZERO, FILL_NEG_INF, FILL_POS_INF, FILL_QUAT };   // FILL_QUAT: identity quaternions (0, 0, 0, 1)
 
@@ -34,6 +34,7 @@ static const CostDesc kCostDesc[COST_COUNT] = {
     {DDP_HIP_FLAG_STATE_LIMITS, 3, {1, 1, 1}, {FILL_NEG_INF, FILL_POS_INF, FILL_ZERO}, 0, true, false},                 // lo | hi | weight, per tangent row
     {DDP_HIP_FLAG_COM_COST, 2, {3, 3, 0}, {FILL_ZERO, FILL_ZERO, 0}, 1, true, true},                                    // target | weight
     {DDP_HIP_FLAG_FRAME_VEL_COST, 2, {6, 6, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, true},       // target | weight, per frame
+    {DDP_HIP_FLAG_MOMENTUM_COST, 2, {6, 6, 0}, {FILL_ZERO, FILL_ZERO, 0}, 1, true, true},                               // target | weight
     {DDP_HIP_FLAG_OBSTACLE_COST, 2, {4, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_OBSTACLES, false, true},          // geom | weight, per slot
     {DDP_HIP_FLAG_SELF_COLLISION_COST, 2, {1, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COLLISION_PAIRS, false, true},   // margin | weight, per pair
 };

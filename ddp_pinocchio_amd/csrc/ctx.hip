@@ -250,8 +250,8 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   if ((flags & DDP_HIP_FLAG_FRAME_VEL_COST) && !(flags & DDP_HIP_FLAG_FRAME_COST)) return DDP_HIP_E_ARG;   // the velocity terms alike
   if ((flags & DDP_HIP_FLAG_OBSTACLE_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // collision points are points of a tree's joints
   if ((flags & DDP_HIP_FLAG_SELF_COLLISION_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the spheres alike
-  if (flags & DDP_HIP_FLAG_COM_COST) {
-    if (mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the CoM is of a tree's bodies
+  if (flags & (DDP_HIP_FLAG_COM_COST | DDP_HIP_FLAG_MOMENTUM_COST)) {
+    if (mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the CoM, and the momentum about it, are of a tree's bodies
     if (!mo.mass_j || !mo.jtype) return DDP_HIP_E_ARG;
     double total = 0.0;
     for (int i = 0; i < (mo.jtype[0] == DDP_HIP_JOINT_FREEFLYER ? mo.nv - 5 : mo.nv); ++i) total += mo.mass_j[i];
@@ -358,7 +358,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipStreamSynchronize(ctx->stream));
   }
   for (int term = 0; term < COST_COUNT; ++term) {
-    // frames, obstacle slots and self-collision pairs: no layout until they are set; limits (lo = -inf, hi = +inf, w = 0: no limit anywhere) and CoM: fixed
+    // frames, obstacle slots and self-collision pairs: no layout until they are set; limits (lo = -inf, hi = +inf, w = 0: no limit anywhere), CoM and momentum: fixed
     CostBlock& k = ctx->cost[term];
     k.desc = &kCostDesc[term];
     k.max_items = k.desc->max_items ? k.desc->max_items : (int32_t)d.n;
@@ -709,6 +709,16 @@ extern "C" int ddp_hip_com_cost_upload(ddp_hip_ctx* ctx, const double* target, c
 extern "C" int ddp_hip_com_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first, int64_t count) {
   double* host[] = {target, weight};
   return cost_block_download(ctx, COST_COM, host, first, count);
+}
+
+extern "C" int ddp_hip_momentum_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first, int64_t count) {
+  const double* host[] = {target, weight};
+  const CostSideOk ok[] = {cost_finite_side, cost_weight_side};
+  return cost_block_upload(ctx, COST_MOMENTUM, host, ok, first, count);
+}
+extern "C" int ddp_hip_momentum_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first, int64_t count) {
+  double* host[] = {target, weight};
+  return cost_block_download(ctx, COST_MOMENTUM, host, first, count);
 }
 
 // state limits: lo <= hi, before anything is written: a side that arrives alone is held against the resident other side (read

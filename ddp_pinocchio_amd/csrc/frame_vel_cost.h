@@ -232,8 +232,10 @@ __device__ __forceinline__ void vel_frame_lane(const DevModel& m, int j, int f, 
 //   gx[row] += sum_f sum_a A_f[a][row] (w_a r_a),   gxx[i][j] += sum_f sum_a A_f[a][min] w_a A_f[a][max]     (Gauss-Newton)
 // the frames and axes in their fixed order and entry (i, j) in (min, max) order: the block stays symmetric bit for bit.  w / wr:
 // weights and weighted residuals [nf][6] (0 where the weight is 0).  A term of weight 0, or of a column that carries nothing of
-// the axis' group, is left out; an entry that no term reaches is not written
-__device__ __forceinline__ void vel_add_wave(const VelWaveLds& S, int nf, const double* w, const double* wr, int nu, int tid, int nt, int nv,
+// the axis' group, is left out; an entry that no term reaches is not written.  Rec: VelWaveLds, or another record with its A, cm
+// and idx (momentum_cost.h: one "frame" over every column)
+template <class Rec>
+__device__ __forceinline__ void vel_add_wave(const Rec& S, int nf, const double* w, const double* wr, int nu, int tid, int nt, int nv,
                                              int n, double* gx, double* gxx) {
   for (int k = tid; k < 2 * nu; k += nt) {
     const int h = k >= nu ? 1 : 0, c = S.idx[h ? k - nu : k];

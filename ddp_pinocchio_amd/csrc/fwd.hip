@@ -15,6 +15,7 @@
 #include "frame_cost.h"
 #include "frame_vel_cost.h"
 #include "internal.h"
+#include "momentum_cost.h"
 #include "obstacle_cost.h"
 #include "rbd.h"
 #include "self_collision_cost.h"
@@ -806,7 +807,7 @@ __global__ void cand_sum_kernel(FwdParams p) {
   p.fw_dcost[(int64_t)b * na + a] = dsum;
 }
 
-// The add-on cost kernels below (CoM, frame velocities, obstacles) run over a list of `count` (trajectory, t) pairs, t = 0 .. T,
+// The add-on cost kernels below (CoM, frame velocities, momentum, obstacles) run over a list of `count` (trajectory, t) pairs, t = 0 .. T,
 // `na` trajectories per instance.  Pair e: which trajectory, which t, whose instance, which block bt1 = b (T+1) + t of the term's
 // data.  skip: nothing is written for this pair (past the list, or a candidate the rollout kernels skip: state != 0, beyond
 // 2^-33; state == nullptr: a resident trajectory, none is skipped).  live: the pair is evaluated (the kernels narrow it further)
@@ -936,6 +937,42 @@ __global__ __launch_bounds__(64) void frame_vel_cost_kernel(FrameVelCostDev fv, 
     *term = rbd::frame_vel_term(w, fv.target + (bt1 * fv.nf + f) * 6, pd, om);
     return true;
   });
+}
+
+// The centroidal-momentum terms (DDP_HIP_FLAG_MOMENTUM_COST, ddp_hip.h) of a list of states, added on top like the CoM terms above:
+// the same list, the same two uses, the same `lpe` lanes per evaluation.  Lane j walks joint j's path once with its body alone
+// (rbd::momentum_body: no jacobian, no per-joint arrays) and leaves m_j, m_j p_j, m_j pdot_j and its angular momentum about the
+// world origin in LDS; the group's first lane adds them up in ascending order, shifts the angular part to the CoM
+// (rbd::momentum_fold) and forms 1/2 sum_a w_a (h_a - g_a)^2.  A term of weight 0 is left out, with the three angular weights 0
+// no inertia and no angular momentum is formed, and with all six the walk is left out: such a pair adds nothing (add != 0) or
+// stores +0 (add == 0).  A non-finite state gives a NaN term, as com_cost_kernel's does
+__global__ __launch_bounds__(64) void momentum_cost_kernel(MomentumCostDev mo, const DevModel* model, const double* xs, int64_t traj_stride,
+                                                           int64_t count, int32_t T1, int32_t nx, int32_t na, int32_t lpe, const int32_t* state,
+                                                           int32_t round, double* out, int32_t add) {
+  __shared__ double s_rec[64 * 10];
+  const DevModel& m = *model;
+  const int tid = threadIdx.x, g = tid / lpe, j = tid % lpe;
+  const int64_t e = (int64_t)blockIdx.x * (64 / lpe) + g;
+  const CostPair pr = cost_pair_decode(e, count, T1, na, state, round);
+  const double* w = mo.weight + pr.bt1 * 6;
+  bool live = pr.live, ang = false;
+  if (live && !rbd::weights_any(w, 6)) live = false;
+  if (live) ang = rbd::frame_weights_any(w + 3);
+  if (live && j < m.nj) {
+    const double* x = xs + pr.traj * traj_stride + (int64_t)pr.t * nx;
+    double* r = s_rec + 10 * tid;
+    r[7] = r[8] = r[9] = 0.0;
+    r[0] = rbd::momentum_body(m, j, x, x + m.nq, ang, r + 1, r + 4, r + 7);
+  }
+  __syncthreads();
+  if (j != 0 || pr.skip) return;
+  double term = 0.0;
+  if (live) {
+    double h[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    rbd::momentum_fold(s_rec + 10 * tid, m.nj, ang, h);
+    term = rbd::frame_vel_term(w, mo.target + pr.bt1 * 6, h, h + 3);
+  }
+  cost_pair_store(out, e, term, live, add);
 }
 
 // The obstacle terms (DDP_HIP_FLAG_OBSTACLE_COST, ddp_hip.h) of a list of states, added on top like the frame-velocity terms above:
@@ -1280,6 +1317,11 @@ static void launch_com_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t 
 static void launch_frame_vel_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   launch_add_on(frame_vel_cost_kernel, frame_vel_cost_dev(ctx), DDP_HIP_MAX_COST_FRAMES, ctx, xs, na, count, state, round, out, add);
 }
+static void launch_momentum_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
+  int32_t lpe = 8;
+  while (lpe < ctx->model_h.nj) lpe *= 2;
+  launch_add_on(momentum_cost_kernel, momentum_cost_dev(ctx), lpe, ctx, xs, na, count, state, round, out, add, lpe);
+}
 static void launch_obstacle_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   launch_add_on(obstacle_cost_kernel, obstacle_cost_dev(ctx), DDP_HIP_MAX_COLLISION_POINTS, ctx, xs, na, count, state, round, out, add);
 }
@@ -1288,13 +1330,14 @@ static void launch_self_collision_cost(ddp_hip_ctx* ctx, const double* xs, int n
 }
 
 // The terms formed out of line, in the fixed order of their additions (after everything cost_kernel / the rollout kernels form
-// inline): CoM, frame velocities, obstacles, self-collision.  launch_cost and ddp_hip_forward both walk this table and nothing else
+// inline): CoM, frame velocities, momentum, obstacles, self-collision.  launch_cost and ddp_hip_forward both walk this table and nothing else
 struct AddOnTerm {
   int term;
   AddOnLaunch launch;
 };
 static const AddOnTerm kAddOn[] = {{COST_COM, launch_com_cost},
                                    {COST_FRAME_VEL, launch_frame_vel_cost},
+                                   {COST_MOMENTUM, launch_momentum_cost},
                                    {COST_OBSTACLE, launch_obstacle_cost},
                                    {COST_SELF_COLLISION, launch_self_collision_cost}};
 

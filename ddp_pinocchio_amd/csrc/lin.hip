@@ -18,6 +18,7 @@
 #include "frame_vel_cost.h"
 #include "internal.h"
 #include "lin_common.h"
+#include "momentum_cost.h"
 #include "obstacle_cost.h"
 #include "rbd.h"
 #include "rbd_deriv.h"
@@ -350,8 +351,41 @@ __global__ __launch_bounds__(64) void lin_frame_vel_cost_kernel(LinParams p, Fra
   rbd::vel_add_wave(S, nf, s_w, s_wr, __builtin_popcountll(U), tid, (int)blockDim.x, nv, n, gx, gxx);
 }
 
+// Centroidal-momentum cost (DDP_HIP_FLAG_MOMENTUM_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost
+// kernel on the same stream (the fixed order of additions: ..., CoM, frame velocities, momentum).  r = h(q, v) - g depends on q and
+// on v and every joint has a column in both halves of A = [dh/d(delta q) | dh/dv], so the term fills all of lx and lxx.  Lane-parallel
+// over joints like lin_com_cost_kernel: lane j walks its own path once and leaves a_j, o_j, its path, its body's mass, first moment
+// and inertia about the world origin and its own rate's twist in LDS (rbd::mom_stage_lane), then forms its body's twist over its
+// path in ascending order and the body's momentum (rbd::mom_prefix_lane), then mass, first moment, inertia and momentum of its
+// subtree over the records in ascending order and from them its column(s) of A (rbd::mom_column_lane); then the wave adds the
+// gradient rows and the entries (rbd::vel_add_wave with one "frame" over every column: entry (i, j) in (min, max) order, symmetric
+// bit for bit).  It reads p.x and touches nothing but lx / lxx.  A term of weight 0 is left out, with the three angular weights 0
+// no inertia and no angular quantity is formed, a block whose six weights are 0 returns at once.  t = T: lfx / lfxx
+__global__ __launch_bounds__(64) void lin_momentum_cost_kernel(LinParams p, MomentumCostDev mo) {
+  const int64_t bt1 = blockIdx.x;
+  const int n = (int)p.d.n, nv = (int)p.d.nv;
+  const int tid = threadIdx.x;
+  const double* w = mo.weight + bt1 * 6;
+  if (!rbd::weights_any(w, 6)) return;
+  const bool ang = rbd::frame_weights_any(w + 3);
+  const DevModel& m = *p.model;
+  const LinCostBlock blk = lin_cost_block(p, bt1);
+  const double* q = blk.q;
+  __shared__ rbd::MomWaveLds S;
+  __shared__ double s_w[6], s_wr[6];
+  rbd::mom_jacobians_wave(m, q, q + m.nq, tid, ang, S);
+  if (tid < 6) {
+    const double wa = w[tid];
+    s_w[tid] = wa;
+    s_wr[tid] = wa != 0.0 ? wa * (S.h[tid] - mo.target[bt1 * 6 + tid]) : 0.0;
+  }
+  __syncthreads();
+  double *gx = blk.gx, *gxx = blk.gxx;
+  rbd::vel_add_wave(S, 1, s_w, s_wr, nv, tid, (int)blockDim.x, nv, n, gx, gxx);
+}
+
 // Obstacle cost (DDP_HIP_FLAG_OBSTACLE_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost kernel
-// on the same stream (the fixed order of additions: ..., CoM, frame velocities, obstacles).  The penalty is one-sided, so most
+// on the same stream (the fixed order of additions: ..., frame velocities, momentum, obstacles).  The penalty is one-sided, so most
 // waves have nothing to add and must cost next to nothing.  A block whose weights are all 0 returns at once.  Phase 1: lane
 // k < n_points walks point k (rbd::frame_point) and runs over its live slots in ascending order; a lane with an active pair
 // (w != 0, e != 0, a direction u) forms g_k = sum_o w e u and the symmetric M_k = sum_o w u u^T on the way, in registers.  One
@@ -400,7 +434,7 @@ __global__ __launch_bounds__(64) void lin_obstacle_cost_kernel(LinParams p, Obst
 }
 
 // Self-collision cost (DDP_HIP_FLAG_SELF_COLLISION_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost
-// kernel on the same stream (the fixed order of additions: ..., frame velocities, obstacles, self-collision).  One-sided like the
+// kernel on the same stream (the fixed order of additions: ..., momentum, obstacles, self-collision).  One-sided like the
 // obstacle cost: most waves have nothing to add.  A block whose weights are all 0 returns at once.  Phase 1: lane k < n_points
 // walks sphere k (rbd::frame_point); lane i < n_pairs fetches p_a and p_b from the lanes that hold them (cross-lane reads: no
 // LDS) and forms d_i.  One wave-level vote decides: a wave without an active pair (w != 0, e != 0, a direction u) returns here,
@@ -1300,12 +1334,13 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
       hipLaunchKernelGGL(lin_track_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p);
     else hipLaunchKernelGGL(lin_cost_kernel, dim3((unsigned)BT), dim3(64), 0, ctx->stream, p);
     // the add-on terms, one kernel per live term, each adding onto what the ones before it left.  The fixed order of additions:
-    // cost, tracking, frame positions, frame orientations, limits, CoM, frame velocities, obstacles, self-collision
+    // cost, tracking, frame positions, frame orientations, limits, CoM, frame velocities, momentum, obstacles, self-collision
     const dim3 blocks((unsigned)(BT + d.batch));
     const FrameCostDev fc = frame_cost_dev(ctx);
     const StateLimitsDev sl = state_limits_dev(ctx);
     const CoMCostDev cm = com_cost_dev(ctx);
     const FrameVelCostDev fv = frame_vel_cost_dev(ctx);
+    const MomentumCostDev mo = momentum_cost_dev(ctx);
     const ObstacleCostDev ob = obstacle_cost_dev(ctx);
     const SelfCollisionDev sc = self_collision_dev(ctx);
     auto add = [&](bool live, auto kernel, const auto& dev) { if (live) hipLaunchKernelGGL(kernel, blocks, dim3(64), 0, ctx->stream, p, dev); };
@@ -1314,6 +1349,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     add(sl.weight, lin_limit_cost_kernel, sl);
     add(cm.target, lin_com_cost_kernel, cm);
     add(fv.target, lin_frame_vel_cost_kernel, fv);
+    add(mo.target, lin_momentum_cost_kernel, mo);
     add(ob.geom, lin_obstacle_cost_kernel, ob);
     add(sc.margin, lin_self_collision_cost_kernel, sc);
   }

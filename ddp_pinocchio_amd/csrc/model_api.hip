@@ -10,6 +10,7 @@
 #include "com_cost.h"
 #include "frame_vel_cost.h"
 #include "internal.h"
+#include "momentum_cost.h"
 #include "rbd.h"
 #include "rbd_deriv.h"
 
@@ -109,6 +110,21 @@ __global__ __launch_bounds__(64) void model_frame_vel_kernel(const DevModel* m, 
   }
 }
 
+// h = (l, k) and A = [dh/d(delta q) | dh/dv] by one wave, with the traversal of lin_momentum_cost_kernel (momentum_cost.h):
+// in = q | v, out = h6 | Jq[6 nv] | Jv[6 nv] (the columns that are identically zero 0).  Always with the angular part and always
+// all 6 + 12 nv outputs (they fit the handle's output area of 3 * 64 * 64 + 4 * 64 doubles), whether the caller asked for the
+// jacobians or not: h6 of a call with them is bit for bit h6 of a call without
+__global__ __launch_bounds__(64) void model_momentum_kernel(const DevModel* m, const double* in, double* out) {
+  __shared__ rbd::MomWaveLds S;
+  const int tid = threadIdx.x, nv = m->nv;
+  rbd::mom_jacobians_wave(*m, in, in + m->nq, tid, true, S);
+  if (tid < 6) out[tid] = S.h[tid];
+  for (int i = tid; i < 12 * nv; i += blockDim.x) {
+    const int h = i / (6 * nv), c = (i % (6 * nv)) / 6, a = i % 6;
+    out[6 + i] = ((S.cm[0][2 * h + a / 3] >> c) & 1) ? S.A[0][h][c][a] : 0.0;
+  }
+}
+
 #define MODEL_DISPATCH(nv, CALL)       \
   do {                                 \
     if ((nv) <= 6) { CALL(6); }        \
@@ -141,6 +157,8 @@ int run(ddp_hip_model_handle* h, const double* in, size_t n_in, double* out, siz
     hipLaunchKernelGGL(model_com_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o);
   } else if (what == 4) {
     hipLaunchKernelGGL(model_frame_vel_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac);   // (want_jac: the joint)
+  } else if (what == 5) {
+    hipLaunchKernelGGL(model_momentum_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o);
   } else {
 #define CALL(NJ) hipLaunchKernelGGL((model_frame_kernel<NJ>), dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac)
     MODEL_DISPATCH(nv, CALL);
@@ -259,6 +277,23 @@ extern "C" int ddp_hip_model_frame_velocity(ddp_hip_model_handle* h, int32_t joi
   const int rc = run(h, in, (size_t)(nq + nv + 3), out, (size_t)(6 + ((Jq || Jv) ? 12 * nv : 0)), 4, joint);
   if (rc != DDP_HIP_OK) return rc;
   memcpy(vel6, out, sizeof(double) * 6);
+  if (Jq) memcpy(Jq, out + 6, sizeof(double) * 6 * nv);
+  if (Jv) memcpy(Jv, out + 6 + 6 * nv, sizeof(double) * 6 * nv);
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_model_centroidal_momentum(ddp_hip_model_handle* h, const double* q, const double* v, double* h6, double* Jq, double* Jv) {
+  if (!h || !q || !v || !h6 || h->model_h.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_ARG;
+  const int nv = h->model_h.nv, nq = h->model_h.nq;
+  double total = 0.0;
+  for (int i = 0; i < h->model_h.nj; ++i) total += h->model_h.I6[i][9];   // the body masses (ctx.hip: pack_body_inertia)
+  if (!(total > 0.0)) return DDP_HIP_E_ARG;
+  double in[2 * DDP_MAXJ + 1];
+  memcpy(in, q, sizeof(double) * nq); memcpy(in + nq, v, sizeof(double) * nv);
+  double out[6 + 12 * DDP_MAXJ];
+  const int rc = run(h, in, (size_t)(nq + nv), out, (size_t)(6 + ((Jq || Jv) ? 12 * nv : 0)), 5, 0);
+  if (rc != DDP_HIP_OK) return rc;
+  memcpy(h6, out, sizeof(double) * 6);
   if (Jq) memcpy(Jq, out + 6, sizeof(double) * 6 * nv);
   if (Jv) memcpy(Jv, out + 6 + 6 * nv, sizeof(double) * 6 * nv);
   return DDP_HIP_OK;

@@ -14,6 +14,13 @@ __device__ __forceinline__ void cross3(const double* a, const double* b, double*
   c[1] = a[2] * b[0] - a[0] * b[2];
   c[2] = a[0] * b[1] - a[1] * b[0];
 }
+__device__ __forceinline__ double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+// y = S x, S symmetric 3 x 3 as a packed lower triangle (xx, yx, yy, zx, zy, zz), the layout of the first rows of DevModel::I6
+__device__ __forceinline__ void sym3_mv(const double* S, const double* x, double* y) {
+  y[0] = S[0] * x[0] + S[1] * x[1] + S[3] * x[2];
+  y[1] = S[1] * x[0] + S[2] * x[1] + S[4] * x[2];
+  y[2] = S[3] * x[0] + S[4] * x[1] + S[5] * x[2];
+}
 // y = A x, y = A^T x  (row-major 3x3)
 __device__ __forceinline__ void mv3(const double* A, const double* x, double* y) {
   y[0] = A[0] * x[0] + A[1] * x[1] + A[2] * x[2];

@@ -325,6 +325,42 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * after the obstacles'). */
 #define DDP_HIP_FLAG_SELF_COLLISION_COST 1024u
 #define DDP_HIP_MAX_COLLISION_PAIRS 32
+/* Say how much momentum the robot as a whole may carry: "do not build up angular momentum in the swing phase", "land with zero
+ * momentum", "regulate the CoM velocity to 0.3 m/s forward", "spin up for the jump".  The flag stands alone and needs no other
+ * flag.  The centroidal momentum h(q, v) = A_G(q) v in world-aligned axes: for body j with mass m_j, p_j(q) the world position of
+ * its CoM (point com[j] of joint j), R_j the world rotation of joint j's frame, I_j = R_j Ic_j R_j^T, omega_j the angular velocity
+ * of that frame and pdot_j the velocity of p_j (omega_f and pdot_f of DDP_HIP_FLAG_FRAME_VEL_COST for the frame (j, com[j])),
+ * M = sum_j m_j and c = sum_j m_j p_j / M,
+ *   l = sum_j m_j pdot_j                                     (linear momentum, M cdot)
+ *   k = sum_j [ m_j (p_j - c) x pdot_j + I_j omega_j ]       (angular momentum about the centre of mass)
+ *   h = (l, k) in R^6.
+ * Per instance b and t = 0 .. T a target g[b][t] in R^6 and weights w[b][t] in R^6 (>= 0), r = h - g[b][t]:
+ *   l(t, x, u) += 1/2 sum_a w[b][t][a] r_a^2      t < T
+ *   lf(x_T)    += 1/2 sum_a w[b][T][a] r_a^2
+ * to whatever the context optimises otherwise; with w = (w, w, w, 0, 0, 0) a CoM-velocity cost scaled by M^2.  Derivatives in the
+ * tangent at x, A = [ dh/d(delta q) | dh/dv ] (6 x 2 nv), by column, formed by subtree with spatial quantities about the world
+ * origin: S_i = (al, be) joint i's axis as a twist (revolute: al = a_i, be = o_i x a_i; prismatic: al = 0, be = a_i, with a_i the
+ * world axis and o_i the world origin of joint i), V_i = (omega_i, vO_i) body i's twist, and for a motion (al', be') the momentum
+ * of the subtree rooted at i (itself included)
+ *   I_sub(i)(al', be') = sum_{j in sub(i)} ( m_j u_j,  p_j x m_j u_j + I_j al' ),   u_j = be' + al' x p_j;
+ * with (l_sub, kO_sub) the subtree's momentum about the origin:
+ *   (lv, kv) = I_sub(i)(S_i)                          dh/dv_i = ( lv,  kv - c x lv )
+ *   X = S_i x V_i = ( al x omega_i,  al x vO_i + be x omega_i ),      (l2, k2) = I_sub(i)(X)
+ *   lq = al x l_sub - l2,    kq = al x kO_sub + be x l_sub - k2       dh/dq_i = ( lq,  kq - (lv / M) x l - c x lq )
+ *   free-flyer root (body twists, linear part first; e_c column c of R_0): dh/dv = (M e_c, 0) for the linear columns and I_sub(0)
+ *   applied to (e_c, o_0 x e_c), shifted to c alike, for the angular ones; dh/dq = 0 for the linear columns and (e_c x l, e_c x k)
+ *   for the angular ones.
+ *   lx += A^T (w o r) over all 2 nv rows,   lxx += A^T diag(w) A  (the q-q, q-v, v-q and v-v blocks),   lfx / lfxx alike at T;
+ * lu, luu and lux are untouched.  Columns that are identically zero (the root's linear dh/dq, the angular part of the root's
+ * linear dh/dv) are left out, not added as rounding residue.  lxx is Gauss-Newton (the term sum_a w_a r_a d^2 h_a is dropped: exact
+ * where r = 0, positive semidefinite); entry (i, j) is formed in (min, max) order with the axes in fixed order: symmetric bit for
+ * bit, no atomics.  The data travels through ddp_hip_momentum_cost_* below.  At create targets and weights are 0.  A term of
+ * weight 0 is left out (not multiplied by 0): a block whose six weights are 0 forms nothing, one whose three angular weights
+ * are 0 forms no inertia and no angular momentum, and with nothing uploaded or every weight 0 a context computes bit for bit what
+ * it computes without the flag.  Tree models only (the pendulum: DDP_HIP_E_UNSUPPORTED); a total mass M <= 0 is DDP_HIP_E_ARG.
+ * The flag combines with every other flag: the terms are formed by kernels of their own, which add onto what the other terms'
+ * kernels leave (after the frame velocities', before the obstacles'). */
+#define DDP_HIP_FLAG_MOMENTUM_COST 2048u
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -422,6 +458,12 @@ int ddp_hip_self_collision_download(ddp_hip_ctx* ctx, double* margin, double* we
  * (which = 0) or X_NEW (which = 1), +inf where no pair is live, NaN where a distance is.  From the first
  * ddp_hip_self_collision_set_pairs on (before: DDP_HIP_E_ARG), live weights or not. */
 int ddp_hip_self_collision_clearance(ddp_hip_ctx* ctx, int which, double* out);
+/* The momentum targets and weights of a context created with DDP_HIP_FLAG_MOMENTUM_COST (else DDP_HIP_E_UNSUPPORTED),
+ * stream-ordered like ddp_hip_com_cost_upload.  Host arrays [n_instances][T+1][6] (linear part, then angular part); a NULL pointer
+ * leaves that side as it is.  An upload is refused as a whole (DDP_HIP_E_ARG, nothing written) for a bad instance range, a
+ * non-finite target and a negative or non-finite weight. */
+int ddp_hip_momentum_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first_instance, int64_t n_instances);
+int ddp_hip_momentum_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first_instance, int64_t n_instances);
 
 /* make_trajectory (ddp.hpp:392-415): X[0] and U given -> X[1..T] */
 int ddp_hip_rollout(ddp_hip_ctx* ctx);
@@ -577,6 +619,10 @@ int ddp_hip_model_com(ddp_hip_model_handle* h, const double* q, double* c3, doub
  * the hand's present speed" */
 int ddp_hip_model_frame_velocity(ddp_hip_model_handle* h, int32_t joint, const double off[3], const double* q, const double* v,
                                  double* vel6, double* Jq, double* Jv);
+/* The centroidal momentum h6 = (l, k) of a tree model at the state (q, v), world-aligned axes, as DDP_HIP_FLAG_MOMENTUM_COST
+ * defines it, and, where not NULL, its jacobians Jq = dh / d(delta q) and Jv = dh / dv = A_G, each 6 x nv column-major, formed by
+ * the traversal the cost kernels use.  A total mass <= 0: DDP_HIP_E_ARG.  For targets such as "half the present momentum" */
+int ddp_hip_model_centroidal_momentum(ddp_hip_model_handle* h, const double* q, const double* v, double* h6, double* Jq, double* Jv);
 
 /* ---- built-in seeded model tables (no URDF exists offline: SURVEY.md D4, 8d) -------------- */
 /* ..._FF: the same robots on a free-flyer root instead of a fixed base / 3 prismatic + 3 revolute base joints */
