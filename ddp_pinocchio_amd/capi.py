@@ -32,9 +32,11 @@ FLAG_FRAME_VEL_COST = 256
 FLAG_OBSTACLE_COST = 512
 FLAG_SELF_COLLISION_COST = 1024
 FLAG_MOMENTUM_COST = 2048
+FLAG_RELATIVE_FRAME_COST = 4096
 MAX_COST_FRAMES = 4
 MAX_COLLISION_POINTS, MAX_OBSTACLES = 16, 8
 MAX_COLLISION_PAIRS = 32
+MAX_FRAME_PAIRS = 4
 OBSTACLE_SPHERE, OBSTACLE_HALFSPACE = 0, 1
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
 
@@ -73,6 +75,8 @@ EXPORTS = [
     "ddp_hip_self_collision_set_pairs", "ddp_hip_self_collision_upload", "ddp_hip_self_collision_download",
     "ddp_hip_self_collision_clearance",
     "ddp_hip_momentum_cost_upload", "ddp_hip_momentum_cost_download", "ddp_hip_model_centroidal_momentum",
+    "ddp_hip_relative_frame_set_pairs", "ddp_hip_relative_frame_upload", "ddp_hip_relative_frame_download",
+    "ddp_hip_relative_frame_error", "ddp_hip_model_relative_frame",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -184,6 +188,12 @@ def lib():
         L.ddp_hip_momentum_cost_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_momentum_cost_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_model_centroidal_momentum.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp]
+    if hasattr(L, "ddp_hip_relative_frame_upload"):  # (likewise: set_relative_frame_pairs, set_relative_frame_cost, relative_frame_error, ModelHandle.relative_frame)
+        L.ddp_hip_relative_frame_set_pairs.argtypes = [C.c_void_p, C.c_int32, _ip, _dp, _ip, _dp]
+        L.ddp_hip_relative_frame_upload.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_relative_frame_download.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_relative_frame_error.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.ddp_hip_model_relative_frame.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp]
     L.ddp_hip_rollout.argtypes = [C.c_void_p]
     L.ddp_hip_linearize.argtypes = [C.c_void_p]
     L.ddp_hip_linearize_stages.argtypes = [C.c_void_p, C.c_uint32]
@@ -372,6 +382,18 @@ class ModelHandle:
                                                        _ptr(Jv) if jacobian else None), "model_centroidal_momentum")
         return (h6, Jq.reshape(self.nv, 6).T.copy(), Jv.reshape(self.nv, 6).T.copy()) if jacobian else h6
 
+    def relative_frame(self, joint_a, off_a, joint_b, off_b, q, jacobian=False):
+        """The placement of frame B = (joint_b, off_b) relative to frame A = (joint_a, off_a) at q, as FLAG_RELATIVE_FRAME_COST
+        defines it (ddp_hip.h): (p3, quat4) = R_a^T (p_b - p_a) and the quaternion of R_a^T R_b (x y z w, w >= 0); with
+        jacobian=True (p3, quat4, J), J = [J_pos; R_b^T (W_b - W_a)] as (6, nv), the jacobian of the residual at e_rot = 0"""
+        off_a, off_b, q = _f64(off_a), _f64(off_b), _f64(q)
+        if off_a.shape != (3,) or off_b.shape != (3,):
+            raise ValueError("relative_frame: every off is a 3-vector")
+        p3, qt, J = np.zeros(3), np.zeros(4), np.zeros(6 * self.nv)
+        _check(lib().ddp_hip_model_relative_frame(self._h, int(joint_a), _ptr(off_a), int(joint_b), _ptr(off_b), _ptr(q), _ptr(p3), _ptr(qt),
+                                                  _ptr(J) if jacobian else None), "model_relative_frame")
+        return (p3, qt, J.reshape(self.nv, 6).T.copy()) if jacobian else (p3, qt)
+
 
 
 class ProblemSpec:
@@ -417,6 +439,7 @@ class Context:
         self.n_cost_frames = 0
         self.n_obstacles = 0
         self.n_collision_pairs = 0
+        self.n_frame_pairs = 0
 
     def close(self):
         if self._h:
@@ -609,6 +632,54 @@ class Context:
         """(target, weight) of instances first .. first + count - 1, each (count, T+1, 6)"""
         per = (self.spec.T + 1, 6)
         return self._cost_download(lib().ddp_hip_momentum_cost_download, "momentum_cost_download", (per, per), first, count)
+
+    def set_relative_frame_pairs(self, pairs):
+        """The frame pairs [((joint_a, off_a), (joint_b, off_b)), ...] (1 .. MAX_FRAME_PAIRS of them, the two frames of a pair on
+        different joints) of a context created with FLAG_RELATIVE_FRAME_COST (ddp_hip.h), shared by the batch: base frame A, tip
+        frame B.  With the same count and the same joints as before the per-instance data stays (the points may move), else
+        targets and weights are reset to 0 and the references to identity quaternions"""
+        pairs = list(pairs)
+        if any(len(p) != 2 or len(p[0]) != 2 or len(p[1]) != 2 for p in pairs):
+            raise ValueError("set_relative_frame_pairs: every pair is ((joint_a, off_a), (joint_b, off_b))")
+        ja = np.ascontiguousarray([int(p[0][0]) for p in pairs], dtype=np.int32)
+        jb = np.ascontiguousarray([int(p[1][0]) for p in pairs], dtype=np.int32)
+        offa = [np.asarray(p[0][1], dtype=np.float64) for p in pairs]
+        offb = [np.asarray(p[1][1], dtype=np.float64) for p in pairs]
+        if any(o.shape != (3,) for o in offa + offb):
+            raise ValueError("set_relative_frame_pairs: every off is a 3-vector")
+        offa, offb = _f64(offa).reshape(-1), _f64(offb).reshape(-1)
+        _check(lib().ddp_hip_relative_frame_set_pairs(self._h, len(pairs), ja.ctypes.data_as(_ip), _ptr(offa), jb.ctypes.data_as(_ip),
+                                                      _ptr(offb)), "relative_frame_set_pairs")
+        self.n_frame_pairs = len(pairs)
+
+    def set_relative_frame_cost(self, target=None, quat=None, weight=None, first=0, count=None):
+        """The relative-frame terms of instances first .. first + count - 1 (a context created with FLAG_RELATIVE_FRAME_COST;
+        ddp_hip.h), of the P pairs of set_relative_frame_pairs.  target: B's point as seen from A in A's joint axes, quat: B's
+        axes as seen from A's as unit quaternions (x y z w), weight: three position axes, then three rotation axes, >= 0; each
+        (T+1, P, 3 | 4 | 6) for every instance of the range or (count, T+1, P, .) with one per instance; weight also takes (P, 6),
+        (6,) and scalars by broadcast.  None leaves that side as it is.  The pair count is the one this object last passed to
+        set_relative_frame_pairs; before that call there is no shape to check against and the call raises ValueError."""
+        T1, P = self.spec.T + 1, getattr(self, "n_frame_pairs", 0)
+        if not P:
+            raise ValueError("set_relative_frame_cost: no pairs yet, call set_relative_frame_pairs first")
+        count, arrs = self._cost_sides("set_relative_frame_cost", (("target", target, (T1, P, 3), ()), ("quat", quat, (T1, P, 4), ()),
+                                                                   ("weight", weight, (T1, P, 6), ((P, 6), (6,), ()))), first, count)
+        if arrs[1] is not None and not bool(np.all(np.abs(np.sqrt(np.sum(arrs[1] ** 2, axis=-1)) - 1.0) <= 1e-10)):
+            raise ValueError("set_relative_frame_cost quat: every quaternion has unit norm (to 1e-10)")
+        self._cost_upload(lib().ddp_hip_relative_frame_upload, "relative_frame_upload", arrs, first, count)
+
+    def relative_frame_cost(self, first=0, count=None):
+        """(target, quat, weight) of instances first .. first + count - 1: (count, T+1, P, 3), (.., 4) and (.., 6)"""
+        T1, P = self.spec.T + 1, getattr(self, "n_frame_pairs", 0)    # (0 before set_relative_frame_pairs: empty arrays)
+        return self._cost_download(lib().ddp_hip_relative_frame_download, "relative_frame_download", ((T1, P, 3), (T1, P, 4), (T1, P, 6)),
+                                   first, count)
+
+    def relative_frame_error(self, which=0):
+        """(batch, T+1, P, 6): the unweighted residual r = (r_pos, e_rot) of every pair along X (which = 0) or X_NEW (which = 1),
+        against the resident targets and references, live weights or not"""
+        out = np.zeros((self.batch, self.spec.T + 1, getattr(self, "n_frame_pairs", 0), 6))
+        _check(lib().ddp_hip_relative_frame_error(self._h, int(which), _ptr(out)), "relative_frame_error")
+        return out
 
     def set_obstacle_points(self, points, kinds):
         """The collision points [(joint, off, radius), ...] (up to MAX_COLLISION_POINTS spheres on the robot) and the kinds of the

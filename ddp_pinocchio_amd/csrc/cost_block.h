@@ -9,8 +9,10 @@
 #include "ddp_hip/ddp_hip.h"
 
 // The terms, in the order the kernels add them (after the stage cost and the tracking cost): lin.hip launches one kernel per
-// live term in this order, fwd.hip forms the first three inline and the others in kernels of their own, in this order
-enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_LIMITS, COST_COM, COST_FRAME_VEL, COST_MOMENTUM, COST_OBSTACLE, COST_SELF_COLLISION, COST_COUNT };
+// live term in this order, fwd.hip forms the first three inline and the others in kernels of their own, in this order: frame
+// positions, frame orientations, limits, CoM, frame velocities, momentum, relative frames, obstacles, self-collision
+enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_LIMITS, COST_COM, COST_FRAME_VEL, COST_MOMENTUM, COST_RELATIVE_FRAME, COST_OBSTACLE,
+                          COST_SELF_COLLISION, COST_COUNT };
 
 enum CostFill : int32_t { FILL_ZERO, FILL_NEG_INF, FILL_POS_INF, FILL_QUAT };   // FILL_QUAT: identity quaternions (0, 0, 0, 1)
 
@@ -35,6 +37,7 @@ static const CostDesc kCostDesc[COST_COUNT] = {
     {DDP_HIP_FLAG_COM_COST, 2, {3, 3, 0}, {FILL_ZERO, FILL_ZERO, 0}, 1, true, true},                                    // target | weight
     {DDP_HIP_FLAG_FRAME_VEL_COST, 2, {6, 6, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, true},       // target | weight, per frame
     {DDP_HIP_FLAG_MOMENTUM_COST, 2, {6, 6, 0}, {FILL_ZERO, FILL_ZERO, 0}, 1, true, true},                               // target | weight
+    {DDP_HIP_FLAG_RELATIVE_FRAME_COST, 3, {3, 4, 6}, {FILL_ZERO, FILL_QUAT, FILL_ZERO}, DDP_HIP_MAX_FRAME_PAIRS, false, true},   // target | quat | weight, per pair
     {DDP_HIP_FLAG_OBSTACLE_COST, 2, {4, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_OBSTACLES, false, true},          // geom | weight, per slot
     {DDP_HIP_FLAG_SELF_COLLISION_COST, 2, {1, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COLLISION_PAIRS, false, true},   // margin | weight, per pair
 };
@@ -118,6 +121,17 @@ static inline bool cost_pair_list_ok(int32_t n_points, const int32_t* joint, int
   for (int32_t i = 0; i < n_pairs; ++i) {
     if (a[i] < 0 || a[i] >= n_points || b[i] < 0 || b[i] >= n_points) return false;
     if (a[i] == b[i] || joint[a[i]] == joint[b[i]]) return false;
+  }
+  return true;
+}
+
+// a relative-frame pair list over a model of nj joints (pair i: base frame on joint ja[i], tip frame on jb[i]): joints in range,
+// ja != jb (on one joint the relative placement is constant), offsets finite.  Duplicate pairs, and a pair in both orders, are allowed
+static inline bool cost_frame_pairs_ok(int32_t nj, int32_t n_pairs, const int32_t* ja, const double* offa, const int32_t* jb, const double* offb) {
+  for (int32_t i = 0; i < n_pairs; ++i) {
+    if (ja[i] < 0 || ja[i] >= nj || jb[i] < 0 || jb[i] >= nj || ja[i] == jb[i]) return false;
+    for (int a = 0; a < 3; ++a)
+      if (!isfinite(offa[3 * i + a]) || !isfinite(offb[3 * i + a])) return false;
   }
   return true;
 }

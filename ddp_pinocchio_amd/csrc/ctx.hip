@@ -250,6 +250,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   if ((flags & DDP_HIP_FLAG_FRAME_VEL_COST) && !(flags & DDP_HIP_FLAG_FRAME_COST)) return DDP_HIP_E_ARG;   // the velocity terms alike
   if ((flags & DDP_HIP_FLAG_OBSTACLE_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // collision points are points of a tree's joints
   if ((flags & DDP_HIP_FLAG_SELF_COLLISION_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the spheres alike
+  if ((flags & DDP_HIP_FLAG_RELATIVE_FRAME_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the frame pairs alike
   if (flags & (DDP_HIP_FLAG_COM_COST | DDP_HIP_FLAG_MOMENTUM_COST)) {
     if (mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the CoM, and the momentum about it, are of a tree's bodies
     if (!mo.mass_j || !mo.jtype) return DDP_HIP_E_ARG;
@@ -358,7 +359,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipStreamSynchronize(ctx->stream));
   }
   for (int term = 0; term < COST_COUNT; ++term) {
-    // frames, obstacle slots and self-collision pairs: no layout until they are set; limits (lo = -inf, hi = +inf, w = 0: no limit anywhere), CoM and momentum: fixed
+    // frames, frame pairs, obstacle slots and self-collision pairs: no layout until they are set; limits (lo = -inf, hi = +inf, w = 0: no limit anywhere), CoM and momentum: fixed
     CostBlock& k = ctx->cost[term];
     k.desc = &kCostDesc[term];
     k.max_items = k.desc->max_items ? k.desc->max_items : (int32_t)d.n;
@@ -368,6 +369,8 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   }
   if (flags & DDP_HIP_FLAG_OBSTACLE_COST) CTX_TRY(hipMalloc(&ctx->ob_clear_d, sizeof(double) * (size_t)(d.batch * (d.T + 1))));
   if (flags & DDP_HIP_FLAG_SELF_COLLISION_COST) CTX_TRY(hipMalloc(&ctx->sc_clear_d, sizeof(double) * (size_t)(d.batch * (d.T + 1))));
+  if (flags & DDP_HIP_FLAG_RELATIVE_FRAME_COST)
+    CTX_TRY(hipMalloc(&ctx->rf_err_d, sizeof(double) * (size_t)(d.batch * (d.T + 1) * DDP_HIP_MAX_FRAME_PAIRS * 6)));
   int rc = bwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = fwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = lin_setup(ctx);
@@ -394,6 +397,7 @@ extern "C" int ddp_hip_destroy(ddp_hip_ctx* ctx) {
   }
   if (ctx->ob_clear_d) (void)hipFree(ctx->ob_clear_d);
   if (ctx->sc_clear_d) (void)hipFree(ctx->sc_clear_d);
+  if (ctx->rf_err_d) (void)hipFree(ctx->rf_err_d);
   if (ctx->ne_d) (void)hipFree(ctx->ne_d);
   if (ctx->Epre_d) (void)hipFree(ctx->Epre_d);
   if (ctx->target_d) (void)hipFree(ctx->target_d);
@@ -699,6 +703,41 @@ extern "C" int ddp_hip_self_collision_upload(ddp_hip_ctx* ctx, const double* mar
 extern "C" int ddp_hip_self_collision_download(ddp_hip_ctx* ctx, double* margin, double* weight, int64_t first, int64_t count) {
   double* host[] = {margin, weight};
   return cost_block_download(ctx, COST_SELF_COLLISION, host, first, count);
+}
+
+// frame pairs shared by the batch; a target, a reference quaternion and six weights per (instance, t, pair)
+extern "C" int ddp_hip_relative_frame_set_pairs(ddp_hip_ctx* ctx, int32_t n_pairs, const int32_t* joint_a, const double* off_a, const int32_t* joint_b,
+                                                const double* off_b) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_RELATIVE_FRAME_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (n_pairs < 1 || n_pairs > DDP_HIP_MAX_FRAME_PAIRS || !joint_a || !off_a || !joint_b || !off_b) return DDP_HIP_E_ARG;
+  if (!cost_frame_pairs_ok(ctx->model_h.nj, n_pairs, joint_a, off_a, joint_b, off_b)) return DDP_HIP_E_ARG;
+  bool same = n_pairs == ctx->rf_np;
+  for (int i = 0; same && i < n_pairs; ++i) same = joint_a[i] == ctx->rf_ja[i] && joint_b[i] == ctx->rf_jb[i];
+  if (!same) {
+    // other joints are another meaning of the per-pair data: targets and weights start again at 0, references at the identity
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int rc_ = cost_block_setup(ctx, COST_RELATIVE_FRAME, n_pairs);
+    if (rc_ != DDP_HIP_OK) return rc_;
+  }
+  ctx->rf_np = n_pairs;
+  for (int i = 0; i < n_pairs; ++i) {
+    ctx->rf_ja[i] = joint_a[i];
+    ctx->rf_jb[i] = joint_b[i];
+    for (int a = 0; a < 3; ++a) { ctx->rf_offa[i][a] = off_a[3 * i + a]; ctx->rf_offb[i][a] = off_b[3 * i + a]; }
+  }
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_relative_frame_upload(ddp_hip_ctx* ctx, const double* target, const double* quat, const double* weight, int64_t first,
+                                             int64_t count) {
+  const double* host[] = {target, quat, weight};
+  const CostSideOk ok[] = {cost_finite_side, cost_quat_side, cost_weight_side};
+  return cost_block_upload(ctx, COST_RELATIVE_FRAME, host, ok, first, count);
+}
+extern "C" int ddp_hip_relative_frame_download(ddp_hip_ctx* ctx, double* target, double* quat, double* weight, int64_t first, int64_t count) {
+  double* host[] = {target, quat, weight};
+  return cost_block_download(ctx, COST_RELATIVE_FRAME, host, first, count);
 }
 
 extern "C" int ddp_hip_com_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first, int64_t count) {

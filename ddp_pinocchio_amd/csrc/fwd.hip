@@ -18,6 +18,7 @@
 #include "momentum_cost.h"
 #include "obstacle_cost.h"
 #include "rbd.h"
+#include "relative_frame_cost.h"
 #include "self_collision_cost.h"
 #include "state_limits.h"
 
@@ -807,7 +808,7 @@ __global__ void cand_sum_kernel(FwdParams p) {
   p.fw_dcost[(int64_t)b * na + a] = dsum;
 }
 
-// The add-on cost kernels below (CoM, frame velocities, momentum, obstacles) run over a list of `count` (trajectory, t) pairs, t = 0 .. T,
+// The add-on cost kernels below (CoM, frame velocities, momentum, relative frames, obstacles) run over a list of `count` (trajectory, t) pairs, t = 0 .. T,
 // `na` trajectories per instance.  Pair e: which trajectory, which t, whose instance, which block bt1 = b (T+1) + t of the term's
 // data.  skip: nothing is written for this pair (past the list, or a candidate the rollout kernels skip: state != 0, beyond
 // 2^-33; state == nullptr: a resident trajectory, none is skipped).  live: the pair is evaluated (the kernels narrow it further)
@@ -973,6 +974,42 @@ __global__ __launch_bounds__(64) void momentum_cost_kernel(MomentumCostDev mo, c
     term = rbd::frame_vel_term(w, mo.target + pr.bt1 * 6, h, h + 3);
   }
   cost_pair_store(out, e, term, live, add);
+}
+
+// The relative-frame terms (DDP_HIP_FLAG_RELATIVE_FRAME_COST, ddp_hip.h) of a list of states, added on top like the frame-velocity
+// terms above: the same list, the same two uses (add != 0: out[pair] += term behind cost_kernel; add == 0: out[pair] = term, its
+// candidates' array in a line-search round, with the candidates the rollout kernels skip skipped here).  DDP_HIP_MAX_FRAME_PAIRS
+// lanes per state, 16 states per wave: lane i walks frame pair i (rbd::relative_placement: two walks joint -> root, no jacobian, no
+// per-joint arrays) and leaves 1/2 sum_a w_a r_a^2 in LDS; the group's first lane adds the pairs' terms in ascending order.  A term
+// of weight 0 is left out, a pair whose six weights are 0 is not walked, one whose rotation (position) weights are 0 reads no
+// quaternion and forms no log (reads no target), and a state without a live weight adds nothing (add != 0) or stores +0
+// (add == 0).  A non-finite state gives a NaN term, as com_cost_kernel's does
+__global__ __launch_bounds__(64) void relative_frame_cost_kernel(RelativeFrameDev rf, const DevModel* model, const double* xs, int64_t traj_stride,
+                                                                 int64_t count, int32_t T1, int32_t nx, int32_t na, const int32_t* state,
+                                                                 int32_t round, double* out, int32_t add) {
+  __shared__ double s_term[64];
+  __shared__ int32_t s_walked[64];
+  const DevModel& m = *model;
+  pair_lanes_fold<DDP_HIP_MAX_FRAME_PAIRS, false>(s_term, s_walked, rf.np, xs, traj_stride, count, T1, nx, na, state, round, out, add,
+                                                  [&](int i, int64_t bt1, const double* x, double* term) {
+    if (!rbd::weights_any(rf.weight + (bt1 * rf.np + i) * 6, 6)) return false;
+    *term = rbd::relative_frame_term(m, rf, i, bt1, x);
+    return true;
+  });
+}
+
+// ddp_hip_relative_frame_error: one lane per (instance, t, pair) of one resident trajectory, out[(bt1 np + i) 6 ..] = the unweighted
+// residual r = (r_pos, e_rot) of pair i against the resident target and reference, whatever the weights
+__global__ __launch_bounds__(64) void relative_frame_error_kernel(RelativeFrameDev rf, const DevModel* model, const double* xs, int64_t count,
+                                                                  int32_t nx, double* out) {
+  const int64_t e = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (e >= count * rf.np) return;
+  const int64_t bt1 = e / rf.np;
+  const int i = (int)(e % rf.np);
+  const DevModel& m = *model;
+  rbd::RelativePlacement P;
+  rbd::relative_placement(m, m.ff != 0, rf.ja[i], rf.offa[i], rf.jb[i], rf.offb[i], xs + bt1 * nx, true, P);
+  rbd::relative_frame_residual(P, rf.target + e * 3, rf.quat + e * 4, out + e * 6);
 }
 
 // The obstacle terms (DDP_HIP_FLAG_OBSTACLE_COST, ddp_hip.h) of a list of states, added on top like the frame-velocity terms above:
@@ -1322,6 +1359,9 @@ static void launch_momentum_cost(ddp_hip_ctx* ctx, const double* xs, int na, int
   while (lpe < ctx->model_h.nj) lpe *= 2;
   launch_add_on(momentum_cost_kernel, momentum_cost_dev(ctx), lpe, ctx, xs, na, count, state, round, out, add, lpe);
 }
+static void launch_relative_frame_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
+  launch_add_on(relative_frame_cost_kernel, relative_frame_dev(ctx), DDP_HIP_MAX_FRAME_PAIRS, ctx, xs, na, count, state, round, out, add);
+}
 static void launch_obstacle_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   launch_add_on(obstacle_cost_kernel, obstacle_cost_dev(ctx), DDP_HIP_MAX_COLLISION_POINTS, ctx, xs, na, count, state, round, out, add);
 }
@@ -1330,7 +1370,8 @@ static void launch_self_collision_cost(ddp_hip_ctx* ctx, const double* xs, int n
 }
 
 // The terms formed out of line, in the fixed order of their additions (after everything cost_kernel / the rollout kernels form
-// inline): CoM, frame velocities, momentum, obstacles, self-collision.  launch_cost and ddp_hip_forward both walk this table and nothing else
+// inline): CoM, frame velocities, momentum, relative frames, obstacles, self-collision.  launch_cost and ddp_hip_forward both walk
+// this table and nothing else
 struct AddOnTerm {
   int term;
   AddOnLaunch launch;
@@ -1338,6 +1379,7 @@ struct AddOnTerm {
 static const AddOnTerm kAddOn[] = {{COST_COM, launch_com_cost},
                                    {COST_FRAME_VEL, launch_frame_vel_cost},
                                    {COST_MOMENTUM, launch_momentum_cost},
+                                   {COST_RELATIVE_FRAME, launch_relative_frame_cost},
                                    {COST_OBSTACLE, launch_obstacle_cost},
                                    {COST_SELF_COLLISION, launch_self_collision_cost}};
 
@@ -1397,6 +1439,22 @@ extern "C" int ddp_hip_self_collision_clearance(ddp_hip_ctx* ctx, int which, dou
                      which == 0 ? p.x_old : p.x_new, total, (int32_t)ctx->d.nx, ctx->sc_clear_d);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, ctx->sc_clear_d, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_relative_frame_error(ddp_hip_ctx* ctx, int which, double* out) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_RELATIVE_FRAME_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (!out || (which != 0 && which != 1) || ctx->rf_np == 0) return DDP_HIP_E_ARG;   // (no pairs set: nothing to measure)
+  HIP_TRY(hipSetDevice(ctx->device));
+  const FwdParams p = make_params(ctx);
+  const RelativeFrameDev rf = relative_frame_dev(ctx, true);
+  const int64_t total = ctx->d.batch * (ctx->d.T + 1);
+  hipLaunchKernelGGL(relative_frame_error_kernel, dim3((unsigned)((total * rf.np + 63) / 64)), dim3(64), 0, ctx->stream, rf, ctx->model_d,
+                     which == 0 ? p.x_old : p.x_new, total, (int32_t)ctx->d.nx, ctx->rf_err_d);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, ctx->rf_err_d, sizeof(double) * (size_t)(total * rf.np * 6), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return DDP_HIP_OK;
 }

@@ -287,6 +287,11 @@ struct ddp_hip_ctx {
   double sc_radius[DDP_HIP_MAX_COLLISION_POINTS] = {};
   int32_t sc_pa[DDP_HIP_MAX_COLLISION_PAIRS] = {}, sc_pb[DDP_HIP_MAX_COLLISION_PAIRS] = {};
   double* sc_clear_d = nullptr;               // [batch][T+1] what ddp_hip_self_collision_clearance hands back
+  // the relative-frame pairs (ddp_hip_relative_frame_set_pairs): base frame A = (rf_ja, rf_offa), tip frame B = (rf_jb, rf_offb)
+  int32_t rf_np = 0;                          // pairs set (0: none yet)
+  int32_t rf_ja[DDP_HIP_MAX_FRAME_PAIRS] = {}, rf_jb[DDP_HIP_MAX_FRAME_PAIRS] = {};
+  double rf_offa[DDP_HIP_MAX_FRAME_PAIRS][3] = {}, rf_offb[DDP_HIP_MAX_FRAME_PAIRS][3] = {};
+  double* rf_err_d = nullptr;                 // [batch][T+1][DDP_HIP_MAX_FRAME_PAIRS][6] what ddp_hip_relative_frame_error hands back
 
   bool box_dirty = false;       // CTRL_LO / CTRL_HI were uploaded since lo <= hi was last checked (ctx.hip: box_check)
 

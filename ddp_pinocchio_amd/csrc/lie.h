@@ -94,6 +94,11 @@ __device__ __forceinline__ void R_to_quat(const double* M, double* qt) {
     qt[3] = (M[3] - M[1]) / s; qt[0] = (M[2] + M[6]) / s; qt[1] = (M[5] + M[7]) / s; qt[2] = 0.25 * s;
   }
 }
+// ... and the one of the two with w >= 0
+__device__ __forceinline__ void R_to_quat_pos(const double* M, double* qt) {
+  R_to_quat(M, qt);
+  if (qt[3] < 0) { qt[0] = -qt[0]; qt[1] = -qt[1]; qt[2] = -qt[2]; qt[3] = -qt[3]; }
+}
 // e = log3(R_ref^T R), |e| <= pi, R_ref the rotation of the unit quaternion qref, R row-major: the rotation from the reference
 // frame to R's, in the axes of either (exp(e) e = e).  Through the quaternion of R_ref^T R and quat_log, whose k = 2 atan2(|v|, w)
 // / |v| does not depend on the quaternion's norm.  At |e| = pi the log is not differentiable, and which of the two axes +-e comes

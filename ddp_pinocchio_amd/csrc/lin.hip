@@ -22,6 +22,7 @@
 #include "obstacle_cost.h"
 #include "rbd.h"
 #include "rbd_deriv.h"
+#include "relative_frame_cost.h"
 #include "self_collision_cost.h"
 #include "state_limits.h"
 
@@ -384,8 +385,79 @@ __global__ __launch_bounds__(64) void lin_momentum_cost_kernel(LinParams p, Mome
   rbd::vel_add_wave(S, 1, s_w, s_wr, nv, tid, (int)blockDim.x, nv, n, gx, gxx);
 }
 
+// Relative-frame cost (DDP_HIP_FLAG_RELATIVE_FRAME_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost
+// kernel on the same stream (the fixed order of additions: ..., frame velocities, momentum, relative frames).  A block whose
+// weights are all 0 returns at once, before any LDS access or barrier.  Lanes j < nj stage world axis, world origin and path of
+// their joint in LDS (rbd::stage_joint_lane); lane 63 - i walks live pair i (rbd::relative_placement: two walks; the top lanes, so
+// that on a robot of fewer than 60 joints no lane does both) and leaves R_a^T, Jlog3(e) R_b^T, p_b, w and w o r.  After the barrier
+// every lane forms the two halves of each live pair's symmetric difference, path(ja) \ path(jb) and path(jb) \ path(ja), as column
+// masks; their union is compacted (rbd::column_index_lane) and the 6 x n_u columns of each live pair are staged in LDS
+// (rbd::relative_frame_stage_columns).  A joint on both paths moves both frames alike and is in neither half: the wave adds over
+// the union of the symmetric differences alone (rbd::relative_frame_add_wave: pairs ascending, position axes, then rotation axes,
+// entry (i, j) in (min, max) order, symmetric bit for bit).  It reads p.x and touches nothing but those entries.  A term of weight
+// 0 is left out, a pair whose six weights are 0 is not walked, one whose rotation (position) weights are 0 reads no quaternion and
+// forms no log (reads no target).  No scratch, no atomics.  t = T: lfx / lfxx
+__global__ __launch_bounds__(64) void lin_relative_frame_cost_kernel(LinParams p, RelativeFrameDev rf) {
+  const int64_t bt1 = blockIdx.x;
+  const int n = (int)p.d.n;
+  const int tid = threadIdx.x, np = rf.np;
+  const double* w = rf.weight + bt1 * np * 6;
+  if (!rbd::weights_any(w, 6 * np)) return;
+  const DevModel& m = *p.model;
+  const bool ff = m.ff != 0;
+  const LinCostBlock blk = lin_cost_block(p, bt1);
+  const double* q = blk.q;
+  __shared__ rbd::RelativeWaveLds S;
+  if (tid < m.nj) rbd::stage_joint_lane<0>(m, q, tid, S.jw, nullptr);
+  const int i = 63 - tid;
+  if (i < np && rbd::weights_any(w + 6 * i, 6)) {
+    const bool pos = rbd::frame_weights_any(w + 6 * i), rot = rbd::frame_weights_any(w + 6 * i + 3);
+    rbd::RelativePlacement P;
+    rbd::relative_placement(m, ff, rf.ja[i], rf.offa[i], rf.jb[i], rf.offb[i], q, rot, P);
+    double r[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    rbd::relative_frame_residual(P, pos ? rf.target + (bt1 * np + i) * 3 : nullptr, rot ? rf.quat + (bt1 * np + i) * 4 : nullptr, r);
+    for (int k = 0; k < 3; ++k) {
+      S.pb[i][k] = P.pb[k];
+      for (int a = 0; a < 3; ++a) S.RaT[i][3 * k + a] = P.ca[k][a];
+    }
+    if (rot) {
+      double J[9];
+      lie::so3_Jlog(r + 3, J);
+      for (int k = 0; k < 3; ++k)
+        for (int a = 0; a < 3; ++a) S.JR[i][3 * k + a] = J[3 * k] * P.cb[0][a] + J[3 * k + 1] * P.cb[1][a] + J[3 * k + 2] * P.cb[2][a];   // Jlog3 R_b^T
+    }
+    for (int a = 0; a < 6; ++a) {
+      const double wa = w[6 * i + a];
+      S.w[i][a] = wa;
+      S.wr[i][a] = wa != 0.0 ? wa * r[a] : 0.0;
+    }
+  }
+  // the tangent columns of the revolute joints: the ones that carry rotation (a free-flyer root's are on every path)
+  const unsigned long long revj = __ballot(tid < m.nj && !(ff && tid == 0) && m.jtype[tid] == DDP_HIP_JOINT_REVOLUTE);
+  const unsigned long long rot_cols = ff ? (revj >> 1) << 6 : revj;
+  __syncthreads();
+  unsigned long long U = 0;
+  for (int k = 0; k < np; ++k) {
+    unsigned long long ca = 0, cb = 0;
+    if (rbd::weights_any(w + 6 * k, 6)) {
+      const unsigned long long ma = rbd::tangent_mask(ff, S.jw.mask[rf.ja[k]]), mb = rbd::tangent_mask(ff, S.jw.mask[rf.jb[k]]);
+      ca = ma & ~mb;
+      cb = mb & ~ma;
+      U |= ca | cb;
+    }
+    if (k == tid) { S.ca[k] = ca; S.cb[k] = cb; }
+  }
+  rbd::column_index_lane(U, tid, S.idx);
+  __syncthreads();
+  const int nu = __builtin_popcountll(U);
+  rbd::relative_frame_stage_columns(m, S, np, nu, tid, (int)blockDim.x);
+  __syncthreads();
+  double *gx = blk.gx, *gxx = blk.gxx;
+  rbd::relative_frame_add_wave(S, np, rot_cols, nu, tid, (int)blockDim.x, n, gx, gxx);
+}
+
 // Obstacle cost (DDP_HIP_FLAG_OBSTACLE_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost kernel
-// on the same stream (the fixed order of additions: ..., frame velocities, momentum, obstacles).  The penalty is one-sided, so most
+// on the same stream (the fixed order of additions: ..., momentum, relative frames, obstacles).  The penalty is one-sided, so most
 // waves have nothing to add and must cost next to nothing.  A block whose weights are all 0 returns at once.  Phase 1: lane
 // k < n_points walks point k (rbd::frame_point) and runs over its live slots in ascending order; a lane with an active pair
 // (w != 0, e != 0, a direction u) forms g_k = sum_o w e u and the symmetric M_k = sum_o w u u^T on the way, in registers.  One
@@ -434,7 +506,7 @@ __global__ __launch_bounds__(64) void lin_obstacle_cost_kernel(LinParams p, Obst
 }
 
 // Self-collision cost (DDP_HIP_FLAG_SELF_COLLISION_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost
-// kernel on the same stream (the fixed order of additions: ..., momentum, obstacles, self-collision).  One-sided like the
+// kernel on the same stream (the fixed order of additions: ..., relative frames, obstacles, self-collision).  One-sided like the
 // obstacle cost: most waves have nothing to add.  A block whose weights are all 0 returns at once.  Phase 1: lane k < n_points
 // walks sphere k (rbd::frame_point); lane i < n_pairs fetches p_a and p_b from the lanes that hold them (cross-lane reads: no
 // LDS) and forms d_i.  One wave-level vote decides: a wave without an active pair (w != 0, e != 0, a direction u) returns here,
@@ -1334,13 +1406,15 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
       hipLaunchKernelGGL(lin_track_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p);
     else hipLaunchKernelGGL(lin_cost_kernel, dim3((unsigned)BT), dim3(64), 0, ctx->stream, p);
     // the add-on terms, one kernel per live term, each adding onto what the ones before it left.  The fixed order of additions:
-    // cost, tracking, frame positions, frame orientations, limits, CoM, frame velocities, momentum, obstacles, self-collision
+    // cost, tracking, frame positions, frame orientations, limits, CoM, frame velocities, momentum, relative frames, obstacles,
+    // self-collision
     const dim3 blocks((unsigned)(BT + d.batch));
     const FrameCostDev fc = frame_cost_dev(ctx);
     const StateLimitsDev sl = state_limits_dev(ctx);
     const CoMCostDev cm = com_cost_dev(ctx);
     const FrameVelCostDev fv = frame_vel_cost_dev(ctx);
     const MomentumCostDev mo = momentum_cost_dev(ctx);
+    const RelativeFrameDev rf = relative_frame_dev(ctx);
     const ObstacleCostDev ob = obstacle_cost_dev(ctx);
     const SelfCollisionDev sc = self_collision_dev(ctx);
     auto add = [&](bool live, auto kernel, const auto& dev) { if (live) hipLaunchKernelGGL(kernel, blocks, dim3(64), 0, ctx->stream, p, dev); };
@@ -1350,6 +1424,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     add(cm.target, lin_com_cost_kernel, cm);
     add(fv.target, lin_frame_vel_cost_kernel, fv);
     add(mo.target, lin_momentum_cost_kernel, mo);
+    add(rf.weight, lin_relative_frame_cost_kernel, rf);
     add(ob.geom, lin_obstacle_cost_kernel, ob);
     add(sc.margin, lin_self_collision_cost_kernel, sc);
   }

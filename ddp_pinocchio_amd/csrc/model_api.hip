@@ -13,6 +13,7 @@
 #include "momentum_cost.h"
 #include "rbd.h"
 #include "rbd_deriv.h"
+#include "relative_frame_cost.h"
 
 extern void ddp_hip_fill_dev_model(const ddp_hip_model* mo, DevModel& dm);   // ctx.hip
 extern bool ddp_hip_build_tables(DevModel& dm);
@@ -125,6 +126,37 @@ __global__ __launch_bounds__(64) void model_momentum_kernel(const DevModel* m, c
   }
 }
 
+// The placement of frame B = (jb, off_b) relative to A = (ja, off_a) and its jacobian at e_rot = 0 by one wave, with the traversal
+// of lin_relative_frame_cost_kernel (relative_frame_cost.h): in = q | off_a[3] | off_b[3], out = rel3 | quat4 | J[6 nv] (column-major;
+// columns on both paths or on neither 0, and the rotation rows of a prismatic column)
+__global__ __launch_bounds__(64) void model_relative_frame_kernel(const DevModel* m, const double* in, double* out, int ja, int jb) {
+  __shared__ rbd::RelativeWaveLds S;
+  const int tid = threadIdx.x, nv = m->nv;
+  const bool ff = m->ff != 0;
+  if (tid < m->nj) rbd::stage_joint_lane<0>(*m, in, tid, S.jw, nullptr);
+  if (tid == 63) {
+    rbd::RelativePlacement P;
+    rbd::relative_placement(*m, ff, ja, in + m->nq, jb, in + m->nq + 3, in, true, P);
+    double qt[4];
+    lie::R_to_quat_pos(P.E, qt);
+    for (int k = 0; k < 3; ++k) {
+      out[k] = P.rel[k];
+      S.pb[0][k] = P.pb[k];
+      for (int a = 0; a < 3; ++a) { S.RaT[0][3 * k + a] = P.ca[k][a]; S.JR[0][3 * k + a] = P.cb[k][a]; }   // (Jlog3(0) = I: R_b^T alone)
+    }
+    for (int k = 0; k < 4; ++k) out[3 + k] = qt[k];
+  }
+  __syncthreads();
+  const unsigned long long ma = rbd::tangent_mask(ff, S.jw.mask[ja]), mb = rbd::tangent_mask(ff, S.jw.mask[jb]);
+  if (tid == 0) { S.ca[0] = ma & ~mb; S.cb[0] = mb & ~ma; }
+  __syncthreads();
+  for (int c = tid; c < nv; c += blockDim.x) {
+    double col[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (((ma ^ mb) >> c) & 1) rbd::relative_frame_column(*m, ff, S, 0, c, true, true, col);
+    for (int a = 0; a < 6; ++a) out[7 + 6 * c + a] = col[a];
+  }
+}
+
 #define MODEL_DISPATCH(nv, CALL)       \
   do {                                 \
     if ((nv) <= 6) { CALL(6); }        \
@@ -159,6 +191,9 @@ int run(ddp_hip_model_handle* h, const double* in, size_t n_in, double* out, siz
     hipLaunchKernelGGL(model_frame_vel_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac);   // (want_jac: the joint)
   } else if (what == 5) {
     hipLaunchKernelGGL(model_momentum_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o);
+  } else if (what == 6) {
+    hipLaunchKernelGGL(model_relative_frame_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac % DDP_MAXJ,
+                       want_jac / DDP_MAXJ);   // (want_jac: the two joints)
   } else {
 #define CALL(NJ) hipLaunchKernelGGL((model_frame_kernel<NJ>), dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac)
     MODEL_DISPATCH(nv, CALL);
@@ -296,5 +331,21 @@ extern "C" int ddp_hip_model_centroidal_momentum(ddp_hip_model_handle* h, const 
   memcpy(h6, out, sizeof(double) * 6);
   if (Jq) memcpy(Jq, out + 6, sizeof(double) * 6 * nv);
   if (Jv) memcpy(Jv, out + 6 + 6 * nv, sizeof(double) * 6 * nv);
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_model_relative_frame(ddp_hip_model_handle* h, int32_t joint_a, const double off_a[3], int32_t joint_b, const double off_b[3],
+                                            const double* q, double* p3, double* quat4, double* J) {
+  if (!h || !off_a || !off_b || !q || !p3 || !quat4 || h->model_h.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_ARG;
+  const int nv = h->model_h.nv, nq = h->model_h.nq, nj = h->model_h.nj;
+  if (joint_a < 0 || joint_a >= nj || joint_b < 0 || joint_b >= nj || joint_a == joint_b) return DDP_HIP_E_ARG;
+  double in[DDP_MAXJ + 1 + 6];
+  memcpy(in, q, sizeof(double) * nq); memcpy(in + nq, off_a, sizeof(double) * 3); memcpy(in + nq + 3, off_b, sizeof(double) * 3);
+  double out[7 + 6 * DDP_MAXJ];
+  const int rc = run(h, in, (size_t)(nq + 6), out, (size_t)(7 + (J ? 6 * nv : 0)), 6, joint_a + DDP_MAXJ * joint_b);
+  if (rc != DDP_HIP_OK) return rc;
+  memcpy(p3, out, sizeof(double) * 3);
+  memcpy(quat4, out + 3, sizeof(double) * 4);
+  if (J) memcpy(J, out + 7, sizeof(double) * 6 * nv);
   return DDP_HIP_OK;
 }

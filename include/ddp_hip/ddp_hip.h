@@ -361,6 +361,41 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * The flag combines with every other flag: the terms are formed by kernels of their own, which add onto what the other terms'
  * kernels leave (after the frame velocities', before the obstacles'). */
 #define DDP_HIP_FLAG_MOMENTUM_COST 2048u
+/* Say "keep this frame where it is relative to that frame": "carry the box: the right hand stays 30 cm from the left one, in the
+ * left hand's axes, palm facing it", "keep the tray level relative to the chest while the legs walk", "keep the feet parallel and a
+ * hip-width apart".  Two world-frame targets would fix the pair's common motion too, which is what such a task wants left free.
+ * The flag stands alone: it needs no DDP_HIP_FLAG_FRAME_COST and has its own frames.  Pairs, shared by the batch, up to
+ * DDP_HIP_MAX_FRAME_PAIRS: pair i has a base frame A = (joint ja_i, point offa_i) and a tip frame B = (joint jb_i, point offb_i),
+ * both by the convention of the cost frames, ja_i != jb_i (on one joint the relative placement is constant); one joint may be an
+ * ancestor of the other.  With p_a, p_b the points' world positions and R_a, R_b the world rotations of the two joints' frames
+ * (world = R body), per instance b, t = 0 .. T and pair i a target g[b][t][i] in R^3 (B's point as seen from A, in A's joint
+ * axes), a unit quaternion ref[b][t][i] = (x y z w) (R_ref: B's axes as seen from A's) and weights w[b][t][i] in R^6 (>= 0):
+ *   r_pos = R_a^T (p_b - p_a) - g,      e_rot = log3(R_ref^T R_a^T R_b), |e_rot| <= pi,      r = (r_pos, e_rot)
+ *   l(t, x, u) += 1/2 sum_i sum_a w[b][t][i][a] r_a^2      t < T
+ *   lf(x_T)    += 1/2 sum_i sum_a w[b][T][i][a] r_a^2
+ * to whatever the context optimises otherwise.  Derivatives in the tangent at x, by tangent column c, with s_c = +1 where c is on
+ * path(jb) alone and s_c = -1 where c is on path(ja) alone, a_c the world axis and o_c the world origin of column c's joint:
+ *   c on both paths or on neither:  nothing
+ *   J_pos[:, c] = s_c R_a^T point_column(c, p_b)       point_column: a_c x (p_b - o_c) revolute, a_c prismatic -- about p_b on BOTH sides
+ *   J_rot[:, c] = s_c Jlog3(e_rot) R_b^T a_c           revolute only: a prismatic column has no rotation part and it is left out
+ *   lx[q rows] += J^T (w o r),   lxx[q, q] += J^T diag(w) J,   lfx / lfxx alike at T.
+ * The A side uses p_b because d(R_a^T d) = R_a^T (dd - dw_a x d) with d = p_b - p_a: for a revolute column on A's side alone,
+ * -a x (p_a - o) - a x (p_b - p_a) = -a x (p_b - o).  A relative placement does not change when a common ancestor joint moves: for
+ * a column on both paths the two halves cancel identically, and such a column -- a free-flyer root's six always -- is left out, not
+ * added as rounding residue.  The orientation convention is that of DDP_HIP_FLAG_FRAME_ORIENT_COST, applied to R_a^T R_b: a
+ * perturbation acts as R_a^T R_b exp([R_b^T (dw_b - dw_a)]x), with the same Jlog3; ref and -ref are the same reference, and at
+ * |e_rot| = pi the same words apply as there.  The term touches the symmetric differences of the live pairs' paths only: velocity
+ * rows and columns, lu, luu, lux, every other q row and a free-flyer root's six rows are untouched.  lxx is Gauss-Newton (the term
+ * sum_a w_a r_a d^2 r_a is dropped: exact where r = 0, positive semidefinite); pairs ascending, the three position axes, then the
+ * three rotation axes, entry (i, j) formed in (min, max) order: symmetric bit for bit, no atomics.  A term of weight 0 is left out
+ * (not multiplied by 0): a pair whose six weights are 0 is not walked, one whose three rotation weights are 0 reads no quaternion
+ * and forms no log, one whose three position weights are 0 reads no target, and with nothing uploaded or every weight 0 a context
+ * computes bit for bit what it computes without the flag.  The data travels through ddp_hip_relative_frame_* below; at create no
+ * pairs are set.  Tree models only (the pendulum: DDP_HIP_E_UNSUPPORTED).  The flag combines with every other flag: the terms are
+ * formed by kernels of their own, which add onto what the other terms' kernels leave (after the momentum's, before the
+ * obstacles'). */
+#define DDP_HIP_FLAG_RELATIVE_FRAME_COST 4096u
+#define DDP_HIP_MAX_FRAME_PAIRS 4
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -464,6 +499,24 @@ int ddp_hip_self_collision_clearance(ddp_hip_ctx* ctx, int which, double* out);
  * non-finite target and a negative or non-finite weight. */
 int ddp_hip_momentum_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first_instance, int64_t n_instances);
 int ddp_hip_momentum_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first_instance, int64_t n_instances);
+/* The frame pairs of a context created with DDP_HIP_FLAG_RELATIVE_FRAME_COST (else DDP_HIP_E_UNSUPPORTED), shared by the batch:
+ * joint_a[n_pairs], off_a[n_pairs][3], joint_b[n_pairs], off_b[n_pairs][3].  DDP_HIP_E_ARG for n_pairs outside
+ * 1 .. DDP_HIP_MAX_FRAME_PAIRS, a joint outside the model, joint_a[i] == joint_b[i] and a non-finite offset.  It may be called
+ * again: with the same count and the same joints the per-instance data stays (the points may move), otherwise targets and weights
+ * are reset to 0 and the references to identity quaternions. */
+int ddp_hip_relative_frame_set_pairs(ddp_hip_ctx* ctx, int32_t n_pairs, const int32_t* joint_a, const double* off_a, const int32_t* joint_b,
+                                     const double* off_b);
+/* The pairs' targets, references and weights, stream-ordered like ddp_hip_frame_orient_upload.  Host arrays
+ * [n_instances][T+1][n_pairs][3], [..][4] and [..][6] (position weights, then rotation weights); a NULL pointer leaves that side
+ * as it is.  An upload is refused as a whole (DDP_HIP_E_ARG, nothing written) before ddp_hip_relative_frame_set_pairs, for a bad
+ * instance range, a non-finite value, a quaternion whose norm differs from 1 by more than 1e-10 and a negative weight. */
+int ddp_hip_relative_frame_upload(ddp_hip_ctx* ctx, const double* target, const double* quat, const double* weight, int64_t first_instance,
+                                  int64_t n_instances);
+int ddp_hip_relative_frame_download(ddp_hip_ctx* ctx, double* target, double* quat, double* weight, int64_t first_instance, int64_t n_instances);
+/* "Did the grasp hold": out[batch][T+1][n_pairs][6] (host) = the unweighted residual r = (r_pos, e_rot) of every pair along X
+ * (which = 0) or X_NEW (which = 1), against the resident targets and references.  From the first
+ * ddp_hip_relative_frame_set_pairs on (before: DDP_HIP_E_ARG), live weights or not. */
+int ddp_hip_relative_frame_error(ddp_hip_ctx* ctx, int which, double* out);
 
 /* make_trajectory (ddp.hpp:392-415): X[0] and U given -> X[1..T] */
 int ddp_hip_rollout(ddp_hip_ctx* ctx);
@@ -623,6 +676,13 @@ int ddp_hip_model_frame_velocity(ddp_hip_model_handle* h, int32_t joint, const d
  * defines it, and, where not NULL, its jacobians Jq = dh / d(delta q) and Jv = dh / dv = A_G, each 6 x nv column-major, formed by
  * the traversal the cost kernels use.  A total mass <= 0: DDP_HIP_E_ARG.  For targets such as "half the present momentum" */
 int ddp_hip_model_centroidal_momentum(ddp_hip_model_handle* h, const double* q, const double* v, double* h6, double* Jq, double* Jv);
+/* The placement of frame B = (joint_b, off_b) relative to frame A = (joint_a, off_a) of a tree model at the configuration q, as
+ * DDP_HIP_FLAG_RELATIVE_FRAME_COST defines it: p3 = R_a^T (p_b - p_a), quat4 the quaternion of R_a^T R_b (x y z w, w >= 0) and,
+ * where not NULL, J = [J_pos; R_b^T (W_b - W_a)] as 6 x nv column-major, the jacobian of r at e_rot = 0, formed by the traversal the
+ * cost kernels use (columns on both paths or on neither are 0).  joint_a == joint_b: DDP_HIP_E_ARG.  For targets such as "as the
+ * hands are now" */
+int ddp_hip_model_relative_frame(ddp_hip_model_handle* h, int32_t joint_a, const double off_a[3], int32_t joint_b, const double off_b[3],
+                                 const double* q, double* p3, double* quat4, double* J);
 
 /* ---- built-in seeded model tables (no URDF exists offline: SURVEY.md D4, 8d) -------------- */
 /* ..._FF: the same robots on a free-flyer root instead of a fixed base / 3 prismatic + 3 revolute base joints */
