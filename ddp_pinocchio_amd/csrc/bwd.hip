@@ -38,6 +38,8 @@ struct BwdParams {
   int32_t half_mode;         // 1: symmetric tensors with two-entry upper halves (static mode-2 stencil); 2: this context's analytic mode-1
                              // tensors -- no symmetry, the upper half of every f_xx / f_ux column and all of f_uu exact zeros
   int32_t packed;            // half_mode 1: the tensors are the stencil's packed records (lin_common.h: LinParams::pack)
+  const K3hUnit* units_half; // ... read in full units (bwd_split.h: bwd_contract_units), K3H_UNITS_PER_JOB per job; or null
+  int32_t njobs_units;
   const double *u, *ctrl_lo, *ctrl_hi;   // control bounds (DDP_HIP_FLAG_CONTROL_BOUNDS), else ctrl_lo / ctrl_hi null
   double* box_stat;
   int32_t has_tensors;
@@ -562,6 +564,9 @@ BwdParams make_params(ddp_hip_ctx* ctx, const SweepPlan& plan) {
   p.njobs_half = plan.half_mode ? ctx->njobs_half : 0;
   p.half_mode = plan.half_mode;
   p.packed = plan.packed ? 1 : 0;
+  const bool full_units = plan.half_mode == 1 && plan.packed && !ctx->sw.k3h_column_jobs;
+  p.units_half = full_units ? ctx->units_half_d : nullptr;
+  p.njobs_units = full_units ? ctx->njobs_units : 0;
   p.has_tensors = (ctx->flags & DDP_HIP_FLAG_NO_TENSORS) ? 0 : 1;
   return p;
 }
@@ -589,6 +594,7 @@ int enqueue_sweep_v2(ddp_hip_ctx* ctx, const BwdParams& p) {
   const int cn_max = ctx->cbx > ctx->cbu ? ctx->cbx : ctx->cbu;
   const size_t lds_c = sizeof(double) * (size_t)(NC + (NC + MC) * cn_max + 2 * (NC / 2 + 1) * MC);
   const size_t lds_h = sizeof(double) * (size_t)(NC + 3 * NC + 2 * (MC / 2 + 1) * NC);
+  const size_t lds_u = sizeof(double) * (size_t)(NC + K3H_UNITS_PER_JOB * NC + 2 * (MC / 2 + 1) * NC + 4 * NC);
   const size_t lds_5 = sizeof(double) * (size_t)(NC * NC + NC * (NC + MC) + NC + d.emax);
   const unsigned nblk5 = (unsigned)((NC + MC + CB5 - 1) / CB5);
   const unsigned B = (unsigned)d.batch;
@@ -599,7 +605,8 @@ int enqueue_sweep_v2(ddp_hip_ctx* ctx, const BwdParams& p) {
     prof_end(ctx, DDP_HIP_K_BWD_GAINS);
     if (p.has_tensors) {
       prof_begin(ctx, DDP_HIP_K_BWD_ASSEMBLE);
-      if (p.jobs_half && p.packed) hipLaunchKernelGGL((bwd_contract_half<NC, MC, true>), dim3((unsigned)p.njobs_half, B), dim3(BSF), lds_h, ctx->stream, p, t);
+      if (p.units_half) hipLaunchKernelGGL((bwd_contract_units<NC, MC, K3H_UNITS_PER_JOB>), dim3((unsigned)p.njobs_units, B), dim3(BSF), lds_u, ctx->stream, p, t);
+      else if (p.jobs_half && p.packed) hipLaunchKernelGGL((bwd_contract_half<NC, MC, true>), dim3((unsigned)p.njobs_half, B), dim3(BSF), lds_h, ctx->stream, p, t);
       else if (p.jobs_half) hipLaunchKernelGGL((bwd_contract_half<NC, MC, false>), dim3((unsigned)p.njobs_half, B), dim3(BSF), lds_h, ctx->stream, p, t);
       else hipLaunchKernelGGL((bwd_contract<NC, MC>), dim3((unsigned)ctx->njobs, B), dim3(BSF), lds_c, ctx->stream, p, t);
       prof_end(ctx, DDP_HIP_K_BWD_ASSEMBLE);
@@ -639,7 +646,7 @@ int launch_sweep_v2(ddp_hip_ctx* ctx, const BwdParams& p0) {
   // profiled sweeps take the direct path: events recorded by a graph's event-record nodes cannot be read back with
   // hipEventElapsedTime on this ROCm (hipErrorInvalidHandle -- tried)
   if (ctx->sw.bwd_no_graph || (ctx->profile_mask & bwd_mask)) return enqueue_sweep_v2<NC, MC, BOX>(ctx, p0);
-  const uint64_t key_misc = (uint64_t)p0.has_tensors | ((uint64_t)(p0.vx_trace != nullptr) << 1) | ((uint64_t)p0.sym_tensors << 2) | ((uint64_t)(p0.jobs_half != nullptr) << 3) | ((uint64_t)p0.half_mode << 4) | ((uint64_t)p0.packed << 8);
+  const uint64_t key_misc = (uint64_t)p0.has_tensors | ((uint64_t)(p0.vx_trace != nullptr) << 1) | ((uint64_t)p0.sym_tensors << 2) | ((uint64_t)(p0.jobs_half != nullptr) << 3) | ((uint64_t)p0.half_mode << 4) | ((uint64_t)p0.packed << 8) | ((uint64_t)(p0.units_half != nullptr) << 9);
   auto find = [&](const void* key_x) -> ddp_hip_ctx::BwdGraph* {
     for (auto& g : ctx->bwd_graph)
       if (g.exec && g.key_x == key_x && g.key_misc == key_misc) return &g;
@@ -745,12 +752,16 @@ int bwd_setup(ddp_hip_ctx* ctx) {
     HIP_TRY(hipMalloc(&ctx->jobs_sym_d, sizeof(BwdJob) * js.size()));
     HIP_TRY(hipMemcpy(ctx->jobs_sym_d, js.data(), sizeof(BwdJob) * js.size(), hipMemcpyHostToDevice));
     // K3h (bwd_contract_half): x-columns in pairs (3 units each), u-columns in groups of 6 (3 units), the rest in one
-    std::vector<BwdJob> jh;
-    for (int64_t c = 0; c < n; c += 2) jh.push_back(BwdJob{10, (int32_t)c, 2, 0});
-    for (int64_t c = 0; c < m; c += 6) jh.push_back(BwdJob{11, (int32_t)c, (int32_t)((m - c) < 6 ? (m - c) : 6), 0});
+    const std::vector<BwdJob> jh = k3h_column_jobs((int)n, (int)m);
     ctx->njobs_half = (int32_t)jh.size();
     HIP_TRY(hipMalloc(&ctx->jobs_half_d, sizeof(BwdJob) * jh.size()));
     HIP_TRY(hipMemcpy(ctx->jobs_half_d, jh.data(), sizeof(BwdJob) * jh.size(), hipMemcpyHostToDevice));
+    // ... and the packed K3h (bwd_contract_units): the same columns in full units (bwd_jobs.h)
+    std::vector<K3hUnit> us = k3h_full_units((int)n, (int)m);
+    if (!k3h_units_in_bounds(us, (int)n, (int)m)) return DDP_HIP_E_ARG;
+    ctx->njobs_units = k3h_pad_to_jobs(us, K3H_UNITS_PER_JOB);
+    HIP_TRY(hipMalloc(&ctx->units_half_d, sizeof(K3hUnit) * us.size()));
+    HIP_TRY(hipMemcpy(ctx->units_half_d, us.data(), sizeof(K3hUnit) * us.size(), hipMemcpyHostToDevice));
   }
   return DDP_HIP_OK;
 }
@@ -769,6 +780,7 @@ void bwd_teardown(ddp_hip_ctx* ctx) {
   if (ctx->jobs_d) (void)hipFree(ctx->jobs_d);
   if (ctx->jobs_sym_d) (void)hipFree(ctx->jobs_sym_d);
   if (ctx->jobs_half_d) (void)hipFree(ctx->jobs_half_d);
+  if (ctx->units_half_d) (void)hipFree(ctx->units_half_d);
 }
 
 // The sweep's LDS against the 160 KB of a gfx950 workgroup, on the host: bwd_gains holds Q_uu, [k | K] and Q_ux, which fits up to

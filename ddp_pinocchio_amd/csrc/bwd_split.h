@@ -6,7 +6,9 @@
 //       always in flight; 0.25 flop/byte.
 //   K3h bwd_contract_half<N, M>  the same contraction for tensors with known structure: reads only what is not known
 //       in advance (below).
-//   Both add C to the Q workspace, which already holds every other term of Q (K5, bwd_v2.h).
+//   K3h on full units  bwd_contract_units<N, M, UPJ>  K3h for the stencil's packed records, on a job list without empty
+//       column slots (bwd_jobs.h; at the end of this file).
+//   All add C to the Q workspace, which already holds every other term of Q (K5, bwd_v2.h).
 #pragma once
 
 template <int N, int M>
@@ -310,5 +312,156 @@ __global__ __launch_bounds__(BSF, BWD_WAVES_PER_SIMD) void bwd_contract_half(Bwd
     const double v = s_out[tid];
     *dst = old_d + v;
     if (dm) *dm = old_m + v;
+  }
+}
+
+// ---- K3h on full units: the packed records of the symmetric tensors (half_mode 1), bwd_jobs.h's list ------------------------
+// bwd_contract_half<N, M, true> gives every slab of f_xx / f_uu a unit of its own, and of slab c only the columns j >= c are
+// needed: at (76, 38) 35 % of its column slots load nothing and still take their share of a barrier and a reduction.  Here a
+// unit is a short list of RUNS -- cnt consecutive records of one slab -- whose columns fill the N slots one after another
+// (bwd_jobs.h: k3h_full_units pairs the tails so that they do): 87 units instead of 133, 29 workgroups per instance instead of 45.
+// A record is HP + 1 f64x2 words, [top0 top1 | rows M .. N-1], and a run is contiguous, so the lanes walk a unit word by word --
+// (HP + 1) N <= R BSF words -- and the tops word comes with the same loads as the rows (it goes to the column's lane through LDS).
+// The sums are bwd_contract_half's: a column's upper-half partials in bwd_contract's order, then its HP two-term partials with
+// ip ascending, in one lane; which unit a column rides in changes nothing in them.  Every (tensor, slab, column) is in exactly
+// one run (host/test_k3h_jobs.cpp), so one lane owns its entry of Q and the mirror entry.
+template <int N, int M, int UPJ>
+__global__ __launch_bounds__(BSF, BWD_WAVES_PER_SIMD) void bwd_contract_units(BwdParams p, int64_t t) {
+  int b, jb;
+  {
+    const int njobs = (int)gridDim.x, B = (int)gridDim.y;
+    const int lin = blockIdx.y * njobs + blockIdx.x;
+    if ((B & 7) == 0) {
+      const int xcd = lin & 7, k = lin >> 3;
+      b = xcd + 8 * (k / njobs);
+      jb = k % njobs;
+    } else { b = blockIdx.y; jb = blockIdx.x; }
+  }
+  if (p.status[b] != 0) return;
+  constexpr int n = N, m = M;
+  static_assert(N == 2 * M && M % 2 == 0, "lower halves of M rows, in row pairs");
+  using HS = HalfShape<N, M>;
+  constexpr int W = HS::HP + 1;                      // f64x2 words of a record
+  constexpr int R = (W * N + BSF - 1) / BSF;         // loads per lane and unit
+  static_assert(UPJ * N <= BSF, "one output entry per lane");
+  const K3hUnit* units = p.units_half + (int64_t)jb * UPJ;
+  const int64_t T = p.d.T;
+  const int tid = threadIdx.x;
+  const int64_t bt = (int64_t)b * T + t;
+  const double* Vx = p.ws_V + (int64_t)b * (n + n * n);
+  double* C = p.ws_Q + (int64_t)b * (n + m + n * n + m * n + m * m) + n + m;   // Q_xx | Q_ux | Q_uu, holding what K5 left
+  constexpr int OXX = 0, OUX = n * n, OUU = n * n + m * n;
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  double* s_v = smem;                          // n
+  double* s_out = s_v + n;                     // units x N
+  double* s_p0 = s_out + UPJ * N;              // HS::LD * N
+  double* s_p1 = s_p0 + HS::LD * N;
+  f64x2* s_t0 = reinterpret_cast<f64x2*>(s_p1 + HS::LD * N);   // N tops words
+  f64x2* s_t1 = s_t0 + N;
+  // first word of a run's first record
+  auto run_base = [&](const K3hRun& r) -> const f64x2* {
+    const double* slab = r.tensor == K3H_FXX ? p.fxx + (bt * n + r.slab) * (int64_t)(n * n)
+                       : r.tensor == K3H_FUX ? p.fux + (bt * n + r.slab) * (int64_t)(n * m)
+                                             : p.fuu + (bt * m + r.slab) * (int64_t)(n * m);
+    return reinterpret_cast<const f64x2*>(slab + (int64_t)r.j0 * (M + 2));
+  };
+  f64x2 buf[UPJ][R];
+#pragma unroll
+  for (int u = 0; u < UPJ; ++u) {
+    const K3hUnit un = units[u];
+    // word f of the unit is word f - e_k of run k
+    const int e1 = W * un.run[0].cnt, e2 = e1 + W * un.run[1].cnt, e3 = e2 + W * un.run[2].cnt, e4 = e3 + W * un.run[3].cnt;
+    const f64x2 *b0 = run_base(un.run[0]), *b1 = run_base(un.run[1]) - e1, *b2 = run_base(un.run[2]) - e2, *b3 = run_base(un.run[3]) - e3;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int f = tid + r * BSF;
+      const int k = (f >= e1) + (f >= e2) + (f >= e3);
+      const f64x2* src = (k == 0 ? b0 : k == 1 ? b1 : k == 2 ? b2 : b3) + f;
+      const int tensor = k == 0 ? un.run[0].tensor : k == 1 ? un.run[1].tensor : k == 2 ? un.run[2].tensor : un.run[3].tensor;
+      // (f_uu: its directions are controls, the upper half is all zeros and its tops word is not read)
+      const bool need = f < e4 && !(tensor == K3H_FUU && f % W == 0);
+      if (need) buf[u][r] = BWD_NT ? __builtin_nontemporal_load(src) : *src;
+      else buf[u][r] = f64x2{0.0, 0.0};
+    }
+  }
+  // this lane's output entry (UPJ * N <= BSF: one per lane) and what the workspace holds there (the dense terms K5 left),
+  // requested now so that the read-modify-write at the end does not wait for a round trip of its own
+  int dst = -1, dm = -1;
+  double old_d = 0.0, old_m = 0.0;
+  if (tid < UPJ * N) {
+    const int u = tid / N, jj = tid - u * N;
+    const K3hCol c = k3h_col(units[u], jj);
+    if (c.need) {
+      if (c.tensor == K3H_FUX) dst = OUX + c.j + c.slab * m;
+      else {
+        const int o = c.tensor == K3H_FXX ? OXX : OUU, ld = c.tensor == K3H_FXX ? n : m;
+        dst = o + c.j + c.slab * ld;
+        if (c.j > c.slab) dm = o + c.slab + c.j * ld;
+      }
+      old_d = C[dst];
+      if (dm >= 0) old_m = C[dm];
+    }
+  }
+  for (int i = tid; i < n; i += BSF) s_v[i] = Vx[i];
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < UPJ; ++u) {
+    double* sp = (u & 1) ? s_p1 : s_p0;
+    f64x2* st = (u & 1) ? s_t1 : s_t0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int f = tid + r * BSF;
+      if (r < R - 1 || f < W * N) {
+        const int jj = f / W, w = f - jj * W;
+        if (w == 0) st[jj] = buf[u][r];
+        else {
+          const int ip = w - 1;
+          const f64x2 vv = *reinterpret_cast<const f64x2*>(s_v + M + 2 * ip);
+          sp[jj * HS::LD + ip] = vv.x * buf[u][r].x + vv.y * buf[u][r].y;
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < n) {
+      const K3hCol c = k3h_col(units[u], tid);
+      const int slab = c.slab, j = c.j;
+      const bool xcol = c.tensor == K3H_FXX;
+      double sacc = 0.0;
+      if (c.need && c.tensor != K3H_FUU) {
+        const f64x2 tw = st[tid];
+        double top[2];
+        top[0] = tw.x;                                                  // the slab's direction is an x direction (f_xx and f_ux)
+        top[1] = 0.0;
+        if (xcol && (j % M) != (slab % M)) top[1] = tw.y;               // (else: never written)
+        // the upper half's partials, in bwd_contract's order: row pair (2 ip, 2 ip + 1), ip ascending; all others are zeros
+        const int ra = slab % M, rb = xcol ? j % M : ra;
+        const int lo = ra < rb ? ra : rb, hi = ra < rb ? rb : ra;
+        const double tlo = ra <= rb ? top[0] : top[1], thi = ra <= rb ? (ra == rb ? 0.0 : top[1]) : top[0];
+        if (lo == hi) {
+          const int e = lo & ~1;
+          const f64x2 vv = *reinterpret_cast<const f64x2*>(s_v + e);
+          const double tx = (lo & 1) ? 0.0 : tlo, ty = (lo & 1) ? tlo : 0.0;
+          sacc += vv.x * tx + vv.y * ty;
+        } else if ((lo >> 1) == (hi >> 1)) {
+          const f64x2 vv = *reinterpret_cast<const f64x2*>(s_v + lo);      // lo even, hi = lo + 1
+          sacc += vv.x * tlo + vv.y * thi;
+        } else {
+          const f64x2 va = *reinterpret_cast<const f64x2*>(s_v + (lo & ~1));
+          const f64x2 vb = *reinterpret_cast<const f64x2*>(s_v + (hi & ~1));
+          sacc += va.x * ((lo & 1) ? 0.0 : tlo) + va.y * ((lo & 1) ? tlo : 0.0);
+          sacc += vb.x * ((hi & 1) ? 0.0 : thi) + vb.y * ((hi & 1) ? thi : 0.0);
+        }
+      }
+      const double* pj = sp + tid * HS::LD;
+#pragma unroll
+      for (int k = 0; k < HS::HP; ++k) sacc += pj[k];
+      s_out[u * N + tid] = sacc;
+    }
+  }
+  __syncthreads();
+  if (dst >= 0) {
+    const double v = s_out[tid];
+    C[dst] = old_d + v;
+    if (dm >= 0) C[dm] = old_m + v;
   }
 }

@@ -6,6 +6,7 @@
 
 #include <vector>
 
+#include "bwd_jobs.h"
 #include "cost_block.h"
 #include "ddp_hip/ddp_hip.h"
 
@@ -56,12 +57,6 @@ struct SeqBuf {
   int64_t size = 0;        // per-instance element count
 };
 
-struct BwdJob {
-  int32_t kind;   // 0: x-columns (Q_xx, Q_ux, Q_x), 1: u-columns (Q_uu, Q_u)
-  int32_t c0, cn;
-  int32_t pad_;
-};
-
 // Development switches (DDP_HIP_*), read once by ddp_hip_create (lin_plan.cpp: read_switches): a context
 // keeps the paths it was created with.  A tuning knob of 0 is unset (or out of its range): the context's own choice holds.
 struct DevSwitches {
@@ -69,6 +64,7 @@ struct DevSwitches {
   bool k3_no_sym = false;      // K3_NO_SYM: K3 reads every half-slab (and the static stencil writes the mirror images)
   bool k3_no_half = false;     // K3_NO_HALF: no K3h
   bool k3_no_pack = false;     // K3_NO_PACK: the static stencil writes the contract layout, K3h reads it strided (no packed records)
+  bool k3h_column_jobs = false;   // K3H_COLUMN_JOBS: the packed K3h on the column jobs of the strided one (133 units per instance), not on full units
   bool fxx_full = false;       // FXX_FULL: the static stencil writes the configuration rows and the mirror images
   bool no_static = false;      // NO_STATIC: the generic level kernels instead of the static-topology ones
   bool no_qcache = false;      // NO_QCACHE: no configuration caches
@@ -219,6 +215,8 @@ struct ddp_hip_ctx {
   BwdJob* jobs_d = nullptr;
   BwdJob* jobs_half_d = nullptr;  // K3h's job list (bwd_split.h: bwd_contract_half)
   int32_t njobs_half = 0;
+  K3hUnit* units_half_d = nullptr;   // the packed K3h's full units (bwd_jobs.h), K3H_UNITS_PER_JOB per job
+  int32_t njobs_units = 0;
   TensorState tensors;            // what FXX / FUX / FUU hold
   BwdJob* jobs_sym_d = nullptr;   // K3's job list for symmetric tensors (bwd_split.h, job kind 2)
   int32_t njobs = 0;

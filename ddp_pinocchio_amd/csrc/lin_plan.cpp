@@ -16,6 +16,7 @@ DevSwitches read_switches() {
   sw.k3_no_sym = on("DDP_HIP_K3_NO_SYM");
   sw.k3_no_half = on("DDP_HIP_K3_NO_HALF");
   sw.k3_no_pack = on("DDP_HIP_K3_NO_PACK");
+  sw.k3h_column_jobs = on("DDP_HIP_K3H_COLUMN_JOBS");
   sw.fxx_full = on("DDP_HIP_FXX_FULL");
   sw.no_static = on("DDP_HIP_NO_STATIC");
   sw.no_qcache = on("DDP_HIP_NO_QCACHE");
