@@ -33,6 +33,7 @@ FLAG_OBSTACLE_COST = 512
 FLAG_SELF_COLLISION_COST = 1024
 FLAG_MOMENTUM_COST = 2048
 FLAG_RELATIVE_FRAME_COST = 4096
+FLAG_CONTROL_GRAV_COST = 8192
 MAX_COST_FRAMES = 4
 MAX_COLLISION_POINTS, MAX_OBSTACLES = 16, 8
 MAX_COLLISION_PAIRS = 32
@@ -77,6 +78,7 @@ EXPORTS = [
     "ddp_hip_momentum_cost_upload", "ddp_hip_momentum_cost_download", "ddp_hip_model_centroidal_momentum",
     "ddp_hip_relative_frame_set_pairs", "ddp_hip_relative_frame_upload", "ddp_hip_relative_frame_download",
     "ddp_hip_relative_frame_error", "ddp_hip_model_relative_frame",
+    "ddp_hip_control_grav_cost_upload", "ddp_hip_control_grav_cost_download", "ddp_hip_model_gravity_torque",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -194,6 +196,10 @@ def lib():
         L.ddp_hip_relative_frame_download.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_relative_frame_error.argtypes = [C.c_void_p, C.c_int, _dp]
         L.ddp_hip_model_relative_frame.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp]
+    if hasattr(L, "ddp_hip_control_grav_cost_upload"):  # (likewise: set_control_grav_cost and ModelHandle.gravity_torque)
+        L.ddp_hip_control_grav_cost_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_control_grav_cost_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_model_gravity_torque.argtypes = [C.c_void_p, _dp, _dp, _dp]
     L.ddp_hip_rollout.argtypes = [C.c_void_p]
     L.ddp_hip_linearize.argtypes = [C.c_void_p]
     L.ddp_hip_linearize_stages.argtypes = [C.c_void_p, C.c_uint32]
@@ -393,6 +399,15 @@ class ModelHandle:
         _check(lib().ddp_hip_model_relative_frame(self._h, int(joint_a), _ptr(off_a), int(joint_b), _ptr(off_b), _ptr(q), _ptr(p3), _ptr(qt),
                                                   _ptr(J) if jacobian else None), "model_relative_frame")
         return (p3, qt, J.reshape(self.nv, 6).T.copy()) if jacobian else (p3, qt)
+
+    def gravity_torque(self, q, jacobian=False):
+        """The generalised gravity torque g(q) of a tree model as (nv,): the control that holds the robot at rest, aba(q, 0, g) = 0,
+        as FLAG_CONTROL_GRAV_COST defines it (ddp_hip.h); with jacobian=True (g, G), G = dg / d(delta q) as (nv, nv).  A
+        free-flyer root's six rows are returned as well.  For targets and warm starts: "start from U = g(q0)" """
+        q = _f64(q)
+        g, G = np.zeros(self.nv), np.zeros(self.nv * self.nv)
+        _check(lib().ddp_hip_model_gravity_torque(self._h, _ptr(q), _ptr(g), _ptr(G) if jacobian else None), "model_gravity_torque")
+        return (g, G.reshape(self.nv, self.nv).T.copy()) if jacobian else g
 
 
 
@@ -632,6 +647,20 @@ class Context:
         """(target, weight) of instances first .. first + count - 1, each (count, T+1, 6)"""
         per = (self.spec.T + 1, 6)
         return self._cost_download(lib().ddp_hip_momentum_cost_download, "momentum_cost_download", (per, per), first, count)
+
+    def set_control_grav_cost(self, offset=None, weight=None, first=0, count=None):
+        """The control-gravity terms of instances first .. first + count - 1 (a context created with FLAG_CONTROL_GRAV_COST;
+        ddp_hip.h): 1/2 sum_j w_j (u_j - g_j(q) - o_j)^2 at t < T.  offset, weight: (T, m) for every instance of the range or
+        (count, T, m) with one per instance; both also take (m,) and scalars by broadcast.  weight >= 0, and 0 on a free-flyer
+        root's six rows.  None leaves that side as it is."""
+        per, extra = (self.spec.T, self.spec.m), ((self.spec.m,), ())
+        count, arrs = self._cost_sides("set_control_grav_cost", (("offset", offset, per, extra), ("weight", weight, per, extra)), first, count)
+        self._cost_upload(lib().ddp_hip_control_grav_cost_upload, "control_grav_cost_upload", arrs, first, count)
+
+    def control_grav_cost(self, first=0, count=None):
+        """(offset, weight) of instances first .. first + count - 1, each (count, T, m)"""
+        per = (self.spec.T, self.spec.m)
+        return self._cost_download(lib().ddp_hip_control_grav_cost_download, "control_grav_cost_download", (per, per), first, count)
 
     def set_relative_frame_pairs(self, pairs):
         """The frame pairs [((joint_a, off_a), (joint_b, off_b)), ...] (1 .. MAX_FRAME_PAIRS of them, the two frames of a pair on

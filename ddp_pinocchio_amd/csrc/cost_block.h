@@ -8,38 +8,47 @@
 
 #include "ddp_hip/ddp_hip.h"
 
-// The terms, in the order the kernels add them (after the stage cost and the tracking cost): lin.hip launches one kernel per
-// live term in this order, fwd.hip forms the first three inline and the others in kernels of their own, in this order: frame
-// positions, frame orientations, limits, CoM, frame velocities, momentum, relative frames, obstacles, self-collision
-enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_LIMITS, COST_COM, COST_FRAME_VEL, COST_MOMENTUM, COST_RELATIVE_FRAME, COST_OBSTACLE,
-                          COST_SELF_COLLISION, COST_COUNT };
+// The terms.  The order in which the kernels add them (after the stage cost and the tracking cost) is stated where they are launched:
+// lin.hip launches one kernel per live term, fwd.hip forms the first three inline and walks kAddOn for the others, both in the order
+// frame positions, frame orientations, limits, CoM, frame velocities, momentum, relative frames, control-gravity, obstacles,
+// self-collision.  The enumerators are indices of ctx->cost[] and kCostDesc[] and follow that order but for COST_CONTROL_GRAV: the
+// host programs hold momentum, relative frames, obstacles and self-collision as neighbours and self-collision as the last
+// (host/test_relative_frame_block.cpp, host/test_self_collision_block.cpp), so the term whose additions come between the relative
+// frames' and the obstacles' has its index in front of that run
+enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_LIMITS, COST_COM, COST_FRAME_VEL, COST_CONTROL_GRAV, COST_MOMENTUM, COST_RELATIVE_FRAME,
+                          COST_OBSTACLE, COST_SELF_COLLISION, COST_COUNT };
 
 enum CostFill : int32_t { FILL_ZERO, FILL_NEG_INF, FILL_POS_INF, FILL_QUAT };   // FILL_QUAT: identity quaternions (0, 0, 0, 1)
 
 #define COST_MAX_SIDES 3
+#define COST_ITEMS_STATE 0          // CostDesc::max_items: one item per tangent row of the state, n
+#define COST_ITEMS_CONTROL (-1)     // ... one item per control row, m
 
-// What a term is made of.  A side is one array [batch][T+1][items][unit]; the last side is the weights
+// What a term is made of.  A side is one array [batch][rows][items][unit], rows = T+1 (t = 0 .. T), or T for a term of the
+// stages alone (stage_only: t = 0 .. T-1, no terminal row); the last side is the weights
 struct CostDesc {
   uint32_t flag;                    // the creation flag that enables the term
   int32_t nside;
   int32_t unit[COST_MAX_SIDES];     // doubles per item
   int32_t fill[COST_MAX_SIDES];     // CostFill: what a side holds at create and after a change of layout
-  int32_t max_items;                // items the arrays have room for; 0: the tangent dimension n (CostBlock::max_items, set at create)
+  int32_t max_items;                // items the arrays have room for; COST_ITEMS_STATE / COST_ITEMS_CONTROL: n / m (CostBlock::max_items, set at create)
   bool fixed;                       // laid out at create for max_items; else by the frames / slots set, up to max_items
   bool cand;                        // the term has a candidates' array for the line search
+  bool stage_only;                  // a term of l(t, x, u), t < T, alone: T rows per instance, not T+1 (a term that reads u has no row at T)
 };
 
 static const CostDesc kCostDesc[COST_COUNT] = {
-    // flag, sides, doubles per item, fill, room, fixed, cand
-    {DDP_HIP_FLAG_FRAME_COST, 2, {3, 3, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, false},          // target | weight, per frame
-    {DDP_HIP_FLAG_FRAME_ORIENT_COST, 2, {4, 3, 0}, {FILL_QUAT, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, false},   // quat | weight, per frame
-    {DDP_HIP_FLAG_STATE_LIMITS, 3, {1, 1, 1}, {FILL_NEG_INF, FILL_POS_INF, FILL_ZERO}, 0, true, false},                 // lo | hi | weight, per tangent row
-    {DDP_HIP_FLAG_COM_COST, 2, {3, 3, 0}, {FILL_ZERO, FILL_ZERO, 0}, 1, true, true},                                    // target | weight
-    {DDP_HIP_FLAG_FRAME_VEL_COST, 2, {6, 6, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, true},       // target | weight, per frame
-    {DDP_HIP_FLAG_MOMENTUM_COST, 2, {6, 6, 0}, {FILL_ZERO, FILL_ZERO, 0}, 1, true, true},                               // target | weight
-    {DDP_HIP_FLAG_RELATIVE_FRAME_COST, 3, {3, 4, 6}, {FILL_ZERO, FILL_QUAT, FILL_ZERO}, DDP_HIP_MAX_FRAME_PAIRS, false, true},   // target | quat | weight, per pair
-    {DDP_HIP_FLAG_OBSTACLE_COST, 2, {4, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_OBSTACLES, false, true},          // geom | weight, per slot
-    {DDP_HIP_FLAG_SELF_COLLISION_COST, 2, {1, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COLLISION_PAIRS, false, true},   // margin | weight, per pair
+    // flag, sides, doubles per item, fill, room, fixed, cand, stage_only
+    {DDP_HIP_FLAG_FRAME_COST, 2, {3, 3, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, false, false},          // target | weight, per frame
+    {DDP_HIP_FLAG_FRAME_ORIENT_COST, 2, {4, 3, 0}, {FILL_QUAT, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, false, false},   // quat | weight, per frame
+    {DDP_HIP_FLAG_STATE_LIMITS, 3, {1, 1, 1}, {FILL_NEG_INF, FILL_POS_INF, FILL_ZERO}, 0, true, false, false},                 // lo | hi | weight, per tangent row
+    {DDP_HIP_FLAG_COM_COST, 2, {3, 3, 0}, {FILL_ZERO, FILL_ZERO, 0}, 1, true, true, false},                                    // target | weight
+    {DDP_HIP_FLAG_FRAME_VEL_COST, 2, {6, 6, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, true, false},       // target | weight, per frame
+    {DDP_HIP_FLAG_CONTROL_GRAV_COST, 2, {1, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, COST_ITEMS_CONTROL, true, true, true},              // offset | weight, per control row, t < T
+    {DDP_HIP_FLAG_MOMENTUM_COST, 2, {6, 6, 0}, {FILL_ZERO, FILL_ZERO, 0}, 1, true, true, false},                               // target | weight
+    {DDP_HIP_FLAG_RELATIVE_FRAME_COST, 3, {3, 4, 6}, {FILL_ZERO, FILL_QUAT, FILL_ZERO}, DDP_HIP_MAX_FRAME_PAIRS, false, true, false},   // target | quat | weight, per pair
+    {DDP_HIP_FLAG_OBSTACLE_COST, 2, {4, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_OBSTACLES, false, true, false},          // geom | weight, per slot
+    {DDP_HIP_FLAG_SELF_COLLISION_COST, 2, {1, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COLLISION_PAIRS, false, true, false},   // margin | weight, per pair
 };
 
 // One term of one context
@@ -52,8 +61,9 @@ struct CostBlock {
   bool live = false;                // some non-zero weight is resident: the kernels form the term (cost_live_rule)
 };
 
-// doubles of side s per instance, as laid out now
-static inline int64_t cost_side_words(const CostBlock& k, int s, int64_t T) { return (T + 1) * (int64_t)k.items * k.desc->unit[s]; }
+// rows of a side per instance, and doubles of side s per instance, as laid out now
+static inline int64_t cost_rows(const CostBlock& k, int64_t T) { return k.desc->stage_only ? T : T + 1; }
+static inline int64_t cost_side_words(const CostBlock& k, int s, int64_t T) { return cost_rows(k, T) * (int64_t)k.items * k.desc->unit[s]; }
 
 // What the validators of one upload know beside the values
 struct CostCheck {
@@ -106,7 +116,8 @@ static inline bool cost_limit_hi_side(const CostCheck&, const double* v, int64_t
     if (isnan(v[i]) || v[i] == -INFINITY) return false;
   return true;
 }
-// ... and its weights: a free-flyer root's pose rows carry no limit
+// ... and its weights: a free-flyer root's pose rows carry no limit.  (The control-gravity term's weights alike, with one item per
+// control row: a free-flyer root's six rows carry no term)
 static inline bool cost_limit_weight_side(const CostCheck& c, const double* v, int64_t words) {
   for (int64_t i = 0; i < words; ++i) {
     if (!cost_weight_ok(v[i])) return false;

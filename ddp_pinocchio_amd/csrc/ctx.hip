@@ -217,7 +217,7 @@ static int fill_device(ddp_hip_ctx* ctx, double* p, int64_t n, double v) {
 // the term off, laid out by `items`.  ddp_hip_create, and the set_frames / set_points entry points when the layout changes
 static int cost_block_setup(ddp_hip_ctx* ctx, int term, int32_t items) {
   CostBlock& k = ctx->cost[term];
-  const int64_t slots = ctx->d.batch * (ctx->d.T + 1) * k.max_items;
+  const int64_t slots = ctx->d.batch * cost_rows(k, ctx->d.T) * k.max_items;
   for (int s = 0; s < k.desc->nside; ++s) {
     const int64_t words = slots * k.desc->unit[s];
     const int fill = k.desc->fill[s];
@@ -251,6 +251,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   if ((flags & DDP_HIP_FLAG_OBSTACLE_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // collision points are points of a tree's joints
   if ((flags & DDP_HIP_FLAG_SELF_COLLISION_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the spheres alike
   if ((flags & DDP_HIP_FLAG_RELATIVE_FRAME_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the frame pairs alike
+  if ((flags & DDP_HIP_FLAG_CONTROL_GRAV_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // g(q) is of a tree's bodies
   if (flags & (DDP_HIP_FLAG_COM_COST | DDP_HIP_FLAG_MOMENTUM_COST)) {
     if (mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the CoM, and the momentum about it, are of a tree's bodies
     if (!mo.mass_j || !mo.jtype) return DDP_HIP_E_ARG;
@@ -359,10 +360,11 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipStreamSynchronize(ctx->stream));
   }
   for (int term = 0; term < COST_COUNT; ++term) {
-    // frames, frame pairs, obstacle slots and self-collision pairs: no layout until they are set; limits (lo = -inf, hi = +inf, w = 0: no limit anywhere), CoM and momentum: fixed
+    // frames, frame pairs, obstacle slots and self-collision pairs: no layout until they are set; limits (lo = -inf, hi = +inf, w = 0: no limit anywhere), CoM, momentum
+    // and control-gravity (one item per control row, T rows): fixed
     CostBlock& k = ctx->cost[term];
     k.desc = &kCostDesc[term];
-    k.max_items = k.desc->max_items ? k.desc->max_items : (int32_t)d.n;
+    k.max_items = k.desc->max_items == COST_ITEMS_STATE ? (int32_t)d.n : k.desc->max_items == COST_ITEMS_CONTROL ? (int32_t)d.m : k.desc->max_items;
     if (!(flags & k.desc->flag)) continue;
     const int rc_ = cost_block_setup(ctx, term, k.desc->fixed ? k.max_items : 0);
     if (rc_ != DDP_HIP_OK) { ddp_hip_destroy(ctx); return rc_; }
@@ -738,6 +740,17 @@ extern "C" int ddp_hip_relative_frame_upload(ddp_hip_ctx* ctx, const double* tar
 extern "C" int ddp_hip_relative_frame_download(ddp_hip_ctx* ctx, double* target, double* quat, double* weight, int64_t first, int64_t count) {
   double* host[] = {target, quat, weight};
   return cost_block_download(ctx, COST_RELATIVE_FRAME, host, first, count);
+}
+
+// an offset and a weight per (instance, t < T, control row): the record's rows are T (CostDesc::stage_only), the public shape
+extern "C" int ddp_hip_control_grav_cost_upload(ddp_hip_ctx* ctx, const double* offset, const double* weight, int64_t first, int64_t count) {
+  const double* host[] = {offset, weight};
+  const CostSideOk ok[] = {cost_finite_side, cost_limit_weight_side};   // (a free-flyer root's six rows carry no term)
+  return cost_block_upload(ctx, COST_CONTROL_GRAV, host, ok, first, count);
+}
+extern "C" int ddp_hip_control_grav_cost_download(ddp_hip_ctx* ctx, double* offset, double* weight, int64_t first, int64_t count) {
+  double* host[] = {offset, weight};
+  return cost_block_download(ctx, COST_CONTROL_GRAV, host, first, count);
 }
 
 extern "C" int ddp_hip_com_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first, int64_t count) {

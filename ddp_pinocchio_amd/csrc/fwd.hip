@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "com_cost.h"
+#include "control_grav_cost.h"
 #include "frame_cost.h"
 #include "frame_vel_cost.h"
 #include "internal.h"
@@ -808,7 +809,7 @@ __global__ void cand_sum_kernel(FwdParams p) {
   p.fw_dcost[(int64_t)b * na + a] = dsum;
 }
 
-// The add-on cost kernels below (CoM, frame velocities, momentum, relative frames, obstacles) run over a list of `count` (trajectory, t) pairs, t = 0 .. T,
+// The add-on cost kernels below (CoM, frame velocities, momentum, relative frames, control-gravity, obstacles) run over a list of `count` (trajectory, t) pairs, t = 0 .. T,
 // `na` trajectories per instance.  Pair e: which trajectory, which t, whose instance, which block bt1 = b (T+1) + t of the term's
 // data.  skip: nothing is written for this pair (past the list, or a candidate the rollout kernels skip: state != 0, beyond
 // 2^-33; state == nullptr: a resident trajectory, none is skipped).  live: the pair is evaluated (the kernels narrow it further)
@@ -1010,6 +1011,57 @@ __global__ __launch_bounds__(64) void relative_frame_error_kernel(RelativeFrameD
   rbd::RelativePlacement P;
   rbd::relative_placement(m, m.ff != 0, rf.ja[i], rf.offa[i], rf.jb[i], rf.offb[i], xs + bt1 * nx, true, P);
   rbd::relative_frame_residual(P, rf.target + e * 3, rf.quat + e * 4, out + e * 6);
+}
+
+// The control-gravity terms (DDP_HIP_FLAG_CONTROL_GRAV_COST, ddp_hip.h) of a list of states and their controls, added on top like
+// the CoM terms above: the same list, the same two uses (add != 0: out[pair] += term behind cost_kernel; add == 0: out[pair] = term,
+// its candidates' array in a line-search round, with the candidates the rollout kernels skip skipped here).  us: the controls that
+// belong to xs, trajectory k's at us + k u_stride (U, U_NEW, or the candidates' fw_u: the controls the rollout applied, clamped
+// where there are bounds).  `lpe` lanes (a power of two >= the joint count) cooperate on one evaluation, 64 / lpe per wave: lane
+// j walks joint j's path once with its axis, its origin and its body's first moment (rbd::grav_value_stage: no jacobian, no
+// scratch) and leaves mass, m_j p_j and the path in LDS; after the barrier lane j forms the sums of its subtree over the records in
+// ascending order, g_j, and w_j r_j^2 with r_j = u_j - g_j - o_j; the group's first lane adds the rows' terms in ascending order.
+// A term of weight 0 is left out (a free-flyer root's six rows always), and with all m of them the walk; t = T has no control and
+// no term: such a pair adds nothing (add != 0) or stores +0 (add == 0).  A non-finite state gives a NaN term, as com_cost_kernel's does
+__global__ __launch_bounds__(64) void control_grav_cost_kernel(ControlGravDev cg, const DevModel* model, const double* xs, int64_t traj_stride,
+                                                               int64_t count, int32_t T1, int32_t nx, int32_t na, int32_t lpe, const double* us,
+                                                               int64_t u_stride, const int32_t* state, int32_t round, double* out, int32_t add) {
+  __shared__ double s_m[64], s_mp[64 * 3], s_term[64];
+  __shared__ unsigned long long s_mask[64];
+  __shared__ int32_t s_formed[64];
+  const DevModel& m = *model;
+  const bool ff = m.ff != 0;
+  const int tid = threadIdx.x, g = tid / lpe, j = tid % lpe, base = tid - j, mu = m.nv;
+  const int64_t e = (int64_t)blockIdx.x * (64 / lpe) + g;
+  const CostPair pr = cost_pair_decode(e, count, T1, na, state, round);
+  const int t = pr.t, T = T1 - 1;
+  const int64_t bt = pr.b * T + t;                       // the record's rows are t < T
+  bool live = pr.live && t < T;
+  if (live && !rbd::weights_any(cg.weight + bt * mu, mu)) live = false;
+  rbd::GravLane own;
+  if (live && j < m.nj)
+    rbd::grav_value_stage(m, ff, j, xs + pr.traj * traj_stride + (int64_t)t * nx, s_m + tid, s_mp + 3 * tid, s_mask + tid, own);
+  __syncthreads();
+  double term = 0.0;
+  bool formed = false;
+  if (live && j < m.nj && !(ff && j == 0)) {
+    const int i = ff ? j + 5 : j;                        // the control row of joint j
+    const double wi = cg.weight[bt * mu + i];
+    if (wi != 0.0) {
+      const double r = us[pr.traj * u_stride + (int64_t)t * mu + i] - rbd::grav_value_joint(m, j, s_m + base, s_mp + 3 * base, s_mask + base, own) -
+                       cg.offset[bt * mu + i];
+      term = wi * r * r;
+      formed = true;
+    }
+  }
+  s_term[tid] = term;
+  s_formed[tid] = formed ? 1 : 0;
+  __syncthreads();
+  if (j != 0 || pr.skip) return;
+  double acc = 0.0;
+  for (int i = 0; i < m.nj; ++i)
+    if (s_formed[tid + i]) acc += s_term[tid + i];
+  cost_pair_store(out, e, 0.5 * acc, live, add);
 }
 
 // The obstacle terms (DDP_HIP_FLAG_OBSTACLE_COST, ddp_hip.h) of a list of states, added on top like the frame-velocity terms above:
@@ -1332,8 +1384,10 @@ extern "C" int ddp_hip_rollout(ddp_hip_ctx* ctx) {
     else LAUNCH(0, false);                                     \
   } while (0)
 
-// The add-on kernels over `count` (trajectory, t) pairs of trajectories laid out like X (na per instance): one signature
-typedef void (*AddOnLaunch)(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add);
+// The add-on kernels over `count` (trajectory, t) pairs of trajectories laid out like X (na per instance): one signature.  us: the
+// controls that belong to xs, laid out like U (trajectory k's at us + k T m: U, U_NEW or the candidates' fw_u); the terms of the
+// state alone ignore them
+typedef void (*AddOnLaunch)(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add);
 
 // ... and one launch: one wave per `lanes`-lane group of pairs, the kernel's view `dev` of its term first; mid: what a kernel takes
 // between na and state (com_cost_kernel's lanes per evaluation)
@@ -1346,32 +1400,37 @@ static void launch_add_on(Kernel kernel, const Dev& dev, int lanes, ddp_hip_ctx*
                      (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, mid..., state, (int32_t)round, out, (int32_t)add);
 }
 
-static void launch_com_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
+static void launch_com_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   int32_t lpe = 8;
   while (lpe < ctx->model_h.nj) lpe *= 2;                            // (nj <= DDP_MAXJ = 64: one wave)
   launch_add_on(com_cost_kernel, com_cost_dev(ctx), lpe, ctx, xs, na, count, state, round, out, add, lpe);
 }
-static void launch_frame_vel_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
+static void launch_frame_vel_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   launch_add_on(frame_vel_cost_kernel, frame_vel_cost_dev(ctx), DDP_HIP_MAX_COST_FRAMES, ctx, xs, na, count, state, round, out, add);
 }
-static void launch_momentum_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
+static void launch_momentum_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   int32_t lpe = 8;
   while (lpe < ctx->model_h.nj) lpe *= 2;
   launch_add_on(momentum_cost_kernel, momentum_cost_dev(ctx), lpe, ctx, xs, na, count, state, round, out, add, lpe);
 }
-static void launch_relative_frame_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
+static void launch_relative_frame_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   launch_add_on(relative_frame_cost_kernel, relative_frame_dev(ctx), DDP_HIP_MAX_FRAME_PAIRS, ctx, xs, na, count, state, round, out, add);
 }
-static void launch_obstacle_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
+static void launch_control_grav_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
+  int32_t lpe = 8;
+  while (lpe < ctx->model_h.nj) lpe *= 2;
+  launch_add_on(control_grav_cost_kernel, control_grav_dev(ctx), lpe, ctx, xs, na, count, state, round, out, add, lpe, us, ctx->d.T * ctx->d.m);
+}
+static void launch_obstacle_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   launch_add_on(obstacle_cost_kernel, obstacle_cost_dev(ctx), DDP_HIP_MAX_COLLISION_POINTS, ctx, xs, na, count, state, round, out, add);
 }
-static void launch_self_collision_cost(ddp_hip_ctx* ctx, const double* xs, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
+static void launch_self_collision_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   launch_add_on(self_collision_cost_kernel, self_collision_dev(ctx), DDP_HIP_MAX_COLLISION_POINTS, ctx, xs, na, count, state, round, out, add);
 }
 
 // The terms formed out of line, in the fixed order of their additions (after everything cost_kernel / the rollout kernels form
-// inline): CoM, frame velocities, momentum, relative frames, obstacles, self-collision.  launch_cost and ddp_hip_forward both walk
-// this table and nothing else
+// inline): CoM, frame velocities, momentum, relative frames, control-gravity, obstacles, self-collision.  launch_cost and
+// ddp_hip_forward both walk this table and nothing else
 struct AddOnTerm {
   int term;
   AddOnLaunch launch;
@@ -1380,6 +1439,7 @@ static const AddOnTerm kAddOn[] = {{COST_COM, launch_com_cost},
                                    {COST_FRAME_VEL, launch_frame_vel_cost},
                                    {COST_MOMENTUM, launch_momentum_cost},
                                    {COST_RELATIVE_FRAME, launch_relative_frame_cost},
+                                   {COST_CONTROL_GRAV, launch_control_grav_cost},
                                    {COST_OBSTACLE, launch_obstacle_cost},
                                    {COST_SELF_COLLISION, launch_self_collision_cost}};
 
@@ -1393,7 +1453,7 @@ static int launch_cost(ddp_hip_ctx* ctx, FwdParams& p, int which) {
 #undef LAUNCH
 #undef CALL
   for (const AddOnTerm& a : kAddOn)                                   // + each live add-on term, onto what cost_kernel has left
-    if (ctx->cost[a.term].live) a.launch(ctx, which == 0 ? p.x_old : p.x_new, 1, total, nullptr, 0, which == 0 ? p.costs_old : p.costs_new, 1);
+    if (ctx->cost[a.term].live) a.launch(ctx, which == 0 ? p.x_old : p.x_new, which == 0 ? p.u_old : p.u_new, 1, total, nullptr, 0, which == 0 ? p.costs_old : p.costs_new, 1);
   HIP_TRY(hipGetLastError());
   return DDP_HIP_OK;
 }
@@ -1515,7 +1575,7 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
       // fw_dcost (a candidate whose sum is +0 -- no weight, no obstacle touched -- has nothing added)
       const CostBlock& k = ctx->cost[a.term];
       if (!k.live) continue;
-      a.launch(ctx, p.fw_x, n_alpha, B * n_alpha * (d.T + 1), p.state, round, k.cand, 0);
+      a.launch(ctx, p.fw_x, p.fw_u, n_alpha, B * n_alpha * (d.T + 1), p.state, round, k.cand, 0);
       hipLaunchKernelGGL(com_sum_kernel, dim3((unsigned)((B * n_alpha + 63) / 64)), dim3(64), 0, ctx->stream, k.cand, p.fw_dcost, p.state,
                          (int32_t)B, (int32_t)n_alpha, (int32_t)round, d.T);
     }

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include "com_cost.h"
+#include "control_grav_cost.h"
 #include "frame_cost.h"
 #include "frame_vel_cost.h"
 #include "internal.h"
@@ -456,8 +457,91 @@ __global__ __launch_bounds__(64) void lin_relative_frame_cost_kernel(LinParams p
   rbd::relative_frame_add_wave(S, np, rot_cols, nu, tid, (int)blockDim.x, n, gx, gxx);
 }
 
+// Control-gravity cost (DDP_HIP_FLAG_CONTROL_GRAV_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T-1, after every other
+// cost kernel on the same stream (the fixed order of additions: ..., momentum, relative frames, control-gravity).  The first add-on
+// kernel that writes lu / luu / lux.  A block whose m weights are all 0 returns at once, before any LDS access or barrier.  Lanes
+// j < nj stage world axis, world origin, path, mass and first moment of their joint (rbd::grav_stage_lane), then form their
+// subtree's sums and D, D x F and g of their tangent (rbd::grav_tangent_lane); lane i < m leaves w_i, w_i r_i (r = u - g - o) and
+// makes the two additions of its own row, lu[i] += w_i r_i and luu[i][i] += w_i.  Then the wave forms the entries of G on the
+// pattern into dynamic LDS (s_G[i nv + c] = G_ic, nv^2 doubles; an entry off the pattern is neither formed nor read) with
+// lux[i][c] += -(w_i G_ic) for the live rows on the way, lane c gathers rel[c], the live rows whose G_ic is on the pattern, and
+//   lx[c] += -sum_{i in rel[c]} G_ic (w_i r_i),      lxx[a][b] += sum_{i in rel[a] & rel[b]} G_i,min w_i G_i,max      (Gauss-Newton)
+// rows ascending, entry (a, b) in (min, max) order: the block stays symmetric bit for bit.  An entry that no live row reaches is
+// not written, a row of weight 0 is in no rel[].  It reads p.x and p.u.  No scratch, no atomics
+__global__ __launch_bounds__(64) void lin_control_grav_cost_kernel(LinParams p, ControlGravDev cg) {
+  const int64_t T = p.d.T;
+  const int64_t bt = blockIdx.x;                        // b T + t, t < T: the record has no terminal row
+  const int n = (int)p.d.n, nv = (int)p.d.nv, mu = (int)p.d.m;
+  const int tid = threadIdx.x;
+  const double* w = cg.weight + bt * mu;
+  if (!rbd::weights_any(w, mu)) return;
+  const DevModel& m = *p.model;
+  const bool ff = m.ff != 0;
+  const int64_t b = bt / T, t = bt % T;
+  const double* q = p.x + (b * (T + 1) + t) * p.d.nx;
+  __shared__ rbd::GravWaveLds S;
+  __shared__ double s_w[DDP_MAXJ], s_wr[DDP_MAXJ];
+  __shared__ unsigned long long s_rel[DDP_MAXJ];
+  extern __shared__ double s_G[];
+  if (tid < m.nj) rbd::grav_stage_lane(m, q, tid, S);
+  const unsigned long long rot = __ballot(tid < nv && rbd::grav_tangent_rotational(m, ff, tid < nv ? tid : 0));
+  const unsigned long long live = __ballot(tid < mu && w[tid < mu ? tid : 0] != 0.0);
+  __syncthreads();
+  rbd::grav_tangent_lane(m, tid, rot, S);
+  __syncthreads();
+  if (tid < mu) {
+    const double wi = w[tid];
+    double wr = 0.0;
+    if (wi != 0.0) {
+      wr = wi * (p.u[bt * mu + tid] - S.g[tid] - cg.offset[bt * mu + tid]);
+      p.lu[bt * mu + tid] += wr;
+      p.luu[bt * mu * mu + tid + (int64_t)tid * mu] += wi;
+    }
+    s_w[tid] = wi;
+    s_wr[tid] = wr;
+  }
+  double* lux = p.lux + bt * mu * n;
+  for (int e = tid; e < nv * nv; e += (int)blockDim.x) {
+    const int c = e % nv, i = e / nv;
+    double gic;
+    if (!rbd::grav_entry(S, ff, i, c, &gic)) continue;
+    s_G[e] = gic;
+    if ((live >> i) & 1) lux[i + (int64_t)c * mu] += -(w[i] * gic);
+  }
+  if (tid < nv) {
+    unsigned long long rel = 0;
+    double unused;
+    for (int i = 0; i < nv; ++i)
+      if (((live >> i) & 1) && rbd::grav_entry(S, ff, i, tid, &unused)) rel |= 1ull << i;
+    s_rel[tid] = rel;
+  }
+  __syncthreads();
+  double* gx = p.lx + bt * n;
+  double* gxx = p.lxx + bt * n * n;
+  if (tid < nv && s_rel[tid]) {
+    double s = 0.0;
+    for (unsigned long long r = s_rel[tid]; r; r &= r - 1) {
+      const int i = __builtin_ctzll(r);
+      s += s_G[i * nv + tid] * s_wr[i];
+    }
+    gx[tid] += -s;
+  }
+  for (int e = tid; e < nv * nv; e += (int)blockDim.x) {
+    const int a = e % nv, c = e / nv;
+    const unsigned long long both = s_rel[a] & s_rel[c];
+    if (!both) continue;
+    const int lo = a < c ? a : c, hi = a < c ? c : a;
+    double h = 0.0;
+    for (unsigned long long r = both; r; r &= r - 1) {
+      const int i = __builtin_ctzll(r);
+      h += s_G[i * nv + lo] * s_w[i] * s_G[i * nv + hi];
+    }
+    gxx[a + (int64_t)c * n] += h;
+  }
+}
+
 // Obstacle cost (DDP_HIP_FLAG_OBSTACLE_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost kernel
-// on the same stream (the fixed order of additions: ..., momentum, relative frames, obstacles).  The penalty is one-sided, so most
+// on the same stream (the fixed order of additions: ..., relative frames, control-gravity, obstacles).  The penalty is one-sided, so most
 // waves have nothing to add and must cost next to nothing.  A block whose weights are all 0 returns at once.  Phase 1: lane
 // k < n_points walks point k (rbd::frame_point) and runs over its live slots in ascending order; a lane with an active pair
 // (w != 0, e != 0, a direction u) forms g_k = sum_o w e u and the symmetric M_k = sum_o w u u^T on the way, in registers.  One
@@ -506,7 +590,7 @@ __global__ __launch_bounds__(64) void lin_obstacle_cost_kernel(LinParams p, Obst
 }
 
 // Self-collision cost (DDP_HIP_FLAG_SELF_COLLISION_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost
-// kernel on the same stream (the fixed order of additions: ..., relative frames, obstacles, self-collision).  One-sided like the
+// kernel on the same stream (the fixed order of additions: ..., control-gravity, obstacles, self-collision).  One-sided like the
 // obstacle cost: most waves have nothing to add.  A block whose weights are all 0 returns at once.  Phase 1: lane k < n_points
 // walks sphere k (rbd::frame_point); lane i < n_pairs fetches p_a and p_b from the lanes that hold them (cross-lane reads: no
 // LDS) and forms d_i.  One wave-level vote decides: a wave without an active pair (w != 0, e != 0, a direction u) returns here,
@@ -1406,8 +1490,8 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
       hipLaunchKernelGGL(lin_track_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p);
     else hipLaunchKernelGGL(lin_cost_kernel, dim3((unsigned)BT), dim3(64), 0, ctx->stream, p);
     // the add-on terms, one kernel per live term, each adding onto what the ones before it left.  The fixed order of additions:
-    // cost, tracking, frame positions, frame orientations, limits, CoM, frame velocities, momentum, relative frames, obstacles,
-    // self-collision
+    // cost, tracking, frame positions, frame orientations, limits, CoM, frame velocities, momentum, relative frames,
+    // control-gravity, obstacles, self-collision
     const dim3 blocks((unsigned)(BT + d.batch));
     const FrameCostDev fc = frame_cost_dev(ctx);
     const StateLimitsDev sl = state_limits_dev(ctx);
@@ -1415,6 +1499,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     const FrameVelCostDev fv = frame_vel_cost_dev(ctx);
     const MomentumCostDev mo = momentum_cost_dev(ctx);
     const RelativeFrameDev rf = relative_frame_dev(ctx);
+    const ControlGravDev cg = control_grav_dev(ctx);
     const ObstacleCostDev ob = obstacle_cost_dev(ctx);
     const SelfCollisionDev sc = self_collision_dev(ctx);
     auto add = [&](bool live, auto kernel, const auto& dev) { if (live) hipLaunchKernelGGL(kernel, blocks, dim3(64), 0, ctx->stream, p, dev); };
@@ -1425,6 +1510,8 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     add(fv.target, lin_frame_vel_cost_kernel, fv);
     add(mo.target, lin_momentum_cost_kernel, mo);
     add(rf.weight, lin_relative_frame_cost_kernel, rf);
+    if (cg.weight)   // (t < T alone; G in dynamic LDS, nv^2 doubles)
+      hipLaunchKernelGGL(lin_control_grav_cost_kernel, dim3((unsigned)BT), dim3(64), sizeof(double) * (size_t)(d.nv * d.nv), ctx->stream, p, cg);
     add(ob.geom, lin_obstacle_cost_kernel, ob);
     add(sc.margin, lin_self_collision_cost_kernel, sc);
   }

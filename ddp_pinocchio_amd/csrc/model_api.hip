@@ -8,6 +8,7 @@
 #include <new>
 
 #include "com_cost.h"
+#include "control_grav_cost.h"
 #include "frame_vel_cost.h"
 #include "internal.h"
 #include "momentum_cost.h"
@@ -157,6 +158,26 @@ __global__ __launch_bounds__(64) void model_relative_frame_kernel(const DevModel
   }
 }
 
+// g(q) and G = dg / d(delta q) by one wave, with the traversal of lin_control_grav_cost_kernel (control_grav_cost.h): in = q,
+// out = g[nv] | G[nv nv] (column-major; entries off the pattern 0).  want_jac == 0: g alone, by the same steps
+__global__ __launch_bounds__(64) void model_gravity_torque_kernel(const DevModel* m, const double* in, double* out, int want_jac) {
+  __shared__ rbd::GravWaveLds S;
+  const int tid = threadIdx.x, nv = m->nv;
+  const bool ff = m->ff != 0;
+  if (tid < m->nj) rbd::grav_stage_lane(*m, in, tid, S);
+  const unsigned long long rot = __ballot(tid < nv && rbd::grav_tangent_rotational(*m, ff, tid < nv ? tid : 0));
+  __syncthreads();
+  rbd::grav_tangent_lane(*m, tid, rot, S);
+  __syncthreads();
+  if (tid < nv) out[tid] = S.g[tid];
+  if (!want_jac) return;
+  for (int e = tid; e < nv * nv; e += blockDim.x) {
+    double gic = 0.0;
+    (void)rbd::grav_entry(S, ff, e % nv, e / nv, &gic);
+    out[nv + e] = gic;
+  }
+}
+
 #define MODEL_DISPATCH(nv, CALL)       \
   do {                                 \
     if ((nv) <= 6) { CALL(6); }        \
@@ -191,6 +212,8 @@ int run(ddp_hip_model_handle* h, const double* in, size_t n_in, double* out, siz
     hipLaunchKernelGGL(model_frame_vel_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac);   // (want_jac: the joint)
   } else if (what == 5) {
     hipLaunchKernelGGL(model_momentum_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o);
+  } else if (what == 7) {
+    hipLaunchKernelGGL(model_gravity_torque_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac);
   } else if (what == 6) {
     hipLaunchKernelGGL(model_relative_frame_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac % DDP_MAXJ,
                        want_jac / DDP_MAXJ);   // (want_jac: the two joints)
@@ -348,4 +371,18 @@ extern "C" int ddp_hip_model_relative_frame(ddp_hip_model_handle* h, int32_t joi
   memcpy(quat4, out + 3, sizeof(double) * 4);
   if (J) memcpy(J, out + 7, sizeof(double) * 6 * nv);
   return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_model_gravity_torque(ddp_hip_model_handle* h, const double* q, double* g, double* G) {
+  if (!h || !q || !g || h->model_h.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_ARG;
+  const size_t nv = (size_t)h->model_h.nv;
+  double* out = new (std::nothrow) double[nv + nv * nv];
+  if (!out) return DDP_HIP_E_HIP;
+  const int rc = run(h, q, (size_t)h->model_h.nq, out, nv + (G ? nv * nv : 0), 7, G ? 1 : 0);
+  if (rc == DDP_HIP_OK) {
+    memcpy(g, out, sizeof(double) * nv);
+    if (G) memcpy(G, out + nv, sizeof(double) * nv * nv);
+  }
+  delete[] out;
+  return rc;
 }

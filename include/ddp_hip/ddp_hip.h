@@ -396,6 +396,34 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * obstacles'). */
 #define DDP_HIP_FLAG_RELATIVE_FRAME_COST 4096u
 #define DDP_HIP_MAX_FRAME_PAIRS 4
+/* Regularise the control about the torque that merely holds the robot up: on an arm or a humanoid under gravity 1/2 c |u|^2 (and
+ * a tracking cost against a reference fixed in advance) penalises *holding the posture*, and every task term has to out-shout the
+ * weight of the robot.  g(q) in R^nv is the generalised gravity torque, defined by the model's own forward dynamics: the control
+ * for which aba(q, v = 0, u = g(q)) = 0 (no sign or frame convention enters).  Per instance b and t = 0 .. T-1 an offset
+ * o[b][t] in R^m and weights w[b][t] in R^m (>= 0, finite), m = nv:
+ *   r(q, u) = u - g(q) - o,      l(t, x, u) += 1/2 sum_j w_j r_j^2      t < T      (there is no control at T: no terminal term)
+ * to whatever the context optimises otherwise.  With G = dg / d(delta q) (nv x nv, in the tangent at q) the term adds
+ *   lu += w o r,   luu += diag(w),   lux[:, q columns] += -diag(w) G,   lx[q rows] += -G^T (w o r),   lxx[q, q] += G^T diag(w) G.
+ * The first add-on term that writes lu / luu / lux.  With F = -gravity, a_k the world rotation axis of tangent k (a revolute
+ * joint's axis; a free-flyer root's R_0 e_c for its three rotation tangents; none for a prismatic joint and the root's
+ * translations), sub(k) the bodies that tangent k moves, and D_k = a_k x sum_sub m_b (p_b - o_k) (rotation), m_sub a_k
+ * (translation):  g_k = F . D_k, and for tangent i with k on the path root .. i (k's joint an ancestor of i's, or the same joint)
+ *   G_ik = a_k . (D_i x F)      (k rotational; 0 for a translation),      G_ki = the same for k's joint a strict ancestor of i's:
+ * turning an ancestor turns the subtree's axis and lever alike, moving a descendant changes the ancestor's first moment by D.  On
+ * a fixed base G is the Hessian of the potential energy and symmetric, bit for bit.  G_ik is formed only when i and k lie on one
+ * root path, and of those only the entries whose ancestor side is rotational: everything else is identically zero and is left
+ * out, not added as zeros -- a free-flyer root's three translation columns among them, while its three rotation columns are there
+ * (turning the base turns gravity in the body).  The velocity rows and columns, lfx and lfxx are untouched.  lxx is Gauss-Newton
+ * (sum_j w_j r_j d^2 g_j is dropped: exact where r = 0, positive semidefinite): rows ascending, entry (i, j) formed in (min, max)
+ * order, symmetric bit for bit, no atomics; an entry that no live row reaches is not written.  A term of weight 0 is left out
+ * (not multiplied by 0), a (b, t) whose weights are all 0 forms nothing, and with nothing uploaded or every weight 0 a context
+ * computes bit for bit what it computes without the flag.  A free-flyer root's six rows carry no term (a weight there:
+ * DDP_HIP_E_ARG, as for the pose rows of DDP_HIP_FLAG_STATE_LIMITS).  With DDP_HIP_FLAG_CONTROL_BOUNDS r is formed from the
+ * control the rollout applied: the clamped one, as stored in U / U_NEW and the candidates' controls.  The data travels through
+ * ddp_hip_control_grav_cost_* below; at create offsets and weights are 0.  Tree models only (the pendulum: DDP_HIP_E_UNSUPPORTED).
+ * The flag stands alone and combines with every other flag: the terms are formed by kernels of their own, which add onto what the
+ * other terms' kernels leave (after the relative frames', before the obstacles'). */
+#define DDP_HIP_FLAG_CONTROL_GRAV_COST 8192u
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -517,6 +545,12 @@ int ddp_hip_relative_frame_download(ddp_hip_ctx* ctx, double* target, double* qu
  * (which = 0) or X_NEW (which = 1), against the resident targets and references.  From the first
  * ddp_hip_relative_frame_set_pairs on (before: DDP_HIP_E_ARG), live weights or not. */
 int ddp_hip_relative_frame_error(ddp_hip_ctx* ctx, int which, double* out);
+/* The control-gravity terms of a context created with DDP_HIP_FLAG_CONTROL_GRAV_COST (else DDP_HIP_E_UNSUPPORTED), stream-ordered
+ * like ddp_hip_momentum_cost_upload.  Host arrays [n_instances][T][m]: offsets and weights, one per control row and t < T; a NULL
+ * pointer leaves that side as it is.  An upload is refused as a whole (DDP_HIP_E_ARG, nothing written) for a bad instance range, a
+ * non-finite offset, a negative or non-finite weight and a non-zero weight on one of a free-flyer root's six rows. */
+int ddp_hip_control_grav_cost_upload(ddp_hip_ctx* ctx, const double* offset, const double* weight, int64_t first_instance, int64_t n_instances);
+int ddp_hip_control_grav_cost_download(ddp_hip_ctx* ctx, double* offset, double* weight, int64_t first_instance, int64_t n_instances);
 
 /* make_trajectory (ddp.hpp:392-415): X[0] and U given -> X[1..T] */
 int ddp_hip_rollout(ddp_hip_ctx* ctx);
@@ -683,6 +717,11 @@ int ddp_hip_model_centroidal_momentum(ddp_hip_model_handle* h, const double* q, 
  * hands are now" */
 int ddp_hip_model_relative_frame(ddp_hip_model_handle* h, int32_t joint_a, const double off_a[3], int32_t joint_b, const double off_b[3],
                                  const double* q, double* p3, double* quat4, double* J);
+/* The generalised gravity torque g(q) [nv] of a tree model at the configuration q, as DDP_HIP_FLAG_CONTROL_GRAV_COST defines it
+ * (aba(q, 0, g(q)) = 0), and, where not NULL, G = dg / d(delta q) as nv x nv column-major (G[i + nv j] = dg_i / d(delta q_j);
+ * entries off the pattern are 0), formed by the traversal the cost kernels use.  A free-flyer root's six rows are returned as
+ * well: the definition covers them, only the cost leaves them out.  For targets and warm starts: "start from U = g(q0)" */
+int ddp_hip_model_gravity_torque(ddp_hip_model_handle* h, const double* q, double* g, double* G);
 
 /* ---- built-in seeded model tables (no URDF exists offline: SURVEY.md D4, 8d) -------------- */
 /* ..._FF: the same robots on a free-flyer root instead of a fixed base / 3 prismatic + 3 revolute base joints */
