@@ -34,10 +34,12 @@ FLAG_SELF_COLLISION_COST = 1024
 FLAG_MOMENTUM_COST = 2048
 FLAG_RELATIVE_FRAME_COST = 4096
 FLAG_CONTROL_GRAV_COST = 8192
+FLAG_FRAME_AIM_COST = 16384
 MAX_COST_FRAMES = 4
 MAX_COLLISION_POINTS, MAX_OBSTACLES = 16, 8
 MAX_COLLISION_PAIRS = 32
 MAX_FRAME_PAIRS = 4
+MAX_AIM_FRAMES = 4
 OBSTACLE_SPHERE, OBSTACLE_HALFSPACE = 0, 1
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
 
@@ -79,6 +81,8 @@ EXPORTS = [
     "ddp_hip_relative_frame_set_pairs", "ddp_hip_relative_frame_upload", "ddp_hip_relative_frame_download",
     "ddp_hip_relative_frame_error", "ddp_hip_model_relative_frame",
     "ddp_hip_control_grav_cost_upload", "ddp_hip_control_grav_cost_download", "ddp_hip_model_gravity_torque",
+    "ddp_hip_frame_aim_set_frames", "ddp_hip_frame_aim_upload", "ddp_hip_frame_aim_download", "ddp_hip_frame_aim_error",
+    "ddp_hip_model_frame_axis",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -200,6 +204,12 @@ def lib():
         L.ddp_hip_control_grav_cost_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_control_grav_cost_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_model_gravity_torque.argtypes = [C.c_void_p, _dp, _dp, _dp]
+    if hasattr(L, "ddp_hip_frame_aim_upload"):  # (likewise: set_aim_frames, set_frame_aim_cost, frame_aim_error, ModelHandle.frame_axis)
+        L.ddp_hip_frame_aim_set_frames.argtypes = [C.c_void_p, C.c_int32, _ip, _dp, _dp]
+        L.ddp_hip_frame_aim_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_frame_aim_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_frame_aim_error.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.ddp_hip_model_frame_axis.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]
     L.ddp_hip_rollout.argtypes = [C.c_void_p]
     L.ddp_hip_linearize.argtypes = [C.c_void_p]
     L.ddp_hip_linearize_stages.argtypes = [C.c_void_p, C.c_uint32]
@@ -400,6 +410,18 @@ class ModelHandle:
                                                   _ptr(J) if jacobian else None), "model_relative_frame")
         return (p3, qt, J.reshape(self.nv, 6).T.copy()) if jacobian else (p3, qt)
 
+    def frame_axis(self, joint, off, axis, q, jacobian=False):
+        """The eye and the axis of the aim frame (joint, off, axis) at q, as FLAG_FRAME_AIM_COST defines them (ddp_hip.h):
+        (p3, n3), the point's world position and the axis' world direction; with jacobian=True (p3, n3, J), J = [dp; dn] /
+        d(delta q) as (6, nv).  For targets such as what it looks at now, one metre ahead: g = p + n"""
+        off, axis, q = _f64(off), _f64(axis), _f64(q)
+        if off.shape != (3,) or axis.shape != (3,):
+            raise ValueError("frame_axis: off and axis are 3-vectors")
+        p3, n3, J = np.zeros(3), np.zeros(3), np.zeros(6 * self.nv)
+        _check(lib().ddp_hip_model_frame_axis(self._h, int(joint), _ptr(off), _ptr(axis), _ptr(q), _ptr(p3), _ptr(n3),
+                                              _ptr(J) if jacobian else None), "model_frame_axis")
+        return (p3, n3, J.reshape(self.nv, 6).T.copy()) if jacobian else (p3, n3)
+
     def gravity_torque(self, q, jacobian=False):
         """The generalised gravity torque g(q) of a tree model as (nv,): the control that holds the robot at rest, aba(q, 0, g) = 0,
         as FLAG_CONTROL_GRAV_COST defines it (ddp_hip.h); with jacobian=True (g, G), G = dg / d(delta q) as (nv, nv).  A
@@ -455,6 +477,7 @@ class Context:
         self.n_obstacles = 0
         self.n_collision_pairs = 0
         self.n_frame_pairs = 0
+        self.n_aim_frames = 0
 
     def close(self):
         if self._h:
@@ -661,6 +684,49 @@ class Context:
         """(offset, weight) of instances first .. first + count - 1, each (count, T, m)"""
         per = (self.spec.T, self.spec.m)
         return self._cost_download(lib().ddp_hip_control_grav_cost_download, "control_grav_cost_download", (per, per), first, count)
+
+    def set_aim_frames(self, frames):
+        """The aim frames [(joint, off, axis), ...] (0 .. MAX_AIM_FRAMES of them; off: the eye, a point in the joint's
+        coordinates; axis: a unit vector in the joint's axes) of a context created with FLAG_FRAME_AIM_COST (ddp_hip.h), shared
+        by the batch.  With the same count and the same joints as before the per-instance data stays (points and axes may move),
+        else targets, stand-offs and weights are reset to 0"""
+        frames = list(frames)
+        if any(len(f) != 3 for f in frames):
+            raise ValueError("set_aim_frames: every frame is (joint, off, axis)")
+        joint = np.ascontiguousarray([int(f[0]) for f in frames], dtype=np.int32)
+        off = [np.asarray(f[1], dtype=np.float64) for f in frames]
+        axis = [np.asarray(f[2], dtype=np.float64) for f in frames]
+        if any(o.shape != (3,) for o in off + axis):
+            raise ValueError("set_aim_frames: every off and every axis is a 3-vector")
+        off, axis = _f64(off).reshape(-1), _f64(axis).reshape(-1)
+        _check(lib().ddp_hip_frame_aim_set_frames(self._h, len(frames), joint.ctypes.data_as(_ip), _ptr(off), _ptr(axis)), "frame_aim_set_frames")
+        self.n_aim_frames = len(frames)
+
+    def set_frame_aim_cost(self, target=None, weight=None, first=0, count=None):
+        """The frame-aiming terms of instances first .. first + count - 1 (a context created with FLAG_FRAME_AIM_COST; ddp_hip.h),
+        of the F frames of set_aim_frames.  target: (g, rho), the world point the axis looks at and the stand-off >= 0, weight:
+        (w_aim, w_range) >= 0; (T+1, F, 4) / (T+1, F, 2) for every instance of the range or (count, T+1, F, .) with one per
+        instance; weight also takes (F, 2), (2,) and scalars by broadcast.  None leaves that side as it is.  The frame count is
+        the one this object last passed to set_aim_frames; before that call there is no shape to check against and the call
+        raises ValueError."""
+        T1, F = self.spec.T + 1, getattr(self, "n_aim_frames", 0)
+        if not F:
+            raise ValueError("set_frame_aim_cost: no frames yet, call set_aim_frames first")
+        count, arrs = self._cost_sides("set_frame_aim_cost", (("target", target, (T1, F, 4), ()), ("weight", weight, (T1, F, 2), ((F, 2), (2,), ()))),
+                                       first, count)
+        self._cost_upload(lib().ddp_hip_frame_aim_upload, "frame_aim_upload", arrs, first, count)
+
+    def get_frame_aim_cost(self, first=0, count=None):
+        """(target, weight) of instances first .. first + count - 1: (count, T+1, F, 4) and (count, T+1, F, 2)"""
+        T1, F = self.spec.T + 1, getattr(self, "n_aim_frames", 0)    # (0 before set_aim_frames: empty arrays)
+        return self._cost_download(lib().ddp_hip_frame_aim_download, "frame_aim_download", ((T1, F, 4), (T1, F, 2)), first, count)
+
+    def frame_aim_error(self, which=0):
+        """(batch, T+1, F, 2): (theta, l) of every aim frame along X (which = 0) or X_NEW (which = 1) against the resident targets,
+        live weights or not: the angle between the axis and the line of sight in radians, and the distance to the target"""
+        out = np.zeros((self.batch, self.spec.T + 1, getattr(self, "n_aim_frames", 0), 2))
+        _check(lib().ddp_hip_frame_aim_error(self._h, int(which), _ptr(out)), "frame_aim_error")
+        return out
 
     def set_relative_frame_pairs(self, pairs):
         """The frame pairs [((joint_a, off_a), (joint_b, off_b)), ...] (1 .. MAX_FRAME_PAIRS of them, the two frames of a pair on

@@ -10,13 +10,15 @@
 
 // The terms.  The order in which the kernels add them (after the stage cost and the tracking cost) is stated where they are launched:
 // lin.hip launches one kernel per live term, fwd.hip forms the first three inline and walks kAddOn for the others, both in the order
-// frame positions, frame orientations, limits, CoM, frame velocities, momentum, relative frames, control-gravity, obstacles,
-// self-collision.  The enumerators are indices of ctx->cost[] and kCostDesc[] and follow that order but for COST_CONTROL_GRAV: the
-// host programs hold momentum, relative frames, obstacles and self-collision as neighbours and self-collision as the last
-// (host/test_relative_frame_block.cpp, host/test_self_collision_block.cpp), so the term whose additions come between the relative
-// frames' and the obstacles' has its index in front of that run
-enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_LIMITS, COST_COM, COST_FRAME_VEL, COST_CONTROL_GRAV, COST_MOMENTUM, COST_RELATIVE_FRAME,
-                          COST_OBSTACLE, COST_SELF_COLLISION, COST_COUNT };
+// frame positions, frame orientations, limits, CoM, frame velocities, momentum, relative frames, control-gravity, frame aiming,
+// obstacles, self-collision.  The enumerators are indices of ctx->cost[] and kCostDesc[] and follow that order but for
+// COST_CONTROL_GRAV and COST_FRAME_AIM: the host programs hold momentum, relative frames, obstacles and self-collision as neighbours
+// and self-collision as the last (host/test_relative_frame_block.cpp, host/test_self_collision_block.cpp), so the term whose
+// additions come between the relative frames' and the obstacles' has its index in front of that run; they hold frame velocities and
+// control-gravity as neighbours too (host/test_control_grav_block.cpp), so the term whose additions come after control-gravity's
+// has its index in front of the frame velocities'.  No order is read off the enumerators
+enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_LIMITS, COST_COM, COST_FRAME_AIM, COST_FRAME_VEL, COST_CONTROL_GRAV, COST_MOMENTUM,
+                          COST_RELATIVE_FRAME, COST_OBSTACLE, COST_SELF_COLLISION, COST_COUNT };
 
 enum CostFill : int32_t { FILL_ZERO, FILL_NEG_INF, FILL_POS_INF, FILL_QUAT };   // FILL_QUAT: identity quaternions (0, 0, 0, 1)
 
@@ -43,6 +45,7 @@ static const CostDesc kCostDesc[COST_COUNT] = {
     {DDP_HIP_FLAG_FRAME_ORIENT_COST, 2, {4, 3, 0}, {FILL_QUAT, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, false, false},   // quat | weight, per frame
     {DDP_HIP_FLAG_STATE_LIMITS, 3, {1, 1, 1}, {FILL_NEG_INF, FILL_POS_INF, FILL_ZERO}, 0, true, false, false},                 // lo | hi | weight, per tangent row
     {DDP_HIP_FLAG_COM_COST, 2, {3, 3, 0}, {FILL_ZERO, FILL_ZERO, 0}, 1, true, true, false},                                    // target | weight
+    {DDP_HIP_FLAG_FRAME_AIM_COST, 2, {4, 2, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_AIM_FRAMES, false, true, false},        // (target, stand-off) | (w_aim, w_range), per aim frame
     {DDP_HIP_FLAG_FRAME_VEL_COST, 2, {6, 6, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, true, false},       // target | weight, per frame
     {DDP_HIP_FLAG_CONTROL_GRAV_COST, 2, {1, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, COST_ITEMS_CONTROL, true, true, true},              // offset | weight, per control row, t < T
     {DDP_HIP_FLAG_MOMENTUM_COST, 2, {6, 6, 0}, {FILL_ZERO, FILL_ZERO, 0}, 1, true, true, false},                               // target | weight
@@ -90,6 +93,14 @@ static inline bool cost_weight_side(const CostCheck&, const double* v, int64_t w
 static inline bool cost_quat_side(const CostCheck&, const double* v, int64_t words) {
   for (int64_t k = 0; k < words; k += 4)
     if (!cost_quat_ok(v[k] * v[k] + v[k + 1] * v[k + 1] + v[k + 2] * v[k + 2] + v[k + 3] * v[k + 3])) return false;
+  return true;
+}
+// aim targets (g, rho): finite, and a stand-off rho >= 0
+static inline bool cost_aim_target_side(const CostCheck&, const double* v, int64_t words) {
+  for (int64_t k = 0; k < words; k += 4) {
+    if (!isfinite(v[k]) || !isfinite(v[k + 1]) || !isfinite(v[k + 2]) || !isfinite(v[k + 3])) return false;
+    if (v[k + 3] < 0.0) return false;
+  }
   return true;
 }
 // obstacle geometry by slot kind: a sphere's radius >= 0, a half-space's unit normal
@@ -143,6 +154,19 @@ static inline bool cost_frame_pairs_ok(int32_t nj, int32_t n_pairs, const int32_
     if (ja[i] < 0 || ja[i] >= nj || jb[i] < 0 || jb[i] >= nj || ja[i] == jb[i]) return false;
     for (int a = 0; a < 3; ++a)
       if (!isfinite(offa[3 * i + a]) || !isfinite(offb[3 * i + a])) return false;
+  }
+  return true;
+}
+
+// an aim-frame list over a model of nj joints (frame i: the point off[i] and the axis axis[i] of joint[i]): joints in range,
+// offsets finite, axes of unit length by the quaternions' rule (cost_quat_ok).  Several frames on one joint are allowed
+static inline bool cost_aim_frames_ok(int32_t nj, int32_t n_frames, const int32_t* joint, const double* off, const double* axis) {
+  for (int32_t i = 0; i < n_frames; ++i) {
+    if (joint[i] < 0 || joint[i] >= nj) return false;
+    for (int a = 0; a < 3; ++a)
+      if (!isfinite(off[3 * i + a])) return false;
+    const double* x = axis + 3 * i;
+    if (!cost_quat_ok(x[0] * x[0] + x[1] * x[1] + x[2] * x[2])) return false;
   }
   return true;
 }

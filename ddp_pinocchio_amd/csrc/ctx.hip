@@ -252,6 +252,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   if ((flags & DDP_HIP_FLAG_SELF_COLLISION_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the spheres alike
   if ((flags & DDP_HIP_FLAG_RELATIVE_FRAME_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the frame pairs alike
   if ((flags & DDP_HIP_FLAG_CONTROL_GRAV_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // g(q) is of a tree's bodies
+  if ((flags & DDP_HIP_FLAG_FRAME_AIM_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // aim frames are frames of a tree's joints
   if (flags & (DDP_HIP_FLAG_COM_COST | DDP_HIP_FLAG_MOMENTUM_COST)) {
     if (mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the CoM, and the momentum about it, are of a tree's bodies
     if (!mo.mass_j || !mo.jtype) return DDP_HIP_E_ARG;
@@ -360,7 +361,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipStreamSynchronize(ctx->stream));
   }
   for (int term = 0; term < COST_COUNT; ++term) {
-    // frames, frame pairs, obstacle slots and self-collision pairs: no layout until they are set; limits (lo = -inf, hi = +inf, w = 0: no limit anywhere), CoM, momentum
+    // frames, aim frames, frame pairs, obstacle slots and self-collision pairs: no layout until they are set; limits (lo = -inf, hi = +inf, w = 0: no limit anywhere), CoM, momentum
     // and control-gravity (one item per control row, T rows): fixed
     CostBlock& k = ctx->cost[term];
     k.desc = &kCostDesc[term];
@@ -373,6 +374,8 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   if (flags & DDP_HIP_FLAG_SELF_COLLISION_COST) CTX_TRY(hipMalloc(&ctx->sc_clear_d, sizeof(double) * (size_t)(d.batch * (d.T + 1))));
   if (flags & DDP_HIP_FLAG_RELATIVE_FRAME_COST)
     CTX_TRY(hipMalloc(&ctx->rf_err_d, sizeof(double) * (size_t)(d.batch * (d.T + 1) * DDP_HIP_MAX_FRAME_PAIRS * 6)));
+  if (flags & DDP_HIP_FLAG_FRAME_AIM_COST)
+    CTX_TRY(hipMalloc(&ctx->fa_err_d, sizeof(double) * (size_t)(d.batch * (d.T + 1) * DDP_HIP_MAX_AIM_FRAMES * 2)));
   int rc = bwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = fwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = lin_setup(ctx);
@@ -400,6 +403,7 @@ extern "C" int ddp_hip_destroy(ddp_hip_ctx* ctx) {
   if (ctx->ob_clear_d) (void)hipFree(ctx->ob_clear_d);
   if (ctx->sc_clear_d) (void)hipFree(ctx->sc_clear_d);
   if (ctx->rf_err_d) (void)hipFree(ctx->rf_err_d);
+  if (ctx->fa_err_d) (void)hipFree(ctx->fa_err_d);
   if (ctx->ne_d) (void)hipFree(ctx->ne_d);
   if (ctx->Epre_d) (void)hipFree(ctx->Epre_d);
   if (ctx->target_d) (void)hipFree(ctx->target_d);
@@ -751,6 +755,38 @@ extern "C" int ddp_hip_control_grav_cost_upload(ddp_hip_ctx* ctx, const double* 
 extern "C" int ddp_hip_control_grav_cost_download(ddp_hip_ctx* ctx, double* offset, double* weight, int64_t first, int64_t count) {
   double* host[] = {offset, weight};
   return cost_block_download(ctx, COST_CONTROL_GRAV, host, first, count);
+}
+
+// aim frames shared by the batch; a target with its stand-off and two weights per (instance, t, frame)
+extern "C" int ddp_hip_frame_aim_set_frames(ddp_hip_ctx* ctx, int32_t n_frames, const int32_t* joint, const double* off, const double* axis) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_FRAME_AIM_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (n_frames < 0 || n_frames > DDP_HIP_MAX_AIM_FRAMES || (n_frames > 0 && (!joint || !off || !axis))) return DDP_HIP_E_ARG;
+  if (!cost_aim_frames_ok(ctx->model_h.nj, n_frames, joint, off, axis)) return DDP_HIP_E_ARG;
+  bool same = n_frames == ctx->fa_nf;
+  for (int i = 0; same && i < n_frames; ++i) same = joint[i] == ctx->fa_joint[i];
+  if (!same) {
+    // other joints are another meaning of the per-frame data: targets, stand-offs and weights start again at 0
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int rc_ = cost_block_setup(ctx, COST_FRAME_AIM, n_frames);
+    if (rc_ != DDP_HIP_OK) return rc_;
+  }
+  ctx->fa_nf = n_frames;
+  for (int i = 0; i < n_frames; ++i) {
+    ctx->fa_joint[i] = joint[i];
+    for (int a = 0; a < 3; ++a) { ctx->fa_off[i][a] = off[3 * i + a]; ctx->fa_axis[i][a] = axis[3 * i + a]; }
+  }
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_frame_aim_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first, int64_t count) {
+  const double* host[] = {target, weight};
+  const CostSideOk ok[] = {cost_aim_target_side, cost_weight_side};
+  return cost_block_upload(ctx, COST_FRAME_AIM, host, ok, first, count);
+}
+extern "C" int ddp_hip_frame_aim_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first, int64_t count) {
+  double* host[] = {target, weight};
+  return cost_block_download(ctx, COST_FRAME_AIM, host, first, count);
 }
 
 extern "C" int ddp_hip_com_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first, int64_t count) {

@@ -13,6 +13,7 @@
 
 #include "com_cost.h"
 #include "control_grav_cost.h"
+#include "frame_aim_cost.h"
 #include "frame_cost.h"
 #include "frame_vel_cost.h"
 #include "internal.h"
@@ -809,7 +810,7 @@ __global__ void cand_sum_kernel(FwdParams p) {
   p.fw_dcost[(int64_t)b * na + a] = dsum;
 }
 
-// The add-on cost kernels below (CoM, frame velocities, momentum, relative frames, control-gravity, obstacles) run over a list of `count` (trajectory, t) pairs, t = 0 .. T,
+// The add-on cost kernels below (CoM, frame velocities, momentum, relative frames, control-gravity, frame aiming, obstacles) run over a list of `count` (trajectory, t) pairs, t = 0 .. T,
 // `na` trajectories per instance.  Pair e: which trajectory, which t, whose instance, which block bt1 = b (T+1) + t of the term's
 // data.  skip: nothing is written for this pair (past the list, or a candidate the rollout kernels skip: state != 0, beyond
 // 2^-33; state == nullptr: a resident trajectory, none is skipped).  live: the pair is evaluated (the kernels narrow it further)
@@ -1062,6 +1063,46 @@ __global__ __launch_bounds__(64) void control_grav_cost_kernel(ControlGravDev cg
   for (int i = 0; i < m.nj; ++i)
     if (s_formed[tid + i]) acc += s_term[tid + i];
   cost_pair_store(out, e, 0.5 * acc, live, add);
+}
+
+// The frame-aiming terms (DDP_HIP_FLAG_FRAME_AIM_COST, ddp_hip.h) of a list of states, added on top like the frame-velocity terms
+// above: the same list, the same two uses (add != 0: out[pair] += term behind cost_kernel; add == 0: out[pair] = term, its
+// candidates' array in a line-search round, with the candidates the rollout kernels skip skipped here).  DDP_HIP_MAX_AIM_FRAMES
+// lanes per state, 16 states per wave: lane i walks frame i (rbd::frame_aim_term: one walk joint -> root with the eye and the
+// axis, no jacobian, no per-joint arrays) and leaves 1/2 (w_aim |r_aim|^2 + w_range r_range^2) in LDS; the group's first lane adds
+// the frames' terms in ascending order.  A term of weight 0 is left out, a frame whose two weights are 0 is not walked, with
+// w_range = 0 rho is not read, a frame whose line of sight is shorter than 1e-12 forms nothing, and a state without a formed term
+// adds nothing (add != 0) or stores +0 (add == 0).  A non-finite state gives a NaN term, as com_cost_kernel's does
+__global__ __launch_bounds__(64) void frame_aim_cost_kernel(FrameAimDev fa, const DevModel* model, const double* xs, int64_t traj_stride,
+                                                            int64_t count, int32_t T1, int32_t nx, int32_t na, const int32_t* state,
+                                                            int32_t round, double* out, int32_t add) {
+  __shared__ double s_term[64];
+  __shared__ int32_t s_formed[64];
+  const DevModel& m = *model;
+  pair_lanes_fold<DDP_HIP_MAX_AIM_FRAMES, false>(s_term, s_formed, fa.nf, xs, traj_stride, count, T1, nx, na, state, round, out, add,
+                                                 [&](int i, int64_t bt1, const double* x, double* term) {
+    return rbd::frame_aim_term(m, fa, i, bt1, x, term);
+  });
+}
+
+// ddp_hip_frame_aim_error: one lane per (instance, t, frame) of one resident trajectory, out[(bt1 nf + i) 2 ..] = (theta, l) of
+// frame i against the resident target, whatever the weights: theta = atan2(|n x dh|, n . dh), 0 where l <= 1e-12
+__global__ __launch_bounds__(64) void frame_aim_error_kernel(FrameAimDev fa, const DevModel* model, const double* xs, int64_t count, int32_t nx,
+                                                             double* out) {
+  const int64_t e = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (e >= count * fa.nf) return;
+  const int64_t bt1 = e / fa.nf;
+  const int i = (int)(e % fa.nf);
+  const DevModel& m = *model;
+  double p[3], nw[3], dh[3], l, theta = 0.0;
+  rbd::frame_aim_walk(m, m.ff != 0, fa.joint[i], fa.off[i], fa.axis[i], xs + bt1 * nx, p, nw);
+  if (rbd::frame_aim_sight(p, fa.target + e * 4, dh, &l)) {
+    double c[3];
+    rbd::cross3(nw, dh, c);
+    theta = atan2(sqrt(rbd::dot3(c, c)), rbd::dot3(nw, dh));
+  }
+  out[e * 2] = theta;
+  out[e * 2 + 1] = l;
 }
 
 // The obstacle terms (DDP_HIP_FLAG_OBSTACLE_COST, ddp_hip.h) of a list of states, added on top like the frame-velocity terms above:
@@ -1421,6 +1462,9 @@ static void launch_control_grav_cost(ddp_hip_ctx* ctx, const double* xs, const d
   while (lpe < ctx->model_h.nj) lpe *= 2;
   launch_add_on(control_grav_cost_kernel, control_grav_dev(ctx), lpe, ctx, xs, na, count, state, round, out, add, lpe, us, ctx->d.T * ctx->d.m);
 }
+static void launch_frame_aim_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
+  launch_add_on(frame_aim_cost_kernel, frame_aim_dev(ctx), DDP_HIP_MAX_AIM_FRAMES, ctx, xs, na, count, state, round, out, add);
+}
 static void launch_obstacle_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   launch_add_on(obstacle_cost_kernel, obstacle_cost_dev(ctx), DDP_HIP_MAX_COLLISION_POINTS, ctx, xs, na, count, state, round, out, add);
 }
@@ -1429,8 +1473,8 @@ static void launch_self_collision_cost(ddp_hip_ctx* ctx, const double* xs, const
 }
 
 // The terms formed out of line, in the fixed order of their additions (after everything cost_kernel / the rollout kernels form
-// inline): CoM, frame velocities, momentum, relative frames, control-gravity, obstacles, self-collision.  launch_cost and
-// ddp_hip_forward both walk this table and nothing else
+// inline): CoM, frame velocities, momentum, relative frames, control-gravity, frame aiming, obstacles, self-collision.  launch_cost
+// and ddp_hip_forward both walk this table and nothing else
 struct AddOnTerm {
   int term;
   AddOnLaunch launch;
@@ -1440,6 +1484,7 @@ static const AddOnTerm kAddOn[] = {{COST_COM, launch_com_cost},
                                    {COST_MOMENTUM, launch_momentum_cost},
                                    {COST_RELATIVE_FRAME, launch_relative_frame_cost},
                                    {COST_CONTROL_GRAV, launch_control_grav_cost},
+                                   {COST_FRAME_AIM, launch_frame_aim_cost},
                                    {COST_OBSTACLE, launch_obstacle_cost},
                                    {COST_SELF_COLLISION, launch_self_collision_cost}};
 
@@ -1515,6 +1560,22 @@ extern "C" int ddp_hip_relative_frame_error(ddp_hip_ctx* ctx, int which, double*
                      which == 0 ? p.x_old : p.x_new, total, (int32_t)ctx->d.nx, ctx->rf_err_d);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, ctx->rf_err_d, sizeof(double) * (size_t)(total * rf.np * 6), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_frame_aim_error(ddp_hip_ctx* ctx, int which, double* out) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_FRAME_AIM_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (!out || (which != 0 && which != 1) || ctx->fa_nf == 0) return DDP_HIP_E_ARG;   // (no frames set: nothing to measure)
+  HIP_TRY(hipSetDevice(ctx->device));
+  const FwdParams p = make_params(ctx);
+  const FrameAimDev fa = frame_aim_dev(ctx, true);
+  const int64_t total = ctx->d.batch * (ctx->d.T + 1);
+  hipLaunchKernelGGL(frame_aim_error_kernel, dim3((unsigned)((total * fa.nf + 63) / 64)), dim3(64), 0, ctx->stream, fa, ctx->model_d,
+                     which == 0 ? p.x_old : p.x_new, total, (int32_t)ctx->d.nx, ctx->fa_err_d);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, ctx->fa_err_d, sizeof(double) * (size_t)(total * fa.nf * 2), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return DDP_HIP_OK;
 }

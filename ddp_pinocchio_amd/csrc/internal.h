@@ -290,6 +290,11 @@ struct ddp_hip_ctx {
   int32_t rf_ja[DDP_HIP_MAX_FRAME_PAIRS] = {}, rf_jb[DDP_HIP_MAX_FRAME_PAIRS] = {};
   double rf_offa[DDP_HIP_MAX_FRAME_PAIRS][3] = {}, rf_offb[DDP_HIP_MAX_FRAME_PAIRS][3] = {};
   double* rf_err_d = nullptr;                 // [batch][T+1][DDP_HIP_MAX_FRAME_PAIRS][6] what ddp_hip_relative_frame_error hands back
+  // the aim frames (ddp_hip_frame_aim_set_frames): the eye fa_off and the unit axis fa_axis of joint fa_joint
+  int32_t fa_nf = 0;                          // frames set (0: none yet)
+  int32_t fa_joint[DDP_HIP_MAX_AIM_FRAMES] = {};
+  double fa_off[DDP_HIP_MAX_AIM_FRAMES][3] = {}, fa_axis[DDP_HIP_MAX_AIM_FRAMES][3] = {};
+  double* fa_err_d = nullptr;                 // [batch][T+1][DDP_HIP_MAX_AIM_FRAMES][2] what ddp_hip_frame_aim_error hands back
 
   bool box_dirty = false;       // CTRL_LO / CTRL_HI were uploaded since lo <= hi was last checked (ctx.hip: box_check)
 

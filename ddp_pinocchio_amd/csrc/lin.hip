@@ -15,6 +15,7 @@
 
 #include "com_cost.h"
 #include "control_grav_cost.h"
+#include "frame_aim_cost.h"
 #include "frame_cost.h"
 #include "frame_vel_cost.h"
 #include "internal.h"
@@ -540,8 +541,49 @@ __global__ __launch_bounds__(64) void lin_control_grav_cost_kernel(LinParams p, 
   }
 }
 
+// Frame-aiming cost (DDP_HIP_FLAG_FRAME_AIM_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost kernel
+// on the same stream (the fixed order of additions: ..., relative frames, control-gravity, frame aiming).  A block whose weights
+// are all 0 returns at once, before any LDS access or barrier.  Lanes j < nj stage world axis, world origin and path of their
+// joint in LDS (rbd::stage_joint_lane); lane 63 - i walks frame i (rbd::frame_aim_stage_frame: one walk with the eye and the axis;
+// the top lanes, so that on a robot of fewer than 60 joints no lane does both) and leaves p, n, the line of sight, 1 / l, w and
+// w o r -- or that the frame forms nothing here (both weights 0: no walk; l <= 1e-12).  After the barrier every lane forms the live
+// frames' paths as column masks; their union is compacted (rbd::column_index_lane) and the 4 x n_u columns of each live frame are
+// staged in LDS (rbd::frame_aim_stage_columns), then the wave adds over the union alone (rbd::frame_aim_add_wave: frames ascending,
+// the three aim rows, then the range row, entry (i, j) in (min, max) order, symmetric bit for bit).  It reads p.x and touches
+// nothing but those entries.  A term of weight 0 is left out: with w_aim = 0 no aim row is formed, with w_range = 0 rho is not
+// read.  No scratch, no atomics.  t = T: lfx / lfxx
+__global__ __launch_bounds__(64) void lin_frame_aim_cost_kernel(LinParams p, FrameAimDev fa) {
+  const int64_t bt1 = blockIdx.x;
+  const int n = (int)p.d.n;
+  const int tid = threadIdx.x, nf = fa.nf;
+  const double* w = fa.weight + bt1 * nf * 2;
+  if (!rbd::weights_any(w, 2 * nf)) return;
+  const DevModel& m = *p.model;
+  const bool ff = m.ff != 0;
+  const LinCostBlock blk = lin_cost_block(p, bt1);
+  const double* q = blk.q;
+  __shared__ rbd::FrameAimWaveLds S;
+  if (tid < m.nj) rbd::stage_joint_lane<0>(m, q, tid, S.jw, nullptr);
+  const int i = 63 - tid;
+  if (i < nf) rbd::frame_aim_stage_frame(m, ff, fa, i, q, fa.target + (bt1 * nf + i) * 4, w + 2 * i, S);
+  __syncthreads();
+  unsigned long long U = 0;
+  for (int k = 0; k < nf; ++k) {
+    const unsigned long long ck = S.live[k] ? rbd::tangent_mask(ff, S.jw.mask[fa.joint[k]]) : 0ull;
+    U |= ck;
+    if (k == tid) S.cols[k] = ck;
+  }
+  rbd::column_index_lane(U, tid, S.idx);
+  __syncthreads();
+  const int nu = __builtin_popcountll(U);
+  rbd::frame_aim_stage_columns(m, S, nf, nu, tid, (int)blockDim.x);
+  __syncthreads();
+  double *gx = blk.gx, *gxx = blk.gxx;
+  rbd::frame_aim_add_wave(S, nf, nu, tid, (int)blockDim.x, n, gx, gxx);
+}
+
 // Obstacle cost (DDP_HIP_FLAG_OBSTACLE_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost kernel
-// on the same stream (the fixed order of additions: ..., relative frames, control-gravity, obstacles).  The penalty is one-sided, so most
+// on the same stream (the fixed order of additions: ..., control-gravity, frame aiming, obstacles).  The penalty is one-sided, so most
 // waves have nothing to add and must cost next to nothing.  A block whose weights are all 0 returns at once.  Phase 1: lane
 // k < n_points walks point k (rbd::frame_point) and runs over its live slots in ascending order; a lane with an active pair
 // (w != 0, e != 0, a direction u) forms g_k = sum_o w e u and the symmetric M_k = sum_o w u u^T on the way, in registers.  One
@@ -1491,7 +1533,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     else hipLaunchKernelGGL(lin_cost_kernel, dim3((unsigned)BT), dim3(64), 0, ctx->stream, p);
     // the add-on terms, one kernel per live term, each adding onto what the ones before it left.  The fixed order of additions:
     // cost, tracking, frame positions, frame orientations, limits, CoM, frame velocities, momentum, relative frames,
-    // control-gravity, obstacles, self-collision
+    // control-gravity, frame aiming, obstacles, self-collision
     const dim3 blocks((unsigned)(BT + d.batch));
     const FrameCostDev fc = frame_cost_dev(ctx);
     const StateLimitsDev sl = state_limits_dev(ctx);
@@ -1500,6 +1542,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     const MomentumCostDev mo = momentum_cost_dev(ctx);
     const RelativeFrameDev rf = relative_frame_dev(ctx);
     const ControlGravDev cg = control_grav_dev(ctx);
+    const FrameAimDev fa = frame_aim_dev(ctx);
     const ObstacleCostDev ob = obstacle_cost_dev(ctx);
     const SelfCollisionDev sc = self_collision_dev(ctx);
     auto add = [&](bool live, auto kernel, const auto& dev) { if (live) hipLaunchKernelGGL(kernel, blocks, dim3(64), 0, ctx->stream, p, dev); };
@@ -1512,6 +1555,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     add(rf.weight, lin_relative_frame_cost_kernel, rf);
     if (cg.weight)   // (t < T alone; G in dynamic LDS, nv^2 doubles)
       hipLaunchKernelGGL(lin_control_grav_cost_kernel, dim3((unsigned)BT), dim3(64), sizeof(double) * (size_t)(d.nv * d.nv), ctx->stream, p, cg);
+    add(fa.weight, lin_frame_aim_cost_kernel, fa);
     add(ob.geom, lin_obstacle_cost_kernel, ob);
     add(sc.margin, lin_self_collision_cost_kernel, sc);
   }

@@ -9,6 +9,7 @@
 
 #include "com_cost.h"
 #include "control_grav_cost.h"
+#include "frame_aim_cost.h"
 #include "frame_vel_cost.h"
 #include "internal.h"
 #include "momentum_cost.h"
@@ -178,6 +179,31 @@ __global__ __launch_bounds__(64) void model_gravity_torque_kernel(const DevModel
   }
 }
 
+// The eye p and the world axis n of the aim frame (joint, off, axis) and their jacobians by one wave, with the traversal of
+// lin_frame_aim_cost_kernel (frame_aim_cost.h): in = q | off[3] | axis[3], out = p3 | n3 | J[6 nv] (column-major: the rows of p,
+// point_column, then the rows of n, a_c x n; columns off the path 0, and the rows of n at a column that carries no rotation)
+__global__ __launch_bounds__(64) void model_frame_axis_kernel(const DevModel* m, const double* in, double* out, int joint) {
+  __shared__ rbd::JointWorldLds S;
+  __shared__ double s_pn[6];
+  const int tid = threadIdx.x, nv = m->nv;
+  const bool ff = m->ff != 0;
+  if (tid < m->nj) rbd::stage_joint_lane<0>(*m, in, tid, S, nullptr);
+  if (tid == 63) {
+    rbd::frame_aim_walk(*m, ff, joint, in + m->nq, in + m->nq + 3, in, s_pn, s_pn + 3);
+    for (int k = 0; k < 6; ++k) out[k] = s_pn[k];
+  }
+  __syncthreads();
+  const unsigned long long path = rbd::tangent_mask(ff, S.mask[joint]);
+  for (int c = tid; c < nv; c += blockDim.x) {
+    double col[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, ax[3];
+    if ((path >> c) & 1) {
+      rbd::point_column(*m, ff, S, c, s_pn, col);
+      if (rbd::rotation_column(*m, ff, S, c, ax)) rbd::cross3(ax, s_pn + 3, col + 3);
+    }
+    for (int a = 0; a < 6; ++a) out[6 + 6 * c + a] = col[a];
+  }
+}
+
 #define MODEL_DISPATCH(nv, CALL)       \
   do {                                 \
     if ((nv) <= 6) { CALL(6); }        \
@@ -217,6 +243,8 @@ int run(ddp_hip_model_handle* h, const double* in, size_t n_in, double* out, siz
   } else if (what == 6) {
     hipLaunchKernelGGL(model_relative_frame_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac % DDP_MAXJ,
                        want_jac / DDP_MAXJ);   // (want_jac: the two joints)
+  } else if (what == 8) {
+    hipLaunchKernelGGL(model_frame_axis_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac);   // (want_jac: the joint)
   } else {
 #define CALL(NJ) hipLaunchKernelGGL((model_frame_kernel<NJ>), dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac)
     MODEL_DISPATCH(nv, CALL);
@@ -385,4 +413,20 @@ extern "C" int ddp_hip_model_gravity_torque(ddp_hip_model_handle* h, const doubl
   }
   delete[] out;
   return rc;
+}
+
+extern "C" int ddp_hip_model_frame_axis(ddp_hip_model_handle* h, int32_t joint, const double off[3], const double axis[3], const double* q, double* p3,
+                                        double* n3, double* J) {
+  if (!h || !off || !axis || !q || !p3 || !n3 || h->model_h.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_ARG;
+  const int nv = h->model_h.nv, nq = h->model_h.nq;
+  if (!cost_aim_frames_ok(h->model_h.nj, 1, &joint, off, axis)) return DDP_HIP_E_ARG;
+  double in[DDP_MAXJ + 1 + 6];
+  memcpy(in, q, sizeof(double) * nq); memcpy(in + nq, off, sizeof(double) * 3); memcpy(in + nq + 3, axis, sizeof(double) * 3);
+  double out[6 + 6 * DDP_MAXJ];
+  const int rc = run(h, in, (size_t)(nq + 6), out, (size_t)(6 + (J ? 6 * nv : 0)), 8, joint);
+  if (rc != DDP_HIP_OK) return rc;
+  memcpy(p3, out, sizeof(double) * 3);
+  memcpy(n3, out + 3, sizeof(double) * 3);
+  if (J) memcpy(J, out + 6, sizeof(double) * 6 * nv);
+  return DDP_HIP_OK;
 }

@@ -424,6 +424,40 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * The flag stands alone and combines with every other flag: the terms are formed by kernels of their own, which add onto what the
  * other terms' kernels leave (after the relative frames', before the obstacles'). */
 #define DDP_HIP_FLAG_CONTROL_GRAV_COST 8192u
+/* Say "this axis looks at that point": "the head camera keeps the object in view while the arms work", "the gripper's approach
+ * axis points at the grasp point before it closes", "the tool points at the seam from 30 cm away".  The orientation cost cannot
+ * say it: its reference is a fixed rotation, while the direction to a target changes with the frame's own position.  Aiming fixes
+ * two degrees of freedom about a direction that depends on q through the frame's own point, and leaves the roll about the axis
+ * and -- without a range weight -- the distance free.  The flag stands alone: it needs no DDP_HIP_FLAG_FRAME_COST and has its own
+ * frames.  Aim frames, shared by the batch, up to DDP_HIP_MAX_AIM_FRAMES: frame i is a joint j_i, a point off_i in the joint's
+ * coordinates (the eye) and a unit axis a_i in the joint's axes; several frames may sit on one joint.  With p the point's world
+ * position and n = R_j a the axis' world direction, per instance b, t = 0 .. T and frame i a target point g in R^3 (world), a
+ * stand-off rho >= 0 and two weights w_aim, w_range (>= 0, finite):
+ *   d = g - p,   l = |d|,   dh = d / l
+ *   r_aim   = n - dh       (R^3; |r_aim| = 2 sin(theta / 2), theta the angle between the axis and the line of sight: zero only
+ *                           when aligned and monotone up to theta = pi -- not n x dh, which is also zero looking away)
+ *   r_range = l - rho
+ *   l(t, x, u) += 1/2 sum_i (w_aim |r_aim|^2 + w_range r_range^2)      t < T
+ *   lf(x_T)    += the same with row T
+ * to whatever the context optimises otherwise.  Derivatives in the tangent at x, on the tangent columns c of path(j_i) only, with
+ * point_column(c, p) as in the relative-frame text (a_c x (p - o_c) revolute, a_c prismatic; a free-flyer root's six columns by
+ * the conventions of DDP_HIP_FLAG_FRAME_COST and DDP_HIP_FLAG_FRAME_ORIENT_COST: R_0 e_c and (R_0 e_c) x (p - o_0), the latter
+ * three carrying the rotation axis R_0 e_c):
+ *   J_aim[:, c] = (a_c x n, where c carries rotation)  +  (I - dh dh^T) point_column(c, p) / l
+ *   J_range[c]  = -dh . point_column(c, p)
+ *   lx[q rows] += J^T (w o r),   lxx[q, q] += J^T diag(w) J,   lfx / lfxx alike at T.
+ * lxx is Gauss-Newton (sum_a w_a r_a d^2 r_a is dropped: exact where r = 0, positive semidefinite): frames ascending, the three
+ * aim rows first, then the range row, entry (i, j) formed in (min, max) order: symmetric bit for bit, no atomics.  Velocity rows
+ * and columns, lu, luu, lux and every q row off the live frames' paths are not written.  A term of weight 0 is left out (not
+ * multiplied by 0): a frame with both weights 0 is not walked, with w_aim = 0 no aim row is formed, with w_range = 0 rho is not
+ * read, and with nothing uploaded or every weight 0 a context computes bit for bit what it computes without the flag.  The
+ * degenerate line of sight: where l <= 1e-12 the direction to the target does not exist, and frame i forms nothing at that
+ * (b, t) -- no value and no derivative, of the aim rows and of the range row alike.  The data travels through ddp_hip_frame_aim_*
+ * below; at create no frames are set.  Tree models only (the pendulum: DDP_HIP_E_UNSUPPORTED).  The flag combines with every other
+ * flag: the terms are formed by kernels of their own, which add onto what the other terms' kernels leave (after the
+ * control-gravity terms', before the obstacles'). */
+#define DDP_HIP_FLAG_FRAME_AIM_COST 16384u
+#define DDP_HIP_MAX_AIM_FRAMES 4
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -551,6 +585,23 @@ int ddp_hip_relative_frame_error(ddp_hip_ctx* ctx, int which, double* out);
  * non-finite offset, a negative or non-finite weight and a non-zero weight on one of a free-flyer root's six rows. */
 int ddp_hip_control_grav_cost_upload(ddp_hip_ctx* ctx, const double* offset, const double* weight, int64_t first_instance, int64_t n_instances);
 int ddp_hip_control_grav_cost_download(ddp_hip_ctx* ctx, double* offset, double* weight, int64_t first_instance, int64_t n_instances);
+/* The aim frames of a context created with DDP_HIP_FLAG_FRAME_AIM_COST (else DDP_HIP_E_UNSUPPORTED), shared by the batch:
+ * joint[n_frames], off[n_frames][3], axis[n_frames][3].  DDP_HIP_E_ARG for n_frames outside 0 .. DDP_HIP_MAX_AIM_FRAMES, a joint
+ * outside the model, a non-finite offset and an axis whose length differs from 1 by more than 1e-10 (the quaternions' rule).  It
+ * may be called again: with the same count and the same joints the per-instance data stays (the points and the axes may move),
+ * otherwise targets, stand-offs and weights are reset to 0.  n_frames = 0 takes the frames away. */
+int ddp_hip_frame_aim_set_frames(ddp_hip_ctx* ctx, int32_t n_frames, const int32_t* joint, const double* off, const double* axis);
+/* The frames' targets and weights, stream-ordered like ddp_hip_frame_cost_upload.  Host arrays [n_instances][T+1][n_frames][4] =
+ * (g, rho) and [n_instances][T+1][n_frames][2] = (w_aim, w_range); a NULL pointer leaves that side as it is.  An upload is refused
+ * as a whole (DDP_HIP_E_ARG, nothing written) before ddp_hip_frame_aim_set_frames, for a bad instance range, a non-finite target
+ * or stand-off, a negative stand-off and a negative or non-finite weight. */
+int ddp_hip_frame_aim_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first_instance, int64_t n_instances);
+int ddp_hip_frame_aim_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first_instance, int64_t n_instances);
+/* "Did it stay in view, from how far": out[batch][T+1][n_frames][2] (host) = (theta, l) of every frame along X (which = 0) or
+ * X_NEW (which = 1), against the resident targets: theta in radians, the angle between the axis and the line of sight, formed as
+ * atan2(|n x dh|, n . dh), and l the distance from the eye to the target (theta = 0 where l <= 1e-12).  From the first
+ * ddp_hip_frame_aim_set_frames with a frame on (before: DDP_HIP_E_ARG), live weights or not. */
+int ddp_hip_frame_aim_error(ddp_hip_ctx* ctx, int which, double* out);
 
 /* make_trajectory (ddp.hpp:392-415): X[0] and U given -> X[1..T] */
 int ddp_hip_rollout(ddp_hip_ctx* ctx);
@@ -722,6 +773,13 @@ int ddp_hip_model_relative_frame(ddp_hip_model_handle* h, int32_t joint_a, const
  * entries off the pattern are 0), formed by the traversal the cost kernels use.  A free-flyer root's six rows are returned as
  * well: the definition covers them, only the cost leaves them out.  For targets and warm starts: "start from U = g(q0)" */
 int ddp_hip_model_gravity_torque(ddp_hip_model_handle* h, const double* q, double* g, double* G);
+/* The eye and the axis of the aim frame (joint, off, axis) of a tree model at the configuration q, as DDP_HIP_FLAG_FRAME_AIM_COST
+ * defines them: p3 the point's world position, n3 = R_j axis the axis' world direction and, where not NULL, J as 6 x nv
+ * column-major: the rows of p (point_column), then the rows of n (a_c x n where column c carries rotation), formed by the
+ * traversal the cost kernels use (columns off the joint's path are 0).  An axis off unit length (1e-10): DDP_HIP_E_ARG.  For
+ * targets such as "what it looks at now, one metre ahead: g = p + n" */
+int ddp_hip_model_frame_axis(ddp_hip_model_handle* h, int32_t joint, const double off[3], const double axis[3], const double* q, double* p3,
+                             double* n3, double* J);
 
 /* ---- built-in seeded model tables (no URDF exists offline: SURVEY.md D4, 8d) -------------- */
 /* ..._FF: the same robots on a free-flyer root instead of a fixed base / 3 prismatic + 3 revolute base joints */
