@@ -453,6 +453,7 @@ struct FwdPipeLds {
   double k[nu], uo[nu], xo[n];
   double dx[NC * n], x[2 * NC * n], u[NC * nu], qdd[NC * nu];
   rbd::CoopModel<NJ> model;
+  int u_step;                                      // the hand-off inside a step: the t whose u_t is whole in `u` (rbd::lds_post / lds_await)
 };
 template <int NJ>
 struct FwdPipeLdsBox : FwdPipeLds<NJ> {
@@ -465,8 +466,15 @@ static bool fwd_use_pipe(const ddp_hip_ctx* ctx, int64_t batch, int n_alpha) {
   return !ctx->sw.fwd_no_pipe && batch * ((n_alpha + 1) / 2) <= ctx->cu_count;
 }
 
+// The pipelined instantiations that run the third wave (the assistant, below).  Five closed-loop ones spilled 4 to 8 bytes more
+// per lane with it than without (profiles/summary_fwd_assist.txt): those keep the two-wave pipelined body
+constexpr bool fwd_pipe_assist(bool open, bool ff, int cost, bool box) {
+  if (open || box) return true;
+  return ff ? cost != 3 && cost != 6 && cost != 7 : cost != 3 && cost != 10;
+}
+
 #ifdef FWD_STAMPS
-__device__ unsigned long long g_fwd_stamps[24];   // the leading wave's phases | the pipelined form's helper wave's
+__device__ unsigned long long g_fwd_stamps[36];   // the leading wave's phases | the pipelined form's helper wave's | its assistant wave's
 #endif
 
 // OPEN: the open-loop rollout of make_trajectory (ddp.hpp:392-415) on the same machinery: one candidate, u = U as given, x to X
@@ -484,10 +492,15 @@ __device__ unsigned long long g_fwd_stamps[24];   // the leading wave's phases |
 // it at the start of step t and runs the q-part of step t + 1's traversal (rbd::aba_pipe_q: placements, inertia sums, U, 1/D, Ia,
 // X^T Ia X) into the record buffer (t + 1) & 1 while the leading wave runs step t's x-part (rbd::aba_pipe_x) on buffer t & 1; the
 // two meet at ONE workgroup barrier per step.  Two candidates per workgroup (FwdPipeLds), grid = instances x ceil(n_alpha / 2).
-// Iteration t = -1 is the prologue: the helper forms the q-part of step 0, the leading wave waits.  Every early return above the
-// loop is workgroup-uniform and both waves run T + 1 iterations with one barrier each, whatever `live` is
+// Iteration t = -1 is the prologue: the helper forms the q-part of step 0, the other waves wait.  A third wave, the assistant,
+// takes everything of step t that needs x_t but not the dynamics: dx, K_t dx, u_t (to LDS, to fw_u), the inline cost terms and
+// their sum, the prefetch of step t + 1's operands and their parking.  Pass 1 of the x-part reads no control, so the leading wave
+// starts it right after the barrier and waits for u_t only between pass 1 and pass 2 (S.u_step: rbd::lds_post / lds_await; the
+// assistant never waits on the leading wave ahead of its post).  K_t, k_t, u_old, x_old, lo_t, hi_t in LDS are the assistant's
+// alone.  Every early return above the loop is workgroup-uniform and all three waves run T + 1 iterations with one barrier each,
+// whatever `live` is.  (ASSIST: where fwd_pipe_assist says no, wave 0 keeps those parts ahead of pass 1 and there is no third wave)
 template <int NJ, bool OPEN = false, bool FF = false, int COST = 0, bool BOX = false, bool PIPE = false>
-__global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
+__global__ __launch_bounds__(PIPE && fwd_pipe_assist(OPEN, FF, COST, BOX) ? 192 : 128) void forward_kernel_lat2(FwdParams p) {
   static_assert(!(OPEN && BOX), "the open-loop rollout applies U as given");
   constexpr bool TRACK = (COST & 1) != 0, FRAME = (COST & 2) != 0, LIMIT = (COST & 4) != 0, ORIENT = (COST & 8) != 0;
   static_assert(!ORIENT || FRAME, "the orientation terms are of the cost frames: bit 3 implies bit 1");
@@ -505,14 +518,16 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
   if (!OPEN && p.state[b] != 0) return;
   if (half * NC >= na) return;
   // two waves: wave 0 runs the rollout, wave 1 joins it for the inertia half of the leaf -> root pass (rbd::aba_tree_coop2w), or
-  // runs one step ahead of it (PIPE)
+  // runs one step ahead of it (PIPE); ASSIST: wave 2, the assistant, forms the controls, the cost and the prefetch beside wave 0
+  constexpr bool ASSIST = PIPE && fwd_pipe_assist(OPEN, FF, COST, BOX);
+  constexpr int CTRL = ASSIST ? 2 : 0;               // the wave that owns u_t, dsum and request / park
   const int wave = threadIdx.x / 64, tid = threadIdx.x % 64, al0 = tid / NH, h = tid % NH;
   const int al = al0 < NC ? al0 : NC - 1;            // (PIPE: the upper lanes of a wave have no candidate; they stay inside the arrays)
   const int a = half * NC + al;
   const int cand = p.round * na + a;
   const bool mine = al0 < NC && a < na;
   const bool live = mine && cand <= 33;              // 2^-34 < 1e-10: never tried (ddp_fwd.ipp:35-37)
-  if (!OPEN && mine && cand > 33 && h == 0 && wave == 0) p.fw_dcost[(int64_t)b * na + a] = INFINITY;
+  if (!OPEN && mine && cand > 33 && h == 0 && wave == CTRL) p.fw_dcost[(int64_t)b * na + a] = INFINITY;
   const double step = ldexp(1.0, -cand);
   const int64_t T = p.d.T;
   const double* xo = p.x_old + (int64_t)b * (T + 1) * nx;
@@ -588,20 +603,23 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
     }
   };
   static_assert(nx <= 128, "x_old is parked by two words per lane");
+  // ASSIST: u_t is whole in S.u: the leading wave's pass 2 may start.  Every path of the control wave through step t posts once
+  auto post_u = [&](int64_t t) { if constexpr (ASSIST) { if (tid == 0) rbd::lds_post(&S.u_step, (int)t); } };
   double cold_t = 0.0, dsum = 0.0;
   const double mc = p.model->c, mdt = p.model->dt;
-  if (wave == 0) {
+  if (wave == CTRL) {
     request(0);
     const double* x0 = OPEN ? xw : p.x_new + (int64_t)b * (T + 1) * nx;   // x_new,0 is preset by the caller (ddp.hpp:752)
     if (live)
       for (int i = h; i < nx; i += NH) { const double v = x0[i]; x[i] = v; if (!OPEN) xw[i] = v; }
     park();
     cold_t = coldreg;
+    if constexpr (ASSIST) { if (tid == 0) S.u_step = -1; }
   }
-  rbd::wg_sync_lds();                              // the model tables are in LDS for both waves
+  rbd::wg_sync_lds();                              // the model tables are in LDS for all waves
   // one loop, one call site of the traversal for all waves (a second call site keeps the compiler from inlining it): the helper
   // waves skip the rollout's own parts and meet wave 0 at the traversal's workgroup barriers
-  const bool lead = wave == 0;
+  const bool lead = wave == 0, ctrl = wave == CTRL;
   rbd::FwdStamp* fs = nullptr;
 #ifdef FWD_STAMPS
   rbd::FwdStamp fsv{};
@@ -610,10 +628,11 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
 #endif
   for (int64_t t = PIPE ? -1 : 0; t < T; ++t) {
     if constexpr (PIPE) x = S.x + ((int)(t & 1) * NC + al) * XS;   // x_t; t = -1: the prologue
-    if (lead && (!PIPE || t >= 0)) {
+    if (ctrl && (!PIPE || t >= 0)) {
     if constexpr (OPEN) {
       if (live)
         for (int i = h; i < nu; i += NH) u[i] = S.uo[i];
+      if constexpr (ASSIST) { rbd::coop_sync<true>(); post_u(t); }
     } else {
     if constexpr (FF) {
       if (live) {                                                              // :45 difference(out, old, new) on SE(3) x R^(nv-6) x R^nv
@@ -655,6 +674,7 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
       }
     }
     rbd::coop_sync<true>();
+    post_u(t);
     FSTAMP(fs, 0);
     double c_track = 0.0;
     if constexpr (TRACK) c_track = track_lanes_sum<FF>(p, b, t, x, u, h, live);
@@ -678,7 +698,8 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
       double* xn = S.x + ((int)((t + 1) & 1) * NC + al) * XS;                    // x_{t+1}: q by the helper, v by the leading wave
       if (lead) {
         if (t >= 0) {
-          rbd::aba_pipe_x<NJ, NC, NH, rbd::CoopModel<NJ>, FF>(S.model, S.rec[t & 1], x + nq, u, qdd, S.state, al, h, live, fs);   // :50
+          rbd::aba_pipe_x<NJ, NC, NH, rbd::CoopModel<NJ>, FF>(S.model, S.rec[t & 1], x + nq, u, qdd, S.state, al, h, live, fs,
+                                                              [&]() { if constexpr (ASSIST) rbd::lds_await(&S.u_step, (int)t); });   // :50
           if (live)
             for (int i = h; i < NJ; i += NH) {                                  // dynamics_t::eval_to, problem.hpp:441-461: the velocities
               const double vn = x[nq + i] + qdd[i] * mdt;
@@ -686,9 +707,14 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
               xw[(t + 1) * nx + nq + i] = vn;
             }
           FSTAMP(fs, 7);
-          if (t + 1 < T) { park(); cold_t = coldreg; }
-          FSTAMP(fs, 8);
+          if constexpr (!ASSIST) {
+            if (t + 1 < T) { park(); cold_t = coldreg; }
+            FSTAMP(fs, 8);
+          }
         }
+      } else if (ASSIST && ctrl) {
+        if (t >= 0 && t + 1 < T) { park(); cold_t = coldreg; }   // this wave's own reads of step t are behind it
+        FSTAMP(fs, 8);
       } else {
         if (t >= 0) {
           // ... the configuration: the one expression q_{t+1} comes from
@@ -713,7 +739,7 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
         if (t + 1 < T) rbd::aba_pipe_q<NJ, NC, NH, rbd::CoopModel<NJ>, FF>(S.model, xn, S.rec[(t + 1) & 1], S.z, al, h, live, fs);
       }
       rbd::wg_sync_lds();                            // the step's one barrier: x_{t+1} and its record are whole
-      FSTAMP(fs, lead ? 3 : 5);
+      FSTAMP(fs, wave == 1 ? 5 : 3);
       if (lead && t >= 0 && live)
         for (int i = h; i < nq; i += NH) xw[(t + 1) * nx + i] = xn[i];
       continue;
@@ -760,11 +786,11 @@ __global__ __launch_bounds__(128) void forward_kernel_lat2(FwdParams p) {
 #endif
   if constexpr (PIPE) x = S.x + ((int)(T & 1) * NC + al) * XS;                   // x_T
   double c_term = 0.0;
-  if constexpr (TRACK) { if (lead) c_term = track_lanes_sum<FF>(p, b, T, x, u, h, live); }
-  if constexpr (FRAME && !ORIENT) { if (lead) c_term += frame_lanes_sum<FF>(p, S.model, b, T, x, h, live); }
-  if constexpr (ORIENT) { if (lead) c_term += frame_orient_lanes_sum<FF>(p, S.model, b, T, x, h, live); }
-  if constexpr (LIMIT) { if (lead) c_term += limit_lanes_sum<FF>(p, b, T, x, h, live); }
-  if (!OPEN && h == 0 && live && lead && p.cost_inline) {
+  if constexpr (TRACK) { if (ctrl) c_term = track_lanes_sum<FF>(p, b, T, x, u, h, live); }
+  if constexpr (FRAME && !ORIENT) { if (ctrl) c_term += frame_lanes_sum<FF>(p, S.model, b, T, x, h, live); }
+  if constexpr (ORIENT) { if (ctrl) c_term += frame_orient_lanes_sum<FF>(p, S.model, b, T, x, h, live); }
+  if constexpr (LIMIT) { if (ctrl) c_term += limit_lanes_sum<FF>(p, b, T, x, h, live); }
+  if (!OPEN && h == 0 && live && ctrl && p.cost_inline) {
     dsum += c_term - cold[T];
     p.fw_dcost[(int64_t)b * na + a] = dsum;
   }
@@ -1387,8 +1413,8 @@ void fwd_teardown(ddp_hip_ctx* ctx) {
 }
 
 #ifdef FWD_STAMPS
-extern "C" int ddp_hip_debug_fwd_stamps(unsigned long long* out24) {
-  return hipMemcpyFromSymbol(out24, HIP_SYMBOL(g_fwd_stamps), sizeof(unsigned long long) * 24) == hipSuccess ? 0 : -2;
+extern "C" int ddp_hip_debug_fwd_stamps(unsigned long long* out36) {
+  return hipMemcpyFromSymbol(out36, HIP_SYMBOL(g_fwd_stamps), sizeof(unsigned long long) * 36) == hipSuccess ? 0 : -2;
 }
 #endif
 
@@ -1399,7 +1425,7 @@ extern "C" int ddp_hip_rollout(ddp_hip_ctx* ctx) {
   if (fwd_lat_supported(ctx)) {
     // unconstrained trees of the Talos size: the open-loop form of the latency kernel (one workgroup per instance)
     const bool pipe = fwd_use_pipe(ctx, ctx->d.batch, 1);
-    hipLaunchKernelGGL(lat2_open_kernel(ctx->model_h.ff != 0, pipe), dim3((unsigned)ctx->d.batch), dim3(128), lat2_lds(false, pipe), ctx->stream, p);
+    hipLaunchKernelGGL(lat2_open_kernel(ctx->model_h.ff != 0, pipe), dim3((unsigned)ctx->d.batch), dim3(pipe && fwd_pipe_assist(true, ctx->model_h.ff != 0, 0, false) ? 192 : 128), lat2_lds(false, pipe), ctx->stream, p);
   } else {
     const int bs = 64;
     const unsigned grid = (unsigned)((ctx->d.batch + bs - 1) / bs);
@@ -1610,11 +1636,12 @@ extern "C" int ddp_hip_forward(ddp_hip_ctx* ctx, const double* mu, int32_t n_alp
     if (lat_path) {
       // the pipelined form while its grid fits the device (fwd_use_pipe), else four candidates per workgroup
       const bool pipe = fwd_use_pipe(ctx, B, n_alpha);
-      const dim3 g((unsigned)(pipe ? B * ((n_alpha + 1) / 2) : 2 * B)), blk(128);
+      const dim3 g((unsigned)(pipe ? B * ((n_alpha + 1) / 2) : 2 * B));
       // the cost terms an unconstrained problem forms inline: bit 0 tracking, bit 1 frames, bit 2 state limits (forward_kernel_lat2: COST)
       // bit 3 the frame orientations, which imply bit 1
       const int cost = p.cost_inline ? (p.track ? 1 : 0) | (p.fc.target ? 2 : 0) | (p.sl.weight ? 4 : 0) | (p.fc.oquat ? 10 : 0) : 0;
       const bool box = p.ctrl_lo != nullptr;
+      const dim3 blk(pipe && fwd_pipe_assist(false, ctx->model_h.ff != 0, cost, box) ? 192 : 128);   // (the pipelined form's third wave)
       hipLaunchKernelGGL(lat2_kernel(ctx->model_h.ff != 0, cost, box, pipe), g, blk, lat2_lds(box, pipe), ctx->stream, p);
       if (!p.cost_inline) {
         const dim3 gc((unsigned)((B * n_alpha * (d.T + 1) + 63) / 64));

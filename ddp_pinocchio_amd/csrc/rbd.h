@@ -1224,10 +1224,26 @@ __device__ __forceinline__ void aba_pipe_q(const M& m, const double* q, double* 
   }
 }
 
-// the x-part from a finished record `rec` of q; `xst`: its own per-joint slots.  One wave; every lane of it calls
-template <int NJ, int TPB, int NH, class M, bool FF = false>
+// A hand-off between two waves of a workgroup through one LDS word: the producer posts a number behind its LDS stores (a wave's
+// LDS operations are processed in order; the s_waitcnt is the belt to those braces), the consumer sleeps until it reads that
+// number.  The word is read by all lanes and compared on the scalar side, so the loop is a scalar branch.  The producer must not
+// wait on the consumer ahead of its post, and both waves must be resident together (waves of one workgroup are)
+__device__ __forceinline__ void lds_post(int* word, int value) {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  *(volatile int*)word = value;
+}
+__device__ __forceinline__ void lds_await(const int* word, int value) {
+  while (__builtin_amdgcn_readfirstlane(*(volatile const int*)word) != value) __builtin_amdgcn_s_sleep(1);
+  asm volatile("" ::: "memory");
+}
+struct NoHandOff { __device__ __forceinline__ void operator()() const {} };
+
+// the x-part from a finished record `rec` of q; `xst`: its own per-joint slots.  One wave; every lane of it calls.  Pass 1 reads
+// v only; `tau_ready` is invoked between pass 1 and pass 2, ahead of the first read of tau (forward_kernel_lat2: the wait for the
+// wave that forms the controls)
+template <int NJ, int TPB, int NH, class M, bool FF = false, class HandOff = NoHandOff>
 __device__ __forceinline__ void aba_pipe_x(const M& m, const double* rec, const double* v, const double* tau, double* qdd,
-                                           double* xst, int cand, int h, bool live, FwdStamp* fs = nullptr) {
+                                           double* xst, int cand, int h, bool live, FwdStamp* fs = nullptr, HandOff tau_ready = HandOff()) {
   auto VI = [](int i) { return FF ? i + 5 : i; };
   auto Q = [&](int joint, int slot) -> const double& { return rec[(joint * ABA_PIPE_QSLOTS + slot) * TPB + cand]; };
   auto S = [&](int joint, int slot) -> double& { return xst[(joint * ABA_PIPE_XSLOTS + slot) * TPB + cand]; };
@@ -1255,6 +1271,8 @@ __device__ __forceinline__ void aba_pipe_x(const M& m, const double* rec, const 
     coop_sync<true>();
   }
   FSTAMP(fs, 4);
+  tau_ready();
+  FSTAMP(fs, 0);
   for (int L = NL - 1; L >= 0; --L) {              // pass 2, leaves -> root: the forces
     const unsigned long long rr = m.role[L * NH + h];
     if (live && role_joint(rr) != 255) {
