@@ -35,6 +35,7 @@ FLAG_MOMENTUM_COST = 2048
 FLAG_RELATIVE_FRAME_COST = 4096
 FLAG_CONTROL_GRAV_COST = 8192
 FLAG_FRAME_AIM_COST = 16384
+FLAG_BALANCE_REGION_COST = 32768
 MAX_COST_FRAMES = 4
 MAX_COLLISION_POINTS, MAX_OBSTACLES = 16, 8
 MAX_COLLISION_PAIRS = 32
@@ -83,6 +84,8 @@ EXPORTS = [
     "ddp_hip_control_grav_cost_upload", "ddp_hip_control_grav_cost_download", "ddp_hip_model_gravity_torque",
     "ddp_hip_frame_aim_set_frames", "ddp_hip_frame_aim_upload", "ddp_hip_frame_aim_download", "ddp_hip_frame_aim_error",
     "ddp_hip_model_frame_axis",
+    "ddp_hip_balance_region_set_planes", "ddp_hip_balance_region_upload", "ddp_hip_balance_region_download",
+    "ddp_hip_balance_region_margin", "ddp_hip_model_capture_point",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -210,6 +213,12 @@ def lib():
         L.ddp_hip_frame_aim_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_frame_aim_error.argtypes = [C.c_void_p, C.c_int, _dp]
         L.ddp_hip_model_frame_axis.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]
+    if hasattr(L, "ddp_hip_balance_region_upload"):  # (likewise: set_balance_region_planes, set_balance_region_cost, balance_region_margin, ModelHandle.capture_point)
+        L.ddp_hip_balance_region_set_planes.argtypes = [C.c_void_p, C.c_int32]
+        L.ddp_hip_balance_region_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_balance_region_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_balance_region_margin.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.ddp_hip_model_capture_point.argtypes = [C.c_void_p, _dp, _dp, C.c_double, _dp, _dp, _dp]
     L.ddp_hip_rollout.argtypes = [C.c_void_p]
     L.ddp_hip_linearize.argtypes = [C.c_void_p]
     L.ddp_hip_linearize_stages.argtypes = [C.c_void_p, C.c_uint32]
@@ -421,6 +430,16 @@ class ModelHandle:
         _check(lib().ddp_hip_model_frame_axis(self._h, int(joint), _ptr(off), _ptr(axis), _ptr(q), _ptr(p3), _ptr(n3),
                                               _ptr(J) if jacobian else None), "model_frame_axis")
         return (p3, n3, J.reshape(self.nv, 6).T.copy()) if jacobian else (p3, n3)
+
+    def capture_point(self, q, v, tau, jacobian=False):
+        """The test point xi = c + tau cdot of FLAG_BALANCE_REGION_COST (ddp_hip.h) at the state (q, v) as (3,): the centre of mass
+        at tau = 0, the capture point at tau = sqrt(z_c / g); with jacobian=True (xi, Jq, Jv), Jq = Jc + tau d cdot / d(delta q)
+        and Jv = tau Jc as (3, nv).  For targets such as the plane 4 cm behind where the capture point is now"""
+        q, v = _f64(q), _f64(v)
+        xi, Jq, Jv = np.zeros(3), np.zeros(3 * self.nv), np.zeros(3 * self.nv)
+        _check(lib().ddp_hip_model_capture_point(self._h, _ptr(q), _ptr(v), float(tau), _ptr(xi), _ptr(Jq) if jacobian else None,
+                                                 _ptr(Jv) if jacobian else None), "model_capture_point")
+        return (xi, Jq.reshape(self.nv, 3).T.copy(), Jv.reshape(self.nv, 3).T.copy()) if jacobian else xi
 
     def gravity_torque(self, q, jacobian=False):
         """The generalised gravity torque g(q) of a tree model as (nv,): the control that holds the robot at rest, aba(q, 0, g) = 0,
@@ -726,6 +745,39 @@ class Context:
         live weights or not: the angle between the axis and the line of sight in radians, and the distance to the target"""
         out = np.zeros((self.batch, self.spec.T + 1, getattr(self, "n_aim_frames", 0), 2))
         _check(lib().ddp_hip_frame_aim_error(self._h, int(which), _ptr(out)), "frame_aim_error")
+        return out
+
+    def set_balance_region_planes(self, n_planes):
+        """The plane count (0 .. MAX_REGION_PLANES) of a context created with FLAG_BALANCE_REGION_COST (ddp_hip.h), shared by the
+        batch.  With the same count as before the per-instance data stays, else geometry and weights are reset to 0; 0 takes the
+        planes away"""
+        _check(lib().ddp_hip_balance_region_set_planes(self._h, int(n_planes)), "balance_region_set_planes")
+        self.n_region_planes = int(n_planes)
+
+    def set_balance_region_cost(self, geom=None, weight=None, first=0, count=None):
+        """The balance-region terms of instances first .. first + count - 1 (a context created with FLAG_BALANCE_REGION_COST;
+        ddp_hip.h), of the P plane slots of set_balance_region_planes.  geom: (n, h, tau) -- a unit normal in world axes, the
+        offset and the time constant >= 0 of the tested point c + tau cdot (free side n . xi - h >= 0) -- as (P, 5) for every
+        instance and t, (T+1, P, 5) for every instance or (count, T+1, P, 5); weight: >= 0, as (P,), (T+1, P) or (count, T+1, P).
+        None leaves that side as it is.  The plane count is the one this object last passed to set_balance_region_planes; before
+        that call there is no shape to check against and the call raises ValueError."""
+        T1, P = self.spec.T + 1, getattr(self, "n_region_planes", 0)
+        if not P:
+            raise ValueError("set_balance_region_cost: no planes yet, call set_balance_region_planes first")
+        count, arrs = self._cost_sides("set_balance_region_cost", (("geom", geom, (T1, P, 5), ((P, 5),)), ("weight", weight, (T1, P), ((P,),))),
+                                       first, count)
+        self._cost_upload(lib().ddp_hip_balance_region_upload, "balance_region_upload", arrs, first, count)
+
+    def get_balance_region_cost(self, first=0, count=None):
+        """(geom, weight) of instances first .. first + count - 1: (count, T+1, P, 5) and (count, T+1, P)"""
+        T1, P = self.spec.T + 1, getattr(self, "n_region_planes", 0)    # (0 before set_balance_region_planes: empty arrays)
+        return self._cost_download(lib().ddp_hip_balance_region_download, "balance_region_download", ((T1, P, 5), (T1, P)), first, count)
+
+    def balance_region_margin(self, which=0):
+        """(batch, T+1): the least d_o = n . (c + tau cdot) - h over the planes of non-zero weight along X (which = 0) or X_NEW
+        (which = 1); +inf where no plane is live, negative where the tested point has left the region"""
+        out = np.zeros((self.batch, self.spec.T + 1))
+        _check(lib().ddp_hip_balance_region_margin(self._h, int(which), _ptr(out)), "balance_region_margin")
         return out
 
     def set_relative_frame_pairs(self, pairs):

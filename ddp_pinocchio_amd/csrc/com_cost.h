@@ -61,30 +61,32 @@ __device__ __forceinline__ void com_fold(const double* mass, const double* mp, i
 }
 
 // Jc by a wave, step 1 of 2: lane j < nj walks its joint's path once, m_j c_j riding along, and leaves its record in S.  (A
-// workgroup barrier follows.)
-__device__ __forceinline__ void com_stage_lane(const DevModel& m, const double* q, int j, CoMWaveLds& S) {
+// workgroup barrier follows.)  Both steps come in a form that takes the record's parts: the balance-region kernels keep the same
+// records inside the momentum's staged record (balance_region_cost.h)
+__device__ __forceinline__ void com_stage_lane(const DevModel& m, const double* q, int j, JointWorldLds& jw, double* sm, double (*smp)[3]) {
   double d[1][3];
   const double mass = body_mass_com(m, j, d[0]);
-  stage_joint_lane<1>(m, q, j, S.jw, d);
-  S.m[j] = mass;
+  stage_joint_lane<1>(m, q, j, jw, d);
+  sm[j] = mass;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) S.mp[j][k] = mass * S.jw.o[j][k] + d[0][k];
+  for (int k = 0; k < 3; ++k) smp[j][k] = mass * jw.o[j][k] + d[0][k];
 }
+__device__ __forceinline__ void com_stage_lane(const DevModel& m, const double* q, int j, CoMWaveLds& S) { com_stage_lane(m, q, j, S.jw, S.m, S.mp); }
 
 // ... step 2 of 2: lane j < nj forms the mass and the first moment of its subtree by running over the records in ascending
 // order and testing bit j of each record's path (a fixed order, no atomics), the totals alike, and from them its column(s) of
 // Jc; lane 0 leaves c(q) as well.  The column is (f a_j) x lever, not point_column's a_j x lever scaled by f afterwards: scaling
 // before the cross product rounds differently from scaling after it.  (A workgroup barrier follows.)
-__device__ __forceinline__ void com_column_lane(const DevModel& m, int j, CoMWaveLds& S) {
+__device__ __forceinline__ void com_column_lane(const DevModel& m, int j, const JointWorldLds& W, const double* sm, const double (*smp)[3],
+                                                double* sJ, double* sc) {
   const int nj = m.nj;
-  const JointWorldLds& W = S.jw;
   double M = 0.0, tot[3] = {0.0, 0.0, 0.0}, msub = 0.0, sub[3] = {0.0, 0.0, 0.0};
   for (int i = 0; i < nj; ++i) {
-    const double mi = S.m[i];
-    M += mi; tot[0] += S.mp[i][0]; tot[1] += S.mp[i][1]; tot[2] += S.mp[i][2];
-    if ((W.mask[i] >> j) & 1) { msub += mi; sub[0] += S.mp[i][0]; sub[1] += S.mp[i][1]; sub[2] += S.mp[i][2]; }
+    const double mi = sm[i];
+    M += mi; tot[0] += smp[i][0]; tot[1] += smp[i][1]; tot[2] += smp[i][2];
+    if ((W.mask[i] >> j) & 1) { msub += mi; sub[0] += smp[i][0]; sub[1] += smp[i][1]; sub[2] += smp[i][2]; }
   }
-  if (j == 0) { S.c[0] = tot[0] / M; S.c[1] = tot[1] / M; S.c[2] = tot[2] / M; }
+  if (j == 0) { sc[0] = tot[0] / M; sc[1] = tot[1] / M; sc[2] = tot[2] / M; }
   const double f = msub / M;
   double lever[3] = {0.0, 0.0, 0.0};
   if (msub != 0.0) { lever[0] = sub[0] / msub - W.o[j][0]; lever[1] = sub[1] / msub - W.o[j][1]; lever[2] = sub[2] / msub - W.o[j][2]; }
@@ -92,15 +94,16 @@ __device__ __forceinline__ void com_column_lane(const DevModel& m, int j, CoMWav
     // the free-flyer root (body twists, linear part first): its subtree is the whole robot, f = 1 and lever = c - o_0
     for (int cc = 0; cc < 3; ++cc) {
       const double e[3] = {f * W.R0[cc], f * W.R0[3 + cc], f * W.R0[6 + cc]};
-      S.J[3 * cc] = e[0]; S.J[3 * cc + 1] = e[1]; S.J[3 * cc + 2] = e[2];
-      cross3(e, lever, S.J + 3 * (3 + cc));
+      sJ[3 * cc] = e[0]; sJ[3 * cc + 1] = e[1]; sJ[3 * cc + 2] = e[2];
+      cross3(e, lever, sJ + 3 * (3 + cc));
     }
     return;
   }
   const int vi = m.ff ? j + 5 : j;
   const double fa[3] = {f * W.a[j][0], f * W.a[j][1], f * W.a[j][2]};
-  if (m.jtype[j] == DDP_HIP_JOINT_REVOLUTE) cross3(fa, lever, S.J + 3 * vi);
-  else { S.J[3 * vi] = fa[0]; S.J[3 * vi + 1] = fa[1]; S.J[3 * vi + 2] = fa[2]; }
+  if (m.jtype[j] == DDP_HIP_JOINT_REVOLUTE) cross3(fa, lever, sJ + 3 * vi);
+  else { sJ[3 * vi] = fa[0]; sJ[3 * vi + 1] = fa[1]; sJ[3 * vi + 2] = fa[2]; }
 }
+__device__ __forceinline__ void com_column_lane(const DevModel& m, int j, CoMWaveLds& S) { com_column_lane(m, j, S.jw, S.m, S.mp, S.J, S.c); }
 
 }  // namespace rbd

@@ -10,14 +10,17 @@
 
 // The terms.  The order in which the kernels add them (after the stage cost and the tracking cost) is stated where they are launched:
 // lin.hip launches one kernel per live term, fwd.hip forms the first three inline and walks kAddOn for the others, both in the order
-// frame positions, frame orientations, limits, CoM, frame velocities, momentum, relative frames, control-gravity, frame aiming,
-// obstacles, self-collision.  The enumerators are indices of ctx->cost[] and kCostDesc[] and follow that order but for
-// COST_CONTROL_GRAV and COST_FRAME_AIM: the host programs hold momentum, relative frames, obstacles and self-collision as neighbours
+// frame positions, frame orientations, limits, CoM, frame velocities, momentum, balance regions, relative frames, control-gravity,
+// frame aiming, obstacles, self-collision.  The enumerators are indices of ctx->cost[] and kCostDesc[] and follow that order but for
+// COST_CONTROL_GRAV, COST_FRAME_AIM and COST_BALANCE_REGION: the host programs hold momentum, relative frames, obstacles and self-collision as neighbours
 // and self-collision as the last (host/test_relative_frame_block.cpp, host/test_self_collision_block.cpp), so the term whose
 // additions come between the relative frames' and the obstacles' has its index in front of that run; they hold frame velocities and
 // control-gravity as neighbours too (host/test_control_grav_block.cpp), so the term whose additions come after control-gravity's
-// has its index in front of the frame velocities'.  No order is read off the enumerators
-enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_LIMITS, COST_COM, COST_FRAME_AIM, COST_FRAME_VEL, COST_CONTROL_GRAV, COST_MOMENTUM,
+// has its index in front of the frame velocities'; and they hold the CoM, frame aiming and the frame velocities as neighbours
+// (host/test_frame_aim_block.cpp), and momentum and the relative frames, so the term whose additions come between the momentum's and
+// the relative frames' has its index in front of the CoM's.  No order is read off the enumerators: the kernels' order is the
+// order of the launches in lin.hip and of kAddOn in fwd.hip, nothing else
+enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_LIMITS, COST_BALANCE_REGION, COST_COM, COST_FRAME_AIM, COST_FRAME_VEL, COST_CONTROL_GRAV, COST_MOMENTUM,
                           COST_RELATIVE_FRAME, COST_OBSTACLE, COST_SELF_COLLISION, COST_COUNT };
 
 enum CostFill : int32_t { FILL_ZERO, FILL_NEG_INF, FILL_POS_INF, FILL_QUAT };   // FILL_QUAT: identity quaternions (0, 0, 0, 1)
@@ -44,6 +47,7 @@ static const CostDesc kCostDesc[COST_COUNT] = {
     {DDP_HIP_FLAG_FRAME_COST, 2, {3, 3, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, false, false},          // target | weight, per frame
     {DDP_HIP_FLAG_FRAME_ORIENT_COST, 2, {4, 3, 0}, {FILL_QUAT, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, false, false},   // quat | weight, per frame
     {DDP_HIP_FLAG_STATE_LIMITS, 3, {1, 1, 1}, {FILL_NEG_INF, FILL_POS_INF, FILL_ZERO}, 0, true, false, false},                 // lo | hi | weight, per tangent row
+    {DDP_HIP_FLAG_BALANCE_REGION_COST, 2, {5, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_REGION_PLANES, false, true, false},   // (n, h, tau) | weight, per plane slot
     {DDP_HIP_FLAG_COM_COST, 2, {3, 3, 0}, {FILL_ZERO, FILL_ZERO, 0}, 1, true, true, false},                                    // target | weight
     {DDP_HIP_FLAG_FRAME_AIM_COST, 2, {4, 2, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_AIM_FRAMES, false, true, false},        // (target, stand-off) | (w_aim, w_range), per aim frame
     {DDP_HIP_FLAG_FRAME_VEL_COST, 2, {6, 6, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, true, false},       // target | weight, per frame
@@ -113,6 +117,16 @@ static inline bool cost_obstacle_geom_side(const CostCheck& c, const double* v, 
     } else if (fabs(sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) - 1.0) > 1e-10) {
       return false;
     }
+  }
+  return true;
+}
+// balance-region planes (n, h, tau): finite, a unit normal by the half-spaces' rule, a time constant tau >= 0
+static inline bool cost_region_geom_side(const CostCheck&, const double* v, int64_t words) {
+  for (int64_t k = 0; k < words; k += 5) {
+    const double* g = v + k;
+    if (!isfinite(g[0]) || !isfinite(g[1]) || !isfinite(g[2]) || !isfinite(g[3]) || !isfinite(g[4])) return false;
+    if (fabs(sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) - 1.0) > 1e-10) return false;
+    if (g[4] < 0.0) return false;
   }
   return true;
 }

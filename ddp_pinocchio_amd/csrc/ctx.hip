@@ -253,8 +253,8 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   if ((flags & DDP_HIP_FLAG_RELATIVE_FRAME_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the frame pairs alike
   if ((flags & DDP_HIP_FLAG_CONTROL_GRAV_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // g(q) is of a tree's bodies
   if ((flags & DDP_HIP_FLAG_FRAME_AIM_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // aim frames are frames of a tree's joints
-  if (flags & (DDP_HIP_FLAG_COM_COST | DDP_HIP_FLAG_MOMENTUM_COST)) {
-    if (mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the CoM, and the momentum about it, are of a tree's bodies
+  if (flags & (DDP_HIP_FLAG_COM_COST | DDP_HIP_FLAG_MOMENTUM_COST | DDP_HIP_FLAG_BALANCE_REGION_COST)) {
+    if (mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the CoM, the momentum about it and the capture point are of a tree's bodies
     if (!mo.mass_j || !mo.jtype) return DDP_HIP_E_ARG;
     double total = 0.0;
     for (int i = 0; i < (mo.jtype[0] == DDP_HIP_JOINT_FREEFLYER ? mo.nv - 5 : mo.nv); ++i) total += mo.mass_j[i];
@@ -361,7 +361,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipStreamSynchronize(ctx->stream));
   }
   for (int term = 0; term < COST_COUNT; ++term) {
-    // frames, aim frames, frame pairs, obstacle slots and self-collision pairs: no layout until they are set; limits (lo = -inf, hi = +inf, w = 0: no limit anywhere), CoM, momentum
+    // frames, aim frames, frame pairs, region planes, obstacle slots and self-collision pairs: no layout until they are set; limits (lo = -inf, hi = +inf, w = 0: no limit anywhere), CoM, momentum
     // and control-gravity (one item per control row, T rows): fixed
     CostBlock& k = ctx->cost[term];
     k.desc = &kCostDesc[term];
@@ -376,6 +376,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipMalloc(&ctx->rf_err_d, sizeof(double) * (size_t)(d.batch * (d.T + 1) * DDP_HIP_MAX_FRAME_PAIRS * 6)));
   if (flags & DDP_HIP_FLAG_FRAME_AIM_COST)
     CTX_TRY(hipMalloc(&ctx->fa_err_d, sizeof(double) * (size_t)(d.batch * (d.T + 1) * DDP_HIP_MAX_AIM_FRAMES * 2)));
+  if (flags & DDP_HIP_FLAG_BALANCE_REGION_COST) CTX_TRY(hipMalloc(&ctx->br_margin_d, sizeof(double) * (size_t)(d.batch * (d.T + 1))));
   int rc = bwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = fwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = lin_setup(ctx);
@@ -404,6 +405,7 @@ extern "C" int ddp_hip_destroy(ddp_hip_ctx* ctx) {
   if (ctx->sc_clear_d) (void)hipFree(ctx->sc_clear_d);
   if (ctx->rf_err_d) (void)hipFree(ctx->rf_err_d);
   if (ctx->fa_err_d) (void)hipFree(ctx->fa_err_d);
+  if (ctx->br_margin_d) (void)hipFree(ctx->br_margin_d);
   if (ctx->ne_d) (void)hipFree(ctx->ne_d);
   if (ctx->Epre_d) (void)hipFree(ctx->Epre_d);
   if (ctx->target_d) (void)hipFree(ctx->target_d);
@@ -787,6 +789,31 @@ extern "C" int ddp_hip_frame_aim_upload(ddp_hip_ctx* ctx, const double* target, 
 extern "C" int ddp_hip_frame_aim_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first, int64_t count) {
   double* host[] = {target, weight};
   return cost_block_download(ctx, COST_FRAME_AIM, host, first, count);
+}
+
+// a plane count shared by the batch; a plane (n, h, tau) and a weight per (instance, t, slot)
+extern "C" int ddp_hip_balance_region_set_planes(ddp_hip_ctx* ctx, int32_t n_planes) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_BALANCE_REGION_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (n_planes < 0 || n_planes > DDP_HIP_MAX_REGION_PLANES) return DDP_HIP_E_ARG;
+  if (n_planes != ctx->br_np) {
+    // another count is another layout: geometry and weights start again at 0
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int rc_ = cost_block_setup(ctx, COST_BALANCE_REGION, n_planes);
+    if (rc_ != DDP_HIP_OK) return rc_;
+  }
+  ctx->br_np = n_planes;
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_balance_region_upload(ddp_hip_ctx* ctx, const double* geom, const double* weight, int64_t first, int64_t count) {
+  const double* host[] = {geom, weight};
+  const CostSideOk ok[] = {cost_region_geom_side, cost_weight_side};
+  return cost_block_upload(ctx, COST_BALANCE_REGION, host, ok, first, count);
+}
+extern "C" int ddp_hip_balance_region_download(ddp_hip_ctx* ctx, double* geom, double* weight, int64_t first, int64_t count) {
+  double* host[] = {geom, weight};
+  return cost_block_download(ctx, COST_BALANCE_REGION, host, first, count);
 }
 
 extern "C" int ddp_hip_com_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first, int64_t count) {

@@ -11,6 +11,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "balance_region_cost.h"
 #include "com_cost.h"
 #include "control_grav_cost.h"
 #include "frame_aim_cost.h"
@@ -836,7 +837,7 @@ __global__ void cand_sum_kernel(FwdParams p) {
   p.fw_dcost[(int64_t)b * na + a] = dsum;
 }
 
-// The add-on cost kernels below (CoM, frame velocities, momentum, relative frames, control-gravity, frame aiming, obstacles) run over a list of `count` (trajectory, t) pairs, t = 0 .. T,
+// The add-on cost kernels below (CoM, frame velocities, momentum, balance regions, relative frames, control-gravity, frame aiming, obstacles) run over a list of `count` (trajectory, t) pairs, t = 0 .. T,
 // `na` trajectories per instance.  Pair e: which trajectory, which t, whose instance, which block bt1 = b (T+1) + t of the term's
 // data.  skip: nothing is written for this pair (past the list, or a candidate the rollout kernels skip: state != 0, beyond
 // 2^-33; state == nullptr: a resident trajectory, none is skipped).  live: the pair is evaluated (the kernels narrow it further)
@@ -1002,6 +1003,59 @@ __global__ __launch_bounds__(64) void momentum_cost_kernel(MomentumCostDev mo, c
     term = rbd::frame_vel_term(w, mo.target + pr.bt1 * 6, h, h + 3);
   }
   cost_pair_store(out, e, term, live, add);
+}
+
+// The balance-region terms (DDP_HIP_FLAG_BALANCE_REGION_COST, ddp_hip.h) of a list of states, added on top like the momentum terms
+// above: the same list, the same two uses, the same `lpe` lanes per evaluation.  Lane j walks joint j's path once with its body
+// alone (rbd::momentum_body with ang = false: no inertia, no jacobian, no per-joint arrays) and leaves m_j, m_j p_j and m_j pdot_j
+// in LDS; the group's first lane folds c in ascending order -- and cdot where a live plane of the row has tau != 0, else the
+// rates are not summed (rbd::region_fold) -- and runs over the planes in ascending order.  A plane with w == 0 or e == 0 is left
+// out, a state whose weights are all 0 is not walked, and a state without an active plane adds nothing (add != 0) or stores +0
+// (add == 0).  A non-finite state gives a NaN term, as com_cost_kernel's does.  MARGIN (ddp_hip_balance_region_margin): over the
+// (instance, t) pairs of one resident trajectory, min instead of sum: out[pair] = min over the planes with w != 0 of d_o, +inf
+// where none is live, NaN where a d is
+template <bool MARGIN>
+__device__ __forceinline__ void balance_region_pairs(const BalanceRegionDev& br, const DevModel& m, double* s_rec, const double* xs,
+                                                     int64_t traj_stride, int64_t count, int32_t T1, int32_t nx, int32_t na, int32_t lpe,
+                                                     const int32_t* state, int32_t round, double* out, int32_t add) {
+  const int tid = threadIdx.x, g = tid / lpe, j = tid % lpe;
+  const int64_t e = (int64_t)blockIdx.x * (64 / lpe) + g;
+  const CostPair pr = cost_pair_decode(e, count, T1, na, state, round);
+  const double* w = br.weight + pr.bt1 * br.np;
+  const double* geom = br.geom + pr.bt1 * br.np * 5;
+  const bool live = pr.live && rbd::weights_any(w, br.np);
+  if (live && j < m.nj) {
+    const double* x = xs + pr.traj * traj_stride + (int64_t)pr.t * nx;
+    double* r = s_rec + 7 * tid;
+    r[0] = rbd::momentum_body(m, j, x, x + m.nq, false, r + 1, r + 4, nullptr);
+  }
+  __syncthreads();
+  if (j != 0 || pr.skip) return;
+  double acc = MARGIN ? INFINITY : 0.0;
+  bool any = false;
+  if (live) {
+    double c[3], cd[3] = {0.0, 0.0, 0.0};
+    rbd::region_fold(s_rec + 7 * tid, m.nj, rbd::region_needs_rate(geom, w, br.np), c, cd);
+    for (int o = 0; o < br.np; ++o) {
+      const double wo = w[o];
+      if (wo == 0.0) continue;
+      const double d = rbd::region_distance(geom + 5 * o, c, cd);
+      if (MARGIN) acc = rbd::obstacle_min(acc, d);
+      else if (rbd::obstacle_active(d)) { acc += wo * d * d; any = true; }
+    }
+  }
+  cost_pair_store(out, e, MARGIN ? acc : 0.5 * acc, any, add);
+}
+__global__ __launch_bounds__(64) void balance_region_cost_kernel(BalanceRegionDev br, const DevModel* model, const double* xs, int64_t traj_stride,
+                                                                 int64_t count, int32_t T1, int32_t nx, int32_t na, int32_t lpe,
+                                                                 const int32_t* state, int32_t round, double* out, int32_t add) {
+  __shared__ double s_rec[64 * 7];
+  balance_region_pairs<false>(br, *model, s_rec, xs, traj_stride, count, T1, nx, na, lpe, state, round, out, add);
+}
+__global__ __launch_bounds__(64) void balance_region_margin_kernel(BalanceRegionDev br, const DevModel* model, const double* xs, int64_t count,
+                                                                   int32_t nx, int32_t lpe, double* out) {
+  __shared__ double s_rec[64 * 7];
+  balance_region_pairs<true>(br, *model, s_rec, xs, nx, count, 1, nx, 1, lpe, nullptr, 0, out, 0);
 }
 
 // The relative-frame terms (DDP_HIP_FLAG_RELATIVE_FRAME_COST, ddp_hip.h) of a list of states, added on top like the frame-velocity
@@ -1480,6 +1534,11 @@ static void launch_momentum_cost(ddp_hip_ctx* ctx, const double* xs, const doubl
   while (lpe < ctx->model_h.nj) lpe *= 2;
   launch_add_on(momentum_cost_kernel, momentum_cost_dev(ctx), lpe, ctx, xs, na, count, state, round, out, add, lpe);
 }
+static void launch_balance_region_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
+  int32_t lpe = 8;
+  while (lpe < ctx->model_h.nj) lpe *= 2;
+  launch_add_on(balance_region_cost_kernel, balance_region_dev(ctx), lpe, ctx, xs, na, count, state, round, out, add, lpe);
+}
 static void launch_relative_frame_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   launch_add_on(relative_frame_cost_kernel, relative_frame_dev(ctx), DDP_HIP_MAX_FRAME_PAIRS, ctx, xs, na, count, state, round, out, add);
 }
@@ -1499,8 +1558,8 @@ static void launch_self_collision_cost(ddp_hip_ctx* ctx, const double* xs, const
 }
 
 // The terms formed out of line, in the fixed order of their additions (after everything cost_kernel / the rollout kernels form
-// inline): CoM, frame velocities, momentum, relative frames, control-gravity, frame aiming, obstacles, self-collision.  launch_cost
-// and ddp_hip_forward both walk this table and nothing else
+// inline): CoM, frame velocities, momentum, balance regions, relative frames, control-gravity, frame aiming, obstacles,
+// self-collision.  launch_cost and ddp_hip_forward both walk this table and nothing else
 struct AddOnTerm {
   int term;
   AddOnLaunch launch;
@@ -1508,6 +1567,7 @@ struct AddOnTerm {
 static const AddOnTerm kAddOn[] = {{COST_COM, launch_com_cost},
                                    {COST_FRAME_VEL, launch_frame_vel_cost},
                                    {COST_MOMENTUM, launch_momentum_cost},
+                                   {COST_BALANCE_REGION, launch_balance_region_cost},
                                    {COST_RELATIVE_FRAME, launch_relative_frame_cost},
                                    {COST_CONTROL_GRAV, launch_control_grav_cost},
                                    {COST_FRAME_AIM, launch_frame_aim_cost},
@@ -1602,6 +1662,25 @@ extern "C" int ddp_hip_frame_aim_error(ddp_hip_ctx* ctx, int which, double* out)
                      which == 0 ? p.x_old : p.x_new, total, (int32_t)ctx->d.nx, ctx->fa_err_d);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, ctx->fa_err_d, sizeof(double) * (size_t)(total * fa.nf * 2), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_balance_region_margin(ddp_hip_ctx* ctx, int which, double* out) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_BALANCE_REGION_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (!out || (which != 0 && which != 1) || ctx->br_np == 0) return DDP_HIP_E_ARG;   // (no planes set: nothing to measure)
+  HIP_TRY(hipSetDevice(ctx->device));
+  const FwdParams p = make_params(ctx);
+  const BalanceRegionDev br = balance_region_dev(ctx, true);
+  const int64_t total = ctx->d.batch * (ctx->d.T + 1);
+  int32_t lpe = 8;
+  while (lpe < ctx->model_h.nj) lpe *= 2;
+  const int64_t per = 64 / lpe;
+  hipLaunchKernelGGL(balance_region_margin_kernel, dim3((unsigned)((total + per - 1) / per)), dim3(64), 0, ctx->stream, br, ctx->model_d,
+                     which == 0 ? p.x_old : p.x_new, total, (int32_t)ctx->d.nx, lpe, ctx->br_margin_d);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, ctx->br_margin_d, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return DDP_HIP_OK;
 }

@@ -296,6 +296,10 @@ struct ddp_hip_ctx {
   double fa_off[DDP_HIP_MAX_AIM_FRAMES][3] = {}, fa_axis[DDP_HIP_MAX_AIM_FRAMES][3] = {};
   double* fa_err_d = nullptr;                 // [batch][T+1][DDP_HIP_MAX_AIM_FRAMES][2] what ddp_hip_frame_aim_error hands back
 
+  // the balance-region planes (ddp_hip_balance_region_set_planes): a count alone, the planes themselves are per-instance data
+  int32_t br_np = 0;                          // plane slots set (0: none yet)
+  double* br_margin_d = nullptr;              // [batch][T+1] what ddp_hip_balance_region_margin hands back
+
   bool box_dirty = false;       // CTRL_LO / CTRL_HI were uploaded since lo <= hi was last checked (ctx.hip: box_check)
 
   bool async_mode = false;     // ddp_hip_set_async: entry points that hand nothing back to the host do not wait for the stream

@@ -13,6 +13,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include "balance_region_cost.h"
 #include "com_cost.h"
 #include "control_grav_cost.h"
 #include "frame_aim_cost.h"
@@ -387,8 +388,57 @@ __global__ __launch_bounds__(64) void lin_momentum_cost_kernel(LinParams p, Mome
   rbd::vel_add_wave(S, 1, s_w, s_wr, nv, tid, (int)blockDim.x, nv, n, gx, gxx);
 }
 
+// Balance-region cost (DDP_HIP_FLAG_BALANCE_REGION_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost
+// kernel on the same stream (the fixed order of additions: ..., frame velocities, momentum, balance regions).  The penalty is
+// one-sided, so most waves have nothing to add: a block whose weights are all 0 returns at once, before any LDS access or barrier,
+// and one whose live planes are all clear returns after the values, before any jacobian.  Lane j < nj walks its joint's path once
+// and leaves a_j, o_j, its path, m_j and m_j p_j in LDS -- and, where a live plane has tau != 0, its rate's twist, then its body's
+// twist and linear momentum (rbd::region_stage_wave: the CoM's stage lane, or the momentum's stage and prefix lanes with
+// ang = false).  Lane o < n_planes folds c (and cdot) over the records in ascending order and leaves w, w e, tau and whether plane
+// o is active.  Then lane j forms its column(s) of Jc (rbd::com_column_lane) and, where an active plane has tau != 0, of
+// dl/d(delta q) (rbd::mom_column_lane, ang = false); the wave stages z_o of the active planes (rbd::region_stage_z) and adds the
+// gradient rows and the entries (rbd::region_add_wave: planes ascending, entry (i, j) in (min, max) order, symmetric bit for bit).
+// A plane with tau = 0 touches no v row or column.  It reads p.x and touches nothing but lx / lxx.  No scratch, no atomics.
+// t = T: lfx / lfxx
+__global__ __launch_bounds__(64) void lin_balance_region_cost_kernel(LinParams p, BalanceRegionDev br) {
+  const int64_t bt1 = blockIdx.x;
+  const int n = (int)p.d.n, nv = (int)p.d.nv;
+  const int tid = threadIdx.x, np = br.np;
+  const double* w = br.weight + bt1 * np;
+  if (!rbd::weights_any(w, np)) return;
+  const double* geom = br.geom + bt1 * np * 5;
+  const DevModel& m = *p.model;
+  const LinCostBlock blk = lin_cost_block(p, bt1);
+  const double* q = blk.q;
+  __shared__ rbd::BalanceWaveLds S;
+  const bool rate = rbd::region_needs_rate(geom, w, np);
+  rbd::region_stage_wave(m, q, q + m.nq, tid, rate, S);
+  if (tid < np) {
+    const double wo = w[tid];
+    double we = 0.0;
+    int act = 0;
+    if (wo != 0.0) {
+      double c[3], cd[3] = {0.0, 0.0, 0.0};
+      rbd::region_point_lds(S, m.nj, rate, c, cd);
+      const double d = rbd::region_distance(geom + 5 * tid, c, cd);
+      if (rbd::obstacle_active(d)) { act = 1; we = wo * d; }
+    }
+    S.w[tid] = wo; S.we[tid] = we; S.tau[tid] = geom[5 * tid + 4]; S.act[tid] = act;
+  }
+  __syncthreads();
+  bool any = false, rate_q = false;
+  for (int o = 0; o < np; ++o)
+    if (S.act[o]) { any = true; rate_q |= S.tau[o] != 0.0; }
+  if (!any) return;
+  rbd::region_columns_wave(m, tid, rate_q, S);
+  rbd::region_stage_z(m, geom, np, tid, (int)blockDim.x, S);
+  __syncthreads();
+  double *gx = blk.gx, *gxx = blk.gxx;
+  rbd::region_add_wave(S, np, nv, tid, (int)blockDim.x, n, gx, gxx);
+}
+
 // Relative-frame cost (DDP_HIP_FLAG_RELATIVE_FRAME_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost
-// kernel on the same stream (the fixed order of additions: ..., frame velocities, momentum, relative frames).  A block whose
+// kernel on the same stream (the fixed order of additions: ..., momentum, balance regions, relative frames).  A block whose
 // weights are all 0 returns at once, before any LDS access or barrier.  Lanes j < nj stage world axis, world origin and path of
 // their joint in LDS (rbd::stage_joint_lane); lane 63 - i walks live pair i (rbd::relative_placement: two walks; the top lanes, so
 // that on a robot of fewer than 60 joints no lane does both) and leaves R_a^T, Jlog3(e) R_b^T, p_b, w and w o r.  After the barrier
@@ -1532,14 +1582,15 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
       hipLaunchKernelGGL(lin_track_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p);
     else hipLaunchKernelGGL(lin_cost_kernel, dim3((unsigned)BT), dim3(64), 0, ctx->stream, p);
     // the add-on terms, one kernel per live term, each adding onto what the ones before it left.  The fixed order of additions:
-    // cost, tracking, frame positions, frame orientations, limits, CoM, frame velocities, momentum, relative frames,
-    // control-gravity, frame aiming, obstacles, self-collision
+    // cost, tracking, frame positions, frame orientations, limits, CoM, frame velocities, momentum, balance regions, relative
+    // frames, control-gravity, frame aiming, obstacles, self-collision
     const dim3 blocks((unsigned)(BT + d.batch));
     const FrameCostDev fc = frame_cost_dev(ctx);
     const StateLimitsDev sl = state_limits_dev(ctx);
     const CoMCostDev cm = com_cost_dev(ctx);
     const FrameVelCostDev fv = frame_vel_cost_dev(ctx);
     const MomentumCostDev mo = momentum_cost_dev(ctx);
+    const BalanceRegionDev br = balance_region_dev(ctx);
     const RelativeFrameDev rf = relative_frame_dev(ctx);
     const ControlGravDev cg = control_grav_dev(ctx);
     const FrameAimDev fa = frame_aim_dev(ctx);
@@ -1552,6 +1603,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     add(cm.target, lin_com_cost_kernel, cm);
     add(fv.target, lin_frame_vel_cost_kernel, fv);
     add(mo.target, lin_momentum_cost_kernel, mo);
+    add(br.geom, lin_balance_region_cost_kernel, br);
     add(rf.weight, lin_relative_frame_cost_kernel, rf);
     if (cg.weight)   // (t < T alone; G in dynamic LDS, nv^2 doubles)
       hipLaunchKernelGGL(lin_control_grav_cost_kernel, dim3((unsigned)BT), dim3(64), sizeof(double) * (size_t)(d.nv * d.nv), ctx->stream, p, cg);

@@ -7,6 +7,7 @@
 
 #include <new>
 
+#include "balance_region_cost.h"
 #include "com_cost.h"
 #include "control_grav_cost.h"
 #include "frame_aim_cost.h"
@@ -204,6 +205,26 @@ __global__ __launch_bounds__(64) void model_frame_axis_kernel(const DevModel* m,
   }
 }
 
+// xi = c + tau cdot and its jacobians by one wave, with the traversal of lin_balance_region_cost_kernel (balance_region_cost.h):
+// in = q | v | tau, out = xi3 | Jq[3 nv] | Jv[3 nv] (column-major).  Jq = Jc + tau dcq and Jv = tau Jc entry by entry, dcq the
+// momentum's dl/dq entry divided by M (a free-flyer root's three linear columns: Jc alone).  tau = 0: the CoM's lanes alone, v is
+// not read, Jq is Jc and Jv is 0
+__global__ __launch_bounds__(64) void model_capture_point_kernel(const DevModel* m, const double* in, double* out) {
+  __shared__ rbd::BalanceWaveLds S;
+  const int tid = threadIdx.x, nv = m->nv;
+  const double tau = in[m->nq + nv];
+  const bool rate = tau != 0.0;
+  rbd::region_stage_wave(*m, in, in + m->nq, tid, rate, S);
+  rbd::region_columns_wave(*m, tid, rate, S);
+  const double M = rbd::region_total_mass(S, m->nj);
+  if (tid < 3) out[tid] = rate ? S.c[tid] + tau * (S.mo.h[tid] / M) : S.c[tid];
+  for (int i = tid; i < 3 * nv; i += blockDim.x) {
+    const double jc = S.J[i];
+    out[3 + i] = rate && rbd::region_rate_column(*m, i / 3) ? jc + tau * (S.mo.A[0][0][i / 3][i % 3] / M) : jc;
+    out[3 + 3 * nv + i] = rate ? tau * jc : 0.0;
+  }
+}
+
 #define MODEL_DISPATCH(nv, CALL)       \
   do {                                 \
     if ((nv) <= 6) { CALL(6); }        \
@@ -243,6 +264,8 @@ int run(ddp_hip_model_handle* h, const double* in, size_t n_in, double* out, siz
   } else if (what == 6) {
     hipLaunchKernelGGL(model_relative_frame_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac % DDP_MAXJ,
                        want_jac / DDP_MAXJ);   // (want_jac: the two joints)
+  } else if (what == 9) {
+    hipLaunchKernelGGL(model_capture_point_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o);
   } else if (what == 8) {
     hipLaunchKernelGGL(model_frame_axis_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac);   // (want_jac: the joint)
   } else {
@@ -428,5 +451,24 @@ extern "C" int ddp_hip_model_frame_axis(ddp_hip_model_handle* h, int32_t joint, 
   memcpy(p3, out, sizeof(double) * 3);
   memcpy(n3, out + 3, sizeof(double) * 3);
   if (J) memcpy(J, out + 6, sizeof(double) * 6 * nv);
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_model_capture_point(ddp_hip_model_handle* h, const double* q, const double* v, double tau, double* xi3, double* Jq, double* Jv) {
+  if (!h || !q || !v || !xi3 || h->model_h.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_ARG;
+  if (!isfinite(tau) || tau < 0.0) return DDP_HIP_E_ARG;
+  const int nv = h->model_h.nv, nq = h->model_h.nq;
+  double total = 0.0;
+  for (int i = 0; i < h->model_h.nj; ++i) total += h->model_h.I6[i][9];   // the body masses (ctx.hip: pack_body_inertia)
+  if (!(total > 0.0)) return DDP_HIP_E_ARG;
+  double in[2 * DDP_MAXJ + 2];
+  memcpy(in, q, sizeof(double) * nq); memcpy(in + nq, v, sizeof(double) * nv);
+  in[nq + nv] = tau;
+  double out[3 + 6 * DDP_MAXJ];
+  const int rc = run(h, in, (size_t)(nq + nv + 1), out, (size_t)(3 + ((Jq || Jv) ? 6 * nv : 0)), 9, 0);
+  if (rc != DDP_HIP_OK) return rc;
+  memcpy(xi3, out, sizeof(double) * 3);
+  if (Jq) memcpy(Jq, out + 3, sizeof(double) * 3 * nv);
+  if (Jv) memcpy(Jv, out + 3 + 3 * nv, sizeof(double) * 3 * nv);
   return DDP_HIP_OK;
 }

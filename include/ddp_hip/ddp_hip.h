@@ -458,6 +458,41 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * control-gravity terms', before the obstacles'). */
 #define DDP_HIP_FLAG_FRAME_AIM_COST 16384u
 #define DDP_HIP_MAX_AIM_FRAMES 4
+/* Say "stay balanced": "the centre of mass stays over the support polygon while the arms work", "the capture point stays over the
+ * feet during the step".  A balance task is an inequality: DDP_HIP_FLAG_COM_COST pulls the CoM towards a point and fights every
+ * reach, DDP_HIP_FLAG_MOMENTUM_COST regulates cdot; neither leaves the robot free inside a region.  The batch shares a plane count
+ * (ddp_hip_balance_region_set_planes, up to DDP_HIP_MAX_REGION_PLANES); per instance b, t = 0 .. T and plane slot o five doubles
+ * geom = (n, h, tau) -- a unit normal n in world axes, an offset h, a time constant tau >= 0 -- and a weight w >= 0.  With
+ *   c(q)       the centre of mass of DDP_HIP_FLAG_COM_COST
+ *   cdot(q, v) = Jc(q) v = l / M      (l the linear momentum of DDP_HIP_FLAG_MOMENTUM_COST, M the total mass)
+ *   xi_o = c + tau_o cdot             (tau = 0: the CoM itself, no velocity quantity is read;  tau = 1 / omega_0 = sqrt(z_c / g):
+ *                                      the capture point, where the robot must step to come to rest)
+ *   d_o  = n_o . xi_o - h_o           (formed as (n_0 xi_0 + n_1 xi_1 + n_2 xi_2) - h; the free side is d >= 0, a safety margin
+ *                                      goes into h)
+ *   e_o  = !(d_o >= 0) ? d_o : 0      (a NaN d is active and its term NaN, the self-collision rule)
+ *   l(t, x, u) += 1/2 sum_o w e_o^2      t < T
+ *   lf(x_T)    += the same with row T
+ * to whatever the context optimises otherwise.  tau lives per plane: each plane tests its own point, so one context holds "CoM
+ * inside the polygon" (tau = 0) on some slots and "capture point inside the polygon" on others, and per-instance, per-t geometry
+ * gives support polygons that change with the gait phase.  Derivatives in the tangent at x, over the planes with w != 0 and
+ * e != 0 only, with dcq = d cdot / d(delta q) the linear rows of the momentum flag's dh/dq, each entry divided by M:
+ *   z_o = [ (Jc + tau_o dcq)^T n_o  |  tau_o Jc^T n_o ]      (2 nv)
+ *   lx += sum_o w e_o z_o,   lxx += sum_o w z_o z_o^T,   lfx / lfxx alike at T;   lu, luu, lux untouched.
+ * Column i of z's q part is associated as (Jc[:, i] . n) + tau (dcq[:, i] . n) -- Jc . n first, then the product tau (dcq . n)
+ * added -- and of its v part as tau (Jc[:, i] . n); the gradient entry is (w e) z[i] and the second-order entry
+ * (z[min] w) z[max].  ddp_hip_model_capture_point forms the matrices entry by entry, Jc + tau dcq and tau Jc, with the same Jc and
+ * dcq.  A free-flyer root's three linear columns of dcq are identically zero and are left out.  A plane with tau = 0 forms no
+ * velocity quantity and touches neither the v rows nor the v columns; if no live plane (w != 0) of an (instance, t) has
+ * tau != 0, cdot is not formed at all, and if no active one has, dcq is not.  lxx is Gauss-Newton (w e d^2 d is dropped:
+ * positive semidefinite); planes ascending, entry (i, j) formed in (min, max) order: symmetric bit for bit, no atomics.  A plane
+ * with w == 0 or e == 0 is left out (not multiplied by 0, not added as +0): with nothing uploaded, with every weight 0, and
+ * with non-zero weights on planes that neither the trajectory nor any line-search candidate violates, a context computes bit for
+ * bit what it computes without the flag.  The data travels through ddp_hip_balance_region_* below; at create no planes are set.
+ * Tree models only (the pendulum: DDP_HIP_E_UNSUPPORTED); a total mass M <= 0 is DDP_HIP_E_ARG.  The flag stands alone and
+ * combines with every other flag: the terms are formed by kernels of their own, which add onto what the other terms' kernels
+ * leave (after the momentum's, before the relative frames'). */
+#define DDP_HIP_FLAG_BALANCE_REGION_COST 32768u
+#define DDP_HIP_MAX_REGION_PLANES 8
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -602,6 +637,20 @@ int ddp_hip_frame_aim_download(ddp_hip_ctx* ctx, double* target, double* weight,
  * atan2(|n x dh|, n . dh), and l the distance from the eye to the target (theta = 0 where l <= 1e-12).  From the first
  * ddp_hip_frame_aim_set_frames with a frame on (before: DDP_HIP_E_ARG), live weights or not. */
 int ddp_hip_frame_aim_error(ddp_hip_ctx* ctx, int which, double* out);
+/* The plane count of a context created with DDP_HIP_FLAG_BALANCE_REGION_COST (else DDP_HIP_E_UNSUPPORTED), shared by the batch:
+ * n_planes in 0 .. DDP_HIP_MAX_REGION_PLANES (else DDP_HIP_E_ARG).  It may be called again: with the same count the per-instance
+ * data stays, another count resets geometry and weights to 0.  n_planes = 0 takes the planes away. */
+int ddp_hip_balance_region_set_planes(ddp_hip_ctx* ctx, int32_t n_planes);
+/* The planes' geometry and weights, stream-ordered like ddp_hip_obstacle_upload.  Host arrays [n_instances][T+1][n_planes][5] =
+ * (n, h, tau) and [n_instances][T+1][n_planes]; a NULL pointer leaves that side as it is.  An upload is refused as a whole
+ * (DDP_HIP_E_ARG, nothing written) before ddp_hip_balance_region_set_planes with a count >= 1, for a bad instance range, a
+ * non-finite value, a normal n with | |n| - 1 | > 1e-10 (the obstacle half-spaces' rule), tau < 0 and a negative weight. */
+int ddp_hip_balance_region_upload(ddp_hip_ctx* ctx, const double* geom, const double* weight, int64_t first_instance, int64_t n_instances);
+int ddp_hip_balance_region_download(ddp_hip_ctx* ctx, double* geom, double* weight, int64_t first_instance, int64_t n_instances);
+/* "Did it stay balanced, by how much": out[batch][T+1] (host) = min over the planes with w != 0 of d_o along X (which = 0) or
+ * X_NEW (which = 1), +inf where no plane is live, NaN where a d is.  From the first ddp_hip_balance_region_set_planes with a
+ * plane on (before: DDP_HIP_E_ARG), live weights or not. */
+int ddp_hip_balance_region_margin(ddp_hip_ctx* ctx, int which, double* out);
 
 /* make_trajectory (ddp.hpp:392-415): X[0] and U given -> X[1..T] */
 int ddp_hip_rollout(ddp_hip_ctx* ctx);
@@ -780,6 +829,12 @@ int ddp_hip_model_gravity_torque(ddp_hip_model_handle* h, const double* q, doubl
  * targets such as "what it looks at now, one metre ahead: g = p + n" */
 int ddp_hip_model_frame_axis(ddp_hip_model_handle* h, int32_t joint, const double off[3], const double axis[3], const double* q, double* p3,
                              double* n3, double* J);
+/* The test point xi = c + tau cdot of DDP_HIP_FLAG_BALANCE_REGION_COST of a tree model at the state (q, v) (tau = 0: the CoM;
+ * tau = sqrt(z_c / g): the capture point): xi3 and, where not NULL, Jq = Jc + tau d cdot / d(delta q) and Jv = tau Jc, each
+ * 3 x nv column-major, formed entry by entry by the traversal the cost kernels use (a free-flyer root's three linear columns of
+ * Jq are Jc's alone).  tau < 0 or non-finite, or a total mass <= 0: DDP_HIP_E_ARG.  For targets such as "the plane 4 cm behind
+ * where the capture point is now" */
+int ddp_hip_model_capture_point(ddp_hip_model_handle* h, const double* q, const double* v, double tau, double* xi3, double* Jq, double* Jv);
 
 /* ---- built-in seeded model tables (no URDF exists offline: SURVEY.md D4, 8d) -------------- */
 /* ..._FF: the same robots on a free-flyer root instead of a fixed base / 3 prismatic + 3 revolute base joints */
