@@ -36,6 +36,7 @@ FLAG_RELATIVE_FRAME_COST = 4096
 FLAG_CONTROL_GRAV_COST = 8192
 FLAG_FRAME_AIM_COST = 16384
 FLAG_BALANCE_REGION_COST = 32768
+FLAG_JOINT_ACCEL_COST = 65536
 MAX_COST_FRAMES = 4
 MAX_COLLISION_POINTS, MAX_OBSTACLES = 16, 8
 MAX_COLLISION_PAIRS = 32
@@ -86,6 +87,7 @@ EXPORTS = [
     "ddp_hip_model_frame_axis",
     "ddp_hip_balance_region_set_planes", "ddp_hip_balance_region_upload", "ddp_hip_balance_region_download",
     "ddp_hip_balance_region_margin", "ddp_hip_model_capture_point",
+    "ddp_hip_joint_accel_cost_upload", "ddp_hip_joint_accel_cost_download", "ddp_hip_joint_accel",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -213,6 +215,10 @@ def lib():
         L.ddp_hip_frame_aim_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_frame_aim_error.argtypes = [C.c_void_p, C.c_int, _dp]
         L.ddp_hip_model_frame_axis.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]
+    if hasattr(L, "ddp_hip_joint_accel_cost_upload"):  # (likewise: set_joint_accel_cost, joint_accel_cost, joint_accel)
+        L.ddp_hip_joint_accel_cost_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_joint_accel_cost_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_joint_accel.argtypes = [C.c_void_p, C.c_int, _dp]
     if hasattr(L, "ddp_hip_balance_region_upload"):  # (likewise: set_balance_region_planes, set_balance_region_cost, balance_region_margin, ModelHandle.capture_point)
         L.ddp_hip_balance_region_set_planes.argtypes = [C.c_void_p, C.c_int32]
         L.ddp_hip_balance_region_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
@@ -778,6 +784,30 @@ class Context:
         (which = 1); +inf where no plane is live, negative where the tested point has left the region"""
         out = np.zeros((self.batch, self.spec.T + 1))
         _check(lib().ddp_hip_balance_region_margin(self._h, int(which), _ptr(out)), "balance_region_margin")
+        return out
+
+    def set_joint_accel_cost(self, target=None, weight=None, first=0, count=None):
+        """The joint-acceleration terms of instances first .. first + count - 1 (a context created with FLAG_JOINT_ACCEL_COST;
+        ddp_hip.h): 1/2 sum_i w_i (a_i - target_i)^2 at t < T with a = aba(q_t, v_t, u_t), a free-flyer root's six rows included.
+        target, weight: (T, nv) for every instance of the range or (count, T, nv) with one per instance; both also take (nv,)
+        and scalars by broadcast.  weight >= 0.  None leaves that side as it is.  (The library's record has a row T that belongs
+        to no term: the zero row is appended here, a (T+1, nv) array is refused.)"""
+        per, extra = (self.spec.T, self.spec.nv), ((self.spec.nv,), ())
+        count, arrs = self._cost_sides("set_joint_accel_cost", (("target", target, per, extra), ("weight", weight, per, extra)), first, count)
+        arrs = [None if a is None else np.ascontiguousarray(np.concatenate([a, np.zeros((count, 1, self.spec.nv))], axis=1)) for a in arrs]
+        self._cost_upload(lib().ddp_hip_joint_accel_cost_upload, "joint_accel_cost_upload", arrs, first, count)
+
+    def joint_accel_cost(self, first=0, count=None):
+        """(target, weight) of instances first .. first + count - 1, each (count, T, nv)"""
+        per = (self.spec.T + 1, self.spec.nv)
+        target, weight = self._cost_download(lib().ddp_hip_joint_accel_cost_download, "joint_accel_cost_download", (per, per), first, count)
+        return np.ascontiguousarray(target[:, :-1]), np.ascontiguousarray(weight[:, :-1])
+
+    def joint_accel(self, which=0):
+        """(batch, T, nv): the accelerations a_t = aba(x_t, u_t) along X / U (which = 0) or X_NEW / U_NEW (which = 1) of a
+        context created with FLAG_JOINT_ACCEL_COST, live weights or not ("how hard did it accelerate")"""
+        out = np.zeros((self.batch, self.spec.T, self.spec.nv))
+        _check(lib().ddp_hip_joint_accel(self._h, int(which), _ptr(out)), "joint_accel")
         return out
 
     def set_relative_frame_pairs(self, pairs):

@@ -11,16 +11,18 @@
 // The terms.  The order in which the kernels add them (after the stage cost and the tracking cost) is stated where they are launched:
 // lin.hip launches one kernel per live term, fwd.hip forms the first three inline and walks kAddOn for the others, both in the order
 // frame positions, frame orientations, limits, CoM, frame velocities, momentum, balance regions, relative frames, control-gravity,
-// frame aiming, obstacles, self-collision.  The enumerators are indices of ctx->cost[] and kCostDesc[] and follow that order but for
-// COST_CONTROL_GRAV, COST_FRAME_AIM and COST_BALANCE_REGION: the host programs hold momentum, relative frames, obstacles and self-collision as neighbours
+// frame aiming, joint accelerations, obstacles, self-collision.  The enumerators are indices of ctx->cost[] and kCostDesc[] and follow that order but for
+// COST_CONTROL_GRAV, COST_FRAME_AIM, COST_BALANCE_REGION and COST_JOINT_ACCEL: the host programs hold momentum, relative frames, obstacles and self-collision as neighbours
 // and self-collision as the last (host/test_relative_frame_block.cpp, host/test_self_collision_block.cpp), so the term whose
 // additions come between the relative frames' and the obstacles' has its index in front of that run; they hold frame velocities and
 // control-gravity as neighbours too (host/test_control_grav_block.cpp), so the term whose additions come after control-gravity's
 // has its index in front of the frame velocities'; and they hold the CoM, frame aiming and the frame velocities as neighbours
 // (host/test_frame_aim_block.cpp), and momentum and the relative frames, so the term whose additions come between the momentum's and
-// the relative frames' has its index in front of the CoM's.  No order is read off the enumerators: the kernels' order is the
+// the relative frames' has its index in front of the CoM's.  With that every adjacency from the limits to self-collision is held by
+// some host program (host/test_balance_region_block.cpp holds the limits and the balance regions), so the term whose additions come
+// between frame aiming's and the obstacles', the joint accelerations, has its index in front of the limits'.  No order is read off the enumerators: the kernels' order is the
 // order of the launches in lin.hip and of kAddOn in fwd.hip, nothing else
-enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_LIMITS, COST_BALANCE_REGION, COST_COM, COST_FRAME_AIM, COST_FRAME_VEL, COST_CONTROL_GRAV, COST_MOMENTUM,
+enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_JOINT_ACCEL, COST_LIMITS, COST_BALANCE_REGION, COST_COM, COST_FRAME_AIM, COST_FRAME_VEL, COST_CONTROL_GRAV, COST_MOMENTUM,
                           COST_RELATIVE_FRAME, COST_OBSTACLE, COST_SELF_COLLISION, COST_COUNT };
 
 enum CostFill : int32_t { FILL_ZERO, FILL_NEG_INF, FILL_POS_INF, FILL_QUAT };   // FILL_QUAT: identity quaternions (0, 0, 0, 1)
@@ -28,6 +30,7 @@ enum CostFill : int32_t { FILL_ZERO, FILL_NEG_INF, FILL_POS_INF, FILL_QUAT };   
 #define COST_MAX_SIDES 3
 #define COST_ITEMS_STATE 0          // CostDesc::max_items: one item per tangent row of the state, n
 #define COST_ITEMS_CONTROL (-1)     // ... one item per control row, m
+#define COST_ITEMS_VELOCITY (-2)    // ... one item per tangent row of v, nv
 
 // What a term is made of.  A side is one array [batch][rows][items][unit], rows = T+1 (t = 0 .. T), or T for a term of the
 // stages alone (stage_only: t = 0 .. T-1, no terminal row); the last side is the weights
@@ -36,7 +39,7 @@ struct CostDesc {
   int32_t nside;
   int32_t unit[COST_MAX_SIDES];     // doubles per item
   int32_t fill[COST_MAX_SIDES];     // CostFill: what a side holds at create and after a change of layout
-  int32_t max_items;                // items the arrays have room for; COST_ITEMS_STATE / COST_ITEMS_CONTROL: n / m (CostBlock::max_items, set at create)
+  int32_t max_items;                // items the arrays have room for; COST_ITEMS_STATE / _CONTROL / _VELOCITY: n / m / nv (CostBlock::max_items, set at create)
   bool fixed;                       // laid out at create for max_items; else by the frames / slots set, up to max_items
   bool cand;                        // the term has a candidates' array for the line search
   bool stage_only;                  // a term of l(t, x, u), t < T, alone: T rows per instance, not T+1 (a term that reads u has no row at T)
@@ -46,6 +49,7 @@ static const CostDesc kCostDesc[COST_COUNT] = {
     // flag, sides, doubles per item, fill, room, fixed, cand, stage_only
     {DDP_HIP_FLAG_FRAME_COST, 2, {3, 3, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, false, false},          // target | weight, per frame
     {DDP_HIP_FLAG_FRAME_ORIENT_COST, 2, {4, 3, 0}, {FILL_QUAT, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, false, false},   // quat | weight, per frame
+    {DDP_HIP_FLAG_JOINT_ACCEL_COST, 2, {1, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, COST_ITEMS_VELOCITY, true, true, false},           // target | weight, per tangent row of v; row T carries no term
     {DDP_HIP_FLAG_STATE_LIMITS, 3, {1, 1, 1}, {FILL_NEG_INF, FILL_POS_INF, FILL_ZERO}, 0, true, false, false},                 // lo | hi | weight, per tangent row
     {DDP_HIP_FLAG_BALANCE_REGION_COST, 2, {5, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_REGION_PLANES, false, true, false},   // (n, h, tau) | weight, per plane slot
     {DDP_HIP_FLAG_COM_COST, 2, {3, 3, 0}, {FILL_ZERO, FILL_ZERO, 0}, 1, true, true, false},                                    // target | weight
@@ -77,6 +81,7 @@ struct CostCheck {
   int64_t items = 0;                // per (instance, t)
   bool ff = false;                  // free-flyer root: the first six tangent rows carry no limit
   const int32_t* kind = nullptr;    // [items] obstacle slot kinds
+  int64_t rows = 0;                 // rows of a side per instance (cost_rows): the joint accelerations' weights find row T by it
 };
 typedef bool (*CostSideOk)(const CostCheck& c, const double* v, int64_t words);
 
@@ -147,6 +152,14 @@ static inline bool cost_limit_weight_side(const CostCheck& c, const double* v, i
   for (int64_t i = 0; i < words; ++i) {
     if (!cost_weight_ok(v[i])) return false;
     if (c.ff && i % c.items < 6 && v[i] != 0.0) return false;
+  }
+  return true;
+}
+// the joint accelerations' weights: the record has T+1 rows (c.rows) but the term is of t < T alone, so row T carries no weight
+static inline bool cost_stage_weight_side(const CostCheck& c, const double* v, int64_t words) {
+  for (int64_t i = 0; i < words; ++i) {
+    if (!cost_weight_ok(v[i])) return false;
+    if (i / c.items % c.rows == c.rows - 1 && v[i] != 0.0) return false;
   }
   return true;
 }

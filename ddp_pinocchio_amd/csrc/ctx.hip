@@ -253,6 +253,10 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   if ((flags & DDP_HIP_FLAG_RELATIVE_FRAME_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the frame pairs alike
   if ((flags & DDP_HIP_FLAG_CONTROL_GRAV_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // g(q) is of a tree's bodies
   if ((flags & DDP_HIP_FLAG_FRAME_AIM_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // aim frames are frames of a tree's joints
+  if (flags & DDP_HIP_FLAG_JOINT_ACCEL_COST) {
+    if (mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // a = aba(q, v, u) of a tree
+    if (mo.nv > DDP_HIP_MAX_JOINT_ACCEL_NV) return DDP_HIP_E_UNSUPPORTED;   // the recursion's LDS record beside the jacobian: the 38 instantiation alone
+  }
   if (flags & (DDP_HIP_FLAG_COM_COST | DDP_HIP_FLAG_MOMENTUM_COST | DDP_HIP_FLAG_BALANCE_REGION_COST)) {
     if (mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the CoM, the momentum about it and the capture point are of a tree's bodies
     if (!mo.mass_j || !mo.jtype) return DDP_HIP_E_ARG;
@@ -365,7 +369,8 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     // and control-gravity (one item per control row, T rows): fixed
     CostBlock& k = ctx->cost[term];
     k.desc = &kCostDesc[term];
-    k.max_items = k.desc->max_items == COST_ITEMS_STATE ? (int32_t)d.n : k.desc->max_items == COST_ITEMS_CONTROL ? (int32_t)d.m : k.desc->max_items;
+    k.max_items = k.desc->max_items == COST_ITEMS_STATE ? (int32_t)d.n : k.desc->max_items == COST_ITEMS_CONTROL ? (int32_t)d.m :
+                  k.desc->max_items == COST_ITEMS_VELOCITY ? (int32_t)d.nv : k.desc->max_items;
     if (!(flags & k.desc->flag)) continue;
     const int rc_ = cost_block_setup(ctx, term, k.desc->fixed ? k.max_items : 0);
     if (rc_ != DDP_HIP_OK) { ddp_hip_destroy(ctx); return rc_; }
@@ -376,6 +381,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipMalloc(&ctx->rf_err_d, sizeof(double) * (size_t)(d.batch * (d.T + 1) * DDP_HIP_MAX_FRAME_PAIRS * 6)));
   if (flags & DDP_HIP_FLAG_FRAME_AIM_COST)
     CTX_TRY(hipMalloc(&ctx->fa_err_d, sizeof(double) * (size_t)(d.batch * (d.T + 1) * DDP_HIP_MAX_AIM_FRAMES * 2)));
+  if (flags & DDP_HIP_FLAG_JOINT_ACCEL_COST) CTX_TRY(hipMalloc(&ctx->ja_acc_d, sizeof(double) * (size_t)(d.batch * d.T * d.nv)));
   if (flags & DDP_HIP_FLAG_BALANCE_REGION_COST) CTX_TRY(hipMalloc(&ctx->br_margin_d, sizeof(double) * (size_t)(d.batch * (d.T + 1))));
   int rc = bwd_setup(ctx);
   if (rc == DDP_HIP_OK) rc = fwd_setup(ctx);
@@ -405,6 +411,7 @@ extern "C" int ddp_hip_destroy(ddp_hip_ctx* ctx) {
   if (ctx->sc_clear_d) (void)hipFree(ctx->sc_clear_d);
   if (ctx->rf_err_d) (void)hipFree(ctx->rf_err_d);
   if (ctx->fa_err_d) (void)hipFree(ctx->fa_err_d);
+  if (ctx->ja_acc_d) (void)hipFree(ctx->ja_acc_d);
   if (ctx->br_margin_d) (void)hipFree(ctx->br_margin_d);
   if (ctx->ne_d) (void)hipFree(ctx->ne_d);
   if (ctx->Epre_d) (void)hipFree(ctx->Epre_d);
@@ -538,7 +545,7 @@ static int cost_block_upload(ddp_hip_ctx* ctx, int term, const double* const* ho
   CostBlock& k = ctx->cost[term];
   const Dims& d = ctx->d;
   CostCheck c;
-  c.items = k.items; c.ff = ctx->model_h.ff != 0; c.kind = ctx->ob_kind;
+  c.items = k.items; c.ff = ctx->model_h.ff != 0; c.kind = ctx->ob_kind; c.rows = cost_rows(k, d.T);
   bool copy, nonzero;
   const int rc = cost_upload_check(ctx->flags, k, c, d.batch, d.T, host, ok, first, count, &copy, &nonzero);
   if (rc != DDP_HIP_OK || !copy) return rc;
@@ -814,6 +821,17 @@ extern "C" int ddp_hip_balance_region_upload(ddp_hip_ctx* ctx, const double* geo
 extern "C" int ddp_hip_balance_region_download(ddp_hip_ctx* ctx, double* geom, double* weight, int64_t first, int64_t count) {
   double* host[] = {geom, weight};
   return cost_block_download(ctx, COST_BALANCE_REGION, host, first, count);
+}
+
+// a target and a weight per (instance, t, tangent row of v): T+1 rows like the other records, row T without a term (a weight there: E_ARG)
+extern "C" int ddp_hip_joint_accel_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first, int64_t count) {
+  const double* host[] = {target, weight};
+  const CostSideOk ok[] = {cost_finite_side, cost_stage_weight_side};
+  return cost_block_upload(ctx, COST_JOINT_ACCEL, host, ok, first, count);
+}
+extern "C" int ddp_hip_joint_accel_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first, int64_t count) {
+  double* host[] = {target, weight};
+  return cost_block_download(ctx, COST_JOINT_ACCEL, host, first, count);
 }
 
 extern "C" int ddp_hip_com_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first, int64_t count) {

@@ -18,6 +18,7 @@
 #include "frame_cost.h"
 #include "frame_vel_cost.h"
 #include "internal.h"
+#include "joint_accel_cost.h"
 #include "momentum_cost.h"
 #include "obstacle_cost.h"
 #include "rbd.h"
@@ -837,7 +838,7 @@ __global__ void cand_sum_kernel(FwdParams p) {
   p.fw_dcost[(int64_t)b * na + a] = dsum;
 }
 
-// The add-on cost kernels below (CoM, frame velocities, momentum, balance regions, relative frames, control-gravity, frame aiming, obstacles) run over a list of `count` (trajectory, t) pairs, t = 0 .. T,
+// The add-on cost kernels below (CoM, frame velocities, momentum, balance regions, relative frames, control-gravity, frame aiming, joint accelerations, obstacles) run over a list of `count` (trajectory, t) pairs, t = 0 .. T,
 // `na` trajectories per instance.  Pair e: which trajectory, which t, whose instance, which block bt1 = b (T+1) + t of the term's
 // data.  skip: nothing is written for this pair (past the list, or a candidate the rollout kernels skip: state != 0, beyond
 // 2^-33; state == nullptr: a resident trajectory, none is skipped).  live: the pair is evaluated (the kernels narrow it further)
@@ -1183,6 +1184,52 @@ __global__ __launch_bounds__(64) void frame_aim_error_kernel(FrameAimDev fa, con
   }
   out[e * 2] = theta;
   out[e * 2 + 1] = l;
+}
+
+// The joint-acceleration terms (DDP_HIP_FLAG_JOINT_ACCEL_COST, ddp_hip.h) of a list of states and their controls, added on top like
+// the control-gravity terms above: the same list, the same two uses, us and u_stride as there (the controls the rollout applied,
+// clamped where there are bounds: the kernel knows no bounds).  `lpe` lanes cooperate on one evaluation, 64 / lpe per wave:
+// a = aba(x_t, u_t) by rbd::accel_group (forward dynamics alone, no jacobian; never (v_{t+1} - v_t) / dt: the list need not be a
+// rollout of its controls) with the joints' records and a in dynamic LDS (rbd::accel_group_words doubles per evaluation); the
+// group's first lane adds w_i (a_i - a_ref_i)^2 over the rows of weight != 0 in ascending order.  A pair whose nv weights are
+// all 0 does no arithmetic; t = T has no control and no term: such a pair adds nothing (add != 0) or stores +0 (add == 0).  A
+// non-finite state gives a NaN term.  ja.report != nullptr (ddp_hip_joint_accel): the weights are ignored, a goes to
+// report[trajectory][T][nv] and nothing to out.  No scratch
+__global__ __launch_bounds__(64) void joint_accel_cost_kernel(JointAccelDev ja, const DevModel* model, const double* xs, int64_t traj_stride,
+                                                              int64_t count, int32_t T1, int32_t nx, int32_t na, int32_t lpe, const double* us,
+                                                              int64_t u_stride, const int32_t* state, int32_t round, double* out, int32_t add) {
+  extern __shared__ double s_ja[];
+  const DevModel& m = *model;
+  const int tid = threadIdx.x, g = tid / lpe, h = tid % lpe, N = m.nv;
+  const int64_t e = (int64_t)blockIdx.x * (64 / lpe) + g;
+  const CostPair pr = cost_pair_decode(e, count, T1, na, state, round);
+  const int t = pr.t, T = T1 - 1;
+  const double* w = ja.weight + pr.bt1 * N;
+  bool live = pr.live && t < T;
+  if (live && !ja.report && !rbd::weights_any(w, N)) live = false;
+  double* st = s_ja + g * rbd::accel_group_words(m.nj, N);
+  double* s_a = st + rbd::ABA_LDS_SLOTS * m.nj;
+  const double* x = xs + pr.traj * traj_stride + (int64_t)t * nx;
+  const double* u = us + pr.traj * u_stride + (int64_t)t * N;
+  if (m.ff) rbd::accel_group<true>(m, x, x + m.nq, u, s_a, st, h, lpe, live);
+  else rbd::accel_group<false>(m, x, x + m.nq, u, s_a, st, h, lpe, live);
+  if (ja.report) {
+    if (live)
+      for (int i = h; i < N; i += lpe) ja.report[(pr.traj * T + t) * N + i] = s_a[i];
+    return;
+  }
+  if (h != 0 || pr.skip) return;
+  double acc = 0.0;
+  if (live) {
+    const double* ref = ja.target + pr.bt1 * N;
+    for (int i = 0; i < N; ++i) {
+      const double wi = w[i];
+      if (wi == 0.0) continue;
+      const double r = s_a[i] - ref[i];
+      acc += wi * r * r;
+    }
+  }
+  cost_pair_store(out, e, 0.5 * acc, live, add);
 }
 
 // The obstacle terms (DDP_HIP_FLAG_OBSTACLE_COST, ddp_hip.h) of a list of states, added on top like the frame-velocity terms above:
@@ -1550,6 +1597,22 @@ static void launch_control_grav_cost(ddp_hip_ctx* ctx, const double* xs, const d
 static void launch_frame_aim_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   launch_add_on(frame_aim_cost_kernel, frame_aim_dev(ctx), DDP_HIP_MAX_AIM_FRAMES, ctx, xs, na, count, state, round, out, add);
 }
+// (one wave per two evaluations: a level of a tree is seldom wider than 32 joints; the records in dynamic LDS, < 64 KB at nv <= 38)
+static constexpr int32_t kJointAccelLanes = 32;
+static size_t joint_accel_lds(const ddp_hip_ctx* ctx) {
+  return sizeof(double) * (size_t)((64 / kJointAccelLanes) * rbd::accel_group_words(ctx->model_h.nj, (int)ctx->d.nv));
+}
+static void launch_joint_accel(const JointAccelDev& ja, ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state,
+                               int round, double* out, int add) {
+  const Dims& d = ctx->d;
+  const int64_t per = 64 / kJointAccelLanes;
+  hipLaunchKernelGGL(joint_accel_cost_kernel, dim3((unsigned)((count + per - 1) / per)), dim3(64), joint_accel_lds(ctx), ctx->stream, ja, ctx->model_d, xs,
+                     (d.T + 1) * d.nx, count, (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, kJointAccelLanes, us, d.T * d.m, state, (int32_t)round, out,
+                     (int32_t)add);
+}
+static void launch_joint_accel_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
+  launch_joint_accel(joint_accel_dev(ctx), ctx, xs, us, na, count, state, round, out, add);
+}
 static void launch_obstacle_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   launch_add_on(obstacle_cost_kernel, obstacle_cost_dev(ctx), DDP_HIP_MAX_COLLISION_POINTS, ctx, xs, na, count, state, round, out, add);
 }
@@ -1558,8 +1621,8 @@ static void launch_self_collision_cost(ddp_hip_ctx* ctx, const double* xs, const
 }
 
 // The terms formed out of line, in the fixed order of their additions (after everything cost_kernel / the rollout kernels form
-// inline): CoM, frame velocities, momentum, balance regions, relative frames, control-gravity, frame aiming, obstacles,
-// self-collision.  launch_cost and ddp_hip_forward both walk this table and nothing else
+// inline): CoM, frame velocities, momentum, balance regions, relative frames, control-gravity, frame aiming, joint
+// accelerations, obstacles, self-collision.  launch_cost and ddp_hip_forward both walk this table and nothing else
 struct AddOnTerm {
   int term;
   AddOnLaunch launch;
@@ -1571,6 +1634,7 @@ static const AddOnTerm kAddOn[] = {{COST_COM, launch_com_cost},
                                    {COST_RELATIVE_FRAME, launch_relative_frame_cost},
                                    {COST_CONTROL_GRAV, launch_control_grav_cost},
                                    {COST_FRAME_AIM, launch_frame_aim_cost},
+                                   {COST_JOINT_ACCEL, launch_joint_accel_cost},
                                    {COST_OBSTACLE, launch_obstacle_cost},
                                    {COST_SELF_COLLISION, launch_self_collision_cost}};
 
@@ -1681,6 +1745,22 @@ extern "C" int ddp_hip_balance_region_margin(ddp_hip_ctx* ctx, int which, double
                      which == 0 ? p.x_old : p.x_new, total, (int32_t)ctx->d.nx, lpe, ctx->br_margin_d);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, ctx->br_margin_d, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_joint_accel(ddp_hip_ctx* ctx, int which, double* out) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_JOINT_ACCEL_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (!out || (which != 0 && which != 1)) return DDP_HIP_E_ARG;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const FwdParams p = make_params(ctx);
+  JointAccelDev ja = joint_accel_dev(ctx, true);
+  ja.report = ctx->ja_acc_d;
+  const Dims& d = ctx->d;
+  launch_joint_accel(ja, ctx, which == 0 ? p.x_old : p.x_new, which == 0 ? p.u_old : p.u_new, 1, d.batch * (d.T + 1), nullptr, 0, nullptr, 0);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, ctx->ja_acc_d, sizeof(double) * (size_t)(d.batch * d.T * d.nv), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return DDP_HIP_OK;
 }

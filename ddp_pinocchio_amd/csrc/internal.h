@@ -298,6 +298,7 @@ struct ddp_hip_ctx {
 
   // the balance-region planes (ddp_hip_balance_region_set_planes): a count alone, the planes themselves are per-instance data
   int32_t br_np = 0;                          // plane slots set (0: none yet)
+  double* ja_acc_d = nullptr;                 // [batch][T][nv] what ddp_hip_joint_accel hands back
   double* br_margin_d = nullptr;              // [batch][T+1] what ddp_hip_balance_region_margin hands back
 
   bool box_dirty = false;       // CTRL_LO / CTRL_HI were uploaded since lo <= hi was last checked (ctx.hip: box_check)

@@ -20,6 +20,7 @@
 #include "frame_cost.h"
 #include "frame_vel_cost.h"
 #include "internal.h"
+#include "joint_accel_cost.h"
 #include "lin_common.h"
 #include "momentum_cost.h"
 #include "obstacle_cost.h"
@@ -632,8 +633,99 @@ __global__ __launch_bounds__(64) void lin_frame_aim_cost_kernel(LinParams p, Fra
   rbd::frame_aim_add_wave(S, nf, nu, tid, (int)blockDim.x, n, gx, gxx);
 }
 
+// Joint-acceleration cost (DDP_HIP_FLAG_JOINT_ACCEL_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T-1, after every other
+// cost kernel on the same stream (the fixed order of additions: ..., control-gravity, frame aiming, joint accelerations).  A block
+// whose nv weights are all 0 returns at once, before any LDS access or barrier.  The wave runs the analytic recursion of
+// rbd_deriv.h at (x_t, u_t) (tree_derivatives_wave on a fixed base, ff_derivatives_wave on a free-flyer root: analytic whatever
+// the context's first order is; FX / FU are not read), which leaves T = [dtau/dq | dtau/dv], M^-1 and a = qdd in LDS.  Then
+//   Z = [Zq Zv] = -M^-1 T, row-major nv x 2 nv, over the spent M and column records of FfLds (contiguous; the rows of weight != 0),
+//   Zu = M^-1 where it stands (Zu_rj = X[r + j nv]),   w and w o r (r = a - a_ref) over the spent local placements,
+// and the five additions, each entry by one lane as a sum over the rows of weight != 0 in ascending order (no atomics):
+//   lx[j] += sum_r Z_rj (w r)_r,   lu[j] += sum_r Zu_rj (w r)_r,   lux[j][c] += sum_r Zu_rj w_r Z_rc,
+//   lxx[a][c] += sum_r Z_ra w_r Z_rc,   luu[a][c] += sum_r Zu_ra w_r Zu_rc      for a >= c, the same number added at [c][a]:
+// Gauss-Newton, symmetric bit for bit.  The products run on the vector ALU (lanes along a row of Z: conflict-free LDS reads, the
+// other operand a broadcast).  No scratch; dynamic LDS FfLds<NJ>::TOTAL doubles
+template <int NJ>
+__global__ __launch_bounds__(64) void lin_joint_accel_cost_kernel(LinParams p, JointAccelDev ja) {
+  typedef rbdd::FfLds<NJ> L;
+  static_assert(NJ * NJ + L::CR * NJ >= 2 * NJ * NJ, "Z must fit over M and the column records");
+  const int64_t T = p.d.T;
+  const int64_t bt = blockIdx.x;                        // b T + t, t < T
+  const int64_t row = bt / T * (T + 1) + bt % T;        // the record and X have T+1 rows per instance
+  const int N = (int)p.d.nv, W2 = 2 * N, n = (int)p.d.n, mu = (int)p.d.m;
+  const int tid = threadIdx.x;
+  const double* w = ja.weight + row * N;
+  if (!rbd::weights_any(w, N)) return;
+  const DevModel& m = *p.model;
+  const double* x = p.x + row * p.d.nx;
+  const double* u = p.u + bt * mu;
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  if (m.ff) rbdd::ff_derivatives_wave<NJ>(m, x, x + m.nq, u, lds, tid);
+  else rbdd::tree_derivatives_wave<NJ>(m, x, x + m.nq, u, lds, tid);
+  const double* s_X = lds + L::X;
+  const double* s_T = lds + L::T;
+  double* s_Z = lds + L::M;
+  double* s_w = lds + L::LOC;
+  double* s_wr = s_w + NJ;
+  if (tid < N) {
+    const double wi = w[tid];
+    s_w[tid] = wi;
+    s_wr[tid] = wi != 0.0 ? wi * (rbdd::wave_qdd<NJ>(lds)[tid] - ja.target[row * N + tid]) : 0.0;
+  }
+  __syncthreads();
+  for (int r = 0; r < N; ++r) {
+    if (s_w[r] == 0.0) continue;
+    for (int j = tid; j < W2; j += 64) {
+      double s = 0.0;
+      for (int l = 0; l < N; ++l) s += s_X[r + l * N] * s_T[l * W2 + j];
+      s_Z[r * W2 + j] = -s;
+    }
+  }
+  __syncthreads();
+  double* gx = p.lx + bt * n;
+  double* gxx = p.lxx + bt * n * n;
+  double* gu = p.lu + bt * mu;
+  double* guu = p.luu + bt * mu * mu;
+  double* gux = p.lux + bt * mu * n;
+  for (int j = tid; j < W2; j += 64) {
+    double s = 0.0;
+    for (int r = 0; r < N; ++r)
+      if (s_w[r] != 0.0) s += s_Z[r * W2 + j] * s_wr[r];
+    gx[j] += s;
+  }
+  if (tid < N) {
+    double s = 0.0;
+    for (int r = 0; r < N; ++r)
+      if (s_w[r] != 0.0) s += s_X[r + tid * N] * s_wr[r];
+    gu[tid] += s;
+  }
+  for (int c = 0; c < W2; ++c)
+    for (int a = c + tid; a < W2; a += 64) {
+      double h = 0.0;
+      for (int r = 0; r < N; ++r)
+        if (s_w[r] != 0.0) h += s_Z[r * W2 + a] * s_w[r] * s_Z[r * W2 + c];
+      gxx[a + (int64_t)c * n] += h;
+      if (a != c) gxx[c + (int64_t)a * n] += h;
+    }
+  for (int j = 0; j < N; ++j)
+    for (int c = tid; c < W2; c += 64) {
+      double h = 0.0;
+      for (int r = 0; r < N; ++r)
+        if (s_w[r] != 0.0) h += s_X[r + j * N] * s_w[r] * s_Z[r * W2 + c];
+      gux[j + (int64_t)c * mu] += h;
+    }
+  for (int c = 0; c < N; ++c)
+    for (int a = c + tid; a < N; a += 64) {
+      double h = 0.0;
+      for (int r = 0; r < N; ++r)
+        if (s_w[r] != 0.0) h += s_X[r + a * N] * s_w[r] * s_X[r + c * N];
+      guu[a + (int64_t)c * mu] += h;
+      if (a != c) guu[c + (int64_t)a * mu] += h;
+    }
+}
+
 // Obstacle cost (DDP_HIP_FLAG_OBSTACLE_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost kernel
-// on the same stream (the fixed order of additions: ..., control-gravity, frame aiming, obstacles).  The penalty is one-sided, so most
+// on the same stream (the fixed order of additions: ..., frame aiming, joint accelerations, obstacles).  The penalty is one-sided, so most
 // waves have nothing to add and must cost next to nothing.  A block whose weights are all 0 returns at once.  Phase 1: lane
 // k < n_points walks point k (rbd::frame_point) and runs over its live slots in ascending order; a lane with an active pair
 // (w != 0, e != 0, a direction u) forms g_k = sum_o w e u and the symmetric M_k = sum_o w u u^T on the way, in registers.  One
@@ -682,7 +774,7 @@ __global__ __launch_bounds__(64) void lin_obstacle_cost_kernel(LinParams p, Obst
 }
 
 // Self-collision cost (DDP_HIP_FLAG_SELF_COLLISION_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost
-// kernel on the same stream (the fixed order of additions: ..., control-gravity, obstacles, self-collision).  One-sided like the
+// kernel on the same stream (the fixed order of additions: ..., joint accelerations, obstacles, self-collision).  One-sided like the
 // obstacle cost: most waves have nothing to add.  A block whose weights are all 0 returns at once.  Phase 1: lane k < n_points
 // walks sphere k (rbd::frame_point); lane i < n_pairs fetches p_a and p_b from the lanes that hold them (cross-lane reads: no
 // LDS) and forms d_i.  One wave-level vote decides: a wave without an active pair (w != 0, e != 0, a direction u) returns here,
@@ -1583,7 +1675,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     else hipLaunchKernelGGL(lin_cost_kernel, dim3((unsigned)BT), dim3(64), 0, ctx->stream, p);
     // the add-on terms, one kernel per live term, each adding onto what the ones before it left.  The fixed order of additions:
     // cost, tracking, frame positions, frame orientations, limits, CoM, frame velocities, momentum, balance regions, relative
-    // frames, control-gravity, frame aiming, obstacles, self-collision
+    // frames, control-gravity, frame aiming, joint accelerations, obstacles, self-collision
     const dim3 blocks((unsigned)(BT + d.batch));
     const FrameCostDev fc = frame_cost_dev(ctx);
     const StateLimitsDev sl = state_limits_dev(ctx);
@@ -1594,6 +1686,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     const RelativeFrameDev rf = relative_frame_dev(ctx);
     const ControlGravDev cg = control_grav_dev(ctx);
     const FrameAimDev fa = frame_aim_dev(ctx);
+    const JointAccelDev ja = joint_accel_dev(ctx);
     const ObstacleCostDev ob = obstacle_cost_dev(ctx);
     const SelfCollisionDev sc = self_collision_dev(ctx);
     auto add = [&](bool live, auto kernel, const auto& dev) { if (live) hipLaunchKernelGGL(kernel, blocks, dim3(64), 0, ctx->stream, p, dev); };
@@ -1608,6 +1701,12 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     if (cg.weight)   // (t < T alone; G in dynamic LDS, nv^2 doubles)
       hipLaunchKernelGGL(lin_control_grav_cost_kernel, dim3((unsigned)BT), dim3(64), sizeof(double) * (size_t)(d.nv * d.nv), ctx->stream, p, cg);
     add(fa.weight, lin_frame_aim_cost_kernel, fa);
+    if (ja.weight) {   // (t < T alone; nv <= 38 by the create-time check: the recursion's record in dynamic LDS, above 64 KB)
+      constexpr int lds = (int)(sizeof(double) * rbdd::FfLds<DDP_HIP_MAX_JOINT_ACCEL_NV>::TOTAL);
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&lin_joint_accel_cost_kernel<DDP_HIP_MAX_JOINT_ACCEL_NV>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      hipLaunchKernelGGL((lin_joint_accel_cost_kernel<DDP_HIP_MAX_JOINT_ACCEL_NV>), dim3((unsigned)BT), dim3(64), lds, ctx->stream, p, ja);
+    }
     add(ob.geom, lin_obstacle_cost_kernel, ob);
     add(sc.margin, lin_self_collision_cost_kernel, sc);
   }

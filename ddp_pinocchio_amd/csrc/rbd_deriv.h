@@ -564,6 +564,226 @@ __device__ void ff_derivatives_wave(const DevModel& m, const double* q, const do
   __syncthreads();
 }
 
+// The fixed-base sibling of ff_derivatives_wave: partials of qdd = ABA(q, v, tau) for a tree of 1-DoF joints on a fixed base
+// (nq = nv, column c = joint c = body c), the recursion of aba_derivatives_lane in the cooperative layout above -- one wave, lane =
+// joint, the records of FfLds<NJ>.  It leaves T = [d tau/dq | d tau/dv] in lds + FfLds::T, M^-1 in lds + FfLds::X and qdd in the
+// last NJ doubles of FfLds::VEC's run (wave_qdd), as ff_derivatives_wave does.  What falls away against the free flyer: every
+// column is a 1-DoF column with a parent frame that moves (u = J x ov, g = u x ov - J x oa, w = 2 u), no two columns share a body,
+// and the root joint's velocity product enters oa0 like any other (it is zero: ov_0 = J_0 v_0).  A forest (several joints with
+// parent -1) is allowed.  Called by every thread of a one-wave work-group; q, v, tau may be global.  nv <= NJ <= 64.
+template <int NJ>
+__device__ void tree_derivatives_wave(const DevModel& m, const double* q, const double* v, const double* tau, double* lds, int lane) {
+  typedef FfLds<NJ> L;
+  constexpr int BR = L::BR, CR = L::CR;
+  const int N = m.nv, W2 = 2 * N;
+  const int nth = blockDim.x;
+  double* s_loc = lds + L::LOC;
+  double* s_bod = lds + L::BOD;
+  double* s_M = lds + L::M;
+  double* s_col = lds + L::COL;
+  double* s_X = lds + L::X;
+  double* s_q = lds + L::VEC;
+  double* s_v = s_q + NJ + 1;
+  double* s_tau = s_v + NJ;
+  double* s_rhs = s_tau + NJ;
+  double* s_qdd = s_rhs + NJ;
+  int* s_par = reinterpret_cast<int*>(lds + L::PAR);
+  for (int k = lane; k < N; k += nth) { s_q[k] = q[k]; s_v[k] = v[k]; s_tau[k] = tau[k]; s_par[k] = m.parent[k]; }
+  for (int k = lane; k < N * N; k += nth) s_M[k] = 0.0;
+  __syncthreads();
+  // joint placements (parent coordinates = Rc child coordinates + r), then world placements along each joint's path
+  if (lane < N) {
+    double E[9], r[3];
+    rbd::joint_placement(m, lane, s_q[lane], E, r);
+    double* o = s_loc + 12 * lane;
+    for (int k = 0; k < 3; ++k)
+      for (int l = 0; l < 3; ++l) o[3 * k + l] = E[3 * l + k];
+    for (int k = 0; k < 3; ++k) o[9 + k] = r[k];
+  }
+  __syncthreads();
+  if (lane < N) {
+    double oR[9], op[3];
+    const double* o = s_loc + 12 * lane;
+    for (int k = 0; k < 9; ++k) oR[k] = o[k];
+    for (int k = 0; k < 3; ++k) op[k] = o[9 + k];
+    for (int a = s_par[lane]; a >= 0; a = s_par[a]) {
+      const double* wa = s_loc + 12 * a;
+      double t9[9], t3[3];
+      mm3(wa, oR, t9);
+      mv3(wa, op, t3);
+      for (int k = 0; k < 9; ++k) oR[k] = t9[k];
+      for (int k = 0; k < 3; ++k) op[k] = wa[9 + k] + t3[k];
+    }
+    double* br = s_bod + BR * lane;
+    for (int k = 0; k < 9; ++k) br[k] = oR[k];
+    for (int k = 0; k < 3; ++k) br[9 + k] = op[k];
+    // the axis J_c and J_c v_c (parked in the u slot)
+    double J[6];
+    world_axis(m, lane, oR, op, J);
+    double* cr = s_col + CR * lane;
+    for (int k = 0; k < 6; ++k) { cr[k] = J[k]; cr[6 + k] = J[k] * s_v[lane]; }
+  }
+  __syncthreads();
+  // body velocities: ov_b = sum over the path of J_c v_c
+  if (lane < N) {
+    double ov[6] = {0, 0, 0, 0, 0, 0};
+    for (int a = lane; a >= 0; a = s_par[a])
+      for (int k = 0; k < 6; ++k) ov[k] += s_col[CR * a + 6 + k];
+    for (int k = 0; k < 6; ++k) s_bod[BR * lane + 12 + k] = ov[k];
+    // the velocity-product term ov_c x J_c v_c (parked in the g slot)
+    double* cr = s_col + CR * lane;
+    crm(ov, cr + 6, cr + 12);
+  }
+  __syncthreads();
+  // per body at qdd = 0: oa0 = a_grav + path sum of the velocity products; world inertia, bias matrix, force f0 = I oa0 + ov x* I ov
+  if (lane < N) {
+    double* br = s_bod + BR * lane;
+    double oa[6] = {0, 0, 0, -m.gravity[0], -m.gravity[1], -m.gravity[2]};
+    for (int a = lane; a >= 0; a = s_par[a])
+      for (int k = 0; k < 6; ++k) oa[k] += s_col[CR * a + 12 + k];
+    double I6[36], B[36], h[6], Ioa[6], vxh[6];
+    world_inertia(m.I6[lane], br, br + 9, I6);
+    m6v(I6, br + 12, h);
+    m6v(I6, oa, Ioa);
+    crf(br + 12, h, vxh);
+    bias_matrix(I6, br + 12, h, B);
+    for (int k = 0; k < 6; ++k) { br[18 + k] = oa[k]; br[96 + k] = Ioa[k] + vxh[k]; }
+    for (int k = 0; k < 36; ++k) { br[24 + k] = I6[k]; br[60 + k] = B[k]; }
+  }
+  __syncthreads();
+  // subtree sums leaves -> root (Ic | Bc | f0): a thread only ever touches its own entries, children precede parents
+  for (int i = N - 1; i >= 1; --i) {
+    const int par = s_par[i];
+    if (par < 0) continue;
+    for (int k = lane; k < 78; k += nth) s_bod[BR * par + 24 + k] += s_bod[BR * i + 24 + k];
+  }
+  __syncthreads();
+  // y_c = Ic J_c; the bias torques J_c . f0c; M's lower triangle: M(c, i) = J_i . y_c for the joints i of c's path
+  if (lane < N) {
+    const double* br = s_bod + BR * lane;
+    double* cr = s_col + CR * lane;
+    double y[6], bias = 0.0;
+    m6v(br + 24, cr, y);
+    for (int k = 0; k < 6; ++k) { cr[24 + k] = y[k]; bias += cr[k] * br[96 + k]; }
+    s_rhs[lane] = s_tau[lane] - bias;
+    for (int i = lane; i >= 0; i = s_par[i]) {
+      double s = 0.0;
+      for (int k = 0; k < 6; ++k) s += s_col[CR * i + k] * y[k];
+      s_M[lane + i * N] = s;
+    }
+  }
+  __syncthreads();
+  // Cholesky M = L L^T in place (lower triangle): thread r owns row r
+  for (int k = 0; k < N; ++k) {
+    const double dk = sqrt(s_M[k + k * N]);
+    __syncthreads();
+    if (lane == k) s_M[k + k * N] = dk;
+    if (lane > k && lane < N) s_M[lane + k * N] = s_M[lane + k * N] / dk;
+    __syncthreads();
+    if (lane > k && lane < N) {
+      const double lrk = s_M[lane + k * N];
+      for (int c = k + 1; c <= lane; ++c) s_M[lane + c * N] -= lrk * s_M[c + k * N];
+    }
+    __syncthreads();
+  }
+  // M^-1: thread c solves L L^T x = e_c into column c of X
+  if (lane < N) {
+    double* x = s_X + lane * N;
+    for (int i = 0; i < N; ++i) {
+      double s = i == lane ? 1.0 : 0.0;
+      for (int l = 0; l < i; ++l) s -= s_M[i + l * N] * x[l];
+      x[i] = s / s_M[i + i * N];
+    }
+    for (int i = N - 1; i >= 0; --i) {
+      double s = x[i];
+      for (int l = i + 1; l < N; ++l) s -= s_M[l + i * N] * x[l];
+      x[i] = s / s_M[i + i * N];
+    }
+  }
+  __syncthreads();
+  if (lane < N) {
+    double s = 0.0;
+    for (int l = 0; l < N; ++l) s += s_X[lane + l * N] * s_rhs[l];
+    s_qdd[lane] = s;
+  }
+  __syncthreads();
+  // accelerations: oa = oa0 + alpha, alpha_b = path sum of J_c qdd_c; forces I_b alpha_b (over the spent placements) summed
+  // leaves -> root and added to f0c: ofc
+  if (lane < N) {
+    double* br = s_bod + BR * lane;
+    double al[6] = {0, 0, 0, 0, 0, 0};
+    for (int a = lane; a >= 0; a = s_par[a])
+      for (int k = 0; k < 6; ++k) al[k] += s_col[CR * a + k] * s_qdd[a];
+    double I6[36], f[6];
+    world_inertia(m.I6[lane], br, br + 9, I6);
+    m6v(I6, al, f);
+    for (int k = 0; k < 6; ++k) { br[18 + k] += al[k]; s_loc[12 * lane + k] = f[k]; }
+  }
+  __syncthreads();
+  for (int i = N - 1; i >= 1; --i) {
+    const int par = s_par[i];
+    if (par < 0) continue;
+    for (int k = lane; k < 6; k += nth) s_loc[12 * par + k] += s_loc[12 * i + k];
+  }
+  __syncthreads();
+  for (int k = lane; k < 6 * N; k += nth) s_bod[BR * (k / 6) + 96 + k % 6] += s_loc[12 * (k / 6) + k % 6];
+  __syncthreads();
+  // column quantities u | g | w | z | Fq | Fv
+  if (lane < N) {
+    const double* br = s_bod + BR * lane;
+    double* cr = s_col + CR * lane;
+    const double* J = cr;
+    const double* ov = br + 12;
+    double u[6], g[6], w[6], t1[6], t2[6], t3[6];
+    m6tv(br + 60, J, cr + 30);                            // z
+    crm(J, ov, u);
+    crm(u, ov, t1);
+    crm(J, br + 18, t2);
+    for (int k = 0; k < 6; ++k) { g[k] = t1[k] - t2[k]; w[k] = 2.0 * u[k]; }
+    for (int k = 0; k < 6; ++k) { cr[6 + k] = u[k]; cr[12 + k] = g[k]; cr[18 + k] = w[k]; }
+    crf(J, br + 96, t1);
+    m6v(br + 60, u, t2);
+    m6v(br + 24, g, t3);
+    for (int k = 0; k < 6; ++k) cr[36 + k] = t1[k] - t2[k] + t3[k];
+    m6v(br + 60, J, t1);
+    m6v(br + 24, w, t2);
+    for (int k = 0; k < 6; ++k) cr[42 + k] = t1[k] - t2[k];
+  }
+  __syncthreads();
+  double* s_T = lds + L::T;
+  for (int k = lane; k < N * W2; k += nth) s_T[k] = 0.0;
+  __syncthreads();
+  // T: thread c walks its path; it writes row c (columns i of the path) and column c of the rows of its proper ancestors -- no
+  // entry has two writers
+  if (lane < N) {
+    const int c = lane;
+    const double* cc = s_col + CR * c;
+    double sq = 0, sv = 0;
+    for (int k = 0; k < 6; ++k) { sq += cc[k] * cc[36 + k]; sv += cc[k] * cc[42 + k]; }
+    s_T[c * W2 + c] = sq;
+    s_T[c * W2 + N + c] = sv;
+    for (int i = s_par[c]; i >= 0; i = s_par[i]) {
+      const double* ci = s_col + CR * i;
+      double aq = 0, av = 0, dq = 0, dv = 0;
+      for (int k = 0; k < 6; ++k) {
+        aq += ci[k] * cc[36 + k];                          // d tau_i / d(q, v)_c: i a proper ancestor
+        av += ci[k] * cc[42 + k];
+        dq += -cc[30 + k] * ci[6 + k] + cc[24 + k] * ci[12 + k];   // d tau_c / d(q, v)_i
+        dv += cc[30 + k] * ci[k] - cc[24 + k] * ci[18 + k];
+      }
+      s_T[i * W2 + c] = aq;
+      s_T[i * W2 + N + c] = av;
+      s_T[c * W2 + i] = dq;
+      s_T[c * W2 + N + i] = dv;
+    }
+  }
+  __syncthreads();
+}
+
+// qdd of the trajectory point (after ff_derivatives_wave / tree_derivatives_wave): nv doubles
+template <int NJ>
+__device__ __forceinline__ const double* wave_qdd(const double* lds) { return lds + FfLds<NJ>::VEC + 4 * NJ + 1; }
+
 // row r of -M^-1 T, column j (after ff_derivatives_wave)
 template <int NJ>
 __device__ __forceinline__ double ff_minv_T(const double* lds, int N, int r, int j) {

@@ -493,6 +493,34 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * leave (after the momentum's, before the relative frames'). */
 #define DDP_HIP_FLAG_BALANCE_REGION_COST 32768u
 #define DDP_HIP_MAX_REGION_PLANES 8
+/* Say how hard the robot accelerates: "move smoothly", "arrive at rest and stay at rest", "do not jerk the torso", "follow this
+ * acceleration profile".  A weight on v damps speed, not its change, and a weight on u penalises torque, a poor stand-in for
+ * acceleration on a robot whose inertia varies by orders of magnitude between the wrist and the hip.  The first term whose
+ * residual goes through the dynamics itself.  Per instance b, t = 0 .. T-1 and tangent row i = 0 .. nv-1 a target
+ * a_ref[b][t][i] (finite) and a weight w[b][t][i] >= 0:
+ *   a = aba(q_t, v_t, u_t),      r = a - a_ref[b][t],      l(t, x, u) += 1/2 sum_i w_i r_i^2      t < T
+ * with a the model's own forward dynamics (what ddp_hip_model_aba returns), the six root rows of a free flyer included: the
+ * rate of the body twist [linear; angular].  There is no control at T and no term at T.  Derivatives are taken in the tangent at
+ * x: with Z = [Zq | Zv | Zu] = [da/d(delta q) | da/dv | M^-1] = [-M^-1 dtau/dq | -M^-1 dtau/dv | M^-1] (nv x 3 nv, dense: what
+ * ddp_hip_model_aba_derivatives returns), over the rows with w_i != 0 alone,
+ *   lx += [Zq Zv]^T (w o r),   lu += Zu^T (w o r),
+ *   lxx += [Zq Zv]^T diag(w) [Zq Zv],   lux += Zu^T diag(w) [Zq Zv],   luu += Zu^T diag(w) Zu      (Gauss-Newton: sum_i w_i r_i
+ * d^2 a_i is dropped; exact where r = 0, positive semidefinite).  The jacobians are the analytic ones whatever first_order_fd /
+ * fd_mode the context uses for FX / FU: the term neither reads FX / FU nor depends on the order of the linearisation's stages.  lxx
+ * and luu are formed on the lower triangle with the diagonal and mirrored: symmetric bit for bit; every sum runs over the rows in
+ * ascending order, no atomics: reproducible run to run.  A row of weight 0 is left out (not multiplied by 0), a (b, t) whose
+ * weights are all 0 forms nothing, and with nothing uploaded or every weight 0 no kernel of the term is launched: the context
+ * computes bit for bit what it computes without the flag.  With DDP_HIP_FLAG_CONTROL_BOUNDS a is formed from the control the
+ * rollout applied: the clamped one, as stored in U / U_NEW and the candidates' controls.  The values are formed by the forward
+ * dynamics at (x_t, u_t), never by (v_{t+1} - v_t) / dt: ddp_hip_cost_seq_aug is also asked about trajectories that are no
+ * rollouts of their controls.  The data travels through ddp_hip_joint_accel_cost_* below; at create targets and weights are 0.
+ * Tree models only (the pendulum: DDP_HIP_E_UNSUPPORTED), fixed base or free-flyer root, with nv <= 38 (39 .. 64:
+ * DDP_HIP_E_UNSUPPORTED at create -- the limit of ddp_hip_model_aba_derivatives and of the free-flyer first order: the
+ * recursion's LDS record does not fit beside the jacobian at 64).  The flag stands alone and combines with every other flag: the
+ * terms are formed by kernels of their own, which add onto what the other terms' kernels leave (after frame aiming's, before the
+ * obstacles'). */
+#define DDP_HIP_FLAG_JOINT_ACCEL_COST 65536u
+#define DDP_HIP_MAX_JOINT_ACCEL_NV 38
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -651,6 +679,16 @@ int ddp_hip_balance_region_download(ddp_hip_ctx* ctx, double* geom, double* weig
  * X_NEW (which = 1), +inf where no plane is live, NaN where a d is.  From the first ddp_hip_balance_region_set_planes with a
  * plane on (before: DDP_HIP_E_ARG), live weights or not. */
 int ddp_hip_balance_region_margin(ddp_hip_ctx* ctx, int which, double* out);
+/* The joint-acceleration terms of a context created with DDP_HIP_FLAG_JOINT_ACCEL_COST (else DDP_HIP_E_UNSUPPORTED), stream-ordered
+ * like ddp_hip_momentum_cost_upload.  Host arrays [n_instances][T+1][nv]: targets and weights, one per tangent row of v; row T
+ * belongs to no term (there is no control at T), keeps what it held at create and is read by no kernel.  A NULL pointer leaves
+ * that side as it is.  An upload is refused as a whole (DDP_HIP_E_ARG, nothing written) for a bad instance range, a non-finite
+ * target, a negative or non-finite weight and a non-zero weight in row T.  A free-flyer root's six rows carry terms like any other. */
+int ddp_hip_joint_accel_cost_upload(ddp_hip_ctx* ctx, const double* target, const double* weight, int64_t first_instance, int64_t n_instances);
+int ddp_hip_joint_accel_cost_download(ddp_hip_ctx* ctx, double* target, double* weight, int64_t first_instance, int64_t n_instances);
+/* "How hard did it accelerate": out[batch][T][nv] = aba(x_t, u_t) along X / U (which = 0) or X_NEW / U_NEW (which = 1), formed by
+ * the cost kernel's forward dynamics in one launch, live weights or not. */
+int ddp_hip_joint_accel(ddp_hip_ctx* ctx, int which, double* out);
 
 /* make_trajectory (ddp.hpp:392-415): X[0] and U given -> X[1..T] */
 int ddp_hip_rollout(ddp_hip_ctx* ctx);
