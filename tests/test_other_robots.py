@@ -1,7 +1,8 @@
 """The run-time-shaped kernels on robots of other sizes and trees (tests/robots.py): everything a user's own robot runs is
 instantiated for a size class (1 / 6 / 38 / 64 joints) and reads nv at run time, and the built-in robots reach one size per
 class.  Every GPU test holds the device against the C oracle on the same TableModel, at the project's own tolerances, and
-asserts the path ctx.info() reports, so that a case cannot silently stop reaching its kernel.
+asserts the path ctx.info() reports, so that a case cannot silently stop reaching its kernel.  The add-on cost terms on these
+robots are in test_cost_terms_other_robots.py (test_com_term stays here).
 
 Horizons are 2 .. 4 and the batch is 3 (one instance per workgroup or lane group: the second and third catch a wrong instance
 stride).  The oracle-only guards (the catalogue is what it claims; the line-search decisions do not hang on rounding) run
