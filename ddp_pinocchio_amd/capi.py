@@ -44,6 +44,7 @@ MAX_FRAME_PAIRS = 4
 MAX_AIM_FRAMES = 4
 OBSTACLE_SPHERE, OBSTACLE_HALFSPACE = 0, 1
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
+ADVANCE_NO_ROLL, ADVANCE_OPEN_LOOP, ADVANCE_CLOSED_LOOP = 0, 1, 2
 
 SEQ_NAMES = [
     "X", "U", "X_NEW", "U_NEW", "LFX", "LFXX", "LX", "LU", "LXX", "LUX", "LUU",
@@ -88,6 +89,7 @@ EXPORTS = [
     "ddp_hip_balance_region_set_planes", "ddp_hip_balance_region_upload", "ddp_hip_balance_region_download",
     "ddp_hip_balance_region_margin", "ddp_hip_model_capture_point",
     "ddp_hip_joint_accel_cost_upload", "ddp_hip_joint_accel_cost_download", "ddp_hip_joint_accel",
+    "ddp_hip_advance",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -225,6 +227,8 @@ def lib():
         L.ddp_hip_balance_region_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_balance_region_margin.argtypes = [C.c_void_p, C.c_int, _dp]
         L.ddp_hip_model_capture_point.argtypes = [C.c_void_p, _dp, _dp, C.c_double, _dp, _dp, _dp]
+    if hasattr(L, "ddp_hip_advance"):  # (likewise: Context.advance and solver.mpc_step)
+        L.ddp_hip_advance.argtypes = [C.c_void_p, C.c_int64, _dp, C.c_int32]
     L.ddp_hip_rollout.argtypes = [C.c_void_p]
     L.ddp_hip_linearize.argtypes = [C.c_void_p]
     L.ddp_hip_linearize_stages.argtypes = [C.c_void_p, C.c_uint32]
@@ -1001,6 +1005,22 @@ class Context:
 
     def swap_traj(self):
         _check(lib().ddp_hip_swap_traj(self._h), "swap_traj")
+
+    def advance(self, shift, x0=None, mode=ADVANCE_CLOSED_LOOP):
+        """Moves the window on by `shift` steps on the resident data (ddp_hip_advance; ddp_hip.h): the trajectory, the gains and
+        every per-step table of every instance, then the re-roll `mode` asks for.  x0: the measured states, (nx,) for every
+        instance or (batch, nx); None: X[0] becomes the old X[shift].  shift in 1 .. T"""
+        sp = self.spec
+        if isinstance(shift, bool) or int(shift) != shift or not 1 <= int(shift) <= sp.T:
+            raise ValueError(f"advance: shift {shift!r}, expected an integer in 1 .. {sp.T}")
+        if mode not in (ADVANCE_NO_ROLL, ADVANCE_OPEN_LOOP, ADVANCE_CLOSED_LOOP):
+            raise ValueError(f"advance: mode {mode!r}, expected ADVANCE_NO_ROLL, ADVANCE_OPEN_LOOP or ADVANCE_CLOSED_LOOP")
+        if x0 is not None:
+            x0 = np.asarray(x0, dtype=np.float64)
+            if x0.shape not in ((sp.nx,), (self.batch, sp.nx)):
+                raise ValueError(f"advance x0: shape {x0.shape}, expected {(sp.nx,)} or {(self.batch, sp.nx)}")
+            x0 = np.ascontiguousarray(np.broadcast_to(x0, (self.batch, sp.nx)))
+        return _check(lib().ddp_hip_advance(self._h, int(shift), _ptr(x0) if x0 is not None else None, int(mode)), "advance")
 
     def shard_pick(self, comm=None):
         """(best cost, global index) over every instance of every rank of `comm` (a Comm, or None: this context alone):

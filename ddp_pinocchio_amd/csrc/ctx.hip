@@ -234,6 +234,7 @@ static int cost_block_setup(ddp_hip_ctx* ctx, int term, int32_t items) {
   }
   k.items = items;
   k.live = false;
+  ctx->adv_dirty = true;   // (the advance's descriptor table goes by the layout)
   return DDP_HIP_OK;
 }
 
@@ -398,6 +399,7 @@ extern "C" int ddp_hip_destroy(ddp_hip_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   lin_teardown(ctx);
+  adv_teardown(ctx);
   fwd_teardown(ctx);
   bwd_teardown(ctx);
   for (int s = 0; s < DDP_HIP_SEQ_COUNT; ++s)

@@ -303,6 +303,14 @@ struct ddp_hip_ctx {
 
   bool box_dirty = false;       // CTRL_LO / CTRL_HI were uploaded since lo <= hi was last checked (ctx.hip: box_check)
 
+  // the receding-horizon advance (advance.hip, advance_plan.h): allocated by the first ddp_hip_advance, freed by adv_teardown
+  void* adv_tab_d = nullptr;    // the descriptor table, one record per array the shift moves
+  double* adv_x0_d = nullptr;   // [batch][nx] the measured states on their way to X[0]
+  int32_t adv_narr = 0;         // records in the table ...
+  int64_t adv_blocks = 0;       // ... and the workgroups of one shift launch
+  bool adv_dirty = true;        // a cost block's layout changed since the table was built (ctx.hip: cost_block_setup)
+  std::vector<double> adv_mu_h, adv_step_h;   // [batch] what the closed-loop roll hands ddp_hip_forward
+
   bool async_mode = false;     // ddp_hip_set_async: entry points that hand nothing back to the host do not wait for the stream
   uint32_t profile_mask = 0;   // bit (1 + kernel_id): that kernel class is bracketed by HIP events
   ProfSlot prof[DDP_HIP_K_COUNT];
@@ -356,6 +364,7 @@ int box_check(ddp_hip_ctx* ctx);                  // control bounds: DDP_HIP_E_A
 int fwd_setup(ddp_hip_ctx* ctx);
 bool fwd_lat_supported(const ddp_hip_ctx* ctx);   // the latency kernels of the forward sweep apply (tree, no constraints, Talos size)
 void fwd_teardown(ddp_hip_ctx* ctx);
+void adv_teardown(ddp_hip_ctx* ctx);              // advance.hip
 int lin_setup(ddp_hip_ctx* ctx);
 // the transitions of ctx->tensors (lin.hip); linearise's own two (about to write / has written the second order) are local to it
 int tensors_written_outside(ddp_hip_ctx* ctx, int seq);   // ddp_hip_device_ptr / upload / fill of `seq`: a no-op unless it is FXX / FUX / FUU

@@ -17,6 +17,17 @@ def solve(ctx, max_iterations, threshold, mu, reg, w, n, n_alpha=8, max_restarts
     return log
 
 
+def mpc_step(ctx, shift, x0=None, mode=None, **solve_args):
+    """One step of a receding-horizon loop on resident data: the window moves on by `shift` steps (Context.advance: x0 the
+    measured states or None, mode one of capi.ADVANCE_*, default the closed-loop re-roll), then `solve(ctx, **solve_args)` runs
+    from what the advance left -- which is the input `solve` documents.  Targets, obstacles and bounds of the steps that have
+    entered the window are uploaded by the caller, after this call or between an `advance` and a `solve` of their own (a tail
+    row holds the last stage row until then).  Returns the solve's log."""
+    from . import capi
+    ctx.advance(shift, x0, capi.ADVANCE_CLOSED_LOOP if mode is None else mode)
+    return solve(ctx, **solve_args)
+
+
 def solve_stepwise(ctx, max_iterations, threshold, mu, reg, w, n, n_alpha=8, max_restarts=1000):
     """The same loop, one C-ABI call per operation (cross-check of ddp_hip_solve)."""
     B = ctx.batch

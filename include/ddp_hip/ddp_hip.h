@@ -723,6 +723,39 @@ int ddp_hip_cost_seq_aug(ddp_hip_ctx* ctx, int which, const double* mu);
 /* swap(traj, new_traj) (ddp.hpp:826) */
 int ddp_hip_swap_traj(ddp_hip_ctx* ctx);
 
+/* The receding-horizon advance (model-predictive control: solve, apply the first control, move the window on by `shift` steps, take
+ * the measured state, solve again), on the resident data: nothing is downloaded.  s = shift, 1 <= s <= T; "old" is the value before
+ * the call; x0: host [batch][nx], the measured states, or NULL (X[0] becomes the old X[s]).  The call applies to every instance,
+ * whatever ddp_hip_set_active says, and leaves the active mask as it is.
+ *   arrays with T rows (U, COST_UREF, COST_WU, CTRL_LO, CTRL_HI, every side of the control-gravity block):
+ *     row[t] = old[t + s] for t < T - s,  row[t] = old[T - 1] for t >= T - s: a tail row holds the last stage row.
+ *   arrays with T + 1 rows whose last row is the terminal cost (COST_XREF, COST_WX, every side of every other add-on cost block,
+ *   as it is laid out now): rows 0 .. T-1 by the rule above; row T is not touched -- the terminal cost belongs to the end of the
+ *   window, not to an absolute time (the joint accelerations' weights keep their zero row T this way).
+ *   X:       X[t] = old[t + s] for t <= T - s,  old[T] for t > T - s (finite rows under the tail's zero gains), then X[0] = x0.
+ *   FB_JAC:  FB_JAC[t] = old[t + s] for t < T - s, exact zeros in the tail.    FB_VAL: 0 everywhere (the step has been taken).
+ * What new information enters the window at its far end (targets, obstacles, bounds of the new steps) is the caller's to upload,
+ * with the uploads above, after the call.  Then, by mode:
+ *   NO_ROLL      nothing more.
+ *   OPEN_LOOP    X[1..T] = the rollout of the shifted U from X[0]: bit for bit what ddp_hip_rollout gives (U as given, no clamp).
+ *   CLOSED_LOOP  u_t = clamp(U[t] + K[t] (x_t (-) X[t])), x_{t+1} = f(x_t, u_t) with the shifted U, K = FB_JAC and X: bit for bit
+ *                what ddp_hip_forward(n_alpha = 0) followed by ddp_hip_swap_traj gives with every instance active, X_NEW[0] = X[0]
+ *                and FB_VAL = 0 (the clamp with DDP_HIP_FLAG_CONTROL_BOUNDS alone); COSTS_OLD is written as that call writes it.
+ *                x_0 is X[0] itself, so u_0 = clamp(U[0]) and the gains act from t = 1 on, on what x_1 = f(x0, u_0) differs by.
+ * On return FB_ORIGIN[t] = MULT_ORIGIN[t] = X[t] for t < T and X_NEW / U_NEW are clones of X / U: the context is the input
+ * ddp_hip_solve documents.  Not touched, and stale exactly as after an upload of X: BOX_STAT, COSTS_OLD / COSTS_NEW (but for
+ * CLOSED_LOOP's), the candidates' arrays, every derivative sequence and what the context knows about its tensors.  Which add-on
+ * terms are live does not change (rows are permuted and repeated, never created), nor whether lo <= hi has been checked (a
+ * CLOSED_LOOP call checks it first, as ddp_hip_forward does).
+ * Refused before anything is written: ctx NULL, s < 1, s > T, an unknown mode, a non-finite entry of x0 and, on a free-flyer model,
+ * a root quaternion of x0 with | |quat| - 1 | > 1e-10 (DDP_HIP_E_ARG); a context with constraint rows (DDP_HIP_E_UNSUPPORTED: ne[t]
+ * varies with t and the batch shares eq_target, so the multipliers have no well-defined shift).  Everything runs on the context's
+ * stream; NO_ROLL honours ddp_hip_set_async, the rolling modes wait where ddp_hip_rollout / ddp_hip_forward do. */
+#define DDP_HIP_ADVANCE_NO_ROLL     0   /* shift and refill only */
+#define DDP_HIP_ADVANCE_OPEN_LOOP   1   /* ... then X[1..T] = rollout of the shifted U from X[0] (as ddp_hip_rollout: U as given) */
+#define DDP_HIP_ADVANCE_CLOSED_LOOP 2   /* ... then u_t = clamp(U[t] + K[t] (x_t (-) X[t])), x_{t+1} = f(x_t, u_t), with the shifted U, K, X */
+int ddp_hip_advance(ddp_hip_ctx* ctx, int64_t shift, const double* x0, int32_t mode);
+
 /* ---- outer augmented-Lagrangian loop (solve<M>, ddp.hpp:745-842): the parts of update_derivatives
  * (ddp.hpp:642-696) between compute_derivatives and backward_pass, on the resident sequences ---------- */
 /* affine_vector_function_seq_t::update_origin (mat_seq_common.hpp:62-89) with x_new = X:
