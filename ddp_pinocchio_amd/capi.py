@@ -37,11 +37,14 @@ FLAG_CONTROL_GRAV_COST = 8192
 FLAG_FRAME_AIM_COST = 16384
 FLAG_BALANCE_REGION_COST = 32768
 FLAG_JOINT_ACCEL_COST = 65536
+FLAG_CAPSULE_COST = 131072
 MAX_COST_FRAMES = 4
 MAX_COLLISION_POINTS, MAX_OBSTACLES = 16, 8
 MAX_COLLISION_PAIRS = 32
 MAX_FRAME_PAIRS = 4
 MAX_AIM_FRAMES = 4
+MAX_CAPSULES, MAX_CAPSULE_PAIRS = 16, 32
+CAPSULE_VS_ROBOT, CAPSULE_VS_CAPSULE, CAPSULE_VS_HALFSPACE = 0, 1, 2
 OBSTACLE_SPHERE, OBSTACLE_HALFSPACE = 0, 1
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
 ADVANCE_NO_ROLL, ADVANCE_OPEN_LOOP, ADVANCE_CLOSED_LOOP = 0, 1, 2
@@ -89,6 +92,8 @@ EXPORTS = [
     "ddp_hip_balance_region_set_planes", "ddp_hip_balance_region_upload", "ddp_hip_balance_region_download",
     "ddp_hip_balance_region_margin", "ddp_hip_model_capture_point",
     "ddp_hip_joint_accel_cost_upload", "ddp_hip_joint_accel_cost_download", "ddp_hip_joint_accel",
+    "ddp_hip_capsule_set_pairs", "ddp_hip_capsule_upload", "ddp_hip_capsule_download", "ddp_hip_capsule_clearance",
+    "ddp_hip_model_capsule_pair",
     "ddp_hip_advance",
 ]
 
@@ -227,6 +232,12 @@ def lib():
         L.ddp_hip_balance_region_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_balance_region_margin.argtypes = [C.c_void_p, C.c_int, _dp]
         L.ddp_hip_model_capture_point.argtypes = [C.c_void_p, _dp, _dp, C.c_double, _dp, _dp, _dp]
+    if hasattr(L, "ddp_hip_capsule_upload"):  # (likewise: set_capsule_pairs, set_capsule_cost, capsule_clearance, ModelHandle.capsule_pair)
+        L.ddp_hip_capsule_set_pairs.argtypes = [C.c_void_p, C.c_int32, _ip, _dp, _dp, _dp, C.c_int32, _ip, _ip, _ip]
+        L.ddp_hip_capsule_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_capsule_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
+        L.ddp_hip_capsule_clearance.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.ddp_hip_model_capsule_pair.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
     if hasattr(L, "ddp_hip_advance"):  # (likewise: Context.advance and solver.mpc_step)
         L.ddp_hip_advance.argtypes = [C.c_void_p, C.c_int64, _dp, C.c_int32]
     L.ddp_hip_rollout.argtypes = [C.c_void_p]
@@ -440,6 +451,19 @@ class ModelHandle:
         _check(lib().ddp_hip_model_frame_axis(self._h, int(joint), _ptr(off), _ptr(axis), _ptr(q), _ptr(p3), _ptr(n3),
                                               _ptr(J) if jacobian else None), "model_frame_axis")
         return (p3, n3, J.reshape(self.nv, 6).T.copy()) if jacobian else (p3, n3)
+
+    def capsule_pair(self, joint_a, a0, a1, joint_b, b0, b1, q, jacobian=False):
+        """The distance of two robot capsules at q, as FLAG_CAPSULE_COST defines it (ddp_hip.h): the segment a0 .. a1 fixed in
+        joint_a against b0 .. b1 fixed in joint_b (another joint).  (D, ca, cb): the distance of the closest points and the two
+        points in the world; with jacobian=True (D, ca, cb, J), J = dD / d(delta q) as (nv,).  No radius and no margin enter.
+        For margins such as "2 cm less than they are apart now" """
+        a0, a1, b0, b1, q = _f64(a0), _f64(a1), _f64(b0), _f64(b1), _f64(q)
+        if any(e.shape != (3,) for e in (a0, a1, b0, b1)):
+            raise ValueError("capsule_pair: every end is a 3-vector")
+        D, ca, cb, J = np.zeros(1), np.zeros(3), np.zeros(3), np.zeros(self.nv)
+        _check(lib().ddp_hip_model_capsule_pair(self._h, int(joint_a), _ptr(a0), _ptr(a1), int(joint_b), _ptr(b0), _ptr(b1), _ptr(q), _ptr(D),
+                                                _ptr(ca), _ptr(cb), _ptr(J) if jacobian else None), "model_capsule_pair")
+        return (float(D[0]), ca, cb, J) if jacobian else (float(D[0]), ca, cb)
 
     def capture_point(self, q, v, tau, jacobian=False):
         """The test point xi = c + tau cdot of FLAG_BALANCE_REGION_COST (ddp_hip.h) at the state (q, v) as (3,): the centre of mass
@@ -944,6 +968,54 @@ class Context:
         +inf where no pair is live, negative where two spheres are closer than their radii and margin allow"""
         out = np.zeros((self.batch, self.spec.T + 1))
         _check(lib().ddp_hip_self_collision_clearance(self._h, int(which), _ptr(out)), "self_collision_clearance")
+        return out
+
+    def set_capsule_pairs(self, capsules, pairs):
+        """The robot capsules [(joint, end0, end1, radius), ...] (1 .. MAX_CAPSULES of them; end0 == end1 is a sphere) and the
+        pairs [(a, kind, b), ...] (up to MAX_CAPSULE_PAIRS) of a context created with FLAG_CAPSULE_COST (ddp_hip.h), shared by the
+        batch: body A of a pair is capsule a, body B robot capsule b on another joint (CAPSULE_VS_ROBOT), or a world capsule
+        (CAPSULE_VS_CAPSULE) or a half-space (CAPSULE_VS_HALFSPACE) of the pair's own per-instance geometry; b is then not read
+        and (a, kind) is accepted.  With the same counts and kinds as before the per-instance data stays, else it is reset to 0"""
+        capsules, pairs = list(capsules), list(pairs)
+        if any(len(c) != 4 for c in capsules) or any(len(p) not in (2, 3) for p in pairs):
+            raise ValueError("set_capsule_pairs: every capsule is (joint, (x, y, z), (x, y, z), radius), every pair (a, kind, b)")
+        joint = np.ascontiguousarray([int(c[0]) for c in capsules], dtype=np.int32)
+        end0 = np.ascontiguousarray([c[1] for c in capsules], dtype=np.float64).reshape(-1)
+        end1 = np.ascontiguousarray([c[2] for c in capsules], dtype=np.float64).reshape(-1)
+        radius = np.ascontiguousarray([c[3] for c in capsules], dtype=np.float64)
+        if end0.size != 3 * len(joint) or end1.size != 3 * len(joint) or radius.shape != (len(joint),):
+            raise ValueError("set_capsule_pairs: every capsule is (joint, (x, y, z), (x, y, z), radius)")
+        pa = np.ascontiguousarray([int(p[0]) for p in pairs], dtype=np.int32)
+        kind = np.ascontiguousarray([int(p[1]) for p in pairs], dtype=np.int32)
+        pb = np.ascontiguousarray([int(p[2]) if len(p) == 3 else 0 for p in pairs], dtype=np.int32)
+        _check(lib().ddp_hip_capsule_set_pairs(self._h, len(joint), joint.ctypes.data_as(_ip), _ptr(end0), _ptr(end1), _ptr(radius), len(pa),
+                                               pa.ctypes.data_as(_ip), kind.ctypes.data_as(_ip), pb.ctypes.data_as(_ip)), "capsule_set_pairs")
+        self.n_capsule_pairs = len(pa)
+
+    def set_capsule_cost(self, geom=None, weight=None, first=0, count=None):
+        """The capsule terms of instances first .. first + count - 1 (a context created with FLAG_CAPSULE_COST; ddp_hip.h), of the
+        n_pairs pairs of set_capsule_pairs.  geom: eight doubles per pair, the last the margin -- (., ., ., ., ., ., ., m) of a
+        robot pair, (b0, b1, rho, m) of a world capsule, (n, h, ., ., ., m) of a half-space -- as (n_pairs, 8) for every instance
+        and t, (T+1, n_pairs, 8) for every instance or (count, T+1, n_pairs, 8); weight: >= 0, as (n_pairs,), (T+1, n_pairs) or
+        (count, T+1, n_pairs).  None leaves that side as it is.  The pair count is the one this object last passed to
+        set_capsule_pairs; before that call there is no shape to check against and the call raises ValueError."""
+        T1, npair = self.spec.T + 1, getattr(self, "n_capsule_pairs", 0)
+        if not npair:
+            raise ValueError("set_capsule_cost: no pairs yet, call set_capsule_pairs first")
+        count, arrs = self._cost_sides("set_capsule_cost", (("geom", geom, (T1, npair, 8), ((npair, 8),)),
+                                                            ("weight", weight, (T1, npair), ((npair,),))), first, count)
+        self._cost_upload(lib().ddp_hip_capsule_upload, "capsule_upload", arrs, first, count)
+
+    def capsule_cost(self, first=0, count=None):
+        """(geom, weight) of instances first .. first + count - 1: (count, T+1, n_pairs, 8) and (count, T+1, n_pairs)"""
+        T1, npair = self.spec.T + 1, getattr(self, "n_capsule_pairs", 0)        # (0 before set_capsule_pairs: empty arrays)
+        return self._cost_download(lib().ddp_hip_capsule_download, "capsule_download", ((T1, npair, 8), (T1, npair)), first, count)
+
+    def capsule_clearance(self, which=0):
+        """(batch, T+1): the least signed distance d_i of a pair of non-zero weight along X (which = 0) or X_NEW (which = 1);
+        +inf where no pair is live, negative where two bodies are closer than their radii and margin allow"""
+        out = np.zeros((self.batch, self.spec.T + 1))
+        _check(lib().ddp_hip_capsule_clearance(self._h, int(which), _ptr(out)), "capsule_clearance")
         return out
 
     def set_state_limits(self, lo=None, hi=None, weight=None, first=0, count=None):

@@ -1,0 +1,210 @@
+// capsule_cost.h -- per-instance capsule collision costs (DDP_HIP_FLAG_CAPSULE_COST, ddp_hip.h): capsules on the robot against each
+// other, against per-instance world capsules and against half-spaces, a one-sided penalty on their distance.  First the
+// closest-point routine, which calls no HIP function and compiles for the host as well (in the manner of advance_plan.h:
+// host/test_capsule_block.cpp runs it alone); then, for the device compiler, the kernel-side description and the device helpers.
+// The terms themselves are formed by kernels of their own in fwd.hip (cost values: capsule_cost_kernel, summed by com_sum_kernel;
+// clearances: capsule_clearance_kernel), lin.hip (derivatives: lin_capsule_cost_kernel) and model_api.hip (one pair:
+// model_capsule_pair_kernel).
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define CAP_HD __host__ __device__
+#else
+#define CAP_HD
+#endif
+
+CAP_HD static inline double capsule_clamp01(double x) { return x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x); }
+
+// The parameters s, t in [0, 1] of the closest points a0 + s (a1 - a0) and b0 + t (b1 - b0) of two segments, by the rule ddp_hip.h
+// pins: the degenerate cases first (a segment of length 0 is a point), then the interior solution for s, the t that belongs to
+// it, and where that t leaves [0, 1] the end of B and the s that belongs to the end.  Parallel segments (den <= 0) start from
+// s = 0.  Every product is rounded on its own (no contraction), so that a restatement in another language takes the same branches
+CAP_HD static inline void capsule_closest_params(const double* a0, const double* a1, const double* b0, const double* b1, double* s_out,
+                                                 double* t_out) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double d1[3] = {a1[0] - a0[0], a1[1] - a0[1], a1[2] - a0[2]};
+  const double d2[3] = {b1[0] - b0[0], b1[1] - b0[1], b1[2] - b0[2]};
+  const double r[3] = {a0[0] - b0[0], a0[1] - b0[1], a0[2] - b0[2]};
+  const double A = d1[0] * d1[0] + d1[1] * d1[1] + d1[2] * d1[2];
+  const double E = d2[0] * d2[0] + d2[1] * d2[1] + d2[2] * d2[2];
+  const double F = d2[0] * r[0] + d2[1] * r[1] + d2[2] * r[2];
+  const double C = d1[0] * r[0] + d1[1] * r[1] + d1[2] * r[2];
+  if (A == 0.0 && E == 0.0) { *s_out = 0.0; *t_out = 0.0; return; }
+  if (A == 0.0) { *s_out = 0.0; *t_out = capsule_clamp01(F / E); return; }
+  if (E == 0.0) { *t_out = 0.0; *s_out = capsule_clamp01(-C / A); return; }
+  const double Bv = d1[0] * d2[0] + d1[1] * d2[1] + d1[2] * d2[2];
+  const double den = A * E - Bv * Bv;
+  double s = den > 0.0 ? capsule_clamp01((Bv * F - C * E) / den) : 0.0;
+  double t = (Bv * s + F) / E;
+  if (t < 0.0) { t = 0.0; s = capsule_clamp01(-C / A); }
+  else if (t > 1.0) { t = 1.0; s = capsule_clamp01((Bv - C) / A); }
+  *s_out = s;
+  *t_out = t;
+}
+
+// ... and the two points themselves; returns their distance D
+CAP_HD static inline double capsule_closest_points(const double* a0, const double* a1, const double* b0, const double* b1, double* ca, double* cb) {
+  double s, t;
+  capsule_closest_params(a0, a1, b0, b1, &s, &t);
+  for (int k = 0; k < 3; ++k) {
+    ca[k] = a0[k] + s * (a1[k] - a0[k]);
+    cb[k] = b0[k] + t * (b1[k] - b0[k]);
+  }
+  const double x = ca[0] - cb[0], y = ca[1] - cb[1], z = ca[2] - cb[2];
+  return sqrt(x * x + y * y + z * z);
+}
+
+// A segment against the half-space n . p >= h: the end with the smaller n . p (end0 wins a tie) into ca; returns n . ca - h
+CAP_HD static inline double capsule_halfspace_point(const double* a0, const double* a1, const double* n, double h, double* ca) {
+  const double p0 = n[0] * a0[0] + n[1] * a0[1] + n[2] * a0[2], p1 = n[0] * a1[0] + n[1] * a1[1] + n[2] * a1[2];
+  const bool second = p1 < p0;
+  const double* e = second ? a1 : a0;
+  ca[0] = e[0]; ca[1] = e[1]; ca[2] = e[2];
+  return (second ? p1 : p0) - h;
+}
+
+#if defined(__HIPCC__)
+#include "frame_walk.h"
+#include "internal.h"
+#include "lie.h"
+#include "obstacle_cost.h"
+#include "rbd.h"
+
+// What a kernel reads of the context's capsule cost.  geom == nullptr: no terms (the flag is off, no pairs are set, or no
+// non-zero weight has been uploaded: the block's CostBlock::live)
+struct CapsuleCostDev {
+  const double *geom, *weight;     // [batch][T+1][npair][8], [batch][T+1][npair]
+  int32_t nc, npair;               // robot capsules, pairs
+  int32_t joint[DDP_HIP_MAX_CAPSULES];
+  uint8_t pa[DDP_HIP_MAX_CAPSULE_PAIRS], kind[DDP_HIP_MAX_CAPSULE_PAIRS], pb[DDP_HIP_MAX_CAPSULE_PAIRS];   // pair i: capsule pa[i] against kind[i] (pb[i]: a robot pair's)
+  double end[DDP_HIP_MAX_CAPSULES][2][3];
+  double radius[DDP_HIP_MAX_CAPSULES];
+};
+
+// always: the description whether or not a weight is live (ddp_hip_capsule_clearance works from the first set_pairs on)
+inline CapsuleCostDev capsule_cost_dev(const ddp_hip_ctx* ctx, bool always = false) {
+  CapsuleCostDev c{};
+  const CostBlock& k = ctx->cost[COST_CAPSULE];
+  if (!(always ? ctx->cp_npair > 0 : k.live)) return c;
+  c.geom = k.side[0];
+  c.weight = k.side[1];
+  c.nc = ctx->cp_nc;
+  c.npair = ctx->cp_npair;
+  for (int s = 0; s < ctx->cp_nc; ++s) {
+    c.joint[s] = ctx->cp_joint[s];
+    c.radius[s] = ctx->cp_radius[s];
+    for (int e = 0; e < 2; ++e)
+      for (int a = 0; a < 3; ++a) c.end[s][e][a] = ctx->cp_end[s][e][a];
+  }
+  for (int i = 0; i < ctx->cp_npair; ++i) {
+    c.pa[i] = (uint8_t)ctx->cp_pa[i];
+    c.kind[i] = (uint8_t)ctx->cp_kind[i];
+    c.pb[i] = (uint8_t)ctx->cp_pb[i];
+  }
+  return c;
+}
+
+namespace rbd {
+
+// Both ends of robot capsule k in the world: one walk joint -> root with the two points (no jacobian, no per-joint arrays)
+template <class M>
+__device__ __forceinline__ void capsule_ends(const M& m, bool ff, const CapsuleCostDev& cp, int k, const double* q, double (*e)[3]) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) e[s][a] = cp.end[k][s][a];
+  (void)walk_to_root<2, 0>(m, ff, cp.joint[k], q, e, nullptr, -1);
+}
+
+// The signed distance d_i of pair i, its closest points c_a, c_b and the direction u_i = dd / dc_a = -dd / dc_b.  a0, a1: the
+// world ends of body A; b0, b1: those of body B where it is a robot capsule (else not read); g: the pair's eight doubles.
+// Returns false where u does not exist (the closest points coincide: the pair has its value and no derivative)
+__device__ __forceinline__ bool capsule_distance(const CapsuleCostDev& cp, int i, const double* a0, const double* a1, const double* b0,
+                                                 const double* b1, const double* g, double* d, double* ca, double* cb, double* u) {
+  const double ra = cp.radius[cp.pa[i]], margin = g[7];
+  if (cp.kind[i] == DDP_HIP_CAPSULE_VS_HALFSPACE) {
+    *d = capsule_halfspace_point(a0, a1, g, g[3], ca) - ra - margin;
+    cb[0] = ca[0]; cb[1] = ca[1]; cb[2] = ca[2];
+    u[0] = g[0]; u[1] = g[1]; u[2] = g[2];
+    return true;
+  }
+  const bool robot = cp.kind[i] == DDP_HIP_CAPSULE_VS_ROBOT;
+  const double dist = capsule_closest_points(a0, a1, robot ? b0 : g, robot ? b1 : g + 3, ca, cb);
+  *d = dist - (ra + (robot ? cp.radius[cp.pb[i]] : g[6]) + margin);
+  if (dist == 0.0) { u[0] = u[1] = u[2] = 0.0; return false; }
+  u[0] = (ca[0] - cb[0]) / dist; u[1] = (ca[1] - cb[1]) / dist; u[2] = (ca[2] - cb[2]) / dist;
+  return true;
+}
+
+// What the lanes of one wave leave each other for the derivatives at one configuration (lin_capsule_cost_kernel, phase 2): lanes
+// j < nj their joint (rbd::stage_joint_lane), the active pairs' lanes their pair
+struct CapsuleWaveLds {
+  JointWorldLds jw;                                      // a_j, o_j, the paths, R_0
+  double ca[DDP_HIP_MAX_CAPSULE_PAIRS][3];               // of the active pairs: the closest point on A,
+  double cb[DDP_HIP_MAX_CAPSULE_PAIRS][3];               // ... on B,
+  double u[DDP_HIP_MAX_CAPSULE_PAIRS][3];                // u_i,
+  double w[DDP_HIP_MAX_CAPSULE_PAIRS];                   // w_i,
+  double we[DDP_HIP_MAX_CAPSULE_PAIRS];                  // w_i e_i,
+  unsigned long long ma[DDP_HIP_MAX_CAPSULE_PAIRS];      // the tangent columns on path(A) alone (a world pair: all of path(A))
+  unsigned long long mb[DDP_HIP_MAX_CAPSULE_PAIRS];      // ... and on path(B) alone (a world pair: none)
+  int idx[DDP_MAXJ];                                     // the union of them all, ascending
+};
+
+// The two column masks of pair i from the staged paths, by its own lane.  (A workgroup barrier follows.)
+__device__ __forceinline__ unsigned long long capsule_masks_lane(const CapsuleCostDev& cp, bool ff, int i, CapsuleWaveLds& S, bool mine) {
+  const unsigned long long pa = tangent_mask(ff, S.jw.mask[cp.joint[cp.pa[i]]]);
+  const unsigned long long pb = cp.kind[i] == DDP_HIP_CAPSULE_VS_ROBOT ? tangent_mask(ff, S.jw.mask[cp.joint[cp.pb[i]]]) : 0ull;
+  if (mine) { S.ma[i] = pa & ~pb; S.mb[i] = pb & ~pa; }
+  return pa ^ pb;
+}
+
+// z_i[c] of an active pair at a column c of its column set: + P_ca[:, c] . u_i on A's side, - P_cb[:, c] . u_i on B's.  The
+// closest point is frozen in its joint: the column of P is that of a fixed point there, formed on the fly (rbd::point_column)
+__device__ __forceinline__ double capsule_z(const DevModel& m, bool ff, const CapsuleWaveLds& S, int i, int c) {
+  const bool on_a = (S.ma[i] >> c) & 1;
+  double col[3];
+  point_column(m, ff, S.jw, c, on_a ? S.ca[i] : S.cb[i], col);
+  const double z = col[0] * S.u[i][0] + col[1] * S.u[i][1] + col[2] * S.u[i][2];
+  return on_a ? z : -z;
+}
+
+// Phase 2, last step: the wave (lane tid of nt) adds, over the nu tangent columns of S.idx (the union of the active pairs' column
+// sets) alone,
+//   gx[c] += sum_i (w e)_i z_i[c],      gxx[r][c] += sum_i w_i z_i[min] z_i[max]      (Gauss-Newton)
+// the active pairs (bit i of `active`) in ascending order, a pair outside whose column set r or c lies left out, entry (r, c) in
+// (min, max) order: the block stays symmetric bit for bit.  A column on both paths of a robot pair is in neither mask
+__device__ __forceinline__ void capsule_add_wave(const DevModel& m, const CapsuleWaveLds& S, int npair, unsigned active, int nu, int tid, int nt,
+                                                 int n, double* gx, double* gxx) {
+  const bool ff = m.ff != 0;
+  for (int r = tid; r < nu; r += nt) {
+    const int c = S.idx[r];
+    double s = 0.0;
+    for (int i = 0; i < npair; ++i) {
+      if (!((active >> i) & 1) || !(((S.ma[i] | S.mb[i]) >> c) & 1)) continue;
+      s += S.we[i] * capsule_z(m, ff, S, i, c);
+    }
+    gx[c] += s;
+  }
+  for (int e = tid; e < nu * nu; e += nt) {
+    const int r = S.idx[e % nu], c = S.idx[e / nu];
+    const int lo = r < c ? r : c, hi = r < c ? c : r;
+    double h = 0.0;
+    bool hit = false;
+    for (int i = 0; i < npair; ++i) {
+      if (!((active >> i) & 1)) continue;
+      const unsigned long long cs = S.ma[i] | S.mb[i];
+      if (!((cs >> r) & 1) || !((cs >> c) & 1)) continue;
+      h += S.w[i] * capsule_z(m, ff, S, i, lo) * capsule_z(m, ff, S, i, hi);
+      hit = true;
+    }
+    if (hit) gxx[r + (int64_t)c * n] += h;
+  }
+}
+
+}  // namespace rbd
+#endif  // __HIPCC__

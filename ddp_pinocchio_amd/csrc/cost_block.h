@@ -11,8 +11,8 @@
 // The terms.  The order in which the kernels add them (after the stage cost and the tracking cost) is stated where they are launched:
 // lin.hip launches one kernel per live term, fwd.hip forms the first three inline and walks kAddOn for the others, both in the order
 // frame positions, frame orientations, limits, CoM, frame velocities, momentum, balance regions, relative frames, control-gravity,
-// frame aiming, joint accelerations, obstacles, self-collision.  The enumerators are indices of ctx->cost[] and kCostDesc[] and follow that order but for
-// COST_CONTROL_GRAV, COST_FRAME_AIM, COST_BALANCE_REGION and COST_JOINT_ACCEL: the host programs hold momentum, relative frames, obstacles and self-collision as neighbours
+// frame aiming, joint accelerations, obstacles, self-collision, capsules.  The enumerators are indices of ctx->cost[] and kCostDesc[] and follow that order but for
+// COST_CONTROL_GRAV, COST_FRAME_AIM, COST_BALANCE_REGION, COST_JOINT_ACCEL and COST_CAPSULE: the host programs hold momentum, relative frames, obstacles and self-collision as neighbours
 // and self-collision as the last (host/test_relative_frame_block.cpp, host/test_self_collision_block.cpp), so the term whose
 // additions come between the relative frames' and the obstacles' has its index in front of that run; they hold frame velocities and
 // control-gravity as neighbours too (host/test_control_grav_block.cpp), so the term whose additions come after control-gravity's
@@ -20,9 +20,11 @@
 // (host/test_frame_aim_block.cpp), and momentum and the relative frames, so the term whose additions come between the momentum's and
 // the relative frames' has its index in front of the CoM's.  With that every adjacency from the limits to self-collision is held by
 // some host program (host/test_balance_region_block.cpp holds the limits and the balance regions), so the term whose additions come
-// between frame aiming's and the obstacles', the joint accelerations, has its index in front of the limits'.  No order is read off the enumerators: the kernels' order is the
+// between frame aiming's and the obstacles', the joint accelerations, has its index in front of the limits'.  The capsules' additions come last of all, but
+// self-collision is held as the last index and every adjacency from the frame orientations on is held, so their index stands between
+// the frame positions' and the frame orientations' (host/test_capsule_block.cpp).  No order is read off the enumerators: the kernels' order is the
 // order of the launches in lin.hip and of kAddOn in fwd.hip, nothing else
-enum CostTerm : int32_t { COST_FRAME, COST_ORIENT, COST_JOINT_ACCEL, COST_LIMITS, COST_BALANCE_REGION, COST_COM, COST_FRAME_AIM, COST_FRAME_VEL, COST_CONTROL_GRAV, COST_MOMENTUM,
+enum CostTerm : int32_t { COST_FRAME, COST_CAPSULE, COST_ORIENT, COST_JOINT_ACCEL, COST_LIMITS, COST_BALANCE_REGION, COST_COM, COST_FRAME_AIM, COST_FRAME_VEL, COST_CONTROL_GRAV, COST_MOMENTUM,
                           COST_RELATIVE_FRAME, COST_OBSTACLE, COST_SELF_COLLISION, COST_COUNT };
 
 enum CostFill : int32_t { FILL_ZERO, FILL_NEG_INF, FILL_POS_INF, FILL_QUAT };   // FILL_QUAT: identity quaternions (0, 0, 0, 1)
@@ -48,6 +50,7 @@ struct CostDesc {
 static const CostDesc kCostDesc[COST_COUNT] = {
     // flag, sides, doubles per item, fill, room, fixed, cand, stage_only
     {DDP_HIP_FLAG_FRAME_COST, 2, {3, 3, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, false, false},          // target | weight, per frame
+    {DDP_HIP_FLAG_CAPSULE_COST, 2, {8, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, DDP_HIP_MAX_CAPSULE_PAIRS, false, true, false},      // geom | weight, per pair
     {DDP_HIP_FLAG_FRAME_ORIENT_COST, 2, {4, 3, 0}, {FILL_QUAT, FILL_ZERO, 0}, DDP_HIP_MAX_COST_FRAMES, false, false, false},   // quat | weight, per frame
     {DDP_HIP_FLAG_JOINT_ACCEL_COST, 2, {1, 1, 0}, {FILL_ZERO, FILL_ZERO, 0}, COST_ITEMS_VELOCITY, true, true, false},           // target | weight, per tangent row of v; row T carries no term
     {DDP_HIP_FLAG_STATE_LIMITS, 3, {1, 1, 1}, {FILL_NEG_INF, FILL_POS_INF, FILL_ZERO}, 0, true, false, false},                 // lo | hi | weight, per tangent row
@@ -80,7 +83,7 @@ static inline int64_t cost_side_words(const CostBlock& k, int s, int64_t T) { re
 struct CostCheck {
   int64_t items = 0;                // per (instance, t)
   bool ff = false;                  // free-flyer root: the first six tangent rows carry no limit
-  const int32_t* kind = nullptr;    // [items] obstacle slot kinds
+  const int32_t* kind = nullptr;    // [items] obstacle slot kinds, or capsule pair kinds
   int64_t rows = 0;                 // rows of a side per instance (cost_rows): the joint accelerations' weights find row T by it
 };
 typedef bool (*CostSideOk)(const CostCheck& c, const double* v, int64_t words);
@@ -121,6 +124,22 @@ static inline bool cost_obstacle_geom_side(const CostCheck& c, const double* v, 
       if (g[3] < 0.0) return false;
     } else if (fabs(sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) - 1.0) > 1e-10) {
       return false;
+    }
+  }
+  return true;
+}
+// capsule pair geometry by pair kind, eight doubles: all finite (the last is the margin, the ignored ones too); a world capsule
+// (b0, b1, rho, m) has rho >= 0, a half-space (n, h, ., ., ., m) a unit normal by the obstacle half-spaces' rule
+static inline bool cost_capsule_geom_side(const CostCheck& c, const double* v, int64_t words) {
+  for (int64_t i = 0; i < words / 8; ++i) {
+    const double* g = v + 8 * i;
+    for (int a = 0; a < 8; ++a)
+      if (!isfinite(g[a])) return false;
+    const int32_t kind = c.kind[i % c.items];
+    if (kind == DDP_HIP_CAPSULE_VS_CAPSULE) {
+      if (g[6] < 0.0) return false;
+    } else if (kind == DDP_HIP_CAPSULE_VS_HALFSPACE) {
+      if (fabs(sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) - 1.0) > 1e-10) return false;
     }
   }
   return true;
@@ -169,6 +188,21 @@ static inline bool cost_stage_weight_side(const CostCheck& c, const double* v, i
 static inline bool cost_pair_list_ok(int32_t n_points, const int32_t* joint, int32_t n_pairs, const int32_t* a, const int32_t* b) {
   for (int32_t i = 0; i < n_pairs; ++i) {
     if (a[i] < 0 || a[i] >= n_points || b[i] < 0 || b[i] >= n_points) return false;
+    if (a[i] == b[i] || joint[a[i]] == joint[b[i]]) return false;
+  }
+  return true;
+}
+
+// a capsule pair list over n_capsules robot capsules (capsule k on joint[k]): body A in range, a known kind, and for a robot pair
+// body B in range, a != b and not both capsules on one joint (their distance is constant); pair_b of a world pair is not read.
+// Duplicate pairs are allowed
+static inline bool cost_capsule_pairs_ok(int32_t n_capsules, const int32_t* joint, int32_t n_pairs, const int32_t* a, const int32_t* kind,
+                                         const int32_t* b) {
+  for (int32_t i = 0; i < n_pairs; ++i) {
+    if (a[i] < 0 || a[i] >= n_capsules) return false;
+    if (kind[i] == DDP_HIP_CAPSULE_VS_CAPSULE || kind[i] == DDP_HIP_CAPSULE_VS_HALFSPACE) continue;
+    if (kind[i] != DDP_HIP_CAPSULE_VS_ROBOT) return false;
+    if (b[i] < 0 || b[i] >= n_capsules) return false;
     if (a[i] == b[i] || joint[a[i]] == joint[b[i]]) return false;
   }
   return true;

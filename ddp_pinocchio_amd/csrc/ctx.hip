@@ -251,6 +251,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   if ((flags & DDP_HIP_FLAG_FRAME_VEL_COST) && !(flags & DDP_HIP_FLAG_FRAME_COST)) return DDP_HIP_E_ARG;   // the velocity terms alike
   if ((flags & DDP_HIP_FLAG_OBSTACLE_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // collision points are points of a tree's joints
   if ((flags & DDP_HIP_FLAG_SELF_COLLISION_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the spheres alike
+  if ((flags & DDP_HIP_FLAG_CAPSULE_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // ... and the capsules
   if ((flags & DDP_HIP_FLAG_RELATIVE_FRAME_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the frame pairs alike
   if ((flags & DDP_HIP_FLAG_CONTROL_GRAV_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // g(q) is of a tree's bodies
   if ((flags & DDP_HIP_FLAG_FRAME_AIM_COST) && mo.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // aim frames are frames of a tree's joints
@@ -366,7 +367,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
     CTX_TRY(hipStreamSynchronize(ctx->stream));
   }
   for (int term = 0; term < COST_COUNT; ++term) {
-    // frames, aim frames, frame pairs, region planes, obstacle slots and self-collision pairs: no layout until they are set; limits (lo = -inf, hi = +inf, w = 0: no limit anywhere), CoM, momentum
+    // frames, aim frames, frame pairs, region planes, obstacle slots, self-collision pairs and capsule pairs: no layout until they are set; limits (lo = -inf, hi = +inf, w = 0: no limit anywhere), CoM, momentum
     // and control-gravity (one item per control row, T rows): fixed
     CostBlock& k = ctx->cost[term];
     k.desc = &kCostDesc[term];
@@ -378,6 +379,7 @@ extern "C" int ddp_hip_create(const ddp_hip_problem* prob, int device, uint32_t 
   }
   if (flags & DDP_HIP_FLAG_OBSTACLE_COST) CTX_TRY(hipMalloc(&ctx->ob_clear_d, sizeof(double) * (size_t)(d.batch * (d.T + 1))));
   if (flags & DDP_HIP_FLAG_SELF_COLLISION_COST) CTX_TRY(hipMalloc(&ctx->sc_clear_d, sizeof(double) * (size_t)(d.batch * (d.T + 1))));
+  if (flags & DDP_HIP_FLAG_CAPSULE_COST) CTX_TRY(hipMalloc(&ctx->cp_clear_d, sizeof(double) * (size_t)(d.batch * (d.T + 1))));
   if (flags & DDP_HIP_FLAG_RELATIVE_FRAME_COST)
     CTX_TRY(hipMalloc(&ctx->rf_err_d, sizeof(double) * (size_t)(d.batch * (d.T + 1) * DDP_HIP_MAX_FRAME_PAIRS * 6)));
   if (flags & DDP_HIP_FLAG_FRAME_AIM_COST)
@@ -411,6 +413,7 @@ extern "C" int ddp_hip_destroy(ddp_hip_ctx* ctx) {
   }
   if (ctx->ob_clear_d) (void)hipFree(ctx->ob_clear_d);
   if (ctx->sc_clear_d) (void)hipFree(ctx->sc_clear_d);
+  if (ctx->cp_clear_d) (void)hipFree(ctx->cp_clear_d);
   if (ctx->rf_err_d) (void)hipFree(ctx->rf_err_d);
   if (ctx->fa_err_d) (void)hipFree(ctx->fa_err_d);
   if (ctx->ja_acc_d) (void)hipFree(ctx->ja_acc_d);
@@ -547,7 +550,7 @@ static int cost_block_upload(ddp_hip_ctx* ctx, int term, const double* const* ho
   CostBlock& k = ctx->cost[term];
   const Dims& d = ctx->d;
   CostCheck c;
-  c.items = k.items; c.ff = ctx->model_h.ff != 0; c.kind = ctx->ob_kind; c.rows = cost_rows(k, d.T);
+  c.items = k.items; c.ff = ctx->model_h.ff != 0; c.kind = term == COST_CAPSULE ? ctx->cp_kind : ctx->ob_kind; c.rows = cost_rows(k, d.T);
   bool copy, nonzero;
   const int rc = cost_upload_check(ctx->flags, k, c, d.batch, d.T, host, ok, first, count, &copy, &nonzero);
   if (rc != DDP_HIP_OK || !copy) return rc;
@@ -720,6 +723,54 @@ extern "C" int ddp_hip_self_collision_upload(ddp_hip_ctx* ctx, const double* mar
 extern "C" int ddp_hip_self_collision_download(ddp_hip_ctx* ctx, double* margin, double* weight, int64_t first, int64_t count) {
   double* host[] = {margin, weight};
   return cost_block_download(ctx, COST_SELF_COLLISION, host, first, count);
+}
+
+// robot capsules and pairs shared by the batch; eight doubles of geometry and a weight per (instance, t, pair)
+extern "C" int ddp_hip_capsule_set_pairs(ddp_hip_ctx* ctx, int32_t n_capsules, const int32_t* joint, const double* end0, const double* end1,
+                                         const double* radius, int32_t n_pairs, const int32_t* pair_a, const int32_t* pair_kind,
+                                         const int32_t* pair_b) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_CAPSULE_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (n_capsules < 1 || n_capsules > DDP_HIP_MAX_CAPSULES || n_pairs < 1 || n_pairs > DDP_HIP_MAX_CAPSULE_PAIRS) return DDP_HIP_E_ARG;
+  if (!joint || !end0 || !end1 || !radius || !pair_a || !pair_kind || !pair_b) return DDP_HIP_E_ARG;
+  for (int k = 0; k < n_capsules; ++k) {
+    if (joint[k] < 0 || joint[k] >= ctx->model_h.nj) return DDP_HIP_E_ARG;
+    for (int a = 0; a < 3; ++a)
+      if (!isfinite(end0[3 * k + a]) || !isfinite(end1[3 * k + a])) return DDP_HIP_E_ARG;
+    if (!isfinite(radius[k]) || radius[k] < 0.0) return DDP_HIP_E_ARG;
+  }
+  if (!cost_capsule_pairs_ok(n_capsules, joint, n_pairs, pair_a, pair_kind, pair_b)) return DDP_HIP_E_ARG;
+  bool same = n_capsules == ctx->cp_nc && n_pairs == ctx->cp_npair;
+  for (int i = 0; same && i < n_pairs; ++i) same = pair_kind[i] == ctx->cp_kind[i];
+  if (!same) {
+    // other counts are another layout, other kinds another meaning of the eight doubles: geometry and weights start again at 0
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int rc_ = cost_block_setup(ctx, COST_CAPSULE, n_pairs);
+    if (rc_ != DDP_HIP_OK) return rc_;
+  }
+  ctx->cp_nc = n_capsules;
+  ctx->cp_npair = n_pairs;
+  for (int k = 0; k < n_capsules; ++k) {
+    ctx->cp_joint[k] = joint[k];
+    ctx->cp_radius[k] = radius[k];
+    for (int a = 0; a < 3; ++a) { ctx->cp_end[k][0][a] = end0[3 * k + a]; ctx->cp_end[k][1][a] = end1[3 * k + a]; }
+  }
+  for (int i = 0; i < n_pairs; ++i) {
+    ctx->cp_pa[i] = pair_a[i];
+    ctx->cp_kind[i] = pair_kind[i];
+    ctx->cp_pb[i] = pair_kind[i] == DDP_HIP_CAPSULE_VS_ROBOT ? pair_b[i] : 0;
+  }
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_capsule_upload(ddp_hip_ctx* ctx, const double* geom, const double* weight, int64_t first, int64_t count) {
+  const double* host[] = {geom, weight};
+  const CostSideOk ok[] = {cost_capsule_geom_side, cost_weight_side};
+  return cost_block_upload(ctx, COST_CAPSULE, host, ok, first, count);
+}
+extern "C" int ddp_hip_capsule_download(ddp_hip_ctx* ctx, double* geom, double* weight, int64_t first, int64_t count) {
+  double* host[] = {geom, weight};
+  return cost_block_download(ctx, COST_CAPSULE, host, first, count);
 }
 
 // frame pairs shared by the batch; a target, a reference quaternion and six weights per (instance, t, pair)

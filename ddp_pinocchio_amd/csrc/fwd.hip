@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "balance_region_cost.h"
+#include "capsule_cost.h"
 #include "com_cost.h"
 #include "control_grav_cost.h"
 #include "frame_aim_cost.h"
@@ -838,7 +839,7 @@ __global__ void cand_sum_kernel(FwdParams p) {
   p.fw_dcost[(int64_t)b * na + a] = dsum;
 }
 
-// The add-on cost kernels below (CoM, frame velocities, momentum, balance regions, relative frames, control-gravity, frame aiming, joint accelerations, obstacles) run over a list of `count` (trajectory, t) pairs, t = 0 .. T,
+// The add-on cost kernels below (CoM, frame velocities, momentum, balance regions, relative frames, control-gravity, frame aiming, joint accelerations, obstacles, self-collision, capsules) run over a list of `count` (trajectory, t) pairs, t = 0 .. T,
 // `na` trajectories per instance.  Pair e: which trajectory, which t, whose instance, which block bt1 = b (T+1) + t of the term's
 // data.  skip: nothing is written for this pair (past the list, or a candidate the rollout kernels skip: state != 0, beyond
 // 2^-33; state == nullptr: a resident trajectory, none is skipped).  live: the pair is evaluated (the kernels narrow it further)
@@ -1346,6 +1347,75 @@ __global__ __launch_bounds__(64) void self_collision_clearance_kernel(SelfCollis
   self_collision_fold<true>(sc, *model, s_p, s_min, s_live, xs, nx, count, 1, nx, 1, nullptr, 0, out, 0);
 }
 
+// The capsule kernels below take the two steps of the self-collision kernels above: DDP_HIP_MAX_CAPSULES lanes per pair of the
+// list (a state), 4 states per wave.  Step 1: lane k < n_capsules of the group walks both ends of capsule k in one walk
+// (rbd::capsule_ends) and leaves them in LDS (s_e: 64 x 2 x 3, the kernel's own).  After a barrier, step 2: the lanes take the
+// capsule pairs, lane k pair k and pair k + 16, form the closest points and d (rbd::capsule_distance: a world body is read from
+// the pair's geometry) and leave w d^2 of an active pair -- with MIN: d of a pair with w != 0 -- and a flag in LDS (s_term,
+// s_formed: 4 x DDP_HIP_MAX_CAPSULE_PAIRS each).  After a second barrier the group's first lane folds in ascending pair order: 1/2
+// the sum of the formed ones, or with MIN the rbd::obstacle_min of them all from +inf, and cost_pair_store writes the result.  A
+// state whose weights are all 0 is not walked
+template <bool MIN>
+__device__ __forceinline__ void capsule_fold(const CapsuleCostDev& cp, const DevModel& m, double (*s_e)[2][3], double* s_term, int32_t* s_formed,
+                                             const double* xs, int64_t traj_stride, int64_t count, int32_t T1, int32_t nx, int32_t na,
+                                             const int32_t* state, int32_t round, double* out, int32_t add) {
+  constexpr int L = DDP_HIP_MAX_CAPSULES, NP = DDP_HIP_MAX_CAPSULE_PAIRS;
+  const int tid = threadIdx.x, g = tid / L, k = tid % L;
+  const int64_t e = (int64_t)blockIdx.x * (64 / L) + g;
+  const CostPair pr = cost_pair_decode(e, count, T1, na, state, round);
+  const double* w = cp.weight + pr.bt1 * cp.npair;
+  const bool live = pr.live && rbd::weights_any(w, cp.npair);
+  if (live && k < cp.nc) rbd::capsule_ends(m, m.ff != 0, cp, k, xs + pr.traj * traj_stride + (int64_t)pr.t * nx, s_e[tid]);
+  __syncthreads();
+  for (int i = k; i < NP; i += L) {
+    double term = MIN ? INFINITY : 0.0;
+    bool formed = false;
+    if (live && i < cp.npair && w[i] != 0.0) {
+      const double (*ea)[3] = s_e[g * L + cp.pa[i]];
+      const double (*eb)[3] = s_e[g * L + cp.pb[i]];
+      double d, ca[3], cb[3], u[3];
+      (void)rbd::capsule_distance(cp, i, ea[0], ea[1], eb[0], eb[1], cp.geom + (pr.bt1 * cp.npair + i) * 8, &d, ca, cb, u);
+      if (MIN) { term = d; formed = true; }
+      else if (rbd::obstacle_active(d)) { term = w[i] * d * d; formed = true; }
+    }
+    s_term[g * NP + i] = term;
+    s_formed[g * NP + i] = formed ? 1 : 0;
+  }
+  __syncthreads();
+  if (k != 0 || pr.skip) return;
+  double acc = MIN ? INFINITY : 0.0;
+  bool any = false;
+  for (int i = 0; i < cp.npair; ++i) {
+    if (!s_formed[g * NP + i]) continue;
+    acc = MIN ? rbd::obstacle_min(acc, s_term[g * NP + i]) : acc + s_term[g * NP + i];
+    any = true;
+  }
+  cost_pair_store(out, e, MIN ? acc : 0.5 * acc, any, add);
+}
+
+// The capsule terms (DDP_HIP_FLAG_CAPSULE_COST, ddp_hip.h) of a list of states, added on top like the self-collision terms above:
+// the same list, the same two uses (add != 0: out[pair] += term behind cost_kernel; add == 0: out[pair] = term, the candidates'
+// array in a line-search round, with the candidates the rollout kernels skip skipped here).  A pair of bodies with w == 0 or
+// e == 0 is left out, and a state without an active pair adds nothing (add != 0) or stores +0 (add == 0).  A non-finite state
+// gives a NaN term, as com_cost_kernel's does
+__global__ __launch_bounds__(64) void capsule_cost_kernel(CapsuleCostDev cp, const DevModel* model, const double* xs, int64_t traj_stride,
+                                                          int64_t count, int32_t T1, int32_t nx, int32_t na, const int32_t* state,
+                                                          int32_t round, double* out, int32_t add) {
+  __shared__ double s_e[64][2][3], s_term[4 * DDP_HIP_MAX_CAPSULE_PAIRS];
+  __shared__ int32_t s_act[4 * DDP_HIP_MAX_CAPSULE_PAIRS];
+  capsule_fold<false>(cp, *model, s_e, s_term, s_act, xs, traj_stride, count, T1, nx, na, state, round, out, add);
+}
+
+// ddp_hip_capsule_clearance: the same layout over the `count` (instance, t) pairs of one resident trajectory (a list of one-state
+// trajectories, no candidates to skip), min instead of sum: out[pair] = min over the capsule pairs with w != 0 of d_i, +inf where
+// none is live, NaN where a distance is NaN
+__global__ __launch_bounds__(64) void capsule_clearance_kernel(CapsuleCostDev cp, const DevModel* model, const double* xs, int64_t count,
+                                                               int32_t nx, double* out) {
+  __shared__ double s_e[64][2][3], s_min[4 * DDP_HIP_MAX_CAPSULE_PAIRS];
+  __shared__ int32_t s_live[4 * DDP_HIP_MAX_CAPSULE_PAIRS];
+  capsule_fold<true>(cp, *model, s_e, s_min, s_live, xs, nx, count, 1, nx, 1, nullptr, 0, out, 0);
+}
+
 // accept rule (ddp_fwd.ipp:56-60): the first (= largest) candidate with sum(new - old) <= 0; the winner's
 // trajectory becomes (X_NEW, U_NEW).  grid = batch.
 __global__ void select_kernel(FwdParams p) {
@@ -1619,10 +1689,13 @@ static void launch_obstacle_cost(ddp_hip_ctx* ctx, const double* xs, const doubl
 static void launch_self_collision_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   launch_add_on(self_collision_cost_kernel, self_collision_dev(ctx), DDP_HIP_MAX_COLLISION_POINTS, ctx, xs, na, count, state, round, out, add);
 }
+static void launch_capsule_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
+  launch_add_on(capsule_cost_kernel, capsule_cost_dev(ctx), DDP_HIP_MAX_CAPSULES, ctx, xs, na, count, state, round, out, add);
+}
 
 // The terms formed out of line, in the fixed order of their additions (after everything cost_kernel / the rollout kernels form
 // inline): CoM, frame velocities, momentum, balance regions, relative frames, control-gravity, frame aiming, joint
-// accelerations, obstacles, self-collision.  launch_cost and ddp_hip_forward both walk this table and nothing else
+// accelerations, obstacles, self-collision, capsules.  launch_cost and ddp_hip_forward both walk this table and nothing else
 struct AddOnTerm {
   int term;
   AddOnLaunch launch;
@@ -1636,7 +1709,8 @@ static const AddOnTerm kAddOn[] = {{COST_COM, launch_com_cost},
                                    {COST_FRAME_AIM, launch_frame_aim_cost},
                                    {COST_JOINT_ACCEL, launch_joint_accel_cost},
                                    {COST_OBSTACLE, launch_obstacle_cost},
-                                   {COST_SELF_COLLISION, launch_self_collision_cost}};
+                                   {COST_SELF_COLLISION, launch_self_collision_cost},
+                                   {COST_CAPSULE, launch_capsule_cost}};
 
 static int launch_cost(ddp_hip_ctx* ctx, FwdParams& p, int which) {
   const int bs = 64;
@@ -1694,6 +1768,23 @@ extern "C" int ddp_hip_self_collision_clearance(ddp_hip_ctx* ctx, int which, dou
                      which == 0 ? p.x_old : p.x_new, total, (int32_t)ctx->d.nx, ctx->sc_clear_d);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, ctx->sc_clear_d, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_capsule_clearance(ddp_hip_ctx* ctx, int which, double* out) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_CAPSULE_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (!out || (which != 0 && which != 1) || ctx->cp_npair == 0) return DDP_HIP_E_ARG;   // (no pairs set: nothing to measure)
+  HIP_TRY(hipSetDevice(ctx->device));
+  const FwdParams p = make_params(ctx);
+  const CapsuleCostDev cp = capsule_cost_dev(ctx, true);
+  const int64_t total = ctx->d.batch * (ctx->d.T + 1);
+  const int64_t per = 64 / DDP_HIP_MAX_CAPSULES;
+  hipLaunchKernelGGL(capsule_clearance_kernel, dim3((unsigned)((total + per - 1) / per)), dim3(64), 0, ctx->stream, cp, ctx->model_d,
+                     which == 0 ? p.x_old : p.x_new, total, (int32_t)ctx->d.nx, ctx->cp_clear_d);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, ctx->cp_clear_d, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return DDP_HIP_OK;
 }

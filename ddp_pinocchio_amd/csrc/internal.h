@@ -285,6 +285,13 @@ struct ddp_hip_ctx {
   double sc_radius[DDP_HIP_MAX_COLLISION_POINTS] = {};
   int32_t sc_pa[DDP_HIP_MAX_COLLISION_PAIRS] = {}, sc_pb[DDP_HIP_MAX_COLLISION_PAIRS] = {};
   double* sc_clear_d = nullptr;               // [batch][T+1] what ddp_hip_self_collision_clearance hands back
+  // the robot capsules and the pairs they take part in (ddp_hip_capsule_set_pairs)
+  int32_t cp_nc = 0, cp_npair = 0;            // capsules and pairs set (0: none yet)
+  int32_t cp_joint[DDP_HIP_MAX_CAPSULES] = {};
+  double cp_end[DDP_HIP_MAX_CAPSULES][2][3] = {};
+  double cp_radius[DDP_HIP_MAX_CAPSULES] = {};
+  int32_t cp_pa[DDP_HIP_MAX_CAPSULE_PAIRS] = {}, cp_kind[DDP_HIP_MAX_CAPSULE_PAIRS] = {}, cp_pb[DDP_HIP_MAX_CAPSULE_PAIRS] = {};
+  double* cp_clear_d = nullptr;               // [batch][T+1] what ddp_hip_capsule_clearance hands back
   // the relative-frame pairs (ddp_hip_relative_frame_set_pairs): base frame A = (rf_ja, rf_offa), tip frame B = (rf_jb, rf_offb)
   int32_t rf_np = 0;                          // pairs set (0: none yet)
   int32_t rf_ja[DDP_HIP_MAX_FRAME_PAIRS] = {}, rf_jb[DDP_HIP_MAX_FRAME_PAIRS] = {};

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include "balance_region_cost.h"
+#include "capsule_cost.h"
 #include "com_cost.h"
 #include "control_grav_cost.h"
 #include "frame_aim_cost.h"
@@ -835,6 +836,67 @@ __global__ __launch_bounds__(64) void lin_self_collision_cost_kernel(LinParams p
   __syncthreads();
   double *gx = blk.gx, *gxx = blk.gxx;
   rbd::self_collision_add_wave(m, S, sc, active, __builtin_popcountll(U), tid, (int)blockDim.x, n, gx, gxx);
+}
+
+// Capsule cost (DDP_HIP_FLAG_CAPSULE_COST, ddp_hip.h): one wave per (instance, t), t = 0 .. T, after every other cost kernel on the
+// same stream (the fixed order of additions: ..., obstacles, self-collision, capsules).  One-sided like its two siblings: most waves
+// have nothing to add.  A block whose weights are all 0 returns at once.  Phase 1: lane k < n_capsules walks both ends of capsule
+// k in one walk (rbd::capsule_ends); lane i < n_pairs fetches the ends of its pair's robot capsules from the lanes that hold them
+// (cross-lane reads: no LDS), reads a world body from the pair's geometry, and forms the closest points and d_i
+// (rbd::capsule_distance).  One wave-level vote decides: a wave without an active pair (w != 0, e != 0, a direction u) returns
+// here, before any LDS access or barrier.  Phase 2: lanes j < nj stage world axis, world origin and path of their joint in LDS
+// (rbd::stage_joint_lane), the active pairs' lanes c_a, c_b, u_i, w_i, w_i e_i; after the barrier the same lanes leave their
+// pair's two column masks: path(A) \ path(B) and path(B) \ path(A) of a robot pair, all of path(A) and nothing of a world pair.
+// The wave adds over the union of the masks alone
+//   lx[c] += sum_i (w e)_i z_i[c],     lxx[r][c] += sum_i w_i z_i[min] z_i[max]     (Gauss-Newton)
+// (rbd::capsule_add_wave: pairs in ascending order, z formed on the fly at the closest points frozen in their joints, symmetric bit
+// for bit).  It reads p.x and touches nothing but those entries.  No atomics.  t = T: lfx / lfxx
+static_assert(sizeof(LinParams) + sizeof(CapsuleCostDev) <= 4096, "the kernel's arguments must fit the kernarg segment");
+__global__ __launch_bounds__(64) void lin_capsule_cost_kernel(LinParams p, CapsuleCostDev cp) {
+  const int64_t bt1 = blockIdx.x;
+  const int n = (int)p.d.n;
+  const int tid = threadIdx.x;
+  const double* w = cp.weight + bt1 * cp.npair;
+  if (!rbd::weights_any(w, cp.npair)) return;
+  const DevModel& m = *p.model;
+  const bool ff = m.ff != 0;
+  const LinCostBlock blk = lin_cost_block(p, bt1);
+  const double* q = blk.q;
+  double e[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+  if (tid < cp.nc) rbd::capsule_ends(m, ff, cp, tid, q, e);
+  const bool pair_lane = tid < cp.npair;
+  const int ia = pair_lane ? cp.pa[tid] : 0, ib = pair_lane ? cp.pb[tid] : 0;
+  const double a0[3] = {__shfl(e[0][0], ia), __shfl(e[0][1], ia), __shfl(e[0][2], ia)};
+  const double a1[3] = {__shfl(e[1][0], ia), __shfl(e[1][1], ia), __shfl(e[1][2], ia)};
+  const double b0[3] = {__shfl(e[0][0], ib), __shfl(e[0][1], ib), __shfl(e[0][2], ib)};
+  const double b1[3] = {__shfl(e[1][0], ib), __shfl(e[1][1], ib), __shfl(e[1][2], ib)};
+  double d = 0.0, ca[3] = {0.0, 0.0, 0.0}, cb[3] = {0.0, 0.0, 0.0}, u[3] = {0.0, 0.0, 0.0}, wi = 0.0;
+  bool act = false;
+  if (pair_lane) {
+    wi = w[tid];
+    if (wi != 0.0) {
+      const bool has_u = rbd::capsule_distance(cp, tid, a0, a1, b0, b1, cp.geom + (bt1 * cp.npair + tid) * 8, &d, ca, cb, u);
+      act = rbd::obstacle_active(d) && has_u;
+    }
+  }
+  const unsigned active = (unsigned)__ballot(act);                  // bit i: pair i is active
+  if (active == 0) return;
+  __shared__ rbd::CapsuleWaveLds S;
+  if (tid < m.nj) rbd::stage_joint_lane<0>(m, q, tid, S.jw, nullptr);
+  if (act) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { S.ca[tid][a] = ca[a]; S.cb[tid][a] = cb[a]; S.u[tid][a] = u[a]; }
+    S.w[tid] = wi;
+    S.we[tid] = wi * d;
+  }
+  __syncthreads();
+  unsigned long long U = 0;
+  for (int i = 0; i < cp.npair; ++i)
+    if ((active >> i) & 1) U |= rbd::capsule_masks_lane(cp, ff, i, S, i == tid);
+  rbd::column_index_lane(U, tid, S.idx);
+  __syncthreads();
+  double *gx = blk.gx, *gxx = blk.gxx;
+  rbd::capsule_add_wave(m, S, cp.npair, active, __builtin_popcountll(U), tid, (int)blockDim.x, n, gx, gxx);
 }
 
 template <int NJ>
@@ -1675,7 +1737,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     else hipLaunchKernelGGL(lin_cost_kernel, dim3((unsigned)BT), dim3(64), 0, ctx->stream, p);
     // the add-on terms, one kernel per live term, each adding onto what the ones before it left.  The fixed order of additions:
     // cost, tracking, frame positions, frame orientations, limits, CoM, frame velocities, momentum, balance regions, relative
-    // frames, control-gravity, frame aiming, joint accelerations, obstacles, self-collision
+    // frames, control-gravity, frame aiming, joint accelerations, obstacles, self-collision, capsules
     const dim3 blocks((unsigned)(BT + d.batch));
     const FrameCostDev fc = frame_cost_dev(ctx);
     const StateLimitsDev sl = state_limits_dev(ctx);
@@ -1689,6 +1751,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     const JointAccelDev ja = joint_accel_dev(ctx);
     const ObstacleCostDev ob = obstacle_cost_dev(ctx);
     const SelfCollisionDev sc = self_collision_dev(ctx);
+    const CapsuleCostDev cp = capsule_cost_dev(ctx);
     auto add = [&](bool live, auto kernel, const auto& dev) { if (live) hipLaunchKernelGGL(kernel, blocks, dim3(64), 0, ctx->stream, p, dev); };
     add(fc.target, lin_frame_cost_kernel, fc);
     add(fc.oquat, lin_frame_orient_cost_kernel, fc);
@@ -1709,6 +1772,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     }
     add(ob.geom, lin_obstacle_cost_kernel, ob);
     add(sc.margin, lin_self_collision_cost_kernel, sc);
+    add(cp.geom, lin_capsule_cost_kernel, cp);
   }
   // the q- / v-caches of the mode-2 stencil also serve the first order (base configuration and base (q, v)), so they are built
   // ahead of whichever stage comes first

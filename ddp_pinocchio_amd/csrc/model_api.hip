@@ -8,6 +8,7 @@
 #include <new>
 
 #include "balance_region_cost.h"
+#include "capsule_cost.h"
 #include "com_cost.h"
 #include "control_grav_cost.h"
 #include "frame_aim_cost.h"
@@ -225,6 +226,33 @@ __global__ __launch_bounds__(64) void model_capture_point_kernel(const DevModel*
   }
 }
 
+// The distance of the segments a0 .. a1 of joint ja and b0 .. b1 of joint jb and its gradient by one wave, with the traversal of
+// lin_capsule_cost_kernel (capsule_cost.h): in = q | a0[3] | a1[3] | b0[3] | b1[3] (joint coordinates), out = D | ca3 | cb3 | J[nv]
+// (columns on both paths or on neither 0; all 0 where D == 0)
+__global__ __launch_bounds__(64) void model_capsule_pair_kernel(const DevModel* m, const double* in, double* out, int ja, int jb) {
+  __shared__ rbd::CapsuleWaveLds S;
+  __shared__ double s_D;
+  const int tid = threadIdx.x, nv = m->nv;
+  const bool ff = m->ff != 0;
+  if (tid < m->nj) rbd::stage_joint_lane<0>(*m, in, tid, S.jw, nullptr);
+  if (tid == 63) {
+    const double* e = in + m->nq;
+    double a[2][3] = {{e[0], e[1], e[2]}, {e[3], e[4], e[5]}}, b[2][3] = {{e[6], e[7], e[8]}, {e[9], e[10], e[11]}};
+    (void)rbd::walk_to_root<2, 0>(*m, ff, ja, in, a, nullptr, -1);
+    (void)rbd::walk_to_root<2, 0>(*m, ff, jb, in, b, nullptr, -1);
+    const double D = capsule_closest_points(a[0], a[1], b[0], b[1], S.ca[0], S.cb[0]);
+    for (int k = 0; k < 3; ++k) S.u[0][k] = D == 0.0 ? 0.0 : (S.ca[0][k] - S.cb[0][k]) / D;
+    s_D = D;
+    out[0] = D;
+    for (int k = 0; k < 3; ++k) { out[1 + k] = S.ca[0][k]; out[4 + k] = S.cb[0][k]; }
+  }
+  __syncthreads();
+  const unsigned long long ma = rbd::tangent_mask(ff, S.jw.mask[ja]), mb = rbd::tangent_mask(ff, S.jw.mask[jb]);
+  if (tid == 0) { S.ma[0] = ma & ~mb; S.mb[0] = mb & ~ma; }
+  __syncthreads();
+  for (int c = tid; c < nv; c += blockDim.x) out[7 + c] = (((ma ^ mb) >> c) & 1) && s_D != 0.0 ? rbd::capsule_z(*m, ff, S, 0, c) : 0.0;
+}
+
 #define MODEL_DISPATCH(nv, CALL)       \
   do {                                 \
     if ((nv) <= 6) { CALL(6); }        \
@@ -266,6 +294,9 @@ int run(ddp_hip_model_handle* h, const double* in, size_t n_in, double* out, siz
                        want_jac / DDP_MAXJ);   // (want_jac: the two joints)
   } else if (what == 9) {
     hipLaunchKernelGGL(model_capture_point_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o);
+  } else if (what == 10) {
+    hipLaunchKernelGGL(model_capsule_pair_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac % DDP_MAXJ,
+                       want_jac / DDP_MAXJ);   // (want_jac: the two joints)
   } else if (what == 8) {
     hipLaunchKernelGGL(model_frame_axis_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac);   // (want_jac: the joint)
   } else {
@@ -470,5 +501,26 @@ extern "C" int ddp_hip_model_capture_point(ddp_hip_model_handle* h, const double
   memcpy(xi3, out, sizeof(double) * 3);
   if (Jq) memcpy(Jq, out + 3, sizeof(double) * 3 * nv);
   if (Jv) memcpy(Jv, out + 3 + 3 * nv, sizeof(double) * 3 * nv);
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_model_capsule_pair(ddp_hip_model_handle* h, int32_t ja, const double a0[3], const double a1[3], int32_t jb, const double b0[3],
+                                          const double b1[3], const double* q, double* D, double* ca3, double* cb3, double* J) {
+  if (!h || !a0 || !a1 || !b0 || !b1 || !q || !D || !ca3 || !cb3 || h->model_h.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_ARG;
+  const int nv = h->model_h.nv, nq = h->model_h.nq, nj = h->model_h.nj;
+  if (ja < 0 || ja >= nj || jb < 0 || jb >= nj || ja == jb) return DDP_HIP_E_ARG;
+  double in[DDP_MAXJ + 1 + 12];
+  memcpy(in, q, sizeof(double) * nq);
+  memcpy(in + nq, a0, sizeof(double) * 3); memcpy(in + nq + 3, a1, sizeof(double) * 3);
+  memcpy(in + nq + 6, b0, sizeof(double) * 3); memcpy(in + nq + 9, b1, sizeof(double) * 3);
+  for (int k = 0; k < 12; ++k)
+    if (!isfinite(in[nq + k])) return DDP_HIP_E_ARG;
+  double out[7 + DDP_MAXJ];
+  const int rc = run(h, in, (size_t)(nq + 12), out, (size_t)(7 + (J ? nv : 0)), 10, ja + DDP_MAXJ * jb);
+  if (rc != DDP_HIP_OK) return rc;
+  *D = out[0];
+  memcpy(ca3, out + 1, sizeof(double) * 3);
+  memcpy(cb3, out + 4, sizeof(double) * 3);
+  if (J) memcpy(J, out + 7, sizeof(double) * nv);
   return DDP_HIP_OK;
 }

@@ -55,7 +55,7 @@ int main() {
   // ---- limits', every adjacency behind it as the sibling programs hold them (the order of additions is the launch lists') ---------
   {
     const CostDesc& d = kCostDesc[COST_JOINT_ACCEL];
-    CHECK(COST_FRAME == 0 && COST_ORIENT == 1);
+    CHECK(COST_FRAME == 0 && COST_ORIENT == 2);                          // (the capsules' index stands between the two: test_capsule_block.cpp)
     CHECK(COST_JOINT_ACCEL == COST_ORIENT + 1 && COST_JOINT_ACCEL == COST_LIMITS - 1);
     CHECK(COST_BALANCE_REGION == COST_LIMITS + 1 && COST_COM == COST_BALANCE_REGION + 1);
     CHECK(COST_FRAME_AIM == COST_COM + 1 && COST_FRAME_VEL == COST_FRAME_AIM + 1);

@@ -521,6 +521,57 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * obstacles'). */
 #define DDP_HIP_FLAG_JOINT_ACCEL_COST 65536u
 #define DDP_HIP_MAX_JOINT_ACCEL_NV 38
+/* Say "keep the limbs off the table edge, off the pole, off each other and off the floor" with the shape a limb has: a capsule, a
+ * segment fixed in a joint swept by a radius.  Spheres (DDP_HIP_FLAG_OBSTACLE_COST, DDP_HIP_FLAG_SELF_COLLISION_COST) either leave
+ * holes along a forearm or are so fat that the hands cannot come near each other.  The flag stands alone: it needs neither of the
+ * two and has its own bodies.  Robot capsules, shared by the batch, up to DDP_HIP_MAX_CAPSULES: capsule k is the segment from
+ * end0_k to end1_k, both points fixed in joint joint_k (the convention of the cost frames), with a radius r_k >= 0; end0 == end1
+ * is a sphere.  Pairs, shared by the batch, up to DDP_HIP_MAX_CAPSULE_PAIRS: body A of pair i is robot capsule pair_a[i], body B
+ * is what pair_kind[i] says.  Per instance b, t = 0 .. T and pair i eight doubles geom[b][t][i] and a weight w[b][t][i] >= 0; the
+ * last geom entry is always the margin m (finite, may be negative):
+ *   DDP_HIP_CAPSULE_VS_ROBOT      B is robot capsule pair_b[i] (another joint's);  geom = (., ., ., ., ., ., ., m), the first seven
+ *                                 ignored but finite
+ *   DDP_HIP_CAPSULE_VS_CAPSULE    B is a world capsule of the pair's own: geom = (b0(3), b1(3), rho >= 0, m), a world segment
+ *                                 with a radius that moves with t and differs per instance
+ *   DDP_HIP_CAPSULE_VS_HALFSPACE  B is a half-space: geom = (n(3), h, ., ., ., m), n unit by the obstacle half-spaces' rule
+ *                                 (| |n| - 1 | <= 1e-10), the free side n . p >= h
+ * With c_a, c_b the closest points of the two segments (below):
+ *   D_i = |c_a - c_b|,   d_i = D_i - (r_a + r_b + m)   (a world capsule: r_b = rho),   u_i = (c_a - c_b) / D_i
+ *   half-space:  d_i = min_end (n . p_end) - h - r_a - m,   c_a the end with the smaller n . p (end0 wins a tie),   u_i = n
+ *   e_i = d_i < 0 ? d_i : 0          (a NaN distance is active and its term NaN)
+ *   l(t, x, u) += 1/2 sum_i w[b][t][i] e_i^2      t < T
+ *   lf(x_T)    += 1/2 sum_i w[b][T][i] e_i^2
+ * to whatever the context optimises otherwise.  The closest points of the segments a0 + s d1 and b0 + t d2 are pinned: with
+ * d1 = a1 - a0, d2 = b1 - b0, r = a0 - b0, A = d1 . d1, E = d2 . d2, F = d2 . r, C = d1 . r, Bv = d1 . d2, den = A E - Bv^2 and
+ * clamp to [0, 1]:
+ *   A == 0 and E == 0:  s = t = 0;       A == 0:  s = 0, t = clamp(F / E);       E == 0:  t = 0, s = clamp(-C / A);
+ *   otherwise  s = den > 0 ? clamp((Bv F - C E) / den) : 0,  t = (Bv s + F) / E;  t < 0: t = 0, s = clamp(-C / A);
+ *              t > 1: t = 1, s = clamp((Bv - C) / A);
+ *   c_a = a0 + s d1,   c_b = b0 + t d2
+ * (capsule_closest_params in csrc/capsule_cost.h, a routine that compiles for the host as well).  Derivatives in the tangent at x,
+ * over the pairs with w != 0, e != 0 and (the two segment kinds) D_i != 0 only.  The closest points are frozen in their joints
+ * with s and t held -- by the envelope theorem the parameters do not move d to first order -- so the pair is a sphere pair at
+ * c_a and c_b, and with P_c the true point jacobian of DDP_HIP_FLAG_FRAME_COST at the point c:
+ *   z_i[c] = + P_{c_a}[:, c] . u_i     c a tangent column of path(A) that is not on path(B)
+ *   z_i[c] = - P_{c_b}[:, c] . u_i     c a tangent column of path(B) that is not on path(A)       (robot pairs alone)
+ *            nothing                    c on both paths or on neither
+ *   lx[q rows] += sum_i w e_i z_i,   lxx[q rows, q rows] += sum_i w z_i z_i^T,   lfx / lfxx alike at T.
+ * A column on both paths of a robot pair -- a free-flyer root's six always -- is left out, not added as rounding residue, as for
+ * DDP_HIP_FLAG_SELF_COLLISION_COST.  A world body has no path: all of path(A), a free-flyer root's six columns included, carries
+ * + P . u.  Velocity rows and columns, lu, luu, lux and every q row outside the active pairs' column sets are untouched.  lxx is
+ * Gauss-Newton (positive semidefinite); entry (r, c) is formed in (min, max) order with the pairs in ascending order: symmetric
+ * bit for bit, no atomics.  A pair with D_i == 0 contributes its value and no derivative.  A pair with w == 0 or e == 0 is left
+ * out (not multiplied by 0, not added as +0): with nothing uploaded, with every weight 0, and with non-zero weights on pairs that
+ * neither the trajectory nor any line-search candidate brings within their margin, a context computes bit for bit what it
+ * computes without the flag.  The data travels through ddp_hip_capsule_* below; at create no pairs are set and geometry and
+ * weights are 0.  Tree models only (the pendulum: DDP_HIP_E_UNSUPPORTED).  The flag combines with every other flag: the terms are
+ * formed by kernels of their own, which add onto what the other terms' kernels leave (last, after self-collision's). */
+#define DDP_HIP_FLAG_CAPSULE_COST 131072u
+#define DDP_HIP_MAX_CAPSULES 16
+#define DDP_HIP_MAX_CAPSULE_PAIRS 32
+#define DDP_HIP_CAPSULE_VS_ROBOT 0      /* the other body is a robot capsule */
+#define DDP_HIP_CAPSULE_VS_CAPSULE 1    /* ... a world capsule of the pair's own, per instance and t */
+#define DDP_HIP_CAPSULE_VS_HALFSPACE 2  /* ... a half-space, per instance and t */
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -689,6 +740,27 @@ int ddp_hip_joint_accel_cost_download(ddp_hip_ctx* ctx, double* target, double* 
 /* "How hard did it accelerate": out[batch][T][nv] = aba(x_t, u_t) along X / U (which = 0) or X_NEW / U_NEW (which = 1), formed by
  * the cost kernel's forward dynamics in one launch, live weights or not. */
 int ddp_hip_joint_accel(ddp_hip_ctx* ctx, int which, double* out);
+/* The robot capsules and the pairs of a context created with DDP_HIP_FLAG_CAPSULE_COST (else DDP_HIP_E_UNSUPPORTED), shared by the
+ * batch: joint[n_capsules], end0[n_capsules][3], end1[n_capsules][3], radius[n_capsules], pair_a[n_pairs], pair_kind[n_pairs],
+ * pair_b[n_pairs] (read for DDP_HIP_CAPSULE_VS_ROBOT pairs alone).  DDP_HIP_E_ARG for n_capsules outside
+ * 1 .. DDP_HIP_MAX_CAPSULES, n_pairs outside 1 .. DDP_HIP_MAX_CAPSULE_PAIRS, a joint outside the model, a non-finite end, a
+ * negative or non-finite radius, a capsule index outside the capsules, an unknown kind, and a robot pair with a == b or with both
+ * capsules on the same joint (their distance is constant).  Duplicate pairs are allowed.  It may be called again: with the same
+ * two counts and the same kinds the per-instance data stays (capsules may move, radii may change, a pair may name other capsules),
+ * otherwise geometry and weights are reset to 0. */
+int ddp_hip_capsule_set_pairs(ddp_hip_ctx* ctx, int32_t n_capsules, const int32_t* joint, const double* end0, const double* end1,
+                              const double* radius, int32_t n_pairs, const int32_t* pair_a, const int32_t* pair_kind, const int32_t* pair_b);
+/* The pairs' geometry and weights, stream-ordered like ddp_hip_obstacle_upload.  Host arrays [n_instances][T+1][n_pairs][8] and
+ * [n_instances][T+1][n_pairs]; a NULL pointer leaves that side as it is.  An upload is refused as a whole (DDP_HIP_E_ARG, nothing
+ * written) before ddp_hip_capsule_set_pairs, for a bad instance range, a non-finite geom entry (the ignored ones included), a
+ * world capsule's rho < 0, a half-space normal n with | |n| - 1 | > 1e-10 and a negative or non-finite weight.  A geom that
+ * arrives alone is checked against the pair kinds; weights that arrive alone need no geometry check. */
+int ddp_hip_capsule_upload(ddp_hip_ctx* ctx, const double* geom, const double* weight, int64_t first_instance, int64_t n_instances);
+int ddp_hip_capsule_download(ddp_hip_ctx* ctx, double* geom, double* weight, int64_t first_instance, int64_t n_instances);
+/* "Did a limb touch, where, by how much": out[batch][T+1] (host) = min over the pairs with w != 0 of d_i along X (which = 0) or
+ * X_NEW (which = 1), +inf where no pair is live, NaN where a distance is.  From the first ddp_hip_capsule_set_pairs on (before:
+ * DDP_HIP_E_ARG), live weights or not. */
+int ddp_hip_capsule_clearance(ddp_hip_ctx* ctx, int which, double* out);
 
 /* make_trajectory (ddp.hpp:392-415): X[0] and U given -> X[1..T] */
 int ddp_hip_rollout(ddp_hip_ctx* ctx);
@@ -906,6 +978,13 @@ int ddp_hip_model_frame_axis(ddp_hip_model_handle* h, int32_t joint, const doubl
  * Jq are Jc's alone).  tau < 0 or non-finite, or a total mass <= 0: DDP_HIP_E_ARG.  For targets such as "the plane 4 cm behind
  * where the capture point is now" */
 int ddp_hip_model_capture_point(ddp_hip_model_handle* h, const double* q, const double* v, double tau, double* xi3, double* Jq, double* Jv);
+/* The distance of two robot capsules of a tree model at the configuration q, as DDP_HIP_FLAG_CAPSULE_COST defines it: the segment
+ * a0 .. a1 fixed in joint ja against b0 .. b1 fixed in joint jb (ja != jb, else DDP_HIP_E_ARG; a non-finite end alike).  *D the
+ * distance of the closest points, ca3 and cb3 the two points in the world and, where not NULL, J = dD / d(delta q) as nv doubles,
+ * formed by the traversal the cost kernels use: + P_ca . u on path(ja) alone, - P_cb . u on path(jb) alone, 0 elsewhere, and all 0
+ * where D == 0.  No radius and no margin enter: d = D - (r_a + r_b + m).  For margins such as "2 cm less than they are apart now" */
+int ddp_hip_model_capsule_pair(ddp_hip_model_handle* h, int32_t ja, const double a0[3], const double a1[3], int32_t jb, const double b0[3],
+                               const double b1[3], const double* q, double* D, double* ca3, double* cb3, double* J);
 
 /* ---- built-in seeded model tables (no URDF exists offline: SURVEY.md D4, 8d) -------------- */
 /* ..._FF: the same robots on a free-flyer root instead of a fixed base / 3 prismatic + 3 revolute base joints */
