@@ -69,6 +69,7 @@ struct DevSwitches {
   bool no_static = false;      // NO_STATIC: the generic level kernels instead of the static-topology ones
   bool no_qcache = false;      // NO_QCACHE: no configuration caches
   bool qcache_dense = false;   // QCACHE_DENSE: the static stencil's q-cache keeps a whole block per stepped configuration (no base + deltas layout)
+  bool vcache_dense = false;   // VCACHE_DENSE: the static stencil's v-cache keeps its 2 nv + 1 whole entries (no base + deltas layout)
   bool cfg_full_aba = false;   // CFG_FULL_ABA: the (q_i, q_j) points of the static stencil run the whole ABA (two kernels, two streams)
   bool ana_own_aba = false;    // ANA_OWN_ABA: the analytic pass forms its own accelerations
   bool ana_split = false;      // ANA_SPLIT: the three-kernel analytic path with its HBM workspaces
@@ -142,6 +143,8 @@ struct LinPlan {
   int32_t ncfg = 0, nvcfg = 0; // q- / v-cache entries per (instance, t)
   bool qc_sparse = false;      // the static stencil's q-cache is the base block and, per stepped joint, the records its step changes
                                // (caches); false: ncfg whole blocks
+  bool vc_sparse = false;      // with qc_sparse: the v-cache is entry 0, a v-step base block and the records a q or v step changes; false:
+                               // nvcfg whole entries
   bool has_tensors = false;    // FXX / FUX / FUU are resident
   bool skip_top = false;       // LinParams::skip_top
   bool skip_qv_mirror = false; // LinParams::skip_qv_mirror

@@ -1651,6 +1651,12 @@ int64_t lin_qc_per_bt(const ddp_hip_ctx* ctx) {
   return pl.qc_sparse ? lin_static_qc_per_bt(pl.topo) : (int64_t)pl.ncfg * ctx->d.nv * rbd::QC_STRIDE;
 }
 
+// ... of the v-cache: nvcfg whole entries, or the static stencil's base blocks + deltas
+int64_t lin_vc_per_bt(const ddp_hip_ctx* ctx) {
+  const LinPlan& pl = ctx->plan;
+  return pl.vc_sparse ? lin_static_vc_per_bt(pl.topo) : (int64_t)pl.nvcfg * ctx->d.nv * rbd::VC_STRIDE;
+}
+
 LinParams make_params(ddp_hip_ctx* ctx) {
   LinParams p{};
   p.d = ctx->d;
@@ -1678,6 +1684,8 @@ LinParams make_params(ddp_hip_ctx* ctx) {
   p.qc_sparse = pl.qc_sparse ? 1 : 0;
   p.qc_bt = lin_qc_per_bt(ctx);
   p.vcache = p.qcache ? p.qcache + ctx->d.batch * ctx->d.T * p.qc_bt : nullptr;
+  p.vc_sparse = pl.vc_sparse ? 1 : 0;
+  p.vc_bt = lin_vc_per_bt(ctx);
   p.xref = S(DDP_HIP_SEQ_COST_XREF); p.wx = S(DDP_HIP_SEQ_COST_WX); p.uref = S(DDP_HIP_SEQ_COST_UREF); p.wu = S(DDP_HIP_SEQ_COST_WU);
   return p;
 }
@@ -1931,7 +1939,7 @@ int lin_setup(ddp_hip_ctx* ctx) {
   const LinPlan& pl = ctx->plan;
   if (pl.refuse) return pl.refuse;
   if (pl.ws_lin)
-    HIP_TRY(hipMalloc(&ctx->lin_ws, sizeof(double) * (size_t)(d.batch * d.T * (lin_qc_per_bt(ctx) + (int64_t)pl.nvcfg * d.nv * rbd::VC_STRIDE))));
+    HIP_TRY(hipMalloc(&ctx->lin_ws, sizeof(double) * (size_t)(d.batch * d.T * (lin_qc_per_bt(ctx) + lin_vc_per_bt(ctx)))));
   if (pl.ws_qws) {
     const int64_t BT = d.batch * d.T;
     // With the spine pre-pass forked ahead of the torque rows (LIN_FORK_SPINE) only the first slice's pre-pass runs beside them.

@@ -14,7 +14,10 @@ struct LinParams {
   double *eq_val, *eq_x, *eq_u, *eq_xx, *eq_ux, *eq_uu;
   int32_t has_tensors;
   double *eq_xk, *eq_fxk, *eq_c;   // large-model constraint chain workspace: x_1..x_K | f_x(x_1..x_{K-1}) | base jacobian
-  double* vcache;   // [batch*T][2nv+1][nv*VC_STRIDE]: (q, v)-dependent part at (q,v), (q, v+eps e_i), (q+eps e_i, v)
+  double* vcache;   // [batch*T][2nv+1][nv*VC_STRIDE]: (q, v)-dependent part at (q,v), (q, v+eps e_i), (q+eps e_i, v);
+                    // with vc_sparse, per (instance, t): entry 0, the v-step base block and the records a step changes (lin_static.hip: VcLayout)
+  int64_t vc_bt;    // doubles per (instance, t) of the v-cache: nvcfg * nv * VC_STRIDE, or VcLayout::WORDS
+  int32_t vc_sparse;   // LinPlan::vc_sparse
   double* qcache;   // [batch*T][nv+1][nv*QC_STRIDE]: q-dependent part of the ABA at the base q and at q + eps e_i (mode 2);
                     // with qc_sparse, per (instance, t): the base block and the records a step changes (lin_static.hip: QcLayout)
   int64_t qc_bt;    // doubles per (instance, t) of the q-cache: ncfg * nv * QC_STRIDE, or QcLayout::WORDS
@@ -57,6 +60,7 @@ enum class StaticLevel {
 int lin_static_launch(ddp_hip_ctx* ctx, const LinParams& p, StaticLevel level);   // DDP_HIP_OK or an error code
 int64_t lin_static_ws_per_bt(const DevModel& m);
 int64_t lin_static_qc_per_bt(int topo);   // doubles per (instance, t) of the base + deltas q-cache of a compiled-in topology (LinPlan::qc_sparse)
+int64_t lin_static_vc_per_bt(int topo);   // ... of its base + deltas v-cache (LinPlan::vc_sparse)
 
 // analytic first order / mode-1 second order of large tree models (lin_analytic.hip): stage 0 = f_x, f_u at the
 // trajectory points (problem.hpp:463-503), stage 1 = forward differences of those jacobians (problem.hpp:67-150)

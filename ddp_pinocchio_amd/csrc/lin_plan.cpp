@@ -1,8 +1,8 @@
 // lin_plan.cpp -- which kernels a context's linearisation runs: one pure function, no HIP calls, and the
 // development switches it is a function of, read from the environment.
 // With -DLIN_PLAN_TABLE the file is a program that prints the plan of every combination of its inputs (tests/test_lin_plan.py),
-// or, as `lin_plan_table schedule` / `lin_plan_table caches`, the schedule / the cache layout of the flagship plan under the
-// environment's switches (tests/test_lin_overlap.py, tests/test_sparse_caches.py).
+// or, as `lin_plan_table schedule` / `lin_plan_table caches` / `lin_plan_table vcaches`, the schedule / the cache layouts of the flagship plan under the
+// environment's switches (tests/test_lin_overlap.py, tests/test_sparse_caches.py, tests/test_sparse_vcache.py).
 #include <stdlib.h>
 
 #include "internal.h"
@@ -21,6 +21,7 @@ DevSwitches read_switches() {
   sw.no_static = on("DDP_HIP_NO_STATIC");
   sw.no_qcache = on("DDP_HIP_NO_QCACHE");
   sw.qcache_dense = on("DDP_HIP_QCACHE_DENSE");
+  sw.vcache_dense = on("DDP_HIP_VCACHE_DENSE");
   sw.cfg_full_aba = on("DDP_HIP_CFG_FULL_ABA");
   sw.ana_own_aba = on("DDP_HIP_ANA_OWN_ABA");
   sw.ana_split = on("DDP_HIP_ANA_SPLIT");
@@ -81,6 +82,7 @@ LinPlan lin_plan_decide(const DevModel& m, const Dims& d, uint32_t flags, const 
   pl.ws_qws2 = pl.second == LinSecond::Mode2Static && sw.cfg_full_aba;
   // base + deltas q-cache: the static stencil's readers alone know it (the full-ABA configuration level reads whole blocks)
   pl.qc_sparse = pl.second == LinSecond::Mode2Static && !sw.qcache_dense && !sw.cfg_full_aba;
+  pl.vc_sparse = pl.qc_sparse && !sw.vcache_dense;
   // (with DDP_HIP_NO_QCACHE on forward-differenced jacobians the two marks below are set although Mode2Plain runs: DESIGN.md 4j)
   pl.skip_top = pl.topo && mode == 2 && tensors && !sw.fxx_full;
   pl.skip_qv_mirror = pl.skip_top && sweep_sym_ok;   // only for a sweep that never reads the mirror images
@@ -125,7 +127,7 @@ LinPlan lin_plan_decide(const DevModel& m, const Dims& d, uint32_t flags, const 
 // argument checks let the combination through to lin_setup (ctx.hip: a pendulum has nv = 1 and no free flyer; a free flyer
 // leaves nj = nv - 5 >= 1 joints and is refused in mode 1 and under the config constraint; no constraint kind, no rows).
 int main(int argc, char** argv) {
-  if (argc > 1 && (argv[1][0] == 's' || argv[1][0] == 'c')) {
+  if (argc > 1 && (argv[1][0] == 's' || argv[1][0] == 'c' || argv[1][0] == 'v')) {
     // `schedule`: the forks of the flagship plan (Talos-size tree on its compiled-in topology, mode 2, forward-differenced first
     // order) under the switches of this process's environment (tests/test_lin_overlap.py)
     DevModel m{};
@@ -135,6 +137,8 @@ int main(int argc, char** argv) {
     const LinPlan p = lin_plan_decide(m, d, 0u, read_switches(), 1, true);
     // `caches`: the q-cache layout of the same plan (tests/test_sparse_caches.py)
     if (argv[1][0] == 'c') { printf("qc_sparse %d ncfg %d nvcfg %d\n", (int)p.qc_sparse, p.ncfg, p.nvcfg); return 0; }
+    // `vcaches`: its v-cache layout (tests/test_sparse_vcache.py)
+    if (argv[1][0] == 'v') { printf("vc_sparse %d qc_sparse %d nvcfg %d\n", (int)p.vc_sparse, (int)p.qc_sparse, p.nvcfg); return 0; }
     printf("forks %u topo %d\n", p.forks, p.topo);
     return 0;
   }

@@ -116,6 +116,55 @@ __device__ __forceinline__ int qc_word(int g, unsigned long long anc, int K, int
   const int w_own = (int)(e < L::ER) & (int)(K == g), w_path = (int)(e >= L::ER) & (int)((anc >> K) & 1ull);
   return base + w_own * (own - base) + w_path * (path - base);
 }
+
+// ---- the v-cache as base blocks and deltas (LinPlan::vc_sparse) ----------------------------------------------------------
+// Of the v records (cb | pA0 | Ia cb), a q_g step changes those of g's strict ancestors (their Ia) and of g's subtree, g included
+// (their link velocities); a v_g step those of g's subtree.  A subtree is one contiguous index range.  Per (instance, t), in records
+// of VC_STRIDE doubles and packed exactly (no padding to the deepest joint):
+//   entry 0               [N]                  at 0     the base (q, v), as the configuration fill writes it
+//   the v-step base block [N]                  at VB    the unstepped point as the v-step fill's own instruction stream forms it
+//   q-step deltas of g    [depth g + |sub g|]  at qoff[g]   strict ancestors root first (the popcount rule of qc_word), then the subtree
+//   v-step deltas of g    [|sub g|]            at voff[g]   the subtree
+// (165 KB per (instance, t) for the Talos-like tree against 421 KB for its 77 whole entries)
+template <class T>
+struct VcTab { int qoff[T::N], voff[T::N], sub[T::N]; int words; };   // offsets in doubles from the (instance, t)'s v-cache; subtree sizes
+template <class T>
+constexpr VcTab<T> make_vc_tab() {
+  constexpr int N = T::N, R = rbd::VC_STRIDE;
+  VcTab<T> t{};
+  int depth[N] = {};
+  for (int k = 0; k < N; ++k)
+    for (int a = T::parent[k]; a >= 0; a = T::parent[a]) { ++depth[k]; ++t.sub[a]; }
+  for (int k = 0; k < N; ++k) ++t.sub[k];          // the joint itself
+  int off = 2 * N * R;
+  for (int g = 0; g < N; ++g) { t.qoff[g] = off; off += (depth[g] + t.sub[g]) * R; }
+  for (int g = 0; g < N; ++g) { t.voff[g] = off; off += t.sub[g] * R; }
+  t.words = off;
+  return t;
+}
+template <class T>
+struct VcLayout {
+  static constexpr int N = T::N, R = rbd::VC_STRIDE;
+  static constexpr int VB = N * R;                                   // the v-step base block
+  static constexpr int WORDS = make_vc_tab<T>().words;
+};
+template <class T> __device__ const VcTab<T> g_vc_tab = make_vc_tab<T>();
+// Where word e of joint K's v record lives at the point a row reads, counted from the (instance, t)'s v-cache: kind 0, q_g stepped
+// (g = -1, anc = 0: entry 0), anc the strict ancestors of g; kind 1, v_g stepped (anc is not looked at).  Like qc_word a blend of
+// finished offsets by 0 / 1 weights
+template <class T>
+__device__ __forceinline__ int vc_word(int kind, int g, unsigned long long anc, int K, int e) {
+  using L = VcLayout<T>;
+  const VcTab<T>& tab = g_vc_tab<T>;
+  const int gi = g < 0 ? 0 : g;
+  const int nsub = g < 0 ? 0 : tab.sub[gi];
+  const int off = kind ? tab.voff[gi] : tab.qoff[gi];
+  const unsigned long long a = kind ? 0ull : anc;
+  const int dg = __popcll(a), d = __popcll(a & ((1ull << K) - 1ull));      // depth of g; of K, where K is an ancestor of g
+  const int base = kind * L::VB + K * L::R + e, below = off + (dg + K - g) * L::R + e, path = off + d * L::R + e;
+  const int w_below = (int)(K >= g) & (int)(K < g + nsub), w_path = (int)((a >> K) & 1ull);
+  return base + w_below * (below - base) + w_path * (path - base);
+}
 // ---- per-lane state ----------------------------------------------------------------------------------------------
 template <class T>
 struct TauState {
@@ -263,8 +312,11 @@ struct StageRegs {
     }
   }
   // the same words from the base + deltas layout: qc0 the (instance, t)'s q-cache, the row's configuration 1+g (qc_word)
-  template <class T>
-  __device__ __forceinline__ void load_sparse(const double* __restrict__ qc0, int g, unsigned long long anc, const double* __restrict__ vc, int lane) {
+  // VSP (LinPlan::vc_sparse): vc is the (instance, t)'s v-cache and the row's point is (vkind, vg) with the ancestors vanc
+  // (vc_word); else vc is the row's whole entry
+  template <class T, bool VSP>
+  __device__ __forceinline__ void load_sparse(const double* __restrict__ qc0, int g, unsigned long long anc, const double* __restrict__ vc,
+                                              int vkind, int vg, unsigned long long vanc, int lane) {
 #pragma unroll
     for (int c = 0; c < CP; ++c) {
       int idx = c * LBS + lane;
@@ -276,7 +328,12 @@ struct StageRegs {
     for (int c = 0; c < CV; ++c) {
       int idx = c * LBS + lane;
       idx = idx < NVW ? idx : NVW - 1;
-      rv[c] = vc[K0 * rbd::VC_STRIDE + idx];
+      if constexpr (VSP) {
+        const int K = K0 + idx / rbd::VC_STRIDE, e = idx % rbd::VC_STRIDE;
+        rv[c] = vc[vc_word<T>(vkind, vg, vanc, K, e)];
+      } else {
+        rv[c] = vc[K0 * rbd::VC_STRIDE + idx];
+      }
     }
   }
   // (no branches: the lanes past the end store the last word again -- control flow in the middle of the evaluation would split
@@ -599,7 +656,9 @@ __device__ __forceinline__ LinParams emit_params() {
 // register bound: with the layout picked at run time inside the stage it gains scratch (132 -> 148-164 B per lane in three forms
 // tried), as a template parameter the contract-layout kernel is untouched and the record one needs no scratch
 // SP (rows only): the q-cache is a base block and deltas; the staged LDS image is the same, word by word
-template <class T, bool ROWS, bool PACK = false, bool SP = false>
+// VSP (rows only, with SP): so is the v-cache (VcLayout): rows g < nv read entry 0 and the q-step deltas of g, rows g >= nv the v-step
+// base block and the v-step deltas of g - nv
+template <class T, bool ROWS, bool PACK = false, bool SP = false, bool VSP = false>
 __global__ __launch_bounds__(LBS, ROWS ? 1 : 3) void lin_static_tau_kernel(LinParams p) {
   constexpr int nv = T::N, n = 2 * nv;
   constexpr int TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS, G = ROWS ? 2 * nv : GU;
@@ -623,12 +682,14 @@ __global__ __launch_bounds__(LBS, ROWS ? 1 : 3) void lin_static_tau_kernel(LinPa
   const double eps = sqrt(sqrt(DBL_EPSILON));
   static_assert(ROWS || !SP, "the pairs read the base block alone");
   const double* __restrict__ qc = p.qcache + bt * p.qc_bt + (SP ? 0 : cfg * (nv * rbd::QC_STRIDE));
-  const double* __restrict__ vc = p.vcache + (bt * (2 * nv + 1) + vcfg) * (int64_t)nv * rbd::VC_STRIDE;
+  static_assert(SP || !VSP, "the base + deltas v-cache comes with the base + deltas q-cache");
+  const double* __restrict__ vc = p.vcache + bt * p.vc_bt + (VSP ? 0 : vcfg * (nv * rbd::VC_STRIDE));
   const double* __restrict__ xg = p.x + ((int64_t)b * (Tn + 1) + t) * n;
   const double* __restrict__ ug = p.u + ((int64_t)b * Tn + t) * nv;
   const int iu = i - n, ju = j - n;
   const int gq = cfg - 1;                                                         // the stepped joint, -1: none (SP)
   [[maybe_unused]] const unsigned long long ganc = SP && cfg > 0 ? g_anc_tab<T>.anc[gq] : 0ull;
+  [[maybe_unused]] const int vkind = g < nv ? 0 : 1, vg = g < nv ? g : g - nv;   // the row's v point (VSP)
   // the staged operands are dead once the acceleration pass is over, the output stage's buffers (rows: RowStage, pairs: OutStage)
   // are not alive before: one LDS region for all of them (the evaluation and the output stage are a barrier apart)
   __shared__ union TauLds { double P[nv * PS + nv * rbd::VC_STRIDE]; RowStage<nv> S; OutStage<nv, LBS / 2> O; } s_lds;
@@ -640,7 +701,7 @@ __global__ __launch_bounds__(LBS, ROWS ? 1 : 3) void lin_static_tau_kernel(LinPa
   StageRegs<nv, 0, (KH > 0) ? KH : 1> lower;   // (KH == 0: joint 0 once more, harmless)            // joints 0 .. KH-1: in flight through the first half of the leaf -> root pass
   {
     StageRegs<nv, KH, nv> upper;
-    if constexpr (SP) { upper.template load_sparse<T>(qc, gq, ganc, vc, lane); lower.template load_sparse<T>(qc, gq, ganc, vc, lane); }
+    if constexpr (SP) { upper.template load_sparse<T, VSP>(qc, gq, ganc, vc, vkind, vg, ganc, lane); lower.template load_sparse<T, VSP>(qc, gq, ganc, vc, vkind, vg, ganc, lane); }
     else { upper.load(qc, vc, lane); lower.load(qc, vc, lane); }
     upper.park(s_P, s_V, lane);
     rbd::coop_sync<true>();                         // one wave per workgroup: LDS is in order, no vmcnt(0) behind this fence
@@ -1365,7 +1426,7 @@ __device__ __forceinline__ bool xcd_slot(int nb, int& btl, int& g) {
 // SP: the stepped configurations' records come from the delta blocks (they are exactly the records a step changes)
 template <class T, bool SP>
 __global__ __launch_bounds__(LBS) void lin_static_spine_kernel(const DevModel* __restrict__ model, const double* __restrict__ qcache, int64_t qc_bt,
-                                                               const double* __restrict__ vcache, double* __restrict__ spine, int64_t bt0, int nb) {
+                                                               const double* __restrict__ vcache, int64_t vc_bt, double* __restrict__ spine, int64_t bt0, int nb) {
   constexpr int nv = T::N, TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS, NREC = spine_records<T>();
   int btl, g;
   if (!xcd_slot<GU>(nb, btl, g)) return;
@@ -1377,7 +1438,7 @@ __global__ __launch_bounds__(LBS) void lin_static_spine_kernel(const DevModel* _
   const int rstride = tab.rstride[slot];
   [[maybe_unused]] const unsigned long long anc_i = tab.anc[i], anc_j = tab.anc[j];
   const double* __restrict__ qc0 = qcache + (bt0 + btl) * qc_bt;
-  const double* __restrict__ vc0 = vcache + ((bt0 + btl) * (2 * nv + 1)) * (int64_t)nv * rbd::VC_STRIDE;   // entry 0: the base (q, v)
+  const double* __restrict__ vc0 = vcache + (bt0 + btl) * vc_bt;   // entry 0: the base (q, v), first in either layout
   double* __restrict__ out = spine + ((int64_t)btl * NREC + tab.rbase[slot]) * SREC;
   double Ia[21];
 #pragma unroll
@@ -1614,7 +1675,7 @@ __global__ __launch_bounds__(LBS) void lin_static_first_kernel(LinParams p, cons
   __shared__ double s_q[(nv + 1) * (nv + 1)];
   double* uq = s_q + (valid ? lane : nv) * (nv + 1);
   if constexpr (LEVEL == 3) {
-    const double* __restrict__ vc = p.vcache + (bt * p.nvcfg) * (int64_t)nv * rbd::VC_STRIDE;
+    const double* __restrict__ vc = p.vcache + bt * p.vc_bt;     // entry 0
     TauState<T> s;
     auto tau = [&](int k) { double v = ug[k]; if (k == lane) v = v + eps; return v; };
     tau_up_all<T, rbd::QC_STRIDE>(*model, qc0, vc, tau, s, std::make_integer_sequence<int, nv>{});
@@ -1722,9 +1783,9 @@ __device__ __forceinline__ void placement_static(const DevModel& m, double q, do
   }
 }
 
-template <class T, bool SP_>
+template <class T, bool SP_, bool VSP_>
 struct QvCtx {
-  static constexpr bool SP = SP_;
+  static constexpr bool SP = SP_, VSP = VSP_;
   static constexpr bool V_STEPPED = false;
   static constexpr bool LDS_VEL = true;
   const DevModel* __restrict__ m;
@@ -1733,7 +1794,10 @@ struct QvCtx {
   double* qown;                // SP, a stepped configuration: E | r of the stepped joint, the head of its delta block
   double* qpath;               // SP, a stepped configuration: the path records behind it ([depth][28])
   unsigned long long anc;      // SP: strict ancestors of the stepped joint
-  double* __restrict__ vc;     // this lane's v-cache block
+  double* __restrict__ vc;     // this lane's v-cache block (VSP: entry 0 of its (instance, t), which all of its lanes store onto)
+  int vpath;                   // VSP, a stepped configuration: its q-step deltas, counted from vc -- the records of the ancestors ([depth][18]) ...
+  int vsub;                    // ... and behind them those of the subtree, counted so that joint K's is at vc + vsub + K * 18
+  int sub_end;                 // VSP: one past the stepped joint's subtree, jn .. sub_end - 1 (0: no step)
   double* lvel;                // LDS: link velocities of the chain being swept
   int jn;                      // joint whose position this lane steps (-1: none)
   double eps;
@@ -1751,8 +1815,8 @@ struct QvState {
   double accI[T::N][21];
 };
 // leaf -> root step of the cache fill (rbd::aba_qpart, and rbd::aba_vpart_cached at the base velocity) for the joints K .. F of a chain
-template <class T, int K, int F, bool SP>
-__device__ __forceinline__ void chain_up(const QvCtx<T, SP>& c, QvState<T>& s) {
+template <class T, int K, int F, bool SP, bool VSP>
+__device__ __forceinline__ void chain_up(const QvCtx<T, SP, VSP>& c, QvState<T>& s) {
   constexpr int o = T::prismatic[K] ? 3 : 0;
   const double* a = c.m->axis[K];
   double Pb[12], IA[21], U[6], Ia[21], vel[6], dinv;
@@ -1796,14 +1860,23 @@ __device__ __forceinline__ void chain_up(const QvCtx<T, SP>& c, QvState<T>& s) {
   qo_ud[6] = dinv;
 #pragma unroll
   for (int k = 0; k < 21; ++k) qo_ud[7 + k] = Ia[k];
-  double* vo = c.vc + K * rbd::VC_STRIDE;
+  // the v record likewise (VSP): one the step changes -- an ancestor's or the subtree's -- goes to the lane's q-step deltas, any other
+  // onto entry 0, where the base configuration's lane stores the same bits
+  // (an offset from the one pointer is selected, not a pointer: the stores stay global stores)
+  int voff = K * rbd::VC_STRIDE;
+  if constexpr (VSP) {
+    constexpr int DK = depth_of<T>(K);
+    voff = (K >= c.jn) & (K < c.sub_end) ? c.vsub + K * rbd::VC_STRIDE : voff;
+    if constexpr (has_child<T>(K)) voff = ((c.anc >> K) & 1ull) ? c.vpath + DK * rbd::VC_STRIDE : voff;
+  }
+  double* vo = c.vc + voff;
 #pragma unroll
   for (int k = 0; k < 18; ++k) vo[k] = vrec[k];
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (K > F) chain_up<T, K - 1, F>(c, s);
 }
 
-template <class T, bool SP>
+template <class T, bool SP, bool VSP = false>
 __global__ __launch_bounds__(LBS, 2) void lin_static_qvcache_kernel(LinParams p, const DevModel* __restrict__ model, const double* __restrict__ xs,
                                                                  double* __restrict__ qcache, double* __restrict__ vcache) {
   constexpr int nv = T::N, n = 2 * nv, MAXCH = max_chain<T>();
@@ -1818,7 +1891,8 @@ __global__ __launch_bounds__(LBS, 2) void lin_static_qvcache_kernel(LinParams p,
   const int64_t t = bt % Tn;
   __shared__ double s_vel[MAXCH * 6 * LBS];
   if (bt >= p.d.batch * Tn) return;                       // (no workgroup barrier below)
-  QvCtx<T, SP> c;
+  static_assert(SP || !VSP, "the base + deltas v-cache comes with the base + deltas q-cache");
+  QvCtx<T, SP, VSP> c;
   c.m = model;
   c.xg = xs + ((int64_t)b * (Tn + 1) + t) * n;
   c.qc = qcache + bt * p.qc_bt + (SP ? 0 : cfgi * (nv * rbd::QC_STRIDE));
@@ -1827,8 +1901,11 @@ __global__ __launch_bounds__(LBS, 2) void lin_static_qvcache_kernel(LinParams p,
     c.qown = c.qc + (QcLayout<T>::DELTA + g * QcLayout<T>::DW);
     c.qpath = c.qown + QcLayout<T>::ER;
     c.anc = g_anc_tab<T>.anc[g];
+    c.vc = vcache + bt * p.vc_bt + (VSP || cfgi == 0 ? 0 : (nv + cfgi) * (nv * rbd::VC_STRIDE));
+    c.vpath = g_vc_tab<T>.qoff[g];
+    c.vsub = c.vpath + (__popcll(c.anc) - g) * rbd::VC_STRIDE;
+    c.sub_end = cfgi > 0 ? g + g_vc_tab<T>.sub[g] : 0;
   }
-  c.vc = vcache + (bt * p.nvcfg + (cfgi == 0 ? 0 : nv + cfgi)) * (int64_t)nv * rbd::VC_STRIDE;
   c.lvel = s_vel + lane;
   c.jn = cfgi - 1;
   c.eps = sqrt(sqrt(DBL_EPSILON));
@@ -1837,9 +1914,13 @@ __global__ __launch_bounds__(LBS, 2) void lin_static_qvcache_kernel(LinParams p,
 }
 
 // lin_static_vcache_kernel: v-cache entries 1 + i = (q, v + eps e_i): first pass of the ABA on the cached base q-part
-template <class T, int K>
+// VSP (LinPlan::vc_sparse): lane g stores the records of its subtree (K in g .. sub_end - 1: the ones its step changes) into its v-step
+// deltas (vc + vown + K * 18) and every other record onto the v-step base block (vc), and lane nv runs the chain unstepped and stores the
+// whole base block: outside g's subtree the lanes g and nv execute the same instructions on the same operands.  Selected
+// addresses, as in the configuration fill
+template <class T, int K, bool VSP>
 __device__ __forceinline__ void vc_joint(const DevModel& m, const double* __restrict__ qc, const double* __restrict__ xg, int iv, double eps,
-                                         double (&vel)[T::N][6], double* __restrict__ vc) {
+                                         double (&vel)[T::N][6], double* __restrict__ vc, int vown, int sub_end) {
   constexpr int o = T::prismatic[K] ? 3 : 0;
   const double* E = qc + K * rbd::QC_STRIDE;
   const double* r = E + 9;
@@ -1851,17 +1932,19 @@ __device__ __forceinline__ void vc_joint(const DevModel& m, const double* __rest
   step_joint_motion<o>(a, vK, vJ);
   step_link_vel<(T::parent[K] < 0)>(E, r, vel[T::parent[K] >= 0 ? T::parent[K] : 0], vJ, vel[K]);
   step_vpart(m.I6[K], Ia, vel[K], vJ, vrec);
-  double* vo = vc + K * rbd::VC_STRIDE;
+  int voff = K * rbd::VC_STRIDE;
+  if constexpr (VSP) voff = (K >= iv) & (K < sub_end) ? vown + K * rbd::VC_STRIDE : voff;
+  double* vo = vc + voff;
 #pragma unroll
   for (int k = 0; k < 18; ++k) vo[k] = vrec[k];
   __builtin_amdgcn_sched_barrier(0);
 }
-template <class T, int... Ks>
+template <class T, bool VSP, int... Ks>
 __device__ __forceinline__ void vc_all(const DevModel& m, const double* __restrict__ qc, const double* __restrict__ xg, int iv, double eps,
-                                       double (&vel)[T::N][6], double* __restrict__ vc, std::integer_sequence<int, Ks...>) {
-  (vc_joint<T, Ks>(m, qc, xg, iv, eps, vel, vc), ...);
+                                       double (&vel)[T::N][6], double* __restrict__ vc, int vown, int sub_end, std::integer_sequence<int, Ks...>) {
+  (vc_joint<T, Ks, VSP>(m, qc, xg, iv, eps, vel, vc, vown, sub_end), ...);
 }
-template <class T>
+template <class T, bool VSP>
 __global__ __launch_bounds__(LBS) void lin_static_vcache_kernel(LinParams p, const DevModel* __restrict__ model, const double* __restrict__ xs,
                                                                 const double* __restrict__ qcache, double* __restrict__ vcache) {
   constexpr int nv = T::N, n = 2 * nv;
@@ -1870,12 +1953,16 @@ __global__ __launch_bounds__(LBS) void lin_static_vcache_kernel(LinParams p, con
   const int64_t Tn = p.d.T;
   const int b = (int)(bt / Tn);
   const int64_t t = bt % Tn;
-  if (lane >= nv) return;
+  if (lane >= nv + (VSP ? 1 : 0)) return;
   const double* __restrict__ qc = qcache + bt * p.qc_bt;       // the base block
   const double* __restrict__ xg = xs + ((int64_t)b * (Tn + 1) + t) * n;
-  double* __restrict__ vc = vcache + (bt * (2 * nv + 1) + 1 + lane) * (int64_t)nv * rbd::VC_STRIDE;
+  double* vc0 = vcache + bt * p.vc_bt;
+  double* vc = vc0 + (VSP ? VcLayout<T>::VB : (1 + lane) * (nv * rbd::VC_STRIDE));
+  const int g = lane < nv ? lane : 0;
+  const int vown = g_vc_tab<T>.voff[g] - g * rbd::VC_STRIDE - VcLayout<T>::VB;   // counted from vc
+  const int sub_end = lane < nv ? g + g_vc_tab<T>.sub[g] : 0;
   double vel[nv][6];
-  vc_all<T>(*model, qc, xg, lane, sqrt(sqrt(DBL_EPSILON)), vel, vc, std::make_integer_sequence<int, nv>{});
+  vc_all<T, VSP>(*model, qc, xg, lane, sqrt(sqrt(DBL_EPSILON)), vel, vc, vown, sub_end, std::make_integer_sequence<int, nv>{});
 }
 
 }  // namespace
@@ -1902,6 +1989,16 @@ int64_t lin_static_qc_per_bt(int topo) {
   return 0;
 }
 
+// doubles per (instance, t) of the base + deltas v-cache (LinPlan::vc_sparse)
+int64_t lin_static_vc_per_bt(int topo) {
+  if (topo == 1) return VcLayout<TopoTalos38>::WORDS;
+  if (topo == 2) return VcLayout<TopoChain6>::WORDS;
+#define DDP_TOPO_VC(ID, TOPO) if (topo == (ID) - 1) return VcLayout<TOPO>::WORDS;
+  DDP_TOPO_EXTRA(DDP_TOPO_VC)
+#undef DDP_TOPO_VC
+  return 0;
+}
+
 int64_t lin_static_ws_per_bt(const DevModel& m) {
   const int64_t nv = m.nv, TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS;
   int64_t rec = 0;
@@ -1920,13 +2017,15 @@ int64_t lin_static_ws_per_bt(const DevModel& m) {
 template <class T>
 static void launch_qvcache(const LinParams& p, int64_t BT, hipStream_t s) {
   const dim3 grid((unsigned)((BT * p.ncfg + LBS - 1) / LBS));
-  if (p.qc_sparse) hipLaunchKernelGGL((lin_static_qvcache_kernel<T, true>), grid, dim3(LBS), 0, s, p, p.model, p.x, p.qcache, p.vcache);
+  if (p.vc_sparse) hipLaunchKernelGGL((lin_static_qvcache_kernel<T, true, true>), grid, dim3(LBS), 0, s, p, p.model, p.x, p.qcache, p.vcache);
+  else if (p.qc_sparse) hipLaunchKernelGGL((lin_static_qvcache_kernel<T, true>), grid, dim3(LBS), 0, s, p, p.model, p.x, p.qcache, p.vcache);
   else hipLaunchKernelGGL((lin_static_qvcache_kernel<T, false>), grid, dim3(LBS), 0, s, p, p.model, p.x, p.qcache, p.vcache);
 }
 template <class T>
 static void launch_tau_rows(const LinParams& p, int64_t BT, hipStream_t s) {
   const dim3 grid((unsigned)(BT * 2 * T::N));
-  if (p.qc_sparse) hipLaunchKernelGGL((lin_static_tau_kernel<T, true, false, true>), grid, dim3(LBS), 0, s, p);
+  if (p.vc_sparse) hipLaunchKernelGGL((lin_static_tau_kernel<T, true, false, true, true>), grid, dim3(LBS), 0, s, p);
+  else if (p.qc_sparse) hipLaunchKernelGGL((lin_static_tau_kernel<T, true, false, true>), grid, dim3(LBS), 0, s, p);
   else hipLaunchKernelGGL((lin_static_tau_kernel<T, true>), grid, dim3(LBS), 0, s, p);
 }
 template <class T>
@@ -1964,8 +2063,8 @@ static int launch_cfg_slices(ddp_hip_ctx* ctx, const LinParams& p, hipStream_t s
   for (int64_t bt0 = 0; bt0 < BT; bt0 += per) {
     const int nb = (int)(BT - bt0 < per ? BT - bt0 : per);
     const dim3 grid((unsigned)((nb + 7) / 8 * 8 * GU));
-    if (p.qc_sparse) hipLaunchKernelGGL((lin_static_spine_kernel<T, true>), grid, dim3(LBS), 0, s, p.model, p.qcache, p.qc_bt, p.vcache, ctx->lin_qws, bt0, nb);
-    else hipLaunchKernelGGL((lin_static_spine_kernel<T, false>), grid, dim3(LBS), 0, s, p.model, p.qcache, p.qc_bt, p.vcache, ctx->lin_qws, bt0, nb);
+    if (p.qc_sparse) hipLaunchKernelGGL((lin_static_spine_kernel<T, true>), grid, dim3(LBS), 0, s, p.model, p.qcache, p.qc_bt, p.vcache, p.vc_bt, ctx->lin_qws, bt0, nb);
+    else hipLaunchKernelGGL((lin_static_spine_kernel<T, false>), grid, dim3(LBS), 0, s, p.model, p.qcache, p.qc_bt, p.vcache, p.vc_bt, ctx->lin_qws, bt0, nb);
     if (rows_done) { HIP_TRY(hipStreamWaitEvent(s, rows_done, 0)); rows_done = nullptr; }
     if (p.qc_sparse) hipLaunchKernelGGL((lin_static_cfg_pair_kernel<T, true>), grid, dim3(LBS), 0, s, p, ctx->lin_qws, bt0, nb);
     else hipLaunchKernelGGL((lin_static_cfg_pair_kernel<T, false>), grid, dim3(LBS), 0, s, p, ctx->lin_qws, bt0, nb);
@@ -2014,7 +2113,8 @@ static int lin_static_launch_t(ddp_hip_ctx* ctx, const LinParams& p, StaticLevel
     else hipLaunchKernelGGL((lin_static_tau_kernel<T, false, false>), dim3((unsigned)(BT * GU)), dim3(LBS), 0, ctx->stream, p);
   } else if (level == StaticLevel::Caches) {
     launch_qvcache<T>(p, BT, ctx->stream);
-    if (p.nvcfg > 1) hipLaunchKernelGGL((lin_static_vcache_kernel<T>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.x, p.qcache, p.vcache);
+    if (p.nvcfg > 1 && p.vc_sparse) hipLaunchKernelGGL((lin_static_vcache_kernel<T, true>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.x, p.qcache, p.vcache);
+    else if (p.nvcfg > 1) hipLaunchKernelGGL((lin_static_vcache_kernel<T, false>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.x, p.qcache, p.vcache);
   } else if (level == StaticLevel::AccelXU || level == StaticLevel::AccelX) {   // -> p.accel_out, after the base caches
     if (!p.accel_out) return DDP_HIP_E_ARG;
     launch_qvcache<T>(p, BT, ctx->stream);
