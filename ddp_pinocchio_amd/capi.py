@@ -46,6 +46,7 @@ MAX_AIM_FRAMES = 4
 MAX_CAPSULES, MAX_CAPSULE_PAIRS = 16, 32
 CAPSULE_VS_ROBOT, CAPSULE_VS_CAPSULE, CAPSULE_VS_HALFSPACE = 0, 1, 2
 OBSTACLE_SPHERE, OBSTACLE_HALFSPACE = 0, 1
+OBSTACLE_GRID, MAX_GRID_DIM = 2, 256
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
 ADVANCE_NO_ROLL, ADVANCE_OPEN_LOOP, ADVANCE_CLOSED_LOOP = 0, 1, 2
 
@@ -81,6 +82,7 @@ EXPORTS = [
     "ddp_hip_com_cost_upload", "ddp_hip_com_cost_download", "ddp_hip_model_com",
     "ddp_hip_frame_vel_upload", "ddp_hip_frame_vel_download", "ddp_hip_model_frame_velocity",
     "ddp_hip_obstacle_set_points", "ddp_hip_obstacle_upload", "ddp_hip_obstacle_download", "ddp_hip_obstacle_clearance",
+    "ddp_hip_obstacle_set_grid", "ddp_hip_obstacle_set_occupancy", "ddp_hip_obstacle_grid_download", "ddp_hip_obstacle_grid_query",
     "ddp_hip_self_collision_set_pairs", "ddp_hip_self_collision_upload", "ddp_hip_self_collision_download",
     "ddp_hip_self_collision_clearance",
     "ddp_hip_momentum_cost_upload", "ddp_hip_momentum_cost_download", "ddp_hip_model_centroidal_momentum",
@@ -197,6 +199,11 @@ def lib():
         L.ddp_hip_obstacle_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_obstacle_download.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
         L.ddp_hip_obstacle_clearance.argtypes = [C.c_void_p, C.c_int, _dp]
+    if hasattr(L, "ddp_hip_obstacle_set_grid"):      # (likewise: set_obstacle_grid, set_obstacle_occupancy, obstacle_grid, obstacle_grid_query)
+        L.ddp_hip_obstacle_set_grid.argtypes = [C.c_void_p, _ip, _dp, C.c_double, _dp]
+        L.ddp_hip_obstacle_set_occupancy.argtypes = [C.c_void_p, _ip, _dp, C.c_double, C.POINTER(C.c_uint8)]
+        L.ddp_hip_obstacle_grid_download.argtypes = [C.c_void_p, _ip, _dp, _dp, _dp]
+        L.ddp_hip_obstacle_grid_query.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp]
     if hasattr(L, "ddp_hip_self_collision_upload"):  # (likewise: set_self_collision_pairs, set_self_collision_cost, self_collision_clearance)
         L.ddp_hip_self_collision_set_pairs.argtypes = [C.c_void_p, C.c_int32, _ip, _dp, _dp, C.c_int32, _ip, _ip]
         L.ddp_hip_self_collision_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
@@ -888,8 +895,9 @@ class Context:
 
     def set_obstacle_points(self, points, kinds):
         """The collision points [(joint, off, radius), ...] (up to MAX_COLLISION_POINTS spheres on the robot) and the kinds of the
-        obstacle slots (OBSTACLE_SPHERE / OBSTACLE_HALFSPACE, up to MAX_OBSTACLES) of a context created with FLAG_OBSTACLE_COST
-        (ddp_hip.h), shared by the batch.  With the same counts and kinds as before the per-instance data stays, else it is reset"""
+        obstacle slots (OBSTACLE_SPHERE / OBSTACLE_HALFSPACE / OBSTACLE_GRID, up to MAX_OBSTACLES) of a context created with
+        FLAG_OBSTACLE_COST (ddp_hip.h), shared by the batch.  OBSTACLE_GRID needs a resident grid (set_obstacle_grid or
+        set_obstacle_occupancy first).  With the same counts and kinds as before the per-instance data stays, else it is reset"""
         joint = np.ascontiguousarray([int(p[0]) for p in points], dtype=np.int32)
         off = np.ascontiguousarray([p[1] for p in points], dtype=np.float64).reshape(-1)
         radius = np.ascontiguousarray([p[2] for p in points], dtype=np.float64)
@@ -903,7 +911,8 @@ class Context:
 
     def set_obstacle_cost(self, geom=None, weight=None, first=0, count=None):
         """The obstacles of instances first .. first + count - 1 (a context created with FLAG_OBSTACLE_COST; ddp_hip.h), of the
-        n_obs slots of set_obstacle_points.  geom: (c, rho) of a sphere, (n, h) of a half-space, as (n_obs, 4) for every instance
+        n_obs slots of set_obstacle_points.  geom: (c, rho) of a sphere, (n, h) of a half-space, (shift, margin) of a grid slot (the
+        grid is seen displaced by shift; d = phi(p - shift) - r - margin), as (n_obs, 4) for every instance
         and t, (T+1, n_obs, 4) for every instance or (count, T+1, n_obs, 4); weight: >= 0, as (n_obs,), (T+1, n_obs) or
         (count, T+1, n_obs).  None leaves that side as it is.  The slot count is the one this object last passed to
         set_obstacle_points; before that call there is no shape to check against and the call raises ValueError."""
@@ -925,6 +934,57 @@ class Context:
         out = np.zeros((self.batch, self.spec.T + 1))
         _check(lib().ddp_hip_obstacle_clearance(self._h, int(which), _ptr(out)), "obstacle_clearance")
         return out
+
+    @staticmethod
+    def _grid_args(who, field, origin, cell, dtype):
+        """dims, origin and the C-contiguous field of a set_obstacle_grid / set_obstacle_occupancy call, shapes checked"""
+        field = np.asarray(field)
+        if field.ndim != 3:
+            raise ValueError(f"{who}: the grid is an array of shape (nx, ny, nz), got {field.shape}")
+        origin = np.ascontiguousarray(origin, dtype=np.float64)
+        if origin.shape != (3,):
+            raise ValueError(f"{who}: origin is (x, y, z), got shape {origin.shape}")
+        if np.ndim(cell) != 0:
+            raise ValueError(f"{who}: cell is one number, the node spacing on the three axes")
+        return np.ascontiguousarray(field.shape, dtype=np.int32), origin, float(cell), np.ascontiguousarray(field, dtype=dtype)
+
+    def set_obstacle_grid(self, phi, origin, cell):
+        """The signed distance field of the OBSTACLE_GRID slots (a context created with FLAG_OBSTACLE_COST; ddp_hip.h): phi of
+        shape (nx, ny, nz), 2 <= n <= MAX_GRID_DIM, finite; origin the world position of node (0, 0, 0); cell > 0 the node
+        spacing.  Replaces the resident grid, of whatever shape; waits for the context's stream"""
+        dims, origin, cell, phi = self._grid_args("set_obstacle_grid", phi, origin, cell, np.float64)
+        _check(lib().ddp_hip_obstacle_set_grid(self._h, dims.ctypes.data_as(_ip), _ptr(origin), cell, _ptr(phi)), "obstacle_set_grid")
+
+    def set_obstacle_occupancy(self, occ, origin, cell):
+        """The same from occupancy voxels occ of shape (nx, ny, nz), non-zero (or True) meaning occupied: the field is built on the
+        device by an exact Euclidean distance transform, the surface halfway between a free voxel and its occupied neighbour"""
+        occ = np.asarray(occ)
+        if occ.dtype == np.bool_:
+            occ = occ.view(np.uint8)
+        elif occ.dtype != np.uint8:
+            occ = (occ != 0).view(np.uint8)           # (a bool or uint8 array that is C-contiguous is passed as it is, no copy)
+        dims, origin, cell, occ = self._grid_args("set_obstacle_occupancy", occ, origin, cell, np.uint8)
+        _check(lib().ddp_hip_obstacle_set_occupancy(self._h, dims.ctypes.data_as(_ip), _ptr(origin), cell,
+                                                    occ.ctypes.data_as(C.POINTER(C.c_uint8))), "obstacle_set_occupancy")
+
+    def obstacle_grid(self):
+        """(phi, origin, cell) of the resident grid: (nx, ny, nz), (3,) and a float"""
+        dims, origin, cell = np.zeros(3, dtype=np.int32), np.zeros(3), C.c_double(0.0)
+        _check(lib().ddp_hip_obstacle_grid_download(self._h, dims.ctypes.data_as(_ip), _ptr(origin), C.byref(cell), None), "obstacle_grid_download")
+        phi = np.zeros(tuple(int(n) for n in dims))
+        _check(lib().ddp_hip_obstacle_grid_download(self._h, dims.ctypes.data_as(_ip), _ptr(origin), C.byref(cell), _ptr(phi)), "obstacle_grid_download")
+        return phi, origin, cell.value
+
+    def obstacle_grid_query(self, points, grad=True):
+        """phi at the world points (n, 3) by the device function the cost kernels use, and with grad its gradient (n, 3): +inf and
+        a zero gradient outside the grid.  Returns phi, or (phi, grad)"""
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        if points.ndim != 2 or points.shape[1] != 3:
+            raise ValueError(f"obstacle_grid_query: points is (n, 3), got {points.shape}")
+        n = points.shape[0]
+        val, g = np.zeros(n), (np.zeros((n, 3)) if grad else None)
+        _check(lib().ddp_hip_obstacle_grid_query(self._h, n, _ptr(points), _ptr(val), _ptr(g) if grad else None), "obstacle_grid_query")
+        return (val, g) if grad else val
 
     def set_self_collision_pairs(self, points, pairs):
         """The spheres [(joint, off, radius), ...] (2 .. MAX_COLLISION_POINTS of them) and the pairs [(a, b), ...] of sphere indices

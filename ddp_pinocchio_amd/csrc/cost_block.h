@@ -115,14 +115,16 @@ static inline bool cost_aim_target_side(const CostCheck&, const double* v, int64
   }
   return true;
 }
-// obstacle geometry by slot kind: a sphere's radius >= 0, a half-space's unit normal
+// obstacle geometry by slot kind: a sphere's radius >= 0, a half-space's unit normal; a grid's shift and margin are finite, no more
+// (a margin may be negative)
 static inline bool cost_obstacle_geom_side(const CostCheck& c, const double* v, int64_t words) {
   for (int64_t i = 0; i < words / 4; ++i) {
     const double* g = v + 4 * i;
     if (!isfinite(g[0]) || !isfinite(g[1]) || !isfinite(g[2]) || !isfinite(g[3])) return false;
-    if (c.kind[i % c.items] == DDP_HIP_OBSTACLE_SPHERE) {
+    const int32_t kind = c.kind[i % c.items];
+    if (kind == DDP_HIP_OBSTACLE_SPHERE) {
       if (g[3] < 0.0) return false;
-    } else if (fabs(sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) - 1.0) > 1e-10) {
+    } else if (kind == DDP_HIP_OBSTACLE_HALFSPACE && fabs(sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) - 1.0) > 1e-10) {
       return false;
     }
   }

@@ -412,6 +412,10 @@ extern "C" int ddp_hip_destroy(ddp_hip_ctx* ctx) {
     if (k.cand) (void)hipFree(k.cand);
   }
   if (ctx->ob_clear_d) (void)hipFree(ctx->ob_clear_d);
+  for (double* p : ctx->og_phi)
+    if (p) (void)hipFree(p);
+  if (ctx->og_d2) (void)hipFree(ctx->og_d2);
+  if (ctx->og_occ) (void)hipFree(ctx->og_occ);
   if (ctx->sc_clear_d) (void)hipFree(ctx->sc_clear_d);
   if (ctx->cp_clear_d) (void)hipFree(ctx->cp_clear_d);
   if (ctx->rf_err_d) (void)hipFree(ctx->rf_err_d);
@@ -652,7 +656,9 @@ extern "C" int ddp_hip_obstacle_set_points(ddp_hip_ctx* ctx, int32_t n_points, c
     if (!isfinite(radius[k]) || radius[k] < 0.0) return DDP_HIP_E_ARG;
   }
   for (int o = 0; o < n_obstacles; ++o)
-    if (kind[o] != DDP_HIP_OBSTACLE_SPHERE && kind[o] != DDP_HIP_OBSTACLE_HALFSPACE) return DDP_HIP_E_ARG;
+    if (kind[o] != DDP_HIP_OBSTACLE_SPHERE && kind[o] != DDP_HIP_OBSTACLE_HALFSPACE &&
+        !(kind[o] == DDP_HIP_OBSTACLE_GRID && ctx->og_cur >= 0))   // (a grid slot needs a grid: ddp_hip_obstacle_set_grid / _set_occupancy first)
+      return DDP_HIP_E_ARG;
   bool same = n_points == ctx->ob_np && n_obstacles == ctx->ob_no;
   for (int o = 0; same && o < n_obstacles; ++o) same = kind[o] == ctx->ob_kind[o];
   if (!same) {

@@ -1240,6 +1240,7 @@ __global__ __launch_bounds__(64) void joint_accel_cost_kernel(JointAccelDev ja, 
 // its live slots in LDS; the group's first lane adds the points' terms in ascending order.  A pair (point, slot) with w == 0 or
 // e == 0 is left out, a block whose weights are all 0 walks nothing, and a pair without an active term adds nothing (add != 0) or
 // stores +0 (add == 0).  A non-finite state gives a NaN term, as com_cost_kernel's does
+template <bool GRID>
 __global__ __launch_bounds__(64) void obstacle_cost_kernel(ObstacleCostDev ob, const DevModel* model, const double* xs, int64_t traj_stride,
                                                            int64_t count, int32_t T1, int32_t nx, int32_t na, const int32_t* state,
                                                            int32_t round, double* out, int32_t add) {
@@ -1254,7 +1255,7 @@ __global__ __launch_bounds__(64) void obstacle_cost_kernel(ObstacleCostDev ob, c
     double pk[3];
     bool act = false;
     rbd::frame_point(m, m.ff != 0, ob.joint[k], off, x, pk);
-    *term = rbd::obstacle_point_term(ob, k, pk, ob.geom + bt1 * ob.no * 4, w, &act);
+    *term = rbd::obstacle_point_term<GRID>(ob, k, pk, ob.geom + bt1 * ob.no * 4, w, &act);
     return act;
   });
 }
@@ -1262,6 +1263,7 @@ __global__ __launch_bounds__(64) void obstacle_cost_kernel(ObstacleCostDev ob, c
 // ddp_hip_obstacle_clearance: the same lane layout over the `count` (instance, t) pairs of one resident trajectory (a list of
 // one-state trajectories, no candidates to skip), min instead of sum: out[pair] = min over points and over slots with w != 0 of
 // d_ko, +inf where no slot is live, NaN where a distance is NaN
+template <bool GRID>
 __global__ __launch_bounds__(64) void obstacle_clearance_kernel(ObstacleCostDev ob, const DevModel* model, const double* xs, int64_t count,
                                                                 int32_t nx, double* out) {
   __shared__ double s_min[64];
@@ -1273,7 +1275,7 @@ __global__ __launch_bounds__(64) void obstacle_clearance_kernel(ObstacleCostDev 
     const double off[3] = {ob.off[k][0], ob.off[k][1], ob.off[k][2]};
     double pk[3];
     rbd::frame_point(m, m.ff != 0, ob.joint[k], off, x, pk);
-    *best = rbd::obstacle_point_clearance(ob, k, pk, ob.geom + e * ob.no * 4, w);
+    *best = rbd::obstacle_point_clearance<GRID>(ob, k, pk, ob.geom + e * ob.no * 4, w);
     return true;
   });
 }
@@ -1684,7 +1686,9 @@ static void launch_joint_accel_cost(ddp_hip_ctx* ctx, const double* xs, const do
   launch_joint_accel(joint_accel_dev(ctx), ctx, xs, us, na, count, state, round, out, add);
 }
 static void launch_obstacle_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
-  launch_add_on(obstacle_cost_kernel, obstacle_cost_dev(ctx), DDP_HIP_MAX_COLLISION_POINTS, ctx, xs, na, count, state, round, out, add);
+  const ObstacleCostDev ob = obstacle_cost_dev(ctx);
+  launch_add_on(ob.grid_slots ? obstacle_cost_kernel<true> : obstacle_cost_kernel<false>, ob, DDP_HIP_MAX_COLLISION_POINTS, ctx, xs, na, count, state,
+                round, out, add);
 }
 static void launch_self_collision_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   launch_add_on(self_collision_cost_kernel, self_collision_dev(ctx), DDP_HIP_MAX_COLLISION_POINTS, ctx, xs, na, count, state, round, out, add);
@@ -1747,7 +1751,7 @@ extern "C" int ddp_hip_obstacle_clearance(ddp_hip_ctx* ctx, int which, double* o
   const ObstacleCostDev ob = obstacle_cost_dev(ctx, true);
   const int64_t total = ctx->d.batch * (ctx->d.T + 1);
   const int64_t per = 64 / DDP_HIP_MAX_COLLISION_POINTS;
-  hipLaunchKernelGGL(obstacle_clearance_kernel, dim3((unsigned)((total + per - 1) / per)), dim3(64), 0, ctx->stream, ob, ctx->model_d,
+  hipLaunchKernelGGL(ob.grid_slots ? obstacle_clearance_kernel<true> : obstacle_clearance_kernel<false>, dim3((unsigned)((total + per - 1) / per)), dim3(64), 0, ctx->stream, ob, ctx->model_d,
                      which == 0 ? p.x_old : p.x_new, total, (int32_t)ctx->d.nx, ctx->ob_clear_d);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, ctx->ob_clear_d, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));

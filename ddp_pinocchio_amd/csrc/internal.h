@@ -281,6 +281,17 @@ struct ddp_hip_ctx {
   double ob_radius[DDP_HIP_MAX_COLLISION_POINTS] = {};
   int32_t ob_kind[DDP_HIP_MAX_OBSTACLES] = {};
   double* ob_clear_d = nullptr;               // [batch][T+1] what ddp_hip_obstacle_clearance hands back
+  // the voxel grid the slots of kind DDP_HIP_OBSTACLE_GRID read (ddp_hip_obstacle_set_grid / _set_occupancy, obstacle_grid.hip):
+  // two fields, the one in force (og_cur) and the one the next set call writes, so that a failed call leaves the old grid in force
+  // and a scene refreshed at the same shape allocates nothing
+  double* og_phi[2] = {nullptr, nullptr};     // [nx][ny][nz] each
+  int64_t og_cap[2] = {0, 0};                 // their sizes in doubles
+  int32_t og_cur = -1;                        // -1: no grid yet
+  int32_t og_n[3] = {};
+  double og_origin[3] = {}, og_cell = 0.0;
+  int32_t* og_d2 = nullptr;                   // [2][voxels] the transform's squared distances (D_occ, D_free), kept between calls
+  uint8_t* og_occ = nullptr;                  // [voxels] the occupancy as uploaded, kept likewise
+  int64_t og_tmp_cap = 0;                     // voxels the two hold
   // the self-collision spheres and the pairs of them (ddp_hip_self_collision_set_pairs)
   int32_t sc_np = 0, sc_npair = 0;            // spheres and pairs set (0: none yet)
   int32_t sc_joint[DDP_HIP_MAX_COLLISION_POINTS] = {};

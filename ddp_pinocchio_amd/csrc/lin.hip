@@ -737,6 +737,7 @@ __global__ __launch_bounds__(64) void lin_joint_accel_cost_kernel(LinParams p, J
 // with the columns of P_k formed from the staged axes and origins (rbd::obstacle_add_wave: points in ascending order, entry
 // (i, j) in (min, max) order, symmetric bit for bit).  It reads p.x and touches nothing but those entries.  No atomics.
 // t = T: lfx / lfxx
+template <bool GRID>
 __global__ __launch_bounds__(64) void lin_obstacle_cost_kernel(LinParams p, ObstacleCostDev ob) {
   const int64_t bt1 = blockIdx.x;
   const int n = (int)p.d.n;
@@ -752,7 +753,7 @@ __global__ __launch_bounds__(64) void lin_obstacle_cost_kernel(LinParams p, Obst
   if (tid < ob.np) {
     const double off[3] = {ob.off[tid][0], ob.off[tid][1], ob.off[tid][2]};
     rbd::frame_point(m, ff, ob.joint[tid], off, q, pk);
-    act = rbd::obstacle_point_reduce(ob, tid, pk, ob.geom + bt1 * ob.no * 4, w, g, M);
+    act = rbd::obstacle_point_reduce<GRID>(ob, tid, pk, ob.geom + bt1 * ob.no * 4, w, g, M);
   }
   const unsigned active = (unsigned)__ballot(act);                  // bit k: point k has an active pair
   if (active == 0) return;
@@ -1778,7 +1779,8 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       hipLaunchKernelGGL((lin_joint_accel_cost_kernel<DDP_HIP_MAX_JOINT_ACCEL_NV>), dim3((unsigned)BT), dim3(64), lds, ctx->stream, p, ja);
     }
-    add(ob.geom, lin_obstacle_cost_kernel, ob);
+    if (ob.grid_slots) add(ob.geom, lin_obstacle_cost_kernel<true>, ob);
+    else add(ob.geom, lin_obstacle_cost_kernel<false>, ob);
     add(sc.margin, lin_self_collision_cost_kernel, sc);
     add(cp.geom, lin_capsule_cost_kernel, cp);
   }

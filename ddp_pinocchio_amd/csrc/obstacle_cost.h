@@ -6,6 +6,7 @@
 #include "frame_walk.h"
 #include "internal.h"
 #include "lie.h"
+#include "obstacle_grid.h"
 #include "rbd.h"
 
 // What a kernel reads of the context's obstacle cost.  geom == nullptr: no terms (the flag is off, no points are set, or no
@@ -17,7 +18,18 @@ struct ObstacleCostDev {
   int32_t kind[DDP_HIP_MAX_OBSTACLES];
   double off[DDP_HIP_MAX_COLLISION_POINTS][3];
   double radius[DDP_HIP_MAX_COLLISION_POINTS];
+  ObstacleGridDev grid;            // what the slots of kind DDP_HIP_OBSTACLE_GRID read (phi == nullptr: no grid is resident)
+  bool grid_slots;                 // some slot is of that kind: the kernels' GRID instantiation runs
 };
+
+inline ObstacleGridDev obstacle_grid_dev(const ddp_hip_ctx* ctx) {
+  ObstacleGridDev g{};
+  if (ctx->og_cur < 0) return g;
+  g.phi = ctx->og_phi[ctx->og_cur];
+  g.cell = ctx->og_cell;
+  for (int a = 0; a < 3; ++a) { g.n[a] = ctx->og_n[a]; g.origin[a] = ctx->og_origin[a]; }
+  return g;
+}
 
 // always: the description whether or not a weight is live (ddp_hip_obstacle_clearance works from the first set_points on)
 inline ObstacleCostDev obstacle_cost_dev(const ddp_hip_ctx* ctx, bool always = false) {
@@ -33,7 +45,11 @@ inline ObstacleCostDev obstacle_cost_dev(const ddp_hip_ctx* ctx, bool always = f
     c.radius[k] = ctx->ob_radius[k];
     for (int a = 0; a < 3; ++a) c.off[k][a] = ctx->ob_off[k][a];
   }
-  for (int o = 0; o < ctx->ob_no; ++o) c.kind[o] = ctx->ob_kind[o];
+  for (int o = 0; o < ctx->ob_no; ++o) {
+    c.kind[o] = ctx->ob_kind[o];
+    c.grid_slots |= ctx->ob_kind[o] == DDP_HIP_OBSTACLE_GRID;
+  }
+  c.grid = obstacle_grid_dev(ctx);
   return c;
 }
 
@@ -42,8 +58,13 @@ namespace rbd {
 // The signed distance d_ko of the sphere (p, r) on the robot to an obstacle slot, and the direction u_ko = dd / dp:
 //   sphere      g = (c, rho):  d = |p - c| - (r + rho),   u = (p - c) / |p - c|
 //   half-space  g = (n, h):    d = n . p - h - r,         u = n
-// Returns false where u does not exist (a sphere's centre at p: the pair has its value and no derivative)
-__device__ __forceinline__ bool obstacle_distance(int kind, const double* g, const double* p, double r, double* d, double* u) {
+//   grid        g = (s, m):    d = phi(p - s) - r - m,    u = grad phi(p - s)      (obstacle_grid.h; outside the grid d = +inf)
+// Returns false where u does not exist (a sphere's centre at p, a grid's zero gradient: the pair has its value and no derivative).
+// GRID: some slot may be a grid's.  The kernels are instantiated both ways and a context without a grid slot runs the instruction
+// stream it ran before the kind existed
+template <bool GRID>
+__device__ __forceinline__ bool obstacle_distance(const ObstacleCostDev& ob, int kind, const double* g, const double* p, double r, double* d, double* u) {
+  if (GRID && kind == DDP_HIP_OBSTACLE_GRID) return obstacle_grid_distance(ob.grid, g, p, r, d, u);
   if (kind == DDP_HIP_OBSTACLE_HALFSPACE) {
     *d = (g[0] * p[0] + g[1] * p[1] + g[2] * p[2]) - g[3] - r;
     u[0] = g[0]; u[1] = g[1]; u[2] = g[2];
@@ -63,6 +84,7 @@ __device__ __forceinline__ bool obstacle_active(double d) { return !(d >= 0.0); 
 
 // 1/2 sum_o w_o e_ko^2 of one point over the live slots in ascending order, the pairs with w == 0 or e == 0 left out; *active:
 // some pair took part.  The caller has found a live slot; a non-finite point gives NaN
+template <bool GRID>
 __device__ __forceinline__ double obstacle_point_term(const ObstacleCostDev& ob, int k, const double* p, const double* geom, const double* w,
                                                       bool* active) {
   double s = 0.0;
@@ -72,7 +94,7 @@ __device__ __forceinline__ double obstacle_point_term(const ObstacleCostDev& ob,
     const double wo = w[o];
     if (wo == 0.0) continue;
     double d, u[3];
-    (void)obstacle_distance(ob.kind[o], geom + 4 * o, p, ob.radius[k], &d, u);
+    (void)obstacle_distance<GRID>(ob, ob.kind[o], geom + 4 * o, p, ob.radius[k], &d, u);
     if (obstacle_active(d)) { s += wo * d * d; act = true; }
   }
   *active = act;
@@ -83,12 +105,13 @@ __device__ __forceinline__ double obstacle_point_term(const ObstacleCostDev& ob,
 __device__ __forceinline__ double obstacle_min(double a, double b) { return (a != a || b >= a) ? a : b; }
 
 // min_o d_ko of one point over the slots with w != 0 (+inf without one; NaN if any distance is)
+template <bool GRID>
 __device__ __forceinline__ double obstacle_point_clearance(const ObstacleCostDev& ob, int k, const double* p, const double* geom, const double* w) {
   double best = INFINITY;
   for (int o = 0; o < ob.no; ++o) {
     if (w[o] == 0.0) continue;
     double d, u[3];
-    (void)obstacle_distance(ob.kind[o], geom + 4 * o, p, ob.radius[k], &d, u);
+    (void)obstacle_distance<GRID>(ob, ob.kind[o], geom + 4 * o, p, ob.radius[k], &d, u);
     best = obstacle_min(best, d);
   }
   return best;
@@ -106,6 +129,7 @@ struct ObstacleWaveLds {
 
 // g_k and M_k of one point over its slots in ascending order, the pairs with w == 0 or e == 0 left out (and a sphere's centre at
 // p: no direction).  Returns whether any pair took part
+template <bool GRID>
 __device__ __forceinline__ bool obstacle_point_reduce(const ObstacleCostDev& ob, int k, const double* p, const double* geom, const double* w,
                                                       double* g, double* M) {
   bool act = false;
@@ -115,7 +139,7 @@ __device__ __forceinline__ bool obstacle_point_reduce(const ObstacleCostDev& ob,
     const double wo = w[o];
     if (wo == 0.0) continue;
     double d, u[3];
-    const bool has_u = obstacle_distance(ob.kind[o], geom + 4 * o, p, ob.radius[k], &d, u);
+    const bool has_u = obstacle_distance<GRID>(ob, ob.kind[o], geom + 4 * o, p, ob.radius[k], &d, u);
     if (!obstacle_active(d) || !has_u) continue;
     const double we = wo * d;
     g[0] += we * u[0]; g[1] += we * u[1]; g[2] += we * u[2];

@@ -287,12 +287,33 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * line-search candidate touches, a context computes bit for bit what it computes without the flag.  The data travels through
  * ddp_hip_obstacle_* below; at create no points are set and geometry and weights are 0.  Tree models only (the pendulum:
  * DDP_HIP_E_UNSUPPORTED).  The flag combines with every other flag: the terms are formed by kernels of their own, which add onto
- * what the other terms' kernels leave (last, after the frame velocities'). */
+ * what the other terms' kernels leave (last, after the frame velocities').
+ *
+ * A third slot kind, DDP_HIP_OBSTACLE_GRID, reads its distance from a voxel grid: a workspace as a depth camera sees it, which
+ * eight primitives cannot say.  The context holds at most one grid, shared by the batch and by every slot of the kind
+ * (ddp_hip_obstacle_set_grid takes a signed distance field, ddp_hip_obstacle_set_occupancy builds one on the device from occupancy
+ * voxels): dims (nx, ny, nz), 2 <= n_a <= DDP_HIP_MAX_GRID_DIM, origin[3] the world position of node (0, 0, 0), cell > 0 the node
+ * spacing on the three axes, and nx ny nz doubles phi[(ix ny + iy) nz + iz].  The slot's four doubles are geom = (shift s(3),
+ * margin m), all finite, m of either sign: every instance can see the scene displaced, and a scanned object can move with t.
+ * The distance is the trilinear interpolant and the direction its gradient:
+ *   s = (p_k - shift - origin) / cell (per axis);  inside iff 0 <= s_a <= n_a - 1 on the three axes
+ *   i_a = min(floor(s_a), n_a - 2),  f_a = s_a - i_a
+ *   phi(p)  = sum over the 8 corners c of phi[i + c] prod_a (c_a ? f_a : 1 - f_a)
+ *   grad_a  = (1 / cell) sum over the 8 corners c of phi[i + c] (c_a ? +1 : -1) prod_{b != a} (c_b ? f_b : 1 - f_b)
+ *   d_ko = phi(p_k) - r_k - m,   u_ko = grad phi(p_k)      (not normalised: it is dd/dp of this d)
+ * Outside the grid is free space: d = +inf, the pair forms nothing and ddp_hip_obstacle_clearance does not see it -- size the grid
+ * to the workspace and close it with half-space slots where that matters.  A gradient that is exactly zero has the pair's value
+ * and no derivative (the rule of a sphere's centre at p); a non-finite point is NaN as for the other kinds.  Everything else is
+ * the text above: e, z = P_k^T u, the pairs left out, the bit-for-bit rules.  A context whose slots are all spheres and
+ * half-spaces computes the same bits whether or not a grid is resident.  ddp_hip_advance shifts a grid slot's geom and weight
+ * rows like the others'; the grid itself is not a per-t table and stays. */
 #define DDP_HIP_FLAG_OBSTACLE_COST 512u
 #define DDP_HIP_MAX_COLLISION_POINTS 16
 #define DDP_HIP_MAX_OBSTACLES 8
 #define DDP_HIP_OBSTACLE_SPHERE 0
 #define DDP_HIP_OBSTACLE_HALFSPACE 1
+#define DDP_HIP_OBSTACLE_GRID 2
+#define DDP_HIP_MAX_GRID_DIM 256
 /* Say "do not run one part of the robot through another": pairs of spheres on the robot, a one-sided soft cost on their distance
  * -- "the hand stays out of the torso", "the knees do not cross".  Both ends of a pair move with q, which the obstacle flag cannot
  * express.  The flag stands alone: it needs no DDP_HIP_FLAG_OBSTACLE_COST and has its own spheres.  Spheres, shared by the batch,
@@ -636,21 +657,44 @@ int ddp_hip_frame_vel_download(ddp_hip_ctx* ctx, double* target, double* weight,
 /* The collision points and the obstacle slots of a context created with DDP_HIP_FLAG_OBSTACLE_COST (else DDP_HIP_E_UNSUPPORTED),
  * shared by the batch: joint[n_points], off[n_points][3], radius[n_points], kind[n_obstacles].  DDP_HIP_E_ARG for counts outside
  * 1 .. DDP_HIP_MAX_COLLISION_POINTS or 1 .. DDP_HIP_MAX_OBSTACLES, a joint outside the model, a non-finite offset, a negative or
- * non-finite radius, an unknown kind.  It may be called again: with the same two counts and the same kinds the per-instance data
- * stays (points may move, radii may change), otherwise geometry and weights are reset to 0. */
+ * non-finite radius, an unknown kind, and DDP_HIP_OBSTACLE_GRID while no grid is resident.  It may be called again: with the
+ * same two counts and the same kinds the per-instance data stays (points may move, radii may change), otherwise geometry and
+ * weights are reset to 0. */
 int ddp_hip_obstacle_set_points(ddp_hip_ctx* ctx, int32_t n_points, const int32_t* joint, const double* off, const double* radius,
                                 int32_t n_obstacles, const int32_t* kind);
 /* The obstacles' geometry and weights, stream-ordered like ddp_hip_com_cost_upload.  Host arrays [n_instances][T+1][n_obstacles][4]
  * and [n_instances][T+1][n_obstacles]; a NULL pointer leaves that side as it is.  An upload is refused as a whole (DDP_HIP_E_ARG,
  * nothing written) before ddp_hip_obstacle_set_points, for a bad instance range, a non-finite value, a negative weight, a negative
- * sphere radius and a half-space normal n with | |n| - 1 | > 1e-10.  A geom that arrives alone is checked against the slot kinds;
- * weights that arrive alone need no geometry check. */
+ * sphere radius and a half-space normal n with | |n| - 1 | > 1e-10 (a grid slot's shift and margin: finite).  A geom that
+ * arrives alone is checked against the slot kinds; weights that arrive alone need no geometry check. */
 int ddp_hip_obstacle_upload(ddp_hip_ctx* ctx, const double* geom, const double* weight, int64_t first_instance, int64_t n_instances);
 int ddp_hip_obstacle_download(ddp_hip_ctx* ctx, double* geom, double* weight, int64_t first_instance, int64_t n_instances);
 /* "Did the result collide, where, by how much": out[batch][T+1] (host) = min over the collision points and over the slots with
  * w != 0 of d_ko along X (which = 0) or X_NEW (which = 1), +inf where no slot is live.  From the first
  * ddp_hip_obstacle_set_points on (before: DDP_HIP_E_ARG), live weights or not. */
 int ddp_hip_obstacle_clearance(ddp_hip_ctx* ctx, int which, double* out);
+/* The grid of the slots of kind DDP_HIP_OBSTACLE_GRID, in a context created with DDP_HIP_FLAG_OBSTACLE_COST (else
+ * DDP_HIP_E_UNSUPPORTED).  set_grid takes a field made elsewhere, phi[nx][ny][nz] (host, C order).  set_occupancy takes voxels in
+ * the same index order, occ != 0 meaning occupied, and builds the field on the device by an exact Euclidean distance transform:
+ * with D_occ(v) (D_free(v)) the least squared index distance from voxel v to an occupied (a free) voxel, nx^2 + ny^2 + nz^2 where
+ * there is none,
+ *   phi(v) = +cell (sqrt(D_occ(v)) - 0.5) for a free v,   phi(v) = -cell (sqrt(D_free(v)) - 0.5) for an occupied v:
+ * the surface lies halfway between a free voxel's centre and its occupied neighbour's, and an all-free or all-occupied grid stays
+ * finite.  The squared distances are exact integers, so phi does not depend on how the transform is scheduled.  Either call may be
+ * repeated at any time between other calls, with other dims as well; the new grid replaces the old one for everything that runs
+ * afterwards (slots, their geometry and weights stay).  Both run on the context's stream and wait for it before they return.
+ * DDP_HIP_E_ARG for a NULL pointer, a dim outside 2 .. DDP_HIP_MAX_GRID_DIM, a non-finite origin, a cell that is not finite and
+ * positive and, for set_grid, a non-finite value of phi.  A refused call, and one that cannot allocate (DDP_HIP_E_HIP), leaves
+ * the old grid in force. */
+int ddp_hip_obstacle_set_grid(ddp_hip_ctx* ctx, const int32_t dims[3], const double origin[3], double cell, const double* phi);
+int ddp_hip_obstacle_set_occupancy(ddp_hip_ctx* ctx, const int32_t dims[3], const double origin[3], double cell, const uint8_t* occ);
+/* The resident grid: dims, origin, cell and, unless phi is NULL (shape only), the field.  Before any grid: DDP_HIP_E_ARG. */
+int ddp_hip_obstacle_grid_download(ddp_hip_ctx* ctx, int32_t dims[3], double origin[3], double* cell, double* phi);
+/* phi and (unless grad_out is NULL) grad phi of the resident grid at n world points (host, points[n][3]), by the device function
+ * the cost kernels use: +inf and a zero gradient outside the grid, NaN for a point with a NaN coordinate.  n >= 0.  Before any
+ * grid: DDP_HIP_E_ARG.  A diagnostic call, not one for a control loop: it allocates a device buffer of 7 n doubles and frees it
+ * before it returns (unlike the transform's temporaries, which the context keeps), and waits for the context's stream. */
+int ddp_hip_obstacle_grid_query(ddp_hip_ctx* ctx, int64_t n, const double* points, double* phi_out, double* grad_out);
 /* The spheres and the pairs of a context created with DDP_HIP_FLAG_SELF_COLLISION_COST (else DDP_HIP_E_UNSUPPORTED), shared by the
  * batch: joint[n_points], off[n_points][3], radius[n_points], pair_a[n_pairs], pair_b[n_pairs].  DDP_HIP_E_ARG for n_points
  * outside 2 .. DDP_HIP_MAX_COLLISION_POINTS, n_pairs outside 1 .. DDP_HIP_MAX_COLLISION_PAIRS, a joint outside the model, a
