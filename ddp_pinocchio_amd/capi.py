@@ -45,6 +45,7 @@ MAX_FRAME_PAIRS = 4
 MAX_AIM_FRAMES = 4
 MAX_CAPSULES, MAX_CAPSULE_PAIRS = 16, 32
 CAPSULE_VS_ROBOT, CAPSULE_VS_CAPSULE, CAPSULE_VS_HALFSPACE = 0, 1, 2
+CAPSULE_VS_GRID, CAPSULE_GRID_MAX_INTERVALS = 3, 32
 OBSTACLE_SPHERE, OBSTACLE_HALFSPACE = 0, 1
 OBSTACLE_GRID, MAX_GRID_DIM = 2, 256
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
@@ -83,6 +84,7 @@ EXPORTS = [
     "ddp_hip_frame_vel_upload", "ddp_hip_frame_vel_download", "ddp_hip_model_frame_velocity",
     "ddp_hip_obstacle_set_points", "ddp_hip_obstacle_upload", "ddp_hip_obstacle_download", "ddp_hip_obstacle_clearance",
     "ddp_hip_obstacle_set_grid", "ddp_hip_obstacle_set_occupancy", "ddp_hip_obstacle_grid_download", "ddp_hip_obstacle_grid_query",
+    "ddp_hip_obstacle_grid_segment_query",
     "ddp_hip_self_collision_set_pairs", "ddp_hip_self_collision_upload", "ddp_hip_self_collision_download",
     "ddp_hip_self_collision_clearance",
     "ddp_hip_momentum_cost_upload", "ddp_hip_momentum_cost_download", "ddp_hip_model_centroidal_momentum",
@@ -204,6 +206,8 @@ def lib():
         L.ddp_hip_obstacle_set_occupancy.argtypes = [C.c_void_p, _ip, _dp, C.c_double, C.POINTER(C.c_uint8)]
         L.ddp_hip_obstacle_grid_download.argtypes = [C.c_void_p, _ip, _dp, _dp, _dp]
         L.ddp_hip_obstacle_grid_query.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp]
+    if hasattr(L, "ddp_hip_obstacle_grid_segment_query"):      # (likewise: obstacle_grid_segment_query)
+        L.ddp_hip_obstacle_grid_segment_query.argtypes = [C.c_void_p, C.c_int64, _dp, _ip, _dp, _ip, _dp, _dp]
     if hasattr(L, "ddp_hip_self_collision_upload"):  # (likewise: set_self_collision_pairs, set_self_collision_cost, self_collision_clearance)
         L.ddp_hip_self_collision_set_pairs.argtypes = [C.c_void_p, C.c_int32, _ip, _dp, _dp, C.c_int32, _ip, _ip]
         L.ddp_hip_self_collision_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
@@ -949,7 +953,8 @@ class Context:
         return np.ascontiguousarray(field.shape, dtype=np.int32), origin, float(cell), np.ascontiguousarray(field, dtype=dtype)
 
     def set_obstacle_grid(self, phi, origin, cell):
-        """The signed distance field of the OBSTACLE_GRID slots (a context created with FLAG_OBSTACLE_COST; ddp_hip.h): phi of
+        """The signed distance field of the OBSTACLE_GRID slots and the CAPSULE_VS_GRID pairs (a context created with
+        FLAG_OBSTACLE_COST or FLAG_CAPSULE_COST; ddp_hip.h): phi of
         shape (nx, ny, nz), 2 <= n <= MAX_GRID_DIM, finite; origin the world position of node (0, 0, 0); cell > 0 the node
         spacing.  Replaces the resident grid, of whatever shape; waits for the context's stream"""
         dims, origin, cell, phi = self._grid_args("set_obstacle_grid", phi, origin, cell, np.float64)
@@ -985,6 +990,25 @@ class Context:
         val, g = np.zeros(n), (np.zeros((n, 3)) if grad else None)
         _check(lib().ddp_hip_obstacle_grid_query(self._h, n, _ptr(points), _ptr(val), _ptr(g) if grad else None), "obstacle_grid_query")
         return (val, g) if grad else val
+
+    def obstacle_grid_segment_query(self, segments, n_intervals):
+        """What the capsule cost sees along a limb: the rule of the CAPSULE_VS_GRID pairs (ddp_hip.h) on the world segments (n, 6)
+        = (a0, a1), the shift already taken off, with n_intervals (one number or (n,), 0 .. CAPSULE_GRID_MAX_INTERVALS) intervals
+        each, by the device routine the cost kernels use.  Returns (phi, j, point, grad): the least sample value (+inf: every
+        sample outside the grid), its index j* (-1: every sample outside), the sample point (n, 3) and the gradient there (n, 3)"""
+        segments = np.ascontiguousarray(segments, dtype=np.float64)
+        if segments.ndim != 2 or segments.shape[1] != 6:
+            raise ValueError(f"obstacle_grid_segment_query: segments is (n, 6), got {segments.shape}")
+        n = segments.shape[0]
+        if np.ndim(n_intervals) == 0:
+            n_intervals = np.full(n, int(n_intervals))
+        nint = np.ascontiguousarray(n_intervals, dtype=np.int32)
+        if nint.shape != (n,):
+            raise ValueError(f"obstacle_grid_segment_query: n_intervals is one number or ({n},), got {nint.shape}")
+        val, j, point, g = np.zeros(n), np.zeros(n, dtype=np.int32), np.zeros((n, 3)), np.zeros((n, 3))
+        _check(lib().ddp_hip_obstacle_grid_segment_query(self._h, n, _ptr(segments), nint.ctypes.data_as(_ip), _ptr(val), j.ctypes.data_as(_ip),
+                                                         _ptr(point), _ptr(g)), "obstacle_grid_segment_query")
+        return val, j, point, g
 
     def set_self_collision_pairs(self, points, pairs):
         """The spheres [(joint, off, radius), ...] (2 .. MAX_COLLISION_POINTS of them) and the pairs [(a, b), ...] of sphere indices
@@ -1034,7 +1058,8 @@ class Context:
         """The robot capsules [(joint, end0, end1, radius), ...] (1 .. MAX_CAPSULES of them; end0 == end1 is a sphere) and the
         pairs [(a, kind, b), ...] (up to MAX_CAPSULE_PAIRS) of a context created with FLAG_CAPSULE_COST (ddp_hip.h), shared by the
         batch: body A of a pair is capsule a, body B robot capsule b on another joint (CAPSULE_VS_ROBOT), or a world capsule
-        (CAPSULE_VS_CAPSULE) or a half-space (CAPSULE_VS_HALFSPACE) of the pair's own per-instance geometry; b is then not read
+        (CAPSULE_VS_CAPSULE) or a half-space (CAPSULE_VS_HALFSPACE) of the pair's own per-instance geometry, or the resident voxel
+        grid (CAPSULE_VS_GRID: set_obstacle_grid or set_obstacle_occupancy first, which such a context accepts); b is then not read
         and (a, kind) is accepted.  With the same counts and kinds as before the per-instance data stays, else it is reset to 0"""
         capsules, pairs = list(capsules), list(pairs)
         if any(len(c) != 4 for c in capsules) or any(len(p) not in (2, 3) for p in pairs):
@@ -1055,7 +1080,9 @@ class Context:
     def set_capsule_cost(self, geom=None, weight=None, first=0, count=None):
         """The capsule terms of instances first .. first + count - 1 (a context created with FLAG_CAPSULE_COST; ddp_hip.h), of the
         n_pairs pairs of set_capsule_pairs.  geom: eight doubles per pair, the last the margin -- (., ., ., ., ., ., ., m) of a
-        robot pair, (b0, b1, rho, m) of a world capsule, (n, h, ., ., ., m) of a half-space -- as (n_pairs, 8) for every instance
+        robot pair, (b0, b1, rho, m) of a world capsule, (n, h, ., ., ., m) of a half-space, (s, ., ., ., ., m) of a grid pair (the
+        shift s of the grid as for an OBSTACLE_GRID slot; the capsule is sampled at its N + 1 material points, N from its length and
+        the grid's cell, and the least trilinear value counts) -- as (n_pairs, 8) for every instance
         and t, (T+1, n_pairs, 8) for every instance or (count, T+1, n_pairs, 8); weight: >= 0, as (n_pairs,), (T+1, n_pairs) or
         (count, T+1, n_pairs).  None leaves that side as it is.  The pair count is the one this object last passed to
         set_capsule_pairs; before that call there is no shape to check against and the call raises ValueError."""

@@ -1,7 +1,8 @@
 // capsule_cost.h -- per-instance capsule collision costs (DDP_HIP_FLAG_CAPSULE_COST, ddp_hip.h): capsules on the robot against each
-// other, against per-instance world capsules and against half-spaces, a one-sided penalty on their distance.  First the
-// closest-point routine, which calls no HIP function and compiles for the host as well (in the manner of advance_plan.h:
-// host/test_capsule_block.cpp runs it alone); then, for the device compiler, the kernel-side description and the device helpers.
+// other, against per-instance world capsules, against half-spaces and against the context's voxel grid, a one-sided penalty on
+// their distance.  First the closest-point routines, which call no HIP function and compile for the host as well (in the manner of
+// advance_plan.h: host/test_capsule_block.cpp and host/test_capsule_grid_block.cpp run them alone); then, for the device compiler,
+// the kernel-side description and the device helpers.
 // The terms themselves are formed by kernels of their own in fwd.hip (cost values: capsule_cost_kernel, summed by com_sum_kernel;
 // clearances: capsule_clearance_kernel), lin.hip (derivatives: lin_capsule_cost_kernel) and model_api.hip (one pair:
 // model_capsule_pair_kernel).
@@ -9,6 +10,9 @@
 
 #include <math.h>
 #include <stdint.h>
+
+#include "../../include/ddp_hip/ddp_hip.h"
+#include "obstacle_grid.h"
 
 #if defined(__HIPCC__)
 #define CAP_HD __host__ __device__
@@ -68,6 +72,69 @@ CAP_HD static inline double capsule_halfspace_point(const double* a0, const doub
   return (second ? p1 : p0) - h;
 }
 
+// ---- a segment against the voxel grid (DDP_HIP_CAPSULE_VS_GRID, ddp_hip.h) --------------------------------------------------------
+// The number of intervals N of a robot capsule with the ends end0, end1 (joint frame) on a grid of spacing cell: 0 for a sphere,
+// else ceil(L / cell) kept within 1 .. DDP_HIP_CAPSULE_GRID_MAX_INTERVALS.  Host arithmetic in double, every product rounded on its
+// own (capsule_cost_dev calls it whenever a description is built: the state never enters)
+CAP_HD static inline int32_t capsule_grid_intervals(const double* end0, const double* end1, double cell) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double dx = end1[0] - end0[0], dy = end1[1] - end0[1], dz = end1[2] - end0[2];
+  const double L = sqrt(dx * dx + dy * dy + dz * dz);
+  if (L == 0.0) return 0;
+  const double r = ceil(L / cell);
+  if (!(r < (double)DDP_HIP_CAPSULE_GRID_MAX_INTERVALS)) return DDP_HIP_CAPSULE_GRID_MAX_INTERVALS;
+  return r < 1.0 ? 1 : (int32_t)r;
+}
+
+// Sample j of N: the material point c_j = a0 + (j / N) (a1 - a0) and the field there, phi_j and g_j at c_j - shift
+// (obstacle_grid_lookup as it is: +inf and a zero gradient outside, NaN for a NaN coordinate)
+CAP_HD static inline void capsule_grid_sample(const ObstacleGridDev& G, const double* a0, const double* a1, const double* shift, int32_t N, int32_t j,
+                                              double* c, double* phi, double* grad) {
+  const double sigma = N > 0 ? (double)j / (double)N : 0.0;
+  double x[3];
+  for (int k = 0; k < 3; ++k) {
+    c[k] = a0[k] + sigma * (a1[k] - a0[k]);
+    x[k] = c[k] - shift[k];
+  }
+  (void)obstacle_grid_lookup(G, x, phi, grad);
+}
+
+// The selection, one step of a scan in ascending j: does sample `phi` replace the best so far?  (first: there is none yet.)  A NaN
+// that has been taken stays, a NaN replaces everything else, otherwise the strictly smaller value: the smallest j wins a tie
+CAP_HD static inline bool capsule_grid_better(double phi, double best, bool first) {
+  if (first) return true;
+  if (best != best) return false;
+  return phi != phi || phi < best;
+}
+
+// The rule: over the samples j = 0 .. N the smallest j attaining min_j phi_j (the first NaN before everything).  *j = -1 and
+// *phi = +inf where every sample lies outside the grid (then c = a0, grad = 0); else c = c_j*, grad = g_j*.  The one definition
+// behind the value, clearance, derivative and query kernels: those that deal the samples over lanes use capsule_grid_sample and
+// capsule_grid_better, scan in ascending j and form point and gradient by capsule_grid_sample at j* again
+CAP_HD static inline void capsule_grid_closest(const ObstacleGridDev& G, const double* a0, const double* a1, const double* shift, int32_t N, double* phi,
+                                               int32_t* j, double* c, double* grad) {
+  double best = INFINITY;
+  int32_t bj = 0;
+  for (int32_t s = 0; s <= N; ++s) {
+    double cs[3], ps, gs[3];
+    capsule_grid_sample(G, a0, a1, shift, N, s, cs, &ps, gs);
+    if (capsule_grid_better(ps, best, s == 0)) { best = ps; bj = s; }
+  }
+  capsule_grid_sample(G, a0, a1, shift, N, best == INFINITY ? 0 : bj, c, phi, grad);
+  *j = best == INFINITY ? -1 : bj;
+}
+
+// d, c_a = c_b and u of a grid pair from the selected sample: false where the pair has no derivative (every sample outside:
+// d = +inf; a gradient of exactly zero)
+CAP_HD static inline bool capsule_grid_pair(double phi, const double* grad, double ra, double margin, double* d, double* u) {
+  u[0] = grad[0]; u[1] = grad[1]; u[2] = grad[2];
+  if (phi == INFINITY) { *d = INFINITY; return false; }
+  *d = phi - ra - margin;
+  return phi != phi || u[0] != 0.0 || u[1] != 0.0 || u[2] != 0.0;
+}
+
 #if defined(__HIPCC__)
 #include "frame_walk.h"
 #include "internal.h"
@@ -84,6 +151,12 @@ struct CapsuleCostDev {
   uint8_t pa[DDP_HIP_MAX_CAPSULE_PAIRS], kind[DDP_HIP_MAX_CAPSULE_PAIRS], pb[DDP_HIP_MAX_CAPSULE_PAIRS];   // pair i: capsule pa[i] against kind[i] (pb[i]: a robot pair's)
   double end[DDP_HIP_MAX_CAPSULES][2][3];
   double radius[DDP_HIP_MAX_CAPSULES];
+  // the pairs of kind DDP_HIP_CAPSULE_VS_GRID (behind everything else: a context without one reads what it read before the kind)
+  int32_t grid_pairs;                             // how many: != 0 runs the kernels' GRID instantiation
+  int32_t grid_items;                             // their samples in all: sum over them of nseg[pa] + 1
+  int32_t nseg[DDP_HIP_MAX_CAPSULES];             // N_k of capsule k on the resident grid (capsule_grid_intervals)
+  uint16_t gbase[DDP_HIP_MAX_CAPSULE_PAIRS];      // pair i of the kind: its first item (the others: not read)
+  ObstacleGridDev grid;                           // the resident field (phi == nullptr: none)
 };
 
 // always: the description whether or not a weight is live (ddp_hip_capsule_clearance works from the first set_pairs on)
@@ -106,6 +179,16 @@ inline CapsuleCostDev capsule_cost_dev(const ddp_hip_ctx* ctx, bool always = fal
     c.kind[i] = (uint8_t)ctx->cp_kind[i];
     c.pb[i] = (uint8_t)ctx->cp_pb[i];
   }
+  c.grid = obstacle_grid_dev(ctx);
+  if (c.grid.phi) {
+    for (int s = 0; s < ctx->cp_nc; ++s) c.nseg[s] = capsule_grid_intervals(ctx->cp_end[s][0], ctx->cp_end[s][1], c.grid.cell);
+    for (int i = 0; i < ctx->cp_npair; ++i) {
+      if (ctx->cp_kind[i] != DDP_HIP_CAPSULE_VS_GRID) continue;
+      c.gbase[i] = (uint16_t)c.grid_items;
+      c.grid_items += c.nseg[ctx->cp_pa[i]] + 1;
+      ++c.grid_pairs;
+    }
+  }
   return c;
 }
 
@@ -123,10 +206,20 @@ __device__ __forceinline__ void capsule_ends(const M& m, bool ff, const CapsuleC
 
 // The signed distance d_i of pair i, its closest points c_a, c_b and the direction u_i = dd / dc_a = -dd / dc_b.  a0, a1: the
 // world ends of body A; b0, b1: those of body B where it is a robot capsule (else not read); g: the pair's eight doubles.
-// Returns false where u does not exist (the closest points coincide: the pair has its value and no derivative)
+// Returns false where u does not exist (the closest points coincide: the pair has its value and no derivative).  GRID: some pair
+// may be a grid's (the whole scan on this lane: the kernels that deal the samples over lanes do not come here for such a pair).  The
+// kernels are instantiated both ways and a context without a grid pair runs the instruction stream it ran before the kind existed
+template <bool GRID>
 __device__ __forceinline__ bool capsule_distance(const CapsuleCostDev& cp, int i, const double* a0, const double* a1, const double* b0,
                                                  const double* b1, const double* g, double* d, double* ca, double* cb, double* u) {
   const double ra = cp.radius[cp.pa[i]], margin = g[7];
+  if (GRID && cp.kind[i] == DDP_HIP_CAPSULE_VS_GRID) {
+    double phi, grad[3];
+    int32_t j;
+    capsule_grid_closest(cp.grid, a0, a1, g, cp.nseg[cp.pa[i]], &phi, &j, ca, grad);
+    cb[0] = ca[0]; cb[1] = ca[1]; cb[2] = ca[2];
+    return capsule_grid_pair(phi, grad, ra, margin, d, u);
+  }
   if (cp.kind[i] == DDP_HIP_CAPSULE_VS_HALFSPACE) {
     *d = capsule_halfspace_point(a0, a1, g, g[3], ca) - ra - margin;
     cb[0] = ca[0]; cb[1] = ca[1]; cb[2] = ca[2];

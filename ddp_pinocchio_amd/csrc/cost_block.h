@@ -131,7 +131,8 @@ static inline bool cost_obstacle_geom_side(const CostCheck& c, const double* v, 
   return true;
 }
 // capsule pair geometry by pair kind, eight doubles: all finite (the last is the margin, the ignored ones too); a world capsule
-// (b0, b1, rho, m) has rho >= 0, a half-space (n, h, ., ., ., m) a unit normal by the obstacle half-spaces' rule
+// (b0, b1, rho, m) has rho >= 0, a half-space (n, h, ., ., ., m) a unit normal by the obstacle half-spaces' rule; a grid pair's
+// (s, ., ., ., ., m) needs no more than that
 static inline bool cost_capsule_geom_side(const CostCheck& c, const double* v, int64_t words) {
   for (int64_t i = 0; i < words / 8; ++i) {
     const double* g = v + 8 * i;
@@ -197,17 +198,27 @@ static inline bool cost_pair_list_ok(int32_t n_points, const int32_t* joint, int
 
 // a capsule pair list over n_capsules robot capsules (capsule k on joint[k]): body A in range, a known kind, and for a robot pair
 // body B in range, a != b and not both capsules on one joint (their distance is constant); pair_b of a world pair is not read.
-// Duplicate pairs are allowed
+// Duplicate pairs are allowed.  grid_resident: the context holds a voxel grid, which a pair of kind DDP_HIP_CAPSULE_VS_GRID needs (the
+// obstacle slots' rule)
 static inline bool cost_capsule_pairs_ok(int32_t n_capsules, const int32_t* joint, int32_t n_pairs, const int32_t* a, const int32_t* kind,
-                                         const int32_t* b) {
+                                         const int32_t* b, bool grid_resident) {
   for (int32_t i = 0; i < n_pairs; ++i) {
     if (a[i] < 0 || a[i] >= n_capsules) return false;
     if (kind[i] == DDP_HIP_CAPSULE_VS_CAPSULE || kind[i] == DDP_HIP_CAPSULE_VS_HALFSPACE) continue;
+    if (kind[i] == DDP_HIP_CAPSULE_VS_GRID) {
+      if (!grid_resident) return false;
+      continue;
+    }
     if (kind[i] != DDP_HIP_CAPSULE_VS_ROBOT) return false;
     if (b[i] < 0 || b[i] >= n_capsules) return false;
     if (a[i] == b[i] || joint[a[i]] == joint[b[i]]) return false;
   }
   return true;
+}
+// ... without a grid
+static inline bool cost_capsule_pairs_ok(int32_t n_capsules, const int32_t* joint, int32_t n_pairs, const int32_t* a, const int32_t* kind,
+                                         const int32_t* b) {
+  return cost_capsule_pairs_ok(n_capsules, joint, n_pairs, a, kind, b, false);
 }
 
 // a relative-frame pair list over a model of nj joints (pair i: base frame on joint ja[i], tip frame on jb[i]): joints in range,

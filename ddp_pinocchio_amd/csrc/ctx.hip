@@ -745,7 +745,7 @@ extern "C" int ddp_hip_capsule_set_pairs(ddp_hip_ctx* ctx, int32_t n_capsules, c
       if (!isfinite(end0[3 * k + a]) || !isfinite(end1[3 * k + a])) return DDP_HIP_E_ARG;
     if (!isfinite(radius[k]) || radius[k] < 0.0) return DDP_HIP_E_ARG;
   }
-  if (!cost_capsule_pairs_ok(n_capsules, joint, n_pairs, pair_a, pair_kind, pair_b)) return DDP_HIP_E_ARG;
+  if (!cost_capsule_pairs_ok(n_capsules, joint, n_pairs, pair_a, pair_kind, pair_b, ctx->og_cur >= 0)) return DDP_HIP_E_ARG;   // (a grid pair needs a grid)
   bool same = n_capsules == ctx->cp_nc && n_pairs == ctx->cp_npair;
   for (int i = 0; same && i < n_pairs; ++i) same = pair_kind[i] == ctx->cp_kind[i];
   if (!same) {

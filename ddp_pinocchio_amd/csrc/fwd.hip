@@ -1356,10 +1356,17 @@ __global__ __launch_bounds__(64) void self_collision_clearance_kernel(SelfCollis
 // the pair's geometry) and leave w d^2 of an active pair -- with MIN: d of a pair with w != 0 -- and a flag in LDS (s_term,
 // s_formed: 4 x DDP_HIP_MAX_CAPSULE_PAIRS each).  After a second barrier the group's first lane folds in ascending pair order: 1/2
 // the sum of the formed ones, or with MIN the rbd::obstacle_min of them all from +inf, and cost_pair_store writes the result.  A
-// state whose weights are all 0 is not walked
-template <bool MIN>
+// state whose weights are all 0 is not walked.
+// GRID (some pair is of kind DDP_HIP_CAPSULE_VS_GRID; the other instantiation is the code from before the kind): one lane running a
+// grid pair's up to 33 independent lookups of 8 doubles one after another is a latency chain, and a line-search round runs it for
+// every candidate.  So between the two steps the group's 16 lanes take the (grid pair, sample) items of the state in strides, item
+// `it` of the description's flat list (CapsuleCostDev::gbase) by lane it % 16, and leave phi of each in LDS (s_phi: 4 x
+// grid_items, dynamic).  After one more barrier the pair's own lane of step 2 scans its pair's values in ascending j
+// (capsule_grid_better: smallest j on a tie, the first NaN before everything), which no dealing can change, and forms d; the
+// value and the clearance need no gradient
+template <bool MIN, bool GRID>
 __device__ __forceinline__ void capsule_fold(const CapsuleCostDev& cp, const DevModel& m, double (*s_e)[2][3], double* s_term, int32_t* s_formed,
-                                             const double* xs, int64_t traj_stride, int64_t count, int32_t T1, int32_t nx, int32_t na,
+                                             double* s_phi, const double* xs, int64_t traj_stride, int64_t count, int32_t T1, int32_t nx, int32_t na,
                                              const int32_t* state, int32_t round, double* out, int32_t add) {
   constexpr int L = DDP_HIP_MAX_CAPSULES, NP = DDP_HIP_MAX_CAPSULE_PAIRS;
   const int tid = threadIdx.x, g = tid / L, k = tid % L;
@@ -1369,6 +1376,20 @@ __device__ __forceinline__ void capsule_fold(const CapsuleCostDev& cp, const Dev
   const bool live = pr.live && rbd::weights_any(w, cp.npair);
   if (live && k < cp.nc) rbd::capsule_ends(m, m.ff != 0, cp, k, xs + pr.traj * traj_stride + (int64_t)pr.t * nx, s_e[tid]);
   __syncthreads();
+  if constexpr (GRID) {
+    int i = 0;                                                       // the grid pair that holds item `it` (it only grows)
+    for (int it = k; it < cp.grid_items; it += L) {
+      while (cp.kind[i] != DDP_HIP_CAPSULE_VS_GRID || it >= cp.gbase[i] + cp.nseg[cp.pa[i]] + 1) ++i;
+      double phi = INFINITY;
+      if (live && w[i] != 0.0) {
+        const double (*ea)[3] = s_e[g * L + cp.pa[i]];
+        double c[3], grad[3];
+        capsule_grid_sample(cp.grid, ea[0], ea[1], cp.geom + (pr.bt1 * cp.npair + i) * 8, cp.nseg[cp.pa[i]], it - cp.gbase[i], c, &phi, grad);
+      }
+      s_phi[g * cp.grid_items + it] = phi;
+    }
+    __syncthreads();
+  }
   for (int i = k; i < NP; i += L) {
     double term = MIN ? INFINITY : 0.0;
     bool formed = false;
@@ -1376,7 +1397,16 @@ __device__ __forceinline__ void capsule_fold(const CapsuleCostDev& cp, const Dev
       const double (*ea)[3] = s_e[g * L + cp.pa[i]];
       const double (*eb)[3] = s_e[g * L + cp.pb[i]];
       double d, ca[3], cb[3], u[3];
-      (void)rbd::capsule_distance(cp, i, ea[0], ea[1], eb[0], eb[1], cp.geom + (pr.bt1 * cp.npair + i) * 8, &d, ca, cb, u);
+      if (GRID && cp.kind[i] == DDP_HIP_CAPSULE_VS_GRID) {
+        const double* ph = s_phi + g * cp.grid_items + cp.gbase[i];
+        double best = ph[0];
+        for (int j = 1; j <= cp.nseg[cp.pa[i]]; ++j)
+          if (capsule_grid_better(ph[j], best, false)) best = ph[j];
+        u[0] = u[1] = u[2] = 0.0;
+        (void)capsule_grid_pair(best, u, cp.radius[cp.pa[i]], cp.geom[(pr.bt1 * cp.npair + i) * 8 + 7], &d, u);
+      } else {
+        (void)rbd::capsule_distance<false>(cp, i, ea[0], ea[1], eb[0], eb[1], cp.geom + (pr.bt1 * cp.npair + i) * 8, &d, ca, cb, u);
+      }
       if (MIN) { term = d; formed = true; }
       else if (rbd::obstacle_active(d)) { term = w[i] * d * d; formed = true; }
     }
@@ -1399,23 +1429,26 @@ __device__ __forceinline__ void capsule_fold(const CapsuleCostDev& cp, const Dev
 // the same list, the same two uses (add != 0: out[pair] += term behind cost_kernel; add == 0: out[pair] = term, the candidates'
 // array in a line-search round, with the candidates the rollout kernels skip skipped here).  A pair of bodies with w == 0 or
 // e == 0 is left out, and a state without an active pair adds nothing (add != 0) or stores +0 (add == 0).  A non-finite state
-// gives a NaN term, as com_cost_kernel's does
+// gives a NaN term, as com_cost_kernel's does.  GRID: 4 x grid_items doubles of dynamic LDS
+extern __shared__ double s_capsule_phi[];
+template <bool GRID>
 __global__ __launch_bounds__(64) void capsule_cost_kernel(CapsuleCostDev cp, const DevModel* model, const double* xs, int64_t traj_stride,
                                                           int64_t count, int32_t T1, int32_t nx, int32_t na, const int32_t* state,
                                                           int32_t round, double* out, int32_t add) {
   __shared__ double s_e[64][2][3], s_term[4 * DDP_HIP_MAX_CAPSULE_PAIRS];
   __shared__ int32_t s_act[4 * DDP_HIP_MAX_CAPSULE_PAIRS];
-  capsule_fold<false>(cp, *model, s_e, s_term, s_act, xs, traj_stride, count, T1, nx, na, state, round, out, add);
+  capsule_fold<false, GRID>(cp, *model, s_e, s_term, s_act, GRID ? s_capsule_phi : nullptr, xs, traj_stride, count, T1, nx, na, state, round, out, add);
 }
 
 // ddp_hip_capsule_clearance: the same layout over the `count` (instance, t) pairs of one resident trajectory (a list of one-state
 // trajectories, no candidates to skip), min instead of sum: out[pair] = min over the capsule pairs with w != 0 of d_i, +inf where
 // none is live, NaN where a distance is NaN
+template <bool GRID>
 __global__ __launch_bounds__(64) void capsule_clearance_kernel(CapsuleCostDev cp, const DevModel* model, const double* xs, int64_t count,
                                                                int32_t nx, double* out) {
   __shared__ double s_e[64][2][3], s_min[4 * DDP_HIP_MAX_CAPSULE_PAIRS];
   __shared__ int32_t s_live[4 * DDP_HIP_MAX_CAPSULE_PAIRS];
-  capsule_fold<true>(cp, *model, s_e, s_min, s_live, xs, nx, count, 1, nx, 1, nullptr, 0, out, 0);
+  capsule_fold<true, GRID>(cp, *model, s_e, s_min, s_live, GRID ? s_capsule_phi : nullptr, xs, nx, count, 1, nx, 1, nullptr, 0, out, 0);
 }
 
 // accept rule (ddp_fwd.ipp:56-60): the first (= largest) candidate with sum(new - old) <= 0; the winner's
@@ -1693,8 +1726,16 @@ static void launch_obstacle_cost(ddp_hip_ctx* ctx, const double* xs, const doubl
 static void launch_self_collision_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   launch_add_on(self_collision_cost_kernel, self_collision_dev(ctx), DDP_HIP_MAX_COLLISION_POINTS, ctx, xs, na, count, state, round, out, add);
 }
+// dynamic LDS of the capsule kernels' GRID instantiation: phi of every (grid pair, sample) item of the wave's four states (at most
+// 4 x 32 x 33 doubles = 33 KB)
+static size_t capsule_grid_lds(const CapsuleCostDev& cp) { return sizeof(double) * (size_t)((64 / DDP_HIP_MAX_CAPSULES) * cp.grid_items); }
 static void launch_capsule_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
-  launch_add_on(capsule_cost_kernel, capsule_cost_dev(ctx), DDP_HIP_MAX_CAPSULES, ctx, xs, na, count, state, round, out, add);
+  const CapsuleCostDev cp = capsule_cost_dev(ctx);
+  if (!cp.grid_pairs) { launch_add_on(capsule_cost_kernel<false>, cp, DDP_HIP_MAX_CAPSULES, ctx, xs, na, count, state, round, out, add); return; }
+  const Dims& d = ctx->d;
+  const int64_t per = 64 / DDP_HIP_MAX_CAPSULES;                      // (launch_add_on's launch with the samples' LDS)
+  hipLaunchKernelGGL(capsule_cost_kernel<true>, dim3((unsigned)((count + per - 1) / per)), dim3(64), capsule_grid_lds(cp), ctx->stream, cp, ctx->model_d,
+                     xs, (d.T + 1) * d.nx, count, (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, state, (int32_t)round, out, (int32_t)add);
 }
 
 // The terms formed out of line, in the fixed order of their additions (after everything cost_kernel / the rollout kernels form
@@ -1785,7 +1826,8 @@ extern "C" int ddp_hip_capsule_clearance(ddp_hip_ctx* ctx, int which, double* ou
   const CapsuleCostDev cp = capsule_cost_dev(ctx, true);
   const int64_t total = ctx->d.batch * (ctx->d.T + 1);
   const int64_t per = 64 / DDP_HIP_MAX_CAPSULES;
-  hipLaunchKernelGGL(capsule_clearance_kernel, dim3((unsigned)((total + per - 1) / per)), dim3(64), 0, ctx->stream, cp, ctx->model_d,
+  hipLaunchKernelGGL(cp.grid_pairs ? capsule_clearance_kernel<true> : capsule_clearance_kernel<false>, dim3((unsigned)((total + per - 1) / per)), dim3(64),
+                     cp.grid_pairs ? capsule_grid_lds(cp) : 0, ctx->stream, cp, ctx->model_d,
                      which == 0 ? p.x_old : p.x_new, total, (int32_t)ctx->d.nx, ctx->cp_clear_d);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, ctx->cp_clear_d, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));

@@ -851,8 +851,15 @@ __global__ __launch_bounds__(64) void lin_self_collision_cost_kernel(LinParams p
 // The wave adds over the union of the masks alone
 //   lx[c] += sum_i (w e)_i z_i[c],     lxx[r][c] += sum_i w_i z_i[min] z_i[max]     (Gauss-Newton)
 // (rbd::capsule_add_wave: pairs in ascending order, z formed on the fly at the closest points frozen in their joints, symmetric bit
-// for bit).  It reads p.x and touches nothing but those entries.  No atomics.  t = T: lfx / lfxx
+// for bit).  It reads p.x and touches nothing but those entries.  No atomics.  t = T: lfx / lfxx.
+// GRID (some pair is of kind DDP_HIP_CAPSULE_VS_GRID; the other instantiation is the code from before the kind): the capsules' lanes
+// leave their ends in LDS, and the wave's 64 lanes take the (grid pair, sample) items of the description's flat list in strides
+// and leave phi of each in LDS (the pairs with w == 0 are not looked up).  After a barrier a grid pair's own lane scans its values
+// in ascending j (capsule_grid_better: smallest j on a tie, the first NaN before everything -- whatever the dealing) and forms the
+// point and the gradient at j* by the sample routine again: the same bits as the scan on one lane (capsule_grid_closest).  The
+// vote and everything behind it are as before
 static_assert(sizeof(LinParams) + sizeof(CapsuleCostDev) <= 4096, "the kernel's arguments must fit the kernarg segment");
+template <bool GRID>
 __global__ __launch_bounds__(64) void lin_capsule_cost_kernel(LinParams p, CapsuleCostDev cp) {
   const int64_t bt1 = blockIdx.x;
   const int n = (int)p.d.n;
@@ -873,10 +880,47 @@ __global__ __launch_bounds__(64) void lin_capsule_cost_kernel(LinParams p, Capsu
   const double b1[3] = {__shfl(e[1][0], ib), __shfl(e[1][1], ib), __shfl(e[1][2], ib)};
   double d = 0.0, ca[3] = {0.0, 0.0, 0.0}, cb[3] = {0.0, 0.0, 0.0}, u[3] = {0.0, 0.0, 0.0}, wi = 0.0;
   bool act = false;
+  [[maybe_unused]] const double* s_phi_of = nullptr;
+  if constexpr (GRID) {
+    __shared__ double s_e[DDP_HIP_MAX_CAPSULES][2][3];
+    __shared__ double s_phi[DDP_HIP_MAX_CAPSULE_PAIRS * (DDP_HIP_CAPSULE_GRID_MAX_INTERVALS + 1)];
+    if (tid < cp.nc) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) { s_e[tid][0][a] = e[0][a]; s_e[tid][1][a] = e[1][a]; }
+    }
+    __syncthreads();
+    int i = 0;                                                       // the grid pair that holds item `it` (it only grows)
+    for (int it = tid; it < cp.grid_items; it += (int)blockDim.x) {
+      while (cp.kind[i] != DDP_HIP_CAPSULE_VS_GRID || it >= cp.gbase[i] + cp.nseg[cp.pa[i]] + 1) ++i;
+      double phi = INFINITY;
+      if (w[i] != 0.0) {
+        double c[3], grad[3];
+        capsule_grid_sample(cp.grid, s_e[cp.pa[i]][0], s_e[cp.pa[i]][1], cp.geom + (bt1 * cp.npair + i) * 8, cp.nseg[cp.pa[i]], it - cp.gbase[i], c, &phi, grad);
+      }
+      s_phi[it] = phi;
+    }
+    __syncthreads();
+    s_phi_of = s_phi;
+  }
   if (pair_lane) {
     wi = w[tid];
     if (wi != 0.0) {
-      const bool has_u = rbd::capsule_distance(cp, tid, a0, a1, b0, b1, cp.geom + (bt1 * cp.npair + tid) * 8, &d, ca, cb, u);
+      const double* g = cp.geom + (bt1 * cp.npair + tid) * 8;
+      bool has_u;
+      if (GRID && cp.kind[tid] == DDP_HIP_CAPSULE_VS_GRID) {
+        const double* ph = s_phi_of + cp.gbase[tid];
+        const int N = cp.nseg[ia];
+        double best = ph[0], phi, grad[3] = {0.0, 0.0, 0.0};
+        int bj = 0;
+        for (int j = 1; j <= N; ++j)
+          if (capsule_grid_better(ph[j], best, false)) { best = ph[j]; bj = j; }
+        phi = best;
+        if (best != INFINITY) capsule_grid_sample(cp.grid, a0, a1, g, N, bj, ca, &phi, grad);
+        cb[0] = ca[0]; cb[1] = ca[1]; cb[2] = ca[2];
+        has_u = capsule_grid_pair(phi, grad, cp.radius[ia], g[7], &d, u);
+      } else {
+        has_u = rbd::capsule_distance<false>(cp, tid, a0, a1, b0, b1, g, &d, ca, cb, u);
+      }
       act = rbd::obstacle_active(d) && has_u;
     }
   }
@@ -1782,7 +1826,8 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     if (ob.grid_slots) add(ob.geom, lin_obstacle_cost_kernel<true>, ob);
     else add(ob.geom, lin_obstacle_cost_kernel<false>, ob);
     add(sc.margin, lin_self_collision_cost_kernel, sc);
-    add(cp.geom, lin_capsule_cost_kernel, cp);
+    if (cp.grid_pairs) add(cp.geom, lin_capsule_cost_kernel<true>, cp);
+    else add(cp.geom, lin_capsule_cost_kernel<false>, cp);
   }
   // the q- / v-caches of the mode-2 stencil also serve the first order (base configuration and base (q, v)), so they are built
   // ahead of whichever stage comes first

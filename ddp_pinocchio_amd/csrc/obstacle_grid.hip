@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 
+#include "capsule_cost.h"
 #include "internal.h"
 #include "obstacle_cost.h"
 
@@ -105,9 +106,47 @@ __global__ __launch_bounds__(EDT_THREADS) void obstacle_grid_query_kernel(Obstac
   if (grad) { grad[3 * i] = g[0]; grad[3 * i + 1] = g[1]; grad[3 * i + 2] = g[2]; }
 }
 
+// ddp_hip_obstacle_grid_segment_query: the rule of the capsule pairs of kind DDP_HIP_CAPSULE_VS_GRID (capsule_cost.h), SEG_LANES lanes
+// per segment as the cost kernels deal a pair's samples: lane k looks up the samples k, k + 16, k + 32 and leaves phi in LDS; the
+// group's first lane scans them in ascending j and forms point and gradient at j* by the sample routine again
+static constexpr int SEG_LANES = 16;
+__global__ __launch_bounds__(EDT_THREADS) void obstacle_grid_segment_query_kernel(ObstacleGridDev G, int64_t n, const double* seg, const int32_t* nint,
+                                                                                  double* val, int32_t* jout, double* point, double* grad) {
+  constexpr int PER = EDT_THREADS / SEG_LANES, NS = DDP_HIP_CAPSULE_GRID_MAX_INTERVALS + 1;
+  __shared__ double s_phi[PER][NS];
+  const int g = threadIdx.x / SEG_LANES, k = threadIdx.x % SEG_LANES;
+  const int64_t i = (int64_t)blockIdx.x * PER + g;
+  const bool valid = i < n;
+  const double zero[3] = {0.0, 0.0, 0.0};
+  double a0[3] = {0.0, 0.0, 0.0}, a1[3] = {0.0, 0.0, 0.0};
+  int32_t N = 0;
+  if (valid) {
+    for (int a = 0; a < 3; ++a) { a0[a] = seg[6 * i + a]; a1[a] = seg[6 * i + 3 + a]; }
+    N = nint[i];
+    for (int j = k; j <= N; j += SEG_LANES) {
+      double c[3], gj[3];
+      capsule_grid_sample(G, a0, a1, zero, N, j, c, &s_phi[g][j], gj);
+    }
+  }
+  __syncthreads();
+  if (!valid || k != 0) return;
+  double best = s_phi[g][0];
+  int32_t bj = 0;
+  for (int32_t j = 1; j <= N; ++j)
+    if (capsule_grid_better(s_phi[g][j], best, false)) { best = s_phi[g][j]; bj = j; }
+  double c[3], phi, gj[3];
+  capsule_grid_sample(G, a0, a1, zero, N, best == INFINITY ? 0 : bj, c, &phi, gj);
+  val[i] = phi;
+  if (jout) jout[i] = best == INFINITY ? -1 : bj;
+  for (int a = 0; a < 3; ++a) {
+    if (point) point[3 * i + a] = c[a];
+    if (grad) grad[3 * i + a] = gj[a];
+  }
+}
+
 static int grid_entry_check(const ddp_hip_ctx* ctx) {
   if (!ctx) return DDP_HIP_E_ARG;
-  if (!(ctx->flags & DDP_HIP_FLAG_OBSTACLE_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (!(ctx->flags & (DDP_HIP_FLAG_OBSTACLE_COST | DDP_HIP_FLAG_CAPSULE_COST))) return DDP_HIP_E_UNSUPPORTED;   // (grid slots, grid pairs)
   return DDP_HIP_OK;
 }
 
@@ -214,6 +253,36 @@ extern "C" int ddp_hip_obstacle_grid_query(ddp_hip_ctx* ctx, int64_t n, const do
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(phi_out, val, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && grad_out) e = hipMemcpyAsync(grad_out, grad, sizeof(double) * (size_t)(3 * n), hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(buf);
+  if (e != hipSuccess || es != hipSuccess) { (void)hipGetLastError(); return DDP_HIP_E_HIP; }
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_obstacle_grid_segment_query(ddp_hip_ctx* ctx, int64_t n, const double* seg, const int32_t* n_intervals, double* phi_out,
+                                                   int32_t* j_out, double* point_out, double* grad_out) {
+  { const int rc = grid_entry_check(ctx); if (rc != DDP_HIP_OK) return rc; }
+  if (n < 0 || ctx->og_cur < 0 || (n > 0 && (!seg || !n_intervals || !phi_out))) return DDP_HIP_E_ARG;
+  for (int64_t i = 0; i < n; ++i)
+    if (n_intervals[i] < 0 || n_intervals[i] > DDP_HIP_CAPSULE_GRID_MAX_INTERVALS) return DDP_HIP_E_ARG;
+  if (n == 0) return DDP_HIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  double* buf = nullptr;                                                     // segments | values | points | gradients | counts | j*
+  HIP_TRY(hipMalloc(&buf, sizeof(double) * (size_t)(13 * n) + sizeof(int32_t) * (size_t)(2 * n)));
+  double *val = buf + 6 * n, *point = buf + 7 * n, *grad = buf + 10 * n;
+  int32_t *nint = reinterpret_cast<int32_t*>(buf + 13 * n), *jd = nint + n;
+  hipError_t e = hipMemcpyAsync(buf, seg, sizeof(double) * (size_t)(6 * n), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(nint, n_intervals, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    constexpr int per = EDT_THREADS / SEG_LANES;
+    hipLaunchKernelGGL(obstacle_grid_segment_query_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(EDT_THREADS), 0, ctx->stream,
+                       obstacle_grid_dev(ctx), n, buf, nint, val, jd, point, grad);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(phi_out, val, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && j_out) e = hipMemcpyAsync(j_out, jd, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && point_out) e = hipMemcpyAsync(point_out, point, sizeof(double) * (size_t)(3 * n), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess && grad_out) e = hipMemcpyAsync(grad_out, grad, sizeof(double) * (size_t)(3 * n), hipMemcpyDeviceToHost, ctx->stream);
   const hipError_t es = hipStreamSynchronize(ctx->stream);
   (void)hipFree(buf);

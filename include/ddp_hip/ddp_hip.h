@@ -586,13 +586,39 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * neither the trajectory nor any line-search candidate brings within their margin, a context computes bit for bit what it
  * computes without the flag.  The data travels through ddp_hip_capsule_* below; at create no pairs are set and geometry and
  * weights are 0.  Tree models only (the pendulum: DDP_HIP_E_UNSUPPORTED).  The flag combines with every other flag: the terms are
- * formed by kernels of their own, which add onto what the other terms' kernels leave (last, after self-collision's). */
+ * formed by kernels of their own, which add onto what the other terms' kernels leave (last, after self-collision's).
+ *
+ * A fourth pair kind, DDP_HIP_CAPSULE_VS_GRID, reads the context's voxel grid (ddp_hip_obstacle_set_grid / _set_occupancy, which a
+ * context created with this flag accepts as well): "keep the forearm out of the scanned shelf" without a string of spheres.
+ *   DDP_HIP_CAPSULE_VS_GRID       B is the resident signed distance field: geom = (shift s(3), ., ., ., ., m), all eight finite,
+ *                                 entries 3 .. 6 ignored; shift and margin mean what they mean for a DDP_HIP_OBSTACLE_GRID slot
+ * The segment of body A is sampled at N_k + 1 material points, N_k fixed by the capsule and the resident grid, not by the state:
+ *   L_k = sqrt(dx^2 + dy^2 + dz^2) of end1_k - end0_k in the joint's frame (host, double, each product rounded on its own)
+ *   N_k = 0 if L_k == 0 (a sphere), else min(DDP_HIP_CAPSULE_GRID_MAX_INTERVALS, max(1, (int)ceil(L_k / cell)))
+ * recomputed whenever the description is built for a launch: a new grid needs no second ddp_hip_capsule_set_pairs.  With a0, a1
+ * the world ends of body A:
+ *   sigma_j = (double)j / (double)N, j = 0 .. N (sigma_0 = 0 when N = 0),   c_j = a0 + sigma_j (a1 - a0),   x_j = c_j - s,
+ *   (phi_j, g_j) = the trilinear lookup of DDP_HIP_OBSTACLE_GRID at x_j (obstacle_grid_lookup), +inf outside the grid
+ *   j* = the smallest j attaining min_j phi_j; a NaN sample wins over everything, the first NaN taken
+ *   every sample outside: d_i = +inf, the pair forms nothing and ddp_hip_capsule_clearance does not see it (the grid slot's rule)
+ *   otherwise d_i = phi_j* - r_a - m,   c_a = c_b = c_j*,   u_i = g_j* (not normalised: it is dd / dp of this d)
+ * (capsule_grid_intervals, capsule_grid_closest in csrc/capsule_cost.h, host and device).  e, the cost and the "left out" rules
+ * are those above.  c_j* is frozen in A's joint, so the pair is a world pair: all of path(A) carries + P_{c_a}^T u, a free-flyer
+ * root's six columns included; u == 0 exactly means value and no derivative; lxx is Gauss-Newton in (min, max) order, pairs
+ * ascending.  There is no sub-sample refinement: the term is the minimum over N + 1 material points of the trilinear field, a
+ * piecewise-smooth function whose exact derivative (where the argmin is unique) is the frozen-point one, so the line search's
+ * values and the lineariser's derivatives agree without an envelope argument; a refinement would claim accuracy below a cell,
+ * which the field does not have.  For a 1-Lipschitz field the continuous minimum along the segment is at least
+ * min_j phi_j - L_k / (2 N_k): a caller who wants a bound puts that into the margin.  A capsule with L_k > 32 cell is sampled
+ * coarser than the grid.  ddp_hip_capsule_set_pairs accepts the kind only while a grid is resident. */
 #define DDP_HIP_FLAG_CAPSULE_COST 131072u
 #define DDP_HIP_MAX_CAPSULES 16
 #define DDP_HIP_MAX_CAPSULE_PAIRS 32
 #define DDP_HIP_CAPSULE_VS_ROBOT 0      /* the other body is a robot capsule */
 #define DDP_HIP_CAPSULE_VS_CAPSULE 1    /* ... a world capsule of the pair's own, per instance and t */
 #define DDP_HIP_CAPSULE_VS_HALFSPACE 2  /* ... a half-space, per instance and t */
+#define DDP_HIP_CAPSULE_VS_GRID 3       /* ... the context's voxel grid (ddp_hip_obstacle_set_grid / _set_occupancy) */
+#define DDP_HIP_CAPSULE_GRID_MAX_INTERVALS 32
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -673,8 +699,8 @@ int ddp_hip_obstacle_download(ddp_hip_ctx* ctx, double* geom, double* weight, in
  * w != 0 of d_ko along X (which = 0) or X_NEW (which = 1), +inf where no slot is live.  From the first
  * ddp_hip_obstacle_set_points on (before: DDP_HIP_E_ARG), live weights or not. */
 int ddp_hip_obstacle_clearance(ddp_hip_ctx* ctx, int which, double* out);
-/* The grid of the slots of kind DDP_HIP_OBSTACLE_GRID, in a context created with DDP_HIP_FLAG_OBSTACLE_COST (else
- * DDP_HIP_E_UNSUPPORTED).  set_grid takes a field made elsewhere, phi[nx][ny][nz] (host, C order).  set_occupancy takes voxels in
+/* The grid of the slots of kind DDP_HIP_OBSTACLE_GRID and of the capsule pairs of kind DDP_HIP_CAPSULE_VS_GRID, in a context
+ * created with DDP_HIP_FLAG_OBSTACLE_COST or DDP_HIP_FLAG_CAPSULE_COST (with neither: DDP_HIP_E_UNSUPPORTED).  set_grid takes a field made elsewhere, phi[nx][ny][nz] (host, C order).  set_occupancy takes voxels in
  * the same index order, occ != 0 meaning occupied, and builds the field on the device by an exact Euclidean distance transform:
  * with D_occ(v) (D_free(v)) the least squared index distance from voxel v to an occupied (a free) voxel, nx^2 + ny^2 + nz^2 where
  * there is none,
@@ -695,6 +721,14 @@ int ddp_hip_obstacle_grid_download(ddp_hip_ctx* ctx, int32_t dims[3], double ori
  * grid: DDP_HIP_E_ARG.  A diagnostic call, not one for a control loop: it allocates a device buffer of 7 n doubles and frees it
  * before it returns (unlike the transform's temporaries, which the context keeps), and waits for the context's stream. */
 int ddp_hip_obstacle_grid_query(ddp_hip_ctx* ctx, int64_t n, const double* points, double* phi_out, double* grad_out);
+/* "What does the capsule cost see along this limb": the rule of DDP_HIP_CAPSULE_VS_GRID on n world segments (host, seg[n][6] =
+ * (a0, a1), the shift already taken off) with n_intervals[n] intervals each, 0 .. DDP_HIP_CAPSULE_GRID_MAX_INTERVALS, by the device
+ * routine the cost kernels use (capsule_grid_closest), one segment per lane group.  phi_out[n] = min_j phi_j (+inf: every sample
+ * outside; NaN: a NaN sample), j_out[n] = j* (-1: every sample outside), point_out[n][3] = c_j*, grad_out[n][3] = g_j* (where
+ * every sample is outside: the point a0 and a zero gradient); the last three may be NULL.  Refusals are those of
+ * ddp_hip_obstacle_grid_query, and DDP_HIP_E_ARG for an interval count out of range.  A diagnostic call like that one. */
+int ddp_hip_obstacle_grid_segment_query(ddp_hip_ctx* ctx, int64_t n, const double* seg, const int32_t* n_intervals, double* phi_out,
+                                        int32_t* j_out, double* point_out, double* grad_out);
 /* The spheres and the pairs of a context created with DDP_HIP_FLAG_SELF_COLLISION_COST (else DDP_HIP_E_UNSUPPORTED), shared by the
  * batch: joint[n_points], off[n_points][3], radius[n_points], pair_a[n_pairs], pair_b[n_pairs].  DDP_HIP_E_ARG for n_points
  * outside 2 .. DDP_HIP_MAX_COLLISION_POINTS, n_pairs outside 1 .. DDP_HIP_MAX_COLLISION_PAIRS, a joint outside the model, a
@@ -788,8 +822,8 @@ int ddp_hip_joint_accel(ddp_hip_ctx* ctx, int which, double* out);
  * batch: joint[n_capsules], end0[n_capsules][3], end1[n_capsules][3], radius[n_capsules], pair_a[n_pairs], pair_kind[n_pairs],
  * pair_b[n_pairs] (read for DDP_HIP_CAPSULE_VS_ROBOT pairs alone).  DDP_HIP_E_ARG for n_capsules outside
  * 1 .. DDP_HIP_MAX_CAPSULES, n_pairs outside 1 .. DDP_HIP_MAX_CAPSULE_PAIRS, a joint outside the model, a non-finite end, a
- * negative or non-finite radius, a capsule index outside the capsules, an unknown kind, and a robot pair with a == b or with both
- * capsules on the same joint (their distance is constant).  Duplicate pairs are allowed.  It may be called again: with the same
+ * negative or non-finite radius, a capsule index outside the capsules, an unknown kind, DDP_HIP_CAPSULE_VS_GRID while no grid is
+ * resident, and a robot pair with a == b or with both capsules on the same joint (their distance is constant).  Duplicate pairs are allowed.  It may be called again: with the same
  * two counts and the same kinds the per-instance data stays (capsules may move, radii may change, a pair may name other capsules),
  * otherwise geometry and weights are reset to 0. */
 int ddp_hip_capsule_set_pairs(ddp_hip_ctx* ctx, int32_t n_capsules, const int32_t* joint, const double* end0, const double* end1,
