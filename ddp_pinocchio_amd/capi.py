@@ -46,6 +46,7 @@ MAX_AIM_FRAMES = 4
 MAX_CAPSULES, MAX_CAPSULE_PAIRS = 16, 32
 CAPSULE_VS_ROBOT, CAPSULE_VS_CAPSULE, CAPSULE_VS_HALFSPACE = 0, 1, 2
 CAPSULE_VS_GRID, CAPSULE_GRID_MAX_INTERVALS = 3, 32
+CAPSULE_VS_BOX, MAX_CAPSULE_BOXES = 4, 8
 OBSTACLE_SPHERE, OBSTACLE_HALFSPACE = 0, 1
 OBSTACLE_GRID, MAX_GRID_DIM = 2, 256
 LIN_COST, LIN_FIRST, LIN_SECOND, LIN_EQ = 1, 2, 4, 8
@@ -97,7 +98,7 @@ EXPORTS = [
     "ddp_hip_balance_region_margin", "ddp_hip_model_capture_point",
     "ddp_hip_joint_accel_cost_upload", "ddp_hip_joint_accel_cost_download", "ddp_hip_joint_accel",
     "ddp_hip_capsule_set_pairs", "ddp_hip_capsule_upload", "ddp_hip_capsule_download", "ddp_hip_capsule_clearance",
-    "ddp_hip_model_capsule_pair",
+    "ddp_hip_model_capsule_pair", "ddp_hip_capsule_set_boxes", "ddp_hip_model_capsule_box",
     "ddp_hip_advance",
 ]
 
@@ -208,6 +209,9 @@ def lib():
         L.ddp_hip_obstacle_grid_query.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp]
     if hasattr(L, "ddp_hip_obstacle_grid_segment_query"):      # (likewise: obstacle_grid_segment_query)
         L.ddp_hip_obstacle_grid_segment_query.argtypes = [C.c_void_p, C.c_int64, _dp, _ip, _dp, _ip, _dp, _dp]
+    if hasattr(L, "ddp_hip_capsule_set_boxes"):      # (likewise: set_capsule_boxes, ModelHandle.capsule_box)
+        L.ddp_hip_capsule_set_boxes.argtypes = [C.c_void_p, C.c_int32, _dp]
+        L.ddp_hip_model_capsule_box.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
     if hasattr(L, "ddp_hip_self_collision_upload"):  # (likewise: set_self_collision_pairs, set_self_collision_cost, self_collision_clearance)
         L.ddp_hip_self_collision_set_pairs.argtypes = [C.c_void_p, C.c_int32, _ip, _dp, _dp, C.c_int32, _ip, _ip]
         L.ddp_hip_self_collision_upload.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, C.c_int64]
@@ -475,6 +479,19 @@ class ModelHandle:
         _check(lib().ddp_hip_model_capsule_pair(self._h, int(joint_a), _ptr(a0), _ptr(a1), int(joint_b), _ptr(b0), _ptr(b1), _ptr(q), _ptr(D),
                                                 _ptr(ca), _ptr(cb), _ptr(J) if jacobian else None), "model_capsule_pair")
         return (float(D[0]), ca, cb, J) if jacobian else (float(D[0]), ca, cb)
+
+    def capsule_box(self, joint, a0, a1, radius, half, pose, q, gradient=False):
+        """One robot capsule against one oriented box at q, as CAPSULE_VS_BOX defines it (ddp_hip.h), by the device routine the cost
+        kernels use: the segment a0 .. a1 fixed in `joint` with `radius`, the box of half extents half (3,) at pose (7,) = (centre,
+        unit quaternion x y z w).  (d, s, ca, u): the signed distance with margin 0, the segment parameter, the closest point on the
+        segment axis in the world and u = dd / dc_a; with gradient=True (d, s, ca, u, grad), grad = P_ca^T u as (nv,)"""
+        a0, a1, half, pose, q = _f64(a0), _f64(a1), _f64(half), _f64(pose), _f64(q)
+        if any(e.shape != (3,) for e in (a0, a1, half)) or pose.shape != (7,):
+            raise ValueError("capsule_box: a0, a1 and half are 3-vectors, pose is (centre, quaternion x y z w)")
+        d, s, ca, u, g = np.zeros(1), np.zeros(1), np.zeros(3), np.zeros(3), np.zeros(self.nv)
+        _check(lib().ddp_hip_model_capsule_box(self._h, int(joint), _ptr(a0), _ptr(a1), float(radius), _ptr(half), _ptr(pose), _ptr(q), _ptr(d),
+                                               _ptr(s), _ptr(ca), _ptr(u), _ptr(g) if gradient else None), "model_capsule_box")
+        return (float(d[0]), float(s[0]), ca, u, g) if gradient else (float(d[0]), float(s[0]), ca, u)
 
     def capture_point(self, q, v, tau, jacobian=False):
         """The test point xi = c + tau cdot of FLAG_BALANCE_REGION_COST (ddp_hip.h) at the state (q, v) as (3,): the centre of mass
@@ -1060,7 +1077,8 @@ class Context:
         batch: body A of a pair is capsule a, body B robot capsule b on another joint (CAPSULE_VS_ROBOT), or a world capsule
         (CAPSULE_VS_CAPSULE) or a half-space (CAPSULE_VS_HALFSPACE) of the pair's own per-instance geometry, or the resident voxel
         grid (CAPSULE_VS_GRID: set_obstacle_grid or set_obstacle_occupancy first, which such a context accepts); b is then not read
-        and (a, kind) is accepted.  With the same counts and kinds as before the per-instance data stays, else it is reset to 0"""
+        and (a, kind) is accepted.  Or an oriented box (CAPSULE_VS_BOX: b is the index of a shape of set_capsule_boxes, called
+        first; the pose is the pair's own per-instance geometry).  With the same counts and kinds as before the per-instance data stays, else it is reset to 0"""
         capsules, pairs = list(capsules), list(pairs)
         if any(len(c) != 4 for c in capsules) or any(len(p) not in (2, 3) for p in pairs):
             raise ValueError("set_capsule_pairs: every capsule is (joint, (x, y, z), (x, y, z), radius), every pair (a, kind, b)")
@@ -1077,12 +1095,20 @@ class Context:
                                                pa.ctypes.data_as(_ip), kind.ctypes.data_as(_ip), pb.ctypes.data_as(_ip)), "capsule_set_pairs")
         self.n_capsule_pairs = len(pa)
 
+    def set_capsule_boxes(self, half):
+        """The box shapes of the CAPSULE_VS_BOX pairs (a context created with FLAG_CAPSULE_COST; ddp_hip.h), shared by the batch: half
+        of shape (n_boxes, 3), 0 .. MAX_CAPSULE_BOXES rows, the half extents along the box's own axes, each finite and > 0.  It may be
+        called again (extents may change while the pairs stand), but not so as to leave a box pair without its shape"""
+        half = np.ascontiguousarray(half, dtype=np.float64).reshape(-1, 3)
+        _check(lib().ddp_hip_capsule_set_boxes(self._h, half.shape[0], _ptr(half) if half.size else None), "capsule_set_boxes")
+
     def set_capsule_cost(self, geom=None, weight=None, first=0, count=None):
         """The capsule terms of instances first .. first + count - 1 (a context created with FLAG_CAPSULE_COST; ddp_hip.h), of the
         n_pairs pairs of set_capsule_pairs.  geom: eight doubles per pair, the last the margin -- (., ., ., ., ., ., ., m) of a
         robot pair, (b0, b1, rho, m) of a world capsule, (n, h, ., ., ., m) of a half-space, (s, ., ., ., ., m) of a grid pair (the
         shift s of the grid as for an OBSTACLE_GRID slot; the capsule is sampled at its N + 1 material points, N from its length and
-        the grid's cell, and the least trilinear value counts) -- as (n_pairs, 8) for every instance
+        the grid's cell, and the least trilinear value counts), (c, quaternion x y z w, m) of a box pair (the box's centre and its axes
+        in the world, a unit quaternion) -- as (n_pairs, 8) for every instance
         and t, (T+1, n_pairs, 8) for every instance or (count, T+1, n_pairs, 8); weight: >= 0, as (n_pairs,), (T+1, n_pairs) or
         (count, T+1, n_pairs).  None leaves that side as it is.  The pair count is the one this object last passed to
         set_capsule_pairs; before that call there is no shape to check against and the call raises ValueError."""

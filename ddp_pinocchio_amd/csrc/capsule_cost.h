@@ -1,11 +1,11 @@
 // capsule_cost.h -- per-instance capsule collision costs (DDP_HIP_FLAG_CAPSULE_COST, ddp_hip.h): capsules on the robot against each
-// other, against per-instance world capsules, against half-spaces and against the context's voxel grid, a one-sided penalty on
-// their distance.  First the closest-point routines, which call no HIP function and compile for the host as well (in the manner of
-// advance_plan.h: host/test_capsule_block.cpp and host/test_capsule_grid_block.cpp run them alone); then, for the device compiler,
+// other, against per-instance world capsules, against half-spaces, against the context's voxel grid and against oriented boxes, a one-sided
+// penalty on their distance.  First the closest-point routines, which call no HIP function and compile for the host as well (in the manner of
+// advance_plan.h: host/test_capsule_block.cpp, host/test_capsule_grid_block.cpp and host/test_capsule_box_block.cpp run them alone); then, for the device compiler,
 // the kernel-side description and the device helpers.
 // The terms themselves are formed by kernels of their own in fwd.hip (cost values: capsule_cost_kernel, summed by com_sum_kernel;
 // clearances: capsule_clearance_kernel), lin.hip (derivatives: lin_capsule_cost_kernel) and model_api.hip (one pair:
-// model_capsule_pair_kernel).
+// model_capsule_pair_kernel, model_capsule_box_kernel).
 #pragma once
 
 #include <math.h>
@@ -16,8 +16,10 @@
 
 #if defined(__HIPCC__)
 #define CAP_HD __host__ __device__
+#define CAP_UNROLL _Pragma("unroll")
 #else
 #define CAP_HD
+#define CAP_UNROLL
 #endif
 
 CAP_HD static inline double capsule_clamp01(double x) { return x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x); }
@@ -135,6 +137,173 @@ CAP_HD static inline bool capsule_grid_pair(double phi, const double* grad, doub
   return phi != phi || u[0] != 0.0 || u[1] != 0.0 || u[2] != 0.0;
 }
 
+// ---- a segment against an oriented box (DDP_HIP_CAPSULE_VS_BOX, ddp_hip.h) --------------------------------------------------------
+// The box's signed distance at p (box axes, half extents h): the length of the part of |p| - h above 0 where that is > 0, else the
+// largest of |p_k| - h_k (<= 0: on or inside); NaN where a coordinate is
+CAP_HD static inline double capsule_box_phi(double p0, double p1, double p2, const double* h) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double q0 = fabs(p0) - h[0], q1 = fabs(p1) - h[1], q2 = fabs(p2) - h[2];
+  if (q0 != q0 || q1 != q1 || q2 != q2) return NAN;
+  const double e0 = q0 > 0.0 ? q0 : 0.0, e1 = q1 > 0.0 ? q1 : 0.0, e2 = q2 > 0.0 ? q2 : 0.0;
+  const double o = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
+  if (o > 0.0) return o;
+  double m = q0;
+  if (q1 > m) m = q1;
+  if (q2 > m) m = q2;
+  return m;
+}
+
+// What a search over the candidates carries: segment and box in box axes, the best candidate so far and, where that is a crossing
+// of two of the six face lines, which two (else -1)
+struct CapsuleBoxSearch {
+  double a[3], dl[3], h[3];
+  double s, f;
+  int32_t li, lj;
+  bool first;
+};
+// One candidate, in the order met: replaces the best only if strictly smaller (capsule_grid_better: the first NaN before everything)
+CAP_HD static inline void capsule_box_try(CapsuleBoxSearch& B, double s, int32_t li, int32_t lj) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double f = capsule_box_phi(B.a[0] + s * B.dl[0], B.a[1] + s * B.dl[1], B.a[2] + s * B.dl[2], B.h);
+  if (capsule_grid_better(f, B.f, B.first)) { B.f = f; B.s = s; B.li = li; B.lj = lj; }
+  B.first = false;
+}
+
+// The rule of ddp_hip.h: the least signed distance f* of the box (half extents h, pose = centre(3) | quaternion x y z w, world =
+// R box) along the segment a0 .. a1, the smallest parameter s* attaining it among the candidates, the point c_a = a0 + s* (a1 - a0)
+// and the direction u = df* / dc_a, all in the world.  phi is convex, so f(s) = phi(p(s)) is convex on [0, 1] and on each
+// sub-interval between two breakpoints (where p crosses a face plane) it is one smooth piece: outside the box the distance to one
+// face, edge or corner (stationary point of a quadratic), inside the largest of six lines (a minimum only where two cross).  The
+// candidates therefore hold the exact minimum.  The sub-intervals are walked in ascending order by taking the least breakpoint above
+// the last one: the same candidates in the same order as after a sort, but for equal breakpoints, whose empty intervals add none.
+// No array is indexed by a run-time value (on the device: registers only).  A quaternion of all zeros (fresh geometry, which no
+// upload accepts) gives R = identity by the formula: the box is evaluated with its axes along the world's.
+CAP_HD static inline double capsule_box_closest(const double* a0, const double* a1, const double* half, const double* pose, double* s_out, double* ca,
+                                                double* u) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double x = pose[3], y = pose[4], z = pose[5], w = pose[6];
+  const double R[3][3] = {{1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w), 2.0 * (x * z + y * w)},
+                          {2.0 * (x * y + z * w), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w)},
+                          {2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y)}};
+  const double ra[3] = {a0[0] - pose[0], a0[1] - pose[1], a0[2] - pose[2]}, rb[3] = {a1[0] - pose[0], a1[1] - pose[1], a1[2] - pose[2]};
+  CapsuleBoxSearch B;
+  double bp[3][2];                                                   // the breakpoints of axis k at +h_k and -h_k (2: none)
+CAP_UNROLL
+  for (int k = 0; k < 3; ++k) {
+    B.a[k] = R[0][k] * ra[0] + R[1][k] * ra[1] + R[2][k] * ra[2];
+    const double bk = R[0][k] * rb[0] + R[1][k] * rb[1] + R[2][k] * rb[2];
+    B.dl[k] = bk - B.a[k];
+    B.h[k] = half[k];
+    const double sp = (B.h[k] - B.a[k]) / B.dl[k], sm = (-B.h[k] - B.a[k]) / B.dl[k];
+    bp[k][0] = B.dl[k] != 0.0 && sp > 0.0 && sp < 1.0 ? sp : 2.0;
+    bp[k][1] = B.dl[k] != 0.0 && sm > 0.0 && sm < 1.0 ? sm : 2.0;
+  }
+  B.s = 0.0; B.f = 0.0; B.li = -1; B.lj = -1; B.first = true;
+  // the six lines l_i(s) = +-p_k(s) - h_k, i = 2 k + (0: +, 1: -): value at 0 and slope
+  const double c0[6] = {B.a[0] - B.h[0], -B.a[0] - B.h[0], B.a[1] - B.h[1], -B.a[1] - B.h[1], B.a[2] - B.h[2], -B.a[2] - B.h[2]};
+  const double m0[6] = {B.dl[0], -B.dl[0], B.dl[1], -B.dl[1], B.dl[2], -B.dl[2]};
+  double lo = 0.0;
+  for (int it = 0; it < 7 && lo < 1.0; ++it) {
+    double hi = 1.0;
+CAP_UNROLL
+    for (int k = 0; k < 3; ++k) {
+      if (bp[k][0] > lo && bp[k][0] < hi) hi = bp[k][0];
+      if (bp[k][1] > lo && bp[k][1] < hi) hi = bp[k][1];
+    }
+    const double mid = 0.5 * (lo + hi);
+    capsule_box_try(B, lo, -1, -1);
+    double A = 0.0, C = 0.0;
+    bool outside = false;
+CAP_UNROLL
+    for (int k = 0; k < 3; ++k) {
+      const double pm = B.a[k] + mid * B.dl[k];
+      const double sg = pm > B.h[k] ? 1.0 : (pm < -B.h[k] ? -1.0 : 0.0);
+      if (sg != 0.0) {
+        outside = true;
+        A = A + B.dl[k] * B.dl[k];
+        C = C + B.dl[k] * (B.a[k] - sg * B.h[k]);
+      }
+    }
+    if (outside) {
+      const double s = -C / A;
+      if (A > 0.0 && s > lo && s < hi) capsule_box_try(B, s, -1, -1);
+    } else {
+CAP_UNROLL
+      for (int i = 0; i < 5; ++i)
+CAP_UNROLL
+        for (int j = i + 1; j < 6; ++j) {
+          if (m0[i] == m0[j]) continue;
+          const double s = (c0[j] - c0[i]) / (m0[i] - m0[j]);
+          if (s > lo && s < hi) capsule_box_try(B, s, i, j);
+        }
+    }
+    capsule_box_try(B, hi, -1, -1);
+    lo = hi;
+  }
+  // the direction in box axes
+  const double sb = B.s, fb = B.f;
+  double p[3], n[3] = {0.0, 0.0, 0.0};
+CAP_UNROLL
+  for (int k = 0; k < 3; ++k) p[k] = B.a[k] + sb * B.dl[k];
+  bool kink = false;
+  if (!(fb > 0.0) && B.li >= 0) {
+    double mi = 0.0, mj = 0.0;
+CAP_UNROLL
+    for (int i = 0; i < 6; ++i) {
+      if (i == B.li) mi = m0[i];
+      if (i == B.lj) mj = m0[i];
+    }
+    if ((mi > 0.0 && mj < 0.0) || (mi < 0.0 && mj > 0.0)) {
+      kink = true;
+      const double ai = fabs(mi), aj = fabs(mj), den = ai + aj;
+CAP_UNROLL
+      for (int i = 0; i < 6; ++i) {
+        const double sgn = (i & 1) ? -1.0 : 1.0;
+        if (i == B.li) n[i >> 1] = n[i >> 1] + sgn * aj;
+        if (i == B.lj) n[i >> 1] = n[i >> 1] + sgn * ai;
+      }
+      n[0] = n[0] / den; n[1] = n[1] / den; n[2] = n[2] / den;
+    }
+  }
+  if (fb > 0.0) {
+CAP_UNROLL
+    for (int k = 0; k < 3; ++k) {
+      const double cl = p[k] < -B.h[k] ? -B.h[k] : (p[k] > B.h[k] ? B.h[k] : p[k]);
+      n[k] = (p[k] - cl) / fb;
+    }
+  } else if (!kink) {
+    // the first of the six lines that attains the largest value at s* (a NaN coordinate: line 0, and d is NaN)
+    const double l[6] = {p[0] - B.h[0], -p[0] - B.h[0], p[1] - B.h[1], -p[1] - B.h[1], p[2] - B.h[2], -p[2] - B.h[2]};
+    double best = l[0];
+    int32_t bi = 0;
+CAP_UNROLL
+    for (int i = 1; i < 6; ++i)
+      if (l[i] > best) { best = l[i]; bi = i; }
+CAP_UNROLL
+    for (int i = 0; i < 6; ++i)
+      if (i == bi) n[i >> 1] = (i & 1) ? -1.0 : 1.0;
+  }
+CAP_UNROLL
+  for (int k = 0; k < 3; ++k) {
+    ca[k] = a0[k] + sb * (a1[k] - a0[k]);
+    u[k] = R[k][0] * n[0] + R[k][1] * n[1] + R[k][2] * n[2];
+  }
+  *s_out = sb;
+  return fb;
+}
+
+// d and whether the pair has a derivative (f* == 0 exactly: value only, the D == 0 rule of the segment kinds; a NaN is active)
+CAP_HD static inline bool capsule_box_pair(double f, double ra, double margin, double* d) {
+  *d = f - ra - margin;
+  return f != 0.0;
+}
+
 #if defined(__HIPCC__)
 #include "frame_walk.h"
 #include "internal.h"
@@ -157,6 +326,9 @@ struct CapsuleCostDev {
   int32_t nseg[DDP_HIP_MAX_CAPSULES];             // N_k of capsule k on the resident grid (capsule_grid_intervals)
   uint16_t gbase[DDP_HIP_MAX_CAPSULE_PAIRS];      // pair i of the kind: its first item (the others: not read)
   ObstacleGridDev grid;                           // the resident field (phi == nullptr: none)
+  // the pairs of kind DDP_HIP_CAPSULE_VS_BOX (behind everything else again); pb[i] of such a pair is its shape
+  int32_t box_pairs;                              // how many: != 0 runs the kernels' BOX instantiation
+  double half[DDP_HIP_MAX_CAPSULE_BOXES][3];      // the half extents of the box shapes (ddp_hip_capsule_set_boxes)
 };
 
 // always: the description whether or not a weight is live (ddp_hip_capsule_clearance works from the first set_pairs on)
@@ -189,6 +361,9 @@ inline CapsuleCostDev capsule_cost_dev(const ddp_hip_ctx* ctx, bool always = fal
       ++c.grid_pairs;
     }
   }
+  for (int i = 0; i < ctx->cp_npair; ++i) c.box_pairs += ctx->cp_kind[i] == DDP_HIP_CAPSULE_VS_BOX;
+  for (int s = 0; s < ctx->cp_nbox; ++s)
+    for (int a = 0; a < 3; ++a) c.half[s][a] = ctx->cp_half[s][a];
   return c;
 }
 
@@ -208,8 +383,9 @@ __device__ __forceinline__ void capsule_ends(const M& m, bool ff, const CapsuleC
 // world ends of body A; b0, b1: those of body B where it is a robot capsule (else not read); g: the pair's eight doubles.
 // Returns false where u does not exist (the closest points coincide: the pair has its value and no derivative).  GRID: some pair
 // may be a grid's (the whole scan on this lane: the kernels that deal the samples over lanes do not come here for such a pair).  The
-// kernels are instantiated both ways and a context without a grid pair runs the instruction stream it ran before the kind existed
-template <bool GRID>
+// kernels are instantiated both ways and a context without a grid pair runs the instruction stream it ran before the kind existed.
+// BOX: some pair may be a box's, likewise (one evaluation of capsule_box_closest on the pair's own lane: g = centre, quaternion, m)
+template <bool GRID, bool BOX>
 __device__ __forceinline__ bool capsule_distance(const CapsuleCostDev& cp, int i, const double* a0, const double* a1, const double* b0,
                                                  const double* b1, const double* g, double* d, double* ca, double* cb, double* u) {
   const double ra = cp.radius[cp.pa[i]], margin = g[7];
@@ -219,6 +395,12 @@ __device__ __forceinline__ bool capsule_distance(const CapsuleCostDev& cp, int i
     capsule_grid_closest(cp.grid, a0, a1, g, cp.nseg[cp.pa[i]], &phi, &j, ca, grad);
     cb[0] = ca[0]; cb[1] = ca[1]; cb[2] = ca[2];
     return capsule_grid_pair(phi, grad, ra, margin, d, u);
+  }
+  if (BOX && cp.kind[i] == DDP_HIP_CAPSULE_VS_BOX) {
+    double s;
+    const double f = capsule_box_closest(a0, a1, cp.half[cp.pb[i]], g, &s, ca, u);
+    cb[0] = ca[0]; cb[1] = ca[1]; cb[2] = ca[2];
+    return capsule_box_pair(f, ra, margin, d);
   }
   if (cp.kind[i] == DDP_HIP_CAPSULE_VS_HALFSPACE) {
     *d = capsule_halfspace_point(a0, a1, g, g[3], ca) - ra - margin;

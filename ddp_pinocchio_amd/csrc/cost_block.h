@@ -132,7 +132,7 @@ static inline bool cost_obstacle_geom_side(const CostCheck& c, const double* v, 
 }
 // capsule pair geometry by pair kind, eight doubles: all finite (the last is the margin, the ignored ones too); a world capsule
 // (b0, b1, rho, m) has rho >= 0, a half-space (n, h, ., ., ., m) a unit normal by the obstacle half-spaces' rule; a grid pair's
-// (s, ., ., ., ., m) needs no more than that
+// (s, ., ., ., ., m) needs no more than that; a box pair's (c, quaternion x y z w, m) has a unit quaternion by cost_quat_ok
 static inline bool cost_capsule_geom_side(const CostCheck& c, const double* v, int64_t words) {
   for (int64_t i = 0; i < words / 8; ++i) {
     const double* g = v + 8 * i;
@@ -143,6 +143,8 @@ static inline bool cost_capsule_geom_side(const CostCheck& c, const double* v, i
       if (g[6] < 0.0) return false;
     } else if (kind == DDP_HIP_CAPSULE_VS_HALFSPACE) {
       if (fabs(sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) - 1.0) > 1e-10) return false;
+    } else if (kind == DDP_HIP_CAPSULE_VS_BOX) {
+      if (!cost_quat_ok(g[3] * g[3] + g[4] * g[4] + g[5] * g[5] + g[6] * g[6])) return false;
     }
   }
   return true;
@@ -197,16 +199,22 @@ static inline bool cost_pair_list_ok(int32_t n_points, const int32_t* joint, int
 }
 
 // a capsule pair list over n_capsules robot capsules (capsule k on joint[k]): body A in range, a known kind, and for a robot pair
-// body B in range, a != b and not both capsules on one joint (their distance is constant); pair_b of a world pair is not read.
+// body B in range, a != b and not both capsules on one joint (their distance is constant); pair_b of a world pair is not read
+// (a box pair's is its shape).
 // Duplicate pairs are allowed.  grid_resident: the context holds a voxel grid, which a pair of kind DDP_HIP_CAPSULE_VS_GRID needs (the
-// obstacle slots' rule)
+// obstacle slots' rule).  n_boxes: the box shapes set, of which a pair of kind DDP_HIP_CAPSULE_VS_BOX names one by b (with none set every
+// such pair is refused)
 static inline bool cost_capsule_pairs_ok(int32_t n_capsules, const int32_t* joint, int32_t n_pairs, const int32_t* a, const int32_t* kind,
-                                         const int32_t* b, bool grid_resident) {
+                                         const int32_t* b, bool grid_resident, int32_t n_boxes) {
   for (int32_t i = 0; i < n_pairs; ++i) {
     if (a[i] < 0 || a[i] >= n_capsules) return false;
     if (kind[i] == DDP_HIP_CAPSULE_VS_CAPSULE || kind[i] == DDP_HIP_CAPSULE_VS_HALFSPACE) continue;
     if (kind[i] == DDP_HIP_CAPSULE_VS_GRID) {
       if (!grid_resident) return false;
+      continue;
+    }
+    if (kind[i] == DDP_HIP_CAPSULE_VS_BOX) {
+      if (b[i] < 0 || b[i] >= n_boxes) return false;
       continue;
     }
     if (kind[i] != DDP_HIP_CAPSULE_VS_ROBOT) return false;
@@ -215,7 +223,12 @@ static inline bool cost_capsule_pairs_ok(int32_t n_capsules, const int32_t* join
   }
   return true;
 }
-// ... without a grid
+// ... without boxes
+static inline bool cost_capsule_pairs_ok(int32_t n_capsules, const int32_t* joint, int32_t n_pairs, const int32_t* a, const int32_t* kind,
+                                         const int32_t* b, bool grid_resident) {
+  return cost_capsule_pairs_ok(n_capsules, joint, n_pairs, a, kind, b, grid_resident, 0);
+}
+// ... and without a grid
 static inline bool cost_capsule_pairs_ok(int32_t n_capsules, const int32_t* joint, int32_t n_pairs, const int32_t* a, const int32_t* kind,
                                          const int32_t* b) {
   return cost_capsule_pairs_ok(n_capsules, joint, n_pairs, a, kind, b, false);

@@ -745,7 +745,7 @@ extern "C" int ddp_hip_capsule_set_pairs(ddp_hip_ctx* ctx, int32_t n_capsules, c
       if (!isfinite(end0[3 * k + a]) || !isfinite(end1[3 * k + a])) return DDP_HIP_E_ARG;
     if (!isfinite(radius[k]) || radius[k] < 0.0) return DDP_HIP_E_ARG;
   }
-  if (!cost_capsule_pairs_ok(n_capsules, joint, n_pairs, pair_a, pair_kind, pair_b, ctx->og_cur >= 0)) return DDP_HIP_E_ARG;   // (a grid pair needs a grid)
+  if (!cost_capsule_pairs_ok(n_capsules, joint, n_pairs, pair_a, pair_kind, pair_b, ctx->og_cur >= 0, ctx->cp_nbox)) return DDP_HIP_E_ARG;   // (a grid pair needs a grid, a box pair its box)
   bool same = n_capsules == ctx->cp_nc && n_pairs == ctx->cp_npair;
   for (int i = 0; same && i < n_pairs; ++i) same = pair_kind[i] == ctx->cp_kind[i];
   if (!same) {
@@ -764,8 +764,23 @@ extern "C" int ddp_hip_capsule_set_pairs(ddp_hip_ctx* ctx, int32_t n_capsules, c
   for (int i = 0; i < n_pairs; ++i) {
     ctx->cp_pa[i] = pair_a[i];
     ctx->cp_kind[i] = pair_kind[i];
-    ctx->cp_pb[i] = pair_kind[i] == DDP_HIP_CAPSULE_VS_ROBOT ? pair_b[i] : 0;
+    ctx->cp_pb[i] = pair_kind[i] == DDP_HIP_CAPSULE_VS_ROBOT || pair_kind[i] == DDP_HIP_CAPSULE_VS_BOX ? pair_b[i] : 0;
   }
+  return DDP_HIP_OK;
+}
+
+// the box shapes of the pairs of kind DDP_HIP_CAPSULE_VS_BOX, shared by the batch: context state like the capsules, read whenever a
+// description is built for a launch
+extern "C" int ddp_hip_capsule_set_boxes(ddp_hip_ctx* ctx, int32_t n_boxes, const double* half) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  if (!(ctx->flags & DDP_HIP_FLAG_CAPSULE_COST)) return DDP_HIP_E_UNSUPPORTED;
+  if (n_boxes < 0 || n_boxes > DDP_HIP_MAX_CAPSULE_BOXES || (n_boxes > 0 && !half)) return DDP_HIP_E_ARG;
+  for (int k = 0; k < 3 * n_boxes; ++k)
+    if (!isfinite(half[k]) || !(half[k] > 0.0)) return DDP_HIP_E_ARG;
+  for (int i = 0; i < ctx->cp_npair; ++i)
+    if (ctx->cp_kind[i] == DDP_HIP_CAPSULE_VS_BOX && ctx->cp_pb[i] >= n_boxes) return DDP_HIP_E_ARG;   // (a live pair keeps its box)
+  ctx->cp_nbox = n_boxes;
+  for (int k = 0; k < 3 * n_boxes; ++k) ctx->cp_half[k / 3][k % 3] = half[k];
   return DDP_HIP_OK;
 }
 

@@ -1363,8 +1363,10 @@ __global__ __launch_bounds__(64) void self_collision_clearance_kernel(SelfCollis
 // `it` of the description's flat list (CapsuleCostDev::gbase) by lane it % 16, and leave phi of each in LDS (s_phi: 4 x
 // grid_items, dynamic).  After one more barrier the pair's own lane of step 2 scans its pair's values in ascending j
 // (capsule_grid_better: smallest j on a tie, the first NaN before everything), which no dealing can change, and forms d; the
-// value and the clearance need no gradient
-template <bool MIN, bool GRID>
+// value and the clearance need no gradient.
+// BOX (some pair is of kind DDP_HIP_CAPSULE_VS_BOX): such a pair is one closed-form evaluation on its own lane in step 2
+// (rbd::capsule_distance); nothing is dealt, and without a grid pair nothing of the grid's dealing is compiled in
+template <bool MIN, bool GRID, bool BOX>
 __device__ __forceinline__ void capsule_fold(const CapsuleCostDev& cp, const DevModel& m, double (*s_e)[2][3], double* s_term, int32_t* s_formed,
                                              double* s_phi, const double* xs, int64_t traj_stride, int64_t count, int32_t T1, int32_t nx, int32_t na,
                                              const int32_t* state, int32_t round, double* out, int32_t add) {
@@ -1405,7 +1407,7 @@ __device__ __forceinline__ void capsule_fold(const CapsuleCostDev& cp, const Dev
         u[0] = u[1] = u[2] = 0.0;
         (void)capsule_grid_pair(best, u, cp.radius[cp.pa[i]], cp.geom[(pr.bt1 * cp.npair + i) * 8 + 7], &d, u);
       } else {
-        (void)rbd::capsule_distance<false>(cp, i, ea[0], ea[1], eb[0], eb[1], cp.geom + (pr.bt1 * cp.npair + i) * 8, &d, ca, cb, u);
+        (void)rbd::capsule_distance<false, BOX>(cp, i, ea[0], ea[1], eb[0], eb[1], cp.geom + (pr.bt1 * cp.npair + i) * 8, &d, ca, cb, u);
       }
       if (MIN) { term = d; formed = true; }
       else if (rbd::obstacle_active(d)) { term = w[i] * d * d; formed = true; }
@@ -1431,24 +1433,24 @@ __device__ __forceinline__ void capsule_fold(const CapsuleCostDev& cp, const Dev
 // e == 0 is left out, and a state without an active pair adds nothing (add != 0) or stores +0 (add == 0).  A non-finite state
 // gives a NaN term, as com_cost_kernel's does.  GRID: 4 x grid_items doubles of dynamic LDS
 extern __shared__ double s_capsule_phi[];
-template <bool GRID>
+template <bool GRID, bool BOX>
 __global__ __launch_bounds__(64) void capsule_cost_kernel(CapsuleCostDev cp, const DevModel* model, const double* xs, int64_t traj_stride,
                                                           int64_t count, int32_t T1, int32_t nx, int32_t na, const int32_t* state,
                                                           int32_t round, double* out, int32_t add) {
   __shared__ double s_e[64][2][3], s_term[4 * DDP_HIP_MAX_CAPSULE_PAIRS];
   __shared__ int32_t s_act[4 * DDP_HIP_MAX_CAPSULE_PAIRS];
-  capsule_fold<false, GRID>(cp, *model, s_e, s_term, s_act, GRID ? s_capsule_phi : nullptr, xs, traj_stride, count, T1, nx, na, state, round, out, add);
+  capsule_fold<false, GRID, BOX>(cp, *model, s_e, s_term, s_act, GRID ? s_capsule_phi : nullptr, xs, traj_stride, count, T1, nx, na, state, round, out, add);
 }
 
 // ddp_hip_capsule_clearance: the same layout over the `count` (instance, t) pairs of one resident trajectory (a list of one-state
 // trajectories, no candidates to skip), min instead of sum: out[pair] = min over the capsule pairs with w != 0 of d_i, +inf where
 // none is live, NaN where a distance is NaN
-template <bool GRID>
+template <bool GRID, bool BOX>
 __global__ __launch_bounds__(64) void capsule_clearance_kernel(CapsuleCostDev cp, const DevModel* model, const double* xs, int64_t count,
                                                                int32_t nx, double* out) {
   __shared__ double s_e[64][2][3], s_min[4 * DDP_HIP_MAX_CAPSULE_PAIRS];
   __shared__ int32_t s_live[4 * DDP_HIP_MAX_CAPSULE_PAIRS];
-  capsule_fold<true, GRID>(cp, *model, s_e, s_min, s_live, GRID ? s_capsule_phi : nullptr, xs, nx, count, 1, nx, 1, nullptr, 0, out, 0);
+  capsule_fold<true, GRID, BOX>(cp, *model, s_e, s_min, s_live, GRID ? s_capsule_phi : nullptr, xs, nx, count, 1, nx, 1, nullptr, 0, out, 0);
 }
 
 // accept rule (ddp_fwd.ipp:56-60): the first (= largest) candidate with sum(new - old) <= 0; the winner's
@@ -1731,10 +1733,15 @@ static void launch_self_collision_cost(ddp_hip_ctx* ctx, const double* xs, const
 static size_t capsule_grid_lds(const CapsuleCostDev& cp) { return sizeof(double) * (size_t)((64 / DDP_HIP_MAX_CAPSULES) * cp.grid_items); }
 static void launch_capsule_cost(ddp_hip_ctx* ctx, const double* xs, const double* us, int na, int64_t count, const int32_t* state, int round, double* out, int add) {
   const CapsuleCostDev cp = capsule_cost_dev(ctx);
-  if (!cp.grid_pairs) { launch_add_on(capsule_cost_kernel<false>, cp, DDP_HIP_MAX_CAPSULES, ctx, xs, na, count, state, round, out, add); return; }
+  if (!cp.grid_pairs) {
+    if (cp.box_pairs) launch_add_on(capsule_cost_kernel<false, true>, cp, DDP_HIP_MAX_CAPSULES, ctx, xs, na, count, state, round, out, add);
+    else launch_add_on(capsule_cost_kernel<false, false>, cp, DDP_HIP_MAX_CAPSULES, ctx, xs, na, count, state, round, out, add);
+    return;
+  }
   const Dims& d = ctx->d;
   const int64_t per = 64 / DDP_HIP_MAX_CAPSULES;                      // (launch_add_on's launch with the samples' LDS)
-  hipLaunchKernelGGL(capsule_cost_kernel<true>, dim3((unsigned)((count + per - 1) / per)), dim3(64), capsule_grid_lds(cp), ctx->stream, cp, ctx->model_d,
+  const auto kernel = cp.box_pairs ? capsule_cost_kernel<true, true> : capsule_cost_kernel<true, false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((count + per - 1) / per)), dim3(64), capsule_grid_lds(cp), ctx->stream, cp, ctx->model_d,
                      xs, (d.T + 1) * d.nx, count, (int32_t)(d.T + 1), (int32_t)d.nx, (int32_t)na, state, (int32_t)round, out, (int32_t)add);
 }
 
@@ -1826,7 +1833,9 @@ extern "C" int ddp_hip_capsule_clearance(ddp_hip_ctx* ctx, int which, double* ou
   const CapsuleCostDev cp = capsule_cost_dev(ctx, true);
   const int64_t total = ctx->d.batch * (ctx->d.T + 1);
   const int64_t per = 64 / DDP_HIP_MAX_CAPSULES;
-  hipLaunchKernelGGL(cp.grid_pairs ? capsule_clearance_kernel<true> : capsule_clearance_kernel<false>, dim3((unsigned)((total + per - 1) / per)), dim3(64),
+  const auto clearance = cp.grid_pairs ? (cp.box_pairs ? capsule_clearance_kernel<true, true> : capsule_clearance_kernel<true, false>)
+                                       : (cp.box_pairs ? capsule_clearance_kernel<false, true> : capsule_clearance_kernel<false, false>);
+  hipLaunchKernelGGL(clearance, dim3((unsigned)((total + per - 1) / per)), dim3(64),
                      cp.grid_pairs ? capsule_grid_lds(cp) : 0, ctx->stream, cp, ctx->model_d,
                      which == 0 ? p.x_old : p.x_new, total, (int32_t)ctx->d.nx, ctx->cp_clear_d);
   HIP_TRY(hipGetLastError());

@@ -305,6 +305,8 @@ struct ddp_hip_ctx {
   double cp_end[DDP_HIP_MAX_CAPSULES][2][3] = {};
   double cp_radius[DDP_HIP_MAX_CAPSULES] = {};
   int32_t cp_pa[DDP_HIP_MAX_CAPSULE_PAIRS] = {}, cp_kind[DDP_HIP_MAX_CAPSULE_PAIRS] = {}, cp_pb[DDP_HIP_MAX_CAPSULE_PAIRS] = {};
+  int32_t cp_nbox = 0;                        // the box shapes of the pairs of kind DDP_HIP_CAPSULE_VS_BOX (ddp_hip_capsule_set_boxes)
+  double cp_half[DDP_HIP_MAX_CAPSULE_BOXES][3] = {};
   double* cp_clear_d = nullptr;               // [batch][T+1] what ddp_hip_capsule_clearance hands back
   // the relative-frame pairs (ddp_hip_relative_frame_set_pairs): base frame A = (rf_ja, rf_offa), tip frame B = (rf_jb, rf_offb)
   int32_t rf_np = 0;                          // pairs set (0: none yet)

@@ -857,9 +857,11 @@ __global__ __launch_bounds__(64) void lin_self_collision_cost_kernel(LinParams p
 // and leave phi of each in LDS (the pairs with w == 0 are not looked up).  After a barrier a grid pair's own lane scans its values
 // in ascending j (capsule_grid_better: smallest j on a tie, the first NaN before everything -- whatever the dealing) and forms the
 // point and the gradient at j* by the sample routine again: the same bits as the scan on one lane (capsule_grid_closest).  The
-// vote and everything behind it are as before
+// vote and everything behind it are as before.
+// BOX (some pair is of kind DDP_HIP_CAPSULE_VS_BOX): the pair's own lane evaluates capsule_box_closest in phase 1 (rbd::capsule_distance);
+// a box pair is a world pair with c_b = c_a and everything behind the vote is as before
 static_assert(sizeof(LinParams) + sizeof(CapsuleCostDev) <= 4096, "the kernel's arguments must fit the kernarg segment");
-template <bool GRID>
+template <bool GRID, bool BOX>
 __global__ __launch_bounds__(64) void lin_capsule_cost_kernel(LinParams p, CapsuleCostDev cp) {
   const int64_t bt1 = blockIdx.x;
   const int n = (int)p.d.n;
@@ -919,7 +921,7 @@ __global__ __launch_bounds__(64) void lin_capsule_cost_kernel(LinParams p, Capsu
         cb[0] = ca[0]; cb[1] = ca[1]; cb[2] = ca[2];
         has_u = capsule_grid_pair(phi, grad, cp.radius[ia], g[7], &d, u);
       } else {
-        has_u = rbd::capsule_distance<false>(cp, tid, a0, a1, b0, b1, g, &d, ca, cb, u);
+        has_u = rbd::capsule_distance<false, BOX>(cp, tid, a0, a1, b0, b1, g, &d, ca, cb, u);
       }
       act = rbd::obstacle_active(d) && has_u;
     }
@@ -1826,8 +1828,10 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
     if (ob.grid_slots) add(ob.geom, lin_obstacle_cost_kernel<true>, ob);
     else add(ob.geom, lin_obstacle_cost_kernel<false>, ob);
     add(sc.margin, lin_self_collision_cost_kernel, sc);
-    if (cp.grid_pairs) add(cp.geom, lin_capsule_cost_kernel<true>, cp);
-    else add(cp.geom, lin_capsule_cost_kernel<false>, cp);
+    if (cp.grid_pairs && cp.box_pairs) add(cp.geom, lin_capsule_cost_kernel<true, true>, cp);
+    else if (cp.grid_pairs) add(cp.geom, lin_capsule_cost_kernel<true, false>, cp);
+    else if (cp.box_pairs) add(cp.geom, lin_capsule_cost_kernel<false, true>, cp);
+    else add(cp.geom, lin_capsule_cost_kernel<false, false>, cp);
   }
   // the q- / v-caches of the mode-2 stencil also serve the first order (base configuration and base (q, v)), so they are built
   // ahead of whichever stage comes first

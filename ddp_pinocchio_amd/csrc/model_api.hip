@@ -253,6 +253,33 @@ __global__ __launch_bounds__(64) void model_capsule_pair_kernel(const DevModel* 
   for (int c = tid; c < nv; c += blockDim.x) out[7 + c] = (((ma ^ mb) >> c) & 1) && s_D != 0.0 ? rbd::capsule_z(*m, ff, S, 0, c) : 0.0;
 }
 
+// One robot capsule (the segment a0 .. a1 of joint ja, radius r) against one oriented box at one configuration by the routine the
+// cost kernels use (capsule_box_closest, capsule_cost.h): in = q | a0[3] | a1[3] | half[3] | pose[7] | r, out = d (margin 0) | s |
+// ca3 | u3 | grad[nv] = P_ca^T u over all of path(A), a world pair (all 0 where f* == 0: the pair has no derivative there)
+__global__ __launch_bounds__(64) void model_capsule_box_kernel(const DevModel* m, const double* in, double* out, int ja) {
+  __shared__ rbd::CapsuleWaveLds S;
+  __shared__ int s_has;
+  const int tid = threadIdx.x, nv = m->nv;
+  const bool ff = m->ff != 0;
+  if (tid < m->nj) rbd::stage_joint_lane<0>(*m, in, tid, S.jw, nullptr);
+  if (tid == 63) {
+    const double* e = in + m->nq;
+    double a[2][3] = {{e[0], e[1], e[2]}, {e[3], e[4], e[5]}};
+    (void)rbd::walk_to_root<2, 0>(*m, ff, ja, in, a, nullptr, -1);
+    double s, d;
+    const double f = capsule_box_closest(a[0], a[1], e + 6, e + 9, &s, S.ca[0], S.u[0]);
+    s_has = capsule_box_pair(f, e[16], 0.0, &d) ? 1 : 0;
+    out[0] = d;
+    out[1] = s;
+    for (int k = 0; k < 3; ++k) { S.cb[0][k] = S.ca[0][k]; out[2 + k] = S.ca[0][k]; out[5 + k] = S.u[0][k]; }
+  }
+  __syncthreads();
+  const unsigned long long ma = rbd::tangent_mask(ff, S.jw.mask[ja]);
+  if (tid == 0) { S.ma[0] = ma; S.mb[0] = 0ull; }
+  __syncthreads();
+  for (int c = tid; c < nv; c += blockDim.x) out[8 + c] = ((ma >> c) & 1) && s_has ? rbd::capsule_z(*m, ff, S, 0, c) : 0.0;
+}
+
 #define MODEL_DISPATCH(nv, CALL)       \
   do {                                 \
     if ((nv) <= 6) { CALL(6); }        \
@@ -297,6 +324,8 @@ int run(ddp_hip_model_handle* h, const double* in, size_t n_in, double* out, siz
   } else if (what == 10) {
     hipLaunchKernelGGL(model_capsule_pair_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac % DDP_MAXJ,
                        want_jac / DDP_MAXJ);   // (want_jac: the two joints)
+  } else if (what == 11) {
+    hipLaunchKernelGGL(model_capsule_box_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac);   // (want_jac: the joint)
   } else if (what == 8) {
     hipLaunchKernelGGL(model_frame_axis_kernel, dim3(1), dim3(64), 0, h->stream, h->model_d, h->buf_d, o, want_jac);   // (want_jac: the joint)
   } else {
@@ -522,5 +551,31 @@ extern "C" int ddp_hip_model_capsule_pair(ddp_hip_model_handle* h, int32_t ja, c
   memcpy(ca3, out + 1, sizeof(double) * 3);
   memcpy(cb3, out + 4, sizeof(double) * 3);
   if (J) memcpy(J, out + 7, sizeof(double) * nv);
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_model_capsule_box(ddp_hip_model_handle* h, int32_t joint, const double a0[3], const double a1[3], double radius,
+                                         const double half[3], const double pose[7], const double* q, double* d, double* s, double ca[3],
+                                         double u[3], double* grad) {
+  if (!h || !a0 || !a1 || !half || !pose || !q || !d || !s || !ca || !u || h->model_h.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_ARG;
+  const int nv = h->model_h.nv, nq = h->model_h.nq, nj = h->model_h.nj;
+  if (joint < 0 || joint >= nj || !isfinite(radius) || radius < 0.0) return DDP_HIP_E_ARG;
+  double in[DDP_MAXJ + 1 + 17];
+  memcpy(in, q, sizeof(double) * nq);
+  memcpy(in + nq, a0, sizeof(double) * 3); memcpy(in + nq + 3, a1, sizeof(double) * 3);
+  memcpy(in + nq + 6, half, sizeof(double) * 3); memcpy(in + nq + 9, pose, sizeof(double) * 7);
+  in[nq + 16] = radius;
+  for (int k = 0; k < 16; ++k)
+    if (!isfinite(in[nq + k])) return DDP_HIP_E_ARG;
+  if (!(half[0] > 0.0) || !(half[1] > 0.0) || !(half[2] > 0.0)) return DDP_HIP_E_ARG;
+  if (!cost_quat_ok(pose[3] * pose[3] + pose[4] * pose[4] + pose[5] * pose[5] + pose[6] * pose[6])) return DDP_HIP_E_ARG;
+  double out[8 + DDP_MAXJ];
+  const int rc = run(h, in, (size_t)(nq + 17), out, (size_t)(8 + (grad ? nv : 0)), 11, joint);
+  if (rc != DDP_HIP_OK) return rc;
+  *d = out[0];
+  *s = out[1];
+  memcpy(ca, out + 2, sizeof(double) * 3);
+  memcpy(u, out + 5, sizeof(double) * 3);
+  if (grad) memcpy(grad, out + 8, sizeof(double) * nv);
   return DDP_HIP_OK;
 }

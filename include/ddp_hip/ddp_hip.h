@@ -610,7 +610,42 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
  * values and the lineariser's derivatives agree without an envelope argument; a refinement would claim accuracy below a cell,
  * which the field does not have.  For a 1-Lipschitz field the continuous minimum along the segment is at least
  * min_j phi_j - L_k / (2 N_k): a caller who wants a bound puts that into the margin.  A capsule with L_k > 32 cell is sampled
- * coarser than the grid.  ddp_hip_capsule_set_pairs accepts the kind only while a grid is resident. */
+ * coarser than the grid.  ddp_hip_capsule_set_pairs accepts the kind only while a grid is resident.
+ *
+ * A fifth pair kind, DDP_HIP_CAPSULE_VS_BOX, is the shape a workspace is made of: an oriented box (a table top, a shelf board, a
+ * tote).  The shapes, up to DDP_HIP_MAX_CAPSULE_BOXES half-extent triples h > 0 along the box's own axes, are shared by the batch
+ * (ddp_hip_capsule_set_boxes); pair_b[i] names the shape, several pairs may name one, and each pair has its own pose per
+ * instance and t:
+ *   DDP_HIP_CAPSULE_VS_BOX        B is box shape pair_b[i]: geom = (centre c(3), quaternion x y z w (4), m), all eight finite, the
+ *                                 quaternion unit (| |q| - 1 | <= 1e-10) with world = R(q) box, R by the free-flyer's formula
+ * The distance is exact, by a pinned search (capsule_box_closest in csrc/capsule_cost.h, host and device, every product rounded on
+ * its own).  With a = R^T (a0 - c), b = R^T (a1 - c), dl = b - a, p(s) = a + s dl and the box's signed distance
+ *   phi(p) = | max(|p| - h, 0) |_2 if that is > 0, else max_k (|p_k| - h_k)            (NaN where a coordinate is)
+ * f(s) = phi(p(s)) is convex on [0, 1], and between two crossings of a face plane it is one smooth piece:
+ *   1. breakpoints: 0, 1 and, for every axis k with dl_k != 0 and either sign, s = (+-h_k - a_k) / dl_k where 0 < s < 1 (+ before
+ *      -), sorted ascending; equal values change nothing (an empty interval adds no new candidate)
+ *   2. for consecutive breakpoints lo <= hi the pattern sg_k of p(1/2 (lo + hi)): +1 for p_k > h_k, -1 for p_k < -h_k, else 0
+ *   3. candidates, in this order: lo; then, if some sg_k != 0 (outside), with A = sum dl_k^2 and C = sum dl_k (a_k - sg_k h_k) over
+ *      those k in ascending k, s = -C / A if A > 0 and lo < s < hi; if all sg_k = 0 (inside), with the six lines
+ *      l_i(s) = +-p_k(s) - h_k in the order i = (0+, 0-, 1+, 1-, 2+, 2-), for each pair i < j in lexicographic order whose slopes
+ *      differ, s = (l_j(0) - l_i(0)) / (slope_i - slope_j) if lo < s < hi; last hi
+ *   4. f is evaluated at every candidate in the order met and a candidate replaces the best only if strictly smaller: the smallest s,
+ *      first met, wins a tie; a NaN wins over everything, the first one taken.  This gives s*, f*, c_a = a0 + s* (a1 - a0)
+ *   5. u = R n with n in box axes: f* > 0: n = (p - clamp(p, -h, h)) / f*;  f* <= 0 and the winner a crossing of the lines i, j
+ *      with slopes of opposite sign: n = (|slope_j| n_i + |slope_i| n_j) / (|slope_i| + |slope_j|), n_i the outward normal of
+ *      face i -- the derivative of a min-max at its kink, not of unit length (as the grid kind's u is not);  otherwise n is the
+ *      normal of the first line in the order above that attains max_i l_i(s*)
+ *   d_i = f* - r_a - m,   c_b = c_a,   u_i = u
+ * Convexity makes the search exact: the minimum of a convex f over [0, 1] is at an end or where a smooth piece is stationary, and
+ * every such point is a candidate.  e, the cost, the Gauss-Newton block and the "left out" rules are those above.  The pair is a
+ * world pair: with s* held (the envelope argument above) all of path(A) carries + P_{c_a}^T u, a free-flyer root's six columns
+ * included.  f* == 0 exactly means value and no derivative (the D == 0 rule).  Inside the box the direction is exact where the
+ * minimiser is unique; where the segment runs parallel to the nearest face the smallest s is taken and the direction is that
+ * face's normal, one of the subgradients.  The penalty pushes a limb out through the nearest face, so a plate thinner than the
+ * step the solver takes can be crossed unseen: inflate the margin of such a pair until box plus margin is thicker than that.
+ * Geometry is validated on upload only; freshly reset geometry is all zeros, no unit quaternion, and a pair whose weight is 0 is
+ * never evaluated.  Were a zero quaternion evaluated, R would be the identity by the formula: the box with its axes along the
+ * world's, a defined value. */
 #define DDP_HIP_FLAG_CAPSULE_COST 131072u
 #define DDP_HIP_MAX_CAPSULES 16
 #define DDP_HIP_MAX_CAPSULE_PAIRS 32
@@ -619,6 +654,8 @@ typedef struct ddp_hip_ctx ddp_hip_ctx;
 #define DDP_HIP_CAPSULE_VS_HALFSPACE 2  /* ... a half-space, per instance and t */
 #define DDP_HIP_CAPSULE_VS_GRID 3       /* ... the context's voxel grid (ddp_hip_obstacle_set_grid / _set_occupancy) */
 #define DDP_HIP_CAPSULE_GRID_MAX_INTERVALS 32
+#define DDP_HIP_CAPSULE_VS_BOX 4        /* ... an oriented box of the pair's own pose, per instance and t (ddp_hip_capsule_set_boxes) */
+#define DDP_HIP_MAX_CAPSULE_BOXES 8
 
 int ddp_hip_abi_version(void);
 const char* ddp_hip_strerror(int code);
@@ -825,13 +862,20 @@ int ddp_hip_joint_accel(ddp_hip_ctx* ctx, int which, double* out);
  * negative or non-finite radius, a capsule index outside the capsules, an unknown kind, DDP_HIP_CAPSULE_VS_GRID while no grid is
  * resident, and a robot pair with a == b or with both capsules on the same joint (their distance is constant).  Duplicate pairs are allowed.  It may be called again: with the same
  * two counts and the same kinds the per-instance data stays (capsules may move, radii may change, a pair may name other capsules),
- * otherwise geometry and weights are reset to 0. */
+ * otherwise geometry and weights are reset to 0.  A pair of kind DDP_HIP_CAPSULE_VS_BOX reads pair_b[i] as the index of a box shape,
+ * 0 .. n_boxes - 1 of ddp_hip_capsule_set_boxes (outside, or with no boxes set: DDP_HIP_E_ARG). */
 int ddp_hip_capsule_set_pairs(ddp_hip_ctx* ctx, int32_t n_capsules, const int32_t* joint, const double* end0, const double* end1,
                               const double* radius, int32_t n_pairs, const int32_t* pair_a, const int32_t* pair_kind, const int32_t* pair_b);
+/* The box shapes of the pairs of kind DDP_HIP_CAPSULE_VS_BOX, shared by the batch, in a context created with DDP_HIP_FLAG_CAPSULE_COST
+ * (else DDP_HIP_E_UNSUPPORTED): half[n_boxes][3] (host), the half extents along the box's own axes, each finite and > 0.
+ * DDP_HIP_E_ARG, with nothing changed, for n_boxes outside 0 .. DDP_HIP_MAX_CAPSULE_BOXES, a bad extent, and a call that would leave
+ * a box pair already set without its shape (pair_b >= n_boxes).  It may be called again: extents may change while the pairs stand,
+ * and the next launch reads the new ones. */
+int ddp_hip_capsule_set_boxes(ddp_hip_ctx* ctx, int32_t n_boxes, const double* half);
 /* The pairs' geometry and weights, stream-ordered like ddp_hip_obstacle_upload.  Host arrays [n_instances][T+1][n_pairs][8] and
  * [n_instances][T+1][n_pairs]; a NULL pointer leaves that side as it is.  An upload is refused as a whole (DDP_HIP_E_ARG, nothing
  * written) before ddp_hip_capsule_set_pairs, for a bad instance range, a non-finite geom entry (the ignored ones included), a
- * world capsule's rho < 0, a half-space normal n with | |n| - 1 | > 1e-10 and a negative or non-finite weight.  A geom that
+ * world capsule's rho < 0, a half-space normal n with | |n| - 1 | > 1e-10, a box pair's quaternion q with | |q| - 1 | > 1e-10 and a negative or non-finite weight.  A geom that
  * arrives alone is checked against the pair kinds; weights that arrive alone need no geometry check. */
 int ddp_hip_capsule_upload(ddp_hip_ctx* ctx, const double* geom, const double* weight, int64_t first_instance, int64_t n_instances);
 int ddp_hip_capsule_download(ddp_hip_ctx* ctx, double* geom, double* weight, int64_t first_instance, int64_t n_instances);
@@ -1063,6 +1107,15 @@ int ddp_hip_model_capture_point(ddp_hip_model_handle* h, const double* q, const 
  * where D == 0.  No radius and no margin enter: d = D - (r_a + r_b + m).  For margins such as "2 cm less than they are apart now" */
 int ddp_hip_model_capsule_pair(ddp_hip_model_handle* h, int32_t ja, const double a0[3], const double a1[3], int32_t jb, const double b0[3],
                                const double b1[3], const double* q, double* D, double* ca3, double* cb3, double* J);
+/* One robot capsule of a tree model against one oriented box at the configuration q, as DDP_HIP_CAPSULE_VS_BOX defines it, by the
+ * device routine the cost kernels use: the segment a0 .. a1 fixed in `joint` with the radius `radius` >= 0, the box of half extents
+ * half[3] > 0 at pose[7] = (centre, unit quaternion x y z w).  *d the signed distance f* - radius (margin 0), *s the segment
+ * parameter s*, ca the closest point on the segment axis in the world, u = dd / dc_a and, where not NULL, grad[nv] = P_{c_a}^T u
+ * over all of path(joint) (all 0 where f* == 0).  A joint outside the model, a non-finite entry, an extent <= 0 or a quaternion
+ * that is not unit: DDP_HIP_E_ARG. */
+int ddp_hip_model_capsule_box(ddp_hip_model_handle* h, int32_t joint, const double a0[3], const double a1[3], double radius,
+                              const double half[3], const double pose[7], const double* q, double* d, double* s, double ca[3], double u[3],
+                              double* grad);
 
 /* ---- built-in seeded model tables (no URDF exists offline: SURVEY.md D4, 8d) -------------- */
 /* ..._FF: the same robots on a free-flyer root instead of a fixed base / 3 prismatic + 3 revolute base joints */
