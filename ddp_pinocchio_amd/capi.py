@@ -100,6 +100,7 @@ EXPORTS = [
     "ddp_hip_capsule_set_pairs", "ddp_hip_capsule_upload", "ddp_hip_capsule_download", "ddp_hip_capsule_clearance",
     "ddp_hip_model_capsule_pair", "ddp_hip_capsule_set_boxes", "ddp_hip_model_capsule_box",
     "ddp_hip_advance",
+    "ddp_hip_set_armature", "ddp_hip_get_armature", "ddp_hip_model_set_armature",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -289,6 +290,10 @@ def lib():
     L.ddp_hip_model_aba.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
     L.ddp_hip_model_aba_derivatives.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _dp]
     L.ddp_hip_model_frame.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp]
+    if hasattr(L, "ddp_hip_set_armature"):           # (likewise: set_armature / get_armature, ModelHandle.set_armature)
+        L.ddp_hip_set_armature.argtypes = [C.c_void_p, _dp]
+        L.ddp_hip_get_armature.argtypes = [C.c_void_p, _dp]
+        L.ddp_hip_model_set_armature.argtypes = [C.c_void_p, _dp]
     _lib = L
     return L
 
@@ -311,6 +316,14 @@ def _f64(a):
 
 def _ptr(a):
     return a.ctypes.data_as(_dp)
+
+
+def _armature(armature, nv):
+    """joint armature as a contiguous [nv] array; a wrong length is refused here, before any device call"""
+    a = _f64(armature).reshape(-1)
+    if a.size != nv:
+        raise ValueError(f"armature has {a.size} entries, the model has nv = {nv}")
+    return a
 
 
 class BuiltinModel:
@@ -396,6 +409,12 @@ class ModelHandle:
 
     def __exit__(self, *a):
         self.close()
+
+    def set_armature(self, armature):
+        """Joint armature [nv] of the handle's model (ddp_hip_model_set_armature): aba / aba_derivatives after it use
+        D_i + a_i.  None passes NULL (refused)."""
+        a = None if armature is None else _armature(armature, self.nv)
+        _check(lib().ddp_hip_model_set_armature(self._h, None if a is None else _ptr(a)), "model_set_armature")
 
     def aba(self, q, v, tau):
         q, v, tau, out = _f64(q), _f64(v), _f64(tau), np.zeros(self.nv)
@@ -518,8 +537,10 @@ class ProblemSpec:
     """Host-side description of problem_t (problem.hpp:872-1150) for one context."""
 
     def __init__(self, model, T, dt=0.01, c=1.0, batch=1, eq_kind=EQ_NONE, eq_advance=2, ne=None, eq_target=None,
-                 frame_joint=0, frame_off=(0.0, 0.0, 0.0), first_order_fd=None, fd_mode=0):
+                 frame_joint=0, frame_off=(0.0, 0.0, 0.0), first_order_fd=None, fd_mode=0, armature=None):
         self.model = model
+        # joint armature [nv] (ddp_hip_set_armature), applied by Context right after create; None: none
+        self.armature = None if armature is None else _armature(armature, model.nv)
         self.T, self.dt, self.c, self.batch = int(T), float(dt), float(c), int(batch)
         self.eq_kind, self.eq_advance = int(eq_kind), int(eq_advance)
         self.ne = np.zeros(self.T, dtype=np.int64) if ne is None else np.ascontiguousarray(ne, dtype=np.int64)
@@ -559,6 +580,23 @@ class Context:
         self.n_collision_pairs = 0
         self.n_frame_pairs = 0
         self.n_aim_frames = 0
+        if getattr(spec, "armature", None) is not None:
+            try:
+                self.set_armature(spec.armature)
+            except Exception:
+                self.close()
+                raise
+
+    def set_armature(self, armature):
+        """Joint armature [nv] (reflected rotor inertia; ddp_hip_set_armature): waits for the stream, every launch after it sees
+        the values.  None passes NULL (refused)."""
+        a = None if armature is None else _armature(armature, self.spec.nv)
+        _check(lib().ddp_hip_set_armature(self._h, None if a is None else _ptr(a)), "set_armature")
+
+    def get_armature(self):
+        out = np.zeros(self.spec.nv)
+        _check(lib().ddp_hip_get_armature(self._h, _ptr(out)), "get_armature")
+        return out
 
     def close(self):
         if self._h:

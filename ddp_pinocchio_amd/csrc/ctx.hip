@@ -975,6 +975,39 @@ extern "C" int ddp_hip_set_active(ddp_hip_ctx* ctx, const int32_t* active) {
   return DDP_HIP_OK;
 }
 
+// Joint armature [nv] into a resident model (shared with model_api.hip): checked as a whole first, so a refused call leaves the
+// old values in force; then the stream is drained (kernels in flight read the old values to their end) and the array alone is
+// written.  DevModel keeps it by joint, like axis: tangent row i of a fixed-base model is joint i, of a free-flyer model joint i - 5
+int ddp_hip_apply_armature(DevModel& mh, DevModel* md, hipStream_t stream, const double* armature) {
+  if (!armature) return DDP_HIP_E_ARG;
+  if (mh.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;   // the pendulum's closed form is the reference's own
+  const int vo = mh.ff ? 5 : 0;
+  for (int i = 0; i < mh.nv; ++i) {
+    if (!std::isfinite(armature[i]) || armature[i] < 0.0) return DDP_HIP_E_ARG;
+    if (mh.ff && i < 6 && armature[i] != 0.0) return DDP_HIP_E_ARG;   // the six rows of the free-flyer root carry none
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  double a[DDP_MAXJ] = {};
+  for (int j = mh.ff ? 1 : 0; j < mh.nj; ++j) a[j] = armature[j + vo];
+  HIP_TRY(hipMemcpy(md->armature, a, sizeof(a), hipMemcpyHostToDevice));
+  memcpy(mh.armature, a, sizeof(a));
+  return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_set_armature(ddp_hip_ctx* ctx, const double* armature) {
+  if (!ctx) return DDP_HIP_E_ARG;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ddp_hip_apply_armature(ctx->model_h, ctx->model_d, ctx->stream, armature);
+}
+
+extern "C" int ddp_hip_get_armature(ddp_hip_ctx* ctx, double* armature) {
+  if (!ctx || !armature) return DDP_HIP_E_ARG;
+  const DevModel& mh = ctx->model_h;
+  if (mh.kind != DDP_HIP_MODEL_TREE) return DDP_HIP_E_UNSUPPORTED;
+  for (int i = 0; i < mh.nv; ++i) armature[i] = (mh.ff && i < 6) ? 0.0 : mh.armature[mh.ff ? i - 5 : i];
+  return DDP_HIP_OK;
+}
+
 extern "C" int ddp_hip_ctx_info(const ddp_hip_ctx* ctx, ddp_hip_info* out) {
   if (!ctx || !out) return DDP_HIP_E_ARG;
   const Dims& d = ctx->d;

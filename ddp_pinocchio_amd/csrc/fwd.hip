@@ -551,6 +551,7 @@ __global__ __launch_bounds__(PIPE && fwd_pipe_assist(OPEN, FF, COST, BOX) ? 192 
       for (int k2 = 0; k2 < 21; ++k2) cm.I6[i][k2] = m.I6[i][k2];
       for (int k2 = 0; k2 < 9; ++k2) cm.Rp[i][k2] = m.Rp[i][k2];
       for (int k2 = 0; k2 < 3; ++k2) { cm.axis[i][k2] = m.axis[i][k2]; cm.pp[i][k2] = m.pp[i][k2]; }
+      cm.armature[i] = m.armature[i];
       cm.parent[i] = m.parent[i]; cm.jtype[i] = m.jtype[i];
       cm.lvl_joint[i] = m.lvl_joint[i]; cm.child_list[i] = m.child_list[i];
       cm.lvl_start[i] = m.lvl_start[i]; cm.child_start[i] = m.child_start[i];

@@ -43,6 +43,9 @@ struct DevModel {
   // constraint chain
   int32_t eq_kind, eq_advance, frame_joint, first_order_fd, fd_mode, pad_;
   double frame_off[3];
+  // joint armature (reflected rotor inertia), by joint like axis: D = S^T IA S + armature, M_ii += armature.  Zero at create,
+  // written by ddp_hip_set_armature / ddp_hip_model_set_armature; the free-flyer root (joint 0 of an ff model) carries none
+  double armature[DDP_MAXJ];
 };
 
 // Everything a kernel needs to find a block of a flat sequence.

@@ -98,7 +98,7 @@ __device__ void accel_group(const DevModel& m, const double* q, const double* v,
           for (int k = 0; k < 6; ++k) S(i, oP + k) = pAi[k];
           continue;
         }
-        const double dinv = step_U(IA, a, rev, U);
+        const double dinv = step_U(IA, a, rev, m.armature[i], U);
         const double ui = step_u(pAi, a, rev, tau[i + vo]);
 #pragma unroll
         for (int k = 0; k < 6; ++k) S(i, oU + k) = U[k];

@@ -1075,7 +1075,8 @@ __global__ void lin_diag_kernel(LinParams p) {
   const bool at_x = i < n;
   const int idx = at_x ? i : i - n;
   if (at_x) lie::perturb_x(m, x, idx, eps); else u[idx] = u[idx] + eps;
-  if (p.qcache) {
+  // (ncfg == 1: the base point's caches alone, kept for the static first order under DDP_HIP_NO_QCACHE -- no block per stepped q)
+  if (p.qcache && p.ncfg > 1) {
     const int nv = m.nv, cfg = (at_x && idx < nv) ? 1 + idx : 0;
     const double* qc = p.qcache + (bt * (nv + 1) + cfg) * (int64_t)nv * rbd::QC_STRIDE;
     if (!at_x) rbd::eval_f_ucached<NJ>(m, qc, p.vcache + (bt * (2 * nv + 1)) * (int64_t)nv * rbd::VC_STRIDE, x, u, f1);

@@ -466,7 +466,10 @@ __global__ __launch_bounds__(AW) void ana_eval_kernel(AnaParams ap) {
       s_T[i * W2 + j] = sq;
       s_T[i * W2 + N + j] = sv;
       if constexpr (!FUSED) {
-        if (want_M) { Mo[i + (int64_t)j * N] = sm; Mo[j + (int64_t)i * N] = sm; }
+        if (want_M) {
+          if (i == j) sm += m.armature[j];                 // M + diag(armature)
+          Mo[i + (int64_t)j * N] = sm; Mo[j + (int64_t)i * N] = sm;
+        }
       }
       if (i != j) {                                       // a proper ancestor of j: its u | g
         double s1 = 0, s2 = 0, s3 = 0, s4 = 0;
@@ -481,12 +484,14 @@ __global__ __launch_bounds__(AW) void ana_eval_kernel(AnaParams ap) {
     // the lane's row of M, M(j, k) = J_k . y_j for k on the path of j: a register array cannot be indexed by the run-time joint
     // number the walk above meets, so the product is formed for EVERY k (J_k: one broadcast read) and kept where the path says so
     if (want_M && live) {
+      const double arm = m.armature[lane];                // M + diag(armature): added to the lane's own diagonal entry alone
 #pragma unroll
       for (int k = 0; k < NJ; ++k) {                      // (k >= nv: no bit in the mask)
         const double* Jk = s_W + 30 * k + 12;
         double sm = 0;
 #pragma unroll
         for (int c = 0; c < 6; ++c) sm += Jk[c] * Pr[c];
+        if (k == lane) sm += arm;
         arow[k] = ((path_mask >> k) & 1) ? sm : 0.0;
       }
     }

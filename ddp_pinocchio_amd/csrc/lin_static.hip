@@ -805,14 +805,15 @@ __device__ __forceinline__ void step_bias_force0(const double* I6, const double*
   rbd::sym6_mv(I6, vel, Iv);
   rbd::crf(vel, Iv, pA);
 }
-// U = IA S and 1/D = 1 / (S^T U) (rbd::aba_tree / aba_qpart, leaf -> root loop)
+// U = IA S and 1/D = 1 / (S^T U + arm), arm the joint's armature (rbd::aba_tree / aba_qpart, leaf -> root loop)
 template <int o>
-__device__ __forceinline__ void step_U_dinv(const double* IA, const double* a, double* U, double& dinv) {
+__device__ __forceinline__ void step_U_dinv(const double* IA, const double* a, double arm, double* U, double& dinv) {
   double d = 0;
 #pragma unroll
   for (int r = 0; r < 6; ++r) U[r] = IA[rbd::sidx(r, o)] * a[0] + IA[rbd::sidx(r, o + 1)] * a[1] + IA[rbd::sidx(r, o + 2)] * a[2];
 #pragma unroll
   for (int k = 0; k < 3; ++k) d += a[k] * U[o + k];
+  d += arm;
   dinv = 1.0 / d;
 }
 // Ia = IA - U U^T / D (the same loop)
@@ -1225,7 +1226,7 @@ __device__ __forceinline__ void chain_up(const CfgCtx<T>& c, CfgState<T>& s) {
     for (int k = 0; k < 21; ++k) IA[k] = c.m->I6[K][k];
     step_bias_force0(c.m->I6[K], velK, pAi);
   }
-  step_U_dinv<o>(IA, a, U, dinv);
+  step_U_dinv<o>(IA, a, c.m->armature[K], U, dinv);
   const double ui = step_u<o>(a, pAi, c.ug + K);
 #pragma unroll
   for (int k = 0; k < 6; ++k) c.W[(K * WS_PER_JOINT + k) * LBS] = U[k];
@@ -1482,6 +1483,7 @@ __global__ __launch_bounds__(LBS) void lin_static_spine_kernel(const DevModel* _
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) d += a[k] * (pris ? U[3 + k] : U[k]);
+    d += m.armature[K];
     const double dinv = 1.0 / d;
 #pragma unroll
     for (int r = 0; r < 6; ++r)
@@ -1829,7 +1831,7 @@ __device__ __forceinline__ void chain_up(const QvCtx<T, SP, VSP>& c, QvState<T>&
 #pragma unroll
     for (int k = 0; k < 21; ++k) IA[k] = c.m->I6[K][k];
   }
-  step_U_dinv<o>(IA, a, U, dinv);
+  step_U_dinv<o>(IA, a, c.m->armature[K], U, dinv);
   step_Ia(IA, U, dinv, Ia);
   constexpr int par = T::parent[K];
   if constexpr (par >= 0) {

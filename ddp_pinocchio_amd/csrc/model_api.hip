@@ -21,6 +21,7 @@
 
 extern void ddp_hip_fill_dev_model(const ddp_hip_model* mo, DevModel& dm);   // ctx.hip
 extern bool ddp_hip_build_tables(DevModel& dm);
+extern int ddp_hip_apply_armature(DevModel& mh, DevModel* md, hipStream_t stream, const double* armature);
 
 struct ddp_hip_model_handle {
   int device = 0;
@@ -381,6 +382,12 @@ extern "C" int ddp_hip_model_destroy(ddp_hip_model_handle* h) {
   if (h->buf_d) (void)hipFree(h->buf_d);
   delete h;
   return DDP_HIP_OK;
+}
+
+extern "C" int ddp_hip_model_set_armature(ddp_hip_model_handle* h, const double* armature) {
+  if (!h) return DDP_HIP_E_ARG;
+  HIP_TRY(hipSetDevice(h->device));
+  return ddp_hip_apply_armature(h->model_h, h->model_d, h->stream, armature);
 }
 
 extern "C" int ddp_hip_model_aba(ddp_hip_model_handle* h, const double* q, const double* v, const double* tau, double* qdd) {

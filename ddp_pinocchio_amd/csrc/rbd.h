@@ -275,6 +275,7 @@ __device__ void aba_tree(const DevModel& m, const double* q, const double* v, co
     double d = 0, sp = 0;
     for (int r = 0; r < 6; ++r) U[i][r] = IA[sidx(r, o)] * a[0] + IA[sidx(r, o + 1)] * a[1] + IA[sidx(r, o + 2)] * a[2];
     for (int k = 0; k < 3; ++k) { d += a[k] * U[i][o + k]; sp += a[k] * pAi[o + k]; }
+    d += m.armature[i];                           // reflected rotor inertia: D = S^T IA S + a (0.0 leaves d as it is)
     Dinv[i] = 1.0 / d;
     uu[i] = tau[i + vo] - sp;
     const int par = m.parent[i];
@@ -447,6 +448,7 @@ __device__ void aba_qpart(const DevModel& m, const double* q, double* __restrict
     double U[6], d = 0;
     for (int r = 0; r < 6; ++r) U[r] = IA[i][sidx(r, o)] * a[0] + IA[i][sidx(r, o + 1)] * a[1] + IA[i][sidx(r, o + 2)] * a[2];
     for (int k = 0; k < 3; ++k) d += a[k] * U[o + k];
+    d += m.armature[i];
     const double dinv = 1.0 / d;
     double Ia[21];
     for (int r = 0; r < 6; ++r)
@@ -676,6 +678,7 @@ template <int NJ>
 struct CoopModel {
   double I6[NJ][21];
   double axis[NJ][3];
+  double armature[NJ];
   double Rp[NJ][9];
   double pp[NJ][3];
   double gravity[3];
@@ -788,9 +791,9 @@ __device__ __forceinline__ void step_add_children(unsigned long long rr, double*
   }
 }
 
-// U = IA S for the 1-DoF joint along a (S = [a; 0] revolute, [0; a] prismatic); returns 1 / D, D = S^T U.
+// U = IA S for the 1-DoF joint along a (S = [a; 0] revolute, [0; a] prismatic); returns 1 / D, D = S^T U + arm (the joint's armature).
 // rev is per lane: static indices under a select (dynamic ones would put IA in scratch: a store / load round trip per level)
-__device__ __forceinline__ double step_U(const double* IA, const double* a, bool rev, double* U) {
+__device__ __forceinline__ double step_U(const double* IA, const double* a, bool rev, double arm, double* U) {
 #pragma unroll
   for (int r = 0; r < 6; ++r) {
     const double i0 = rev ? IA[sidx(r, 0)] : IA[sidx(r, 3)];
@@ -801,6 +804,7 @@ __device__ __forceinline__ double step_U(const double* IA, const double* a, bool
   double d = 0;
 #pragma unroll
   for (int k = 0; k < 3; ++k) d += a[k] * (rev ? U[k] : U[3 + k]);
+  d += arm;
   return 1.0 / d;
 }
 
@@ -940,7 +944,7 @@ __device__ void aba_tree_coop(const M& m, const double* q, const double* v, cons
 #pragma unroll
         for (int k = 0; k < 6; ++k) pAi[k] += S(c, oP + k);
       }
-      const double dinv = step_U(IA, a, rev, U);
+      const double dinv = step_U(IA, a, rev, m.armature[i], U);
       const double ui = step_u(pAi, a, rev, tau[i]);
 #pragma unroll
       for (int k = 0; k < 6; ++k) S(i, oU + k) = U[k];
@@ -1075,7 +1079,7 @@ __device__ __forceinline__ void aba_tree_coop2w(const M& m, const double* q, con
           for (int k = 0; k < 21; ++k) S(i, oZ + k) = IA[k];
         }
       } else {
-        const double dinv = step_U(IA, a, rev, U);
+        const double dinv = step_U(IA, a, rev, m.armature[i], U);
         FSTAMP(fs, 10);
         const bool has_parent = role_parent(rr) >= 0;
         if (wave == 0) {
@@ -1199,7 +1203,7 @@ __device__ __forceinline__ void aba_pipe_q(const M& m, const double* q, double* 
 #pragma unroll
         for (int k = 0; k < 21; ++k) Q(i, oA + k) = IA[k];   // resolved in the x-part's last pass (step_accel_ff_root)
       } else {
-        const double dinv = step_U(IA, m.axis[i], role_rev(rr), U);
+        const double dinv = step_U(IA, m.axis[i], role_rev(rr), m.armature[i], U);
         FSTAMP(fs, 10);
 #pragma unroll
         for (int k = 0; k < 6; ++k) Q(i, oU + k) = U[k];

@@ -243,6 +243,7 @@ __device__ void aba_derivatives_lane(const DevModel& m, const double* q, const d
       Tv[j + a * NJ] = s3 - 2.0 * s4;
     }
   }
+  for (int i = 0; i < N; ++i) M[i + i * NJ] += m.armature[i];   // M + diag(armature)
   chol_inverse_lane<NJ>(N, M, Minv);
   for (int c = 0; c < N; ++c)
     for (int r = 0; r < N; ++r) {
@@ -437,6 +438,7 @@ __device__ void ff_derivatives_wave(const DevModel& m, const double* q, const do
         s_M[lane + i * N] = s;
       }
     }
+    s_M[lane + lane * N] += m.armature[bc];   // M + diag(armature); the root's six columns carry none (armature[0] is 0 there)
   }
   __syncthreads();
   // Cholesky M = L L^T in place (lower triangle): thread r owns row r
@@ -671,6 +673,7 @@ __device__ void tree_derivatives_wave(const DevModel& m, const double* q, const 
       for (int k = 0; k < 6; ++k) s += s_col[CR * i + k] * y[k];
       s_M[lane + i * N] = s;
     }
+    s_M[lane + lane * N] += m.armature[lane];   // M + diag(armature)
   }
   __syncthreads();
   // Cholesky M = L L^T in place (lower triangle): thread r owns row r

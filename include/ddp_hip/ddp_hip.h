@@ -966,6 +966,22 @@ int ddp_hip_update_multipliers(ddp_hip_ctx* ctx, const double* mu);
  * entries are left as they are) and ddp_hip_swap_traj keeps its (X, U).  active: host [batch] of 0 / 1, NULL = all. */
 int ddp_hip_set_active(ddp_hip_ctx* ctx, const int32_t* active);
 
+/* Joint armature: the rotor inertia reflected through the gearbox, N^2 I_rotor, a constant added to the joint's diagonal
+ * inertia.  armature: host [nv], one entry a_i >= 0 per tangent row of a 1-DoF joint (kg m^2 revolute, kg prismatic), shared by
+ * the batch; the six rows of a free-flyer root carry none (0).  The forward dynamics becomes
+ *     qdd = (M(q) + diag(a))^-1 (tau - h(q, v)),   h = RNEA(q, v, 0) unchanged;
+ * in the articulated-body algorithm D_i = S_i^T IA_i S_i + a_i and nothing else.  Everything that evaluates f(x, u) or its
+ * derivatives follows: rollout, linearise (FD and analytic, both orders), forward, the joint-acceleration cost and
+ * ddp_hip_joint_accel.  The gravity torque g(q), the centre of mass and the centroidal momentum are those of the links and do
+ * not change (rotor momentum is not modelled).
+ * ddp_hip_set_armature waits for the context's stream and writes the values into the resident model: every launch after it
+ * sees them; it may be repeated at any time between other calls.  A context it was never called on, or called with zeros,
+ * computes bit for bit what it computed without the feature.  DDP_HIP_E_ARG: NULL, a non-finite or negative entry, a non-zero
+ * entry in a free-flyer root's rows; DDP_HIP_E_UNSUPPORTED: the pendulum model.  A refused call leaves the old values in force.
+ * ddp_hip_get_armature hands the values in force back (zeros after create). */
+int ddp_hip_set_armature(ddp_hip_ctx* ctx, const double* armature /* [nv] */);
+int ddp_hip_get_armature(ddp_hip_ctx* ctx, double* armature /* [nv] */);
+
 /* solve<primal_dual_affine_multipliers> (ddp.hpp:745-842) for every instance of the context, each with the reference's
  * per-problem semantics: an instance stops at its first optimum (result 1, `iterations` = the iteration that found it)
  * or after max_iterations (result 0), whatever its batch-mates do.  In: X / U the initial trajectory, X_NEW / U_NEW a
@@ -1053,6 +1069,9 @@ int ddp_hip_shard_broadcast(ddp_hip_comm* comm, ddp_hip_ctx* ctx, int64_t best_g
 typedef struct ddp_hip_model_handle ddp_hip_model_handle;
 int ddp_hip_model_create(const ddp_hip_model* model, int device, ddp_hip_model_handle** out);
 int ddp_hip_model_destroy(ddp_hip_model_handle* h);
+/* joint armature of the handle's model (ddp_hip_set_armature: the same values, checks and error codes): ddp_hip_model_aba and
+ * ddp_hip_model_aba_derivatives called after it use D_i + a_i / M + diag(a) */
+int ddp_hip_model_set_armature(ddp_hip_model_handle* h, const double* armature /* [nv] */);
 /* model_t::dynamics_aba, pinocchio_model.ipp:337-356 */
 int ddp_hip_model_aba(ddp_hip_model_handle* h, const double* q, const double* v, const double* tau, double* qdd);
 /* model_t::d_dynamics_aba, pinocchio_model.ipp:359-400: d qdd/dq, d qdd/dv, d qdd/dtau = M^-1, each nv x nv; with a free-flyer
