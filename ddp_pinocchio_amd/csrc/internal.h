@@ -73,6 +73,7 @@ struct DevSwitches {
   bool no_qcache = false;      // NO_QCACHE: no configuration caches
   bool qcache_dense = false;   // QCACHE_DENSE: the static stencil's q-cache keeps a whole block per stepped configuration (no base + deltas layout)
   bool vcache_dense = false;   // VCACHE_DENSE: the static stencil's v-cache keeps its 2 nv + 1 whole entries (no base + deltas layout)
+  bool first_scalar = false;   // FIRST_SCALAR: the static first order's u waves and the u diagonal as two kernels on the scalar path (no LDS staging, no fused launch)
   bool cfg_full_aba = false;   // CFG_FULL_ABA: the (q_i, q_j) points of the static stencil run the whole ABA (two kernels, two streams)
   bool ana_own_aba = false;    // ANA_OWN_ABA: the analytic pass forms its own accelerations
   bool ana_split = false;      // ANA_SPLIT: the three-kernel analytic path with its HBM workspaces

@@ -1787,6 +1787,10 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
   const bool second_stage = (stages & DDP_HIP_LIN_SECOND) && pl.second != LinSecond::None;
   const bool eq_stage = (stages & DDP_HIP_LIN_EQ) && pl.eq != LinEq::None;
   const bool m1_fused = pl.m1_fused && eq_stage;   // LIN_SECOND's mode-1 pass is issued by the LIN_EQ stage
+  // both orders of the static stencil in one call: the first order's u waves go on to the u diagonal of f_uu (lin_static.hip:
+  // lin_static_first_tau_fused_kernel), and the second order runs without its UDiagonal launch
+  const bool u_diag_fused = (stages & DDP_HIP_LIN_FIRST) && second_stage && pl.first == LinFirst::FdStatic &&
+                            pl.second == LinSecond::Mode2Static && !ctx->sw.first_scalar;
   if (stages & DDP_HIP_LIN_COST) {
     if (ctx->flags & DDP_HIP_FLAG_TRACKING_COST)
       hipLaunchKernelGGL(lin_track_cost_kernel, dim3((unsigned)(BT + d.batch)), dim3(64), 0, ctx->stream, p);
@@ -1864,7 +1868,7 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
       }
       case LinFirst::FdStatic: {
         build_caches();
-        const int rc_ = lin_static_launch(ctx, p, StaticLevel::FirstOrder);
+        const int rc_ = lin_static_launch(ctx, p, u_diag_fused ? StaticLevel::FirstOrderUDiag : StaticLevel::FirstOrder);
         if (rc_ != DDP_HIP_OK) return rc_;
         break;
       }
@@ -1882,12 +1886,13 @@ int run_linearize(ddp_hip_ctx* ctx, const LinParams& p, LinCall& call, uint32_t 
       case LinSecond::Mode2Static:
         build_caches();
         if (pl.forks) {   // the whole second order as one launch graph on the context's stream and the side stream
-          const int rc_ = lin_static_launch(ctx, p, StaticLevel::SecondOrder);
+          const int rc_ = lin_static_launch(ctx, p, u_diag_fused ? StaticLevel::SecondOrderAfterUDiag : StaticLevel::SecondOrder);
           if (rc_ != DDP_HIP_OK) return rc_;
           break;
         }
         // torque level ahead of the other two: its row kernel also forms the diagonal entries of the q and v directions
         for (StaticLevel level : {StaticLevel::UDiagonal, StaticLevel::Torque, StaticLevel::Velocity, StaticLevel::Configuration}) {
+          if (level == StaticLevel::UDiagonal && u_diag_fused) continue;
           const int rc_ = lin_static_launch(ctx, p, level);
           if (rc_ != DDP_HIP_OK) return rc_;
         }

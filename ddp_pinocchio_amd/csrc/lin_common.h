@@ -54,6 +54,8 @@ enum class StaticLevel {
   Velocity,        // mode 2: velocity-level stencil points
   Configuration,   // mode 2: (q_i, q_j) stencil points
   SecondOrder,     // mode 2, concurrent schedule (LinPlan::forks): UDiagonal, Torque, Velocity and Configuration as one launch graph
+  FirstOrderUDiag, // FirstOrder whose u waves also leave the u diagonal of f_uu (a call that runs both orders of a mode-2 context)
+  SecondOrderAfterUDiag,   // SecondOrder behind FirstOrderUDiag: without UDiagonal
   AccelX,          // mode 1: accelerations at x + sqrt(eps_mach) e_k into p.accel_out (builds the base caches itself)
   AccelXU,         // ... and at u + sqrt(eps_mach) e_k
 };

@@ -22,6 +22,7 @@ DevSwitches read_switches() {
   sw.no_qcache = on("DDP_HIP_NO_QCACHE");
   sw.qcache_dense = on("DDP_HIP_QCACHE_DENSE");
   sw.vcache_dense = on("DDP_HIP_VCACHE_DENSE");
+  sw.first_scalar = on("DDP_HIP_FIRST_SCALAR");
   sw.cfg_full_aba = on("DDP_HIP_CFG_FULL_ABA");
   sw.ana_own_aba = on("DDP_HIP_ANA_OWN_ABA");
   sw.ana_split = on("DDP_HIP_ANA_SPLIT");

@@ -8,8 +8,8 @@
 // evaluation lives in registers.  One wave = 64 stencil points that share their configuration q (and, at the
 // torque level, their velocity): what the articulated-body algorithm derives from q (and v) alone is read from the
 // q- / v-caches -- wave-uniform blocks, copied into LDS with every load in flight and read as broadcasts by the row and
-// pair kernels of the velocity and torque levels, walked through the scalar path by the first-order kernels -- and each
-// lane only carries what its own perturbation changes.  The arithmetic is the operation sequence of
+// pair kernels of the velocity and torque levels and by the first order's u waves, walked through the scalar path by
+// the first order's q and v waves -- and each lane only carries what its own perturbation changes.  The arithmetic is the operation sequence of
 // rbd::aba_u_cached / rbd::aba_vu_cached.
 #include <float.h>
 #include <math.h>
@@ -1743,6 +1743,169 @@ __global__ __launch_bounds__(LBS) void lin_static_first_kernel(LinParams p, cons
                          DIAG && kp->pack != 0);
 }
 
+// ---- first order along u, and the u diagonal, on LDS-staged operands ----------------------------------------------------------
+// The same evaluations as lin_static_first_kernel<T, 3, *> (one wave per (instance, t), lane d perturbs u_d), with the operand
+// path of the tau rows: E | r | U | 1/D of the base block and v-cache entry 0 are copied into LDS with every load in flight, and
+// the evaluators read broadcasts from there instead of one dependent scalar-load round trip per joint stage.  The operation
+// sequence of an evaluation is the scalar-path kernel's (tau_up / tau_down): the outputs are equal bit for bit
+// (tests/test_first_staged.py).  The staged operands and the buffer the output stage reads the accelerations from share one LDS
+// region, a barrier apart, which keeps a wave at 12 KB of LDS and the kernels at three waves per SIMD.
+// (The v directions stay on lin_static_first_kernel<T, 2, false>: staged like the velocity rows the kernel was no faster -- DESIGN.md
+// section 6b.)
+
+// one torque-level evaluation of the wave's nv points (lane d: u_d + eps) on the two-phase staging of the tau rows; the joint
+// accelerations are left in s.uu
+template <class T>
+__device__ __forceinline__ void first_tau_eval(const DevModel& m, const double* __restrict__ qc0, const double* __restrict__ vc,
+                                               const double* __restrict__ ug, int lane, double eps, double* s_P, TauState<T>& s) {
+  constexpr int nv = T::N;
+  double* s_V = s_P + nv * PS;
+  constexpr int KH = stage_split<T>();
+  StageRegs<nv, 0, (KH > 0) ? KH : 1> lower;       // joints 0 .. KH-1: in flight through the first half of the leaf -> root pass
+  {
+    StageRegs<nv, KH, nv> upper;
+    upper.load(qc0, vc, lane); lower.load(qc0, vc, lane);
+    upper.park(s_P, s_V, lane);
+    rbd::coop_sync<true>();                         // one wave per workgroup: LDS is in order
+  }
+  auto tau = [&](int k) { double v = ug[k]; if (k == lane) v = v + eps; return v; };
+  static_assert(parents_at_least<T>(KH + 1, KH), "the first half of the pass must not reach below record KH");
+  tau_up_range<T, PS, nv - 1>(m, s_P, s_V, tau, s, std::make_integer_sequence<int, nv - 1 - KH>{});
+  lower.park(s_P, s_V, lane);
+  rbd::coop_sync<true>();
+  tau_up_range<T, PS, KH>(m, s_P, s_V, tau, s, std::make_integer_sequence<int, KH + 1>{});
+  tau_down_all<T, PS>(m, s_P, s_V, s, std::make_integer_sequence<int, nv>{});
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// DIAG false: the u columns (f_u, or the accelerations with accel_out set); true: the diagonal columns (u_d, u_d) of f_uu from
+// the resident f_u (StaticLevel::UDiagonal)
+template <class T, bool DIAG>
+__global__ __launch_bounds__(LBS, 3) void lin_static_first_tau_kernel(LinParams p) {
+  constexpr int nv = T::N, n = 2 * nv;
+  const int64_t bt = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int64_t Tn = p.d.T;
+  const int b = (int)(bt / Tn);
+  const int64_t t = bt % Tn;
+  const DevModel& m = *p.model;
+  const double* __restrict__ qc0 = p.qcache + bt * p.qc_bt;      // the base block: first in either layout
+  const double* __restrict__ vc = p.vcache + bt * p.vc_bt;       // entry 0
+  const double* __restrict__ xg = p.x + ((int64_t)b * (Tn + 1) + t) * n;
+  const double* __restrict__ ug = p.u + ((int64_t)b * Tn + t) * nv;
+  __shared__ union FirstTauLds { double P[nv * PS + nv * rbd::VC_STRIDE]; double q[(nv + 1) * (nv + 1)]; } s_lds;
+  const double eps = DIAG ? sqrt(sqrt(DBL_EPSILON)) : sqrt(DBL_EPSILON);
+  TauState<T> s;
+  first_tau_eval<T>(m, qc0, vc, ug, lane, eps, s_lds.P, s);
+  const kernarg_t kp = kernarg_params();
+  __syncthreads();                         // every lane is done with the staged operands
+  double* uq = s_lds.q + (lane < nv ? lane : nv) * (nv + 1);     // idle lanes share the spare row
+#pragma unroll
+  for (int k = 0; k < nv; ++k) uq[k] = s.uu[k];
+  __syncthreads();
+  if constexpr (!DIAG) {
+    if (double* ao = kp->accel_out) {             // (lin_static_first_kernel: the u directions' block)
+      double* al = ao + bt * (3 * nv + 1) * nv + 2 * nv * nv;
+      for (int e = lane; e < nv * nv; e += LBS) { const int c = e / nv; al[e] = s_lds.q[c * (nv + 1) + (e - c * nv)]; }
+      return;
+    }
+    double* fcol = kp->fu + bt * n * nv;
+    first_output<nv, false>(s_lds.q, lane, n, fcol, n, fcol, kp->f_val + bt * n, xg, m.dt, eps);
+  } else {
+    // column (d, d) of f_uu at d (cs + n m): records (LinParams::pack) or contract columns
+    const int64_t cs = kp->pack ? nv + 2 : n;
+    first_output<nv, true>(s_lds.q, lane, n, kp->fuu + bt * n * nv * nv, cs + (int64_t)n * nv, kp->fu + bt * n * nv, kp->f_val + bt * n, xg, m.dt,
+                           eps, kp->skip_top != 0, kp->pack != 0);
+  }
+}
+
+// f_u and the u diagonal of one (instance, t) from one staged image: a workgroup of two waves, wave 0 evaluating at
+// eps = sqrt(eps_mach), wave 1 at eps_mach^(1/4) -- the same instructions on a wave-uniform step.  Wave 0 then emits f_u; behind a
+// workgroup barrier wave 1 emits the diagonal columns of f_uu, subtracting eps * f_u as it reads it back from memory: the stored
+// value.  (Both evaluations in ONE wave would put the second behind the global stores of the first output stage: its reads of
+// the model are then no longer provably unclobbered, leave the scalar path, and the kernel spills -- 168 VGPRs and 168 B of
+// scratch per lane for the Talos-like tree in that form.)  Wave 1 keeps its accelerations in registers across wave 0's output
+// stage; its first store behind the evaluation is unconditional (into a row of its own that nobody reads), like every
+// evaluation's in this file.
+template <class T>
+__global__ __launch_bounds__(2 * LBS, 3) void lin_static_first_tau_fused_kernel(LinParams p) {
+  constexpr int nv = T::N, n = 2 * nv;
+  const int64_t bt = blockIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / LBS), lane = (int)threadIdx.x % LBS;
+  const int64_t Tn = p.d.T;
+  const int b = (int)(bt / Tn);
+  const int64_t t = bt % Tn;
+  const DevModel& m = *p.model;
+  const double* __restrict__ qc0 = p.qcache + bt * p.qc_bt;      // the base block: first in either layout
+  const double* __restrict__ vc = p.vcache + bt * p.vc_bt;       // entry 0
+  const double* __restrict__ xg = p.x + ((int64_t)b * (Tn + 1) + t) * n;
+  const double* __restrict__ ug = p.u + ((int64_t)b * Tn + t) * nv;
+  struct Out { double q[(nv + 1) * (nv + 1)]; double park[nv + 1]; };
+  __shared__ union FirstTauFusedLds { double P[nv * PS + nv * rbd::VC_STRIDE]; Out o; } s_lds;
+  double* s_P = s_lds.P;
+  double* s_V = s_P + nv * PS;
+  const double eps1 = sqrt(DBL_EPSILON), eps2 = sqrt(sqrt(DBL_EPSILON));
+  const double eps = wave ? eps2 : eps1;
+  {
+    // E | r | U | 1/D of the base block and v-cache entry 0, copied by the two waves together, every load ahead of the first LDS store
+    constexpr int NPW = nv * 19, NVW = nv * rbd::VC_STRIDE, NT = 2 * LBS;
+    constexpr int CP = (NPW + NT - 1) / NT, CV = (NVW + NT - 1) / NT;
+    const int tid = (int)threadIdx.x;
+    double rp[CP], rv[CV];
+#pragma unroll
+    for (int c = 0; c < CP; ++c) {
+      int idx = c * NT + tid;
+      idx = idx < NPW ? idx : NPW - 1;
+      rp[c] = qc0[(idx / 19) * rbd::QC_STRIDE + idx % 19];
+    }
+#pragma unroll
+    for (int c = 0; c < CV; ++c) {
+      int idx = c * NT + tid;
+      idx = idx < NVW ? idx : NVW - 1;
+      rv[c] = vc[idx];
+    }
+#pragma unroll
+    for (int c = 0; c < CP; ++c) {
+      int idx = c * NT + tid;
+      idx = idx < NPW ? idx : NPW - 1;
+      s_P[(idx / 19) * PS + idx % 19] = rp[c];
+    }
+#pragma unroll
+    for (int c = 0; c < CV; ++c) {
+      int idx = c * NT + tid;
+      idx = idx < NVW ? idx : NVW - 1;
+      s_V[idx] = rv[c];
+    }
+    __syncthreads();
+  }
+  TauState<T> s;
+  auto tau = [&](int k) { double v = ug[k]; if (k == lane) v = v + eps; return v; };
+  tau_up_all<T, PS>(m, s_P, s_V, tau, s, std::make_integer_sequence<int, nv>{});
+  tau_down_all<T, PS>(m, s_P, s_V, s, std::make_integer_sequence<int, nv>{});
+  __builtin_amdgcn_sched_barrier(0);
+  const kernarg_t kp = kernarg_params();
+  __syncthreads();                         // both waves are done with the staged operands
+  double* const own = s_lds.o.q + (lane < nv ? lane : nv) * (nv + 1);     // idle lanes share the spare row
+  double* const row = wave ? s_lds.o.park : own;
+#pragma unroll
+  for (int k = 0; k < nv; ++k) row[k] = s.uu[k];
+  rbd::coop_sync<true>();                  // q is wave 0's alone here
+  if (wave == 0) {
+    double* fcol = kp->fu + bt * n * nv;
+    first_output<nv, false>(s_lds.o.q, lane, n, fcol, n, fcol, kp->f_val + bt * n, xg, m.dt, eps1);
+  }
+  __syncthreads();                         // f_u is in memory for wave 1, and q has been read
+  if (wave == 1) {
+#pragma unroll
+    for (int k = 0; k < nv; ++k) own[k] = s.uu[k];
+    rbd::coop_sync<true>();
+    // column (d, d) of f_uu at d (cs + n m): records (LinParams::pack) or contract columns
+    const int64_t cs = kp->pack ? nv + 2 : n;
+    first_output<nv, true>(s_lds.o.q, lane, n, kp->fuu + bt * n * nv * nv, cs + (int64_t)n * nv, kp->fu + bt * n * nv, kp->f_val + bt * n, xg, m.dt,
+                           eps2, kp->skip_top != 0, kp->pack != 0);
+  }
+}
+
 // ---- q- and v-caches ------------------------------------------------------------------------------------------------
 // lin_static_qvcache_kernel: one wave per (instance, t), lane c = configuration c of the mode-2 stencil (0: q, 1+i:
 // q + eps e_i).  The chain-wise sweep of the configuration level, reduced to what the caches hold: rbd::aba_qpart
@@ -2037,9 +2200,18 @@ static void launch_vel_rows(const LinParams& p, int64_t BT, hipStream_t s) {
   else hipLaunchKernelGGL((lin_static_vel_kernel<T, true>), grid, dim3(LBS), 0, s, p);
 }
 
-// the first-order kernels along the q, v and (with_u) u directions: jacobian columns, or accelerations with p.accel_out set
+// the diagonal second-order entries of the u directions, from the resident f_u
 template <class T>
-static void launch_first_columns(ddp_hip_ctx* ctx, const LinParams& p, bool with_u) {
+static void launch_u_diagonal(ddp_hip_ctx* ctx, const LinParams& p) {
+  const int64_t BT = ctx->d.batch * ctx->d.T;
+  if (ctx->sw.first_scalar) hipLaunchKernelGGL((lin_static_first_kernel<T, 3, true>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
+  else hipLaunchKernelGGL((lin_static_first_tau_kernel<T, true>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p);
+}
+
+// the first-order kernels along the q, v and (with_u) u directions: jacobian columns, or accelerations with p.accel_out set;
+// u_diag: the u waves go on to the diagonal columns of f_uu (StaticLevel::FirstOrderUDiag, never with the scalar-path kernels)
+template <class T>
+static void launch_first_columns(ddp_hip_ctx* ctx, const LinParams& p, bool with_u, bool u_diag = false) {
   const int64_t BT = ctx->d.batch * ctx->d.T;
   constexpr int nv = T::N, TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS;
   const int64_t per = ctx->lin_qws_bt * GU;     // one wave per (instance, t) uses one of the GU workspace slots of a slice entry
@@ -2048,7 +2220,11 @@ static void launch_first_columns(ddp_hip_ctx* ctx, const LinParams& p, bool with
     hipLaunchKernelGGL((lin_static_first_kernel<T, 1, false>), dim3((unsigned)nb), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, bt0);
   }
   hipLaunchKernelGGL((lin_static_first_kernel<T, 2, false>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
-  if (with_u) hipLaunchKernelGGL((lin_static_first_kernel<T, 3, false>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
+  if (!with_u) return;
+  // (DDP_HIP_FIRST_SCALAR: the u waves walk the cache blocks through the scalar path)
+  if (ctx->sw.first_scalar) hipLaunchKernelGGL((lin_static_first_kernel<T, 3, false>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
+  else if (u_diag) hipLaunchKernelGGL((lin_static_first_tau_fused_kernel<T>), dim3((unsigned)BT), dim3(2 * LBS), 0, ctx->stream, p);
+  else hipLaunchKernelGGL((lin_static_first_tau_kernel<T, false>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p);
 }
 
 // the configuration level's slices on `s`: spine pre-pass, then the pair kernel on spliced operands, in slices of (instance, t)
@@ -2081,15 +2257,16 @@ static int launch_cfg_slices(ddp_hip_ctx* ctx, const LinParams& p, hipStream_t s
 // write disjoint columns in every layout.  The first spine pre-pass reads the caches alone and writes the workspace, which the
 // first order's q columns are done with at this point of the stream: it starts beside the u diagonal.  Each fork is taken only
 // with its LinFork bit; without it the kernels keep their place in the single-stream order.  The caller joins the side stream
-// (lin.hip: ahead of the bracket's end).
+// (lin.hip: ahead of the bracket's end).  u_diag_done: the first order's u waves have left the u diagonal already
+// (StaticLevel::FirstOrderUDiag); the spine pre-pass then starts beside the torque rows alone.
 template <class T>
-static int launch_second_order(ddp_hip_ctx* ctx, const LinParams& p) {
+static int launch_second_order(ddp_hip_ctx* ctx, const LinParams& p, bool u_diag_done) {
   const int64_t BT = ctx->d.batch * ctx->d.T;
   constexpr int nv = T::N, TRI = nv * (nv - 1) / 2, GU = (TRI + LBS - 1) / LBS;
   const bool fork_cfg = (ctx->plan.forks & LIN_FORK_CFG) != 0, spine_ahead = fork_cfg && (ctx->plan.forks & LIN_FORK_SPINE);
   hipStream_t s0 = ctx->stream;
   if (spine_ahead) HIP_TRY(lin_fork(ctx));
-  hipLaunchKernelGGL((lin_static_first_kernel<T, 3, true>), dim3((unsigned)BT), dim3(LBS), 0, s0, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
+  if (!u_diag_done) launch_u_diagonal<T>(ctx, p);
   launch_tau_rows<T>(p, BT, s0);
   if (fork_cfg) {
     if (spine_ahead) HIP_TRY(hipEventRecord(ctx->lin_ev_rows, s0));
@@ -2123,12 +2300,15 @@ static int lin_static_launch_t(ddp_hip_ctx* ctx, const LinParams& p, StaticLevel
     launch_first_columns<T>(ctx, p, level == StaticLevel::AccelXU);
   } else if (level == StaticLevel::FirstOrder) {
     launch_first_columns<T>(ctx, p, true);
-  } else if (level == StaticLevel::SecondOrder) {
-    { const int rc_ = launch_second_order<T>(ctx, p); if (rc_ != DDP_HIP_OK) return rc_; }
+  } else if (level == StaticLevel::FirstOrderUDiag) {
+    if (ctx->sw.first_scalar || !p.fuu) return DDP_HIP_E_ARG;   // (lin.hip asks for it on the staged kernels of a context with tensors alone)
+    launch_first_columns<T>(ctx, p, true, true);
+  } else if (level == StaticLevel::SecondOrder || level == StaticLevel::SecondOrderAfterUDiag) {
+    { const int rc_ = launch_second_order<T>(ctx, p, level == StaticLevel::SecondOrderAfterUDiag); if (rc_ != DDP_HIP_OK) return rc_; }
   } else if (level == StaticLevel::UDiagonal) {
     // diagonal second-order entries of the u directions; those of the q and v directions are formed by the torque-level
     // row kernel (Torque) on an otherwise idle lane, which therefore runs ahead of Velocity and Configuration
-    hipLaunchKernelGGL((lin_static_first_kernel<T, 3, true>), dim3((unsigned)BT), dim3(LBS), 0, ctx->stream, p, p.model, p.qcache, p.x, p.u, ctx->lin_qws, (int64_t)0);
+    launch_u_diagonal<T>(ctx, p);
   } else if (level == StaticLevel::Configuration && !ctx->sw.cfg_full_aba) {
     { const int rc_ = launch_cfg_slices<T>(ctx, p, ctx->stream, nullptr); if (rc_ != DDP_HIP_OK) return rc_; }
   } else if (level == StaticLevel::Configuration) {
